@@ -16,6 +16,12 @@ Extra    : "roofline" for the dominant kernel (k_pathtrace_persistent; launch ti
            bounded row-interleaved sample of the same workload, rank 0 at N = 1 only).
 Fields that cannot be measured from inside this process (PMC counters) are read from profiles/ and every such field
 carries its "source".
+Outputs  : `--dump-outputs DIR` writes what the last timed image computed, as rank 0 holds it after the gather, once the
+           timed steps are over: DIR/accum.npy, the float4 accumulation image (1080 x 1920 x 4 float32, the same as
+           readAccum()), and DIR/frame_sample.npy, the RGBA8 output of present() (captureFrame()) at a fixed sample of a
+           quarter of the pixels (seed 0, pixel order kept), as float32 (N x 4).  41 MB in all.  The scene and the frame
+           numbers are fixed, so two builds run with the same arguments can be compared output for output.  (present()
+           blends with the history of the frames presented before it, so the frame depends on --warmup + --steps.)
 """
 import argparse
 import json
@@ -58,7 +64,31 @@ def parse_args():
     ap.add_argument("--no-world-update", action="store_true", help="skip the World::update(t) block (host / GPU builder / device-resident)")
     ap.add_argument("--batch", type=int, default=32,
                     help="frames per batched dispatch (the recorder batches up to 50 compute() calls; 1 = one dispatch per frame)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the outputs of the last timed image as DIR/<name>.npy")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_SAMPLE_SEED = 0
+DUMP_MAX_BYTES = 64 * 10**6
+
+
+def dump_outputs(out_dir, accum, frame):
+    """Write the headline's outputs (see the module docstring) to out_dir."""
+    import numpy as np
+    px = frame.shape[0] * frame.shape[1]
+    pick = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(px, px // 4, replace=False))
+    arrays = {"accum": np.ascontiguousarray(accum, dtype=np.float32),
+              "frame_sample": frame.reshape(px, 4)[pick].astype(np.float32)}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit("bench.py: --dump-outputs would write %d bytes (limit %d)" % (total, DUMP_MAX_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def launch_ranks(args):
@@ -264,8 +294,9 @@ def main():
         dist.all_reduce(rsum, op=dist.ReduceOp.SUM)
         return float(tmax.item()), float(rsum.item())
 
-    def run_workload(scene, frames, depth, steps, warmup, batch, width=WIDTH, height=HEIGHT):
-        """Time `steps` images of one scene on all ranks; returns the renderer, the sharding and the measurements."""
+    def run_workload(scene, frames, depth, steps, warmup, batch, width=WIDTH, height=HEIGHT, capture=False):
+        """Time `steps` images of one scene on all ranks; returns the renderer, the sharding and the measurements.
+        capture: rank 0 also returns the last timed image's outputs (accumulation image, presented RGBA8 frame)."""
         bridge = pkg.WorldBridge()
         if scene == "viewer_diamond":
             bridge.loadScene("viewer", DIAMOND_OBJ)
@@ -309,6 +340,8 @@ def main():
         counts = r.getCounters()
         rays_local = counts["primary_rays"] + counts["extension_rays"] + counts["shadow_rays"]
         elapsed, rays_total = reduce_stats(elapsed, rays_local)
+        # read before the detailed pass below accumulates into the same buffers again
+        outputs = (shard.read_image(), r.captureFrame()["data"].copy()) if capture and rank == 0 else None
         # one extra untimed image with the detailed-counter kernel variant: algorithmic bytes of the path-trace stage
         # (the counts are deterministic, so they equal the timed launches')
         r.setCounting(True)
@@ -320,7 +353,7 @@ def main():
         return {"bridge": bridge, "renderer": r, "shard": shard, "elapsed": elapsed, "rays": rays_total,
                 "ktimes": ktimes, "kc": kc, "steps": steps, "collective_ms": coll_ms / coll_n if coll_n else None,
                 "unpack_ms": unpack_ms / unpack_n if unpack_n else None, "render_ms": render_ms,
-                "wire_bytes_per_rank": shard.wire_bytes_per_rank() if distributed else 0}
+                "wire_bytes_per_rank": shard.wire_bytes_per_rank() if distributed else 0, "outputs": outputs}
 
     def live_loop(scene, nframes, depth, width=WIDTH, height=HEIGHT, passes=3, lookahead=0):
         """The reference's live loop (src/main.ts:168-173): compute(frameCount); present() per displayed frame, one call per
@@ -504,7 +537,9 @@ def main():
         return res
 
     frames = list(range(1, SPP_TOTAL + 1))
-    head = run_workload(SCENE, frames, DEPTH, args.steps, args.warmup, args.batch)
+    head = run_workload(SCENE, frames, DEPTH, args.steps, args.warmup, args.batch, capture=bool(args.dump_outputs))
+    if head["outputs"] is not None:
+        dump_outputs(args.dump_outputs, *head["outputs"])
     extra = []
     if not args.no_extra_configs:
         for name, scene, nframes, depth, images, cw, ch in EXTRA_CONFIGS:
