@@ -6,7 +6,8 @@ the same arrays on the GPU at upload time): test infrastructure.  From the bridg
                                  {R.max, skipX};  L = X + 1, R = the node L's skip pointer names;
                                  word(C) = 0x80000000 | index of C's own record (C inner) or C's leaf word;
                                  skipX = index of the record whose RIGHT child follows X's subtree in pre-order, or
-                                 0xffffffff when that leaves the TLAS / the BLAS
+                                 0xffffffff when that leaves the TLAS / the BLAS.  A single-child inner node (L's skip
+                                 names X's successor) gets the empty R slot: box +inf..+inf, word 0 (NONE)
   troot      (8,) f32            {TLAS root.min, word(root)} {TLAS root.max, 0}
   inst_root  (n_inst, 8) f32     the same for the BLAS root of every instance
 """
@@ -14,6 +15,7 @@ import numpy as np
 
 INNER = 0x80000000
 END = 0xFFFFFFFF
+NONE = 0
 
 
 def build(tlas, blas, instances):
@@ -38,6 +40,10 @@ def build(tlas, blas, instances):
         r = roots[np.clip(np.searchsorted(roots, local, side="right") - 1, 0, len(roots) - 1)]
         start[n_tlas:] = n_tlas + r
         end[n_tlas:] = n_tlas + r + skip[n_tlas + r]
+        below = local < roots[0]                              # below every root: no instance reaches it, never walked
+        start[n_tlas:][below] = n_tlas + local[below]
+        end[n_tlas:][below] = n_tlas + local[below]
+    end = np.minimum(end, n)
     is_tlas = np.arange(n) < n_tlas
     target = np.where(is_tlas, skip, start + skip)           # absolute index of the node the skip pointer names
     inner = data == 0
@@ -45,18 +51,20 @@ def build(tlas, blas, instances):
     ids = np.nonzero(inner)[0]
     left = ids + 1
     right = target[np.minimum(left, n - 1)]
-    ok = (left < n) & (right < n) & (right > left)            # nodes no instance reaches may hold anything: kept in range
+    single = (left < end[ids]) & (right == target[ids])       # L's subtree ends where X's does: no second child
+    ok = (left < end[ids]) & (single | ((right < end[ids]) & (right > left)))   # nodes no instance reaches: kept in range
+    both = ok & ~single
     left = np.where(ok, left, 0)
-    right = np.where(ok, right, 0)
+    right = np.where(both, right, 0)
     parent = np.full(n, -1, np.int64)
     parent[left[ok]] = ids[ok]
-    parent[right[ok]] = ids[ok]
+    parent[right[both]] = ids[ok & ~single]
 
     def word(c):
         return np.where(inner[c], INNER | pair_of[c], data[c]).astype(np.uint32)
 
     succ = target[ids]
-    off_level = (succ >= end[ids]) | (succ >= n)
+    off_level = (succ >= end[ids]) | (succ >= n) | ~ok
     sp = parent[np.minimum(succ, n - 1)]
     skipx = np.where(off_level | (sp < 0), END, pair_of[np.maximum(sp, 0)]).astype(np.uint32)
     pairs = np.zeros((len(ids), 16), np.float32)
@@ -67,6 +75,10 @@ def build(tlas, blas, instances):
     pairs[:, 8:11] = nodes[right, 0:3]
     pu[:, 11] = word(right)
     pairs[:, 12:15] = nodes[right, 4:7]
+    single = ok & single
+    pairs[single, 8:11] = np.inf
+    pu[single, 11] = NONE
+    pairs[single, 12:15] = np.inf
     pu[:, 15] = skipx
 
     def root_rec(i):

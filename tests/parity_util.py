@@ -95,3 +95,61 @@ def assert_parity(gpu, cpu, check_output=True, check_counters=True):
     assert np.array_equal(gpu.readUniforms(), cpu.readUniforms()), "uniform block differs"
     if check_counters:
         assert gpu.getCounters() == cpu.getCounters()
+
+
+def check_traversal_nodes(r, b):
+    """tnodes (csrc/k_treelet.hip.h) of the scene `b` uploaded to renderer `r`: a permutation of the bridge's nodes with
+    both successors explicit.  Following them from the roots must walk every BLAS and the TLAS in the ORIGINAL pre-order,
+    with the original boxes and leaf words.  Returns the array read back."""
+    import ctypes
+    tl, bl = np.asarray(b.tlas, np.float32).reshape(-1, 8), np.asarray(b.blas, np.float32).reshape(-1, 8)
+    nodes = np.concatenate([tl, bl])
+    n, n_tlas = len(nodes), len(tl)
+    inst = np.asarray(b.instances, np.float32).reshape(-1, 36).view(np.uint32)
+    tn = np.zeros((n, 8), np.float32)
+    new = np.zeros(n, np.uint32)
+    roots = np.zeros(len(inst), np.uint32)
+    vp = ctypes.c_void_p
+    got = r.L.rt_debug_read_traversal_nodes(r.ctx, tn.ctypes.data_as(vp), new.ctypes.data_as(vp), roots.ctypes.data_as(vp), n)
+    assert got == n
+    assert sorted(new.tolist()) == list(range(n)) and new[0] == 0           # a permutation; the TLAS root stays node 0
+    u, tu = nodes.view(np.uint32), tn.view(np.uint32)
+    END, INNER = 0xffffffff, 0x80000000
+    # boxes travel with their node; leaves keep their word; inner nodes point at their first child, skips at the original target
+    assert np.array_equal(tu[new][:, [0, 1, 2, 4, 5, 6]], u[:, [0, 1, 2, 4, 5, 6]])
+    leaf = u[:, 7] != 0
+    assert np.array_equal(tu[new[leaf], 7], u[leaf, 7])
+    inner = np.flatnonzero(~leaf)
+    reach = np.zeros(n, bool)           # nodes inside a TLAS / BLAS range that a walk can reach
+    reach[:int(u[0, 3])] = True
+    skip_target = np.full(n, -1, np.int64)
+    skip_target[:n_tlas] = np.where(u[:n_tlas, 3] < u[0, 3], u[:n_tlas, 3].astype(np.int64), -1)
+    for off in sorted(set(inst[:, 32].tolist())):
+        root = n_tlas + off
+        end = root + int(u[root, 3])
+        reach[root:end] = True
+        tgt = root + u[root:end, 3].astype(np.int64)
+        skip_target[root:end] = np.where(tgt < end, tgt, -1)
+    ri = inner[reach[inner]]
+    assert np.array_equal(tu[new[ri], 7], INNER | new[ri + 1])
+    rr = np.flatnonzero(reach)
+    expect = np.where(skip_target[rr] >= 0, new[np.maximum(skip_target[rr], 0)], END).astype(np.uint32)
+    assert np.array_equal(tu[new[rr], 3], expect)
+    assert np.array_equal(roots, new[n_tlas + inst[:, 32]])
+    return tn
+
+
+def check_pair_records(r, b):
+    """The child-pair records the trace kernels walk (csrc/k_pairs.hip.h, built on the GPU at upload) for the scene `b`
+    uploaded to renderer `r`, against tests/pair_layout.py, byte for byte."""
+    import ctypes
+    import pair_layout
+    pairs, troot, inst_root = pair_layout.build(b.tlas, b.blas, b.instances)
+    got_pairs = np.zeros((len(pairs) + 1, 16), np.float32)
+    got_roots = np.zeros((len(inst_root) + 1, 8), np.float32)
+    vp = ctypes.c_void_p
+    n = r.L.rt_debug_read_pairs(r.ctx, got_pairs.ctypes.data_as(vp), got_roots.ctypes.data_as(vp), len(got_pairs))
+    assert n == len(pairs)
+    assert np.array_equal(got_pairs[:n].view(np.uint32), pairs.view(np.uint32))
+    assert np.array_equal(got_roots[:-1].view(np.uint32), inst_root.view(np.uint32))
+    assert np.array_equal(got_roots[-1].view(np.uint32), troot.view(np.uint32))

@@ -22,7 +22,9 @@ def model_lib():
     deps = [SRC, os.path.join(REPO, "webgpu-raytracer_amd", "csrc", "k_pairwalk.hip.h"), os.path.join(REPO, "include", "mi355rt_math.h")]
     if not os.path.exists(LIB) or any(os.path.getmtime(d) > os.path.getmtime(LIB) for d in deps):
         os.makedirs(os.path.dirname(LIB), exist_ok=True)
-        subprocess.run(["g++", "-O2", "-ffp-contract=off", "-std=c++17", "-shared", "-fPIC", "-o", LIB, SRC], check=True)
+        tmp = "%s.%d.so" % (LIB[:-3], os.getpid())   # parallel test processes: each builds its own, the rename is atomic
+        subprocess.run(["g++", "-O2", "-ffp-contract=off", "-std=c++17", "-shared", "-fPIC", "-o", tmp, SRC], check=True)
+        os.replace(tmp, LIB)
     L = ctypes.CDLL(LIB)
     vp = ctypes.c_void_p
     L.pwm_trace.argtypes = [vp, vp, vp, vp, vp, vp, ctypes.c_uint32, ctypes.c_int, ctypes.c_uint32, ctypes.c_int, vp, vp, vp]

@@ -11,6 +11,11 @@
 //              (C inner) or C's own leaf word (BLAS: first << 3 | count; TLAS: instance << 3 | 1).  skipX = record whose
 //              RIGHT child follows X's subtree in pre-order, RT_REF_END when that leaves the TLAS / the BLAS: the
 //              stackless fall-back of the walk follows it.
+//              A SINGLE-CHILD inner node (L's skip names the same node as X's own: the reference walks X, then L's subtree,
+//              then X's successor) gets an empty R slot: the box {+inf}..{+inf}, which every ray misses whose bound is
+//              finite and whose direction has a component with a finite reciprocal (that axis puts both slab ends at the
+//              same +-inf), and the word RT_PAIR_NONE, which no node emits and by which the counting build knows not to
+//              count the slot (k_pairwalk.hip.h, pw_pair).  So the product build's step is unchanged.
 //   root_rec   2 x float4 per instance: {BLAS root.min, word(root)} {root.max, 0}, and one more for the TLAS root
 //              (record index n_instances): roots are tested from these, they have no parent pair.
 //
@@ -90,7 +95,9 @@ __global__ __launch_bounds__(1024) void k_pair_number(PairArgs A, const uint32_t
   A.pair_of[i] = work[RT_TREELET_WORK_HEAD + blockIdx.x] + before + rank;
   A.parent[i] = 0xffffffffu;
 }
-// children of inner node i (absolute indices), or false when the node is not a walkable inner node
+// children of inner node i (absolute indices; r = RT_PAIR_NO_CHILD for a single-child node), or false when the node is not
+// a walkable inner node
+#define RT_PAIR_NO_CHILD 0xffffffffu
 __device__ __forceinline__ bool pair_children(const PairArgs& A, uint32_t i, uint32_t& l, uint32_t& r) {
   uint32_t start, end, target;
   pair_level(A, i, start, end, target);
@@ -98,8 +105,8 @@ __device__ __forceinline__ bool pair_children(const PairArgs& A, uint32_t i, uin
   if (l >= end) return false;
   uint32_t ls, le, lt;
   pair_level(A, l, ls, le, lt);
-  r = lt;
-  return r > l && r < end;
+  r = lt == target ? RT_PAIR_NO_CHILD : lt;   // L's subtree ends where X's does: X has no second child
+  return r == RT_PAIR_NO_CHILD || (r > l && r < end);
 }
 __global__ __launch_bounds__(256) void k_pair_parent(PairArgs A) {
   const uint32_t i = blockIdx.x * 256u + threadIdx.x;
@@ -107,7 +114,7 @@ __global__ __launch_bounds__(256) void k_pair_parent(PairArgs A) {
   uint32_t l, r;
   if (!pair_children(A, i, l, r)) return;
   A.parent[l] = i;
-  A.parent[r] = i;
+  if (r != RT_PAIR_NO_CHILD) A.parent[r] = i;
 }
 __device__ __forceinline__ uint32_t pair_word(const PairArgs& A, uint32_t c) {
   const uint32_t data = __float_as_uint(A.nodes[2 * (size_t)c + 1].w);
@@ -126,12 +133,15 @@ __global__ __launch_bounds__(256) void k_pair_emit(PairArgs A) {
     const uint32_t p = A.parent[target];
     if (p != 0xffffffffu) skip_x = A.pair_of[p];
   }
+  const bool none = ok && r == RT_PAIR_NO_CHILD;
   const float4 llo = A.nodes[2 * (size_t)l], lhi = A.nodes[2 * (size_t)l + 1];
-  const float4 rlo = A.nodes[2 * (size_t)r], rhi = A.nodes[2 * (size_t)r + 1];
+  const float inf = __builtin_inff();
+  const float4 rlo = none ? make_float4(inf, inf, inf, 0.0f) : A.nodes[2 * (size_t)r];
+  const float4 rhi = none ? rlo : A.nodes[2 * (size_t)r + 1];
   float4* out = A.pairs + 4 * (size_t)A.pair_of[i];
   out[0] = make_float4(llo.x, llo.y, llo.z, __uint_as_float(pair_word(A, l)));
   out[1] = make_float4(lhi.x, lhi.y, lhi.z, 0.0f);
-  out[2] = make_float4(rlo.x, rlo.y, rlo.z, __uint_as_float(pair_word(A, r)));
+  out[2] = make_float4(rlo.x, rlo.y, rlo.z, __uint_as_float(none ? RT_PAIR_NONE : pair_word(A, r)));
   out[3] = make_float4(rhi.x, rhi.y, rhi.z, __uint_as_float(skip_x));
 }
 // root records: one per instance (its BLAS root), then the TLAS root at index n_inst

@@ -311,13 +311,16 @@ __device__ __forceinline__ bool pw_flush(const PairMem& M, const f4* lds, const 
     W.rays[2 * lane] = ra;
     W.rays[2 * lane + 1] = rb;
     W.res[lane] = ~0ull;
-    // four unconditional ordered stores, the highest slot first (trav_flush, k_traverse.hip.h, has the argument)
+    // four unconditional ordered stores, the highest slot first, and none at all from a lane at a count-0 leaf
+    // (trav_flush, k_traverse.hip.h, has the argument)
     const rt_lptr32_ordered it = (rt_lptr32_ordered)(W.items + excl);
     const uint32_t word = (lane << 26) | first;
-    it[3] = word + 3u;
-    it[2] = word + 2u;
-    it[1] = word + 1u;
-    it[0] = word;
+    if (cnt != 0u) {
+      it[3] = word + 3u;
+      it[2] = word + 2u;
+      it[1] = word + 1u;
+      it[0] = word;
+    }
   }
   // leaves of the reference's builder hold <= 4 triangles (blas.rs:99); only its fallback leaves hold 5-7
   if ((b2 & (b0 | b1)) != 0ull) {

@@ -36,6 +36,8 @@ namespace rtk {
 
 #define RT_PAIR_INNER 0x80000000u   // child word: inner node -> low bits = index of the child's own pair record
 #define RT_REF_END 0xffffffffu      // skip reference: the walk leaves the TLAS / the BLAS
+#define RT_PAIR_NONE 0u             // child word of the empty right slot of a single-child node (k_pairs.hip.h): inner words
+                                    // carry RT_PAIR_INNER and leaf words are non-zero, so no node has this word
 
 #define RT_PW_SENTINEL 0x7ffffff0u  // stack word pushed at instance entry: popping it leaves the instance (no leaf word
                                     // looks like it: triangle ids stay below 2^26, k_traverse.hip.h items)
@@ -165,12 +167,15 @@ RT_HD void pw_pair(PairLane& s, uint32_t self, float l0x, float l0y, float l0z, 
   bool hit_l = pw_box(l0x, l0y, l0z, l1x, l1y, l1z, s.r, t_min, s.closest, a_l);
   const bool hit_r = pw_box(r0x, r0y, r0z, r1x, r1y, r1z, s.r, t_min, s.closest, a_r);
   hit_l = hit_l && !only_r;
-  if (COUNT) n_nodes += (only_r ? 0u : 1u) + (hit_l ? 0u : 1u);   // L is reached now; R too when L is not entered
+  // a single-child node's empty R slot (k_pairs.hip.h) always misses: only the counting build needs to know it is there,
+  // so that it neither counts the slot nor pushes it for a count at the pop
+  const bool has_r = !COUNT || word_r != RT_PAIR_NONE;
+  if (COUNT) n_nodes += (only_r ? 0u : 1u) + ((hit_l || !has_r) ? 0u : 1u);   // L is reached now; R too when L is not entered
   const bool in_blas = pw_flag(s, PW_F_IN_BLAS);
   bool sl = pw_flag(s, in_blas ? PW_F_SL_BLAS : PW_F_SL_TLAS);
   // With L hit, R is reached after L's subtree.  It passes later iff it passes now AND a_r <= the closest of that moment:
   // tm_far = min(closest, far) only shrinks with closest, and a_r <= min(c_old, far) implies a_r <= far.
-  const bool want_push = hit_l && !sl && (hit_r || COUNT);
+  const bool want_push = hit_l && !sl && (hit_r || (COUNT && has_r));
   const bool overflow = want_push && s.sp >= K;
   const bool do_push = want_push && !overflow;
   if (do_push) stk.push(s.sp, word_r, hit_r ? a_r : rt_u2f(0x7fc00000u));   // NaN: counted when popped, never entered

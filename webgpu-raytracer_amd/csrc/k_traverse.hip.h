@@ -184,7 +184,9 @@ __device__ unsigned long long g_lane_stats[32];
 //   curr       the node to test next, or RT_CURR_END (the successor field of a node that ends its array), RT_CURR_ENTER (mixed
 //              mode: the lane hit a TLAS leaf and waits for its instance transform), RT_CURR_IDLE (the lane does not search:
 //              it waits for the triangles of a leaf, has finished, or never had a ray)
-//   leaf       0, or the leaf word (first triangle << 3 | count, count >= 1) of the BLAS leaf whose triangles the lane waits for
+//   leaf       0, or the leaf word (first triangle << 3 | count) of the BLAS leaf whose triangles the lane waits for.  A leaf
+//              word is non-zero (0 marks an inner node), but its count may be 0 when first > 0: such a lane waits, queues
+//              no item and goes on (trav_flush)
 //   resume     while waiting: the node to go on with
 //   tlas_next  RT_TLAS_NONE while the lane walks the TLAS; inside an instance the successor of the TLAS leaf (a node or
 //              RT_NODE_END)
@@ -469,15 +471,20 @@ __device__ __forceinline__ bool trav_flush(const TravMem& M, const f4* lds, cons
     // store to its slot j is a LATER instruction — the LDS executes a wave's instructions in order, so the valid word is the
     // one that stays.  (volatile: the compiler may neither reorder nor merge them.)  The last slot written this way is
     // excl + 3 <= 63 * 7 + 3: inside the 448-entry queue.  Conditional stores cost a compare, an exec save and a branch each.
+    // That argument needs cnt >= 1: a lane at a count-0 leaf (legal, the reference runs an empty loop) has the same excl as
+    // the next waiting lane and its slot-0 store would be the SAME instruction as that lane's — which of the two stays is
+    // not specified.  So such a lane stores nothing: one compare and exec mask per flush, nothing per node step.
     const rt_lptr32_ordered it = (rt_lptr32_ordered)(W.items + excl);
     const uint32_t word = (lane << 26) | first;
 #ifdef RT_EXP_COND_STORES
     for (uint32_t i = 0; i < 4u; i++) if (i < cnt) W.items[excl + i] = word + i;
 #else
-    it[3] = word + 3u;
-    it[2] = word + 2u;
-    it[1] = word + 1u;
-    it[0] = word;
+    if (cnt != 0u) {
+      it[3] = word + 3u;
+      it[2] = word + 2u;
+      it[1] = word + 1u;
+      it[0] = word;
+    }
 #endif
   }
   // leaves of the reference's builder hold <= 4 triangles (blas.rs:99); only its fallback leaves hold 5-7: those three
