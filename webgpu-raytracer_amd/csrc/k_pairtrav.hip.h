@@ -116,7 +116,7 @@ typedef __attribute__((address_space(3))) void* rt_lvptr;
 // VALU-bound on them; the same four loads as plain global_load_dwordx4 + four ds_write_b128 once they are back: 183.2
 // against 176.7 ms per 32-frame batch of the 263 k-triangle hall — an LDS-DMA load costs the wave ~175 cycles to issue, but
 // sixteen more live registers cost more).  The four regions (1 KB + 16 B of padding each, so that the read-back spreads over all banks) lie
-// over the wave's triangle work queue, which is only live inside pw_flush.
+// over the wave's triangle work queue, which is only live inside tri_flush.
 #define RT_PW_REGION_SLOTS 65u   // 16-byte slots per region
 __device__ __forceinline__ void pw_fetch_dma(const f4* gpairs, f4* wave_lds, unsigned long long need_mask, uint32_t idx) {
   const uint32_t c16 = (threadIdx.x & 3u) * 16u;
@@ -143,7 +143,6 @@ __device__ __forceinline__ void pw_fetch_wait() {
 __device__ __forceinline__ bool pw_can_step(const PairLane& s) {
   return s.state == PW_FETCH || s.state == PW_FETCHR || s.state == PW_POP;
 }
-__device__ __forceinline__ bool pw_busy(const PairLane& s) { return s.state != PW_DONE; }
 
 #ifndef RT_PW_ENTER_BATCH
 #define RT_PW_ENTER_BATCH 16u   // lanes that wait for an instance entry before the wave does it (deferred entry, as before)
@@ -282,95 +281,42 @@ __device__ __forceinline__ void pw_trip(const PairMem& M, const f4* lds, f4* wav
   }
 }
 
-// Flush the wave's triangle queue when it is due (the LDS work queue of k_traverse.hip.h, per-lane ray kind).  Returns
-// false when no lane has anything left to do.
-template <bool COUNT, bool LDS>
-__device__ __forceinline__ bool pw_flush(const PairMem& M, const f4* lds, const WaveWork& W, PairLane& s, uint32_t& n_tris) {
-  const uint32_t lane = threadIdx.x & 63u;
-  const bool waiting = s.state == PW_WAIT;
-  const unsigned long long wmask = __builtin_amdgcn_ballot_w64(waiting);
-  if (wmask == 0ull) return __builtin_amdgcn_ballot_w64(pw_busy(s)) != 0ull;
-  // due when RT_FLUSH_LANES lanes wait (k_traverse.hip.h), or nobody can produce more items without a flush
-  const unsigned long long pmask = __builtin_amdgcn_ballot_w64(pw_can_step(s) || s.state == PW_ENTER);
-  const uint32_t n_wait = pmask != 0ull ? (uint32_t)__builtin_popcountll(wmask) : 64u;
-  if (n_wait < RT_FLUSH_LANES) return true;
-  const uint32_t cnt = waiting ? (s.leaf & 7u) : 0u;
-  const unsigned long long b0 = __builtin_amdgcn_ballot_w64((cnt & 1u) != 0u), b1 = __builtin_amdgcn_ballot_w64((cnt & 2u) != 0u),
-                           b2 = __builtin_amdgcn_ballot_w64((cnt & 4u) != 0u);
-  const uint32_t total = (uint32_t)__builtin_popcountll(b0) + 2u * (uint32_t)__builtin_popcountll(b1) +
-                         4u * (uint32_t)__builtin_popcountll(b2);
-  const uint32_t excl =
-      __builtin_amdgcn_mbcnt_hi((uint32_t)(b0 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b0, 0u)) +
-      2u * __builtin_amdgcn_mbcnt_hi((uint32_t)(b1 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b1, 0u)) +
-      4u * __builtin_amdgcn_mbcnt_hi((uint32_t)(b2 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b2, 0u));
-  const uint32_t first = s.leaf >> 3;
-  if (waiting) {
+// The pair walk's flush hooks (tri_flush, k_traverse.hip.h).  The ray kind is per lane: a waiting lane posts its whole
+// instance-space ray with the any flag beside the origin and the bound at leaf entry beside the direction.
+template <bool COUNT_, bool LDS>
+struct PairWalk {
+  typedef PairLane Lane;
+  typedef PairMem Mem;
+  static constexpr bool COUNT = COUNT_, ALL_LDS = LDS, LEAF_CLEARED = false;   // leaf outlives the wait
+  static __device__ __forceinline__ bool waiting(const PairLane& s) { return s.state == PW_WAIT; }
+  static __device__ __forceinline__ bool producing(const PairLane& s) { return pw_can_step(s) || s.state == PW_ENTER; }
+  static __device__ __forceinline__ void post(const WaveWork& W, uint32_t lane, const PairLane& s) {
     f4 ra, rb;
     ra.x = rt_opaque(s.r.o.x); ra.y = rt_opaque(s.r.o.y); ra.z = rt_opaque(s.r.o.z); ra.w = rt_u2f(s.flags & PW_F_ANY);
     rb.x = rt_opaque(s.r.d.x); rb.y = rt_opaque(s.r.d.y); rb.z = rt_opaque(s.r.d.z); rb.w = s.closest;
     W.rays[2 * lane] = ra;
     W.rays[2 * lane + 1] = rb;
-    W.res[lane] = ~0ull;
-    // four unconditional ordered stores, the highest slot first, and none at all from a lane at a count-0 leaf
-    // (trav_flush, k_traverse.hip.h, has the argument)
-    const rt_lptr32_ordered it = (rt_lptr32_ordered)(W.items + excl);
-    const uint32_t word = (lane << 26) | first;
-    if (cnt != 0u) {
-      it[3] = word + 3u;
-      it[2] = word + 2u;
-      it[1] = word + 1u;
-      it[0] = word;
-    }
   }
-  // leaves of the reference's builder hold <= 4 triangles (blas.rs:99); only its fallback leaves hold 5-7
-  if ((b2 & (b0 | b1)) != 0ull) {
-    if (waiting) {
-      const rt_lptr32_ordered it = (rt_lptr32_ordered)(W.items + excl);
-      const uint32_t word = (lane << 26) | first;
-#pragma unroll
-      for (uint32_t i = 4; i < 7u; i++)
-        if (i < cnt) it[i] = word + i;
-    }
+  static __device__ __forceinline__ void owner_ray(const PairMem& M, const WaveWork& W, uint32_t owner, LocalRay& q, float& t_min,
+                                                   float& bound, bool& any) {
+    const f4 ra = W.rays[2 * owner], rb = W.rays[2 * owner + 1];
+    q.o = rt3_make(ra.x, ra.y, ra.z);
+    q.d = rt3_make(rb.x, rb.y, rb.z);
+    t_min = M.t_min;
+    bound = rb.w;
+    any = rt_f2u(ra.w) != 0u;
   }
-  __builtin_amdgcn_wave_barrier();
-  const bool tri_lds = LDS || M.l_tri != RT_LDS_NONE;   // wave-uniform
-  for (uint32_t c = 0; c < total; c += 64u) {
-    const uint32_t j = c + lane;
-    if (j < total) {
-      const uint32_t it = W.items[j];
-      const uint32_t owner = it >> 26, tri = it & 0x03ffffffu;
-      f4 ra = W.rays[2 * owner], rb = W.rays[2 * owner + 1];
-      LocalRay q;
-      q.o = rt3_make(ra.x, ra.y, ra.z);
-      q.d = rt3_make(rb.x, rb.y, rb.z);
-      f4 g0, g1, g2;
-      if (tri_lds) {
-        g0 = ld_l(lds, M.l_tri + (uint32_t)RT_TRI_STRIDE * tri);
-        g1 = ld_l(lds, M.l_tri + (uint32_t)RT_TRI_STRIDE * tri + 1u);
-        g2 = ld_l(lds, M.l_tri + (uint32_t)RT_TRI_STRIDE * tri + 2u);
-      } else {
-        g0 = ld_g(M.gtri, RT_TRI_STRIDE * (size_t)tri);
-        g1 = ld_g(M.gtri, RT_TRI_STRIDE * (size_t)tri + 1);
-        g2 = ld_g(M.gtri, RT_TRI_STRIDE * (size_t)tri + 2);
-      }
-      float t;
-      const bool ok = hit_tri_nb(g0, g1, g2, q, M.t_min, rb.w, t);
-      // the reference's leaf loop ends with the minimum over (t, position) of the tests that pass against the bound at
-      // leaf entry (k_traverse.hip.h); a shadow ray needs only the first accepted position
-      const bool any_ray = rt_f2u(ra.w) != 0u;
-      if (ok) atomicMin(&W.res[owner], any_ray ? (unsigned long long)tri : (((unsigned long long)rt_f2u(t) << 32) | tri));
-    }
+  static __device__ __forceinline__ bool any(const PairLane& s) { return pw_flag(s, PW_F_ANY); }
+  static __device__ __forceinline__ uint32_t tri_slot(const PairMem& M, uint32_t tri) {
+    return M.l_tri + (uint32_t)RT_TRI_STRIDE * tri;   // (as a 24-bit multiply the pair kernels compile differently)
   }
-  __builtin_amdgcn_wave_barrier();
-  if (waiting) {
-    const unsigned long long best = W.res[lane];
-    const bool found = best != ~0ull;
-    if (COUNT) n_tris += (pw_flag(s, PW_F_ANY) && found) ? ((uint32_t)best - first + 1u) : cnt;   // the any-hit loop stops at its first hit
+  static __device__ __forceinline__ void take(PairLane& s, bool found, unsigned long long best) {
     pw_after_leaf(s, found, rt_u2f((uint32_t)(best >> 32)), (uint32_t)best);
   }
-  __builtin_amdgcn_wave_barrier();
-  return true;
-}
+#ifdef RT_LANE_STATS
+  static __device__ __forceinline__ void lane_stat_chunk(const PairLane&, bool) {}
+#endif
+};
 
 // start a ray: the TLAS root comes from the kernel arguments (scalar registers)
 template <bool COUNT>

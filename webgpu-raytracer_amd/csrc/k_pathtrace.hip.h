@@ -208,7 +208,7 @@ __global__ __launch_bounds__(64) void k_pathtrace(DevScene S, DevFrame F, rt_sce
 // Per-path arithmetic and RNG draw order are exactly those of ray_color above (and of the oracle);
 // only the scheduling differs, which cannot change any pixel because paths are independent.
 
-// (the wave-level walk itself — TravMem, trav_step, trav_flush, traverse() — is in k_traverse.hip.h)
+// (the wave-level walk itself — TravMem, trav_step, tri_flush, traverse() — is in k_traverse.hip.h)
 
 struct PathState {
   uint32_t pixel, rng, depth, sample;
@@ -635,12 +635,6 @@ __global__ __launch_bounds__(256, LDS ? RT_PT_LDS_WAVES : RT_PT_GLOBAL_WAVES) vo
       if (ended) path_done = true;
     }
 
-#ifdef RT_EXP_NOSHADOW
-    want_shadow = false;  // timing experiment only
-#endif
-#ifdef RT_EXP_NOEXT
-    if (want_extend) { want_extend = false; path_done = true; }  // timing experiment only
-#endif
 #ifdef RT_PT_STAMPS
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     const unsigned long long ps2 = __builtin_amdgcn_s_memtime();

@@ -123,7 +123,7 @@ __device__ __forceinline__ bool hit_tri_nb(f4 g0, f4 g1, f4 g2, const LocalRay& 
 // Divergence control.  A lane is SEARCHING (walking nodes: slab tests, instance entry/exit) or
 // WAITING (it reached a BLAS leaf whose box it hits and has queued that leaf's triangles).  Every
 // trip lets all searching lanes take ONE node step (trav_step).  When enough triangle tests are queued
-// (RT_FLUSH_ITEMS) or nobody is searching any more, the wave flushes the queue (trav_flush):
+// (RT_FLUSH_ITEMS) or nobody is searching any more, the wave flushes the queue (tri_flush):
 //   * (lane, triangle) work items are compacted into LDS with a ballot/mbcnt prefix sum over the
 //     3-bit leaf counts, each owner also posts its instance-space ray;
 //   * the items are tested 64 at a time, one item per lane, whatever lane they came from — a leaf
@@ -186,7 +186,7 @@ __device__ unsigned long long g_lane_stats[32];
 //              it waits for the triangles of a leaf, has finished, or never had a ray)
 //   leaf       0, or the leaf word (first triangle << 3 | count) of the BLAS leaf whose triangles the lane waits for.  A leaf
 //              word is non-zero (0 marks an inner node), but its count may be 0 when first > 0: such a lane waits, queues
-//              no item and goes on (trav_flush)
+//              no item and goes on (tri_flush)
 //   resume     while waiting: the node to go on with
 //   tlas_next  RT_TLAS_NONE while the lane walks the TLAS; inside an instance the successor of the TLAS leaf (a node or
 //              RT_NODE_END)
@@ -423,26 +423,31 @@ __device__ __forceinline__ void trav_trip(const TravMem& M, const f4* lds, const
   }
 }
 
-// Flush the wave's triangle queue when it is due.  Returns false when no lane is searching or waiting any more
-// (the walk of every ray of the wave is over) — `idle_ok` callers (k_wf_trace) ignore that and refill instead.
+// Flush the wave's triangle queue when it is due: ONE copy for both walks (the node walk here, the pair walk of
+// k_pairtrav.hip.h).  WALK is a type with static hooks for what differs between them: the lane state (Lane), the record
+// locations (Mem), COUNT, ALL_LDS (every record is in LDS), LEAF_CLEARED (a lane's leaf word is 0 unless it waits), which
+// lanes wait / can still produce items, what a waiting lane posts to W.rays and how the tester reads it back, the LDS slot of
+// a triangle, the ray kind, and what a lane does with its leaf's result.  The hooks are written so that each walk compiles
+// to the instructions of its own former copy.
+// Returns false when no lane is searching or waiting any more (the walk of every ray of the wave is over) — the trace
+// kernels (k_wf_trace*) ignore that and refill instead.
 // Due: RT_FLUSH_LANES lanes wait at a leaf (a leaf of the reference's builder holds 1-4 triangles, 3.3 on average in Cornell:
-// the round-2 threshold of 24 queued tests, for a third of the instructions of the look), or nobody can step any more.
+// the round-2 threshold of 24 queued tests, for a third of the instructions of the look), or nobody can produce items any more.
 #ifndef RT_FLUSH_LANES
 #define RT_FLUSH_LANES 7u
 #endif
-template <bool ANY, bool COUNT, int MODE>
-__device__ __forceinline__ bool trav_flush(const TravMem& M, const f4* lds, const WaveWork& W, Trav& s, uint32_t& n_tris) {
+template <class WALK>
+__device__ __forceinline__ bool tri_flush(const typename WALK::Mem& M, const f4* lds, const WaveWork& W, typename WALK::Lane& s,
+                                          uint32_t& n_tris) {
   const uint32_t lane = threadIdx.x & 63u;
-  const bool waiting = trav_waiting(s);
+  const bool waiting = WALK::waiting(s);
   const unsigned long long wmask = __builtin_amdgcn_ballot_w64(waiting);
-  const unsigned long long smask = __builtin_amdgcn_ballot_w64(trav_searching(s));
-  if (wmask == 0ull) return smask != 0ull;
-  // (one scalar select and one scalar compare: as `few waiting && some searching` the compiler builds lane masks for both)
-  const uint32_t n_wait = smask != 0ull ? (uint32_t)__builtin_popcountll(wmask) : 64u;
-#ifndef RT_EXP_ITEMS24
+  const unsigned long long pmask = __builtin_amdgcn_ballot_w64(WALK::producing(s));
+  if (wmask == 0ull) return pmask != 0ull;
+  // (one scalar select and one scalar compare: as `few waiting && some producing` the compiler builds lane masks for both)
+  const uint32_t n_wait = pmask != 0ull ? (uint32_t)__builtin_popcountll(wmask) : 64u;
   if (n_wait < RT_FLUSH_LANES) return true;
-#endif
-  const uint32_t cnt = s.leaf & 7u;   // 0 for a lane that does not wait
+  const uint32_t cnt = (WALK::LEAF_CLEARED || waiting) ? (s.leaf & 7u) : 0u;   // 0 for a lane that does not wait
   const unsigned long long b0 = __builtin_amdgcn_ballot_w64((cnt & 1u) != 0u), b1 = __builtin_amdgcn_ballot_w64((cnt & 2u) != 0u),
                            b2 = __builtin_amdgcn_ballot_w64((cnt & 4u) != 0u);
   const uint32_t total = (uint32_t)__builtin_popcountll(b0) + 2u * (uint32_t)__builtin_popcountll(b1) +
@@ -451,20 +456,9 @@ __device__ __forceinline__ bool trav_flush(const TravMem& M, const f4* lds, cons
       __builtin_amdgcn_mbcnt_hi((uint32_t)(b0 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b0, 0u)) +
       2u * __builtin_amdgcn_mbcnt_hi((uint32_t)(b1 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b1, 0u)) +
       4u * __builtin_amdgcn_mbcnt_hi((uint32_t)(b2 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b2, 0u));
-#ifdef RT_EXP_ITEMS24
-  if (total < 24u && smask != 0ull) return true;
-#endif
   const uint32_t first = s.leaf >> 3;
   if (waiting) {
-    if (trav_post_at_entry<MODE>()) {
-      reinterpret_cast<float*>(W.rays)[8u * lane + 3u] = s.closest;   // the bound at leaf entry, beside the origin
-    } else {
-      f4 ra, rb;
-      ra.x = rt_opaque(s.io.x); ra.y = rt_opaque(s.io.y); ra.z = rt_opaque(s.io.z); ra.w = s.closest;
-      rb.x = rt_opaque(s.id.x); rb.y = rt_opaque(s.id.y); rb.z = rt_opaque(s.id.z); rb.w = 0.0f;
-      W.rays[2 * lane] = ra;
-      W.rays[2 * lane + 1] = rb;
-    }
+    WALK::post(W, lane, s);
     W.res[lane] = ~0ull;
     // Items (owner lane << 26 | triangle) of the lane's leaf at [excl, excl + cnt).  Four UNCONDITIONAL stores, the highest
     // slot first: a store past the lane's count lands on slot j < i of a later lane (excl' >= excl + cnt), and that lane's own
@@ -476,16 +470,12 @@ __device__ __forceinline__ bool trav_flush(const TravMem& M, const f4* lds, cons
     // not specified.  So such a lane stores nothing: one compare and exec mask per flush, nothing per node step.
     const rt_lptr32_ordered it = (rt_lptr32_ordered)(W.items + excl);
     const uint32_t word = (lane << 26) | first;
-#ifdef RT_EXP_COND_STORES
-    for (uint32_t i = 0; i < 4u; i++) if (i < cnt) W.items[excl + i] = word + i;
-#else
     if (cnt != 0u) {
       it[3] = word + 3u;
       it[2] = word + 2u;
       it[1] = word + 1u;
       it[0] = word;
     }
-#endif
   }
   // leaves of the reference's builder hold <= 4 triangles (blas.rs:99); only its fallback leaves hold 5-7: those three
   // stores sit behind a wave-uniform test (count bit 2 set together with bit 0 or bit 1) and come after the four above
@@ -499,23 +489,22 @@ __device__ __forceinline__ bool trav_flush(const TravMem& M, const f4* lds, cons
     }
   }
   __builtin_amdgcn_wave_barrier();
-  const bool tri_lds = MODE == RT_TRAV_LDS || M.l_tri != RT_LDS_NONE;   // wave-uniform
+  const bool tri_lds = WALK::ALL_LDS || M.l_tri != RT_LDS_NONE;   // wave-uniform
   for (uint32_t c = 0; c < total; c += 64u) {
     const uint32_t j = c + lane;
 #ifdef RT_LANE_STATS
-    RT_LSTAT(s.stat_kind + 1u, j < total);
+    WALK::lane_stat_chunk(s, j < total);
 #endif
     if (j < total) {
       const uint32_t it = W.items[j];
       const uint32_t owner = it >> 26, tri = it & 0x03ffffffu;
-      const f4 ra = W.rays[2 * owner];
-      const rt_f3_16 rb = *(const rt_f3_16 __attribute__((address_space(3)))*)(W.rays + 2 * owner + 1);   // 12 of the 16 bytes
       LocalRay q;
-      q.o = rt3_make(ra.x, ra.y, ra.z);
-      q.d = rt3_make(rb.x, rb.y, rb.z);
+      float t_min, bound;
+      bool any_ray;
+      WALK::owner_ray(M, W, owner, q, t_min, bound, any_ray);
       f4 g0, g1, g2;
       if (tri_lds) {
-        const uint32_t slot = M.l_tri + __umul24(tri, (uint32_t)RT_TRI_STRIDE);   // tri < 2^26 / 3 slots: a 24-bit multiply
+        const uint32_t slot = WALK::tri_slot(M, tri);
         g0 = ld_l(lds, slot);
         g1 = ld_l(lds, slot + 1u);
         g2 = ld_l(lds, slot + 2u);
@@ -525,19 +514,60 @@ __device__ __forceinline__ bool trav_flush(const TravMem& M, const f4* lds, cons
         g2 = ld_g(M.gtri, RT_TRI_STRIDE * (size_t)tri + 2);
       }
       float t;
-      const bool ok = hit_tri_nb(g0, g1, g2, q, RT_T_MIN, ra.w, t);
+      const bool ok = hit_tri_nb(g0, g1, g2, q, t_min, bound, t);
       // The reference's leaf loop (Raytracer.wgsl:474-482) accepts test i iff it passes and t_i < the running closest,
       // so it ends with the smallest accepted t and, among equal ones, the first in leaf order: a minimum over
       // (t, position), whatever the order of evaluation.  t > 0 here, so its bits order like the value; the triangle id
-      // grows with the position in the leaf.  ANY (shadow rays) needs only the first accepted position.
-      if (ok) atomicMin(&W.res[owner], ANY ? (unsigned long long)tri : (((unsigned long long)rt_f2u(t) << 32) | tri));
+      // grows with the position in the leaf.  An any-hit (shadow) ray needs only the first accepted position.
+      if (ok) atomicMin(&W.res[owner], any_ray ? (unsigned long long)tri : (((unsigned long long)rt_f2u(t) << 32) | tri));
     }
   }
   __builtin_amdgcn_wave_barrier();
   if (waiting) {
     const unsigned long long best = W.res[lane];
     const bool found = best != ~0ull;
-    if (COUNT) n_tris += (ANY && found) ? ((uint32_t)best - first + 1u) : cnt;   // the any-hit loop stops at its first hit
+    if (WALK::COUNT) n_tris += (WALK::any(s) && found) ? ((uint32_t)best - first + 1u) : cnt;   // the any-hit loop stops at its first hit
+    WALK::take(s, found, best);
+  }
+  __builtin_amdgcn_wave_barrier();
+  return true;
+}
+
+// The node walk's flush hooks.  A waiting lane posts the bound at leaf entry beside the instance-space origin that
+// trav_into_instance posted (or, RT_TRAV_MIXED_RAYREG, the whole ray); ANY is the kind of every ray of the walk.
+template <bool ANY_, bool COUNT_, int MODE>
+struct NodeWalk {
+  typedef Trav Lane;
+  typedef TravMem Mem;
+  static constexpr bool ANY = ANY_, COUNT = COUNT_, ALL_LDS = MODE == RT_TRAV_LDS, LEAF_CLEARED = true;   // leaf == 0 unless waiting
+  static __device__ __forceinline__ bool waiting(const Trav& s) { return trav_waiting(s); }
+  static __device__ __forceinline__ bool producing(const Trav& s) { return trav_searching(s); }
+  static __device__ __forceinline__ void post(const WaveWork& W, uint32_t lane, const Trav& s) {
+    if (trav_post_at_entry<MODE>()) {
+      reinterpret_cast<float*>(W.rays)[8u * lane + 3u] = s.closest;   // the bound at leaf entry, beside the origin
+    } else {
+      f4 ra, rb;
+      ra.x = rt_opaque(s.io.x); ra.y = rt_opaque(s.io.y); ra.z = rt_opaque(s.io.z); ra.w = s.closest;
+      rb.x = rt_opaque(s.id.x); rb.y = rt_opaque(s.id.y); rb.z = rt_opaque(s.id.z); rb.w = 0.0f;
+      W.rays[2 * lane] = ra;
+      W.rays[2 * lane + 1] = rb;
+    }
+  }
+  static __device__ __forceinline__ void owner_ray(const TravMem&, const WaveWork& W, uint32_t owner, LocalRay& q, float& t_min,
+                                                   float& bound, bool& any) {
+    const f4 ra = W.rays[2 * owner];
+    const rt_f3_16 rb = *(const rt_f3_16 __attribute__((address_space(3)))*)(W.rays + 2 * owner + 1);   // 12 of the 16 bytes
+    q.o = rt3_make(ra.x, ra.y, ra.z);
+    q.d = rt3_make(rb.x, rb.y, rb.z);
+    t_min = RT_T_MIN;
+    bound = ra.w;
+    any = ANY;
+  }
+  static __device__ __forceinline__ bool any(const Trav&) { return ANY; }
+  static __device__ __forceinline__ uint32_t tri_slot(const TravMem& M, uint32_t tri) {
+    return M.l_tri + __umul24(tri, (uint32_t)RT_TRI_STRIDE);   // tri < 2^26 / 3 slots: a 24-bit multiply
+  }
+  static __device__ __forceinline__ void take(Trav& s, bool found, unsigned long long best) {
     if (found) {
       s.best_tri = (int32_t)(uint32_t)best;
       if (!ANY) {
@@ -548,9 +578,10 @@ __device__ __forceinline__ bool trav_flush(const TravMem& M, const f4* lds, cons
     s.leaf = 0u;
     s.curr = (ANY && found) ? RT_CURR_IDLE : s.resume;
   }
-  __builtin_amdgcn_wave_barrier();
-  return true;
-}
+#ifdef RT_LANE_STATS
+  static __device__ __forceinline__ void lane_stat_chunk(const Trav& s, bool active) { RT_LSTAT(s.stat_kind + 1u, active); }
+#endif
+};
 
 // traverse(): the whole walk of one wave's rays (persistent kernel, one traversal per bounce and ray kind)
 template <bool ANY, bool COUNT, int MODE>
@@ -566,7 +597,7 @@ __device__ __forceinline__ void traverse(const TravMem& M, const f4* lds, const 
     // RT_STEPS_PER_TRIP node steps between two looks at the triangle queue: the look (ballots, population counts, the
     // branch) costs a third of a trip; a lane that reaches a leaf in an earlier step simply sits out the later ones
     trav_trip<COUNT, MODE, RT_STEPS_PER_TRIP>(M, lds, W, s, n_nodes);
-    if (!trav_flush<ANY, COUNT, MODE>(M, lds, W, s, n_tris)) break;
+    if (!tri_flush<NodeWalk<ANY, COUNT, MODE>>(M, lds, W, s, n_tris)) break;
   }
   out_t = s.closest;
   out_tri = s.best_tri;

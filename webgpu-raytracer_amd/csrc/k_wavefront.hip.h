@@ -14,7 +14,7 @@ namespace rtk {
 //                term, hit of the extension ray), surface frame + shade_bounce(); appends the shadow ray and the
 //                extension ray WITH their ray data to device queues (wave-aggregated atomics), finishes paths that end
 //   k_wf_trace   persistent waves, RAY-level regeneration: a lane that finishes its ray writes the result to the ray's
-//                queue slot and pulls the next ray of the queue (batched, >= RT_WF_REFILL lanes), so the slowest ray
+//                queue slot and pulls the next ray of the queue (batched, >= RT_WF_REFILL / RT_WF_PAIR_REFILL lanes), so the slowest ray
 //                no longer holds 63 lanes; same node step / LDS triangle queue as traverse().  Rays in, results out,
 //                both streamed by slot: the path records are never touched here.
 // Stages of one depth run as separate launches in stream order; the host enqueues all depths without reading anything
@@ -226,10 +226,13 @@ __global__ __launch_bounds__(256, RT_SHADE_WAVES) void k_wf_shade(DevScene S, De
 // Persistent ray tracer over a device queue: rays stream in by queue slot ({o, t_max} {d} written by k_wf_shade) and
 // results stream out by queue slot — ANY (shadow rays): one occlusion word; else (extension rays): {t, triangle,
 // instance} of the closest hit.  The path state is not touched here.  Ray-level regeneration: a lane whose ray is
-// finished writes its result and, when >= RT_WF_REFILL lanes are idle, the wave pulls the next rays of its chunk.
+// finished writes its result and, when >= REFILL lanes are idle, the wave pulls the next rays of its chunk.
 // BLOCK threads per workgroup (256 / 512 / 1024; 256 x 6 per CU by default): a bigger workgroup shares one staged copy of
 // the records among more waves at the price of fewer waves per SIMD (LdsPlan, rt_api.hip plan_lds; measured without gain,
 // DESIGN.md 4.1b).  LDS = true: every traversal record fits (RT_TRAV_LDS).
+// Two walks, one trace loop (wf_trace_loop): k_wf_trace over single nodes (k_traverse.hip.h, the multi-instance scenes) and
+// k_wf_trace_pairs over child-pair records (k_pairwalk.hip.h / k_pairtrav.hip.h, the single-instance scenes); rt_api.hip
+// rt_set_walk / MI355RT_WALK picks.
 #ifndef RT_WF_WAVES
 #define RT_WF_WAVES 5   // waves per SIMD of the trace kernels: what the per-wave LDS block (work queue + stack, 8.3 KB at K = 8) leaves room for
 #endif
@@ -245,13 +248,183 @@ __global__ __launch_bounds__(256, RT_SHADE_WAVES) void k_wf_shade(DevScene S, De
 // sections of the trace loop, summed over all waves of all launches: [ANY][0..2] = cycles in retire/pull, node step,
 // triangle flush; [3..5] = how often each section did work; [6] = waves; [7] = loop trips.  Nothing else reads it.
 __device__ unsigned long long g_trace_sections[2][8];
-// ---- walk over single nodes (rounds 1-2): kept behind rt_set_walk / MI355RT_WALK=node for A/B measurements
+// ---- walk over single nodes (rounds 1-2): the auto walk's choice for multi-instance scenes
 #ifndef RT_WF_NODE_WAVES
 #define RT_WF_NODE_WAVES 6
 #endif
 #ifndef RT_WF_NODE_STEPS_PER_TRIP
 #define RT_WF_NODE_STEPS_PER_TRIP 6
 #endif
+// ---- walk over child-pair records (round 3)
+#ifndef RT_WF_PAIR_REFILL
+#define RT_WF_PAIR_REFILL 16   // idle lanes that trigger a pull (swept 8 / 12 / 16 / 24 / 32 on the 263 k-triangle hall, ms per
+                               // 32-frame batch: 181.3 / 179.6 (one pop per round) / 181.6 / 187.0 / 226.9)
+#endif
+
+// What the trace loop needs of a walk beyond its flush hooks: start a ray, take the node steps of one trip, is the ray
+// still busy / did it find a hit, and the walk's refill threshold.  stepping() only feeds the RT_TRACE_STAMPS counters.
+template <bool ANY_, bool DETAIL, int MODE>
+struct WfNodeWalk : NodeWalk<ANY_, DETAIL, MODE> {
+  static constexpr uint32_t REFILL = RT_WF_REFILL;
+  static constexpr bool PW_STAMPS = false;
+  static __device__ __forceinline__ void begin(const TravMem&, Trav& s, bool active, uint32_t blas_base, rt3 o, rt3 d, float t_max,
+                                               uint32_t&) {
+    trav_begin(s, active, blas_base, o, d, t_max);
+  }
+  static __device__ __forceinline__ void trip(const TravMem& M, const f4* lds, const WaveWork& W, Trav& s, uint32_t& n_nodes,
+                                              unsigned long long*) {
+    trav_trip<DETAIL, MODE, RT_WF_NODE_STEPS_PER_TRIP>(M, lds, W, s, n_nodes);
+  }
+  static __device__ __forceinline__ bool busy(const Trav& s) { return trav_busy(s); }
+  static __device__ __forceinline__ bool occluded(const Trav& s) { return trav_any(s); }
+  static __device__ __forceinline__ bool stepping(const Trav& s) { return trav_searching(s); }
+};
+template <bool ANY_, bool DETAIL, bool LDS>
+struct WfPairWalk : PairWalk<DETAIL, LDS> {
+  static constexpr bool ANY = ANY_;
+  static constexpr uint32_t REFILL = RT_WF_PAIR_REFILL;
+  static constexpr bool PW_STAMPS = true;   // -DRT_PW_STAMPS (tools/exp/pw_sections.py): the sections of pw_trip
+  static __device__ __forceinline__ void begin(const PairMem& M, PairLane& s, bool active, uint32_t blas_base, rt3 o, rt3 d,
+                                               float t_max, uint32_t& n_nodes) {
+    pw_start<DETAIL>(M, s, active, ANY, blas_base, o, d, t_max, n_nodes);
+  }
+  // the fetch regions of pw_trip and the lane stacks lie in the wave's LDS block, which starts with its WaveWork
+  static __device__ __forceinline__ void trip(const PairMem& M, const f4* lds, const WaveWork& W, PairLane& s, uint32_t& n_nodes,
+                                              unsigned long long* pw_cyc) {
+    LdsStack stk = pw_stack_at(reinterpret_cast<char*>(W.rays));
+#ifdef RT_PW_STAMPS
+    pw_trip<DETAIL, LDS, RT_WF_STEPS_PER_TRIP>(M, lds, W.rays, stk, s, n_nodes, pw_cyc);
+#else
+    (void)pw_cyc;
+    pw_trip<DETAIL, LDS, RT_WF_STEPS_PER_TRIP>(M, lds, W.rays, stk, s, n_nodes);
+#endif
+  }
+  static __device__ __forceinline__ bool busy(const PairLane& s) { return s.state != PW_DONE; }
+  static __device__ __forceinline__ bool occluded(const PairLane& s) { return pw_flag(s, PW_F_FOUND); }
+  static __device__ __forceinline__ bool stepping(const PairLane& s) { return pw_can_step(s); }
+};
+
+// The body of both trace kernels after staging: pull rays off the queue, walk them, write their results, flush the counters.
+template <class WALK, int BLOCK>
+__device__ __forceinline__ void wf_trace_loop(const typename WALK::Mem& M, const f4* lds, const WaveWork& W, const DevFrame& F,
+                                              const rt_scene_uniforms& U, const WfQueues& Q, uint32_t depth) {
+  constexpr bool ANY = WALK::ANY;
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t blas_base = U.blas_base_idx;
+  uint32_t* cnt = Q.counters + 8u * depth;
+  const uint32_t n_rays = ANY ? cnt[1] : cnt[2];
+  uint32_t* head = ANY ? &cnt[3] : &cnt[4];
+  const uint32_t* ids = ANY ? Q.shadow_ids : Q.ext_ids;
+  const float4* rays = ANY ? Q.shadow_rays : Q.ext_rays[depth & 1u];
+
+  // per-lane ray + traversal state
+  bool have_ray = false;
+  uint32_t slot = 0u;
+  typename WALK::Lane s;
+  uint32_t n_nodes = 0, n_tris = 0, n_traced = 0;
+  WALK::begin(M, s, false, blas_base, rt3_splat(1.0f), rt3_splat(1.0f), 0.0f, n_nodes);
+  bool queue_left = true;
+  uint32_t chunk_pos = 0u, chunk_end = 0u;  // wave-uniform cursor into the chunk of the input queue this wave holds
+  unsigned long long pw_cyc[6] = {0, 0, 0, 0, 0, 0};   // -DRT_PW_STAMPS only (otherwise never read)
+
+#ifdef RT_TRACE_STAMPS
+  unsigned long long st_cyc[3] = {0, 0, 0}, st_cnt[3] = {0, 0, 0}, st_trips = 0;
+#endif
+  for (;;) {
+#ifdef RT_TRACE_STAMPS
+    const unsigned long long st0 = __builtin_amdgcn_s_memtime();
+    st_trips++;
+#endif
+    // ---- retire finished rays and pull new ones (batched: a block that runs for one lane costs as much as for 64)
+    const bool done = have_ray && !WALK::busy(s);
+    const bool idle = !have_ray || done;
+    const unsigned long long idle_m = __ballot(idle), done_m = __ballot(done);
+    const unsigned long long busy_m = __ballot(WALK::busy(s));
+    if (idle_m != 0ull &&
+        ((uint32_t)__builtin_popcountll(done_m) >= WALK::REFILL ||
+         (queue_left && (uint32_t)__builtin_popcountll(idle_m) >= WALK::REFILL) || busy_m == 0ull)) {
+#ifdef RT_TRACE_STAMPS
+      st_cnt[0]++;
+#endif
+      if (done) {
+        if (ANY)
+          Q.occluded[slot] = WALK::occluded(s) ? 1u : 0u;
+        else
+          Q.ext_hit[slot] = make_float4(s.closest, rt_u2f((uint32_t)s.best_tri), rt_u2f((uint32_t)s.best_inst), 0.0f);
+        have_ray = false;
+      }
+      // pull: needy lanes take consecutive entries of the wave's chunk; a new chunk costs one atomic
+      const bool need = !have_ray;
+      const unsigned long long need_m = __ballot(need);
+      if (queue_left && need_m != 0ull) {
+        if (chunk_pos >= chunk_end) {
+          uint32_t bq = 0;
+          if (lane == 0u) bq = atomicAdd(head, RT_WF_CHUNK);
+          bq = __shfl(bq, 0, 64);
+          if (bq >= n_rays) {
+            queue_left = false;
+          } else {
+            chunk_pos = bq;
+            chunk_end = bq + RT_WF_CHUNK < n_rays ? bq + RT_WF_CHUNK : n_rays;
+          }
+        }
+        if (queue_left) {
+          const uint32_t rank =
+              __builtin_amdgcn_mbcnt_hi((uint32_t)(need_m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)need_m, 0u));
+          const uint32_t qi = chunk_pos + rank;
+          chunk_pos += (uint32_t)__builtin_popcountll(need_m);
+          if (need && qi < chunk_end && ids[qi] != RT_WF_INVALID) {
+            const float4 r0 = rays[2 * qi], r1 = rays[2 * qi + 1];
+            slot = qi;
+            n_traced++;
+            have_ray = true;
+            WALK::begin(M, s, true, blas_base, xyz(r0), xyz(r1), ANY ? r0.w : RT_T_MAX, n_nodes);
+          }
+        }
+      }
+    }
+    if (!queue_left && __ballot(have_ray) == 0ull) break;  // queue exhausted and every ray retired
+
+#ifdef RT_TRACE_STAMPS
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    const unsigned long long st1 = __builtin_amdgcn_s_memtime();
+    st_cyc[0] += st1 - st0;
+    if (__ballot(WALK::stepping(s)) != 0ull) st_cnt[1]++;
+#endif
+    WALK::trip(M, lds, W, s, n_nodes, pw_cyc);
+#ifdef RT_TRACE_STAMPS
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    const unsigned long long st2 = __builtin_amdgcn_s_memtime();
+    st_cyc[1] += st2 - st1;
+    const bool was_waiting = __ballot(WALK::waiting(s)) != 0ull;
+#endif
+    tri_flush<WALK>(M, lds, W, s, n_tris);
+#ifdef RT_TRACE_STAMPS
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    st_cyc[2] += __builtin_amdgcn_s_memtime() - st2;
+    if (was_waiting && __ballot(WALK::waiting(s)) == 0ull) st_cnt[2]++;
+#endif
+  }
+#ifdef RT_TRACE_STAMPS
+  if (lane == 0u) {
+    for (int k = 0; k < 3; k++) {
+      atomicAdd(&g_trace_sections[ANY ? 1 : 0][k], st_cyc[k]);
+      atomicAdd(&g_trace_sections[ANY ? 1 : 0][3 + k], st_cnt[k]);
+    }
+    atomicAdd(&g_trace_sections[ANY ? 1 : 0][6], 1ull);
+    atomicAdd(&g_trace_sections[ANY ? 1 : 0][7], st_trips);
+  }
+#endif
+#ifdef RT_PW_STAMPS
+  if (WALK::PW_STAMPS && lane == 0u) {
+    for (int k = 0; k < 6; k++) atomicAdd(&g_trace_sections[ANY ? 1 : 0][k], pw_cyc[k]);
+    atomicAdd(&g_trace_sections[ANY ? 1 : 0][6], 1ull);
+  }
+#endif
+  LaneCounters c = {0, ANY ? 0u : n_traced, ANY ? n_traced : 0u, n_nodes, n_tris, 0};
+  flush_counters<WALK::COUNT>(c, F.counters, blockIdx.x * (BLOCK / 64) + (threadIdx.x >> 6));
+}
+
 // RAYREG (mixed mode only): the instance-space origin / direction stay in registers (RT_TRAV_MIXED_RAYREG, k_traverse.hip.h).
 template <bool ANY, bool DETAIL, bool LDS, int BLOCK, bool RAYREG = false>
 __global__ __launch_bounds__(BLOCK, BLOCK == 256 ? (LDS ? 4 : RT_WF_NODE_WAVES) : (BLOCK == 512 ? 2 : 4))
@@ -259,8 +432,7 @@ void k_wf_trace(DevScene Sg, DevFrame F, rt_scene_uniforms U, WfQueues Q, uint32
                 uint32_t n_tris_total, uint32_t n_inst_total, LdsPlan plan) {
   extern __shared__ f4 s_scene[];
   WaveWork W;
-  char* const wbase = reinterpret_cast<char*>(s_scene) + (threadIdx.x >> 6) * RT_WORK_BYTES_PER_WAVE;
-  wave_work_at(W, wbase);
+  wave_work_at(W, reinterpret_cast<char*>(s_scene) + (threadIdx.x >> 6) * RT_WORK_BYTES_PER_WAVE);
   const uint32_t rec0 = ((BLOCK / 64) * RT_WORK_BYTES_PER_WAVE) / 16;
   TravMem M;
   if (LDS) {
@@ -274,129 +446,16 @@ void k_wf_trace(DevScene Sg, DevFrame F, rt_scene_uniforms U, WfQueues Q, uint32
   }
   __syncthreads();
   constexpr int MODE = LDS ? RT_TRAV_LDS : (RAYREG ? RT_TRAV_MIXED_RAYREG : RT_TRAV_MIXED);
-  const uint32_t lane = threadIdx.x & 63u;
-  const uint32_t blas_base = U.blas_base_idx;
-  uint32_t* cnt = Q.counters + 8u * depth;
-  const uint32_t n_rays = ANY ? cnt[1] : cnt[2];
-  uint32_t* head = ANY ? &cnt[3] : &cnt[4];
-  const uint32_t* ids = ANY ? Q.shadow_ids : Q.ext_ids;
-  const float4* rays = ANY ? Q.shadow_rays : Q.ext_rays[depth & 1u];
-
-  // per-lane ray + traversal state
-  bool have_ray = false;
-  uint32_t slot = 0u;
-  Trav s;
-  trav_begin(s, false, blas_base, rt3_splat(1.0f), rt3_splat(1.0f), 0.0f);
-  bool queue_left = true;
-  uint32_t chunk_pos = 0u, chunk_end = 0u;  // wave-uniform cursor into the chunk of the input queue this wave holds
-  uint32_t n_nodes = 0, n_tris = 0, n_traced = 0;
-
-#ifdef RT_TRACE_STAMPS
-  unsigned long long st_cyc[3] = {0, 0, 0}, st_cnt[3] = {0, 0, 0}, st_trips = 0;
-#endif
-  for (;;) {
-#ifdef RT_TRACE_STAMPS
-    const unsigned long long st0 = __builtin_amdgcn_s_memtime();
-    st_trips++;
-#endif
-    // ---- retire finished rays and pull new ones (batched: a block that runs for one lane costs as much as for 64)
-    const bool done = have_ray && !trav_busy(s);
-    const bool idle = !have_ray || done;
-    const unsigned long long idle_m = __ballot(idle), done_m = __ballot(done);
-    const unsigned long long busy_m = __ballot(trav_busy(s));
-    if (idle_m != 0ull &&
-        ((uint32_t)__builtin_popcountll(done_m) >= RT_WF_REFILL ||
-         (queue_left && (uint32_t)__builtin_popcountll(idle_m) >= RT_WF_REFILL) || busy_m == 0ull)) {
-#ifdef RT_TRACE_STAMPS
-      st_cnt[0]++;
-#endif
-      if (done) {
-        if (ANY)
-          Q.occluded[slot] = trav_any(s) ? 1u : 0u;
-        else
-          Q.ext_hit[slot] = make_float4(s.closest, rt_u2f((uint32_t)s.best_tri), rt_u2f((uint32_t)s.best_inst), 0.0f);
-        have_ray = false;
-      }
-      // pull: needy lanes take consecutive entries of the wave's chunk; a new chunk costs one atomic
-      const bool need = !have_ray;
-      const unsigned long long need_m = __ballot(need);
-      if (queue_left && need_m != 0ull) {
-        if (chunk_pos >= chunk_end) {
-          uint32_t bq = 0;
-          if (lane == 0u) bq = atomicAdd(head, RT_WF_CHUNK);
-          bq = __shfl(bq, 0, 64);
-          if (bq >= n_rays) {
-            queue_left = false;
-          } else {
-            chunk_pos = bq;
-            chunk_end = bq + RT_WF_CHUNK < n_rays ? bq + RT_WF_CHUNK : n_rays;
-          }
-        }
-        if (queue_left) {
-          const uint32_t rank =
-              __builtin_amdgcn_mbcnt_hi((uint32_t)(need_m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)need_m, 0u));
-          const uint32_t qi = chunk_pos + rank;
-          chunk_pos += (uint32_t)__builtin_popcountll(need_m);
-          if (need && qi < chunk_end && ids[qi] != RT_WF_INVALID) {
-            const float4 r0 = rays[2 * qi], r1 = rays[2 * qi + 1];
-            slot = qi;
-            n_traced++;
-            have_ray = true;
-            trav_begin(s, true, blas_base, xyz(r0), xyz(r1), ANY ? r0.w : RT_T_MAX);
-          }
-        }
-      }
-    }
-    if (!queue_left && __ballot(have_ray) == 0ull) break;  // queue exhausted and every ray retired
-
-#ifdef RT_TRACE_STAMPS
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    const unsigned long long st1 = __builtin_amdgcn_s_memtime();
-    st_cyc[0] += st1 - st0;
-    if (__ballot(trav_searching(s)) != 0ull) st_cnt[1]++;
-#endif
-    trav_trip<DETAIL, MODE, RT_WF_NODE_STEPS_PER_TRIP>(M, s_scene, W, s, n_nodes);
-#ifdef RT_TRACE_STAMPS
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    const unsigned long long st2 = __builtin_amdgcn_s_memtime();
-    st_cyc[1] += st2 - st1;
-    const bool was_waiting = __ballot(trav_waiting(s)) != 0ull;
-#endif
-    trav_flush<ANY, DETAIL, MODE>(M, s_scene, W, s, n_tris);
-#ifdef RT_TRACE_STAMPS
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    st_cyc[2] += __builtin_amdgcn_s_memtime() - st2;
-    if (was_waiting && __ballot(trav_waiting(s)) == 0ull) st_cnt[2]++;
-#endif
-  }
-#ifdef RT_TRACE_STAMPS
-  if (lane == 0u) {
-    for (int k = 0; k < 3; k++) {
-      atomicAdd(&g_trace_sections[ANY ? 1 : 0][k], st_cyc[k]);
-      atomicAdd(&g_trace_sections[ANY ? 1 : 0][3 + k], st_cnt[k]);
-    }
-    atomicAdd(&g_trace_sections[ANY ? 1 : 0][6], 1ull);
-    atomicAdd(&g_trace_sections[ANY ? 1 : 0][7], st_trips);
-  }
-#endif
-  LaneCounters c = {0, ANY ? 0u : n_traced, ANY ? n_traced : 0u, n_nodes, n_tris, 0};
-  flush_counters<DETAIL>(c, F.counters, blockIdx.x * (BLOCK / 64) + (threadIdx.x >> 6));
+  wf_trace_loop<WfNodeWalk<ANY, DETAIL, MODE>, BLOCK>(M, s_scene, W, F, U, Q, depth);
 }
 
-// ---- walk over child-pair records (round 3, k_pairwalk.hip.h / k_pairtrav.hip.h)
-#ifndef RT_WF_PAIR_REFILL
-#define RT_WF_PAIR_REFILL 16   // idle lanes that trigger a pull (swept 8 / 12 / 16 / 24 / 32 on the 263 k-triangle hall, ms per
-                               // 32-frame batch: 181.3 / 179.6 (one pop per round) / 181.6 / 187.0 / 226.9)
-#endif
 template <bool ANY, bool DETAIL, bool LDS, int BLOCK>
 __global__ __launch_bounds__(BLOCK, BLOCK == 256 ? (LDS ? 4 : RT_WF_WAVES) : (BLOCK == 512 ? 2 : 4))
 void k_wf_trace_pairs(DevScene Sg, DevFrame F, rt_scene_uniforms U, WfQueues Q, uint32_t depth, uint32_t n_pairs_total,
                 uint32_t n_tris_total, uint32_t n_inst_total, PairPlan plan) {
   extern __shared__ f4 s_scene[];
   WaveWork W;
-  char* const wbase = reinterpret_cast<char*>(s_scene) + (threadIdx.x >> 6) * RT_PW_BYTES_PER_WAVE;
-  wave_work_at(W, wbase);
-  LdsStack stk = pw_stack_at(wbase);
+  wave_work_at(W, reinterpret_cast<char*>(s_scene) + (threadIdx.x >> 6) * RT_PW_BYTES_PER_WAVE);
   const uint32_t rec0 = ((BLOCK / 64) * RT_PW_BYTES_PER_WAVE) / 16;
   PairMem M;
   if (LDS) {
@@ -407,126 +466,7 @@ void k_wf_trace_pairs(DevScene Sg, DevFrame F, rt_scene_uniforms U, WfQueues Q, 
     pw_stage(M, s_scene, rec0, Sg, plan, n_pairs_total, n_tris_total, n_inst_total, RT_T_MIN);
   }
   __syncthreads();
-  const uint32_t lane = threadIdx.x & 63u;
-  const uint32_t blas_base = U.blas_base_idx;
-  uint32_t* cnt = Q.counters + 8u * depth;
-  const uint32_t n_rays = ANY ? cnt[1] : cnt[2];
-  uint32_t* head = ANY ? &cnt[3] : &cnt[4];
-  const uint32_t* ids = ANY ? Q.shadow_ids : Q.ext_ids;
-  const float4* rays = ANY ? Q.shadow_rays : Q.ext_rays[depth & 1u];
-
-  // per-lane ray + traversal state
-  bool have_ray = false;
-  uint32_t slot = 0u;
-  PairLane s;
-  uint32_t n_nodes = 0, n_tris = 0, n_traced = 0;
-  pw_start<false>(M, s, false, ANY, blas_base, rt3_splat(1.0f), rt3_splat(1.0f), 0.0f, n_nodes);
-  bool queue_left = true;
-  uint32_t chunk_pos = 0u, chunk_end = 0u;  // wave-uniform cursor into the chunk of the input queue this wave holds
-#ifdef RT_PW_STAMPS
-  unsigned long long pw_cyc[6] = {0, 0, 0, 0, 0, 0};
-#endif
-
-#ifdef RT_TRACE_STAMPS
-  unsigned long long st_cyc[3] = {0, 0, 0}, st_cnt[3] = {0, 0, 0}, st_trips = 0;
-#endif
-  for (;;) {
-#ifdef RT_TRACE_STAMPS
-    const unsigned long long st0 = __builtin_amdgcn_s_memtime();
-    st_trips++;
-#endif
-    // ---- retire finished rays and pull new ones (batched: a block that runs for one lane costs as much as for 64)
-    const bool done = have_ray && s.state == PW_DONE;
-    const bool idle = !have_ray || done;
-    const unsigned long long idle_m = __ballot(idle), done_m = __ballot(done);
-    const unsigned long long busy_m = __ballot(s.state != PW_DONE);
-    if (idle_m != 0ull &&
-        ((uint32_t)__builtin_popcountll(done_m) >= RT_WF_PAIR_REFILL ||
-         (queue_left && (uint32_t)__builtin_popcountll(idle_m) >= RT_WF_PAIR_REFILL) || busy_m == 0ull)) {
-#ifdef RT_TRACE_STAMPS
-      st_cnt[0]++;
-#endif
-      if (done) {
-        if (ANY)
-          Q.occluded[slot] = pw_flag(s, PW_F_FOUND) ? 1u : 0u;
-        else
-          Q.ext_hit[slot] = make_float4(s.closest, rt_u2f((uint32_t)s.best_tri), rt_u2f((uint32_t)s.best_inst), 0.0f);
-        have_ray = false;
-      }
-      // pull: needy lanes take consecutive entries of the wave's chunk; a new chunk costs one atomic
-      const bool need = !have_ray;
-      const unsigned long long need_m = __ballot(need);
-      if (queue_left && need_m != 0ull) {
-        if (chunk_pos >= chunk_end) {
-          uint32_t bq = 0;
-          if (lane == 0u) bq = atomicAdd(head, RT_WF_CHUNK);
-          bq = __shfl(bq, 0, 64);
-          if (bq >= n_rays) {
-            queue_left = false;
-          } else {
-            chunk_pos = bq;
-            chunk_end = bq + RT_WF_CHUNK < n_rays ? bq + RT_WF_CHUNK : n_rays;
-          }
-        }
-        if (queue_left) {
-          const uint32_t rank =
-              __builtin_amdgcn_mbcnt_hi((uint32_t)(need_m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)need_m, 0u));
-          const uint32_t qi = chunk_pos + rank;
-          chunk_pos += (uint32_t)__builtin_popcountll(need_m);
-          if (need && qi < chunk_end && ids[qi] != RT_WF_INVALID) {
-            const float4 r0 = rays[2 * qi], r1 = rays[2 * qi + 1];
-            slot = qi;
-            n_traced++;
-            have_ray = true;
-            pw_start<DETAIL>(M, s, true, ANY, blas_base, xyz(r0), xyz(r1), ANY ? r0.w : RT_T_MAX, n_nodes);
-          }
-        }
-      }
-    }
-    if (!queue_left && __ballot(have_ray) == 0ull) break;  // queue exhausted and every ray retired
-
-#ifdef RT_TRACE_STAMPS
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    const unsigned long long st1 = __builtin_amdgcn_s_memtime();
-    st_cyc[0] += st1 - st0;
-    if (__ballot(pw_can_step(s)) != 0ull) st_cnt[1]++;
-#endif
-#ifdef RT_PW_STAMPS
-    pw_trip<DETAIL, LDS, RT_WF_STEPS_PER_TRIP>(M, s_scene, reinterpret_cast<f4*>(wbase), stk, s, n_nodes, pw_cyc);
-#else
-    pw_trip<DETAIL, LDS, RT_WF_STEPS_PER_TRIP>(M, s_scene, reinterpret_cast<f4*>(wbase), stk, s, n_nodes);
-#endif
-#ifdef RT_TRACE_STAMPS
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    const unsigned long long st2 = __builtin_amdgcn_s_memtime();
-    st_cyc[1] += st2 - st1;
-    const bool was_waiting = __ballot(s.state == PW_WAIT) != 0ull;
-#endif
-    pw_flush<DETAIL, LDS>(M, s_scene, W, s, n_tris);
-#ifdef RT_TRACE_STAMPS
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    st_cyc[2] += __builtin_amdgcn_s_memtime() - st2;
-    if (was_waiting && __ballot(s.state == PW_WAIT) == 0ull) st_cnt[2]++;
-#endif
-  }
-#ifdef RT_TRACE_STAMPS
-  if (lane == 0u) {
-    for (int k = 0; k < 3; k++) {
-      atomicAdd(&g_trace_sections[ANY ? 1 : 0][k], st_cyc[k]);
-      atomicAdd(&g_trace_sections[ANY ? 1 : 0][3 + k], st_cnt[k]);
-    }
-    atomicAdd(&g_trace_sections[ANY ? 1 : 0][6], 1ull);
-    atomicAdd(&g_trace_sections[ANY ? 1 : 0][7], st_trips);
-  }
-#endif
-#ifdef RT_PW_STAMPS
-  if (lane == 0u) {
-    for (int k = 0; k < 6; k++) atomicAdd(&g_trace_sections[ANY ? 1 : 0][k], pw_cyc[k]);
-    atomicAdd(&g_trace_sections[ANY ? 1 : 0][6], 1ull);
-  }
-#endif
-  LaneCounters c = {0, ANY ? 0u : n_traced, ANY ? n_traced : 0u, n_nodes, n_tris, 0};
-  flush_counters<DETAIL>(c, F.counters, blockIdx.x * (BLOCK / 64) + (threadIdx.x >> 6));
+  wf_trace_loop<WfPairWalk<ANY, DETAIL, LDS>, BLOCK>(M, s_scene, W, F, U, Q, depth);
 }
 
 // Ordered accumulation of a batched dispatch: acc = (frame_count > 1 ? acc : 0) + (col_f, 1) for f = 0..n-1, the

@@ -131,7 +131,7 @@ struct rt_ctx {
   int occ_blocks[4] = {0, 0, 0, 0};   // cached occupancy query per persistent-kernel variant
   int wf_occ_blocks[2] = {0, 0};      // ... and for the two wavefront trace kernels
   size_t wf_occ_dyn = (size_t)-1;
-  int wf_occ_detail = -1, wf_occ_block = 0, wf_occ_walk = -1;
+  int wf_occ_detail = -1, wf_occ_block = 0, wf_occ_walk = -1, wf_occ_rayreg = -1;   // walk: 0 node, 1 pair
   int walk = 2;                  // traversal of the wavefront trace kernels: 1 = child-pair records, 0 = single nodes, 2 = auto
                                  // (MI355RT_WALK): pairs for a scene of ONE instance (measured: the 263 k-triangle hall -9 % per
                                  // batch; glass blob, 2 instances and short walks: +7 %; 1 001 instances of 8 triangles: +20 %)
@@ -1520,16 +1520,18 @@ int rt_recreate_bind_group(rt_ctx* c) { return c ? RT_OK : RT_ERR_INVALID; }
 // What one workgroup stages in LDS behind its wave queues, given `budget` bytes of LDS per workgroup: the tnodes, the
 // triangle records and the instance rows + BLAS roots, each if it fits whole.
 // *dyn_bytes = dynamic LDS size of the launch.
+// The LDS left for records beside the workgroup's `queue_bytes` of wave blocks, in 16-byte slots.
+static size_t lds_avail(size_t budget, size_t queue_bytes) {
+  budget &= ~(size_t)2047;   // LDS is allocated in granules: leave room so that the intended number of workgroups fits a CU
+  const size_t avail = budget > queue_bytes ? budget - queue_bytes : 0;
+  return avail & ~(size_t)15;
+}
 static rtk::LdsPlan plan_lds(const rt_ctx* c, size_t budget, size_t queue_bytes, size_t* dyn_bytes) {
   rtk::LdsPlan P;
   P.k_nodes = P.stage_inst = P.stage_tri = P.pad = 0;
-  if (c->no_lds_staging) {
-    *dyn_bytes = queue_bytes;
-    return P;
-  }
-  budget &= ~(size_t)2047;   // LDS is allocated in granules: leave room so that the intended number of workgroups fits a CU
-  size_t avail = budget > queue_bytes ? budget - queue_bytes : 0;
-  avail &= ~(size_t)15;
+  *dyn_bytes = queue_bytes;
+  if (c->no_lds_staging) return P;
+  size_t avail = lds_avail(budget, queue_bytes);
   // Nodes: all of them or none.  A partial treelet (the most visited nodes in LDS, the rest behind the L1) was measured
   // at 350 ... 3 200 nodes and never paid; MI355RT_TREELET_MAX = n stages min(n, what fits) for sweeps.
   size_t k = (size_t)c->n_nodes * 32 <= avail ? c->n_nodes : 0;
@@ -1546,7 +1548,7 @@ static rtk::LdsPlan plan_lds(const rt_ctx* c, size_t budget, size_t queue_bytes,
     P.stage_inst = 1;
     avail -= inst_bytes;
   }
-  *dyn_bytes = queue_bytes + (size_t)P.k_nodes * 32 + (P.stage_tri ? tri_bytes : 0) + (P.stage_inst ? inst_bytes : 0);
+  *dyn_bytes += (size_t)P.k_nodes * 32 + (P.stage_tri ? tri_bytes : 0) + (P.stage_inst ? inst_bytes : 0);
   return P;
 }
 
@@ -1554,13 +1556,9 @@ static rtk::LdsPlan plan_lds(const rt_ctx* c, size_t budget, size_t queue_bytes,
 static rtk::PairPlan plan_pairs(const rt_ctx* c, size_t budget, size_t queue_bytes, size_t* dyn_bytes) {
   rtk::PairPlan P;
   P.stage_pairs = P.stage_inst = P.stage_tri = P.pad = 0;
-  if (c->no_lds_staging) {
-    *dyn_bytes = queue_bytes;
-    return P;
-  }
-  budget &= ~(size_t)2047;
-  size_t avail = budget > queue_bytes ? budget - queue_bytes : 0;
-  avail &= ~(size_t)15;
+  *dyn_bytes = queue_bytes;
+  if (c->no_lds_staging) return P;
+  size_t avail = lds_avail(budget, queue_bytes);
   const size_t pair_bytes = (size_t)c->n_pairs * 64, tri_bytes = (size_t)c->n_tris * 16 * RT_TRI_STRIDE,
                inst_bytes = (size_t)c->n_instances * 96;
   if (pair_bytes <= avail) {
@@ -1575,36 +1573,26 @@ static rtk::PairPlan plan_pairs(const rt_ctx* c, size_t budget, size_t queue_byt
     P.stage_inst = 1;
     avail -= inst_bytes;
   }
-  *dyn_bytes = queue_bytes + (P.stage_pairs ? pair_bytes : 0) + (P.stage_tri ? tri_bytes : 0) + (P.stage_inst ? inst_bytes : 0);
+  *dyn_bytes += (P.stage_pairs ? pair_bytes : 0) + (P.stage_tri ? tri_bytes : 0) + (P.stage_inst ? inst_bytes : 0);
   return P;
 }
 
-extern "C++" {
-template <int BLOCK>
-static const void* wf_trace_fn(bool any, bool detail, bool lds, bool rayreg) {
-  if (BLOCK == 256 && rayreg && !lds) {   // instance-space ray in registers: compiled for the default workgroup size only
-    if (any) return detail ? (const void*)rtk::k_wf_trace<true, true, false, 256, true> : (const void*)rtk::k_wf_trace<true, false, false, 256, true>;
-    return detail ? (const void*)rtk::k_wf_trace<false, true, false, 256, true> : (const void*)rtk::k_wf_trace<false, false, false, 256, true>;
-  }
-  if (any) {
-    if (detail) return lds ? (const void*)rtk::k_wf_trace<true, true, true, BLOCK> : (const void*)rtk::k_wf_trace<true, true, false, BLOCK>;
-    return lds ? (const void*)rtk::k_wf_trace<true, false, true, BLOCK> : (const void*)rtk::k_wf_trace<true, false, false, BLOCK>;
-  }
-  if (detail) return lds ? (const void*)rtk::k_wf_trace<false, true, true, BLOCK> : (const void*)rtk::k_wf_trace<false, true, false, BLOCK>;
-  return lds ? (const void*)rtk::k_wf_trace<false, false, true, BLOCK> : (const void*)rtk::k_wf_trace<false, false, false, BLOCK>;
-}
-}  // extern "C++"
-extern "C++" {
-template <int BLOCK>
-static const void* wf_trace_pairs_fn(bool any, bool detail, bool lds) {
-  if (any) {
-    if (detail) return lds ? (const void*)rtk::k_wf_trace_pairs<true, true, true, BLOCK> : (const void*)rtk::k_wf_trace_pairs<true, true, false, BLOCK>;
-    return lds ? (const void*)rtk::k_wf_trace_pairs<true, false, true, BLOCK> : (const void*)rtk::k_wf_trace_pairs<true, false, false, BLOCK>;
-  }
-  if (detail) return lds ? (const void*)rtk::k_wf_trace_pairs<false, true, true, BLOCK> : (const void*)rtk::k_wf_trace_pairs<false, true, false, BLOCK>;
-  return lds ? (const void*)rtk::k_wf_trace_pairs<false, false, true, BLOCK> : (const void*)rtk::k_wf_trace_pairs<false, false, false, BLOCK>;
-}
-}  // extern "C++"
+// The trace kernels by [workgroup size 256 / 512 / 1024][any][detail][lds].  The node walk's RAYREG form is compiled for
+// 256-thread workgroups in mixed mode only: [any][detail].
+#define RT_WF_TRACE_FNS(K, B)                                                                                          \
+  {{{(const void*)K<false, false, false, B>, (const void*)K<false, false, true, B>},                                 \
+    {(const void*)K<false, true, false, B>, (const void*)K<false, true, true, B>}},                                  \
+   {{(const void*)K<true, false, false, B>, (const void*)K<true, false, true, B>},                                   \
+    {(const void*)K<true, true, false, B>, (const void*)K<true, true, true, B>}}}
+static const void* const wf_node_fns[3][2][2][2] = {RT_WF_TRACE_FNS(rtk::k_wf_trace, 256), RT_WF_TRACE_FNS(rtk::k_wf_trace, 512),
+                                                    RT_WF_TRACE_FNS(rtk::k_wf_trace, 1024)};
+static const void* const wf_pair_fns[3][2][2][2] = {RT_WF_TRACE_FNS(rtk::k_wf_trace_pairs, 256),
+                                                    RT_WF_TRACE_FNS(rtk::k_wf_trace_pairs, 512),
+                                                    RT_WF_TRACE_FNS(rtk::k_wf_trace_pairs, 1024)};
+#undef RT_WF_TRACE_FNS
+static const void* const wf_node_rayreg_fns[2][2] = {
+    {(const void*)rtk::k_wf_trace<false, false, false, 256, true>, (const void*)rtk::k_wf_trace<false, true, false, 256, true>},
+    {(const void*)rtk::k_wf_trace<true, false, false, 256, true>, (const void*)rtk::k_wf_trace<true, true, false, 256, true>}};
 
 // Wavefront form: per depth one shade launch and two trace launches, all enqueued without host readback.
 static int launch_wavefront(rt_ctx* c, const DevScene& S, const DevFrame& F, const DevFrameSlot* dslots, uint32_t n,
@@ -1644,80 +1632,62 @@ static int launch_wavefront(rt_ctx* c, const DevScene& S, const DevFrame& F, con
   Q.counters = (uint32_t*)c->wf_counters.ptr;
   const bool detail = c->detailed_counters;
   const bool pairs = c->walk == 1 || (c->walk == 2 && c->n_instances == 1);   // rt_set_walk
+  // Workgroup shape of the trace kernels.  Every wave owns `wave_bytes` of LDS: the triangle work queue, and for the pair walk
+  // the stack of deferred right children.  Everything fits beside four wave blocks in 64 KB: 256-thread workgroups, all records
+  // in LDS.  Otherwise 256-thread workgroups, each staging what fits whole in its share of the LDS (plan_pairs / plan_lds): the
+  // pair walk as many per CU as the wave blocks allow (4 at K = 8), the node walk six (6 waves per SIMD).
+  // MI355RT_WF_BLOCK / MI355RT_WF_BLOCKS_PER_CU override the shape for sweeps.
+  const size_t wave_bytes = pairs ? RT_PW_BYTES_PER_WAVE : RT_WORK_BYTES_PER_WAVE;
+  const size_t lds_records =
+      (pairs ? (size_t)4 * c->n_pairs + (size_t)RT_TRI_STRIDE * c->n_tris + (size_t)6 * c->n_instances
+             : (size_t)2 * c->n_nodes + (size_t)RT_TRI_STRIDE * c->n_tris + (size_t)4 * c->n_instances + ((size_t)c->n_instances + 3) / 4) * 16;
+  const bool trace_lds = !c->no_lds_staging && fits_lds && lds_records + (size_t)4 * wave_bytes <= 64 * 1024;
   int block = 256, blocks_per_cu = 0;
-  size_t dyn = 0;
-  bool trace_lds = false;
+  if (!trace_lds) {
+    block = c->wf_block ? c->wf_block : 256;
+    blocks_per_cu = c->wf_blocks_per_cu ? c->wf_blocks_per_cu
+                    : pairs ? std::max(1, std::min((int)(c->lds_per_cu / ((size_t)(block / 64) * wave_bytes)), (RT_WF_WAVES * 256) / block))
+                            : (block == 1024 ? 1 : (block == 512 ? 2 : 6));
+  }
+  const size_t queue_bytes = (size_t)(block / 64) * wave_bytes;
+  size_t dyn = queue_bytes + lds_records;
   rtk::PairPlan plan;
+  plan.stage_pairs = plan.stage_inst = plan.stage_tri = 1;
+  plan.pad = 0;
   rtk::LdsPlan nplan;
+  nplan.k_nodes = c->n_nodes;
+  nplan.stage_inst = nplan.stage_tri = 1;
+  nplan.pad = 0;
+  if (!trace_lds) {
+    const size_t budget = c->lds_per_cu / (size_t)blocks_per_cu;
+    if (pairs)
+      plan = plan_pairs(c, budget, queue_bytes, &dyn);
+    else
+      nplan = plan_lds(c, budget, queue_bytes, &dyn);
+  }
+  plan.troot = c->troot;
+  // few instances with deep trees (glass blob: 3 instances, 400 k nodes): a ray enters an instance once and then waits at
+  // many leaves; measured, the form that keeps its instance-space origin / direction in registers is the faster one there,
+  // the other one where rays enter many small instances (k_traverse.hip.h, trav_post_at_entry; MI355RT_WF_RAYREG=0/1 overrides)
+  const bool rayreg = !pairs && (c->wf_rayreg < 0 ? (size_t)c->n_nodes >= (size_t)1024 * std::max<size_t>(1, c->n_instances) : c->wf_rayreg != 0);
+  const int bi = block == 1024 ? 2 : (block == 512 ? 1 : 0);
   const void* trace_fn[2];
-  if (pairs) {
-    // Workgroup shape of the trace kernels.  Every wave owns RT_PW_BYTES_PER_WAVE of LDS (triangle work queue + the stack of
-    // deferred right children).  Everything fits beside four wave blocks in 64 KB: 256-thread workgroups, all records in
-    // LDS.  Otherwise 256-thread workgroups, as many per CU as the wave blocks allow (4 at K = 8), each staging what fits
-    // whole in its share of the LDS (plan_pairs); MI355RT_WF_BLOCK / MI355RT_WF_BLOCKS_PER_CU override the shape for sweeps.
-    const size_t lds_records = ((size_t)4 * c->n_pairs + (size_t)RT_TRI_STRIDE * c->n_tris + (size_t)6 * c->n_instances) * 16;
-    trace_lds = !c->no_lds_staging && fits_lds && lds_records + (size_t)4 * RT_PW_BYTES_PER_WAVE <= 64 * 1024;
-    if (!trace_lds) {
-      block = c->wf_block ? c->wf_block : 256;
-      const int fit = (int)(c->lds_per_cu / ((size_t)(block / 64) * RT_PW_BYTES_PER_WAVE));
-      blocks_per_cu = c->wf_blocks_per_cu ? c->wf_blocks_per_cu : std::max(1, std::min(fit, (RT_WF_WAVES * 256) / block));
+  for (int k = 0; k < 2; k++)   // k = 0: any hit (shadow rays), 1: closest hit (extension rays)
+    trace_fn[k] = pairs ? wf_pair_fns[bi][k == 0][detail][trace_lds]
+                        : (rayreg && bi == 0 && !trace_lds ? wf_node_rayreg_fns[k == 0][detail] : wf_node_fns[bi][k == 0][detail][trace_lds]);
+  if (c->wf_occ_dyn != dyn || c->wf_occ_detail != (int)detail || c->wf_occ_block != block || c->wf_occ_walk != (int)pairs ||
+      c->wf_occ_rayreg != (int)rayreg || c->wf_occ_blocks[0] == 0) {
+    for (int k = 0; k < 2; k++) {
+      HIP_TRY(c, hipFuncSetAttribute(trace_fn[k], hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
+      int per_cu = 0;
+      HIP_TRY(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, trace_fn[k], block, dyn));
+      c->wf_occ_blocks[k] = per_cu < 1 ? 1 : per_cu;
     }
-    const size_t queue_bytes = (size_t)(block / 64) * RT_PW_BYTES_PER_WAVE;
-    dyn = queue_bytes + lds_records;
-    plan.stage_pairs = plan.stage_inst = plan.stage_tri = 1;
-    plan.pad = 0;
-    if (!trace_lds) plan = plan_pairs(c, c->lds_per_cu / (size_t)blocks_per_cu, queue_bytes, &dyn);
-    plan.troot = c->troot;
-    for (int k = 0; k < 2; k++)
-      trace_fn[k] = block == 1024 ? wf_trace_pairs_fn<1024>(k == 0, detail, trace_lds)
-                                  : (block == 512 ? wf_trace_pairs_fn<512>(k == 0, detail, trace_lds) : wf_trace_pairs_fn<256>(k == 0, detail, trace_lds));
-    if (c->wf_occ_dyn != dyn || c->wf_occ_detail != (int)detail || c->wf_occ_block != block || c->wf_occ_walk != (int)pairs || c->wf_occ_blocks[0] == 0) {
-      for (int k = 0; k < 2; k++) {
-        HIP_TRY(c, hipFuncSetAttribute(trace_fn[k], hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
-        int per_cu = 0;
-        HIP_TRY(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, trace_fn[k], block, dyn));
-        c->wf_occ_blocks[k] = per_cu < 1 ? 1 : per_cu;
-      }
-      c->wf_occ_dyn = dyn;
-      c->wf_occ_detail = (int)detail;
-      c->wf_occ_block = block;
-      c->wf_occ_walk = (int)pairs;
-    }
-  } else {
-    // Workgroup shape of the trace kernels.  Everything fits beside four wave queues in 64 KB: 256-thread workgroups, all
-    // records in LDS.  Otherwise six 256-thread workgroups per CU (6 waves per SIMD), each staging what fits whole in its
-    // sixth of the LDS (plan_lds); MI355RT_WF_BLOCK / MI355RT_WF_BLOCKS_PER_CU override the shape for sweeps.
-    const size_t lds_records = ((size_t)2 * c->n_nodes + (size_t)RT_TRI_STRIDE * c->n_tris + (size_t)4 * c->n_instances + ((size_t)c->n_instances + 3) / 4) * 16;
-    trace_lds = !c->no_lds_staging && fits_lds && lds_records + (size_t)4 * RT_WORK_BYTES_PER_WAVE <= 64 * 1024;
-    if (!trace_lds) {
-      block = c->wf_block ? c->wf_block : 256;
-      blocks_per_cu = c->wf_blocks_per_cu ? c->wf_blocks_per_cu : (block == 1024 ? 1 : (block == 512 ? 2 : 6));
-    }
-    const size_t queue_bytes = (size_t)(block / 64) * RT_WORK_BYTES_PER_WAVE;
-    dyn = queue_bytes + lds_records;
-    nplan.k_nodes = c->n_nodes;
-    nplan.stage_inst = nplan.stage_tri = 1;
-    nplan.pad = 0;
-    if (!trace_lds) nplan = plan_lds(c, c->lds_per_cu / (size_t)blocks_per_cu, queue_bytes, &dyn);
-    // few instances with deep trees (glass blob: 3 instances, 400 k nodes): a ray enters an instance once and then waits at
-    // many leaves; measured, the form that keeps its instance-space origin / direction in registers is the faster one there,
-    // the other one where rays enter many small instances (k_traverse.hip.h, trav_post_at_entry; MI355RT_WF_RAYREG=0/1 overrides)
-    const bool rayreg = c->wf_rayreg < 0 ? (size_t)c->n_nodes >= (size_t)1024 * std::max<size_t>(1, c->n_instances) : c->wf_rayreg != 0;
-    for (int k = 0; k < 2; k++)
-      trace_fn[k] = block == 1024 ? wf_trace_fn<1024>(k == 0, detail, trace_lds, rayreg)
-                                  : (block == 512 ? wf_trace_fn<512>(k == 0, detail, trace_lds, rayreg) : wf_trace_fn<256>(k == 0, detail, trace_lds, rayreg));
-    if (c->wf_occ_dyn != dyn || c->wf_occ_detail != (int)detail || c->wf_occ_block != block || c->wf_occ_walk != (rayreg ? 2 : 0) || c->wf_occ_blocks[0] == 0) {
-      for (int k = 0; k < 2; k++) {
-        HIP_TRY(c, hipFuncSetAttribute(trace_fn[k], hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
-        int per_cu = 0;
-        HIP_TRY(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, trace_fn[k], block, dyn));
-        c->wf_occ_blocks[k] = per_cu < 1 ? 1 : per_cu;
-      }
-      c->wf_occ_dyn = dyn;
-      c->wf_occ_detail = (int)detail;
-      c->wf_occ_block = block;
-      c->wf_occ_walk = rayreg ? 2 : 0;
-    }
+    c->wf_occ_dyn = dyn;
+    c->wf_occ_detail = (int)detail;
+    c->wf_occ_block = block;
+    c->wf_occ_walk = (int)pairs;
+    c->wf_occ_rayreg = (int)rayreg;
   }
   if (getenv("MI355RT_DEBUG_SHAPE"))
     fprintf(stderr, "[mi355rt] trace kernels: %s walk, %d threads per workgroup, %zu bytes of LDS, resident workgroups per CU: any-hit %d, closest-hit %d\n",
@@ -1937,17 +1907,15 @@ static int compute_frames(rt_ctx* c, const uint32_t* frame_counts, uint32_t n, u
   } else {
     // persistent kernel: grid = resident workgroups, tiles handed out through a ticket counter
     HIP_TRY(c, hipMemsetAsync(c->ticket.ptr, 0, 4, c->stream));
-    const size_t lds_bytes = rtk::scene_lds_slots(c->n_nodes, c->n_tris, c->n_instances, c->n_verts, c->n_lights) * 16;
-    const bool use_lds = !c->no_lds_staging && lds_bytes + (size_t)4 * RT_WORK_BYTES_PER_WAVE <= 64 * 1024;
-    size_t dyn = (size_t)4 * RT_WORK_BYTES_PER_WAVE + lds_bytes;  // work queues + records
+    size_t dyn = (size_t)4 * RT_WORK_BYTES_PER_WAVE + scene_lds;  // work queues + records
     rtk::LdsPlan plan;
     plan.k_nodes = c->n_nodes;
     plan.stage_inst = plan.stage_tri = 1;
     plan.pad = 0;
     // a scene that does not fit as a whole: six 256-thread workgroups per CU (6 waves / SIMD), each with its share of the
     // CU's LDS for the top of the tree
-    if (!use_lds) plan = plan_lds(c, c->lds_per_cu / 6, (size_t)4 * RT_WORK_BYTES_PER_WAVE, &dyn);
-    const int vi = (c->detailed_counters ? 2 : 0) + (use_lds ? 1 : 0);
+    if (!fits_lds) plan = plan_lds(c, c->lds_per_cu / 6, (size_t)4 * RT_WORK_BYTES_PER_WAVE, &dyn);
+    const int vi = (c->detailed_counters ? 2 : 0) + (fits_lds ? 1 : 0);
     static const void* const fns[4] = {(const void*)rtk::k_pathtrace_persistent<false, false>,
                                        (const void*)rtk::k_pathtrace_persistent<false, true>,
                                        (const void*)rtk::k_pathtrace_persistent<true, false>,
