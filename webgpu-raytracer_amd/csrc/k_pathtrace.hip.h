@@ -1,214 +1,17 @@
-// k_pathtrace.hip.h — k_pathtrace (one pixel per lane), the wave-level traverse() with its LDS triangle queue, shade_bounce() and k_pathtrace_persistent.
+// k_pathtrace.hip.h — the per-path state machine of Raytracer.wgsl `main` + ray_color (:607-819) (start_sample,
+// setup_surface, shade_bounce, finish_pixel) and two kernels that drive it: k_pathtrace (one pixel per lane) and
+// k_pathtrace_persistent.  k_wf_shade (k_wavefront.hip.h) is the third driver.
 // Part of the kernel set of csrc/kernels.hip.h (included from there, in order; not a stand-alone header).
 #ifndef MI355RT_K_PATHTRACE_HIP_H
 #define MI355RT_K_PATHTRACE_HIP_H
 
 namespace rtk {
 
-// ======================================================================= path tracer
-// One sample: Raytracer.wgsl ray_color (:607-783).
-template <bool DETAIL>
-__device__ rt3 ray_color(const DevScene& S, const DevFrame& F, const rt_scene_uniforms& U, rt3 ro, rt3 rd,
-                         uint32_t& rng, uint32_t p_idx, LaneCounters& c) {
-  rt3 throughput = rt3_splat(1.0f);
-  rt3 radiance = rt3_splat(0.0f);
-  float prev_bsdf_pdf = 0.0f;
-  bool specular_bounce = true;
-
-  // depth 0 comes from the G-buffer
-  if (F.depth[p_idx] >= 1.0f) return radiance;
-  float4 g = F.normal_id[p_idx];
-  uint32_t tri = rt_f2u(g.z);
-  uint32_t inst = rt_f2u(g.w);
-  InvRows m = load_inv_rows(S, inst);
-  Bary b = barycentrics(S, tri, mul_point(m, ro), mul_dir(m, rd));
-  float hit_t = b.t;
-  float4 tidx = S.topo[5 * tri];
-  float2 uv0 = S.uv[rt_f2u(tidx.x)], uv1 = S.uv[rt_f2u(tidx.y)], uv2 = S.uv[rt_f2u(tidx.z)];
-  rt2 tex_uv = rt2_make(uv0.x, uv0.y) * b.w + rt2_make(uv1.x, uv1.y) * b.u + rt2_make(uv2.x, uv2.y) * b.v;
-  rt3 normal = unpack_normal(g.x, g.y);
-  uint32_t ga = F.albedo[p_idx];
-  rt3 albedo = rt3_make(rt_from_unorm8(ga & 255u), rt_from_unorm8((ga >> 8) & 255u), rt_from_unorm8((ga >> 16) & 255u));
-  rt3 world_geom_n = rt_normalize(normal_to_world(m, rt_normalize(rt_cross(b.e1, b.e2))));
-
-  for (uint32_t depth = 0u; depth < F.max_depth; depth++) {
-    if (DETAIL) c.shaded++;
-    float4 d0 = S.topo[5 * tri + 1], d1 = S.topo[5 * tri + 2], d2 = S.topo[5 * tri + 3], d3 = S.topo[5 * tri + 4];
-    uint32_t mat_type = rt_f2u32_sat(d0.w + 0.5f);
-    rt3 hit_p = ro + rd * hit_t;
-
-    normal = (rt_dot(rd, normal) < 0.0f) ? normal : -normal;
-    world_geom_n = (rt_dot(rd, world_geom_n) < 0.0f) ? world_geom_n : -world_geom_n;
-
-    float metallic = d1.x, roughness = d1.y;
-    if (d2.y > -0.5f) {
-      rt3 mr = sample_tex(S, tex_uv, rt_f2i32_sat(d2.y));
-      metallic *= mr.z;
-      roughness *= mr.y;
-    }
-    roughness = rt_max(roughness, 0.005f);
-    rt3 emissive = xyz(d3);
-    if (d2.w > -0.5f) emissive = emissive * sample_tex(S, tex_uv, rt_f2i32_sat(d2.w));
-    rt3 f0 = rt_mix3(rt3_splat(0.04f), albedo, metallic);
-
-    // emissive / light
-    if (mat_type == 3u || rt_length(emissive) > 1e-4f) {
-      rt3 em_val = (mat_type == 3u) ? albedo : emissive;
-      if (specular_bounce) {
-        radiance = radiance + throughput * em_val;
-      } else {
-        radiance = radiance +
-                   throughput * em_val * power_heuristic(prev_bsdf_pdf, light_pdf(S, U.light_count, tri, inst, hit_t, rd));
-      }
-      if (mat_type == 3u) break;
-    }
-
-    // next-event estimation
-    if (mat_type != 2u) {
-      LightSample ls = sample_light(S, U.light_count, hit_p, rng);
-      if (ls.pdf > 0.0f) {
-        c.shadow++;
-        if (!trace_any<DETAIL>(S, U.blas_base_idx, hit_p + world_geom_n * 1e-4f, ls.dir, RT_T_MIN, ls.dist - 2e-4f, c)) {
-          rt3 bsdf_val = rt3_splat(0.0f);
-          float bsdf_pdf = 0.0f;
-          if (mat_type == 0u) {
-            bsdf_val = rt_div_pi3(albedo);
-            bsdf_pdf = rt_div_pi(rt_max(rt_dot(normal, ls.dir), 0.0f));
-          } else if (mat_type == 1u) {
-            bsdf_val = eval_ggx(normal, -rd, ls.dir, roughness, f0);
-            rt3 H = rt_normalize(-rd + ls.dir);
-            bsdf_pdf = rt_div(ggx_d(rt_dot(normal, H), roughness * roughness) * rt_max(rt_dot(normal, H), 0.0f),
-                              4.0f * rt_max(rt_dot(-rd, H), 0.0f));
-          }
-          if (bsdf_pdf > 0.0f) {
-            radiance = radiance + rt_div3z(throughput * bsdf_val * ls.L * power_heuristic(ls.pdf, bsdf_pdf) *
-                                               rt_max(rt_dot(normal, ls.dir), 0.0f), ls.pdf);
-          }
-        }
-      }
-    }
-
-    Scatter sc;
-    if (mat_type == 0u) {
-      sc = sample_diffuse(normal, albedo, rng);
-    } else if (mat_type == 1u) {
-      sc = sample_ggx(normal, -rd, roughness, f0, rng);
-    } else {
-      sc = sample_dielectric(rd, normal, d1.z, albedo, rng);
-    }
-    if (mat_type != 2u && rt_dot(sc.dir, world_geom_n) <= 0.0f) {
-      sc.pdf = 0.0f;
-      sc.throughput = rt3_splat(0.0f);
-    }
-    if (sc.pdf <= 0.0f || rt_length(sc.throughput) <= 0.0f) break;
-
-    throughput = throughput * sc.throughput;
-    rt3 offset_n = (rt_dot(sc.dir, world_geom_n) > 0.0f) ? world_geom_n : -world_geom_n;
-    ro = hit_p + offset_n * 1e-4f;
-    rd = sc.dir;
-    prev_bsdf_pdf = sc.pdf;
-    specular_bounce = sc.specular;
-
-    if (depth > 3u) {  // Russian roulette
-      float p = rt_max(throughput.x, rt_max(throughput.y, throughput.z));
-      if (rand_pcg(rng) > p) break;
-      throughput = rt_div3z(throughput, p);
-    }
-
-    if (depth < F.max_depth - 1u) {
-      c.extension++;
-      Hit hit = trace_closest<DETAIL>(S, U.blas_base_idx, ro, rd, RT_T_MIN, RT_T_MAX, c);
-      if (hit.inst < 0) break;
-      hit_t = hit.t;
-      tri = (uint32_t)hit.tri;
-      inst = (uint32_t)hit.inst;
-      m = load_inv_rows(S, inst);
-      b = barycentrics(S, tri, mul_point(m, ro), mul_dir(m, rd));
-      tidx = S.topo[5 * tri];
-      uint32_t i0 = rt_f2u(tidx.x), i1 = rt_f2u(tidx.y), i2 = rt_f2u(tidx.z);
-      uv0 = S.uv[i0];
-      uv1 = S.uv[i1];
-      uv2 = S.uv[i2];
-      tex_uv = rt2_make(uv0.x, uv0.y) * b.w + rt2_make(uv1.x, uv1.y) * b.u + rt2_make(uv2.x, uv2.y) * b.v;
-      rt3 ln = rt_normalize(xyz(S.nrm[i0]) * b.w + xyz(S.nrm[i1]) * b.u + xyz(S.nrm[i2]) * b.v);
-      normal = rt_normalize(normal_to_world(m, ln));
-      float4 nd0 = S.topo[5 * tri + 1], nd2 = S.topo[5 * tri + 3];
-      albedo = xyz(nd0);
-      if (nd2.x > -0.5f) albedo = albedo * sample_tex(S, tex_uv, rt_f2i32_sat(nd2.x));
-      if (nd2.z > -0.5f) {
-        rt3 n_map = sample_tex(S, tex_uv, rt_f2i32_sat(nd2.z)) * 2.0f - rt3_splat(1.0f);
-        rt3 T = rt_normalize(b.e1);
-        rt3 B = rt_normalize(rt_cross(ln, T));
-        rt3 ln_mapped = rt_normalize(T * n_map.x + B * n_map.y + ln * n_map.z);
-        normal = rt_normalize(normal_to_world(m, ln_mapped));
-      }
-      world_geom_n = rt_normalize(normal_to_world(m, rt_normalize(rt_cross(b.e1, b.e2))));
-    }
-  }
-  return radiance;
-}
-
-// Raytracer.wgsl `main` (:791-819)
-template <bool DETAIL>
-__global__ __launch_bounds__(64) void k_pathtrace(DevScene S, DevFrame F, rt_scene_uniforms U) {
-  uint32_t x, y;
-  bool live = tile_pixel(U, x, y) && owns_row(F, y);
-  LaneCounters c = {0, 0, 0, 0, 0, 0};
-  if (live) {
-    const uint32_t p_idx = y * U.width + x;
-    rt3 cam_o = rt3_make(U.camera.origin[0], U.camera.origin[1], U.camera.origin[2]);
-    rt3 cam_ll = rt3_make(U.camera.lower_left[0], U.camera.lower_left[1], U.camera.lower_left[2]);
-    rt3 cam_h = rt3_make(U.camera.horizontal[0], U.camera.horizontal[1], U.camera.horizontal[2]);
-    rt3 cam_v = rt3_make(U.camera.vertical[0], U.camera.vertical[1], U.camera.vertical[2]);
-    const float lens = U.camera.origin[3];
-    rt3 col = rt3_splat(0.0f);
-    for (uint32_t i = 0u; i < F.spp; i++) {
-      uint32_t rng = init_rng(p_idx, U.frame_count * F.spp + i);
-      rt3 off = rt3_splat(0.0f);
-      if (lens > 0.0f) {  // random_in_unit_disk (:201-205)
-        float r = rt_sqrt(rand_pcg(rng));
-        float theta = RT_TWO_PI * rand_pcg(rng);
-        float st, ct;
-        rt_sincos(theta, &st, &ct);
-        rt3 rdk = lens * rt3_make(r * ct, r * st, 0.0f);
-        rt3 cu = rt3_make(U.camera.u[0], U.camera.u[1], U.camera.u[2]);
-        rt3 cv = rt3_make(U.camera.v[0], U.camera.v[1], U.camera.v[2]);
-        off = cu * rdk.x + cv * rdk.y;
-      }
-      float u = rt_div((float)x + 0.5f + U.jitter[0] * (float)U.width, (float)U.width);
-      float v = 1.0f - rt_div((float)y + 0.5f + U.jitter[1] * (float)U.height, (float)U.height);
-      rt3 d = cam_ll + u * cam_h + v * cam_v - cam_o - off;
-      col = col + ray_color<DETAIL>(S, F, U, cam_o + off, d, rng, p_idx, c);
-    }
-    if (F.spp != 1u) col = rt_div3z(col, (float)F.spp);   // x / 1 = x
-    float4 acc = make_float4(col.x, col.y, col.z, 1.0f);
-    if (U.frame_count > 1u) {
-      float4 prev = F.accum[p_idx];
-      acc = make_float4(prev.x + col.x, prev.y + col.y, prev.z + col.z, prev.w + 1.0f);
-    }
-    F.accum[p_idx] = acc;
-  }
-  flush_counters<DETAIL>(c, F.counters, blockIdx.x);
-}
-
-// ============================================================ path tracer, persistent form
-// k_pathtrace_persistent: the production path-trace kernel.
-//
-//  * persistent waves: the grid is sized to the resident wave count; each wave pulls 8x8 pixel
-//    tiles from a global ticket counter until the image is exhausted (one ray per lane);
-//  * path regeneration: a lane whose path ended (light hit, miss, absorbed, Russian roulette,
-//    depth limit) takes the next pixel of its wave's current tile, found with a ballot/mbcnt prefix
-//    over the idle mask, so the 64 lanes stay busy instead of waiting for the longest path;
-//  * per trip every live lane executes exactly one bounce: shade -> (NEE shadow ray) -> scatter ->
-//    (extension ray), so the wave runs the two traversals and the shading code converged;
-//  * traversal data (nodes, triangle records, instance records) is staged once per workgroup in LDS
-//    when it fits (LDS = true); larger scenes read the same records through L1/L2;
-//  * TLAS and BLAS are walked by ONE loop with an in-instance flag, so lanes in different
-//    instances / levels share the node fetch + slab test.
-// Per-path arithmetic and RNG draw order are exactly those of ray_color above (and of the oracle);
-// only the scheduling differs, which cannot change any pixel because paths are independent.
-
-// (the wave-level walk itself — TravMem, trav_step, tri_flush, traverse() — is in k_traverse.hip.h)
+// ======================================================================= per-path state machine
+// One sample of the reference is a PathState that advances one bounce per shade_bounce() call.  The three kernel forms
+// differ only in how they schedule paths and when they trace the rays a bounce asks for; traversal draws no random
+// numbers, so per path the arithmetic, the RNG draw order and the order of f32 additions are those of ray_color (and of
+// the oracle) in every form, and so are the pixels.
 
 struct PathState {
   uint32_t pixel, rng, depth, sample;
@@ -221,6 +24,19 @@ struct PathState {
   rt3 normal, geom_n, albedo;
   rt2 tex_uv;
 };
+
+// the state of a lane without a path: every field zero, specular = true (set field by field: `PathState p = {}` costs the
+// global-memory persistent kernel 3 more VGPR spills in the product build)
+__device__ __forceinline__ PathState idle_path() {
+  PathState p;
+  p.pixel = p.rng = p.depth = p.sample = 0u;
+  p.ro = p.rd = p.throughput = p.radiance = p.col = p.normal = p.geom_n = p.albedo = rt3_splat(0.0f);
+  p.prev_pdf = p.hit_t = 0.0f;
+  p.specular = true;
+  p.tri = p.inst = 0u;
+  p.tex_uv = rt2_make(0.0f, 0.0f);
+  return p;
+}
 
 // surface frame of the hit (tri, inst) for the ray (ro, rd): Raytracer.wgsl:738-779
 __device__ __forceinline__ void setup_surface(const DevScene& S, PathState& p, bool from_gbuffer, float gx, float gy,
@@ -250,6 +66,62 @@ __device__ __forceinline__ void setup_surface(const DevScene& S, PathState& p, b
     }
   }
   p.geom_n = rt_normalize(normal_to_world(m, rt_normalize(rt_cross(b.e1, b.e2))));
+}
+
+// the camera of the uniforms, read once per kernel
+struct CameraBasis {
+  rt3 o, ll, h, v;
+  float lens;   // camera.origin.w: > 0 draws a thin-lens offset per sample
+};
+__device__ __forceinline__ CameraBasis camera_basis(const rt_scene_uniforms& U) {
+  CameraBasis c;
+  c.o = rt3_make(U.camera.origin[0], U.camera.origin[1], U.camera.origin[2]);
+  c.ll = rt3_make(U.camera.lower_left[0], U.camera.lower_left[1], U.camera.lower_left[2]);
+  c.h = rt3_make(U.camera.horizontal[0], U.camera.horizontal[1], U.camera.horizontal[2]);
+  c.v = rt3_make(U.camera.vertical[0], U.camera.vertical[1], U.camera.vertical[2]);
+  c.lens = U.camera.origin[3];
+  return c;
+}
+
+// Start sample p.sample of pixel p.pixel = (x, y) in the frame `slot` (Raytracer.wgsl:798-809, :608-619): seed the RNG,
+// make the camera ray, reset the path and take the depth-0 surface from the frame's G-buffer.  Returns false for a
+// background pixel (or MAX_DEPTH = 0): the sample is black and ends at once.
+__device__ __forceinline__ bool start_sample(const DevScene& S, const DevFrame& F, const rt_scene_uniforms& U,
+                                             const CameraBasis& cam, const DevFrameSlot& slot, uint32_t x, uint32_t y,
+                                             PathState& p) {
+  p.rng = init_rng(p.pixel, slot.frame_count * F.spp + p.sample);
+  rt3 off = rt3_splat(0.0f);
+  if (cam.lens > 0.0f) {  // random_in_unit_disk (:201-205)
+    float r = rt_sqrt(rand_pcg(p.rng));
+    float theta = RT_TWO_PI * rand_pcg(p.rng);
+    float st, ct;
+    rt_sincos(theta, &st, &ct);
+    rt3 rdk = cam.lens * rt3_make(r * ct, r * st, 0.0f);
+    rt3 cu = rt3_make(U.camera.u[0], U.camera.u[1], U.camera.u[2]);
+    rt3 cv = rt3_make(U.camera.v[0], U.camera.v[1], U.camera.v[2]);
+    off = cu * rdk.x + cv * rdk.y;
+  }
+  float u = rt_div((float)x + 0.5f + slot.jitter_x * (float)U.width, (float)U.width);
+  float v = 1.0f - rt_div((float)y + 0.5f + slot.jitter_y * (float)U.height, (float)U.height);
+  p.rd = cam.ll + u * cam.h + v * cam.v - cam.o - off;
+  p.ro = cam.o + off;
+  p.throughput = rt3_splat(1.0f);
+  p.radiance = rt3_splat(0.0f);
+  p.prev_pdf = 0.0f;
+  p.specular = true;
+  p.depth = 0u;
+  // the three G-buffer words of the pixel are requested together (they come from HBM: one round trip instead of depth
+  // first, then the rest)
+  const float gdepth = slot.depth[p.pixel];
+  const float4 g = slot.normal_id[p.pixel];
+  const uint32_t galbedo = slot.albedo[p.pixel];
+  if (!(gdepth >= 1.0f) && F.max_depth != 0u) {
+    p.tri = rt_f2u(g.z);
+    p.inst = rt_f2u(g.w);
+    setup_surface(S, p, true, g.x, g.y, galbedo);
+    return true;
+  }
+  return false;
 }
 
 // One bounce of ray_color for a path whose surface frame is ready (Raytracer.wgsl:656-728): emissive / MIS, the
@@ -359,6 +231,88 @@ __device__ __forceinline__ void shade_bounce(const DevScene& S, uint32_t light_c
   }
   o.ended = ended;
 }
+
+// The pixel's last sample is done (Raytracer.wgsl:811-818): average the samples, then accumulate, or park the colour of
+// frame `item_slot` of a batch in frame_col (F.frame_col is set for batched and wavefront dispatches, whose frames
+// k_accumulate_frames adds in order).  Unbatched, slots[0] is the frame.
+__device__ __forceinline__ void finish_pixel(const DevFrame& F, const rt_scene_uniforms& U, const DevFrameSlot* slots,
+                                             uint32_t item_slot, uint32_t pixel, rt3 col) {
+  if (F.spp != 1u) col = rt_div3z(col, (float)F.spp);   // x / 1 = x, bit for bit
+  if (F.frame_col) {
+    F.frame_col[(size_t)item_slot * ((size_t)U.width * U.height) + pixel] = make_float4(col.x, col.y, col.z, 1.0f);
+  } else {
+    float4 acc = make_float4(col.x, col.y, col.z, 1.0f);
+    if (slots[0].frame_count > 1u) {
+      float4 prev = F.accum[pixel];
+      acc = make_float4(prev.x + col.x, prev.y + col.y, prev.z + col.z, prev.w + 1.0f);
+    }
+    F.accum[pixel] = acc;
+  }
+}
+
+// ======================================================================= path tracer, one pixel per lane
+// Raytracer.wgsl `main` (:791-819) as written: a lane runs its pixel's samples one after another and traces the rays of
+// each bounce at once with the per-lane walk (k_intersect.hip.h).  Kept for A/B timing (kernel variant 0); unbatched only.
+template <bool DETAIL>
+__global__ __launch_bounds__(64) void k_pathtrace(DevScene S, DevFrame F, rt_scene_uniforms U,
+                                                  const DevFrameSlot* __restrict__ slots) {
+  uint32_t x, y;
+  bool live = tile_pixel(U, x, y) && owns_row(F, y);
+  LaneCounters c = {0, 0, 0, 0, 0, 0};
+  if (live) {
+    const CameraBasis cam = camera_basis(U);
+    const DevFrameSlot slot = slots[0];
+    PathState p = idle_path();
+    p.pixel = y * U.width + x;
+    for (p.sample = 0u; p.sample < F.spp; p.sample++) {
+      bool alive = start_sample(S, F, U, cam, slot, x, y, p);
+      while (alive) {
+        if (DETAIL) c.shaded++;
+        BounceOut bo;
+        shade_bounce(S, U.light_count, F.max_depth, p, bo);
+        if (bo.want_shadow) {
+          c.shadow++;
+          const bool occluded = trace_any<DETAIL>(S, U.blas_base_idx, bo.sh_o, bo.sh_d, RT_T_MIN, bo.sh_tmax, c);
+          if (!occluded && bo.nee_valid) p.radiance = p.radiance + bo.nee;
+        }
+        alive = bo.want_extend;
+        if (alive) {
+          c.extension++;
+          const Hit hit = trace_closest<DETAIL>(S, U.blas_base_idx, p.ro, p.rd, RT_T_MIN, RT_T_MAX, c);
+          alive = hit.inst >= 0;   // a miss ends the path
+          if (alive) {
+            p.hit_t = hit.t;
+            p.tri = (uint32_t)hit.tri;
+            p.inst = (uint32_t)hit.inst;
+            setup_surface(S, p, false, 0.0f, 0.0f, 0u);
+            p.depth++;
+          }
+        }
+      }
+      p.col = p.col + p.radiance;
+    }
+    finish_pixel(F, U, slots, 0u, p.pixel, p.col);
+  }
+  flush_counters<DETAIL>(c, F.counters, blockIdx.x);
+}
+
+// ============================================================ path tracer, persistent form
+// k_pathtrace_persistent: the production path-trace kernel.
+//
+//  * persistent waves: the grid is sized to the resident wave count; each wave pulls 8x8 pixel
+//    tiles from a global ticket counter until the image is exhausted (one ray per lane);
+//  * path regeneration: a lane whose path ended (light hit, miss, absorbed, Russian roulette,
+//    depth limit) takes the next pixel of its wave's current tile, found with a ballot/mbcnt prefix
+//    over the idle mask, so the 64 lanes stay busy instead of waiting for the longest path;
+//  * per trip every live lane executes exactly one bounce: shade -> (NEE shadow ray) -> scatter ->
+//    (extension ray), so the wave runs the two traversals and the shading code converged;
+//  * traversal data (nodes, triangle records, instance records) is staged once per workgroup in LDS
+//    when it fits (LDS = true); larger scenes read the same records through L1/L2;
+//  * TLAS and BLAS are walked by ONE loop with an in-instance flag, so lanes in different
+//    instances / levels share the node fetch + slab test.
+// Only the scheduling differs from k_pathtrace, which cannot change any pixel because paths are independent.
+
+// (the wave-level walk itself — TravMem, trav_step, tri_flush, traverse() — is in k_traverse.hip.h)
 
 // number of 16-byte LDS slots the whole scene needs (traversal records + shading arrays)
 __host__ __device__ inline size_t scene_lds_slots(uint32_t n_nodes, uint32_t n_tris, uint32_t n_inst, uint32_t n_verts,
@@ -493,27 +447,19 @@ __global__ __launch_bounds__(256, LDS ? RT_PT_LDS_WAVES : RT_PT_GLOBAL_WAVES) vo
   const uint32_t tiles_x = (U.width + 7u) / 8u;
   // tickets enumerate only the tile rows this rank owns when the stripes are tile-aligned
   const uint32_t n_tiles = tiles_x * (F.own_period ? F.own_tile_rows : (U.height + 7u) / 8u);
-  const rt3 cam_o = rt3_make(U.camera.origin[0], U.camera.origin[1], U.camera.origin[2]);
-  const rt3 cam_ll = rt3_make(U.camera.lower_left[0], U.camera.lower_left[1], U.camera.lower_left[2]);
-  const rt3 cam_h = rt3_make(U.camera.horizontal[0], U.camera.horizontal[1], U.camera.horizontal[2]);
-  const rt3 cam_v = rt3_make(U.camera.vertical[0], U.camera.vertical[1], U.camera.vertical[2]);
-  const float lens = U.camera.origin[3];
+  const CameraBasis cam = camera_basis(U);
 
   // wave-uniform work cursor: pixels [tile_pos, 64) of the wave's tile are still unassigned; the tile's origin and frame are
   // worked out once per ticket (two divisions by run-time values, 20 instructions each: not once per regenerated lane)
   uint32_t tile_pos = 64u, tile_x0 = 0u, tile_y0 = 0u, tile_slot = 0u;
   bool work_left = true;
 
-  PathState p;
+  PathState p = idle_path();
   uint32_t item_slot = 0u;  // frame of the batch the lane's current (frame, pixel) item belongs to
   uint32_t pixel_xy = 0u;   // x | y << 16 of p.pixel
   bool alive = false;       // lane owns a running path
   bool have_pixel = false;  // lane owns a pixel whose samples are not all done
   uint32_t cnt_ext = 0, cnt_shadow = 0, cnt_nodes = 0, cnt_tris = 0, cnt_shaded = 0;
-  p.pixel = 0; p.rng = 0; p.depth = 0; p.sample = 0; p.prev_pdf = 0.0f; p.specular = true; p.hit_t = 0.0f;
-  p.tri = 0; p.inst = 0;
-  p.ro = p.rd = p.throughput = p.radiance = p.col = p.normal = p.geom_n = p.albedo = rt3_splat(0.0f);
-  p.tex_uv = rt2_make(0.0f, 0.0f);
 
 #ifdef RT_PT_STAMPS
   unsigned long long pt_cyc[5] = {0, 0, 0, 0, 0}, pt_trips = 0;
@@ -574,38 +520,7 @@ __global__ __launch_bounds__(256, LDS ? RT_PT_LDS_WAVES : RT_PT_GLOBAL_WAVES) vo
     if (!alive && have_pixel) {
       const uint32_t x = pixel_xy & 0xffffu, y = pixel_xy >> 16;
       const DevFrameSlot slot = slots[item_slot];
-      p.rng = init_rng(p.pixel, slot.frame_count * F.spp + p.sample);
-      rt3 off = rt3_splat(0.0f);
-      if (lens > 0.0f) {
-        float r = rt_sqrt(rand_pcg(p.rng));
-        float theta = RT_TWO_PI * rand_pcg(p.rng);
-        float st, ct;
-        rt_sincos(theta, &st, &ct);
-        rt3 rdk = lens * rt3_make(r * ct, r * st, 0.0f);
-        rt3 cu = rt3_make(U.camera.u[0], U.camera.u[1], U.camera.u[2]);
-        rt3 cv = rt3_make(U.camera.v[0], U.camera.v[1], U.camera.v[2]);
-        off = cu * rdk.x + cv * rdk.y;
-      }
-      float u = rt_div((float)x + 0.5f + slot.jitter_x * (float)U.width, (float)U.width);
-      float v = 1.0f - rt_div((float)y + 0.5f + slot.jitter_y * (float)U.height, (float)U.height);
-      p.rd = cam_ll + u * cam_h + v * cam_v - cam_o - off;
-      p.ro = cam_o + off;
-      p.throughput = rt3_splat(1.0f);
-      p.radiance = rt3_splat(0.0f);
-      p.prev_pdf = 0.0f;
-      p.specular = true;
-      p.depth = 0u;
-      // background pixel (or MAX_DEPTH = 0): the sample is black and ends at once.  The three G-buffer words of the
-      // pixel are requested together (they come from HBM: one round trip instead of depth first, then the rest)
-      const float gdepth = slot.depth[p.pixel];
-      const float4 g = slot.normal_id[p.pixel];
-      const uint32_t galbedo = slot.albedo[p.pixel];
-      if (!(gdepth >= 1.0f) && F.max_depth != 0u) {
-        p.tri = rt_f2u(g.z);
-        p.inst = rt_f2u(g.w);
-        setup_surface(S, p, true, g.x, g.y, galbedo);
-        alive = true;
-      }
+      alive = start_sample(S, F, U, cam, slot, x, y, p);
     }
     const bool running = alive;
     bool path_done = have_pixel && !alive;  // background sample ends immediately
@@ -688,20 +603,8 @@ __global__ __launch_bounds__(256, LDS ? RT_PT_LDS_WAVES : RT_PT_GLOBAL_WAVES) vo
       alive = false;
       p.col = p.col + p.radiance;
       p.sample++;
-      if (p.sample >= F.spp) {  // the item's last sample: Raytracer.wgsl:811-818
-        rt3 c = p.col;
-        if (F.spp != 1u) c = rt_div3z(p.col, (float)F.spp);   // x / 1 = x, bit for bit
-        if (F.frame_col) {
-          // batched: park the frame colour; k_accumulate_frames adds the frames in order
-          F.frame_col[(size_t)item_slot * ((size_t)U.width * U.height) + p.pixel] = make_float4(c.x, c.y, c.z, 1.0f);
-        } else {
-          float4 acc = make_float4(c.x, c.y, c.z, 1.0f);
-          if (slots[0].frame_count > 1u) {
-            float4 prev = F.accum[p.pixel];
-            acc = make_float4(prev.x + c.x, prev.y + c.y, prev.z + c.z, prev.w + 1.0f);
-          }
-          F.accum[p.pixel] = acc;
-        }
+      if (p.sample >= F.spp) {  // the item's last sample
+        finish_pixel(F, U, slots, item_slot, p.pixel, p.col);
         have_pixel = false;
       }
     }

@@ -87,6 +87,7 @@ __global__ __launch_bounds__(256, RT_SHADE_WAVES) void k_wf_shade(DevScene S, De
   uint32_t* next_count = Q.counters + 8u * (depth + 1u);
   uint32_t cnt_shaded = 0;
   WaveQueueWriter wq_shadow = {0u, 0u}, wq_ext = {0u, 0u}, wq_next = {0u, 0u};
+  const CameraBasis cam = camera_basis(U);   // FIRST only
   // wave-uniform loop (every lane of a wave takes part in the queue appends)
   for (uint32_t base_idx = (blockIdx.x * 256u + (threadIdx.x & ~63u)); base_idx < count; base_idx += gridDim.x * 256u) {
     const uint32_t idx = base_idx + (threadIdx.x & 63u);
@@ -100,55 +101,16 @@ __global__ __launch_bounds__(256, RT_SHADE_WAVES) void k_wf_shade(DevScene S, De
     bo.want_shadow = bo.want_extend = bo.nee_valid = bo.ended = false;
     bo.sh_o = bo.sh_d = bo.nee = rt3_splat(0.0f);
     bo.sh_tmax = 0.0f;
-    PathState p;
-    p.col = rt3_splat(0.0f);
-    p.sample = 0u;
+    PathState p = idle_path();
     p.pixel = id % npx;
-    p.tri = p.inst = p.depth = p.rng = 0u;
-    p.hit_t = p.prev_pdf = 0.0f;
-    p.specular = true;
-    p.ro = p.rd = p.throughput = p.radiance = p.normal = p.geom_n = p.albedo = rt3_splat(0.0f);
-    p.tex_uv = rt2_make(0.0f, 0.0f);
     if (live) {
     if (FIRST) {
       const uint32_t x = p.pixel % U.width, y = p.pixel / U.width;
-      if (!owns_row(F, y)) live = false;
-      const DevFrameSlot slot = slots[id / npx];
-      p.rng = init_rng(p.pixel, slot.frame_count);  // SPP == 1: frame_count * SPP + 0
-      rt3 cam_o = rt3_make(U.camera.origin[0], U.camera.origin[1], U.camera.origin[2]);
-      rt3 off = rt3_splat(0.0f);
-      const float lens = U.camera.origin[3];
-      if (lens > 0.0f) {
-        float r = rt_sqrt(rand_pcg(p.rng));
-        float theta = RT_TWO_PI * rand_pcg(p.rng);
-        float st, ct;
-        rt_sincos(theta, &st, &ct);
-        rt3 rdk = lens * rt3_make(r * ct, r * st, 0.0f);
-        rt3 cu = rt3_make(U.camera.u[0], U.camera.u[1], U.camera.u[2]);
-        rt3 cv = rt3_make(U.camera.v[0], U.camera.v[1], U.camera.v[2]);
-        off = cu * rdk.x + cv * rdk.y;
-      }
-      rt3 cam_ll = rt3_make(U.camera.lower_left[0], U.camera.lower_left[1], U.camera.lower_left[2]);
-      rt3 cam_h = rt3_make(U.camera.horizontal[0], U.camera.horizontal[1], U.camera.horizontal[2]);
-      rt3 cam_v = rt3_make(U.camera.vertical[0], U.camera.vertical[1], U.camera.vertical[2]);
-      float u = ((float)x + 0.5f + slot.jitter_x * (float)U.width) / (float)U.width;
-      float v = 1.0f - ((float)y + 0.5f + slot.jitter_y * (float)U.height) / (float)U.height;
-      p.rd = cam_ll + u * cam_h + v * cam_v - cam_o - off;
-      p.ro = cam_o + off;
-      p.throughput = rt3_splat(1.0f);
-      p.radiance = rt3_splat(0.0f);
-      p.prev_pdf = 0.0f;
-      p.specular = true;
-      p.depth = 0u;
-      if (live && (slot.depth[p.pixel] >= 1.0f || F.max_depth == 0u)) {  // background (or MAX_DEPTH = 0): black sample
+      if (!owns_row(F, y)) {
+        live = false;
+      } else if (!start_sample(S, F, U, cam, slots[id / npx], x, y, p)) {  // SPP == 1: p.sample = 0
         F.frame_col[id] = make_float4(0.0f, 0.0f, 0.0f, 1.0f);
         live = false;
-      }
-      if (live) {
-        float4 g = slot.normal_id[p.pixel];
-        p.tri = rt_f2u(g.z);
-        p.inst = rt_f2u(g.w);
-        setup_surface(S, p, true, g.x, g.y, slot.albedo[p.pixel]);
       }
     } else {
       const WfPath* const rec = W.p[depth & 1u] + idx;   // the path's record sits at its position in this depth's list

@@ -11,7 +11,8 @@
 //   k_traverse.hip.h          the wave-level TLAS / BLAS walk (node step + LDS triangle queue) of the persistent kernel
 //   k_pairwalk.hip.h          per-ray state machine of the walk over pair records (plain C++: also run on the host by the tests)
 //   k_pairtrav.hip.h          its wave-level side: quad-cooperative record fetch, LDS stack, batched entry, triangle flush
-//   k_pathtrace.hip.h         Raytracer.wgsl `main` + ray_color (:607-819): k_pathtrace, k_pathtrace_persistent
+//   k_pathtrace.hip.h         Raytracer.wgsl `main` + ray_color (:607-819) as a per-path state machine (start_sample,
+//                             shade_bounce, ...) and its drivers k_pathtrace (one pixel per lane), k_pathtrace_persistent
 //   k_wavefront.hip.h         the same bounce as shade / trace stages over device queues (large scenes)
 //   k_texture_post.hip.h      k_resize_texture; k_postprocess = PostProcess.wgsl `main` (:103-176)
 //   k_validate.hip.h          k_validate_scene: every index the kernels follow, checked once per upload

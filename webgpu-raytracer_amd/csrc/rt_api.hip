@@ -1900,9 +1900,9 @@ static int compute_frames(rt_ctx* c, const uint32_t* frame_counts, uint32_t n, u
     ev = next_events(c, RT_TIMER_PATHTRACE);
     if (ev) HIP_TRY(c, hipEventRecord(ev->a, c->stream));
     if (c->detailed_counters)
-      hipLaunchKernelGGL(rtk::k_pathtrace<true>, dim3(tiles), dim3(64), 0, c->stream, S, F, c->uniforms);
+      hipLaunchKernelGGL(rtk::k_pathtrace<true>, dim3(tiles), dim3(64), 0, c->stream, S, F, c->uniforms, dslots);
     else
-      hipLaunchKernelGGL(rtk::k_pathtrace<false>, dim3(tiles), dim3(64), 0, c->stream, S, F, c->uniforms);
+      hipLaunchKernelGGL(rtk::k_pathtrace<false>, dim3(tiles), dim3(64), 0, c->stream, S, F, c->uniforms, dslots);
     if (ev) HIP_TRY(c, hipEventRecord(ev->b, c->stream));
   } else {
     // persistent kernel: grid = resident workgroups, tiles handed out through a ticket counter
