@@ -1875,7 +1875,9 @@ static int compute_frames(rt_ctx* c, const uint32_t* frame_counts, uint32_t n, u
   // 1. primary visibility (the reference clears + rasterises the G-buffer every compute()); frame = blockIdx.y
   EventPair* ev = next_events(c, RT_TIMER_PRIMARY);
   if (ev) HIP_TRY(c, hipEventRecord(ev->a, c->stream));
-  {
+  // ptiles == 0: tile-aligned stripes and a rank that owns no tile row (fewer tile rows than ranks) - nothing to cast, and a
+  // grid of x-size 0 is an invalid launch configuration
+  if (ptiles) {
     const size_t plds = rtk::primary_lds_slots(c->n_nodes, c->n_tris, c->n_instances, c->n_verts) * 16;
     const uint32_t nn = c->n_nodes, nt = c->n_tris, ni = c->n_instances, nv = c->n_verts;
     if (plds <= 32 * 1024 && !c->no_lds_staging) {  // small scene: records staged in LDS, four tiles per workgroup
