@@ -380,7 +380,8 @@ __device__ __forceinline__ uint32_t trav_stage_mixed(TravMem& M, f4* lds, uint32
 #ifndef RT_PT_GLOBAL_WAVES
 #define RT_PT_GLOBAL_WAVES 6   // workgroups of 4 waves per CU = waves per SIMD of the global-memory form (tools/SWEEPS.md)
 #endif
-template <bool DETAIL, bool LDS>
+// ONE_INST (LDS form only): the scene's TLAS is a single leaf (k_traverse.hip.h traverse<.., ONE_INST>).
+template <bool DETAIL, bool LDS, bool ONE_INST = false>
 __global__ __launch_bounds__(256, LDS ? RT_PT_LDS_WAVES : RT_PT_GLOBAL_WAVES) void k_pathtrace_persistent(DevScene Sg, DevFrame F, rt_scene_uniforms U,
                                                               uint32_t* __restrict__ ticket, uint32_t n_nodes_total,
                                                               uint32_t n_tris_total, uint32_t n_inst_total,
@@ -559,7 +560,7 @@ __global__ __launch_bounds__(256, LDS ? RT_PT_LDS_WAVES : RT_PT_GLOBAL_WAVES) vo
       float t_;
       int32_t a_, b_;
       bool occluded;
-      traverse<true, DETAIL, MODE>(M, s_scene, WW, U.blas_base_idx, want_shadow, sh_o, sh_d, sh_tmax, t_, a_, b_,
+      traverse<true, DETAIL, MODE, ONE_INST>(M, s_scene, WW, U.blas_base_idx, want_shadow, sh_o, sh_d, sh_tmax, t_, a_, b_,
                                    occluded, cnt_nodes, cnt_tris);
       if (want_shadow) {
         cnt_shadow++;
@@ -576,7 +577,7 @@ __global__ __launch_bounds__(256, LDS ? RT_PT_LDS_WAVES : RT_PT_GLOBAL_WAVES) vo
       float t_;
       int32_t tri_, inst_;
       bool any_;
-      traverse<false, DETAIL, MODE>(M, s_scene, WW, U.blas_base_idx, want_extend, p.ro, p.rd, RT_T_MAX, t_, tri_,
+      traverse<false, DETAIL, MODE, ONE_INST>(M, s_scene, WW, U.blas_base_idx, want_extend, p.ro, p.rd, RT_T_MAX, t_, tri_,
                                     inst_, any_, cnt_nodes, cnt_tris);
       RT_LSTAT(5, want_extend && inst_ >= 0);
       if (want_extend) {

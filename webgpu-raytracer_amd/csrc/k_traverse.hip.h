@@ -290,8 +290,8 @@ __device__ __forceinline__ void trav_enter(const TravMem& M, const f4* lds, cons
 // what a lane does with the node record it fetched (Raytracer.wgsl:462-473, 498-518): slab test against the current
 // bound, successor, leaf bookkeeping.  DEFER: a TLAS-leaf hit only parks the lane as RT_CURR_ENTER (trav_enter does the
 // transform later, for many lanes at once); otherwise the instance is entered on the spot.  Only stepping lanes come here,
-// and a stepping lane has leaf == 0.
-template <bool COUNT, int MODE, bool DEFER>
+// and a stepping lane has leaf == 0.  IN_BLAS: no lane walks the TLAS (traverse<.., ONE_INST> below).
+template <bool COUNT, int MODE, bool DEFER, bool IN_BLAS = false>
 __device__ __forceinline__ void trav_node(const TravMem& M, const f4* lds, const WaveWork& W, Trav& s, f4 lo, f4 hi,
                                           uint32_t& n_nodes) {
   if (COUNT) n_nodes++;
@@ -305,14 +305,15 @@ __device__ __forceinline__ void trav_node(const TravMem& M, const f4* lds, const
   const unsigned long long tm = __builtin_amdgcn_ballot_w64(s.tlas_next == RT_TLAS_NONE);
   const unsigned long long lm = hm & ~im;                                                  // a leaf whose box is hit
   const bool hit_inner = __builtin_amdgcn_inverse_ballot_w64(hm & im);
-  const bool tlas_leaf = __builtin_amdgcn_inverse_ballot_w64(lm & tm);
-  const bool got_leaf = __builtin_amdgcn_inverse_ballot_w64(lm & ~tm);
+  // (IN_BLAS: a constant, not an inverse ballot of a zero mask, which the compiler keeps as a dead exec-mask branch)
+  const bool tlas_leaf = IN_BLAS ? false : __builtin_amdgcn_inverse_ballot_w64(lm & tm);
+  const bool got_leaf = __builtin_amdgcn_inverse_ballot_w64(IN_BLAS ? lm : lm & ~tm);
 #else
   const bool hit = hit_box4(lo, hi, s.inv_d, s.o_inv_d, RT_T_MIN, s.closest);
   const bool inner = (data & RT_NODE_INNER) != 0u;
   const bool leafhit = hit & !inner;
   const bool hit_inner = hit & inner;
-  const bool in_tlas = s.tlas_next == RT_TLAS_NONE;
+  const bool in_tlas = !IN_BLAS && s.tlas_next == RT_TLAS_NONE;
   const bool got_leaf = leafhit & !in_tlas;
   const bool tlas_leaf = leafhit & in_tlas;
 #endif
@@ -339,7 +340,7 @@ __device__ __forceinline__ void trav_node(const TravMem& M, const f4* lds, const
 #define RT_LEAVE_PER_STEP 0
 #endif
 // one node step for every stepping lane; select-based, two branches only
-template <bool COUNT, int MODE>
+template <bool COUNT, int MODE, bool IN_BLAS = false>
 __device__ __forceinline__ void trav_step(const TravMem& M, const f4* lds, const WaveWork& W, Trav& s, uint32_t& n_nodes) {
 #if RT_LEAVE_PER_STEP
   trav_leave(s);
@@ -350,7 +351,7 @@ __device__ __forceinline__ void trav_step(const TravMem& M, const f4* lds, const
   if (trav_stepping(s)) {
     f4 lo, hi;
     trav_fetch_node<MODE>(M, lds, s.curr, lo, hi);
-    trav_node<COUNT, MODE, false>(M, lds, W, s, lo, hi, n_nodes);
+    trav_node<COUNT, MODE, false, IN_BLAS>(M, lds, W, s, lo, hi, n_nodes);
   }
 }
 
@@ -410,11 +411,12 @@ __device__ __forceinline__ void trav_trip_mixed(const TravMem& M, const f4* lds,
 }
 
 // the node steps between two looks at the queues
-template <bool COUNT, int MODE, int STEPS>
+template <bool COUNT, int MODE, int STEPS, bool IN_BLAS = false>
 __device__ __forceinline__ void trav_trip(const TravMem& M, const f4* lds, const WaveWork& W, Trav& s, uint32_t& n_nodes) {
+  static_assert(!IN_BLAS || MODE == RT_TRAV_LDS, "IN_BLAS: LDS mode only");
   if (MODE == RT_TRAV_LDS) {
 #pragma unroll
-    for (int k = 0; k < STEPS; k++) trav_step<COUNT, MODE>(M, lds, W, s, n_nodes);
+    for (int k = 0; k < STEPS; k++) trav_step<COUNT, MODE, IN_BLAS>(M, lds, W, s, n_nodes);
 #if !RT_LEAVE_PER_STEP
     trav_leave(s);   // before the look at the queues, which must see a finished lane as idle
 #endif
@@ -583,8 +585,14 @@ struct NodeWalk {
 #endif
 };
 
-// traverse(): the whole walk of one wave's rays (persistent kernel, one traversal per bounce and ray kind)
-template <bool ANY, bool COUNT, int MODE>
+// traverse(): the whole walk of one wave's rays (persistent kernel, one traversal per bounce and ray kind).
+// ONE_INST (LDS mode): the TLAS is one node, a leaf (rt_api.hip: blas_offset == 1; k_validate_scene refuses an uploaded
+// one-node TLAS that is not a leaf, and the TLAS builder of rt_world_update makes one instance a leaf).  Every walk then starts with that node's test — a hit enters the instance, a miss ends the walk — and
+// never comes back to the TLAS: the leaf's successor is RT_NODE_END (k_treelet_remap), so trav_leave finishes a lane at the
+// end of the BLAS.  That first step runs on its own, and every later one takes the node step without its TLAS half: no
+// instance-entry branch and no transform code in the trip loop, which also leaves the kernel without spills (Cornell
+// 40.0 -> 38.4 ms per image in a same-box A/B).  Per lane the same nodes, tests and counters.
+template <bool ANY, bool COUNT, int MODE, bool ONE_INST = false>
 __device__ __forceinline__ void traverse(const TravMem& M, const f4* lds, const WaveWork& W, uint32_t blas_base, bool active,
                                          rt3 o, rt3 d, float t_max, float& out_t, int32_t& out_tri,
                                          int32_t& out_inst, bool& out_any, uint32_t& n_nodes, uint32_t& n_tris) {
@@ -593,10 +601,12 @@ __device__ __forceinline__ void traverse(const TravMem& M, const f4* lds, const 
 #ifdef RT_LANE_STATS
   s.stat_kind = ANY ? 1u : 3u;
 #endif
+  static_assert(!ONE_INST || MODE == RT_TRAV_LDS, "ONE_INST: LDS mode only");
+  if (ONE_INST) trav_step<COUNT, MODE>(M, lds, W, s, n_nodes);   // node 0: the TLAS leaf
   for (;;) {
     // RT_STEPS_PER_TRIP node steps between two looks at the triangle queue: the look (ballots, population counts, the
     // branch) costs a third of a trip; a lane that reaches a leaf in an earlier step simply sits out the later ones
-    trav_trip<COUNT, MODE, RT_STEPS_PER_TRIP>(M, lds, W, s, n_nodes);
+    trav_trip<COUNT, MODE, RT_STEPS_PER_TRIP, ONE_INST>(M, lds, W, s, n_nodes);
     if (!tri_flush<NodeWalk<ANY, COUNT, MODE>>(M, lds, W, s, n_tris)) break;
   }
   out_t = s.closest;

@@ -128,7 +128,7 @@ struct rt_ctx {
   int variant = 3;        // 3 = auto (default): persistent kernel for LDS-resident scenes, wavefront for larger ones;
                           // 0 = one-pixel-per-lane megakernel, 1 = persistent kernel, 2 = wavefront
   int num_cus = 256;      // multiProcessorCount of the device
-  int occ_blocks[4] = {0, 0, 0, 0};   // cached occupancy query per persistent-kernel variant
+  int occ_blocks[6] = {0, 0, 0, 0, 0, 0};   // cached occupancy query per persistent-kernel variant
   int wf_occ_blocks[2] = {0, 0};      // ... and for the two wavefront trace kernels
   size_t wf_occ_dyn = (size_t)-1;
   int wf_occ_detail = -1, wf_occ_block = 0, wf_occ_walk = -1, wf_occ_rayreg = -1;   // walk: 0 node, 1 pair
@@ -140,7 +140,7 @@ struct rt_ctx {
   long treelet_cap = -1;
   int treelet_order = 2;          // order of tnodes: 0 = by visit probability, 1 = the bridge's depth-first order, 2 = auto (MI355RT_TREELET_ORDER)
   bool nodes_from_device = false; // the node array was made by rt_world_update (an animated world), not uploaded
-  size_t occ_dyn[4] = {0, 0, 0, 0};
+  size_t occ_dyn[6] = {0, 0, 0, 0, 0, 0};
   DeviceBuffer ticket;    // tile ticket counter of the persistent kernel
   DeviceBuffer slots;     // DevFrameSlot table of the current (batched) dispatch
   // pinned staging ring for the slot tables: the H2D copy of a dispatch's table is truly asynchronous and its source
@@ -1917,11 +1917,16 @@ static int compute_frames(rt_ctx* c, const uint32_t* frame_counts, uint32_t n, u
     // a scene that does not fit as a whole: six 256-thread workgroups per CU (6 waves / SIMD), each with its share of the
     // CU's LDS for the top of the tree
     if (!fits_lds) plan = plan_lds(c, c->lds_per_cu / 6, (size_t)4 * RT_WORK_BYTES_PER_WAVE, &dyn);
-    const int vi = (c->detailed_counters ? 2 : 0) + (fits_lds ? 1 : 0);
-    static const void* const fns[4] = {(const void*)rtk::k_pathtrace_persistent<false, false>,
+    // LDS form of a scene whose TLAS is one node, which is a leaf (k_validate_scene, or the world update's builder): the walks skip the TLAS
+    // half of the node step (k_traverse.hip.h traverse<.., ONE_INST>)
+    const bool one_inst = fits_lds && c->blas_offset == 1;
+    const int vi = one_inst ? (c->detailed_counters ? 5 : 4) : (c->detailed_counters ? 2 : 0) + (fits_lds ? 1 : 0);
+    static const void* const fns[6] = {(const void*)rtk::k_pathtrace_persistent<false, false>,
                                        (const void*)rtk::k_pathtrace_persistent<false, true>,
                                        (const void*)rtk::k_pathtrace_persistent<true, false>,
-                                       (const void*)rtk::k_pathtrace_persistent<true, true>};
+                                       (const void*)rtk::k_pathtrace_persistent<true, true>,
+                                       (const void*)rtk::k_pathtrace_persistent<false, true, true>,
+                                       (const void*)rtk::k_pathtrace_persistent<true, true, true>};
     const void* fn = fns[vi];
     // resident workgroups per CU: queried once per (variant, LDS size)
     if (c->occ_dyn[vi] != dyn || c->occ_blocks[vi] == 0) {
