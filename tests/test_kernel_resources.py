@@ -1,0 +1,50 @@
+"""Register budget of the headline kernel.  The one-leaf-TLAS LDS form of the persistent path tracer
+(k_pathtrace_persistent<false, true, true>, csrc/k_pathtrace.hip.h) runs at RT_PT_ONE_INST_WAVES = 5 waves per SIMD, which
+leaves it 96 VGPRs; a spill there costs more than the fifth wave gains.  This compiles the library's
+device code for gfx950 with the product flags and reads the compiler's resource report: 0 VGPR spills, 0 scratch and an
+occupancy of at least 5 waves per SIMD.  No GPU needed; skipped where hipcc is absent."""
+import os
+import re
+import subprocess
+
+import pytest
+
+import webgpu_raytracer_amd as W
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(REPO, "webgpu-raytracer_amd", "csrc")
+PRODUCT_ONE_LEAF = "_ZN3rtk22k_pathtrace_persistentILb0ELb1ELb1E"
+
+
+def resource_report(tmp_path):
+    """{mangled kernel name: {remark key: value}} of every kernel of rt_api.hip (device code only)."""
+    hipcc = W._build.HIPCC
+    if not os.path.exists(hipcc):
+        pytest.skip("hipcc not found at %s" % hipcc)
+    flags = [f for f in W._build.HIP_FLAGS if f not in ("-shared", "-fPIC")]
+    cmd = [hipcc] + flags + ["--cuda-device-only", "-c", "-Rpass-analysis=kernel-resource-usage", "-I", W._build.INCLUDE,
+                             "-o", str(tmp_path / "rt_api.o"), os.path.join(CSRC, "rt_api.hip")]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-4000:]
+    kernels, cur = {}, None
+    for line in r.stderr.splitlines():
+        m = re.search(r"remark:\s+(.*?) \[-Rpass", line)
+        if not m:
+            continue
+        text = m.group(1).strip()
+        if text.startswith("Function Name:"):
+            cur = kernels.setdefault(text.split(":", 1)[1].strip(), {})
+        elif cur is not None and ":" in text:
+            k, v = text.split(":", 1)
+            cur[k.strip()] = v.strip()
+    return kernels
+
+
+def test_one_leaf_product_kernel_fits_five_waves(tmp_path):
+    kernels = resource_report(tmp_path)
+    names = [n for n in kernels if n.startswith(PRODUCT_ONE_LEAF)]
+    assert len(names) == 1, sorted(kernels)
+    res = kernels[names[0]]
+    assert int(res["VGPRs Spill"]) == 0, res
+    assert int(res["ScratchSize [bytes/lane]"]) == 0, res
+    assert int(res["Occupancy [waves/SIMD]"]) >= 5, res

@@ -373,16 +373,44 @@ __device__ __forceinline__ uint32_t trav_stage_mixed(TravMem& M, f4* lds, uint32
 }
 
 // Occupancy: the LDS-resident form is latency bound at 4 waves/SIMD (registers), the global-memory form gains ~11 %
-// from 6 waves/SIMD even with the spills that costs (measured on MI355X).
+// from 6 waves/SIMD even with the spills that costs (measured on MI355X).  The one-leaf-TLAS LDS form (ONE_INST, product
+// build) fits 96 VGPRs without spills (LEAN below, tests/test_kernel_resources.py) and runs at 5 waves/SIMD: Cornell
+// 38.6 -> 34.0 ms per image.  Five is also the LDS ceiling of Cornell (about 29.5 KB per workgroup); a
+// one-leaf scene that stages more gets fewer workgroups from the host's occupancy query.  Its counting build stays at 4.
 #ifndef RT_PT_LDS_WAVES
 #define RT_PT_LDS_WAVES 4      // waves per SIMD of the LDS-resident form (128 VGPRs)
 #endif
 #ifndef RT_PT_GLOBAL_WAVES
 #define RT_PT_GLOBAL_WAVES 6   // workgroups of 4 waves per CU = waves per SIMD of the global-memory form (tools/SWEEPS.md)
 #endif
+#ifndef RT_PT_ONE_INST_WAVES
+#define RT_PT_ONE_INST_WAVES 5 // waves per SIMD of the one-leaf-TLAS LDS form, product build (96 VGPRs)
+#endif
+// a wave-uniform value taken as new at this point: nothing computed from it is hoisted out of the loop it is used in
+__device__ __forceinline__ uint32_t rt_fresh(uint32_t v) {
+  asm volatile("" : "+s"(v));
+  return v;
+}
+__device__ __forceinline__ rt_scene_uniforms fresh_size(const rt_scene_uniforms& U) {
+  rt_scene_uniforms u = U;
+  u.width = rt_fresh(U.width);
+  u.height = rt_fresh(U.height);
+  return u;
+}
+__device__ __forceinline__ DevFrame fresh_stripes(const DevFrame& F) {
+  DevFrame f = F;
+  f.stripe_rows = rt_fresh(F.stripe_rows);
+  f.stripe_count = rt_fresh(F.stripe_count);
+  return f;
+}
+__device__ __forceinline__ DevFrame fresh_spp(const DevFrame& F) {
+  DevFrame f = F;
+  f.spp = rt_fresh(F.spp);
+  return f;
+}
 // ONE_INST (LDS form only): the scene's TLAS is a single leaf (k_traverse.hip.h traverse<.., ONE_INST>).
 template <bool DETAIL, bool LDS, bool ONE_INST = false>
-__global__ __launch_bounds__(256, LDS ? RT_PT_LDS_WAVES : RT_PT_GLOBAL_WAVES) void k_pathtrace_persistent(DevScene Sg, DevFrame F, rt_scene_uniforms U,
+__global__ __launch_bounds__(256, LDS ? ((ONE_INST && !DETAIL) ? RT_PT_ONE_INST_WAVES : RT_PT_LDS_WAVES) : RT_PT_GLOBAL_WAVES) void k_pathtrace_persistent(DevScene Sg, DevFrame F, rt_scene_uniforms U,
                                                               uint32_t* __restrict__ ticket, uint32_t n_nodes_total,
                                                               uint32_t n_tris_total, uint32_t n_inst_total,
                                                               uint32_t n_verts_total,
@@ -393,11 +421,18 @@ __global__ __launch_bounds__(256, LDS ? RT_PT_LDS_WAVES : RT_PT_GLOBAL_WAVES) vo
   // persistent waves stay fed and balanced even when a rank owns 1/8 of the image. With n_slots > 1 every item
   // writes its frame colour to F.frame_col and k_accumulate_frames adds the frames in frame order afterwards, which
   // makes the result bit-identical to n_slots separate dispatches; with n_slots == 1 the item accumulates directly.
+  // LEAN: the one-leaf form runs at RT_PT_ONE_INST_WAVES = 5 waves per SIMD, 96 VGPRs (the other forms keep their code).
+  // The wave-uniform ticket is read into a scalar register, and the sizes the trip divides by are taken as new values where
+  // they are used (rt_fresh), so that the compiler does not compute their conversions and reciprocals once before the loop
+  // and carry them, wave-uniform, in a dozen VGPRs through the whole kernel.
+  constexpr bool LEAN = ONE_INST;
   extern __shared__ f4 s_scene[];
   // per-wave triangle work queue at the start of LDS, staged scene after it
+  // (LEAN: the wave's index in a scalar register, and so the addresses of its queue)
+  const uint32_t wave = LEAN ? __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) : threadIdx.x >> 6;
   WaveWork WW;
   {
-    wave_work_at(WW, reinterpret_cast<char*>(s_scene) + (threadIdx.x >> 6) * RT_WORK_BYTES_PER_WAVE);
+    wave_work_at(WW, reinterpret_cast<char*>(s_scene) + wave * RT_WORK_BYTES_PER_WAVE);
   }
   const uint32_t rec0 = (4 * RT_WORK_BYTES_PER_WAVE) / 16;   // first slot behind the wave queues
   TravMem M;
@@ -410,6 +445,7 @@ __global__ __launch_bounds__(256, LDS ? RT_PT_LDS_WAVES : RT_PT_GLOBAL_WAVES) vo
       f4* base = s_scene + slot;
       lds_stage(base, src, n);
       slot += (uint32_t)n;
+      if (LEAN) slot = __builtin_amdgcn_readfirstlane(slot);   // else the compiler carries the LDS addresses of S in VGPRs
       return base;
     };
     M.gnodes = M.gtri = M.ginst = nullptr;
@@ -482,7 +518,7 @@ __global__ __launch_bounds__(256, LDS ? RT_PT_LDS_WAVES : RT_PT_GLOBAL_WAVES) vo
           const int leader = __builtin_ctzll(mask);
           uint32_t t = 0;
           if (lane == (uint32_t)leader) t = atomicAdd(ticket, 1u);
-          t = __shfl(t, leader, 64);
+          t = LEAN ? __builtin_amdgcn_readlane(t, leader) : __shfl(t, leader, 64);
           if (t >= n_tiles * n_slots) {
             work_left = false;
             break;
@@ -504,7 +540,7 @@ __global__ __launch_bounds__(256, LDS ? RT_PT_LDS_WAVES : RT_PT_GLOBAL_WAVES) vo
           const uint32_t x = tile_x0 + (slot & 7u);
           const uint32_t y = tile_y0 + (slot >> 3);
           need = false;
-          if (x < U.width && y < U.height && owns_row(F, y)) {
+          if (x < U.width && y < U.height && (LEAN ? owns_row(fresh_stripes(F), y) : owns_row(F, y))) {
             have_pixel = true;
             p.pixel = y * U.width + x;
             pixel_xy = x | (y << 16);   // width, height <= 65535: rt_resize refuses more
@@ -521,7 +557,7 @@ __global__ __launch_bounds__(256, LDS ? RT_PT_LDS_WAVES : RT_PT_GLOBAL_WAVES) vo
     if (!alive && have_pixel) {
       const uint32_t x = pixel_xy & 0xffffu, y = pixel_xy >> 16;
       const DevFrameSlot slot = slots[item_slot];
-      alive = start_sample(S, F, U, cam, slot, x, y, p);
+      alive = LEAN ? start_sample(S, F, fresh_size(U), cam, slot, x, y, p) : start_sample(S, F, U, cam, slot, x, y, p);
     }
     const bool running = alive;
     bool path_done = have_pixel && !alive;  // background sample ends immediately
@@ -539,7 +575,7 @@ __global__ __launch_bounds__(256, LDS ? RT_PT_LDS_WAVES : RT_PT_GLOBAL_WAVES) vo
     if (running) {
       if (DETAIL) cnt_shaded++;
       BounceOut bo;
-      shade_bounce(S, U.light_count, F.max_depth, p, bo);
+      shade_bounce(S, LEAN ? rt_fresh(U.light_count) : U.light_count, LEAN ? rt_fresh(F.max_depth) : F.max_depth, p, bo);
       want_shadow = bo.want_shadow;
       want_extend = bo.want_extend;
       nee_valid = bo.nee_valid;
@@ -604,8 +640,12 @@ __global__ __launch_bounds__(256, LDS ? RT_PT_LDS_WAVES : RT_PT_GLOBAL_WAVES) vo
       alive = false;
       p.col = p.col + p.radiance;
       p.sample++;
-      if (p.sample >= F.spp) {  // the item's last sample
-        finish_pixel(F, U, slots, item_slot, p.pixel, p.col);
+      if (p.sample >= (LEAN ? rt_fresh(F.spp) : F.spp)) {  // the item's last sample
+        if (LEAN) {
+          finish_pixel(fresh_spp(F), U, slots, item_slot, p.pixel, p.col);
+        } else {
+          finish_pixel(F, U, slots, item_slot, p.pixel, p.col);
+        }
         have_pixel = false;
       }
     }
@@ -641,7 +681,7 @@ __global__ __launch_bounds__(256, LDS ? RT_PT_LDS_WAVES : RT_PT_GLOBAL_WAVES) vo
   c.nodes = cnt_nodes;
   c.tris = cnt_tris;
   c.shaded = cnt_shaded;
-  flush_counters<DETAIL>(c, F.counters, blockIdx.x * 4u + (threadIdx.x >> 6));
+  flush_counters<DETAIL>(c, F.counters, blockIdx.x * 4u + wave);
 }
 
 }  // namespace rtk

@@ -235,11 +235,15 @@ __device__ __forceinline__ void trav_begin(Trav& s, bool active, uint32_t blas_b
 }
 
 // the walk ran off its array: leave the instance (back to the world-space ray and the TLAS cursor), or finish.  Behind a
-// wave-uniform test (one compare and a branch per step when nobody is at an end).
+// wave-uniform test (one compare and a branch per step when nobody is at an end).  IN_BLAS (traverse<.., ONE_INST>): the
+// TLAS leaf has no successor, so no lane ever leaves and a lane at an end finishes; written out, because the compiler cannot
+// tell that tlas_next is RT_NODE_END and would keep the world-space ray and tlas_next live through the whole walk for the
+// restore (20 of the 61 spills the one-leaf persistent kernel had at 96 VGPRs).
+template <bool IN_BLAS = false>
 __device__ __forceinline__ void trav_leave(Trav& s) {
   const bool at_end = s.curr == RT_CURR_END;
   if (__builtin_amdgcn_ballot_w64(at_end) != 0ull) {
-    const bool leave = at_end & (s.tlas_next < RT_TLAS_NONE);   // inside an instance whose TLAS leaf has a successor
+    const bool leave = !IN_BLAS && (at_end & (s.tlas_next < RT_TLAS_NONE));   // inside an instance whose TLAS leaf has a successor
     // the six selects that restore the ray sit behind a second wave-uniform test (as a per-lane branch the compiler
     // predicates them: nine moves whenever some lane is at an end, which in a one-instance scene is never a way back)
     if (__builtin_amdgcn_ballot_w64(leave) != 0ull) {
@@ -343,7 +347,7 @@ __device__ __forceinline__ void trav_node(const TravMem& M, const f4* lds, const
 template <bool COUNT, int MODE, bool IN_BLAS = false>
 __device__ __forceinline__ void trav_step(const TravMem& M, const f4* lds, const WaveWork& W, Trav& s, uint32_t& n_nodes) {
 #if RT_LEAVE_PER_STEP
-  trav_leave(s);
+  trav_leave<IN_BLAS>(s);
 #endif
 #ifdef RT_LANE_STATS
   RT_LSTAT(s.stat_kind, trav_stepping(s));
@@ -418,7 +422,7 @@ __device__ __forceinline__ void trav_trip(const TravMem& M, const f4* lds, const
 #pragma unroll
     for (int k = 0; k < STEPS; k++) trav_step<COUNT, MODE, IN_BLAS>(M, lds, W, s, n_nodes);
 #if !RT_LEAVE_PER_STEP
-    trav_leave(s);   // before the look at the queues, which must see a finished lane as idle
+    trav_leave<IN_BLAS>(s);   // before the look at the queues, which must see a finished lane as idle
 #endif
   } else {
     trav_trip_mixed<COUNT, MODE, STEPS>(M, lds, W, s, n_nodes);
@@ -611,8 +615,15 @@ __device__ __forceinline__ void traverse(const TravMem& M, const f4* lds, const 
   }
   out_t = s.closest;
   out_tri = s.best_tri;
-  out_inst = s.best_inst;
   out_any = trav_any(s);
+  if (ONE_INST) {
+    // every hit is in the one instance: read its index back from the TLAS leaf (node 0) instead of carrying cur_inst
+    // through the walk
+    const uint32_t inst0 = rt_f2u(ld_l(lds, M.l_nodes + 1u).w) >> 3;
+    out_inst = (!ANY && out_any) ? (int32_t)inst0 : -1;
+  } else {
+    out_inst = s.best_inst;
+  }
 }
 
 }  // namespace rtk
