@@ -10,12 +10,14 @@ N > 1    : `python bench.py --gpus N` starts its own N ranks (one process per GP
            anything in this process touches the GPU); under a launcher (WORLD_SIZE set) it is one of the ranks.
            The image is split into interleaved 8-row stripes across ranks (strong scaling of one image), one RCCL
            gather of the ranks' compact stripes (1/N of the float4 accumulation buffer each) to rank 0 per image.
-Extra    : "roofline" for the dominant kernel (k_pathtrace_persistent; launch time from HIP events inside the C
-           library, on the stream the kernel runs on), "configs" (BASELINE configs 3-5, timed the same way,
-           with the roofline of their dominant kernel k_wf_trace) and "cpu_baseline" (the CPU oracle timed on a
-           bounded row-interleaved sample of the same workload, rank 0 at N = 1 only).
-Fields that cannot be measured from inside this process (PMC counters) are read from profiles/ and every such field
-carries its "source".
+Plain run: sets up, warms up, times the steps, writes --dump-outputs and prints the headline line; nothing else.
+--full   : also "roofline" for the dominant kernel (k_pathtrace_persistent; launch time from HIP events inside the C
+           library, on the stream the kernel runs on, and one extra untimed image with the detailed counters),
+           "configs" (BASELINE configs 3-5, timed the same way, with the roofline of their dominant kernel k_wf_trace),
+           "live_loop", "live_loop_animated", "world_update" and "cpu_baseline" (the CPU oracle timed on a bounded
+           row-interleaved sample of the same workload, rank 0 at N = 1 only); the --no-* options leave parts of it out.
+           Fields that cannot be measured from inside this process (PMC counters) are read from profiles/ and every such
+           field carries its "source".
 Outputs  : `--dump-outputs DIR` writes what the last timed image computed, as rank 0 holds it after the gather, once the
            timed steps are over: DIR/accum.npy, the float4 accumulation image (1080 x 1920 x 4 float32, the same as
            readAccum()), and DIR/frame_sample.npy, the RGBA8 output of present() (captureFrame()) at a fixed sample of a
@@ -58,10 +60,14 @@ def parse_args():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra-configs", action="store_true", help="skip the lines of BASELINE configs 3-5")
-    ap.add_argument("--no-live-loop", action="store_true", help="skip the per-frame compute(); present() block")
-    ap.add_argument("--no-world-update", action="store_true", help="skip the World::update(t) block (host / GPU builder / device-resident)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure the roofline, BASELINE configs 3-5, the live loop, the world "
+                         "update and the CPU baseline (the --no-* options below leave parts of it out)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extra-configs", action="store_true", help="with --full: skip the lines of BASELINE configs 3-5")
+    ap.add_argument("--no-live-loop", action="store_true", help="with --full: skip the per-frame compute(); present() block")
+    ap.add_argument("--no-world-update", action="store_true",
+                    help="with --full: skip the World::update(t) block (host / GPU builder / device-resident)")
     ap.add_argument("--batch", type=int, default=32,
                     help="frames per batched dispatch (the recorder batches up to 50 compute() calls; 1 = one dispatch per frame)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
@@ -294,9 +300,10 @@ def main():
         dist.all_reduce(rsum, op=dist.ReduceOp.SUM)
         return float(tmax.item()), float(rsum.item())
 
-    def run_workload(scene, frames, depth, steps, warmup, batch, width=WIDTH, height=HEIGHT, capture=False):
+    def run_workload(scene, frames, depth, steps, warmup, batch, width=WIDTH, height=HEIGHT, capture=False, detail=True):
         """Time `steps` images of one scene on all ranks; returns the renderer, the sharding and the measurements.
-        capture: rank 0 also returns the last timed image's outputs (accumulation image, presented RGBA8 frame)."""
+        capture: rank 0 also returns the last timed image's outputs (accumulation image, presented RGBA8 frame).
+        detail: afterwards, render one untimed image with the detailed counters (kc, for the roofline; None without)."""
         bridge = pkg.WorldBridge()
         if scene == "viewer_diamond":
             bridge.loadScene("viewer", DIAMOND_OBJ)
@@ -344,12 +351,14 @@ def main():
         outputs = (shard.read_image(), r.captureFrame()["data"].copy()) if capture and rank == 0 else None
         # one extra untimed image with the detailed-counter kernel variant: algorithmic bytes of the path-trace stage
         # (the counts are deterministic, so they equal the timed launches')
-        r.setCounting(True)
-        r.resetCounters()
-        shard.render(frames, batch=batch)
-        r.sync()
-        kc = r.getKernelCounters(1)
-        r.setCounting(False)
+        kc = None
+        if detail:
+            r.setCounting(True)
+            r.resetCounters()
+            shard.render(frames, batch=batch)
+            r.sync()
+            kc = r.getKernelCounters(1)
+            r.setCounting(False)
         return {"bridge": bridge, "renderer": r, "shard": shard, "elapsed": elapsed, "rays": rays_total,
                 "ktimes": ktimes, "kc": kc, "steps": steps, "collective_ms": coll_ms / coll_n if coll_n else None,
                 "unpack_ms": unpack_ms / unpack_n if unpack_n else None, "render_ms": render_ms,
@@ -537,11 +546,12 @@ def main():
         return res
 
     frames = list(range(1, SPP_TOTAL + 1))
-    head = run_workload(SCENE, frames, DEPTH, args.steps, args.warmup, args.batch, capture=bool(args.dump_outputs))
+    head = run_workload(SCENE, frames, DEPTH, args.steps, args.warmup, args.batch, capture=bool(args.dump_outputs),
+                        detail=args.full)
     if head["outputs"] is not None:
         dump_outputs(args.dump_outputs, *head["outputs"])
     extra = []
-    if not args.no_extra_configs:
+    if args.full and not args.no_extra_configs:
         for name, scene, nframes, depth, images, cw, ch in EXTRA_CONFIGS:
             m = run_workload(scene, list(range(1, nframes + 1)), depth, images, 1, args.batch, cw, ch)
             m["renderer"].destroy()      # the 4K batch holds 63 GB of path state, queues and G-buffers
@@ -549,93 +559,95 @@ def main():
             extra.append((name, scene, nframes, depth, m, cw, ch))
 
     if rank == 0:
-        ref = pmc_reference()
-        n_launch = (len(frames) + args.batch - 1) // args.batch   # path-trace launches per image
-        owned_px = int(head["shard"].owned_rows(HEIGHT).sum()) * WIDTH
-        kt, kc = head["ktimes"], head["kc"]
-        launch_ms = kt["pathtrace"]["ms"] / max(1, kt["pathtrace"]["launches"])
-        gather_bytes = (32.0 * kc["nodes_visited"] + 64.0 * kc["tris_tested"] + 344.0 * kc["shaded_hits"]) / n_launch
-        stream_bytes = (32.0 + 24.0 * min(args.batch, len(frames))) * owned_px  # accumulation read+write per launch, G-buffer read per frame
-        alg_gather = gather_bytes / (launch_ms * 1e-3) / 1e9 if launch_ms > 0 else 0.0
-        pt = ref.get("k_pathtrace_persistent", {}) if world == 1 else {}
-        src = ref.get("source")
-        roof = {"kernel": "k_pathtrace_persistent", "bound": "valu", "unit": "T lane-instr/s",
-                "peak": round(VALU_PEAK_TLANE, 2),
-                "peak_note": "f32 VALU spec: 256 CUs x 4 SIMDs x 32 lanes/clk x 2.4 GHz (157.3 TFLOP/s / 2 flop per FMA)",
-                "avg_launch_ms": round(launch_ms, 4), "launches": kt["pathtrace"]["launches"],
-                "avg_primary_ms": round(kt["primary"]["ms"] / max(1, kt["primary"]["launches"]), 4),
-                "frames_per_launch": min(args.batch, len(frames)),
-                "alg_gather_GBps": round(alg_gather, 1), "alg_gather_bytes_per_launch": int(gather_bytes),
-                "alg_gather_served_by": "lds (the 8.4 KB scene is staged per workgroup; SURVEY 8d gather bytes never reach HBM)",
-                "alg_hbm_bytes_per_launch": int(stream_bytes),
-                "achieved": None, "frac": None, "traffic": None}
-        stale = bool(ref.get("_stale"))
-        if ref and world == 1:
-            roof["pmc_stale"] = stale
-            roof["pmc_csrc_sha16"] = {"collected_from": ref.get("csrc_sha16"), "this_build": pkg._build.kernel_source_hash()}
-        if stale:
-            roof["pmc_stale_note"] = ("profiles/pmc_reference.json was collected from other kernel sources than this build's: "
-                                      "achieved / frac / traffic (counter-derived) are withheld; re-run tools/make_profiles_round.sh")
-        if pt.get("lane_instr_per_launch") and launch_ms > 0 and not stale:
-            scale = min(args.batch, len(frames)) / float(pt.get("frames_per_launch", 32))
-            lane = pt["lane_instr_per_launch"] * scale
-            roof["achieved"] = round(lane / (launch_ms * 1e-3) / 1e12, 3)
-            roof["frac"] = round(roof["achieved"] / VALU_PEAK_TLANE, 4)
-            roof["lane_instr_per_launch"] = {"value": lane, "source": src}
-            for k in ("valu_lane_utilization", "effective_clock_GHz", "measured_issue_peak_Tlane", "insts_valu_per_launch",
-                      "insts_salu_per_launch", "frac_of_wave_cycles_active_inst_any", "frac_of_wave_cycles_wait_any",
-                      "frac_of_wave_cycles_wait_inst_any", "lds_bank_conflict_frac_of_lds_cycles"):
-                if k in pt:
-                    roof[k] = {"value": pt[k], "source": src}
-            if pt.get("measured_issue_peak_Tlane"):
-                roof["frac_of_measured_issue_peak"] = round(roof["achieved"] / pt["measured_issue_peak_Tlane"], 4)
-            if "valu_busy_per_simd" in pt:
-                roof["valu_busy_per_simd"] = {"value": pt["valu_busy_per_simd"], "note": pt.get("valu_busy_note"), "source": src}
-            # `achieved` counts the vector lane-instructions the kernel EXECUTES for its rays, so a round that removes
-            # instructions lowers it while the image gets faster.  The same rays cost round 3's build 656.4 G lane-instructions
-            # per 32-frame launch (profiles/r03_cornell_pmc.json); that stream over this build's launch time is the
-            # like-for-like figure.
-            try:
-                r3 = json.load(open(os.path.join(REPO, "profiles", "r03_cornell_pmc.json")))
-                r3k = [v for k, v in r3.items() if "k_pathtrace_persistent" in k][0]
-                r3_lane = float(r3k["SQ_THREAD_CYCLES_VALU"]) * scale
-                roof["same_rays_comparison"] = {
-                    "r03_lane_instr_per_launch": r3_lane, "r03_insts_valu_per_launch": float(r3k["SQ_INSTS_VALU"]) * scale,
-                    "r03_insts_salu_per_launch": float(r3k["SQ_INSTS_SALU"]) * scale,
-                    "this_build_over_r03_lane_instr": round(lane / r3_lane, 4),
-                    "frac_at_r03_instruction_stream": round(r3_lane / (launch_ms * 1e-3) / 1e12 / VALU_PEAK_TLANE, 4),
-                    "note": "round 3: 0.369 at 22.63 ms per launch; the rays, their hits and every counter of the image are unchanged",
-                    "source": "profiles/r03_cornell_pmc.json (SQ_THREAD_CYCLES_VALU) / this run's launch time"}
-            except (OSError, ValueError, KeyError, IndexError):
-                pass
-            ic = issue_calibration()
-            if ic and pt.get("insts_valu_per_launch") and pt.get("insts_salu_per_launch") and pt.get("effective_clock_GHz"):
-                # Round 3 called the kernel "issue-bound at 0.79" against span-derived rates that wall clock does not confirm.
-                # By wall clock (tools/issue_peak.hip, >= 10 ms launches) a SIMD with 4 resident waves issues 0.40 independent
-                # v_add_f32 per cycle, 0.23 s_add_u32 (the scalar unit is shared by the CU's four SIMDs: 0.25), and of a
-                # 3 : 1 vector : scalar stream - this kernel's mix - what the "3 v_add : 1 s_add" rows say.
-                scale_i = scale
-                valu = pt["insts_valu_per_launch"] * scale_i
-                salu = pt["insts_salu_per_launch"] * scale_i
-                lds = pt.get("insts_lds_per_launch", 0.0) * scale_i
-                simd_cycles = launch_ms * 1e-3 * pt["effective_clock_GHz"] * 1e9 * 256 * 4
-                mix = ic.get("3 v_add : 1 s_add (mixed)", {}).get(4)
-                roof["issue"] = {"waves_per_simd": 4,
-                                 "valu_instr_per_cycle_per_simd": round(valu / simd_cycles, 4),
-                                 "salu_instr_per_cycle_per_simd": round(salu / simd_cycles, 4),
-                                 "all_instr_per_cycle_per_simd": round((valu + salu + lds) / simd_cycles, 4),
-                                 "wall_clock_peak_valu_only": ic.get("v_add_f32", {}).get(4),
-                                 "wall_clock_peak_salu_only": ic.get("s_add_u32", {}).get(4),
-                                 "wall_clock_peak_3to1_mix": mix,
-                                 "valu_frac_of_wall_clock_valu_peak": round(valu / simd_cycles / ic["v_add_f32"][4], 4) if ic.get("v_add_f32", {}).get(4) else None,
-                                 "all_frac_of_wall_clock_3to1_peak": round((valu + salu + lds) / simd_cycles / mix, 4) if mix else None,
-                                 "source": "instruction counts: " + str(src) + "; issue rates: profiles/r04_issue_peak.txt (tools/issue_peak.hip, wall-clock column)"}
-            if pt.get("hbm_bytes_per_launch"):
-                tb = pt["hbm_bytes_per_launch"] * scale
-                roof["traffic"] = tb
-                roof["traffic_source"] = src
-                roof["hbm_GBps"] = round(tb / (launch_ms * 1e-3) / 1e9, 1)
-                roof["hbm_frac"] = round(roof["hbm_GBps"] / HBM_PEAK_GBS, 4)
+        ref = pmc_reference() if args.full else {}
+        roof = None
+        if args.full:
+            n_launch = (len(frames) + args.batch - 1) // args.batch   # path-trace launches per image
+            owned_px = int(head["shard"].owned_rows(HEIGHT).sum()) * WIDTH
+            kt, kc = head["ktimes"], head["kc"]
+            launch_ms = kt["pathtrace"]["ms"] / max(1, kt["pathtrace"]["launches"])
+            gather_bytes = (32.0 * kc["nodes_visited"] + 64.0 * kc["tris_tested"] + 344.0 * kc["shaded_hits"]) / n_launch
+            stream_bytes = (32.0 + 24.0 * min(args.batch, len(frames))) * owned_px  # accumulation read+write per launch, G-buffer read per frame
+            alg_gather = gather_bytes / (launch_ms * 1e-3) / 1e9 if launch_ms > 0 else 0.0
+            pt = ref.get("k_pathtrace_persistent", {}) if world == 1 else {}
+            src = ref.get("source")
+            roof = {"kernel": "k_pathtrace_persistent", "bound": "valu", "unit": "T lane-instr/s",
+                    "peak": round(VALU_PEAK_TLANE, 2),
+                    "peak_note": "f32 VALU spec: 256 CUs x 4 SIMDs x 32 lanes/clk x 2.4 GHz (157.3 TFLOP/s / 2 flop per FMA)",
+                    "avg_launch_ms": round(launch_ms, 4), "launches": kt["pathtrace"]["launches"],
+                    "avg_primary_ms": round(kt["primary"]["ms"] / max(1, kt["primary"]["launches"]), 4),
+                    "frames_per_launch": min(args.batch, len(frames)),
+                    "alg_gather_GBps": round(alg_gather, 1), "alg_gather_bytes_per_launch": int(gather_bytes),
+                    "alg_gather_served_by": "lds (the 8.4 KB scene is staged per workgroup; SURVEY 8d gather bytes never reach HBM)",
+                    "alg_hbm_bytes_per_launch": int(stream_bytes),
+                    "achieved": None, "frac": None, "traffic": None}
+            stale = bool(ref.get("_stale"))
+            if ref and world == 1:
+                roof["pmc_stale"] = stale
+                roof["pmc_csrc_sha16"] = {"collected_from": ref.get("csrc_sha16"), "this_build": pkg._build.kernel_source_hash()}
+            if stale:
+                roof["pmc_stale_note"] = ("profiles/pmc_reference.json was collected from other kernel sources than this build's: "
+                                          "achieved / frac / traffic (counter-derived) are withheld; re-run tools/make_profiles_round.sh")
+            if pt.get("lane_instr_per_launch") and launch_ms > 0 and not stale:
+                scale = min(args.batch, len(frames)) / float(pt.get("frames_per_launch", 32))
+                lane = pt["lane_instr_per_launch"] * scale
+                roof["achieved"] = round(lane / (launch_ms * 1e-3) / 1e12, 3)
+                roof["frac"] = round(roof["achieved"] / VALU_PEAK_TLANE, 4)
+                roof["lane_instr_per_launch"] = {"value": lane, "source": src}
+                for k in ("valu_lane_utilization", "effective_clock_GHz", "measured_issue_peak_Tlane", "insts_valu_per_launch",
+                          "insts_salu_per_launch", "frac_of_wave_cycles_active_inst_any", "frac_of_wave_cycles_wait_any",
+                          "frac_of_wave_cycles_wait_inst_any", "lds_bank_conflict_frac_of_lds_cycles"):
+                    if k in pt:
+                        roof[k] = {"value": pt[k], "source": src}
+                if pt.get("measured_issue_peak_Tlane"):
+                    roof["frac_of_measured_issue_peak"] = round(roof["achieved"] / pt["measured_issue_peak_Tlane"], 4)
+                if "valu_busy_per_simd" in pt:
+                    roof["valu_busy_per_simd"] = {"value": pt["valu_busy_per_simd"], "note": pt.get("valu_busy_note"), "source": src}
+                # `achieved` counts the vector lane-instructions the kernel EXECUTES for its rays, so a round that removes
+                # instructions lowers it while the image gets faster.  The same rays cost round 3's build 656.4 G lane-instructions
+                # per 32-frame launch (profiles/r03_cornell_pmc.json); that stream over this build's launch time is the
+                # like-for-like figure.
+                try:
+                    r3 = json.load(open(os.path.join(REPO, "profiles", "r03_cornell_pmc.json")))
+                    r3k = [v for k, v in r3.items() if "k_pathtrace_persistent" in k][0]
+                    r3_lane = float(r3k["SQ_THREAD_CYCLES_VALU"]) * scale
+                    roof["same_rays_comparison"] = {
+                        "r03_lane_instr_per_launch": r3_lane, "r03_insts_valu_per_launch": float(r3k["SQ_INSTS_VALU"]) * scale,
+                        "r03_insts_salu_per_launch": float(r3k["SQ_INSTS_SALU"]) * scale,
+                        "this_build_over_r03_lane_instr": round(lane / r3_lane, 4),
+                        "frac_at_r03_instruction_stream": round(r3_lane / (launch_ms * 1e-3) / 1e12 / VALU_PEAK_TLANE, 4),
+                        "note": "round 3: 0.369 at 22.63 ms per launch; the rays, their hits and every counter of the image are unchanged",
+                        "source": "profiles/r03_cornell_pmc.json (SQ_THREAD_CYCLES_VALU) / this run's launch time"}
+                except (OSError, ValueError, KeyError, IndexError):
+                    pass
+                ic = issue_calibration()
+                if ic and pt.get("insts_valu_per_launch") and pt.get("insts_salu_per_launch") and pt.get("effective_clock_GHz"):
+                    # Round 3 called the kernel "issue-bound at 0.79" against span-derived rates that wall clock does not confirm.
+                    # By wall clock (tools/issue_peak.hip, >= 10 ms launches) a SIMD with 4 resident waves issues 0.40 independent
+                    # v_add_f32 per cycle, 0.23 s_add_u32 (the scalar unit is shared by the CU's four SIMDs: 0.25), and of a
+                    # 3 : 1 vector : scalar stream - this kernel's mix - what the "3 v_add : 1 s_add" rows say.
+                    scale_i = scale
+                    valu = pt["insts_valu_per_launch"] * scale_i
+                    salu = pt["insts_salu_per_launch"] * scale_i
+                    lds = pt.get("insts_lds_per_launch", 0.0) * scale_i
+                    simd_cycles = launch_ms * 1e-3 * pt["effective_clock_GHz"] * 1e9 * 256 * 4
+                    mix = ic.get("3 v_add : 1 s_add (mixed)", {}).get(4)
+                    roof["issue"] = {"waves_per_simd": 4,
+                                     "valu_instr_per_cycle_per_simd": round(valu / simd_cycles, 4),
+                                     "salu_instr_per_cycle_per_simd": round(salu / simd_cycles, 4),
+                                     "all_instr_per_cycle_per_simd": round((valu + salu + lds) / simd_cycles, 4),
+                                     "wall_clock_peak_valu_only": ic.get("v_add_f32", {}).get(4),
+                                     "wall_clock_peak_salu_only": ic.get("s_add_u32", {}).get(4),
+                                     "wall_clock_peak_3to1_mix": mix,
+                                     "valu_frac_of_wall_clock_valu_peak": round(valu / simd_cycles / ic["v_add_f32"][4], 4) if ic.get("v_add_f32", {}).get(4) else None,
+                                     "all_frac_of_wall_clock_3to1_peak": round((valu + salu + lds) / simd_cycles / mix, 4) if mix else None,
+                                     "source": "instruction counts: " + str(src) + "; issue rates: profiles/r04_issue_peak.txt (tools/issue_peak.hip, wall-clock column)"}
+                if pt.get("hbm_bytes_per_launch"):
+                    tb = pt["hbm_bytes_per_launch"] * scale
+                    roof["traffic"] = tb
+                    roof["traffic_source"] = src
+                    roof["hbm_GBps"] = round(tb / (launch_ms * 1e-3) / 1e9, 1)
+                    roof["hbm_frac"] = round(roof["hbm_GBps"] / HBM_PEAK_GBS, 4)
         out = {
             "metric": "Mrays/s (primary+secondary) at 1920x1080 SPP=64 depth=8",
             "value": round(head["rays"] / head["elapsed"] / 1e6, 2),
@@ -654,8 +666,9 @@ def main():
                        "scene": SCENE, "width": WIDTH, "height": HEIGHT, "spp": SPP_TOTAL, "max_depth": DEPTH,
                        "parallelism": "%d-row stripes x %d ranks + 1 RCCL gather of compact stripes/image" % (rtdist.STRIPE_ROWS, world) if world > 1 else "1 GPU",
                        "frames_per_dispatch": args.batch, "rays_per_image": int(head["rays"] / args.steps)},
-            "roofline": roof,
         }
+        if roof is not None:
+            out["roofline"] = roof
         if distributed:
             # pack + gather + unpack on rank 0's stream, per image (events around the collective section)
             out["collective_ms"] = round(head["collective_ms"], 4) if head["collective_ms"] is not None else None
@@ -719,7 +732,7 @@ def main():
             cfgs.append(entry)
         if cfgs:
             out["configs"] = cfgs
-        if world == 1 and not args.no_live_loop:
+        if args.full and world == 1 and not args.no_live_loop:
             # the reference's hot loop as it is written: per-frame dispatch + present, beside the batched cadence
             ll = []
             batched = {SCENE: out["ms_per_step"] / SPP_TOTAL}
@@ -755,9 +768,9 @@ def main():
             out["live_loop"] = ll
             if not args.no_world_update:
                 out["live_loop_animated"] = [animated_live_loop("tube"), animated_live_loop("hall")]
-        if world == 1 and not args.no_world_update:
+        if args.full and world == 1 and not args.no_world_update:
             out["world_update"] = world_update_block()
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(pkg, head["bridge"], frames)
         print(json.dumps(out), flush=True)
     if distributed:

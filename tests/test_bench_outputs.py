@@ -76,3 +76,22 @@ def test_dumped_outputs_are_the_headline_image(W, tmp_path):
     px = bench.WIDTH * bench.HEIGHT
     pick = np.sort(np.random.default_rng(bench.DUMP_SAMPLE_SEED).choice(px, px // 4, replace=False))
     assert np.array_equal(got["frame_sample"], frame.reshape(px, 4)[pick].astype(np.float32))
+
+
+@pytest.mark.gpu
+def test_a_plain_run_prints_the_headline_alone(W):
+    """Without --full the benchmark times the headline and prints its line; the roofline, the other configs, the live
+    loop, the world update and the CPU baseline come with --full only."""
+    W._build.build_rt()
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        env.pop(k, None)
+    out = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "1", "--warmup", "0"],
+                         env=env, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, out.stdout
+    rec = json.loads(lines[0])
+    assert rec["unit"] == "Mrays/s" and rec["value"] > 0 and rec["higher_is_better"] is True and rec["dtype"] == "f32"
+    assert rec["steps"] == 1 and rec["warmup"] == 0 and rec["ms_per_step"] > 0
+    assert not {"roofline", "configs", "live_loop", "live_loop_animated", "world_update", "cpu_baseline"} & set(rec)

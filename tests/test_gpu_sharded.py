@@ -136,7 +136,7 @@ def test_bench_py_gpus_2_from_a_plain_shell(W):
     rec = json.loads(lines[0])
     assert rec["n_gpus"] == 2 and rec["steps"] == 2 and rec["unit"] == "Mrays/s" and rec["value"] > 0
     # every ray of the image is traced exactly once across the ranks: same count as one GPU (deterministic)
-    one = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "0",
+    one = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "0", "--full",
                           "--no-extra-configs", "--no-cpu-baseline", "--no-live-loop", "--no-world-update"], env=env, capture_output=True, text=True, timeout=600)
     assert one.returncode == 0, one.stderr[-3000:]
     rec1 = json.loads([l for l in one.stdout.splitlines() if l.startswith("{")][0])
