@@ -263,6 +263,10 @@ int rt_debug_trace_sections(rt_ctx* ctx, uint64_t* out16, int reset);
 /* Diagnostic build (-DRT_PT_STAMPS) only: the same for k_pathtrace_persistent: out8[0..4] = cycles in {regenerate + start,
  * shade, shadow traversal, extension traversal + surface frame, finish}, [5] trips, [6] waves. */
 int rt_debug_pt_sections(rt_ctx* ctx, uint64_t* out8, int reset);
+/* Shape of the last launch of the persistent path-trace kernel: out4 = {threads per workgroup (256, or 512 for the wide
+ * one-leaf form), workgroups, dynamic LDS bytes per workgroup, resident workgroups per CU from the occupancy query}.  All
+ * zero before the first such launch. */
+int rt_debug_pt_launch(rt_ctx* ctx, uint32_t* out4);
 /* Diagnostic build (-DRT_LANE_STATS) only: lane utilisation of the parts of a trip of k_pathtrace_persistent:
  * out32[2 k] = times part k ran (wave level), out32[2 k + 1] = active lanes summed; k = 0 shade, 1 / 2 node step / triangle
  * chunk of the shadow walk, 3 / 4 of the extension walk, 5 surface frame of a new hit, 6 start of a sample, 7 end of a sample.

@@ -377,6 +377,11 @@ __device__ __forceinline__ uint32_t trav_stage_mixed(TravMem& M, f4* lds, uint32
 // build) fits 96 VGPRs without spills (LEAN below, tests/test_kernel_resources.py) and runs at 5 waves/SIMD: Cornell
 // 38.6 -> 34.0 ms per image.  Five is also the LDS ceiling of Cornell (about 29.5 KB per workgroup); a
 // one-leaf scene that stages more gets fewer workgroups from the host's occupancy query.  Its counting build stays at 4.
+// Where three 512-thread workgroups fit the CU's LDS (Cornell: about 52 KB each, one staged scene per eight waves), the
+// host runs the same product form of a batched dispatch as k_pathtrace_persistent_wide at RT_PT_WIDE_WAVES = 6 waves per
+// SIMD.  At 80 VGPRs it still
+// spills (64 B/lane of scratch, SLIM in k_pathtrace_persistent.hip.h, tests/test_kernel_resources_wide.py) and is faster
+// all the same: Cornell 34.02 -> 33.15 ms per image.
 #ifndef RT_PT_LDS_WAVES
 #define RT_PT_LDS_WAVES 4      // waves per SIMD of the LDS-resident form (128 VGPRs)
 #endif
@@ -386,6 +391,10 @@ __device__ __forceinline__ uint32_t trav_stage_mixed(TravMem& M, f4* lds, uint32
 #ifndef RT_PT_ONE_INST_WAVES
 #define RT_PT_ONE_INST_WAVES 5 // waves per SIMD of the one-leaf-TLAS LDS form, product build (96 VGPRs)
 #endif
+#ifndef RT_PT_WIDE_WAVES
+#define RT_PT_WIDE_WAVES 6     // waves per SIMD of the same form in 512-thread workgroups (80 VGPRs)
+#endif
+#define RT_PT_COL_BYTES_PER_WAVE (64 * 12)   // the wide form's parked sample sums (rt_api.hip sizes its LDS with it)
 // a wave-uniform value taken as new at this point: nothing computed from it is hoisted out of the loop it is used in
 __device__ __forceinline__ uint32_t rt_fresh(uint32_t v) {
   asm volatile("" : "+s"(v));
@@ -408,281 +417,46 @@ __device__ __forceinline__ DevFrame fresh_spp(const DevFrame& F) {
   f.spp = rt_fresh(F.spp);
   return f;
 }
-// ONE_INST (LDS form only): the scene's TLAS is a single leaf (k_traverse.hip.h traverse<.., ONE_INST>).
-template <bool DETAIL, bool LDS, bool ONE_INST = false>
-__global__ __launch_bounds__(256, LDS ? ((ONE_INST && !DETAIL) ? RT_PT_ONE_INST_WAVES : RT_PT_LDS_WAVES) : RT_PT_GLOBAL_WAVES) void k_pathtrace_persistent(DevScene Sg, DevFrame F, rt_scene_uniforms U,
-                                                              uint32_t* __restrict__ ticket, uint32_t n_nodes_total,
-                                                              uint32_t n_tris_total, uint32_t n_inst_total,
-                                                              uint32_t n_verts_total,
-                                                              const DevFrameSlot* __restrict__ slots, uint32_t n_slots,
-                                                              LdsPlan plan) {
-  // Batched dispatch (rt_compute_batch): the launch covers n_slots consecutive compute() frames. The work item is
-  // one (frame, pixel): tickets enumerate (frame, tile) pairs, so a launch has n_slots times as many tickets and the
-  // persistent waves stay fed and balanced even when a rank owns 1/8 of the image. With n_slots > 1 every item
-  // writes its frame colour to F.frame_col and k_accumulate_frames adds the frames in frame order afterwards, which
-  // makes the result bit-identical to n_slots separate dispatches; with n_slots == 1 the item accumulates directly.
-  // LEAN: the one-leaf form runs at RT_PT_ONE_INST_WAVES = 5 waves per SIMD, 96 VGPRs (the other forms keep their code).
-  // The wave-uniform ticket is read into a scalar register, and the sizes the trip divides by are taken as new values where
-  // they are used (rt_fresh), so that the compiler does not compute their conversions and reciprocals once before the loop
-  // and carry them, wave-uniform, in a dozen VGPRs through the whole kernel.
-  constexpr bool LEAN = ONE_INST;
-  extern __shared__ f4 s_scene[];
-  // per-wave triangle work queue at the start of LDS, staged scene after it
-  // (LEAN: the wave's index in a scalar register, and so the addresses of its queue)
-  const uint32_t wave = LEAN ? __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) : threadIdx.x >> 6;
-  WaveWork WW;
-  {
-    wave_work_at(WW, reinterpret_cast<char*>(s_scene) + wave * RT_WORK_BYTES_PER_WAVE);
-  }
-  const uint32_t rec0 = (4 * RT_WORK_BYTES_PER_WAVE) / 16;   // first slot behind the wave queues
-  TravMem M;
-  DevScene S = Sg;
-  if (LDS) {
-    // Small scene: the whole scene (traversal records AND the arrays shading reads) lives in LDS,
-    // staged once per workgroup; only textures, the G-buffer and the accumulation buffer stay in HBM.
-    uint32_t slot = rec0;
-    auto stage = [&](const void* src, size_t n) {
-      f4* base = s_scene + slot;
-      lds_stage(base, src, n);
-      slot += (uint32_t)n;
-      if (LEAN) slot = __builtin_amdgcn_readfirstlane(slot);   // else the compiler carries the LDS addresses of S in VGPRs
-      return base;
-    };
-    M.gnodes = M.gtri = M.ginst = nullptr;
-    M.groot = nullptr;
-    M.k_lds = n_nodes_total;
-    M.l_nodes = slot;
-    f4* ln = stage(Sg.tnodes, (size_t)2 * n_nodes_total);
-    M.l_tri = slot;
-    f4* lt = stage(Sg.tri_geom, (size_t)RT_TRI_STRIDE * n_tris_total);
-    M.l_inst = slot;
-    f4* li = stage(Sg.inst_trav, (size_t)4 * n_inst_total);
-    M.l_root = slot;
-    stage(Sg.inst_root, ((size_t)n_inst_total + 3) / 4);
-    S.tri_shade = reinterpret_cast<const float4*>(stage(Sg.tri_shade, (size_t)8 * n_tris_total));
-    S.topo = reinterpret_cast<const float4*>(stage(Sg.topo, (size_t)5 * n_tris_total));
-    S.pos = reinterpret_cast<const float4*>(stage(Sg.pos, n_verts_total));   // S.nrm stays in global memory: no reader left here
-    // uv (8 B/vertex) and lights (8 B each): the device buffers are allocated with >= 16-byte slack
-    S.uv = reinterpret_cast<const float2*>(stage(Sg.uv, ((size_t)n_verts_total + 1) / 2));
-    S.inst = reinterpret_cast<const float4*>(stage(Sg.inst, (size_t)9 * n_inst_total));
-    S.lights = reinterpret_cast<const uint2*>(stage(Sg.lights, ((size_t)Sg.n_lights + 1) / 2));
-    S.light_rec = reinterpret_cast<const float4*>(stage(Sg.light_rec, (size_t)4 * Sg.n_lights));
-    __syncthreads();
-    S.tnodes = reinterpret_cast<const float4*>(ln);
-    S.tri_geom = reinterpret_cast<const float4*>(lt);
-    S.inst_trav = reinterpret_cast<const float4*>(li);
-  } else {
-    trav_stage_mixed(M, s_scene, rec0, Sg, plan, n_tris_total, n_inst_total);
-    __syncthreads();
-  }
-  constexpr int MODE = LDS ? RT_TRAV_LDS : RT_TRAV_MIXED;
-
-#ifdef RT_CLOCK_STAMP
-  const unsigned long long stamp_c0 = __builtin_amdgcn_s_memtime(), stamp_r0 = __builtin_amdgcn_s_memrealtime();
-#endif
-  const uint32_t lane = threadIdx.x & 63u;
-  const uint32_t tiles_x = (U.width + 7u) / 8u;
-  // tickets enumerate only the tile rows this rank owns when the stripes are tile-aligned
-  const uint32_t n_tiles = tiles_x * (F.own_period ? F.own_tile_rows : (U.height + 7u) / 8u);
-  const CameraBasis cam = camera_basis(U);
-
-  // wave-uniform work cursor: pixels [tile_pos, 64) of the wave's tile are still unassigned; the tile's origin and frame are
-  // worked out once per ticket (two divisions by run-time values, 20 instructions each: not once per regenerated lane)
-  uint32_t tile_pos = 64u, tile_x0 = 0u, tile_y0 = 0u, tile_slot = 0u;
-  bool work_left = true;
-
-  PathState p = idle_path();
-  uint32_t item_slot = 0u;  // frame of the batch the lane's current (frame, pixel) item belongs to
-  uint32_t pixel_xy = 0u;   // x | y << 16 of p.pixel
-  bool alive = false;       // lane owns a running path
-  bool have_pixel = false;  // lane owns a pixel whose samples are not all done
-  uint32_t cnt_ext = 0, cnt_shadow = 0, cnt_nodes = 0, cnt_tris = 0, cnt_shaded = 0;
-
-#ifdef RT_PT_STAMPS
-  unsigned long long pt_cyc[5] = {0, 0, 0, 0, 0}, pt_trips = 0;
-#endif
-  for (;;) {
-#ifdef RT_PT_STAMPS
-    const unsigned long long ps0 = __builtin_amdgcn_s_memtime();
-#endif
-    // ------------------------------------------------------------ regenerate
-    // (a) wave-wide: every lane without a pixel takes the next unassigned one of the wave's tile.
-    //     All lanes execute this loop (busy lanes with need = false) so that the wave-uniform cursor
-    //     (tile, tile_pos, work_left) stays identical in every lane.
-    {
-      bool need = !alive && !have_pixel;
-      for (;;) {
-        const unsigned long long mask = __ballot(need);
-        if (mask == 0ull || !work_left) break;
-        if (tile_pos >= 64u) {
-          const int leader = __builtin_ctzll(mask);
-          uint32_t t = 0;
-          if (lane == (uint32_t)leader) t = atomicAdd(ticket, 1u);
-          t = LEAN ? __builtin_amdgcn_readlane(t, leader) : __shfl(t, leader, 64);
-          if (t >= n_tiles * n_slots) {
-            work_left = false;
-            break;
-          }
-          // frame-major ticket: frame = t / n_tiles, tile = t % n_tiles
-          tile_slot = t / n_tiles;
-          const uint32_t tile_in_frame = t - tile_slot * n_tiles;
-          uint32_t trow = tile_in_frame / tiles_x;
-          tile_x0 = (tile_in_frame - trow * tiles_x) * 8u;
-          if (F.own_period) trow = (trow / F.own_run) * F.own_period + F.own_first + (trow % F.own_run);
-          tile_y0 = trow * 8u;
-          tile_pos = 0u;
-        }
-        // rank of this lane among the needy lanes
-        const uint32_t rank =
-            __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-        const uint32_t slot = tile_pos + rank;
-        if (need && slot < 64u) {
-          const uint32_t x = tile_x0 + (slot & 7u);
-          const uint32_t y = tile_y0 + (slot >> 3);
-          need = false;
-          if (x < U.width && y < U.height && (LEAN ? owns_row(fresh_stripes(F), y) : owns_row(F, y))) {
-            have_pixel = true;
-            p.pixel = y * U.width + x;
-            pixel_xy = x | (y << 16);   // width, height <= 65535: rt_resize refuses more
-            p.sample = 0u;
-            item_slot = tile_slot;
-            p.col = rt3_splat(0.0f);
-          }
-        }
-        tile_pos += (uint32_t)__builtin_popcountll(mask);
-      }
-    }
-    // (b) start the next sample of the owned pixel: camera ray + depth-0 surface from the G-buffer
-    RT_LSTAT(6, !alive && have_pixel);
-    if (!alive && have_pixel) {
-      const uint32_t x = pixel_xy & 0xffffu, y = pixel_xy >> 16;
-      const DevFrameSlot slot = slots[item_slot];
-      alive = LEAN ? start_sample(S, F, fresh_size(U), cam, slot, x, y, p) : start_sample(S, F, U, cam, slot, x, y, p);
-    }
-    const bool running = alive;
-    bool path_done = have_pixel && !alive;  // background sample ends immediately
-
-#ifdef RT_PT_STAMPS
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    const unsigned long long ps1 = __builtin_amdgcn_s_memtime();
-#endif
-    // ------------------------------------------------------------ shade one bounce
-    bool want_shadow = false, want_extend = false;
-    bool nee_valid = false;
-    rt3 sh_o = rt3_splat(0.0f), sh_d = rt3_splat(0.0f), nee = rt3_splat(0.0f);
-    float sh_tmax = 0.0f;
-    RT_LSTAT(0, running);
-    if (running) {
-      if (DETAIL) cnt_shaded++;
-      BounceOut bo;
-      shade_bounce(S, LEAN ? rt_fresh(U.light_count) : U.light_count, LEAN ? rt_fresh(F.max_depth) : F.max_depth, p, bo);
-      want_shadow = bo.want_shadow;
-      want_extend = bo.want_extend;
-      nee_valid = bo.nee_valid;
-      sh_o = bo.sh_o;
-      sh_d = bo.sh_d;
-      sh_tmax = bo.sh_tmax;
-      nee = bo.nee;
-      const bool ended = bo.ended;
-      if (ended) path_done = true;
-    }
-
-#ifdef RT_PT_STAMPS
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    const unsigned long long ps2 = __builtin_amdgcn_s_memtime();
-#endif
-    // ------------------------------------------------------------ shadow rays (any hit)
-    if (__ballot(want_shadow) != 0ull) {
-      float t_;
-      int32_t a_, b_;
-      bool occluded;
-      traverse<true, DETAIL, MODE, ONE_INST>(M, s_scene, WW, U.blas_base_idx, want_shadow, sh_o, sh_d, sh_tmax, t_, a_, b_,
-                                   occluded, cnt_nodes, cnt_tris);
-      if (want_shadow) {
-        cnt_shadow++;
-        if (!occluded && nee_valid) p.radiance = p.radiance + nee;  // nothing is added when bsdf_pdf <= 0
-      }
-    }
-
-#ifdef RT_PT_STAMPS
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    const unsigned long long ps3 = __builtin_amdgcn_s_memtime();
-#endif
-    // ------------------------------------------------------------ extension rays (closest hit)
-    if (__ballot(want_extend) != 0ull) {
-      float t_;
-      int32_t tri_, inst_;
-      bool any_;
-      traverse<false, DETAIL, MODE, ONE_INST>(M, s_scene, WW, U.blas_base_idx, want_extend, p.ro, p.rd, RT_T_MAX, t_, tri_,
-                                    inst_, any_, cnt_nodes, cnt_tris);
-      RT_LSTAT(5, want_extend && inst_ >= 0);
-      if (want_extend) {
-        cnt_ext++;
-        if (inst_ < 0) {
-          path_done = true;
-        } else {
-          p.hit_t = t_;
-          p.tri = (uint32_t)tri_;
-          p.inst = (uint32_t)inst_;
-          setup_surface(S, p, false, 0.0f, 0.0f, 0u);
-          p.depth++;
-        }
-      }
-    }
-
-#ifdef RT_PT_STAMPS
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    const unsigned long long ps4 = __builtin_amdgcn_s_memtime();
-#endif
-    // ------------------------------------------------------------ sample / pixel finished
-    RT_LSTAT(7, path_done);
-    if (path_done) {
-      alive = false;
-      p.col = p.col + p.radiance;
-      p.sample++;
-      if (p.sample >= (LEAN ? rt_fresh(F.spp) : F.spp)) {  // the item's last sample
-        if (LEAN) {
-          finish_pixel(fresh_spp(F), U, slots, item_slot, p.pixel, p.col);
-        } else {
-          finish_pixel(F, U, slots, item_slot, p.pixel, p.col);
-        }
-        have_pixel = false;
-      }
-    }
-#ifdef RT_PT_STAMPS
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    {
-      const unsigned long long ps5 = __builtin_amdgcn_s_memtime();
-      pt_cyc[0] += ps1 - ps0; pt_cyc[1] += ps2 - ps1; pt_cyc[2] += ps3 - ps2; pt_cyc[3] += ps4 - ps3; pt_cyc[4] += ps5 - ps4;
-      pt_trips++;
-    }
-#endif
-    if (!work_left && __ballot(alive || have_pixel) == 0ull) break;
-  }
-#ifdef RT_PT_STAMPS
-  if (lane == 0u) {
-    for (int k = 0; k < 5; k++) atomicAdd(&g_pt_sections[k], pt_cyc[k]);
-    atomicAdd(&g_pt_sections[5], pt_trips);
-    atomicAdd(&g_pt_sections[6], 1ull);
-  }
-#endif
-
-#ifdef RT_CLOCK_STAMP
-  if (threadIdx.x == 0 && blockIdx.x < RT_CLOCK_STAMP_SLOTS) {
-    g_clock_stamps[2 * blockIdx.x] = __builtin_amdgcn_s_memtime() - stamp_c0;
-    g_clock_stamps[2 * blockIdx.x + 1] = __builtin_amdgcn_s_memrealtime() - stamp_r0;
-  }
-#endif
-  // counters: one flush per persistent wave
-  LaneCounters c;
-  c.primary = 0;
-  c.extension = cnt_ext;
-  c.shadow = cnt_shadow;
-  c.nodes = cnt_nodes;
-  c.tris = cnt_tris;
-  c.shaded = cnt_shaded;
-  flush_counters<DETAIL>(c, F.counters, blockIdx.x * 4u + wave);
+// SLIM (k_pathtrace_persistent_wide): the lane's sample sum is parked in LDS behind the WAVES wave queues, in three planes
+// of WAVES * 64 floats (RT_PT_COL_BYTES_PER_WAVE per wave; rt_api.hip sizes the launch's LDS with it)
+template <uint32_t WAVES>
+__device__ __forceinline__ float* col_park_at(f4* lds) {
+  return reinterpret_cast<float*>(reinterpret_cast<char*>(lds) + WAVES * RT_WORK_BYTES_PER_WAVE) + threadIdx.x;
 }
+template <uint32_t WAVES>
+__device__ __forceinline__ void col_park_clear(f4* lds) {
+  float* park = col_park_at<WAVES>(lds);
+  park[0] = park[WAVES * 64] = park[2 * WAVES * 64] = 0.0f;
+}
+template <uint32_t WAVES>
+__device__ __forceinline__ rt3 col_park_add(f4* lds, rt3 radiance) {   // the sum + radiance, parked again and returned
+  float* park = col_park_at<WAVES>(lds);
+  const rt3 col = rt3_make(park[0], park[WAVES * 64], park[2 * WAVES * 64]) + radiance;
+  park[0] = col.x;
+  park[WAVES * 64] = col.y;
+  park[2 * WAVES * 64] = col.z;
+  return col;
+}
+
+// k_pathtrace_persistent: 256-thread workgroups, every form
+#define RT_PT_KERNEL k_pathtrace_persistent
+#define RT_PT_WAVES 4
+#define RT_PT_SIMD_WAVES (LDS ? ((ONE_INST && !DETAIL) ? RT_PT_ONE_INST_WAVES : RT_PT_LDS_WAVES) : RT_PT_GLOBAL_WAVES)
+#include "k_pathtrace_persistent.hip.h"
+#undef RT_PT_KERNEL
+#undef RT_PT_WAVES
+#undef RT_PT_SIMD_WAVES
+
+// k_pathtrace_persistent_wide: the one-leaf-TLAS LDS form of the product build (rt_api.hip instantiates <false, true, true>
+// only) in 512-thread workgroups.  Eight waves share one staged scene, so that three workgroups of a small scene (24 waves,
+// 6 per SIMD) fit the CU's LDS where six 256-thread ones would not.
+#define RT_PT_KERNEL k_pathtrace_persistent_wide
+#define RT_PT_WAVES 8
+#define RT_PT_SIMD_WAVES RT_PT_WIDE_WAVES
+#include "k_pathtrace_persistent.hip.h"
+#undef RT_PT_KERNEL
+#undef RT_PT_WAVES
+#undef RT_PT_SIMD_WAVES
 
 }  // namespace rtk
 #endif

@@ -128,7 +128,7 @@ struct rt_ctx {
   int variant = 3;        // 3 = auto (default): persistent kernel for LDS-resident scenes, wavefront for larger ones;
                           // 0 = one-pixel-per-lane megakernel, 1 = persistent kernel, 2 = wavefront
   int num_cus = 256;      // multiProcessorCount of the device
-  int occ_blocks[6] = {0, 0, 0, 0, 0, 0};   // cached occupancy query per persistent-kernel variant
+  int occ_blocks[7] = {0, 0, 0, 0, 0, 0, 0};   // cached occupancy query per persistent-kernel variant
   int wf_occ_blocks[2] = {0, 0};      // ... and for the two wavefront trace kernels
   size_t wf_occ_dyn = (size_t)-1;
   int wf_occ_detail = -1, wf_occ_block = 0, wf_occ_walk = -1, wf_occ_rayreg = -1;   // walk: 0 node, 1 pair
@@ -140,7 +140,8 @@ struct rt_ctx {
   long treelet_cap = -1;
   int treelet_order = 2;          // order of tnodes: 0 = by visit probability, 1 = the bridge's depth-first order, 2 = auto (MI355RT_TREELET_ORDER)
   bool nodes_from_device = false; // the node array was made by rt_world_update (an animated world), not uploaded
-  size_t occ_dyn[6] = {0, 0, 0, 0, 0, 0};
+  size_t occ_dyn[7] = {0, 0, 0, 0, 0, 0, 0};
+  uint32_t pt_launch[4] = {0, 0, 0, 0};   // last persistent launch: threads, workgroups, dynamic LDS, workgroups per CU
   DeviceBuffer ticket;    // tile ticket counter of the persistent kernel
   DeviceBuffer slots;     // DevFrameSlot table of the current (batched) dispatch
   // pinned staging ring for the slot tables: the H2D copy of a dispatch's table is truly asynchronous and its source
@@ -1920,33 +1921,47 @@ static int compute_frames(rt_ctx* c, const uint32_t* frame_counts, uint32_t n, u
     // LDS form of a scene whose TLAS is one node, which is a leaf (k_validate_scene, or the world update's builder): the walks skip the TLAS
     // half of the node step (k_traverse.hip.h traverse<.., ONE_INST>)
     const bool one_inst = fits_lds && c->blas_offset == 1;
-    const int vi = one_inst ? (c->detailed_counters ? 5 : 4) : (c->detailed_counters ? 2 : 0) + (fits_lds ? 1 : 0);
-    static const void* const fns[6] = {(const void*)rtk::k_pathtrace_persistent<false, false>,
+    // the product build of that form in 512-thread workgroups (k_pathtrace_persistent_wide, 6 waves per SIMD) when three of
+    // them, each with eight wave queues, eight waves' parked sample sums and one copy of the scene, fit the CU's LDS, and the
+    // dispatch carries more than one frame: a single 1080p frame gives its 6 144 waves 1.3 tickets each, and there the
+    // slower waves of the wide form lose more in the tail than the sixth wave gains (Cornell live loop, one dispatch per
+    // frame: 0.906 -> 0.945 ms per frame)
+    const size_t dyn_wide = (size_t)8 * (RT_WORK_BYTES_PER_WAVE + RT_PT_COL_BYTES_PER_WAVE) + scene_lds;
+    const bool wide = one_inst && !c->detailed_counters && n > 1 && dyn_wide <= c->lds_per_cu / 3;
+    if (wide) dyn = dyn_wide;
+    const int vi = wide ? 6 : one_inst ? (c->detailed_counters ? 5 : 4) : (c->detailed_counters ? 2 : 0) + (fits_lds ? 1 : 0);
+    const uint32_t waves = wide ? 8u : 4u;   // per workgroup
+    static const void* const fns[7] = {(const void*)rtk::k_pathtrace_persistent<false, false>,
                                        (const void*)rtk::k_pathtrace_persistent<false, true>,
                                        (const void*)rtk::k_pathtrace_persistent<true, false>,
                                        (const void*)rtk::k_pathtrace_persistent<true, true>,
                                        (const void*)rtk::k_pathtrace_persistent<false, true, true>,
-                                       (const void*)rtk::k_pathtrace_persistent<true, true, true>};
+                                       (const void*)rtk::k_pathtrace_persistent<true, true, true>,
+                                       (const void*)rtk::k_pathtrace_persistent_wide<false, true, true>};
     const void* fn = fns[vi];
     // resident workgroups per CU: queried once per (variant, LDS size)
     if (c->occ_dyn[vi] != dyn || c->occ_blocks[vi] == 0) {
       int per_cu = 0;
       HIP_TRY(c, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
-      HIP_TRY(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 256, dyn));
+      HIP_TRY(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, (int)(64 * waves), dyn));
       c->occ_blocks[vi] = per_cu < 1 ? 1 : per_cu;
       c->occ_dyn[vi] = dyn;
     }
     uint32_t blocks = (uint32_t)c->occ_blocks[vi] * (uint32_t)c->num_cus;
     const uint32_t own_tiles = F.own_period ? ((c->width + 7) / 8) * F.own_tile_rows : tiles;
     // as many waves as there are tickets (tiles x frames), up to the resident limit; fewer, longer-lived waves measured worse
-    const uint32_t max_useful = (own_tiles * n + 3) / 4;
+    const uint32_t max_useful = (own_tiles * n + waves - 1) / waves;
     if (blocks > max_useful) blocks = max_useful ? max_useful : 1;
     uint32_t* ticket = (uint32_t*)c->ticket.ptr;
     uint32_t nn = c->n_nodes, nt = c->n_tris, ni = c->n_instances, nv = c->n_verts, ns = n;
     void* args[] = {&S, &F, &c->uniforms, &ticket, &nn, &nt, &ni, &nv, &dslots, &ns, &plan};
     ev = next_events(c, RT_TIMER_PATHTRACE);
     if (ev) HIP_TRY(c, hipEventRecord(ev->a, c->stream));
-    HIP_TRY(c, hipLaunchKernel(fn, dim3(blocks), dim3(256), args, dyn, c->stream));
+    HIP_TRY(c, hipLaunchKernel(fn, dim3(blocks), dim3(64 * waves), args, dyn, c->stream));
+    c->pt_launch[0] = 64 * waves;
+    c->pt_launch[1] = blocks;
+    c->pt_launch[2] = (uint32_t)dyn;
+    c->pt_launch[3] = (uint32_t)c->occ_blocks[vi];
     if (ev) HIP_TRY(c, hipEventRecord(ev->b, c->stream));
     if (n > 1)  // ordered accumulation of the batch's frame colours
       hipLaunchKernelGGL(rtk::k_accumulate_frames, dim3((uint32_t)((npx + 255) / 256)), dim3(256), 0, c->stream, F, dslots,
@@ -2278,6 +2293,11 @@ int rt_debug_pt_sections(rt_ctx* c, uint64_t* out8, int reset) {
 #else
   return 0;
 #endif
+}
+int rt_debug_pt_launch(rt_ctx* c, uint32_t* out4) {
+  if (!c || !out4) return RT_ERR_INVALID;
+  for (int k = 0; k < 4; k++) out4[k] = c->pt_launch[k];
+  return RT_OK;
 }
 int rt_debug_lane_stats(rt_ctx* c, uint64_t* out32, int reset) {
   if (!c || !out32) return RT_ERR_INVALID;
