@@ -85,7 +85,10 @@ __device__ __forceinline__ CameraBasis camera_basis(const rt_scene_uniforms& U) 
 
 // Start sample p.sample of pixel p.pixel = (x, y) in the frame `slot` (Raytracer.wgsl:798-809, :608-619): seed the RNG,
 // make the camera ray, reset the path and take the depth-0 surface from the frame's G-buffer.  Returns false for a
-// background pixel (or MAX_DEPTH = 0): the sample is black and ends at once.
+// background pixel (or MAX_DEPTH = 0): the sample is black and ends at once.  LIVE: the caller has made that test on the
+// pixel's G-buffer depth already (k_pathtrace_persistent hands out no other pixel); the depth is not read again and the
+// sample always starts.
+template <bool LIVE = false>
 __device__ __forceinline__ bool start_sample(const DevScene& S, const DevFrame& F, const rt_scene_uniforms& U,
                                              const CameraBasis& cam, const DevFrameSlot& slot, uint32_t x, uint32_t y,
                                              PathState& p) {
@@ -112,10 +115,10 @@ __device__ __forceinline__ bool start_sample(const DevScene& S, const DevFrame& 
   p.depth = 0u;
   // the three G-buffer words of the pixel are requested together (they come from HBM: one round trip instead of depth
   // first, then the rest)
-  const float gdepth = slot.depth[p.pixel];
+  const float gdepth = LIVE ? 0.0f : slot.depth[p.pixel];
   const float4 g = slot.normal_id[p.pixel];
   const uint32_t galbedo = slot.albedo[p.pixel];
-  if (!(gdepth >= 1.0f) && F.max_depth != 0u) {
+  if (LIVE || (!(gdepth >= 1.0f) && F.max_depth != 0u)) {
     p.tri = rt_f2u(g.z);
     p.inst = rt_f2u(g.w);
     setup_surface(S, p, true, g.x, g.y, galbedo);
@@ -249,6 +252,14 @@ __device__ __forceinline__ void finish_pixel(const DevFrame& F, const rt_scene_u
     F.accum[pixel] = acc;
   }
 }
+// finish_pixel of a pixel whose samples were all background: their sum is +0 and so is its average, +0 / SPP for every
+// SPP >= 1 (rt_set_pipeline refuses 0), so no division is made
+__device__ __forceinline__ void finish_black_pixel(const DevFrame& F, const rt_scene_uniforms& U, const DevFrameSlot* slots,
+                                                   uint32_t item_slot, uint32_t pixel) {
+  DevFrame f = F;
+  f.spp = 1u;
+  finish_pixel(f, U, slots, item_slot, pixel, rt3_splat(0.0f));
+}
 
 // ======================================================================= path tracer, one pixel per lane
 // Raytracer.wgsl `main` (:791-819) as written: a lane runs its pixel's samples one after another and traces the rays of
@@ -303,7 +314,9 @@ __global__ __launch_bounds__(64) void k_pathtrace(DevScene S, DevFrame F, rt_sce
 //    tiles from a global ticket counter until the image is exhausted (one ray per lane);
 //  * path regeneration: a lane whose path ended (light hit, miss, absorbed, Russian roulette,
 //    depth limit) takes the next pixel of its wave's current tile, found with a ballot/mbcnt prefix
-//    over the idle mask, so the 64 lanes stay busy instead of waiting for the longest path;
+//    over the idle mask, so the 64 lanes stay busy instead of waiting for the longest path; a pixel
+//    whose G-buffer holds background is finished there (colour +0) and the lane takes the next one, so
+//    that no trip carries a lane with nothing to trace;
 //  * per trip every live lane executes exactly one bounce: shade -> (NEE shadow ray) -> scatter ->
 //    (extension ray), so the wave runs the two traversals and the shading code converged;
 //  * traversal data (nodes, triangle records, instance records) is staged once per workgroup in LDS

@@ -95,6 +95,7 @@ __global__ __launch_bounds__(64 * RT_PT_WAVES, RT_PT_SIMD_WAVES) void RT_PT_KERN
   uint32_t pixel_xy = 0u;   // x | y << 16 of p.pixel
   bool alive = false;       // lane owns a running path
   bool have_pixel = false;  // lane owns a pixel whose samples are not all done
+  // cnt_ext, cnt_shadow: rays of the whole wave, wave-uniform (scalar registers); the others count per lane
   uint32_t cnt_ext = 0, cnt_shadow = 0, cnt_nodes = 0, cnt_tris = 0, cnt_shaded = 0;
 
 #ifdef RT_PT_STAMPS
@@ -108,6 +109,12 @@ __global__ __launch_bounds__(64 * RT_PT_WAVES, RT_PT_SIMD_WAVES) void RT_PT_KERN
     // (a) wave-wide: every lane without a pixel takes the next unassigned one of the wave's tile.
     //     All lanes execute this loop (busy lanes with need = false) so that the wave-uniform cursor
     //     (tile, tile_pos, work_left) stays identical in every lane.
+    //     A lane keeps a pixel only if the pixel has a path to trace.  It reads the pixel's G-buffer depth here; a
+    //     background pixel (or every pixel, when MAX_DEPTH = 0: start_sample's test) is finished at once with colour +0,
+    //     and the lane takes the next slot in the same refill instead of sitting out a whole trip; so does a lane whose
+    //     slot is outside the image or the rank's rows.  A background sample draws no random number, traces nothing and
+    //     counts nothing, and +0 summed over the samples is +0, so the pixel gets the bits it got from a lane trip per
+    //     sample.
     {
       bool need = !alive && !have_pixel;
       for (;;) {
@@ -138,33 +145,41 @@ __global__ __launch_bounds__(64 * RT_PT_WAVES, RT_PT_SIMD_WAVES) void RT_PT_KERN
         if (need && slot < 64u) {
           const uint32_t x = tile_x0 + (slot & 7u);
           const uint32_t y = tile_y0 + (slot >> 3);
-          need = false;
           if (x < U.width && y < U.height && (LEAN ? owns_row(fresh_stripes(F), y) : owns_row(F, y))) {
-            have_pixel = true;
-            if constexpr (!SLIM) p.pixel = y * U.width + x;
-            pixel_xy = x | (y << 16);   // width, height <= 65535: rt_resize refuses more
-            p.sample = 0u;
-            item_slot = tile_slot;
-            if constexpr (SLIM) {
-              col_park_clear<WAVES>(s_scene);
+            const uint32_t pixel = y * (LEAN ? rt_fresh(U.width) : U.width) + x;
+            // (LEAN: MAX_DEPTH taken as new here, or its test is carried through the trip as a lane mask in two SGPRs)
+            if (!(slots[tile_slot].depth[pixel] >= 1.0f) && (LEAN ? rt_fresh(F.max_depth) : F.max_depth) != 0u) {
+              need = false;
+              have_pixel = true;
+              if constexpr (!SLIM) p.pixel = y * U.width + x;
+              pixel_xy = x | (y << 16);   // width, height <= 65535: rt_resize refuses more
+              p.sample = 0u;
+              item_slot = tile_slot;
+              if constexpr (SLIM) {
+                col_park_clear<WAVES>(s_scene);
+              } else {
+                p.col = rt3_splat(0.0f);
+              }
             } else {
-              p.col = rt3_splat(0.0f);
+              finish_black_pixel(F, U, slots, tile_slot, pixel);
             }
           }
         }
         tile_pos += (uint32_t)__builtin_popcountll(mask);
       }
     }
-    // (b) start the next sample of the owned pixel: camera ray + depth-0 surface from the G-buffer
+    // (b) start the next sample of the owned pixel: camera ray + depth-0 surface from the G-buffer (the pixel is not
+    //     background: the sample always starts)
     RT_LSTAT(6, !alive && have_pixel);
     if (!alive && have_pixel) {
       const uint32_t x = pixel_xy & 0xffffu, y = pixel_xy >> 16;
       const DevFrameSlot slot = slots[item_slot];
       if constexpr (SLIM) p.pixel = y * rt_fresh(U.width) + x;
-      alive = LEAN ? start_sample(S, F, fresh_size(U), cam, slot, x, y, p) : start_sample(S, F, U, cam, slot, x, y, p);
+      alive = LEAN ? start_sample<true>(S, F, fresh_size(U), cam, slot, x, y, p)
+                   : start_sample<true>(S, F, U, cam, slot, x, y, p);
     }
     const bool running = alive;
-    bool path_done = have_pixel && !alive;  // background sample ends immediately
+    bool path_done = false;
 
 #ifdef RT_PT_STAMPS
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
@@ -196,14 +211,15 @@ __global__ __launch_bounds__(64 * RT_PT_WAVES, RT_PT_SIMD_WAVES) void RT_PT_KERN
     const unsigned long long ps2 = __builtin_amdgcn_s_memtime();
 #endif
     // ------------------------------------------------------------ shadow rays (any hit)
-    if (__ballot(want_shadow) != 0ull) {
+    const unsigned long long shadow_mask = __ballot(want_shadow);
+    if (shadow_mask != 0ull) {
+      cnt_shadow += (uint32_t)__builtin_popcountll(shadow_mask);
       float t_;
       int32_t a_, b_;
       bool occluded;
       traverse<true, DETAIL, MODE, ONE_INST>(M, s_scene, WW, U.blas_base_idx, want_shadow, sh_o, sh_d, sh_tmax, t_, a_, b_,
                                    occluded, cnt_nodes, cnt_tris);
       if (want_shadow) {
-        cnt_shadow++;
         if (!occluded && nee_valid) p.radiance = p.radiance + nee;  // nothing is added when bsdf_pdf <= 0
       }
     }
@@ -213,7 +229,9 @@ __global__ __launch_bounds__(64 * RT_PT_WAVES, RT_PT_SIMD_WAVES) void RT_PT_KERN
     const unsigned long long ps3 = __builtin_amdgcn_s_memtime();
 #endif
     // ------------------------------------------------------------ extension rays (closest hit)
-    if (__ballot(want_extend) != 0ull) {
+    const unsigned long long extend_mask = __ballot(want_extend);
+    if (extend_mask != 0ull) {
+      cnt_ext += (uint32_t)__builtin_popcountll(extend_mask);
       float t_;
       int32_t tri_, inst_;
       bool any_;
@@ -221,7 +239,6 @@ __global__ __launch_bounds__(64 * RT_PT_WAVES, RT_PT_SIMD_WAVES) void RT_PT_KERN
                                     inst_, any_, cnt_nodes, cnt_tris);
       RT_LSTAT(5, want_extend && inst_ >= 0);
       if (want_extend) {
-        cnt_ext++;
         if (inst_ < 0) {
           path_done = true;
         } else {
@@ -285,8 +302,8 @@ __global__ __launch_bounds__(64 * RT_PT_WAVES, RT_PT_SIMD_WAVES) void RT_PT_KERN
   // counters: one flush per persistent wave
   LaneCounters c;
   c.primary = 0;
-  c.extension = cnt_ext;
-  c.shadow = cnt_shadow;
+  c.extension = lane == 0u ? cnt_ext : 0u;   // the wave's count, once
+  c.shadow = lane == 0u ? cnt_shadow : 0u;
   c.nodes = cnt_nodes;
   c.tris = cnt_tris;
   c.shaded = cnt_shaded;
