@@ -36,7 +36,8 @@ enum {
   RT_ERR_HIP = -2,
   RT_ERR_NOT_READY = -3,
   RT_ERR_NO_DEVICE = -4,
-  RT_ERR_INTERNAL = -5
+  RT_ERR_INTERNAL = -5,
+  RT_ERR_RCCL = -6 /* librccl could not be loaded, or one of its calls failed (sharded image, below) */
 };
 
 /* updateBuffer(type, data) kinds — WebGPURenderer.ts:55-60 */
@@ -296,6 +297,59 @@ int rt_debug_ieee_check(rt_ctx* ctx, int op, uint64_t first, uint64_t count, rt_
  *   0 = one pixel per lane, one 8x8 tile per wave (the reference's dispatch shape; kept for A/B timing; no batches) */
 int rt_set_kernel_variant(rt_ctx* ctx, int variant);
 int rt_device_count(void);
+
+/* ---- the sharded image: one picture rendered by `world` contexts ("ranks"), assembled on rank 0 ----
+ * Rank k owns the image rows y with (y / stripe_rows) % world == k and traces only those (rt_set_stripes).  Its COMPACT
+ * BLOCK holds the rows it owns in ascending y, width float4 each, padded with zero rows to max_rows = the largest share
+ * over all ranks, so all blocks are rt_dist_block_bytes long: row j of block k is image row
+ * ((j / stripe_rows) * world + k) * stripe_rows + j % stripe_rows when that is < height, a padding row otherwise.
+ * A gather is pack (accumulator -> this rank's block), exchange (every block to rank 0) and unpack (rank 0: the world
+ * blocks -> its display buffer, which rt_present then reads).  Pack, exchange and unpack are copies: the display buffer is
+ * bit for bit the accumulation buffer one context would hold.  The gather is out of place - the accumulators are only
+ * read - so a progressive render goes on after it (render, gather, render, gather ...).  The exchange is either RCCL on
+ * the context's stream (rt_gather_stripes; needs a communicator) or the host's own: rt_dist_read_block on every rank,
+ * any transport, rt_dist_write_block on rank 0 (ranks that share a GPU, ranks on other machines).
+ * The context owns every buffer of it (send block; on rank 0 `world` receive blocks and the display buffer).  rt_resize
+ * allocates them anew for the new size (display buffer and blocks zeroed) - nothing goes stale, nothing is re-bound.
+ * While a context is a rank, rt_bind_accum and rt_bind_present_source are refused (the rank reads the context's own
+ * accumulator and presents from its own display buffer) and so is an rt_set_stripes that says anything else than
+ * rt_dist_init did. */
+
+/* ncclGetUniqueId: rank 0 calls it and the host hands the 128 bytes to the other ranks (pipe, file, IPC message).
+ * Loads librccl on first use (see rt_dist_init).  No context: on failure the message is rt_last_error(NULL). */
+int rt_dist_unique_id(uint8_t out[128]);
+/* Make the context rank `rank` of `world` (<= 65535) with stripes of `stripe_rows` rows: sets the stripes as
+ * rt_set_stripes(stripe_rows, rank, world) would and allocates the buffers for the current size (none yet: at the first
+ * rt_resize).  unique_id128 != NULL: also ncclCommInitRank on the context's device - collective, every rank of the id must
+ * call it.  NULL: no communicator; the host moves the blocks.
+ * RCCL is never linked: it is dlopen'ed here, in this order: MI355RT_RCCL=<path> when set; the librccl.so.1 that is already
+ * mapped into the process (a process that has loaded PyTorch has PyTorch's copy, built against the HIP runtime it
+ * shares with this library); the system's librccl.so.1.  A library that cannot be loaded or a failing ncclCommInitRank
+ * is RT_ERR_RCCL with the file in use named in the message, and leaves the context a plain one.
+ * RT_ERR_INVALID: rank >= world, world == 0 or > 65535, stripe_rows == 0, a context that is a rank already, or one with
+ * an rt_bind_accum / rt_bind_present_source binding. */
+int rt_dist_init(rt_ctx* ctx, uint32_t rank, uint32_t world, uint32_t stripe_rows, const uint8_t* unique_id128);
+/* Back to a plain context that renders every row and presents its accumulator: frees the buffers and the communicator.
+ * Fences the stream first.  rt_destroy does the same.  RT_OK on a context that is no rank. */
+int rt_dist_shutdown(rt_ctx* ctx);
+/* max_rows * width * 16 at the current size; 0 when the context is no rank or has no size yet. */
+size_t rt_dist_block_bytes(const rt_ctx* ctx);
+/* Enqueue: accumulator -> this rank's compact block (k_pack_stripes). */
+int rt_pack_stripes(rt_ctx* ctx);
+/* This rank's block as the last rt_pack_stripes left it -> host (blocking).  cap >= rt_dist_block_bytes. */
+int rt_dist_read_block(rt_ctx* ctx, void* host_out, size_t cap);
+/* Rank 0: host -> the receive block of rank `from_rank` (rank 0's own block included: it takes the same way as everyone
+ * else's).  bytes must be rt_dist_block_bytes.  The source may be reused on return. */
+int rt_dist_write_block(rt_ctx* ctx, uint32_t from_rank, const void* host_in, size_t bytes);
+/* Rank 0, enqueue: the `world` receive blocks -> display buffer, one launch (k_unpack_stripes). */
+int rt_unpack_stripes(rt_ctx* ctx);
+/* pack -> every rank ncclSend's its block to rank 0, rank 0 ncclRecv's `world` blocks (one group) -> unpack on rank 0,
+ * all enqueued on the context's stream (rt_set_stream respected) without host synchronisation.  Collective: every rank
+ * calls it once per gather.  world == 1 still runs the send / receive pair.  Without a communicator: RT_ERR_INVALID (move the
+ * blocks with rt_dist_read_block / rt_dist_write_block instead). */
+int rt_gather_stripes(rt_ctx* ctx);
+/* Rank 0: the display buffer (the assembled float4 image of the last unpack; zero before the first) -> host (blocking). */
+int rt_read_display(rt_ctx* ctx, float* out_rgba32f, size_t cap_bytes);
 
 #ifdef __cplusplus
 }

@@ -9,6 +9,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <dlfcn.h>
 #include <execinfo.h>
 
 #include <algorithm>
@@ -18,6 +19,7 @@
 #include <cstring>
 #include <deque>
 #include <exception>
+#include <mutex>
 #include <string>
 #include <vector>
 
@@ -114,6 +116,14 @@ struct rt_ctx {
   bool accum_stale = false;         // rt_bind_accum's buffer was sized for the screen before the last rt_resize ...
   bool present_stale = false;       // ... and so was rt_bind_present_source's: each is cleared only by its own bind call
   int history_index = 0;
+  // the sharded image (rt_dist_*, k_stripes.hip.h): this context is rank `rank` of `world`
+  struct {
+    bool active = false;
+    uint32_t rank = 0, world = 1, stripe_rows = 0;
+    uint32_t max_rows = 0;             // rows of a compact block at the current size (0: no size yet)
+    DeviceBuffer send, recv, display;  // this rank's block; rank 0: the world receive blocks, the assembled image
+    void* comm = nullptr;              // ncclComm_t, or null: the host moves the blocks
+  } dist;
 
   // uniforms + host state (ResourceManager fields)
   rt_scene_uniforms uniforms;
@@ -281,6 +291,165 @@ void write_mixed(rt_ctx* c, uint32_t frame_count) {  // the 48 bytes at offset 1
 }
 
 float4* accum_ptr(rt_ctx* c) { return (float4*)(c->external_accum ? c->external_accum : c->accum.ptr); }
+
+// ---------------------------------------------------------------- the sharded image (rt_dist_*, k_stripes.hip.h)
+// RCCL is loaded at run time, never linked: the library loads and renders on a machine without librccl.  The public NCCL
+// API (nccl.h), declared here for the few calls the gather makes.
+struct RcclUniqueId {
+  char internal[128];
+};
+struct Rccl {
+  void* handle = nullptr;
+  std::string file;    // the file the calls resolve into (dladdr), for error messages
+  std::string error;   // why it is unusable (empty: usable)
+  int (*GetUniqueId)(RcclUniqueId*) = nullptr;
+  int (*CommInitRank)(void**, int, RcclUniqueId, int) = nullptr;
+  int (*CommDestroy)(void*) = nullptr;
+  int (*GroupStart)() = nullptr;
+  int (*GroupEnd)() = nullptr;
+  int (*Send)(const void*, size_t, int, int, void*, hipStream_t) = nullptr;
+  int (*Recv)(void*, size_t, int, int, void*, hipStream_t) = nullptr;
+  const char* (*GetErrorString)(int) = nullptr;
+};
+constexpr int kNcclFloat32 = 7;   // ncclDataType_t
+
+// One copy per process.  Order: MI355RT_RCCL=<path>; the librccl.so.1 already mapped (a process that has loaded PyTorch has
+// PyTorch's, built against the HIP runtime it shares with this library: INTEGRATION.md "One HIP runtime per process");
+// the system's.  A failure is remembered (the message says why) and never aborts.
+Rccl& rccl() {
+  static Rccl R;
+  static std::once_flag once;
+  std::call_once(once, [] {
+    std::string tried;
+    auto open = [&](const char* name, int flags) {
+      if (R.handle) return;
+      R.handle = dlopen(name, flags);
+      if (!R.handle) {
+        const char* e = dlerror();
+        if (!(flags & RTLD_NOLOAD)) tried += std::string(tried.empty() ? "" : "; ") + (e ? e : name);
+      }
+    };
+    const char* env = getenv("MI355RT_RCCL");
+    if (env && env[0]) {
+      open(env, RTLD_NOW | RTLD_LOCAL);
+    } else {
+      open("librccl.so.1", RTLD_NOW | RTLD_NOLOAD);
+      open("librccl.so", RTLD_NOW | RTLD_NOLOAD);
+      open("librccl.so.1", RTLD_NOW | RTLD_LOCAL);
+      open("/opt/rocm/lib/librccl.so.1", RTLD_NOW | RTLD_LOCAL);
+    }
+    if (!R.handle) {
+      R.error = "librccl could not be loaded (" + tried + "); set MI355RT_RCCL=<path of librccl.so>";
+      return;
+    }
+    struct {
+      const char* name;
+      void** slot;
+    } syms[] = {{"ncclGetUniqueId", (void**)&R.GetUniqueId},   {"ncclCommInitRank", (void**)&R.CommInitRank},
+                {"ncclCommDestroy", (void**)&R.CommDestroy},   {"ncclGroupStart", (void**)&R.GroupStart},
+                {"ncclGroupEnd", (void**)&R.GroupEnd},         {"ncclSend", (void**)&R.Send},
+                {"ncclRecv", (void**)&R.Recv},                 {"ncclGetErrorString", (void**)&R.GetErrorString}};
+    for (auto& sy : syms) {
+      *sy.slot = dlsym(R.handle, sy.name);
+      if (!*sy.slot && R.error.empty()) R.error = std::string("librccl has no symbol ") + sy.name;
+    }
+    Dl_info info;
+    if (R.GetUniqueId && dladdr((void*)R.GetUniqueId, &info) && info.dli_fname) R.file = info.dli_fname;
+    if (!R.error.empty()) R.error += " (" + R.file + ")";
+  });
+  return R;
+}
+std::string rccl_what(const char* call, int rc) {
+  Rccl& R = rccl();
+  return std::string(call) + ": " + (R.GetErrorString ? R.GetErrorString(rc) : "error") + " (" + std::to_string(rc) +
+         ", RCCL from " + R.file + ")";
+}
+
+// rows of the largest share - rank 0's: whole periods of stripe_rows * world rows, then the first stripe of the rest
+uint32_t dist_max_rows(uint32_t height, uint32_t stripe_rows, uint32_t world) {
+  const uint64_t period = (uint64_t)stripe_rows * world;
+  return (uint32_t)((height / period) * stripe_rows + std::min<uint64_t>(height % period, stripe_rows));
+}
+rtk::StripePlan dist_plan(const rt_ctx* c) {
+  rtk::StripePlan p;
+  p.width = c->width;
+  p.height = c->height;
+  p.stripe_rows = c->dist.stripe_rows;
+  p.world = c->dist.world;
+  p.max_rows = c->dist.max_rows;
+  p.chunks = (c->width + 255u) / 256u;
+  return p;
+}
+size_t dist_block_bytes(const rt_ctx* c) { return (size_t)c->dist.max_rows * c->width * 16; }
+void dist_free_buffers(rt_ctx* c) {
+  free_buffer(c->dist.send);
+  free_buffer(c->dist.recv);
+  free_buffer(c->dist.display);
+  c->dist.max_rows = 0;
+}
+// (Re)allocate a rank's buffers for the current screen, zeroed; the stream is idle on return.
+int dist_alloc(rt_ctx* c) {
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  dist_free_buffers(c);
+  if (!c->width || !c->height) return RT_OK;   // no screen yet: rt_resize comes back here
+  c->dist.max_rows = dist_max_rows(c->height, c->dist.stripe_rows, c->dist.world);
+  const size_t block = dist_block_bytes(c);
+  struct {
+    DeviceBuffer* b;
+    size_t bytes;
+  } items[] = {{&c->dist.send, block},
+               {&c->dist.recv, c->dist.rank == 0 ? block * c->dist.world : 0},
+               {&c->dist.display, c->dist.rank == 0 ? (size_t)c->width * c->height * 16 : 0}};
+  for (auto& it : items) {
+    if (!it.bytes) continue;
+    int r = ensure_buffer(c, *it.b, it.bytes, false);
+    if (r >= 0 && hipMemsetAsync(it.b->ptr, 0, it.bytes, c->stream) != hipSuccess) r = fail(c, RT_ERR_HIP, "hipMemsetAsync (sharded image buffers)");
+    if (r < 0) {
+      (void)hipGetLastError();
+      dist_free_buffers(c);
+      return r;
+    }
+  }
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return RT_OK;
+}
+// rt_dist_shutdown / rt_destroy: the caller has fenced the stream
+void dist_release(rt_ctx* c) {
+  if (c->dist.comm) (void)rccl().CommDestroy(c->dist.comm);
+  c->dist.comm = nullptr;
+  dist_free_buffers(c);
+  if (c->dist.active) {
+    c->dist.active = false;
+    c->stripe_rows = 0;
+    c->stripe_rank = 0;
+    c->stripe_count = 1;
+    c->epoch++;
+  }
+}
+// what every entry point of a rank checks first; rank0: the call is rank 0's alone
+int dist_ready(rt_ctx* c, const char* what, bool rank0) {
+  if (!c->dist.active) return fail(c, RT_ERR_INVALID, std::string(what) + ": the context is no rank of a sharded image (rt_dist_init)");
+  if (rank0 && c->dist.rank != 0) return fail(c, RT_ERR_INVALID, std::string(what) + ": only rank 0 assembles the image");
+  if (!c->dist.max_rows || !c->dist.send.ptr) return fail(c, RT_ERR_NOT_READY, std::string(what) + ": no screen size yet (rt_resize)");
+  return RT_OK;
+}
+int dist_launch_pack(rt_ctx* c) {
+  const rtk::StripePlan p = dist_plan(c);
+  const uint32_t items = p.max_rows * p.chunks;
+  hipLaunchKernelGGL(rtk::k_pack_stripes, dim3(std::min<uint32_t>(items, 2048u)), dim3(256), 0, c->stream,
+                     (const float4*)accum_ptr(c), (float4*)c->dist.send.ptr, p, c->dist.rank);
+  HIP_TRY(c, hipGetLastError());
+  return RT_OK;
+}
+int dist_launch_unpack(rt_ctx* c) {
+  const rtk::StripePlan p = dist_plan(c);
+  const uint64_t items = (uint64_t)p.max_rows * p.chunks * p.world;
+  hipLaunchKernelGGL(rtk::k_unpack_stripes, dim3((uint32_t)std::min<uint64_t>(items, 2048u)), dim3(256), 0, c->stream,
+                     (const float4*)c->dist.recv.ptr, (float4*)c->dist.display.ptr, p);
+  HIP_TRY(c, hipGetLastError());
+  return RT_OK;
+}
 
 DevScene dev_scene(const rt_ctx* c);
 
@@ -595,6 +764,7 @@ void rt_destroy(rt_ctx* c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
   (void)hipStreamSynchronize(c->stream);
+  dist_release(c);
   DeviceBuffer* all[] = {&c->topology, &c->instances, &c->lights, &c->draw_commands, &c->pos, &c->nrm, &c->uv,
                          &c->nodes, &c->textures, &c->tri_geom, &c->tri_shade, &c->inst_trav, &c->light_rec, &c->accum, &c->render_target,
                          &c->g_normal, &c->g_depth, &c->history[0], &c->history[1], &c->counters, &c->ticket,
@@ -674,6 +844,7 @@ int rt_resize(rt_ctx* c, uint32_t width, uint32_t height) {
   c->external_accum = nullptr;
   c->present_source = nullptr;
   HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (c->dist.active) return dist_alloc(c);   // a rank's blocks and display buffer follow the screen on their own
   return RT_OK;
 }
 
@@ -2060,9 +2231,12 @@ int rt_present(rt_ctx* c) {
     return fail(c, RT_ERR_INVALID, "the bound accumulation buffer was dropped by rt_resize: call rt_bind_accum again");
   if (c->present_stale)
     return fail(c, RT_ERR_INVALID, "the bound present source was dropped by rt_resize: call rt_bind_present_source again");
+  if (c->dist.active && c->dist.rank == 0 && !c->dist.display.ptr)
+    return fail(c, RT_ERR_NOT_READY, "rank 0 has no display buffer (its allocation failed at the last rt_resize)");
   HIP_TRY(c, hipSetDevice(c->device));
   DevPost P;
   P.accum = c->present_source ? (const float4*)c->present_source : accum_ptr(c);
+  if (c->dist.active && c->dist.rank == 0) P.accum = (const float4*)c->dist.display.ptr;   // the assembled image
   P.history_in = (const ushort4*)c->history[1 - c->history_index].ptr;  // previous frame (read)
   P.history_out = (ushort4*)c->history[c->history_index].ptr;           // current frame (write)
   P.out_rgba8 = (uint32_t*)c->render_target.ptr;
@@ -2190,6 +2364,11 @@ int rt_set_counting(rt_ctx* c, int detailed) {
 int rt_set_stripes(rt_ctx* c, uint32_t stripe_rows, uint32_t rank, uint32_t count) {
   if (!c) return RT_ERR_INVALID;
   if (count > 1 && (stripe_rows == 0 || rank >= count)) return fail(c, RT_ERR_INVALID, "invalid stripe spec");
+  if (c->dist.active) {
+    if (stripe_rows != c->dist.stripe_rows || rank != c->dist.rank || (count ? count : 1) != c->dist.world)
+      return fail(c, RT_ERR_INVALID, "rt_set_stripes contradicts the rank rt_dist_init made this context (rt_dist_shutdown first)");
+    return RT_OK;
+  }
   c->epoch++;
   c->stripe_rows = stripe_rows;
   c->stripe_rank = rank;
@@ -2199,6 +2378,8 @@ int rt_set_stripes(rt_ctx* c, uint32_t stripe_rows, uint32_t rank, uint32_t coun
 void* rt_accum_device_ptr(rt_ctx* c) { return c ? (void*)accum_ptr(c) : nullptr; }
 int rt_bind_accum(rt_ctx* c, void* device_ptr) {
   if (!c) return RT_ERR_INVALID;
+  if (c->dist.active)
+    return fail(c, RT_ERR_INVALID, "rt_bind_accum: the context is a rank of a sharded image and packs its own accumulator (rt_dist_shutdown first)");
   HIP_TRY(c, hipSetDevice(c->device));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   c->external_accum = device_ptr;
@@ -2207,6 +2388,8 @@ int rt_bind_accum(rt_ctx* c, void* device_ptr) {
 }
 int rt_bind_present_source(rt_ctx* c, void* device_ptr) {
   if (!c) return RT_ERR_INVALID;
+  if (c->dist.active)
+    return fail(c, RT_ERR_INVALID, "rt_bind_present_source: the context is a rank of a sharded image and presents its own display buffer (rt_dist_shutdown first)");
   HIP_TRY(c, hipSetDevice(c->device));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   c->present_source = device_ptr;
@@ -2389,6 +2572,138 @@ int rt_kernel_time_ms(rt_ctx* c, double* avg_pt, double* avg_pv, uint32_t* launc
   if (avg_pv) *avg_pv = cnt[RT_TIMER_PRIMARY] ? sum[RT_TIMER_PRIMARY] / cnt[RT_TIMER_PRIMARY] : 0.0;
   if (avg_pt) *avg_pt = cnt[RT_TIMER_PATHTRACE] ? sum[RT_TIMER_PATHTRACE] / cnt[RT_TIMER_PATHTRACE] : 0.0;
   if (launches) *launches = cnt[RT_TIMER_PATHTRACE];
+  return RT_OK;
+}
+
+// ---------------------------------------------------------------- the sharded image
+int rt_dist_unique_id(uint8_t out[128]) {
+  if (!out) return RT_ERR_INVALID;
+  Rccl& R = rccl();
+  if (!R.error.empty()) {
+    g_create_error = R.error;
+    return RT_ERR_RCCL;
+  }
+  RcclUniqueId id;
+  std::memset(&id, 0, sizeof(id));
+  const int rc = R.GetUniqueId(&id);
+  if (rc != 0) {
+    g_create_error = rccl_what("ncclGetUniqueId", rc);
+    return RT_ERR_RCCL;
+  }
+  std::memcpy(out, id.internal, 128);
+  return RT_OK;
+}
+int rt_dist_init(rt_ctx* c, uint32_t rank, uint32_t world, uint32_t stripe_rows, const uint8_t* unique_id128) {
+  if (!c) return RT_ERR_INVALID;
+  if (world == 0 || world > 65535u) return fail(c, RT_ERR_INVALID, "rt_dist_init: world must be 1 .. 65535");
+  if (rank >= world) return fail(c, RT_ERR_INVALID, "rt_dist_init: rank >= world");
+  if (stripe_rows == 0) return fail(c, RT_ERR_INVALID, "rt_dist_init: stripe_rows must be >= 1");
+  if (c->dist.active) return fail(c, RT_ERR_INVALID, "rt_dist_init: the context is a rank already (rt_dist_shutdown first)");
+  if (c->external_accum || c->present_source || c->accum_stale || c->present_stale)
+    return fail(c, RT_ERR_INVALID, "rt_dist_init: unbind rt_bind_accum / rt_bind_present_source first (a rank uses the context's own buffers)");
+  HIP_TRY(c, hipSetDevice(c->device));
+  void* comm = nullptr;
+  if (unique_id128) {
+    Rccl& R = rccl();
+    if (!R.error.empty()) return fail(c, RT_ERR_RCCL, "rt_dist_init: " + R.error);
+    RcclUniqueId id;
+    std::memcpy(id.internal, unique_id128, 128);
+    const int rc = R.CommInitRank(&comm, (int)world, id, (int)rank);
+    if (rc != 0 || !comm) return fail(c, RT_ERR_RCCL, "rt_dist_init: " + rccl_what("ncclCommInitRank", rc));
+  }
+  c->dist.active = true;
+  c->dist.rank = rank;
+  c->dist.world = world;
+  c->dist.stripe_rows = stripe_rows;
+  c->dist.comm = comm;
+  c->stripe_rows = stripe_rows;
+  c->stripe_rank = rank;
+  c->stripe_count = world;
+  c->epoch++;   // drops frames traced ahead for other stripes (rt_set_lookahead)
+  const int r = dist_alloc(c);
+  if (r < 0) {
+    const std::string why = c->error;
+    (void)hipStreamSynchronize(c->stream);
+    dist_release(c);
+    return fail(c, r, "rt_dist_init: " + why);
+  }
+  return RT_OK;
+}
+int rt_dist_shutdown(rt_ctx* c) {
+  if (!c) return RT_ERR_INVALID;
+  if (!c->dist.active) return RT_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  dist_release(c);
+  return RT_OK;
+}
+size_t rt_dist_block_bytes(const rt_ctx* c) { return (c && c->dist.active) ? dist_block_bytes(c) : 0; }
+int rt_pack_stripes(rt_ctx* c) {
+  if (!c) return RT_ERR_INVALID;
+  if (int r = dist_ready(c, "rt_pack_stripes", false)) return r;
+  HIP_TRY(c, hipSetDevice(c->device));
+  return dist_launch_pack(c);
+}
+int rt_dist_read_block(rt_ctx* c, void* host_out, size_t cap) {
+  if (!c) return RT_ERR_INVALID;
+  if (int r = dist_ready(c, "rt_dist_read_block", false)) return r;
+  if (!host_out) return fail(c, RT_ERR_INVALID, "rt_dist_read_block: null buffer");
+  const size_t bytes = dist_block_bytes(c);
+  if (cap < bytes) return fail(c, RT_ERR_INVALID, "rt_dist_read_block: buffer smaller than rt_dist_block_bytes");
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, hipMemcpyAsync(host_out, c->dist.send.ptr, bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return RT_OK;
+}
+int rt_dist_write_block(rt_ctx* c, uint32_t from_rank, const void* host_in, size_t bytes) {
+  if (!c) return RT_ERR_INVALID;
+  if (int r = dist_ready(c, "rt_dist_write_block", true)) return r;
+  if (!host_in) return fail(c, RT_ERR_INVALID, "rt_dist_write_block: null buffer");
+  if (from_rank >= c->dist.world) return fail(c, RT_ERR_INVALID, "rt_dist_write_block: from_rank >= world");
+  const size_t block = dist_block_bytes(c);
+  if (bytes != block) return fail(c, RT_ERR_INVALID, "rt_dist_write_block: byte count is not rt_dist_block_bytes");
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, hipMemcpyAsync((char*)c->dist.recv.ptr + (size_t)from_rank * block, host_in, bytes, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));   // queue.writeBuffer semantics: the source may be reused on return
+  return RT_OK;
+}
+int rt_unpack_stripes(rt_ctx* c) {
+  if (!c) return RT_ERR_INVALID;
+  if (int r = dist_ready(c, "rt_unpack_stripes", true)) return r;
+  HIP_TRY(c, hipSetDevice(c->device));
+  return dist_launch_unpack(c);
+}
+int rt_gather_stripes(rt_ctx* c) {
+  if (!c) return RT_ERR_INVALID;
+  if (int r = dist_ready(c, "rt_gather_stripes", false)) return r;
+  if (!c->dist.comm)
+    return fail(c, RT_ERR_INVALID, "rt_gather_stripes: no communicator (rt_dist_init was given no unique id): move the blocks with "
+                                   "rt_dist_read_block / rt_dist_write_block and call rt_pack_stripes / rt_unpack_stripes");
+  HIP_TRY(c, hipSetDevice(c->device));
+  if (int r = dist_launch_pack(c)) return r;
+  Rccl& R = rccl();
+  const size_t block = dist_block_bytes(c), count = block / 4;
+  int rc = R.GroupStart();
+  if (rc != 0) return fail(c, RT_ERR_RCCL, rccl_what("ncclGroupStart", rc));
+  int rc_op = R.Send(c->dist.send.ptr, count, kNcclFloat32, 0, c->dist.comm, c->stream);
+  if (c->dist.rank == 0)
+    for (uint32_t k = 0; k < c->dist.world && rc_op == 0; k++)
+      rc_op = R.Recv((char*)c->dist.recv.ptr + (size_t)k * block, count, kNcclFloat32, (int)k, c->dist.comm, c->stream);
+  rc = R.GroupEnd();   // always closed, also after a failed call inside the group
+  if (rc_op != 0) return fail(c, RT_ERR_RCCL, rccl_what("ncclSend / ncclRecv", rc_op));
+  if (rc != 0) return fail(c, RT_ERR_RCCL, rccl_what("ncclGroupEnd", rc));
+  if (c->dist.rank == 0) return dist_launch_unpack(c);
+  return RT_OK;
+}
+int rt_read_display(rt_ctx* c, float* out, size_t cap) {
+  if (!c) return RT_ERR_INVALID;
+  if (int r = dist_ready(c, "rt_read_display", true)) return r;
+  if (!out) return fail(c, RT_ERR_INVALID, "rt_read_display: null buffer");
+  const size_t bytes = (size_t)c->width * c->height * 16;
+  if (cap < bytes) return fail(c, RT_ERR_INVALID, "rt_read_display: buffer too small");
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, hipMemcpyAsync(out, c->dist.display.ptr, bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
   return RT_OK;
 }
 

@@ -229,3 +229,76 @@ class ShardedImage:
             self.stream.synchronize()
         else:
             self.r.sync()
+
+
+class NativeShardedImage:
+    """`ShardedImage`'s surface over the library's own gather (rt_dist_*, include/mi355rt.h): HIP pack / unpack kernels
+    and, with a unique id, an RCCL send / receive group on the context's stream.  No torch anywhere: the context owns
+    the blocks and rank 0's display buffer, and a resize needs no re-binding.
+
+    unique_id (the 128 bytes of renderer.dist_unique_id(), made by rank 0 and handed to every rank): gather() is
+    rt_gather_stripes, a collective that every rank calls.
+    unique_id None: the host moves the blocks.  `exchange(rank, block)` gets this rank's packed block ((max_rows, width, 4)
+    float32), carries it to rank 0 by whatever means the host has, and on rank 0 returns the blocks of all ranks indexed by
+    rank (its own included); what it returns elsewhere is ignored.  One rank needs no exchange function."""
+
+    def __init__(self, renderer, rank, world_size, stripe_rows=STRIPE_ROWS, unique_id=None, exchange=None):
+        self.r = renderer
+        self.rank = rank
+        self.world = world_size
+        self.stripe_rows = stripe_rows
+        self.collective = unique_id is not None
+        if not self.collective and exchange is None:
+            if world_size != 1:
+                raise ValueError("NativeShardedImage needs a unique id (RCCL gather) or an exchange function for the blocks")
+            exchange = lambda rank, block: [block]
+        self.exchange = exchange
+        renderer.distInit(rank, world_size, stripe_rows, unique_id)
+
+    def owned_rows(self, height):
+        return (np.arange(height) // self.stripe_rows) % self.world == self.rank
+
+    def rows_of(self, rank, height):
+        """Row indices (ascending) of the image that `rank` owns."""
+        return np.nonzero((np.arange(height) // self.stripe_rows) % self.world == rank)[0]
+
+    def max_rows(self, height):
+        return max(len(self.rows_of(k, height)) for k in range(self.world))
+
+    def wire_bytes_per_rank(self):
+        """Bytes one rank contributes to one gather (the padded compact block)."""
+        return self.r.distBlockBytes()
+
+    def render(self, frames, batch=1):
+        frames = list(frames)
+        if batch > 1:
+            for i in range(0, len(frames), batch):
+                self.r.computeBatch(frames[i:i + batch])
+        else:
+            for f in frames:
+                self.r.compute(f)
+
+    def gather(self, present=True):
+        """Assemble the image in rank 0's display buffer; rank 0 then runs the post pass on it.  The accumulators are only read."""
+        if self.collective:
+            self.r.gatherStripes()
+        else:
+            self.r.packStripes()
+            blocks = self.exchange(self.rank, self.r.readBlock())
+            if self.rank == 0:
+                for k in range(self.world):
+                    self.r.writeBlock(k, blocks[k])
+                self.r.unpackStripes()
+        if present and self.rank == 0:
+            self.r.present()
+
+    def read_image(self):
+        """Rank 0: the assembled float4 accumulation image of the last gather() as (H, W, 4) float32."""
+        return self.r.readDisplay()
+
+    def synchronize(self):
+        self.r.sync()
+
+    def close(self):
+        """Back to a plain context (rt_dist_shutdown); the renderer's destroy() does it too."""
+        self.r.distShutdown()

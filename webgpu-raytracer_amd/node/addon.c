@@ -443,6 +443,90 @@ static napi_value msTexture(napi_env env, napi_callback_info info) {
   return ta;
 }
 
+/* ------------------------------------------------------- the sharded image (rt_dist_*, mi355rt.h) */
+static napi_value rtDeviceCount(napi_env env, napi_callback_info info) {
+  (void)info;
+  return make_int(env, rt_device_count());
+}
+static napi_value rtSetStripes(napi_env env, napi_callback_info info) {
+  napi_value a[4];
+  if (!get_args(env, info, 4, a)) return NULL;
+  return make_int(env, rt_set_stripes((rt_ctx*)get_ptr(env, a[0]), get_u32(env, a[1]), get_u32(env, a[2]), get_u32(env, a[3])));
+}
+/* () -> Uint8Array(128); throws with rt_last_error(NULL) when RCCL cannot be loaded */
+static napi_value rtDistUniqueId(napi_env env, napi_callback_info info) {
+  (void)info;
+  void* dst = NULL;
+  napi_value ab, ta;
+  NAPI_OK(env, napi_create_arraybuffer(env, 128, &dst, &ab));
+  if (rt_dist_unique_id((uint8_t*)dst) < 0) {
+    napi_throw_error(env, NULL, rt_last_error(NULL));
+    return NULL;
+  }
+  NAPI_OK(env, napi_create_typedarray(env, napi_uint8_array, 128, ab, 0, &ta));
+  return ta;
+}
+/* (ctx, rank, world, stripeRows, uniqueId: Uint8Array(128) | null) */
+static napi_value rtDistInit(napi_env env, napi_callback_info info) {
+  napi_value a[5];
+  void* id = NULL;
+  size_t n = 0;
+  if (!get_args(env, info, 5, a) || !get_bytes(env, a[4], &id, &n)) return NULL;
+  if (id && n != 128) {
+    napi_throw_range_error(env, NULL, "rtDistInit: the unique id must be 128 bytes");
+    return NULL;
+  }
+  return make_int(env, rt_dist_init((rt_ctx*)get_ptr(env, a[0]), get_u32(env, a[1]), get_u32(env, a[2]), get_u32(env, a[3]),
+                                    (const uint8_t*)id));
+}
+static napi_value rtDistShutdown(napi_env env, napi_callback_info info) {
+  napi_value a[1];
+  if (!get_args(env, info, 1, a)) return NULL;
+  return make_int(env, rt_dist_shutdown((rt_ctx*)get_ptr(env, a[0])));
+}
+static napi_value rtDistBlockBytes(napi_env env, napi_callback_info info) {
+  napi_value a[1], d;
+  if (!get_args(env, info, 1, a)) return NULL;
+  NAPI_OK(env, napi_create_double(env, (double)rt_dist_block_bytes((const rt_ctx*)get_ptr(env, a[0])), &d));
+  return d;
+}
+static napi_value rtPackStripes(napi_env env, napi_callback_info info) {
+  napi_value a[1];
+  if (!get_args(env, info, 1, a)) return NULL;
+  return make_int(env, rt_pack_stripes((rt_ctx*)get_ptr(env, a[0])));
+}
+static napi_value rtDistReadBlock(napi_env env, napi_callback_info info) {
+  napi_value a[2];
+  void* p;
+  size_t n;
+  if (!get_args(env, info, 2, a) || !get_bytes(env, a[1], &p, &n)) return NULL;
+  return make_int(env, rt_dist_read_block((rt_ctx*)get_ptr(env, a[0]), p, n));
+}
+static napi_value rtDistWriteBlock(napi_env env, napi_callback_info info) {
+  napi_value a[3];
+  void* p;
+  size_t n;
+  if (!get_args(env, info, 3, a) || !get_bytes(env, a[2], &p, &n)) return NULL;
+  return make_int(env, rt_dist_write_block((rt_ctx*)get_ptr(env, a[0]), get_u32(env, a[1]), p, n));
+}
+static napi_value rtUnpackStripes(napi_env env, napi_callback_info info) {
+  napi_value a[1];
+  if (!get_args(env, info, 1, a)) return NULL;
+  return make_int(env, rt_unpack_stripes((rt_ctx*)get_ptr(env, a[0])));
+}
+static napi_value rtGatherStripes(napi_env env, napi_callback_info info) {
+  napi_value a[1];
+  if (!get_args(env, info, 1, a)) return NULL;
+  return make_int(env, rt_gather_stripes((rt_ctx*)get_ptr(env, a[0])));
+}
+static napi_value rtReadDisplay(napi_env env, napi_callback_info info) {
+  napi_value a[2];
+  void* p;
+  size_t n;
+  if (!get_args(env, info, 2, a) || !get_bytes(env, a[1], &p, &n)) return NULL;
+  return make_int(env, rt_read_display((rt_ctx*)get_ptr(env, a[0]), (float*)p, n));
+}
+
 static napi_value Init(napi_env env, napi_value exports) {
   static const struct {
     const char* name;
@@ -454,7 +538,11 @@ static napi_value Init(napi_env env, napi_value exports) {
                {"rtUploadBVH", rtUploadBVH}, {"rtSetScene", rtSetScene}, {"rtCompute", rtCompute},
                {"rtComputeBatch", rtComputeBatch},
                {"rtPresent", rtPresent}, {"rtSync", rtSync}, {"rtCapture", rtCapture}, {"rtReadAccum", rtReadAccum},
-               {"rtGetCounters", rtGetCounters}, {"msCreate", msCreate}, {"msDestroy", msDestroy},
+               {"rtGetCounters", rtGetCounters}, {"rtDeviceCount", rtDeviceCount}, {"rtSetStripes", rtSetStripes},
+               {"rtDistUniqueId", rtDistUniqueId}, {"rtDistInit", rtDistInit}, {"rtDistShutdown", rtDistShutdown},
+               {"rtDistBlockBytes", rtDistBlockBytes}, {"rtPackStripes", rtPackStripes}, {"rtDistReadBlock", rtDistReadBlock},
+               {"rtDistWriteBlock", rtDistWriteBlock}, {"rtUnpackStripes", rtUnpackStripes},
+               {"rtGatherStripes", rtGatherStripes}, {"rtReadDisplay", rtReadDisplay}, {"msCreate", msCreate}, {"msDestroy", msDestroy},
                {"msUpdate", msUpdate}, {"msUpdateCamera", msUpdateCamera}, {"msGet", msGet},
                {"msTextureCount", msTextureCount}, {"msTexture", msTexture},
                {"msAnimationNames", msAnimationNames}, {"msSetAnimation", msSetAnimation},

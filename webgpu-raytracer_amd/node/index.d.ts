@@ -19,6 +19,28 @@ export class WebGPURenderer {
   captureFrame(): Promise<{ data: ArrayBufferLike; width: number; height: number }>;
   readAccum(): Float32Array;
   getCounters(): Record<string, number>;
+  /** compute() traces only rows y with floor(y / stripeRows) % count === rank */
+  setStripes(stripeRows: number, rank: number, count: number): void;
+  /** ncclGetUniqueId: rank 0 makes the 128 bytes and the host hands them to the other ranks */
+  static distUniqueId(): Uint8Array;
+  static deviceCount(): number;
+  /** become rank `rank` of `world` of one sharded image; uniqueId given: RCCL gather, else the host moves the blocks */
+  distInit(rank: number, world: number, stripeRows?: number, uniqueId?: Uint8Array | null): void;
+  distShutdown(): void;
+  /** bytes of one rank's compact block at the current size */
+  distBlockBytes(): number;
+  /** enqueue: accumulator -> this rank's compact block */
+  packStripes(): void;
+  /** this rank's packed block (blocking) */
+  readBlock(): Float32Array;
+  /** rank 0: the block of `fromRank` into its receive slot */
+  writeBlock(fromRank: number, block: Float32Array | Uint8Array): void;
+  /** rank 0, enqueue: all receive blocks -> the display buffer present() reads */
+  unpackStripes(): void;
+  /** pack -> RCCL gather to rank 0 -> unpack on the context's stream; collective */
+  gatherStripes(): void;
+  /** rank 0: the assembled float4 image (blocking) */
+  readDisplay(): Float32Array;
   destroy(): void;
 }
 export class WorldBridge {

@@ -124,6 +124,32 @@ class WebGPURenderer {
     const c = native.rtGetCounters(this._ctx);
     return { primary_rays: c[0], extension_rays: c[1], shadow_rays: c[2], nodes_visited: c[3], tris_tested: c[4], shaded_hits: c[5] };
   }
+  // interleaved row stripes: compute() traces only rows y with floor(y / stripeRows) % count === rank (rt_set_stripes)
+  setStripes(stripeRows, rank, count) { this._check(native.rtSetStripes(this._ctx, stripeRows, rank, count), 'setStripes'); }
+  // ---- the sharded image (rt_dist_*): this context as rank `rank` of `world`; the image is assembled on rank 0 ----
+  // uniqueId: the Uint8Array(128) of WebGPURenderer.distUniqueId() -> RCCL gather (gatherStripes); null / undefined -> the host
+  // moves the blocks itself (packStripes + readBlock on every rank, writeBlock + unpackStripes on rank 0)
+  static distUniqueId() { return native.rtDistUniqueId(); }
+  static deviceCount() { return native.rtDeviceCount(); }
+  distInit(rank, world, stripeRows = 8, uniqueId = null) {
+    this._check(native.rtDistInit(this._ctx, rank, world, stripeRows, uniqueId || null), 'distInit');
+  }
+  distShutdown() { this._check(native.rtDistShutdown(this._ctx), 'distShutdown'); }
+  distBlockBytes() { return native.rtDistBlockBytes(this._ctx); }
+  packStripes() { this._check(native.rtPackStripes(this._ctx), 'packStripes'); }
+  readBlock() {
+    const out = new Float32Array(this.distBlockBytes() / 4);
+    this._check(native.rtDistReadBlock(this._ctx, out), 'readBlock');
+    return out;
+  }
+  writeBlock(fromRank, block) { this._check(native.rtDistWriteBlock(this._ctx, fromRank, block), 'writeBlock'); }
+  unpackStripes() { this._check(native.rtUnpackStripes(this._ctx), 'unpackStripes'); }
+  gatherStripes() { this._check(native.rtGatherStripes(this._ctx), 'gatherStripes'); }
+  readDisplay() {
+    const out = new Float32Array(this.width * this.height * 4);
+    this._check(native.rtReadDisplay(this._ctx, out), 'readDisplay');
+    return out;
+  }
   destroy() { if (this._ctx) { native.rtDestroy(this._ctx); this._ctx = null; } }
 }
 

@@ -180,6 +180,11 @@ def load_library(path=None):
         "rt_build_blas_levels": (i32, [vp]),
         "rt_world_update": (i32, [vp, vp]), "rt_world_set_static_cache": (i32, [vp, i32]), "rt_world_last_ms": (ctypes.c_double, [vp]), "rt_world_last_tlas_ms": (ctypes.c_double, [vp]),
         "rt_world_read": (i32, [vp, i32, vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]),
+        # the sharded image (rt_dist_*)
+        "rt_dist_unique_id": (i32, [vp]), "rt_dist_init": (i32, [vp, u32, u32, u32, vp]), "rt_dist_shutdown": (i32, [vp]),
+        "rt_dist_block_bytes": (ctypes.c_size_t, [vp]), "rt_pack_stripes": (i32, [vp]),
+        "rt_dist_read_block": (i32, [vp, vp, ctypes.c_size_t]), "rt_dist_write_block": (i32, [vp, u32, vp, ctypes.c_size_t]),
+        "rt_unpack_stripes": (i32, [vp]), "rt_gather_stripes": (i32, [vp]), "rt_read_display": (i32, [vp, vp, ctypes.c_size_t]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(L, name)  # AttributeError here = header/library mismatch
@@ -198,7 +203,9 @@ EXPORTED_SYMBOLS = (
     "rt_get_kernel_counters rt_bind_accum rt_bind_present_source rt_kernel_times rt_debug_clock_stamps rt_debug_trace_sections rt_debug_pt_sections rt_debug_pt_launch rt_debug_lane_stats rt_debug_read_traversal_nodes rt_debug_read_pairs rt_debug_ieee_check "
     "rt_reset_counters rt_set_counting rt_set_stripes rt_accum_device_ptr rt_set_stream rt_kernel_time_ms "
     "rt_set_kernel_timing rt_device_count rt_set_kernel_variant rt_set_walk rt_set_lookahead "
-    "rt_world_update rt_world_last_ms rt_world_last_tlas_ms rt_world_read rt_build_blas_levels rt_set_lookahead_limit rt_world_set_static_cache").split()
+    "rt_world_update rt_world_last_ms rt_world_last_tlas_ms rt_world_read rt_build_blas_levels rt_set_lookahead_limit rt_world_set_static_cache "
+    "rt_dist_unique_id rt_dist_init rt_dist_shutdown rt_dist_block_bytes rt_pack_stripes rt_dist_read_block rt_dist_write_block "
+    "rt_unpack_stripes rt_gather_stripes rt_read_display").split()
 
 
 def _ptr(a):
@@ -443,6 +450,49 @@ class WebGPURenderer:
     def setStream(self, hip_stream_handle):
         self._check(self.L.rt_set_stream(self.ctx, ctypes.c_void_p(hip_stream_handle)), "setStream")
 
+    # ---- the sharded image (rt_dist_*): this context as one rank of `world` ----
+    def distInit(self, rank, world, stripe_rows=8, unique_id=None):
+        """Become rank `rank` of `world`.  unique_id: the 128 bytes of dist_unique_id() (RCCL gather, gatherStripes());
+        None: no communicator, the host moves the blocks (readBlock / writeBlock)."""
+        if unique_id is not None:
+            unique_id = bytes(unique_id)
+            if len(unique_id) != 128:
+                raise RendererError("distInit: the unique id must be 128 bytes")
+        self._check(self.L.rt_dist_init(self.ctx, int(rank), int(world), int(stripe_rows), unique_id), "distInit")
+
+    def distShutdown(self):
+        self._check(self.L.rt_dist_shutdown(self.ctx), "distShutdown")
+
+    def distBlockBytes(self):
+        return int(self.L.rt_dist_block_bytes(self.ctx))
+
+    def packStripes(self):
+        self._check(self.L.rt_pack_stripes(self.ctx), "packStripes")
+
+    def readBlock(self):
+        """This rank's compact block as (max_rows, width, 4) float32 (blocking)."""
+        out = np.empty((self.distBlockBytes() // (self.width * 16) if self.width else 0, self.width, 4), dtype=np.float32)
+        self._check(self.L.rt_dist_read_block(self.ctx, _ptr(out), out.nbytes), "readBlock")
+        return out
+
+    def writeBlock(self, from_rank, block):
+        """Rank 0: the block of rank `from_rank` (any array or bytes-like of distBlockBytes() bytes) into its receive slot."""
+        a = np.ascontiguousarray(np.frombuffer(block, dtype=np.uint8) if isinstance(block, (bytes, bytearray, memoryview)) else block)
+        self._check(self.L.rt_dist_write_block(self.ctx, int(from_rank), _ptr(a), a.nbytes), "writeBlock")
+
+    def unpackStripes(self):
+        self._check(self.L.rt_unpack_stripes(self.ctx), "unpackStripes")
+
+    def gatherStripes(self):
+        """pack -> RCCL gather to rank 0 -> unpack, enqueued on the context's stream (collective: every rank calls it)."""
+        self._check(self.L.rt_gather_stripes(self.ctx), "gatherStripes")
+
+    def readDisplay(self):
+        """Rank 0: the assembled float4 image as (height, width, 4) float32 (blocking)."""
+        out = np.empty((self.height, self.width, 4), dtype=np.float32)
+        self._check(self.L.rt_read_display(self.ctx, _ptr(out), out.nbytes), "readDisplay")
+        return out
+
     def setKernelVariant(self, variant):
         """3 = auto (default: persistent kernel for LDS-resident scenes, wavefront form for larger ones), 2 = wavefront,
         1 = persistent waves + path regeneration, 0 = one pixel per lane megakernel; all bit-identical"""
@@ -468,6 +518,17 @@ class WebGPURenderer:
         self._check(self.L.rt_kernel_time_ms(self.ctx, ctypes.byref(pt), ctypes.byref(pv), ctypes.byref(n)),
                     "kernelTimeMs")
         return {"pathtrace_ms": pt.value, "primary_ms": pv.value, "launches": n.value}
+
+
+def dist_unique_id():
+    """ncclGetUniqueId through the library (rt_dist_unique_id): 128 bytes that rank 0 hands to every other rank."""
+    L = load_library()
+    out = ctypes.create_string_buffer(128)
+    rc = L.rt_dist_unique_id(out)
+    if rc < 0:
+        msg = L.rt_last_error(None)
+        raise RendererError("rt_dist_unique_id failed (%d): %s" % (rc, msg.decode() if msg else ""))
+    return out.raw
 
 
 TIMER_NAMES = ("primary", "pathtrace", "wf_shade", "wf_trace_shadow", "wf_trace_ext", "post")
