@@ -2,7 +2,9 @@
 accumulation buffer every stage before the tone map is the identity — firefly clamp (c <= 3c + 0.1), bilinear un-jitter,
 bilateral filter (all range weights 1), neighbourhood clamp of the history (mean = c, stddev = 0 pulls the zero history
 to c), alpha blend — so the output must be gamma(ACES(c)) and the f16 history c, whatever the frame count.  The expected
-bytes are computed here in float64 from the two closed-form curves (PostProcess.wgsl:36-39, 174)."""
+bytes are computed here in float64 from the two closed-form curves (PostProcess.wgsl:36-39, 174).
+Non-uniform images, where the filters are not the identity: tests/test_post_model.py (the oracle against a float64 model of
+the whole pass) and tests/test_gpu_post.py (the kernel, special values included)."""
 import numpy as np
 import pytest
 
