@@ -22,7 +22,13 @@
 //              {blas_node_offset, inv[3], inv[7], inv[11]}                    (64 B instead of 144 B)
 //   light_rec  4 x float4 / light  world-space light triangle, its unit normal and area (what sample_light_source
 //              recomputes per NEE sample from topology + positions + instance matrix, Raytracer.wgsl:354-373)
-//   topo/pos/nrm/uv/inst/lights    raw arrays, read once per shaded hit
+//   tri_world  2 x float4 / tri    one-leaf-TLAS scenes that fit LDS only (k_prepare_world_tris), behind the n_tris records
+//              of tri_shade in the same buffer: {geom_n.xyz, area} {light normal.xyz, 0} — the world-space geometric normal
+//              of setup_surface and the area and unit normal light_pdf makes of the world-space triangle, which depend on
+//              (instance, triangle) alone and are computed there by the per-hit functions, bit for bit
+//   tri_shade_w  8 x float4 / tri  same scenes: tri_shade with the three vertex normals in world space, normalised, as
+//              k_primary_visibility computes them per pixel (its LDS form stages this copy instead)
+//   topo/pos/nrm/uv/inst/lights    raw arrays, read once per shaded hit (not by the one-leaf forms of the persistent kernel)
 #ifndef MI355RT_DEVICE_SCENE_H
 #define MI355RT_DEVICE_SCENE_H
 

@@ -39,13 +39,26 @@ __device__ __forceinline__ PathState idle_path() {
 }
 
 // surface frame of the hit (tri, inst) for the ray (ro, rd): Raytracer.wgsl:738-779
+// REC (the one-leaf forms of the persistent kernel): wrec holds the world record of every triangle (k_prepare_world_tris),
+// and the geometric normal, which depends on (instance, triangle) alone, is read from it: the bits the expression below
+// gives, made once per upload.  The texture coordinates are interpolated only when the scene has a texture layer:
+// without one sample_tex returns 1 and never looks at them.
+template <bool REC = false>
 __device__ __forceinline__ void setup_surface(const DevScene& S, PathState& p, bool from_gbuffer, float gx, float gy,
-                                              uint32_t galbedo) {
+                                              uint32_t galbedo, const float4* wrec = nullptr) {
   InvRows m = load_inv_rows(S, p.inst);
   Bary b = barycentrics(S, p.tri, mul_point(m, p.ro), mul_dir(m, p.rd));
   const float4* ts = S.tri_shade + 8 * (size_t)p.tri;   // the hit's shading record: one 128-byte line
-  const float4 q4 = ts[4], q5 = ts[5], q6 = ts[6], q7 = ts[7];
-  p.tex_uv = rt2_make(q4.w, q5.w) * b.w + rt2_make(q6.w, q7.x) * b.u + rt2_make(q7.y, q7.z) * b.v;
+  float4 q4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), q5 = q4, q6 = q4;
+  if (!REC || !from_gbuffer) {   // the vertex normals: the G-buffer has the depth-0 normal already
+    q4 = ts[4];
+    q5 = ts[5];
+    q6 = ts[6];
+  }
+  if (!REC || S.tex_layers != 0u) {   // wave-uniform
+    const float4 q7 = ts[7];
+    p.tex_uv = rt2_make(ts[4].w, ts[5].w) * b.w + rt2_make(ts[6].w, q7.x) * b.u + rt2_make(q7.y, q7.z) * b.v;
+  }
   if (from_gbuffer) {
     p.hit_t = b.t;
     p.normal = unpack_normal(gx, gy);
@@ -65,7 +78,11 @@ __device__ __forceinline__ void setup_surface(const DevScene& S, PathState& p, b
       p.normal = rt_normalize(normal_to_world(m, ln_mapped));
     }
   }
-  p.geom_n = rt_normalize(normal_to_world(m, rt_normalize(rt_cross(b.e1, b.e2))));
+  if constexpr (REC) {
+    p.geom_n = xyz(wrec[2 * p.tri]);
+  } else {
+    p.geom_n = rt_normalize(normal_to_world(m, rt_normalize(rt_cross(b.e1, b.e2))));
+  }
 }
 
 // the camera of the uniforms, read once per kernel
@@ -88,10 +105,10 @@ __device__ __forceinline__ CameraBasis camera_basis(const rt_scene_uniforms& U) 
 // background pixel (or MAX_DEPTH = 0): the sample is black and ends at once.  LIVE: the caller has made that test on the
 // pixel's G-buffer depth already (k_pathtrace_persistent hands out no other pixel); the depth is not read again and the
 // sample always starts.
-template <bool LIVE = false>
+template <bool LIVE = false, bool REC = false>
 __device__ __forceinline__ bool start_sample(const DevScene& S, const DevFrame& F, const rt_scene_uniforms& U,
                                              const CameraBasis& cam, const DevFrameSlot& slot, uint32_t x, uint32_t y,
-                                             PathState& p) {
+                                             PathState& p, const float4* wrec = nullptr) {
   p.rng = init_rng(p.pixel, slot.frame_count * F.spp + p.sample);
   rt3 off = rt3_splat(0.0f);
   if (cam.lens > 0.0f) {  // random_in_unit_disk (:201-205)
@@ -121,7 +138,7 @@ __device__ __forceinline__ bool start_sample(const DevScene& S, const DevFrame& 
   if (LIVE || (!(gdepth >= 1.0f) && F.max_depth != 0u)) {
     p.tri = rt_f2u(g.z);
     p.inst = rt_f2u(g.w);
-    setup_surface(S, p, true, g.x, g.y, galbedo);
+    setup_surface<REC>(S, p, true, g.x, g.y, galbedo, wrec);
     return true;
   }
   return false;
@@ -135,8 +152,10 @@ struct BounceOut {
   rt3 sh_o, sh_d, nee;
   float sh_tmax;
 };
+// REC: light_pdf and sample_light read the records of the one-leaf forms (setup_surface)
+template <bool REC = false>
 __device__ __forceinline__ void shade_bounce(const DevScene& S, uint32_t light_count, uint32_t max_depth, PathState& p,
-                                             BounceOut& o) {
+                                             BounceOut& o, const float4* wrec = nullptr) {
   o.want_shadow = o.want_extend = o.nee_valid = false;
   o.sh_o = o.sh_d = o.nee = rt3_splat(0.0f);
   o.sh_tmax = 0.0f;
@@ -164,13 +183,14 @@ __device__ __forceinline__ void shade_bounce(const DevScene& S, uint32_t light_c
       p.radiance = p.radiance + p.throughput * em_val;
     } else {
       p.radiance = p.radiance + p.throughput * em_val *
-                                    power_heuristic(p.prev_pdf, light_pdf(S, light_count, p.tri, p.inst, p.hit_t, p.rd));
+                                    power_heuristic(p.prev_pdf, REC ? light_pdf_rec(wrec, light_count, p.tri, p.hit_t, p.rd)
+                                                                    : light_pdf(S, light_count, p.tri, p.inst, p.hit_t, p.rd));
     }
     if (mat_type == 3u) ended = true;
   }
   if (!ended) {
     if (mat_type != 2u) {  // NEE: the 3 draws happen here, the shadow ray is traced below
-      LightSample ls = sample_light(S, light_count, hit_p, p.rng);
+      LightSample ls = REC ? sample_light_rec(S, light_count, hit_p, p.rng) : sample_light(S, light_count, hit_p, p.rng);
       if (ls.pdf > 0.0f) {
         rt3 bsdf_val = rt3_splat(0.0f);
         float bsdf_pdf = 0.0f;
@@ -335,6 +355,16 @@ __host__ __device__ inline size_t scene_lds_slots(uint32_t n_nodes, uint32_t n_t
   return (size_t)2 * n_nodes + (size_t)RT_TRI_STRIDE * n_tris + (size_t)4 * n_inst + ((size_t)n_inst + 3) / 4 + (size_t)8 * n_tris +
          (size_t)5 * n_tris + (size_t)n_verts + ((size_t)n_verts + 1) / 2 + (size_t)9 * n_inst + ((size_t)n_lights + 1) / 2 +
          (size_t)4 * n_lights;
+}
+
+// What the one-leaf forms (ONE_INST) really stage: no topo, pos, uv or inst, and two slots of world record per triangle
+// (k_prepare_world_tris).  The launch asks for this much; the host still chooses between the 256-thread and the wide form,
+// and decides whether a scene fits LDS at all, on scene_lds_slots, so that the scenes on either side of those lines stay
+// where they were measured.
+__host__ __device__ inline size_t one_leaf_lds_slots(uint32_t n_nodes, uint32_t n_tris, uint32_t n_inst, uint32_t n_lights) {
+  // tnodes, tri_geom, inst_trav, inst_root | tri_shade | tri_world | lights, light_rec
+  return (size_t)2 * n_nodes + (size_t)RT_TRI_STRIDE * n_tris + (size_t)4 * n_inst + ((size_t)n_inst + 3) / 4 + (size_t)8 * n_tris +
+         (size_t)2 * n_tris + ((size_t)n_lights + 1) / 2 + (size_t)4 * n_lights;
 }
 
 // Diagnostic build only (-DRT_CLOCK_STAMP, tools/clock_check.py): every workgroup of the persistent kernel stamps

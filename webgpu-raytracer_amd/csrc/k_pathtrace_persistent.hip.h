@@ -1,7 +1,9 @@
 // The persistent path-trace kernel, written once and compiled under two names (k_pathtrace.hip.h includes this file twice,
 // inside namespace rtk): RT_PT_KERNEL is the kernel's name, RT_PT_WAVES its waves per workgroup and RT_PT_SIMD_WAVES the
 // waves per SIMD of its launch bounds (an expression that may use the template parameters).  No include guard.
-// ONE_INST (LDS form only): the scene's TLAS is a single leaf (k_traverse.hip.h traverse<.., ONE_INST>).
+// ONE_INST (LDS form only): the scene's TLAS is a single leaf (k_traverse.hip.h traverse<.., ONE_INST>).  Every hit is then in
+// the one instance, and what a trip would compute from (instance, triangle) alone is read from the per-triangle world
+// records the host built at upload time behind the shading records (k_prepare_world_tris: Sg.tri_shade + 8 * n_tris).
 template <bool DETAIL, bool LDS, bool ONE_INST = false>
 __global__ __launch_bounds__(64 * RT_PT_WAVES, RT_PT_SIMD_WAVES) void RT_PT_KERNEL(DevScene Sg, DevFrame F, rt_scene_uniforms U,
                                                               uint32_t* __restrict__ ticket, uint32_t n_nodes_total,
@@ -36,6 +38,7 @@ __global__ __launch_bounds__(64 * RT_PT_WAVES, RT_PT_SIMD_WAVES) void RT_PT_KERN
   const uint32_t rec0 = (WAVES * (RT_WORK_BYTES_PER_WAVE + (SLIM ? RT_PT_COL_BYTES_PER_WAVE : 0u))) / 16;
   TravMem M;
   DevScene S = Sg;
+  const float4* wrec = nullptr;   // ONE_INST: the staged world records
   if (LDS) {
     // Small scene: the whole scene (traversal records AND the arrays shading reads) lives in LDS,
     // staged once per workgroup; only textures, the G-buffer and the accumulation buffer stay in HBM.
@@ -58,12 +61,19 @@ __global__ __launch_bounds__(64 * RT_PT_WAVES, RT_PT_SIMD_WAVES) void RT_PT_KERN
     f4* li = stage(Sg.inst_trav, (size_t)4 * n_inst_total);
     M.l_root = slot;
     stage(Sg.inst_root, ((size_t)n_inst_total + 3) / 4);
-    S.tri_shade = reinterpret_cast<const float4*>(stage(Sg.tri_shade, (size_t)8 * n_tris_total));
-    S.topo = reinterpret_cast<const float4*>(stage(Sg.topo, (size_t)5 * n_tris_total));
-    S.pos = reinterpret_cast<const float4*>(stage(Sg.pos, n_verts_total));   // S.nrm stays in global memory: no reader left here
-    // uv (8 B/vertex) and lights (8 B each): the device buffers are allocated with >= 16-byte slack
-    S.uv = reinterpret_cast<const float2*>(stage(Sg.uv, ((size_t)n_verts_total + 1) / 2));
-    S.inst = reinterpret_cast<const float4*>(stage(Sg.inst, (size_t)9 * n_inst_total));
+    // ONE_INST: the two slots of world record per triangle lie behind the shading records, and come along
+    S.tri_shade = reinterpret_cast<const float4*>(stage(Sg.tri_shade, (size_t)(ONE_INST ? 10 : 8) * n_tris_total));
+    if constexpr (ONE_INST) {
+      // topo, pos, uv and inst have no reader in these forms: light_pdf takes the world record, sample_light the shading
+      // record (one_leaf_lds_slots, k_pathtrace.hip.h)
+      wrec = S.tri_shade + 8 * n_tris_total;
+    } else {
+      S.topo = reinterpret_cast<const float4*>(stage(Sg.topo, (size_t)5 * n_tris_total));
+      S.pos = reinterpret_cast<const float4*>(stage(Sg.pos, n_verts_total));   // S.nrm stays in global memory: no reader left here
+      // uv (8 B/vertex) and lights (8 B each): the device buffers are allocated with >= 16-byte slack
+      S.uv = reinterpret_cast<const float2*>(stage(Sg.uv, ((size_t)n_verts_total + 1) / 2));
+      S.inst = reinterpret_cast<const float4*>(stage(Sg.inst, (size_t)9 * n_inst_total));
+    }
     S.lights = reinterpret_cast<const uint2*>(stage(Sg.lights, ((size_t)Sg.n_lights + 1) / 2));
     S.light_rec = reinterpret_cast<const float4*>(stage(Sg.light_rec, (size_t)4 * Sg.n_lights));
     __syncthreads();
@@ -175,7 +185,7 @@ __global__ __launch_bounds__(64 * RT_PT_WAVES, RT_PT_SIMD_WAVES) void RT_PT_KERN
       const uint32_t x = pixel_xy & 0xffffu, y = pixel_xy >> 16;
       const DevFrameSlot slot = slots[item_slot];
       if constexpr (SLIM) p.pixel = y * rt_fresh(U.width) + x;
-      alive = LEAN ? start_sample<true>(S, F, fresh_size(U), cam, slot, x, y, p)
+      alive = LEAN ? start_sample<true, ONE_INST>(S, F, fresh_size(U), cam, slot, x, y, p, wrec)
                    : start_sample<true>(S, F, U, cam, slot, x, y, p);
     }
     const bool running = alive;
@@ -194,7 +204,8 @@ __global__ __launch_bounds__(64 * RT_PT_WAVES, RT_PT_SIMD_WAVES) void RT_PT_KERN
     if (running) {
       if (DETAIL) cnt_shaded++;
       BounceOut bo;
-      shade_bounce(S, LEAN ? rt_fresh(U.light_count) : U.light_count, LEAN ? rt_fresh(F.max_depth) : F.max_depth, p, bo);
+      shade_bounce<ONE_INST>(S, LEAN ? rt_fresh(U.light_count) : U.light_count, LEAN ? rt_fresh(F.max_depth) : F.max_depth, p,
+                             bo, wrec);
       want_shadow = bo.want_shadow;
       want_extend = bo.want_extend;
       nee_valid = bo.nee_valid;
@@ -245,7 +256,7 @@ __global__ __launch_bounds__(64 * RT_PT_WAVES, RT_PT_SIMD_WAVES) void RT_PT_KERN
           p.hit_t = t_;
           p.tri = (uint32_t)tri_;
           p.inst = (uint32_t)inst_;
-          setup_surface(S, p, false, 0.0f, 0.0f, 0u);
+          setup_surface<ONE_INST>(S, p, false, 0.0f, 0.0f, 0u, wrec);
           p.depth++;
         }
       }

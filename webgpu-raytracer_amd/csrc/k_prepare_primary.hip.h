@@ -62,6 +62,45 @@ __global__ void k_prepare_lights(DevScene S, float4* __restrict__ light_rec, uin
   light_rec[4 * i + 2] = make_float4(w.v2.x, w.v2.y, w.v2.z, n_raw.y);
   light_rec[4 * i + 3] = make_float4(n_raw.z, rt_u2f(ref.y), 0.0f, 0.0f);
 }
+// Per-triangle world records of a scene whose TLAS is one node, a leaf: every hit is in the instance that node names, so
+// what the kernels would compute per hit from (instance, triangle) alone is made here once per upload, by the very
+// functions they call (the library is compiled without contraction and with correctly rounded division, square root and
+// normalisation: the same expression on the same inputs gives the same bits in any kernel, NaN of a zero-area triangle
+// included).
+//   tri_world    2 x float4 / tri   {geom_n.xyz, light area} {light normal.xyz, 0}: setup_surface's geometric normal, and
+//                area and unit normal of the world-space triangle as light_pdf computes them.  The host places them
+//                behind the n_tris shading records, in the same buffer (tri_shade + 8 * n_tris)
+//   tri_shade_w  8 x float4 / tri   the shading record with the three vertex normals taken to world space and normalised,
+//                as k_primary_visibility does per pixel
+// Runs after k_prepare_tris / k_prepare_tri_shade / k_prepare_instances and the node pass (it reads their outputs).
+__global__ void k_prepare_world_tris(DevScene S, float4* __restrict__ tri_world, float4* __restrict__ tri_shade_w,
+                                     uint32_t n_tris, uint32_t n_inst) {
+  uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_tris) return;
+  // the instance of the TLAS leaf (node 0), as traverse<.., ONE_INST> reads it: further instances may exist, unreferenced
+  uint32_t inst = rt_f2u(S.tnodes[1].w) >> 3;
+  if (inst >= n_inst) inst = n_inst - 1;  // robust buffer access: clamp instead of faulting
+  const InvRows m = load_inv_rows(S, inst);
+  const rt3 e1 = xyz(S.tri_geom[RT_TRI_STRIDE * i + 1]), e2 = xyz(S.tri_geom[RT_TRI_STRIDE * i + 2]);
+  const rt3 geom_n = rt_normalize(normal_to_world(m, rt_normalize(rt_cross(e1, e2))));
+  const WorldTri w = world_triangle(S, i, inst);   // light_pdf's first lines, as in k_prepare_lights
+  const rt3 edge1 = w.v1 - w.v0;
+  const rt3 edge2 = w.v2 - w.v0;
+  const rt3 cr = rt_cross(edge1, edge2);
+  const float area = rt_length(cr) * 0.5f;
+  const rt3 normal = rt_normalize(cr);
+  tri_world[2 * i + 0] = make_float4(geom_n.x, geom_n.y, geom_n.z, area);
+  tri_world[2 * i + 1] = make_float4(normal.x, normal.y, normal.z, 0.0f);
+  const float4* ts = S.tri_shade + 8 * (size_t)i;
+  float4* dst = tri_shade_w + 8 * (size_t)i;
+  for (int k = 0; k < 4; k++) dst[k] = ts[k];
+  for (int k = 4; k < 7; k++) {
+    const float4 q = ts[k];
+    const rt3 wn = rt_normalize(normal_to_world(m, xyz(q)));
+    dst[k] = make_float4(wn.x, wn.y, wn.z, q.w);
+  }
+  dst[7] = ts[7];
+}
 __global__ void k_prepare_instances(const float4* __restrict__ inst, float4* __restrict__ inst_trav, uint32_t n) {
   uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -86,7 +125,10 @@ template <bool DETAIL, bool LDS>
 __global__ __launch_bounds__(LDS ? 256 : 64) void k_primary_visibility(DevScene Sg, DevFrame F, rt_scene_uniforms U,
                                                                        const DevFrameSlot* __restrict__ slots, uint32_t n_tiles,
                                                                        uint32_t n_nodes_total, uint32_t n_tris_total,
-                                                                       uint32_t n_inst_total, uint32_t n_verts_total) {
+                                                                       uint32_t n_inst_total, uint32_t n_verts_total,
+                                                                       const float4* __restrict__ tri_shade_w) {
+  // tri_shade_w (LDS form, one-leaf-TLAS scenes; else null): the shading records with world-space vertex normals
+  // (k_prepare_world_tris), staged in place of tri_shade
   extern __shared__ float4 s_primary[];
   DevScene S = Sg;
   if (LDS) {
@@ -101,7 +143,7 @@ __global__ __launch_bounds__(LDS ? 256 : 64) void k_primary_visibility(DevScene 
     S.nodes = stage(Sg.nodes, (size_t)2 * n_nodes_total);
     S.tri_geom = stage(Sg.tri_geom, (size_t)RT_TRI_STRIDE * n_tris_total);
     S.inst_trav = stage(Sg.inst_trav, (size_t)4 * n_inst_total);
-    S.tri_shade = stage(Sg.tri_shade, (size_t)8 * n_tris_total);
+    S.tri_shade = stage(tri_shade_w ? tri_shade_w : Sg.tri_shade, (size_t)8 * n_tris_total);
     __syncthreads();
   }
   const uint32_t tile_id = LDS ? blockIdx.x * 4u + (threadIdx.x >> 6) : blockIdx.x;
@@ -154,9 +196,12 @@ __global__ __launch_bounds__(LDS ? 256 : 64) void k_primary_visibility(DevScene 
       Bary b = barycentrics(S, (uint32_t)hit.tri, mul_point(m, eye), mul_dir(m, d));
       const float4* ts = S.tri_shade + 8 * (size_t)hit.tri;
       const float4 d0 = ts[0], d2 = ts[2], q4 = ts[4], q5 = ts[5], q6 = ts[6], q7 = ts[7];
-      rt3 wn0 = rt_normalize(normal_to_world(m, xyz(q4)));
-      rt3 wn1 = rt_normalize(normal_to_world(m, xyz(q5)));
-      rt3 wn2 = rt_normalize(normal_to_world(m, xyz(q6)));
+      rt3 wn0 = xyz(q4), wn1 = xyz(q5), wn2 = xyz(q6);
+      if (!LDS || !tri_shade_w) {   // wave-uniform
+        wn0 = rt_normalize(normal_to_world(m, wn0));
+        wn1 = rt_normalize(normal_to_world(m, wn1));
+        wn2 = rt_normalize(normal_to_world(m, wn2));
+      }
       rt3 n = rt_normalize(wn0 * b.w + wn1 * b.u + wn2 * b.v);
       rt2 pn = pack_normal(n);
       rt3 albedo = xyz(d0);

@@ -198,7 +198,11 @@ __device__ __forceinline__ WorldTri world_triangle(const DevScene& S, uint32_t t
   w.v2 = rt_mat_mul_point(m, xyz(S.pos[rt_f2u(idx.z)]));
   return w;
 }
-__device__ LightSample sample_light(const DevScene& S, uint32_t light_count, rt3 hit_p, uint32_t& rng) {  // :345-399
+// REC (the one-leaf forms of the persistent kernel): the picked light's emission, base-colour texture index and texture
+// coordinates come from its shading record (k_prepare_tri_shade copied them there from topo / uv: the same bits), so that
+// those forms need neither topo nor uv
+template <bool REC>
+__device__ __forceinline__ LightSample sample_light_impl(const DevScene& S, uint32_t light_count, rt3 hit_p, uint32_t& rng) {  // :345-399
   LightSample none;
   none.L = rt3_splat(0.0f);
   none.dir = rt3_splat(0.0f);
@@ -232,12 +236,24 @@ __device__ LightSample sample_light(const DevScene& S, uint32_t light_count, rt3
   rt3 unit_l = l_dir / dist;
   float cos_l = rt_max(rt_dot(n_raw, -unit_l), 0.0f);
   if (cos_l < 1e-6f) return none;
-  float4 idx = S.topo[5 * ref.y], d0 = S.topo[5 * ref.y + 1], d2 = S.topo[5 * ref.y + 3];
-  rt3 L = xyz(d0);
-  if (d2.x > -0.5f) {
-    float2 a = S.uv[rt_f2u(idx.x)], b = S.uv[rt_f2u(idx.y)], c = S.uv[rt_f2u(idx.z)];
-    rt2 tuv = rt2_make(a.x, a.y) * u + rt2_make(b.x, b.y) * v + rt2_make(c.x, c.y) * ww;
-    L = L * sample_tex(S, tuv, rt_f2i32_sat(d2.x));
+  rt3 L;
+  if constexpr (REC) {
+    const float4* ts = S.tri_shade + 8 * (size_t)ref.y;
+    const float4 d0 = ts[0], d2 = ts[2];
+    L = xyz(d0);
+    if (d2.x > -0.5f) {
+      const float4 q4 = ts[4], q5 = ts[5], q6 = ts[6], q7 = ts[7];
+      rt2 tuv = rt2_make(q4.w, q5.w) * u + rt2_make(q6.w, q7.x) * v + rt2_make(q7.y, q7.z) * ww;
+      L = L * sample_tex(S, tuv, rt_f2i32_sat(d2.x));
+    }
+  } else {
+    float4 idx = S.topo[5 * ref.y], d0 = S.topo[5 * ref.y + 1], d2 = S.topo[5 * ref.y + 3];
+    L = xyz(d0);
+    if (d2.x > -0.5f) {
+      float2 a = S.uv[rt_f2u(idx.x)], b = S.uv[rt_f2u(idx.y)], c = S.uv[rt_f2u(idx.z)];
+      rt2 tuv = rt2_make(a.x, a.y) * u + rt2_make(b.x, b.y) * v + rt2_make(c.x, c.y) * ww;
+      L = L * sample_tex(S, tuv, rt_f2i32_sat(d2.x));
+    }
   }
   LightSample s;
   s.L = L;
@@ -245,6 +261,12 @@ __device__ LightSample sample_light(const DevScene& S, uint32_t light_count, rt3
   s.dist = dist;
   s.pdf = rt_div(rt_div(dist_sq, cos_l * area), (float)light_count);
   return s;
+}
+__device__ LightSample sample_light(const DevScene& S, uint32_t light_count, rt3 hit_p, uint32_t& rng) {
+  return sample_light_impl<false>(S, light_count, hit_p, rng);
+}
+__device__ LightSample sample_light_rec(const DevScene& S, uint32_t light_count, rt3 hit_p, uint32_t& rng) {
+  return sample_light_impl<true>(S, light_count, hit_p, rng);
 }
 __device__ float light_pdf(const DevScene& S, uint32_t light_count, uint32_t tri, uint32_t inst, float t,
                            rt3 l_dir) {  // :401-421
@@ -254,6 +276,17 @@ __device__ float light_pdf(const DevScene& S, uint32_t light_count, uint32_t tri
   rt3 cr = rt_cross(edge1, edge2);
   float area = rt_length(cr) * 0.5f;
   rt3 normal = rt_normalize(cr);
+  float cos_l = rt_max(rt_dot(normal, -l_dir), 0.0f);
+  if (cos_l < 1e-4f) return 0.0f;
+  float dist_sq = t * t;
+  return rt_div(rt_div(dist_sq, cos_l * area), (float)light_count);
+}
+// light_pdf with the triangle's area and unit normal read from its world record (k_prepare_world_tris made them at upload
+// time from world_triangle(S, tri, inst), by the operations above): the one-leaf forms of the persistent kernel
+__device__ float light_pdf_rec(const float4* wrec, uint32_t light_count, uint32_t tri, float t, rt3 l_dir) {
+  const float4 r0 = wrec[2 * tri], r1 = wrec[2 * tri + 1];
+  float area = r0.w;
+  rt3 normal = xyz(r1);
   float cos_l = rt_max(rt_dot(normal, -l_dir), 0.0f);
   if (cos_l < 1e-4f) return 0.0f;
   float dist_sq = t * t;

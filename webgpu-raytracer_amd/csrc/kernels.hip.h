@@ -3,7 +3,8 @@
 //   k_common.hip.h            helpers, texture fetch, RNG
 //   k_intersect.hip.h         rays, slab / triangle tests, per-lane stackless walk
 //   k_shading.hip.h           surface frame, BSDFs, light sampling, counters
-//   k_prepare_primary.hip.h   k_prepare_tris / _instances / _lights (upload-time re-layout, device_scene.h) and
+//   k_prepare_primary.hip.h   k_prepare_tris / _tri_shade / _instances / _lights / _world_tris (upload-time re-layout and
+//                             per-triangle world records of one-leaf-TLAS scenes, device_scene.h) and
 //                             k_primary_visibility: the hardware-raster G-buffer pass (Rasterizer.wgsl:81-173,
 //                             RasterizerPass.ts:97-140) as one closest-hit cast per pixel
 //   k_treelet.hip.h           upload-time re-layout of the node array: explicit successors, most-visited nodes first

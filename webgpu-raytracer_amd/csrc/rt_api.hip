@@ -90,6 +90,8 @@ struct rt_ctx {
   } world;
   // derived buffers (device_scene.h)
   DeviceBuffer tri_geom, tri_shade, inst_trav, light_rec;
+  DeviceBuffer tri_shade_w;   // per-triangle world records of a one-leaf-TLAS scene (k_prepare_world_tris); the path tracer's
+                              // part, tri_world, lies behind the shading records in tri_shade
   DeviceBuffer tnodes, node_key, node_newidx, inst_root, root_w, treelet_work;   // k_treelet.hip.h
   DeviceBuffer pairs, pair_of, pair_parent, root_rec;                             // k_pairs.hip.h
   uint32_t n_pairs = 0;             // inner nodes of the uploaded TLAS ++ BLAS arrays (counted on the host at upload)
@@ -98,6 +100,8 @@ struct rt_ctx {
                                     // node array or the SET of BLAS roots changed
   std::vector<float> root_w_host;                                   // per entry of blas_roots: sum of squared instance scales
   bool tris_dirty = true, inst_dirty = true, lights_dirty = true, nodes_dirty = true, pairs_dirty = true;
+  bool world_rec_dirty = true;      // tri_world / tri_shade_w: set with tris_dirty, inst_dirty and nodes_dirty, cleared when
+                                    // prepare_scene has rebuilt them (only for a scene that takes a one-leaf LDS form)
   bool pairs_wanted = false;        // rt_debug_read_pairs: build the pair records whatever walk is selected
   int wf_block = 0;              // threads per workgroup of the wavefront trace kernels (0 = default; MI355RT_WF_BLOCK)
   size_t lds_per_cu = 160 * 1024;
@@ -495,6 +499,15 @@ static int validate_scene(rt_ctx* c) {
   return RT_OK;
 }
 
+// the whole scene fits one workgroup's LDS beside four wave queues (the persistent kernel's LDS forms)
+bool scene_fits_lds(const rt_ctx* c) {
+  const size_t scene_lds = rtk::scene_lds_slots(c->n_nodes, c->n_tris, c->n_instances, c->n_verts, c->n_lights) * 16;
+  return !c->no_lds_staging && scene_lds + (size_t)4 * RT_WORK_BYTES_PER_WAVE <= 64 * 1024;
+}
+// ... and its TLAS is one node, which is a leaf (k_validate_scene, or the world update's builder): the one-leaf forms, which
+// read the per-triangle world records
+bool one_leaf_lds(const rt_ctx* c) { return scene_fits_lds(c) && c->blas_offset == 1; }
+
 int prepare_scene(rt_ctx* c) {
   {
     int r = validate_scene(c);
@@ -507,7 +520,7 @@ int prepare_scene(rt_ctx* c) {
                        (const float4*)c->topology.ptr, (const float4*)c->pos.ptr, (float4*)c->tri_geom.ptr,
                        c->n_tris, c->n_verts);
     HIP_TRY(c, hipGetLastError());
-    r = ensure_buffer(c, c->tri_shade, (size_t)c->n_tris * 128, true);
+    r = ensure_buffer(c, c->tri_shade, (size_t)c->n_tris * (128 + 32), true);   // + tri_world (k_prepare_world_tris)
     if (r < 0) return r;
     hipLaunchKernelGGL(rtk::k_prepare_tri_shade, dim3((c->n_tris + 255) / 256), dim3(256), 0, c->stream,
                        (const float4*)c->topology.ptr, (const float4*)c->nrm.ptr, (const float2*)c->uv.ptr,
@@ -621,6 +634,18 @@ int prepare_scene(rt_ctx* c) {
                        (float4*)c->light_rec.ptr, c->n_lights, c->n_tris, c->n_instances);
     HIP_TRY(c, hipGetLastError());
     c->lights_dirty = false;
+  }
+  // per-triangle world records: only a scene that takes a one-leaf LDS form reads them (a large animated world does not
+  // pay for them on every update); the flag stays set until they are built
+  if (c->world_rec_dirty && one_leaf_lds(c) && c->n_tris && c->n_verts && c->n_instances && c->n_nodes) {
+    int r = ensure_buffer(c, c->tri_shade_w, (size_t)c->n_tris * 128, true);
+    if (r < 0) return r;
+    DevScene S = dev_scene(c);
+    hipLaunchKernelGGL(rtk::k_prepare_world_tris, dim3((c->n_tris + 255) / 256), dim3(256), 0, c->stream, S,
+                       (float4*)c->tri_shade.ptr + (size_t)8 * c->n_tris, (float4*)c->tri_shade_w.ptr, c->n_tris,
+                       c->n_instances);
+    HIP_TRY(c, hipGetLastError());
+    c->world_rec_dirty = false;
   }
   return RT_OK;
 }
@@ -766,7 +791,8 @@ void rt_destroy(rt_ctx* c) {
   (void)hipStreamSynchronize(c->stream);
   dist_release(c);
   DeviceBuffer* all[] = {&c->topology, &c->instances, &c->lights, &c->draw_commands, &c->pos, &c->nrm, &c->uv,
-                         &c->nodes, &c->textures, &c->tri_geom, &c->tri_shade, &c->inst_trav, &c->light_rec, &c->accum, &c->render_target,
+                         &c->nodes, &c->textures, &c->tri_geom, &c->tri_shade, &c->inst_trav, &c->light_rec, &c->tri_shade_w,
+                         &c->accum, &c->render_target,
                          &c->g_normal, &c->g_depth, &c->history[0], &c->history[1], &c->counters, &c->ticket,
                          &c->slots, &c->gbuf_batch, &c->frame_col, &c->wf_state, &c->wf_queues, &c->wf_counters,
                          &c->tex_staging, &c->bv_in, &c->bv_tri, &c->bv_order, &c->bv_nodes, &c->bv_out,
@@ -1449,7 +1475,7 @@ static int world_update_body(rt_ctx* c, const rt_world_frame* f, bool* touched) 
     c->validate_dirty = false;
     c->scene_valid = true;
     c->nodes_from_device = true;
-    c->tris_dirty = c->inst_dirty = c->lights_dirty = c->nodes_dirty = c->pairs_dirty = c->roots_dirty = true;
+    c->tris_dirty = c->inst_dirty = c->lights_dirty = c->nodes_dirty = c->pairs_dirty = c->roots_dirty = c->world_rec_dirty = true;
     if (W.cache_enabled && !W.static_cached) {   // first full update of this description: keep the static geometries' node blocks
       W.static_count.assign(G, 0u);
       W.static_off.assign(G, 0u);
@@ -1485,7 +1511,7 @@ int rt_world_update(rt_ctx* c, const rt_world_frame* f) {
     c->scene_valid = false;
     c->validate_dirty = false;
     c->scene_problem = "the device-resident world update failed part-way (" + why + "): the scene buffers hold a mix of two scenes; upload the scene again";
-    c->tris_dirty = c->inst_dirty = c->lights_dirty = c->nodes_dirty = c->pairs_dirty = c->roots_dirty = true;
+    c->tris_dirty = c->inst_dirty = c->lights_dirty = c->nodes_dirty = c->pairs_dirty = c->roots_dirty = c->world_rec_dirty = true;
     c->world.static_cached = false;
     c->world.valid = false;
     c->error = why;
@@ -1549,6 +1575,7 @@ int rt_upload(rt_ctx* c, rt_kind kind, const void* data, size_t bytes) {
       c->n_tris = (uint32_t)(bytes / sizeof(rt_topology));
       c->validate_dirty = true;
       c->tris_dirty = true;
+      c->world_rec_dirty = true;
       c->lights_dirty = true;
       return r;
     case RT_KIND_INSTANCE:
@@ -1582,6 +1609,7 @@ int rt_upload(rt_ctx* c, rt_kind kind, const void* data, size_t bytes) {
       c->nodes_dirty = true;
       c->validate_dirty = true;
       c->inst_dirty = true;
+      c->world_rec_dirty = true;
       c->lights_dirty = true;
       return r;
     case RT_KIND_LIGHTS:
@@ -1630,6 +1658,7 @@ int rt_upload_geometry(rt_ctx* c, const float* pos4, const float* nrm4, const fl
   c->vertex_count = vertex_count;
   c->validate_dirty = true;
   c->tris_dirty = true;
+  c->world_rec_dirty = true;
   c->lights_dirty = true;
   return (r0 | r1 | r2) ? RT_REALLOCATED : RT_OK;
 }
@@ -1670,6 +1699,7 @@ int rt_upload_bvh(rt_ctx* c, const float* tlas, uint32_t n_tlas, const float* bl
   c->roots_dirty = true;
   c->validate_dirty = true;
   c->nodes_dirty = true;
+  c->world_rec_dirty = true;
   c->pairs_dirty = true;
   c->nodes_from_device = false;
   return r ? RT_REALLOCATED : RT_OK;
@@ -1974,7 +2004,7 @@ static int compute_frames(rt_ctx* c, const uint32_t* frame_counts, uint32_t n, u
 
   const size_t npx = (size_t)c->width * c->height;
   const size_t scene_lds = rtk::scene_lds_slots(c->n_nodes, c->n_tris, c->n_instances, c->n_verts, c->n_lights) * 16;
-  const bool fits_lds = !c->no_lds_staging && scene_lds + (size_t)4 * RT_WORK_BYTES_PER_WAVE <= 64 * 1024;
+  const bool fits_lds = scene_fits_lds(c);
   // auto: the wavefront form pays from 4 frames per dispatch (measured: 1 frame 11.9 vs 8.7 ms persistent, 2: 17.0 vs
   // 15.7, 4: 27.8 vs 29.5, 8: 47.9 vs 57.0 on sponza-like) — a single frame leaves its deeper stages too few rays
   const bool wavefront = c->spp == 1 && (c->variant == 2 || (c->variant == 3 && !fits_lds && n >= 4));
@@ -2052,16 +2082,18 @@ static int compute_frames(rt_ctx* c, const uint32_t* frame_counts, uint32_t n, u
   if (ptiles) {
     const size_t plds = rtk::primary_lds_slots(c->n_nodes, c->n_tris, c->n_instances, c->n_verts) * 16;
     const uint32_t nn = c->n_nodes, nt = c->n_tris, ni = c->n_instances, nv = c->n_verts;
+    // one-leaf scenes: the LDS form stages the shading records with world-space vertex normals
+    const float4* tsw = (one_leaf_lds(c) && !c->world_rec_dirty) ? (const float4*)c->tri_shade_w.ptr : nullptr;
     if (plds <= 32 * 1024 && !c->no_lds_staging) {  // small scene: records staged in LDS, four tiles per workgroup
       const dim3 grid((ptiles + 3) / 4, n);
       if (c->detailed_counters)
-        hipLaunchKernelGGL((rtk::k_primary_visibility<true, true>), grid, dim3(256), plds, c->stream, S, Fp, c->uniforms, dslots, ptiles, nn, nt, ni, nv);
+        hipLaunchKernelGGL((rtk::k_primary_visibility<true, true>), grid, dim3(256), plds, c->stream, S, Fp, c->uniforms, dslots, ptiles, nn, nt, ni, nv, tsw);
       else
-        hipLaunchKernelGGL((rtk::k_primary_visibility<false, true>), grid, dim3(256), plds, c->stream, S, Fp, c->uniforms, dslots, ptiles, nn, nt, ni, nv);
+        hipLaunchKernelGGL((rtk::k_primary_visibility<false, true>), grid, dim3(256), plds, c->stream, S, Fp, c->uniforms, dslots, ptiles, nn, nt, ni, nv, tsw);
     } else if (c->detailed_counters) {
-      hipLaunchKernelGGL((rtk::k_primary_visibility<true, false>), dim3(ptiles, n), dim3(64), 0, c->stream, S, Fp, c->uniforms, dslots, ptiles, nn, nt, ni, nv);
+      hipLaunchKernelGGL((rtk::k_primary_visibility<true, false>), dim3(ptiles, n), dim3(64), 0, c->stream, S, Fp, c->uniforms, dslots, ptiles, nn, nt, ni, nv, tsw);
     } else {
-      hipLaunchKernelGGL((rtk::k_primary_visibility<false, false>), dim3(ptiles, n), dim3(64), 0, c->stream, S, Fp, c->uniforms, dslots, ptiles, nn, nt, ni, nv);
+      hipLaunchKernelGGL((rtk::k_primary_visibility<false, false>), dim3(ptiles, n), dim3(64), 0, c->stream, S, Fp, c->uniforms, dslots, ptiles, nn, nt, ni, nv, tsw);
     }
   }
   if (ev) HIP_TRY(c, hipEventRecord(ev->b, c->stream));
@@ -2091,7 +2123,12 @@ static int compute_frames(rt_ctx* c, const uint32_t* frame_counts, uint32_t n, u
     if (!fits_lds) plan = plan_lds(c, c->lds_per_cu / 6, (size_t)4 * RT_WORK_BYTES_PER_WAVE, &dyn);
     // LDS form of a scene whose TLAS is one node, which is a leaf (k_validate_scene, or the world update's builder): the walks skip the TLAS
     // half of the node step (k_traverse.hip.h traverse<.., ONE_INST>)
-    const bool one_inst = fits_lds && c->blas_offset == 1;
+    const bool one_inst = one_leaf_lds(c);
+    if (one_inst && c->world_rec_dirty) return fail(c, RT_ERR_INTERNAL, "one-leaf form without its world records");
+    // These forms stage less than scene_lds (rtk::one_leaf_lds_slots): the launch asks for what they stage, while the
+    // choice of the form, here and below, stays on scene_lds, the size the two sides of each line were measured at
+    const size_t staged_lds = one_inst ? rtk::one_leaf_lds_slots(c->n_nodes, c->n_tris, c->n_instances, c->n_lights) * 16 : scene_lds;
+    if (one_inst) dyn = (size_t)4 * RT_WORK_BYTES_PER_WAVE + staged_lds;
     // the product build of that form in 512-thread workgroups (k_pathtrace_persistent_wide, 6 waves per SIMD) when three of
     // them, each with eight wave queues, eight waves' parked sample sums and one copy of the scene, fit the CU's LDS, and the
     // dispatch carries more than one frame: a single 1080p frame gives its 6 144 waves 1.3 tickets each, and there the
@@ -2099,7 +2136,7 @@ static int compute_frames(rt_ctx* c, const uint32_t* frame_counts, uint32_t n, u
     // frame: 0.906 -> 0.945 ms per frame)
     const size_t dyn_wide = (size_t)8 * (RT_WORK_BYTES_PER_WAVE + RT_PT_COL_BYTES_PER_WAVE) + scene_lds;
     const bool wide = one_inst && !c->detailed_counters && n > 1 && dyn_wide <= c->lds_per_cu / 3;
-    if (wide) dyn = dyn_wide;
+    if (wide) dyn = (size_t)8 * (RT_WORK_BYTES_PER_WAVE + RT_PT_COL_BYTES_PER_WAVE) + staged_lds;
     const int vi = wide ? 6 : one_inst ? (c->detailed_counters ? 5 : 4) : (c->detailed_counters ? 2 : 0) + (fits_lds ? 1 : 0);
     const uint32_t waves = wide ? 8u : 4u;   // per workgroup
     static const void* const fns[7] = {(const void*)rtk::k_pathtrace_persistent<false, false>,
