@@ -298,6 +298,39 @@ int rt_debug_ieee_check(rt_ctx* ctx, int op, uint64_t first, uint64_t count, rt_
 int rt_set_kernel_variant(rt_ctx* ctx, int variant);
 int rt_device_count(void);
 
+/* ---- ray queries against the uploaded scene: "what does this ray hit?" (picking, line of sight, bakes, placement) ----
+ * The rays go through the acceleration structure the renderer keeps on the device - after rt_upload* as after
+ * rt_world_update, whose arrays never reach the host - with the walks of the wavefront trace kernels (k_ray_query,
+ * csrc/k_rayquery.hip.h).  Results are those of intersect_tlas / intersect_tlas_shadow (Raytracer.wgsl:496-528, 566-600):
+ *   RT_RAYS_CLOSEST  {t, tri, inst, hit = 1} of the closest hit with t_min < t < t_max; a miss is {the ray's t_max, bits
+ *                    unchanged, -1, -1, 0}
+ *   RT_RAYS_ANY      {0, -1, -1, hit = 1 when anything lies in (t_min, t_max), else 0}
+ * tri is the global triangle index and inst the TLAS-order instance index, the numbers rt_read_gbuffer and the topology
+ * array use.  Directions need not be normalised; t counts in units of the direction's length.  t_max is per ray (rt_ray),
+ * t_min one value per call, >= 0 (the renderer's own rays use 0.001).  A scene with blas_base_idx == 0 (no TLAS) is missed
+ * by every ray.
+ * The floats of a ray are not validated: both walks terminate for any bit pattern (node order is strictly increasing,
+ * k_validate_scene; the pair walk's stack is finite), and a NaN, an infinity or a zero direction gets whatever the
+ * reference's arithmetic gives it.
+ * The form of the kernel is picked as for the wavefront trace kernels (rt_set_walk / MI355RT_WALK, MI355RT_NO_LDS_STAGING,
+ * MI355RT_WF_RAYREG, the size of the scene), in 256-thread workgroups; rt_set_kernel_variant does not matter.
+ * A query leaves the renderer as it was: accumulation, jitter and frame counts, the rt_counters, the G-buffer and the frames
+ * traced ahead under rt_set_lookahead are untouched, and a render interrupted by queries is bit for bit the uninterrupted one.
+ *   rt_trace_rays          blocking: copies n rays in, traces, copies n hits out (staging buffers are kept and grown).  stats
+ *                          != NULL also runs the node / triangle counting kernel and fills *stats.  n == 0 is RT_OK; n >= 2^31,
+ *                          a NULL pointer, an unknown mode or a t_min that is negative or NaN is RT_ERR_INVALID; without a
+ *                          valid scene (nothing uploaded, a scene k_validate_scene refused, the state after a failed
+ *                          rt_world_update) RT_ERR_NOT_READY with the reason in rt_last_error.
+ *   rt_trace_rays_device   the same on device-accessible arrays (n rt_ray in, n rt_ray_hit out; 16-byte aligned, on the
+ *                          context's device): only enqueues on the context's stream (rt_set_stream respected), no host
+ *                          synchronisation - the entry for torch tensors.  Counts nodes and triangles while
+ *                          rt_set_counting(ctx, 1) is on.
+ *   rt_ray_query_stats     stats of the last query (blocking: fences the stream). */
+enum { RT_RAYS_CLOSEST = 0, RT_RAYS_ANY = 1 };
+int rt_trace_rays(rt_ctx* ctx, const rt_ray* rays, uint32_t n, int mode, float t_min, rt_ray_hit* out, rt_ray_stats* stats);
+int rt_trace_rays_device(rt_ctx* ctx, const void* dev_rays, uint32_t n, int mode, float t_min, void* dev_out);
+int rt_ray_query_stats(rt_ctx* ctx, rt_ray_stats* out);
+
 /* ---- the sharded image: one picture rendered by `world` contexts ("ranks"), assembled on rank 0 ----
  * Rank k owns the image rows y with (y / stripe_rows) % world == k and traces only those (rt_set_stripes).  Its COMPACT
  * BLOCK holds the rows it owns in ascending y, width float4 each, padded with zero rows to max_rows = the largest share

@@ -108,8 +108,33 @@ typedef struct rt_world_frame {
   const float* joint_mats;             /* 16 f32 each (column-major), this frame */
 } rt_world_frame;
 
+/* ---- ray queries (rt_trace_rays, mi355rt.h) ---- */
+typedef struct rt_ray {       /* 32 B: the trace kernels' own queue record {o, t_max} {d, -} */
+  float origin[3];
+  float t_max;
+  float dir[3];               /* need not be normalised */
+  uint32_t pad;
+} rt_ray;
+typedef struct rt_ray_hit {   /* 16 B */
+  float t;
+  int32_t tri;                /* global triangle index (the topology array's, rt_read_gbuffer's), -1 = none */
+  int32_t inst;               /* TLAS-order instance index, -1 = none */
+  uint32_t hit;
+} rt_ray_hit;
+typedef struct rt_ray_stats { /* of ONE call */
+  uint64_t rays, nodes_visited, tris_tested; /* the last two only from the counting kernel, else 0 */
+  uint32_t walk;              /* 0 node, 1 pairs */
+  uint32_t lds;               /* every traversal record staged in LDS */
+  uint32_t rayreg;            /* node walk, mixed mode: RAYREG form */
+  uint32_t workgroups;        /* launched */
+  double kernel_ms;           /* device events around the launch while rt_set_kernel_timing is on, else 0 */
+} rt_ray_stats;
+
 #ifdef __cplusplus
 }
+static_assert(sizeof(rt_ray) == 32, "rt_ray is 32 bytes");
+static_assert(sizeof(rt_ray_hit) == 16, "rt_ray_hit is 16 bytes");
+static_assert(sizeof(rt_ray_stats) == 48, "rt_ray_stats is 48 bytes");
 static_assert(sizeof(rt_topology) == 80, "MeshTopology is 80 bytes");
 static_assert(sizeof(rt_node) == 32, "BVHNode is 32 bytes");
 static_assert(sizeof(rt_instance) == 144, "Instance is 144 bytes");

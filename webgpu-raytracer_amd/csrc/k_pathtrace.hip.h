@@ -395,6 +395,7 @@ __device__ __forceinline__ uint32_t trav_stage_mixed(TravMem& M, f4* lds, uint32
   M.ginst = reinterpret_cast<const f4*>(Sg.inst_trav);
   M.groot = Sg.inst_root;
   M.k_lds = P.k_nodes;
+  M.t_min = RT_T_MIN;
   M.l_nodes = slot;
   lds_stage(lds + slot, Sg.tnodes, (size_t)2 * P.k_nodes);
   slot += 2u * P.k_nodes;

@@ -53,6 +53,7 @@ __global__ __launch_bounds__(64 * RT_PT_WAVES, RT_PT_SIMD_WAVES) void RT_PT_KERN
     M.gnodes = M.gtri = M.ginst = nullptr;
     M.groot = nullptr;
     M.k_lds = n_nodes_total;
+    M.t_min = RT_T_MIN;
     M.l_nodes = slot;
     f4* ln = stage(Sg.tnodes, (size_t)2 * n_nodes_total);
     M.l_tri = slot;

@@ -46,6 +46,8 @@ struct TravMem {
   const uint32_t* groot;      // inst_root, 1 per instance: index in tnodes of the instance's BLAS root
   uint32_t k_lds;             // nodes [0, k_lds) are read from LDS
   uint32_t l_nodes, l_tri, l_inst, l_root;
+  float t_min;                // RT_T_MIN (a compile-time constant in every render kernel: whoever fills a TravMem sets it);
+                              // the ray query (k_rayquery.hip.h) takes its caller's
 };
 
 // MODE_LDS: every record is in LDS (the whole scene fits: k_lds >= n_nodes and all l_* set) — the compiler sees plain
@@ -201,7 +203,7 @@ struct Trav {
                              // entry): the triangle tests read them there, the node steps never need them
   LocalRay rw;               // the world-space ray (rw.o, rw.d = the ray as given)
   rt3 io, id;                // trav_post_at_entry() == false only: origin and direction of the instance-space ray
-  float closest;             // t_min is the constant RT_T_MIN for every ray of the reference (Raytracer.wgsl:6,688,732)
+  float closest;             // t_min is per launch (TravMem::t_min): RT_T_MIN for every ray of the reference (Raytracer.wgsl:6,688,732)
   int32_t best_tri, best_inst;
   uint32_t curr, tlas_next, cur_inst, leaf, resume;
 #ifdef RT_LANE_STATS
@@ -304,7 +306,7 @@ __device__ __forceinline__ void trav_node(const TravMem& M, const f4* lds, const
   // The three facts about the lane (box hit, inner node, walking the TLAS) as lane masks, combined by scalar and / andn2 and
   // handed back as conditions (inverse ballot: no instruction).  Written as bools the compiler computes `!inner` with a
   // second vector compare and `!in_tlas` with a scalar xor: two instructions more per step.
-  const unsigned long long hm = __builtin_amdgcn_ballot_w64(hit_box4(lo, hi, s.inv_d, s.o_inv_d, RT_T_MIN, s.closest));
+  const unsigned long long hm = __builtin_amdgcn_ballot_w64(hit_box4(lo, hi, s.inv_d, s.o_inv_d, M.t_min, s.closest));
   const unsigned long long im = __builtin_amdgcn_ballot_w64((int32_t)data < 0);           // RT_NODE_INNER is the sign bit
   const unsigned long long tm = __builtin_amdgcn_ballot_w64(s.tlas_next == RT_TLAS_NONE);
   const unsigned long long lm = hm & ~im;                                                  // a leaf whose box is hit
@@ -313,7 +315,7 @@ __device__ __forceinline__ void trav_node(const TravMem& M, const f4* lds, const
   const bool tlas_leaf = IN_BLAS ? false : __builtin_amdgcn_inverse_ballot_w64(lm & tm);
   const bool got_leaf = __builtin_amdgcn_inverse_ballot_w64(IN_BLAS ? lm : lm & ~tm);
 #else
-  const bool hit = hit_box4(lo, hi, s.inv_d, s.o_inv_d, RT_T_MIN, s.closest);
+  const bool hit = hit_box4(lo, hi, s.inv_d, s.o_inv_d, M.t_min, s.closest);
   const bool inner = (data & RT_NODE_INNER) != 0u;
   const bool leafhit = hit & !inner;
   const bool hit_inner = hit & inner;
@@ -559,13 +561,13 @@ struct NodeWalk {
       W.rays[2 * lane + 1] = rb;
     }
   }
-  static __device__ __forceinline__ void owner_ray(const TravMem&, const WaveWork& W, uint32_t owner, LocalRay& q, float& t_min,
+  static __device__ __forceinline__ void owner_ray(const TravMem& M, const WaveWork& W, uint32_t owner, LocalRay& q, float& t_min,
                                                    float& bound, bool& any) {
     const f4 ra = W.rays[2 * owner];
     const rt_f3_16 rb = *(const rt_f3_16 __attribute__((address_space(3)))*)(W.rays + 2 * owner + 1);   // 12 of the 16 bytes
     q.o = rt3_make(ra.x, ra.y, ra.z);
     q.d = rt3_make(rb.x, rb.y, rb.z);
-    t_min = RT_T_MIN;
+    t_min = M.t_min;
     bound = ra.w;
     any = ANY;
   }

@@ -266,18 +266,63 @@ struct WfPairWalk : PairWalk<DETAIL, LDS> {
   static __device__ __forceinline__ bool stepping(const PairLane& s) { return pw_can_step(s); }
 };
 
-// The body of both trace kernels after staging: pull rays off the queue, walk them, write their results, flush the counters.
-template <class WALK, int BLOCK>
-__device__ __forceinline__ void wf_trace_loop(const typename WALK::Mem& M, const f4* lds, const WaveWork& W, const DevFrame& F,
-                                              const rt_scene_uniforms& U, const WfQueues& Q, uint32_t depth) {
+// Where the trace loop's rays come from and where its results go.  A source hands out ray indices [0, n_rays) in chunks
+// of CHUNK behind one atomic counter (head); the loop asks it whether entry qi holds a ray, for the ray's two float4
+// {o, t_max} {d, -} and its bound, and gives a finished lane's state back under the index the ray came from.
+// WfQueueIO: the device queues of the wavefront form, by queue slot — ANY (shadow rays): one occlusion word; else
+// (extension rays): {t, triangle, instance} of the closest hit.  RayQueryIO (k_rayquery.hip.h): a caller's flat arrays.
+template <bool ANY>
+struct WfQueueIO;
+struct WfQueueSrc {   // what a kernel hands the loop: where its IO, the TLAS size and the counter shards come from
+  template <bool ANY>
+  using IO = WfQueueIO<ANY>;
+  const DevFrame& F;
+  const rt_scene_uniforms& U;
+  const WfQueues& Q;
+  uint32_t depth;
+  __device__ __forceinline__ uint32_t blas_base() const { return U.blas_base_idx; }
+  __device__ __forceinline__ uint64_t* counters() const { return F.counters; }
+};
+template <bool ANY>
+struct WfQueueIO {
+  static constexpr uint32_t CHUNK = RT_WF_CHUNK;
+  const WfQueues& Q;
+  uint32_t n_rays;
+  uint32_t* head;
+  const uint32_t* ids;
+  const float4* rays;
+  __device__ __forceinline__ explicit WfQueueIO(const WfQueueSrc& src) : Q(src.Q) {
+    const uint32_t depth = src.depth;
+    uint32_t* cnt = Q.counters + 8u * depth;
+    n_rays = ANY ? cnt[1] : cnt[2];
+    head = ANY ? &cnt[3] : &cnt[4];
+    ids = ANY ? Q.shadow_ids : Q.ext_ids;
+    rays = ANY ? Q.shadow_rays : Q.ext_rays[depth & 1u];
+  }
+  __device__ __forceinline__ bool valid(uint32_t qi) const { return ids[qi] != RT_WF_INVALID; }
+  __device__ __forceinline__ float4 ray0(uint32_t qi) const { return rays[2 * qi]; }       // {o, t_max}
+  __device__ __forceinline__ float4 ray1(uint32_t qi) const { return rays[2 * qi + 1]; }   // {d, -}
+  static __device__ __forceinline__ float t_max(float4 r0) { return ANY ? r0.w : RT_T_MAX; }   // (by value: by reference the kernels compile differently)
+  template <class WALK>
+  __device__ __forceinline__ void store(uint32_t slot, const typename WALK::Lane& s) const {
+    if (ANY)
+      Q.occluded[slot] = WALK::occluded(s) ? 1u : 0u;
+    else
+      Q.ext_hit[slot] = make_float4(s.closest, rt_u2f((uint32_t)s.best_tri), rt_u2f((uint32_t)s.best_inst), 0.0f);
+  }
+};
+
+// The body of the trace kernels after staging: pull rays off the source, walk them, write their results, flush the
+// counters (shard by wave).
+template <class WALK, int BLOCK, class SRC>
+__device__ __forceinline__ void wf_trace_loop(const typename WALK::Mem& M, const f4* lds, const WaveWork& W, const SRC& src) {
   constexpr bool ANY = WALK::ANY;
+  typedef typename SRC::template IO<ANY> IO;
   const uint32_t lane = threadIdx.x & 63u;
-  const uint32_t blas_base = U.blas_base_idx;
-  uint32_t* cnt = Q.counters + 8u * depth;
-  const uint32_t n_rays = ANY ? cnt[1] : cnt[2];
-  uint32_t* head = ANY ? &cnt[3] : &cnt[4];
-  const uint32_t* ids = ANY ? Q.shadow_ids : Q.ext_ids;
-  const float4* rays = ANY ? Q.shadow_rays : Q.ext_rays[depth & 1u];
+  const uint32_t blas_base = src.blas_base();
+  const IO io(src);
+  const uint32_t n_rays = io.n_rays;
+  uint32_t* head = io.head;
 
   // per-lane ray + traversal state
   bool have_ray = false;
@@ -309,10 +354,7 @@ __device__ __forceinline__ void wf_trace_loop(const typename WALK::Mem& M, const
       st_cnt[0]++;
 #endif
       if (done) {
-        if (ANY)
-          Q.occluded[slot] = WALK::occluded(s) ? 1u : 0u;
-        else
-          Q.ext_hit[slot] = make_float4(s.closest, rt_u2f((uint32_t)s.best_tri), rt_u2f((uint32_t)s.best_inst), 0.0f);
+        io.template store<WALK>(slot, s);
         have_ray = false;
       }
       // pull: needy lanes take consecutive entries of the wave's chunk; a new chunk costs one atomic
@@ -321,13 +363,13 @@ __device__ __forceinline__ void wf_trace_loop(const typename WALK::Mem& M, const
       if (queue_left && need_m != 0ull) {
         if (chunk_pos >= chunk_end) {
           uint32_t bq = 0;
-          if (lane == 0u) bq = atomicAdd(head, RT_WF_CHUNK);
+          if (lane == 0u) bq = atomicAdd(head, IO::CHUNK);
           bq = __shfl(bq, 0, 64);
           if (bq >= n_rays) {
             queue_left = false;
           } else {
             chunk_pos = bq;
-            chunk_end = bq + RT_WF_CHUNK < n_rays ? bq + RT_WF_CHUNK : n_rays;
+            chunk_end = bq + IO::CHUNK < n_rays ? bq + IO::CHUNK : n_rays;
           }
         }
         if (queue_left) {
@@ -335,12 +377,12 @@ __device__ __forceinline__ void wf_trace_loop(const typename WALK::Mem& M, const
               __builtin_amdgcn_mbcnt_hi((uint32_t)(need_m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)need_m, 0u));
           const uint32_t qi = chunk_pos + rank;
           chunk_pos += (uint32_t)__builtin_popcountll(need_m);
-          if (need && qi < chunk_end && ids[qi] != RT_WF_INVALID) {
-            const float4 r0 = rays[2 * qi], r1 = rays[2 * qi + 1];
+          if (need && qi < chunk_end && io.valid(qi)) {
+            const float4 r0 = io.ray0(qi), r1 = io.ray1(qi);
             slot = qi;
             n_traced++;
             have_ray = true;
-            WALK::begin(M, s, true, blas_base, xyz(r0), xyz(r1), ANY ? r0.w : RT_T_MAX, n_nodes);
+            WALK::begin(M, s, true, blas_base, xyz(r0), xyz(r1), IO::t_max(r0), n_nodes);
           }
         }
       }
@@ -384,7 +426,7 @@ __device__ __forceinline__ void wf_trace_loop(const typename WALK::Mem& M, const
   }
 #endif
   LaneCounters c = {0, ANY ? 0u : n_traced, ANY ? n_traced : 0u, n_nodes, n_tris, 0};
-  flush_counters<WALK::COUNT>(c, F.counters, blockIdx.x * (BLOCK / 64) + (threadIdx.x >> 6));
+  flush_counters<WALK::COUNT>(c, src.counters(), blockIdx.x * (BLOCK / 64) + (threadIdx.x >> 6));
 }
 
 // RAYREG (mixed mode only): the instance-space origin / direction stay in registers (RT_TRAV_MIXED_RAYREG, k_traverse.hip.h).
@@ -408,7 +450,7 @@ void k_wf_trace(DevScene Sg, DevFrame F, rt_scene_uniforms U, WfQueues Q, uint32
   }
   __syncthreads();
   constexpr int MODE = LDS ? RT_TRAV_LDS : (RAYREG ? RT_TRAV_MIXED_RAYREG : RT_TRAV_MIXED);
-  wf_trace_loop<WfNodeWalk<ANY, DETAIL, MODE>, BLOCK>(M, s_scene, W, F, U, Q, depth);
+  wf_trace_loop<WfNodeWalk<ANY, DETAIL, MODE>, BLOCK>(M, s_scene, W, WfQueueSrc{F, U, Q, depth});
 }
 
 template <bool ANY, bool DETAIL, bool LDS, int BLOCK>
@@ -428,7 +470,7 @@ void k_wf_trace_pairs(DevScene Sg, DevFrame F, rt_scene_uniforms U, WfQueues Q, 
     pw_stage(M, s_scene, rec0, Sg, plan, n_pairs_total, n_tris_total, n_inst_total, RT_T_MIN);
   }
   __syncthreads();
-  wf_trace_loop<WfPairWalk<ANY, DETAIL, LDS>, BLOCK>(M, s_scene, W, F, U, Q, depth);
+  wf_trace_loop<WfPairWalk<ANY, DETAIL, LDS>, BLOCK>(M, s_scene, W, WfQueueSrc{F, U, Q, depth});
 }
 
 // Ordered accumulation of a batched dispatch: acc = (frame_count > 1 ? acc : 0) + (col_f, 1) for f = 0..n-1, the

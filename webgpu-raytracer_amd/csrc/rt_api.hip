@@ -189,6 +189,15 @@ struct rt_ctx {
   DeviceBuffer gbuf_batch;  // G-buffer planes of frames 0..n-2 of a batch (the last frame uses the main planes)
   DeviceBuffer frame_col;   // per-frame colours of a batch, added in frame order by k_accumulate_frames
   DeviceBuffer wf_state, wf_queues, wf_counters;  // wavefront form: path state, ray / path queues, queue counters
+  // ray queries (rt_trace_rays): staging arrays of the host entry; the query's own counter shards with the chunk counter
+  // behind them; events around the launch; shape and stats of the last query
+  DeviceBuffer rq_rays, rq_hits, rq_counters;
+  hipEvent_t rq_ev[2] = {nullptr, nullptr};
+  bool rq_timed = false;            // the last query recorded its events
+  rt_ray_stats rq_last = {};
+  const void* rq_occ_fn = nullptr;  // cached occupancy query
+  size_t rq_occ_dyn = 0;
+  int rq_occ_blocks = 0;
 
   // kernel timing
   bool timing = false;
@@ -795,6 +804,7 @@ void rt_destroy(rt_ctx* c) {
                          &c->accum, &c->render_target,
                          &c->g_normal, &c->g_depth, &c->history[0], &c->history[1], &c->counters, &c->ticket,
                          &c->slots, &c->gbuf_batch, &c->frame_col, &c->wf_state, &c->wf_queues, &c->wf_counters,
+                         &c->rq_rays, &c->rq_hits, &c->rq_counters,
                          &c->tex_staging, &c->bv_in, &c->bv_tri, &c->bv_order, &c->bv_nodes, &c->bv_out,
                          &c->bv_counters, &c->bv_big, &c->val_roots, &c->val_bad, &c->tnodes, &c->node_key, &c->node_newidx,
                          &c->inst_root, &c->root_w, &c->treelet_work, &c->pairs, &c->pair_of, &c->pair_parent, &c->root_rec,
@@ -803,6 +813,8 @@ void rt_destroy(rt_ctx* c) {
                          &c->world.static_nodes};
   for (DeviceBuffer* b : all) free_buffer(*b);
   if (c->world.pinned) (void)hipHostFree(c->world.pinned);
+  for (hipEvent_t e : c->rq_ev)
+    if (e) (void)hipEventDestroy(e);
   if (c->world.ev0) (void)hipEventDestroy(c->world.ev0);
   if (c->world.ev1) (void)hipEventDestroy(c->world.ev1);
   if (c->world.ev_t0) (void)hipEventDestroy(c->world.ev_t0);
@@ -1779,6 +1791,68 @@ static rtk::PairPlan plan_pairs(const rt_ctx* c, size_t budget, size_t queue_byt
   return P;
 }
 
+// Form and workgroup shape of the trace kernels for the uploaded scene: what launch_wavefront runs k_wf_trace /
+// k_wf_trace_pairs in and rt_trace_rays its k_ray_query.  wf_block: threads per workgroup where not everything fits LDS
+// (0 = 256; the ray query has 256-thread forms only).
+struct TraceShape {
+  bool pairs, trace_lds, rayreg;
+  int block, blocks_per_cu;
+  size_t dyn;              // dynamic LDS per workgroup
+  rtk::PairPlan plan;      // pair walk: what a workgroup stages
+  rtk::LdsPlan nplan;      // node walk
+};
+static TraceShape trace_shape(const rt_ctx* c, bool fits_lds, int wf_block) {
+  const bool pairs = c->walk == 1 || (c->walk == 2 && c->n_instances == 1);   // rt_set_walk
+  // Workgroup shape of the trace kernels.  Every wave owns `wave_bytes` of LDS: the triangle work queue, and for the pair walk
+  // the stack of deferred right children.  Everything fits beside four wave blocks in 64 KB: 256-thread workgroups, all records
+  // in LDS.  Otherwise 256-thread workgroups, each staging what fits whole in its share of the LDS (plan_pairs / plan_lds): the
+  // pair walk as many per CU as the wave blocks allow (4 at K = 8), the node walk six (6 waves per SIMD).
+  // MI355RT_WF_BLOCK / MI355RT_WF_BLOCKS_PER_CU override the shape for sweeps.
+  const size_t wave_bytes = pairs ? RT_PW_BYTES_PER_WAVE : RT_WORK_BYTES_PER_WAVE;
+  const size_t lds_records =
+      (pairs ? (size_t)4 * c->n_pairs + (size_t)RT_TRI_STRIDE * c->n_tris + (size_t)6 * c->n_instances
+             : (size_t)2 * c->n_nodes + (size_t)RT_TRI_STRIDE * c->n_tris + (size_t)4 * c->n_instances + ((size_t)c->n_instances + 3) / 4) * 16;
+  const bool trace_lds = !c->no_lds_staging && fits_lds && lds_records + (size_t)4 * wave_bytes <= 64 * 1024;
+  int block = 256, blocks_per_cu = 0;
+  if (!trace_lds) {
+    block = wf_block ? wf_block : 256;
+    blocks_per_cu = c->wf_blocks_per_cu ? c->wf_blocks_per_cu
+                    : pairs ? std::max(1, std::min((int)(c->lds_per_cu / ((size_t)(block / 64) * wave_bytes)), (RT_WF_WAVES * 256) / block))
+                            : (block == 1024 ? 1 : (block == 512 ? 2 : 6));
+  }
+  const size_t queue_bytes = (size_t)(block / 64) * wave_bytes;
+  size_t dyn = queue_bytes + lds_records;
+  rtk::PairPlan plan;
+  plan.stage_pairs = plan.stage_inst = plan.stage_tri = 1;
+  plan.pad = 0;
+  rtk::LdsPlan nplan;
+  nplan.k_nodes = c->n_nodes;
+  nplan.stage_inst = nplan.stage_tri = 1;
+  nplan.pad = 0;
+  if (!trace_lds) {
+    const size_t budget = c->lds_per_cu / (size_t)blocks_per_cu;
+    if (pairs)
+      plan = plan_pairs(c, budget, queue_bytes, &dyn);
+    else
+      nplan = plan_lds(c, budget, queue_bytes, &dyn);
+  }
+  plan.troot = c->troot;
+  // few instances with deep trees (glass blob: 3 instances, 400 k nodes): a ray enters an instance once and then waits at
+  // many leaves; measured, the form that keeps its instance-space origin / direction in registers is the faster one there,
+  // the other one where rays enter many small instances (k_traverse.hip.h, trav_post_at_entry; MI355RT_WF_RAYREG=0/1 overrides)
+  const bool rayreg = !pairs && (c->wf_rayreg < 0 ? (size_t)c->n_nodes >= (size_t)1024 * std::max<size_t>(1, c->n_instances) : c->wf_rayreg != 0);
+  TraceShape T;
+  T.pairs = pairs;
+  T.trace_lds = trace_lds;
+  T.rayreg = rayreg;
+  T.block = block;
+  T.blocks_per_cu = blocks_per_cu;
+  T.dyn = dyn;
+  T.plan = plan;
+  T.nplan = nplan;
+  return T;
+}
+
 // The trace kernels by [workgroup size 256 / 512 / 1024][any][detail][lds].  The node walk's RAYREG form is compiled for
 // 256-thread workgroups in mixed mode only: [any][detail].
 #define RT_WF_TRACE_FNS(K, B)                                                                                          \
@@ -1833,45 +1907,12 @@ static int launch_wavefront(rt_ctx* c, const DevScene& S, const DevFrame& F, con
   Q.occluded = (uint32_t*)(qb + qcap * 128);
   Q.counters = (uint32_t*)c->wf_counters.ptr;
   const bool detail = c->detailed_counters;
-  const bool pairs = c->walk == 1 || (c->walk == 2 && c->n_instances == 1);   // rt_set_walk
-  // Workgroup shape of the trace kernels.  Every wave owns `wave_bytes` of LDS: the triangle work queue, and for the pair walk
-  // the stack of deferred right children.  Everything fits beside four wave blocks in 64 KB: 256-thread workgroups, all records
-  // in LDS.  Otherwise 256-thread workgroups, each staging what fits whole in its share of the LDS (plan_pairs / plan_lds): the
-  // pair walk as many per CU as the wave blocks allow (4 at K = 8), the node walk six (6 waves per SIMD).
-  // MI355RT_WF_BLOCK / MI355RT_WF_BLOCKS_PER_CU override the shape for sweeps.
-  const size_t wave_bytes = pairs ? RT_PW_BYTES_PER_WAVE : RT_WORK_BYTES_PER_WAVE;
-  const size_t lds_records =
-      (pairs ? (size_t)4 * c->n_pairs + (size_t)RT_TRI_STRIDE * c->n_tris + (size_t)6 * c->n_instances
-             : (size_t)2 * c->n_nodes + (size_t)RT_TRI_STRIDE * c->n_tris + (size_t)4 * c->n_instances + ((size_t)c->n_instances + 3) / 4) * 16;
-  const bool trace_lds = !c->no_lds_staging && fits_lds && lds_records + (size_t)4 * wave_bytes <= 64 * 1024;
-  int block = 256, blocks_per_cu = 0;
-  if (!trace_lds) {
-    block = c->wf_block ? c->wf_block : 256;
-    blocks_per_cu = c->wf_blocks_per_cu ? c->wf_blocks_per_cu
-                    : pairs ? std::max(1, std::min((int)(c->lds_per_cu / ((size_t)(block / 64) * wave_bytes)), (RT_WF_WAVES * 256) / block))
-                            : (block == 1024 ? 1 : (block == 512 ? 2 : 6));
-  }
-  const size_t queue_bytes = (size_t)(block / 64) * wave_bytes;
-  size_t dyn = queue_bytes + lds_records;
-  rtk::PairPlan plan;
-  plan.stage_pairs = plan.stage_inst = plan.stage_tri = 1;
-  plan.pad = 0;
-  rtk::LdsPlan nplan;
-  nplan.k_nodes = c->n_nodes;
-  nplan.stage_inst = nplan.stage_tri = 1;
-  nplan.pad = 0;
-  if (!trace_lds) {
-    const size_t budget = c->lds_per_cu / (size_t)blocks_per_cu;
-    if (pairs)
-      plan = plan_pairs(c, budget, queue_bytes, &dyn);
-    else
-      nplan = plan_lds(c, budget, queue_bytes, &dyn);
-  }
-  plan.troot = c->troot;
-  // few instances with deep trees (glass blob: 3 instances, 400 k nodes): a ray enters an instance once and then waits at
-  // many leaves; measured, the form that keeps its instance-space origin / direction in registers is the faster one there,
-  // the other one where rays enter many small instances (k_traverse.hip.h, trav_post_at_entry; MI355RT_WF_RAYREG=0/1 overrides)
-  const bool rayreg = !pairs && (c->wf_rayreg < 0 ? (size_t)c->n_nodes >= (size_t)1024 * std::max<size_t>(1, c->n_instances) : c->wf_rayreg != 0);
+  const TraceShape shape = trace_shape(c, fits_lds, c->wf_block);
+  const bool pairs = shape.pairs, trace_lds = shape.trace_lds, rayreg = shape.rayreg;
+  const int block = shape.block;
+  const size_t dyn = shape.dyn;
+  rtk::PairPlan plan = shape.plan;
+  rtk::LdsPlan nplan = shape.nplan;
   const int bi = block == 1024 ? 2 : (block == 512 ? 1 : 0);
   const void* trace_fn[2];
   for (int k = 0; k < 2; k++)   // k = 0: any hit (shadow rays), 1: closest hit (extension rays)
@@ -1954,6 +1995,159 @@ static int launch_wavefront(rt_ctx* c, const DevScene& S, const DevFrame& F, con
   hipLaunchKernelGGL(rtk::k_accumulate_frames, dim3((uint32_t)((npx + 255) / 256)), dim3(256), 0, c->stream, F, dslots, c->acc_frames,
                      c->width, c->height);
   HIP_TRY(c, hipGetLastError());
+  return RT_OK;
+}
+
+// ---- ray queries: k_ray_query by [form][any][detail], form as in k_rayquery.hip.h
+#define RT_RQ_FNS(F)                                                                                                  \
+  {{(const void*)rtk::k_ray_query<false, false, F>, (const void*)rtk::k_ray_query<false, true, F>},                  \
+   {(const void*)rtk::k_ray_query<true, false, F>, (const void*)rtk::k_ray_query<true, true, F>}}
+static const void* const rq_fns[5][2][2] = {RT_RQ_FNS(rtk::RT_RQ_NODE_LDS), RT_RQ_FNS(rtk::RT_RQ_NODE_MIXED), RT_RQ_FNS(rtk::RT_RQ_NODE_RAYREG),
+                                            RT_RQ_FNS(rtk::RT_RQ_PAIR_LDS), RT_RQ_FNS(rtk::RT_RQ_PAIR_GLOBAL)};
+#undef RT_RQ_FNS
+
+// Enqueue one query on the context's stream: n > 0 rays at d_rays, results to d_out (device pointers).  Touches the scene's
+// derived records (prepare_scene, as a compute() would) and the query's own buffers, nothing of the renderer's frame state.
+static int launch_ray_query(rt_ctx* c, const void* d_rays, uint32_t n, int mode, float t_min, void* d_out, bool detail) {
+  if (!(c->n_tris && c->n_verts && c->n_instances && c->n_nodes))
+    return fail(c, RT_ERR_NOT_READY, "ray query: no scene (geometry, topology, instances and BVH must be uploaded first)");
+  if (c->blas_offset > c->n_nodes) return fail(c, RT_ERR_NOT_READY, "ray query: blas_base_idx exceeds the node buffer");
+  HIP_TRY(c, hipSetDevice(c->device));
+  int r = prepare_scene(c);
+  if (r < 0) {
+    if (!c->validate_dirty && !c->scene_valid) return fail(c, RT_ERR_NOT_READY, "ray query: " + c->scene_problem);
+    return r;
+  }
+  const TraceShape shape = trace_shape(c, scene_fits_lds(c), 0);
+  const int form = shape.pairs ? (shape.trace_lds ? rtk::RT_RQ_PAIR_LDS : rtk::RT_RQ_PAIR_GLOBAL)
+                               : (shape.trace_lds ? rtk::RT_RQ_NODE_LDS : (shape.rayreg ? rtk::RT_RQ_NODE_RAYREG : rtk::RT_RQ_NODE_MIXED));
+  const void* fn = rq_fns[form][mode == RT_RAYS_ANY][detail];
+  const size_t dyn = shape.dyn;
+  if (c->rq_occ_fn != fn || c->rq_occ_dyn != dyn || c->rq_occ_blocks == 0) {
+    HIP_TRY(c, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
+    int per_cu = 0;
+    HIP_TRY(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 256, dyn));
+    c->rq_occ_blocks = per_cu < 1 ? 1 : per_cu;
+    c->rq_occ_fn = fn;
+    c->rq_occ_dyn = dyn;
+  }
+  uint32_t per_cu = (uint32_t)c->rq_occ_blocks;
+  if (c->wf_blocks_per_cu > 0 && per_cu > (uint32_t)c->wf_blocks_per_cu) per_cu = (uint32_t)c->wf_blocks_per_cu;
+  uint32_t blocks = per_cu * (uint32_t)c->num_cus;
+  const uint32_t max_useful = (n + 255u) / 256u;
+  if (blocks > max_useful) blocks = max_useful;
+  if (getenv("MI355RT_DEBUG_SHAPE"))
+    fprintf(stderr, "[mi355rt] ray query: %s walk, form %d, %zu bytes of LDS, resident workgroups per CU %d, %u workgroups\n",
+            shape.pairs ? "pair" : "node", form, dyn, c->rq_occ_blocks, blocks);
+  const size_t counter_bytes = (size_t)RT_COUNTER_SHARDS * 6 * 8;
+  r = ensure_buffer(c, c->rq_counters, counter_bytes + 16, false);
+  if (r < 0) return r;
+  HIP_TRY(c, hipMemsetAsync(c->rq_counters.ptr, 0, counter_bytes + 16, c->stream));
+  rtk::RayQueryArgs A;
+  A.rays = (const float4*)d_rays;
+  A.out = (uint4*)d_out;
+  A.head = (uint32_t*)((char*)c->rq_counters.ptr + counter_bytes);
+  A.counters = (uint64_t*)c->rq_counters.ptr;
+  A.n_rays = n;
+  A.blas_base = c->blas_offset;
+  A.t_min = t_min;
+  A.n_recs = shape.pairs ? c->n_pairs : c->n_nodes;
+  A.n_tris = c->n_tris;
+  A.n_inst = c->n_instances;
+  DevScene S = dev_scene(c);
+  rtk::LdsPlan nplan = shape.nplan;
+  rtk::PairPlan plan = shape.plan;
+  void* args[] = {&S, &A, &nplan, &plan};
+  c->rq_timed = false;
+  if (c->timing) {
+    for (hipEvent_t& e : c->rq_ev)
+      if (!e) HIP_TRY(c, hipEventCreate(&e));
+    HIP_TRY(c, hipEventRecord(c->rq_ev[0], c->stream));
+  }
+  HIP_TRY(c, hipLaunchKernel(fn, dim3(blocks), dim3(256), args, dyn, c->stream));
+  if (c->timing) {
+    HIP_TRY(c, hipEventRecord(c->rq_ev[1], c->stream));
+    c->rq_timed = true;
+  }
+  c->rq_last = rt_ray_stats();
+  c->rq_last.walk = shape.pairs ? 1u : 0u;
+  c->rq_last.lds = shape.trace_lds ? 1u : 0u;
+  c->rq_last.rayreg = form == rtk::RT_RQ_NODE_RAYREG ? 1u : 0u;
+  c->rq_last.workgroups = blocks;
+  return RT_OK;
+}
+
+static int ray_query_args_ok(rt_ctx* c, uint32_t n, int mode, float t_min) {
+  if (mode != RT_RAYS_CLOSEST && mode != RT_RAYS_ANY) return fail(c, RT_ERR_INVALID, "ray query: unknown mode");
+  if (!(t_min >= 0.0f)) return fail(c, RT_ERR_INVALID, "ray query: t_min must be >= 0");
+  if (n >= (1u << 31)) return fail(c, RT_ERR_INVALID, "ray query: too many rays for one call (n must be below 2^31)");
+  return RT_OK;
+}
+
+int rt_ray_query_stats(rt_ctx* c, rt_ray_stats* out) {
+  if (!c || !out) return RT_ERR_INVALID;
+  HIP_TRY(c, hipSetDevice(c->device));
+  *out = c->rq_last;
+  if (!c->rq_counters.ptr || c->rq_last.workgroups == 0) return RT_OK;   // no query yet, or an empty one
+  std::vector<uint64_t> host((size_t)RT_COUNTER_SHARDS * 6);
+  HIP_TRY(c, hipMemcpyAsync(host.data(), c->rq_counters.ptr, host.size() * 8, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  for (size_t s = 0; s < RT_COUNTER_SHARDS; s++) {
+    out->rays += host[s * 6 + 1] + host[s * 6 + 2];
+    out->nodes_visited += host[s * 6 + 3];
+    out->tris_tested += host[s * 6 + 4];
+  }
+  if (c->rq_timed) {
+    float ms = 0.0f;
+    HIP_TRY(c, hipEventElapsedTime(&ms, c->rq_ev[0], c->rq_ev[1]));
+    out->kernel_ms = (double)ms;
+  }
+  return RT_OK;
+}
+
+int rt_trace_rays_device(rt_ctx* c, const void* dev_rays, uint32_t n, int mode, float t_min, void* dev_out) {
+  if (!c) return RT_ERR_INVALID;
+  int r = ray_query_args_ok(c, n, mode, t_min);
+  if (r < 0) return r;
+  if (n == 0) {
+    c->rq_last = rt_ray_stats();
+    return RT_OK;
+  }
+  if (!dev_rays || !dev_out) return fail(c, RT_ERR_INVALID, "ray query: NULL array");
+  if ((((uintptr_t)dev_rays) | ((uintptr_t)dev_out)) & 15u) return fail(c, RT_ERR_INVALID, "ray query: device arrays must be 16-byte aligned");
+  HIP_TRY(c, hipSetDevice(c->device));
+  for (const void* p : {dev_rays, (const void*)dev_out}) {
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, p) != hipSuccess) {
+      (void)hipGetLastError();
+      return fail(c, RT_ERR_INVALID, "ray query: not a device-accessible pointer");
+    }
+    if (at.type == hipMemoryTypeDevice && at.device != c->device)
+      return fail(c, RT_ERR_INVALID, "ray query: the array lives on another device than the context");
+    if (at.type != hipMemoryTypeDevice && at.type != hipMemoryTypeHost && at.type != hipMemoryTypeManaged)
+      return fail(c, RT_ERR_INVALID, "ray query: not a device-accessible pointer");
+  }
+  return launch_ray_query(c, dev_rays, n, mode, t_min, dev_out, c->detailed_counters);
+}
+
+int rt_trace_rays(rt_ctx* c, const rt_ray* rays, uint32_t n, int mode, float t_min, rt_ray_hit* out, rt_ray_stats* stats) {
+  if (!c) return RT_ERR_INVALID;
+  int r = ray_query_args_ok(c, n, mode, t_min);
+  if (r < 0) return r;
+  if (n == 0) {
+    c->rq_last = rt_ray_stats();
+    if (stats) *stats = c->rq_last;
+    return RT_OK;
+  }
+  if (!rays || !out) return fail(c, RT_ERR_INVALID, "ray query: NULL array");
+  HIP_TRY(c, hipSetDevice(c->device));
+  if ((r = ensure_buffer(c, c->rq_rays, (size_t)n * sizeof(rt_ray), true)) < 0) return r;
+  if ((r = ensure_buffer(c, c->rq_hits, (size_t)n * sizeof(rt_ray_hit), true)) < 0) return r;
+  HIP_TRY(c, hipMemcpyAsync(c->rq_rays.ptr, rays, (size_t)n * sizeof(rt_ray), hipMemcpyHostToDevice, c->stream));
+  if ((r = launch_ray_query(c, c->rq_rays.ptr, n, mode, t_min, c->rq_hits.ptr, stats != nullptr)) < 0) return r;
+  HIP_TRY(c, hipMemcpyAsync(out, c->rq_hits.ptr, (size_t)n * sizeof(rt_ray_hit), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (stats) return rt_ray_query_stats(c, stats);
   return RT_OK;
 }
 

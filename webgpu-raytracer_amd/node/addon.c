@@ -527,6 +527,57 @@ static napi_value rtReadDisplay(napi_env env, napi_callback_info info) {
   return make_int(env, rt_read_display((rt_ctx*)get_ptr(env, a[0]), (float*)p, n));
 }
 
+/* ------------------------------------------------------- ray queries (rt_trace_rays, mi355rt.h) */
+static void set_u64_as_double(napi_env env, napi_value obj, const char* name, uint64_t v) {
+  napi_value d;
+  napi_create_double(env, (double)v, &d);
+  napi_set_named_property(env, obj, name, d);
+}
+static napi_value ray_stats_object(napi_env env, const rt_ray_stats* st) {
+  napi_value obj, d;
+  if (napi_create_object(env, &obj) != napi_ok) return NULL;
+  set_u64_as_double(env, obj, "rays", st->rays);
+  set_u64_as_double(env, obj, "nodes_visited", st->nodes_visited);
+  set_u64_as_double(env, obj, "tris_tested", st->tris_tested);
+  set_u64_as_double(env, obj, "walk", st->walk);
+  set_u64_as_double(env, obj, "lds", st->lds);
+  set_u64_as_double(env, obj, "rayreg", st->rayreg);
+  set_u64_as_double(env, obj, "workgroups", st->workgroups);
+  napi_create_double(env, st->kernel_ms, &d);
+  napi_set_named_property(env, obj, "kernel_ms", d);
+  return obj;
+}
+/* (ctx, rays: Float32Array of 8 per ray {o, t_max, d, -}, mode, tMin, hits: Uint32Array of 4 per ray, wantStats)
+ * -> status, or the stats object when wantStats and the call succeeded */
+static napi_value rtTraceRays(napi_env env, napi_callback_info info) {
+  napi_value a[6];
+  void *rays = NULL, *hits = NULL;
+  size_t nr = 0, nh = 0;
+  double t_min = 0;
+  bool want_stats = false;
+  if (!get_args(env, info, 6, a) || !get_bytes(env, a[1], &rays, &nr) || !get_bytes(env, a[4], &hits, &nh)) return NULL;
+  napi_get_value_double(env, a[3], &t_min);
+  napi_get_value_bool(env, a[5], &want_stats);
+  const size_t n = nr / sizeof(rt_ray);
+  if (nr % sizeof(rt_ray) != 0 || nh < n * sizeof(rt_ray_hit) || n > 0x7fffffffu) {
+    napi_throw_range_error(env, NULL, "rtTraceRays: rays must hold 8 floats per ray and hits 4 words per ray");
+    return NULL;
+  }
+  rt_ray_stats st;
+  const int rc = rt_trace_rays((rt_ctx*)get_ptr(env, a[0]), (const rt_ray*)rays, (uint32_t)n, (int)get_u32(env, a[2]), (float)t_min,
+                               (rt_ray_hit*)hits, want_stats ? &st : NULL);
+  if (rc < 0 || !want_stats) return make_int(env, rc);
+  return ray_stats_object(env, &st);
+}
+static napi_value rtRayQueryStats(napi_env env, napi_callback_info info) {
+  napi_value a[1];
+  if (!get_args(env, info, 1, a)) return NULL;
+  rt_ray_stats st;
+  const int rc = rt_ray_query_stats((rt_ctx*)get_ptr(env, a[0]), &st);
+  if (rc < 0) return make_int(env, rc);
+  return ray_stats_object(env, &st);
+}
+
 static napi_value Init(napi_env env, napi_value exports) {
   static const struct {
     const char* name;
@@ -542,7 +593,8 @@ static napi_value Init(napi_env env, napi_value exports) {
                {"rtDistUniqueId", rtDistUniqueId}, {"rtDistInit", rtDistInit}, {"rtDistShutdown", rtDistShutdown},
                {"rtDistBlockBytes", rtDistBlockBytes}, {"rtPackStripes", rtPackStripes}, {"rtDistReadBlock", rtDistReadBlock},
                {"rtDistWriteBlock", rtDistWriteBlock}, {"rtUnpackStripes", rtUnpackStripes},
-               {"rtGatherStripes", rtGatherStripes}, {"rtReadDisplay", rtReadDisplay}, {"msCreate", msCreate}, {"msDestroy", msDestroy},
+               {"rtGatherStripes", rtGatherStripes}, {"rtReadDisplay", rtReadDisplay}, {"rtTraceRays", rtTraceRays},
+               {"rtRayQueryStats", rtRayQueryStats}, {"msCreate", msCreate}, {"msDestroy", msDestroy},
                {"msUpdate", msUpdate}, {"msUpdateCamera", msUpdateCamera}, {"msGet", msGet},
                {"msTextureCount", msTextureCount}, {"msTexture", msTexture},
                {"msAnimationNames", msAnimationNames}, {"msSetAnimation", msSetAnimation},

@@ -1,5 +1,9 @@
 // TypeScript view of index.js: the method surface of the reference classes
 // (src/renderer/WebGPURenderer.ts:7-138, src/world-bridge.ts:4-216).
+export interface RayQueryStats {
+  rays: number; nodes_visited: number; tris_tested: number; walk: number; lds: number; rayreg: number; workgroups: number; kernel_ms: number;
+}
+
 export class WebGPURenderer {
   constructor(device?: number);
   readonly device: { queue: { onSubmittedWorkDone(): Promise<void> } };
@@ -41,6 +45,11 @@ export class WebGPURenderer {
   gatherStripes(): void;
   /** rank 0: the assembled float4 image (blocking) */
   readDisplay(): Float32Array;
+  /** Ray casts against the uploaded scene (rt_trace_rays): 8 floats per ray {origin, tMax, direction, -}.  Closest hit: a miss
+   *  is {the ray's tMax, -1, -1, 0}; anyHit: {0, -1, -1, occluded}.  `words` are the raw 16-byte hit records. */
+  traceRays(rays: Float32Array, opts?: { anyHit?: boolean; tMin?: number; stats?: boolean }):
+    { t: Float32Array; tri: Int32Array; inst: Int32Array; hit: Uint32Array; words: Uint32Array; stats?: RayQueryStats };
+  rayQueryStats(): RayQueryStats;
   destroy(): void;
 }
 export class WorldBridge {

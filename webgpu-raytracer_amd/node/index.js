@@ -150,6 +150,29 @@ class WebGPURenderer {
     this._check(native.rtReadDisplay(this._ctx, out), 'readDisplay');
     return out;
   }
+  // ---- ray queries against the uploaded scene (rt_trace_rays): rays = 8 floats per ray {origin, tMax, direction, -};
+  // opts: {anyHit = false, tMin = 0.001, stats = false}.  Closest hit: {t, tri, inst, hit} per ray, a miss is
+  // {the ray's tMax, -1, -1, 0}; any hit: {0, -1, -1, occluded}.  With stats the result also carries .stats.
+  traceRays(rays, opts = {}) {
+    if (!(rays instanceof Float32Array) || rays.length % 8 !== 0) throw new TypeError('traceRays: a Float32Array of 8 floats per ray');
+    const n = rays.length / 8;
+    const words = new Uint32Array(n * 4);
+    const r = native.rtTraceRays(this._ctx, rays, opts.anyHit ? 1 : 0, opts.tMin === undefined ? 0.001 : opts.tMin, words, !!opts.stats);
+    if (typeof r === 'number') this._check(r, 'traceRays');
+    const asF = new Float32Array(words.buffer), asI = new Int32Array(words.buffer);
+    const out = { t: new Float32Array(n), tri: new Int32Array(n), inst: new Int32Array(n), hit: new Uint32Array(n) };
+    for (let i = 0; i < n; i++) {
+      out.t[i] = asF[4 * i]; out.tri[i] = asI[4 * i + 1]; out.inst[i] = asI[4 * i + 2]; out.hit[i] = words[4 * i + 3];
+    }
+    out.words = words;   // the raw rt_ray_hit records (t as its bit pattern)
+    if (typeof r === 'object' && r) out.stats = r;
+    return out;
+  }
+  rayQueryStats() {
+    const r = native.rtRayQueryStats(this._ctx);
+    if (typeof r === 'number') this._check(r, 'rayQueryStats');
+    return r;
+  }
   destroy() { if (this._ctx) { native.rtDestroy(this._ctx); this._ctx = null; } }
 }
 

@@ -185,6 +185,10 @@ def load_library(path=None):
         "rt_dist_block_bytes": (ctypes.c_size_t, [vp]), "rt_pack_stripes": (i32, [vp]),
         "rt_dist_read_block": (i32, [vp, vp, ctypes.c_size_t]), "rt_dist_write_block": (i32, [vp, u32, vp, ctypes.c_size_t]),
         "rt_unpack_stripes": (i32, [vp]), "rt_gather_stripes": (i32, [vp]), "rt_read_display": (i32, [vp, vp, ctypes.c_size_t]),
+        # ray queries
+        "rt_trace_rays": (i32, [vp, vp, u32, i32, ctypes.c_float, vp, vp]),
+        "rt_trace_rays_device": (i32, [vp, vp, u32, i32, ctypes.c_float, vp]),
+        "rt_ray_query_stats": (i32, [vp, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(L, name)  # AttributeError here = header/library mismatch
@@ -205,7 +209,32 @@ EXPORTED_SYMBOLS = (
     "rt_set_kernel_timing rt_device_count rt_set_kernel_variant rt_set_walk rt_set_lookahead "
     "rt_world_update rt_world_last_ms rt_world_last_tlas_ms rt_world_read rt_build_blas_levels rt_set_lookahead_limit rt_world_set_static_cache "
     "rt_dist_unique_id rt_dist_init rt_dist_shutdown rt_dist_block_bytes rt_pack_stripes rt_dist_read_block rt_dist_write_block "
-    "rt_unpack_stripes rt_gather_stripes rt_read_display").split()
+    "rt_unpack_stripes rt_gather_stripes rt_read_display "
+    "rt_trace_rays rt_trace_rays_device rt_ray_query_stats").split()
+
+
+# ---- ray queries: mirrors of rt_ray / rt_ray_hit / rt_ray_stats (include/mi355rt_layout.h)
+RT_RAYS_CLOSEST, RT_RAYS_ANY = 0, 1
+
+
+class RtRay(ctypes.Structure):
+    _fields_ = [("origin", ctypes.c_float * 3), ("t_max", ctypes.c_float), ("dir", ctypes.c_float * 3), ("pad", ctypes.c_uint32)]
+
+
+class RtRayHit(ctypes.Structure):
+    _fields_ = [("t", ctypes.c_float), ("tri", ctypes.c_int32), ("inst", ctypes.c_int32), ("hit", ctypes.c_uint32)]
+
+
+class RtRayStats(ctypes.Structure):
+    _fields_ = [("rays", ctypes.c_uint64), ("nodes_visited", ctypes.c_uint64), ("tris_tested", ctypes.c_uint64),
+                ("walk", ctypes.c_uint32), ("lds", ctypes.c_uint32), ("rayreg", ctypes.c_uint32), ("workgroups", ctypes.c_uint32),
+                ("kernel_ms", ctypes.c_double)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+RAY_HIT_DTYPE = np.dtype([("t", np.float32), ("tri", np.int32), ("inst", np.int32), ("hit", np.uint32)])
 
 
 def _ptr(a):
@@ -449,6 +478,34 @@ class WebGPURenderer:
 
     def setStream(self, hip_stream_handle):
         self._check(self.L.rt_set_stream(self.ctx, ctypes.c_void_p(hip_stream_handle)), "setStream")
+
+    # ---- ray queries against the uploaded scene (rt_trace_rays) ----
+    def traceRays(self, rays, any_hit=False, t_min=0.001, stats=False):
+        """rays: (n, 8) float32 in the rt_ray layout {origin, t_max, direction, -}.  Returns a structured array (n,) with
+        the fields t, tri, inst, hit (RAY_HIT_DTYPE) - closest hit: a miss is (the ray's t_max, -1, -1, 0); any_hit:
+        (0, -1, -1, occluded) - and with stats=True the pair (hits, stats dict of rt_ray_stats: the counting kernel runs)."""
+        r = np.ascontiguousarray(rays, dtype=np.float32)
+        if r.ndim != 2 or r.shape[1] != 8:
+            raise ValueError("traceRays expects an (n, 8) float32 array")
+        n = r.shape[0]
+        out = np.empty(n, dtype=RAY_HIT_DTYPE)
+        st = RtRayStats()
+        self._check(self.L.rt_trace_rays(self.ctx, _ptr(r), n, RT_RAYS_ANY if any_hit else RT_RAYS_CLOSEST, float(t_min),
+                                         _ptr(out), ctypes.addressof(st) if stats else None), "traceRays")
+        return (out, st.as_dict()) if stats else out
+
+    def traceRaysDevice(self, rays_ptr, n, out_ptr, any_hit=False, t_min=0.001):
+        """Enqueue a query on device arrays (n rt_ray at rays_ptr, n rt_ray_hit to out_ptr; e.g. tensor.data_ptr()) on the
+        context's stream; no host synchronisation."""
+        self._check(self.L.rt_trace_rays_device(self.ctx, ctypes.c_void_p(rays_ptr), int(n),
+                                                RT_RAYS_ANY if any_hit else RT_RAYS_CLOSEST, float(t_min),
+                                                ctypes.c_void_p(out_ptr)), "traceRaysDevice")
+
+    def rayQueryStats(self):
+        """rt_ray_stats of the last query as a dict (blocking)."""
+        st = RtRayStats()
+        self._check(self.L.rt_ray_query_stats(self.ctx, ctypes.addressof(st)), "rayQueryStats")
+        return st.as_dict()
 
     # ---- the sharded image (rt_dist_*): this context as one rank of `world` ----
     def distInit(self, rank, world, stripe_rows=8, unique_id=None):
