@@ -331,6 +331,43 @@ int rt_trace_rays(rt_ctx* ctx, const rt_ray* rays, uint32_t n, int mode, float t
 int rt_trace_rays_device(rt_ctx* ctx, const void* dev_rays, uint32_t n, int mode, float t_min, void* dev_out);
 int rt_ray_query_stats(rt_ctx* ctx, rt_ray_stats* out);
 
+/* ---- radiance queries: "what radiance arrives along this ray?" (light probes, irradiance and lightmap bakes, reflection
+ * captures, panorama / fisheye / orthographic cameras, renderers that make their own primary rays) ----
+ * The renderer's shading - materials, textures, next-event estimation with MIS, Russian roulette: ray_color
+ * (Raytracer.wgsl:607-783) - on rays the caller supplies, by the fourth driver of the path state machine
+ * (k_radiance_query, csrc/k_radiance.hip.h).  For ray i (rt_ray) and sample s in 0 .. spp-1:
+ *   rng     init_rng(rays[i].pad, seed * spp + s) in u32 arithmetic: `main`'s init_rng(pixel, frame_count * spp + sample)
+ *           (:798-800) with both numbers chosen by the caller.  pad, which rt_trace_rays ignores, is the ray's RNG stream id.
+ *   sample  ray_color with the depth-0 surface taken from the TRACED hit, exactly as at every later depth (:738-779): no
+ *           G-buffer, no octahedral normal, no unorm8 albedo, no lens offset, no jitter.  The first segment is the closest
+ *           hit in (0.001, rays[i].t_max); every later segment uses 0.001 / 1e30 (:6-7) and shadow rays are traced as in a
+ *           frame.  Directions are not normalised by the library (the reference's camera rays are not either).  The light
+ *           count is that of the last rt_set_scene; light_count above the uploaded lights buffer is RT_ERR_INVALID, as for a
+ *           frame.
+ *   result  rgb = (((0 + r_0) + r_1) + ...) in sample order, divided by spp the way `main` does (:811; no division for spp
+ *           == 1); t = the first segment's hit distance.  A miss is rgb = +0 and t = the ray's t_max, bits unchanged (the
+ *           reference has no environment light).  max_depth == 0: the first segment is traced and t reported, rgb = +0.
+ * The first segment does not depend on the sample: it is traced once per ray and counts as one extension ray.  A result
+ * depends on (scene, ray, pad, seed, spp, max_depth) only - never on the ray's position in the array, its neighbours, n or
+ * the form of the kernel (whole scene in LDS when it fits, as for the persistent path tracer, else global memory;
+ * MI355RT_NO_LDS_STAGING respected; rt_set_kernel_variant and rt_set_walk do not matter).
+ * A query leaves the renderer as it was, exactly like rt_trace_rays: it has its own chunk counter, counter shards and event
+ * pair, and the accumulation, jitter and frame counts, the rt_counters, the G-buffer and the frames traced ahead under
+ * rt_set_lookahead are untouched.
+ *   rt_trace_radiance         blocking: copies n rays in, traces, copies n results out (staging buffers are kept and
+ *                             grown).  stats != NULL runs the counting kernel and fills *stats.  n == 0 is RT_OK; n >= 2^31,
+ *                             a NULL pointer, spp == 0 or spp > 65536 is RT_ERR_INVALID; without a valid scene
+ *                             RT_ERR_NOT_READY with the reason in rt_last_error.
+ *   rt_trace_radiance_device  the same on device-accessible arrays (n rt_ray in, n rt_radiance out; 16-byte aligned, on the
+ *                             context's device): only enqueues on the context's stream (rt_set_stream respected).  Counts
+ *                             while rt_set_counting(ctx, 1) is on.
+ *   rt_radiance_query_stats   stats of the last radiance query (blocking: fences the stream). */
+int rt_trace_radiance(rt_ctx* ctx, const rt_ray* rays, uint32_t n, uint32_t max_depth, uint32_t spp, uint32_t seed,
+                      rt_radiance* out, rt_radiance_stats* stats);
+int rt_trace_radiance_device(rt_ctx* ctx, const void* dev_rays, uint32_t n, uint32_t max_depth, uint32_t spp, uint32_t seed,
+                             void* dev_out);
+int rt_radiance_query_stats(rt_ctx* ctx, rt_radiance_stats* out);
+
 /* ---- the sharded image: one picture rendered by `world` contexts ("ranks"), assembled on rank 0 ----
  * Rank k owns the image rows y with (y / stripe_rows) % world == k and traces only those (rt_set_stripes).  Its COMPACT
  * BLOCK holds the rows it owns in ascending y, width float4 each, padded with zero rows to max_rows = the largest share

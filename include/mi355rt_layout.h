@@ -130,8 +130,24 @@ typedef struct rt_ray_stats { /* of ONE call */
   double kernel_ms;           /* device events around the launch while rt_set_kernel_timing is on, else 0 */
 } rt_ray_stats;
 
+/* ---- radiance queries (rt_trace_radiance, mi355rt.h) ---- */
+typedef struct rt_radiance {  /* 16 B: one vector store of k_radiance_query */
+  float rgb[3];               /* sum of the samples' ray_color (Raytracer.wgsl:607-783) / spp, as `main` averages (:811) */
+  float t;                    /* the first segment's hit distance; a miss: the ray's t_max, bits unchanged */
+} rt_radiance;
+typedef struct rt_radiance_stats { /* 72 B, of ONE call */
+  uint64_t rays, samples;     /* n and n * spp */
+  uint64_t extension_rays, shadow_rays; /* the rt_counters of the same names; a ray's first segment is ONE extension ray */
+  uint64_t shaded_hits, nodes_visited, tris_tested; /* only from the counting kernel, else 0 */
+  uint32_t lds;               /* the whole scene staged in LDS (the persistent kernel's LDS form) */
+  uint32_t workgroups;        /* launched */
+  double kernel_ms;           /* device events around the launch while rt_set_kernel_timing is on, else 0 */
+} rt_radiance_stats;
+
 #ifdef __cplusplus
 }
+static_assert(sizeof(rt_radiance) == 16, "rt_radiance is 16 bytes");
+static_assert(sizeof(rt_radiance_stats) == 72, "rt_radiance_stats is 72 bytes");
 static_assert(sizeof(rt_ray) == 32, "rt_ray is 32 bytes");
 static_assert(sizeof(rt_ray_hit) == 16, "rt_ray_hit is 16 bytes");
 static_assert(sizeof(rt_ray_stats) == 48, "rt_ray_stats is 48 bytes");

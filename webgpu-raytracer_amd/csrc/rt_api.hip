@@ -198,6 +198,14 @@ struct rt_ctx {
   const void* rq_occ_fn = nullptr;  // cached occupancy query
   size_t rq_occ_dyn = 0;
   int rq_occ_blocks = 0;
+  // radiance queries (rt_trace_radiance): the same set, their own
+  DeviceBuffer rd_rays, rd_out, rd_counters;
+  hipEvent_t rd_ev[2] = {nullptr, nullptr};
+  bool rd_timed = false;
+  rt_radiance_stats rd_last = {};
+  const void* rd_occ_fn = nullptr;
+  size_t rd_occ_dyn = 0;
+  int rd_occ_blocks = 0;
 
   // kernel timing
   bool timing = false;
@@ -804,7 +812,7 @@ void rt_destroy(rt_ctx* c) {
                          &c->accum, &c->render_target,
                          &c->g_normal, &c->g_depth, &c->history[0], &c->history[1], &c->counters, &c->ticket,
                          &c->slots, &c->gbuf_batch, &c->frame_col, &c->wf_state, &c->wf_queues, &c->wf_counters,
-                         &c->rq_rays, &c->rq_hits, &c->rq_counters,
+                         &c->rq_rays, &c->rq_hits, &c->rq_counters, &c->rd_rays, &c->rd_out, &c->rd_counters,
                          &c->tex_staging, &c->bv_in, &c->bv_tri, &c->bv_order, &c->bv_nodes, &c->bv_out,
                          &c->bv_counters, &c->bv_big, &c->val_roots, &c->val_bad, &c->tnodes, &c->node_key, &c->node_newidx,
                          &c->inst_root, &c->root_w, &c->treelet_work, &c->pairs, &c->pair_of, &c->pair_parent, &c->root_rec,
@@ -814,6 +822,8 @@ void rt_destroy(rt_ctx* c) {
   for (DeviceBuffer* b : all) free_buffer(*b);
   if (c->world.pinned) (void)hipHostFree(c->world.pinned);
   for (hipEvent_t e : c->rq_ev)
+    if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : c->rd_ev)
     if (e) (void)hipEventDestroy(e);
   if (c->world.ev0) (void)hipEventDestroy(c->world.ev0);
   if (c->world.ev1) (void)hipEventDestroy(c->world.ev1);
@@ -2148,6 +2158,168 @@ int rt_trace_rays(rt_ctx* c, const rt_ray* rays, uint32_t n, int mode, float t_m
   HIP_TRY(c, hipMemcpyAsync(out, c->rq_hits.ptr, (size_t)n * sizeof(rt_ray_hit), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   if (stats) return rt_ray_query_stats(c, stats);
+  return RT_OK;
+}
+
+// ---- radiance queries: k_radiance_query by [detail][lds]
+static const void* const rd_fns[2][2] = {
+    {(const void*)rtk::k_radiance_query<false, false>, (const void*)rtk::k_radiance_query<false, true>},
+    {(const void*)rtk::k_radiance_query<true, false>, (const void*)rtk::k_radiance_query<true, true>}};
+
+// Enqueue one query on the context's stream: n > 0 rays at d_rays, results to d_out (device pointers).  Like
+// launch_ray_query it touches the scene's derived records and the query's own buffers, nothing of the renderer's frame state.
+static int launch_radiance_query(rt_ctx* c, const void* d_rays, uint32_t n, uint32_t max_depth, uint32_t spp, uint32_t seed,
+                                 void* d_out, bool detail) {
+  if (!(c->n_tris && c->n_verts && c->n_instances && c->n_nodes))
+    return fail(c, RT_ERR_NOT_READY, "radiance query: no scene (geometry, topology, instances and BVH must be uploaded first)");
+  if (c->blas_offset > c->n_nodes) return fail(c, RT_ERR_NOT_READY, "radiance query: blas_base_idx exceeds the node buffer");
+  if (c->light_count > c->n_lights) return fail(c, RT_ERR_INVALID, "light_count exceeds the uploaded lights buffer");
+  HIP_TRY(c, hipSetDevice(c->device));
+  int r = prepare_scene(c);
+  if (r < 0) {
+    if (!c->validate_dirty && !c->scene_valid) return fail(c, RT_ERR_NOT_READY, "radiance query: " + c->scene_problem);
+    return r;
+  }
+  // the form choice of the persistent kernel's 256-thread forms without the one-leaf one: the whole scene in LDS when it
+  // fits beside four wave queues, else six workgroups per CU, each with its share of the LDS for the traversal records
+  const bool lds = scene_fits_lds(c);
+  size_t dyn = (size_t)4 * RT_WORK_BYTES_PER_WAVE +
+               rtk::scene_lds_slots(c->n_nodes, c->n_tris, c->n_instances, c->n_verts, c->n_lights) * 16;
+  rtk::LdsPlan plan;
+  plan.k_nodes = c->n_nodes;
+  plan.stage_inst = plan.stage_tri = 1;
+  plan.pad = 0;
+  if (!lds) plan = plan_lds(c, c->lds_per_cu / 6, (size_t)4 * RT_WORK_BYTES_PER_WAVE, &dyn);
+  const void* fn = rd_fns[detail][lds];
+  if (c->rd_occ_fn != fn || c->rd_occ_dyn != dyn || c->rd_occ_blocks == 0) {
+    HIP_TRY(c, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
+    int per_cu = 0;
+    HIP_TRY(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 256, dyn));
+    c->rd_occ_blocks = per_cu < 1 ? 1 : per_cu;
+    c->rd_occ_fn = fn;
+    c->rd_occ_dyn = dyn;
+  }
+  uint32_t blocks = (uint32_t)c->rd_occ_blocks * (uint32_t)c->num_cus;
+  const uint32_t max_useful = (n + 255u) / 256u;
+  if (blocks > max_useful) blocks = max_useful;
+  if (getenv("MI355RT_DEBUG_SHAPE"))
+    fprintf(stderr, "[mi355rt] radiance query: %s form, %zu bytes of LDS, resident workgroups per CU %d, %u workgroups\n",
+            lds ? "LDS" : "global", dyn, c->rd_occ_blocks, blocks);
+  const size_t counter_bytes = (size_t)RT_COUNTER_SHARDS * 6 * 8;
+  r = ensure_buffer(c, c->rd_counters, counter_bytes + 16, false);
+  if (r < 0) return r;
+  HIP_TRY(c, hipMemsetAsync(c->rd_counters.ptr, 0, counter_bytes + 16, c->stream));
+  rtk::RadianceArgs A;
+  A.rays = (const float4*)d_rays;
+  A.out = (float4*)d_out;
+  A.head = (uint32_t*)((char*)c->rd_counters.ptr + counter_bytes);
+  A.counters = (uint64_t*)c->rd_counters.ptr;
+  A.n_rays = n;
+  A.max_depth = max_depth;
+  A.spp = spp;
+  A.seed = seed;
+  A.light_count = c->light_count;
+  A.blas_base = c->blas_offset;
+  A.n_nodes = c->n_nodes;
+  A.n_tris = c->n_tris;
+  A.n_inst = c->n_instances;
+  A.n_verts = c->n_verts;
+  DevScene S = dev_scene(c);
+  void* args[] = {&S, &A, &plan};
+  c->rd_timed = false;
+  if (c->timing) {
+    for (hipEvent_t& e : c->rd_ev)
+      if (!e) HIP_TRY(c, hipEventCreate(&e));
+    HIP_TRY(c, hipEventRecord(c->rd_ev[0], c->stream));
+  }
+  HIP_TRY(c, hipLaunchKernel(fn, dim3(blocks), dim3(256), args, dyn, c->stream));
+  if (c->timing) {
+    HIP_TRY(c, hipEventRecord(c->rd_ev[1], c->stream));
+    c->rd_timed = true;
+  }
+  c->rd_last = rt_radiance_stats();
+  c->rd_last.rays = n;
+  c->rd_last.samples = (uint64_t)n * spp;
+  c->rd_last.lds = lds ? 1u : 0u;
+  c->rd_last.workgroups = blocks;
+  return RT_OK;
+}
+
+static int radiance_query_args_ok(rt_ctx* c, uint32_t n, uint32_t spp) {
+  if (n >= (1u << 31)) return fail(c, RT_ERR_INVALID, "radiance query: too many rays for one call (n must be below 2^31)");
+  if (spp == 0 || spp > 65536) return fail(c, RT_ERR_INVALID, "radiance query: spp must be 1 .. 65536");
+  return RT_OK;
+}
+
+int rt_radiance_query_stats(rt_ctx* c, rt_radiance_stats* out) {
+  if (!c || !out) return RT_ERR_INVALID;
+  HIP_TRY(c, hipSetDevice(c->device));
+  *out = c->rd_last;
+  if (!c->rd_counters.ptr || c->rd_last.workgroups == 0) return RT_OK;   // no query yet, or an empty one
+  std::vector<uint64_t> host((size_t)RT_COUNTER_SHARDS * 6);
+  HIP_TRY(c, hipMemcpyAsync(host.data(), c->rd_counters.ptr, host.size() * 8, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  for (size_t s = 0; s < RT_COUNTER_SHARDS; s++) {
+    out->extension_rays += host[s * 6 + 1];
+    out->shadow_rays += host[s * 6 + 2];
+    out->nodes_visited += host[s * 6 + 3];
+    out->tris_tested += host[s * 6 + 4];
+    out->shaded_hits += host[s * 6 + 5];
+  }
+  if (c->rd_timed) {
+    float ms = 0.0f;
+    HIP_TRY(c, hipEventElapsedTime(&ms, c->rd_ev[0], c->rd_ev[1]));
+    out->kernel_ms = (double)ms;
+  }
+  return RT_OK;
+}
+
+int rt_trace_radiance_device(rt_ctx* c, const void* dev_rays, uint32_t n, uint32_t max_depth, uint32_t spp, uint32_t seed,
+                             void* dev_out) {
+  if (!c) return RT_ERR_INVALID;
+  int r = radiance_query_args_ok(c, n, spp);
+  if (r < 0) return r;
+  if (n == 0) {
+    c->rd_last = rt_radiance_stats();
+    return RT_OK;
+  }
+  if (!dev_rays || !dev_out) return fail(c, RT_ERR_INVALID, "radiance query: NULL array");
+  if ((((uintptr_t)dev_rays) | ((uintptr_t)dev_out)) & 15u)
+    return fail(c, RT_ERR_INVALID, "radiance query: device arrays must be 16-byte aligned");
+  HIP_TRY(c, hipSetDevice(c->device));
+  for (const void* p : {dev_rays, (const void*)dev_out}) {
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, p) != hipSuccess) {
+      (void)hipGetLastError();
+      return fail(c, RT_ERR_INVALID, "radiance query: not a device-accessible pointer");
+    }
+    if (at.type == hipMemoryTypeDevice && at.device != c->device)
+      return fail(c, RT_ERR_INVALID, "radiance query: the array lives on another device than the context");
+    if (at.type != hipMemoryTypeDevice && at.type != hipMemoryTypeHost && at.type != hipMemoryTypeManaged)
+      return fail(c, RT_ERR_INVALID, "radiance query: not a device-accessible pointer");
+  }
+  return launch_radiance_query(c, dev_rays, n, max_depth, spp, seed, dev_out, c->detailed_counters);
+}
+
+int rt_trace_radiance(rt_ctx* c, const rt_ray* rays, uint32_t n, uint32_t max_depth, uint32_t spp, uint32_t seed,
+                      rt_radiance* out, rt_radiance_stats* stats) {
+  if (!c) return RT_ERR_INVALID;
+  int r = radiance_query_args_ok(c, n, spp);
+  if (r < 0) return r;
+  if (n == 0) {
+    c->rd_last = rt_radiance_stats();
+    if (stats) *stats = c->rd_last;
+    return RT_OK;
+  }
+  if (!rays || !out) return fail(c, RT_ERR_INVALID, "radiance query: NULL array");
+  HIP_TRY(c, hipSetDevice(c->device));
+  if ((r = ensure_buffer(c, c->rd_rays, (size_t)n * sizeof(rt_ray), true)) < 0) return r;
+  if ((r = ensure_buffer(c, c->rd_out, (size_t)n * sizeof(rt_radiance), true)) < 0) return r;
+  HIP_TRY(c, hipMemcpyAsync(c->rd_rays.ptr, rays, (size_t)n * sizeof(rt_ray), hipMemcpyHostToDevice, c->stream));
+  if ((r = launch_radiance_query(c, c->rd_rays.ptr, n, max_depth, spp, seed, c->rd_out.ptr, stats != nullptr)) < 0) return r;
+  HIP_TRY(c, hipMemcpyAsync(out, c->rd_out.ptr, (size_t)n * sizeof(rt_radiance), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (stats) return rt_radiance_query_stats(c, stats);
   return RT_OK;
 }
 

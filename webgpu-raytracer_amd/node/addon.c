@@ -578,6 +578,44 @@ static napi_value rtRayQueryStats(napi_env env, napi_callback_info info) {
   return ray_stats_object(env, &st);
 }
 
+/* ------------------------------------------------------- radiance queries (rt_trace_radiance, mi355rt.h) */
+static napi_value radiance_stats_object(napi_env env, const rt_radiance_stats* st) {
+  napi_value obj, d;
+  if (napi_create_object(env, &obj) != napi_ok) return NULL;
+  set_u64_as_double(env, obj, "rays", st->rays);
+  set_u64_as_double(env, obj, "samples", st->samples);
+  set_u64_as_double(env, obj, "extension_rays", st->extension_rays);
+  set_u64_as_double(env, obj, "shadow_rays", st->shadow_rays);
+  set_u64_as_double(env, obj, "shaded_hits", st->shaded_hits);
+  set_u64_as_double(env, obj, "nodes_visited", st->nodes_visited);
+  set_u64_as_double(env, obj, "tris_tested", st->tris_tested);
+  set_u64_as_double(env, obj, "lds", st->lds);
+  set_u64_as_double(env, obj, "workgroups", st->workgroups);
+  napi_create_double(env, st->kernel_ms, &d);
+  napi_set_named_property(env, obj, "kernel_ms", d);
+  return obj;
+}
+/* (ctx, rays: Float32Array of 8 per ray {o, t_max, d, pad}, maxDepth, spp, seed, out: Float32Array of 4 per ray, wantStats)
+ * -> status, or the stats object when wantStats and the call succeeded */
+static napi_value rtTraceRadiance(napi_env env, napi_callback_info info) {
+  napi_value a[7];
+  void *rays = NULL, *out = NULL;
+  size_t nr = 0, no = 0;
+  bool want_stats = false;
+  if (!get_args(env, info, 7, a) || !get_bytes(env, a[1], &rays, &nr) || !get_bytes(env, a[5], &out, &no)) return NULL;
+  napi_get_value_bool(env, a[6], &want_stats);
+  const size_t n = nr / sizeof(rt_ray);
+  if (nr % sizeof(rt_ray) != 0 || no < n * sizeof(rt_radiance) || n > 0x7fffffffu) {
+    napi_throw_range_error(env, NULL, "rtTraceRadiance: rays must hold 8 floats per ray and out 4 floats per ray");
+    return NULL;
+  }
+  rt_radiance_stats st;
+  const int rc = rt_trace_radiance((rt_ctx*)get_ptr(env, a[0]), (const rt_ray*)rays, (uint32_t)n, get_u32(env, a[2]),
+                                   get_u32(env, a[3]), get_u32(env, a[4]), (rt_radiance*)out, want_stats ? &st : NULL);
+  if (rc < 0 || !want_stats) return make_int(env, rc);
+  return radiance_stats_object(env, &st);
+}
+
 static napi_value Init(napi_env env, napi_value exports) {
   static const struct {
     const char* name;
@@ -594,7 +632,7 @@ static napi_value Init(napi_env env, napi_value exports) {
                {"rtDistBlockBytes", rtDistBlockBytes}, {"rtPackStripes", rtPackStripes}, {"rtDistReadBlock", rtDistReadBlock},
                {"rtDistWriteBlock", rtDistWriteBlock}, {"rtUnpackStripes", rtUnpackStripes},
                {"rtGatherStripes", rtGatherStripes}, {"rtReadDisplay", rtReadDisplay}, {"rtTraceRays", rtTraceRays},
-               {"rtRayQueryStats", rtRayQueryStats}, {"msCreate", msCreate}, {"msDestroy", msDestroy},
+               {"rtRayQueryStats", rtRayQueryStats}, {"rtTraceRadiance", rtTraceRadiance}, {"msCreate", msCreate}, {"msDestroy", msDestroy},
                {"msUpdate", msUpdate}, {"msUpdateCamera", msUpdateCamera}, {"msGet", msGet},
                {"msTextureCount", msTextureCount}, {"msTexture", msTexture},
                {"msAnimationNames", msAnimationNames}, {"msSetAnimation", msSetAnimation},

@@ -3,6 +3,10 @@
 export interface RayQueryStats {
   rays: number; nodes_visited: number; tris_tested: number; walk: number; lds: number; rayreg: number; workgroups: number; kernel_ms: number;
 }
+export interface RadianceQueryStats {
+  rays: number; samples: number; extension_rays: number; shadow_rays: number; shaded_hits: number; nodes_visited: number;
+  tris_tested: number; lds: number; workgroups: number; kernel_ms: number;
+}
 
 export class WebGPURenderer {
   constructor(device?: number);
@@ -50,6 +54,11 @@ export class WebGPURenderer {
   traceRays(rays: Float32Array, opts?: { anyHit?: boolean; tMin?: number; stats?: boolean }):
     { t: Float32Array; tri: Int32Array; inst: Int32Array; hit: Uint32Array; words: Uint32Array; stats?: RayQueryStats };
   rayQueryStats(): RayQueryStats;
+  /** The path tracer's radiance along the caller's rays (rt_trace_radiance): 8 words per ray {origin, tMax, direction, pad},
+   *  pad = the bits of a uint32, the ray's RNG stream id.  `data` holds 4 floats per ray {r, g, b, t}; a miss is
+   *  {0, 0, 0, the ray's tMax}. */
+  traceRadiance(rays: Float32Array, maxDepth: number, spp: number, opts?: { seed?: number; stats?: boolean }):
+    { data: Float32Array; n: number; stats?: RadianceQueryStats };
   destroy(): void;
 }
 export class WorldBridge {

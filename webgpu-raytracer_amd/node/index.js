@@ -173,6 +173,20 @@ class WebGPURenderer {
     if (typeof r === 'number') this._check(r, 'rayQueryStats');
     return r;
   }
+  // ---- radiance queries (rt_trace_radiance): the path tracer's radiance along the caller's rays.  rays = 8 words per ray
+  // {origin, tMax, direction, pad}; pad holds the bits of a uint32, the ray's RNG stream id (write it through a Uint32Array
+  // on the same buffer).  opts: {seed = 0, stats = false}.  Result: 4 floats per ray {r, g, b, t} in .data; a miss is
+  // {0, 0, 0, the ray's tMax}.  With stats the result also carries .stats.
+  traceRadiance(rays, maxDepth, spp, opts = {}) {
+    if (!(rays instanceof Float32Array) || rays.length % 8 !== 0) throw new TypeError('traceRadiance: a Float32Array of 8 floats per ray');
+    const n = rays.length / 8;
+    const data = new Float32Array(n * 4);
+    const r = native.rtTraceRadiance(this._ctx, rays, maxDepth >>> 0, spp >>> 0, (opts.seed || 0) >>> 0, data, !!opts.stats);
+    if (typeof r === 'number') this._check(r, 'traceRadiance');
+    const out = { data, n };
+    if (typeof r === 'object' && r) out.stats = r;
+    return out;
+  }
   destroy() { if (this._ctx) { native.rtDestroy(this._ctx); this._ctx = null; } }
 }
 

@@ -189,6 +189,10 @@ def load_library(path=None):
         "rt_trace_rays": (i32, [vp, vp, u32, i32, ctypes.c_float, vp, vp]),
         "rt_trace_rays_device": (i32, [vp, vp, u32, i32, ctypes.c_float, vp]),
         "rt_ray_query_stats": (i32, [vp, vp]),
+        # radiance queries
+        "rt_trace_radiance": (i32, [vp, vp, u32, u32, u32, u32, vp, vp]),
+        "rt_trace_radiance_device": (i32, [vp, vp, u32, u32, u32, u32, vp]),
+        "rt_radiance_query_stats": (i32, [vp, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(L, name)  # AttributeError here = header/library mismatch
@@ -210,7 +214,8 @@ EXPORTED_SYMBOLS = (
     "rt_world_update rt_world_last_ms rt_world_last_tlas_ms rt_world_read rt_build_blas_levels rt_set_lookahead_limit rt_world_set_static_cache "
     "rt_dist_unique_id rt_dist_init rt_dist_shutdown rt_dist_block_bytes rt_pack_stripes rt_dist_read_block rt_dist_write_block "
     "rt_unpack_stripes rt_gather_stripes rt_read_display "
-    "rt_trace_rays rt_trace_rays_device rt_ray_query_stats").split()
+    "rt_trace_rays rt_trace_rays_device rt_ray_query_stats "
+    "rt_trace_radiance rt_trace_radiance_device rt_radiance_query_stats").split()
 
 
 # ---- ray queries: mirrors of rt_ray / rt_ray_hit / rt_ray_stats (include/mi355rt_layout.h)
@@ -235,6 +240,20 @@ class RtRayStats(ctypes.Structure):
 
 
 RAY_HIT_DTYPE = np.dtype([("t", np.float32), ("tri", np.int32), ("inst", np.int32), ("hit", np.uint32)])
+
+
+# ---- radiance queries: mirrors of rt_radiance / rt_radiance_stats (include/mi355rt_layout.h)
+class RtRadianceStats(ctypes.Structure):
+    _fields_ = [("rays", ctypes.c_uint64), ("samples", ctypes.c_uint64), ("extension_rays", ctypes.c_uint64),
+                ("shadow_rays", ctypes.c_uint64), ("shaded_hits", ctypes.c_uint64), ("nodes_visited", ctypes.c_uint64),
+                ("tris_tested", ctypes.c_uint64), ("lds", ctypes.c_uint32), ("workgroups", ctypes.c_uint32),
+                ("kernel_ms", ctypes.c_double)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+RADIANCE_DTYPE = np.dtype([("rgb", np.float32, (3,)), ("t", np.float32)])
 
 
 def _ptr(a):
@@ -505,6 +524,34 @@ class WebGPURenderer:
         """rt_ray_stats of the last query as a dict (blocking)."""
         st = RtRayStats()
         self._check(self.L.rt_ray_query_stats(self.ctx, ctypes.addressof(st)), "rayQueryStats")
+        return st.as_dict()
+
+    # ---- radiance queries against the uploaded scene (rt_trace_radiance) ----
+    def traceRadiance(self, rays, max_depth, spp, seed=0, stats=False):
+        """rays: (n, 8) float32 in the rt_ray layout {origin, t_max, direction, pad}; pad holds the bits of a uint32, the
+        ray's RNG stream id.  Returns a structured array (n,) with the fields rgb (3 floats) and t (RADIANCE_DTYPE): the
+        path tracer's radiance along each ray, averaged over spp samples, and the first hit's distance (a miss: +0 and the
+        ray's t_max) - and with stats=True the pair (results, stats dict of rt_radiance_stats: the counting kernel runs)."""
+        r = np.ascontiguousarray(rays, dtype=np.float32)
+        if r.ndim != 2 or r.shape[1] != 8:
+            raise ValueError("traceRadiance expects an (n, 8) float32 array")
+        n = r.shape[0]
+        out = np.empty(n, dtype=RADIANCE_DTYPE)
+        st = RtRadianceStats()
+        self._check(self.L.rt_trace_radiance(self.ctx, _ptr(r), n, int(max_depth), int(spp), int(seed) & 0xffffffff, _ptr(out),
+                                             ctypes.addressof(st) if stats else None), "traceRadiance")
+        return (out, st.as_dict()) if stats else out
+
+    def traceRadianceDevice(self, rays_ptr, n, out_ptr, max_depth, spp, seed=0):
+        """Enqueue a radiance query on device arrays (n rt_ray at rays_ptr, n rt_radiance to out_ptr; e.g.
+        tensor.data_ptr()) on the context's stream; no host synchronisation."""
+        self._check(self.L.rt_trace_radiance_device(self.ctx, ctypes.c_void_p(rays_ptr), int(n), int(max_depth), int(spp),
+                                                    int(seed) & 0xffffffff, ctypes.c_void_p(out_ptr)), "traceRadianceDevice")
+
+    def radianceQueryStats(self):
+        """rt_radiance_stats of the last radiance query as a dict (blocking)."""
+        st = RtRadianceStats()
+        self._check(self.L.rt_radiance_query_stats(self.ctx, ctypes.addressof(st)), "radianceQueryStats")
         return st.as_dict()
 
     # ---- the sharded image (rt_dist_*): this context as one rank of `world` ----
