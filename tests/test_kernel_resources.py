@@ -14,6 +14,7 @@ import webgpu_raytracer_amd as W
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(REPO, "webgpu-raytracer_amd", "csrc")
 PRODUCT_ONE_LEAF = "_ZN3rtk22k_pathtrace_persistentILb0ELb1ELb1E"
+_reports = {}   # kernel_source_hash() -> report: the test files that read it compile the sources once per process
 
 
 def resource_report(tmp_path):
@@ -21,6 +22,9 @@ def resource_report(tmp_path):
     hipcc = W._build.HIPCC
     if not os.path.exists(hipcc):
         pytest.skip("hipcc not found at %s" % hipcc)
+    key = W._build.kernel_source_hash()
+    if key in _reports:
+        return _reports[key]
     flags = [f for f in W._build.HIP_FLAGS if f not in ("-shared", "-fPIC")]
     cmd = [hipcc] + flags + ["--cuda-device-only", "-c", "-Rpass-analysis=kernel-resource-usage", "-I", W._build.INCLUDE,
                              "-o", str(tmp_path / "rt_api.o"), os.path.join(CSRC, "rt_api.hip")]
@@ -37,6 +41,7 @@ def resource_report(tmp_path):
         elif cur is not None and ":" in text:
             k, v = text.split(":", 1)
             cur[k.strip()] = v.strip()
+    _reports[key] = kernels
     return kernels
 
 

@@ -43,6 +43,23 @@ struct EventPair {
   hipEvent_t a, b;
 };
 
+// A kernel prepared for a launch (resident_blocks): the workgroup size and dynamic LDS its attribute was last set for, and
+// the workgroups of that shape a CU holds.  One entry per function.
+struct PreparedKernel {
+  const void* fn;
+  int block;
+  size_t dyn;
+  int per_cu;
+};
+
+// What one kind of query (rt_trace_rays, rt_trace_radiance) keeps between calls: the staging arrays of its host entry, its
+// own counter shards with the chunk counter behind them, and the events around its last launch.
+struct QueryState {
+  DeviceBuffer in, out, counters;
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  bool timed = false;               // the last query recorded its events
+};
+
 }  // namespace
 
 struct rt_ctx {
@@ -142,10 +159,7 @@ struct rt_ctx {
   int variant = 3;        // 3 = auto (default): persistent kernel for LDS-resident scenes, wavefront for larger ones;
                           // 0 = one-pixel-per-lane megakernel, 1 = persistent kernel, 2 = wavefront
   int num_cus = 256;      // multiProcessorCount of the device
-  int occ_blocks[7] = {0, 0, 0, 0, 0, 0, 0};   // cached occupancy query per persistent-kernel variant
-  int wf_occ_blocks[2] = {0, 0};      // ... and for the two wavefront trace kernels
-  size_t wf_occ_dyn = (size_t)-1;
-  int wf_occ_detail = -1, wf_occ_block = 0, wf_occ_walk = -1, wf_occ_rayreg = -1;   // walk: 0 node, 1 pair
+  std::vector<PreparedKernel> prepared;   // every kernel launched with dynamic LDS so far (resident_blocks)
   int walk = 2;                  // traversal of the wavefront trace kernels: 1 = child-pair records, 0 = single nodes, 2 = auto
                                  // (MI355RT_WALK): pairs for a scene of ONE instance (measured: the 263 k-triangle hall -9 % per
                                  // batch; glass blob, 2 instances and short walks: +7 %; 1 001 instances of 8 triangles: +20 %)
@@ -154,7 +168,6 @@ struct rt_ctx {
   long treelet_cap = -1;
   int treelet_order = 2;          // order of tnodes: 0 = by visit probability, 1 = the bridge's depth-first order, 2 = auto (MI355RT_TREELET_ORDER)
   bool nodes_from_device = false; // the node array was made by rt_world_update (an animated world), not uploaded
-  size_t occ_dyn[7] = {0, 0, 0, 0, 0, 0, 0};
   uint32_t pt_launch[4] = {0, 0, 0, 0};   // last persistent launch: threads, workgroups, dynamic LDS, workgroups per CU
   DeviceBuffer ticket;    // tile ticket counter of the persistent kernel
   DeviceBuffer slots;     // DevFrameSlot table of the current (batched) dispatch
@@ -189,23 +202,10 @@ struct rt_ctx {
   DeviceBuffer gbuf_batch;  // G-buffer planes of frames 0..n-2 of a batch (the last frame uses the main planes)
   DeviceBuffer frame_col;   // per-frame colours of a batch, added in frame order by k_accumulate_frames
   DeviceBuffer wf_state, wf_queues, wf_counters;  // wavefront form: path state, ray / path queues, queue counters
-  // ray queries (rt_trace_rays): staging arrays of the host entry; the query's own counter shards with the chunk counter
-  // behind them; events around the launch; shape and stats of the last query
-  DeviceBuffer rq_rays, rq_hits, rq_counters;
-  hipEvent_t rq_ev[2] = {nullptr, nullptr};
-  bool rq_timed = false;            // the last query recorded its events
+  // ray queries (rt_trace_rays) and radiance queries (rt_trace_radiance): buffers and events, shape and stats of the last query
+  QueryState rq, rd;
   rt_ray_stats rq_last = {};
-  const void* rq_occ_fn = nullptr;  // cached occupancy query
-  size_t rq_occ_dyn = 0;
-  int rq_occ_blocks = 0;
-  // radiance queries (rt_trace_radiance): the same set, their own
-  DeviceBuffer rd_rays, rd_out, rd_counters;
-  hipEvent_t rd_ev[2] = {nullptr, nullptr};
-  bool rd_timed = false;
   rt_radiance_stats rd_last = {};
-  const void* rd_occ_fn = nullptr;
-  size_t rd_occ_dyn = 0;
-  int rd_occ_blocks = 0;
 
   // kernel timing
   bool timing = false;
@@ -524,6 +524,9 @@ bool scene_fits_lds(const rt_ctx* c) {
 // ... and its TLAS is one node, which is a leaf (k_validate_scene, or the world update's builder): the one-leaf forms, which
 // read the per-triangle world records
 bool one_leaf_lds(const rt_ctx* c) { return scene_fits_lds(c) && c->blas_offset == 1; }
+// the trace kernels walk child-pair records, not single nodes (rt_set_walk; auto: a scene of one instance).  prepare_scene
+// builds the records this says a launch will read.
+bool walks_pairs(const rt_ctx* c) { return c->walk == 1 || (c->walk == 2 && c->n_instances == 1); }
 
 int prepare_scene(rt_ctx* c) {
   {
@@ -606,7 +609,7 @@ int prepare_scene(rt_ctx* c) {
   }
   // the pair records are only walked by the wavefront trace kernels under the pair walk (rt_set_walk): a scene that takes
   // the node walk does not pay for them on every update(t); they are made when a launch (or rt_debug_read_pairs) wants them
-  const bool want_pairs = c->pairs_wanted || c->walk == 1 || (c->walk == 2 && c->n_instances == 1);
+  const bool want_pairs = c->pairs_wanted || walks_pairs(c);
   if (want_pairs && (c->pairs_dirty || c->roots_dirty) && c->n_nodes && c->n_instances) {
     // child-pair records of the walk (k_pairs.hip.h); validate_scene has uploaded the sorted BLAS roots into val_roots and
     // vouches for every pointer followed here.  An instance upload that keeps the set of BLAS roots only redoes the root
@@ -706,6 +709,127 @@ EventPair* next_events(rt_ctx* c, int tag) {
   }
   c->ev_tags.emplace_back(c->ev_used, tag);
   return &c->ev_pool[c->ev_used++];
+}
+
+// Prepare `fn` for a launch of `block` threads and `dyn` bytes of dynamic LDS per workgroup; *per_cu: the workgroups of that
+// shape a CU holds (registers, LDS), at least 1.  A function has ONE entry: a launch at another size prepares it again, so
+// the attribute is always that of the launch about to be made.  (The attribute belongs to the function in the process, the
+// table to the context: DESIGN.md 4.1, "Launch preparation".)
+int resident_blocks(rt_ctx* c, const void* fn, int block, size_t dyn, int* per_cu) {
+  auto it = std::find_if(c->prepared.begin(), c->prepared.end(), [fn](const PreparedKernel& p) { return p.fn == fn; });
+  if (it == c->prepared.end()) it = c->prepared.insert(it, PreparedKernel{fn, 0, 0, 0});
+  if (it->per_cu == 0 || it->block != block || it->dyn != dyn) {
+    it->per_cu = 0;   // a failure below leaves the entry unprepared
+    HIP_TRY(c, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
+    int n = 0;
+    HIP_TRY(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fn, block, dyn));
+    it->block = block;
+    it->dyn = dyn;
+    it->per_cu = n < 1 ? 1 : n;
+  }
+  *per_cu = it->per_cu;
+  return RT_OK;
+}
+// Grid of a kernel whose workgroups loop over their work: the resident ones (per_cu, or cap_per_cu where that is set and
+// smaller: MI355RT_WF_BLOCKS_PER_CU) on every CU, no more than there is work for (`useful`), at least one.
+uint32_t grid_blocks(const rt_ctx* c, int per_cu, int cap_per_cu, uint64_t useful) {
+  if (cap_per_cu > 0 && per_cu > cap_per_cu) per_cu = cap_per_cu;
+  const uint64_t blocks = std::min<uint64_t>((uint64_t)per_cu * (uint64_t)c->num_cus, useful);
+  return blocks ? (uint32_t)blocks : 1u;
+}
+
+// ---- queries against the uploaded scene (rt_trace_rays, rt_trace_radiance): what the two kinds share.  `what` is the
+// prefix of the kind's messages, "ray query" or "radiance query"; q its QueryState.
+//
+// The scene is there and its derived records are made (prepare_scene, as a compute() would); lights: the kind samples the
+// lights.  Touches nothing of the renderer's frame state.
+int query_scene_ready(rt_ctx* c, const char* what, bool lights) {
+  const std::string w(what);
+  if (!(c->n_tris && c->n_verts && c->n_instances && c->n_nodes))
+    return fail(c, RT_ERR_NOT_READY, w + ": no scene (geometry, topology, instances and BVH must be uploaded first)");
+  if (c->blas_offset > c->n_nodes) return fail(c, RT_ERR_NOT_READY, w + ": blas_base_idx exceeds the node buffer");
+  if (lights && c->light_count > c->n_lights) return fail(c, RT_ERR_INVALID, "light_count exceeds the uploaded lights buffer");
+  HIP_TRY(c, hipSetDevice(c->device));
+  const int r = prepare_scene(c);
+  if (r < 0 && !c->validate_dirty && !c->scene_valid) return fail(c, RT_ERR_NOT_READY, w + ": " + c->scene_problem);
+  return r;
+}
+// the caller's device arrays of the device entries: there, aligned, and memory the context's device can reach
+int query_device_arrays_ok(rt_ctx* c, const char* what, const void* dev_rays, const void* dev_out) {
+  const std::string w(what);
+  if (!dev_rays || !dev_out) return fail(c, RT_ERR_INVALID, w + ": NULL array");
+  if ((((uintptr_t)dev_rays) | ((uintptr_t)dev_out)) & 15u) return fail(c, RT_ERR_INVALID, w + ": device arrays must be 16-byte aligned");
+  HIP_TRY(c, hipSetDevice(c->device));
+  for (const void* p : {dev_rays, dev_out}) {
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, p) != hipSuccess) {
+      (void)hipGetLastError();
+      return fail(c, RT_ERR_INVALID, w + ": not a device-accessible pointer");
+    }
+    if (at.type == hipMemoryTypeDevice && at.device != c->device)
+      return fail(c, RT_ERR_INVALID, w + ": the array lives on another device than the context");
+    if (at.type != hipMemoryTypeDevice && at.type != hipMemoryTypeHost && at.type != hipMemoryTypeManaged)
+      return fail(c, RT_ERR_INVALID, w + ": not a device-accessible pointer");
+  }
+  return RT_OK;
+}
+// the query's counter shards and the chunk counter behind them, zeroed on the stream
+int query_reset_counters(rt_ctx* c, QueryState& q, uint64_t** counters, uint32_t** head) {
+  const size_t counter_bytes = (size_t)RT_COUNTER_SHARDS * 6 * 8;
+  const int r = ensure_buffer(c, q.counters, counter_bytes + 16, false);
+  if (r < 0) return r;
+  HIP_TRY(c, hipMemsetAsync(q.counters.ptr, 0, counter_bytes + 16, c->stream));
+  *counters = (uint64_t*)q.counters.ptr;
+  *head = (uint32_t*)((char*)q.counters.ptr + counter_bytes);
+  return RT_OK;
+}
+// the query kernel (256-thread workgroups) on the context's stream, between the query's events when timing is on
+int query_launch(rt_ctx* c, QueryState& q, const void* fn, uint32_t blocks, void** args, size_t dyn) {
+  q.timed = false;
+  if (c->timing) {
+    for (hipEvent_t& e : q.ev)
+      if (!e) HIP_TRY(c, hipEventCreate(&e));
+    HIP_TRY(c, hipEventRecord(q.ev[0], c->stream));
+  }
+  HIP_TRY(c, hipLaunchKernel(fn, dim3(blocks), dim3(256), args, dyn, c->stream));
+  if (c->timing) {
+    HIP_TRY(c, hipEventRecord(q.ev[1], c->stream));
+    q.timed = true;
+  }
+  return RT_OK;
+}
+// The six counters of the last query summed over their shards (all 0 when `launched` is false: no query yet, or an empty
+// one); *kernel_ms is written when that query recorded its events.  Waits for the stream.
+int query_totals(rt_ctx* c, const QueryState& q, bool launched, uint64_t sum[6], double* kernel_ms) {
+  std::fill(sum, sum + 6, (uint64_t)0);
+  if (!q.counters.ptr || !launched) return RT_OK;
+  std::vector<uint64_t> host((size_t)RT_COUNTER_SHARDS * 6);
+  HIP_TRY(c, hipMemcpyAsync(host.data(), q.counters.ptr, host.size() * 8, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  for (size_t s = 0; s < RT_COUNTER_SHARDS; s++)
+    for (int k = 0; k < 6; k++) sum[k] += host[s * 6 + k];
+  if (q.timed) {
+    float ms = 0.0f;
+    HIP_TRY(c, hipEventElapsedTime(&ms, q.ev[0], q.ev[1]));
+    *kernel_ms = (double)ms;
+  }
+  return RT_OK;
+}
+// The host entries: n > 0 rays up to the query's staging array, launch(d_rays, d_out) enqueues the kind's kernel, n results
+// of out_stride bytes come back; the stream is idle on return.
+template <class Launch>
+int query_from_host(rt_ctx* c, QueryState& q, const char* what, const rt_ray* rays, uint32_t n, void* out, size_t out_stride,
+                    Launch launch) {
+  if (!rays || !out) return fail(c, RT_ERR_INVALID, std::string(what) + ": NULL array");
+  HIP_TRY(c, hipSetDevice(c->device));
+  int r;
+  if ((r = ensure_buffer(c, q.in, (size_t)n * sizeof(rt_ray), true)) < 0) return r;
+  if ((r = ensure_buffer(c, q.out, (size_t)n * out_stride, true)) < 0) return r;
+  HIP_TRY(c, hipMemcpyAsync(q.in.ptr, rays, (size_t)n * sizeof(rt_ray), hipMemcpyHostToDevice, c->stream));
+  if ((r = launch((const void*)q.in.ptr, q.out.ptr)) < 0) return r;
+  HIP_TRY(c, hipMemcpyAsync(out, q.out.ptr, (size_t)n * out_stride, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return RT_OK;
 }
 
 }  // namespace
@@ -812,7 +936,7 @@ void rt_destroy(rt_ctx* c) {
                          &c->accum, &c->render_target,
                          &c->g_normal, &c->g_depth, &c->history[0], &c->history[1], &c->counters, &c->ticket,
                          &c->slots, &c->gbuf_batch, &c->frame_col, &c->wf_state, &c->wf_queues, &c->wf_counters,
-                         &c->rq_rays, &c->rq_hits, &c->rq_counters, &c->rd_rays, &c->rd_out, &c->rd_counters,
+                         &c->rq.in, &c->rq.out, &c->rq.counters, &c->rd.in, &c->rd.out, &c->rd.counters,
                          &c->tex_staging, &c->bv_in, &c->bv_tri, &c->bv_order, &c->bv_nodes, &c->bv_out,
                          &c->bv_counters, &c->bv_big, &c->val_roots, &c->val_bad, &c->tnodes, &c->node_key, &c->node_newidx,
                          &c->inst_root, &c->root_w, &c->treelet_work, &c->pairs, &c->pair_of, &c->pair_parent, &c->root_rec,
@@ -821,10 +945,9 @@ void rt_destroy(rt_ctx* c) {
                          &c->world.static_nodes};
   for (DeviceBuffer* b : all) free_buffer(*b);
   if (c->world.pinned) (void)hipHostFree(c->world.pinned);
-  for (hipEvent_t e : c->rq_ev)
-    if (e) (void)hipEventDestroy(e);
-  for (hipEvent_t e : c->rd_ev)
-    if (e) (void)hipEventDestroy(e);
+  for (QueryState* q : {&c->rq, &c->rd})
+    for (hipEvent_t e : q->ev)
+      if (e) (void)hipEventDestroy(e);
   if (c->world.ev0) (void)hipEventDestroy(c->world.ev0);
   if (c->world.ev1) (void)hipEventDestroy(c->world.ev1);
   if (c->world.ev_t0) (void)hipEventDestroy(c->world.ev_t0);
@@ -1750,6 +1873,14 @@ static size_t lds_avail(size_t budget, size_t queue_bytes) {
   const size_t avail = budget > queue_bytes ? budget - queue_bytes : 0;
   return avail & ~(size_t)15;
 }
+// every record of the scene staged
+static rtk::LdsPlan full_lds_plan(const rt_ctx* c) {
+  rtk::LdsPlan P;
+  P.k_nodes = c->n_nodes;
+  P.stage_inst = P.stage_tri = 1;
+  P.pad = 0;
+  return P;
+}
 static rtk::LdsPlan plan_lds(const rt_ctx* c, size_t budget, size_t queue_bytes, size_t* dyn_bytes) {
   rtk::LdsPlan P;
   P.k_nodes = P.stage_inst = P.stage_tri = P.pad = 0;
@@ -1774,6 +1905,16 @@ static rtk::LdsPlan plan_lds(const rt_ctx* c, size_t budget, size_t queue_bytes,
   }
   *dyn_bytes += (size_t)P.k_nodes * 32 + (P.stage_tri ? tri_bytes : 0) + (P.stage_inst ? inst_bytes : 0);
   return P;
+}
+
+// The 256-thread forms of the persistent kernel (and the radiance query, which runs its path loop): the whole scene in LDS
+// when it fits beside four wave queues (fits_lds = scene_fits_lds), else six workgroups per CU (6 waves per SIMD), each
+// with its share of the CU's LDS for the top of the tree.
+static rtk::LdsPlan persistent_plan(const rt_ctx* c, bool fits_lds, size_t* dyn_bytes) {
+  const size_t queue_bytes = (size_t)4 * RT_WORK_BYTES_PER_WAVE;
+  if (!fits_lds) return plan_lds(c, c->lds_per_cu / 6, queue_bytes, dyn_bytes);
+  *dyn_bytes = queue_bytes + rtk::scene_lds_slots(c->n_nodes, c->n_tris, c->n_instances, c->n_verts, c->n_lights) * 16;
+  return full_lds_plan(c);
 }
 
 // The same for the child-pair walk of the trace kernels: pair records, triangle records, instance rows + root records.
@@ -1812,7 +1953,7 @@ struct TraceShape {
   rtk::LdsPlan nplan;      // node walk
 };
 static TraceShape trace_shape(const rt_ctx* c, bool fits_lds, int wf_block) {
-  const bool pairs = c->walk == 1 || (c->walk == 2 && c->n_instances == 1);   // rt_set_walk
+  const bool pairs = walks_pairs(c);
   // Workgroup shape of the trace kernels.  Every wave owns `wave_bytes` of LDS: the triangle work queue, and for the pair walk
   // the stack of deferred right children.  Everything fits beside four wave blocks in 64 KB: 256-thread workgroups, all records
   // in LDS.  Otherwise 256-thread workgroups, each staging what fits whole in its share of the LDS (plan_pairs / plan_lds): the
@@ -1835,10 +1976,7 @@ static TraceShape trace_shape(const rt_ctx* c, bool fits_lds, int wf_block) {
   rtk::PairPlan plan;
   plan.stage_pairs = plan.stage_inst = plan.stage_tri = 1;
   plan.pad = 0;
-  rtk::LdsPlan nplan;
-  nplan.k_nodes = c->n_nodes;
-  nplan.stage_inst = nplan.stage_tri = 1;
-  nplan.pad = 0;
+  rtk::LdsPlan nplan = full_lds_plan(c);
   if (!trace_lds) {
     const size_t budget = c->lds_per_cu / (size_t)blocks_per_cu;
     if (pairs)
@@ -1879,6 +2017,12 @@ static const void* const wf_pair_fns[3][2][2][2] = {RT_WF_TRACE_FNS(rtk::k_wf_tr
 static const void* const wf_node_rayreg_fns[2][2] = {
     {(const void*)rtk::k_wf_trace<false, false, false, 256, true>, (const void*)rtk::k_wf_trace<false, true, false, 256, true>},
     {(const void*)rtk::k_wf_trace<true, false, false, 256, true>, (const void*)rtk::k_wf_trace<true, true, false, 256, true>}};
+// the shade kernel by [first depth][detail], the primary kernel by [detail][lds]
+static const void* const wf_shade_fns[2][2] = {{(const void*)rtk::k_wf_shade<false, false>, (const void*)rtk::k_wf_shade<false, true>},
+                                               {(const void*)rtk::k_wf_shade<true, false>, (const void*)rtk::k_wf_shade<true, true>}};
+static const void* const primary_fns[2][2] = {
+    {(const void*)rtk::k_primary_visibility<false, false>, (const void*)rtk::k_primary_visibility<false, true>},
+    {(const void*)rtk::k_primary_visibility<true, false>, (const void*)rtk::k_primary_visibility<true, true>}};
 
 // Wavefront form: per depth one shade launch and two trace launches, all enqueued without host readback.
 static int launch_wavefront(rt_ctx* c, const DevScene& S, const DevFrame& F, const DevFrameSlot* dslots, uint32_t n,
@@ -1928,53 +2072,29 @@ static int launch_wavefront(rt_ctx* c, const DevScene& S, const DevFrame& F, con
   for (int k = 0; k < 2; k++)   // k = 0: any hit (shadow rays), 1: closest hit (extension rays)
     trace_fn[k] = pairs ? wf_pair_fns[bi][k == 0][detail][trace_lds]
                         : (rayreg && bi == 0 && !trace_lds ? wf_node_rayreg_fns[k == 0][detail] : wf_node_fns[bi][k == 0][detail][trace_lds]);
-  if (c->wf_occ_dyn != dyn || c->wf_occ_detail != (int)detail || c->wf_occ_block != block || c->wf_occ_walk != (int)pairs ||
-      c->wf_occ_rayreg != (int)rayreg || c->wf_occ_blocks[0] == 0) {
-    for (int k = 0; k < 2; k++) {
-      HIP_TRY(c, hipFuncSetAttribute(trace_fn[k], hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
-      int per_cu = 0;
-      HIP_TRY(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, trace_fn[k], block, dyn));
-      c->wf_occ_blocks[k] = per_cu < 1 ? 1 : per_cu;
-    }
-    c->wf_occ_dyn = dyn;
-    c->wf_occ_detail = (int)detail;
-    c->wf_occ_block = block;
-    c->wf_occ_walk = (int)pairs;
-    c->wf_occ_rayreg = (int)rayreg;
-  }
+  int trace_per_cu[2];
+  for (int k = 0; k < 2; k++)
+    if ((r = resident_blocks(c, trace_fn[k], block, dyn, &trace_per_cu[k])) < 0) return r;
   if (getenv("MI355RT_DEBUG_SHAPE"))
     fprintf(stderr, "[mi355rt] trace kernels: %s walk, %d threads per workgroup, %zu bytes of LDS, resident workgroups per CU: any-hit %d, closest-hit %d\n",
-            pairs ? "pair" : "node", block, dyn, c->wf_occ_blocks[0], c->wf_occ_blocks[1]);
-  uint32_t nn = pairs ? c->n_pairs : c->n_nodes, nt = c->n_tris, ni = c->n_instances;
+            pairs ? "pair" : "node", block, dyn, trace_per_cu[0], trace_per_cu[1]);
+  uint32_t nn = pairs ? c->n_pairs : c->n_nodes, nt = c->n_tris, ni = c->n_instances, depth = 0;
+  DevScene Sa = S;
+  DevFrame Fa = F;
+  rt_scene_uniforms Ua = c->uniforms;
+  void* shade_args[] = {&Sa, &Fa, &Ua, &W, &Q, &dslots, &n, &depth};
+  void* trace_args[] = {&Sa, &Fa, &Ua, &Q, &depth, &nn, &nt, &ni, pairs ? (void*)&plan : (void*)&nplan};
   EventPair* ev = next_events(c, RT_TIMER_PATHTRACE);
   if (ev) HIP_TRY(c, hipEventRecord(ev->a, c->stream));
-  for (uint32_t depth = 0; depth < depths; depth++) {
+  for (; depth < depths; depth++) {
     EventPair* evs = next_events(c, RT_TIMER_WF_SHADE);
     if (evs) HIP_TRY(c, hipEventRecord(evs->a, c->stream));
-    if (depth == 0) {
-      if (detail)
-        hipLaunchKernelGGL((rtk::k_wf_shade<true, true>), dim3(shade_blocks), dim3(256), 0, c->stream, S, F, c->uniforms, W, Q, dslots, n, depth);
-      else
-        hipLaunchKernelGGL((rtk::k_wf_shade<true, false>), dim3(shade_blocks), dim3(256), 0, c->stream, S, F, c->uniforms, W, Q, dslots, n, depth);
-    } else {
-      if (detail)
-        hipLaunchKernelGGL((rtk::k_wf_shade<false, true>), dim3(shade_blocks), dim3(256), 0, c->stream, S, F, c->uniforms, W, Q, dslots, n, depth);
-      else
-        hipLaunchKernelGGL((rtk::k_wf_shade<false, false>), dim3(shade_blocks), dim3(256), 0, c->stream, S, F, c->uniforms, W, Q, dslots, n, depth);
-    }
+    HIP_TRY(c, hipLaunchKernel(wf_shade_fns[depth == 0][detail], dim3(shade_blocks), dim3(256), shade_args, 0, c->stream));
     if (evs) HIP_TRY(c, hipEventRecord(evs->b, c->stream));
     for (int k = 0; k < 2; k++) {
       // resident workgroups: what fits (registers, LDS; since round 4 the node-walk kernels leave room for a seventh wave per
       // SIMD), or MI355RT_WF_BLOCKS_PER_CU
-      uint32_t per_cu = (uint32_t)c->wf_occ_blocks[k];
-      if (c->wf_blocks_per_cu > 0 && per_cu > (uint32_t)c->wf_blocks_per_cu) per_cu = (uint32_t)c->wf_blocks_per_cu;
-      uint32_t blocks = per_cu * (uint32_t)c->num_cus;
-      const uint32_t max_useful = (uint32_t)std::min<size_t>((items + (size_t)block - 1) / (size_t)block, (size_t)0x7fffffff);
-      if (blocks > max_useful) blocks = max_useful ? max_useful : 1;
-      DevScene Sa = S;
-      DevFrame Fa = F;
-      rt_scene_uniforms Ua = c->uniforms;
-      void* args[] = {&Sa, &Fa, &Ua, &Q, &depth, &nn, &nt, &ni, pairs ? (void*)&plan : (void*)&nplan};
+      const uint32_t blocks = grid_blocks(c, trace_per_cu[k], c->wf_blocks_per_cu, (items + (size_t)block - 1) / (size_t)block);
       EventPair* evt = next_events(c, k == 0 ? RT_TIMER_WF_TRACE_SHADOW : RT_TIMER_WF_TRACE_EXT);
       hipStream_t st = c->stream;
       if (k == 0 && c->wf_overlap) {   // any-hit trace: fork to the side stream behind this depth's shade kernel
@@ -1983,7 +2103,7 @@ static int launch_wavefront(rt_ctx* c, const DevScene& S, const DevFrame& F, con
         HIP_TRY(c, hipStreamWaitEvent(st, c->side_fork, 0));
       }
       if (evt) HIP_TRY(c, hipEventRecord(evt->a, st));
-      HIP_TRY(c, hipLaunchKernel(trace_fn[k], dim3(blocks), dim3(block), args, dyn, st));
+      HIP_TRY(c, hipLaunchKernel(trace_fn[k], dim3(blocks), dim3(block), trace_args, dyn, st));
       if (evt) HIP_TRY(c, hipEventRecord(evt->b, st));
       if (k == 0 && c->wf_overlap) HIP_TRY(c, hipEventRecord(c->side_join, st));
     }
@@ -1994,11 +2114,7 @@ static int launch_wavefront(rt_ctx* c, const DevScene& S, const DevFrame& F, con
     // here (every path of this list carries the ENDED flag, so nothing is shaded or queued)
     EventPair* evs = next_events(c, RT_TIMER_WF_SHADE);
     if (evs) HIP_TRY(c, hipEventRecord(evs->a, c->stream));
-    const uint32_t depth = depths;
-    if (detail)
-      hipLaunchKernelGGL((rtk::k_wf_shade<false, true>), dim3(shade_blocks), dim3(256), 0, c->stream, S, F, c->uniforms, W, Q, dslots, n, depth);
-    else
-      hipLaunchKernelGGL((rtk::k_wf_shade<false, false>), dim3(shade_blocks), dim3(256), 0, c->stream, S, F, c->uniforms, W, Q, dslots, n, depth);
+    HIP_TRY(c, hipLaunchKernel(wf_shade_fns[0][detail], dim3(shade_blocks), dim3(256), shade_args, 0, c->stream));   // depth == depths
     if (evs) HIP_TRY(c, hipEventRecord(evs->b, c->stream));
   }
   if (ev) HIP_TRY(c, hipEventRecord(ev->b, c->stream));
@@ -2016,48 +2132,25 @@ static const void* const rq_fns[5][2][2] = {RT_RQ_FNS(rtk::RT_RQ_NODE_LDS), RT_R
                                             RT_RQ_FNS(rtk::RT_RQ_PAIR_LDS), RT_RQ_FNS(rtk::RT_RQ_PAIR_GLOBAL)};
 #undef RT_RQ_FNS
 
-// Enqueue one query on the context's stream: n > 0 rays at d_rays, results to d_out (device pointers).  Touches the scene's
-// derived records (prepare_scene, as a compute() would) and the query's own buffers, nothing of the renderer's frame state.
+// Enqueue one query on the context's stream: n > 0 rays at d_rays, results to d_out (device pointers).
 static int launch_ray_query(rt_ctx* c, const void* d_rays, uint32_t n, int mode, float t_min, void* d_out, bool detail) {
-  if (!(c->n_tris && c->n_verts && c->n_instances && c->n_nodes))
-    return fail(c, RT_ERR_NOT_READY, "ray query: no scene (geometry, topology, instances and BVH must be uploaded first)");
-  if (c->blas_offset > c->n_nodes) return fail(c, RT_ERR_NOT_READY, "ray query: blas_base_idx exceeds the node buffer");
-  HIP_TRY(c, hipSetDevice(c->device));
-  int r = prepare_scene(c);
-  if (r < 0) {
-    if (!c->validate_dirty && !c->scene_valid) return fail(c, RT_ERR_NOT_READY, "ray query: " + c->scene_problem);
-    return r;
-  }
+  int r = query_scene_ready(c, "ray query", false);
+  if (r < 0) return r;
   const TraceShape shape = trace_shape(c, scene_fits_lds(c), 0);
   const int form = shape.pairs ? (shape.trace_lds ? rtk::RT_RQ_PAIR_LDS : rtk::RT_RQ_PAIR_GLOBAL)
                                : (shape.trace_lds ? rtk::RT_RQ_NODE_LDS : (shape.rayreg ? rtk::RT_RQ_NODE_RAYREG : rtk::RT_RQ_NODE_MIXED));
   const void* fn = rq_fns[form][mode == RT_RAYS_ANY][detail];
   const size_t dyn = shape.dyn;
-  if (c->rq_occ_fn != fn || c->rq_occ_dyn != dyn || c->rq_occ_blocks == 0) {
-    HIP_TRY(c, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
-    int per_cu = 0;
-    HIP_TRY(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 256, dyn));
-    c->rq_occ_blocks = per_cu < 1 ? 1 : per_cu;
-    c->rq_occ_fn = fn;
-    c->rq_occ_dyn = dyn;
-  }
-  uint32_t per_cu = (uint32_t)c->rq_occ_blocks;
-  if (c->wf_blocks_per_cu > 0 && per_cu > (uint32_t)c->wf_blocks_per_cu) per_cu = (uint32_t)c->wf_blocks_per_cu;
-  uint32_t blocks = per_cu * (uint32_t)c->num_cus;
-  const uint32_t max_useful = (n + 255u) / 256u;
-  if (blocks > max_useful) blocks = max_useful;
+  int per_cu;
+  if ((r = resident_blocks(c, fn, 256, dyn, &per_cu)) < 0) return r;
+  const uint32_t blocks = grid_blocks(c, per_cu, c->wf_blocks_per_cu, (n + 255u) / 256u);
   if (getenv("MI355RT_DEBUG_SHAPE"))
     fprintf(stderr, "[mi355rt] ray query: %s walk, form %d, %zu bytes of LDS, resident workgroups per CU %d, %u workgroups\n",
-            shape.pairs ? "pair" : "node", form, dyn, c->rq_occ_blocks, blocks);
-  const size_t counter_bytes = (size_t)RT_COUNTER_SHARDS * 6 * 8;
-  r = ensure_buffer(c, c->rq_counters, counter_bytes + 16, false);
-  if (r < 0) return r;
-  HIP_TRY(c, hipMemsetAsync(c->rq_counters.ptr, 0, counter_bytes + 16, c->stream));
+            shape.pairs ? "pair" : "node", form, dyn, per_cu, blocks);
   rtk::RayQueryArgs A;
+  if ((r = query_reset_counters(c, c->rq, &A.counters, &A.head)) < 0) return r;
   A.rays = (const float4*)d_rays;
   A.out = (uint4*)d_out;
-  A.head = (uint32_t*)((char*)c->rq_counters.ptr + counter_bytes);
-  A.counters = (uint64_t*)c->rq_counters.ptr;
   A.n_rays = n;
   A.blas_base = c->blas_offset;
   A.t_min = t_min;
@@ -2068,17 +2161,7 @@ static int launch_ray_query(rt_ctx* c, const void* d_rays, uint32_t n, int mode,
   rtk::LdsPlan nplan = shape.nplan;
   rtk::PairPlan plan = shape.plan;
   void* args[] = {&S, &A, &nplan, &plan};
-  c->rq_timed = false;
-  if (c->timing) {
-    for (hipEvent_t& e : c->rq_ev)
-      if (!e) HIP_TRY(c, hipEventCreate(&e));
-    HIP_TRY(c, hipEventRecord(c->rq_ev[0], c->stream));
-  }
-  HIP_TRY(c, hipLaunchKernel(fn, dim3(blocks), dim3(256), args, dyn, c->stream));
-  if (c->timing) {
-    HIP_TRY(c, hipEventRecord(c->rq_ev[1], c->stream));
-    c->rq_timed = true;
-  }
+  if ((r = query_launch(c, c->rq, fn, blocks, args, dyn)) < 0) return r;
   c->rq_last = rt_ray_stats();
   c->rq_last.walk = shape.pairs ? 1u : 0u;
   c->rq_last.lds = shape.trace_lds ? 1u : 0u;
@@ -2098,20 +2181,12 @@ int rt_ray_query_stats(rt_ctx* c, rt_ray_stats* out) {
   if (!c || !out) return RT_ERR_INVALID;
   HIP_TRY(c, hipSetDevice(c->device));
   *out = c->rq_last;
-  if (!c->rq_counters.ptr || c->rq_last.workgroups == 0) return RT_OK;   // no query yet, or an empty one
-  std::vector<uint64_t> host((size_t)RT_COUNTER_SHARDS * 6);
-  HIP_TRY(c, hipMemcpyAsync(host.data(), c->rq_counters.ptr, host.size() * 8, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  for (size_t s = 0; s < RT_COUNTER_SHARDS; s++) {
-    out->rays += host[s * 6 + 1] + host[s * 6 + 2];
-    out->nodes_visited += host[s * 6 + 3];
-    out->tris_tested += host[s * 6 + 4];
-  }
-  if (c->rq_timed) {
-    float ms = 0.0f;
-    HIP_TRY(c, hipEventElapsedTime(&ms, c->rq_ev[0], c->rq_ev[1]));
-    out->kernel_ms = (double)ms;
-  }
+  uint64_t sum[6];
+  const int r = query_totals(c, c->rq, c->rq_last.workgroups != 0, sum, &out->kernel_ms);
+  if (r < 0) return r;
+  out->rays += sum[1] + sum[2];
+  out->nodes_visited += sum[3];
+  out->tris_tested += sum[4];
   return RT_OK;
 }
 
@@ -2123,20 +2198,7 @@ int rt_trace_rays_device(rt_ctx* c, const void* dev_rays, uint32_t n, int mode, 
     c->rq_last = rt_ray_stats();
     return RT_OK;
   }
-  if (!dev_rays || !dev_out) return fail(c, RT_ERR_INVALID, "ray query: NULL array");
-  if ((((uintptr_t)dev_rays) | ((uintptr_t)dev_out)) & 15u) return fail(c, RT_ERR_INVALID, "ray query: device arrays must be 16-byte aligned");
-  HIP_TRY(c, hipSetDevice(c->device));
-  for (const void* p : {dev_rays, (const void*)dev_out}) {
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, p) != hipSuccess) {
-      (void)hipGetLastError();
-      return fail(c, RT_ERR_INVALID, "ray query: not a device-accessible pointer");
-    }
-    if (at.type == hipMemoryTypeDevice && at.device != c->device)
-      return fail(c, RT_ERR_INVALID, "ray query: the array lives on another device than the context");
-    if (at.type != hipMemoryTypeDevice && at.type != hipMemoryTypeHost && at.type != hipMemoryTypeManaged)
-      return fail(c, RT_ERR_INVALID, "ray query: not a device-accessible pointer");
-  }
+  if ((r = query_device_arrays_ok(c, "ray query", dev_rays, dev_out)) < 0) return r;
   return launch_ray_query(c, dev_rays, n, mode, t_min, dev_out, c->detailed_counters);
 }
 
@@ -2149,14 +2211,10 @@ int rt_trace_rays(rt_ctx* c, const rt_ray* rays, uint32_t n, int mode, float t_m
     if (stats) *stats = c->rq_last;
     return RT_OK;
   }
-  if (!rays || !out) return fail(c, RT_ERR_INVALID, "ray query: NULL array");
-  HIP_TRY(c, hipSetDevice(c->device));
-  if ((r = ensure_buffer(c, c->rq_rays, (size_t)n * sizeof(rt_ray), true)) < 0) return r;
-  if ((r = ensure_buffer(c, c->rq_hits, (size_t)n * sizeof(rt_ray_hit), true)) < 0) return r;
-  HIP_TRY(c, hipMemcpyAsync(c->rq_rays.ptr, rays, (size_t)n * sizeof(rt_ray), hipMemcpyHostToDevice, c->stream));
-  if ((r = launch_ray_query(c, c->rq_rays.ptr, n, mode, t_min, c->rq_hits.ptr, stats != nullptr)) < 0) return r;
-  HIP_TRY(c, hipMemcpyAsync(out, c->rq_hits.ptr, (size_t)n * sizeof(rt_ray_hit), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  r = query_from_host(c, c->rq, "ray query", rays, n, out, sizeof(rt_ray_hit), [&](const void* d_rays, void* d_out) {
+    return launch_ray_query(c, d_rays, n, mode, t_min, d_out, stats != nullptr);
+  });
+  if (r < 0) return r;
   if (stats) return rt_ray_query_stats(c, stats);
   return RT_OK;
 }
@@ -2166,54 +2224,26 @@ static const void* const rd_fns[2][2] = {
     {(const void*)rtk::k_radiance_query<false, false>, (const void*)rtk::k_radiance_query<false, true>},
     {(const void*)rtk::k_radiance_query<true, false>, (const void*)rtk::k_radiance_query<true, true>}};
 
-// Enqueue one query on the context's stream: n > 0 rays at d_rays, results to d_out (device pointers).  Like
-// launch_ray_query it touches the scene's derived records and the query's own buffers, nothing of the renderer's frame state.
+// Enqueue one query on the context's stream: n > 0 rays at d_rays, results to d_out (device pointers).
 static int launch_radiance_query(rt_ctx* c, const void* d_rays, uint32_t n, uint32_t max_depth, uint32_t spp, uint32_t seed,
                                  void* d_out, bool detail) {
-  if (!(c->n_tris && c->n_verts && c->n_instances && c->n_nodes))
-    return fail(c, RT_ERR_NOT_READY, "radiance query: no scene (geometry, topology, instances and BVH must be uploaded first)");
-  if (c->blas_offset > c->n_nodes) return fail(c, RT_ERR_NOT_READY, "radiance query: blas_base_idx exceeds the node buffer");
-  if (c->light_count > c->n_lights) return fail(c, RT_ERR_INVALID, "light_count exceeds the uploaded lights buffer");
-  HIP_TRY(c, hipSetDevice(c->device));
-  int r = prepare_scene(c);
-  if (r < 0) {
-    if (!c->validate_dirty && !c->scene_valid) return fail(c, RT_ERR_NOT_READY, "radiance query: " + c->scene_problem);
-    return r;
-  }
-  // the form choice of the persistent kernel's 256-thread forms without the one-leaf one: the whole scene in LDS when it
-  // fits beside four wave queues, else six workgroups per CU, each with its share of the LDS for the traversal records
+  int r = query_scene_ready(c, "radiance query", true);
+  if (r < 0) return r;
+  // the persistent kernel's 256-thread forms without the one-leaf one
   const bool lds = scene_fits_lds(c);
-  size_t dyn = (size_t)4 * RT_WORK_BYTES_PER_WAVE +
-               rtk::scene_lds_slots(c->n_nodes, c->n_tris, c->n_instances, c->n_verts, c->n_lights) * 16;
-  rtk::LdsPlan plan;
-  plan.k_nodes = c->n_nodes;
-  plan.stage_inst = plan.stage_tri = 1;
-  plan.pad = 0;
-  if (!lds) plan = plan_lds(c, c->lds_per_cu / 6, (size_t)4 * RT_WORK_BYTES_PER_WAVE, &dyn);
+  size_t dyn;
+  rtk::LdsPlan plan = persistent_plan(c, lds, &dyn);
   const void* fn = rd_fns[detail][lds];
-  if (c->rd_occ_fn != fn || c->rd_occ_dyn != dyn || c->rd_occ_blocks == 0) {
-    HIP_TRY(c, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
-    int per_cu = 0;
-    HIP_TRY(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 256, dyn));
-    c->rd_occ_blocks = per_cu < 1 ? 1 : per_cu;
-    c->rd_occ_fn = fn;
-    c->rd_occ_dyn = dyn;
-  }
-  uint32_t blocks = (uint32_t)c->rd_occ_blocks * (uint32_t)c->num_cus;
-  const uint32_t max_useful = (n + 255u) / 256u;
-  if (blocks > max_useful) blocks = max_useful;
+  int per_cu;
+  if ((r = resident_blocks(c, fn, 256, dyn, &per_cu)) < 0) return r;
+  const uint32_t blocks = grid_blocks(c, per_cu, 0, (n + 255u) / 256u);
   if (getenv("MI355RT_DEBUG_SHAPE"))
     fprintf(stderr, "[mi355rt] radiance query: %s form, %zu bytes of LDS, resident workgroups per CU %d, %u workgroups\n",
-            lds ? "LDS" : "global", dyn, c->rd_occ_blocks, blocks);
-  const size_t counter_bytes = (size_t)RT_COUNTER_SHARDS * 6 * 8;
-  r = ensure_buffer(c, c->rd_counters, counter_bytes + 16, false);
-  if (r < 0) return r;
-  HIP_TRY(c, hipMemsetAsync(c->rd_counters.ptr, 0, counter_bytes + 16, c->stream));
+            lds ? "LDS" : "global", dyn, per_cu, blocks);
   rtk::RadianceArgs A;
+  if ((r = query_reset_counters(c, c->rd, &A.counters, &A.head)) < 0) return r;
   A.rays = (const float4*)d_rays;
   A.out = (float4*)d_out;
-  A.head = (uint32_t*)((char*)c->rd_counters.ptr + counter_bytes);
-  A.counters = (uint64_t*)c->rd_counters.ptr;
   A.n_rays = n;
   A.max_depth = max_depth;
   A.spp = spp;
@@ -2226,17 +2256,7 @@ static int launch_radiance_query(rt_ctx* c, const void* d_rays, uint32_t n, uint
   A.n_verts = c->n_verts;
   DevScene S = dev_scene(c);
   void* args[] = {&S, &A, &plan};
-  c->rd_timed = false;
-  if (c->timing) {
-    for (hipEvent_t& e : c->rd_ev)
-      if (!e) HIP_TRY(c, hipEventCreate(&e));
-    HIP_TRY(c, hipEventRecord(c->rd_ev[0], c->stream));
-  }
-  HIP_TRY(c, hipLaunchKernel(fn, dim3(blocks), dim3(256), args, dyn, c->stream));
-  if (c->timing) {
-    HIP_TRY(c, hipEventRecord(c->rd_ev[1], c->stream));
-    c->rd_timed = true;
-  }
+  if ((r = query_launch(c, c->rd, fn, blocks, args, dyn)) < 0) return r;
   c->rd_last = rt_radiance_stats();
   c->rd_last.rays = n;
   c->rd_last.samples = (uint64_t)n * spp;
@@ -2255,22 +2275,14 @@ int rt_radiance_query_stats(rt_ctx* c, rt_radiance_stats* out) {
   if (!c || !out) return RT_ERR_INVALID;
   HIP_TRY(c, hipSetDevice(c->device));
   *out = c->rd_last;
-  if (!c->rd_counters.ptr || c->rd_last.workgroups == 0) return RT_OK;   // no query yet, or an empty one
-  std::vector<uint64_t> host((size_t)RT_COUNTER_SHARDS * 6);
-  HIP_TRY(c, hipMemcpyAsync(host.data(), c->rd_counters.ptr, host.size() * 8, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  for (size_t s = 0; s < RT_COUNTER_SHARDS; s++) {
-    out->extension_rays += host[s * 6 + 1];
-    out->shadow_rays += host[s * 6 + 2];
-    out->nodes_visited += host[s * 6 + 3];
-    out->tris_tested += host[s * 6 + 4];
-    out->shaded_hits += host[s * 6 + 5];
-  }
-  if (c->rd_timed) {
-    float ms = 0.0f;
-    HIP_TRY(c, hipEventElapsedTime(&ms, c->rd_ev[0], c->rd_ev[1]));
-    out->kernel_ms = (double)ms;
-  }
+  uint64_t sum[6];
+  const int r = query_totals(c, c->rd, c->rd_last.workgroups != 0, sum, &out->kernel_ms);
+  if (r < 0) return r;
+  out->extension_rays += sum[1];
+  out->shadow_rays += sum[2];
+  out->nodes_visited += sum[3];
+  out->tris_tested += sum[4];
+  out->shaded_hits += sum[5];
   return RT_OK;
 }
 
@@ -2283,21 +2295,7 @@ int rt_trace_radiance_device(rt_ctx* c, const void* dev_rays, uint32_t n, uint32
     c->rd_last = rt_radiance_stats();
     return RT_OK;
   }
-  if (!dev_rays || !dev_out) return fail(c, RT_ERR_INVALID, "radiance query: NULL array");
-  if ((((uintptr_t)dev_rays) | ((uintptr_t)dev_out)) & 15u)
-    return fail(c, RT_ERR_INVALID, "radiance query: device arrays must be 16-byte aligned");
-  HIP_TRY(c, hipSetDevice(c->device));
-  for (const void* p : {dev_rays, (const void*)dev_out}) {
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, p) != hipSuccess) {
-      (void)hipGetLastError();
-      return fail(c, RT_ERR_INVALID, "radiance query: not a device-accessible pointer");
-    }
-    if (at.type == hipMemoryTypeDevice && at.device != c->device)
-      return fail(c, RT_ERR_INVALID, "radiance query: the array lives on another device than the context");
-    if (at.type != hipMemoryTypeDevice && at.type != hipMemoryTypeHost && at.type != hipMemoryTypeManaged)
-      return fail(c, RT_ERR_INVALID, "radiance query: not a device-accessible pointer");
-  }
+  if ((r = query_device_arrays_ok(c, "radiance query", dev_rays, dev_out)) < 0) return r;
   return launch_radiance_query(c, dev_rays, n, max_depth, spp, seed, dev_out, c->detailed_counters);
 }
 
@@ -2311,14 +2309,10 @@ int rt_trace_radiance(rt_ctx* c, const rt_ray* rays, uint32_t n, uint32_t max_de
     if (stats) *stats = c->rd_last;
     return RT_OK;
   }
-  if (!rays || !out) return fail(c, RT_ERR_INVALID, "radiance query: NULL array");
-  HIP_TRY(c, hipSetDevice(c->device));
-  if ((r = ensure_buffer(c, c->rd_rays, (size_t)n * sizeof(rt_ray), true)) < 0) return r;
-  if ((r = ensure_buffer(c, c->rd_out, (size_t)n * sizeof(rt_radiance), true)) < 0) return r;
-  HIP_TRY(c, hipMemcpyAsync(c->rd_rays.ptr, rays, (size_t)n * sizeof(rt_ray), hipMemcpyHostToDevice, c->stream));
-  if ((r = launch_radiance_query(c, c->rd_rays.ptr, n, max_depth, spp, seed, c->rd_out.ptr, stats != nullptr)) < 0) return r;
-  HIP_TRY(c, hipMemcpyAsync(out, c->rd_out.ptr, (size_t)n * sizeof(rt_radiance), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  r = query_from_host(c, c->rd, "radiance query", rays, n, out, sizeof(rt_radiance), [&](const void* d_rays, void* d_out) {
+    return launch_radiance_query(c, d_rays, n, max_depth, spp, seed, d_out, stats != nullptr);
+  });
+  if (r < 0) return r;
   if (stats) return rt_radiance_query_stats(c, stats);
   return RT_OK;
 }
@@ -2447,20 +2441,13 @@ static int compute_frames(rt_ctx* c, const uint32_t* frame_counts, uint32_t n, u
   // grid of x-size 0 is an invalid launch configuration
   if (ptiles) {
     const size_t plds = rtk::primary_lds_slots(c->n_nodes, c->n_tris, c->n_instances, c->n_verts) * 16;
-    const uint32_t nn = c->n_nodes, nt = c->n_tris, ni = c->n_instances, nv = c->n_verts;
+    uint32_t nn = c->n_nodes, nt = c->n_tris, ni = c->n_instances, nv = c->n_verts, n_ptiles = ptiles;
     // one-leaf scenes: the LDS form stages the shading records with world-space vertex normals
     const float4* tsw = (one_leaf_lds(c) && !c->world_rec_dirty) ? (const float4*)c->tri_shade_w.ptr : nullptr;
-    if (plds <= 32 * 1024 && !c->no_lds_staging) {  // small scene: records staged in LDS, four tiles per workgroup
-      const dim3 grid((ptiles + 3) / 4, n);
-      if (c->detailed_counters)
-        hipLaunchKernelGGL((rtk::k_primary_visibility<true, true>), grid, dim3(256), plds, c->stream, S, Fp, c->uniforms, dslots, ptiles, nn, nt, ni, nv, tsw);
-      else
-        hipLaunchKernelGGL((rtk::k_primary_visibility<false, true>), grid, dim3(256), plds, c->stream, S, Fp, c->uniforms, dslots, ptiles, nn, nt, ni, nv, tsw);
-    } else if (c->detailed_counters) {
-      hipLaunchKernelGGL((rtk::k_primary_visibility<true, false>), dim3(ptiles, n), dim3(64), 0, c->stream, S, Fp, c->uniforms, dslots, ptiles, nn, nt, ni, nv, tsw);
-    } else {
-      hipLaunchKernelGGL((rtk::k_primary_visibility<false, false>), dim3(ptiles, n), dim3(64), 0, c->stream, S, Fp, c->uniforms, dslots, ptiles, nn, nt, ni, nv, tsw);
-    }
+    const bool lds = plds <= 32 * 1024 && !c->no_lds_staging;   // small scene: records staged in LDS, four tiles per workgroup
+    void* args[] = {&S, &Fp, &c->uniforms, &dslots, &n_ptiles, &nn, &nt, &ni, &nv, &tsw};
+    HIP_TRY(c, hipLaunchKernel(primary_fns[c->detailed_counters][lds], lds ? dim3((ptiles + 3) / 4, n) : dim3(ptiles, n),
+                               dim3(lds ? 256 : 64), args, lds ? plds : 0, c->stream));
   }
   if (ev) HIP_TRY(c, hipEventRecord(ev->b, c->stream));
 
@@ -2479,14 +2466,8 @@ static int compute_frames(rt_ctx* c, const uint32_t* frame_counts, uint32_t n, u
   } else {
     // persistent kernel: grid = resident workgroups, tiles handed out through a ticket counter
     HIP_TRY(c, hipMemsetAsync(c->ticket.ptr, 0, 4, c->stream));
-    size_t dyn = (size_t)4 * RT_WORK_BYTES_PER_WAVE + scene_lds;  // work queues + records
-    rtk::LdsPlan plan;
-    plan.k_nodes = c->n_nodes;
-    plan.stage_inst = plan.stage_tri = 1;
-    plan.pad = 0;
-    // a scene that does not fit as a whole: six 256-thread workgroups per CU (6 waves / SIMD), each with its share of the
-    // CU's LDS for the top of the tree
-    if (!fits_lds) plan = plan_lds(c, c->lds_per_cu / 6, (size_t)4 * RT_WORK_BYTES_PER_WAVE, &dyn);
+    size_t dyn;  // work queues + records
+    rtk::LdsPlan plan = persistent_plan(c, fits_lds, &dyn);
     // LDS form of a scene whose TLAS is one node, which is a leaf (k_validate_scene, or the world update's builder): the walks skip the TLAS
     // half of the node step (k_traverse.hip.h traverse<.., ONE_INST>)
     const bool one_inst = one_leaf_lds(c);
@@ -2513,19 +2494,11 @@ static int compute_frames(rt_ctx* c, const uint32_t* frame_counts, uint32_t n, u
                                        (const void*)rtk::k_pathtrace_persistent<true, true, true>,
                                        (const void*)rtk::k_pathtrace_persistent_wide<false, true, true>};
     const void* fn = fns[vi];
-    // resident workgroups per CU: queried once per (variant, LDS size)
-    if (c->occ_dyn[vi] != dyn || c->occ_blocks[vi] == 0) {
-      int per_cu = 0;
-      HIP_TRY(c, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
-      HIP_TRY(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, (int)(64 * waves), dyn));
-      c->occ_blocks[vi] = per_cu < 1 ? 1 : per_cu;
-      c->occ_dyn[vi] = dyn;
-    }
-    uint32_t blocks = (uint32_t)c->occ_blocks[vi] * (uint32_t)c->num_cus;
+    int per_cu;
+    if ((r = resident_blocks(c, fn, (int)(64 * waves), dyn, &per_cu)) < 0) return r;
     const uint32_t own_tiles = F.own_period ? ((c->width + 7) / 8) * F.own_tile_rows : tiles;
     // as many waves as there are tickets (tiles x frames), up to the resident limit; fewer, longer-lived waves measured worse
-    const uint32_t max_useful = (own_tiles * n + waves - 1) / waves;
-    if (blocks > max_useful) blocks = max_useful ? max_useful : 1;
+    const uint32_t blocks = grid_blocks(c, per_cu, 0, (own_tiles * n + waves - 1) / waves);
     uint32_t* ticket = (uint32_t*)c->ticket.ptr;
     uint32_t nn = c->n_nodes, nt = c->n_tris, ni = c->n_instances, nv = c->n_verts, ns = n;
     void* args[] = {&S, &F, &c->uniforms, &ticket, &nn, &nt, &ni, &nv, &dslots, &ns, &plan};
@@ -2535,7 +2508,7 @@ static int compute_frames(rt_ctx* c, const uint32_t* frame_counts, uint32_t n, u
     c->pt_launch[0] = 64 * waves;
     c->pt_launch[1] = blocks;
     c->pt_launch[2] = (uint32_t)dyn;
-    c->pt_launch[3] = (uint32_t)c->occ_blocks[vi];
+    c->pt_launch[3] = (uint32_t)per_cu;
     if (ev) HIP_TRY(c, hipEventRecord(ev->b, c->stream));
     if (n > 1)  // ordered accumulation of the batch's frame colours
       hipLaunchKernelGGL(rtk::k_accumulate_frames, dim3((uint32_t)((npx + 255) / 256)), dim3(256), 0, c->stream, F, dslots,
