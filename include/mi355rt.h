@@ -368,6 +368,53 @@ int rt_trace_radiance_device(rt_ctx* ctx, const void* dev_rays, uint32_t n, uint
                              void* dev_out);
 int rt_radiance_query_stats(rt_ctx* ctx, rt_radiance_stats* out);
 
+/* ---- irradiance gathers: "how much light arrives at this surface point?" (lightmap and light-probe bakes, ambient
+ * occlusion) ----
+ * A radiance query traces the same ray for all spp samples of an entry; an irradiance estimate needs another direction per
+ * sample.  Here the work item is a surface point (rt_gather_point): the hemisphere directions are drawn on the device, the
+ * renderer's path tracing runs behind them and only the per-point mean comes back, by the fifth driver of the path state
+ * machine (k_irradiance_gather, csrc/k_gather.hip.h).  For point i and sample s in 0 .. spp-1, with f = seed * spp + s in
+ * u32 arithmetic:
+ *   direction  the .dir of the reference's Lambert sampler (sample_diffuse, Raytracer.wgsl:228-233, 191-199: build_onb, phi =
+ *              2 pi r1, cos(theta) = sqrt(1 - r2), sin(theta) = sqrt(r2), to_world) on n = normalize(points[i].normal), and
+ *              nothing else of it; its two rand_pcg draws come from a direction stream of their own, init_rng(pad ^
+ *              0x80000000, f).  The direction is not normalised again.  The normal is not validated: a zero or non-finite
+ *              normal gets whatever the arithmetic gives, and both walks terminate for any bit pattern, as for ray queries.
+ *   sample     exactly what rt_trace_radiance returns for the ray {position, t_max, that direction, pad} with spp = 1 and
+ *              seed = f: the path's rng is init_rng(pad, f), the first segment is the closest hit in (0.001, t_max), the
+ *              depth-0 surface comes from the traced hit, later segments use 0.001 / 1e30, and the light count is that of the
+ *              last rt_set_scene.  A gather is thereby the composition of things this header already defines:
+ *              gather(i, s) == radiance query on a host-made ray, bit for bit.  Keep pad < 2^31, so that direction streams
+ *              and path streams stay apart.
+ *   result     rgb = (((0 + r_0) + r_1) + ...) in sample order, divided by spp the way `main` does (:811; no division for
+ *              spp == 1).  This is the cosine-weighted mean incoming radiance, E / pi: no factor pi is applied - multiply by
+ *              pi for irradiance, or by the albedo for the outgoing radiance of a Lambert texel.  hit_fraction = hits / spp,
+ *              hits = the samples whose first segment hit something in (0.001, t_max).  max_depth == 0: all spp first
+ *              segments are still traced, rgb = +0, and 1 - hit_fraction is ambient occlusion of radius t_max.
+ * Every sample's first segment counts as one extension ray, so the stats of a gather (an rt_radiance_stats with rays = n
+ * points and samples = n * spp) are the sums of the stats of the radiance queries it is composed of.  A result depends on
+ * (scene, point, pad, seed, spp, max_depth) only - never on n, the point's position in the array, its neighbours or the
+ * form of the kernel (picked as for radiance queries; MI355RT_NO_LDS_STAGING respected).  A lane keeps its point for all
+ * spp samples, so few points with a very large spp fill few lanes: replicate the point with different pads and average the
+ * results, which is exact.
+ * A gather leaves the renderer as it was, exactly like the two queries above: it has its own staging, chunk counter,
+ * counter shards and event pair, and the accumulation, jitter and frame counts, the rt_counters, the G-buffer and the frames
+ * traced ahead under rt_set_lookahead are untouched.
+ *   rt_gather_irradiance         blocking: copies n points in, gathers, copies n results out (staging buffers are kept and
+ *                                grown).  stats != NULL runs the counting kernel and fills *stats.  n == 0 is RT_OK; n >=
+ *                                2^31, a NULL pointer, spp == 0 or spp > 65536 is RT_ERR_INVALID; without a valid scene
+ *                                RT_ERR_NOT_READY with the reason in rt_last_error; light_count above the uploaded lights
+ *                                buffer is RT_ERR_INVALID.
+ *   rt_gather_irradiance_device  the same on device-accessible arrays (n rt_gather_point in, n rt_irradiance out; 16-byte
+ *                                aligned, on the context's device): only enqueues on the context's stream (rt_set_stream
+ *                                respected).  Counts while rt_set_counting(ctx, 1) is on.
+ *   rt_irradiance_gather_stats   stats of the last gather (blocking: fences the stream). */
+int rt_gather_irradiance(rt_ctx* ctx, const rt_gather_point* points, uint32_t n, uint32_t max_depth, uint32_t spp, uint32_t seed,
+                         rt_irradiance* out, rt_radiance_stats* stats);
+int rt_gather_irradiance_device(rt_ctx* ctx, const void* dev_points, uint32_t n, uint32_t max_depth, uint32_t spp, uint32_t seed,
+                                void* dev_out);
+int rt_irradiance_gather_stats(rt_ctx* ctx, rt_radiance_stats* out);
+
 /* ---- the sharded image: one picture rendered by `world` contexts ("ranks"), assembled on rank 0 ----
  * Rank k owns the image rows y with (y / stripe_rows) % world == k and traces only those (rt_set_stripes).  Its COMPACT
  * BLOCK holds the rows it owns in ascending y, width float4 each, padded with zero rows to max_rows = the largest share

@@ -144,8 +144,26 @@ typedef struct rt_radiance_stats { /* 72 B, of ONE call */
   double kernel_ms;           /* device events around the launch while rt_set_kernel_timing is on, else 0 */
 } rt_radiance_stats;
 
+/* ---- irradiance gathers (rt_gather_irradiance, mi355rt.h); their stats are an rt_radiance_stats with rays = points ---- */
+typedef struct rt_gather_point { /* 32 B: the slots of rt_ray {position, t_max} {normal, pad} */
+  float position[3];
+  float t_max;                /* of every sample's first segment */
+  float normal[3];            /* need not be normalised; not validated */
+  uint32_t pad;               /* the point's RNG stream id; keep it below 2^31 */
+} rt_gather_point;
+typedef struct rt_irradiance { /* 16 B: one vector store of k_irradiance_gather */
+  float rgb[3];               /* cosine-weighted mean incoming radiance = E / pi: sum of the samples / spp */
+  float hit_fraction;         /* samples whose first segment hit something / spp */
+} rt_irradiance;
+
 #ifdef __cplusplus
 }
+static_assert(sizeof(rt_gather_point) == 32, "rt_gather_point is 32 bytes");
+static_assert(__builtin_offsetof(rt_gather_point, t_max) == 12 && __builtin_offsetof(rt_gather_point, normal) == 16 &&
+                  __builtin_offsetof(rt_gather_point, pad) == 28,
+              "rt_gather_point has the slots of rt_ray");
+static_assert(sizeof(rt_irradiance) == 16, "rt_irradiance is 16 bytes");
+static_assert(__builtin_offsetof(rt_irradiance, hit_fraction) == 12, "hit_fraction is the fourth word");
 static_assert(sizeof(rt_radiance) == 16, "rt_radiance is 16 bytes");
 static_assert(sizeof(rt_radiance_stats) == 72, "rt_radiance_stats is 72 bytes");
 static_assert(sizeof(rt_ray) == 32, "rt_ray is 32 bytes");

@@ -52,8 +52,8 @@ struct PreparedKernel {
   int per_cu;
 };
 
-// What one kind of query (rt_trace_rays, rt_trace_radiance) keeps between calls: the staging arrays of its host entry, its
-// own counter shards with the chunk counter behind them, and the events around its last launch.
+// What one kind of query (rt_trace_rays, rt_trace_radiance, rt_gather_irradiance) keeps between calls: the staging arrays of
+// its host entry, its own counter shards with the chunk counter behind them, and the events around its last launch.
 struct QueryState {
   DeviceBuffer in, out, counters;
   hipEvent_t ev[2] = {nullptr, nullptr};
@@ -202,10 +202,12 @@ struct rt_ctx {
   DeviceBuffer gbuf_batch;  // G-buffer planes of frames 0..n-2 of a batch (the last frame uses the main planes)
   DeviceBuffer frame_col;   // per-frame colours of a batch, added in frame order by k_accumulate_frames
   DeviceBuffer wf_state, wf_queues, wf_counters;  // wavefront form: path state, ray / path queues, queue counters
-  // ray queries (rt_trace_rays) and radiance queries (rt_trace_radiance): buffers and events, shape and stats of the last query
-  QueryState rq, rd;
+  // ray queries (rt_trace_rays), radiance queries (rt_trace_radiance) and irradiance gathers (rt_gather_irradiance): buffers
+  // and events, shape and stats of the last query
+  QueryState rq, rd, gi;
   rt_ray_stats rq_last = {};
   rt_radiance_stats rd_last = {};
+  rt_radiance_stats gi_last = {};
 
   // kernel timing
   bool timing = false;
@@ -738,8 +740,8 @@ uint32_t grid_blocks(const rt_ctx* c, int per_cu, int cap_per_cu, uint64_t usefu
   return blocks ? (uint32_t)blocks : 1u;
 }
 
-// ---- queries against the uploaded scene (rt_trace_rays, rt_trace_radiance): what the two kinds share.  `what` is the
-// prefix of the kind's messages, "ray query" or "radiance query"; q its QueryState.
+// ---- queries against the uploaded scene (rt_trace_rays, rt_trace_radiance, rt_gather_irradiance): what the kinds share.
+// `what` is the prefix of the kind's messages, "ray query", "radiance query" or "irradiance gather"; q its QueryState.
 //
 // The scene is there and its derived records are made (prepare_scene, as a compute() would); lights: the kind samples the
 // lights.  Touches nothing of the renderer's frame state.
@@ -815,17 +817,17 @@ int query_totals(rt_ctx* c, const QueryState& q, bool launched, uint64_t sum[6],
   }
   return RT_OK;
 }
-// The host entries: n > 0 rays up to the query's staging array, launch(d_rays, d_out) enqueues the kind's kernel, n results
-// of out_stride bytes come back; the stream is idle on return.
-template <class Launch>
-int query_from_host(rt_ctx* c, QueryState& q, const char* what, const rt_ray* rays, uint32_t n, void* out, size_t out_stride,
+// The host entries: n > 0 records (rt_ray, rt_gather_point) up to the query's staging array, launch(d_rays, d_out) enqueues
+// the kind's kernel, n results of out_stride bytes come back; the stream is idle on return.
+template <class Record, class Launch>
+int query_from_host(rt_ctx* c, QueryState& q, const char* what, const Record* rays, uint32_t n, void* out, size_t out_stride,
                     Launch launch) {
   if (!rays || !out) return fail(c, RT_ERR_INVALID, std::string(what) + ": NULL array");
   HIP_TRY(c, hipSetDevice(c->device));
   int r;
-  if ((r = ensure_buffer(c, q.in, (size_t)n * sizeof(rt_ray), true)) < 0) return r;
+  if ((r = ensure_buffer(c, q.in, (size_t)n * sizeof(Record), true)) < 0) return r;
   if ((r = ensure_buffer(c, q.out, (size_t)n * out_stride, true)) < 0) return r;
-  HIP_TRY(c, hipMemcpyAsync(q.in.ptr, rays, (size_t)n * sizeof(rt_ray), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(q.in.ptr, rays, (size_t)n * sizeof(Record), hipMemcpyHostToDevice, c->stream));
   if ((r = launch((const void*)q.in.ptr, q.out.ptr)) < 0) return r;
   HIP_TRY(c, hipMemcpyAsync(out, q.out.ptr, (size_t)n * out_stride, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -937,6 +939,7 @@ void rt_destroy(rt_ctx* c) {
                          &c->g_normal, &c->g_depth, &c->history[0], &c->history[1], &c->counters, &c->ticket,
                          &c->slots, &c->gbuf_batch, &c->frame_col, &c->wf_state, &c->wf_queues, &c->wf_counters,
                          &c->rq.in, &c->rq.out, &c->rq.counters, &c->rd.in, &c->rd.out, &c->rd.counters,
+                         &c->gi.in, &c->gi.out, &c->gi.counters,
                          &c->tex_staging, &c->bv_in, &c->bv_tri, &c->bv_order, &c->bv_nodes, &c->bv_out,
                          &c->bv_counters, &c->bv_big, &c->val_roots, &c->val_bad, &c->tnodes, &c->node_key, &c->node_newidx,
                          &c->inst_root, &c->root_w, &c->treelet_work, &c->pairs, &c->pair_of, &c->pair_parent, &c->root_rec,
@@ -945,7 +948,7 @@ void rt_destroy(rt_ctx* c) {
                          &c->world.static_nodes};
   for (DeviceBuffer* b : all) free_buffer(*b);
   if (c->world.pinned) (void)hipHostFree(c->world.pinned);
-  for (QueryState* q : {&c->rq, &c->rd})
+  for (QueryState* q : {&c->rq, &c->rd, &c->gi})
     for (hipEvent_t e : q->ev)
       if (e) (void)hipEventDestroy(e);
   if (c->world.ev0) (void)hipEventDestroy(c->world.ev0);
@@ -2314,6 +2317,104 @@ int rt_trace_radiance(rt_ctx* c, const rt_ray* rays, uint32_t n, uint32_t max_de
   });
   if (r < 0) return r;
   if (stats) return rt_radiance_query_stats(c, stats);
+  return RT_OK;
+}
+
+// ---- irradiance gathers: k_irradiance_gather by [detail][lds]
+static const void* const gi_fns[2][2] = {
+    {(const void*)rtk::k_irradiance_gather<false, false>, (const void*)rtk::k_irradiance_gather<false, true>},
+    {(const void*)rtk::k_irradiance_gather<true, false>, (const void*)rtk::k_irradiance_gather<true, true>}};
+
+// Enqueue one gather on the context's stream: n > 0 points at d_points, results to d_out (device pointers).
+static int launch_irradiance_gather(rt_ctx* c, const void* d_points, uint32_t n, uint32_t max_depth, uint32_t spp, uint32_t seed,
+                                    void* d_out, bool detail) {
+  int r = query_scene_ready(c, "irradiance gather", true);
+  if (r < 0) return r;
+  // the forms of the radiance query
+  const bool lds = scene_fits_lds(c);
+  size_t dyn;
+  rtk::LdsPlan plan = persistent_plan(c, lds, &dyn);
+  const void* fn = gi_fns[detail][lds];
+  int per_cu;
+  if ((r = resident_blocks(c, fn, 256, dyn, &per_cu)) < 0) return r;
+  const uint32_t blocks = grid_blocks(c, per_cu, 0, (n + 255u) / 256u);
+  if (getenv("MI355RT_DEBUG_SHAPE"))
+    fprintf(stderr, "[mi355rt] irradiance gather: %s form, %zu bytes of LDS, resident workgroups per CU %d, %u workgroups\n",
+            lds ? "LDS" : "global", dyn, per_cu, blocks);
+  rtk::GatherArgs A;
+  if ((r = query_reset_counters(c, c->gi, &A.counters, &A.head)) < 0) return r;
+  A.points = (const float4*)d_points;
+  A.out = (float4*)d_out;
+  A.n_points = n;
+  A.max_depth = max_depth;
+  A.spp = spp;
+  A.seed = seed;
+  A.light_count = c->light_count;
+  A.blas_base = c->blas_offset;
+  A.n_nodes = c->n_nodes;
+  A.n_tris = c->n_tris;
+  A.n_inst = c->n_instances;
+  A.n_verts = c->n_verts;
+  DevScene S = dev_scene(c);
+  void* args[] = {&S, &A, &plan};
+  if ((r = query_launch(c, c->gi, fn, blocks, args, dyn)) < 0) return r;
+  c->gi_last = rt_radiance_stats();
+  c->gi_last.rays = n;
+  c->gi_last.samples = (uint64_t)n * spp;
+  c->gi_last.lds = lds ? 1u : 0u;
+  c->gi_last.workgroups = blocks;
+  return RT_OK;
+}
+
+static int irradiance_gather_args_ok(rt_ctx* c, uint32_t n, uint32_t spp) {
+  if (n >= (1u << 31)) return fail(c, RT_ERR_INVALID, "irradiance gather: too many points for one call (n must be below 2^31)");
+  if (spp == 0 || spp > 65536) return fail(c, RT_ERR_INVALID, "irradiance gather: spp must be 1 .. 65536");
+  return RT_OK;
+}
+
+int rt_irradiance_gather_stats(rt_ctx* c, rt_radiance_stats* out) {
+  if (!c || !out) return RT_ERR_INVALID;
+  HIP_TRY(c, hipSetDevice(c->device));
+  *out = c->gi_last;
+  uint64_t sum[6];
+  const int r = query_totals(c, c->gi, c->gi_last.workgroups != 0, sum, &out->kernel_ms);
+  if (r < 0) return r;
+  out->extension_rays += sum[1];
+  out->shadow_rays += sum[2];
+  out->nodes_visited += sum[3];
+  out->tris_tested += sum[4];
+  out->shaded_hits += sum[5];
+  return RT_OK;
+}
+
+int rt_gather_irradiance_device(rt_ctx* c, const void* dev_points, uint32_t n, uint32_t max_depth, uint32_t spp, uint32_t seed,
+                                void* dev_out) {
+  if (!c) return RT_ERR_INVALID;
+  int r = irradiance_gather_args_ok(c, n, spp);
+  if (r < 0) return r;
+  if (n == 0) {
+    c->gi_last = rt_radiance_stats();
+    return RT_OK;
+  }
+  if ((r = query_device_arrays_ok(c, "irradiance gather", dev_points, dev_out)) < 0) return r;
+  return launch_irradiance_gather(c, dev_points, n, max_depth, spp, seed, dev_out, c->detailed_counters);
+}
+
+int rt_gather_irradiance(rt_ctx* c, const rt_gather_point* points, uint32_t n, uint32_t max_depth, uint32_t spp, uint32_t seed,
+                         rt_irradiance* out, rt_radiance_stats* stats) {
+  if (!c) return RT_ERR_INVALID;
+  int r = irradiance_gather_args_ok(c, n, spp);
+  if (r < 0) return r;
+  if (n == 0) {
+    c->gi_last = rt_radiance_stats();
+    if (stats) *stats = c->gi_last;
+    return RT_OK;
+  }
+  r = query_from_host(c, c->gi, "irradiance gather", points, n, out, sizeof(rt_irradiance), [&](const void* d_points, void* d_out) {
+    return launch_irradiance_gather(c, d_points, n, max_depth, spp, seed, d_out, stats != nullptr);
+  });
+  if (r < 0) return r;
+  if (stats) return rt_irradiance_gather_stats(c, stats);
   return RT_OK;
 }
 

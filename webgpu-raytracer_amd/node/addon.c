@@ -616,6 +616,28 @@ static napi_value rtTraceRadiance(napi_env env, napi_callback_info info) {
   return radiance_stats_object(env, &st);
 }
 
+/* ------------------------------------------------------- irradiance gathers (rt_gather_irradiance, mi355rt.h) */
+/* (ctx, points: Float32Array of 8 per point {position, t_max, normal, pad}, maxDepth, spp, seed, out: Float32Array of 4 per
+ * point, wantStats) -> status, or the stats object when wantStats and the call succeeded */
+static napi_value rtGatherIrradiance(napi_env env, napi_callback_info info) {
+  napi_value a[7];
+  void *points = NULL, *out = NULL;
+  size_t np = 0, no = 0;
+  bool want_stats = false;
+  if (!get_args(env, info, 7, a) || !get_bytes(env, a[1], &points, &np) || !get_bytes(env, a[5], &out, &no)) return NULL;
+  napi_get_value_bool(env, a[6], &want_stats);
+  const size_t n = np / sizeof(rt_gather_point);
+  if (np % sizeof(rt_gather_point) != 0 || no < n * sizeof(rt_irradiance) || n > 0x7fffffffu) {
+    napi_throw_range_error(env, NULL, "rtGatherIrradiance: points must hold 8 floats per point and out 4 floats per point");
+    return NULL;
+  }
+  rt_radiance_stats st;
+  const int rc = rt_gather_irradiance((rt_ctx*)get_ptr(env, a[0]), (const rt_gather_point*)points, (uint32_t)n, get_u32(env, a[2]),
+                                      get_u32(env, a[3]), get_u32(env, a[4]), (rt_irradiance*)out, want_stats ? &st : NULL);
+  if (rc < 0 || !want_stats) return make_int(env, rc);
+  return radiance_stats_object(env, &st);
+}
+
 static napi_value Init(napi_env env, napi_value exports) {
   static const struct {
     const char* name;
@@ -632,7 +654,8 @@ static napi_value Init(napi_env env, napi_value exports) {
                {"rtDistBlockBytes", rtDistBlockBytes}, {"rtPackStripes", rtPackStripes}, {"rtDistReadBlock", rtDistReadBlock},
                {"rtDistWriteBlock", rtDistWriteBlock}, {"rtUnpackStripes", rtUnpackStripes},
                {"rtGatherStripes", rtGatherStripes}, {"rtReadDisplay", rtReadDisplay}, {"rtTraceRays", rtTraceRays},
-               {"rtRayQueryStats", rtRayQueryStats}, {"rtTraceRadiance", rtTraceRadiance}, {"msCreate", msCreate}, {"msDestroy", msDestroy},
+               {"rtRayQueryStats", rtRayQueryStats}, {"rtTraceRadiance", rtTraceRadiance},
+               {"rtGatherIrradiance", rtGatherIrradiance}, {"msCreate", msCreate}, {"msDestroy", msDestroy},
                {"msUpdate", msUpdate}, {"msUpdateCamera", msUpdateCamera}, {"msGet", msGet},
                {"msTextureCount", msTextureCount}, {"msTexture", msTexture},
                {"msAnimationNames", msAnimationNames}, {"msSetAnimation", msSetAnimation},

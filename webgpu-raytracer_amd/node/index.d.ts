@@ -59,6 +59,12 @@ export class WebGPURenderer {
    *  {0, 0, 0, the ray's tMax}. */
   traceRadiance(rays: Float32Array, maxDepth: number, spp: number, opts?: { seed?: number; stats?: boolean }):
     { data: Float32Array; n: number; stats?: RadianceQueryStats };
+  /** Irradiance gathers at the caller's surface points (rt_gather_irradiance): 8 words per point {position, tMax, normal, pad},
+   *  pad = the bits of a uint32 below 2^31, the point's RNG stream id.  `data` holds 4 floats per point {r, g, b, hitFraction}:
+   *  the cosine-weighted mean incoming radiance (E / pi) over spp directions drawn on the device, and the fraction of them
+   *  that hit something within tMax.  The stats are a radiance query's with rays = points. */
+  gatherIrradiance(points: Float32Array, maxDepth: number, spp: number, opts?: { seed?: number; stats?: boolean }):
+    { data: Float32Array; n: number; stats?: RadianceQueryStats };
   destroy(): void;
 }
 export class WorldBridge {

@@ -187,6 +187,21 @@ class WebGPURenderer {
     if (typeof r === 'object' && r) out.stats = r;
     return out;
   }
+  // ---- irradiance gathers (rt_gather_irradiance): the cosine-weighted mean radiance arriving at the caller's surface
+  // points, over spp hemisphere directions drawn on the device.  points = 8 words per point {position, tMax, normal, pad}; pad
+  // holds the bits of a uint32 below 2^31, the point's RNG stream id.  opts: {seed = 0, stats = false}.  Result: 4 floats per
+  // point {r, g, b, hitFraction} in .data (rgb is E / pi: multiply by pi for irradiance).  With stats the result also
+  // carries .stats.
+  gatherIrradiance(points, maxDepth, spp, opts = {}) {
+    if (!(points instanceof Float32Array) || points.length % 8 !== 0) throw new TypeError('gatherIrradiance: a Float32Array of 8 floats per point');
+    const n = points.length / 8;
+    const data = new Float32Array(n * 4);
+    const r = native.rtGatherIrradiance(this._ctx, points, maxDepth >>> 0, spp >>> 0, (opts.seed || 0) >>> 0, data, !!opts.stats);
+    if (typeof r === 'number') this._check(r, 'gatherIrradiance');
+    const out = { data, n };
+    if (typeof r === 'object' && r) out.stats = r;
+    return out;
+  }
   destroy() { if (this._ctx) { native.rtDestroy(this._ctx); this._ctx = null; } }
 }
 

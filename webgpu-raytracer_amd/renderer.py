@@ -193,6 +193,10 @@ def load_library(path=None):
         "rt_trace_radiance": (i32, [vp, vp, u32, u32, u32, u32, vp, vp]),
         "rt_trace_radiance_device": (i32, [vp, vp, u32, u32, u32, u32, vp]),
         "rt_radiance_query_stats": (i32, [vp, vp]),
+        # irradiance gathers
+        "rt_gather_irradiance": (i32, [vp, vp, u32, u32, u32, u32, vp, vp]),
+        "rt_gather_irradiance_device": (i32, [vp, vp, u32, u32, u32, u32, vp]),
+        "rt_irradiance_gather_stats": (i32, [vp, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(L, name)  # AttributeError here = header/library mismatch
@@ -215,7 +219,8 @@ EXPORTED_SYMBOLS = (
     "rt_dist_unique_id rt_dist_init rt_dist_shutdown rt_dist_block_bytes rt_pack_stripes rt_dist_read_block rt_dist_write_block "
     "rt_unpack_stripes rt_gather_stripes rt_read_display "
     "rt_trace_rays rt_trace_rays_device rt_ray_query_stats "
-    "rt_trace_radiance rt_trace_radiance_device rt_radiance_query_stats").split()
+    "rt_trace_radiance rt_trace_radiance_device rt_radiance_query_stats "
+    "rt_gather_irradiance rt_gather_irradiance_device rt_irradiance_gather_stats").split()
 
 
 # ---- ray queries: mirrors of rt_ray / rt_ray_hit / rt_ray_stats (include/mi355rt_layout.h)
@@ -254,6 +259,8 @@ class RtRadianceStats(ctypes.Structure):
 
 
 RADIANCE_DTYPE = np.dtype([("rgb", np.float32, (3,)), ("t", np.float32)])
+# irradiance gathers: mirror of rt_irradiance; their stats are an RtRadianceStats (rays = points)
+IRRADIANCE_DTYPE = np.dtype([("rgb", np.float32, (3,)), ("hit_fraction", np.float32)])
 
 
 def _ptr(a):
@@ -552,6 +559,36 @@ class WebGPURenderer:
         """rt_radiance_stats of the last radiance query as a dict (blocking)."""
         st = RtRadianceStats()
         self._check(self.L.rt_radiance_query_stats(self.ctx, ctypes.addressof(st)), "radianceQueryStats")
+        return st.as_dict()
+
+    # ---- irradiance gathers at surface points of the uploaded scene (rt_gather_irradiance) ----
+    def gatherIrradiance(self, points, max_depth, spp, seed=0, stats=False):
+        """points: (n, 8) float32 in the rt_gather_point layout {position, t_max, normal, pad}; pad holds the bits of a
+        uint32 below 2^31, the point's RNG stream id.  Returns a structured array (n,) with the fields rgb (3 floats) and
+        hit_fraction (IRRADIANCE_DTYPE): the cosine-weighted mean radiance arriving at each point over spp hemisphere
+        directions drawn on the device (E / pi: multiply by pi for irradiance) and the fraction of them that hit something
+        within t_max - and with stats=True the pair (results, stats dict of rt_radiance_stats with rays = points: the
+        counting kernel runs)."""
+        p = np.ascontiguousarray(points, dtype=np.float32)
+        if p.ndim != 2 or p.shape[1] != 8:
+            raise ValueError("gatherIrradiance expects an (n, 8) float32 array")
+        n = p.shape[0]
+        out = np.empty(n, dtype=IRRADIANCE_DTYPE)
+        st = RtRadianceStats()
+        self._check(self.L.rt_gather_irradiance(self.ctx, _ptr(p), n, int(max_depth), int(spp), int(seed) & 0xffffffff, _ptr(out),
+                                                ctypes.addressof(st) if stats else None), "gatherIrradiance")
+        return (out, st.as_dict()) if stats else out
+
+    def gatherIrradianceDevice(self, points_ptr, n, out_ptr, max_depth, spp, seed=0):
+        """Enqueue an irradiance gather on device arrays (n rt_gather_point at points_ptr, n rt_irradiance to out_ptr; e.g.
+        tensor.data_ptr()) on the context's stream; no host synchronisation."""
+        self._check(self.L.rt_gather_irradiance_device(self.ctx, ctypes.c_void_p(points_ptr), int(n), int(max_depth), int(spp),
+                                                       int(seed) & 0xffffffff, ctypes.c_void_p(out_ptr)), "gatherIrradianceDevice")
+
+    def irradianceGatherStats(self):
+        """rt_radiance_stats of the last irradiance gather as a dict (blocking)."""
+        st = RtRadianceStats()
+        self._check(self.L.rt_irradiance_gather_stats(self.ctx, ctypes.addressof(st)), "irradianceGatherStats")
         return st.as_dict()
 
     # ---- the sharded image (rt_dist_*): this context as one rank of `world` ----
