@@ -334,8 +334,9 @@ int rt_ray_query_stats(rt_ctx* ctx, rt_ray_stats* out);
 /* ---- radiance queries: "what radiance arrives along this ray?" (light probes, irradiance and lightmap bakes, reflection
  * captures, panorama / fisheye / orthographic cameras, renderers that make their own primary rays) ----
  * The renderer's shading - materials, textures, next-event estimation with MIS, Russian roulette: ray_color
- * (Raytracer.wgsl:607-783) - on rays the caller supplies, by the fourth driver of the path state machine
- * (k_radiance_query, csrc/k_radiance.hip.h).  For ray i (rt_ray) and sample s in 0 .. spp-1:
+ * (Raytracer.wgsl:607-783) - on rays the caller supplies, by the path-query loop over the path state machine
+ * (path_query_loop with the policy RadianceItem: k_radiance_query, csrc/k_radiance.hip.h).  For ray i (rt_ray) and sample s
+ * in 0 .. spp-1:
  *   rng     init_rng(rays[i].pad, seed * spp + s) in u32 arithmetic: `main`'s init_rng(pixel, frame_count * spp + sample)
  *           (:798-800) with both numbers chosen by the caller.  pad, which rt_trace_rays ignores, is the ray's RNG stream id.
  *   sample  ray_color with the depth-0 surface taken from the TRACED hit, exactly as at every later depth (:738-779): no
@@ -372,9 +373,9 @@ int rt_radiance_query_stats(rt_ctx* ctx, rt_radiance_stats* out);
  * occlusion) ----
  * A radiance query traces the same ray for all spp samples of an entry; an irradiance estimate needs another direction per
  * sample.  Here the work item is a surface point (rt_gather_point): the hemisphere directions are drawn on the device, the
- * renderer's path tracing runs behind them and only the per-point mean comes back, by the fifth driver of the path state
- * machine (k_irradiance_gather, csrc/k_gather.hip.h).  For point i and sample s in 0 .. spp-1, with f = seed * spp + s in
- * u32 arithmetic:
+ * renderer's path tracing runs behind them and only the per-point mean comes back, by the radiance query's loop with the
+ * policy GatherItem (k_irradiance_gather, csrc/k_gather.hip.h).  For point i and sample s in 0 .. spp-1, with f = seed * spp
+ * + s in u32 arithmetic:
  *   direction  the .dir of the reference's Lambert sampler (sample_diffuse, Raytracer.wgsl:228-233, 191-199: build_onb, phi =
  *              2 pi r1, cos(theta) = sqrt(1 - r2), sin(theta) = sqrt(r2), to_world) on n = normalize(points[i].normal), and
  *              nothing else of it; its two rand_pcg draws come from a direction stream of their own, init_rng(pad ^

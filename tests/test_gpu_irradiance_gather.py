@@ -3,7 +3,7 @@ gather_model.cpp, tied to the radiance model by tests/test_gather_model.py), poi
 the ray, hit, node and triangle counters as sums, in the LDS and the global-memory form; textures and transforms; the
 composition identity on the GPU's own radiance queries; independence of the point's place in the array; t_max, max_depth = 0;
 degenerate points; no side effect on a render; the device entry on a torch side stream; the device-resident animated world;
-the error returns."""
+the error returns; a radiance query and a gather on one context, each with its own state and last stats."""
 import ctypes
 
 import numpy as np
@@ -160,6 +160,39 @@ def test_results_do_not_depend_on_scheduling(W, monkeypatch, no_lds):
         twice = np.concatenate([points[:300], points[100:101], points[300:700], points[100:101]])
         res = gu.result_words(r.gatherIrradiance(twice, 4, 8, gu.SEED))
         assert np.array_equal(res[300], res[100]) and np.array_equal(res[701], res[100])
+    finally:
+        r.destroy()
+
+
+@pytest.mark.parametrize("no_lds,lds", [(None, 1), ("1", 0)])
+def test_the_two_kinds_of_path_query_keep_their_own_state(W, monkeypatch, no_lds, lds):
+    """One context, 130 items (two full chunks of 64 and a partial one), max_depth 4, spp 2: a radiance query and a gather
+    through the one host launch path, both counting.  Each equals its model; the radiance query's stats read AFTER the gather
+    are still the radiance query's and the gather's are the gather's (the kinds share neither a QueryState nor a last-stats
+    record); the radiance query run again, without counting, gives the same words."""
+    b, m, points = _scene(W, "cornell")
+    pts = points[:130]
+    rays = gu.sample_rays(pts, m.gatherDirections(pts, 1, gu.SEED), 0)      # a ray per point: its first gather direction
+    ref_r, counts_r = m.traceRadiance(rays, 4, 2, gu.SEED)
+    ref_g, _, counts_g = m.gatherIrradiance(pts, 4, 2, gu.SEED)
+    sums_r, sums_g = counts_r.sum(axis=0).tolist(), counts_g.sum(axis=0).tolist()
+    print("model counts", dict(zip(gu.COUNT_NAMES, sums_r)), dict(zip(gu.COUNT_NAMES, sums_g)))
+    assert all(a != c for a, c in zip(sums_r, sums_g)), "the two queries must not count alike: mixed-up stats would pass"
+    r = _renderer(W, monkeypatch, b, no_lds)
+    try:
+        res_r, st_r = r.traceRadiance(rays, 4, 2, gu.SEED, stats=True)
+        res_g, st_g = r.gatherIrradiance(pts, 4, 2, gu.SEED, stats=True)
+        after_r, after_g = r.radianceQueryStats(), r.irradianceGatherStats()
+        print("radiance", st_r, after_r)
+        print("gather", st_g, after_g)
+        ru.check_against_model(res_r, ref_r, "radiance query, no_lds=%s" % no_lds)
+        gu.check_against_model(res_g, ref_g, "gather, no_lds=%s" % no_lds)
+        for tag, st, counts in (("radiance query", st_r, counts_r), ("radiance query, read after the gather", after_r, counts_r),
+                                ("gather", st_g, counts_g), ("gather, read again", after_g, counts_g)):
+            gu.check_counts(st, counts, 130, 2, tag)
+            assert st["lds"] == lds and st["workgroups"] == 1, (tag, st)
+        again = r.traceRadiance(rays, 4, 2, gu.SEED)
+        assert np.array_equal(ru.result_words(again), ru.result_words(res_r)), "the second radiance query differs from the first"
     finally:
         r.destroy()
 

@@ -357,6 +357,40 @@ __host__ __device__ inline size_t scene_lds_slots(uint32_t n_nodes, uint32_t n_t
          (size_t)4 * n_lights;
 }
 
+// Stage exactly those slots, in that order, from slot rec0 of the workgroup's LDS on: M reads every traversal record from
+// LDS, and S (a copy of Sg on entry) gets the LDS addresses of the arrays shading reads.  The caller's __syncthreads()
+// follows.  (k_pathtrace_persistent keeps a register-tuned copy of this for its LEAN / ONE_INST forms.)
+__device__ __forceinline__ void stage_whole_scene(TravMem& M, DevScene& S, f4* s_scene, uint32_t rec0, const DevScene& Sg,
+                                                  uint32_t n_nodes, uint32_t n_tris, uint32_t n_inst, uint32_t n_verts) {
+  uint32_t slot = rec0;
+  auto stage = [&](const void* src, size_t n) {
+    f4* base = s_scene + slot;
+    lds_stage(base, src, n);
+    slot += (uint32_t)n;
+    return base;
+  };
+  M.gnodes = M.gtri = M.ginst = nullptr;
+  M.groot = nullptr;
+  M.k_lds = n_nodes;
+  M.t_min = RT_T_MIN;
+  M.l_nodes = slot;
+  S.tnodes = reinterpret_cast<const float4*>(stage(Sg.tnodes, (size_t)2 * n_nodes));
+  M.l_tri = slot;
+  S.tri_geom = reinterpret_cast<const float4*>(stage(Sg.tri_geom, (size_t)RT_TRI_STRIDE * n_tris));
+  M.l_inst = slot;
+  S.inst_trav = reinterpret_cast<const float4*>(stage(Sg.inst_trav, (size_t)4 * n_inst));
+  M.l_root = slot;
+  stage(Sg.inst_root, ((size_t)n_inst + 3) / 4);
+  S.tri_shade = reinterpret_cast<const float4*>(stage(Sg.tri_shade, (size_t)8 * n_tris));
+  S.topo = reinterpret_cast<const float4*>(stage(Sg.topo, (size_t)5 * n_tris));
+  S.pos = reinterpret_cast<const float4*>(stage(Sg.pos, n_verts));
+  // uv (8 B/vertex) and lights (8 B each): the device buffers are allocated with >= 16-byte slack
+  S.uv = reinterpret_cast<const float2*>(stage(Sg.uv, ((size_t)n_verts + 1) / 2));
+  S.inst = reinterpret_cast<const float4*>(stage(Sg.inst, (size_t)9 * n_inst));
+  S.lights = reinterpret_cast<const uint2*>(stage(Sg.lights, ((size_t)Sg.n_lights + 1) / 2));
+  S.light_rec = reinterpret_cast<const float4*>(stage(Sg.light_rec, (size_t)4 * Sg.n_lights));
+}
+
 // What the one-leaf forms (ONE_INST) really stage: no topo, pos, uv or inst, and two slots of world record per triangle
 // (k_prepare_world_tris).  The launch asks for this much; the host still chooses between the 256-thread and the wide form,
 // and decides whether a scene fits LDS at all, on scene_lds_slots, so that the scenes on either side of those lines stay

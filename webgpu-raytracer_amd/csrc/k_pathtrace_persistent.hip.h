@@ -42,6 +42,7 @@ __global__ __launch_bounds__(64 * RT_PT_WAVES, RT_PT_SIMD_WAVES) void RT_PT_KERN
   if (LDS) {
     // Small scene: the whole scene (traversal records AND the arrays shading reads) lives in LDS,
     // staged once per workgroup; only textures, the G-buffer and the accumulation buffer stay in HBM.
+    // (The non-ONE_INST layout is that of stage_whole_scene, k_pathtrace.hip.h: keep the two in step.)
     uint32_t slot = rec0;
     auto stage = [&](const void* src, size_t n) {
       f4* base = s_scene + slot;

@@ -16,9 +16,10 @@
 //                             shade_bounce, ...) and its drivers k_pathtrace (one pixel per lane), k_pathtrace_persistent
 //   k_wavefront.hip.h         the same bounce as shade / trace stages over device queues (large scenes)
 //   k_rayquery.hip.h          k_ray_query: the trace stage over a caller's flat ray array (rt_trace_rays)
-//   k_radiance.hip.h          k_radiance_query: the path state machine over a caller's flat ray array (rt_trace_radiance)
-//   k_gather.hip.h            k_irradiance_gather: the path state machine behind hemisphere directions drawn at a caller's
-//                             surface points (rt_gather_irradiance)
+//   k_radiance.hip.h          path_query_loop: the path state machine over a caller's flat item array, one persistent loop
+//                             with a policy per kind, and k_radiance_query: the items are rays (rt_trace_radiance)
+//   k_gather.hip.h            k_irradiance_gather: the same loop behind hemisphere directions drawn at a caller's surface
+//                             points (rt_gather_irradiance)
 //   k_texture_post.hip.h      k_resize_texture; k_postprocess = PostProcess.wgsl `main` (:103-176)
 //   k_validate.hip.h          k_validate_scene: every index the kernels follow, checked once per upload
 //   k_stripes.hip.h           k_pack_stripes / k_unpack_stripes: the copies of the sharded image's gather

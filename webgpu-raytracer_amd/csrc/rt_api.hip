@@ -2222,32 +2222,44 @@ int rt_trace_rays(rt_ctx* c, const rt_ray* rays, uint32_t n, int mode, float t_m
   return RT_OK;
 }
 
-// ---- radiance queries: k_radiance_query by [detail][lds]
-static const void* const rd_fns[2][2] = {
-    {(const void*)rtk::k_radiance_query<false, false>, (const void*)rtk::k_radiance_query<false, true>},
-    {(const void*)rtk::k_radiance_query<true, false>, (const void*)rtk::k_radiance_query<true, true>}};
+// ---- path queries: radiance queries and irradiance gathers (path_query_loop, k_radiance.hip.h).  What a kind has of its own:
+struct PathQueryKind {
+  const char* what;                   // prefix of its messages
+  const char* items;                  // what it calls its items
+  const void* fns[2][2];              // its kernel by [detail][lds]
+  QueryState rt_ctx::*state;
+  rt_radiance_stats rt_ctx::*last;
+  size_t out_stride;                  // bytes of one result
+};
+#define RT_PQ_FNS(K) {{(const void*)rtk::K<false, false>, (const void*)rtk::K<false, true>}, \
+                      {(const void*)rtk::K<true, false>, (const void*)rtk::K<true, true>}}
+static const PathQueryKind pq_radiance = {"radiance query", "rays", RT_PQ_FNS(k_radiance_query), &rt_ctx::rd, &rt_ctx::rd_last,
+                                          sizeof(rt_radiance)};
+static const PathQueryKind pq_gather = {"irradiance gather", "points", RT_PQ_FNS(k_irradiance_gather), &rt_ctx::gi, &rt_ctx::gi_last,
+                                        sizeof(rt_irradiance)};
+#undef RT_PQ_FNS
 
-// Enqueue one query on the context's stream: n > 0 rays at d_rays, results to d_out (device pointers).
-static int launch_radiance_query(rt_ctx* c, const void* d_rays, uint32_t n, uint32_t max_depth, uint32_t spp, uint32_t seed,
-                                 void* d_out, bool detail) {
-  int r = query_scene_ready(c, "radiance query", true);
+// Enqueue one query on the context's stream: n > 0 items at d_items, results to d_out (device pointers).
+static int launch_path_query(rt_ctx* c, const PathQueryKind& k, const void* d_items, uint32_t n, uint32_t max_depth, uint32_t spp,
+                             uint32_t seed, void* d_out, bool detail) {
+  int r = query_scene_ready(c, k.what, true);
   if (r < 0) return r;
   // the persistent kernel's 256-thread forms without the one-leaf one
   const bool lds = scene_fits_lds(c);
   size_t dyn;
   rtk::LdsPlan plan = persistent_plan(c, lds, &dyn);
-  const void* fn = rd_fns[detail][lds];
+  const void* fn = k.fns[detail][lds];
   int per_cu;
   if ((r = resident_blocks(c, fn, 256, dyn, &per_cu)) < 0) return r;
   const uint32_t blocks = grid_blocks(c, per_cu, 0, (n + 255u) / 256u);
   if (getenv("MI355RT_DEBUG_SHAPE"))
-    fprintf(stderr, "[mi355rt] radiance query: %s form, %zu bytes of LDS, resident workgroups per CU %d, %u workgroups\n",
+    fprintf(stderr, "[mi355rt] %s: %s form, %zu bytes of LDS, resident workgroups per CU %d, %u workgroups\n", k.what,
             lds ? "LDS" : "global", dyn, per_cu, blocks);
-  rtk::RadianceArgs A;
-  if ((r = query_reset_counters(c, c->rd, &A.counters, &A.head)) < 0) return r;
-  A.rays = (const float4*)d_rays;
+  rtk::PathQueryArgs A;
+  if ((r = query_reset_counters(c, c->*k.state, &A.counters, &A.head)) < 0) return r;
+  A.items = (const float4*)d_items;
   A.out = (float4*)d_out;
-  A.n_rays = n;
+  A.n_items = n;
   A.max_depth = max_depth;
   A.spp = spp;
   A.seed = seed;
@@ -2259,27 +2271,29 @@ static int launch_radiance_query(rt_ctx* c, const void* d_rays, uint32_t n, uint
   A.n_verts = c->n_verts;
   DevScene S = dev_scene(c);
   void* args[] = {&S, &A, &plan};
-  if ((r = query_launch(c, c->rd, fn, blocks, args, dyn)) < 0) return r;
-  c->rd_last = rt_radiance_stats();
-  c->rd_last.rays = n;
-  c->rd_last.samples = (uint64_t)n * spp;
-  c->rd_last.lds = lds ? 1u : 0u;
-  c->rd_last.workgroups = blocks;
+  if ((r = query_launch(c, c->*k.state, fn, blocks, args, dyn)) < 0) return r;
+  rt_radiance_stats& last = c->*k.last;
+  last = rt_radiance_stats();
+  last.rays = n;
+  last.samples = (uint64_t)n * spp;
+  last.lds = lds ? 1u : 0u;
+  last.workgroups = blocks;
   return RT_OK;
 }
 
-static int radiance_query_args_ok(rt_ctx* c, uint32_t n, uint32_t spp) {
-  if (n >= (1u << 31)) return fail(c, RT_ERR_INVALID, "radiance query: too many rays for one call (n must be below 2^31)");
-  if (spp == 0 || spp > 65536) return fail(c, RT_ERR_INVALID, "radiance query: spp must be 1 .. 65536");
+static int path_query_args_ok(rt_ctx* c, const PathQueryKind& k, uint32_t n, uint32_t spp) {
+  const std::string w(k.what);
+  if (n >= (1u << 31)) return fail(c, RT_ERR_INVALID, w + ": too many " + k.items + " for one call (n must be below 2^31)");
+  if (spp == 0 || spp > 65536) return fail(c, RT_ERR_INVALID, w + ": spp must be 1 .. 65536");
   return RT_OK;
 }
 
-int rt_radiance_query_stats(rt_ctx* c, rt_radiance_stats* out) {
+static int path_query_stats(rt_ctx* c, const PathQueryKind& k, rt_radiance_stats* out) {
   if (!c || !out) return RT_ERR_INVALID;
   HIP_TRY(c, hipSetDevice(c->device));
-  *out = c->rd_last;
+  *out = c->*k.last;
   uint64_t sum[6];
-  const int r = query_totals(c, c->rd, c->rd_last.workgroups != 0, sum, &out->kernel_ms);
+  const int r = query_totals(c, c->*k.state, out->workgroups != 0, sum, &out->kernel_ms);
   if (r < 0) return r;
   out->extension_rays += sum[1];
   out->shadow_rays += sum[2];
@@ -2289,133 +2303,56 @@ int rt_radiance_query_stats(rt_ctx* c, rt_radiance_stats* out) {
   return RT_OK;
 }
 
+static int path_query_device(rt_ctx* c, const PathQueryKind& k, const void* dev_items, uint32_t n, uint32_t max_depth, uint32_t spp,
+                             uint32_t seed, void* dev_out) {
+  if (!c) return RT_ERR_INVALID;
+  int r = path_query_args_ok(c, k, n, spp);
+  if (r < 0) return r;
+  if (n == 0) {
+    c->*k.last = rt_radiance_stats();
+    return RT_OK;
+  }
+  if ((r = query_device_arrays_ok(c, k.what, dev_items, dev_out)) < 0) return r;
+  return launch_path_query(c, k, dev_items, n, max_depth, spp, seed, dev_out, c->detailed_counters);
+}
+
+// items: rt_ray or rt_gather_point, the same 32 bytes
+static int path_query_host(rt_ctx* c, const PathQueryKind& k, const rt_ray* items, uint32_t n, uint32_t max_depth, uint32_t spp,
+                           uint32_t seed, void* out, rt_radiance_stats* stats) {
+  if (!c) return RT_ERR_INVALID;
+  int r = path_query_args_ok(c, k, n, spp);
+  if (r < 0) return r;
+  if (n == 0) {
+    c->*k.last = rt_radiance_stats();
+    if (stats) *stats = c->*k.last;
+    return RT_OK;
+  }
+  r = query_from_host(c, c->*k.state, k.what, items, n, out, k.out_stride, [&](const void* d_items, void* d_out) {
+    return launch_path_query(c, k, d_items, n, max_depth, spp, seed, d_out, stats != nullptr);
+  });
+  if (r < 0) return r;
+  if (stats) return path_query_stats(c, k, stats);
+  return RT_OK;
+}
+
+int rt_radiance_query_stats(rt_ctx* c, rt_radiance_stats* out) { return path_query_stats(c, pq_radiance, out); }
 int rt_trace_radiance_device(rt_ctx* c, const void* dev_rays, uint32_t n, uint32_t max_depth, uint32_t spp, uint32_t seed,
                              void* dev_out) {
-  if (!c) return RT_ERR_INVALID;
-  int r = radiance_query_args_ok(c, n, spp);
-  if (r < 0) return r;
-  if (n == 0) {
-    c->rd_last = rt_radiance_stats();
-    return RT_OK;
-  }
-  if ((r = query_device_arrays_ok(c, "radiance query", dev_rays, dev_out)) < 0) return r;
-  return launch_radiance_query(c, dev_rays, n, max_depth, spp, seed, dev_out, c->detailed_counters);
+  return path_query_device(c, pq_radiance, dev_rays, n, max_depth, spp, seed, dev_out);
 }
-
 int rt_trace_radiance(rt_ctx* c, const rt_ray* rays, uint32_t n, uint32_t max_depth, uint32_t spp, uint32_t seed,
                       rt_radiance* out, rt_radiance_stats* stats) {
-  if (!c) return RT_ERR_INVALID;
-  int r = radiance_query_args_ok(c, n, spp);
-  if (r < 0) return r;
-  if (n == 0) {
-    c->rd_last = rt_radiance_stats();
-    if (stats) *stats = c->rd_last;
-    return RT_OK;
-  }
-  r = query_from_host(c, c->rd, "radiance query", rays, n, out, sizeof(rt_radiance), [&](const void* d_rays, void* d_out) {
-    return launch_radiance_query(c, d_rays, n, max_depth, spp, seed, d_out, stats != nullptr);
-  });
-  if (r < 0) return r;
-  if (stats) return rt_radiance_query_stats(c, stats);
-  return RT_OK;
+  return path_query_host(c, pq_radiance, rays, n, max_depth, spp, seed, out, stats);
 }
 
-// ---- irradiance gathers: k_irradiance_gather by [detail][lds]
-static const void* const gi_fns[2][2] = {
-    {(const void*)rtk::k_irradiance_gather<false, false>, (const void*)rtk::k_irradiance_gather<false, true>},
-    {(const void*)rtk::k_irradiance_gather<true, false>, (const void*)rtk::k_irradiance_gather<true, true>}};
-
-// Enqueue one gather on the context's stream: n > 0 points at d_points, results to d_out (device pointers).
-static int launch_irradiance_gather(rt_ctx* c, const void* d_points, uint32_t n, uint32_t max_depth, uint32_t spp, uint32_t seed,
-                                    void* d_out, bool detail) {
-  int r = query_scene_ready(c, "irradiance gather", true);
-  if (r < 0) return r;
-  // the forms of the radiance query
-  const bool lds = scene_fits_lds(c);
-  size_t dyn;
-  rtk::LdsPlan plan = persistent_plan(c, lds, &dyn);
-  const void* fn = gi_fns[detail][lds];
-  int per_cu;
-  if ((r = resident_blocks(c, fn, 256, dyn, &per_cu)) < 0) return r;
-  const uint32_t blocks = grid_blocks(c, per_cu, 0, (n + 255u) / 256u);
-  if (getenv("MI355RT_DEBUG_SHAPE"))
-    fprintf(stderr, "[mi355rt] irradiance gather: %s form, %zu bytes of LDS, resident workgroups per CU %d, %u workgroups\n",
-            lds ? "LDS" : "global", dyn, per_cu, blocks);
-  rtk::GatherArgs A;
-  if ((r = query_reset_counters(c, c->gi, &A.counters, &A.head)) < 0) return r;
-  A.points = (const float4*)d_points;
-  A.out = (float4*)d_out;
-  A.n_points = n;
-  A.max_depth = max_depth;
-  A.spp = spp;
-  A.seed = seed;
-  A.light_count = c->light_count;
-  A.blas_base = c->blas_offset;
-  A.n_nodes = c->n_nodes;
-  A.n_tris = c->n_tris;
-  A.n_inst = c->n_instances;
-  A.n_verts = c->n_verts;
-  DevScene S = dev_scene(c);
-  void* args[] = {&S, &A, &plan};
-  if ((r = query_launch(c, c->gi, fn, blocks, args, dyn)) < 0) return r;
-  c->gi_last = rt_radiance_stats();
-  c->gi_last.rays = n;
-  c->gi_last.samples = (uint64_t)n * spp;
-  c->gi_last.lds = lds ? 1u : 0u;
-  c->gi_last.workgroups = blocks;
-  return RT_OK;
-}
-
-static int irradiance_gather_args_ok(rt_ctx* c, uint32_t n, uint32_t spp) {
-  if (n >= (1u << 31)) return fail(c, RT_ERR_INVALID, "irradiance gather: too many points for one call (n must be below 2^31)");
-  if (spp == 0 || spp > 65536) return fail(c, RT_ERR_INVALID, "irradiance gather: spp must be 1 .. 65536");
-  return RT_OK;
-}
-
-int rt_irradiance_gather_stats(rt_ctx* c, rt_radiance_stats* out) {
-  if (!c || !out) return RT_ERR_INVALID;
-  HIP_TRY(c, hipSetDevice(c->device));
-  *out = c->gi_last;
-  uint64_t sum[6];
-  const int r = query_totals(c, c->gi, c->gi_last.workgroups != 0, sum, &out->kernel_ms);
-  if (r < 0) return r;
-  out->extension_rays += sum[1];
-  out->shadow_rays += sum[2];
-  out->nodes_visited += sum[3];
-  out->tris_tested += sum[4];
-  out->shaded_hits += sum[5];
-  return RT_OK;
-}
-
+int rt_irradiance_gather_stats(rt_ctx* c, rt_radiance_stats* out) { return path_query_stats(c, pq_gather, out); }
 int rt_gather_irradiance_device(rt_ctx* c, const void* dev_points, uint32_t n, uint32_t max_depth, uint32_t spp, uint32_t seed,
                                 void* dev_out) {
-  if (!c) return RT_ERR_INVALID;
-  int r = irradiance_gather_args_ok(c, n, spp);
-  if (r < 0) return r;
-  if (n == 0) {
-    c->gi_last = rt_radiance_stats();
-    return RT_OK;
-  }
-  if ((r = query_device_arrays_ok(c, "irradiance gather", dev_points, dev_out)) < 0) return r;
-  return launch_irradiance_gather(c, dev_points, n, max_depth, spp, seed, dev_out, c->detailed_counters);
+  return path_query_device(c, pq_gather, dev_points, n, max_depth, spp, seed, dev_out);
 }
-
 int rt_gather_irradiance(rt_ctx* c, const rt_gather_point* points, uint32_t n, uint32_t max_depth, uint32_t spp, uint32_t seed,
                          rt_irradiance* out, rt_radiance_stats* stats) {
-  if (!c) return RT_ERR_INVALID;
-  int r = irradiance_gather_args_ok(c, n, spp);
-  if (r < 0) return r;
-  if (n == 0) {
-    c->gi_last = rt_radiance_stats();
-    if (stats) *stats = c->gi_last;
-    return RT_OK;
-  }
-  r = query_from_host(c, c->gi, "irradiance gather", points, n, out, sizeof(rt_irradiance), [&](const void* d_points, void* d_out) {
-    return launch_irradiance_gather(c, d_points, n, max_depth, spp, seed, d_out, stats != nullptr);
-  });
-  if (r < 0) return r;
-  if (stats) return rt_irradiance_gather_stats(c, stats);
-  return RT_OK;
+  return path_query_host(c, pq_gather, reinterpret_cast<const rt_ray*>(points), n, max_depth, spp, seed, out, stats);
 }
 
 // compute() for n consecutive frame counts in ONE dispatch of each kernel (n == 1: the plain compute()).
