@@ -38,12 +38,7 @@
 #include "../../include/mi355rt_layout.h"
 #include "k_ieee.hip.h"   // before the math header: the device build's correctly rounded rcp / div / sqrt sequences
 #include "../../include/mi355rt_math.h"
-
-// 16-byte slots per triangle record.  4 (one aligned 64-byte line per triangle; a 48-byte record straddles two lines
-// 37 % of the time) was measured: no gain on any scene, 33 % more memory
-#ifndef RT_TRI_STRIDE
-#define RT_TRI_STRIDE 3
-#endif
+#include "lds_sizes.h"    // RT_TRI_STRIDE
 
 struct DevScene {
   const float4* nodes;      // 2 per node, TLAS ++ BLAS (bridge layout; the per-lane walks of the primary pass read it)

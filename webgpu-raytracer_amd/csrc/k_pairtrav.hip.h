@@ -8,28 +8,16 @@
 
 namespace rtk {
 
-#ifndef RT_PW_STACK_K
-#define RT_PW_STACK_K 7   // deferred right children a lane can hold (8 bytes each in LDS).  Fall-back rate measured on the
-                          // host model (tests/test_pairwalk_model.py, random rays): K = 8: 0.3 % of the rays of the 263 k-
-                          // triangle scene leave the stack, +0.5 % record fetches; K = 6: 2.7 %, +3 %; K = 4: 14 %, +15 %
-#endif
+// (RT_PW_STACK_K, the deferred right children a lane can hold, and the wave's RT_PW_BYTES_PER_WAVE: lds_sizes.h)
 #ifndef RT_PW_STEPS_PER_TRIP
 #define RT_PW_STEPS_PER_TRIP 2   // record fetches (= two node tests each) between two looks at the triangle queue
 #endif
-#define RT_PW_STACK_BYTES_PER_WAVE (RT_PW_STACK_K * 64 * 8)
-#define RT_PW_BYTES_PER_WAVE (RT_WORK_BYTES_PER_WAVE + RT_PW_STACK_BYTES_PER_WAVE)
 
 typedef unsigned long long __attribute__((address_space(3))) * rt_lptr64;
 
 // Where the walk's records live.  Pair records: all of them in LDS (l_pairs set: small scenes) or all in global memory;
 // triangle records, instance rows and root records likewise, each on its own.  Slots are 16-byte units of the
-// workgroup's dynamic LDS array.
-struct TlasRoot {       // the TLAS root's box and word, by value in the kernel arguments (rt_api.hip fills it at upload)
-  float lo[3];
-  uint32_t word;
-  float hi[3];
-  uint32_t pad;
-};
+// workgroup's dynamic LDS array.  (TlasRoot: lds_sizes.h)
 struct PairMem {
   TlasRoot troot;
   const f4* gpairs;     // 4 per pair record
@@ -58,13 +46,8 @@ __device__ __forceinline__ LdsStack pw_stack_at(char* wave_base) {   // wave_bas
   return s;
 }
 
-// What a workgroup stages in LDS behind its wave blocks (decided on the host, rt_api.hip plan_pairs): each array whole or
-// not at all.
-struct PairPlan {
-  uint32_t stage_pairs, stage_inst, stage_tri, pad;
-  TlasRoot troot;
-};
-// Fill PairMem and stage what the plan names (all threads of the workgroup; the caller synchronises).
+// Fill PairMem and stage what the plan names (PairPlan, lds_sizes.h; decided on the host, launch_plan.h plan_pairs).  All
+// threads of the workgroup; the caller synchronises.
 __device__ __forceinline__ void pw_stage(PairMem& M, f4* lds, uint32_t slot0, const DevScene& Sg, const PairPlan& P, uint32_t n_pairs,
                                          uint32_t n_tris, uint32_t n_inst, float t_min) {
   uint32_t slot = slot0;

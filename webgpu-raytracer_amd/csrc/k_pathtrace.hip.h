@@ -347,19 +347,10 @@ __global__ __launch_bounds__(64) void k_pathtrace(DevScene S, DevFrame F, rt_sce
 
 // (the wave-level walk itself — TravMem, trav_step, tri_flush, traverse() — is in k_traverse.hip.h)
 
-// number of 16-byte LDS slots the whole scene needs (traversal records + shading arrays)
-__host__ __device__ inline size_t scene_lds_slots(uint32_t n_nodes, uint32_t n_tris, uint32_t n_inst, uint32_t n_verts,
-                                                  uint32_t n_lights) {
-  // tnodes, tri_geom, inst_trav, inst_root | tri_shade | topo, pos, uv (light_pdf / light sampling of emissive hits), inst,
-  // lights, light_rec
-  return (size_t)2 * n_nodes + (size_t)RT_TRI_STRIDE * n_tris + (size_t)4 * n_inst + ((size_t)n_inst + 3) / 4 + (size_t)8 * n_tris +
-         (size_t)5 * n_tris + (size_t)n_verts + ((size_t)n_verts + 1) / 2 + (size_t)9 * n_inst + ((size_t)n_lights + 1) / 2 +
-         (size_t)4 * n_lights;
-}
-
-// Stage exactly those slots, in that order, from slot rec0 of the workgroup's LDS on: M reads every traversal record from
-// LDS, and S (a copy of Sg on entry) gets the LDS addresses of the arrays shading reads.  The caller's __syncthreads()
-// follows.  (k_pathtrace_persistent keeps a register-tuned copy of this for its LEAN / ONE_INST forms.)
+// Stage the whole scene (traversal records + shading arrays), exactly the slots launch_plan.h scene_lds_slots counts, in its
+// order, from slot rec0 of the workgroup's LDS on: M reads every traversal record from LDS, and S (a copy of Sg on entry)
+// gets the LDS addresses of the arrays shading reads.  The caller's __syncthreads() follows.  (k_pathtrace_persistent keeps
+// a register-tuned copy of this for its LEAN / ONE_INST forms, which stage less: launch_plan.h one_leaf_lds_slots.)
 __device__ __forceinline__ void stage_whole_scene(TravMem& M, DevScene& S, f4* s_scene, uint32_t rec0, const DevScene& Sg,
                                                   uint32_t n_nodes, uint32_t n_tris, uint32_t n_inst, uint32_t n_verts) {
   uint32_t slot = rec0;
@@ -391,16 +382,6 @@ __device__ __forceinline__ void stage_whole_scene(TravMem& M, DevScene& S, f4* s
   S.light_rec = reinterpret_cast<const float4*>(stage(Sg.light_rec, (size_t)4 * Sg.n_lights));
 }
 
-// What the one-leaf forms (ONE_INST) really stage: no topo, pos, uv or inst, and two slots of world record per triangle
-// (k_prepare_world_tris).  The launch asks for this much; the host still chooses between the 256-thread and the wide form,
-// and decides whether a scene fits LDS at all, on scene_lds_slots, so that the scenes on either side of those lines stay
-// where they were measured.
-__host__ __device__ inline size_t one_leaf_lds_slots(uint32_t n_nodes, uint32_t n_tris, uint32_t n_inst, uint32_t n_lights) {
-  // tnodes, tri_geom, inst_trav, inst_root | tri_shade | tri_world | lights, light_rec
-  return (size_t)2 * n_nodes + (size_t)RT_TRI_STRIDE * n_tris + (size_t)4 * n_inst + ((size_t)n_inst + 3) / 4 + (size_t)8 * n_tris +
-         (size_t)2 * n_tris + ((size_t)n_lights + 1) / 2 + (size_t)4 * n_lights;
-}
-
 // Diagnostic build only (-DRT_CLOCK_STAMP, tools/clock_check.py): every workgroup of the persistent kernel stamps
 // s_memtime / s_memrealtime around its work loop into this array, which nothing else reads; the in-kernel clock is
 // delta(memtime) / delta(memrealtime) x 100 MHz.  In the product build no stamp executes.
@@ -413,14 +394,8 @@ __device__ unsigned long long g_pt_sections[8];
 
 // Occupancy: the LDS-resident form is VALU-issue bound (3, 4, 5 waves/SIMD within 2 %), the global-memory form
 // is latency bound and gains ~11 % from 6 waves/SIMD even with the spills that costs (measured on MI355X).
-// What a workgroup stages in LDS behind its wave queues (decided on the host from the scene's size, rt_api.hip plan_lds):
-// the first k_nodes records of tnodes, and — when they fit as a whole — the instance rows + BLAS roots and the triangle
-// records.  LDS = true (the whole scene fits, shading arrays included) ignores it.
-struct LdsPlan {
-  uint32_t k_nodes, stage_inst, stage_tri, pad;
-};
-
-// Fill TravMem for the mixed mode and stage what the plan names; returns the number of 16-byte slots used.
+// Fill TravMem for the mixed mode and stage what the plan names (LdsPlan, lds_sizes.h; decided on the host, launch_plan.h
+// plan_lds); returns the number of 16-byte slots used.
 __device__ __forceinline__ uint32_t trav_stage_mixed(TravMem& M, f4* lds, uint32_t slot0, const DevScene& Sg, const LdsPlan& P,
                                                      uint32_t n_tris_total, uint32_t n_inst_total) {
   uint32_t slot = slot0;
@@ -472,7 +447,6 @@ __device__ __forceinline__ uint32_t trav_stage_mixed(TravMem& M, f4* lds, uint32
 #ifndef RT_PT_WIDE_WAVES
 #define RT_PT_WIDE_WAVES 6     // waves per SIMD of the same form in 512-thread workgroups (80 VGPRs)
 #endif
-#define RT_PT_COL_BYTES_PER_WAVE (64 * 12)   // the wide form's parked sample sums (rt_api.hip sizes its LDS with it)
 // a wave-uniform value taken as new at this point: nothing computed from it is hoisted out of the loop it is used in
 __device__ __forceinline__ uint32_t rt_fresh(uint32_t v) {
   asm volatile("" : "+s"(v));
@@ -496,7 +470,7 @@ __device__ __forceinline__ DevFrame fresh_spp(const DevFrame& F) {
   return f;
 }
 // SLIM (k_pathtrace_persistent_wide): the lane's sample sum is parked in LDS behind the WAVES wave queues, in three planes
-// of WAVES * 64 floats (RT_PT_COL_BYTES_PER_WAVE per wave; rt_api.hip sizes the launch's LDS with it)
+// of WAVES * 64 floats (RT_PT_COL_BYTES_PER_WAVE per wave, lds_sizes.h; launch_plan.h sizes the launch's LDS with it)
 template <uint32_t WAVES>
 __device__ __forceinline__ float* col_park_at(f4* lds) {
   return reinterpret_cast<float*>(reinterpret_cast<char*>(lds) + WAVES * RT_WORK_BYTES_PER_WAVE) + threadIdx.x;

@@ -67,7 +67,7 @@ __global__ __launch_bounds__(64 * RT_PT_WAVES, RT_PT_SIMD_WAVES) void RT_PT_KERN
     S.tri_shade = reinterpret_cast<const float4*>(stage(Sg.tri_shade, (size_t)(ONE_INST ? 10 : 8) * n_tris_total));
     if constexpr (ONE_INST) {
       // topo, pos, uv and inst have no reader in these forms: light_pdf takes the world record, sample_light the shading
-      // record (one_leaf_lds_slots, k_pathtrace.hip.h)
+      // record (one_leaf_lds_slots, launch_plan.h)
       wrec = S.tri_shade + 8 * n_tris_total;
     } else {
       S.topo = reinterpret_cast<const float4*>(stage(Sg.topo, (size_t)5 * n_tris_total));

@@ -113,14 +113,9 @@ __global__ void k_prepare_instances(const float4* __restrict__ inst, float4* __r
 }
 
 // ================================================================ primary visibility
-// 16-byte LDS slots of the records this kernel reads (nodes, triangle records, instance rows, per-triangle shading records)
-__host__ __device__ inline size_t primary_lds_slots(uint32_t n_nodes, uint32_t n_tris, uint32_t n_inst, uint32_t /*n_verts*/) {
-  return (size_t)2 * n_nodes + (size_t)RT_TRI_STRIDE * n_tris + (size_t)4 * n_inst + (size_t)8 * n_tris;
-}
-
 // LDS = false: one wave (one 8x8 tile) per workgroup, records through L1 / L2.  LDS = true (small scenes): four tiles per
 // 256-thread workgroup and the records staged in LDS first — the walk is a chain of dependent fetches, and an LDS
-// fetch returns in a fraction of an L1 hit's time.
+// fetch returns in a fraction of an L1 hit's time.  The launch's dynamic LDS: launch_plan.h primary_lds_slots.
 template <bool DETAIL, bool LDS>
 __global__ __launch_bounds__(LDS ? 256 : 64) void k_primary_visibility(DevScene Sg, DevFrame F, rt_scene_uniforms U,
                                                                        const DevFrameSlot* __restrict__ slots, uint32_t n_tiles,

@@ -65,8 +65,8 @@ struct RayQueryIO {
   }
 };
 
-// FORM: the five forms of the 256-thread trace kernels (rt_api.hip picks as it does for k_wf_trace / k_wf_trace_pairs)
-enum { RT_RQ_NODE_LDS = 0, RT_RQ_NODE_MIXED = 1, RT_RQ_NODE_RAYREG = 2, RT_RQ_PAIR_LDS = 3, RT_RQ_PAIR_GLOBAL = 4 };
+// FORM: the five forms of the 256-thread trace kernels, RT_RQ_* of lds_sizes.h (launch_plan.h trace_shape picks as it does for
+// k_wf_trace / k_wf_trace_pairs)
 
 // Waves per SIMD asked of the compiler: those of the wavefront kernel of the same form — except the plain mixed node walk
 // without counting, where k_wf_trace comes out at 72 VGPRs (7 waves) under a bound of 6 and the per-ray t_max of a

@@ -35,7 +35,7 @@ __device__ __forceinline__ void lds_stage(f4* dst, const void* src, size_t slots
 }
 
 // Where the traversal records live.  `tnodes` (k_treelet.hip.h) has its first k_lds nodes staged in LDS at slot l_nodes
-// of the workgroup's dynamic LDS array (by default all of them or none, rt_api.hip plan_lds); the triangle records, the
+// of the workgroup's dynamic LDS array (by default all of them or none, launch_plan.h plan_lds); the triangle records, the
 // instance rows and the instance BLAS roots are staged as a whole when they fit (l_* != RT_LDS_NONE), else read through
 // L1 / L2.  Slots are 16-byte units.
 #define RT_LDS_NONE 0xffffffffu
@@ -145,7 +145,6 @@ struct WaveWork {
   uint32_t* items;           // up to 64*7: (owner lane << 26) | triangle id
   unsigned long long* res;   // 64: per owner lane, the smallest (bits(t) << 32 | triangle id) among its accepted tests
 };
-#define RT_WORK_BYTES_PER_WAVE (64 * 32 + 64 * 7 * 4 + 64 * 8)
 __device__ __forceinline__ void wave_work_at(WaveWork& W, char* wbase) {
   W.rays = reinterpret_cast<f4*>(wbase);
   W.items = reinterpret_cast<uint32_t*>(wbase + 64 * 32);

@@ -190,14 +190,12 @@ __global__ __launch_bounds__(256, RT_SHADE_WAVES) void k_wf_shade(DevScene S, De
 // instance} of the closest hit.  The path state is not touched here.  Ray-level regeneration: a lane whose ray is
 // finished writes its result and, when >= REFILL lanes are idle, the wave pulls the next rays of its chunk.
 // BLOCK threads per workgroup (256 / 512 / 1024; 256 x 6 per CU by default): a bigger workgroup shares one staged copy of
-// the records among more waves at the price of fewer waves per SIMD (LdsPlan, rt_api.hip plan_lds; measured without gain,
+// the records among more waves at the price of fewer waves per SIMD (LdsPlan, launch_plan.h plan_lds; measured without gain,
 // DESIGN.md 4.1b).  LDS = true: every traversal record fits (RT_TRAV_LDS).
 // Two walks, one trace loop (wf_trace_loop): k_wf_trace over single nodes (k_traverse.hip.h, the multi-instance scenes) and
 // k_wf_trace_pairs over child-pair records (k_pairwalk.hip.h / k_pairtrav.hip.h, the single-instance scenes); rt_api.hip
 // rt_set_walk / MI355RT_WALK picks.
-#ifndef RT_WF_WAVES
-#define RT_WF_WAVES 5   // waves per SIMD of the trace kernels: what the per-wave LDS block (work queue + stack, 8.3 KB at K = 8) leaves room for
-#endif
+// (RT_WF_WAVES, the waves per SIMD of the trace kernels: lds_sizes.h)
 #ifndef RT_WF_STEPS_PER_TRIP
 #define RT_WF_STEPS_PER_TRIP 4   // RECORD fetches (two node tests each) between two looks at the ray queue and the triangle queue.
                                  // Round 2, single-node steps: first sweep on

@@ -1,5 +1,6 @@
 // kernels.hip.h — hand-written gfx950 kernels of the path-tracing hot path.
 //
+//   lds_sizes.h               per-wave LDS blocks and the LdsPlan / PairPlan records, shared with the host's launch_plan.h
 //   k_common.hip.h            helpers, texture fetch, RNG
 //   k_intersect.hip.h         rays, slab / triangle tests, per-lane stackless walk
 //   k_shading.hip.h           surface frame, BSDFs, light sampling, counters
@@ -31,6 +32,7 @@
 #define MI355RT_KERNELS_HIP_H
 
 #include "device_scene.h"
+#include "lds_sizes.h"   // per-wave LDS blocks and the plan records, shared with the host's launch planner (launch_plan.h)
 
 #define RT_T_MIN 0.001f
 #define RT_T_MAX 1e30f

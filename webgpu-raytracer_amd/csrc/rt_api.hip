@@ -25,9 +25,12 @@
 
 #include "../../include/mi355rt.h"
 #include "kernels.hip.h"
+#include "launch_plan.h"
 #include "bvh_build.hip.h"
 #include "world_update.hip.h"
 #include "k_ieee_check.hip.h"
+
+namespace lp = launch_plan;
 
 namespace {
 
@@ -75,7 +78,6 @@ struct rt_ctx {
   int shade_per_cu = 8;          // workgroups per CU of the wavefront shade kernels (MI355RT_SHADE_BLOCKS_PER_CU); swept 4 / 8 /
                                  // 12 / 16 / 24, shade ms per image: sponza-like 64.6 / 63.9 / 63.9 / 64.3 / 64.7, instanced x1000
                                  // 35.9 / 36.4 / 36.7 / 37.4 / 38.7 (every wave may leave a partly used queue chunk per launch)
-  bool no_lds_staging = false;   // MI355RT_NO_LDS_STAGING=1 (test hook): every record through the global-memory paths
   std::string error;
 
   // scene buffers (raw bridge layout)
@@ -120,8 +122,6 @@ struct rt_ctx {
   bool world_rec_dirty = true;      // tri_world / tri_shade_w: set with tris_dirty, inst_dirty and nodes_dirty, cleared when
                                     // prepare_scene has rebuilt them (only for a scene that takes a one-leaf LDS form)
   bool pairs_wanted = false;        // rt_debug_read_pairs: build the pair records whatever walk is selected
-  int wf_block = 0;              // threads per workgroup of the wavefront trace kernels (0 = default; MI355RT_WF_BLOCK)
-  size_t lds_per_cu = 160 * 1024;
   bool validate_dirty = true, scene_valid = false;  // k_validate_scene: run once per upload
   std::string scene_problem;
   std::vector<uint32_t> blas_roots;                 // sorted unique BLAS-local root offsets of the instances
@@ -160,12 +160,7 @@ struct rt_ctx {
                           // 0 = one-pixel-per-lane megakernel, 1 = persistent kernel, 2 = wavefront
   int num_cus = 256;      // multiProcessorCount of the device
   std::vector<PreparedKernel> prepared;   // every kernel launched with dynamic LDS so far (resident_blocks)
-  int walk = 2;                  // traversal of the wavefront trace kernels: 1 = child-pair records, 0 = single nodes, 2 = auto
-                                 // (MI355RT_WALK): pairs for a scene of ONE instance (measured: the 263 k-triangle hall -9 % per
-                                 // batch; glass blob, 2 instances and short walks: +7 %; 1 001 instances of 8 triangles: +20 %)
-  int wf_blocks_per_cu = 0;      // 0 = default for the block size (MI355RT_WF_BLOCKS_PER_CU)
-  int wf_rayreg = -1;            // node-walk trace kernels: -1 = by scene, 0 / 1 = MI355RT_WF_RAYREG
-  long treelet_cap = -1;
+  lp::PlanKnobs knobs;           // what the launch planner takes from the environment and rt_set_walk (launch_plan.h)
   int treelet_order = 2;          // order of tnodes: 0 = by visit probability, 1 = the bridge's depth-first order, 2 = auto (MI355RT_TREELET_ORDER)
   bool nodes_from_device = false; // the node array was made by rt_world_update (an animated world), not uploaded
   uint32_t pt_launch[4] = {0, 0, 0, 0};   // last persistent launch: threads, workgroups, dynamic LDS, workgroups per CU
@@ -518,17 +513,10 @@ static int validate_scene(rt_ctx* c) {
   return RT_OK;
 }
 
-// the whole scene fits one workgroup's LDS beside four wave queues (the persistent kernel's LDS forms)
-bool scene_fits_lds(const rt_ctx* c) {
-  const size_t scene_lds = rtk::scene_lds_slots(c->n_nodes, c->n_tris, c->n_instances, c->n_verts, c->n_lights) * 16;
-  return !c->no_lds_staging && scene_lds + (size_t)4 * RT_WORK_BYTES_PER_WAVE <= 64 * 1024;
+// The uploaded scene as the launch planner (launch_plan.h) sees it; with c->knobs, all it reads of the context.
+lp::SceneSize scene_size(const rt_ctx* c) {
+  return {c->n_nodes, c->n_pairs, c->n_tris, c->n_instances, c->n_verts, c->n_lights, c->blas_offset};
 }
-// ... and its TLAS is one node, which is a leaf (k_validate_scene, or the world update's builder): the one-leaf forms, which
-// read the per-triangle world records
-bool one_leaf_lds(const rt_ctx* c) { return scene_fits_lds(c) && c->blas_offset == 1; }
-// the trace kernels walk child-pair records, not single nodes (rt_set_walk; auto: a scene of one instance).  prepare_scene
-// builds the records this says a launch will read.
-bool walks_pairs(const rt_ctx* c) { return c->walk == 1 || (c->walk == 2 && c->n_instances == 1); }
 
 int prepare_scene(rt_ctx* c) {
   {
@@ -579,7 +567,7 @@ int prepare_scene(rt_ctx* c) {
     T.n_nodes = c->n_nodes;
     T.n_tlas = c->blas_offset;
     T.n_roots = (uint32_t)c->blas_roots.size();
-    T.k_max = (uint32_t)(c->lds_per_cu / 32);
+    T.k_max = (uint32_t)(c->knobs.lds_per_cu / 32);
     const dim3 grid((c->n_nodes + 255) / 256);
     const uint32_t n_blocks = (c->n_nodes + 1023u) / 1024u;
     if ((r = ensure_buffer(c, c->treelet_work, ((size_t)RT_TREELET_WORK_HEAD + n_blocks) * 4, true)) < 0) return r;
@@ -589,7 +577,7 @@ int prepare_scene(rt_ctx* c) {
     // A device-resident update(t) (rt_world_update) re-lays the nodes out on every displayed frame: unless a partial
     // treelet is asked for (MI355RT_TREELET_MAX) the visit-probability order buys nothing there, so it keeps the bridge's
     // depth-first order: 3 launches instead of 10 (MI355RT_TREELET_ORDER=weight / identity forces either, for measurements)
-    const bool identity = c->treelet_order == 1 || (c->treelet_order == 2 && c->nodes_from_device && c->treelet_cap < 0);
+    const bool identity = c->treelet_order == 1 || (c->treelet_order == 2 && c->nodes_from_device && c->knobs.treelet_cap < 0);
     if (identity) {
       hipLaunchKernelGGL(rtk::k_treelet_iota, grid, dim3(256), 0, c->stream, T.new_index, c->n_nodes);
     } else {
@@ -611,7 +599,7 @@ int prepare_scene(rt_ctx* c) {
   }
   // the pair records are only walked by the wavefront trace kernels under the pair walk (rt_set_walk): a scene that takes
   // the node walk does not pay for them on every update(t); they are made when a launch (or rt_debug_read_pairs) wants them
-  const bool want_pairs = c->pairs_wanted || walks_pairs(c);
+  const bool want_pairs = c->pairs_wanted || lp::walks_pairs(scene_size(c), c->knobs);
   if (want_pairs && (c->pairs_dirty || c->roots_dirty) && c->n_nodes && c->n_instances) {
     // child-pair records of the walk (k_pairs.hip.h); validate_scene has uploaded the sorted BLAS roots into val_roots and
     // vouches for every pointer followed here.  An instance upload that keeps the set of BLAS roots only redoes the root
@@ -659,7 +647,7 @@ int prepare_scene(rt_ctx* c) {
   }
   // per-triangle world records: only a scene that takes a one-leaf LDS form reads them (a large animated world does not
   // pay for them on every update); the flag stays set until they are built
-  if (c->world_rec_dirty && one_leaf_lds(c) && c->n_tris && c->n_verts && c->n_instances && c->n_nodes) {
+  if (c->world_rec_dirty && lp::one_leaf_lds(scene_size(c), c->knobs) && c->n_tris && c->n_verts && c->n_instances && c->n_nodes) {
     int r = ensure_buffer(c, c->tri_shade_w, (size_t)c->n_tris * 128, true);
     if (r < 0) return r;
     DevScene S = dev_scene(c);
@@ -890,19 +878,19 @@ rt_ctx* rt_create(int device_ordinal) {
     return nullptr;
   }
   if (const char* e = getenv("MI355RT_WF_OVERLAP")) c->wf_overlap = atoi(e) != 0;
-  if (const char* e = getenv("MI355RT_NO_LDS_STAGING")) c->no_lds_staging = atoi(e) != 0;
+  if (const char* e = getenv("MI355RT_NO_LDS_STAGING")) c->knobs.no_lds_staging = atoi(e) != 0;
   if (const char* e = getenv("MI355RT_SHADE_BLOCKS_PER_CU")) c->shade_per_cu = std::max(1, std::min(4096, atoi(e)));
   if (const char* e = getenv("MI355RT_WF_BLOCK")) {
     const int b = atoi(e);
-    if (b == 256 || b == 512 || b == 1024) c->wf_block = b;
+    if (b == 256 || b == 512 || b == 1024) c->knobs.wf_block = b;
   }
-  if (const char* e = getenv("MI355RT_TREELET_MAX")) c->treelet_cap = atol(e);
+  if (const char* e = getenv("MI355RT_TREELET_MAX")) c->knobs.treelet_cap = atol(e);
   if (const char* e = getenv("MI355RT_TREELET_ORDER")) c->treelet_order = e[0] == 'w' ? 0 : (e[0] == 'i' ? 1 : 2);
-  if (const char* e = getenv("MI355RT_WALK")) c->walk = (e[0] == 'n' || e[0] == '0') ? 0 : ((e[0] == 'a' || e[0] == '2') ? 2 : 1);   // node / pairs / auto
-  if (const char* e = getenv("MI355RT_WF_RAYREG")) c->wf_rayreg = atoi(e) != 0 ? 1 : 0;
+  if (const char* e = getenv("MI355RT_WALK")) c->knobs.walk = (e[0] == 'n' || e[0] == '0') ? 0 : ((e[0] == 'a' || e[0] == '2') ? 2 : 1);   // node / pairs / auto
+  if (const char* e = getenv("MI355RT_WF_RAYREG")) c->knobs.wf_rayreg = atoi(e) != 0 ? 1 : 0;
   if (const char* e = getenv("MI355RT_WF_BLOCKS_PER_CU")) {
     const int b = atoi(e);
-    if (b >= 1 && b <= 8) c->wf_blocks_per_cu = b;
+    if (b >= 1 && b <= 8) c->knobs.wf_blocks_per_cu = b;
   }
   // counters: 2 banks (primary kernel, path-trace kernel) x RT_COUNTER_SHARDS x 6 u64
   if (hipMalloc(&c->counters.ptr, 2 * RT_COUNTER_SHARDS * 6 * sizeof(uint64_t)) != hipSuccess) {
@@ -1867,143 +1855,6 @@ int rt_set_scene(rt_ctx* c, const float camera[24], uint32_t frame_count, uint32
 
 int rt_recreate_bind_group(rt_ctx* c) { return c ? RT_OK : RT_ERR_INVALID; }
 
-// What one workgroup stages in LDS behind its wave queues, given `budget` bytes of LDS per workgroup: the tnodes, the
-// triangle records and the instance rows + BLAS roots, each if it fits whole.
-// *dyn_bytes = dynamic LDS size of the launch.
-// The LDS left for records beside the workgroup's `queue_bytes` of wave blocks, in 16-byte slots.
-static size_t lds_avail(size_t budget, size_t queue_bytes) {
-  budget &= ~(size_t)2047;   // LDS is allocated in granules: leave room so that the intended number of workgroups fits a CU
-  const size_t avail = budget > queue_bytes ? budget - queue_bytes : 0;
-  return avail & ~(size_t)15;
-}
-// every record of the scene staged
-static rtk::LdsPlan full_lds_plan(const rt_ctx* c) {
-  rtk::LdsPlan P;
-  P.k_nodes = c->n_nodes;
-  P.stage_inst = P.stage_tri = 1;
-  P.pad = 0;
-  return P;
-}
-static rtk::LdsPlan plan_lds(const rt_ctx* c, size_t budget, size_t queue_bytes, size_t* dyn_bytes) {
-  rtk::LdsPlan P;
-  P.k_nodes = P.stage_inst = P.stage_tri = P.pad = 0;
-  *dyn_bytes = queue_bytes;
-  if (c->no_lds_staging) return P;
-  size_t avail = lds_avail(budget, queue_bytes);
-  // Nodes: all of them or none.  A partial treelet (the most visited nodes in LDS, the rest behind the L1) was measured
-  // at 350 ... 3 200 nodes and never paid; MI355RT_TREELET_MAX = n stages min(n, what fits) for sweeps.
-  size_t k = (size_t)c->n_nodes * 32 <= avail ? c->n_nodes : 0;
-  if (c->treelet_cap >= 0) k = std::min<size_t>(std::min<size_t>(c->n_nodes, avail / 32), (size_t)c->treelet_cap);
-  P.k_nodes = (uint32_t)k;
-  avail -= k * 32;
-  const size_t tri_bytes = (size_t)c->n_tris * 16 * RT_TRI_STRIDE;
-  if (tri_bytes <= avail) {
-    P.stage_tri = 1;
-    avail -= tri_bytes;
-  }
-  const size_t inst_bytes = (size_t)c->n_instances * 64 + (((size_t)c->n_instances + 3) / 4) * 16;
-  if (inst_bytes <= avail) {
-    P.stage_inst = 1;
-    avail -= inst_bytes;
-  }
-  *dyn_bytes += (size_t)P.k_nodes * 32 + (P.stage_tri ? tri_bytes : 0) + (P.stage_inst ? inst_bytes : 0);
-  return P;
-}
-
-// The 256-thread forms of the persistent kernel (and the radiance query, which runs its path loop): the whole scene in LDS
-// when it fits beside four wave queues (fits_lds = scene_fits_lds), else six workgroups per CU (6 waves per SIMD), each
-// with its share of the CU's LDS for the top of the tree.
-static rtk::LdsPlan persistent_plan(const rt_ctx* c, bool fits_lds, size_t* dyn_bytes) {
-  const size_t queue_bytes = (size_t)4 * RT_WORK_BYTES_PER_WAVE;
-  if (!fits_lds) return plan_lds(c, c->lds_per_cu / 6, queue_bytes, dyn_bytes);
-  *dyn_bytes = queue_bytes + rtk::scene_lds_slots(c->n_nodes, c->n_tris, c->n_instances, c->n_verts, c->n_lights) * 16;
-  return full_lds_plan(c);
-}
-
-// The same for the child-pair walk of the trace kernels: pair records, triangle records, instance rows + root records.
-static rtk::PairPlan plan_pairs(const rt_ctx* c, size_t budget, size_t queue_bytes, size_t* dyn_bytes) {
-  rtk::PairPlan P;
-  P.stage_pairs = P.stage_inst = P.stage_tri = P.pad = 0;
-  *dyn_bytes = queue_bytes;
-  if (c->no_lds_staging) return P;
-  size_t avail = lds_avail(budget, queue_bytes);
-  const size_t pair_bytes = (size_t)c->n_pairs * 64, tri_bytes = (size_t)c->n_tris * 16 * RT_TRI_STRIDE,
-               inst_bytes = (size_t)c->n_instances * 96;
-  if (pair_bytes <= avail) {
-    P.stage_pairs = 1;
-    avail -= pair_bytes;
-  }
-  if (tri_bytes <= avail) {
-    P.stage_tri = 1;
-    avail -= tri_bytes;
-  }
-  if (inst_bytes <= avail) {
-    P.stage_inst = 1;
-    avail -= inst_bytes;
-  }
-  *dyn_bytes += (P.stage_pairs ? pair_bytes : 0) + (P.stage_tri ? tri_bytes : 0) + (P.stage_inst ? inst_bytes : 0);
-  return P;
-}
-
-// Form and workgroup shape of the trace kernels for the uploaded scene: what launch_wavefront runs k_wf_trace /
-// k_wf_trace_pairs in and rt_trace_rays its k_ray_query.  wf_block: threads per workgroup where not everything fits LDS
-// (0 = 256; the ray query has 256-thread forms only).
-struct TraceShape {
-  bool pairs, trace_lds, rayreg;
-  int block, blocks_per_cu;
-  size_t dyn;              // dynamic LDS per workgroup
-  rtk::PairPlan plan;      // pair walk: what a workgroup stages
-  rtk::LdsPlan nplan;      // node walk
-};
-static TraceShape trace_shape(const rt_ctx* c, bool fits_lds, int wf_block) {
-  const bool pairs = walks_pairs(c);
-  // Workgroup shape of the trace kernels.  Every wave owns `wave_bytes` of LDS: the triangle work queue, and for the pair walk
-  // the stack of deferred right children.  Everything fits beside four wave blocks in 64 KB: 256-thread workgroups, all records
-  // in LDS.  Otherwise 256-thread workgroups, each staging what fits whole in its share of the LDS (plan_pairs / plan_lds): the
-  // pair walk as many per CU as the wave blocks allow (4 at K = 8), the node walk six (6 waves per SIMD).
-  // MI355RT_WF_BLOCK / MI355RT_WF_BLOCKS_PER_CU override the shape for sweeps.
-  const size_t wave_bytes = pairs ? RT_PW_BYTES_PER_WAVE : RT_WORK_BYTES_PER_WAVE;
-  const size_t lds_records =
-      (pairs ? (size_t)4 * c->n_pairs + (size_t)RT_TRI_STRIDE * c->n_tris + (size_t)6 * c->n_instances
-             : (size_t)2 * c->n_nodes + (size_t)RT_TRI_STRIDE * c->n_tris + (size_t)4 * c->n_instances + ((size_t)c->n_instances + 3) / 4) * 16;
-  const bool trace_lds = !c->no_lds_staging && fits_lds && lds_records + (size_t)4 * wave_bytes <= 64 * 1024;
-  int block = 256, blocks_per_cu = 0;
-  if (!trace_lds) {
-    block = wf_block ? wf_block : 256;
-    blocks_per_cu = c->wf_blocks_per_cu ? c->wf_blocks_per_cu
-                    : pairs ? std::max(1, std::min((int)(c->lds_per_cu / ((size_t)(block / 64) * wave_bytes)), (RT_WF_WAVES * 256) / block))
-                            : (block == 1024 ? 1 : (block == 512 ? 2 : 6));
-  }
-  const size_t queue_bytes = (size_t)(block / 64) * wave_bytes;
-  size_t dyn = queue_bytes + lds_records;
-  rtk::PairPlan plan;
-  plan.stage_pairs = plan.stage_inst = plan.stage_tri = 1;
-  plan.pad = 0;
-  rtk::LdsPlan nplan = full_lds_plan(c);
-  if (!trace_lds) {
-    const size_t budget = c->lds_per_cu / (size_t)blocks_per_cu;
-    if (pairs)
-      plan = plan_pairs(c, budget, queue_bytes, &dyn);
-    else
-      nplan = plan_lds(c, budget, queue_bytes, &dyn);
-  }
-  plan.troot = c->troot;
-  // few instances with deep trees (glass blob: 3 instances, 400 k nodes): a ray enters an instance once and then waits at
-  // many leaves; measured, the form that keeps its instance-space origin / direction in registers is the faster one there,
-  // the other one where rays enter many small instances (k_traverse.hip.h, trav_post_at_entry; MI355RT_WF_RAYREG=0/1 overrides)
-  const bool rayreg = !pairs && (c->wf_rayreg < 0 ? (size_t)c->n_nodes >= (size_t)1024 * std::max<size_t>(1, c->n_instances) : c->wf_rayreg != 0);
-  TraceShape T;
-  T.pairs = pairs;
-  T.trace_lds = trace_lds;
-  T.rayreg = rayreg;
-  T.block = block;
-  T.blocks_per_cu = blocks_per_cu;
-  T.dyn = dyn;
-  T.plan = plan;
-  T.nplan = nplan;
-  return T;
-}
-
 // The trace kernels by [workgroup size 256 / 512 / 1024][any][detail][lds].  The node walk's RAYREG form is compiled for
 // 256-thread workgroups in mixed mode only: [any][detail].
 #define RT_WF_TRACE_FNS(K, B)                                                                                          \
@@ -2026,10 +1877,8 @@ static const void* const wf_shade_fns[2][2] = {{(const void*)rtk::k_wf_shade<fal
 static const void* const primary_fns[2][2] = {
     {(const void*)rtk::k_primary_visibility<false, false>, (const void*)rtk::k_primary_visibility<false, true>},
     {(const void*)rtk::k_primary_visibility<true, false>, (const void*)rtk::k_primary_visibility<true, true>}};
-
 // Wavefront form: per depth one shade launch and two trace launches, all enqueued without host readback.
-static int launch_wavefront(rt_ctx* c, const DevScene& S, const DevFrame& F, const DevFrameSlot* dslots, uint32_t n,
-                            bool fits_lds) {
+static int launch_wavefront(rt_ctx* c, const DevScene& S, const DevFrame& F, const DevFrameSlot* dslots, uint32_t n) {
   const size_t npx = (size_t)c->width * c->height;
   const size_t items = npx * n;
   if (items >= (1ull << 31)) return fail(c, RT_ERR_INVALID, "batch too large for the wavefront queues");
@@ -2064,29 +1913,26 @@ static int launch_wavefront(rt_ctx* c, const DevScene& S, const DevFrame& F, con
   Q.occluded = (uint32_t*)(qb + qcap * 128);
   Q.counters = (uint32_t*)c->wf_counters.ptr;
   const bool detail = c->detailed_counters;
-  const TraceShape shape = trace_shape(c, fits_lds, c->wf_block);
-  const bool pairs = shape.pairs, trace_lds = shape.trace_lds, rayreg = shape.rayreg;
-  const int block = shape.block;
-  const size_t dyn = shape.dyn;
-  rtk::PairPlan plan = shape.plan;
-  rtk::LdsPlan nplan = shape.nplan;
-  const int bi = block == 1024 ? 2 : (block == 512 ? 1 : 0);
+  lp::TraceShape shape = lp::trace_shape(scene_size(c), c->knobs, c->knobs.wf_block);
+  shape.plan.troot = c->troot;
+  const int bi = shape.block == 1024 ? 2 : (shape.block == 512 ? 1 : 0);
   const void* trace_fn[2];
   for (int k = 0; k < 2; k++)   // k = 0: any hit (shadow rays), 1: closest hit (extension rays)
-    trace_fn[k] = pairs ? wf_pair_fns[bi][k == 0][detail][trace_lds]
-                        : (rayreg && bi == 0 && !trace_lds ? wf_node_rayreg_fns[k == 0][detail] : wf_node_fns[bi][k == 0][detail][trace_lds]);
+    trace_fn[k] = shape.pairs ? wf_pair_fns[bi][k == 0][detail][shape.trace_lds]
+                  : shape.rayreg && bi == 0 && !shape.trace_lds ? wf_node_rayreg_fns[k == 0][detail]
+                                                                : wf_node_fns[bi][k == 0][detail][shape.trace_lds];
   int trace_per_cu[2];
   for (int k = 0; k < 2; k++)
-    if ((r = resident_blocks(c, trace_fn[k], block, dyn, &trace_per_cu[k])) < 0) return r;
+    if ((r = resident_blocks(c, trace_fn[k], shape.block, shape.dyn, &trace_per_cu[k])) < 0) return r;
   if (getenv("MI355RT_DEBUG_SHAPE"))
     fprintf(stderr, "[mi355rt] trace kernels: %s walk, %d threads per workgroup, %zu bytes of LDS, resident workgroups per CU: any-hit %d, closest-hit %d\n",
-            pairs ? "pair" : "node", block, dyn, trace_per_cu[0], trace_per_cu[1]);
-  uint32_t nn = pairs ? c->n_pairs : c->n_nodes, nt = c->n_tris, ni = c->n_instances, depth = 0;
+            shape.pairs ? "pair" : "node", shape.block, shape.dyn, trace_per_cu[0], trace_per_cu[1]);
+  uint32_t nn = shape.pairs ? c->n_pairs : c->n_nodes, nt = c->n_tris, ni = c->n_instances, depth = 0;
   DevScene Sa = S;
   DevFrame Fa = F;
   rt_scene_uniforms Ua = c->uniforms;
   void* shade_args[] = {&Sa, &Fa, &Ua, &W, &Q, &dslots, &n, &depth};
-  void* trace_args[] = {&Sa, &Fa, &Ua, &Q, &depth, &nn, &nt, &ni, pairs ? (void*)&plan : (void*)&nplan};
+  void* trace_args[] = {&Sa, &Fa, &Ua, &Q, &depth, &nn, &nt, &ni, shape.pairs ? (void*)&shape.plan : (void*)&shape.nplan};
   EventPair* ev = next_events(c, RT_TIMER_PATHTRACE);
   if (ev) HIP_TRY(c, hipEventRecord(ev->a, c->stream));
   for (; depth < depths; depth++) {
@@ -2097,7 +1943,8 @@ static int launch_wavefront(rt_ctx* c, const DevScene& S, const DevFrame& F, con
     for (int k = 0; k < 2; k++) {
       // resident workgroups: what fits (registers, LDS; since round 4 the node-walk kernels leave room for a seventh wave per
       // SIMD), or MI355RT_WF_BLOCKS_PER_CU
-      const uint32_t blocks = grid_blocks(c, trace_per_cu[k], c->wf_blocks_per_cu, (items + (size_t)block - 1) / (size_t)block);
+      const uint32_t blocks =
+          grid_blocks(c, trace_per_cu[k], c->knobs.wf_blocks_per_cu, (items + (size_t)shape.block - 1) / (size_t)shape.block);
       EventPair* evt = next_events(c, k == 0 ? RT_TIMER_WF_TRACE_SHADOW : RT_TIMER_WF_TRACE_EXT);
       hipStream_t st = c->stream;
       if (k == 0 && c->wf_overlap) {   // any-hit trace: fork to the side stream behind this depth's shade kernel
@@ -2106,7 +1953,7 @@ static int launch_wavefront(rt_ctx* c, const DevScene& S, const DevFrame& F, con
         HIP_TRY(c, hipStreamWaitEvent(st, c->side_fork, 0));
       }
       if (evt) HIP_TRY(c, hipEventRecord(evt->a, st));
-      HIP_TRY(c, hipLaunchKernel(trace_fn[k], dim3(blocks), dim3(block), trace_args, dyn, st));
+      HIP_TRY(c, hipLaunchKernel(trace_fn[k], dim3(blocks), dim3(shape.block), trace_args, shape.dyn, st));
       if (evt) HIP_TRY(c, hipEventRecord(evt->b, st));
       if (k == 0 && c->wf_overlap) HIP_TRY(c, hipEventRecord(c->side_join, st));
     }
@@ -2139,17 +1986,15 @@ static const void* const rq_fns[5][2][2] = {RT_RQ_FNS(rtk::RT_RQ_NODE_LDS), RT_R
 static int launch_ray_query(rt_ctx* c, const void* d_rays, uint32_t n, int mode, float t_min, void* d_out, bool detail) {
   int r = query_scene_ready(c, "ray query", false);
   if (r < 0) return r;
-  const TraceShape shape = trace_shape(c, scene_fits_lds(c), 0);
-  const int form = shape.pairs ? (shape.trace_lds ? rtk::RT_RQ_PAIR_LDS : rtk::RT_RQ_PAIR_GLOBAL)
-                               : (shape.trace_lds ? rtk::RT_RQ_NODE_LDS : (shape.rayreg ? rtk::RT_RQ_NODE_RAYREG : rtk::RT_RQ_NODE_MIXED));
-  const void* fn = rq_fns[form][mode == RT_RAYS_ANY][detail];
-  const size_t dyn = shape.dyn;
+  lp::TraceShape shape = lp::trace_shape(scene_size(c), c->knobs, 0);
+  shape.plan.troot = c->troot;
+  const void* fn = rq_fns[shape.rq_form][mode == RT_RAYS_ANY][detail];
   int per_cu;
-  if ((r = resident_blocks(c, fn, 256, dyn, &per_cu)) < 0) return r;
-  const uint32_t blocks = grid_blocks(c, per_cu, c->wf_blocks_per_cu, (n + 255u) / 256u);
+  if ((r = resident_blocks(c, fn, 256, shape.dyn, &per_cu)) < 0) return r;
+  const uint32_t blocks = grid_blocks(c, per_cu, c->knobs.wf_blocks_per_cu, (n + 255u) / 256u);
   if (getenv("MI355RT_DEBUG_SHAPE"))
     fprintf(stderr, "[mi355rt] ray query: %s walk, form %d, %zu bytes of LDS, resident workgroups per CU %d, %u workgroups\n",
-            shape.pairs ? "pair" : "node", form, dyn, per_cu, blocks);
+            shape.pairs ? "pair" : "node", shape.rq_form, shape.dyn, per_cu, blocks);
   rtk::RayQueryArgs A;
   if ((r = query_reset_counters(c, c->rq, &A.counters, &A.head)) < 0) return r;
   A.rays = (const float4*)d_rays;
@@ -2161,14 +2006,12 @@ static int launch_ray_query(rt_ctx* c, const void* d_rays, uint32_t n, int mode,
   A.n_tris = c->n_tris;
   A.n_inst = c->n_instances;
   DevScene S = dev_scene(c);
-  rtk::LdsPlan nplan = shape.nplan;
-  rtk::PairPlan plan = shape.plan;
-  void* args[] = {&S, &A, &nplan, &plan};
-  if ((r = query_launch(c, c->rq, fn, blocks, args, dyn)) < 0) return r;
+  void* args[] = {&S, &A, &shape.nplan, &shape.plan};
+  if ((r = query_launch(c, c->rq, fn, blocks, args, shape.dyn)) < 0) return r;
   c->rq_last = rt_ray_stats();
   c->rq_last.walk = shape.pairs ? 1u : 0u;
   c->rq_last.lds = shape.trace_lds ? 1u : 0u;
-  c->rq_last.rayreg = form == rtk::RT_RQ_NODE_RAYREG ? 1u : 0u;
+  c->rq_last.rayreg = shape.rq_form == rtk::RT_RQ_NODE_RAYREG ? 1u : 0u;
   c->rq_last.workgroups = blocks;
   return RT_OK;
 }
@@ -2245,16 +2088,14 @@ static int launch_path_query(rt_ctx* c, const PathQueryKind& k, const void* d_it
   int r = query_scene_ready(c, k.what, true);
   if (r < 0) return r;
   // the persistent kernel's 256-thread forms without the one-leaf one
-  const bool lds = scene_fits_lds(c);
-  size_t dyn;
-  rtk::LdsPlan plan = persistent_plan(c, lds, &dyn);
-  const void* fn = k.fns[detail][lds];
+  lp::PersistentShape shape = lp::persistent_plan(scene_size(c), c->knobs);
+  const void* fn = k.fns[detail][shape.lds];
   int per_cu;
-  if ((r = resident_blocks(c, fn, 256, dyn, &per_cu)) < 0) return r;
+  if ((r = resident_blocks(c, fn, 256, shape.dyn, &per_cu)) < 0) return r;
   const uint32_t blocks = grid_blocks(c, per_cu, 0, (n + 255u) / 256u);
   if (getenv("MI355RT_DEBUG_SHAPE"))
     fprintf(stderr, "[mi355rt] %s: %s form, %zu bytes of LDS, resident workgroups per CU %d, %u workgroups\n", k.what,
-            lds ? "LDS" : "global", dyn, per_cu, blocks);
+            shape.lds ? "LDS" : "global", shape.dyn, per_cu, blocks);
   rtk::PathQueryArgs A;
   if ((r = query_reset_counters(c, c->*k.state, &A.counters, &A.head)) < 0) return r;
   A.items = (const float4*)d_items;
@@ -2270,13 +2111,13 @@ static int launch_path_query(rt_ctx* c, const PathQueryKind& k, const void* d_it
   A.n_inst = c->n_instances;
   A.n_verts = c->n_verts;
   DevScene S = dev_scene(c);
-  void* args[] = {&S, &A, &plan};
-  if ((r = query_launch(c, c->*k.state, fn, blocks, args, dyn)) < 0) return r;
+  void* args[] = {&S, &A, &shape.plan};
+  if ((r = query_launch(c, c->*k.state, fn, blocks, args, shape.dyn)) < 0) return r;
   rt_radiance_stats& last = c->*k.last;
   last = rt_radiance_stats();
   last.rays = n;
   last.samples = (uint64_t)n * spp;
-  last.lds = lds ? 1u : 0u;
+  last.lds = shape.lds ? 1u : 0u;
   last.workgroups = blocks;
   return RT_OK;
 }
@@ -2355,6 +2196,26 @@ int rt_gather_irradiance(rt_ctx* c, const rt_gather_point* points, uint32_t n, u
   return path_query_host(c, pq_gather, reinterpret_cast<const rt_ray*>(points), n, max_depth, spp, seed, out, stats);
 }
 
+// ---- the kernels of compute().  Variant 0, the one-pixel-per-lane megakernel: one tile per workgroup, no dynamic LDS.
+static int launch_megakernel(rt_ctx* c, const DevScene& S, const DevFrame& F, const DevFrameSlot* dslots, uint32_t tiles) {
+  EventPair* ev = next_events(c, RT_TIMER_PATHTRACE);
+  if (ev) HIP_TRY(c, hipEventRecord(ev->a, c->stream));
+  if (c->detailed_counters)
+    hipLaunchKernelGGL(rtk::k_pathtrace<true>, dim3(tiles), dim3(64), 0, c->stream, S, F, c->uniforms, dslots);
+  else
+    hipLaunchKernelGGL(rtk::k_pathtrace<false>, dim3(tiles), dim3(64), 0, c->stream, S, F, c->uniforms, dslots);
+  if (ev) HIP_TRY(c, hipEventRecord(ev->b, c->stream));
+  return RT_OK;
+}
+// The persistent kernel by [detail][lds] of its lp::PersistentShape, its one-leaf LDS form by [detail], and that form's
+// product build in 512-thread workgroups (wide)
+static const void* const pt_fns[2][2] = {
+    {(const void*)rtk::k_pathtrace_persistent<false, false>, (const void*)rtk::k_pathtrace_persistent<false, true>},
+    {(const void*)rtk::k_pathtrace_persistent<true, false>, (const void*)rtk::k_pathtrace_persistent<true, true>}};
+static const void* const pt_one_leaf_fns[2] = {(const void*)rtk::k_pathtrace_persistent<false, true, true>,
+                                               (const void*)rtk::k_pathtrace_persistent<true, true, true>};
+static const void* const pt_wide_fn = (const void*)rtk::k_pathtrace_persistent_wide<false, true, true>;
+
 // compute() for n consecutive frame counts in ONE dispatch of each kernel (n == 1: the plain compute()).
 // n_commit < n: frames n_commit .. n-1 are traced AHEAD (speculative lookahead): their host state is not committed and their
 // colours are not accumulated yet — consume_ahead() does both when the matching compute() call arrives.
@@ -2401,11 +2262,10 @@ static int compute_frames(rt_ctx* c, const uint32_t* frame_counts, uint32_t n, u
   if (r < 0) return r;
 
   const size_t npx = (size_t)c->width * c->height;
-  const size_t scene_lds = rtk::scene_lds_slots(c->n_nodes, c->n_tris, c->n_instances, c->n_verts, c->n_lights) * 16;
-  const bool fits_lds = scene_fits_lds(c);
+  const lp::SceneSize size = scene_size(c);
   // auto: the wavefront form pays from 4 frames per dispatch (measured: 1 frame 11.9 vs 8.7 ms persistent, 2: 17.0 vs
   // 15.7, 4: 27.8 vs 29.5, 8: 47.9 vs 57.0 on sponza-like) — a single frame leaves its deeper stages too few rays
-  const bool wavefront = c->spp == 1 && (c->variant == 2 || (c->variant == 3 && !fits_lds && n >= 4));
+  const bool wavefront = c->spp == 1 && (c->variant == 2 || (c->variant == 3 && !lp::scene_fits_lds(size, c->knobs) && n >= 4));
   if (n > 1) {
     r = ensure_buffer(c, c->gbuf_batch, (size_t)(n - 1) * npx * 24, false);
     if (r < 0) return r;
@@ -2470,82 +2330,53 @@ static int compute_frames(rt_ctx* c, const uint32_t* frame_counts, uint32_t n, u
   DevFrame Fp = F;  // the primary kernel counts into bank 0, the path tracer into bank 1
   F.counters = (uint64_t*)c->counters.ptr + (size_t)RT_COUNTER_SHARDS * 6;
   const uint32_t tiles = ((c->width + 7) / 8) * ((c->height + 7) / 8);
-  const uint32_t ptiles = F.own_period ? ((c->width + 7) / 8) * F.own_tile_rows : tiles;  // primary kernel grid
+  const uint32_t own_tiles = F.own_period ? ((c->width + 7) / 8) * F.own_tile_rows : tiles;  // this rank's: what both kernels cover
 
   // 1. primary visibility (the reference clears + rasterises the G-buffer every compute()); frame = blockIdx.y
   EventPair* ev = next_events(c, RT_TIMER_PRIMARY);
   if (ev) HIP_TRY(c, hipEventRecord(ev->a, c->stream));
-  // ptiles == 0: tile-aligned stripes and a rank that owns no tile row (fewer tile rows than ranks) - nothing to cast, and a
-  // grid of x-size 0 is an invalid launch configuration
-  if (ptiles) {
-    const size_t plds = rtk::primary_lds_slots(c->n_nodes, c->n_tris, c->n_instances, c->n_verts) * 16;
-    uint32_t nn = c->n_nodes, nt = c->n_tris, ni = c->n_instances, nv = c->n_verts, n_ptiles = ptiles;
+  // own_tiles == 0: tile-aligned stripes and a rank that owns no tile row (fewer tile rows than ranks) - nothing to cast, and
+  // a grid of x-size 0 is an invalid launch configuration
+  if (own_tiles) {
+    const lp::PrimaryShape shape = lp::primary_shape(size, c->knobs);
+    uint32_t nn = c->n_nodes, nt = c->n_tris, ni = c->n_instances, nv = c->n_verts, n_ptiles = own_tiles;
     // one-leaf scenes: the LDS form stages the shading records with world-space vertex normals
-    const float4* tsw = (one_leaf_lds(c) && !c->world_rec_dirty) ? (const float4*)c->tri_shade_w.ptr : nullptr;
-    const bool lds = plds <= 32 * 1024 && !c->no_lds_staging;   // small scene: records staged in LDS, four tiles per workgroup
+    const float4* tsw = (lp::one_leaf_lds(size, c->knobs) && !c->world_rec_dirty) ? (const float4*)c->tri_shade_w.ptr : nullptr;
     void* args[] = {&S, &Fp, &c->uniforms, &dslots, &n_ptiles, &nn, &nt, &ni, &nv, &tsw};
-    HIP_TRY(c, hipLaunchKernel(primary_fns[c->detailed_counters][lds], lds ? dim3((ptiles + 3) / 4, n) : dim3(ptiles, n),
-                               dim3(lds ? 256 : 64), args, lds ? plds : 0, c->stream));
+    const uint32_t per_wg = shape.tiles_per_workgroup;
+    HIP_TRY(c, hipLaunchKernel(primary_fns[c->detailed_counters][shape.lds], dim3((own_tiles + per_wg - 1) / per_wg, n),
+                               dim3(shape.block), args, shape.dyn, c->stream));
   }
   if (ev) HIP_TRY(c, hipEventRecord(ev->b, c->stream));
 
   // 2. path trace
   if (wavefront) {
-    r = launch_wavefront(c, S, F, dslots, n, fits_lds);
+    r = launch_wavefront(c, S, F, dslots, n);
     if (r < 0) return r;
   } else if (c->variant == 0) {
-    ev = next_events(c, RT_TIMER_PATHTRACE);
-    if (ev) HIP_TRY(c, hipEventRecord(ev->a, c->stream));
-    if (c->detailed_counters)
-      hipLaunchKernelGGL(rtk::k_pathtrace<true>, dim3(tiles), dim3(64), 0, c->stream, S, F, c->uniforms, dslots);
-    else
-      hipLaunchKernelGGL(rtk::k_pathtrace<false>, dim3(tiles), dim3(64), 0, c->stream, S, F, c->uniforms, dslots);
-    if (ev) HIP_TRY(c, hipEventRecord(ev->b, c->stream));
+    r = launch_megakernel(c, S, F, dslots, tiles);
+    if (r < 0) return r;
   } else {
     // persistent kernel: grid = resident workgroups, tiles handed out through a ticket counter
     HIP_TRY(c, hipMemsetAsync(c->ticket.ptr, 0, 4, c->stream));
-    size_t dyn;  // work queues + records
-    rtk::LdsPlan plan = persistent_plan(c, fits_lds, &dyn);
-    // LDS form of a scene whose TLAS is one node, which is a leaf (k_validate_scene, or the world update's builder): the walks skip the TLAS
-    // half of the node step (k_traverse.hip.h traverse<.., ONE_INST>)
-    const bool one_inst = one_leaf_lds(c);
-    if (one_inst && c->world_rec_dirty) return fail(c, RT_ERR_INTERNAL, "one-leaf form without its world records");
-    // These forms stage less than scene_lds (rtk::one_leaf_lds_slots): the launch asks for what they stage, while the
-    // choice of the form, here and below, stays on scene_lds, the size the two sides of each line were measured at
-    const size_t staged_lds = one_inst ? rtk::one_leaf_lds_slots(c->n_nodes, c->n_tris, c->n_instances, c->n_lights) * 16 : scene_lds;
-    if (one_inst) dyn = (size_t)4 * RT_WORK_BYTES_PER_WAVE + staged_lds;
-    // the product build of that form in 512-thread workgroups (k_pathtrace_persistent_wide, 6 waves per SIMD) when three of
-    // them, each with eight wave queues, eight waves' parked sample sums and one copy of the scene, fit the CU's LDS, and the
-    // dispatch carries more than one frame: a single 1080p frame gives its 6 144 waves 1.3 tickets each, and there the
-    // slower waves of the wide form lose more in the tail than the sixth wave gains (Cornell live loop, one dispatch per
-    // frame: 0.906 -> 0.945 ms per frame)
-    const size_t dyn_wide = (size_t)8 * (RT_WORK_BYTES_PER_WAVE + RT_PT_COL_BYTES_PER_WAVE) + scene_lds;
-    const bool wide = one_inst && !c->detailed_counters && n > 1 && dyn_wide <= c->lds_per_cu / 3;
-    if (wide) dyn = (size_t)8 * (RT_WORK_BYTES_PER_WAVE + RT_PT_COL_BYTES_PER_WAVE) + staged_lds;
-    const int vi = wide ? 6 : one_inst ? (c->detailed_counters ? 5 : 4) : (c->detailed_counters ? 2 : 0) + (fits_lds ? 1 : 0);
-    const uint32_t waves = wide ? 8u : 4u;   // per workgroup
-    static const void* const fns[7] = {(const void*)rtk::k_pathtrace_persistent<false, false>,
-                                       (const void*)rtk::k_pathtrace_persistent<false, true>,
-                                       (const void*)rtk::k_pathtrace_persistent<true, false>,
-                                       (const void*)rtk::k_pathtrace_persistent<true, true>,
-                                       (const void*)rtk::k_pathtrace_persistent<false, true, true>,
-                                       (const void*)rtk::k_pathtrace_persistent<true, true, true>,
-                                       (const void*)rtk::k_pathtrace_persistent_wide<false, true, true>};
-    const void* fn = fns[vi];
+    lp::PersistentShape shape = lp::persistent_shape(size, c->knobs, n, c->detailed_counters);
+    if (shape.one_inst && c->world_rec_dirty) return fail(c, RT_ERR_INTERNAL, "one-leaf form without its world records");
+    const void* fn = shape.wide       ? pt_wide_fn
+                     : shape.one_inst ? pt_one_leaf_fns[c->detailed_counters]
+                                      : pt_fns[c->detailed_counters][shape.lds];
     int per_cu;
-    if ((r = resident_blocks(c, fn, (int)(64 * waves), dyn, &per_cu)) < 0) return r;
-    const uint32_t own_tiles = F.own_period ? ((c->width + 7) / 8) * F.own_tile_rows : tiles;
+    if ((r = resident_blocks(c, fn, (int)(64 * shape.waves), shape.dyn, &per_cu)) < 0) return r;
     // as many waves as there are tickets (tiles x frames), up to the resident limit; fewer, longer-lived waves measured worse
-    const uint32_t blocks = grid_blocks(c, per_cu, 0, (own_tiles * n + waves - 1) / waves);
+    const uint32_t blocks = grid_blocks(c, per_cu, 0, (own_tiles * n + shape.waves - 1) / shape.waves);
     uint32_t* ticket = (uint32_t*)c->ticket.ptr;
     uint32_t nn = c->n_nodes, nt = c->n_tris, ni = c->n_instances, nv = c->n_verts, ns = n;
-    void* args[] = {&S, &F, &c->uniforms, &ticket, &nn, &nt, &ni, &nv, &dslots, &ns, &plan};
+    void* args[] = {&S, &F, &c->uniforms, &ticket, &nn, &nt, &ni, &nv, &dslots, &ns, &shape.plan};
     ev = next_events(c, RT_TIMER_PATHTRACE);
     if (ev) HIP_TRY(c, hipEventRecord(ev->a, c->stream));
-    HIP_TRY(c, hipLaunchKernel(fn, dim3(blocks), dim3(64 * waves), args, dyn, c->stream));
-    c->pt_launch[0] = 64 * waves;
+    HIP_TRY(c, hipLaunchKernel(fn, dim3(blocks), dim3(64 * shape.waves), args, shape.dyn, c->stream));
+    c->pt_launch[0] = 64 * shape.waves;
     c->pt_launch[1] = blocks;
-    c->pt_launch[2] = (uint32_t)dyn;
+    c->pt_launch[2] = (uint32_t)shape.dyn;
     c->pt_launch[3] = (uint32_t)per_cu;
     if (ev) HIP_TRY(c, hipEventRecord(ev->b, c->stream));
     if (n > 1)  // ordered accumulation of the batch's frame colours
@@ -2826,7 +2657,7 @@ int rt_set_kernel_variant(rt_ctx* c, int variant) {
 }
 int rt_set_walk(rt_ctx* c, int walk) {
   if (!c || walk < 0 || walk > 2) return RT_ERR_INVALID;
-  c->walk = walk;
+  c->knobs.walk = walk;
   c->epoch++;
   return RT_OK;
 }
