@@ -24,7 +24,8 @@ KAT = json.load(open(os.path.join(REPO, "tests", "golden", "blas_kat.json")))
 TLAS_KAT = json.load(open(os.path.join(REPO, "tests", "golden", "tlas_kat.json")))
 
 
-def cpu_build_blas(W, verts, tris):
+def cpu_build_blas_raw(W, verts, tris):
+    """ms_build_blas: (nodes (n, 8) float32 rows {min, skip} {max, data}, order (n_tris,) uint32)"""
     lib = ctypes.CDLL(W._build.build_scene())
     v4 = np.zeros((len(verts), 4), np.float32)
     v4[:, :3] = np.asarray(verts, np.float32)
@@ -38,7 +39,11 @@ def cpu_build_blas(W, verts, tris):
     rc = lib.ms_build_blas(v4.ctypes.data_as(vp), len(verts), idx.ctypes.data_as(vp), n_tris, nodes.ctypes.data_as(vp),
                            nodes.shape[0], ctypes.byref(n_nodes), order.ctypes.data_as(vp))
     assert rc == 0
-    nodes = nodes[:n_nodes.value]
+    return nodes[:n_nodes.value].copy(), order
+
+
+def cpu_build_blas(W, verts, tris):
+    nodes, order = cpu_build_blas_raw(W, verts, tris)
     u = nodes.view(np.uint32)
     return [{"min": nodes[i, 0:3].tolist(), "skip": int(u[i, 3]), "max": nodes[i, 4:7].tolist(), "data": int(u[i, 7])}
             for i in range(len(nodes))], order.tolist()
@@ -140,6 +145,48 @@ def _nodes(a):
     return a[:, 0:3], a[:, 4:7], u[:, 3].astype(np.int64), u[:, 7].astype(np.int64)
 
 
+def check_blas_hierarchy(bmin, bmax, skip, data, root, tmin, tmax, may_overflow=False):
+    """The structure of ONE BLAS whose root is node `root` of the arrays (_nodes), independent of any builder: tmin / tmax
+    are the triangles' unpadded boxes in topology order, indexed by the leaves' `first`.  Returns the triangle range
+    (first, end) the leaves tile, or None for a BLAS with overflowed fallback leaves (allowed only with may_overflow), for
+    which only the decode-independent invariants are checked."""
+    n = len(skip)
+    end = root + skip[root]                                       # skip pointers are relative to the BLAS root
+    assert root < end <= n
+    idx = np.arange(root, end)
+    # they go forward and stay inside the BLAS: a pre-order tree
+    assert (root + skip[idx] <= end).all() and (root + skip[idx] > idx).all()
+    leaves = idx[data[idx] != 0]
+    first, count = data[leaves] >> 3, data[leaves] & 7
+    # leaves tile a contiguous triangle range without gaps or overlaps ...
+    o = np.argsort(first)
+    f, c = first[o], count[o]
+    tiled = bool((c >= 1).all() and (f[1:] == f[:-1] + c[:-1]).all())
+    if not may_overflow:
+        assert tiled
+    covered = None
+    if tiled:
+        covered = (int(f[0]), int(f[-1] + c[-1]))
+    else:
+        # ... except where a fallback leaf holds more than 7 triangles: blas.rs:111-115 stores `first << 3 | count`
+        # with an unmasked count, so the word decodes to another (first, count).  "special" has three such leaves
+        # (its light sphere's coincident-centre triangles: raw words 210 = 0 << 3 | 210, 2139, 2169): 280 of its 564
+        # triangles are unreachable, in the reference as here; a leaf of exactly 8 decodes to count 0 ("mixed").
+        # Only the decode-independent invariants are checked for such a BLAS.
+        first, count, leaves = first[:0], count[:0], leaves[:0]
+    # every leaf box encloses its triangles; every inner box encloses its two children
+    for k, (ff, cc) in zip(leaves, zip(first, count)):
+        assert (bmin[k] <= tmin[ff:ff + cc].min(axis=0)).all() and (bmax[k] >= tmax[ff:ff + cc].max(axis=0)).all()
+    inner = idx[data[idx] == 0]
+    left = inner + 1
+    right = root + skip[left]
+    assert (right < end).all()
+    for k, l, r in zip(inner, left, right):
+        assert (bmin[k] <= np.minimum(bmin[l], bmin[r])).all() and (bmax[k] >= np.maximum(bmax[l], bmax[r])).all()
+        assert root + skip[r] == root + skip[k]                     # the right child ends where its parent ends
+    return covered
+
+
 @pytest.mark.parametrize("scene", SCENES)
 def test_bvh_arrays_are_a_valid_hierarchy(W, scene):
     b = pu.bridge_for(W, scene)
@@ -152,46 +199,18 @@ def test_bvh_arrays_are_a_valid_hierarchy(W, scene):
     dc = np.asarray(b.draw_commands, np.uint32).reshape(-1, 4).astype(np.int64)
     assert len(dc) == len(inst) and (dc[:, 1] == 1).all() and (dc[:, 3] == np.arange(len(inst))).all()
     bmin, bmax, skip, data = _nodes(b.blas)
-    n = len(skip)
     seen_tris, unreachable = {}, {}
     dc_range = {int(blas_off[i]): (int(dc[i, 2] // 3), int(dc[i, 2] // 3 + dc[i, 0] // 3)) for i in range(len(inst))}
     for root in sorted(set(blas_off.tolist())):
-        end = root + skip[root]                                       # skip pointers are relative to the BLAS root
-        assert root < end <= n
-        idx = np.arange(root, end)
-        # they go forward and stay inside the BLAS: a pre-order tree
-        assert (root + skip[idx] <= end).all() and (root + skip[idx] > idx).all()
-        leaves = idx[data[idx] != 0]
-        first, count = data[leaves] >> 3, data[leaves] & 7
-        # leaves tile a contiguous triangle range without gaps or overlaps ...
-        o = np.argsort(first)
-        f, c = first[o], count[o]
-        tiled = bool((c >= 1).all() and (f[1:] == f[:-1] + c[:-1]).all())
-        if scene not in UNREACHABLE:
-            assert tiled
-        if tiled:
-            seen_tris[root] = (int(f[0]), int(f[-1] + c[-1]))
-        else:
-            # ... except where a fallback leaf holds more than 7 triangles: blas.rs:111-115 stores `first << 3 | count`
-            # with an unmasked count, so the word decodes to another (first, count).  "special" has three such leaves
-            # (its light sphere's coincident-centre triangles: raw words 210 = 0 << 3 | 210, 2139, 2169): 280 of its 564
-            # triangles are unreachable, in the reference as here; a leaf of exactly 8 decodes to count 0 ("mixed").
-            # Only the decode-independent invariants are checked for such a BLAS.
-            cov = decoded_coverage(data[leaves], len(topo))
-            unreachable[root] = int((cov[dc_range[root][0]:dc_range[root][1]] == 0).sum())
+        tiled = check_blas_hierarchy(bmin, bmax, skip, data, root, tmin, tmax, may_overflow=scene in UNREACHABLE)
+        if tiled is not None:
+            seen_tris[root] = tiled
+        else:   # overflowed fallback leaves: count what their words hide from the traversal
+            words = data[root:root + skip[root]]
+            cov = decoded_coverage(words[words != 0], len(topo))
             assert cov.max() == 1
+            unreachable[root] = int((cov[dc_range[root][0]:dc_range[root][1]] == 0).sum())
             seen_tris[root] = dc_range[root]
-            first, count, leaves = first[:0], count[:0], leaves[:0]
-        # every leaf box encloses its triangles; every inner box encloses its two children
-        for k, (ff, cc) in zip(leaves, zip(first, count)):
-            assert (bmin[k] <= tmin[ff:ff + cc].min(axis=0)).all() and (bmax[k] >= tmax[ff:ff + cc].max(axis=0)).all()
-        inner = idx[data[idx] == 0]
-        left = inner + 1
-        right = root + skip[left]
-        assert (right < end).all()
-        for k, l, r in zip(inner, left, right):
-            assert (bmin[k] <= np.minimum(bmin[l], bmin[r])).all() and (bmax[k] >= np.maximum(bmax[l], bmax[r])).all()
-            assert root + skip[r] == root + skip[k]                     # the right child ends where its parent ends
     assert sum(unreachable.values()) == UNREACHABLE.get(scene, 0)
     # the triangle range a BLAS covers is the range the instance's draw command names (lib.rs:237-262)
     for i in range(len(inst)):

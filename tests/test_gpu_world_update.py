@@ -92,13 +92,16 @@ def nasty_skinned_glb(seed, n_verts=700, n_tris=1500):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("seed", [1, 2, 3])
-def test_device_update_on_degenerate_skinned_input(W, seed):
+@pytest.mark.parametrize("seed,size", [pytest.param(1, (700, 1500), id="1"), pytest.param(2, (700, 1500), id="2"),
+                                       pytest.param(3, (700, 1500), id="3"), pytest.param(1, (3000, 12000), id="1-12000")])
+def test_device_update_on_degenerate_skinned_input(W, seed, size):
     """The corner cases of the skinning loop and of the builders (see nasty_skinned_glb), at times that put the scale
     animation at 1, near 0, at exactly 0, on the way to 1e20 and at 1e20: the device either produces the host's bytes or
-    refuses the frame (a NaN instance box) and the host path takes it."""
+    refuses the frame (a NaN instance box) and the host path takes it.  At 12 000 triangles per geometry the trees are
+    above the builder's large-node threshold and change depth by half a dozen levels between the last two times, so the
+    relaunch with more levels runs with large nodes too."""
     r = W.WebGPURenderer(0)
-    glb = nasty_skinned_glb(seed)
+    glb = nasty_skinned_glb(seed, *size)
     cpu_b, dev_b = W.WorldBridge(), W.WorldBridge()
     dev_b.setDeviceUpdater(r)
     cpu_b.loadScene("viewer", glbData=glb)

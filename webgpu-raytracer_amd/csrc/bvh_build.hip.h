@@ -471,7 +471,8 @@ __device__ __forceinline__ void k_subtree(const Build& B, SubShared& S, uint32_t
 // One tree level: workgroup b takes nodes b, b + gridDim.x, ... of the level (IDS: of the level's small-node list, made by
 // k_big_plan).  T = 256 for the levels of few, larger nodes, T = 64 (one wave per node) for the deep levels: tens of
 // thousands of nodes of a few dozen triangles.  A node of any size is handled correctly (a large one slowly): the
-// large-node kernels below are an optimisation the host schedules for the levels it expects such nodes on.
+// large-node kernels below are an optimisation the host schedules for the levels it expects such nodes on
+// (tests/test_gpu_blas_builder.py puts nodes above kBig through both generic forms, and several nodes through one workgroup).
 template <int T, bool IDS>
 __global__ __launch_bounds__(T) void k_level(Build B, uint32_t level) {
   constexpr uint32_t kThreads = (uint32_t)T;
