@@ -416,6 +416,70 @@ int rt_gather_irradiance_device(rt_ctx* ctx, const void* dev_points, uint32_t n,
                                 void* dev_out);
 int rt_irradiance_gather_stats(rt_ctx* ctx, rt_radiance_stats* out);
 
+/* ---- lightmap bakes: "the gather points of this instance's atlas", rasterised on the device ----
+ * An irradiance gather wants surface points; a lightmap wants one per covered texel of an instance's UV atlas.  The scene
+ * holds what that takes on the device (uv, pos, nrm, topology, the instances' forward transforms, the draw commands with
+ * each instance's triangle range) - also after rt_world_update, when the skinned vertices exist nowhere else - so the
+ * UV-space rasteriser runs there (csrc/k_bake.hip.h) and its points feed rt_gather_irradiance without leaving HBM.
+ *
+ * THE TEXEL RULE.  All arithmetic is f32, unfused (no FMA contraction), in the order written, with rt_div / rt_normalize
+ * of mi355rt_math.h for division and square root.  Inputs: an rt_bake_desc d {inst, width W, height H, pad_base, t_max}
+ * (mi355rt_layout.h) and optionally an override array atlas_uv of 2 f32 per vertex of the WHOLE scene (lightmap UVs are
+ * rarely the texture UVs).  uv(j), the atlas UV of global vertex j, is atlas_uv[j] when the array is given, else the
+ * scene's uv[j].
+ *   triangles   of instance d.inst: the global triangles k in [dc.z / 3, dc.z / 3 + dc.x / 3) of its draw command dc = {3
+ *               n_tris, 1, 3 first_tri, i} (integer division), in ascending k.  A k at or beyond the topology's triangle
+ *               count is skipped and never read.
+ *   vertices    in texel space, with (v0, v1, v2) the topology row's vertex ids: a = (uv(v0).x * (float)W, uv(v0).y *
+ *               (float)H), b and c likewise from v1, v2.
+ *   texel       (x, y), 0 <= x < W, 0 <= y < H, has index y * W + x and centre p = ((float)x + 0.5f, (float)y + 0.5f).
+ *               Row 0 is v near 0: nothing is flipped.
+ *   E(q, r, s)  = (r.x - q.x) * (s.y - q.y) - (r.y - q.y) * (s.x - q.x), and A = E(a, b, c).
+ *   coverage    triangle k covers the texel iff (1) a.x, a.y, b.x, b.y, c.x, c.y and A are all finite and A != 0; (2)
+ *               min(a.x, b.x, c.x) <= p.x <= max(a.x, b.x, c.x) and the same in y; (3) with sg = A > 0 ? 1.0f : -1.0f: sg *
+ *               E(a, b, p) >= 0, sg * E(b, c, p) >= 0 and sg * E(c, a, p) >= 0.  (2) makes a sweep over the triangle's
+ *               bounding box exact, also for needles whose edge values all round to 0.
+ *   owner       of a texel: the LOWEST global triangle index that covers it, or none.  This settles overlapping charts,
+ *               both windings, duplicate triangles and centres on shared edges.
+ *   point       of a texel with owner k: bu = rt_div(E(c, a, p), A) (the weight of v1), bv = rt_div(E(a, b, p), A) (of v2),
+ *               bw = 1.0f - bu - bv;  V0, V1, V2 = rt_mat_mul_point(instance transform, pos[v*]) (the world-space triangle
+ *               light sampling makes);  position = (bw * V0 + bu * V1) + bv * V2;  normal = rt_normalize(rt_vec_mul_mat_dir(
+ *               rt_normalize((nrm[v0] * bw + nrm[v1] * bu) + nrm[v2] * bv), instance inverse)) (the shading normal of a
+ *               traced hit, without the normal map);  t_max = d.t_max;  pad = d.pad_base + y * W + x.
+ *   output      the covered texels in ASCENDING TEXEL INDEX, compacted: points[j] (rt_gather_point) and texels[j] (u32),
+ *               j = 0 .. n-1.  The optional owner map holds W * H i32: the owner's global triangle index, -1 for none.
+ * The rule has no run-time freedom: two bakes of one scene give the same words, and a CPU restatement (tests/model/
+ * bake_model.cpp) gives them too.  Out of scope: chart packing, dilation of uncovered texels (a host one-liner on the owner
+ * map), conservative rasterisation, several instances per call.
+ * Limits, all RT_ERR_INVALID: a NULL descriptor, reserved != 0, W or H == 0, W * H > 2^24, pad_base + W * H > 2^31 (the
+ * gather's pad rule), inst >= the instance count, a NULL output that is needed.  Without a valid scene: RT_ERR_NOT_READY;
+ * also when the scene has no draw command for every instance (rt_upload(RT_KIND_DRAW_COMMANDS) was never called).
+ * A bake leaves the renderer as it was, like the queries above; it has staging arrays of its own, kept and grown.
+ *   rt_bake_points         blocking, one fence.  atlas_uv: host array or NULL = the scene's uvs; when given, n_uv_vertices
+ *                          must be the scene's vertex count.  Writes min(n, cap) records to points_out / texels_out and
+ *                          sets *n_out = n; cap < n is RT_OK with *n_out > cap; cap == 0 (outputs may be NULL) only counts.
+ *                          owner_out: W * H i32 or NULL.  The price of the single fence: min(cap, W * H) records (36 B each)
+ *                          are staged on the device and cross to a host buffer before n is known, whatever the coverage -
+ *                          about 600 MB at 4096 x 4096.  A caller who minds counts first (cap == 0) and passes cap = n.
+ *   rt_bake_points_device  the same on device-accessible arrays (16-byte aligned, on the context's device; dev_atlas_uv: 2
+ *                          f32 per scene vertex or NULL; dev_count: one u32; dev_owner: W * H u32 or NULL; dev_points /
+ *                          dev_texels may be NULL when cap == 0): only enqueues on the context's stream (rt_set_stream
+ *                          respected).
+ *   rt_bake_irradiance     the whole bake: points -> rt_gather_irradiance's kernel on them (max_depth, spp, seed as there) ->
+ *                          scatter.  atlas_out[texels[j]] is, bit for bit, what rt_gather_irradiance returns for points[j];
+ *                          every uncovered texel is {+0, +0, +0, -1.0f} (hit_fraction lies in [0, 1], so -1 says "no
+ *                          surface").  *n_covered_out (may be NULL) = n.  stats (may be NULL) are the gather's: the
+ *                          counting kernel runs, and rt_irradiance_gather_stats reports this gather afterwards.  One host
+ *                          read of the count between the point pass and the gather.  The values are E / pi: multiply by pi *
+ *                          albedo for the outgoing radiance of a Lambert texel.  A device form of the whole bake is not
+ *                          offered: chain rt_bake_points_device and rt_gather_irradiance_device. */
+int rt_bake_points(rt_ctx* ctx, const rt_bake_desc* desc, const float* atlas_uv, uint32_t n_uv_vertices,
+                   rt_gather_point* points_out, uint32_t* texels_out, uint32_t cap, uint32_t* n_out, int32_t* owner_out);
+int rt_bake_points_device(rt_ctx* ctx, const rt_bake_desc* desc, const void* dev_atlas_uv, void* dev_points, void* dev_texels,
+                          uint32_t cap, void* dev_count, void* dev_owner);
+int rt_bake_irradiance(rt_ctx* ctx, const rt_bake_desc* desc, const float* atlas_uv, uint32_t n_uv_vertices, uint32_t max_depth,
+                       uint32_t spp, uint32_t seed, rt_irradiance* atlas_out, uint32_t* n_covered_out, rt_radiance_stats* stats);
+
 /* ---- the sharded image: one picture rendered by `world` contexts ("ranks"), assembled on rank 0 ----
  * Rank k owns the image rows y with (y / stripe_rows) % world == k and traces only those (rt_set_stripes).  Its COMPACT
  * BLOCK holds the rows it owns in ascending y, width float4 each, padded with zero rows to max_rows = the largest share

@@ -156,8 +156,18 @@ typedef struct rt_irradiance { /* 16 B: one vector store of k_irradiance_gather 
   float hit_fraction;         /* samples whose first segment hit something / spp */
 } rt_irradiance;
 
+/* ---- lightmap bakes (rt_bake_points, mi355rt.h): which atlas of which instance ---- */
+typedef struct rt_bake_desc { /* 32 B */
+  uint32_t inst;              /* TLAS-order instance index */
+  uint32_t width, height;     /* of the atlas, in texels: both >= 1, width * height <= 2^24 */
+  uint32_t pad_base;          /* pad of a point = pad_base + texel index; pad_base + width * height <= 2^31 */
+  float t_max;                /* of every point */
+  uint32_t reserved[3];       /* 0 */
+} rt_bake_desc;
+
 #ifdef __cplusplus
 }
+static_assert(sizeof(rt_bake_desc) == 32, "rt_bake_desc is 32 bytes");
 static_assert(sizeof(rt_gather_point) == 32, "rt_gather_point is 32 bytes");
 static_assert(__builtin_offsetof(rt_gather_point, t_max) == 12 && __builtin_offsetof(rt_gather_point, normal) == 16 &&
                   __builtin_offsetof(rt_gather_point, pad) == 28,

@@ -21,6 +21,8 @@
 //                             with a policy per kind, and k_radiance_query: the items are rays (rt_trace_radiance)
 //   k_gather.hip.h            k_irradiance_gather: the same loop behind hemisphere directions drawn at a caller's surface
 //                             points (rt_gather_irradiance)
+//   k_bake.hip.h              k_bake_owner / _count / _scan / _emit: the UV-space rasteriser that makes such points from the
+//                             texels of an instance's atlas (rt_bake_points), and k_bake_scatter, the way back
 //   k_texture_post.hip.h      k_resize_texture; k_postprocess = PostProcess.wgsl `main` (:103-176)
 //   k_validate.hip.h          k_validate_scene: every index the kernels follow, checked once per upload
 //   k_stripes.hip.h           k_pack_stripes / k_unpack_stripes: the copies of the sharded image's gather
@@ -50,6 +52,7 @@
 #include "k_pathtrace.hip.h"
 #include "k_radiance.hip.h"
 #include "k_gather.hip.h"
+#include "k_bake.hip.h"
 #include "k_wavefront.hip.h"
 #include "k_rayquery.hip.h"
 #include "k_texture_post.hip.h"

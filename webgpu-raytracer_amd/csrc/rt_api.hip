@@ -63,6 +63,14 @@ struct QueryState {
   bool timed = false;               // the last query recorded its events
 };
 
+// What lightmap bakes (rt_bake_points, rt_bake_irradiance) keep between calls: their staging arrays, kept and grown.
+struct BakeState {
+  DeviceBuffer uv;                  // the caller's override atlas UVs (host entries)
+  DeviceBuffer owner, blocks, count;   // owner map, per-workgroup counts / prefixes, the device count
+  DeviceBuffer points, texels;      // the compacted points and their texel indices
+  DeviceBuffer results, atlas;      // rt_bake_irradiance: the gather's results, the scattered atlas
+};
+
 }  // namespace
 
 struct rt_ctx {
@@ -203,6 +211,7 @@ struct rt_ctx {
   rt_ray_stats rq_last = {};
   rt_radiance_stats rd_last = {};
   rt_radiance_stats gi_last = {};
+  BakeState bk;
 
   // kernel timing
   bool timing = false;
@@ -928,6 +937,8 @@ void rt_destroy(rt_ctx* c) {
                          &c->slots, &c->gbuf_batch, &c->frame_col, &c->wf_state, &c->wf_queues, &c->wf_counters,
                          &c->rq.in, &c->rq.out, &c->rq.counters, &c->rd.in, &c->rd.out, &c->rd.counters,
                          &c->gi.in, &c->gi.out, &c->gi.counters,
+                         &c->bk.uv, &c->bk.owner, &c->bk.blocks, &c->bk.count, &c->bk.points, &c->bk.texels, &c->bk.results,
+                         &c->bk.atlas,
                          &c->tex_staging, &c->bv_in, &c->bv_tri, &c->bv_order, &c->bv_nodes, &c->bv_out,
                          &c->bv_counters, &c->bv_big, &c->val_roots, &c->val_bad, &c->tnodes, &c->node_key, &c->node_newidx,
                          &c->inst_root, &c->root_w, &c->treelet_work, &c->pairs, &c->pair_of, &c->pair_parent, &c->root_rec,
@@ -2144,8 +2155,9 @@ static int path_query_stats(rt_ctx* c, const PathQueryKind& k, rt_radiance_stats
   return RT_OK;
 }
 
+// detail: run the counting kernel; < 0: as rt_set_counting says
 static int path_query_device(rt_ctx* c, const PathQueryKind& k, const void* dev_items, uint32_t n, uint32_t max_depth, uint32_t spp,
-                             uint32_t seed, void* dev_out) {
+                             uint32_t seed, void* dev_out, int detail = -1) {
   if (!c) return RT_ERR_INVALID;
   int r = path_query_args_ok(c, k, n, spp);
   if (r < 0) return r;
@@ -2154,7 +2166,7 @@ static int path_query_device(rt_ctx* c, const PathQueryKind& k, const void* dev_
     return RT_OK;
   }
   if ((r = query_device_arrays_ok(c, k.what, dev_items, dev_out)) < 0) return r;
-  return launch_path_query(c, k, dev_items, n, max_depth, spp, seed, dev_out, c->detailed_counters);
+  return launch_path_query(c, k, dev_items, n, max_depth, spp, seed, dev_out, detail < 0 ? c->detailed_counters : detail != 0);
 }
 
 // items: rt_ray or rt_gather_point, the same 32 bytes
@@ -2194,6 +2206,178 @@ int rt_gather_irradiance_device(rt_ctx* c, const void* dev_points, uint32_t n, u
 int rt_gather_irradiance(rt_ctx* c, const rt_gather_point* points, uint32_t n, uint32_t max_depth, uint32_t spp, uint32_t seed,
                          rt_irradiance* out, rt_radiance_stats* stats) {
   return path_query_host(c, pq_gather, reinterpret_cast<const rt_ray*>(points), n, max_depth, spp, seed, out, stats);
+}
+
+// ---- lightmap bakes: the texel rule of mi355rt.h as four launches (k_bake.hip.h), then the gather path and the scatter
+static int bake_desc_ok(rt_ctx* c, const rt_bake_desc* d) {
+  if (!d) return fail(c, RT_ERR_INVALID, "bake: NULL descriptor");
+  if (d->reserved[0] | d->reserved[1] | d->reserved[2]) return fail(c, RT_ERR_INVALID, "bake: reserved words must be 0");
+  if (d->width == 0 || d->height == 0) return fail(c, RT_ERR_INVALID, "bake: width and height must be >= 1");
+  const uint64_t texels = (uint64_t)d->width * d->height;
+  if (texels > (1ull << 24)) return fail(c, RT_ERR_INVALID, "bake: width * height must be <= 2^24");
+  if ((uint64_t)d->pad_base + texels > (1ull << 31)) return fail(c, RT_ERR_INVALID, "bake: pad_base + width * height must be <= 2^31");
+  return RT_OK;
+}
+// the scene is there, has a draw command for every instance, and d->inst is one of them
+static int bake_scene_ready(rt_ctx* c, const rt_bake_desc* d, bool lights) {
+  const int r = query_scene_ready(c, "bake", lights);
+  if (r < 0) return r;
+  if (!c->draw_commands.ptr || c->draw_commands.size < (size_t)c->n_instances * 16)
+    return fail(c, RT_ERR_NOT_READY, "bake: the scene has no draw command for every instance (upload RT_KIND_DRAW_COMMANDS)");
+  if (d->inst >= c->n_instances) return fail(c, RT_ERR_INVALID, "bake: inst is not an instance of the scene");
+  return RT_OK;
+}
+// the override UVs of a host entry -> the bake's staging array; *d_uv = that, or null for the scene's
+static int bake_stage_uv(rt_ctx* c, const float* atlas_uv, uint32_t n_uv_vertices, const void** d_uv) {
+  *d_uv = nullptr;
+  if (!atlas_uv) return RT_OK;
+  if (n_uv_vertices != c->n_verts) return fail(c, RT_ERR_INVALID, "bake: n_uv_vertices must be the scene's vertex count");
+  const int r = ensure_buffer(c, c->bk.uv, (size_t)n_uv_vertices * 8, true);
+  if (r < 0) return r;
+  HIP_TRY(c, hipMemcpyAsync(c->bk.uv.ptr, atlas_uv, (size_t)n_uv_vertices * 8, hipMemcpyHostToDevice, c->stream));
+  *d_uv = c->bk.uv.ptr;
+  return RT_OK;
+}
+// Enqueue the owner pass, the counts and their scan: afterwards d_owner (null: the bake's own map) holds the owner map,
+// d_count the number of covered texels, and A everything the emit launch needs but its outputs.
+static int bake_front(rt_ctx* c, const rt_bake_desc* d, const void* d_uv, void* d_owner, void* d_count, rtk::BakeArgs& A) {
+  const uint32_t texels = d->width * d->height;
+  int r;
+  if (!d_owner) {
+    if ((r = ensure_buffer(c, c->bk.owner, (size_t)texels * 4, true)) < 0) return r;
+    d_owner = c->bk.owner.ptr;
+  }
+  A = rtk::BakeArgs();
+  A.n_blocks = (texels + 255u) / 256u;
+  if ((r = ensure_buffer(c, c->bk.blocks, (size_t)A.n_blocks * 4, true)) < 0) return r;
+  A.auv = d_uv ? (const float2*)d_uv : (const float2*)c->uv.ptr;
+  A.draw = (const uint4*)c->draw_commands.ptr;
+  A.owner = (uint32_t*)d_owner;
+  A.block_count = (uint32_t*)c->bk.blocks.ptr;
+  A.count = (uint32_t*)d_count;
+  A.inst = d->inst;
+  A.W = d->width;
+  A.H = d->height;
+  A.pad_base = d->pad_base;
+  A.t_max = d->t_max;
+  A.n_tris = c->n_tris;
+  A.tiles_x = (d->width + 7u) / 8u;
+  A.tiles_y = (d->height + 7u) / 8u;
+  A.bands = (A.tiles_y + RT_BAKE_BAND_TILES - 1u) / RT_BAKE_BAND_TILES;
+  A.n_chunks = (c->n_tris + 63u) / 64u;
+  DevScene S = dev_scene(c);
+  HIP_TRY(c, hipMemsetAsync(d_owner, 0xff, (size_t)texels * 4, c->stream));   // RT_BAKE_NONE
+  // one wave per (64 triangles, band) item up to what the device holds; the waves stride over the rest
+  const uint64_t items = (uint64_t)A.n_chunks * A.bands;
+  const uint32_t owner_blocks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((items + 3) / 4, (uint64_t)c->num_cus * 8));
+  hipLaunchKernelGGL(rtk::k_bake_owner, dim3(owner_blocks), dim3(256), 0, c->stream, S, A);
+  hipLaunchKernelGGL(rtk::k_bake_count, dim3(A.n_blocks), dim3(256), 0, c->stream, A);
+  hipLaunchKernelGGL(rtk::k_bake_scan, dim3(1), dim3(RT_BAKE_SCAN_THREADS), 0, c->stream, A);
+  HIP_TRY(c, hipGetLastError());
+  return RT_OK;
+}
+// Enqueue the emit launch: the first min(n, cap) points and texel indices, in ascending texel order
+static int bake_emit(rt_ctx* c, rtk::BakeArgs& A, void* d_points, void* d_texels, uint32_t cap) {
+  if (cap == 0) return RT_OK;
+  A.points = (float4*)d_points;
+  A.texels = (uint32_t*)d_texels;
+  A.cap = cap;
+  DevScene S = dev_scene(c);
+  hipLaunchKernelGGL(rtk::k_bake_emit, dim3(A.n_blocks), dim3(256), 0, c->stream, S, A);
+  HIP_TRY(c, hipGetLastError());
+  return RT_OK;
+}
+
+int rt_bake_points_device(rt_ctx* c, const rt_bake_desc* d, const void* dev_atlas_uv, void* dev_points, void* dev_texels,
+                          uint32_t cap, void* dev_count, void* dev_owner) {
+  if (!c) return RT_ERR_INVALID;
+  int r = bake_desc_ok(c, d);
+  if (r < 0) return r;
+  if (!dev_count) return fail(c, RT_ERR_INVALID, "bake: NULL array");
+  if (cap != 0 && (r = query_device_arrays_ok(c, "bake", dev_points, dev_texels)) < 0) return r;
+  if ((r = query_device_arrays_ok(c, "bake", dev_count, dev_owner ? dev_owner : dev_count)) < 0) return r;
+  if (dev_atlas_uv && (r = query_device_arrays_ok(c, "bake", dev_atlas_uv, dev_count)) < 0) return r;
+  if ((r = bake_scene_ready(c, d, false)) < 0) return r;
+  rtk::BakeArgs A;
+  if ((r = bake_front(c, d, dev_atlas_uv, dev_owner, dev_count, A)) < 0) return r;
+  return bake_emit(c, A, dev_points, dev_texels, std::min(cap, d->width * d->height));
+}
+
+int rt_bake_points(rt_ctx* c, const rt_bake_desc* d, const float* atlas_uv, uint32_t n_uv_vertices, rt_gather_point* points_out,
+                   uint32_t* texels_out, uint32_t cap, uint32_t* n_out, int32_t* owner_out) {
+  if (!c) return RT_ERR_INVALID;
+  int r = bake_desc_ok(c, d);
+  if (r < 0) return r;
+  if (!n_out || (cap != 0 && (!points_out || !texels_out))) return fail(c, RT_ERR_INVALID, "bake: NULL array");
+  if ((r = bake_scene_ready(c, d, false)) < 0) return r;
+  const void* d_uv;
+  if ((r = bake_stage_uv(c, atlas_uv, n_uv_vertices, &d_uv)) < 0) return r;
+  const uint32_t texels = d->width * d->height, m = std::min(cap, texels);
+  if ((r = ensure_buffer(c, c->bk.count, 16, false)) < 0) return r;
+  if ((r = ensure_buffer(c, c->bk.points, (size_t)m * sizeof(rt_gather_point), true)) < 0) return r;
+  if ((r = ensure_buffer(c, c->bk.texels, (size_t)m * 4, true)) < 0) return r;
+  rtk::BakeArgs A;
+  if ((r = bake_front(c, d, d_uv, nullptr, c->bk.count.ptr, A)) < 0) return r;
+  if ((r = bake_emit(c, A, c->bk.points.ptr, c->bk.texels.ptr, m)) < 0) return r;
+  // one fence: the count and the m staged records come back together, the first min(n, cap) of them go to the caller
+  uint32_t n = 0;
+  std::vector<rt_gather_point> points(m);
+  std::vector<uint32_t> tex(m);
+  HIP_TRY(c, hipMemcpyAsync(&n, c->bk.count.ptr, 4, hipMemcpyDeviceToHost, c->stream));
+  if (m) {
+    HIP_TRY(c, hipMemcpyAsync(points.data(), c->bk.points.ptr, (size_t)m * sizeof(rt_gather_point), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(tex.data(), c->bk.texels.ptr, (size_t)m * 4, hipMemcpyDeviceToHost, c->stream));
+  }
+  if (owner_out) HIP_TRY(c, hipMemcpyAsync(owner_out, c->bk.owner.ptr, (size_t)texels * 4, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  const uint32_t got = std::min(n, m);
+  if (got) {
+    std::memcpy(points_out, points.data(), (size_t)got * sizeof(rt_gather_point));
+    std::memcpy(texels_out, tex.data(), (size_t)got * 4);
+  }
+  *n_out = n;
+  return RT_OK;
+}
+
+int rt_bake_irradiance(rt_ctx* c, const rt_bake_desc* d, const float* atlas_uv, uint32_t n_uv_vertices, uint32_t max_depth,
+                       uint32_t spp, uint32_t seed, rt_irradiance* atlas_out, uint32_t* n_covered_out, rt_radiance_stats* stats) {
+  if (!c) return RT_ERR_INVALID;
+  int r = bake_desc_ok(c, d);
+  if (r < 0) return r;
+  if (!atlas_out) return fail(c, RT_ERR_INVALID, "bake: NULL array");
+  const uint32_t texels = d->width * d->height;
+  if ((r = path_query_args_ok(c, pq_gather, texels, spp)) < 0) return r;
+  if ((r = bake_scene_ready(c, d, true)) < 0) return r;
+  const void* d_uv;
+  if ((r = bake_stage_uv(c, atlas_uv, n_uv_vertices, &d_uv)) < 0) return r;
+  if ((r = ensure_buffer(c, c->bk.count, 16, false)) < 0) return r;
+  rtk::BakeArgs A;
+  if ((r = bake_front(c, d, d_uv, nullptr, c->bk.count.ptr, A)) < 0) return r;
+  // the one host read between the point pass and the gather: how many points there are
+  uint32_t n = 0;
+  HIP_TRY(c, hipMemcpyAsync(&n, c->bk.count.ptr, 4, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if ((r = ensure_buffer(c, c->bk.points, (size_t)n * sizeof(rt_gather_point), true)) < 0) return r;
+  if ((r = ensure_buffer(c, c->bk.texels, (size_t)n * 4, true)) < 0) return r;
+  if ((r = ensure_buffer(c, c->bk.results, (size_t)n * sizeof(rt_irradiance), true)) < 0) return r;
+  if ((r = ensure_buffer(c, c->bk.atlas, (size_t)texels * sizeof(rt_irradiance), true)) < 0) return r;
+  if ((r = bake_emit(c, A, c->bk.points.ptr, c->bk.texels.ptr, n)) < 0) return r;
+  if ((r = path_query_device(c, pq_gather, c->bk.points.ptr, n, max_depth, spp, seed, c->bk.results.ptr, stats != nullptr)) < 0)
+    return r;
+  rtk::BakeScatterArgs B;
+  B.owner = A.owner;
+  B.texels = (const uint32_t*)c->bk.texels.ptr;
+  B.results = (const float4*)c->bk.results.ptr;
+  B.atlas = (float4*)c->bk.atlas.ptr;
+  B.n_texels = texels;
+  B.n = n;
+  hipLaunchKernelGGL(rtk::k_bake_scatter, dim3(A.n_blocks), dim3(256), 0, c->stream, B);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipMemcpyAsync(atlas_out, c->bk.atlas.ptr, (size_t)texels * sizeof(rt_irradiance), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (n_covered_out) *n_covered_out = n;
+  if (stats) return path_query_stats(c, pq_gather, stats);
+  return RT_OK;
 }
 
 // ---- the kernels of compute().  Variant 0, the one-pixel-per-lane megakernel: one tile per workgroup, no dynamic LDS.

@@ -638,6 +638,75 @@ static napi_value rtGatherIrradiance(napi_env env, napi_callback_info info) {
   return radiance_stats_object(env, &st);
 }
 
+/* ------------------------------------------------------- lightmap bakes (rt_bake_points / rt_bake_irradiance, mi355rt.h) */
+static double get_f64(napi_env env, napi_value v) {
+  double x = 0.0;
+  napi_get_value_double(env, v, &x);
+  return x;
+}
+/* [inst, width, height, padBase] and tMax -> descriptor */
+static rt_bake_desc bake_desc(napi_env env, const napi_value* a) {
+  rt_bake_desc d;
+  memset(&d, 0, sizeof(d));
+  d.inst = get_u32(env, a[0]);
+  d.width = get_u32(env, a[1]);
+  d.height = get_u32(env, a[2]);
+  d.pad_base = get_u32(env, a[3]);
+  d.t_max = (float)get_f64(env, a[4]);
+  return d;
+}
+/* (ctx, inst, width, height, padBase, tMax, atlasUv: Float32Array of 2 per scene vertex or null, points: Float32Array of 8
+ * per record, texels: Uint32Array, owner: Int32Array of width * height or null) -> the number of covered texels, or a
+ * negative status; min(n, records the arrays hold) records are written */
+static napi_value rtBakePoints(napi_env env, napi_callback_info info) {
+  napi_value a[10];
+  void *uv = NULL, *points = NULL, *texels = NULL, *owner = NULL;
+  size_t nuv = 0, np = 0, nt = 0, no = 0;
+  if (!get_args(env, info, 10, a) || !get_bytes(env, a[6], &uv, &nuv) || !get_bytes(env, a[7], &points, &np) ||
+      !get_bytes(env, a[8], &texels, &nt) || !get_bytes(env, a[9], &owner, &no))
+    return NULL;
+  const rt_bake_desc d = bake_desc(env, a + 1);
+  size_t cap = np / sizeof(rt_gather_point);
+  if (nt / 4 < cap) cap = nt / 4;
+  if (cap > 0xffffffffu || nuv % 8 != 0 || nuv / 8 > 0xffffffffu || (owner && no / 4 < (size_t)d.width * d.height)) {
+    napi_throw_range_error(env, NULL, "rtBakePoints: atlasUv must hold 2 floats per vertex and owner width * height words");
+    return NULL;
+  }
+  uint32_t n = 0;
+  const int rc = rt_bake_points((rt_ctx*)get_ptr(env, a[0]), &d, (const float*)uv, (uint32_t)(nuv / 8), (rt_gather_point*)points,
+                                (uint32_t*)texels, (uint32_t)cap, &n, (int32_t*)owner);
+  if (rc < 0) return make_int(env, rc);
+  napi_value r;
+  napi_create_uint32(env, n, &r);
+  return r;
+}
+/* (ctx, inst, width, height, padBase, tMax, atlasUv or null, maxDepth, spp, seed, atlas: Float32Array of 4 per texel,
+ * wantStats) -> {covered, stats?}, or a negative status */
+static napi_value rtBakeIrradiance(napi_env env, napi_callback_info info) {
+  napi_value a[12];
+  void *uv = NULL, *atlas = NULL;
+  size_t nuv = 0, na = 0;
+  bool want_stats = false;
+  if (!get_args(env, info, 12, a) || !get_bytes(env, a[6], &uv, &nuv) || !get_bytes(env, a[10], &atlas, &na)) return NULL;
+  napi_get_value_bool(env, a[11], &want_stats);
+  const rt_bake_desc d = bake_desc(env, a + 1);
+  if (nuv % 8 != 0 || nuv / 8 > 0xffffffffu || na / sizeof(rt_irradiance) < (size_t)d.width * d.height) {
+    napi_throw_range_error(env, NULL, "rtBakeIrradiance: atlasUv must hold 2 floats per vertex and atlas 4 floats per texel");
+    return NULL;
+  }
+  rt_radiance_stats st;
+  uint32_t n = 0;
+  const int rc = rt_bake_irradiance((rt_ctx*)get_ptr(env, a[0]), &d, (const float*)uv, (uint32_t)(nuv / 8), get_u32(env, a[7]),
+                                    get_u32(env, a[8]), get_u32(env, a[9]), (rt_irradiance*)atlas, &n, want_stats ? &st : NULL);
+  if (rc < 0) return make_int(env, rc);
+  napi_value obj, v;
+  if (napi_create_object(env, &obj) != napi_ok) return NULL;
+  napi_create_uint32(env, n, &v);
+  napi_set_named_property(env, obj, "covered", v);
+  if (want_stats) napi_set_named_property(env, obj, "stats", radiance_stats_object(env, &st));
+  return obj;
+}
+
 static napi_value Init(napi_env env, napi_value exports) {
   static const struct {
     const char* name;
@@ -655,7 +724,8 @@ static napi_value Init(napi_env env, napi_value exports) {
                {"rtDistWriteBlock", rtDistWriteBlock}, {"rtUnpackStripes", rtUnpackStripes},
                {"rtGatherStripes", rtGatherStripes}, {"rtReadDisplay", rtReadDisplay}, {"rtTraceRays", rtTraceRays},
                {"rtRayQueryStats", rtRayQueryStats}, {"rtTraceRadiance", rtTraceRadiance},
-               {"rtGatherIrradiance", rtGatherIrradiance}, {"msCreate", msCreate}, {"msDestroy", msDestroy},
+               {"rtGatherIrradiance", rtGatherIrradiance}, {"rtBakePoints", rtBakePoints},
+               {"rtBakeIrradiance", rtBakeIrradiance}, {"msCreate", msCreate}, {"msDestroy", msDestroy},
                {"msUpdate", msUpdate}, {"msUpdateCamera", msUpdateCamera}, {"msGet", msGet},
                {"msTextureCount", msTextureCount}, {"msTexture", msTexture},
                {"msAnimationNames", msAnimationNames}, {"msSetAnimation", msSetAnimation},

@@ -65,6 +65,17 @@ export class WebGPURenderer {
    *  that hit something within tMax.  The stats are a radiance query's with rays = points. */
   gatherIrradiance(points: Float32Array, maxDepth: number, spp: number, opts?: { seed?: number; stats?: boolean }):
     { data: Float32Array; n: number; stats?: RadianceQueryStats };
+  /** Lightmap bakes (rt_bake_points): the covered texels of TLAS-order instance `inst`'s width x height atlas as gather points,
+   *  in ascending texel index; pad = padBase + texel index.  atlasUv: 2 floats per scene vertex, overriding the scene's uvs.
+   *  owner: the Int32Array owner map (global triangle index, -1 = uncovered). */
+  bakePoints(inst: number, width: number, height: number,
+             opts?: { tMax?: number; padBase?: number; atlasUv?: Float32Array | null; owner?: boolean }):
+    { n: number; points: Float32Array; texels: Uint32Array; owner?: Int32Array };
+  /** The whole bake (rt_bake_irradiance): points, the irradiance gather on them, scatter.  `data` holds 4 floats per texel
+   *  {r, g, b, hitFraction}, row 0 first; rgb is E / pi (multiply by pi * albedo), uncovered texels are {0, 0, 0, -1}. */
+  bakeIrradiance(inst: number, width: number, height: number, maxDepth: number, spp: number,
+                 opts?: { tMax?: number; padBase?: number; atlasUv?: Float32Array | null; seed?: number; stats?: boolean }):
+    { data: Float32Array; width: number; height: number; covered: number; stats?: RadianceQueryStats };
   destroy(): void;
 }
 export class WorldBridge {
@@ -105,6 +116,8 @@ export class WorldBridge {
 
 /** src/main.ts:133-163 — re-upload what the bridge marks as new, reset the accumulation; true when something was uploaded */
 export function syncWorld(renderer: WebGPURenderer, bridge: WorldBridge, width: number, height: number): boolean;
+/** RGBA8 rows, top first -> the bytes of a PNG file (colour type 6). */
+export function encodePng(rgba: Uint8Array, width: number, height: number): Uint8Array;
 /** `renderFrame` of src/main.ts:119-181 */
 export class LiveLoop {
   constructor(renderer: WebGPURenderer, bridge: WorldBridge, width: number, height: number, updateInterval?: number);

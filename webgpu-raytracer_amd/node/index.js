@@ -202,6 +202,33 @@ class WebGPURenderer {
     if (typeof r === 'object' && r) out.stats = r;
     return out;
   }
+  // ---- lightmap bakes (rt_bake_points, rt_bake_irradiance): the covered texels of TLAS-order instance `inst`'s width x height
+  // atlas as gather points, by the texel rule of include/mi355rt.h.  opts: {tMax = 1e30, padBase = 0, atlasUv = null (a
+  // Float32Array of 2 floats per scene vertex overriding the scene's uvs), owner = false}.  Result: {n, points (8 words per
+  // point), texels (Uint32Array, ascending)} and with owner the Int32Array owner map (global triangle index, -1 = uncovered).
+  bakePoints(inst, width, height, opts = {}) {
+    const texels = new Uint32Array(width * height), points = new Float32Array(width * height * 8);
+    const owner = opts.owner ? new Int32Array(width * height) : null;
+    const n = native.rtBakePoints(this._ctx, inst >>> 0, width >>> 0, height >>> 0, (opts.padBase || 0) >>> 0,
+      opts.tMax === undefined ? 1e30 : opts.tMax, opts.atlasUv || null, points, texels, owner);
+    this._check(n, 'bakePoints');
+    const out = { n, points: points.subarray(0, n * 8), texels: texels.subarray(0, n) };
+    if (owner) out.owner = owner;
+    return out;
+  }
+  // The whole bake: points, the irradiance gather on them, scatter.  opts as above plus {seed = 0, stats = false}.  Result:
+  // {data (4 floats per texel {r, g, b, hitFraction}, row 0 first; uncovered texels are {0, 0, 0, -1}), width, height, covered}
+  // and with stats the gather's .stats.  rgb is E / pi: multiply by pi * albedo for the outgoing radiance of a Lambert texel.
+  bakeIrradiance(inst, width, height, maxDepth, spp, opts = {}) {
+    const data = new Float32Array(width * height * 4);
+    const r = native.rtBakeIrradiance(this._ctx, inst >>> 0, width >>> 0, height >>> 0, (opts.padBase || 0) >>> 0,
+      opts.tMax === undefined ? 1e30 : opts.tMax, opts.atlasUv || null, maxDepth >>> 0, spp >>> 0, (opts.seed || 0) >>> 0, data,
+      !!opts.stats);
+    if (typeof r === 'number') this._check(r, 'bakeIrradiance');
+    const out = { data, width, height, covered: r.covered };
+    if (r.stats) out.stats = r.stats;
+    return out;
+  }
   destroy() { if (this._ctx) { native.rtDestroy(this._ctx); this._ctx = null; } }
 }
 
@@ -332,4 +359,4 @@ class LiveLoop {
   }
 }
 
-module.exports = { WebGPURenderer, WorldBridge, LiveLoop, syncWorld, native };
+module.exports = { WebGPURenderer, WorldBridge, LiveLoop, syncWorld, encodePng, native };

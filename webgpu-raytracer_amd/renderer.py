@@ -197,6 +197,10 @@ def load_library(path=None):
         "rt_gather_irradiance": (i32, [vp, vp, u32, u32, u32, u32, vp, vp]),
         "rt_gather_irradiance_device": (i32, [vp, vp, u32, u32, u32, u32, vp]),
         "rt_irradiance_gather_stats": (i32, [vp, vp]),
+        # lightmap bakes
+        "rt_bake_points": (i32, [vp, vp, vp, u32, vp, vp, u32, vp, vp]),
+        "rt_bake_points_device": (i32, [vp, vp, vp, vp, vp, u32, vp, vp]),
+        "rt_bake_irradiance": (i32, [vp, vp, vp, u32, u32, u32, u32, vp, vp, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(L, name)  # AttributeError here = header/library mismatch
@@ -220,7 +224,8 @@ EXPORTED_SYMBOLS = (
     "rt_unpack_stripes rt_gather_stripes rt_read_display "
     "rt_trace_rays rt_trace_rays_device rt_ray_query_stats "
     "rt_trace_radiance rt_trace_radiance_device rt_radiance_query_stats "
-    "rt_gather_irradiance rt_gather_irradiance_device rt_irradiance_gather_stats").split()
+    "rt_gather_irradiance rt_gather_irradiance_device rt_irradiance_gather_stats "
+    "rt_bake_points rt_bake_points_device rt_bake_irradiance").split()
 
 
 # ---- ray queries: mirrors of rt_ray / rt_ray_hit / rt_ray_stats (include/mi355rt_layout.h)
@@ -261,6 +266,12 @@ class RtRadianceStats(ctypes.Structure):
 RADIANCE_DTYPE = np.dtype([("rgb", np.float32, (3,)), ("t", np.float32)])
 # irradiance gathers: mirror of rt_irradiance; their stats are an RtRadianceStats (rays = points)
 IRRADIANCE_DTYPE = np.dtype([("rgb", np.float32, (3,)), ("hit_fraction", np.float32)])
+
+
+# lightmap bakes: mirror of rt_bake_desc
+class RtBakeDesc(ctypes.Structure):
+    _fields_ = [("inst", ctypes.c_uint32), ("width", ctypes.c_uint32), ("height", ctypes.c_uint32), ("pad_base", ctypes.c_uint32),
+                ("t_max", ctypes.c_float), ("reserved", ctypes.c_uint32 * 3)]
 
 
 def _ptr(a):
@@ -590,6 +601,68 @@ class WebGPURenderer:
         st = RtRadianceStats()
         self._check(self.L.rt_irradiance_gather_stats(self.ctx, ctypes.addressof(st)), "irradianceGatherStats")
         return st.as_dict()
+
+    # ---- lightmap bakes: the texels of an instance's UV atlas as gather points (rt_bake_points) ----
+    @staticmethod
+    def _bake_desc(inst, width, height, t_max, pad_base):
+        d = RtBakeDesc()
+        d.inst, d.width, d.height, d.pad_base, d.t_max = int(inst), int(width), int(height), int(pad_base), float(t_max)
+        return d
+
+    @staticmethod
+    def _atlas_uv(atlas_uv):
+        if atlas_uv is None:
+            return None, None, 0
+        uv = np.ascontiguousarray(atlas_uv, dtype=np.float32).reshape(-1, 2)
+        return uv, _ptr(uv), uv.shape[0]
+
+    def bakePoints(self, inst, width, height, t_max=1e30, pad_base=0, atlas_uv=None, owner=False, cap=None):
+        """The gather points of the covered texels of TLAS-order instance `inst`'s width x height atlas, by the texel rule
+        of include/mi355rt.h: (points (n, 8) float32 in the rt_gather_point layout, pad = pad_base + texel index; texels
+        (n,) uint32, ascending) - and with owner=True a third item, the (height, width) int32 owner map (global triangle
+        index, -1 = uncovered).  atlas_uv: (vertex_count, 2) float32 override UVs of the whole scene, None = the scene's.
+        cap: at most that many records are written (the first ones); the count n is then returned as a last extra item."""
+        d = self._bake_desc(inst, width, height, t_max, pad_base)
+        uv, uv_ptr, n_uv = self._atlas_uv(atlas_uv)
+        room = int(width) * int(height) if cap is None else int(cap)
+        points = np.empty((room, 8), np.float32)
+        texels = np.empty(room, np.uint32)
+        own = np.empty((int(height), int(width)), np.int32) if owner else None
+        n = ctypes.c_uint32(0)
+        self._check(self.L.rt_bake_points(self.ctx, ctypes.addressof(d), uv_ptr, n_uv, _ptr(points) if room else None,
+                                          _ptr(texels) if room else None, room, ctypes.addressof(n),
+                                          _ptr(own) if owner else None), "bakePoints")
+        got = min(n.value, room)
+        out = (points[:got], texels[:got]) + ((own,) if owner else ())
+        return out + (n.value,) if cap is not None else out
+
+    def bakePointsDevice(self, inst, width, height, points_ptr, texels_ptr, cap, count_ptr, t_max=1e30, pad_base=0,
+                         atlas_uv_ptr=None, owner_ptr=None):
+        """Enqueue the point pass on device arrays (cap rt_gather_point at points_ptr, cap u32 at texels_ptr, one u32 at
+        count_ptr, optionally width * height u32 at owner_ptr and 2 f32 per scene vertex at atlas_uv_ptr; e.g.
+        tensor.data_ptr()) on the context's stream; no host synchronisation.  EVERY pointer, the single count word included,
+        must be 16-byte aligned (a fresh tensor is; a slice of one may not be) and lie on the context's device, else
+        RT_ERR_INVALID."""
+        d = self._bake_desc(inst, width, height, t_max, pad_base)
+        self._check(self.L.rt_bake_points_device(self.ctx, ctypes.addressof(d), ctypes.c_void_p(atlas_uv_ptr or 0),
+                                                 ctypes.c_void_p(points_ptr or 0), ctypes.c_void_p(texels_ptr or 0), int(cap),
+                                                 ctypes.c_void_p(count_ptr or 0), ctypes.c_void_p(owner_ptr or 0)),
+                    "bakePointsDevice")
+
+    def bakeIrradiance(self, inst, width, height, max_depth, spp, seed=0, t_max=1e30, pad_base=0, atlas_uv=None, stats=False):
+        """The whole bake: points, the irradiance gather on them, scatter.  Returns the (height, width) IRRADIANCE_DTYPE
+        atlas - texel texels[j] holds what gatherIrradiance returns for points[j] (E / pi: multiply by pi * albedo for a
+        Lambert texel's outgoing radiance), uncovered texels are {0, 0, 0, -1} - and with stats=True the triple (atlas,
+        number of covered texels, stats dict of the gather)."""
+        d = self._bake_desc(inst, width, height, t_max, pad_base)
+        uv, uv_ptr, n_uv = self._atlas_uv(atlas_uv)
+        out = np.empty((int(height), int(width)), dtype=IRRADIANCE_DTYPE)
+        n = ctypes.c_uint32(0)
+        st = RtRadianceStats()
+        self._check(self.L.rt_bake_irradiance(self.ctx, ctypes.addressof(d), uv_ptr, n_uv, int(max_depth), int(spp),
+                                              int(seed) & 0xffffffff, _ptr(out), ctypes.addressof(n),
+                                              ctypes.addressof(st) if stats else None), "bakeIrradiance")
+        return (out, n.value, st.as_dict()) if stats else out
 
     # ---- the sharded image (rt_dist_*): this context as one rank of `world` ----
     def distInit(self, rank, world, stripe_rows=8, unique_id=None):
