@@ -450,7 +450,7 @@ int rt_irradiance_gather_stats(rt_ctx* ctx, rt_radiance_stats* out);
  *               j = 0 .. n-1.  The optional owner map holds W * H i32: the owner's global triangle index, -1 for none.
  * The rule has no run-time freedom: two bakes of one scene give the same words, and a CPU restatement (tests/model/
  * bake_model.cpp) gives them too.  Out of scope: chart packing, dilation of uncovered texels (a host one-liner on the owner
- * map), conservative rasterisation, several instances per call.
+ * map), conservative rasterisation.  Several instances per call: atlas bakes, below.
  * Limits, all RT_ERR_INVALID: a NULL descriptor, reserved != 0, W or H == 0, W * H > 2^24, pad_base + W * H > 2^31 (the
  * gather's pad rule), inst >= the instance count, a NULL output that is needed.  Without a valid scene: RT_ERR_NOT_READY;
  * also when the scene has no draw command for every instance (rt_upload(RT_KIND_DRAW_COMMANDS) was never called).
@@ -479,6 +479,50 @@ int rt_bake_points_device(rt_ctx* ctx, const rt_bake_desc* desc, const void* dev
                           uint32_t cap, void* dev_count, void* dev_owner);
 int rt_bake_irradiance(rt_ctx* ctx, const rt_bake_desc* desc, const float* atlas_uv, uint32_t n_uv_vertices, uint32_t max_depth,
                        uint32_t spp, uint32_t seed, rt_irradiance* atlas_out, uint32_t* n_covered_out, rt_radiance_stats* stats);
+
+/* ---- atlas bakes: "the lightmap of these instances, each in its rectangle of one atlas", in one call ----
+ * Instances of one geometry share their triangles and vertices, hence their UV chart: what tells their texels apart is a
+ * rectangle of the atlas per instance.  An atlas bake is one point pass, one gather and one scatter over a list of them.
+ *
+ * THE ATLAS RULE.  Inputs: an rt_bake_atlas_desc d {width W, height H, pad_base, t_max, n_entries} and n_entries records
+ * rt_bake_rect {inst, x, y, width w, height h} (mi355rt_layout.h), entry e being the e-th; optionally atlas_uv as above.
+ *   local bake  of entry e: by definition THE TEXEL RULE for the rt_bake_desc {inst, w, h}: texel-space vertices are uv *
+ *               ((float)w, (float)h), local texels (lx, ly) with 0 <= lx < w, 0 <= ly < h and centres + 0.5f; coverage,
+ *               owner triangle k and point as written there.  Nothing is offset in float: a chart that runs outside [0, 1]
+ *               is clipped to its rectangle by construction and never reaches a neighbour's texels.
+ *   placement   entry e covers atlas texel (X, Y) = (x + lx, y + ly) with triangle k when its local bake covers (lx, ly)
+ *               with k.  The atlas texel has index Y * W + X.
+ *   owner       of an atlas texel: the lexicographically LOWEST (e, k) that covers it, or none.  This settles overlapping
+ *               rectangles, one instance listed twice, and everything the lowest-k sentence settles.
+ *   point       of an atlas texel with owner (e, k): the local rule's point for (lx, ly), k and the entry's instance -
+ *               position and normal as there, t_max = d.t_max - with pad = d.pad_base + Y * W + X.
+ *   output      the covered atlas texels in ASCENDING ATLAS TEXEL INDEX, compacted: points[j] and texels[j].  The optional
+ *               owner map holds W * H pairs {i32 entry, i32 triangle}, {-1, -1} for none.
+ * Two identities follow.  (A) One entry {inst, 0, 0, W, H} gives, word for word with the pads, what rt_bake_points gives for
+ * {inst, W, H, pad_base, t_max}.  (B) Any atlas bake is the composition of its entries' single-instance bakes:
+ * rt_bake_points per entry, placed at the rectangle, the lowest entry winning, the pads re-based.
+ * Out of scope: chart packing (the caller chooses the rectangles), a t_max per entry, dilation, a device form of the whole
+ * bake.
+ * Limits, all RT_ERR_INVALID: a NULL descriptor or NULL entries, reserved != 0 (descriptor or any entry), n_entries == 0 or
+ * > 65536, W or H == 0, W * H > 2^24, pad_base + W * H > 2^31, any w or h == 0, any rectangle not inside the atlas (x + w
+ * <= W and y + h <= H, taken without u32 overflow), any inst >= the instance count, and what the bake entries above say about
+ * NULL outputs and n_uv_vertices.  RT_ERR_NOT_READY as for a bake.  Messages begin with "bake atlas:".
+ * The entries are a HOST array in all three forms, and the library has copied them when it returns.  cap, n_out, the stats,
+ * {+0, +0, +0, -1.0f} in uncovered texels and "leaves the renderer as it was" are as in the three entries above.
+ *   rt_bake_atlas_points         blocking, one fence.  owner_out: 2 i32 per atlas texel {entry, triangle}, or NULL.
+ *   rt_bake_atlas_points_device  device-accessible arrays as in rt_bake_points_device; dev_owner: W * H u64, (entry << 32) |
+ *                                triangle, all ones for none (the map as the kernels keep it), or NULL.  Only enqueues on
+ *                                the context's stream: the entries go through a pinned staging buffer of the bake's own.
+ *   rt_bake_atlas_irradiance     the whole bake: ONE gather over all entries' points.  atlas_out[texels[j]] is, bit for bit,
+ *                                what rt_gather_irradiance returns for points[j].  One host read of the count. */
+int rt_bake_atlas_points(rt_ctx* ctx, const rt_bake_atlas_desc* desc, const rt_bake_rect* entries, const float* atlas_uv,
+                         uint32_t n_uv_vertices, rt_gather_point* points_out, uint32_t* texels_out, uint32_t cap,
+                         uint32_t* n_out, int32_t* owner_out);
+int rt_bake_atlas_points_device(rt_ctx* ctx, const rt_bake_atlas_desc* desc, const rt_bake_rect* entries, const void* dev_atlas_uv,
+                                void* dev_points, void* dev_texels, uint32_t cap, void* dev_count, void* dev_owner);
+int rt_bake_atlas_irradiance(rt_ctx* ctx, const rt_bake_atlas_desc* desc, const rt_bake_rect* entries, const float* atlas_uv,
+                             uint32_t n_uv_vertices, uint32_t max_depth, uint32_t spp, uint32_t seed, rt_irradiance* atlas_out,
+                             uint32_t* n_covered_out, rt_radiance_stats* stats);
 
 /* ---- the sharded image: one picture rendered by `world` contexts ("ranks"), assembled on rank 0 ----
  * Rank k owns the image rows y with (y / stripe_rows) % world == k and traces only those (rt_set_stripes).  Its COMPACT

@@ -164,10 +164,26 @@ typedef struct rt_bake_desc { /* 32 B */
   float t_max;                /* of every point */
   uint32_t reserved[3];       /* 0 */
 } rt_bake_desc;
+/* ---- atlas bakes (rt_bake_atlas_points, mi355rt.h): one atlas, a list of (instance, rectangle) entries ---- */
+typedef struct rt_bake_atlas_desc { /* 32 B */
+  uint32_t width, height;     /* of the atlas, in texels: both >= 1, width * height <= 2^24 */
+  uint32_t pad_base;          /* pad of a point = pad_base + atlas texel index; pad_base + width * height <= 2^31 */
+  float t_max;                /* of every point */
+  uint32_t n_entries;         /* 1 .. 65536 */
+  uint32_t reserved[3];       /* 0 */
+} rt_bake_atlas_desc;
+typedef struct rt_bake_rect { /* 32 B: two 16-byte loads of k_atlas_owner / k_atlas_emit */
+  uint32_t inst;              /* TLAS-order instance index */
+  uint32_t x, y;              /* the rectangle's first texel in the atlas */
+  uint32_t width, height;     /* of the rectangle = of the entry's local bake: both >= 1, inside the atlas */
+  uint32_t reserved[3];       /* 0 */
+} rt_bake_rect;
 
 #ifdef __cplusplus
 }
 static_assert(sizeof(rt_bake_desc) == 32, "rt_bake_desc is 32 bytes");
+static_assert(sizeof(rt_bake_atlas_desc) == 32, "rt_bake_atlas_desc is 32 bytes");
+static_assert(sizeof(rt_bake_rect) == 32, "rt_bake_rect is 32 bytes");
 static_assert(sizeof(rt_gather_point) == 32, "rt_gather_point is 32 bytes");
 static_assert(__builtin_offsetof(rt_gather_point, t_max) == 12 && __builtin_offsetof(rt_gather_point, normal) == 16 &&
                   __builtin_offsetof(rt_gather_point, pad) == 28,

@@ -63,12 +63,22 @@ struct QueryState {
   bool timed = false;               // the last query recorded its events
 };
 
-// What lightmap bakes (rt_bake_points, rt_bake_irradiance) keep between calls: their staging arrays, kept and grown.
+// What lightmap bakes (rt_bake_points, rt_bake_irradiance and their atlas forms) keep between calls: their staging arrays,
+// kept and grown.
 struct BakeState {
   DeviceBuffer uv;                  // the caller's override atlas UVs (host entries)
   DeviceBuffer owner, blocks, count;   // owner map, per-workgroup counts / prefixes, the device count
   DeviceBuffer points, texels;      // the compacted points and their texel indices
   DeviceBuffer results, atlas;      // rt_bake_irradiance: the gather's results, the scattered atlas
+  DeviceBuffer entries, items, owner64;   // atlas bakes: the rt_bake_rect list, the item counts / prefixes, the 64-bit owner map
+  // pinned staging ring of the entry lists: the copy to `entries` is truly asynchronous and its source outlives it (buffer k
+  // is reused only after the event recorded behind its copy has completed)
+  static constexpr int kEntryRing = 4;
+  void* ring[kEntryRing] = {};
+  size_t ring_bytes[kEntryRing] = {};
+  hipEvent_t ring_ev[kEntryRing] = {};
+  bool ring_used[kEntryRing] = {};
+  int ring_next = 0;
 };
 
 }  // namespace
@@ -938,7 +948,7 @@ void rt_destroy(rt_ctx* c) {
                          &c->rq.in, &c->rq.out, &c->rq.counters, &c->rd.in, &c->rd.out, &c->rd.counters,
                          &c->gi.in, &c->gi.out, &c->gi.counters,
                          &c->bk.uv, &c->bk.owner, &c->bk.blocks, &c->bk.count, &c->bk.points, &c->bk.texels, &c->bk.results,
-                         &c->bk.atlas,
+                         &c->bk.atlas, &c->bk.entries, &c->bk.items, &c->bk.owner64,
                          &c->tex_staging, &c->bv_in, &c->bv_tri, &c->bv_order, &c->bv_nodes, &c->bv_out,
                          &c->bv_counters, &c->bv_big, &c->val_roots, &c->val_bad, &c->tnodes, &c->node_key, &c->node_newidx,
                          &c->inst_root, &c->root_w, &c->treelet_work, &c->pairs, &c->pair_of, &c->pair_parent, &c->root_rec,
@@ -959,6 +969,10 @@ void rt_destroy(rt_ctx* c) {
     (void)hipEventDestroy(p.b);
   }
   if (c->bv_pinned) (void)hipHostFree(c->bv_pinned);
+  for (int k = 0; k < BakeState::kEntryRing; k++) {
+    if (c->bk.ring[k]) (void)hipHostFree(c->bk.ring[k]);
+    if (c->bk.ring_ev[k]) (void)hipEventDestroy(c->bk.ring_ev[k]);
+  }
   if (c->slot_ring) (void)hipHostFree(c->slot_ring);
   for (int k = 0; k < rt_ctx::kSlotRing; k++)
     if (c->slot_ring_ev[k]) (void)hipEventDestroy(c->slot_ring_ev[k]);
@@ -2209,29 +2223,41 @@ int rt_gather_irradiance(rt_ctx* c, const rt_gather_point* points, uint32_t n, u
 }
 
 // ---- lightmap bakes: the texel rule of mi355rt.h as four launches (k_bake.hip.h), then the gather path and the scatter
+// width, height and pad_base of a bake or an atlas bake
+static int bake_size_ok(rt_ctx* c, const std::string& w, uint32_t width, uint32_t height, uint32_t pad_base) {
+  if (width == 0 || height == 0) return fail(c, RT_ERR_INVALID, w + ": width and height must be >= 1");
+  const uint64_t texels = (uint64_t)width * height;
+  if (texels > (1ull << 24)) return fail(c, RT_ERR_INVALID, w + ": width * height must be <= 2^24");
+  if ((uint64_t)pad_base + texels > (1ull << 31)) return fail(c, RT_ERR_INVALID, w + ": pad_base + width * height must be <= 2^31");
+  return RT_OK;
+}
 static int bake_desc_ok(rt_ctx* c, const rt_bake_desc* d) {
   if (!d) return fail(c, RT_ERR_INVALID, "bake: NULL descriptor");
   if (d->reserved[0] | d->reserved[1] | d->reserved[2]) return fail(c, RT_ERR_INVALID, "bake: reserved words must be 0");
-  if (d->width == 0 || d->height == 0) return fail(c, RT_ERR_INVALID, "bake: width and height must be >= 1");
-  const uint64_t texels = (uint64_t)d->width * d->height;
-  if (texels > (1ull << 24)) return fail(c, RT_ERR_INVALID, "bake: width * height must be <= 2^24");
-  if ((uint64_t)d->pad_base + texels > (1ull << 31)) return fail(c, RT_ERR_INVALID, "bake: pad_base + width * height must be <= 2^31");
-  return RT_OK;
+  return bake_size_ok(c, "bake", d->width, d->height, d->pad_base);
 }
-// the scene is there, has a draw command for every instance, and d->inst is one of them
-static int bake_scene_ready(rt_ctx* c, const rt_bake_desc* d, bool lights) {
-  const int r = query_scene_ready(c, "bake", lights);
+// the scene is there and has a draw command for every instance
+static int bake_scene_ready(rt_ctx* c, const char* what, bool lights) {
+  const int r = query_scene_ready(c, what, lights);
   if (r < 0) return r;
   if (!c->draw_commands.ptr || c->draw_commands.size < (size_t)c->n_instances * 16)
-    return fail(c, RT_ERR_NOT_READY, "bake: the scene has no draw command for every instance (upload RT_KIND_DRAW_COMMANDS)");
+    return fail(c, RT_ERR_NOT_READY,
+                std::string(what) + ": the scene has no draw command for every instance (upload RT_KIND_DRAW_COMMANDS)");
+  return RT_OK;
+}
+// ... and d->inst is one of them
+static int bake_scene_ready(rt_ctx* c, const rt_bake_desc* d, bool lights) {
+  const int r = bake_scene_ready(c, "bake", lights);
+  if (r < 0) return r;
   if (d->inst >= c->n_instances) return fail(c, RT_ERR_INVALID, "bake: inst is not an instance of the scene");
   return RT_OK;
 }
 // the override UVs of a host entry -> the bake's staging array; *d_uv = that, or null for the scene's
-static int bake_stage_uv(rt_ctx* c, const float* atlas_uv, uint32_t n_uv_vertices, const void** d_uv) {
+static int bake_stage_uv(rt_ctx* c, const char* what, const float* atlas_uv, uint32_t n_uv_vertices, const void** d_uv) {
   *d_uv = nullptr;
   if (!atlas_uv) return RT_OK;
-  if (n_uv_vertices != c->n_verts) return fail(c, RT_ERR_INVALID, "bake: n_uv_vertices must be the scene's vertex count");
+  if (n_uv_vertices != c->n_verts)
+    return fail(c, RT_ERR_INVALID, std::string(what) + ": n_uv_vertices must be the scene's vertex count");
   const int r = ensure_buffer(c, c->bk.uv, (size_t)n_uv_vertices * 8, true);
   if (r < 0) return r;
   HIP_TRY(c, hipMemcpyAsync(c->bk.uv.ptr, atlas_uv, (size_t)n_uv_vertices * 8, hipMemcpyHostToDevice, c->stream));
@@ -2288,6 +2314,75 @@ static int bake_emit(rt_ctx* c, rtk::BakeArgs& A, void* d_points, void* d_texels
   return RT_OK;
 }
 
+// The host entries of the point pass (rt_bake_points, rt_bake_atlas_points): the staging arrays for m records; front()
+// enqueues the owner pass, the counts and their scan with the count going to the bake's own word, emit(m) the point launch
+// into the staging arrays, owner_back() the copy of the owner map towards the caller.  One fence: the count and the m staged
+// records come back together, the first min(n, cap) of them go to the caller.
+extern "C++" {
+template <class Front, class Emit, class OwnerBack>
+static int bake_points_host(rt_ctx* c, uint32_t m, rt_gather_point* points_out, uint32_t* texels_out, uint32_t* n_out, Front front,
+                            Emit emit, OwnerBack owner_back) {
+  int r;
+  if ((r = ensure_buffer(c, c->bk.count, 16, false)) < 0) return r;
+  if ((r = ensure_buffer(c, c->bk.points, (size_t)m * sizeof(rt_gather_point), true)) < 0) return r;
+  if ((r = ensure_buffer(c, c->bk.texels, (size_t)m * 4, true)) < 0) return r;
+  if ((r = front()) < 0) return r;
+  if ((r = emit(m)) < 0) return r;
+  uint32_t n = 0;
+  std::vector<rt_gather_point> points(m);
+  std::vector<uint32_t> tex(m);
+  HIP_TRY(c, hipMemcpyAsync(&n, c->bk.count.ptr, 4, hipMemcpyDeviceToHost, c->stream));
+  if (m) {
+    HIP_TRY(c, hipMemcpyAsync(points.data(), c->bk.points.ptr, (size_t)m * sizeof(rt_gather_point), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(tex.data(), c->bk.texels.ptr, (size_t)m * 4, hipMemcpyDeviceToHost, c->stream));
+  }
+  if ((r = owner_back()) < 0) return r;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  const uint32_t got = std::min(n, m);
+  if (got) {
+    std::memcpy(points_out, points.data(), (size_t)got * sizeof(rt_gather_point));
+    std::memcpy(texels_out, tex.data(), (size_t)got * 4);
+  }
+  *n_out = n;
+  return RT_OK;
+}
+}  // extern "C++"
+
+// The tail of a whole bake (rt_bake_irradiance, rt_bake_atlas_irradiance) behind its front: the one host read of the count
+// between the point pass and the gather, emit(n) for the n points, the gather on them, scatter(B) for the way back with B
+// complete but for its owner map, and the atlas to the caller.
+extern "C++" {
+template <class Emit, class Scatter>
+static int bake_gather_tail(rt_ctx* c, uint32_t texels, uint32_t max_depth, uint32_t spp, uint32_t seed, rt_irradiance* atlas_out,
+                            uint32_t* n_covered_out, rt_radiance_stats* stats, Emit emit, Scatter scatter) {
+  int r;
+  uint32_t n = 0;
+  HIP_TRY(c, hipMemcpyAsync(&n, c->bk.count.ptr, 4, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if ((r = ensure_buffer(c, c->bk.points, (size_t)n * sizeof(rt_gather_point), true)) < 0) return r;
+  if ((r = ensure_buffer(c, c->bk.texels, (size_t)n * 4, true)) < 0) return r;
+  if ((r = ensure_buffer(c, c->bk.results, (size_t)n * sizeof(rt_irradiance), true)) < 0) return r;
+  if ((r = ensure_buffer(c, c->bk.atlas, (size_t)texels * sizeof(rt_irradiance), true)) < 0) return r;
+  if ((r = emit(n)) < 0) return r;
+  if ((r = path_query_device(c, pq_gather, c->bk.points.ptr, n, max_depth, spp, seed, c->bk.results.ptr, stats != nullptr)) < 0)
+    return r;
+  rtk::BakeScatterArgs B;
+  B.owner = nullptr;
+  B.texels = (const uint32_t*)c->bk.texels.ptr;
+  B.results = (const float4*)c->bk.results.ptr;
+  B.atlas = (float4*)c->bk.atlas.ptr;
+  B.n_texels = texels;
+  B.n = n;
+  scatter(B);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipMemcpyAsync(atlas_out, c->bk.atlas.ptr, (size_t)texels * sizeof(rt_irradiance), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (n_covered_out) *n_covered_out = n;
+  if (stats) return path_query_stats(c, pq_gather, stats);
+  return RT_OK;
+}
+}  // extern "C++"
+
 int rt_bake_points_device(rt_ctx* c, const rt_bake_desc* d, const void* dev_atlas_uv, void* dev_points, void* dev_texels,
                           uint32_t cap, void* dev_count, void* dev_owner) {
   if (!c) return RT_ERR_INVALID;
@@ -2311,32 +2406,16 @@ int rt_bake_points(rt_ctx* c, const rt_bake_desc* d, const float* atlas_uv, uint
   if (!n_out || (cap != 0 && (!points_out || !texels_out))) return fail(c, RT_ERR_INVALID, "bake: NULL array");
   if ((r = bake_scene_ready(c, d, false)) < 0) return r;
   const void* d_uv;
-  if ((r = bake_stage_uv(c, atlas_uv, n_uv_vertices, &d_uv)) < 0) return r;
-  const uint32_t texels = d->width * d->height, m = std::min(cap, texels);
-  if ((r = ensure_buffer(c, c->bk.count, 16, false)) < 0) return r;
-  if ((r = ensure_buffer(c, c->bk.points, (size_t)m * sizeof(rt_gather_point), true)) < 0) return r;
-  if ((r = ensure_buffer(c, c->bk.texels, (size_t)m * 4, true)) < 0) return r;
+  if ((r = bake_stage_uv(c, "bake", atlas_uv, n_uv_vertices, &d_uv)) < 0) return r;
+  const uint32_t texels = d->width * d->height;
   rtk::BakeArgs A;
-  if ((r = bake_front(c, d, d_uv, nullptr, c->bk.count.ptr, A)) < 0) return r;
-  if ((r = bake_emit(c, A, c->bk.points.ptr, c->bk.texels.ptr, m)) < 0) return r;
-  // one fence: the count and the m staged records come back together, the first min(n, cap) of them go to the caller
-  uint32_t n = 0;
-  std::vector<rt_gather_point> points(m);
-  std::vector<uint32_t> tex(m);
-  HIP_TRY(c, hipMemcpyAsync(&n, c->bk.count.ptr, 4, hipMemcpyDeviceToHost, c->stream));
-  if (m) {
-    HIP_TRY(c, hipMemcpyAsync(points.data(), c->bk.points.ptr, (size_t)m * sizeof(rt_gather_point), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(tex.data(), c->bk.texels.ptr, (size_t)m * 4, hipMemcpyDeviceToHost, c->stream));
-  }
-  if (owner_out) HIP_TRY(c, hipMemcpyAsync(owner_out, c->bk.owner.ptr, (size_t)texels * 4, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  const uint32_t got = std::min(n, m);
-  if (got) {
-    std::memcpy(points_out, points.data(), (size_t)got * sizeof(rt_gather_point));
-    std::memcpy(texels_out, tex.data(), (size_t)got * 4);
-  }
-  *n_out = n;
-  return RT_OK;
+  return bake_points_host(
+      c, std::min(cap, texels), points_out, texels_out, n_out, [&] { return bake_front(c, d, d_uv, nullptr, c->bk.count.ptr, A); },
+      [&](uint32_t m) { return bake_emit(c, A, c->bk.points.ptr, c->bk.texels.ptr, m); },
+      [&] {
+        if (owner_out) HIP_TRY(c, hipMemcpyAsync(owner_out, c->bk.owner.ptr, (size_t)texels * 4, hipMemcpyDeviceToHost, c->stream));
+        return (int)RT_OK;
+      });
 }
 
 int rt_bake_irradiance(rt_ctx* c, const rt_bake_desc* d, const float* atlas_uv, uint32_t n_uv_vertices, uint32_t max_depth,
@@ -2349,35 +2428,198 @@ int rt_bake_irradiance(rt_ctx* c, const rt_bake_desc* d, const float* atlas_uv, 
   if ((r = path_query_args_ok(c, pq_gather, texels, spp)) < 0) return r;
   if ((r = bake_scene_ready(c, d, true)) < 0) return r;
   const void* d_uv;
-  if ((r = bake_stage_uv(c, atlas_uv, n_uv_vertices, &d_uv)) < 0) return r;
+  if ((r = bake_stage_uv(c, "bake", atlas_uv, n_uv_vertices, &d_uv)) < 0) return r;
   if ((r = ensure_buffer(c, c->bk.count, 16, false)) < 0) return r;
   rtk::BakeArgs A;
   if ((r = bake_front(c, d, d_uv, nullptr, c->bk.count.ptr, A)) < 0) return r;
-  // the one host read between the point pass and the gather: how many points there are
-  uint32_t n = 0;
-  HIP_TRY(c, hipMemcpyAsync(&n, c->bk.count.ptr, 4, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  if ((r = ensure_buffer(c, c->bk.points, (size_t)n * sizeof(rt_gather_point), true)) < 0) return r;
-  if ((r = ensure_buffer(c, c->bk.texels, (size_t)n * 4, true)) < 0) return r;
-  if ((r = ensure_buffer(c, c->bk.results, (size_t)n * sizeof(rt_irradiance), true)) < 0) return r;
-  if ((r = ensure_buffer(c, c->bk.atlas, (size_t)texels * sizeof(rt_irradiance), true)) < 0) return r;
-  if ((r = bake_emit(c, A, c->bk.points.ptr, c->bk.texels.ptr, n)) < 0) return r;
-  if ((r = path_query_device(c, pq_gather, c->bk.points.ptr, n, max_depth, spp, seed, c->bk.results.ptr, stats != nullptr)) < 0)
-    return r;
-  rtk::BakeScatterArgs B;
-  B.owner = A.owner;
-  B.texels = (const uint32_t*)c->bk.texels.ptr;
-  B.results = (const float4*)c->bk.results.ptr;
-  B.atlas = (float4*)c->bk.atlas.ptr;
-  B.n_texels = texels;
-  B.n = n;
-  hipLaunchKernelGGL(rtk::k_bake_scatter, dim3(A.n_blocks), dim3(256), 0, c->stream, B);
-  HIP_TRY(c, hipGetLastError());
-  HIP_TRY(c, hipMemcpyAsync(atlas_out, c->bk.atlas.ptr, (size_t)texels * sizeof(rt_irradiance), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  if (n_covered_out) *n_covered_out = n;
-  if (stats) return path_query_stats(c, pq_gather, stats);
+  return bake_gather_tail(
+      c, texels, max_depth, spp, seed, atlas_out, n_covered_out, stats,
+      [&](uint32_t n) { return bake_emit(c, A, c->bk.points.ptr, c->bk.texels.ptr, n); },
+      [&](rtk::BakeScatterArgs& B) {
+        B.owner = A.owner;
+        hipLaunchKernelGGL(rtk::k_bake_scatter, dim3(A.n_blocks), dim3(256), 0, c->stream, B);
+      });
+}
+
+// ---- atlas bakes: a list of (instance, rectangle) entries into one atlas (mi355rt.h "atlas bakes"; k_atlas_* of k_bake.hip.h)
+static const char* const kAtlas = "bake atlas";
+// everything the limits say about the descriptor and the entries that needs no scene
+static int bake_atlas_desc_ok(rt_ctx* c, const rt_bake_atlas_desc* d, const rt_bake_rect* entries) {
+  const std::string w(kAtlas);
+  if (!d) return fail(c, RT_ERR_INVALID, w + ": NULL descriptor");
+  if (!entries) return fail(c, RT_ERR_INVALID, w + ": NULL entries");
+  if (d->reserved[0] | d->reserved[1] | d->reserved[2]) return fail(c, RT_ERR_INVALID, w + ": reserved words must be 0");
+  if (d->n_entries == 0 || d->n_entries > 65536) return fail(c, RT_ERR_INVALID, w + ": n_entries must be 1 .. 65536");
+  const int r = bake_size_ok(c, w, d->width, d->height, d->pad_base);
+  if (r < 0) return r;
+  for (uint32_t e = 0; e < d->n_entries; e++) {
+    const rt_bake_rect& q = entries[e];
+    const std::string at = w + ": entry " + std::to_string(e);
+    if (q.reserved[0] | q.reserved[1] | q.reserved[2]) return fail(c, RT_ERR_INVALID, at + ": reserved words must be 0");
+    if (q.width == 0 || q.height == 0) return fail(c, RT_ERR_INVALID, at + ": width and height must be >= 1");
+    if ((uint64_t)q.x + q.width > d->width || (uint64_t)q.y + q.height > d->height)
+      return fail(c, RT_ERR_INVALID, at + ": the rectangle is not inside the atlas");
+  }
   return RT_OK;
+}
+// the scene is there, has a draw command for every instance, and every entry's inst is one of them
+static int bake_atlas_scene_ready(rt_ctx* c, const rt_bake_atlas_desc* d, const rt_bake_rect* entries, bool lights) {
+  const int r = bake_scene_ready(c, kAtlas, lights);
+  if (r < 0) return r;
+  for (uint32_t e = 0; e < d->n_entries; e++)
+    if (entries[e].inst >= c->n_instances)
+      return fail(c, RT_ERR_INVALID, std::string(kAtlas) + ": entry " + std::to_string(e) + ": inst is not an instance of the scene");
+  return RT_OK;
+}
+// The entries -> the bake's device array, through a pinned staging buffer of the bake's own: the caller's array is free when
+// this returns and nothing waits for the stream - unless all kEntryRing buffers are still in flight, when the oldest copy is
+// waited for.
+static int bake_atlas_stage_entries(rt_ctx* c, const rt_bake_rect* entries, uint32_t n) {
+  BakeState& k = c->bk;
+  const size_t bytes = (size_t)n * sizeof(rt_bake_rect);
+  int r = ensure_buffer(c, k.entries, bytes, true);
+  if (r < 0) return r;
+  const int slot = k.ring_next;
+  k.ring_next = (slot + 1) % BakeState::kEntryRing;
+  if (!k.ring_ev[slot]) HIP_TRY(c, hipEventCreateWithFlags(&k.ring_ev[slot], hipEventDisableTiming));
+  if (k.ring_used[slot]) HIP_TRY(c, hipEventSynchronize(k.ring_ev[slot]));
+  if (k.ring_bytes[slot] < bytes) {
+    if (k.ring[slot]) HIP_TRY(c, hipHostFree(k.ring[slot]));
+    k.ring[slot] = nullptr;
+    k.ring_bytes[slot] = 0;
+    HIP_TRY(c, hipHostMalloc(&k.ring[slot], bytes + bytes / 2, hipHostMallocDefault));
+    k.ring_bytes[slot] = bytes + bytes / 2;
+  }
+  std::memcpy(k.ring[slot], entries, bytes);
+  HIP_TRY(c, hipMemcpyAsync(k.entries.ptr, k.ring[slot], bytes, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipEventRecord(k.ring_ev[slot], c->stream));
+  k.ring_used[slot] = true;
+  return RT_OK;
+}
+// Enqueue the work list, the owner pass, the counts and their scan: afterwards d_owner (null: the bake's own map) holds the
+// 64-bit owner map, d_count the number of covered texels, and A everything the emit launch needs but its outputs.
+static int bake_atlas_front(rt_ctx* c, const rt_bake_atlas_desc* d, const rt_bake_rect* entries, const void* d_uv, void* d_owner,
+                            void* d_count, rtk::BakeAtlasArgs& A) {
+  const uint32_t texels = d->width * d->height, n = d->n_entries;
+  int r;
+  if (!d_owner) {
+    if ((r = ensure_buffer(c, c->bk.owner64, (size_t)texels * 8, true)) < 0) return r;
+    d_owner = c->bk.owner64.ptr;
+  }
+  A = rtk::BakeAtlasArgs();
+  A.n_blocks = (texels + 255u) / 256u;
+  if ((r = ensure_buffer(c, c->bk.blocks, (size_t)A.n_blocks * 4, true)) < 0) return r;
+  if ((r = ensure_buffer(c, c->bk.items, ((size_t)n + 1) * 8, true)) < 0) return r;
+  if ((r = bake_atlas_stage_entries(c, entries, n)) < 0) return r;
+  A.auv = d_uv ? (const float2*)d_uv : (const float2*)c->uv.ptr;
+  A.draw = (const uint4*)c->draw_commands.ptr;
+  A.entries = (const uint4*)c->bk.entries.ptr;
+  A.owner = (unsigned long long*)d_owner;
+  A.items = (unsigned long long*)c->bk.items.ptr;
+  A.block_count = (uint32_t*)c->bk.blocks.ptr;
+  A.W = d->width;
+  A.H = d->height;
+  A.pad_base = d->pad_base;
+  A.t_max = d->t_max;
+  A.n_tris = c->n_tris;
+  A.n_entries = n;
+  rtk::BakeArgs scan = rtk::BakeArgs();   // k_bake_scan reads these three
+  scan.block_count = A.block_count;
+  scan.n_blocks = A.n_blocks;
+  scan.count = (uint32_t*)d_count;
+  DevScene S = dev_scene(c);
+  HIP_TRY(c, hipMemsetAsync(d_owner, 0xff, (size_t)texels * 8, c->stream));   // RT_ATLAS_NONE
+  // The item total stays on the device.  What the host knows is a bound, every entry with all triangles of the scene: one wave
+  // per item of that up to what the device holds; the waves stride over the true list.
+  uint64_t bound = 0;
+  for (uint32_t e = 0; e < n; e++)
+    bound += (uint64_t)((c->n_tris + 63u) / 64u) * (((entries[e].height + 7u) / 8u + RT_BAKE_BAND_TILES - 1u) / RT_BAKE_BAND_TILES);
+  const uint32_t owner_blocks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((bound + 3) / 4, (uint64_t)c->num_cus * 8));
+  hipLaunchKernelGGL(rtk::k_atlas_items, dim3((n + 255u) / 256u), dim3(256), 0, c->stream, A);
+  hipLaunchKernelGGL(rtk::k_atlas_scan, dim3(1), dim3(RT_BAKE_SCAN_THREADS), 0, c->stream, A);
+  hipLaunchKernelGGL(rtk::k_atlas_owner, dim3(owner_blocks), dim3(256), 0, c->stream, S, A);
+  hipLaunchKernelGGL(rtk::k_atlas_count, dim3(A.n_blocks), dim3(256), 0, c->stream, A);
+  hipLaunchKernelGGL(rtk::k_bake_scan, dim3(1), dim3(RT_BAKE_SCAN_THREADS), 0, c->stream, scan);
+  HIP_TRY(c, hipGetLastError());
+  return RT_OK;
+}
+static int bake_atlas_emit(rt_ctx* c, rtk::BakeAtlasArgs& A, void* d_points, void* d_texels, uint32_t cap) {
+  if (cap == 0) return RT_OK;
+  A.points = (float4*)d_points;
+  A.texels = (uint32_t*)d_texels;
+  A.cap = cap;
+  DevScene S = dev_scene(c);
+  hipLaunchKernelGGL(rtk::k_atlas_emit, dim3(A.n_blocks), dim3(256), 0, c->stream, S, A);
+  HIP_TRY(c, hipGetLastError());
+  return RT_OK;
+}
+
+int rt_bake_atlas_points_device(rt_ctx* c, const rt_bake_atlas_desc* d, const rt_bake_rect* entries, const void* dev_atlas_uv,
+                                void* dev_points, void* dev_texels, uint32_t cap, void* dev_count, void* dev_owner) {
+  if (!c) return RT_ERR_INVALID;
+  int r = bake_atlas_desc_ok(c, d, entries);
+  if (r < 0) return r;
+  if (!dev_count) return fail(c, RT_ERR_INVALID, std::string(kAtlas) + ": NULL array");
+  if (cap != 0 && (r = query_device_arrays_ok(c, kAtlas, dev_points, dev_texels)) < 0) return r;
+  if ((r = query_device_arrays_ok(c, kAtlas, dev_count, dev_owner ? dev_owner : dev_count)) < 0) return r;
+  if (dev_atlas_uv && (r = query_device_arrays_ok(c, kAtlas, dev_atlas_uv, dev_count)) < 0) return r;
+  if ((r = bake_atlas_scene_ready(c, d, entries, false)) < 0) return r;
+  rtk::BakeAtlasArgs A;
+  if ((r = bake_atlas_front(c, d, entries, dev_atlas_uv, dev_owner, dev_count, A)) < 0) return r;
+  return bake_atlas_emit(c, A, dev_points, dev_texels, std::min(cap, d->width * d->height));
+}
+
+int rt_bake_atlas_points(rt_ctx* c, const rt_bake_atlas_desc* d, const rt_bake_rect* entries, const float* atlas_uv,
+                         uint32_t n_uv_vertices, rt_gather_point* points_out, uint32_t* texels_out, uint32_t cap, uint32_t* n_out,
+                         int32_t* owner_out) {
+  if (!c) return RT_ERR_INVALID;
+  int r = bake_atlas_desc_ok(c, d, entries);
+  if (r < 0) return r;
+  if (!n_out || (cap != 0 && (!points_out || !texels_out))) return fail(c, RT_ERR_INVALID, std::string(kAtlas) + ": NULL array");
+  if ((r = bake_atlas_scene_ready(c, d, entries, false)) < 0) return r;
+  const void* d_uv;
+  if ((r = bake_stage_uv(c, kAtlas, atlas_uv, n_uv_vertices, &d_uv)) < 0) return r;
+  const uint32_t texels = d->width * d->height;
+  rtk::BakeAtlasArgs A;
+  std::vector<uint64_t> map(owner_out ? texels : 0);
+  r = bake_points_host(
+      c, std::min(cap, texels), points_out, texels_out, n_out,
+      [&] { return bake_atlas_front(c, d, entries, d_uv, nullptr, c->bk.count.ptr, A); },
+      [&](uint32_t m) { return bake_atlas_emit(c, A, c->bk.points.ptr, c->bk.texels.ptr, m); },
+      [&] {
+        if (owner_out) HIP_TRY(c, hipMemcpyAsync(map.data(), c->bk.owner64.ptr, (size_t)texels * 8, hipMemcpyDeviceToHost, c->stream));
+        return (int)RT_OK;
+      });
+  if (r < 0) return r;
+  for (size_t i = 0; i < map.size(); i++) {   // (entry << 32) | triangle -> {entry, triangle}; all ones -> {-1, -1}
+    owner_out[2 * i] = (int32_t)(uint32_t)(map[i] >> 32);
+    owner_out[2 * i + 1] = (int32_t)(uint32_t)map[i];
+  }
+  return RT_OK;
+}
+
+int rt_bake_atlas_irradiance(rt_ctx* c, const rt_bake_atlas_desc* d, const rt_bake_rect* entries, const float* atlas_uv,
+                             uint32_t n_uv_vertices, uint32_t max_depth, uint32_t spp, uint32_t seed, rt_irradiance* atlas_out,
+                             uint32_t* n_covered_out, rt_radiance_stats* stats) {
+  if (!c) return RT_ERR_INVALID;
+  int r = bake_atlas_desc_ok(c, d, entries);
+  if (r < 0) return r;
+  if (!atlas_out) return fail(c, RT_ERR_INVALID, std::string(kAtlas) + ": NULL array");
+  const uint32_t texels = d->width * d->height;
+  if ((r = path_query_args_ok(c, pq_gather, texels, spp)) < 0) return r;
+  if ((r = bake_atlas_scene_ready(c, d, entries, true)) < 0) return r;
+  const void* d_uv;
+  if ((r = bake_stage_uv(c, kAtlas, atlas_uv, n_uv_vertices, &d_uv)) < 0) return r;
+  if ((r = ensure_buffer(c, c->bk.count, 16, false)) < 0) return r;
+  rtk::BakeAtlasArgs A;
+  if ((r = bake_atlas_front(c, d, entries, d_uv, nullptr, c->bk.count.ptr, A)) < 0) return r;
+  return bake_gather_tail(
+      c, texels, max_depth, spp, seed, atlas_out, n_covered_out, stats,
+      [&](uint32_t n) { return bake_atlas_emit(c, A, c->bk.points.ptr, c->bk.texels.ptr, n); },
+      [&](rtk::BakeScatterArgs& B) {
+        B.owner = A.owner;
+        hipLaunchKernelGGL(rtk::k_atlas_scatter, dim3(A.n_blocks), dim3(256), 0, c->stream, B);
+      });
 }
 
 // ---- the kernels of compute().  Variant 0, the one-pixel-per-lane megakernel: one tile per workgroup, no dynamic LDS.

@@ -707,6 +707,78 @@ static napi_value rtBakeIrradiance(napi_env env, napi_callback_info info) {
   return obj;
 }
 
+/* ------------------------------------------------------- atlas bakes (rt_bake_atlas_points / rt_bake_atlas_irradiance) */
+/* [width, height, padBase, tMax] and the entries (Uint32Array of 8 words per rt_bake_rect) -> descriptor; false: thrown */
+static bool bake_atlas_desc(napi_env env, const napi_value* a, size_t entry_bytes, rt_bake_atlas_desc* d) {
+  memset(d, 0, sizeof(*d));
+  d->width = get_u32(env, a[0]);
+  d->height = get_u32(env, a[1]);
+  d->pad_base = get_u32(env, a[2]);
+  d->t_max = (float)get_f64(env, a[3]);
+  if (entry_bytes % sizeof(rt_bake_rect) != 0 || entry_bytes / sizeof(rt_bake_rect) > 0xffffffffu) {
+    napi_throw_range_error(env, NULL, "atlas bake: entries must hold 8 words per entry");
+    return false;
+  }
+  d->n_entries = (uint32_t)(entry_bytes / sizeof(rt_bake_rect));
+  return true;
+}
+/* (ctx, width, height, padBase, tMax, entries: Uint32Array of 8 per entry {inst, x, y, w, h, 0, 0, 0}, atlasUv or null, points,
+ * texels, owner: Int32Array of 2 * width * height or null) -> the number of covered texels, or a negative status */
+static napi_value rtBakeAtlasPoints(napi_env env, napi_callback_info info) {
+  napi_value a[10];
+  void *entries = NULL, *uv = NULL, *points = NULL, *texels = NULL, *owner = NULL;
+  size_t ne = 0, nuv = 0, np = 0, nt = 0, no = 0;
+  if (!get_args(env, info, 10, a) || !get_bytes(env, a[5], &entries, &ne) || !get_bytes(env, a[6], &uv, &nuv) ||
+      !get_bytes(env, a[7], &points, &np) || !get_bytes(env, a[8], &texels, &nt) || !get_bytes(env, a[9], &owner, &no))
+    return NULL;
+  rt_bake_atlas_desc d;
+  if (!bake_atlas_desc(env, a + 1, ne, &d)) return NULL;
+  size_t cap = np / sizeof(rt_gather_point);
+  if (nt / 4 < cap) cap = nt / 4;
+  if (cap > 0xffffffffu || nuv % 8 != 0 || nuv / 8 > 0xffffffffu || (owner && no / 8 < (size_t)d.width * d.height)) {
+    napi_throw_range_error(env, NULL, "rtBakeAtlasPoints: atlasUv must hold 2 floats per vertex and owner 2 words per texel");
+    return NULL;
+  }
+  uint32_t n = 0;
+  const int rc = rt_bake_atlas_points((rt_ctx*)get_ptr(env, a[0]), &d, (const rt_bake_rect*)entries, (const float*)uv,
+                                      (uint32_t)(nuv / 8), (rt_gather_point*)points, (uint32_t*)texels, (uint32_t)cap, &n,
+                                      (int32_t*)owner);
+  if (rc < 0) return make_int(env, rc);
+  napi_value r;
+  napi_create_uint32(env, n, &r);
+  return r;
+}
+/* (ctx, width, height, padBase, tMax, entries, atlasUv or null, maxDepth, spp, seed, atlas: Float32Array of 4 per texel,
+ * wantStats) -> {covered, stats?}, or a negative status */
+static napi_value rtBakeAtlasIrradiance(napi_env env, napi_callback_info info) {
+  napi_value a[12];
+  void *entries = NULL, *uv = NULL, *atlas = NULL;
+  size_t ne = 0, nuv = 0, na = 0;
+  bool want_stats = false;
+  if (!get_args(env, info, 12, a) || !get_bytes(env, a[5], &entries, &ne) || !get_bytes(env, a[6], &uv, &nuv) ||
+      !get_bytes(env, a[10], &atlas, &na))
+    return NULL;
+  napi_get_value_bool(env, a[11], &want_stats);
+  rt_bake_atlas_desc d;
+  if (!bake_atlas_desc(env, a + 1, ne, &d)) return NULL;
+  if (nuv % 8 != 0 || nuv / 8 > 0xffffffffu || na / sizeof(rt_irradiance) < (size_t)d.width * d.height) {
+    napi_throw_range_error(env, NULL, "rtBakeAtlasIrradiance: atlasUv must hold 2 floats per vertex and atlas 4 floats per texel");
+    return NULL;
+  }
+  rt_radiance_stats st;
+  uint32_t n = 0;
+  const int rc = rt_bake_atlas_irradiance((rt_ctx*)get_ptr(env, a[0]), &d, (const rt_bake_rect*)entries, (const float*)uv,
+                                          (uint32_t)(nuv / 8), get_u32(env, a[7]), get_u32(env, a[8]), get_u32(env, a[9]),
+                                          (rt_irradiance*)atlas, &n, want_stats ? &st : NULL);
+  if (rc < 0) return make_int(env, rc);
+  napi_value obj, v;
+  if (napi_create_object(env, &obj) != napi_ok) return NULL;
+  napi_create_uint32(env, n, &v);
+  napi_set_named_property(env, obj, "covered", v);
+  if (want_stats) napi_set_named_property(env, obj, "stats", radiance_stats_object(env, &st));
+  return obj;
+}
+
 static napi_value Init(napi_env env, napi_value exports) {
   static const struct {
     const char* name;
@@ -725,7 +797,8 @@ static napi_value Init(napi_env env, napi_value exports) {
                {"rtGatherStripes", rtGatherStripes}, {"rtReadDisplay", rtReadDisplay}, {"rtTraceRays", rtTraceRays},
                {"rtRayQueryStats", rtRayQueryStats}, {"rtTraceRadiance", rtTraceRadiance},
                {"rtGatherIrradiance", rtGatherIrradiance}, {"rtBakePoints", rtBakePoints},
-               {"rtBakeIrradiance", rtBakeIrradiance}, {"msCreate", msCreate}, {"msDestroy", msDestroy},
+               {"rtBakeIrradiance", rtBakeIrradiance}, {"rtBakeAtlasPoints", rtBakeAtlasPoints},
+               {"rtBakeAtlasIrradiance", rtBakeAtlasIrradiance}, {"msCreate", msCreate}, {"msDestroy", msDestroy},
                {"msUpdate", msUpdate}, {"msUpdateCamera", msUpdateCamera}, {"msGet", msGet},
                {"msTextureCount", msTextureCount}, {"msTexture", msTexture},
                {"msAnimationNames", msAnimationNames}, {"msSetAnimation", msSetAnimation},

@@ -1,0 +1,71 @@
+'use strict';
+// Bake the lightmap of the first N instances of a scene into ONE atlas and write it as a PNG:
+// usage: node bake_atlas.js [scene] [N] [cell] [out.png] [maxDepth] [spp] [seed]   defaults: instanced1000, 64, 32, atlas.png, 4, 16, 0
+// The atlas is a square grid of ceil(sqrt(N)) x ceil(sqrt(N)) rectangles of cell x cell texels, instance e in rectangle e.
+// Instances of one geometry share their vertices and so their chart: the rectangle is what tells their texels apart.  The
+// chart itself is an override layout made here - triangle k of a geometry gets cell k of a ceil(sqrt(n)) grid of the unit
+// square, as the triangle (0.11, 0.13) (0.89, 0.12) (0.12, 0.87) of its cell - one layout per distinct geometry, merged into
+// one array (for meshes whose triangles share no vertices across geometries).  One bakeAtlasIrradiance call bakes them all:
+// one point pass, one gather, one scatter.  The picture shows pi * (E / pi) * albedo with albedo = 0.8 and gamma 2.2; texels
+// without a surface are transparent.  Prints one JSON line.
+const fs = require('fs');
+const { WebGPURenderer, WorldBridge, encodePng } = require('./index.js');
+
+(async () => {
+  const [scene = 'instanced1000', count = '64', cellSize = '32', outPath = 'atlas.png', depth = '4', spp = '16', seed = '0'] =
+    process.argv.slice(2);
+  const bridge = new WorldBridge();
+  await bridge.initWasm();
+  await bridge.loadScene(scene);
+  const renderer = new WebGPURenderer(0);
+  await renderer.init();
+  await renderer.loadTexturesFromWorld(bridge);
+  renderer.updateCombinedGeometry(bridge.vertices, bridge.normals, bridge.uvs);
+  renderer.updateCombinedBVH(bridge.tlas, bridge.blas);
+  renderer.updateBuffer('topology', bridge.mesh_topology);
+  renderer.updateBuffer('instance', bridge.instances);
+  renderer.updateBuffer('lights', bridge.lights);
+  renderer.updateBuffer('draw_commands', bridge.draw_commands);   // the bake takes each instance's triangle range from these
+  bridge.updateCamera(16, 16);
+  renderer.updateSceneUniforms(bridge.cameraData, 0, bridge.lightCount);
+  const draw = bridge.draw_commands, topo = bridge.mesh_topology;
+  const nInst = draw.length / 4, nVerts = bridge.uvs.length / 2, nTris = topo.length / 20;
+  const n = Math.min(parseInt(count, 10), nInst), cell = parseInt(cellSize, 10);
+  const side = Math.ceil(Math.sqrt(n));
+  // the entries, and one chart layout per distinct geometry among them
+  const entries = [], geometries = new Set();
+  const atlasUv = new Float32Array(nVerts * 2).fill(-1);
+  const corner = [[0.11, 0.13], [0.89, 0.12], [0.12, 0.87]];
+  for (let e = 0; e < n; e++) {
+    entries.push([e, (e % side) * cell, Math.floor(e / side) * cell, cell, cell]);
+    const first = Math.floor(draw[4 * e + 2] / 3), tris = Math.floor(draw[4 * e] / 3);
+    if (geometries.has(first)) continue;
+    geometries.add(first);
+    const g = Math.max(1, Math.ceil(Math.sqrt(tris)));
+    for (let j = 0; j < tris && first + j < nTris; j++)
+      for (let c = 0; c < 3; c++) {
+        const v = topo[20 * (first + j) + c];
+        atlasUv[2 * v] = (j % g + corner[c][0]) / g;
+        atlasUv[2 * v + 1] = (Math.floor(j / g) + corner[c][1]) / g;
+      }
+  }
+  const size = side * cell;
+  const bake = renderer.bakeAtlasIrradiance(entries, size, size, parseInt(depth, 10), parseInt(spp, 10),
+    { atlasUv, seed: parseInt(seed, 10), stats: true });
+  const rgba = new Uint8Array(size * size * 4);
+  const albedo = 0.8;
+  let lit = 0;
+  for (let i = 0; i < size * size; i++) {
+    if (bake.data[4 * i + 3] < 0) continue;   // no surface
+    for (let c = 0; c < 3; c++) {
+      const v = Math.PI * bake.data[4 * i + c] * albedo;
+      rgba[4 * i + c] = Math.round(255 * Math.pow(Math.min(Math.max(v, 0), 1), 1 / 2.2));
+    }
+    rgba[4 * i + 3] = 255;
+    if (bake.data[4 * i] > 0) lit++;
+  }
+  fs.writeFileSync(outPath, Buffer.from(encodePng(rgba, size, size)));
+  console.log(JSON.stringify({ scene, entries: n, geometries: geometries.size, size, covered: bake.covered, lit, out: outPath,
+    stats: bake.stats }));
+  renderer.destroy();
+})().catch((e) => { console.error(e); process.exit(1); });

@@ -76,6 +76,17 @@ export class WebGPURenderer {
   bakeIrradiance(inst: number, width: number, height: number, maxDepth: number, spp: number,
                  opts?: { tMax?: number; padBase?: number; atlasUv?: Float32Array | null; seed?: number; stats?: boolean }):
     { data: Float32Array; width: number; height: number; covered: number; stats?: RadianceQueryStats };
+  /** Atlas bakes (rt_bake_atlas_points): every entry [inst, x, y, w, h] bakes TLAS-order instance `inst` at w x h texels
+   *  into the rectangle at (x, y) of one width x height atlas; the lowest entry owns a texel several cover.  texels are atlas
+   *  texel indices, ascending; pad = padBase + atlas texel index.  owner: 2 words per texel {entry, global triangle index},
+   *  {-1, -1} = uncovered. */
+  bakeAtlasPoints(entries: number[][] | Uint32Array, width: number, height: number,
+                  opts?: { tMax?: number; padBase?: number; atlasUv?: Float32Array | null; owner?: boolean }):
+    { n: number; points: Float32Array; texels: Uint32Array; owner?: Int32Array };
+  /** The whole atlas bake (rt_bake_atlas_irradiance): the points of all entries, one irradiance gather, scatter. */
+  bakeAtlasIrradiance(entries: number[][] | Uint32Array, width: number, height: number, maxDepth: number, spp: number,
+                      opts?: { tMax?: number; padBase?: number; atlasUv?: Float32Array | null; seed?: number; stats?: boolean }):
+    { data: Float32Array; width: number; height: number; covered: number; stats?: RadianceQueryStats };
   destroy(): void;
 }
 export class WorldBridge {

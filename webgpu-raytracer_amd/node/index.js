@@ -229,6 +229,39 @@ class WebGPURenderer {
     if (r.stats) out.stats = r.stats;
     return out;
   }
+  // ---- atlas bakes (rt_bake_atlas_points, rt_bake_atlas_irradiance): entries = an array of [inst, x, y, w, h] (or a
+  // Uint32Array of 5 words per entry): TLAS-order instance `inst` baked at w x h texels into the rectangle at (x, y) of one
+  // width x height atlas, by the atlas rule of include/mi355rt.h; the lowest entry owns a texel several cover.  opts as for
+  // bakePoints.  Result: {n, points, texels (atlas texel indices, ascending)} and with owner the Int32Array owner map of 2
+  // words per texel {entry, global triangle index}, {-1, -1} = uncovered.
+  static _atlasEntries(entries) {
+    const flat = entries instanceof Uint32Array ? entries : Uint32Array.from(entries.flat());
+    if (flat.length % 5 !== 0) throw new TypeError('atlas bake: entries are [inst, x, y, w, h]');
+    const rects = new Uint32Array(flat.length / 5 * 8);
+    for (let e = 0; e < flat.length / 5; e++) rects.set(flat.subarray(5 * e, 5 * e + 5), 8 * e);
+    return rects;
+  }
+  bakeAtlasPoints(entries, width, height, opts = {}) {
+    const texels = new Uint32Array(width * height), points = new Float32Array(width * height * 8);
+    const owner = opts.owner ? new Int32Array(width * height * 2) : null;
+    const n = native.rtBakeAtlasPoints(this._ctx, width >>> 0, height >>> 0, (opts.padBase || 0) >>> 0,
+      opts.tMax === undefined ? 1e30 : opts.tMax, WebGPURenderer._atlasEntries(entries), opts.atlasUv || null, points, texels, owner);
+    this._check(n, 'bakeAtlasPoints');
+    const out = { n, points: points.subarray(0, n * 8), texels: texels.subarray(0, n) };
+    if (owner) out.owner = owner;
+    return out;
+  }
+  // The whole atlas bake: the points of all entries, ONE irradiance gather on them, scatter.  Result as bakeIrradiance's.
+  bakeAtlasIrradiance(entries, width, height, maxDepth, spp, opts = {}) {
+    const data = new Float32Array(width * height * 4);
+    const r = native.rtBakeAtlasIrradiance(this._ctx, width >>> 0, height >>> 0, (opts.padBase || 0) >>> 0,
+      opts.tMax === undefined ? 1e30 : opts.tMax, WebGPURenderer._atlasEntries(entries), opts.atlasUv || null, maxDepth >>> 0,
+      spp >>> 0, (opts.seed || 0) >>> 0, data, !!opts.stats);
+    if (typeof r === 'number') this._check(r, 'bakeAtlasIrradiance');
+    const out = { data, width, height, covered: r.covered };
+    if (r.stats) out.stats = r.stats;
+    return out;
+  }
   destroy() { if (this._ctx) { native.rtDestroy(this._ctx); this._ctx = null; } }
 }
 

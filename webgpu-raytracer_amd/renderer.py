@@ -201,6 +201,10 @@ def load_library(path=None):
         "rt_bake_points": (i32, [vp, vp, vp, u32, vp, vp, u32, vp, vp]),
         "rt_bake_points_device": (i32, [vp, vp, vp, vp, vp, u32, vp, vp]),
         "rt_bake_irradiance": (i32, [vp, vp, vp, u32, u32, u32, u32, vp, vp, vp]),
+        # atlas bakes
+        "rt_bake_atlas_points": (i32, [vp, vp, vp, vp, u32, vp, vp, u32, vp, vp]),
+        "rt_bake_atlas_points_device": (i32, [vp, vp, vp, vp, vp, vp, u32, vp, vp]),
+        "rt_bake_atlas_irradiance": (i32, [vp, vp, vp, vp, u32, u32, u32, u32, vp, vp, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(L, name)  # AttributeError here = header/library mismatch
@@ -225,7 +229,8 @@ EXPORTED_SYMBOLS = (
     "rt_trace_rays rt_trace_rays_device rt_ray_query_stats "
     "rt_trace_radiance rt_trace_radiance_device rt_radiance_query_stats "
     "rt_gather_irradiance rt_gather_irradiance_device rt_irradiance_gather_stats "
-    "rt_bake_points rt_bake_points_device rt_bake_irradiance").split()
+    "rt_bake_points rt_bake_points_device rt_bake_irradiance "
+    "rt_bake_atlas_points rt_bake_atlas_points_device rt_bake_atlas_irradiance").split()
 
 
 # ---- ray queries: mirrors of rt_ray / rt_ray_hit / rt_ray_stats (include/mi355rt_layout.h)
@@ -272,6 +277,17 @@ IRRADIANCE_DTYPE = np.dtype([("rgb", np.float32, (3,)), ("hit_fraction", np.floa
 class RtBakeDesc(ctypes.Structure):
     _fields_ = [("inst", ctypes.c_uint32), ("width", ctypes.c_uint32), ("height", ctypes.c_uint32), ("pad_base", ctypes.c_uint32),
                 ("t_max", ctypes.c_float), ("reserved", ctypes.c_uint32 * 3)]
+
+
+# atlas bakes: mirrors of rt_bake_atlas_desc / rt_bake_rect
+class RtBakeAtlasDesc(ctypes.Structure):
+    _fields_ = [("width", ctypes.c_uint32), ("height", ctypes.c_uint32), ("pad_base", ctypes.c_uint32), ("t_max", ctypes.c_float),
+                ("n_entries", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 3)]
+
+
+class RtBakeRect(ctypes.Structure):
+    _fields_ = [("inst", ctypes.c_uint32), ("x", ctypes.c_uint32), ("y", ctypes.c_uint32), ("width", ctypes.c_uint32),
+                ("height", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 3)]
 
 
 def _ptr(a):
@@ -662,6 +678,64 @@ class WebGPURenderer:
         self._check(self.L.rt_bake_irradiance(self.ctx, ctypes.addressof(d), uv_ptr, n_uv, int(max_depth), int(spp),
                                               int(seed) & 0xffffffff, _ptr(out), ctypes.addressof(n),
                                               ctypes.addressof(st) if stats else None), "bakeIrradiance")
+        return (out, n.value, st.as_dict()) if stats else out
+
+    # ---- atlas bakes: a list of (instance, rectangle) entries into one atlas (rt_bake_atlas_points) ----
+    @staticmethod
+    def _atlas_args(entries, width, height, t_max, pad_base):
+        """-> (rt_bake_atlas_desc, the entries as an (n, 8) uint32 array in the rt_bake_rect layout)"""
+        e = np.asarray(entries, dtype=np.int64).reshape(-1, 5)
+        if e.size and (e.min() < 0 or e.max() > 0xffffffff):
+            raise ValueError("bake atlas: entries are (inst, x, y, w, h) in uint32")
+        rects = np.zeros((e.shape[0], 8), np.uint32)
+        rects[:, 0:5] = e
+        d = RtBakeAtlasDesc()
+        d.width, d.height, d.pad_base, d.t_max, d.n_entries = int(width), int(height), int(pad_base), float(t_max), e.shape[0]
+        return d, rects
+
+    def bakeAtlasPoints(self, entries, width, height, t_max=1e30, pad_base=0, atlas_uv=None, owner=False, cap=None):
+        """The gather points of the covered texels of a width x height atlas into which every entry (inst, x, y, w, h) - an
+        (n, 5) array or a list of such tuples - bakes TLAS-order instance `inst` at w x h texels, placed at (x, y); by the
+        atlas rule of include/mi355rt.h, the lowest entry owning a texel several cover.  Returns (points (n, 8) float32, pad =
+        pad_base + atlas texel index; texels (n,) uint32, ascending) - and with owner=True a third item, the (height, width,
+        2) int32 owner map {entry, global triangle index}, {-1, -1} = uncovered.  atlas_uv and cap as in bakePoints."""
+        d, rects = self._atlas_args(entries, width, height, t_max, pad_base)
+        uv, uv_ptr, n_uv = self._atlas_uv(atlas_uv)
+        room = int(width) * int(height) if cap is None else int(cap)
+        points = np.empty((room, 8), np.float32)
+        texels = np.empty(room, np.uint32)
+        own = np.empty((int(height), int(width), 2), np.int32) if owner else None
+        n = ctypes.c_uint32(0)
+        self._check(self.L.rt_bake_atlas_points(self.ctx, ctypes.addressof(d), _ptr(rects), uv_ptr, n_uv,
+                                                _ptr(points) if room else None, _ptr(texels) if room else None, room,
+                                                ctypes.addressof(n), _ptr(own) if owner else None), "bakeAtlasPoints")
+        got = min(n.value, room)
+        out = (points[:got], texels[:got]) + ((own,) if owner else ())
+        return out + (n.value,) if cap is not None else out
+
+    def bakeAtlasPointsDevice(self, entries, width, height, points_ptr, texels_ptr, cap, count_ptr, t_max=1e30, pad_base=0,
+                              atlas_uv_ptr=None, owner_ptr=None):
+        """Enqueue the atlas point pass on device arrays, as bakePointsDevice; the entries are a host array, copied before the
+        call returns.  owner_ptr: width * height uint64, (entry << 32) | triangle, all ones = uncovered."""
+        d, rects = self._atlas_args(entries, width, height, t_max, pad_base)
+        self._check(self.L.rt_bake_atlas_points_device(self.ctx, ctypes.addressof(d), _ptr(rects), ctypes.c_void_p(atlas_uv_ptr or 0),
+                                                       ctypes.c_void_p(points_ptr or 0), ctypes.c_void_p(texels_ptr or 0), int(cap),
+                                                       ctypes.c_void_p(count_ptr or 0), ctypes.c_void_p(owner_ptr or 0)),
+                    "bakeAtlasPointsDevice")
+
+    def bakeAtlasIrradiance(self, entries, width, height, max_depth, spp, seed=0, t_max=1e30, pad_base=0, atlas_uv=None,
+                            stats=False):
+        """The whole atlas bake: the points of all entries, ONE irradiance gather on them, scatter.  Returns the (height,
+        width) IRRADIANCE_DTYPE atlas as bakeIrradiance does - and with stats=True the triple (atlas, number of covered
+        texels, stats dict of the gather)."""
+        d, rects = self._atlas_args(entries, width, height, t_max, pad_base)
+        uv, uv_ptr, n_uv = self._atlas_uv(atlas_uv)
+        out = np.empty((int(height), int(width)), dtype=IRRADIANCE_DTYPE)
+        n = ctypes.c_uint32(0)
+        st = RtRadianceStats()
+        self._check(self.L.rt_bake_atlas_irradiance(self.ctx, ctypes.addressof(d), _ptr(rects), uv_ptr, n_uv, int(max_depth),
+                                                    int(spp), int(seed) & 0xffffffff, _ptr(out), ctypes.addressof(n),
+                                                    ctypes.addressof(st) if stats else None), "bakeAtlasIrradiance")
         return (out, n.value, st.as_dict()) if stats else out
 
     # ---- the sharded image (rt_dist_*): this context as one rank of `world` ----
