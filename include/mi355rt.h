@@ -416,6 +416,57 @@ int rt_gather_irradiance_device(rt_ctx* ctx, const void* dev_points, uint32_t n,
                                 void* dev_out);
 int rt_irradiance_gather_stats(rt_ctx* ctx, rt_radiance_stats* out);
 
+/* ---- probe gathers: "which radiance arrives at this point, from every direction?" as nine spherical-harmonic
+ * coefficients per colour (light-probe grids for dynamic objects, irradiance volumes) ----
+ * A probe (rt_probe) is a point in space.  Its spp directions are drawn uniformly on the sphere on the device, the
+ * renderer's path tracing runs behind each, and the samples are projected onto the real spherical harmonics of bands 0 ..
+ * 2; only the 27 coefficients and the hit fraction come back (rt_probe_sh9).  The unit of path work is the (probe,
+ * sample) pair, not the probe: a call is k_probe_rays (one rt_ray per pair) -> the radiance query's kernel on those rays at
+ * spp = 1 -> k_probe_project (one wave per probe; csrc/k_probe.hip.h), so a grid of few probes with very many samples
+ * fills the device, which a lane-per-point gather does not.
+ *
+ * THE PROBE RULE.  All arithmetic is f32, unfused, in the order written, with rt_sqrt / rt_max / rt_sincos / rt_div of
+ * mi355rt_math.h.  For probe i and sample s in 0 .. spp-1, with f = seed * spp + s in u32 arithmetic:
+ *   direction  from the gather's direction stream, rng_d = init_rng(pad ^ 0x80000000, f): u1 = rand_pcg(rng_d), u2 =
+ *              rand_pcg(rng_d); z = 1.0f - 2.0f * u1; r = rt_sqrt(rt_max(0.0f, 1.0f - z * z)); rt_sincos(RT_TWO_PI * u2, &sp,
+ *              &cp); d = (r * cp, r * sp, z).  Uniform on the sphere; not normalised again.
+ *   sample     {r, g, b, t}: exactly what rt_trace_radiance returns for the ray {position, t_max, d, pad} with spp = 1 and
+ *              seed = f.  It is a hit iff t < t_max as a float comparison (false for NaN).  Keep pad < 2^31, as for a gather.
+ *   basis      for d = (x, y, z): Y0 = 0.282094792f; Y1 = 0.488602512f * y; Y2 = 0.488602512f * z; Y3 = 0.488602512f * x;
+ *              Y4 = 1.092548431f * (x * y); Y5 = 1.092548431f * (y * z); Y6 = 0.315391565f * (3.0f * (z * z) - 1.0f);
+ *              Y7 = 1.092548431f * (x * z); Y8 = 0.546274215f * (x * x - y * y).  The term of (k, c) is radiance[c] * Yk.
+ *   sum        a fixed tree, the same for each of the 27 sums: the partial P[l], l = 0 .. 63, is ((+0 + term(l)) + term(l +
+ *              64)) + ... over the samples s = l (mod 64), ascending; then for m = 32, 16, 8, 4, 2, 1, in all l at once, P[l]
+ *              = P[l] + P[l ^ m] (own value first); the sum is P[0].
+ *   result     sh[k][c] = rt_div(sum, (float)spp) * 12.566370614f, the Monte-Carlo estimate of the integral of L(w) Yk(w)
+ *              over the sphere;  hit_fraction = rt_div((float)hits, (float)spp).  max_depth == 0: every first segment is
+ *              still traced and the coefficients are whatever the arithmetic gives from radiance +0.
+ * A result depends on (scene, probe, pad, seed, spp, max_depth) only - never on n, the probe's position in the array or how
+ * the library splits the work: a call is cut into batches of whole probes of at most RT_PROBE_BATCH_SAMPLES samples, whose
+ * rays and radiances live in scratch of the probe gather's own, kept and grown (at most 48 B per sample of a batch, 192
+ * MiB).  The rgb irradiance at a normal n follows from the coefficients by the cosine-lobe convolution (band factors pi, 2
+ * pi / 3, pi / 4), a host one-liner; ringing filters and the layout of a probe grid are the caller's.
+ * The stats are an rt_radiance_stats: rays = n probes, samples = n * spp; the ray, hit, node and triangle counters and
+ * workgroups are the sums over the radiance launches the call makes - hence the sums of the composed queries' counters -
+ * lds is the form that was picked, and kernel_ms is the summed time of the RADIANCE launches only (k_probe_rays and
+ * k_probe_project are not in it).
+ * A probe gather leaves the renderer as it was, like the queries above, and it has a state of its own: the stats and
+ * staging of radiance queries and irradiance gathers are untouched.
+ *   rt_gather_probes         blocking: copies n probes in, gathers, copies n results out.  stats != NULL runs the counting
+ *                            kernel and fills *stats.  n == 0 is RT_OK; n >= 2^31, a NULL pointer, spp == 0 or spp > 65536 is
+ *                            RT_ERR_INVALID; without a valid scene RT_ERR_NOT_READY; light_count above the uploaded lights
+ *                            buffer is RT_ERR_INVALID.  Messages begin with "probe gather:".
+ *   rt_gather_probes_device  the same on device-accessible arrays (n rt_probe in, n rt_probe_sh9 out; 16-byte aligned, on
+ *                            the context's device): only enqueues on the context's stream (rt_set_stream respected).
+ *                            Counts while rt_set_counting(ctx, 1) is on.
+ *   rt_probe_gather_stats    stats of the last probe gather (blocking: fences the stream). */
+#define RT_PROBE_BATCH_SAMPLES (1u << 22)
+int rt_gather_probes(rt_ctx* ctx, const rt_probe* probes, uint32_t n, uint32_t max_depth, uint32_t spp, uint32_t seed,
+                     rt_probe_sh9* out, rt_radiance_stats* stats);
+int rt_gather_probes_device(rt_ctx* ctx, const void* dev_probes, uint32_t n, uint32_t max_depth, uint32_t spp, uint32_t seed,
+                            void* dev_out);
+int rt_probe_gather_stats(rt_ctx* ctx, rt_radiance_stats* out);
+
 /* ---- lightmap bakes: "the gather points of this instance's atlas", rasterised on the device ----
  * An irradiance gather wants surface points; a lightmap wants one per covered texel of an instance's UV atlas.  The scene
  * holds what that takes on the device (uv, pos, nrm, topology, the instances' forward transforms, the draw commands with

@@ -156,6 +156,18 @@ typedef struct rt_irradiance { /* 16 B: one vector store of k_irradiance_gather 
   float hit_fraction;         /* samples whose first segment hit something / spp */
 } rt_irradiance;
 
+/* ---- probe gathers (rt_gather_probes, mi355rt.h); their stats are an rt_radiance_stats with rays = probes ---- */
+typedef struct rt_probe {     /* 32 B: the slots of rt_ray {position, t_max} {unused, pad} */
+  float position[3];
+  float t_max;                /* of every sample's first segment */
+  float unused[3];            /* not read; write 0 */
+  uint32_t pad;               /* the probe's RNG stream id; keep it below 2^31 */
+} rt_probe;
+typedef struct rt_probe_sh9 { /* 112 B: seven 16-byte vector stores of k_probe_project */
+  float sh[9][3];             /* coefficient-major, rgb inside: the estimate of the integral of L(w) Y_k(w) over the sphere */
+  float hit_fraction;         /* samples whose first segment hit something / spp */
+} rt_probe_sh9;
+
 /* ---- lightmap bakes (rt_bake_points, mi355rt.h): which atlas of which instance ---- */
 typedef struct rt_bake_desc { /* 32 B */
   uint32_t inst;              /* TLAS-order instance index */
@@ -184,6 +196,12 @@ typedef struct rt_bake_rect { /* 32 B: two 16-byte loads of k_atlas_owner / k_at
 static_assert(sizeof(rt_bake_desc) == 32, "rt_bake_desc is 32 bytes");
 static_assert(sizeof(rt_bake_atlas_desc) == 32, "rt_bake_atlas_desc is 32 bytes");
 static_assert(sizeof(rt_bake_rect) == 32, "rt_bake_rect is 32 bytes");
+static_assert(sizeof(rt_probe) == 32, "rt_probe is 32 bytes");
+static_assert(__builtin_offsetof(rt_probe, t_max) == 12 && __builtin_offsetof(rt_probe, unused) == 16 &&
+                  __builtin_offsetof(rt_probe, pad) == 28,
+              "rt_probe has the slots of rt_ray");
+static_assert(sizeof(rt_probe_sh9) == 112, "rt_probe_sh9 is 112 bytes");
+static_assert(__builtin_offsetof(rt_probe_sh9, hit_fraction) == 108, "hit_fraction is the twenty-eighth word");
 static_assert(sizeof(rt_gather_point) == 32, "rt_gather_point is 32 bytes");
 static_assert(__builtin_offsetof(rt_gather_point, t_max) == 12 && __builtin_offsetof(rt_gather_point, normal) == 16 &&
                   __builtin_offsetof(rt_gather_point, pad) == 28,

@@ -1,0 +1,273 @@
+"""Probe gathers on the GPU (rt_gather_probes: k_probe_rays -> k_radiance_query -> k_probe_project) against the reference
+model (tests/model/probe_model.cpp, tied to the radiance model by tests/test_probe_model.py), probe by probe: the 27
+coefficients and hit_fraction bit for bit, the ray, hit, node and triangle counters as sums, in the LDS and the global-memory
+form, at sample counts below, at and above the 64 lanes of the projection; the composition identity on the GPU's own radiance
+queries; a call that is cut into two batches; the device entry; non-finite probes; no side effect on a render or on the
+other path queries' state."""
+import ctypes
+
+import numpy as np
+import pytest
+
+import gather_util as gu
+import parity_util as pu
+import probe_util as prb
+import radiance_util as ru
+import ray_query_util as rq
+from test_gpu_irradiance_gather import _render, _renderer
+
+pytestmark = pytest.mark.gpu
+
+RT_ERR_INVALID = -1
+DEPTHS = (0, 1, 4)
+SPPS = (1, 3, 64, 65, 80)     # fewer samples than lanes, one per lane, lanes with one and with two samples
+_cache = {}
+
+
+def _scene(W, scene):
+    """(bridge, model, probes) of a scene, made once: 96 probes, pads 7 i + 3"""
+    if scene not in _cache:
+        b = pu.bridge_for(W, scene)
+        m = prb.model_for(W, b)
+        probes = prb.scene_probes(m, b)
+        probes.setflags(write=False)
+        _cache[scene] = (b, m, probes, {})
+    return _cache[scene][:3]
+
+
+def _ref(W, scene, depth, spp):
+    """the model's (out, hits, counts) for the scene's probes, computed once and left unchanged"""
+    b, m, probes = _scene(W, scene)
+    refs = _cache[scene][3]
+    if (depth, spp) not in refs:
+        res = m.gatherProbes(probes, depth, spp, prb.SEED)
+        for a in res:
+            a.setflags(write=False)
+        refs[depth, spp] = res
+    return refs[depth, spp]
+
+
+def _gather_and_check(r, probes, depth, spp, ref, counts, tag, seed=prb.SEED):
+    res, st = r.gatherProbes(probes, depth, spp, seed, stats=True)
+    print(tag, "lds", st["lds"], "workgroups", st["workgroups"], {k: st[k] for k in prb.COUNT_NAMES})
+    prb.check_against_model(res, ref, tag, nan_as_class=True)
+    prb.check_counts(st, counts, probes.shape[0], spp, tag)
+    assert st["workgroups"] >= 1, tag
+    plain = r.gatherProbes(probes, depth, spp, seed)
+    assert np.array_equal(prb.result_words(plain), prb.result_words(res)), (tag, "counting and product kernel differ")
+    st2 = r.probeGatherStats()
+    assert st2["extension_rays"] == st["extension_rays"] and st2["shadow_rays"] == st["shadow_rays"], tag
+    assert st2["nodes_visited"] == 0 and st2["tris_tested"] == 0 and st2["shaded_hits"] == 0, tag
+    return st
+
+
+@pytest.mark.parametrize("scene,no_lds,lds", [("cornell", None, 1), ("cornell", "1", 0), ("special", None, 0)])
+def test_bit_parity_with_the_model(W, monkeypatch, scene, no_lds, lds):
+    b, m, probes = _scene(W, scene)
+    n = probes.shape[0]
+    assert n == 96 and np.array_equal(probes.view(np.uint32)[:, 7], 7 * np.arange(96, dtype=np.uint32) + 3)
+    ref, hits, _ = _ref(W, scene, 4, 80)
+    some_hit, lit = int((hits > 0).sum()), int((np.abs(ref[:, :27]).max(axis=1) > 0).sum())
+    print(scene, "model: probes with a hit sample", some_hit, "lit", lit, "of", n)
+    assert 2 * some_hit >= n and 4 * lit >= n, (scene, some_hit, lit)      # parity must not pass on darkness
+    r = _renderer(W, monkeypatch, b, no_lds)
+    try:
+        for depth in DEPTHS:
+            for spp in SPPS:
+                ref, _, counts = _ref(W, scene, depth, spp)
+                st = _gather_and_check(r, probes, depth, spp, ref, counts, "%s no_lds=%s depth %d spp %d" % (scene, no_lds, depth, spp))
+                assert st["lds"] == lds, (scene, no_lds, st)
+                if depth == 0:
+                    assert st["extension_rays"] == spp * n and st["shadow_rays"] == 0 and st["shaded_hits"] == 0
+    finally:
+        r.destroy()
+
+
+def test_a_probe_gather_is_the_projection_of_the_gpus_radiance_queries(W, monkeypatch):
+    """gatherProbes equals, word for word, the numpy projection of the GPU's OWN radiance queries on the model's exported
+    directions (spp = 1, seed = f per sample), and its counters are the sums of theirs."""
+    b, m, probes = _scene(W, "cornell")
+    r = _renderer(W, monkeypatch, b)
+    try:
+        for depth, spp in ((4, 65), (0, 3)):
+            dirs = m.probeDirections(probes, spp, prb.SEED)
+
+            def trace(rays, max_depth, one, seed):
+                res, st = r.traceRadiance(rays, max_depth, one, seed, stats=True)
+                return np.ascontiguousarray(res).view(np.float32).reshape(-1, 4), st
+
+            want, want_hits, each = prb.compose(trace, probes, dirs, depth, spp, prb.SEED)
+            got, st = r.gatherProbes(probes, depth, spp, prb.SEED, stats=True)
+            prb.check_against_model(got, want, "composed on the GPU, depth %d" % depth)
+            for name in prb.COUNT_NAMES:
+                assert st[name] == sum(e[name] for e in each), (depth, name)
+            assert np.array_equal(ru.u32(got["hit_fraction"]), ru.u32(want_hits.astype(np.float32) / np.float32(spp)))
+    finally:
+        r.destroy()
+
+
+def test_a_call_cut_into_two_batches(W, monkeypatch):
+    """65 probes at spp = 65536 are two batches, of 64 probes and of 1: the result equals, word for word, the calls on the
+    probes [0, 64) and [64, 65) and the call on the reversed array; the stats are the sums over both radiance launches."""
+    b, m, probes = _scene(W, "cornell")
+    pts = np.array(probes[:65])
+    spp = 65536
+    r = _renderer(W, monkeypatch, b)
+    try:
+        r.setKernelTiming(True)
+        full, st = r.gatherProbes(pts, 1, spp, prb.SEED, stats=True)
+        words = prb.result_words(full)
+        head, st_a = r.gatherProbes(pts[:64], 1, spp, prb.SEED, stats=True)
+        tail, st_b = r.gatherProbes(pts[64:], 1, spp, prb.SEED, stats=True)
+        print("full", st, "head", st_a, "tail", st_b)
+        assert np.array_equal(prb.result_words(head), words[:64]) and np.array_equal(prb.result_words(tail), words[64:])
+        back = r.gatherProbes(pts[::-1], 1, spp, prb.SEED)
+        assert np.array_equal(prb.result_words(back)[::-1], words)
+        assert st["rays"] == 65 and st["samples"] == 65 * spp and st_a["samples"] == 64 * spp and st_b["samples"] == spp
+        for name in prb.COUNT_NAMES + ("workgroups",):
+            assert st[name] == st_a[name] + st_b[name], (name, st[name], st_a[name], st_b[name])
+        assert st["extension_rays"] >= 65 * spp and min(st["kernel_ms"], st_a["kernel_ms"], st_b["kernel_ms"]) > 0.0
+        assert (full["hit_fraction"][:64] > 0).all()            # the grid probes are inside the box
+    finally:
+        r.destroy()
+
+
+def test_device_entry_equals_the_host_entry(W, monkeypatch):
+    import torch
+    from webgpu_raytracer_amd import renderer as R
+    b, m, probes = _scene(W, "cornell")
+    n = probes.shape[0]
+    ref, hits, counts = _ref(W, "cornell", 4, 80)
+    r = _renderer(W, monkeypatch, b)
+    try:
+        host = r.gatherProbes(probes, 4, 80, prb.SEED)
+        side = torch.cuda.Stream()
+        r.setStream(side.cuda_stream)
+        with torch.cuda.stream(side):
+            d_probes = torch.from_numpy(np.array(probes)).cuda(non_blocking=False)
+            d_out = torch.empty((n, 28), dtype=torch.float32, device="cuda")
+            r.gatherProbesDevice(d_probes.data_ptr(), n, d_out.data_ptr(), 4, 80, prb.SEED)
+            n_hit = (d_out[:, 27] > 0).sum()           # a torch op on the same stream, behind the gather
+        side.synchronize()
+        got = d_out.cpu().numpy().view(R.PROBE_SH9_DTYPE).reshape(-1)
+        assert np.array_equal(prb.result_words(got), prb.result_words(host))
+        prb.check_against_model(got, ref, "device entry")
+        assert int(n_hit) == int((hits > 0).sum())
+        st = r.probeGatherStats()
+        assert st["rays"] == n and st["samples"] == 80 * n and st["nodes_visited"] == 0     # counting is off on the device entry ...
+        assert st["extension_rays"] == int(counts[:, 0].sum()) and st["shadow_rays"] == int(counts[:, 1].sum())
+        r.setCounting(True)
+        with torch.cuda.stream(side):
+            r.gatherProbesDevice(d_probes.data_ptr(), n, d_out.data_ptr(), 4, 80, prb.SEED)
+        prb.check_counts(r.probeGatherStats(), counts, n, 80, "device entry, counting")       # ... until asked for
+        assert r.L.rt_gather_probes_device(r.ctx, d_probes.data_ptr() + 8, 4, 4, 2, 0, d_out.data_ptr()) == RT_ERR_INVALID   # misaligned
+        r.setStream(None)
+    finally:
+        r.destroy()
+
+
+def _edge_probes(probes):
+    """Eight ordinary probes, untouched, followed by each of them with ONE component of position or t_max replaced by each of
+    SPECIALS (NaN, +-inf, +-0, a denormal, +-3e38)"""
+    base = probes[8:16]
+    out = [b.copy() for b in base]
+    for b in base:
+        for comp in (0, 1, 2, 3):
+            for v in rq.SPECIALS:
+                p = b.copy()
+                p[comp] = v
+                out.append(p)
+    return np.ascontiguousarray(np.stack(out), np.float32)
+
+
+@pytest.mark.parametrize("no_lds", [None, "1"])
+def test_edge_input(W, monkeypatch, no_lds):
+    """Non-finite positions and t_max: the call returns with the model's results (NaNs as a class only in rows where the
+    model has one), the untouched probes of the same call are bit-exact; n == 0 is RT_OK."""
+    b, m, probes = _scene(W, "cornell")
+    pts = _edge_probes(probes)
+    assert pts.shape[0] == 8 + 8 * 4 * 8
+    r = _renderer(W, monkeypatch, b, no_lds)
+    try:
+        for depth, spp in ((4, 65), (1, 3)):
+            ref, _, _ = m.gatherProbes(pts, depth, spp, prb.SEED)
+            res = r.gatherProbes(pts, depth, spp, prb.SEED)
+            tag = "edge no_lds=%s depth %d" % (no_lds, depth)
+            prb.check_against_model(res, ref, tag, nan_as_class=True)
+            assert not np.isnan(ref[:8]).any(), tag
+            assert np.array_equal(prb.result_words(res)[:8], ru.u32(ref[:8])), tag
+        none, st = r.gatherProbes(pts[:0], 4, 8, prb.SEED, stats=True)
+        assert none.shape == (0,) and st["rays"] == 0 and st["samples"] == 0 and st["workgroups"] == 0
+        assert r.L.rt_gather_probes(r.ctx, None, 0, 4, 8, prb.SEED, None, None) == 0
+        assert r.probeGatherStats()["rays"] == 0
+    finally:
+        r.destroy()
+
+
+def test_probe_gathers_leave_the_render_and_the_other_queries_alone(W, monkeypatch):
+    """Frames 1-4, probe gathers, frames 5-8 with lookahead 8 against the same frames without: accumulation, presented
+    image, counters, G-buffer and uniforms are equal.  The stats of the last radiance query and of the last irradiance
+    gather read the same before and after a probe gather, and a radiance query run again gives the same words."""
+    b, m, probes = _scene(W, "cornell")
+    W._build.build_rt()
+    ref, _, counts = _ref(W, "cornell", 4, 65)
+
+    def gathers(r):
+        _gather_and_check(r, probes, 4, 65, ref, counts, "between frames")
+
+    got = _render(W, b, (1, 2, 3, 4), (5, 6, 7, 8), gathers)
+    want = _render(W, b, (1, 2, 3, 4), (5, 6, 7, 8), lambda r: None)
+    assert np.array_equal(got[0].view(np.uint32), want[0].view(np.uint32)), "accumulation"
+    assert np.array_equal(got[1], want[1]), "captureFrame"
+    assert got[2] == want[2], (got[2], want[2])
+    for a, w in zip(got[3], want[3]):
+        assert np.array_equal(pu.bits(a), pu.bits(w)), "G-buffer"
+    assert np.array_equal(got[4], want[4]), "uniforms"
+
+    r = _renderer(W, monkeypatch, b)
+    try:
+        points = np.array(probes[:40])
+        points[:, 5] = 1.0                                        # gather points: the probes with a normal
+        rays = prb.plain_rays(probes, m.probeDirections(probes, 1, prb.SEED), 0)
+        res_r, st_r = r.traceRadiance(rays, 4, 2, prb.SEED, stats=True)
+        res_g, st_g = r.gatherIrradiance(points, 4, 2, prb.SEED, stats=True)
+        _gather_and_check(r, probes, 4, 65, ref, counts, "after the other queries")
+        after_r, after_g, after_p = r.radianceQueryStats(), r.irradianceGatherStats(), r.probeGatherStats()
+        assert after_r == st_r and after_g == st_g, (st_r, after_r, st_g, after_g)
+        assert after_p["rays"] == 96 and after_p["samples"] == 96 * 65
+        assert len({st_r["extension_rays"], st_g["extension_rays"], after_p["extension_rays"]}) == 3   # mixed-up stats would show
+        again = r.traceRadiance(rays, 4, 2, prb.SEED)
+        assert np.array_equal(ru.result_words(again), ru.result_words(res_r))
+        again_g = r.gatherIrradiance(points, 4, 2, prb.SEED)
+        assert np.array_equal(gu.result_words(again_g), gu.result_words(res_g))
+    finally:
+        r.destroy()
+
+
+def test_errors(W, monkeypatch):
+    """The argument rules on a context without a scene (the body of tests/test_probe_abi.py, here with a device for certain),
+    then with one: the light count, the largest spp, kernel timing."""
+    from webgpu_raytracer_amd import renderer as R
+    from test_probe_abi import test_argument_rules_on_a_context_without_a_scene as argument_rules
+    assert R.load_library().rt_device_count() > 0
+    argument_rules(W)
+    b, m, probes = _scene(W, "cornell")
+    probes = np.array(probes)
+    r = _renderer(W, monkeypatch, b)
+    try:
+        out = np.zeros(probes.shape[0], R.PROBE_SH9_DTYPE)
+        call = r.L.rt_gather_probes
+        assert call(r.ctx, probes.ctypes.data, 16, 4, 1, 0, out.ctypes.data, None) == 0
+        assert call(r.ctx, probes.ctypes.data, 1, 1, 65536, 0, out.ctypes.data, None) == 0      # spp = 65536 is accepted
+        b.updateCamera(16, 16)
+        r.updateSceneUniforms(b.cameraData, 0, len(np.asarray(b.lights)) // 2 + 1)              # a light count above the lights buffer
+        assert call(r.ctx, probes.ctypes.data, 16, 4, 1, 0, out.ctypes.data, None) == RT_ERR_INVALID
+        assert b"light_count" in r.L.rt_last_error(r.ctx)
+        r.updateSceneUniforms(b.cameraData, 0, b.lightCount)
+        res, s = r.gatherProbes(probes, 4, 3, prb.SEED, stats=True)
+        assert s["kernel_ms"] == 0.0
+        r.setKernelTiming(True)
+        res, s = r.gatherProbes(probes, 4, 3, prb.SEED, stats=True)
+        assert s["kernel_ms"] > 0.0
+    finally:
+        r.destroy()

@@ -21,6 +21,8 @@
 //                             with a policy per kind, and k_radiance_query: the items are rays (rt_trace_radiance)
 //   k_gather.hip.h            k_irradiance_gather: the same loop behind hemisphere directions drawn at a caller's surface
 //                             points (rt_gather_irradiance)
+//   k_probe.hip.h             k_probe_rays / k_probe_project: uniform-sphere rays per (probe, sample) in front of
+//                             k_radiance_query and the SH9 projection behind it (rt_gather_probes)
 //   k_bake.hip.h              k_bake_owner / _count / _scan / _emit: the UV-space rasteriser that makes such points from the
 //                             texels of an instance's atlas (rt_bake_points), and k_bake_scatter, the way back
 //   k_texture_post.hip.h      k_resize_texture; k_postprocess = PostProcess.wgsl `main` (:103-176)
@@ -52,6 +54,7 @@
 #include "k_pathtrace.hip.h"
 #include "k_radiance.hip.h"
 #include "k_gather.hip.h"
+#include "k_probe.hip.h"
 #include "k_bake.hip.h"
 #include "k_wavefront.hip.h"
 #include "k_rayquery.hip.h"

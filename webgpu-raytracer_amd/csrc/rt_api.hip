@@ -55,7 +55,7 @@ struct PreparedKernel {
   int per_cu;
 };
 
-// What one kind of query (rt_trace_rays, rt_trace_radiance, rt_gather_irradiance) keeps between calls: the staging arrays of
+// What one kind of query (rt_trace_rays, rt_trace_radiance, rt_gather_irradiance, rt_gather_probes) keeps between calls: the staging arrays of
 // its host entry, its own counter shards with the chunk counter behind them, and the events around its last launch.
 struct QueryState {
   DeviceBuffer in, out, counters;
@@ -221,6 +221,14 @@ struct rt_ctx {
   rt_ray_stats rq_last = {};
   rt_radiance_stats rd_last = {};
   rt_radiance_stats gi_last = {};
+  // probe gathers (rt_gather_probes): a path-query kind of their own (its QueryState: the host entry's staging, the counter
+  // shards of the radiance launches), the scratch of a batch (one rt_ray and one rt_radiance per sample, kept and grown)
+  // and an event pair per radiance launch of the last call
+  QueryState pr;
+  rt_radiance_stats pr_last = {};
+  DeviceBuffer pr_rays, pr_rad;
+  std::vector<hipEvent_t> pr_ev;    // 2 per batch
+  uint32_t pr_timed = 0;            // batches of the last call that recorded their events
   BakeState bk;
 
   // kernel timing
@@ -747,8 +755,9 @@ uint32_t grid_blocks(const rt_ctx* c, int per_cu, int cap_per_cu, uint64_t usefu
   return blocks ? (uint32_t)blocks : 1u;
 }
 
-// ---- queries against the uploaded scene (rt_trace_rays, rt_trace_radiance, rt_gather_irradiance): what the kinds share.
-// `what` is the prefix of the kind's messages, "ray query", "radiance query" or "irradiance gather"; q its QueryState.
+// ---- queries against the uploaded scene (rt_trace_rays, rt_trace_radiance, rt_gather_irradiance, rt_gather_probes): what the
+// kinds share.  `what` is the prefix of the kind's messages, "ray query", "radiance query", "irradiance gather" or "probe
+// gather"; q its QueryState.
 //
 // The scene is there and its derived records are made (prepare_scene, as a compute() would); lights: the kind samples the
 // lights.  Touches nothing of the renderer's frame state.
@@ -782,12 +791,16 @@ int query_device_arrays_ok(rt_ctx* c, const char* what, const void* dev_rays, co
   }
   return RT_OK;
 }
-// the query's counter shards and the chunk counter behind them, zeroed on the stream
-int query_reset_counters(rt_ctx* c, QueryState& q, uint64_t** counters, uint32_t** head) {
+// the query's counter shards and the chunk counter behind them, zeroed on the stream; keep_counts: only the chunk counter
+// is (a later launch of one call, whose counts add up in the shards)
+int query_reset_counters(rt_ctx* c, QueryState& q, uint64_t** counters, uint32_t** head, bool keep_counts = false) {
   const size_t counter_bytes = (size_t)RT_COUNTER_SHARDS * 6 * 8;
   const int r = ensure_buffer(c, q.counters, counter_bytes + 16, false);
   if (r < 0) return r;
-  HIP_TRY(c, hipMemsetAsync(q.counters.ptr, 0, counter_bytes + 16, c->stream));
+  if (keep_counts)
+    HIP_TRY(c, hipMemsetAsync((char*)q.counters.ptr + counter_bytes, 0, 16, c->stream));
+  else
+    HIP_TRY(c, hipMemsetAsync(q.counters.ptr, 0, counter_bytes + 16, c->stream));
   *counters = (uint64_t*)q.counters.ptr;
   *head = (uint32_t*)((char*)q.counters.ptr + counter_bytes);
   return RT_OK;
@@ -947,6 +960,7 @@ void rt_destroy(rt_ctx* c) {
                          &c->slots, &c->gbuf_batch, &c->frame_col, &c->wf_state, &c->wf_queues, &c->wf_counters,
                          &c->rq.in, &c->rq.out, &c->rq.counters, &c->rd.in, &c->rd.out, &c->rd.counters,
                          &c->gi.in, &c->gi.out, &c->gi.counters,
+                         &c->pr.in, &c->pr.out, &c->pr.counters, &c->pr_rays, &c->pr_rad,
                          &c->bk.uv, &c->bk.owner, &c->bk.blocks, &c->bk.count, &c->bk.points, &c->bk.texels, &c->bk.results,
                          &c->bk.atlas, &c->bk.entries, &c->bk.items, &c->bk.owner64,
                          &c->tex_staging, &c->bv_in, &c->bv_tri, &c->bv_order, &c->bv_nodes, &c->bv_out,
@@ -960,6 +974,8 @@ void rt_destroy(rt_ctx* c) {
   for (QueryState* q : {&c->rq, &c->rd, &c->gi})
     for (hipEvent_t e : q->ev)
       if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : c->pr_ev)   // (c->pr.ev only borrows these)
+    if (e) (void)hipEventDestroy(e);
   if (c->world.ev0) (void)hipEventDestroy(c->world.ev0);
   if (c->world.ev1) (void)hipEventDestroy(c->world.ev1);
   if (c->world.ev_t0) (void)hipEventDestroy(c->world.ev_t0);
@@ -2090,7 +2106,8 @@ int rt_trace_rays(rt_ctx* c, const rt_ray* rays, uint32_t n, int mode, float t_m
   return RT_OK;
 }
 
-// ---- path queries: radiance queries and irradiance gathers (path_query_loop, k_radiance.hip.h).  What a kind has of its own:
+// ---- path queries: radiance queries, irradiance gathers and the trace of probe gathers (path_query_loop, k_radiance.hip.h).
+// What a kind has of its own:
 struct PathQueryKind {
   const char* what;                   // prefix of its messages
   const char* items;                  // what it calls its items
@@ -2105,11 +2122,15 @@ static const PathQueryKind pq_radiance = {"radiance query", "rays", RT_PQ_FNS(k_
                                           sizeof(rt_radiance)};
 static const PathQueryKind pq_gather = {"irradiance gather", "points", RT_PQ_FNS(k_irradiance_gather), &rt_ctx::gi, &rt_ctx::gi_last,
                                         sizeof(rt_irradiance)};
+// probe gathers trace with the radiance query's kernel, on a state of their own
+static const PathQueryKind pq_probe = {"probe gather", "probes", RT_PQ_FNS(k_radiance_query), &rt_ctx::pr, &rt_ctx::pr_last,
+                                       sizeof(rt_probe_sh9)};
 #undef RT_PQ_FNS
 
-// Enqueue one query on the context's stream: n > 0 items at d_items, results to d_out (device pointers).
+// Enqueue one query on the context's stream: n > 0 items at d_items, results to d_out (device pointers).  keep_counts: a
+// later launch of the same call, whose counters add to those of the launches before it.
 static int launch_path_query(rt_ctx* c, const PathQueryKind& k, const void* d_items, uint32_t n, uint32_t max_depth, uint32_t spp,
-                             uint32_t seed, void* d_out, bool detail) {
+                             uint32_t seed, void* d_out, bool detail, bool keep_counts = false) {
   int r = query_scene_ready(c, k.what, true);
   if (r < 0) return r;
   // the persistent kernel's 256-thread forms without the one-leaf one
@@ -2122,7 +2143,7 @@ static int launch_path_query(rt_ctx* c, const PathQueryKind& k, const void* d_it
     fprintf(stderr, "[mi355rt] %s: %s form, %zu bytes of LDS, resident workgroups per CU %d, %u workgroups\n", k.what,
             shape.lds ? "LDS" : "global", shape.dyn, per_cu, blocks);
   rtk::PathQueryArgs A;
-  if ((r = query_reset_counters(c, c->*k.state, &A.counters, &A.head)) < 0) return r;
+  if ((r = query_reset_counters(c, c->*k.state, &A.counters, &A.head, keep_counts)) < 0) return r;
   A.items = (const float4*)d_items;
   A.out = (float4*)d_out;
   A.n_items = n;
@@ -2220,6 +2241,107 @@ int rt_gather_irradiance_device(rt_ctx* c, const void* dev_points, uint32_t n, u
 int rt_gather_irradiance(rt_ctx* c, const rt_gather_point* points, uint32_t n, uint32_t max_depth, uint32_t spp, uint32_t seed,
                          rt_irradiance* out, rt_radiance_stats* stats) {
   return path_query_host(c, pq_gather, reinterpret_cast<const rt_ray*>(points), n, max_depth, spp, seed, out, stats);
+}
+
+// ---- probe gathers: SH9 radiance per probe (mi355rt.h "probe gathers"), by composition around the radiance query's kernel:
+// per batch of whole probes k_probe_rays -> k_radiance_query (spp = 1, seed = 0 on the pad' rays) -> k_probe_project
+// (k_probe.hip.h).  Every (probe, sample) is an item of its own, so the cut into batches cannot show in a result.
+static int launch_probe_gather(rt_ctx* c, const void* d_probes, uint32_t n, uint32_t max_depth, uint32_t spp, uint32_t seed,
+                               void* d_out, bool detail) {
+  const PathQueryKind& k = pq_probe;
+  int r = query_scene_ready(c, k.what, true);
+  if (r < 0) return r;
+  const uint32_t per_batch = RT_PROBE_BATCH_SAMPLES / spp;   // whole probes: >= 64, spp being <= 65536
+  const size_t scratch_items = (size_t)std::min(n, per_batch) * spp;
+  if ((r = ensure_buffer(c, c->pr_rays, scratch_items * sizeof(rt_ray), false)) < 0) return r;
+  if ((r = ensure_buffer(c, c->pr_rad, scratch_items * sizeof(rt_radiance), false)) < 0) return r;
+  QueryState& q = c->pr;
+  c->pr_timed = 0;
+  rt_radiance_stats total = rt_radiance_stats();
+  uint32_t batch = 0;
+  for (uint32_t first = 0; first < n; first += per_batch, batch++) {
+    const uint32_t np = std::min(per_batch, n - first);
+    const uint32_t items = np * spp;                         // <= RT_PROBE_BATCH_SAMPLES
+    const float4* probes = (const float4*)d_probes + 2 * (size_t)first;
+    float4* rays = (float4*)c->pr_rays.ptr;
+    float4* rad = (float4*)c->pr_rad.ptr;
+    float4* out = (float4*)d_out + 7 * (size_t)first;
+    {
+      uint32_t a_items = items, a_spp = spp, a_seed = seed;
+      void* args[] = {&probes, &rays, &a_items, &a_spp, &a_seed};
+      HIP_TRY(c, hipLaunchKernel((const void*)rtk::k_probe_rays, dim3((items + 255u) / 256u), dim3(256), args, 0, c->stream));
+    }
+    // the radiance launch between this batch's own event pair
+    if (c->pr_ev.size() < 2 * ((size_t)batch + 1)) c->pr_ev.resize(2 * ((size_t)batch + 1), nullptr);
+    q.ev[0] = c->pr_ev[2 * (size_t)batch];
+    q.ev[1] = c->pr_ev[2 * (size_t)batch + 1];
+    r = launch_path_query(c, k, rays, items, max_depth, 1u, 0u, rad, detail, batch != 0);
+    c->pr_ev[2 * (size_t)batch] = q.ev[0];
+    c->pr_ev[2 * (size_t)batch + 1] = q.ev[1];
+    const bool timed = q.timed;
+    q.ev[0] = q.ev[1] = nullptr;
+    q.timed = false;
+    if (r < 0) {
+      c->pr_last = rt_radiance_stats();
+      return r;
+    }
+    if (timed) c->pr_timed = batch + 1;
+    total.lds = c->pr_last.lds;
+    total.workgroups += c->pr_last.workgroups;
+    {
+      uint32_t a_np = np, a_spp = spp, a_seed = seed;
+      const float4* rad_in = rad;
+      void* args[] = {&probes, &rad_in, &out, &a_np, &a_spp, &a_seed};
+      HIP_TRY(c, hipLaunchKernel((const void*)rtk::k_probe_project, dim3((np + 3u) / 4u), dim3(256), args, 0, c->stream));
+    }
+  }
+  total.rays = n;
+  total.samples = (uint64_t)n * spp;
+  c->pr_last = total;
+  return RT_OK;
+}
+
+int rt_probe_gather_stats(rt_ctx* c, rt_radiance_stats* out) {
+  if (!c || !out) return RT_ERR_INVALID;
+  const int r = path_query_stats(c, pq_probe, out);   // fences the stream; the state itself carries no events
+  if (r < 0) return r;
+  for (uint32_t b = 0; b < c->pr_timed; b++) {
+    float ms = 0.0f;
+    HIP_TRY(c, hipEventElapsedTime(&ms, c->pr_ev[2 * (size_t)b], c->pr_ev[2 * (size_t)b + 1]));
+    out->kernel_ms += (double)ms;
+  }
+  return RT_OK;
+}
+int rt_gather_probes_device(rt_ctx* c, const void* dev_probes, uint32_t n, uint32_t max_depth, uint32_t spp, uint32_t seed,
+                            void* dev_out) {
+  if (!c) return RT_ERR_INVALID;
+  int r = path_query_args_ok(c, pq_probe, n, spp);
+  if (r < 0) return r;
+  if (n == 0) {
+    c->pr_last = rt_radiance_stats();
+    c->pr_timed = 0;
+    return RT_OK;
+  }
+  if ((r = query_device_arrays_ok(c, pq_probe.what, dev_probes, dev_out)) < 0) return r;
+  return launch_probe_gather(c, dev_probes, n, max_depth, spp, seed, dev_out, c->detailed_counters);
+}
+int rt_gather_probes(rt_ctx* c, const rt_probe* probes, uint32_t n, uint32_t max_depth, uint32_t spp, uint32_t seed,
+                     rt_probe_sh9* out, rt_radiance_stats* stats) {
+  if (!c) return RT_ERR_INVALID;
+  int r = path_query_args_ok(c, pq_probe, n, spp);
+  if (r < 0) return r;
+  if (n == 0) {
+    c->pr_last = rt_radiance_stats();
+    c->pr_timed = 0;
+    if (stats) *stats = c->pr_last;
+    return RT_OK;
+  }
+  r = query_from_host(c, c->pr, pq_probe.what, probes, n, out, sizeof(rt_probe_sh9), [&](const void* d_probes, void* d_out) {
+    return launch_probe_gather(c, d_probes, n, max_depth, spp, seed, d_out, stats != nullptr);
+  });
+  if (r < 0) return r;
+  if (stats) return rt_probe_gather_stats(c, stats);
+  return RT_OK;
 }
 
 // ---- lightmap bakes: the texel rule of mi355rt.h as four launches (k_bake.hip.h), then the gather path and the scatter

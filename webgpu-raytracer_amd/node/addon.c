@@ -638,6 +638,28 @@ static napi_value rtGatherIrradiance(napi_env env, napi_callback_info info) {
   return radiance_stats_object(env, &st);
 }
 
+/* ------------------------------------------------------- probe gathers (rt_gather_probes, mi355rt.h) */
+/* (ctx, probes: Float32Array of 8 per probe {position, t_max, 3 unused, pad}, maxDepth, spp, seed, out: Float32Array of 28 per
+ * probe {sh[9][3], hit_fraction}, wantStats) -> status, or the stats object when wantStats and the call succeeded */
+static napi_value rtGatherProbes(napi_env env, napi_callback_info info) {
+  napi_value a[7];
+  void *probes = NULL, *out = NULL;
+  size_t np = 0, no = 0;
+  bool want_stats = false;
+  if (!get_args(env, info, 7, a) || !get_bytes(env, a[1], &probes, &np) || !get_bytes(env, a[5], &out, &no)) return NULL;
+  napi_get_value_bool(env, a[6], &want_stats);
+  const size_t n = np / sizeof(rt_probe);
+  if (np % sizeof(rt_probe) != 0 || no < n * sizeof(rt_probe_sh9) || n > 0x7fffffffu) {
+    napi_throw_range_error(env, NULL, "rtGatherProbes: probes must hold 8 floats per probe and out 28 floats per probe");
+    return NULL;
+  }
+  rt_radiance_stats st;
+  const int rc = rt_gather_probes((rt_ctx*)get_ptr(env, a[0]), (const rt_probe*)probes, (uint32_t)n, get_u32(env, a[2]),
+                                  get_u32(env, a[3]), get_u32(env, a[4]), (rt_probe_sh9*)out, want_stats ? &st : NULL);
+  if (rc < 0 || !want_stats) return make_int(env, rc);
+  return radiance_stats_object(env, &st);
+}
+
 /* ------------------------------------------------------- lightmap bakes (rt_bake_points / rt_bake_irradiance, mi355rt.h) */
 static double get_f64(napi_env env, napi_value v) {
   double x = 0.0;
@@ -796,7 +818,7 @@ static napi_value Init(napi_env env, napi_value exports) {
                {"rtDistWriteBlock", rtDistWriteBlock}, {"rtUnpackStripes", rtUnpackStripes},
                {"rtGatherStripes", rtGatherStripes}, {"rtReadDisplay", rtReadDisplay}, {"rtTraceRays", rtTraceRays},
                {"rtRayQueryStats", rtRayQueryStats}, {"rtTraceRadiance", rtTraceRadiance},
-               {"rtGatherIrradiance", rtGatherIrradiance}, {"rtBakePoints", rtBakePoints},
+               {"rtGatherIrradiance", rtGatherIrradiance}, {"rtGatherProbes", rtGatherProbes}, {"rtBakePoints", rtBakePoints},
                {"rtBakeIrradiance", rtBakeIrradiance}, {"rtBakeAtlasPoints", rtBakeAtlasPoints},
                {"rtBakeAtlasIrradiance", rtBakeAtlasIrradiance}, {"msCreate", msCreate}, {"msDestroy", msDestroy},
                {"msUpdate", msUpdate}, {"msUpdateCamera", msUpdateCamera}, {"msGet", msGet},

@@ -65,6 +65,12 @@ export class WebGPURenderer {
    *  that hit something within tMax.  The stats are a radiance query's with rays = points. */
   gatherIrradiance(points: Float32Array, maxDepth: number, spp: number, opts?: { seed?: number; stats?: boolean }):
     { data: Float32Array; n: number; stats?: RadianceQueryStats };
+  /** Probe gathers (rt_gather_probes): 8 words per probe {position, tMax, 3 unused words, pad}, pad = the bits of a uint32
+   *  below 2^31, the probe's RNG stream id.  `data` holds 28 floats per probe: the SH9 projection of the radiance arriving
+   *  over spp uniform sphere directions drawn on the device, sh[k][c] at 3 k + c, then hitFraction.  The stats are a radiance
+   *  query's with rays = probes; kernel_ms counts the radiance launches only. */
+  gatherProbes(probes: Float32Array, maxDepth: number, spp: number, opts?: { seed?: number; stats?: boolean }):
+    { data: Float32Array; n: number; stats?: RadianceQueryStats };
   /** Lightmap bakes (rt_bake_points): the covered texels of TLAS-order instance `inst`'s width x height atlas as gather points,
    *  in ascending texel index; pad = padBase + texel index.  atlasUv: 2 floats per scene vertex, overriding the scene's uvs.
    *  owner: the Int32Array owner map (global triangle index, -1 = uncovered). */

@@ -202,6 +202,21 @@ class WebGPURenderer {
     if (typeof r === 'object' && r) out.stats = r;
     return out;
   }
+  // ---- probe gathers (rt_gather_probes): the radiance arriving at points in space, over spp directions drawn uniformly on
+  // the sphere on the device, projected onto the nine real spherical harmonics of bands 0 .. 2.  probes = 8 words per probe
+  // {position, tMax, 3 unused words (0), pad}; pad holds the bits of a uint32 below 2^31, the probe's RNG stream id.  opts:
+  // {seed = 0, stats = false}.  Result: 28 floats per probe in .data: sh[k][c] at 3 k + c (coefficient-major, rgb inside),
+  // then hitFraction.  With stats the result also carries .stats.
+  gatherProbes(probes, maxDepth, spp, opts = {}) {
+    if (!(probes instanceof Float32Array) || probes.length % 8 !== 0) throw new TypeError('gatherProbes: a Float32Array of 8 floats per probe');
+    const n = probes.length / 8;
+    const data = new Float32Array(n * 28);
+    const r = native.rtGatherProbes(this._ctx, probes, maxDepth >>> 0, spp >>> 0, (opts.seed || 0) >>> 0, data, !!opts.stats);
+    if (typeof r === 'number') this._check(r, 'gatherProbes');
+    const out = { data, n };
+    if (typeof r === 'object' && r) out.stats = r;
+    return out;
+  }
   // ---- lightmap bakes (rt_bake_points, rt_bake_irradiance): the covered texels of TLAS-order instance `inst`'s width x height
   // atlas as gather points, by the texel rule of include/mi355rt.h.  opts: {tMax = 1e30, padBase = 0, atlasUv = null (a
   // Float32Array of 2 floats per scene vertex overriding the scene's uvs), owner = false}.  Result: {n, points (8 words per

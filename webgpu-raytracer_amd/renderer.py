@@ -197,6 +197,10 @@ def load_library(path=None):
         "rt_gather_irradiance": (i32, [vp, vp, u32, u32, u32, u32, vp, vp]),
         "rt_gather_irradiance_device": (i32, [vp, vp, u32, u32, u32, u32, vp]),
         "rt_irradiance_gather_stats": (i32, [vp, vp]),
+        # probe gathers
+        "rt_gather_probes": (i32, [vp, vp, u32, u32, u32, u32, vp, vp]),
+        "rt_gather_probes_device": (i32, [vp, vp, u32, u32, u32, u32, vp]),
+        "rt_probe_gather_stats": (i32, [vp, vp]),
         # lightmap bakes
         "rt_bake_points": (i32, [vp, vp, vp, u32, vp, vp, u32, vp, vp]),
         "rt_bake_points_device": (i32, [vp, vp, vp, vp, vp, u32, vp, vp]),
@@ -229,6 +233,7 @@ EXPORTED_SYMBOLS = (
     "rt_trace_rays rt_trace_rays_device rt_ray_query_stats "
     "rt_trace_radiance rt_trace_radiance_device rt_radiance_query_stats "
     "rt_gather_irradiance rt_gather_irradiance_device rt_irradiance_gather_stats "
+    "rt_gather_probes rt_gather_probes_device rt_probe_gather_stats "
     "rt_bake_points rt_bake_points_device rt_bake_irradiance "
     "rt_bake_atlas_points rt_bake_atlas_points_device rt_bake_atlas_irradiance").split()
 
@@ -271,6 +276,29 @@ class RtRadianceStats(ctypes.Structure):
 RADIANCE_DTYPE = np.dtype([("rgb", np.float32, (3,)), ("t", np.float32)])
 # irradiance gathers: mirror of rt_irradiance; their stats are an RtRadianceStats (rays = points)
 IRRADIANCE_DTYPE = np.dtype([("rgb", np.float32, (3,)), ("hit_fraction", np.float32)])
+# probe gathers: mirrors of rt_probe / rt_probe_sh9; their stats are an RtRadianceStats (rays = probes)
+PROBE_DTYPE = np.dtype([("position", np.float32, (3,)), ("t_max", np.float32), ("unused", np.float32, (3,)), ("pad", np.uint32)])
+PROBE_SH9_DTYPE = np.dtype([("sh", np.float32, (9, 3)), ("hit_fraction", np.float32)])
+# cosine-lobe convolution of SH bands 0, 1, 2 (Ramamoorthi & Hanrahan 2001): pi, 2 pi / 3, pi / 4
+_SH9_BAND = np.array([np.pi] + [2.0 * np.pi / 3.0] * 3 + [np.pi / 4.0] * 5)
+
+
+def sh9_basis(dirs):
+    """The nine real spherical harmonics of bands 0 .. 2 at unit directions (..., 3) -> (..., 9) float64, in the order and
+    with the constants of the probe rule (mi355rt.h)."""
+    d = np.asarray(dirs, np.float64)
+    x, y, z = d[..., 0], d[..., 1], d[..., 2]
+    return np.stack([np.full_like(x, 0.282094792), 0.488602512 * y, 0.488602512 * z, 0.488602512 * x,
+                     1.092548431 * (x * y), 1.092548431 * (y * z), 0.315391565 * (3.0 * (z * z) - 1.0),
+                     1.092548431 * (x * z), 0.546274215 * (x * x - y * y)], axis=-1)
+
+
+def sh9_irradiance(sh, normals):
+    """Irradiance from SH9 radiance coefficients: sh (..., 9, 3) as gatherProbes returns them (the "sh" field), normals
+    (m, 3) unit vectors -> (..., m, 3) float64, E(n) = sum_k A_band(k) sh[k] Y_k(n) with the cosine-lobe band factors pi,
+    2 pi / 3, pi / 4.  Pure numpy; no ringing filter."""
+    c = np.asarray(sh, np.float64) * _SH9_BAND[:, None]
+    return np.einsum("mk,...kc->...mc", sh9_basis(normals), c)
 
 
 # lightmap bakes: mirror of rt_bake_desc
@@ -616,6 +644,39 @@ class WebGPURenderer:
         """rt_radiance_stats of the last irradiance gather as a dict (blocking)."""
         st = RtRadianceStats()
         self._check(self.L.rt_irradiance_gather_stats(self.ctx, ctypes.addressof(st)), "irradianceGatherStats")
+        return st.as_dict()
+
+    # ---- probe gathers: SH9 radiance at points in space (rt_gather_probes) ----
+    def gatherProbes(self, probes, max_depth, spp, seed=0, stats=False):
+        """probes: (n, 8) float32 in the rt_probe layout {position, t_max, 3 unused words, pad} (or a PROBE_DTYPE array);
+        pad holds the bits of a uint32 below 2^31, the probe's RNG stream id.  Returns a structured array (n,) with the
+        fields sh (9 x 3 floats: coefficient-major, rgb inside) and hit_fraction (PROBE_SH9_DTYPE): the projection of the
+        radiance arriving at each probe, over spp directions drawn uniformly on the sphere on the device, onto the real
+        spherical harmonics of bands 0 .. 2 (sh9_irradiance turns them into irradiance at a normal) - and with stats=True
+        the pair (results, stats dict of rt_radiance_stats with rays = probes: the counting kernel runs)."""
+        p = np.ascontiguousarray(probes)
+        if p.dtype == PROBE_DTYPE:
+            p = p.reshape(-1).view(np.float32).reshape(-1, 8)
+        p = np.ascontiguousarray(p, dtype=np.float32)
+        if p.ndim != 2 or p.shape[1] != 8:
+            raise ValueError("gatherProbes expects an (n, 8) float32 array")
+        n = p.shape[0]
+        out = np.empty(n, dtype=PROBE_SH9_DTYPE)
+        st = RtRadianceStats()
+        self._check(self.L.rt_gather_probes(self.ctx, _ptr(p), n, int(max_depth), int(spp), int(seed) & 0xffffffff, _ptr(out),
+                                            ctypes.addressof(st) if stats else None), "gatherProbes")
+        return (out, st.as_dict()) if stats else out
+
+    def gatherProbesDevice(self, probes_ptr, n, out_ptr, max_depth, spp, seed=0):
+        """Enqueue a probe gather on device arrays (n rt_probe at probes_ptr, n rt_probe_sh9 of 112 bytes to out_ptr; e.g.
+        tensor.data_ptr()) on the context's stream; no host synchronisation."""
+        self._check(self.L.rt_gather_probes_device(self.ctx, ctypes.c_void_p(probes_ptr), int(n), int(max_depth), int(spp),
+                                                   int(seed) & 0xffffffff, ctypes.c_void_p(out_ptr)), "gatherProbesDevice")
+
+    def probeGatherStats(self):
+        """rt_radiance_stats of the last probe gather as a dict (blocking)."""
+        st = RtRadianceStats()
+        self._check(self.L.rt_probe_gather_stats(self.ctx, ctypes.addressof(st)), "probeGatherStats")
         return st.as_dict()
 
     # ---- lightmap bakes: the texels of an instance's UV atlas as gather points (rt_bake_points) ----
