@@ -500,8 +500,8 @@ int rt_probe_gather_stats(rt_ctx* ctx, rt_radiance_stats* out);
  *   output      the covered texels in ASCENDING TEXEL INDEX, compacted: points[j] (rt_gather_point) and texels[j] (u32),
  *               j = 0 .. n-1.  The optional owner map holds W * H i32: the owner's global triangle index, -1 for none.
  * The rule has no run-time freedom: two bakes of one scene give the same words, and a CPU restatement (tests/model/
- * bake_model.cpp) gives them too.  Out of scope: chart packing, dilation of uncovered texels (a host one-liner on the owner
- * map), conservative rasterisation.  Several instances per call: atlas bakes, below.
+ * bake_model.cpp) gives them too.  Out of scope: chart packing, conservative rasterisation.  Several instances per call: atlas
+ * bakes, below; a gutter of copied colour around the charts: atlas dilation, below them.
  * Limits, all RT_ERR_INVALID: a NULL descriptor, reserved != 0, W or H == 0, W * H > 2^24, pad_base + W * H > 2^31 (the
  * gather's pad rule), inst >= the instance count, a NULL output that is needed.  Without a valid scene: RT_ERR_NOT_READY;
  * also when the scene has no draw command for every instance (rt_upload(RT_KIND_DRAW_COMMANDS) was never called).
@@ -552,8 +552,7 @@ int rt_bake_irradiance(rt_ctx* ctx, const rt_bake_desc* desc, const float* atlas
  * Two identities follow.  (A) One entry {inst, 0, 0, W, H} gives, word for word with the pads, what rt_bake_points gives for
  * {inst, W, H, pad_base, t_max}.  (B) Any atlas bake is the composition of its entries' single-instance bakes:
  * rt_bake_points per entry, placed at the rectangle, the lowest entry winning, the pads re-based.
- * Out of scope: chart packing (the caller chooses the rectangles), a t_max per entry, dilation, a device form of the whole
- * bake.
+ * Out of scope: chart packing (the caller chooses the rectangles), a t_max per entry, a device form of the whole bake.
  * Limits, all RT_ERR_INVALID: a NULL descriptor or NULL entries, reserved != 0 (descriptor or any entry), n_entries == 0 or
  * > 65536, W or H == 0, W * H > 2^24, pad_base + W * H > 2^31, any w or h == 0, any rectangle not inside the atlas (x + w
  * <= W and y + h <= H, taken without u32 overflow), any inst >= the instance count, and what the bake entries above say about
@@ -574,6 +573,43 @@ int rt_bake_atlas_points_device(rt_ctx* ctx, const rt_bake_atlas_desc* desc, con
 int rt_bake_atlas_irradiance(rt_ctx* ctx, const rt_bake_atlas_desc* desc, const rt_bake_rect* entries, const float* atlas_uv,
                              uint32_t n_uv_vertices, uint32_t max_depth, uint32_t spp, uint32_t seed, rt_irradiance* atlas_out,
                              uint32_t* n_covered_out, rt_radiance_stats* stats);
+
+/* ---- atlas dilation: "a gutter of copied colour around every chart", the nearest covered texel into the uncovered ones ----
+ * A baked atlas holds {0, 0, 0, -1} wherever no chart covers a texel, and a renderer that samples it bilinearly or through
+ * mip maps blends every chart border with that black.  Dilation copies, into every uncovered texel within `radius` texels of
+ * a chart, the colour of the nearest covered texel.  One ring is simple on the host; a gutter of 4 .. 16 texels, which mip
+ * chains need, is a nearest-source search, and after rt_bake_atlas_points_device plus rt_gather_irradiance_device the atlas
+ * is in HBM and nowhere else - so the search runs there, on a coverage bitmap (csrc/k_dilate.hip.h).
+ *
+ * THE DILATION RULE.  All of it is integer arithmetic; no float is computed, only compared and copied.  Inputs: an
+ * rt_dilate_desc {width W, height H, radius R} (mi355rt_layout.h) and an atlas of W * H texels of 4 f32 {x, y, z, w},
+ * row-major, texel (x, y) at index i = y * W + x.
+ *   coverage   a texel is covered iff w >= 0.0f as a float comparison: NaN is uncovered, -0.0f and +inf are covered, -1.0f
+ *              (no surface) and -2.0f (filled, below) are uncovered.
+ *   source     of an uncovered texel (x, y): among the covered texels (sx, sy) of the atlas with d2 = (sx - x)^2 + (sy - y)^2
+ *              <= R * R, the one with the smallest d2, and among equals the one with the lowest texel index sy * W + sx.
+ *              Texels outside the atlas do not exist.
+ *   result     in place.  A covered texel is untouched.  An uncovered texel with a source receives the source's first three
+ *              words bit for bit and w = -2.0f: "no surface here, colour copied".  An uncovered texel without a source is
+ *              untouched, whatever it holds.
+ *   source map (optional) W * H u32: a covered texel holds its own index, a filled texel its source's index, any other
+ *              texel 0xffffffff.  With it a caller applies the same fill to other layers of the same atlas.
+ *   count      (optional) one u32: the number of filled texels.
+ * Three things follow.  (1) The result does not depend on scheduling: every word is a function of the input alone.  (2)
+ * Dilating a dilated atlas again with the same R gives the same words: filled texels stay uncovered (w = -2.0f) and find the
+ * same sources.  (3) Covered texels are only read and uncovered texels are only written, so in place is safe.
+ * Limits, all RT_ERR_INVALID with messages that begin "dilate atlas:": a NULL descriptor or a NULL atlas, reserved != 0, W or
+ * H == 0, W * H > 2^24 (the bakes' limit), R > RT_DILATE_MAX_RADIUS (24).  R == 0 is valid and fills nothing.
+ * No scene is needed: the calls work on a fresh context, and they leave the renderer and the state of every query as they
+ * were.  Dilation has staging arrays of its own, kept and grown: the bitmap (8 bytes per 64 texels of a row) and, unless the
+ * caller supplies one, the source map.
+ *   rt_dilate_atlas         blocking, host arrays: copies the atlas in, dilates, copies it back; src_out (W * H u32) and
+ *                           filled_out (one u32) may be NULL.
+ *   rt_dilate_atlas_device  the same on device-accessible arrays (16-byte aligned - the single count word too - and on the
+ *                           context's device); dev_src and dev_filled may be NULL.  Only enqueues on the context's stream
+ *                           (rt_set_stream respected). */
+int rt_dilate_atlas(rt_ctx* ctx, const rt_dilate_desc* desc, float* atlas, uint32_t* src_out, uint32_t* filled_out);
+int rt_dilate_atlas_device(rt_ctx* ctx, const rt_dilate_desc* desc, void* dev_atlas, void* dev_src, void* dev_filled);
 
 /* ---- the sharded image: one picture rendered by `world` contexts ("ranks"), assembled on rank 0 ----
  * Rank k owns the image rows y with (y / stripe_rows) % world == k and traces only those (rt_set_stripes).  Its COMPACT

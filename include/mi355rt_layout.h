@@ -191,8 +191,17 @@ typedef struct rt_bake_rect { /* 32 B: two 16-byte loads of k_atlas_owner / k_at
   uint32_t reserved[3];       /* 0 */
 } rt_bake_rect;
 
+/* ---- atlas dilation (rt_dilate_atlas, mi355rt.h): the gutter fill of a baked atlas ---- */
+#define RT_DILATE_MAX_RADIUS 24u
+typedef struct rt_dilate_desc { /* 32 B */
+  uint32_t width, height;     /* of the atlas, in texels: both >= 1, width * height <= 2^24 */
+  uint32_t radius;            /* of the gutter, in texels: 0 .. RT_DILATE_MAX_RADIUS; 0 fills nothing */
+  uint32_t reserved[5];       /* 0 */
+} rt_dilate_desc;
+
 #ifdef __cplusplus
 }
+static_assert(sizeof(rt_dilate_desc) == 32, "rt_dilate_desc is 32 bytes");
 static_assert(sizeof(rt_bake_desc) == 32, "rt_bake_desc is 32 bytes");
 static_assert(sizeof(rt_bake_atlas_desc) == 32, "rt_bake_atlas_desc is 32 bytes");
 static_assert(sizeof(rt_bake_rect) == 32, "rt_bake_rect is 32 bytes");

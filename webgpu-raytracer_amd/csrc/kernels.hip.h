@@ -25,6 +25,8 @@
 //                             k_radiance_query and the SH9 projection behind it (rt_gather_probes)
 //   k_bake.hip.h              k_bake_owner / _count / _scan / _emit: the UV-space rasteriser that makes such points from the
 //                             texels of an instance's atlas (rt_bake_points), and k_bake_scatter, the way back
+//   k_dilate.hip.h            k_dilate_mask / _source / _apply: the nearest-texel gutter fill of a baked atlas on a coverage
+//                             bitmap (rt_dilate_atlas)
 //   k_texture_post.hip.h      k_resize_texture; k_postprocess = PostProcess.wgsl `main` (:103-176)
 //   k_validate.hip.h          k_validate_scene: every index the kernels follow, checked once per upload
 //   k_stripes.hip.h           k_pack_stripes / k_unpack_stripes: the copies of the sharded image's gather
@@ -56,6 +58,7 @@
 #include "k_gather.hip.h"
 #include "k_probe.hip.h"
 #include "k_bake.hip.h"
+#include "k_dilate.hip.h"
 #include "k_wavefront.hip.h"
 #include "k_rayquery.hip.h"
 #include "k_texture_post.hip.h"

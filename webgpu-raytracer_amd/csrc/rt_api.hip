@@ -81,6 +81,12 @@ struct BakeState {
   int ring_next = 0;
 };
 
+// What atlas dilation (rt_dilate_atlas) keeps between calls, kept and grown: the staged atlas and the filled count of the host
+// entry, the coverage bitmap, and the source map of a call that asks for none.
+struct DilateState {
+  DeviceBuffer atlas, filled, bitmap, src;
+};
+
 }  // namespace
 
 struct rt_ctx {
@@ -230,6 +236,7 @@ struct rt_ctx {
   std::vector<hipEvent_t> pr_ev;    // 2 per batch
   uint32_t pr_timed = 0;            // batches of the last call that recorded their events
   BakeState bk;
+  DilateState dl;
 
   // kernel timing
   bool timing = false;
@@ -963,6 +970,7 @@ void rt_destroy(rt_ctx* c) {
                          &c->pr.in, &c->pr.out, &c->pr.counters, &c->pr_rays, &c->pr_rad,
                          &c->bk.uv, &c->bk.owner, &c->bk.blocks, &c->bk.count, &c->bk.points, &c->bk.texels, &c->bk.results,
                          &c->bk.atlas, &c->bk.entries, &c->bk.items, &c->bk.owner64,
+                         &c->dl.atlas, &c->dl.filled, &c->dl.bitmap, &c->dl.src,
                          &c->tex_staging, &c->bv_in, &c->bv_tri, &c->bv_order, &c->bv_nodes, &c->bv_out,
                          &c->bv_counters, &c->bv_big, &c->val_roots, &c->val_bad, &c->tnodes, &c->node_key, &c->node_newidx,
                          &c->inst_root, &c->root_w, &c->treelet_work, &c->pairs, &c->pair_of, &c->pair_parent, &c->root_rec,
@@ -2742,6 +2750,76 @@ int rt_bake_atlas_irradiance(rt_ctx* c, const rt_bake_atlas_desc* d, const rt_ba
         B.owner = A.owner;
         hipLaunchKernelGGL(rtk::k_atlas_scatter, dim3(A.n_blocks), dim3(256), 0, c->stream, B);
       });
+}
+
+// ---- atlas dilation: the nearest-texel gutter fill of mi355rt.h "atlas dilation" as three launches (k_dilate.hip.h).  No
+// scene, no renderer state: only the context's device and stream.
+static const char* const kDilate = "dilate atlas";
+static int dilate_desc_ok(rt_ctx* c, const rt_dilate_desc* d, const void* atlas) {
+  const std::string w(kDilate);
+  if (!d) return fail(c, RT_ERR_INVALID, w + ": NULL descriptor");
+  if (!atlas) return fail(c, RT_ERR_INVALID, w + ": NULL atlas");
+  if (d->reserved[0] | d->reserved[1] | d->reserved[2] | d->reserved[3] | d->reserved[4])
+    return fail(c, RT_ERR_INVALID, w + ": reserved words must be 0");
+  if (d->width == 0 || d->height == 0) return fail(c, RT_ERR_INVALID, w + ": width and height must be >= 1");
+  if ((uint64_t)d->width * d->height > (1ull << 24)) return fail(c, RT_ERR_INVALID, w + ": width * height must be <= 2^24");
+  if (d->radius > RT_DILATE_MAX_RADIUS) return fail(c, RT_ERR_INVALID, w + ": radius must be <= 24");
+  return RT_OK;
+}
+// Enqueue mask, source and apply on the context's stream.  d_src null: the source map lives in the dilation's own scratch;
+// d_filled null: nothing is counted.
+static int launch_dilate(rt_ctx* c, const rt_dilate_desc* d, void* d_atlas, void* d_src, void* d_filled) {
+  const uint32_t texels = d->width * d->height;
+  rtk::DilateArgs A;
+  A.W = d->width;
+  A.H = d->height;
+  A.R = d->radius;
+  A.wpr = (d->width + 63u) / 64u;
+  A.tiles_x = (d->width + RT_DILATE_TILE - 1u) / RT_DILATE_TILE;
+  const uint32_t tiles_y = (d->height + RT_DILATE_TILE - 1u) / RT_DILATE_TILE;
+  const uint32_t n_words = A.H * A.wpr;   // <= 2^24: a row of W texels has at most W words
+  int r;
+  if ((r = ensure_buffer(c, c->dl.bitmap, (size_t)n_words * 8, true)) < 0) return r;
+  if (!d_src) {
+    if ((r = ensure_buffer(c, c->dl.src, (size_t)texels * 4, true)) < 0) return r;
+    d_src = c->dl.src.ptr;
+  }
+  A.atlas = (float4*)d_atlas;
+  A.bitmap = (uint64_t*)c->dl.bitmap.ptr;
+  A.src = (uint32_t*)d_src;
+  A.filled = (uint32_t*)d_filled;
+  if (d_filled) HIP_TRY(c, hipMemsetAsync(d_filled, 0, 4, c->stream));
+  hipLaunchKernelGGL(rtk::k_dilate_mask, dim3((n_words + 3u) / 4u), dim3(256), 0, c->stream, A);
+  hipLaunchKernelGGL(rtk::k_dilate_source, dim3(A.tiles_x * tiles_y), dim3(256), 0, c->stream, A);
+  hipLaunchKernelGGL(rtk::k_dilate_apply, dim3((texels + 255u) / 256u), dim3(256), 0, c->stream, A);
+  HIP_TRY(c, hipGetLastError());
+  return RT_OK;
+}
+
+int rt_dilate_atlas_device(rt_ctx* c, const rt_dilate_desc* d, void* dev_atlas, void* dev_src, void* dev_filled) {
+  if (!c) return RT_ERR_INVALID;
+  int r = dilate_desc_ok(c, d, dev_atlas);
+  if (r < 0) return r;
+  if ((r = query_device_arrays_ok(c, kDilate, dev_atlas, dev_src ? dev_src : dev_atlas)) < 0) return r;
+  if (dev_filled && (r = query_device_arrays_ok(c, kDilate, dev_atlas, dev_filled)) < 0) return r;
+  return launch_dilate(c, d, dev_atlas, dev_src, dev_filled);
+}
+
+int rt_dilate_atlas(rt_ctx* c, const rt_dilate_desc* d, float* atlas, uint32_t* src_out, uint32_t* filled_out) {
+  if (!c) return RT_ERR_INVALID;
+  int r = dilate_desc_ok(c, d, atlas);
+  if (r < 0) return r;
+  HIP_TRY(c, hipSetDevice(c->device));
+  const size_t texels = (size_t)d->width * d->height;
+  if ((r = ensure_buffer(c, c->dl.atlas, texels * 16, true)) < 0) return r;
+  if ((r = ensure_buffer(c, c->dl.filled, 16, false)) < 0) return r;
+  HIP_TRY(c, hipMemcpyAsync(c->dl.atlas.ptr, atlas, texels * 16, hipMemcpyHostToDevice, c->stream));
+  if ((r = launch_dilate(c, d, c->dl.atlas.ptr, nullptr, filled_out ? c->dl.filled.ptr : nullptr)) < 0) return r;
+  HIP_TRY(c, hipMemcpyAsync(atlas, c->dl.atlas.ptr, texels * 16, hipMemcpyDeviceToHost, c->stream));
+  if (src_out) HIP_TRY(c, hipMemcpyAsync(src_out, c->dl.src.ptr, texels * 4, hipMemcpyDeviceToHost, c->stream));
+  if (filled_out) HIP_TRY(c, hipMemcpyAsync(filled_out, c->dl.filled.ptr, 4, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return RT_OK;
 }
 
 // ---- the kernels of compute().  Variant 0, the one-pixel-per-lane megakernel: one tile per workgroup, no dynamic LDS.

@@ -801,6 +801,32 @@ static napi_value rtBakeAtlasIrradiance(napi_env env, napi_callback_info info) {
   return obj;
 }
 
+/* ------------------------------------------------------- atlas dilation (rt_dilate_atlas, mi355rt.h) */
+/* (ctx, width, height, radius, atlas: Float32Array of 4 per texel, dilated in place, src: Uint32Array of width * height or
+ * null) -> the number of filled texels, or a negative status */
+static napi_value rtDilateAtlas(napi_env env, napi_callback_info info) {
+  napi_value a[6];
+  void *atlas = NULL, *src = NULL;
+  size_t na = 0, ns = 0;
+  if (!get_args(env, info, 6, a) || !get_bytes(env, a[4], &atlas, &na) || !get_bytes(env, a[5], &src, &ns)) return NULL;
+  rt_dilate_desc d;
+  memset(&d, 0, sizeof(d));
+  d.width = get_u32(env, a[1]);
+  d.height = get_u32(env, a[2]);
+  d.radius = get_u32(env, a[3]);
+  const size_t texels = (size_t)d.width * d.height;
+  if (na / 16 < texels || (src && ns / 4 < texels)) {
+    napi_throw_range_error(env, NULL, "rtDilateAtlas: atlas must hold 4 floats per texel and src width * height words");
+    return NULL;
+  }
+  uint32_t n = 0;
+  const int rc = rt_dilate_atlas((rt_ctx*)get_ptr(env, a[0]), &d, (float*)atlas, (uint32_t*)src, &n);
+  if (rc < 0) return make_int(env, rc);
+  napi_value r;
+  napi_create_uint32(env, n, &r);
+  return r;
+}
+
 static napi_value Init(napi_env env, napi_value exports) {
   static const struct {
     const char* name;
@@ -820,7 +846,7 @@ static napi_value Init(napi_env env, napi_value exports) {
                {"rtRayQueryStats", rtRayQueryStats}, {"rtTraceRadiance", rtTraceRadiance},
                {"rtGatherIrradiance", rtGatherIrradiance}, {"rtGatherProbes", rtGatherProbes}, {"rtBakePoints", rtBakePoints},
                {"rtBakeIrradiance", rtBakeIrradiance}, {"rtBakeAtlasPoints", rtBakeAtlasPoints},
-               {"rtBakeAtlasIrradiance", rtBakeAtlasIrradiance}, {"msCreate", msCreate}, {"msDestroy", msDestroy},
+               {"rtBakeAtlasIrradiance", rtBakeAtlasIrradiance}, {"rtDilateAtlas", rtDilateAtlas}, {"msCreate", msCreate}, {"msDestroy", msDestroy},
                {"msUpdate", msUpdate}, {"msUpdateCamera", msUpdateCamera}, {"msGet", msGet},
                {"msTextureCount", msTextureCount}, {"msTexture", msTexture},
                {"msAnimationNames", msAnimationNames}, {"msSetAnimation", msSetAnimation},

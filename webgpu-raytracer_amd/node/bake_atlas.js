@@ -1,19 +1,24 @@
 'use strict';
 // Bake the lightmap of the first N instances of a scene into ONE atlas and write it as a PNG:
-// usage: node bake_atlas.js [scene] [N] [cell] [out.png] [maxDepth] [spp] [seed]   defaults: instanced1000, 64, 32, atlas.png, 4, 16, 0
+// usage: node bake_atlas.js [scene] [N] [cell] [out.png] [maxDepth] [spp] [seed] [--dilate R]
+// defaults: instanced1000, 64, 32, atlas.png, 4, 16, 0, no dilation
 // The atlas is a square grid of ceil(sqrt(N)) x ceil(sqrt(N)) rectangles of cell x cell texels, instance e in rectangle e.
 // Instances of one geometry share their vertices and so their chart: the rectangle is what tells their texels apart.  The
 // chart itself is an override layout made here - triangle k of a geometry gets cell k of a ceil(sqrt(n)) grid of the unit
 // square, as the triangle (0.11, 0.13) (0.89, 0.12) (0.12, 0.87) of its cell - one layout per distinct geometry, merged into
 // one array (for meshes whose triangles share no vertices across geometries).  One bakeAtlasIrradiance call bakes them all:
 // one point pass, one gather, one scatter.  The picture shows pi * (E / pi) * albedo with albedo = 0.8 and gamma 2.2; texels
-// without a surface are transparent.  Prints one JSON line.
+// without a surface are transparent.  --dilate R (1 .. 24) puts a gutter of R texels of copied colour around every chart
+// (dilateAtlas); its texels are drawn like covered ones.  Prints one JSON line.
 const fs = require('fs');
 const { WebGPURenderer, WorldBridge, encodePng } = require('./index.js');
 
 (async () => {
+  const argv = process.argv.slice(2);
+  const at = argv.indexOf('--dilate');
+  const dilate = at >= 0 ? parseInt(argv.splice(at, 2)[1], 10) : 0;
   const [scene = 'instanced1000', count = '64', cellSize = '32', outPath = 'atlas.png', depth = '4', spp = '16', seed = '0'] =
-    process.argv.slice(2);
+    argv;
   const bridge = new WorldBridge();
   await bridge.initWasm();
   await bridge.loadScene(scene);
@@ -52,20 +57,22 @@ const { WebGPURenderer, WorldBridge, encodePng } = require('./index.js');
   const size = side * cell;
   const bake = renderer.bakeAtlasIrradiance(entries, size, size, parseInt(depth, 10), parseInt(spp, 10),
     { atlasUv, seed: parseInt(seed, 10), stats: true });
+  let filled = 0;
+  if (dilate > 0) ({ data: bake.data, filled } = renderer.dilateAtlas(bake.data, size, size, dilate));
   const rgba = new Uint8Array(size * size * 4);
   const albedo = 0.8;
   let lit = 0;
   for (let i = 0; i < size * size; i++) {
-    if (bake.data[4 * i + 3] < 0) continue;   // no surface
+    if (bake.data[4 * i + 3] < 0 && bake.data[4 * i + 3] !== -2) continue;   // no surface, no copied colour
     for (let c = 0; c < 3; c++) {
       const v = Math.PI * bake.data[4 * i + c] * albedo;
       rgba[4 * i + c] = Math.round(255 * Math.pow(Math.min(Math.max(v, 0), 1), 1 / 2.2));
     }
     rgba[4 * i + 3] = 255;
-    if (bake.data[4 * i] > 0) lit++;
+    if (bake.data[4 * i] > 0 && bake.data[4 * i + 3] >= 0) lit++;   // covered texels only, not the gutter
   }
   fs.writeFileSync(outPath, Buffer.from(encodePng(rgba, size, size)));
   console.log(JSON.stringify({ scene, entries: n, geometries: geometries.size, size, covered: bake.covered, lit, out: outPath,
-    stats: bake.stats }));
+    ...(dilate > 0 ? { dilate, filled } : {}), stats: bake.stats }));
   renderer.destroy();
 })().catch((e) => { console.error(e); process.exit(1); });

@@ -1,6 +1,6 @@
 'use strict';
 // Bake a lightmap of the floor of the Cornell box and write it as a PNG:
-// usage: node bake_lightmap.js [size] [out.png] [maxDepth] [spp] [seed]      defaults: 256, bake.png, 4, 64, 0
+// usage: node bake_lightmap.js [size] [out.png] [maxDepth] [spp] [seed] [--dilate R]     defaults: 256, bake.png, 4, 64, 0, no dilation
 // The box is one instance whose quads all carry the uvs (0,0) .. (1,1), so the scene's own uvs would lay every quad over the
 // whole atlas.  The example therefore supplies an override layout: the floor - the two largest triangles in the plane
 // y = min y - gets u = (x - min x) / (max x - min x), v = (z - min z) / (max z - min z); every other vertex goes to (-1, -1),
@@ -9,12 +9,16 @@
 // gather below the floor and return black.  The example shows the three steps instead: bakePoints, the normals turned
 // towards the middle of the room on the host, gatherIrradiance, and the scatter by texel index.
 // The gather returns E / pi per point; the picture shows pi * (E / pi) * albedo with albedo = 0.8 and gamma 2.2: the floor seen
-// from above, dark where the two boxes stand and in their shadows.  Prints one JSON line.
+// from above, dark where the two boxes stand and in their shadows.  --dilate R (1 .. 24) puts a gutter of R texels of copied
+// colour around the chart (dilateAtlas); its texels are drawn like covered ones.  Prints one JSON line.
 const fs = require('fs');
 const { WebGPURenderer, WorldBridge, encodePng } = require('./index.js');
 
 (async () => {
-  const [size = '256', outPath = 'bake.png', depth = '4', spp = '64', seed = '0'] = process.argv.slice(2);
+  const argv = process.argv.slice(2);
+  const at = argv.indexOf('--dilate');
+  const dilate = at >= 0 ? parseInt(argv.splice(at, 2)[1], 10) : 0;
+  const [size = '256', outPath = 'bake.png', depth = '4', spp = '64', seed = '0'] = argv;
   const scene = 'cornell', inst = 0;
   const n = parseInt(size, 10);
   const bridge = new WorldBridge();
@@ -71,19 +75,22 @@ const { WebGPURenderer, WorldBridge, encodePng } = require('./index.js');
   const bake = { data: new Float32Array(n * n * 4), covered: pts.n, stats: res.stats };
   for (let i = 0; i < n * n; i++) bake.data[4 * i + 3] = -1;   // no surface
   for (let j = 0; j < pts.n; j++) bake.data.set(res.data.subarray(4 * j, 4 * j + 4), 4 * pts.texels[j]);
+  let filled = 0;
+  if (dilate > 0) ({ data: bake.data, filled } = renderer.dilateAtlas(bake.data, n, n, dilate));
   const rgba = new Uint8Array(n * n * 4);
   const albedo = 0.8;
   let lit = 0;
   for (let i = 0; i < n * n; i++) {
-    if (bake.data[4 * i + 3] < 0) continue;   // no surface
+    if (bake.data[4 * i + 3] < 0 && bake.data[4 * i + 3] !== -2) continue;   // no surface, no copied colour
     for (let c = 0; c < 3; c++) {
       const v = Math.PI * bake.data[4 * i + c] * albedo;
       rgba[4 * i + c] = Math.round(255 * Math.pow(Math.min(Math.max(v, 0), 1), 1 / 2.2));
     }
     rgba[4 * i + 3] = 255;
-    if (bake.data[4 * i] > 0) lit++;
+    if (bake.data[4 * i] > 0 && bake.data[4 * i + 3] >= 0) lit++;   // covered texels only, not the gutter
   }
   fs.writeFileSync(outPath, Buffer.from(encodePng(rgba, n, n)));
-  console.log(JSON.stringify({ scene, inst, size: n, floorTriangles: floor.length, covered: bake.covered, lit, out: outPath, stats: bake.stats }));
+  console.log(JSON.stringify({ scene, inst, size: n, floorTriangles: floor.length, covered: bake.covered, lit, out: outPath,
+    ...(dilate > 0 ? { dilate, filled } : {}), stats: bake.stats }));
   renderer.destroy();
 })().catch((e) => { console.error(e); process.exit(1); });

@@ -93,6 +93,12 @@ export class WebGPURenderer {
   bakeAtlasIrradiance(entries: number[][] | Uint32Array, width: number, height: number, maxDepth: number, spp: number,
                       opts?: { tMax?: number; padBase?: number; atlasUv?: Float32Array | null; seed?: number; stats?: boolean }):
     { data: Float32Array; width: number; height: number; covered: number; stats?: RadianceQueryStats };
+  /** Atlas dilation (rt_dilate_atlas): every uncovered texel (fourth float < 0 or NaN) within `radius` (0 .. 24) texels of a
+   *  covered one receives the first three words of the nearest covered texel, the lowest texel index among equally near
+   *  ones, and -2 as its fourth.  `data` is a new array; `src` the source map (own index in covered texels, the source's in
+   *  filled ones, 0xffffffff elsewhere). */
+  dilateAtlas(atlas: Float32Array, width: number, height: number, radius: number, opts?: { src?: boolean }):
+    { data: Float32Array; width: number; height: number; filled: number; src?: Uint32Array };
   destroy(): void;
 }
 export class WorldBridge {

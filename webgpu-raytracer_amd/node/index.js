@@ -277,6 +277,22 @@ class WebGPURenderer {
     if (r.stats) out.stats = r.stats;
     return out;
   }
+  // ---- atlas dilation (rt_dilate_atlas): a gutter of copied colour around the charts of a baked atlas.  atlas = 4 floats per
+  // texel, covered where the fourth is >= 0 (as the bakes return it).  Every uncovered texel within `radius` (0 .. 24) texels
+  // of a covered one receives the first three words of the nearest covered texel - the lowest texel index among equally near
+  // ones - and -2 as its fourth, by the dilation rule of include/mi355rt.h.  opts: {src = false}.  Result: {data (a new
+  // Float32Array), width, height, filled} and with src the Uint32Array source map (own index in covered texels, the source's
+  // in filled ones, 0xffffffff elsewhere).
+  dilateAtlas(atlas, width, height, radius, opts = {}) {
+    if (!(atlas instanceof Float32Array) || atlas.length !== width * height * 4) throw new TypeError('dilateAtlas: a Float32Array of 4 floats per texel');
+    const data = atlas.slice();   // a copy of the bytes: NaN payloads stay
+    const src = opts.src ? new Uint32Array(width * height) : null;
+    const filled = native.rtDilateAtlas(this._ctx, width >>> 0, height >>> 0, radius >>> 0, data, src);
+    this._check(filled, 'dilateAtlas');
+    const out = { data, width, height, filled };
+    if (src) out.src = src;
+    return out;
+  }
   destroy() { if (this._ctx) { native.rtDestroy(this._ctx); this._ctx = null; } }
 }
 

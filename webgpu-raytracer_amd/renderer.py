@@ -209,6 +209,9 @@ def load_library(path=None):
         "rt_bake_atlas_points": (i32, [vp, vp, vp, vp, u32, vp, vp, u32, vp, vp]),
         "rt_bake_atlas_points_device": (i32, [vp, vp, vp, vp, vp, vp, u32, vp, vp]),
         "rt_bake_atlas_irradiance": (i32, [vp, vp, vp, vp, u32, u32, u32, u32, vp, vp, vp]),
+        # atlas dilation
+        "rt_dilate_atlas": (i32, [vp, vp, vp, vp, vp]),
+        "rt_dilate_atlas_device": (i32, [vp, vp, vp, vp, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(L, name)  # AttributeError here = header/library mismatch
@@ -235,7 +238,8 @@ EXPORTED_SYMBOLS = (
     "rt_gather_irradiance rt_gather_irradiance_device rt_irradiance_gather_stats "
     "rt_gather_probes rt_gather_probes_device rt_probe_gather_stats "
     "rt_bake_points rt_bake_points_device rt_bake_irradiance "
-    "rt_bake_atlas_points rt_bake_atlas_points_device rt_bake_atlas_irradiance").split()
+    "rt_bake_atlas_points rt_bake_atlas_points_device rt_bake_atlas_irradiance "
+    "rt_dilate_atlas rt_dilate_atlas_device").split()
 
 
 # ---- ray queries: mirrors of rt_ray / rt_ray_hit / rt_ray_stats (include/mi355rt_layout.h)
@@ -316,6 +320,12 @@ class RtBakeAtlasDesc(ctypes.Structure):
 class RtBakeRect(ctypes.Structure):
     _fields_ = [("inst", ctypes.c_uint32), ("x", ctypes.c_uint32), ("y", ctypes.c_uint32), ("width", ctypes.c_uint32),
                 ("height", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 3)]
+
+
+# atlas dilation: mirror of rt_dilate_desc
+class RtDilateDesc(ctypes.Structure):
+    _fields_ = [("width", ctypes.c_uint32), ("height", ctypes.c_uint32), ("radius", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32 * 5)]
 
 
 def _ptr(a):
@@ -726,11 +736,13 @@ class WebGPURenderer:
                                                  ctypes.c_void_p(count_ptr or 0), ctypes.c_void_p(owner_ptr or 0)),
                     "bakePointsDevice")
 
-    def bakeIrradiance(self, inst, width, height, max_depth, spp, seed=0, t_max=1e30, pad_base=0, atlas_uv=None, stats=False):
+    def bakeIrradiance(self, inst, width, height, max_depth, spp, seed=0, t_max=1e30, pad_base=0, atlas_uv=None, stats=False,
+                       dilate=0):
         """The whole bake: points, the irradiance gather on them, scatter.  Returns the (height, width) IRRADIANCE_DTYPE
         atlas - texel texels[j] holds what gatherIrradiance returns for points[j] (E / pi: multiply by pi * albedo for a
         Lambert texel's outgoing radiance), uncovered texels are {0, 0, 0, -1} - and with stats=True the triple (atlas,
-        number of covered texels, stats dict of the gather)."""
+        number of covered texels, stats dict of the gather).  dilate > 0: dilateAtlas with that radius on the returned atlas
+        (filled texels carry hit_fraction -2); it costs one more round trip of the atlas to the device and back."""
         d = self._bake_desc(inst, width, height, t_max, pad_base)
         uv, uv_ptr, n_uv = self._atlas_uv(atlas_uv)
         out = np.empty((int(height), int(width)), dtype=IRRADIANCE_DTYPE)
@@ -739,6 +751,8 @@ class WebGPURenderer:
         self._check(self.L.rt_bake_irradiance(self.ctx, ctypes.addressof(d), uv_ptr, n_uv, int(max_depth), int(spp),
                                               int(seed) & 0xffffffff, _ptr(out), ctypes.addressof(n),
                                               ctypes.addressof(st) if stats else None), "bakeIrradiance")
+        if dilate > 0:
+            out = self.dilateAtlas(out, dilate)
         return (out, n.value, st.as_dict()) if stats else out
 
     # ---- atlas bakes: a list of (instance, rectangle) entries into one atlas (rt_bake_atlas_points) ----
@@ -785,10 +799,11 @@ class WebGPURenderer:
                     "bakeAtlasPointsDevice")
 
     def bakeAtlasIrradiance(self, entries, width, height, max_depth, spp, seed=0, t_max=1e30, pad_base=0, atlas_uv=None,
-                            stats=False):
+                            stats=False, dilate=0):
         """The whole atlas bake: the points of all entries, ONE irradiance gather on them, scatter.  Returns the (height,
         width) IRRADIANCE_DTYPE atlas as bakeIrradiance does - and with stats=True the triple (atlas, number of covered
-        texels, stats dict of the gather)."""
+        texels, stats dict of the gather).  dilate > 0: dilateAtlas with that radius on the returned atlas, at the price of
+        one more round trip of the atlas to the device and back."""
         d, rects = self._atlas_args(entries, width, height, t_max, pad_base)
         uv, uv_ptr, n_uv = self._atlas_uv(atlas_uv)
         out = np.empty((int(height), int(width)), dtype=IRRADIANCE_DTYPE)
@@ -797,7 +812,50 @@ class WebGPURenderer:
         self._check(self.L.rt_bake_atlas_irradiance(self.ctx, ctypes.addressof(d), _ptr(rects), uv_ptr, n_uv, int(max_depth),
                                                     int(spp), int(seed) & 0xffffffff, _ptr(out), ctypes.addressof(n),
                                                     ctypes.addressof(st) if stats else None), "bakeAtlasIrradiance")
+        if dilate > 0:
+            out = self.dilateAtlas(out, dilate)
         return (out, n.value, st.as_dict()) if stats else out
+
+    # ---- atlas dilation: the nearest covered texel into the uncovered ones around it (rt_dilate_atlas) ----
+    @staticmethod
+    def _dilate_desc(width, height, radius):
+        d = RtDilateDesc()
+        d.width, d.height, d.radius = int(width), int(height), int(radius)
+        return d
+
+    def dilateAtlas(self, atlas, radius, src=False, filled=False):
+        """atlas: an (H, W, 4) float32 array (or an (H, W) IRRADIANCE_DTYPE one, as the bakes return it), covered where its
+        fourth component is >= 0.  Returns a NEW array of the same shape in which every uncovered texel within `radius` (0
+        .. 24) texels of a covered one holds the first three words of the nearest covered texel - the lowest texel index
+        among equally near ones - and -2 as its fourth; by the dilation rule of include/mi355rt.h.  src=True adds the (H,
+        W) uint32 source map (own index in covered texels, the source's in filled ones, 0xffffffff elsewhere), filled=True
+        the number of filled texels: (atlas[, src][, filled])."""
+        a = np.ascontiguousarray(atlas)
+        if a.dtype == IRRADIANCE_DTYPE and a.ndim == 2:
+            out = a.copy()
+            height, width = a.shape
+        else:
+            out = np.array(a, dtype=np.float32, order="C")
+            if out.ndim != 3 or out.shape[2] != 4:
+                raise ValueError("dilateAtlas expects an (H, W, 4) float32 array")
+            height, width = out.shape[:2]
+        d = self._dilate_desc(width, height, radius)
+        smap = np.empty((height, width), np.uint32) if src else None
+        n = ctypes.c_uint32(0)
+        self._check(self.L.rt_dilate_atlas(self.ctx, ctypes.addressof(d), _ptr(out) if out.size else None,
+                                           _ptr(smap) if src else None, ctypes.addressof(n) if filled else None),
+                    "dilateAtlas")
+        res = (out,) + ((smap,) if src else ()) + ((n.value,) if filled else ())
+        return res if len(res) > 1 else out
+
+    def dilateAtlasDevice(self, atlas_ptr, width, height, radius, src_ptr=0, filled_ptr=0):
+        """Enqueue a dilation, in place, of the width x height atlas of 16-byte texels at atlas_ptr (e.g. tensor.data_ptr())
+        on the context's stream; no host synchronisation.  src_ptr: width * height uint32 for the source map, filled_ptr:
+        one uint32 for the count, 0 = not wanted.  Every pointer must be 16-byte aligned and lie on the context's device."""
+        d = self._dilate_desc(width, height, radius)
+        self._check(self.L.rt_dilate_atlas_device(self.ctx, ctypes.addressof(d), ctypes.c_void_p(atlas_ptr or 0),
+                                                  ctypes.c_void_p(src_ptr or 0), ctypes.c_void_p(filled_ptr or 0)),
+                    "dilateAtlasDevice")
 
     # ---- the sharded image (rt_dist_*): this context as one rank of `world` ----
     def distInit(self, rank, world, stripe_rows=8, unique_id=None):
