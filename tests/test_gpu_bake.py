@@ -1,7 +1,8 @@
 """Lightmap bakes on the GPU (rt_bake_points / rt_bake_points_device / rt_bake_irradiance, csrc/k_bake.hip.h) against the
 reference model (tests/model/bake_model.cpp, tied to a float64 brute force by tests/test_bake_model.py): points, texel
 indices, count and owner map word for word; the hand-worked cases; the bake as the composition of the GPU's own points and
-gather; independence of scheduling and of cap; the device entry on a torch side stream; the device-resident animated world;
+gather; independence of scheduling and of cap; the device entry on a torch side stream, and its owner map without points; scratch shared with atlas bakes; the
+device-resident animated world;
 no side effect on a render; the error returns.
 
 The atlas sizes are the smallest that cross the kernels' edges: 1 x 1, one row of 130 (three waves of the count pass, one
@@ -262,6 +263,56 @@ def test_device_entry_on_a_torch_side_stream(W):
         side.synchronize()
         assert int(d_count[0]) == n
         r.setStream(None)
+    finally:
+        r.destroy()
+
+
+@pytest.mark.parametrize("size", ((65, 63), (1, 1)))
+def test_device_entry_owner_map_without_points(W, size):
+    """cap = 0 and no point arrays, but an owner_ptr: the count and the u32 owner map of the model, all ones where nothing
+    covers.  65 x 63 is no multiple of 256 texels, so the last workgroup of every per-texel launch is partial."""
+    import torch
+    b, m = _scene(W, "instanced1000")
+    width, height = size
+    want = m.bakePoints(0, width, height)
+    assert len(want[1]) > 0.1 * width * height
+    r = _renderer(W, b)
+    try:
+        side = torch.cuda.Stream()
+        r.setStream(side.cuda_stream)
+        with torch.cuda.stream(side):
+            d_count = torch.zeros(4, dtype=torch.int32, device="cuda")
+            d_owner = torch.zeros(width * height, dtype=torch.int32, device="cuda")
+            r.bakePointsDevice(0, width, height, None, None, 0, d_count.data_ptr(), owner_ptr=d_owner.data_ptr())
+        side.synchronize()
+        owner = d_owner.cpu().numpy().reshape(height, width)
+        assert int(d_count[0]) == len(want[1])
+        assert np.array_equal(owner, want[2]), np.argwhere(owner != want[2])[:8].tolist()
+        assert np.array_equal(np.flatnonzero(owner.ravel() >= 0), want[1])
+        assert (owner.view(np.uint32)[want[2] < 0] == 0xffffffff).all()
+        r.setStream(None)
+    finally:
+        r.destroy()
+
+
+def test_scratch_shared_with_atlas_bakes_does_not_leak(W):
+    """an atlas bake of five entries with override uvs, a 7 x 5 single bake with the scene's, the atlas bake again, on one
+    context: the single bake is the model's bit for bit and the second atlas bake is the first (the two kinds of bake share
+    the context's staging arrays, block counts and count word)"""
+    import atlas_bake_util as au
+    b, m = _scene(W, "instanced1000")
+    entries = au.small_entries(au.instance_count(b))
+    uv = au.merged_grid_uv(b, [e[0] for e in entries])
+    want = m.bakePoints(0, 7, 5, t_max=5.0, pad_base=1000)
+    assert len(want[1]) > 0.1 * 35
+    r = _renderer(W, b)
+    try:
+        first = r.bakeAtlasPoints(entries, au.SMALL_W, au.SMALL_H, t_max=5.0, pad_base=1000, atlas_uv=uv, owner=True)
+        assert len(first[1]) > 0.1 * au.SMALL_W * au.SMALL_H and first[2][:, :, 0].max() >= 3
+        check_points(r.bakePoints(0, 7, 5, t_max=5.0, pad_base=1000, owner=True), want, "between two atlas bakes")
+        again = r.bakeAtlasPoints(entries, au.SMALL_W, au.SMALL_H, t_max=5.0, pad_base=1000, atlas_uv=uv, owner=True)
+        for a, c in zip(first, again):
+            assert np.array_equal(pu.bits(a), pu.bits(c))
     finally:
         r.destroy()
 

@@ -9,10 +9,13 @@ every quad spans the whole atlas (36 triangles, each over half of it: the worst 
   points   one rt_bake_points_device call with every output: owner pass, counts, scan, emit
   front    the same with cap = 0: owner pass, counts and scan only (emit = points - front)
   gather   rt_gather_irradiance_device on the points just made, depth 4, spp 16
+  bake     points + gather of the same round: what a caller who chains the two sees
 All on a torch side stream the context was given (rt_set_stream), timed with device events around each call; one warm-up,
 5 rounds, every figure the median with (min .. max).  Nothing is gated on these numbers.
+--atlas-form times the same bakes through rt_bake_atlas_points_device with the one whole-atlas entry {inst, 0, 0, W, H}, which
+puts the entry staging, the item counts and their scan in front of the owner pass and runs every launch on the u64 owner map.
 
-usage: python tools/bake_time.py [--out profiles/bake_rate.txt] [--scenes cornell,sponza_like]"""
+usage: python tools/bake_time.py [--out profiles/bake_rate.txt] [--scenes cornell,sponza_like] [--atlas-form]"""
 import argparse
 import math
 import os
@@ -62,10 +65,11 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--scenes", default="cornell,sponza_like")
+    ap.add_argument("--atlas-form", action="store_true", help="bakeAtlasPointsDevice with one whole-atlas entry")
     args = ap.parse_args()
     texels = SIZE * SIZE
-    lines = ["lightmap bake, %d x %d atlas; gather at depth %d, spp %d; Mtexels/s = 1e-6 * atlas texels / seconds of the point pass"
-             % (SIZE, SIZE, DEPTH, SPP)]
+    lines = ["lightmap bake%s, %d x %d atlas; gather at depth %d, spp %d; Mtexels/s = 1e-6 * atlas texels / seconds of the point pass"
+             % (" as a one-entry atlas bake" if args.atlas_form else "", SIZE, SIZE, DEPTH, SPP)]
     for scene in args.scenes.split(","):
         b = W.WorldBridge()
         b.loadScene(scene)
@@ -97,12 +101,18 @@ def main():
                 d_uv = None if uv is None else torch.from_numpy(uv).cuda()
                 uv_ptr = None if uv is None else d_uv.data_ptr()
 
+                def point_pass(points_ptr, texels_ptr, cap):
+                    if args.atlas_form:
+                        r.bakeAtlasPointsDevice([(inst, 0, 0, SIZE, SIZE)], SIZE, SIZE, points_ptr, texels_ptr, cap,
+                                                d_count.data_ptr(), atlas_uv_ptr=uv_ptr)
+                    else:
+                        r.bakePointsDevice(inst, SIZE, SIZE, points_ptr, texels_ptr, cap, d_count.data_ptr(), atlas_uv_ptr=uv_ptr)
+
                 def points():
-                    r.bakePointsDevice(inst, SIZE, SIZE, d_points.data_ptr(), d_texels.data_ptr(), texels, d_count.data_ptr(),
-                                       atlas_uv_ptr=uv_ptr)
+                    point_pass(d_points.data_ptr(), d_texels.data_ptr(), texels)
 
                 def front():
-                    r.bakePointsDevice(inst, SIZE, SIZE, None, None, 0, d_count.data_ptr(), atlas_uv_ptr=uv_ptr)
+                    point_pass(None, None, 0)
 
                 timed(points)
                 n = int(d_count[0])
@@ -119,9 +129,10 @@ def main():
                     ms["gather"].append(timed(gather))
                 p, f, g = (statistics.median(ms[k]) for k in ("points", "front", "gather"))
                 lines.append("%s, instance %d (%d triangles), %s: %d of %d texels covered" % (scene, inst, int(dc[inst, 0]) // 3, name, n, texels))
-                lines.append("  points (all four launches)      %s; %s" % (fmt(ms["points"]), fmt([texels / (v * 1e-3) * 1e-6 for v in ms["points"]], "Mtexels/s")))
-                lines.append("  front (owner + counts + scan)   %s; emit = points - front = %.3f ms" % (fmt(ms["front"]), p - f))
+                lines.append("  points (%s)          %s; %s" % ("items .. emit" if args.atlas_form else "owner .. emit", fmt(ms["points"]), fmt([texels / (v * 1e-3) * 1e-6 for v in ms["points"]], "Mtexels/s")))
+                lines.append("  front (points without emit)     %s; emit = points - front = %.3f ms" % (fmt(ms["front"]), p - f))
                 lines.append("  gather on those points          %s; the point pass is %.1f %% of points + gather" % (fmt(ms["gather"]), 100.0 * p / (p + g)))
+                lines.append("  bake (points + gather, a round) %s" % fmt([a + b for a, b in zip(ms["points"], ms["gather"])]))
         r.setStream(None)
         r.destroy()
     text = "\n".join(lines) + "\n"

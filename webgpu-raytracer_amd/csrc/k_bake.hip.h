@@ -36,7 +36,6 @@ struct BakeArgs {
   uint32_t* block_count;   // n_blocks: covered texels of each 256-texel block, then (k_bake_scan) their exclusive prefix
   float4* points;          // 2 per covered texel (rt_gather_point)
   uint32_t* texels;
-  uint32_t* count;         // the number of covered texels
   uint32_t inst, W, H, pad_base;
   float t_max;
   uint32_t n_tris;         // triangles of the topology array (robust-access clamp)
@@ -208,9 +207,10 @@ __device__ __forceinline__ void bake_scan(T* a, uint32_t n, T* total, T* s) {
   if (tid == RT_BAKE_SCAN_THREADS - 1u) *total = s[tid];
 }
 
-__global__ __launch_bounds__(RT_BAKE_SCAN_THREADS) void k_bake_scan(BakeArgs A) {
+// block_count[0 .. n_blocks) of either count kernel -> their exclusive prefix in place, the grand total to *count
+__global__ __launch_bounds__(RT_BAKE_SCAN_THREADS) void k_bake_scan(uint32_t* block_count, uint32_t n_blocks, uint32_t* count) {
   __shared__ uint32_t s[RT_BAKE_SCAN_THREADS];
-  bake_scan(A.block_count, A.n_blocks, A.count, s);
+  bake_scan(block_count, n_blocks, count, s);
 }
 
 // the point of texel (x, y) of instance inst's W x H atlas, owned by global triangle k

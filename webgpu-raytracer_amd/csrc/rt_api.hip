@@ -2410,7 +2410,6 @@ static int bake_front(rt_ctx* c, const rt_bake_desc* d, const void* d_uv, void* 
   A.draw = (const uint4*)c->draw_commands.ptr;
   A.owner = (uint32_t*)d_owner;
   A.block_count = (uint32_t*)c->bk.blocks.ptr;
-  A.count = (uint32_t*)d_count;
   A.inst = d->inst;
   A.W = d->width;
   A.H = d->height;
@@ -2428,7 +2427,7 @@ static int bake_front(rt_ctx* c, const rt_bake_desc* d, const void* d_uv, void* 
   const uint32_t owner_blocks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((items + 3) / 4, (uint64_t)c->num_cus * 8));
   hipLaunchKernelGGL(rtk::k_bake_owner, dim3(owner_blocks), dim3(256), 0, c->stream, S, A);
   hipLaunchKernelGGL(rtk::k_bake_count, dim3(A.n_blocks), dim3(256), 0, c->stream, A);
-  hipLaunchKernelGGL(rtk::k_bake_scan, dim3(1), dim3(RT_BAKE_SCAN_THREADS), 0, c->stream, A);
+  hipLaunchKernelGGL(rtk::k_bake_scan, dim3(1), dim3(RT_BAKE_SCAN_THREADS), 0, c->stream, A.block_count, A.n_blocks, (uint32_t*)d_count);
   HIP_TRY(c, hipGetLastError());
   return RT_OK;
 }
@@ -2444,20 +2443,18 @@ static int bake_emit(rt_ctx* c, rtk::BakeArgs& A, void* d_points, void* d_texels
   return RT_OK;
 }
 
-// The host entries of the point pass (rt_bake_points, rt_bake_atlas_points): the staging arrays for m records; front()
-// enqueues the owner pass, the counts and their scan with the count going to the bake's own word, emit(m) the point launch
-// into the staging arrays, owner_back() the copy of the owner map towards the caller.  One fence: the count and the m staged
-// records come back together, the first min(n, cap) of them go to the caller.
-extern "C++" {
-template <class Front, class Emit, class OwnerBack>
-static int bake_points_host(rt_ctx* c, uint32_t m, rt_gather_point* points_out, uint32_t* texels_out, uint32_t* n_out, Front front,
-                            Emit emit, OwnerBack owner_back) {
+// The host entries of the point pass (rt_bake_points, rt_bake_atlas_points), around the front and the emit launch of their
+// kind.  Before them: the bake's own count word and staging arrays for m records.
+static int bake_points_room(rt_ctx* c, uint32_t m) {
   int r;
   if ((r = ensure_buffer(c, c->bk.count, 16, false)) < 0) return r;
   if ((r = ensure_buffer(c, c->bk.points, (size_t)m * sizeof(rt_gather_point), true)) < 0) return r;
-  if ((r = ensure_buffer(c, c->bk.texels, (size_t)m * 4, true)) < 0) return r;
-  if ((r = front()) < 0) return r;
-  if ((r = emit(m)) < 0) return r;
+  return ensure_buffer(c, c->bk.texels, (size_t)m * 4, true);
+}
+// Behind them, one fence: the count and the m staged records come back together, the first min(n, cap) of them go to the
+// caller; with them owner_bytes of the owner map d_owner into owner_host (0: the caller did not ask for the map).
+static int bake_points_back(rt_ctx* c, uint32_t m, rt_gather_point* points_out, uint32_t* texels_out, uint32_t* n_out,
+                            const void* d_owner, void* owner_host, size_t owner_bytes) {
   uint32_t n = 0;
   std::vector<rt_gather_point> points(m);
   std::vector<uint32_t> tex(m);
@@ -2466,7 +2463,7 @@ static int bake_points_host(rt_ctx* c, uint32_t m, rt_gather_point* points_out, 
     HIP_TRY(c, hipMemcpyAsync(points.data(), c->bk.points.ptr, (size_t)m * sizeof(rt_gather_point), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipMemcpyAsync(tex.data(), c->bk.texels.ptr, (size_t)m * 4, hipMemcpyDeviceToHost, c->stream));
   }
-  if ((r = owner_back()) < 0) return r;
+  if (owner_bytes) HIP_TRY(c, hipMemcpyAsync(owner_host, d_owner, owner_bytes, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   const uint32_t got = std::min(n, m);
   if (got) {
@@ -2476,34 +2473,35 @@ static int bake_points_host(rt_ctx* c, uint32_t m, rt_gather_point* points_out, 
   *n_out = n;
   return RT_OK;
 }
-}  // extern "C++"
 
-// The tail of a whole bake (rt_bake_irradiance, rt_bake_atlas_irradiance) behind its front: the one host read of the count
-// between the point pass and the gather, emit(n) for the n points, the gather on them, scatter(B) for the way back with B
-// complete but for its owner map, and the atlas to the caller.
-extern "C++" {
-template <class Emit, class Scatter>
-static int bake_gather_tail(rt_ctx* c, uint32_t texels, uint32_t max_depth, uint32_t spp, uint32_t seed, rt_irradiance* atlas_out,
-                            uint32_t* n_covered_out, rt_radiance_stats* stats, Emit emit, Scatter scatter) {
+// A whole bake (rt_bake_irradiance, rt_bake_atlas_irradiance) behind its front.  First the one host read of the count
+// between the point pass and the gather, and the bake's arrays for *n points and the atlas ...
+static int bake_gather_room(rt_ctx* c, uint32_t texels, uint32_t* n) {
   int r;
-  uint32_t n = 0;
-  HIP_TRY(c, hipMemcpyAsync(&n, c->bk.count.ptr, 4, hipMemcpyDeviceToHost, c->stream));
+  *n = 0;
+  HIP_TRY(c, hipMemcpyAsync(n, c->bk.count.ptr, 4, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  if ((r = ensure_buffer(c, c->bk.points, (size_t)n * sizeof(rt_gather_point), true)) < 0) return r;
-  if ((r = ensure_buffer(c, c->bk.texels, (size_t)n * 4, true)) < 0) return r;
-  if ((r = ensure_buffer(c, c->bk.results, (size_t)n * sizeof(rt_irradiance), true)) < 0) return r;
-  if ((r = ensure_buffer(c, c->bk.atlas, (size_t)texels * sizeof(rt_irradiance), true)) < 0) return r;
-  if ((r = emit(n)) < 0) return r;
+  if ((r = ensure_buffer(c, c->bk.points, (size_t)*n * sizeof(rt_gather_point), true)) < 0) return r;
+  if ((r = ensure_buffer(c, c->bk.texels, (size_t)*n * 4, true)) < 0) return r;
+  if ((r = ensure_buffer(c, c->bk.results, (size_t)*n * sizeof(rt_irradiance), true)) < 0) return r;
+  return ensure_buffer(c, c->bk.atlas, (size_t)texels * sizeof(rt_irradiance), true);
+}
+// ... then, behind the emit launch of the bake's kind for those n points: the gather on them, the scatter kernel of the
+// bake's kind on its owner map d_owner, and the atlas to the caller.
+static int bake_gather_tail(rt_ctx* c, uint32_t texels, uint32_t n, uint32_t max_depth, uint32_t spp, uint32_t seed,
+                            rt_irradiance* atlas_out, uint32_t* n_covered_out, rt_radiance_stats* stats,
+                            void (*scatter)(rtk::BakeScatterArgs), const void* d_owner) {
+  int r;
   if ((r = path_query_device(c, pq_gather, c->bk.points.ptr, n, max_depth, spp, seed, c->bk.results.ptr, stats != nullptr)) < 0)
     return r;
   rtk::BakeScatterArgs B;
-  B.owner = nullptr;
+  B.owner = d_owner;
   B.texels = (const uint32_t*)c->bk.texels.ptr;
   B.results = (const float4*)c->bk.results.ptr;
   B.atlas = (float4*)c->bk.atlas.ptr;
   B.n_texels = texels;
   B.n = n;
-  scatter(B);
+  hipLaunchKernelGGL(scatter, dim3((texels + 255u) / 256u), dim3(256), 0, c->stream, B);
   HIP_TRY(c, hipGetLastError());
   HIP_TRY(c, hipMemcpyAsync(atlas_out, c->bk.atlas.ptr, (size_t)texels * sizeof(rt_irradiance), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -2511,7 +2509,6 @@ static int bake_gather_tail(rt_ctx* c, uint32_t texels, uint32_t max_depth, uint
   if (stats) return path_query_stats(c, pq_gather, stats);
   return RT_OK;
 }
-}  // extern "C++"
 
 int rt_bake_points_device(rt_ctx* c, const rt_bake_desc* d, const void* dev_atlas_uv, void* dev_points, void* dev_texels,
                           uint32_t cap, void* dev_count, void* dev_owner) {
@@ -2537,15 +2534,12 @@ int rt_bake_points(rt_ctx* c, const rt_bake_desc* d, const float* atlas_uv, uint
   if ((r = bake_scene_ready(c, d, false)) < 0) return r;
   const void* d_uv;
   if ((r = bake_stage_uv(c, "bake", atlas_uv, n_uv_vertices, &d_uv)) < 0) return r;
-  const uint32_t texels = d->width * d->height;
+  const uint32_t texels = d->width * d->height, m = std::min(cap, texels);
   rtk::BakeArgs A;
-  return bake_points_host(
-      c, std::min(cap, texels), points_out, texels_out, n_out, [&] { return bake_front(c, d, d_uv, nullptr, c->bk.count.ptr, A); },
-      [&](uint32_t m) { return bake_emit(c, A, c->bk.points.ptr, c->bk.texels.ptr, m); },
-      [&] {
-        if (owner_out) HIP_TRY(c, hipMemcpyAsync(owner_out, c->bk.owner.ptr, (size_t)texels * 4, hipMemcpyDeviceToHost, c->stream));
-        return (int)RT_OK;
-      });
+  if ((r = bake_points_room(c, m)) < 0) return r;
+  if ((r = bake_front(c, d, d_uv, nullptr, c->bk.count.ptr, A)) < 0) return r;
+  if ((r = bake_emit(c, A, c->bk.points.ptr, c->bk.texels.ptr, m)) < 0) return r;
+  return bake_points_back(c, m, points_out, texels_out, n_out, A.owner, owner_out, owner_out ? (size_t)texels * 4 : 0);
 }
 
 int rt_bake_irradiance(rt_ctx* c, const rt_bake_desc* d, const float* atlas_uv, uint32_t n_uv_vertices, uint32_t max_depth,
@@ -2562,13 +2556,10 @@ int rt_bake_irradiance(rt_ctx* c, const rt_bake_desc* d, const float* atlas_uv, 
   if ((r = ensure_buffer(c, c->bk.count, 16, false)) < 0) return r;
   rtk::BakeArgs A;
   if ((r = bake_front(c, d, d_uv, nullptr, c->bk.count.ptr, A)) < 0) return r;
-  return bake_gather_tail(
-      c, texels, max_depth, spp, seed, atlas_out, n_covered_out, stats,
-      [&](uint32_t n) { return bake_emit(c, A, c->bk.points.ptr, c->bk.texels.ptr, n); },
-      [&](rtk::BakeScatterArgs& B) {
-        B.owner = A.owner;
-        hipLaunchKernelGGL(rtk::k_bake_scatter, dim3(A.n_blocks), dim3(256), 0, c->stream, B);
-      });
+  uint32_t n;
+  if ((r = bake_gather_room(c, texels, &n)) < 0) return r;
+  if ((r = bake_emit(c, A, c->bk.points.ptr, c->bk.texels.ptr, n)) < 0) return r;
+  return bake_gather_tail(c, texels, n, max_depth, spp, seed, atlas_out, n_covered_out, stats, rtk::k_bake_scatter, A.owner);
 }
 
 // ---- atlas bakes: a list of (instance, rectangle) entries into one atlas (mi355rt.h "atlas bakes"; k_atlas_* of k_bake.hip.h)
@@ -2653,10 +2644,6 @@ static int bake_atlas_front(rt_ctx* c, const rt_bake_atlas_desc* d, const rt_bak
   A.t_max = d->t_max;
   A.n_tris = c->n_tris;
   A.n_entries = n;
-  rtk::BakeArgs scan = rtk::BakeArgs();   // k_bake_scan reads these three
-  scan.block_count = A.block_count;
-  scan.n_blocks = A.n_blocks;
-  scan.count = (uint32_t*)d_count;
   DevScene S = dev_scene(c);
   HIP_TRY(c, hipMemsetAsync(d_owner, 0xff, (size_t)texels * 8, c->stream));   // RT_ATLAS_NONE
   // The item total stays on the device.  What the host knows is a bound, every entry with all triangles of the scene: one wave
@@ -2669,7 +2656,7 @@ static int bake_atlas_front(rt_ctx* c, const rt_bake_atlas_desc* d, const rt_bak
   hipLaunchKernelGGL(rtk::k_atlas_scan, dim3(1), dim3(RT_BAKE_SCAN_THREADS), 0, c->stream, A);
   hipLaunchKernelGGL(rtk::k_atlas_owner, dim3(owner_blocks), dim3(256), 0, c->stream, S, A);
   hipLaunchKernelGGL(rtk::k_atlas_count, dim3(A.n_blocks), dim3(256), 0, c->stream, A);
-  hipLaunchKernelGGL(rtk::k_bake_scan, dim3(1), dim3(RT_BAKE_SCAN_THREADS), 0, c->stream, scan);
+  hipLaunchKernelGGL(rtk::k_bake_scan, dim3(1), dim3(RT_BAKE_SCAN_THREADS), 0, c->stream, A.block_count, A.n_blocks, (uint32_t*)d_count);
   HIP_TRY(c, hipGetLastError());
   return RT_OK;
 }
@@ -2709,18 +2696,13 @@ int rt_bake_atlas_points(rt_ctx* c, const rt_bake_atlas_desc* d, const rt_bake_r
   if ((r = bake_atlas_scene_ready(c, d, entries, false)) < 0) return r;
   const void* d_uv;
   if ((r = bake_stage_uv(c, kAtlas, atlas_uv, n_uv_vertices, &d_uv)) < 0) return r;
-  const uint32_t texels = d->width * d->height;
+  const uint32_t texels = d->width * d->height, m = std::min(cap, texels);
   rtk::BakeAtlasArgs A;
   std::vector<uint64_t> map(owner_out ? texels : 0);
-  r = bake_points_host(
-      c, std::min(cap, texels), points_out, texels_out, n_out,
-      [&] { return bake_atlas_front(c, d, entries, d_uv, nullptr, c->bk.count.ptr, A); },
-      [&](uint32_t m) { return bake_atlas_emit(c, A, c->bk.points.ptr, c->bk.texels.ptr, m); },
-      [&] {
-        if (owner_out) HIP_TRY(c, hipMemcpyAsync(map.data(), c->bk.owner64.ptr, (size_t)texels * 8, hipMemcpyDeviceToHost, c->stream));
-        return (int)RT_OK;
-      });
-  if (r < 0) return r;
+  if ((r = bake_points_room(c, m)) < 0) return r;
+  if ((r = bake_atlas_front(c, d, entries, d_uv, nullptr, c->bk.count.ptr, A)) < 0) return r;
+  if ((r = bake_atlas_emit(c, A, c->bk.points.ptr, c->bk.texels.ptr, m)) < 0) return r;
+  if ((r = bake_points_back(c, m, points_out, texels_out, n_out, A.owner, map.data(), map.size() * 8)) < 0) return r;
   for (size_t i = 0; i < map.size(); i++) {   // (entry << 32) | triangle -> {entry, triangle}; all ones -> {-1, -1}
     owner_out[2 * i] = (int32_t)(uint32_t)(map[i] >> 32);
     owner_out[2 * i + 1] = (int32_t)(uint32_t)map[i];
@@ -2743,13 +2725,10 @@ int rt_bake_atlas_irradiance(rt_ctx* c, const rt_bake_atlas_desc* d, const rt_ba
   if ((r = ensure_buffer(c, c->bk.count, 16, false)) < 0) return r;
   rtk::BakeAtlasArgs A;
   if ((r = bake_atlas_front(c, d, entries, d_uv, nullptr, c->bk.count.ptr, A)) < 0) return r;
-  return bake_gather_tail(
-      c, texels, max_depth, spp, seed, atlas_out, n_covered_out, stats,
-      [&](uint32_t n) { return bake_atlas_emit(c, A, c->bk.points.ptr, c->bk.texels.ptr, n); },
-      [&](rtk::BakeScatterArgs& B) {
-        B.owner = A.owner;
-        hipLaunchKernelGGL(rtk::k_atlas_scatter, dim3(A.n_blocks), dim3(256), 0, c->stream, B);
-      });
+  uint32_t n;
+  if ((r = bake_gather_room(c, texels, &n)) < 0) return r;
+  if ((r = bake_atlas_emit(c, A, c->bk.points.ptr, c->bk.texels.ptr, n)) < 0) return r;
+  return bake_gather_tail(c, texels, n, max_depth, spp, seed, atlas_out, n_covered_out, stats, rtk::k_atlas_scatter, A.owner);
 }
 
 // ---- atlas dilation: the nearest-texel gutter fill of mi355rt.h "atlas dilation" as three launches (k_dilate.hip.h).  No
