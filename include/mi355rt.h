@@ -501,7 +501,8 @@ int rt_probe_gather_stats(rt_ctx* ctx, rt_radiance_stats* out);
  *               j = 0 .. n-1.  The optional owner map holds W * H i32: the owner's global triangle index, -1 for none.
  * The rule has no run-time freedom: two bakes of one scene give the same words, and a CPU restatement (tests/model/
  * bake_model.cpp) gives them too.  Out of scope: chart packing, conservative rasterisation.  Several instances per call: atlas
- * bakes, below; a gutter of copied colour around the charts: atlas dilation, below them.
+ * bakes, below; a gutter of copied colour around the charts: atlas dilation, below them; the filter of a noisy bake, guided
+ * by these points: atlas denoise, below that.
  * Limits, all RT_ERR_INVALID: a NULL descriptor, reserved != 0, W or H == 0, W * H > 2^24, pad_base + W * H > 2^31 (the
  * gather's pad rule), inst >= the instance count, a NULL output that is needed.  Without a valid scene: RT_ERR_NOT_READY;
  * also when the scene has no draw command for every instance (rt_upload(RT_KIND_DRAW_COMMANDS) was never called).
@@ -610,6 +611,53 @@ int rt_bake_atlas_irradiance(rt_ctx* ctx, const rt_bake_atlas_desc* desc, const 
  *                           (rt_set_stream respected). */
 int rt_dilate_atlas(rt_ctx* ctx, const rt_dilate_desc* desc, float* atlas, uint32_t* src_out, uint32_t* filled_out);
 int rt_dilate_atlas_device(rt_ctx* ctx, const rt_dilate_desc* desc, void* dev_atlas, void* dev_src, void* dev_filled);
+
+/* ---- atlas denoise: "the filter between the gather and the gutter fill", an edge-stopped a-trous blur of a baked atlas ----
+ * A bake a user can afford is tens of samples per texel and visibly noisy.  A plain blur bleeds one wall into the next, for
+ * neighbouring texels of an atlas are often unrelated surfaces; the world position and shading normal that the bake entries
+ * emit for every covered texel say which neighbours lie on the same surface.  After rt_bake_*_points_device and
+ * rt_gather_irradiance_device atlas and points are in HBM and nowhere else - so the filter runs there (csrc/k_denoise.hip.h).
+ *
+ * THE DENOISE RULE.  All arithmetic is f32, unfused (no FMA contraction), in the order written; rt_div of mi355rt_math.h does
+ * the one division.  The weights use no exp: every output word is reproducible.  Inputs: an rt_denoise_desc {width W, height
+ * H, step, passes, normal_cos, plane_eps, max_dist} (mi355rt_layout.h); atlas_in, W * H texels of 4 f32, row-major, texel (x,
+ * y) at index i = y * W + x; points, n rt_gather_point, and texels, n u32 - points[j] and texels[j] exactly as the bake
+ * entries emit them; atlas_out, W * H texels.
+ *   guide      texel i is GUIDED iff some j < n has texels[j] == i; its guide is points[j] for the LOWEST such j (position P,
+ *              normal N, taken as given and not re-normalised).  An entry with texels[j] >= W * H is ignored.  The atlas's own
+ *              fourth component is never consulted.
+ *   one pass   at step s, out of place.  An unguided texel's 16 bytes are copied bit for bit.  A guided texel (x, y) visits
+ *              the taps (dx, dy), dy = -2 .. 2 outer and dx = -2 .. 2 inner, both ascending; the tap texel is q = (x + dx *
+ *              s, y + dy * s) and the tap weight h = k[|dx|] * k[|dy|] with k = {0.375f, 0.25f, 0.0625f}.
+ *   accepted   the centre tap always.  Any other tap iff all of these hold as float comparisons (a NaN fails every one), with
+ *              md2 = max_dist * max_dist:  q is inside the atlas;  q is guided, with guide position Pq and normal Nq;
+ *              (N.x * Nq.x + N.y * Nq.y) + N.z * Nq.z >= normal_cos;  with d = Pq - P,
+ *              |(N.x * d.x + N.y * d.y) + N.z * d.z| <= plane_eps;  (d.x * d.x + d.y * d.y) + d.z * d.z <= md2.
+ *   result     acc[0 .. 3] and wsum start at +0; for every accepted tap in visiting order, for each channel c = 0 .. 3,
+ *              acc[c] = acc[c] + h * in[q][c], and wsum = wsum + h.  out[c] = rt_div(acc[c], wsum).  All four channels are
+ *              filtered alike: hit_fraction stays in [0, 1], and a max_depth = 0 ambient-occlusion bake is denoised too.
+ *   a call     runs `passes` passes, pass p at step `step << p`: in -> ... -> out, by ping-pong through one scratch atlas the
+ *              library owns.  atlas_in is never written.
+ * Three things follow.  (1) {step 1, passes 3} is the composition of {1, 1}, {2, 1} and {4, 1}, word for word.  (2) n == 0
+ * copies the atlas.  (3) A result texel depends only on the inputs, never on tile shape or scheduling: the guide index is an
+ * integer minimum and every sum has a fixed order.
+ * Limits, all RT_ERR_INVALID with messages that begin "denoise atlas:": a NULL descriptor or a NULL array (points and texels
+ * may be NULL only when n == 0), reserved != 0, W or H == 0, W * H > 2^24 (the bakes' limit), step == 0, passes == 0, step <<
+ * (passes - 1) > RT_DENOISE_MAX_STEP (4), n > W * H.  The float parameters are not validated: a normal_cos above 1, or a NaN,
+ * simply rejects every tap but the centre.
+ * Not built: a luminance or variance stop, other texel formats, steps above 4, a device form of the whole bake.
+ * No scene is needed: the calls work on a fresh context, and they leave the renderer and the state of every query as they
+ * were.  Denoising has staging arrays of its own, kept and grown: the guide index map (4 bytes per texel), the scratch atlas
+ * and, for the host entry, the staged inputs and output.
+ *   rt_denoise_atlas         blocking, host arrays: copies atlas, points and texels in, filters, copies the result to
+ *                            atlas_out, which may equal atlas_in.
+ *   rt_denoise_atlas_device  the same on device-accessible arrays (16-byte aligned, on the context's device).  dev_out ==
+ *                            dev_in is refused; any other overlap is the caller's fault.  Only enqueues on the context's
+ *                            stream (rt_set_stream respected): one index build, then `passes` launches. */
+int rt_denoise_atlas(rt_ctx* ctx, const rt_denoise_desc* desc, const float* atlas_in, const rt_gather_point* points,
+                     const uint32_t* texels, uint32_t n, float* atlas_out);
+int rt_denoise_atlas_device(rt_ctx* ctx, const rt_denoise_desc* desc, const void* dev_in, const void* dev_points,
+                            const void* dev_texels, uint32_t n, void* dev_out);
 
 /* ---- the sharded image: one picture rendered by `world` contexts ("ranks"), assembled on rank 0 ----
  * Rank k owns the image rows y with (y / stripe_rows) % world == k and traces only those (rt_set_stripes).  Its COMPACT

@@ -199,8 +199,21 @@ typedef struct rt_dilate_desc { /* 32 B */
   uint32_t reserved[5];       /* 0 */
 } rt_dilate_desc;
 
+/* ---- atlas denoise (rt_denoise_atlas, mi355rt.h): the edge-stopped a-trous filter of a baked atlas ---- */
+#define RT_DENOISE_MAX_STEP 4u
+typedef struct rt_denoise_desc { /* 32 B */
+  uint32_t width, height;     /* of the atlas, in texels: both >= 1, width * height <= 2^24 */
+  uint32_t step;              /* tap spacing of the first pass, in texels: >= 1 */
+  uint32_t passes;            /* pass p has the spacing step << p: >= 1, step << (passes - 1) <= RT_DENOISE_MAX_STEP */
+  float normal_cos;           /* a tap's normal must have at least this dot product with the centre's */
+  float plane_eps;            /* a tap's position lies at most this far from the centre's tangent plane */
+  float max_dist;             /* ... and at most this far from the centre's position */
+  uint32_t reserved[1];       /* 0 */
+} rt_denoise_desc;
+
 #ifdef __cplusplus
 }
+static_assert(sizeof(rt_denoise_desc) == 32, "rt_denoise_desc is 32 bytes");
 static_assert(sizeof(rt_dilate_desc) == 32, "rt_dilate_desc is 32 bytes");
 static_assert(sizeof(rt_bake_desc) == 32, "rt_bake_desc is 32 bytes");
 static_assert(sizeof(rt_bake_atlas_desc) == 32, "rt_bake_atlas_desc is 32 bytes");

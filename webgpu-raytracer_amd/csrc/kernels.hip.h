@@ -27,6 +27,8 @@
 //                             texels of an instance's atlas (rt_bake_points), and k_bake_scatter, the way back
 //   k_dilate.hip.h            k_dilate_mask / _source / _apply: the nearest-texel gutter fill of a baked atlas on a coverage
 //                             bitmap (rt_dilate_atlas)
+//   k_denoise.hip.h           k_denoise_index / _pass: the edge-stopped a-trous filter of a baked atlas, guided by the bake's
+//                             points, on LDS windows (rt_denoise_atlas)
 //   k_texture_post.hip.h      k_resize_texture; k_postprocess = PostProcess.wgsl `main` (:103-176)
 //   k_validate.hip.h          k_validate_scene: every index the kernels follow, checked once per upload
 //   k_stripes.hip.h           k_pack_stripes / k_unpack_stripes: the copies of the sharded image's gather
@@ -59,6 +61,7 @@
 #include "k_probe.hip.h"
 #include "k_bake.hip.h"
 #include "k_dilate.hip.h"
+#include "k_denoise.hip.h"
 #include "k_wavefront.hip.h"
 #include "k_rayquery.hip.h"
 #include "k_texture_post.hip.h"

@@ -87,6 +87,12 @@ struct DilateState {
   DeviceBuffer atlas, filled, bitmap, src;
 };
 
+// What atlas denoising (rt_denoise_atlas) keeps between calls, kept and grown: the guide index map and the scratch atlas of
+// the ping-pong, and the staged inputs and output of the host entry.
+struct DenoiseState {
+  DeviceBuffer index, scratch, in, out, points, texels;
+};
+
 }  // namespace
 
 struct rt_ctx {
@@ -237,6 +243,7 @@ struct rt_ctx {
   uint32_t pr_timed = 0;            // batches of the last call that recorded their events
   BakeState bk;
   DilateState dl;
+  DenoiseState dn;
 
   // kernel timing
   bool timing = false;
@@ -971,6 +978,7 @@ void rt_destroy(rt_ctx* c) {
                          &c->bk.uv, &c->bk.owner, &c->bk.blocks, &c->bk.count, &c->bk.points, &c->bk.texels, &c->bk.results,
                          &c->bk.atlas, &c->bk.entries, &c->bk.items, &c->bk.owner64,
                          &c->dl.atlas, &c->dl.filled, &c->dl.bitmap, &c->dl.src,
+                         &c->dn.index, &c->dn.scratch, &c->dn.in, &c->dn.out, &c->dn.points, &c->dn.texels,
                          &c->tex_staging, &c->bv_in, &c->bv_tri, &c->bv_order, &c->bv_nodes, &c->bv_out,
                          &c->bv_counters, &c->bv_big, &c->val_roots, &c->val_bad, &c->tnodes, &c->node_key, &c->node_newidx,
                          &c->inst_root, &c->root_w, &c->treelet_work, &c->pairs, &c->pair_of, &c->pair_parent, &c->root_rec,
@@ -2797,6 +2805,95 @@ int rt_dilate_atlas(rt_ctx* c, const rt_dilate_desc* d, float* atlas, uint32_t* 
   HIP_TRY(c, hipMemcpyAsync(atlas, c->dl.atlas.ptr, texels * 16, hipMemcpyDeviceToHost, c->stream));
   if (src_out) HIP_TRY(c, hipMemcpyAsync(src_out, c->dl.src.ptr, texels * 4, hipMemcpyDeviceToHost, c->stream));
   if (filled_out) HIP_TRY(c, hipMemcpyAsync(filled_out, c->dl.filled.ptr, 4, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return RT_OK;
+}
+
+// ---- atlas denoise: the edge-stopped a-trous filter of mi355rt.h "atlas denoise" as one index build and `passes` launches
+// (k_denoise.hip.h).  No scene, no renderer state: only the context's device and stream.
+static const char* const kDenoise = "denoise atlas";
+static int denoise_desc_ok(rt_ctx* c, const rt_denoise_desc* d, const void* in, const void* points, const void* texels,
+                           uint32_t n, const void* out) {
+  const std::string w(kDenoise);
+  if (!d) return fail(c, RT_ERR_INVALID, w + ": NULL descriptor");
+  if (!in || !out || (n != 0 && (!points || !texels))) return fail(c, RT_ERR_INVALID, w + ": NULL array");
+  if (d->reserved[0]) return fail(c, RT_ERR_INVALID, w + ": reserved words must be 0");
+  if (d->width == 0 || d->height == 0) return fail(c, RT_ERR_INVALID, w + ": width and height must be >= 1");
+  if ((uint64_t)d->width * d->height > (1ull << 24)) return fail(c, RT_ERR_INVALID, w + ": width * height must be <= 2^24");
+  if (d->step == 0 || d->passes == 0) return fail(c, RT_ERR_INVALID, w + ": step and passes must be >= 1");
+  // step >= 1, so more than three passes always exceed the limit; below that the shift cannot overflow
+  if (d->passes > 3 || d->step > RT_DENOISE_MAX_STEP || (d->step << (d->passes - 1)) > RT_DENOISE_MAX_STEP)
+    return fail(c, RT_ERR_INVALID, w + ": step << (passes - 1) must be <= 4");
+  if (n > d->width * d->height) return fail(c, RT_ERR_INVALID, w + ": more points than texels");
+  return RT_OK;
+}
+// Enqueue the index build and the passes on the context's stream.  Pass p reads the atlas the pass before it wrote (the
+// first one `d_in`) and writes `d_out` when an even number of passes follows it, else the scratch atlas: the last pass lands
+// in `d_out` and `d_in` is only read.
+static int launch_denoise(rt_ctx* c, const rt_denoise_desc* d, const void* d_in, const void* d_points, const void* d_texels,
+                          uint32_t n, void* d_out) {
+  const uint32_t texels = d->width * d->height;
+  int r;
+  if ((r = ensure_buffer(c, c->dn.index, (size_t)texels * 4, true)) < 0) return r;
+  if (d->passes > 1 && (r = ensure_buffer(c, c->dn.scratch, (size_t)texels * 16, true)) < 0) return r;
+  rtk::DenoiseArgs A;
+  A.points = (const float4*)d_points;
+  A.texels = (const uint32_t*)d_texels;
+  A.index = (uint32_t*)c->dn.index.ptr;
+  A.W = d->width;
+  A.H = d->height;
+  A.n = n;
+  A.tiles_x = (d->width + RT_DENOISE_TILE_W - 1u) / RT_DENOISE_TILE_W;
+  const uint32_t tiles_y = (d->height + RT_DENOISE_TILE_H - 1u) / RT_DENOISE_TILE_H;
+  A.normal_cos = d->normal_cos;
+  A.plane_eps = d->plane_eps;
+  A.md2 = d->max_dist * d->max_dist;
+  A.in = (const uint4*)d_in;
+  A.out = nullptr;
+  A.step = d->step;
+  HIP_TRY(c, hipMemsetAsync(c->dn.index.ptr, 0xff, (size_t)texels * 4, c->stream));
+  if (n) hipLaunchKernelGGL(rtk::k_denoise_index, dim3((n + 255u) / 256u), dim3(256), 0, c->stream, A);
+  for (uint32_t p = 0; p < d->passes; p++) {
+    A.out = (uint4*)(((d->passes - 1u - p) & 1u) ? c->dn.scratch.ptr : d_out);
+    A.step = d->step << p;
+    hipLaunchKernelGGL(rtk::k_denoise_pass, dim3(A.tiles_x * tiles_y), dim3(256), 0, c->stream, A);
+    A.in = A.out;
+  }
+  HIP_TRY(c, hipGetLastError());
+  return RT_OK;
+}
+
+int rt_denoise_atlas_device(rt_ctx* c, const rt_denoise_desc* d, const void* dev_in, const void* dev_points,
+                            const void* dev_texels, uint32_t n, void* dev_out) {
+  if (!c) return RT_ERR_INVALID;
+  int r = denoise_desc_ok(c, d, dev_in, dev_points, dev_texels, n, dev_out);
+  if (r < 0) return r;
+  if (dev_in == dev_out) return fail(c, RT_ERR_INVALID, std::string(kDenoise) + ": the output must not be the input");
+  if ((r = query_device_arrays_ok(c, kDenoise, dev_in, dev_out)) < 0) return r;
+  if (n != 0 && (r = query_device_arrays_ok(c, kDenoise, dev_points, dev_texels)) < 0) return r;
+  return launch_denoise(c, d, dev_in, dev_points, dev_texels, n, dev_out);
+}
+
+int rt_denoise_atlas(rt_ctx* c, const rt_denoise_desc* d, const float* atlas_in, const rt_gather_point* points,
+                     const uint32_t* texels, uint32_t n, float* atlas_out) {
+  if (!c) return RT_ERR_INVALID;
+  int r = denoise_desc_ok(c, d, atlas_in, points, texels, n, atlas_out);
+  if (r < 0) return r;
+  HIP_TRY(c, hipSetDevice(c->device));
+  const size_t bytes = (size_t)d->width * d->height * 16;
+  if ((r = ensure_buffer(c, c->dn.in, bytes, true)) < 0) return r;
+  if ((r = ensure_buffer(c, c->dn.out, bytes, true)) < 0) return r;
+  HIP_TRY(c, hipMemcpyAsync(c->dn.in.ptr, atlas_in, bytes, hipMemcpyHostToDevice, c->stream));
+  if (n) {
+    if ((r = ensure_buffer(c, c->dn.points, (size_t)n * sizeof(rt_gather_point), true)) < 0) return r;
+    if ((r = ensure_buffer(c, c->dn.texels, (size_t)n * 4, true)) < 0) return r;
+    HIP_TRY(c, hipMemcpyAsync(c->dn.points.ptr, points, (size_t)n * sizeof(rt_gather_point), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->dn.texels.ptr, texels, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+  }
+  if ((r = launch_denoise(c, d, c->dn.in.ptr, n ? c->dn.points.ptr : nullptr, n ? c->dn.texels.ptr : nullptr, n,
+                          c->dn.out.ptr)) < 0)
+    return r;
+  HIP_TRY(c, hipMemcpyAsync(atlas_out, c->dn.out.ptr, bytes, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return RT_OK;
 }

@@ -827,6 +827,35 @@ static napi_value rtDilateAtlas(napi_env env, napi_callback_info info) {
   return r;
 }
 
+/* ------------------------------------------------------- atlas denoise (rt_denoise_atlas, mi355rt.h) */
+/* (ctx, width, height, step, passes, normalCos, planeEps, maxDist, atlas: Float32Array of 4 per texel (read), points:
+ * Float32Array of 8 per point or null, texels: Uint32Array or null, out: Float32Array of 4 per texel) -> 0, or a negative
+ * status; the number of points is the length of texels */
+static napi_value rtDenoiseAtlas(napi_env env, napi_callback_info info) {
+  napi_value a[12];
+  void *atlas = NULL, *points = NULL, *texels = NULL, *out = NULL;
+  size_t na = 0, np = 0, nt = 0, no = 0;
+  if (!get_args(env, info, 12, a) || !get_bytes(env, a[8], &atlas, &na) || !get_bytes(env, a[9], &points, &np) ||
+      !get_bytes(env, a[10], &texels, &nt) || !get_bytes(env, a[11], &out, &no))
+    return NULL;
+  rt_denoise_desc d;
+  memset(&d, 0, sizeof(d));
+  d.width = get_u32(env, a[1]);
+  d.height = get_u32(env, a[2]);
+  d.step = get_u32(env, a[3]);
+  d.passes = get_u32(env, a[4]);
+  d.normal_cos = (float)get_f64(env, a[5]);
+  d.plane_eps = (float)get_f64(env, a[6]);
+  d.max_dist = (float)get_f64(env, a[7]);
+  const size_t cells = (size_t)d.width * d.height, n = nt / 4;
+  if (na / 16 < cells || no / 16 < cells || np / 32 < n || n > 0xffffffffu) {
+    napi_throw_range_error(env, NULL, "rtDenoiseAtlas: atlas and out must hold 4 floats per texel, points 8 floats per texel index");
+    return NULL;
+  }
+  return make_int(env, rt_denoise_atlas((rt_ctx*)get_ptr(env, a[0]), &d, (const float*)atlas, (const rt_gather_point*)points,
+                                        (const uint32_t*)texels, (uint32_t)n, (float*)out));
+}
+
 static napi_value Init(napi_env env, napi_value exports) {
   static const struct {
     const char* name;
@@ -846,7 +875,8 @@ static napi_value Init(napi_env env, napi_value exports) {
                {"rtRayQueryStats", rtRayQueryStats}, {"rtTraceRadiance", rtTraceRadiance},
                {"rtGatherIrradiance", rtGatherIrradiance}, {"rtGatherProbes", rtGatherProbes}, {"rtBakePoints", rtBakePoints},
                {"rtBakeIrradiance", rtBakeIrradiance}, {"rtBakeAtlasPoints", rtBakeAtlasPoints},
-               {"rtBakeAtlasIrradiance", rtBakeAtlasIrradiance}, {"rtDilateAtlas", rtDilateAtlas}, {"msCreate", msCreate}, {"msDestroy", msDestroy},
+               {"rtBakeAtlasIrradiance", rtBakeAtlasIrradiance}, {"rtDilateAtlas", rtDilateAtlas},
+               {"rtDenoiseAtlas", rtDenoiseAtlas}, {"msCreate", msCreate}, {"msDestroy", msDestroy},
                {"msUpdate", msUpdate}, {"msUpdateCamera", msUpdateCamera}, {"msGet", msGet},
                {"msTextureCount", msTextureCount}, {"msTexture", msTexture},
                {"msAnimationNames", msAnimationNames}, {"msSetAnimation", msSetAnimation},

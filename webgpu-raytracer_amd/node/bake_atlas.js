@@ -1,7 +1,8 @@
 'use strict';
 // Bake the lightmap of the first N instances of a scene into ONE atlas and write it as a PNG:
-// usage: node bake_atlas.js [scene] [N] [cell] [out.png] [maxDepth] [spp] [seed] [--dilate R]
-// defaults: instanced1000, 64, 32, atlas.png, 4, 16, 0, no dilation
+// usage: node bake_atlas.js [scene] [N] [cell] [out.png] [maxDepth] [spp] [seed] [--denoise PASSES --plane-eps E --max-dist D
+//        [--normal-cos C]] [--dilate R]
+// defaults: instanced1000, 64, 32, atlas.png, 4, 16, 0, no denoising, no dilation
 // The atlas is a square grid of ceil(sqrt(N)) x ceil(sqrt(N)) rectangles of cell x cell texels, instance e in rectangle e.
 // Instances of one geometry share their vertices and so their chart: the rectangle is what tells their texels apart.  The
 // chart itself is an override layout made here - triangle k of a geometry gets cell k of a ceil(sqrt(n)) grid of the unit
@@ -9,14 +10,23 @@
 // one array (for meshes whose triangles share no vertices across geometries).  One bakeAtlasIrradiance call bakes them all:
 // one point pass, one gather, one scatter.  The picture shows pi * (E / pi) * albedo with albedo = 0.8 and gamma 2.2; texels
 // without a surface are transparent.  --dilate R (1 .. 24) puts a gutter of R texels of copied colour around every chart
-// (dilateAtlas); its texels are drawn like covered ones.  Prints one JSON line.
+// (dilateAtlas); its texels are drawn like covered ones.  --denoise PASSES (1 .. 3) filters the atlas before that (denoiseAtlas,
+// guided by one more point pass, bakeAtlasPoints: taps count within E of a texel's tangent plane and within D of it, world
+// units, where the normals' dot product is at least C, default 0.9).  Prints one JSON line.
 const fs = require('fs');
 const { WebGPURenderer, WorldBridge, encodePng } = require('./index.js');
 
 (async () => {
   const argv = process.argv.slice(2);
-  const at = argv.indexOf('--dilate');
-  const dilate = at >= 0 ? parseInt(argv.splice(at, 2)[1], 10) : 0;
+  const flag = (name, parse, none) => {
+    const at = argv.indexOf(name);
+    return at >= 0 ? parse(argv.splice(at, 2)[1]) : none;
+  };
+  const dilate = flag('--dilate', (v) => parseInt(v, 10), 0);
+  const denoise = flag('--denoise', (v) => parseInt(v, 10), 0);
+  const planeEps = flag('--plane-eps', parseFloat), maxDist = flag('--max-dist', parseFloat);
+  const normalCos = flag('--normal-cos', parseFloat, 0.9);
+  if (denoise > 0 && (planeEps === undefined || maxDist === undefined)) throw new Error('--denoise needs --plane-eps E and --max-dist D');
   const [scene = 'instanced1000', count = '64', cellSize = '32', outPath = 'atlas.png', depth = '4', spp = '16', seed = '0'] =
     argv;
   const bridge = new WorldBridge();
@@ -57,6 +67,10 @@ const { WebGPURenderer, WorldBridge, encodePng } = require('./index.js');
   const size = side * cell;
   const bake = renderer.bakeAtlasIrradiance(entries, size, size, parseInt(depth, 10), parseInt(spp, 10),
     { atlasUv, seed: parseInt(seed, 10), stats: true });
+  if (denoise > 0) {
+    const pts = renderer.bakeAtlasPoints(entries, size, size, { atlasUv });
+    bake.data = renderer.denoiseAtlas(bake.data, size, size, pts.points, pts.texels, { passes: denoise, planeEps, maxDist, normalCos }).data;
+  }
   let filled = 0;
   if (dilate > 0) ({ data: bake.data, filled } = renderer.dilateAtlas(bake.data, size, size, dilate));
   const rgba = new Uint8Array(size * size * 4);
@@ -73,6 +87,6 @@ const { WebGPURenderer, WorldBridge, encodePng } = require('./index.js');
   }
   fs.writeFileSync(outPath, Buffer.from(encodePng(rgba, size, size)));
   console.log(JSON.stringify({ scene, entries: n, geometries: geometries.size, size, covered: bake.covered, lit, out: outPath,
-    ...(dilate > 0 ? { dilate, filled } : {}), stats: bake.stats }));
+    ...(denoise > 0 ? { denoise, planeEps, maxDist, normalCos } : {}), ...(dilate > 0 ? { dilate, filled } : {}), stats: bake.stats }));
   renderer.destroy();
 })().catch((e) => { console.error(e); process.exit(1); });

@@ -1,6 +1,7 @@
 'use strict';
 // Bake a lightmap of the floor of the Cornell box and write it as a PNG:
-// usage: node bake_lightmap.js [size] [out.png] [maxDepth] [spp] [seed] [--dilate R]     defaults: 256, bake.png, 4, 64, 0, no dilation
+// usage: node bake_lightmap.js [size] [out.png] [maxDepth] [spp] [seed] [--denoise PASSES --plane-eps E --max-dist D [--normal-cos C]]
+//        [--dilate R]     defaults: 256, bake.png, 4, 64, 0, no denoising, no dilation
 // The box is one instance whose quads all carry the uvs (0,0) .. (1,1), so the scene's own uvs would lay every quad over the
 // whole atlas.  The example therefore supplies an override layout: the floor - the two largest triangles in the plane
 // y = min y - gets u = (x - min x) / (max x - min x), v = (z - min z) / (max z - min z); every other vertex goes to (-1, -1),
@@ -10,14 +11,23 @@
 // towards the middle of the room on the host, gatherIrradiance, and the scatter by texel index.
 // The gather returns E / pi per point; the picture shows pi * (E / pi) * albedo with albedo = 0.8 and gamma 2.2: the floor seen
 // from above, dark where the two boxes stand and in their shadows.  --dilate R (1 .. 24) puts a gutter of R texels of copied
-// colour around the chart (dilateAtlas); its texels are drawn like covered ones.  Prints one JSON line.
+// colour around the chart (dilateAtlas); its texels are drawn like covered ones.  --denoise PASSES (1 .. 3) filters the atlas
+// before that (denoiseAtlas, guided by the points of step 1 with their normals as turned: taps count within E of a texel's
+// tangent plane and within D of it, world units, where the normals' dot product is at least C, default 0.9).  Prints one JSON line.
 const fs = require('fs');
 const { WebGPURenderer, WorldBridge, encodePng } = require('./index.js');
 
 (async () => {
   const argv = process.argv.slice(2);
-  const at = argv.indexOf('--dilate');
-  const dilate = at >= 0 ? parseInt(argv.splice(at, 2)[1], 10) : 0;
+  const flag = (name, parse, none) => {
+    const at = argv.indexOf(name);
+    return at >= 0 ? parse(argv.splice(at, 2)[1]) : none;
+  };
+  const dilate = flag('--dilate', (v) => parseInt(v, 10), 0);
+  const denoise = flag('--denoise', (v) => parseInt(v, 10), 0);
+  const planeEps = flag('--plane-eps', parseFloat), maxDist = flag('--max-dist', parseFloat);
+  const normalCos = flag('--normal-cos', parseFloat, 0.9);
+  if (denoise > 0 && (planeEps === undefined || maxDist === undefined)) throw new Error('--denoise needs --plane-eps E and --max-dist D');
   const [size = '256', outPath = 'bake.png', depth = '4', spp = '64', seed = '0'] = argv;
   const scene = 'cornell', inst = 0;
   const n = parseInt(size, 10);
@@ -75,6 +85,7 @@ const { WebGPURenderer, WorldBridge, encodePng } = require('./index.js');
   const bake = { data: new Float32Array(n * n * 4), covered: pts.n, stats: res.stats };
   for (let i = 0; i < n * n; i++) bake.data[4 * i + 3] = -1;   // no surface
   for (let j = 0; j < pts.n; j++) bake.data.set(res.data.subarray(4 * j, 4 * j + 4), 4 * pts.texels[j]);
+  if (denoise > 0) bake.data = renderer.denoiseAtlas(bake.data, n, n, pts.points, pts.texels, { passes: denoise, planeEps, maxDist, normalCos }).data;
   let filled = 0;
   if (dilate > 0) ({ data: bake.data, filled } = renderer.dilateAtlas(bake.data, n, n, dilate));
   const rgba = new Uint8Array(n * n * 4);
@@ -91,6 +102,6 @@ const { WebGPURenderer, WorldBridge, encodePng } = require('./index.js');
   }
   fs.writeFileSync(outPath, Buffer.from(encodePng(rgba, n, n)));
   console.log(JSON.stringify({ scene, inst, size: n, floorTriangles: floor.length, covered: bake.covered, lit, out: outPath,
-    ...(dilate > 0 ? { dilate, filled } : {}), stats: bake.stats }));
+    ...(denoise > 0 ? { denoise, planeEps, maxDist, normalCos } : {}), ...(dilate > 0 ? { dilate, filled } : {}), stats: bake.stats }));
   renderer.destroy();
 })().catch((e) => { console.error(e); process.exit(1); });

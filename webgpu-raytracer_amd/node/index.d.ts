@@ -99,6 +99,13 @@ export class WebGPURenderer {
    *  filled ones, 0xffffffff elsewhere). */
   dilateAtlas(atlas: Float32Array, width: number, height: number, radius: number, opts?: { src?: boolean }):
     { data: Float32Array; width: number; height: number; filled: number; src?: Uint32Array };
+  /** Atlas denoise (rt_denoise_atlas): `passes` passes of the 5 x 5 a-trous kernel at tap spacings step, 2 * step, ... (at
+   *  most 4), guided by the points of bakePoints / bakeAtlasPoints for the same atlas: a tap counts only where its normal has
+   *  a dot product >= normalCos with the texel's and its position lies within planeEps of the texel's tangent plane and
+   *  within maxDist of its position.  Texels without a point are copied.  `data` is a new array. */
+  denoiseAtlas(atlas: Float32Array, width: number, height: number, points: Float32Array | null, texels: Uint32Array | null,
+               opts: { planeEps: number; maxDist: number; normalCos?: number; passes?: number; step?: number }):
+    { data: Float32Array; width: number; height: number };
   destroy(): void;
 }
 export class WorldBridge {

@@ -293,6 +293,24 @@ class WebGPURenderer {
     if (src) out.src = src;
     return out;
   }
+  // ---- atlas denoise (rt_denoise_atlas): the edge-stopped a-trous filter of a baked atlas.  atlas = 4 floats per texel;
+  // points (8 floats each) and texels as bakePoints / bakeAtlasPoints return them for the same atlas.  opts: {planeEps,
+  // maxDist (both required, world units), normalCos = 0.9, passes = 3, step = 1}: `passes` passes of the 5 x 5 kernel at tap
+  // spacings step, 2 * step, ... (at most 4); a tap counts only where its guide's normal has a dot product >= normalCos with
+  // the texel's and its guide's position lies within planeEps of the texel's tangent plane and within maxDist of its position,
+  // by the denoise rule of include/mi355rt.h.  Texels without a point are copied.  Result: {data (a new Float32Array), width,
+  // height}.
+  denoiseAtlas(atlas, width, height, points, texels, opts = {}) {
+    if (!(atlas instanceof Float32Array) || atlas.length !== width * height * 4) throw new TypeError('denoiseAtlas: a Float32Array of 4 floats per texel');
+    if (!(opts.planeEps !== undefined && opts.maxDist !== undefined)) throw new TypeError('denoiseAtlas: opts.planeEps and opts.maxDist are required');
+    const n = texels ? texels.length : 0;
+    if (n && (!(points instanceof Float32Array) || !(texels instanceof Uint32Array) || points.length !== 8 * n)) throw new TypeError('denoiseAtlas: points of 8 floats per texel index');
+    const data = new Float32Array(width * height * 4);
+    this._check(native.rtDenoiseAtlas(this._ctx, width >>> 0, height >>> 0, (opts.step === undefined ? 1 : opts.step) >>> 0,
+      (opts.passes === undefined ? 3 : opts.passes) >>> 0, opts.normalCos === undefined ? 0.9 : opts.normalCos, opts.planeEps,
+      opts.maxDist, atlas, n ? points : null, n ? texels : null, data), 'denoiseAtlas');
+    return { data, width, height };
+  }
   destroy() { if (this._ctx) { native.rtDestroy(this._ctx); this._ctx = null; } }
 }
 

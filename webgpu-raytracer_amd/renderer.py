@@ -212,6 +212,9 @@ def load_library(path=None):
         # atlas dilation
         "rt_dilate_atlas": (i32, [vp, vp, vp, vp, vp]),
         "rt_dilate_atlas_device": (i32, [vp, vp, vp, vp, vp]),
+        # atlas denoise
+        "rt_denoise_atlas": (i32, [vp, vp, vp, vp, vp, u32, vp]),
+        "rt_denoise_atlas_device": (i32, [vp, vp, vp, vp, vp, u32, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(L, name)  # AttributeError here = header/library mismatch
@@ -239,7 +242,8 @@ EXPORTED_SYMBOLS = (
     "rt_gather_probes rt_gather_probes_device rt_probe_gather_stats "
     "rt_bake_points rt_bake_points_device rt_bake_irradiance "
     "rt_bake_atlas_points rt_bake_atlas_points_device rt_bake_atlas_irradiance "
-    "rt_dilate_atlas rt_dilate_atlas_device").split()
+    "rt_dilate_atlas rt_dilate_atlas_device "
+    "rt_denoise_atlas rt_denoise_atlas_device").split()
 
 
 # ---- ray queries: mirrors of rt_ray / rt_ray_hit / rt_ray_stats (include/mi355rt_layout.h)
@@ -326,6 +330,13 @@ class RtBakeRect(ctypes.Structure):
 class RtDilateDesc(ctypes.Structure):
     _fields_ = [("width", ctypes.c_uint32), ("height", ctypes.c_uint32), ("radius", ctypes.c_uint32),
                 ("reserved", ctypes.c_uint32 * 5)]
+
+
+# atlas denoise: mirror of rt_denoise_desc
+class RtDenoiseDesc(ctypes.Structure):
+    _fields_ = [("width", ctypes.c_uint32), ("height", ctypes.c_uint32), ("step", ctypes.c_uint32), ("passes", ctypes.c_uint32),
+                ("normal_cos", ctypes.c_float), ("plane_eps", ctypes.c_float), ("max_dist", ctypes.c_float),
+                ("reserved", ctypes.c_uint32 * 1)]
 
 
 def _ptr(a):
@@ -737,12 +748,15 @@ class WebGPURenderer:
                     "bakePointsDevice")
 
     def bakeIrradiance(self, inst, width, height, max_depth, spp, seed=0, t_max=1e30, pad_base=0, atlas_uv=None, stats=False,
-                       dilate=0):
+                       dilate=0, denoise=None):
         """The whole bake: points, the irradiance gather on them, scatter.  Returns the (height, width) IRRADIANCE_DTYPE
         atlas - texel texels[j] holds what gatherIrradiance returns for points[j] (E / pi: multiply by pi * albedo for a
         Lambert texel's outgoing radiance), uncovered texels are {0, 0, 0, -1} - and with stats=True the triple (atlas,
         number of covered texels, stats dict of the gather).  dilate > 0: dilateAtlas with that radius on the returned atlas
-        (filled texels carry hit_fraction -2); it costs one more round trip of the atlas to the device and back."""
+        (filled texels carry hit_fraction -2); it costs one more round trip of the atlas to the device and back.
+        denoise: None, or a dict of denoiseAtlas's keyword arguments (plane_eps and max_dist at least): the bake then runs
+        bakePoints ONCE MORE with the same arguments - an extra point pass - for the guides and denoises the atlas with them,
+        before any dilation."""
         d = self._bake_desc(inst, width, height, t_max, pad_base)
         uv, uv_ptr, n_uv = self._atlas_uv(atlas_uv)
         out = np.empty((int(height), int(width)), dtype=IRRADIANCE_DTYPE)
@@ -751,6 +765,9 @@ class WebGPURenderer:
         self._check(self.L.rt_bake_irradiance(self.ctx, ctypes.addressof(d), uv_ptr, n_uv, int(max_depth), int(spp),
                                               int(seed) & 0xffffffff, _ptr(out), ctypes.addressof(n),
                                               ctypes.addressof(st) if stats else None), "bakeIrradiance")
+        if denoise is not None:
+            points, texels = self.bakePoints(inst, width, height, t_max, pad_base, atlas_uv)
+            out = self.denoiseAtlas(out, points, texels, **denoise)
         if dilate > 0:
             out = self.dilateAtlas(out, dilate)
         return (out, n.value, st.as_dict()) if stats else out
@@ -799,11 +816,13 @@ class WebGPURenderer:
                     "bakeAtlasPointsDevice")
 
     def bakeAtlasIrradiance(self, entries, width, height, max_depth, spp, seed=0, t_max=1e30, pad_base=0, atlas_uv=None,
-                            stats=False, dilate=0):
+                            stats=False, dilate=0, denoise=None):
         """The whole atlas bake: the points of all entries, ONE irradiance gather on them, scatter.  Returns the (height,
         width) IRRADIANCE_DTYPE atlas as bakeIrradiance does - and with stats=True the triple (atlas, number of covered
         texels, stats dict of the gather).  dilate > 0: dilateAtlas with that radius on the returned atlas, at the price of
-        one more round trip of the atlas to the device and back."""
+        one more round trip of the atlas to the device and back.  denoise: None, or a dict of denoiseAtlas's keyword
+        arguments: the bake then runs bakeAtlasPoints ONCE MORE with the same arguments - an extra point pass - for the
+        guides and denoises the atlas with them, before any dilation."""
         d, rects = self._atlas_args(entries, width, height, t_max, pad_base)
         uv, uv_ptr, n_uv = self._atlas_uv(atlas_uv)
         out = np.empty((int(height), int(width)), dtype=IRRADIANCE_DTYPE)
@@ -812,6 +831,9 @@ class WebGPURenderer:
         self._check(self.L.rt_bake_atlas_irradiance(self.ctx, ctypes.addressof(d), _ptr(rects), uv_ptr, n_uv, int(max_depth),
                                                     int(spp), int(seed) & 0xffffffff, _ptr(out), ctypes.addressof(n),
                                                     ctypes.addressof(st) if stats else None), "bakeAtlasIrradiance")
+        if denoise is not None:
+            points, texels = self.bakeAtlasPoints(entries, width, height, t_max, pad_base, atlas_uv)
+            out = self.denoiseAtlas(out, points, texels, **denoise)
         if dilate > 0:
             out = self.dilateAtlas(out, dilate)
         return (out, n.value, st.as_dict()) if stats else out
@@ -856,6 +878,51 @@ class WebGPURenderer:
         self._check(self.L.rt_dilate_atlas_device(self.ctx, ctypes.addressof(d), ctypes.c_void_p(atlas_ptr or 0),
                                                   ctypes.c_void_p(src_ptr or 0), ctypes.c_void_p(filled_ptr or 0)),
                     "dilateAtlasDevice")
+
+    # ---- atlas denoise: the edge-stopped a-trous filter guided by the bake's points (rt_denoise_atlas) ----
+    @staticmethod
+    def _denoise_desc(width, height, plane_eps, max_dist, normal_cos, passes, step):
+        d = RtDenoiseDesc()
+        d.width, d.height, d.step, d.passes = int(width), int(height), int(step), int(passes)
+        d.normal_cos, d.plane_eps, d.max_dist = float(normal_cos), float(plane_eps), float(max_dist)
+        return d
+
+    def denoiseAtlas(self, atlas, points, texels, *, plane_eps, max_dist, normal_cos=0.9, passes=3, step=1):
+        """atlas: an (H, W, 4) float32 array (or an (H, W) IRRADIANCE_DTYPE one, as the bakes return it); points (n, 8)
+        float32 in the rt_gather_point layout and texels (n,) uint32, as bakePoints / bakeAtlasPoints return them for the
+        same atlas.  Returns a NEW array of the same shape: `passes` passes of the 5 x 5 a-trous kernel at tap spacings step,
+        2 * step, ... (at most 4), each tap accepted only where its guide's normal has a dot product >= normal_cos with the
+        texel's, and its guide's position lies within plane_eps of the texel's tangent plane and within max_dist of its
+        position (world units); by the denoise rule of include/mi355rt.h.  Texels without a guide are copied."""
+        a = np.ascontiguousarray(atlas)
+        if a.dtype == IRRADIANCE_DTYPE and a.ndim == 2:
+            height, width = a.shape
+        else:
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            if a.ndim != 3 or a.shape[2] != 4:
+                raise ValueError("denoiseAtlas expects an (H, W, 4) float32 array")
+            height, width = a.shape[:2]
+        out = np.empty_like(a)
+        pts = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 8)
+        tex = np.ascontiguousarray(texels, dtype=np.uint32).reshape(-1)
+        if len(pts) != len(tex):
+            raise ValueError("denoiseAtlas expects one texel index per point")
+        d = self._denoise_desc(width, height, plane_eps, max_dist, normal_cos, passes, step)
+        self._check(self.L.rt_denoise_atlas(self.ctx, ctypes.addressof(d), _ptr(a) if a.size else None,
+                                            _ptr(pts) if len(pts) else None, _ptr(tex) if len(tex) else None, len(tex),
+                                            _ptr(out) if out.size else None), "denoiseAtlas")
+        return out
+
+    def denoiseAtlasDevice(self, in_ptr, points_ptr, texels_ptr, n, out_ptr, width, height, *, plane_eps, max_dist,
+                           normal_cos=0.9, passes=3, step=1):
+        """Enqueue a denoise of the width x height atlas of 16-byte texels at in_ptr into the one at out_ptr (another
+        array; e.g. tensor.data_ptr()), guided by n rt_gather_point at points_ptr and n uint32 at texels_ptr as
+        bakePointsDevice wrote them, on the context's stream; no host synchronisation.  Every pointer must be 16-byte aligned
+        and lie on the context's device.  The input atlas is only read."""
+        d = self._denoise_desc(width, height, plane_eps, max_dist, normal_cos, passes, step)
+        self._check(self.L.rt_denoise_atlas_device(self.ctx, ctypes.addressof(d), ctypes.c_void_p(in_ptr or 0),
+                                                   ctypes.c_void_p(points_ptr or 0), ctypes.c_void_p(texels_ptr or 0), int(n),
+                                                   ctypes.c_void_p(out_ptr or 0)), "denoiseAtlasDevice")
 
     # ---- the sharded image (rt_dist_*): this context as one rank of `world` ----
     def distInit(self, rank, world, stripe_rows=8, unique_id=None):
