@@ -523,8 +523,9 @@ int rt_probe_gather_stats(rt_ctx* ctx, rt_radiance_stats* out);
  *                          surface").  *n_covered_out (may be NULL) = n.  stats (may be NULL) are the gather's: the
  *                          counting kernel runs, and rt_irradiance_gather_stats reports this gather afterwards.  One host
  *                          read of the count between the point pass and the gather.  The values are E / pi: multiply by pi *
- *                          albedo for the outgoing radiance of a Lambert texel.  A device form of the whole bake is not
- *                          offered: chain rt_bake_points_device and rt_gather_irradiance_device. */
+ *                          albedo for the outgoing radiance of a Lambert texel.  An enqueue-only form of the whole bake is
+ *                          not offered: chain rt_bake_points_device and rt_gather_irradiance_device; the whole pipeline
+ *                          with one read of the count is rt_bake_atlas_lightmap, below. */
 int rt_bake_points(rt_ctx* ctx, const rt_bake_desc* desc, const float* atlas_uv, uint32_t n_uv_vertices,
                    rt_gather_point* points_out, uint32_t* texels_out, uint32_t cap, uint32_t* n_out, int32_t* owner_out);
 int rt_bake_points_device(rt_ctx* ctx, const rt_bake_desc* desc, const void* dev_atlas_uv, void* dev_points, void* dev_texels,
@@ -553,7 +554,8 @@ int rt_bake_irradiance(rt_ctx* ctx, const rt_bake_desc* desc, const float* atlas
  * Two identities follow.  (A) One entry {inst, 0, 0, W, H} gives, word for word with the pads, what rt_bake_points gives for
  * {inst, W, H, pad_base, t_max}.  (B) Any atlas bake is the composition of its entries' single-instance bakes:
  * rt_bake_points per entry, placed at the rectangle, the lowest entry winning, the pads re-based.
- * Out of scope: chart packing (the caller chooses the rectangles), a t_max per entry, a device form of the whole bake.
+ * Out of scope: chart packing (the caller chooses the rectangles), a t_max per entry, an enqueue-only form of the whole bake (the
+ * gather would have to take its count from the device; with one read of the count: rt_bake_atlas_lightmap_device, below).
  * Limits, all RT_ERR_INVALID: a NULL descriptor or NULL entries, reserved != 0 (descriptor or any entry), n_entries == 0 or
  * > 65536, W or H == 0, W * H > 2^24, pad_base + W * H > 2^31, any w or h == 0, any rectangle not inside the atlas (x + w
  * <= W and y + h <= H, taken without u32 overflow), any inst >= the instance count, and what the bake entries above say about
@@ -645,7 +647,8 @@ int rt_dilate_atlas_device(rt_ctx* ctx, const rt_dilate_desc* desc, void* dev_at
  * may be NULL only when n == 0), reserved != 0, W or H == 0, W * H > 2^24 (the bakes' limit), step == 0, passes == 0, step <<
  * (passes - 1) > RT_DENOISE_MAX_STEP (4), n > W * H.  The float parameters are not validated: a normal_cos above 1, or a NaN,
  * simply rejects every tap but the centre.
- * Not built: a luminance or variance stop, other texel formats, steps above 4, a device form of the whole bake.
+ * Not built: a luminance or variance stop, other texel formats, steps above 4.  (The filter inside a
+ * whole bake, on the guides the bake already holds in HBM: rt_bake_atlas_lightmap, below.)
  * No scene is needed: the calls work on a fresh context, and they leave the renderer and the state of every query as they
  * were.  Denoising has staging arrays of its own, kept and grown: the guide index map (4 bytes per texel), the scratch atlas
  * and, for the host entry, the staged inputs and output.
@@ -658,6 +661,71 @@ int rt_denoise_atlas(rt_ctx* ctx, const rt_denoise_desc* desc, const float* atla
                      const uint32_t* texels, uint32_t n, float* atlas_out);
 int rt_denoise_atlas_device(rt_ctx* ctx, const rt_denoise_desc* desc, const void* dev_in, const void* dev_points,
                             const void* dev_texels, uint32_t n, void* dev_out);
+
+/* ---- lightmaps: "the finished lightmap of these instances, in the texel format a renderer loads", in one call ----
+ * The four sections above are the stages of a lightmap: points, gather, filter, gutter.  A caller who chains their host
+ * entries pays a second point pass for the filter's guides and two more round trips of the atlas, and receives 16 bytes per
+ * texel of f32 where a renderer loads half floats or a shared-exponent HDR image.  Here the stages run back to back on the
+ * context's stream, from the entries to the encoded atlas without leaving HBM: one point pass, one host read of the point
+ * count, one copy back of the encoded size (csrc/k_encode.hip.h is the one new kernel).
+ *
+ * THE LIGHTMAP RULE is an identity; there is no new arithmetic but the encoding.  Inputs: an rt_lightmap_desc d
+ * (mi355rt_layout.h) - the five fields of rt_bake_atlas_desc; the gather's max_depth, spp, seed; the filter's passes, step,
+ * normal_cos, plane_eps, max_dist; dilate_radius; format - the entries and optionally atlas_uv, as for an atlas bake.
+ *   f32 atlas   word for word the composition, in this order, of (1) rt_bake_atlas_irradiance for {width, height, pad_base,
+ *               t_max, n_entries}, the entries, atlas_uv, max_depth, spp and seed;  (2) unless passes == 0: rt_denoise_atlas of
+ *               that atlas for {width, height, step, passes, normal_cos, plane_eps, max_dist}, with the points and texels that
+ *               rt_bake_atlas_points gives for the same arguments;  (3) unless dilate_radius == 0: rt_dilate_atlas of the result
+ *               for {width, height, dilate_radius}.
+ *   counts      *n_covered_out = the bake's count n;  *n_filled_out = the dilation's count, 0 when dilate_radius == 0;  the
+ *               stats are the gather's, and rt_irradiance_gather_stats reports this gather afterwards.  Each may be NULL.
+ *   result      RT_LIGHTMAP_F32: that atlas.  Any other format: rt_encode_atlas of it.
+ *   n == 0      (no entry covers a texel) is valid: every texel is {+0, +0, +0, -1.0f}, nothing is filled.
+ *
+ * THE ENCODING RULE.  Texel by texel {r, g, b, w}; every step is exact, and there is no division, no log and no exp.
+ *   F32         the 16 bytes unchanged.
+ *   F16         8 bytes: the four halves rt_f32_to_f16(r), (g), (b), (w) of mi355rt_math.h in this order (round to nearest
+ *               even, overflow to infinity, NaN stays a NaN).  -1 and -2 are exact halves: coverage survives.
+ *   RGBE8       4 bytes, the little-endian word R | G << 8 | B << 16 | E << 24: a Radiance .hdr pixel.  A texel with w ==
+ *               -1.0f (no surface, not filled) is the word 0.  Otherwise each colour is sanitised, c' = (c > 0) ? min(c,
+ *               0x1.fffffep+126f) : 0 as float comparisons, so that a NaN, a negative value and either zero give +0;  v = the
+ *               largest c' and b = its biased exponent field (bits 23 .. 30);  b < 32 (v < 2^-95) is the word 0;  else E = b +
+ *               2 and each byte is floor(c' * 2^(134 - b)) - the scale is a representable power of two for b = 32 .. 253, the
+ *               product is exact and below 256, the largest channel lands in 128 .. 255, and a product that would be
+ *               denormal floors to 0 whether or not it is flushed.  A decoder reads c = (byte + 0.5) * 2^(E - 136): every
+ *               channel comes back within 2^(E - 137) of c'.  (1, 1, 1) is (128, 128, 128, 129), as in Radiance.
+ *               rt_rgbe8 of mi355rt_math.h is this rule on the host and on the device.
+ * Limits, all RT_ERR_INVALID and all raised before anything is enqueued, with messages that begin "lightmap:" (the encode
+ * entries: "encode atlas:"): a NULL descriptor, reserved != 0, a format that is none of the three, passes > 3, and with passes
+ * >= 1 a step of 0 or step << (passes - 1) > RT_DENOISE_MAX_STEP, dilate_radius > RT_DILATE_MAX_RADIUS, a NULL out, out_bytes
+ * below width * height * {16, 8, 4}, a dev_out that is not a 16-byte-aligned array the context's device can reach, and
+ * everything an atlas bake and an irradiance gather refuse for the same arguments (their message follows the prefix).
+ * RT_ERR_NOT_READY as for a bake.  The encode entries: width or height == 0, width * height > 2^24, a NULL array.
+ * A lightmap bake leaves the renderer as it was, like every bake.  It runs in the staging arrays of the stages it is made of
+ * and three of its own (the filtered atlas, the filled count, the encoded atlas), kept and grown, all sized before the first
+ * launch.
+ *   rt_bake_atlas_lightmap         blocking; entries, atlas_uv and out are host arrays.  One host read of the count between
+ *                                  the point pass and the gather, one copy of width * height * {16, 8, 4} bytes, one fence.
+ *   rt_bake_atlas_lightmap_device  dev_atlas_uv (or NULL) and dev_out are device-accessible arrays; the entries stay a host
+ *                                  array.  NOT enqueue-only: it still reads the count once, which fences the stream in the
+ *                                  middle of the call; behind that read it only enqueues, unless n_filled_out or stats is
+ *                                  asked for, which costs a second fence at the end.  An enqueue-only whole bake would need
+ *                                  the gather to take its count from the device, and is not built.
+ *   rt_encode_atlas                the encode stage alone, blocking, on host arrays: any atlas of 16-byte texels, such as one
+ *                                  rt_dilate_atlas returned.  No scene is needed; out may not overlap atlas_in unless the
+ *                                  format is RT_LIGHTMAP_F32 and they are equal.
+ *   rt_encode_atlas_device         the same on device-accessible arrays (16-byte aligned, on the context's device); dev_out
+ *                                  must not overlap dev_in.  Only enqueues on the context's stream. */
+int rt_bake_atlas_lightmap(rt_ctx* ctx, const rt_lightmap_desc* desc, const rt_bake_rect* entries, const float* atlas_uv,
+                           uint32_t n_uv_vertices, void* out, size_t out_bytes, uint32_t* n_covered_out, uint32_t* n_filled_out,
+                           rt_radiance_stats* stats);
+int rt_bake_atlas_lightmap_device(rt_ctx* ctx, const rt_lightmap_desc* desc, const rt_bake_rect* entries,
+                                  const void* dev_atlas_uv, void* dev_out, size_t out_bytes, uint32_t* n_covered_out,
+                                  uint32_t* n_filled_out, rt_radiance_stats* stats);
+int rt_encode_atlas(rt_ctx* ctx, uint32_t width, uint32_t height, uint32_t format, const float* atlas_in, void* out,
+                    size_t out_bytes);
+int rt_encode_atlas_device(rt_ctx* ctx, uint32_t width, uint32_t height, uint32_t format, const void* dev_in, void* dev_out,
+                           size_t out_bytes);
 
 /* ---- the sharded image: one picture rendered by `world` contexts ("ranks"), assembled on rank 0 ----
  * Rank k owns the image rows y with (y / stripe_rows) % world == k and traces only those (rt_set_stripes).  Its COMPACT

@@ -211,8 +211,31 @@ typedef struct rt_denoise_desc { /* 32 B */
   uint32_t reserved[1];       /* 0 */
 } rt_denoise_desc;
 
+/* ---- lightmaps (rt_bake_atlas_lightmap, mi355rt.h): an atlas bake, its filter, its gutter fill and its texel format ---- */
+#define RT_LIGHTMAP_F32 0u    /* 16 B per texel: {r, g, b, w} as the bakes return it */
+#define RT_LIGHTMAP_F16 1u    /* 8 B per texel: four halves, w included */
+#define RT_LIGHTMAP_RGBE8 2u  /* 4 B per texel: R | G << 8 | B << 16 | E << 24, a Radiance .hdr pixel */
+typedef struct rt_lightmap_desc { /* 64 B */
+  uint32_t width, height;     /* the five fields of rt_bake_atlas_desc, with their limits */
+  uint32_t pad_base;
+  float t_max;
+  uint32_t n_entries;
+  uint32_t max_depth, spp, seed; /* of the gather, as in rt_gather_irradiance */
+  uint32_t passes;            /* of the filter: 0 = no filter (the next four fields are then not read), at most 3 */
+  uint32_t step;              /* as in rt_denoise_desc: >= 1, step << (passes - 1) <= RT_DENOISE_MAX_STEP */
+  float normal_cos;           /* as in rt_denoise_desc */
+  float plane_eps;
+  float max_dist;
+  uint32_t dilate_radius;     /* of the gutter fill: 0 = none, at most RT_DILATE_MAX_RADIUS */
+  uint32_t format;            /* RT_LIGHTMAP_* */
+  uint32_t reserved[1];       /* 0 */
+} rt_lightmap_desc;
+
 #ifdef __cplusplus
 }
+static_assert(sizeof(rt_lightmap_desc) == 64, "rt_lightmap_desc is 64 bytes");
+static_assert(__builtin_offsetof(rt_lightmap_desc, passes) == 32 && __builtin_offsetof(rt_lightmap_desc, format) == 56,
+              "rt_lightmap_desc: the filter starts at 32, the format is at 56");
 static_assert(sizeof(rt_denoise_desc) == 32, "rt_denoise_desc is 32 bytes");
 static_assert(sizeof(rt_dilate_desc) == 32, "rt_dilate_desc is 32 bytes");
 static_assert(sizeof(rt_bake_desc) == 32, "rt_bake_desc is 32 bytes");

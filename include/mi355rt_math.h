@@ -357,6 +357,25 @@ RT_HD float rt_f16_to_f32(uint16_t h) {
   return rt_u2f(sign | ((e + 112u) << 23) | (m << 13));
 }
 
+/* One atlas texel {r, g, b, w} -> the shared-exponent word R | G << 8 | B << 16 | E << 24 of a Radiance .hdr pixel, by the
+ * encoding rule of mi355rt.h "lightmaps".  The exponent work is done on the integer bits: the three sanitised colours are
+ * non-negative floats, whose order is that of their bit patterns, and the scale 2^(134 - b) is assembled from its exponent
+ * field (261 - b, 8 .. 229 for b = 253 .. 32).  Each product is exact and below 256, so the conversion truncates = floors. */
+RT_HD uint32_t rt_rgbe8(float r, float g, float b, float w) {
+  if (w == -1.0f) return 0u;
+  const float top = 1.70141173319264429906e38f; /* 0x1.fffffep+126f */
+  float cr = r > 0.0f ? (r < top ? r : top) : 0.0f; /* NaN, negatives and both zeros -> +0 */
+  float cg = g > 0.0f ? (g < top ? g : top) : 0.0f;
+  float cb = b > 0.0f ? (b < top ? b : top) : 0.0f;
+  uint32_t ur = rt_f2u(cr), ug = rt_f2u(cg), ub = rt_f2u(cb);
+  uint32_t uv = ur > ug ? ur : ug;
+  if (ub > uv) uv = ub;
+  uint32_t e = uv >> 23; /* the biased exponent of the largest channel: the sign bit is clear */
+  if (e < 32u) return 0u;
+  float scale = rt_u2f((261u - e) << 23);
+  return (uint32_t)(cr * scale) | ((uint32_t)(cg * scale) << 8) | ((uint32_t)(cb * scale) << 16) | ((e + 2u) << 24);
+}
+
 /* ------------------------------------------------ texture ingest: resize to the 1024 x 1024 layer
  * createImageBitmap(blob, {resizeWidth: 1024, resizeHeight: 1024}) with the default resizeQuality "low"
  * (ResourceManager.ts:164-168): bilinear, pixel centres aligned, clamp to edge, per channel on straight RGBA8.

@@ -8,11 +8,11 @@ repo root) or through importlib.
 """
 from . import _build
 from .world_bridge import WorldBridge
-from .renderer import WebGPURenderer, RendererError, upload_scene, sync_world, LiveLoop
-from .recorder import FrameLoop, FrameJobRunner, job_list, write_png
+from .renderer import WebGPURenderer, RendererError, upload_scene, sync_world, LiveLoop, decode_rgbe
+from .recorder import FrameLoop, FrameJobRunner, job_list, write_png, write_hdr
 from . import textures
 
-__all__ = ["WebGPURenderer", "WorldBridge", "RendererError", "upload_scene", "sync_world", "LiveLoop", "FrameLoop", "FrameJobRunner", "job_list", "write_png", "textures", "build"]
+__all__ = ["WebGPURenderer", "WorldBridge", "RendererError", "upload_scene", "sync_world", "LiveLoop", "FrameLoop", "FrameJobRunner", "job_list", "write_png", "write_hdr", "decode_rgbe", "textures", "build"]
 
 
 def build(force=False):

@@ -29,6 +29,8 @@
 //                             bitmap (rt_dilate_atlas)
 //   k_denoise.hip.h           k_denoise_index / _pass: the edge-stopped a-trous filter of a baked atlas, guided by the bake's
 //                             points, on LDS windows (rt_denoise_atlas)
+//   k_encode.hip.h            k_encode_atlas: a finished f32 atlas as half floats or shared-exponent RGBE8 words
+//                             (rt_encode_atlas, the last stage of rt_bake_atlas_lightmap)
 //   k_texture_post.hip.h      k_resize_texture; k_postprocess = PostProcess.wgsl `main` (:103-176)
 //   k_validate.hip.h          k_validate_scene: every index the kernels follow, checked once per upload
 //   k_stripes.hip.h           k_pack_stripes / k_unpack_stripes: the copies of the sharded image's gather
@@ -62,6 +64,7 @@
 #include "k_bake.hip.h"
 #include "k_dilate.hip.h"
 #include "k_denoise.hip.h"
+#include "k_encode.hip.h"
 #include "k_wavefront.hip.h"
 #include "k_rayquery.hip.h"
 #include "k_texture_post.hip.h"

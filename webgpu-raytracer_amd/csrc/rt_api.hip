@@ -93,6 +93,13 @@ struct DenoiseState {
   DeviceBuffer index, scratch, in, out, points, texels;
 };
 
+// What a lightmap bake (rt_bake_atlas_lightmap) and the encode entries (rt_encode_atlas) keep between calls beyond the state of
+// the stages they are made of, kept and grown: the filtered atlas, the gutter fill's count, the encoded atlas and the staged
+// input of the host encode entry.
+struct LightmapState {
+  DeviceBuffer filtered, filled, encoded, in;
+};
+
 }  // namespace
 
 struct rt_ctx {
@@ -244,6 +251,7 @@ struct rt_ctx {
   BakeState bk;
   DilateState dl;
   DenoiseState dn;
+  LightmapState lm;
 
   // kernel timing
   bool timing = false;
@@ -979,6 +987,7 @@ void rt_destroy(rt_ctx* c) {
                          &c->bk.atlas, &c->bk.entries, &c->bk.items, &c->bk.owner64,
                          &c->dl.atlas, &c->dl.filled, &c->dl.bitmap, &c->dl.src,
                          &c->dn.index, &c->dn.scratch, &c->dn.in, &c->dn.out, &c->dn.points, &c->dn.texels,
+                         &c->lm.filtered, &c->lm.filled, &c->lm.encoded, &c->lm.in,
                          &c->tex_staging, &c->bv_in, &c->bv_tri, &c->bv_order, &c->bv_nodes, &c->bv_out,
                          &c->bv_counters, &c->bv_big, &c->val_roots, &c->val_bad, &c->tnodes, &c->node_key, &c->node_newidx,
                          &c->inst_root, &c->root_w, &c->treelet_work, &c->pairs, &c->pair_of, &c->pair_parent, &c->root_rec,
@@ -2494,14 +2503,12 @@ static int bake_gather_room(rt_ctx* c, uint32_t texels, uint32_t* n) {
   if ((r = ensure_buffer(c, c->bk.results, (size_t)*n * sizeof(rt_irradiance), true)) < 0) return r;
   return ensure_buffer(c, c->bk.atlas, (size_t)texels * sizeof(rt_irradiance), true);
 }
-// ... then, behind the emit launch of the bake's kind for those n points: the gather on them, the scatter kernel of the
-// bake's kind on its owner map d_owner, and the atlas to the caller.
-static int bake_gather_tail(rt_ctx* c, uint32_t texels, uint32_t n, uint32_t max_depth, uint32_t spp, uint32_t seed,
-                            rt_irradiance* atlas_out, uint32_t* n_covered_out, rt_radiance_stats* stats,
-                            void (*scatter)(rtk::BakeScatterArgs), const void* d_owner) {
+// ... then, behind the emit launch of the bake's kind for those n points: the gather on them and the scatter kernel of the
+// bake's kind on its owner map d_owner, enqueued; the atlas stays in bk.atlas ...
+static int bake_gather_scatter(rt_ctx* c, uint32_t texels, uint32_t n, uint32_t max_depth, uint32_t spp, uint32_t seed, bool detail,
+                               void (*scatter)(rtk::BakeScatterArgs), const void* d_owner) {
   int r;
-  if ((r = path_query_device(c, pq_gather, c->bk.points.ptr, n, max_depth, spp, seed, c->bk.results.ptr, stats != nullptr)) < 0)
-    return r;
+  if ((r = path_query_device(c, pq_gather, c->bk.points.ptr, n, max_depth, spp, seed, c->bk.results.ptr, detail)) < 0) return r;
   rtk::BakeScatterArgs B;
   B.owner = d_owner;
   B.texels = (const uint32_t*)c->bk.texels.ptr;
@@ -2511,6 +2518,14 @@ static int bake_gather_tail(rt_ctx* c, uint32_t texels, uint32_t n, uint32_t max
   B.n = n;
   hipLaunchKernelGGL(scatter, dim3((texels + 255u) / 256u), dim3(256), 0, c->stream, B);
   HIP_TRY(c, hipGetLastError());
+  return RT_OK;
+}
+// ... and, for the bakes that end there, the atlas to the caller.
+static int bake_gather_tail(rt_ctx* c, uint32_t texels, uint32_t n, uint32_t max_depth, uint32_t spp, uint32_t seed,
+                            rt_irradiance* atlas_out, uint32_t* n_covered_out, rt_radiance_stats* stats,
+                            void (*scatter)(rtk::BakeScatterArgs), const void* d_owner) {
+  int r;
+  if ((r = bake_gather_scatter(c, texels, n, max_depth, spp, seed, stats != nullptr, scatter, d_owner)) < 0) return r;
   HIP_TRY(c, hipMemcpyAsync(atlas_out, c->bk.atlas.ptr, (size_t)texels * sizeof(rt_irradiance), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   if (n_covered_out) *n_covered_out = n;
@@ -2894,6 +2909,194 @@ int rt_denoise_atlas(rt_ctx* c, const rt_denoise_desc* d, const float* atlas_in,
                           c->dn.out.ptr)) < 0)
     return r;
   HIP_TRY(c, hipMemcpyAsync(atlas_out, c->dn.out.ptr, bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return RT_OK;
+}
+
+// ---- lightmaps: the stages above back to back on the context's stream, and the encode stage (mi355rt.h "lightmaps";
+// k_encode.hip.h).  Bytes per texel of a format; 0 = not a format.
+static const char* const kLightmap = "lightmap";
+static const char* const kEncode = "encode atlas";
+static size_t lightmap_texel_bytes(uint32_t format) {
+  return format == RT_LIGHTMAP_F32 ? 16 : format == RT_LIGHTMAP_F16 ? 8 : format == RT_LIGHTMAP_RGBE8 ? 4 : 0;
+}
+// Enqueue the encode of `texels` texels at d_in into d_out, which is another array: a copy for RT_LIGHTMAP_F32, else the kernel
+static int launch_encode(rt_ctx* c, uint32_t texels, uint32_t format, const void* d_in, void* d_out) {
+  if (format == RT_LIGHTMAP_F32) {
+    HIP_TRY(c, hipMemcpyAsync(d_out, d_in, (size_t)texels * 16, hipMemcpyDeviceToDevice, c->stream));
+    return RT_OK;
+  }
+  rtk::EncodeArgs A;
+  A.in = (const uint4*)d_in;
+  A.out = d_out;
+  A.n = texels;
+  A.format = format;
+  hipLaunchKernelGGL(rtk::k_encode_atlas, dim3((texels + 255u) / 256u), dim3(256), 0, c->stream, A);
+  HIP_TRY(c, hipGetLastError());
+  return RT_OK;
+}
+// a refusal of one of the stages, under the lightmap's name: "lightmap: bake atlas: entry 3: ..."
+static int lightmap_refused(rt_ctx* c, int code) { return fail(c, code, std::string(kLightmap) + ": " + c->error); }
+// everything the limits say that needs neither a scene nor the output
+static int lightmap_desc_ok(rt_ctx* c, const rt_lightmap_desc* d, const rt_bake_rect* entries, rt_bake_atlas_desc* bake) {
+  const std::string w(kLightmap);
+  if (!d) return fail(c, RT_ERR_INVALID, w + ": NULL descriptor");
+  if (d->reserved[0]) return fail(c, RT_ERR_INVALID, w + ": reserved words must be 0");
+  if (!lightmap_texel_bytes(d->format)) return fail(c, RT_ERR_INVALID, w + ": format must be RT_LIGHTMAP_F32, _F16 or _RGBE8");
+  if (d->passes > 3) return fail(c, RT_ERR_INVALID, w + ": passes must be <= 3");
+  if (d->passes && (d->step == 0 || d->step > RT_DENOISE_MAX_STEP || (d->step << (d->passes - 1)) > RT_DENOISE_MAX_STEP))
+    return fail(c, RT_ERR_INVALID, w + ": step must be >= 1 and step << (passes - 1) <= 4");
+  if (d->dilate_radius > RT_DILATE_MAX_RADIUS) return fail(c, RT_ERR_INVALID, w + ": dilate_radius must be <= 24");
+  *bake = rt_bake_atlas_desc();
+  bake->width = d->width;
+  bake->height = d->height;
+  bake->pad_base = d->pad_base;
+  bake->t_max = d->t_max;
+  bake->n_entries = d->n_entries;
+  int r = bake_atlas_desc_ok(c, bake, entries);
+  if (r < 0) return lightmap_refused(c, r);
+  if ((r = path_query_args_ok(c, pq_gather, d->width * d->height, d->spp)) < 0) return lightmap_refused(c, r);
+  return RT_OK;
+}
+// The whole bake behind its checks.  d_out null: the host form, `out` receives the encoded atlas; else the device form.
+static int lightmap_bake(rt_ctx* c, const rt_lightmap_desc* d, const rt_bake_atlas_desc* bake, const rt_bake_rect* entries,
+                         const void* d_uv, void* out, void* d_out, uint32_t* n_covered_out, uint32_t* n_filled_out,
+                         rt_radiance_stats* stats) {
+  const uint32_t texels = d->width * d->height;
+  const size_t atlas_bytes = (size_t)texels * 16, out_bytes = (size_t)texels * lightmap_texel_bytes(d->format);
+  const bool count_filled = n_filled_out && d->dilate_radius;
+  int r;
+  // every atlas-sized array before the first launch: growing one later would wait for the stream (ensure_buffer).  The
+  // stages ask again for what is theirs, and find it there.
+  if ((r = ensure_buffer(c, c->bk.count, 16, false)) < 0) return r;
+  if ((r = ensure_buffer(c, c->bk.atlas, atlas_bytes, true)) < 0) return r;
+  if (d->passes) {
+    if ((r = ensure_buffer(c, c->lm.filtered, atlas_bytes, true)) < 0) return r;
+    if ((r = ensure_buffer(c, c->dn.index, (size_t)texels * 4, true)) < 0) return r;
+    if (d->passes > 1 && (r = ensure_buffer(c, c->dn.scratch, atlas_bytes, true)) < 0) return r;
+  }
+  if (d->dilate_radius) {
+    if ((r = ensure_buffer(c, c->dl.bitmap, (size_t)d->height * ((d->width + 63u) / 64u) * 8, true)) < 0) return r;
+    if ((r = ensure_buffer(c, c->dl.src, (size_t)texels * 4, true)) < 0) return r;
+    if ((r = ensure_buffer(c, c->lm.filled, 16, false)) < 0) return r;
+  }
+  if (!d_out && d->format != RT_LIGHTMAP_F32 && (r = ensure_buffer(c, c->lm.encoded, out_bytes, true)) < 0) return r;
+  // the point pass, once: its points and texels stay in the bake's arrays for the filter
+  rtk::BakeAtlasArgs A;
+  if ((r = bake_atlas_front(c, bake, entries, d_uv, nullptr, c->bk.count.ptr, A)) < 0) return r;
+  uint32_t n;
+  if ((r = bake_gather_room(c, texels, &n)) < 0) return r;
+  if ((r = bake_atlas_emit(c, A, c->bk.points.ptr, c->bk.texels.ptr, n)) < 0) return r;
+  if ((r = bake_gather_scatter(c, texels, n, d->max_depth, d->spp, d->seed, stats != nullptr, rtk::k_atlas_scatter, A.owner)) < 0)
+    return r;
+  void* current = c->bk.atlas.ptr;
+  if (d->passes) {
+    rt_denoise_desc f = {};
+    f.width = d->width;
+    f.height = d->height;
+    f.step = d->step;
+    f.passes = d->passes;
+    f.normal_cos = d->normal_cos;
+    f.plane_eps = d->plane_eps;
+    f.max_dist = d->max_dist;
+    if ((r = launch_denoise(c, &f, current, c->bk.points.ptr, c->bk.texels.ptr, n, c->lm.filtered.ptr)) < 0) return r;
+    current = c->lm.filtered.ptr;
+  }
+  if (d->dilate_radius) {
+    rt_dilate_desc g = {};
+    g.width = d->width;
+    g.height = d->height;
+    g.radius = d->dilate_radius;
+    if ((r = launch_dilate(c, &g, current, nullptr, count_filled ? c->lm.filled.ptr : nullptr)) < 0) return r;
+  }
+  uint32_t filled = 0;
+  if (d_out) {
+    if ((r = launch_encode(c, texels, d->format, current, d_out)) < 0) return r;
+  } else {
+    const void* from = current;
+    if (d->format != RT_LIGHTMAP_F32) {
+      if ((r = launch_encode(c, texels, d->format, current, c->lm.encoded.ptr)) < 0) return r;
+      from = c->lm.encoded.ptr;
+    }
+    HIP_TRY(c, hipMemcpyAsync(out, from, out_bytes, hipMemcpyDeviceToHost, c->stream));
+  }
+  if (count_filled) HIP_TRY(c, hipMemcpyAsync(&filled, c->lm.filled.ptr, 4, hipMemcpyDeviceToHost, c->stream));
+  if (!d_out || count_filled) HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (n_covered_out) *n_covered_out = n;
+  if (n_filled_out) *n_filled_out = filled;
+  if (stats) return path_query_stats(c, pq_gather, stats);
+  return RT_OK;
+}
+
+int rt_bake_atlas_lightmap(rt_ctx* c, const rt_lightmap_desc* d, const rt_bake_rect* entries, const float* atlas_uv,
+                           uint32_t n_uv_vertices, void* out, size_t out_bytes, uint32_t* n_covered_out, uint32_t* n_filled_out,
+                           rt_radiance_stats* stats) {
+  if (!c) return RT_ERR_INVALID;
+  rt_bake_atlas_desc bake;
+  int r = lightmap_desc_ok(c, d, entries, &bake);
+  if (r < 0) return r;
+  if (!out) return fail(c, RT_ERR_INVALID, std::string(kLightmap) + ": NULL array");
+  if (out_bytes < (size_t)d->width * d->height * lightmap_texel_bytes(d->format))
+    return fail(c, RT_ERR_INVALID, std::string(kLightmap) + ": out_bytes is below width * height texels of the format");
+  if ((r = bake_atlas_scene_ready(c, &bake, entries, true)) < 0) return lightmap_refused(c, r);
+  const void* d_uv;
+  if ((r = bake_stage_uv(c, kLightmap, atlas_uv, n_uv_vertices, &d_uv)) < 0) return r;
+  return lightmap_bake(c, d, &bake, entries, d_uv, out, nullptr, n_covered_out, n_filled_out, stats);
+}
+
+int rt_bake_atlas_lightmap_device(rt_ctx* c, const rt_lightmap_desc* d, const rt_bake_rect* entries, const void* dev_atlas_uv,
+                                  void* dev_out, size_t out_bytes, uint32_t* n_covered_out, uint32_t* n_filled_out,
+                                  rt_radiance_stats* stats) {
+  if (!c) return RT_ERR_INVALID;
+  rt_bake_atlas_desc bake;
+  int r = lightmap_desc_ok(c, d, entries, &bake);
+  if (r < 0) return r;
+  if ((r = query_device_arrays_ok(c, kLightmap, dev_out, dev_atlas_uv ? dev_atlas_uv : dev_out)) < 0) return r;
+  if (out_bytes < (size_t)d->width * d->height * lightmap_texel_bytes(d->format))
+    return fail(c, RT_ERR_INVALID, std::string(kLightmap) + ": out_bytes is below width * height texels of the format");
+  if ((r = bake_atlas_scene_ready(c, &bake, entries, true)) < 0) return lightmap_refused(c, r);
+  return lightmap_bake(c, d, &bake, entries, dev_atlas_uv, nullptr, dev_out, n_covered_out, n_filled_out, stats);
+}
+
+static int encode_args_ok(rt_ctx* c, uint32_t width, uint32_t height, uint32_t format, const void* in, const void* out,
+                          size_t out_bytes) {
+  const std::string w(kEncode);
+  if (width == 0 || height == 0) return fail(c, RT_ERR_INVALID, w + ": width and height must be >= 1");
+  if ((uint64_t)width * height > (1ull << 24)) return fail(c, RT_ERR_INVALID, w + ": width * height must be <= 2^24");
+  if (!lightmap_texel_bytes(format)) return fail(c, RT_ERR_INVALID, w + ": format must be RT_LIGHTMAP_F32, _F16 or _RGBE8");
+  if (!in || !out) return fail(c, RT_ERR_INVALID, w + ": NULL array");
+  if (out_bytes < (size_t)width * height * lightmap_texel_bytes(format))
+    return fail(c, RT_ERR_INVALID, w + ": out_bytes is below width * height texels of the format");
+  return RT_OK;
+}
+
+int rt_encode_atlas_device(rt_ctx* c, uint32_t width, uint32_t height, uint32_t format, const void* dev_in, void* dev_out,
+                           size_t out_bytes) {
+  if (!c) return RT_ERR_INVALID;
+  int r = encode_args_ok(c, width, height, format, dev_in, dev_out, out_bytes);
+  if (r < 0) return r;
+  if (dev_in == dev_out) return fail(c, RT_ERR_INVALID, std::string(kEncode) + ": the output must not be the input");
+  if ((r = query_device_arrays_ok(c, kEncode, dev_in, dev_out)) < 0) return r;
+  return launch_encode(c, width * height, format, dev_in, dev_out);
+}
+
+int rt_encode_atlas(rt_ctx* c, uint32_t width, uint32_t height, uint32_t format, const float* atlas_in, void* out,
+                    size_t out_bytes) {
+  if (!c) return RT_ERR_INVALID;
+  int r = encode_args_ok(c, width, height, format, atlas_in, out, out_bytes);
+  if (r < 0) return r;
+  const uint32_t texels = width * height;
+  const size_t bytes = (size_t)texels * lightmap_texel_bytes(format);
+  if (format == RT_LIGHTMAP_F32) {   // the 16 bytes unchanged: nothing for the device to do
+    if (out != (const void*)atlas_in) std::memmove(out, atlas_in, bytes);
+    return RT_OK;
+  }
+  HIP_TRY(c, hipSetDevice(c->device));
+  if ((r = ensure_buffer(c, c->lm.in, (size_t)texels * 16, true)) < 0) return r;
+  if ((r = ensure_buffer(c, c->lm.encoded, bytes, true)) < 0) return r;
+  HIP_TRY(c, hipMemcpyAsync(c->lm.in.ptr, atlas_in, (size_t)texels * 16, hipMemcpyHostToDevice, c->stream));
+  if ((r = launch_encode(c, texels, format, c->lm.in.ptr, c->lm.encoded.ptr)) < 0) return r;
+  HIP_TRY(c, hipMemcpyAsync(out, c->lm.encoded.ptr, bytes, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return RT_OK;
 }

@@ -856,6 +856,72 @@ static napi_value rtDenoiseAtlas(napi_env env, napi_callback_info info) {
                                         (const uint32_t*)texels, (uint32_t)n, (float*)out));
 }
 
+/* ------------------------------------------------------- lightmaps (rt_bake_atlas_lightmap, rt_encode_atlas, mi355rt.h) */
+/* (ctx, width, height, padBase, tMax, entries, atlasUv or null, maxDepth, spp, seed, stages: Float64Array {passes, step,
+ * normalCos, planeEps, maxDist, dilateRadius, format}, out: a typed array of width * height texels of the format, wantStats)
+ * -> {covered, filled, stats?}, or a negative status */
+static napi_value rtBakeAtlasLightmap(napi_env env, napi_callback_info info) {
+  napi_value a[13];
+  void *entries = NULL, *uv = NULL, *stages = NULL, *out = NULL;
+  size_t ne = 0, nuv = 0, ns = 0, no = 0;
+  bool want_stats = false;
+  if (!get_args(env, info, 13, a) || !get_bytes(env, a[5], &entries, &ne) || !get_bytes(env, a[6], &uv, &nuv) ||
+      !get_bytes(env, a[10], &stages, &ns) || !get_bytes(env, a[11], &out, &no))
+    return NULL;
+  napi_get_value_bool(env, a[12], &want_stats);
+  rt_bake_atlas_desc b;
+  if (!bake_atlas_desc(env, a + 1, ne, &b)) return NULL;
+  if (nuv % 8 != 0 || nuv / 8 > 0xffffffffu || !stages || ns != 7 * sizeof(double)) {
+    napi_throw_range_error(env, NULL, "rtBakeAtlasLightmap: atlasUv must hold 2 floats per vertex and stages 7 doubles");
+    return NULL;
+  }
+  const double* s = (const double*)stages;
+  rt_lightmap_desc d;
+  memset(&d, 0, sizeof(d));
+  d.width = b.width;
+  d.height = b.height;
+  d.pad_base = b.pad_base;
+  d.t_max = b.t_max;
+  d.n_entries = b.n_entries;
+  d.max_depth = get_u32(env, a[7]);
+  d.spp = get_u32(env, a[8]);
+  d.seed = get_u32(env, a[9]);
+  d.passes = (uint32_t)s[0];
+  d.step = (uint32_t)s[1];
+  d.normal_cos = (float)s[2];
+  d.plane_eps = (float)s[3];
+  d.max_dist = (float)s[4];
+  d.dilate_radius = (uint32_t)s[5];
+  d.format = (uint32_t)s[6];
+  rt_radiance_stats st;
+  uint32_t n = 0, filled = 0;
+  const int rc = rt_bake_atlas_lightmap((rt_ctx*)get_ptr(env, a[0]), &d, (const rt_bake_rect*)entries, (const float*)uv,
+                                        (uint32_t)(nuv / 8), out, no, &n, &filled, want_stats ? &st : NULL);
+  if (rc < 0) return make_int(env, rc);
+  napi_value obj, v;
+  if (napi_create_object(env, &obj) != napi_ok) return NULL;
+  napi_create_uint32(env, n, &v);
+  napi_set_named_property(env, obj, "covered", v);
+  napi_create_uint32(env, filled, &v);
+  napi_set_named_property(env, obj, "filled", v);
+  if (want_stats) napi_set_named_property(env, obj, "stats", radiance_stats_object(env, &st));
+  return obj;
+}
+/* (ctx, width, height, format, atlas: Float32Array of 4 per texel (read), out: a typed array of width * height texels of the
+ * format) -> 0, or a negative status */
+static napi_value rtEncodeAtlas(napi_env env, napi_callback_info info) {
+  napi_value a[6];
+  void *atlas = NULL, *out = NULL;
+  size_t na = 0, no = 0;
+  if (!get_args(env, info, 6, a) || !get_bytes(env, a[4], &atlas, &na) || !get_bytes(env, a[5], &out, &no)) return NULL;
+  const uint32_t width = get_u32(env, a[1]), height = get_u32(env, a[2]), format = get_u32(env, a[3]);
+  if (na / 16 < (size_t)width * height) {
+    napi_throw_range_error(env, NULL, "rtEncodeAtlas: atlas must hold 4 floats per texel");
+    return NULL;
+  }
+  return make_int(env, rt_encode_atlas((rt_ctx*)get_ptr(env, a[0]), width, height, format, (const float*)atlas, out, no));
+}
+
 static napi_value Init(napi_env env, napi_value exports) {
   static const struct {
     const char* name;
@@ -876,7 +942,8 @@ static napi_value Init(napi_env env, napi_value exports) {
                {"rtGatherIrradiance", rtGatherIrradiance}, {"rtGatherProbes", rtGatherProbes}, {"rtBakePoints", rtBakePoints},
                {"rtBakeIrradiance", rtBakeIrradiance}, {"rtBakeAtlasPoints", rtBakeAtlasPoints},
                {"rtBakeAtlasIrradiance", rtBakeAtlasIrradiance}, {"rtDilateAtlas", rtDilateAtlas},
-               {"rtDenoiseAtlas", rtDenoiseAtlas}, {"msCreate", msCreate}, {"msDestroy", msDestroy},
+               {"rtDenoiseAtlas", rtDenoiseAtlas}, {"rtBakeAtlasLightmap", rtBakeAtlasLightmap},
+               {"rtEncodeAtlas", rtEncodeAtlas}, {"msCreate", msCreate}, {"msDestroy", msDestroy},
                {"msUpdate", msUpdate}, {"msUpdateCamera", msUpdateCamera}, {"msGet", msGet},
                {"msTextureCount", msTextureCount}, {"msTexture", msTexture},
                {"msAnimationNames", msAnimationNames}, {"msSetAnimation", msSetAnimation},

@@ -106,6 +106,19 @@ export class WebGPURenderer {
   denoiseAtlas(atlas: Float32Array, width: number, height: number, points: Float32Array | null, texels: Uint32Array | null,
                opts: { planeEps: number; maxDist: number; normalCos?: number; passes?: number; step?: number }):
     { data: Float32Array; width: number; height: number };
+  /** The finished lightmap in one call (rt_bake_atlas_lightmap): the atlas bake, the filter on the guides the bake already
+   *  holds on the device, the gutter fill and the encode, with one copy back.  'f32': 4 floats per texel, word for word
+   *  bakeAtlasIrradiance -> denoiseAtlas -> dilateAtlas; 'f16': 4 halves per texel; 'rgbe': one Radiance pixel R | G << 8 |
+   *  B << 16 | E << 24 per texel, 0 where there is no surface and nothing was filled. */
+  bakeAtlasLightmap(entries: number[][] | Uint32Array, width: number, height: number, maxDepth: number, spp: number,
+                    opts?: { tMax?: number; padBase?: number; atlasUv?: Float32Array | null; seed?: number; stats?: boolean;
+                             denoise?: { planeEps: number; maxDist: number; normalCos?: number; passes?: number; step?: number } | null;
+                             dilate?: number; format?: 'f32' | 'f16' | 'rgbe' }):
+    { data: Float32Array | Uint16Array | Uint32Array; width: number; height: number; format: 'f32' | 'f16' | 'rgbe';
+      covered: number; filled: number; stats?: RadianceQueryStats };
+  /** The encode stage alone (rt_encode_atlas) on any atlas of 4 floats per texel.  `data` is a new array. */
+  encodeAtlas(atlas: Float32Array, width: number, height: number, format: 'f32' | 'f16' | 'rgbe'):
+    { data: Float32Array | Uint16Array | Uint32Array; width: number; height: number; format: 'f32' | 'f16' | 'rgbe' };
   destroy(): void;
 }
 export class WorldBridge {

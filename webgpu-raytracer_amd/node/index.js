@@ -311,6 +311,43 @@ class WebGPURenderer {
       opts.maxDist, atlas, n ? points : null, n ? texels : null, data), 'denoiseAtlas');
     return { data, width, height };
   }
+  // ---- lightmaps (rt_bake_atlas_lightmap, rt_encode_atlas): the finished lightmap in one call - the atlas bake, the filter on
+  // the guides the bake already holds on the device, the gutter fill and the encode, with one copy back.  opts as for
+  // bakeAtlasIrradiance plus {denoise: null or {planeEps, maxDist, normalCos = 0.9, passes = 3, step = 1}, dilate = 0, format =
+  // 'f32'}.  Result: {data, width, height, format, covered, filled} and with stats the gather's .stats.  data is a Float32Array
+  // of 4 per texel ('f32': word for word bakeAtlasIrradiance, then denoiseAtlas, then dilateAtlas), a Uint16Array of 4 halves per
+  // texel ('f16') or a Uint32Array of one Radiance pixel R | G << 8 | B << 16 | E << 24 per texel ('rgbe').
+  static _lightmapFormat(format) {
+    const f = { f32: 0, f16: 1, rgbe: 2, rgbe8: 2 }[String(format === undefined ? 'f32' : format).toLowerCase()];
+    if (f === undefined) throw new TypeError("lightmap format must be 'f32', 'f16' or 'rgbe'");
+    return f;
+  }
+  static _lightmapArray(texels, f) {
+    return f === 1 ? new Uint16Array(texels * 4) : f === 2 ? new Uint32Array(texels) : new Float32Array(texels * 4);
+  }
+  bakeAtlasLightmap(entries, width, height, maxDepth, spp, opts = {}) {
+    const f = WebGPURenderer._lightmapFormat(opts.format), dn = opts.denoise || null;
+    if (dn && !(dn.planeEps !== undefined && dn.maxDist !== undefined)) throw new TypeError('bakeAtlasLightmap: denoise.planeEps and denoise.maxDist are required');
+    const stages = dn ? Float64Array.of(dn.passes === undefined ? 3 : dn.passes, dn.step === undefined ? 1 : dn.step,
+      dn.normalCos === undefined ? 0.9 : dn.normalCos, dn.planeEps, dn.maxDist, opts.dilate || 0, f)
+      : Float64Array.of(0, 0, 0, 0, 0, opts.dilate || 0, f);
+    const data = WebGPURenderer._lightmapArray(width * height, f);
+    const r = native.rtBakeAtlasLightmap(this._ctx, width >>> 0, height >>> 0, (opts.padBase || 0) >>> 0,
+      opts.tMax === undefined ? 1e30 : opts.tMax, WebGPURenderer._atlasEntries(entries), opts.atlasUv || null, maxDepth >>> 0,
+      spp >>> 0, (opts.seed || 0) >>> 0, stages, data, !!opts.stats);
+    if (typeof r === 'number') this._check(r, 'bakeAtlasLightmap');
+    const out = { data, width, height, format: ['f32', 'f16', 'rgbe'][f], covered: r.covered, filled: r.filled };
+    if (r.stats) out.stats = r.stats;
+    return out;
+  }
+  // The encode stage alone: atlas = 4 floats per texel, e.g. what dilateAtlas returned.  Result: {data, width, height, format}.
+  encodeAtlas(atlas, width, height, format) {
+    if (!(atlas instanceof Float32Array) || atlas.length !== width * height * 4) throw new TypeError('encodeAtlas: a Float32Array of 4 floats per texel');
+    const f = WebGPURenderer._lightmapFormat(format);
+    const data = WebGPURenderer._lightmapArray(width * height, f);
+    this._check(native.rtEncodeAtlas(this._ctx, width >>> 0, height >>> 0, f, atlas, data), 'encodeAtlas');
+    return { data, width, height, format: ['f32', 'f16', 'rgbe'][f] };
+  }
   destroy() { if (this._ctx) { native.rtDestroy(this._ctx); this._ctx = null; } }
 }
 

@@ -117,6 +117,19 @@ def write_png(path, rgba):
         f.write(chunk(b"IEND", b""))
 
 
+# A baked lightmap to disk: the RGBE8 words of bakeAtlasLightmap(format="rgbe") are Radiance pixels already.
+def write_hdr(path, rgbe):
+    """An (H, W) uint32 array of RGBE8 words, as bakeAtlasLightmap(format="rgbe") returns it, as a flat (not run-length
+    coded) Radiance picture: the header lines, an empty line, the resolution "-Y H +X W", then the four bytes R G B E of
+    every texel, row by row from row 0."""
+    a = np.ascontiguousarray(rgbe, dtype=np.uint32)
+    if a.ndim != 2:
+        raise ValueError("write_hdr expects an (H, W) uint32 array")
+    with open(path, "wb") as f:
+        f.write(b"#?RADIANCE\nFORMAT=32-bit_rle_rgbe\n\n-Y %d +X %d\n" % a.shape)
+        f.write(a.astype("<u4").tobytes())
+
+
 def write_frame(out_dir, index, rgba, fmt):
     name = "frame_%06d.%s" % (index, "png" if fmt == "png" else "rgba")
     path = os.path.join(out_dir, name)

@@ -215,6 +215,11 @@ def load_library(path=None):
         # atlas denoise
         "rt_denoise_atlas": (i32, [vp, vp, vp, vp, vp, u32, vp]),
         "rt_denoise_atlas_device": (i32, [vp, vp, vp, vp, vp, u32, vp]),
+        # lightmaps
+        "rt_bake_atlas_lightmap": (i32, [vp, vp, vp, vp, u32, vp, ctypes.c_size_t, vp, vp, vp]),
+        "rt_bake_atlas_lightmap_device": (i32, [vp, vp, vp, vp, vp, ctypes.c_size_t, vp, vp, vp]),
+        "rt_encode_atlas": (i32, [vp, u32, u32, u32, vp, vp, ctypes.c_size_t]),
+        "rt_encode_atlas_device": (i32, [vp, u32, u32, u32, vp, vp, ctypes.c_size_t]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(L, name)  # AttributeError here = header/library mismatch
@@ -243,7 +248,8 @@ EXPORTED_SYMBOLS = (
     "rt_bake_points rt_bake_points_device rt_bake_irradiance "
     "rt_bake_atlas_points rt_bake_atlas_points_device rt_bake_atlas_irradiance "
     "rt_dilate_atlas rt_dilate_atlas_device "
-    "rt_denoise_atlas rt_denoise_atlas_device").split()
+    "rt_denoise_atlas rt_denoise_atlas_device "
+    "rt_bake_atlas_lightmap rt_bake_atlas_lightmap_device rt_encode_atlas rt_encode_atlas_device").split()
 
 
 # ---- ray queries: mirrors of rt_ray / rt_ray_hit / rt_ray_stats (include/mi355rt_layout.h)
@@ -337,6 +343,46 @@ class RtDenoiseDesc(ctypes.Structure):
     _fields_ = [("width", ctypes.c_uint32), ("height", ctypes.c_uint32), ("step", ctypes.c_uint32), ("passes", ctypes.c_uint32),
                 ("normal_cos", ctypes.c_float), ("plane_eps", ctypes.c_float), ("max_dist", ctypes.c_float),
                 ("reserved", ctypes.c_uint32 * 1)]
+
+
+# lightmaps: mirror of rt_lightmap_desc, the RT_LIGHTMAP_* formats by name, and what a texel of each is on the host
+class RtLightmapDesc(ctypes.Structure):
+    _fields_ = [("width", ctypes.c_uint32), ("height", ctypes.c_uint32), ("pad_base", ctypes.c_uint32), ("t_max", ctypes.c_float),
+                ("n_entries", ctypes.c_uint32), ("max_depth", ctypes.c_uint32), ("spp", ctypes.c_uint32), ("seed", ctypes.c_uint32),
+                ("passes", ctypes.c_uint32), ("step", ctypes.c_uint32), ("normal_cos", ctypes.c_float),
+                ("plane_eps", ctypes.c_float), ("max_dist", ctypes.c_float), ("dilate_radius", ctypes.c_uint32),
+                ("format", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 1)]
+
+
+RT_LIGHTMAP_F32, RT_LIGHTMAP_F16, RT_LIGHTMAP_RGBE8 = 0, 1, 2
+LIGHTMAP_FORMATS = {"f32": RT_LIGHTMAP_F32, "f16": RT_LIGHTMAP_F16, "rgbe": RT_LIGHTMAP_RGBE8, "rgbe8": RT_LIGHTMAP_RGBE8}
+LIGHTMAP_TEXEL_BYTES = {RT_LIGHTMAP_F32: 16, RT_LIGHTMAP_F16: 8, RT_LIGHTMAP_RGBE8: 4}
+
+
+def _lightmap_format(format):
+    if isinstance(format, str):
+        if format.lower() not in LIGHTMAP_FORMATS:
+            raise ValueError("lightmap format must be one of %s" % ", ".join(sorted(LIGHTMAP_FORMATS)))
+        return LIGHTMAP_FORMATS[format.lower()]
+    return int(format)
+
+
+def _lightmap_array(height, width, fmt):
+    """the host array of an encoded atlas: (H, W) IRRADIANCE_DTYPE, (H, W, 4) float16 or (H, W) uint32"""
+    if fmt == RT_LIGHTMAP_F16:
+        return np.empty((height, width, 4), np.float16)
+    if fmt == RT_LIGHTMAP_RGBE8:
+        return np.empty((height, width), np.uint32)
+    return np.empty((height, width), dtype=IRRADIANCE_DTYPE)   # an unknown format is the library's to refuse
+
+
+def decode_rgbe(words):
+    """RGBE8 words (any shape, uint32; R | G << 8 | B << 16 | E << 24) -> (..., 3) float64 colours, (byte + 0.5) * 2^(E - 136)
+    as a Radiance reader decodes them; the word 0 (and any word with E == 0) is black."""
+    w = np.asarray(words, np.uint32)
+    e = (w >> 24).astype(np.int64)
+    rgb = np.stack([((w >> s) & 0xff).astype(np.float64) for s in (0, 8, 16)], axis=-1)
+    return np.where((e > 0)[..., None], np.ldexp(rgb + 0.5, (e - 136)[..., None]), 0.0)
 
 
 def _ptr(a):
@@ -923,6 +969,95 @@ class WebGPURenderer:
         self._check(self.L.rt_denoise_atlas_device(self.ctx, ctypes.addressof(d), ctypes.c_void_p(in_ptr or 0),
                                                    ctypes.c_void_p(points_ptr or 0), ctypes.c_void_p(texels_ptr or 0), int(n),
                                                    ctypes.c_void_p(out_ptr or 0)), "denoiseAtlasDevice")
+
+    # ---- lightmaps: bake, filter, gutter fill and encode in one call, without leaving the device (rt_bake_atlas_lightmap) ----
+    @staticmethod
+    def _lightmap_desc(d, max_depth, spp, seed, denoise, dilate, fmt):
+        """rt_lightmap_desc from an rt_bake_atlas_desc and the rest; denoise: None or denoiseAtlas's keyword arguments"""
+        m = RtLightmapDesc()
+        m.width, m.height, m.pad_base, m.t_max, m.n_entries = d.width, d.height, d.pad_base, d.t_max, d.n_entries
+        m.max_depth, m.spp, m.seed = int(max_depth), int(spp), int(seed) & 0xffffffff
+        if denoise is not None:
+            kw = dict(normal_cos=0.9, passes=3, step=1)
+            kw.update(denoise)
+            unknown = set(kw) - {"plane_eps", "max_dist", "normal_cos", "passes", "step"}
+            if unknown or "plane_eps" not in kw or "max_dist" not in kw:
+                raise TypeError("denoise takes denoiseAtlas's keyword arguments, plane_eps and max_dist at least")
+            m.passes, m.step = int(kw["passes"]), int(kw["step"])
+            m.normal_cos, m.plane_eps, m.max_dist = float(kw["normal_cos"]), float(kw["plane_eps"]), float(kw["max_dist"])
+        m.dilate_radius, m.format = int(dilate), fmt
+        return m
+
+    def bakeAtlasLightmap(self, entries, width, height, max_depth, spp, seed=0, t_max=1e30, pad_base=0, atlas_uv=None,
+                          denoise=None, dilate=0, format="f32", stats=False):
+        """The finished lightmap in one call: the atlas bake of bakeAtlasIrradiance, then - denoise: None or a dict of
+        denoiseAtlas's keyword arguments - the filter on the guides the bake already holds on the device, then - dilate > 0
+        - the gutter fill of that radius, then the encode, all on the device; one read of the point count and one copy back.
+        With format "f32" the result is word for word bakeAtlasIrradiance(..., denoise=..., dilate=...), the (height, width)
+        IRRADIANCE_DTYPE atlas; "f16" gives (height, width, 4) float16 {r, g, b, w}; "rgbe" (or "rgbe8") (height, width)
+        uint32 Radiance pixels R | G << 8 | B << 16 | E << 24 (decode_rgbe, write_hdr), 0 where no surface is and nothing was
+        filled.  stats=True: the tuple (atlas, covered texels, filled texels, stats dict of the gather)."""
+        d, rects = self._atlas_args(entries, width, height, t_max, pad_base)
+        fmt = _lightmap_format(format)
+        m = self._lightmap_desc(d, max_depth, spp, seed, denoise, dilate, fmt)
+        uv, uv_ptr, n_uv = self._atlas_uv(atlas_uv)
+        out = _lightmap_array(int(height), int(width), fmt)
+        n, filled = ctypes.c_uint32(0), ctypes.c_uint32(0)
+        st = RtRadianceStats()
+        self._check(self.L.rt_bake_atlas_lightmap(self.ctx, ctypes.addressof(m), _ptr(rects), uv_ptr, n_uv,
+                                                  _ptr(out) if out.size else None, out.nbytes, ctypes.addressof(n),
+                                                  ctypes.addressof(filled), ctypes.addressof(st) if stats else None),
+                    "bakeAtlasLightmap")
+        return (out, n.value, filled.value, st.as_dict()) if stats else out
+
+    def bakeLightmap(self, inst, width, height, max_depth, spp, seed=0, t_max=1e30, pad_base=0, atlas_uv=None, denoise=None,
+                     dilate=0, format="f32", stats=False):
+        """bakeAtlasLightmap for one instance over the whole atlas: the entry (inst, 0, 0, width, height), which by identity
+        (A) of the atlas rule is the single-instance bake."""
+        return self.bakeAtlasLightmap([(inst, 0, 0, width, height)], width, height, max_depth, spp, seed, t_max, pad_base,
+                                      atlas_uv, denoise, dilate, format, stats)
+
+    def bakeAtlasLightmapDevice(self, entries, width, height, out_ptr, out_bytes, max_depth, spp, seed=0, t_max=1e30,
+                                pad_base=0, atlas_uv_ptr=None, denoise=None, dilate=0, format="f32", stats=False):
+        """bakeAtlasLightmap into a device array of out_bytes bytes at out_ptr (e.g. tensor.data_ptr(); 16-byte aligned, on
+        the context's device, at least width * height * {16, 8, 4} bytes), with the override UVs at atlas_uv_ptr or None.
+        NOT enqueue-only: the call reads the point count once.  Returns (covered texels, filled texels), with stats=True
+        (covered, filled, stats dict); both cost a fence at the end, which the C entry spares a caller who passes NULL."""
+        d, rects = self._atlas_args(entries, width, height, t_max, pad_base)
+        m = self._lightmap_desc(d, max_depth, spp, seed, denoise, dilate, _lightmap_format(format))
+        n, filled = ctypes.c_uint32(0), ctypes.c_uint32(0)
+        st = RtRadianceStats()
+        self._check(self.L.rt_bake_atlas_lightmap_device(self.ctx, ctypes.addressof(m), _ptr(rects),
+                                                         ctypes.c_void_p(atlas_uv_ptr or 0), ctypes.c_void_p(out_ptr or 0),
+                                                         int(out_bytes), ctypes.addressof(n), ctypes.addressof(filled),
+                                                         ctypes.addressof(st) if stats else None), "bakeAtlasLightmapDevice")
+        return (n.value, filled.value, st.as_dict()) if stats else (n.value, filled.value)
+
+    def encodeAtlas(self, atlas, format):
+        """atlas: an (H, W, 4) float32 array (or an (H, W) IRRADIANCE_DTYPE one) -> a NEW array in the texel format "f32",
+        "f16" or "rgbe", shaped as bakeAtlasLightmap returns it; by the encoding rule of include/mi355rt.h.  No scene is
+        needed."""
+        a = np.ascontiguousarray(atlas)
+        if a.dtype == IRRADIANCE_DTYPE and a.ndim == 2:
+            height, width = a.shape
+        else:
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            if a.ndim != 3 or a.shape[2] != 4:
+                raise ValueError("encodeAtlas expects an (H, W, 4) float32 array")
+            height, width = a.shape[:2]
+        fmt = _lightmap_format(format)
+        out = _lightmap_array(height, width, fmt)
+        self._check(self.L.rt_encode_atlas(self.ctx, width, height, fmt, _ptr(a) if a.size else None,
+                                           _ptr(out) if out.size else None, out.nbytes), "encodeAtlas")
+        return out
+
+    def encodeAtlasDevice(self, in_ptr, width, height, format, out_ptr, out_bytes):
+        """Enqueue the encode of the width x height atlas of 16-byte texels at in_ptr into the out_bytes bytes at out_ptr
+        (another array) on the context's stream; no host synchronisation.  Both pointers must be 16-byte aligned and lie on
+        the context's device."""
+        self._check(self.L.rt_encode_atlas_device(self.ctx, int(width), int(height), _lightmap_format(format),
+                                                  ctypes.c_void_p(in_ptr or 0), ctypes.c_void_p(out_ptr or 0), int(out_bytes)),
+                    "encodeAtlasDevice")
 
     # ---- the sharded image (rt_dist_*): this context as one rank of `world` ----
     def distInit(self, rank, world, stripe_rows=8, unique_id=None):
