@@ -467,6 +467,60 @@ int rt_gather_probes_device(rt_ctx* ctx, const void* dev_probes, uint32_t n, uin
                             void* dev_out);
 int rt_probe_gather_stats(rt_ctx* ctx, rt_radiance_stats* out);
 
+/* ---- directional gathers: "which radiance arrives at this surface point, from which side?" as four spherical-harmonic
+ * coefficients per colour over the hemisphere of the normal (directional lightmaps for normal-mapped surfaces) ----
+ * An irradiance gather returns one colour per point, the cosine-weighted mean at the interpolated normal; a renderer that
+ * perturbs that normal with a normal map needs the radiance as a function of direction.  Here the work item is again a
+ * surface point (rt_gather_point, unchanged) and the result (rt_directional) is the projection of the radiance over the
+ * hemisphere above it onto the real spherical harmonics of bands 0 .. 1, in world space.  It is the probe gather's
+ * composition at surface points: k_dir_rays (one rt_ray per (point, sample)) -> the radiance query's kernel on those rays
+ * at spp = 1 -> k_dir_project (one wave per point; csrc/k_directional.hip.h).  A lane of the irradiance gather keeps its
+ * point for all spp samples, and twelve accumulators do not fit beside its path state.
+ *
+ * THE DIRECTIONAL RULE.  All arithmetic is f32, unfused, in the order written, with the rt_* functions of mi355rt_math.h.
+ * For point i and sample s in 0 .. spp-1, with f = seed * spp + s in u32 arithmetic:
+ *   direction  d0 = the probe rule's direction for (pad, f): uniform on the sphere, from rng_d = init_rng(pad ^ 0x80000000,
+ *              f).  With N the point's normal as given (not normalised): c = (d0.x * N.x + d0.y * N.y) + d0.z * N.z;  d = (c <
+ *              0.0f) ? (-d0.x, -d0.y, -d0.z) : d0 as a float comparison (a NaN does not flip).  Uniform on the hemisphere of
+ *              N; not normalised again.
+ *   sample     {r, g, b, t}: exactly what rt_trace_radiance returns for the ray {position, t_max, d, pad} with spp = 1 and
+ *              seed = f.  It is a hit iff t < t_max (false for NaN).  Keep pad < 2^31, as for a gather.
+ *   basis      bands 0 and 1 of the probe rule: for d = (x, y, z): Y0 = 0.282094792f; Y1 = 0.488602512f * y; Y2 =
+ *              0.488602512f * z; Y3 = 0.488602512f * x.  The term of (k, c) is radiance[c] * Yk.
+ *   sum        the probe rule's fixed tree, for each of the 12 sums and for the hit count: the partial P[l], l = 0 .. 63, is
+ *              ((+0 + term(l)) + term(l + 64)) + ... over the samples s = l (mod 64), ascending; then for m = 32, 16, 8, 4, 2,
+ *              1, in all l at once, P[l] = P[l] + P[l ^ m] (own value first); the sum is P[0].
+ *   result     layer[k][c] = rt_div(sum, (float)spp) * RT_TWO_PI, the Monte-Carlo estimate of the integral of L(w) Yk(w)
+ *              over the hemisphere, c = 0 .. 2;  layer[k][3] = rt_div((float)hits, (float)spp) for all four k.  max_depth ==
+ *              0: every first segment is still traced, and the twelve coefficients come out +0.
+ * Every row layer[k] has the shape of an rt_irradiance - a 16-byte texel whose fourth word >= 0 says "covered" - so that
+ * scattering a result into four atlas layers is four plain copies and the filter, the gutter fill and the encode read each
+ * layer as the texel they know.  The irradiance at a unit normal n follows by the cosine-lobe convolution of bands 0 .. 1:
+ * E(n) = pi * Y0 * c0 + (2 pi / 3) * 0.488602512 * (c1 n.y + c2 n.z + c3 n.x), a host (or shader) one-liner.
+ * A result depends on (scene, point, pad, seed, spp, max_depth) only - never on n, the point's position in the array or how
+ * the library splits the work: a call is cut into batches of whole points of at most RT_DIRECTIONAL_BATCH_SAMPLES samples,
+ * whose rays and radiances live in the scratch the probe gather uses too (per-call scratch on the one stream).
+ * The stats are an rt_radiance_stats as for a probe gather: rays = n points, samples = n * spp; the counters and workgroups
+ * are the sums over the radiance launches, and kernel_ms is the summed time of the RADIANCE launches only.
+ * A directional gather leaves the renderer as it was and has a state of its own: the stats and staging of radiance queries,
+ * irradiance gathers and probe gathers are untouched.
+ *   rt_gather_directional         blocking: copies n points in, gathers, copies n results out.  stats != NULL runs the
+ *                                 counting kernel and fills *stats.  n == 0 is RT_OK; n >= 2^31, a NULL pointer, spp == 0 or
+ *                                 spp > 65536 is RT_ERR_INVALID; without a valid scene RT_ERR_NOT_READY; light_count above the
+ *                                 uploaded lights buffer is RT_ERR_INVALID.  Messages begin with "directional gather:".
+ *   rt_gather_directional_device  the same on device-accessible arrays (n rt_gather_point in, n rt_directional out; 16-byte
+ *                                 aligned, on the context's device): only enqueues on the context's stream.  Counts while
+ *                                 rt_set_counting(ctx, 1) is on.
+ *   rt_directional_gather_stats   stats of the last directional gather (blocking: fences the stream).
+ * Not built: band 2 (five more layers per atlas), tangent-space bases (the coefficients are world-space; band 1 rotates as
+ * the vector (layer[3], layer[1], layer[2])). */
+#define RT_DIRECTIONAL_BATCH_SAMPLES (1u << 22)
+int rt_gather_directional(rt_ctx* ctx, const rt_gather_point* points, uint32_t n, uint32_t max_depth, uint32_t spp,
+                          uint32_t seed, rt_directional* out, rt_radiance_stats* stats);
+int rt_gather_directional_device(rt_ctx* ctx, const void* dev_points, uint32_t n, uint32_t max_depth, uint32_t spp,
+                                 uint32_t seed, void* dev_out);
+int rt_directional_gather_stats(rt_ctx* ctx, rt_radiance_stats* out);
+
 /* ---- lightmap bakes: "the gather points of this instance's atlas", rasterised on the device ----
  * An irradiance gather wants surface points; a lightmap wants one per covered texel of an instance's UV atlas.  The scene
  * holds what that takes on the device (uv, pos, nrm, topology, the instances' forward transforms, the draw commands with
@@ -726,6 +780,40 @@ int rt_encode_atlas(rt_ctx* ctx, uint32_t width, uint32_t height, uint32_t forma
                     size_t out_bytes);
 int rt_encode_atlas_device(rt_ctx* ctx, uint32_t width, uint32_t height, uint32_t format, const void* dev_in, void* dev_out,
                            size_t out_bytes);
+
+/* ---- directional lightmaps: "the four SH layers of these instances' lightmap", the atlas bake and the finished lightmap
+ * around the directional gather ----
+ * Both entries are identities, like their flat siblings; there is no new arithmetic.  The atlas has four LAYERS of W * H
+ * texels of 16 bytes, layer-major: layer k holds {sh[k].r, sh[k].g, sh[k].b, hit_fraction}, an rt_irradiance in shape.
+ *   rt_bake_atlas_directional           desc, entries, atlas_uv as for rt_bake_atlas_irradiance; blocking, on host arrays.
+ *                                       The atlas point pass, one host read of the count, ONE directional gather on the
+ *                                       points in HBM, one scatter (k_dir_scatter).  layers_out is 4 * W * H rt_irradiance:
+ *                                       layers_out[k * W * H + texels[j]] is, bit for bit, rt_gather_directional(points[j])
+ *                                       .layer[k], and every uncovered texel of every layer is {+0, +0, +0, -1.0f}.
+ *                                       *n_covered_out (may be NULL) = n.  The stats (may be NULL) are the directional
+ *                                       gather's, and rt_directional_gather_stats reports this gather afterwards.  Limits
+ *                                       and messages are an atlas bake's and a directional gather's, behind the prefix "bake
+ *                                       directional:".
+ *   rt_bake_atlas_directional_lightmap  rt_lightmap_desc unchanged; blocking, host arrays.  For each layer k the encoded
+ *                                       layer is word for word the composition of (1) layer k of rt_bake_atlas_directional;
+ *                                       (2) unless passes == 0, rt_denoise_atlas of it with the points and texels of
+ *                                       rt_bake_atlas_points - the filter's weights come from the guides alone, so filtering
+ *                                       each layer is filtering the SH vector; (3) unless dilate_radius == 0, rt_dilate_atlas
+ *                                       of the result; (4) rt_encode_atlas in `format`.  Layer k is written at out + k * W * H
+ *                                       * texel bytes; out_bytes below four layers is RT_ERR_INVALID.  RT_LIGHTMAP_RGBE8 is
+ *                                       RT_ERR_INVALID: band-1 coefficients are signed and the shared-exponent rule zeroes
+ *                                       negatives.  *n_filled_out is layer 0's count; all four are equal, the fourth word
+ *                                       being the same in every layer before and after the filter.  One point pass, one read
+ *                                       of the count, one copy back; every atlas-sized array is sized before the first
+ *                                       launch.  Messages begin with "directional lightmap:".
+ * Not built: _device forms of the two bakes (chain rt_bake_atlas_points_device and rt_gather_directional_device), band 2,
+ * tangent-space bases, an RGBE-style signed encoding. */
+int rt_bake_atlas_directional(rt_ctx* ctx, const rt_bake_atlas_desc* desc, const rt_bake_rect* entries, const float* atlas_uv,
+                              uint32_t n_uv_vertices, uint32_t max_depth, uint32_t spp, uint32_t seed, rt_irradiance* layers_out,
+                              uint32_t* n_covered_out, rt_radiance_stats* stats);
+int rt_bake_atlas_directional_lightmap(rt_ctx* ctx, const rt_lightmap_desc* desc, const rt_bake_rect* entries,
+                                       const float* atlas_uv, uint32_t n_uv_vertices, void* out, size_t out_bytes,
+                                       uint32_t* n_covered_out, uint32_t* n_filled_out, rt_radiance_stats* stats);
 
 /* ---- the sharded image: one picture rendered by `world` contexts ("ranks"), assembled on rank 0 ----
  * Rank k owns the image rows y with (y / stripe_rows) % world == k and traces only those (rt_set_stripes).  Its COMPACT

@@ -168,6 +168,11 @@ typedef struct rt_probe_sh9 { /* 112 B: seven 16-byte vector stores of k_probe_p
   float hit_fraction;         /* samples whose first segment hit something / spp */
 } rt_probe_sh9;
 
+/* ---- directional gathers (rt_gather_directional, mi355rt.h): rt_gather_point in; their stats are an rt_radiance_stats ---- */
+typedef struct rt_directional {   /* 64 B: four 16-byte vector stores of k_dir_project */
+  float layer[4][4];              /* layer[k] = {sh[k].r, sh[k].g, sh[k].b, hit_fraction}: row k is the texel of atlas layer k */
+} rt_directional;
+
 /* ---- lightmap bakes (rt_bake_points, mi355rt.h): which atlas of which instance ---- */
 typedef struct rt_bake_desc { /* 32 B */
   uint32_t inst;              /* TLAS-order instance index */
@@ -247,6 +252,9 @@ static_assert(__builtin_offsetof(rt_probe, t_max) == 12 && __builtin_offsetof(rt
               "rt_probe has the slots of rt_ray");
 static_assert(sizeof(rt_probe_sh9) == 112, "rt_probe_sh9 is 112 bytes");
 static_assert(__builtin_offsetof(rt_probe_sh9, hit_fraction) == 108, "hit_fraction is the twenty-eighth word");
+static_assert(sizeof(rt_directional) == 64, "rt_directional is 64 bytes");
+static_assert(__builtin_offsetof(rt_directional, layer[1]) == 16 && __builtin_offsetof(rt_directional, layer[3][3]) == 60,
+              "rt_directional: a row is a 16-byte texel, the hit fraction its fourth word");
 static_assert(sizeof(rt_gather_point) == 32, "rt_gather_point is 32 bytes");
 static_assert(__builtin_offsetof(rt_gather_point, t_max) == 12 && __builtin_offsetof(rt_gather_point, normal) == 16 &&
                   __builtin_offsetof(rt_gather_point, pad) == 28,

@@ -23,6 +23,9 @@
 //                             points (rt_gather_irradiance)
 //   k_probe.hip.h             k_probe_rays / k_probe_project: uniform-sphere rays per (probe, sample) in front of
 //                             k_radiance_query and the SH9 projection behind it (rt_gather_probes)
+//   k_directional.hip.h       k_dir_rays / k_dir_project: the same around k_radiance_query at surface points, directions on the
+//                             hemisphere of the normal, bands 0 .. 1 (rt_gather_directional), and k_dir_scatter: the results
+//                             into the four layers of an atlas (rt_bake_atlas_directional)
 //   k_bake.hip.h              k_bake_owner / _count / _scan / _emit: the UV-space rasteriser that makes such points from the
 //                             texels of an instance's atlas (rt_bake_points), and k_bake_scatter, the way back
 //   k_dilate.hip.h            k_dilate_mask / _source / _apply: the nearest-texel gutter fill of a baked atlas on a coverage
@@ -61,6 +64,7 @@
 #include "k_radiance.hip.h"
 #include "k_gather.hip.h"
 #include "k_probe.hip.h"
+#include "k_directional.hip.h"
 #include "k_bake.hip.h"
 #include "k_dilate.hip.h"
 #include "k_denoise.hip.h"

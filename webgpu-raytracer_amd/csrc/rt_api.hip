@@ -55,8 +55,9 @@ struct PreparedKernel {
   int per_cu;
 };
 
-// What one kind of query (rt_trace_rays, rt_trace_radiance, rt_gather_irradiance, rt_gather_probes) keeps between calls: the staging arrays of
-// its host entry, its own counter shards with the chunk counter behind them, and the events around its last launch.
+// What one kind of query (rt_trace_rays, rt_trace_radiance, rt_gather_irradiance, rt_gather_probes, rt_gather_directional) keeps
+// between calls: the staging arrays of its host entry, its own counter shards with the chunk counter behind them, and the
+// events around its last launch.
 struct QueryState {
   DeviceBuffer in, out, counters;
   hipEvent_t ev[2] = {nullptr, nullptr};
@@ -248,6 +249,16 @@ struct rt_ctx {
   DeviceBuffer pr_rays, pr_rad;
   std::vector<hipEvent_t> pr_ev;    // 2 per batch
   uint32_t pr_timed = 0;            // batches of the last call that recorded their events
+  // directional gathers (rt_gather_directional): the same composition at surface points, a path-query kind and a state of
+  // its own (staging, counter shards, an event pair per radiance launch); the scratch of a batch is the probe gather's,
+  // pr_rays / pr_rad, both being per-call scratch on the one stream
+  QueryState dg;
+  rt_radiance_stats dg_last = {};
+  std::vector<hipEvent_t> dg_ev;    // 2 per batch
+  uint32_t dg_timed = 0;
+  // directional bakes (rt_bake_atlas_directional, _lightmap): the gather's results, the four scattered layers and the four
+  // encoded layers, kept and grown
+  DeviceBuffer db_results, db_layers, db_encoded;
   BakeState bk;
   DilateState dl;
   DenoiseState dn;
@@ -777,9 +788,9 @@ uint32_t grid_blocks(const rt_ctx* c, int per_cu, int cap_per_cu, uint64_t usefu
   return blocks ? (uint32_t)blocks : 1u;
 }
 
-// ---- queries against the uploaded scene (rt_trace_rays, rt_trace_radiance, rt_gather_irradiance, rt_gather_probes): what the
-// kinds share.  `what` is the prefix of the kind's messages, "ray query", "radiance query", "irradiance gather" or "probe
-// gather"; q its QueryState.
+// ---- queries against the uploaded scene (rt_trace_rays, rt_trace_radiance, rt_gather_irradiance, rt_gather_probes,
+// rt_gather_directional): what the kinds share.  `what` is the prefix of the kind's messages, "ray query", "radiance query",
+// "irradiance gather", "probe gather" or "directional gather"; q its QueryState.
 //
 // The scene is there and its derived records are made (prepare_scene, as a compute() would); lights: the kind samples the
 // lights.  Touches nothing of the renderer's frame state.
@@ -983,6 +994,7 @@ void rt_destroy(rt_ctx* c) {
                          &c->rq.in, &c->rq.out, &c->rq.counters, &c->rd.in, &c->rd.out, &c->rd.counters,
                          &c->gi.in, &c->gi.out, &c->gi.counters,
                          &c->pr.in, &c->pr.out, &c->pr.counters, &c->pr_rays, &c->pr_rad,
+                         &c->dg.in, &c->dg.out, &c->dg.counters, &c->db_results, &c->db_layers, &c->db_encoded,
                          &c->bk.uv, &c->bk.owner, &c->bk.blocks, &c->bk.count, &c->bk.points, &c->bk.texels, &c->bk.results,
                          &c->bk.atlas, &c->bk.entries, &c->bk.items, &c->bk.owner64,
                          &c->dl.atlas, &c->dl.filled, &c->dl.bitmap, &c->dl.src,
@@ -1000,6 +1012,8 @@ void rt_destroy(rt_ctx* c) {
     for (hipEvent_t e : q->ev)
       if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->pr_ev)   // (c->pr.ev only borrows these)
+    if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : c->dg_ev)   // (c->dg.ev likewise)
     if (e) (void)hipEventDestroy(e);
   if (c->world.ev0) (void)hipEventDestroy(c->world.ev0);
   if (c->world.ev1) (void)hipEventDestroy(c->world.ev1);
@@ -2150,6 +2164,9 @@ static const PathQueryKind pq_gather = {"irradiance gather", "points", RT_PQ_FNS
 // probe gathers trace with the radiance query's kernel, on a state of their own
 static const PathQueryKind pq_probe = {"probe gather", "probes", RT_PQ_FNS(k_radiance_query), &rt_ctx::pr, &rt_ctx::pr_last,
                                        sizeof(rt_probe_sh9)};
+// ... and so do directional gathers
+static const PathQueryKind pq_directional = {"directional gather", "points", RT_PQ_FNS(k_radiance_query), &rt_ctx::dg,
+                                             &rt_ctx::dg_last, sizeof(rt_directional)};
 #undef RT_PQ_FNS
 
 // Enqueue one query on the context's stream: n > 0 items at d_items, results to d_out (device pointers).  keep_counts: a
@@ -2271,102 +2288,145 @@ int rt_gather_irradiance(rt_ctx* c, const rt_gather_point* points, uint32_t n, u
 // ---- probe gathers: SH9 radiance per probe (mi355rt.h "probe gathers"), by composition around the radiance query's kernel:
 // per batch of whole probes k_probe_rays -> k_radiance_query (spp = 1, seed = 0 on the pad' rays) -> k_probe_project
 // (k_probe.hip.h).  Every (probe, sample) is an item of its own, so the cut into batches cannot show in a result.
-static int launch_probe_gather(rt_ctx* c, const void* d_probes, uint32_t n, uint32_t max_depth, uint32_t spp, uint32_t seed,
-                               void* d_out, bool detail) {
-  const PathQueryKind& k = pq_probe;
+// Directional gathers (mi355rt.h "directional gathers") are the same composition at surface points, with k_dir_rays and
+// k_dir_project (k_directional.hip.h).  What a composed gather has of its own:
+struct ComposedGather {
+  const PathQueryKind& kind;                 // of its radiance launches: the state, the last stats
+  std::vector<hipEvent_t> rt_ctx::*ev;       // 2 per batch
+  uint32_t rt_ctx::*timed;                   // batches of the last call that recorded their events
+  const void* rays_fn;                       // (items, rays, n_items, spp, seed), one thread per (item, sample)
+  const void* project_fn;                    // (items, radiance, out, n, spp, seed), one wave per item
+  uint32_t out_vec4;                         // float4 per result
+};
+static const ComposedGather cg_probe = {pq_probe, &rt_ctx::pr_ev, &rt_ctx::pr_timed, (const void*)rtk::k_probe_rays,
+                                        (const void*)rtk::k_probe_project, sizeof(rt_probe_sh9) / 16};
+static const ComposedGather cg_directional = {pq_directional, &rt_ctx::dg_ev, &rt_ctx::dg_timed, (const void*)rtk::k_dir_rays,
+                                              (const void*)rtk::k_dir_project, sizeof(rt_directional) / 16};
+static_assert(RT_DIRECTIONAL_BATCH_SAMPLES == RT_PROBE_BATCH_SAMPLES, "the two composed gathers share the scratch of a batch");
+
+static int launch_composed_gather(rt_ctx* c, const ComposedGather& g, const void* d_items, uint32_t n, uint32_t max_depth,
+                                  uint32_t spp, uint32_t seed, void* d_out, bool detail) {
+  const PathQueryKind& k = g.kind;
   int r = query_scene_ready(c, k.what, true);
   if (r < 0) return r;
-  const uint32_t per_batch = RT_PROBE_BATCH_SAMPLES / spp;   // whole probes: >= 64, spp being <= 65536
+  const uint32_t per_batch = RT_PROBE_BATCH_SAMPLES / spp;   // whole items: >= 64, spp being <= 65536
   const size_t scratch_items = (size_t)std::min(n, per_batch) * spp;
   if ((r = ensure_buffer(c, c->pr_rays, scratch_items * sizeof(rt_ray), false)) < 0) return r;
   if ((r = ensure_buffer(c, c->pr_rad, scratch_items * sizeof(rt_radiance), false)) < 0) return r;
-  QueryState& q = c->pr;
-  c->pr_timed = 0;
+  QueryState& q = c->*k.state;
+  std::vector<hipEvent_t>& ev = c->*g.ev;
+  rt_radiance_stats& last = c->*k.last;
+  c->*g.timed = 0;
   rt_radiance_stats total = rt_radiance_stats();
   uint32_t batch = 0;
   for (uint32_t first = 0; first < n; first += per_batch, batch++) {
     const uint32_t np = std::min(per_batch, n - first);
     const uint32_t items = np * spp;                         // <= RT_PROBE_BATCH_SAMPLES
-    const float4* probes = (const float4*)d_probes + 2 * (size_t)first;
+    const float4* src = (const float4*)d_items + 2 * (size_t)first;
     float4* rays = (float4*)c->pr_rays.ptr;
     float4* rad = (float4*)c->pr_rad.ptr;
-    float4* out = (float4*)d_out + 7 * (size_t)first;
+    float4* out = (float4*)d_out + g.out_vec4 * (size_t)first;
     {
       uint32_t a_items = items, a_spp = spp, a_seed = seed;
-      void* args[] = {&probes, &rays, &a_items, &a_spp, &a_seed};
-      HIP_TRY(c, hipLaunchKernel((const void*)rtk::k_probe_rays, dim3((items + 255u) / 256u), dim3(256), args, 0, c->stream));
+      void* args[] = {&src, &rays, &a_items, &a_spp, &a_seed};
+      HIP_TRY(c, hipLaunchKernel(g.rays_fn, dim3((items + 255u) / 256u), dim3(256), args, 0, c->stream));
     }
     // the radiance launch between this batch's own event pair
-    if (c->pr_ev.size() < 2 * ((size_t)batch + 1)) c->pr_ev.resize(2 * ((size_t)batch + 1), nullptr);
-    q.ev[0] = c->pr_ev[2 * (size_t)batch];
-    q.ev[1] = c->pr_ev[2 * (size_t)batch + 1];
+    if (ev.size() < 2 * ((size_t)batch + 1)) ev.resize(2 * ((size_t)batch + 1), nullptr);
+    q.ev[0] = ev[2 * (size_t)batch];
+    q.ev[1] = ev[2 * (size_t)batch + 1];
     r = launch_path_query(c, k, rays, items, max_depth, 1u, 0u, rad, detail, batch != 0);
-    c->pr_ev[2 * (size_t)batch] = q.ev[0];
-    c->pr_ev[2 * (size_t)batch + 1] = q.ev[1];
+    ev[2 * (size_t)batch] = q.ev[0];
+    ev[2 * (size_t)batch + 1] = q.ev[1];
     const bool timed = q.timed;
     q.ev[0] = q.ev[1] = nullptr;
     q.timed = false;
     if (r < 0) {
-      c->pr_last = rt_radiance_stats();
+      last = rt_radiance_stats();
       return r;
     }
-    if (timed) c->pr_timed = batch + 1;
-    total.lds = c->pr_last.lds;
-    total.workgroups += c->pr_last.workgroups;
+    if (timed) c->*g.timed = batch + 1;
+    total.lds = last.lds;
+    total.workgroups += last.workgroups;
     {
       uint32_t a_np = np, a_spp = spp, a_seed = seed;
       const float4* rad_in = rad;
-      void* args[] = {&probes, &rad_in, &out, &a_np, &a_spp, &a_seed};
-      HIP_TRY(c, hipLaunchKernel((const void*)rtk::k_probe_project, dim3((np + 3u) / 4u), dim3(256), args, 0, c->stream));
+      void* args[] = {&src, &rad_in, &out, &a_np, &a_spp, &a_seed};
+      HIP_TRY(c, hipLaunchKernel(g.project_fn, dim3((np + 3u) / 4u), dim3(256), args, 0, c->stream));
     }
   }
   total.rays = n;
   total.samples = (uint64_t)n * spp;
-  c->pr_last = total;
+  last = total;
   return RT_OK;
 }
 
-int rt_probe_gather_stats(rt_ctx* c, rt_radiance_stats* out) {
+static int composed_gather_stats(rt_ctx* c, const ComposedGather& g, rt_radiance_stats* out) {
   if (!c || !out) return RT_ERR_INVALID;
-  const int r = path_query_stats(c, pq_probe, out);   // fences the stream; the state itself carries no events
+  const int r = path_query_stats(c, g.kind, out);   // fences the stream; the state itself carries no events
   if (r < 0) return r;
-  for (uint32_t b = 0; b < c->pr_timed; b++) {
+  const std::vector<hipEvent_t>& ev = c->*g.ev;
+  for (uint32_t b = 0; b < c->*g.timed; b++) {
     float ms = 0.0f;
-    HIP_TRY(c, hipEventElapsedTime(&ms, c->pr_ev[2 * (size_t)b], c->pr_ev[2 * (size_t)b + 1]));
+    HIP_TRY(c, hipEventElapsedTime(&ms, ev[2 * (size_t)b], ev[2 * (size_t)b + 1]));
     out->kernel_ms += (double)ms;
   }
   return RT_OK;
 }
-int rt_gather_probes_device(rt_ctx* c, const void* dev_probes, uint32_t n, uint32_t max_depth, uint32_t spp, uint32_t seed,
-                            void* dev_out) {
+// detail: run the counting kernel; < 0: as rt_set_counting says
+static int composed_gather_device(rt_ctx* c, const ComposedGather& g, const void* dev_items, uint32_t n, uint32_t max_depth,
+                                  uint32_t spp, uint32_t seed, void* dev_out, int detail = -1) {
   if (!c) return RT_ERR_INVALID;
-  int r = path_query_args_ok(c, pq_probe, n, spp);
+  int r = path_query_args_ok(c, g.kind, n, spp);
   if (r < 0) return r;
   if (n == 0) {
-    c->pr_last = rt_radiance_stats();
-    c->pr_timed = 0;
+    c->*g.kind.last = rt_radiance_stats();
+    c->*g.timed = 0;
     return RT_OK;
   }
-  if ((r = query_device_arrays_ok(c, pq_probe.what, dev_probes, dev_out)) < 0) return r;
-  return launch_probe_gather(c, dev_probes, n, max_depth, spp, seed, dev_out, c->detailed_counters);
+  if ((r = query_device_arrays_ok(c, g.kind.what, dev_items, dev_out)) < 0) return r;
+  return launch_composed_gather(c, g, dev_items, n, max_depth, spp, seed, dev_out,
+                                detail < 0 ? c->detailed_counters : detail != 0);
+}
+// items: rt_probe or rt_gather_point, the same 32 bytes
+static int composed_gather_host(rt_ctx* c, const ComposedGather& g, const void* items, uint32_t n, uint32_t max_depth,
+                                uint32_t spp, uint32_t seed, void* out, rt_radiance_stats* stats) {
+  if (!c) return RT_ERR_INVALID;
+  int r = path_query_args_ok(c, g.kind, n, spp);
+  if (r < 0) return r;
+  if (n == 0) {
+    c->*g.kind.last = rt_radiance_stats();
+    c->*g.timed = 0;
+    if (stats) *stats = c->*g.kind.last;
+    return RT_OK;
+  }
+  r = query_from_host(c, c->*g.kind.state, g.kind.what, (const rt_ray*)items, n, out, g.kind.out_stride,
+                      [&](const void* d_items, void* d_out) {
+    return launch_composed_gather(c, g, d_items, n, max_depth, spp, seed, d_out, stats != nullptr);
+  });
+  if (r < 0) return r;
+  if (stats) return composed_gather_stats(c, g, stats);
+  return RT_OK;
+}
+
+int rt_probe_gather_stats(rt_ctx* c, rt_radiance_stats* out) { return composed_gather_stats(c, cg_probe, out); }
+int rt_gather_probes_device(rt_ctx* c, const void* dev_probes, uint32_t n, uint32_t max_depth, uint32_t spp, uint32_t seed,
+                            void* dev_out) {
+  return composed_gather_device(c, cg_probe, dev_probes, n, max_depth, spp, seed, dev_out);
 }
 int rt_gather_probes(rt_ctx* c, const rt_probe* probes, uint32_t n, uint32_t max_depth, uint32_t spp, uint32_t seed,
                      rt_probe_sh9* out, rt_radiance_stats* stats) {
-  if (!c) return RT_ERR_INVALID;
-  int r = path_query_args_ok(c, pq_probe, n, spp);
-  if (r < 0) return r;
-  if (n == 0) {
-    c->pr_last = rt_radiance_stats();
-    c->pr_timed = 0;
-    if (stats) *stats = c->pr_last;
-    return RT_OK;
-  }
-  r = query_from_host(c, c->pr, pq_probe.what, probes, n, out, sizeof(rt_probe_sh9), [&](const void* d_probes, void* d_out) {
-    return launch_probe_gather(c, d_probes, n, max_depth, spp, seed, d_out, stats != nullptr);
-  });
-  if (r < 0) return r;
-  if (stats) return rt_probe_gather_stats(c, stats);
-  return RT_OK;
+  return composed_gather_host(c, cg_probe, probes, n, max_depth, spp, seed, out, stats);
+}
+
+int rt_directional_gather_stats(rt_ctx* c, rt_radiance_stats* out) { return composed_gather_stats(c, cg_directional, out); }
+int rt_gather_directional_device(rt_ctx* c, const void* dev_points, uint32_t n, uint32_t max_depth, uint32_t spp, uint32_t seed,
+                                 void* dev_out) {
+  return composed_gather_device(c, cg_directional, dev_points, n, max_depth, spp, seed, dev_out);
+}
+int rt_gather_directional(rt_ctx* c, const rt_gather_point* points, uint32_t n, uint32_t max_depth, uint32_t spp, uint32_t seed,
+                          rt_directional* out, rt_radiance_stats* stats) {
+  return composed_gather_host(c, cg_directional, points, n, max_depth, spp, seed, out, stats);
 }
 
 // ---- lightmap bakes: the texel rule of mi355rt.h as four launches (k_bake.hip.h), then the gather path and the scatter
@@ -2492,14 +2552,19 @@ static int bake_points_back(rt_ctx* c, uint32_t m, rt_gather_point* points_out, 
 }
 
 // A whole bake (rt_bake_irradiance, rt_bake_atlas_irradiance) behind its front.  First the one host read of the count
-// between the point pass and the gather, and the bake's arrays for *n points and the atlas ...
-static int bake_gather_room(rt_ctx* c, uint32_t texels, uint32_t* n) {
+// between the point pass and the gather, and the bake's arrays for *n points ...
+static int bake_count_room(rt_ctx* c, uint32_t* n) {
   int r;
   *n = 0;
   HIP_TRY(c, hipMemcpyAsync(n, c->bk.count.ptr, 4, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   if ((r = ensure_buffer(c, c->bk.points, (size_t)*n * sizeof(rt_gather_point), true)) < 0) return r;
-  if ((r = ensure_buffer(c, c->bk.texels, (size_t)*n * 4, true)) < 0) return r;
+  return ensure_buffer(c, c->bk.texels, (size_t)*n * 4, true);
+}
+// ... for an irradiance bake also their results and the atlas (a directional bake has arrays of its own, below) ...
+static int bake_gather_room(rt_ctx* c, uint32_t texels, uint32_t* n) {
+  int r;
+  if ((r = bake_count_room(c, n)) < 0) return r;
   if ((r = ensure_buffer(c, c->bk.results, (size_t)*n * sizeof(rt_irradiance), true)) < 0) return r;
   return ensure_buffer(c, c->bk.atlas, (size_t)texels * sizeof(rt_irradiance), true);
 }
@@ -3056,6 +3121,134 @@ int rt_bake_atlas_lightmap_device(rt_ctx* c, const rt_lightmap_desc* d, const rt
     return fail(c, RT_ERR_INVALID, std::string(kLightmap) + ": out_bytes is below width * height texels of the format");
   if ((r = bake_atlas_scene_ready(c, &bake, entries, true)) < 0) return lightmap_refused(c, r);
   return lightmap_bake(c, d, &bake, entries, dev_atlas_uv, nullptr, dev_out, n_covered_out, n_filled_out, stats);
+}
+
+// ---- directional lightmaps: the atlas bake and the finished lightmap around the directional gather (mi355rt.h "directional
+// lightmaps"; k_dir_scatter of k_directional.hip.h).  Four layers of an atlas, layer-major, in db_layers.
+static const char* const kBakeDirectional = "bake directional";
+static const char* const kDirLightmap = "directional lightmap";
+// a refusal of one of the stages, under the entry's name: "bake directional: bake atlas: entry 3: ..."
+static int refused_under(rt_ctx* c, const char* what, int code) { return fail(c, code, std::string(what) + ": " + c->error); }
+// Behind the front of an atlas bake: the one host read of the count, the arrays for *n points, their results and the four
+// layers, the emit launch, the directional gather on the points and the scatter, enqueued; the layers stay in db_layers.
+static int directional_bake(rt_ctx* c, const char* what, uint32_t texels, rtk::BakeAtlasArgs& A, uint32_t max_depth, uint32_t spp,
+                            uint32_t seed, bool detail, uint32_t* n_out) {
+  int r;
+  uint32_t n;
+  if ((r = bake_count_room(c, &n)) < 0) return r;
+  *n_out = n;
+  if ((r = ensure_buffer(c, c->db_results, (size_t)n * sizeof(rt_directional), true)) < 0) return r;
+  if ((r = ensure_buffer(c, c->db_layers, (size_t)texels * 4 * sizeof(rt_irradiance), true)) < 0) return r;
+  if ((r = bake_atlas_emit(c, A, c->bk.points.ptr, c->bk.texels.ptr, n)) < 0) return r;
+  if ((r = composed_gather_device(c, cg_directional, c->bk.points.ptr, n, max_depth, spp, seed, c->db_results.ptr, detail)) < 0)
+    return refused_under(c, what, r);
+  rtk::DirScatterArgs B;
+  B.owner = A.owner;
+  B.texels = (const uint32_t*)c->bk.texels.ptr;
+  B.results = (const float4*)c->db_results.ptr;
+  B.layers = (float4*)c->db_layers.ptr;
+  B.n_texels = texels;
+  B.n = n;
+  hipLaunchKernelGGL(rtk::k_dir_scatter, dim3((texels + 255u) / 256u), dim3(256), 0, c->stream, B);
+  HIP_TRY(c, hipGetLastError());
+  return RT_OK;
+}
+
+int rt_bake_atlas_directional(rt_ctx* c, const rt_bake_atlas_desc* d, const rt_bake_rect* entries, const float* atlas_uv,
+                              uint32_t n_uv_vertices, uint32_t max_depth, uint32_t spp, uint32_t seed, rt_irradiance* layers_out,
+                              uint32_t* n_covered_out, rt_radiance_stats* stats) {
+  if (!c) return RT_ERR_INVALID;
+  int r = bake_atlas_desc_ok(c, d, entries);
+  if (r < 0) return refused_under(c, kBakeDirectional, r);
+  if (!layers_out) return fail(c, RT_ERR_INVALID, std::string(kBakeDirectional) + ": NULL array");
+  const uint32_t texels = d->width * d->height;
+  if ((r = path_query_args_ok(c, pq_directional, texels, spp)) < 0) return refused_under(c, kBakeDirectional, r);
+  if ((r = bake_atlas_scene_ready(c, d, entries, true)) < 0) return refused_under(c, kBakeDirectional, r);
+  const void* d_uv;
+  if ((r = bake_stage_uv(c, kBakeDirectional, atlas_uv, n_uv_vertices, &d_uv)) < 0) return r;
+  if ((r = ensure_buffer(c, c->bk.count, 16, false)) < 0) return r;
+  rtk::BakeAtlasArgs A;
+  if ((r = bake_atlas_front(c, d, entries, d_uv, nullptr, c->bk.count.ptr, A)) < 0) return r;
+  uint32_t n;
+  if ((r = directional_bake(c, kBakeDirectional, texels, A, max_depth, spp, seed, stats != nullptr, &n)) < 0) return r;
+  HIP_TRY(c, hipMemcpyAsync(layers_out, c->db_layers.ptr, (size_t)texels * 4 * sizeof(rt_irradiance), hipMemcpyDeviceToHost,
+                            c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (n_covered_out) *n_covered_out = n;
+  if (stats) return rt_directional_gather_stats(c, stats);
+  return RT_OK;
+}
+
+int rt_bake_atlas_directional_lightmap(rt_ctx* c, const rt_lightmap_desc* d, const rt_bake_rect* entries, const float* atlas_uv,
+                                       uint32_t n_uv_vertices, void* out, size_t out_bytes, uint32_t* n_covered_out,
+                                       uint32_t* n_filled_out, rt_radiance_stats* stats) {
+  if (!c) return RT_ERR_INVALID;
+  const std::string w(kDirLightmap);
+  rt_bake_atlas_desc bake;
+  int r = lightmap_desc_ok(c, d, entries, &bake);
+  if (r < 0) return refused_under(c, kDirLightmap, r);
+  if (d->format == RT_LIGHTMAP_RGBE8)
+    return fail(c, RT_ERR_INVALID, w + ": format must be RT_LIGHTMAP_F32 or _F16 (band-1 coefficients are signed; RGBE8 zeroes negatives)");
+  if (!out) return fail(c, RT_ERR_INVALID, w + ": NULL array");
+  const uint32_t texels = d->width * d->height;
+  const size_t atlas_bytes = (size_t)texels * 16, layer_bytes = (size_t)texels * lightmap_texel_bytes(d->format);
+  if (out_bytes < 4 * layer_bytes)
+    return fail(c, RT_ERR_INVALID, w + ": out_bytes is below four layers of width * height texels of the format");
+  if ((r = bake_atlas_scene_ready(c, &bake, entries, true)) < 0) return refused_under(c, kDirLightmap, r);
+  const void* d_uv;
+  if ((r = bake_stage_uv(c, kDirLightmap, atlas_uv, n_uv_vertices, &d_uv)) < 0) return r;
+  const bool count_filled = n_filled_out && d->dilate_radius;
+  // every atlas-sized array before the first launch, as lightmap_bake does; the point-sized ones follow the read of the count
+  if ((r = ensure_buffer(c, c->bk.count, 16, false)) < 0) return r;
+  if ((r = ensure_buffer(c, c->db_layers, 4 * atlas_bytes, true)) < 0) return r;
+  if ((r = ensure_buffer(c, c->db_encoded, 4 * layer_bytes, true)) < 0) return r;
+  if (d->passes) {
+    if ((r = ensure_buffer(c, c->lm.filtered, atlas_bytes, true)) < 0) return r;
+    if ((r = ensure_buffer(c, c->dn.index, (size_t)texels * 4, true)) < 0) return r;
+    if (d->passes > 1 && (r = ensure_buffer(c, c->dn.scratch, atlas_bytes, true)) < 0) return r;
+  }
+  if (d->dilate_radius) {
+    if ((r = ensure_buffer(c, c->dl.bitmap, (size_t)d->height * ((d->width + 63u) / 64u) * 8, true)) < 0) return r;
+    if ((r = ensure_buffer(c, c->dl.src, (size_t)texels * 4, true)) < 0) return r;
+    if ((r = ensure_buffer(c, c->lm.filled, 16, false)) < 0) return r;
+  }
+  rtk::BakeAtlasArgs A;
+  if ((r = bake_atlas_front(c, &bake, entries, d_uv, nullptr, c->bk.count.ptr, A)) < 0) return r;
+  uint32_t n;
+  if ((r = directional_bake(c, kDirLightmap, texels, A, d->max_depth, d->spp, d->seed, stats != nullptr, &n)) < 0) return r;
+  // filter, gutter and encode layer by layer, with the stages as they stand: the filtered layer is lm.filtered for each in
+  // turn (the stream orders the layers), the gutter fill is in place, the encoded layers lie side by side in db_encoded
+  for (uint32_t k = 0; k < 4u; k++) {
+    void* current = (char*)c->db_layers.ptr + k * atlas_bytes;
+    if (d->passes) {
+      rt_denoise_desc f = {};
+      f.width = d->width;
+      f.height = d->height;
+      f.step = d->step;
+      f.passes = d->passes;
+      f.normal_cos = d->normal_cos;
+      f.plane_eps = d->plane_eps;
+      f.max_dist = d->max_dist;
+      if ((r = launch_denoise(c, &f, current, c->bk.points.ptr, c->bk.texels.ptr, n, c->lm.filtered.ptr)) < 0) return r;
+      current = c->lm.filtered.ptr;
+    }
+    if (d->dilate_radius) {
+      rt_dilate_desc g = {};
+      g.width = d->width;
+      g.height = d->height;
+      g.radius = d->dilate_radius;
+      if ((r = launch_dilate(c, &g, current, nullptr, (count_filled && k == 0) ? c->lm.filled.ptr : nullptr)) < 0) return r;
+    }
+    if ((r = launch_encode(c, texels, d->format, current, (char*)c->db_encoded.ptr + k * layer_bytes)) < 0) return r;
+  }
+  uint32_t filled = 0;
+  HIP_TRY(c, hipMemcpyAsync(out, c->db_encoded.ptr, 4 * layer_bytes, hipMemcpyDeviceToHost, c->stream));
+  if (count_filled) HIP_TRY(c, hipMemcpyAsync(&filled, c->lm.filled.ptr, 4, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (n_covered_out) *n_covered_out = n;
+  if (n_filled_out) *n_filled_out = filled;
+  if (stats) return rt_directional_gather_stats(c, stats);
+  return RT_OK;
 }
 
 static int encode_args_ok(rt_ctx* c, uint32_t width, uint32_t height, uint32_t format, const void* in, const void* out,

@@ -660,6 +660,29 @@ static napi_value rtGatherProbes(napi_env env, napi_callback_info info) {
   return radiance_stats_object(env, &st);
 }
 
+/* ------------------------------------------------------- directional gathers (rt_gather_directional, mi355rt.h) */
+/* (ctx, points: Float32Array of 8 per point {position, t_max, normal, pad}, maxDepth, spp, seed, out: Float32Array of 16 per
+ * point, four rows {sh[k].rgb, hit_fraction}, wantStats) -> status, or the stats object when wantStats and the call succeeded */
+static napi_value rtGatherDirectional(napi_env env, napi_callback_info info) {
+  napi_value a[7];
+  void *points = NULL, *out = NULL;
+  size_t np = 0, no = 0;
+  bool want_stats = false;
+  if (!get_args(env, info, 7, a) || !get_bytes(env, a[1], &points, &np) || !get_bytes(env, a[5], &out, &no)) return NULL;
+  napi_get_value_bool(env, a[6], &want_stats);
+  const size_t n = np / sizeof(rt_gather_point);
+  if (np % sizeof(rt_gather_point) != 0 || no < n * sizeof(rt_directional) || n > 0x7fffffffu) {
+    napi_throw_range_error(env, NULL, "rtGatherDirectional: points must hold 8 floats per point and out 16 floats per point");
+    return NULL;
+  }
+  rt_radiance_stats st;
+  const int rc = rt_gather_directional((rt_ctx*)get_ptr(env, a[0]), (const rt_gather_point*)points, (uint32_t)n,
+                                       get_u32(env, a[2]), get_u32(env, a[3]), get_u32(env, a[4]), (rt_directional*)out,
+                                       want_stats ? &st : NULL);
+  if (rc < 0 || !want_stats) return make_int(env, rc);
+  return radiance_stats_object(env, &st);
+}
+
 /* ------------------------------------------------------- lightmap bakes (rt_bake_points / rt_bake_irradiance, mi355rt.h) */
 static double get_f64(napi_env env, napi_value v) {
   double x = 0.0;
@@ -860,7 +883,7 @@ static napi_value rtDenoiseAtlas(napi_env env, napi_callback_info info) {
 /* (ctx, width, height, padBase, tMax, entries, atlasUv or null, maxDepth, spp, seed, stages: Float64Array {passes, step,
  * normalCos, planeEps, maxDist, dilateRadius, format}, out: a typed array of width * height texels of the format, wantStats)
  * -> {covered, filled, stats?}, or a negative status */
-static napi_value rtBakeAtlasLightmap(napi_env env, napi_callback_info info) {
+static napi_value bake_atlas_lightmap_call(napi_env env, napi_callback_info info, int directional) {
   napi_value a[13];
   void *entries = NULL, *uv = NULL, *stages = NULL, *out = NULL;
   size_t ne = 0, nuv = 0, ns = 0, no = 0;
@@ -895,8 +918,9 @@ static napi_value rtBakeAtlasLightmap(napi_env env, napi_callback_info info) {
   d.format = (uint32_t)s[6];
   rt_radiance_stats st;
   uint32_t n = 0, filled = 0;
-  const int rc = rt_bake_atlas_lightmap((rt_ctx*)get_ptr(env, a[0]), &d, (const rt_bake_rect*)entries, (const float*)uv,
-                                        (uint32_t)(nuv / 8), out, no, &n, &filled, want_stats ? &st : NULL);
+  const int rc = (directional ? rt_bake_atlas_directional_lightmap : rt_bake_atlas_lightmap)(
+      (rt_ctx*)get_ptr(env, a[0]), &d, (const rt_bake_rect*)entries, (const float*)uv, (uint32_t)(nuv / 8), out, no, &n, &filled,
+      want_stats ? &st : NULL);
   if (rc < 0) return make_int(env, rc);
   napi_value obj, v;
   if (napi_create_object(env, &obj) != napi_ok) return NULL;
@@ -906,6 +930,12 @@ static napi_value rtBakeAtlasLightmap(napi_env env, napi_callback_info info) {
   napi_set_named_property(env, obj, "filled", v);
   if (want_stats) napi_set_named_property(env, obj, "stats", radiance_stats_object(env, &st));
   return obj;
+}
+static napi_value rtBakeAtlasLightmap(napi_env env, napi_callback_info info) { return bake_atlas_lightmap_call(env, info, 0); }
+/* directional lightmaps (rt_bake_atlas_directional_lightmap): the same arguments; out holds FOUR layers of width * height texels
+ * of the format, layer-major; filled is the count of one layer */
+static napi_value rtBakeAtlasDirectionalLightmap(napi_env env, napi_callback_info info) {
+  return bake_atlas_lightmap_call(env, info, 1);
 }
 /* (ctx, width, height, format, atlas: Float32Array of 4 per texel (read), out: a typed array of width * height texels of the
  * format) -> 0, or a negative status */
@@ -940,6 +970,7 @@ static napi_value Init(napi_env env, napi_value exports) {
                {"rtGatherStripes", rtGatherStripes}, {"rtReadDisplay", rtReadDisplay}, {"rtTraceRays", rtTraceRays},
                {"rtRayQueryStats", rtRayQueryStats}, {"rtTraceRadiance", rtTraceRadiance},
                {"rtGatherIrradiance", rtGatherIrradiance}, {"rtGatherProbes", rtGatherProbes}, {"rtBakePoints", rtBakePoints},
+               {"rtGatherDirectional", rtGatherDirectional}, {"rtBakeAtlasDirectionalLightmap", rtBakeAtlasDirectionalLightmap},
                {"rtBakeIrradiance", rtBakeIrradiance}, {"rtBakeAtlasPoints", rtBakeAtlasPoints},
                {"rtBakeAtlasIrradiance", rtBakeAtlasIrradiance}, {"rtDilateAtlas", rtDilateAtlas},
                {"rtDenoiseAtlas", rtDenoiseAtlas}, {"rtBakeAtlasLightmap", rtBakeAtlasLightmap},

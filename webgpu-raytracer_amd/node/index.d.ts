@@ -71,6 +71,12 @@ export class WebGPURenderer {
    *  query's with rays = probes; kernel_ms counts the radiance launches only. */
   gatherProbes(probes: Float32Array, maxDepth: number, spp: number, opts?: { seed?: number; stats?: boolean }):
     { data: Float32Array; n: number; stats?: RadianceQueryStats };
+  /** Directional gathers (rt_gather_directional): points as for gatherIrradiance.  `data` holds 16 floats per point, four rows
+   *  {sh[k].r, sh[k].g, sh[k].b, hitFraction}: the projection of the radiance arriving over spp uniform directions on the
+   *  hemisphere of the normal onto Y0 and the y, z, x harmonics of band 1, in world space; row k is the texel of atlas layer k.
+   *  The stats are a radiance query's with rays = points; kernel_ms counts the radiance launches only. */
+  gatherDirectional(points: Float32Array, maxDepth: number, spp: number, opts?: { seed?: number; stats?: boolean }):
+    { data: Float32Array; n: number; stats?: RadianceQueryStats };
   /** Lightmap bakes (rt_bake_points): the covered texels of TLAS-order instance `inst`'s width x height atlas as gather points,
    *  in ascending texel index; pad = padBase + texel index.  atlasUv: 2 floats per scene vertex, overriding the scene's uvs.
    *  owner: the Int32Array owner map (global triangle index, -1 = uncovered). */
@@ -115,6 +121,16 @@ export class WebGPURenderer {
                              denoise?: { planeEps: number; maxDist: number; normalCos?: number; passes?: number; step?: number } | null;
                              dilate?: number; format?: 'f32' | 'f16' | 'rgbe' }):
     { data: Float32Array | Uint16Array | Uint32Array; width: number; height: number; format: 'f32' | 'f16' | 'rgbe';
+      covered: number; filled: number; stats?: RadianceQueryStats };
+  /** The finished directional lightmap in one call (rt_bake_atlas_directional_lightmap): as bakeAtlasLightmap around the
+   *  directional gather.  `data` holds four layers of width * height texels, layer-major; layer k is {sh[k].r, sh[k].g,
+   *  sh[k].b, w}, filtered, gutter-filled and encoded like a flat lightmap.  'rgbe' is refused: band-1 coefficients are signed.
+   *  `filled` is the count of one layer (all four are equal). */
+  bakeAtlasDirectionalLightmap(entries: number[][] | Uint32Array, width: number, height: number, maxDepth: number, spp: number,
+                    opts?: { tMax?: number; padBase?: number; atlasUv?: Float32Array | null; seed?: number; stats?: boolean;
+                             denoise?: { planeEps: number; maxDist: number; normalCos?: number; passes?: number; step?: number } | null;
+                             dilate?: number; format?: 'f32' | 'f16' }):
+    { data: Float32Array | Uint16Array; width: number; height: number; layers: 4; format: 'f32' | 'f16';
       covered: number; filled: number; stats?: RadianceQueryStats };
   /** The encode stage alone (rt_encode_atlas) on any atlas of 4 floats per texel.  `data` is a new array. */
   encodeAtlas(atlas: Float32Array, width: number, height: number, format: 'f32' | 'f16' | 'rgbe'):

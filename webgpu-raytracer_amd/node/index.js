@@ -217,6 +217,21 @@ class WebGPURenderer {
     if (typeof r === 'object' && r) out.stats = r;
     return out;
   }
+  // ---- directional gathers (rt_gather_directional): the radiance arriving at the caller's surface points, over spp directions
+  // drawn uniformly on the hemisphere of the normal on the device, projected onto the four real spherical harmonics of bands 0
+  // .. 1 in world space.  points as for gatherIrradiance.  opts: {seed = 0, stats = false}.  Result: 16 floats per point in
+  // .data, four rows {sh[k].r, sh[k].g, sh[k].b, hitFraction}, k = 0 .. 3 (Y0, then the y, z and x of band 1): row k is the texel
+  // of atlas layer k.  With stats the result also carries .stats.
+  gatherDirectional(points, maxDepth, spp, opts = {}) {
+    if (!(points instanceof Float32Array) || points.length % 8 !== 0) throw new TypeError('gatherDirectional: a Float32Array of 8 floats per point');
+    const n = points.length / 8;
+    const data = new Float32Array(n * 16);
+    const r = native.rtGatherDirectional(this._ctx, points, maxDepth >>> 0, spp >>> 0, (opts.seed || 0) >>> 0, data, !!opts.stats);
+    if (typeof r === 'number') this._check(r, 'gatherDirectional');
+    const out = { data, n };
+    if (typeof r === 'object' && r) out.stats = r;
+    return out;
+  }
   // ---- lightmap bakes (rt_bake_points, rt_bake_irradiance): the covered texels of TLAS-order instance `inst`'s width x height
   // atlas as gather points, by the texel rule of include/mi355rt.h.  opts: {tMax = 1e30, padBase = 0, atlasUv = null (a
   // Float32Array of 2 floats per scene vertex overriding the scene's uvs), owner = false}.  Result: {n, points (8 words per
@@ -325,19 +340,32 @@ class WebGPURenderer {
   static _lightmapArray(texels, f) {
     return f === 1 ? new Uint16Array(texels * 4) : f === 2 ? new Uint32Array(texels) : new Float32Array(texels * 4);
   }
-  bakeAtlasLightmap(entries, width, height, maxDepth, spp, opts = {}) {
+  _bakeLightmap(what, call, layers, entries, width, height, maxDepth, spp, opts) {
     const f = WebGPURenderer._lightmapFormat(opts.format), dn = opts.denoise || null;
-    if (dn && !(dn.planeEps !== undefined && dn.maxDist !== undefined)) throw new TypeError('bakeAtlasLightmap: denoise.planeEps and denoise.maxDist are required');
+    if (dn && !(dn.planeEps !== undefined && dn.maxDist !== undefined)) throw new TypeError(what + ': denoise.planeEps and denoise.maxDist are required');
     const stages = dn ? Float64Array.of(dn.passes === undefined ? 3 : dn.passes, dn.step === undefined ? 1 : dn.step,
       dn.normalCos === undefined ? 0.9 : dn.normalCos, dn.planeEps, dn.maxDist, opts.dilate || 0, f)
       : Float64Array.of(0, 0, 0, 0, 0, opts.dilate || 0, f);
-    const data = WebGPURenderer._lightmapArray(width * height, f);
-    const r = native.rtBakeAtlasLightmap(this._ctx, width >>> 0, height >>> 0, (opts.padBase || 0) >>> 0,
+    const data = WebGPURenderer._lightmapArray(layers * width * height, f);
+    const r = call(this._ctx, width >>> 0, height >>> 0, (opts.padBase || 0) >>> 0,
       opts.tMax === undefined ? 1e30 : opts.tMax, WebGPURenderer._atlasEntries(entries), opts.atlasUv || null, maxDepth >>> 0,
       spp >>> 0, (opts.seed || 0) >>> 0, stages, data, !!opts.stats);
-    if (typeof r === 'number') this._check(r, 'bakeAtlasLightmap');
+    if (typeof r === 'number') this._check(r, what);
     const out = { data, width, height, format: ['f32', 'f16', 'rgbe'][f], covered: r.covered, filled: r.filled };
     if (r.stats) out.stats = r.stats;
+    return out;
+  }
+  bakeAtlasLightmap(entries, width, height, maxDepth, spp, opts = {}) {
+    return this._bakeLightmap('bakeAtlasLightmap', native.rtBakeAtlasLightmap, 1, entries, width, height, maxDepth, spp, opts);
+  }
+  // ---- directional lightmaps (rt_bake_atlas_directional_lightmap): the same call around the directional gather.  Result as
+  // bakeAtlasLightmap's plus layers = 4: data holds four layers of width * height texels, layer-major; layer k is {sh[k].r,
+  // sh[k].g, sh[k].b, w} with the coverage word w of the flat lightmap.  format 'f32' or 'f16'; 'rgbe' is refused (band-1
+  // coefficients are signed).  filled is the count of one layer.
+  bakeAtlasDirectionalLightmap(entries, width, height, maxDepth, spp, opts = {}) {
+    const out = this._bakeLightmap('bakeAtlasDirectionalLightmap', native.rtBakeAtlasDirectionalLightmap, 4, entries, width, height,
+      maxDepth, spp, opts);
+    out.layers = 4;
     return out;
   }
   // The encode stage alone: atlas = 4 floats per texel, e.g. what dilateAtlas returned.  Result: {data, width, height, format}.

@@ -201,6 +201,10 @@ def load_library(path=None):
         "rt_gather_probes": (i32, [vp, vp, u32, u32, u32, u32, vp, vp]),
         "rt_gather_probes_device": (i32, [vp, vp, u32, u32, u32, u32, vp]),
         "rt_probe_gather_stats": (i32, [vp, vp]),
+        # directional gathers
+        "rt_gather_directional": (i32, [vp, vp, u32, u32, u32, u32, vp, vp]),
+        "rt_gather_directional_device": (i32, [vp, vp, u32, u32, u32, u32, vp]),
+        "rt_directional_gather_stats": (i32, [vp, vp]),
         # lightmap bakes
         "rt_bake_points": (i32, [vp, vp, vp, u32, vp, vp, u32, vp, vp]),
         "rt_bake_points_device": (i32, [vp, vp, vp, vp, vp, u32, vp, vp]),
@@ -220,6 +224,9 @@ def load_library(path=None):
         "rt_bake_atlas_lightmap_device": (i32, [vp, vp, vp, vp, vp, ctypes.c_size_t, vp, vp, vp]),
         "rt_encode_atlas": (i32, [vp, u32, u32, u32, vp, vp, ctypes.c_size_t]),
         "rt_encode_atlas_device": (i32, [vp, u32, u32, u32, vp, vp, ctypes.c_size_t]),
+        # directional lightmaps
+        "rt_bake_atlas_directional": (i32, [vp, vp, vp, vp, u32, u32, u32, u32, vp, vp, vp]),
+        "rt_bake_atlas_directional_lightmap": (i32, [vp, vp, vp, vp, u32, vp, ctypes.c_size_t, vp, vp, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(L, name)  # AttributeError here = header/library mismatch
@@ -245,11 +252,13 @@ EXPORTED_SYMBOLS = (
     "rt_trace_radiance rt_trace_radiance_device rt_radiance_query_stats "
     "rt_gather_irradiance rt_gather_irradiance_device rt_irradiance_gather_stats "
     "rt_gather_probes rt_gather_probes_device rt_probe_gather_stats "
+    "rt_gather_directional rt_gather_directional_device rt_directional_gather_stats "
     "rt_bake_points rt_bake_points_device rt_bake_irradiance "
     "rt_bake_atlas_points rt_bake_atlas_points_device rt_bake_atlas_irradiance "
     "rt_dilate_atlas rt_dilate_atlas_device "
     "rt_denoise_atlas rt_denoise_atlas_device "
-    "rt_bake_atlas_lightmap rt_bake_atlas_lightmap_device rt_encode_atlas rt_encode_atlas_device").split()
+    "rt_bake_atlas_lightmap rt_bake_atlas_lightmap_device rt_encode_atlas rt_encode_atlas_device "
+    "rt_bake_atlas_directional rt_bake_atlas_directional_lightmap").split()
 
 
 # ---- ray queries: mirrors of rt_ray / rt_ray_hit / rt_ray_stats (include/mi355rt_layout.h)
@@ -313,6 +322,30 @@ def sh9_irradiance(sh, normals):
     2 pi / 3, pi / 4.  Pure numpy; no ringing filter."""
     c = np.asarray(sh, np.float64) * _SH9_BAND[:, None]
     return np.einsum("mk,...kc->...mc", sh9_basis(normals), c)
+
+
+# directional gathers: mirror of rt_directional; points are rt_gather_point, stats an RtRadianceStats (rays = points)
+DIRECTIONAL_DTYPE = np.dtype([("layer", np.float32, (4, 4))])
+
+
+def sh4_irradiance(layers_or_coeffs, normals):
+    """Irradiance from the band 0 .. 1 radiance coefficients of a directional gather or bake at unit normals, by the cosine-lobe
+    convolution sh9_irradiance uses: E(n) = pi * Y0 * c0 + (2 pi / 3) * 0.488602512 * (c1 n.y + c2 n.z + c3 n.x).
+    layers_or_coeffs: (4, ..., 3 or 4) - four atlas layers as bakeAtlasDirectional returns them (an IRRADIANCE_DTYPE array, or
+    floats whose fourth word, the hit fraction, is ignored) - or a DIRECTIONAL_DTYPE array (...,) as gatherDirectional returns
+    it.  normals: (..., 3), one per texel / point (or broadcastable to that).  Returns (..., 3) float64.  Pure numpy."""
+    a = np.asarray(layers_or_coeffs)
+    if a.dtype == DIRECTIONAL_DTYPE:
+        c = np.moveaxis(a["layer"].astype(np.float64), -2, 0)[..., :3]
+    elif a.dtype == IRRADIANCE_DTYPE:
+        c = a["rgb"].astype(np.float64)
+    else:
+        c = a.astype(np.float64)[..., :3]
+    if c.shape[0] != 4:
+        raise ValueError("sh4_irradiance expects four layers or coefficients first")
+    n = np.asarray(normals, np.float64)
+    band1 = c[1] * n[..., 1:2] + c[2] * n[..., 2:3] + c[3] * n[..., 0:1]
+    return np.pi * 0.282094792 * c[0] + (2.0 * np.pi / 3.0) * 0.488602512 * band1
 
 
 # lightmap bakes: mirror of rt_bake_desc
@@ -746,6 +779,37 @@ class WebGPURenderer:
         self._check(self.L.rt_probe_gather_stats(self.ctx, ctypes.addressof(st)), "probeGatherStats")
         return st.as_dict()
 
+    # ---- directional gathers: SH radiance of bands 0 .. 1 over the hemisphere of surface points (rt_gather_directional) ----
+    def gatherDirectional(self, points, max_depth, spp, seed=0, stats=False):
+        """points: (n, 8) float32 in the rt_gather_point layout {position, t_max, normal, pad}, as for gatherIrradiance.
+        Returns a structured array (n,) with the field layer (4 x 4 floats, DIRECTIONAL_DTYPE): layer[k] = {sh[k].r, sh[k].g,
+        sh[k].b, hit_fraction}, the projection of the radiance arriving at each point, over spp directions drawn uniformly on
+        the hemisphere of its normal on the device, onto the real spherical harmonics Y0, Y1 (y), Y2 (z), Y3 (x) in world
+        space (sh4_irradiance turns them into irradiance at a normal) - and with stats=True the pair (results, stats dict of
+        rt_radiance_stats with rays = points: the counting kernel runs)."""
+        p = np.ascontiguousarray(points, dtype=np.float32)
+        if p.ndim != 2 or p.shape[1] != 8:
+            raise ValueError("gatherDirectional expects an (n, 8) float32 array")
+        n = p.shape[0]
+        out = np.empty(n, dtype=DIRECTIONAL_DTYPE)
+        st = RtRadianceStats()
+        self._check(self.L.rt_gather_directional(self.ctx, _ptr(p), n, int(max_depth), int(spp), int(seed) & 0xffffffff,
+                                                 _ptr(out), ctypes.addressof(st) if stats else None), "gatherDirectional")
+        return (out, st.as_dict()) if stats else out
+
+    def gatherDirectionalDevice(self, points_ptr, n, out_ptr, max_depth, spp, seed=0):
+        """Enqueue a directional gather on device arrays (n rt_gather_point at points_ptr, n rt_directional of 64 bytes to
+        out_ptr; e.g. tensor.data_ptr()) on the context's stream; no host synchronisation."""
+        self._check(self.L.rt_gather_directional_device(self.ctx, ctypes.c_void_p(points_ptr), int(n), int(max_depth), int(spp),
+                                                        int(seed) & 0xffffffff, ctypes.c_void_p(out_ptr)),
+                    "gatherDirectionalDevice")
+
+    def directionalGatherStats(self):
+        """rt_radiance_stats of the last directional gather as a dict (blocking)."""
+        st = RtRadianceStats()
+        self._check(self.L.rt_directional_gather_stats(self.ctx, ctypes.addressof(st)), "directionalGatherStats")
+        return st.as_dict()
+
     # ---- lightmap bakes: the texels of an instance's UV atlas as gather points (rt_bake_points) ----
     @staticmethod
     def _bake_desc(inst, width, height, t_max, pad_base):
@@ -1009,6 +1073,44 @@ class WebGPURenderer:
                                                   ctypes.addressof(filled), ctypes.addressof(st) if stats else None),
                     "bakeAtlasLightmap")
         return (out, n.value, filled.value, st.as_dict()) if stats else out
+
+    # ---- directional lightmaps: four SH layers per atlas (rt_bake_atlas_directional, rt_bake_atlas_directional_lightmap) ----
+    def bakeAtlasDirectional(self, entries, width, height, max_depth, spp, seed=0, t_max=1e30, pad_base=0, atlas_uv=None,
+                             stats=False):
+        """The directional atlas bake: the points of all entries, ONE directional gather on them, scatter.  Returns (layers, n):
+        layers is (4, height, width) IRRADIANCE_DTYPE - layer k of texel texels[j] holds gatherDirectional(points[j]).layer[k],
+        {sh[k].rgb, hit_fraction}; uncovered texels are {0, 0, 0, -1} in all four - and n the number of covered texels; with
+        stats=True the triple (layers, n, stats dict of the gather)."""
+        d, rects = self._atlas_args(entries, width, height, t_max, pad_base)
+        uv, uv_ptr, n_uv = self._atlas_uv(atlas_uv)
+        out = np.empty((4, int(height), int(width)), dtype=IRRADIANCE_DTYPE)
+        n = ctypes.c_uint32(0)
+        st = RtRadianceStats()
+        self._check(self.L.rt_bake_atlas_directional(self.ctx, ctypes.addressof(d), _ptr(rects), uv_ptr, n_uv, int(max_depth),
+                                                     int(spp), int(seed) & 0xffffffff, _ptr(out), ctypes.addressof(n),
+                                                     ctypes.addressof(st) if stats else None), "bakeAtlasDirectional")
+        return (out, n.value, st.as_dict()) if stats else (out, n.value)
+
+    def bakeAtlasDirectionalLightmap(self, entries, width, height, max_depth, spp, seed=0, t_max=1e30, pad_base=0, atlas_uv=None,
+                                     denoise=None, dilate=0, format="f32", stats=False):
+        """The finished directional lightmap in one call: bakeAtlasDirectional, then per layer - denoise: None or a dict of
+        denoiseAtlas's keyword arguments - the filter on the guides the bake holds on the device, then - dilate > 0 - the
+        gutter fill, then the encode; one read of the point count and one copy back.  format "f32" gives (4, height, width)
+        IRRADIANCE_DTYPE, "f16" (4, height, width, 4) float16; "rgbe" is refused (band-1 coefficients are signed).  Returns
+        (layers, covered texels, filled texels of a layer), with stats=True a fourth item, the stats dict of the gather."""
+        d, rects = self._atlas_args(entries, width, height, t_max, pad_base)
+        fmt = _lightmap_format(format)
+        m = self._lightmap_desc(d, max_depth, spp, seed, denoise, dilate, fmt)
+        uv, uv_ptr, n_uv = self._atlas_uv(atlas_uv)
+        out = _lightmap_array(4 * int(height), int(width), fmt)
+        out = out.reshape((4, int(height)) + out.shape[1:])
+        n, filled = ctypes.c_uint32(0), ctypes.c_uint32(0)
+        st = RtRadianceStats()
+        self._check(self.L.rt_bake_atlas_directional_lightmap(self.ctx, ctypes.addressof(m), _ptr(rects), uv_ptr, n_uv,
+                                                              _ptr(out) if out.size else None, out.nbytes, ctypes.addressof(n),
+                                                              ctypes.addressof(filled), ctypes.addressof(st) if stats else None),
+                    "bakeAtlasDirectionalLightmap")
+        return (out, n.value, filled.value, st.as_dict()) if stats else (out, n.value, filled.value)
 
     def bakeLightmap(self, inst, width, height, max_depth, spp, seed=0, t_max=1e30, pad_base=0, atlas_uv=None, denoise=None,
                      dilate=0, format="f32", stats=False):
