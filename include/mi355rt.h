@@ -262,7 +262,9 @@ int rt_debug_read_pairs(rt_ctx* ctx, float* pairs_out, float* root_rec_out, uint
  * diagnostic build, 0 in the product build (where no stamp executes and the array stays zero). */
 int rt_debug_trace_sections(rt_ctx* ctx, uint64_t* out16, int reset);
 /* Diagnostic build (-DRT_PT_STAMPS) only: the same for k_pathtrace_persistent: out8[0..4] = cycles in {regenerate + start,
- * shade, shadow traversal, extension traversal + surface frame, finish}, [5] trips, [6] waves. */
+ * shade, shadow traversal, extension traversal + surface frame, finish}, [5] trips, [6] waves.  The one-leaf forms make the
+ * surface frame of new samples and new hits in one pass between "start" and "shade": its cycles are out8[7], and in neither
+ * [0] nor [3]. */
 int rt_debug_pt_sections(rt_ctx* ctx, uint64_t* out8, int reset);
 /* Shape of the last launch of the persistent path-trace kernel: out4 = {threads per workgroup (256, or 512 for the wide
  * one-leaf form), workgroups, dynamic LDS bytes per workgroup, resident workgroups per CU from the occupancy query}.  All
@@ -270,7 +272,9 @@ int rt_debug_pt_sections(rt_ctx* ctx, uint64_t* out8, int reset);
 int rt_debug_pt_launch(rt_ctx* ctx, uint32_t* out4);
 /* Diagnostic build (-DRT_LANE_STATS) only: lane utilisation of the parts of a trip of k_pathtrace_persistent:
  * out32[2 k] = times part k ran (wave level), out32[2 k + 1] = active lanes summed; k = 0 shade, 1 / 2 node step / triangle
- * chunk of the shadow walk, 3 / 4 of the extension walk, 5 surface frame of a new hit, 6 start of a sample, 7 end of a sample.
+ * chunk of the shadow walk, 3 / 4 of the extension walk, 5 surface frame of a new hit, 6 start of a sample, 7 end of a sample;
+ * in the one-leaf forms 5 only records the hit, 6 makes the camera ray and loads the G-buffer words, and 8 is the one pass that
+ * makes the surface frame of both.
  * Returns 1 in the diagnostic build, 0 in the product build (no counter executes, the array stays zero). */
 int rt_debug_lane_stats(rt_ctx* ctx, uint64_t* out32, int reset);
 /* Proof obligation of the device build's short division / reciprocal / square-root sequences (csrc/k_ieee.hip.h): run

@@ -13,8 +13,13 @@ import numpy as np  # noqa: E402
 import webgpu_raytracer_amd as W  # noqa: E402
 
 scene = sys.argv[1] if len(sys.argv) > 1 else "cornell"
+# one-leaf forms: a new hit only records itself (part 5) and a new sample only makes its camera ray and loads its G-buffer
+# words (part 6); one pass at the start of the trip makes the surface frame of both (part 8).  The other forms make the
+# frame in parts 5 and 6 and have no part 8.
 PARTS = ("shade", "shadow walk: node step", "shadow walk: triangle chunk", "extension walk: node step",
-         "extension walk: triangle chunk", "surface frame of the new hit", "start of a sample", "end of a sample")
+         "extension walk: triangle chunk", "new hit (one-leaf: recorded; else + surface frame)",
+         "start of a sample (one-leaf: camera ray + G-buffer words; else + surface frame)", "end of a sample",
+         "surface frame, one pass (one-leaf forms)")
 
 
 def render(flags):
@@ -38,13 +43,13 @@ try:
     r.computeBatch(fl)
     r.sync()
     r.L.rt_debug_lane_stats(r.ctx, buf.ctypes.data_as(ctypes.c_void_p), 1)
-    n, lanes = buf[0:16:2].astype(float), buf[1:16:2].astype(float)
+    n, lanes = buf[0:18:2].astype(float), buf[1:18:2].astype(float)
     trips = n[0]
     print("scene=%s, one 32-frame batch: %d wave-level trips that shade" % (scene, trips))
-    print("   %-34s %14s %12s %12s" % ("part", "runs per trip", "lanes / run", "utilisation"))
+    print("   %-80s %14s %12s %12s" % ("part", "runs per trip", "lanes / run", "utilisation"))
     for k, name in enumerate(PARTS):
         if n[k]:
-            print("   %-34s %14.2f %12.1f %12.3f" % (name, n[k] / trips, lanes[k] / n[k], lanes[k] / n[k] / 64.0))
+            print("   %-80s %14.2f %12.1f %12.3f" % (name, n[k] / trips, lanes[k] / n[k], lanes[k] / n[k] / 64.0))
     r.destroy()
 finally:
     W._build.build_rt(force=True)

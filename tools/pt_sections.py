@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Where do the waves of k_pathtrace_persistent spend their cycles (Cornell, bench workload)?  DIAGNOSTIC build
-(-DRT_PT_STAMPS): s_memtime around the five sections of a trip, each closed by s_waitcnt 0.  Rebuilds the product library."""
+(-DRT_PT_STAMPS): s_memtime around the sections of a trip, each closed by s_waitcnt 0.  The one-leaf forms make the surface
+frame of new samples and new hits in one pass at the start of the trip, a section of its own; in the other forms it stays
+inside "start" and "extension traversal" and that section is empty.  Rebuilds the product library."""
 import ctypes
 import os
 import sys
@@ -30,10 +32,11 @@ try:
     r.sync()
     kt = r.kernelTimes()
     r.L.rt_debug_pt_sections(r.ctx, buf.ctypes.data_as(ctypes.c_void_p), 1)
-    cyc, trips, waves = buf[:5].astype(float), float(buf[5]), float(buf[6])
+    cyc, trips, waves = np.append(buf[:5], buf[7]).astype(float), float(buf[5]), float(buf[6])
     print("scene=%s: pathtrace %.2f ms; %d waves, %.0f trips/wave, %.0f cycles/trip" % (
         scene, kt["pathtrace"]["ms"], waves, trips / waves, cyc.sum() / trips))
-    for k, name in enumerate(("regenerate + start", "shade", "shadow traversal", "extension traversal + surface", "finish")):
+    for k, name in enumerate(("regenerate + start", "shade", "shadow traversal", "extension traversal", "finish",
+                              "surface frame (one pass)")):
         print("   %-30s %5.1f %%   %7.0f cycles per trip" % (name, 100 * cyc[k] / cyc.sum(), cyc[k] / trips))
     r.destroy()
 finally:

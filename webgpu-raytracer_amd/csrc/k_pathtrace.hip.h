@@ -100,15 +100,54 @@ __device__ __forceinline__ CameraBasis camera_basis(const rt_scene_uniforms& U) 
   return c;
 }
 
+// The arguments of the persistent kernel as they lie in its kernel-argument segment (the parameter list of
+// k_pathtrace_persistent.hip.h, in order: keep the two in step), and the segment seen through an opaque copy of its address.
+// A group of wave-uniform words read through it at the point of use is a scalar load served by the scalar cache, where the
+// same words read from the parameter are loaded once before the loop and held in scalar registers the kernel does not
+// have (it spills them to lanes of a VGPR and reads them back with a vector instruction each).
+struct PtKernArgs {
+  DevScene Sg;
+  DevFrame F;
+  rt_scene_uniforms U;
+  uint32_t* ticket;
+  uint32_t n_nodes_total, n_tris_total, n_inst_total, n_verts_total;
+  const DevFrameSlot* slots;
+  uint32_t n_slots;
+  LdsPlan plan;
+};
+typedef const PtKernArgs __attribute__((address_space(4))) * rt_kernargs;
+__device__ __forceinline__ rt_kernargs fresh_kernargs() {
+  rt_kernargs k = (rt_kernargs)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(k));
+  return k;
+}
+// camera_basis(U) of the kernel's U, read as new
+__device__ __forceinline__ CameraBasis fresh_camera_basis() {
+  const rt_kernargs k = fresh_kernargs();
+  CameraBasis c;
+  c.o = rt3_make(k->U.camera.origin[0], k->U.camera.origin[1], k->U.camera.origin[2]);
+  c.ll = rt3_make(k->U.camera.lower_left[0], k->U.camera.lower_left[1], k->U.camera.lower_left[2]);
+  c.h = rt3_make(k->U.camera.horizontal[0], k->U.camera.horizontal[1], k->U.camera.horizontal[2]);
+  c.v = rt3_make(k->U.camera.vertical[0], k->U.camera.vertical[1], k->U.camera.vertical[2]);
+  c.lens = k->U.camera.origin[3];
+  return c;
+}
+
 // Start sample p.sample of pixel p.pixel = (x, y) in the frame `slot` (Raytracer.wgsl:798-809, :608-619): seed the RNG,
 // make the camera ray, reset the path and take the depth-0 surface from the frame's G-buffer.  Returns false for a
 // background pixel (or MAX_DEPTH = 0): the sample is black and ends at once.  LIVE: the caller has made that test on the
 // pixel's G-buffer depth already (k_pathtrace_persistent hands out no other pixel); the depth is not read again and the
-// sample always starts.
-template <bool LIVE = false, bool REC = false>
+// sample always starts.  DEFER (the one-leaf forms of k_pathtrace_persistent): the surface frame is not made here; p.tri and
+// p.inst are set, the pixel's packed normal and albedo are handed on in `gs`, and the caller's one surface pass of the trip
+// calls setup_surface(.., from_gbuffer = true, ..) for the lane.
+struct GbufSurface {
+  float nx, ny;       // octahedral normal (normal_id.xy)
+  uint32_t albedo;    // rgba8
+};
+template <bool LIVE = false, bool REC = false, bool DEFER = false>
 __device__ __forceinline__ bool start_sample(const DevScene& S, const DevFrame& F, const rt_scene_uniforms& U,
                                              const CameraBasis& cam, const DevFrameSlot& slot, uint32_t x, uint32_t y,
-                                             PathState& p, const float4* wrec = nullptr) {
+                                             PathState& p, const float4* wrec = nullptr, GbufSurface* gs = nullptr) {
   p.rng = init_rng(p.pixel, slot.frame_count * F.spp + p.sample);
   rt3 off = rt3_splat(0.0f);
   if (cam.lens > 0.0f) {  // random_in_unit_disk (:201-205)
@@ -133,12 +172,28 @@ __device__ __forceinline__ bool start_sample(const DevScene& S, const DevFrame& 
   // the three G-buffer words of the pixel are requested together (they come from HBM: one round trip instead of depth
   // first, then the rest)
   const float gdepth = LIVE ? 0.0f : slot.depth[p.pixel];
-  const float4 g = slot.normal_id[p.pixel];
-  const uint32_t galbedo = slot.albedo[p.pixel];
+  float4 g;
+  uint32_t galbedo;
+  if constexpr (DEFER) {
+    // the plane pointers come out of the slot table in memory, so the compiler cannot tell their address space: named
+    // global here, or each load is a flat one that waits on the LDS counter as well (ld_g, k_traverse.hip.h)
+    const f4 gv = ld_g(reinterpret_cast<const f4*>(slot.normal_id), p.pixel);
+    g = make_float4(gv.x, gv.y, gv.z, gv.w);
+    galbedo = ld_g32(slot.albedo, p.pixel);
+  } else {
+    g = slot.normal_id[p.pixel];
+    galbedo = slot.albedo[p.pixel];
+  }
   if (LIVE || (!(gdepth >= 1.0f) && F.max_depth != 0u)) {
     p.tri = rt_f2u(g.z);
     p.inst = rt_f2u(g.w);
-    setup_surface<REC>(S, p, true, g.x, g.y, galbedo, wrec);
+    if constexpr (DEFER) {
+      gs->nx = g.x;
+      gs->ny = g.y;
+      gs->albedo = galbedo;
+    } else {
+      setup_surface<REC>(S, p, true, g.x, g.y, galbedo, wrec);
+    }
     return true;
   }
   return false;
@@ -389,7 +444,8 @@ __device__ __forceinline__ void stage_whole_scene(TravMem& M, DevScene& S, f4* s
 __device__ unsigned long long g_clock_stamps[2 * RT_CLOCK_STAMP_SLOTS];
 // Diagnostic build only (-DRT_PT_STAMPS, tools/pt_sections.py): s_memtime cycles the persistent kernel's waves spend in
 // the five sections of a trip (regenerate + start a sample, shade, shadow traversal, extension traversal + surface frame,
-// finish), summed over all waves; [5] = trips, [6] = waves.
+// finish), summed over all waves; [5] = trips, [6] = waves, [7] = the surface pass of the one-leaf forms, which is then in
+// neither the first nor the fourth section.
 __device__ unsigned long long g_pt_sections[8];
 
 // Occupancy: the LDS-resident form is VALU-issue bound (3, 4, 5 waves/SIMD within 2 %), the global-memory form

@@ -26,6 +26,10 @@ __global__ __launch_bounds__(64 * RT_PT_WAVES, RT_PT_SIMD_WAVES) void RT_PT_KERN
   // behind the wave queues (col_park), and the pixel index p.pixel is recomputed from pixel_xy.
   constexpr uint32_t WAVES = RT_PT_WAVES;   // per workgroup; they share one staged scene
   constexpr bool SLIM = WAVES == 8;
+  // ONE_PASS: one surface-frame pass per trip, at the head of the shade section, for the lanes that have just started a
+  // sample and the lanes whose extension ray of the last trip found a hit together; neither start_sample nor the code behind
+  // the extension walk makes a frame.  The camera is read as new where a sample starts (fresh_camera_basis).
+  constexpr bool ONE_PASS = ONE_INST;
   extern __shared__ f4 s_scene[];
   // per-wave triangle work queue at the start of LDS, staged scene after it
   // (LEAN: the wave's index in a scalar register, and so the addresses of its queue)
@@ -111,7 +115,7 @@ __global__ __launch_bounds__(64 * RT_PT_WAVES, RT_PT_SIMD_WAVES) void RT_PT_KERN
   uint32_t cnt_ext = 0, cnt_shadow = 0, cnt_nodes = 0, cnt_tris = 0, cnt_shaded = 0;
 
 #ifdef RT_PT_STAMPS
-  unsigned long long pt_cyc[5] = {0, 0, 0, 0, 0}, pt_trips = 0;
+  unsigned long long pt_cyc[6] = {0, 0, 0, 0, 0, 0}, pt_trips = 0;
 #endif
   for (;;) {
 #ifdef RT_PT_STAMPS
@@ -160,7 +164,10 @@ __global__ __launch_bounds__(64 * RT_PT_WAVES, RT_PT_SIMD_WAVES) void RT_PT_KERN
           if (x < U.width && y < U.height && (LEAN ? owns_row(fresh_stripes(F), y) : owns_row(F, y))) {
             const uint32_t pixel = y * (LEAN ? rt_fresh(U.width) : U.width) + x;
             // (LEAN: MAX_DEPTH taken as new here, or its test is carried through the trip as a lane mask in two SGPRs)
-            if (!(slots[tile_slot].depth[pixel] >= 1.0f) && (LEAN ? rt_fresh(F.max_depth) : F.max_depth) != 0u) {
+            // (LEAN: the depth plane named global memory, as the G-buffer loads of start_sample)
+            const float gdepth = LEAN ? __builtin_bit_cast(float, ld_g32(reinterpret_cast<const uint32_t*>(slots[tile_slot].depth), pixel))
+                                      : slots[tile_slot].depth[pixel];
+            if (!(gdepth >= 1.0f) && (LEAN ? rt_fresh(F.max_depth) : F.max_depth) != 0u) {
               need = false;
               have_pixel = true;
               if constexpr (!SLIM) p.pixel = y * U.width + x;
@@ -181,29 +188,57 @@ __global__ __launch_bounds__(64 * RT_PT_WAVES, RT_PT_SIMD_WAVES) void RT_PT_KERN
       }
     }
     // (b) start the next sample of the owned pixel: camera ray + depth-0 surface from the G-buffer (the pixel is not
-    //     background: the sample always starts)
+    //     background: the sample always starts).  ONE_PASS: camera ray and the pixel's G-buffer words; the surface frame is
+    //     made below, with the frames of the lanes whose extension ray found a hit in the last trip.
     RT_LSTAT(6, !alive && have_pixel);
+    GbufSurface gs = {0.0f, 0.0f, 0u};
+    bool started = false;   // ONE_PASS: the lane has just started a sample, its surface frame comes from the G-buffer words
     if (!alive && have_pixel) {
       const uint32_t x = pixel_xy & 0xffffu, y = pixel_xy >> 16;
       const DevFrameSlot slot = slots[item_slot];
       if constexpr (SLIM) p.pixel = y * rt_fresh(U.width) + x;
-      alive = LEAN ? start_sample<true, ONE_INST>(S, F, fresh_size(U), cam, slot, x, y, p, wrec)
-                   : start_sample<true>(S, F, U, cam, slot, x, y, p);
+      if constexpr (ONE_PASS) {
+        // (the camera read as new: thirteen scalar registers the rest of the trip can use)
+        alive = started = start_sample<true, true, true>(S, F, fresh_size(U), fresh_camera_basis(), slot, x, y, p, wrec, &gs);
+      } else {
+        alive = LEAN ? start_sample<true, ONE_INST>(S, F, fresh_size(U), cam, slot, x, y, p, wrec)
+                     : start_sample<true>(S, F, U, cam, slot, x, y, p);
+      }
     }
     const bool running = alive;
     bool path_done = false;
-
 #ifdef RT_PT_STAMPS
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    const unsigned long long ps1 = __builtin_amdgcn_s_memtime();
+    const unsigned long long ps0b = __builtin_amdgcn_s_memtime();
+    unsigned long long ps1 = ps0b;
 #endif
-    // ------------------------------------------------------------ shade one bounce
+
+    // ------------------------------------------------------------ surface frame (ONE_PASS) and shade one bounce
     bool want_shadow = false, want_extend = false;
     bool nee_valid = false;
     rt3 sh_o = rt3_splat(0.0f), sh_d = rt3_splat(0.0f), nee = rt3_splat(0.0f);
     float sh_tmax = 0.0f;
     RT_LSTAT(0, running);
+    RT_LSTAT(8, ONE_PASS && running);
     if (running) {
+      // ONE_PASS: a lane that is alive here and has not just started a sample came through the last trip without ending, so
+      // its extension ray of that trip found a hit (shade_bounce asks for the ray or ends the path, and a miss ends it): every
+      // running lane needs a surface frame, and no other lane does.  One pass makes it for both kinds: instance rows, local
+      // ray, triangle records and barycentrics once; the lane condition `started` picks the tail (normal and albedo of the
+      // G-buffer and hit_t of the primary ray, or interpolated vertex normals and the material).  Per lane the functions and
+      // their inputs are those of the two separate calls: a new hit's ray, triangle and distance are not touched between the
+      // walk that found it and this point.  The frame (normal, geometric normal, albedo, texture coordinates) lives from here
+      // to the end of the bounce only.
+      if constexpr (ONE_PASS) {
+        // every hit, the primary pass's too, is in the one instance the TLAS leaf names: its index is read here, as traverse()
+        // reads it, and p.inst is not carried through the walks
+        p.inst = __builtin_amdgcn_readfirstlane(rt_f2u(ld_l(s_scene, M.l_nodes + 1u).w) >> 3);
+        setup_surface<true>(S, p, started, gs.nx, gs.ny, gs.albedo, wrec);
+#ifdef RT_PT_STAMPS
+        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+        ps1 = __builtin_amdgcn_s_memtime();
+#endif
+      }
       if (DETAIL) cnt_shaded++;
       BounceOut bo;
       shade_bounce<ONE_INST>(S, LEAN ? rt_fresh(U.light_count) : U.light_count, LEAN ? rt_fresh(F.max_depth) : F.max_depth, p,
@@ -258,7 +293,8 @@ __global__ __launch_bounds__(64 * RT_PT_WAVES, RT_PT_SIMD_WAVES) void RT_PT_KERN
           p.hit_t = t_;
           p.tri = (uint32_t)tri_;
           p.inst = (uint32_t)inst_;
-          setup_surface<ONE_INST>(S, p, false, 0.0f, 0.0f, 0u, wrec);
+          // (ONE_PASS: the hit's surface frame is made at the start of the next trip)
+          if constexpr (!ONE_PASS) setup_surface<ONE_INST>(S, p, false, 0.0f, 0.0f, 0u, wrec);
           p.depth++;
         }
       }
@@ -292,7 +328,8 @@ __global__ __launch_bounds__(64 * RT_PT_WAVES, RT_PT_SIMD_WAVES) void RT_PT_KERN
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     {
       const unsigned long long ps5 = __builtin_amdgcn_s_memtime();
-      pt_cyc[0] += ps1 - ps0; pt_cyc[1] += ps2 - ps1; pt_cyc[2] += ps3 - ps2; pt_cyc[3] += ps4 - ps3; pt_cyc[4] += ps5 - ps4;
+      pt_cyc[0] += ps0b - ps0; pt_cyc[5] += ps1 - ps0b; pt_cyc[1] += ps2 - ps1;
+      pt_cyc[2] += ps3 - ps2; pt_cyc[3] += ps4 - ps3; pt_cyc[4] += ps5 - ps4;
       pt_trips++;
     }
 #endif
@@ -303,6 +340,7 @@ __global__ __launch_bounds__(64 * RT_PT_WAVES, RT_PT_SIMD_WAVES) void RT_PT_KERN
     for (int k = 0; k < 5; k++) atomicAdd(&g_pt_sections[k], pt_cyc[k]);
     atomicAdd(&g_pt_sections[5], pt_trips);
     atomicAdd(&g_pt_sections[6], 1ull);
+    atomicAdd(&g_pt_sections[7], pt_cyc[5]);
   }
 #endif
 

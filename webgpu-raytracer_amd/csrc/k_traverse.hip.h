@@ -161,7 +161,9 @@ __device__ __forceinline__ void wave_work_at(WaveWork& W, char* wbase) {
 // Diagnostic build only (-DRT_LANE_STATS, tools/lane_stats.py): how many lanes are active each time a wave executes one of
 // the parts of a trip — g_lane_stats[2 k] = times part k ran, [2 k + 1] = active lanes summed.  Parts: 0 shade, 1 / 2 node step
 // and triangle chunk of the shadow walk, 3 / 4 the same of the extension walk, 5 surface frame of the new hit, 6 start of a
-// sample (camera ray + G-buffer surface), 7 end of a sample.  Nothing else reads the array; in the product build RT_LSTAT is empty.
+// sample (camera ray + G-buffer surface), 7 end of a sample.  In the one-leaf forms of the persistent kernel part 5 only records
+// the hit and part 6 makes the camera ray and loads the G-buffer words; 8 is the one pass that makes the surface frame of both.
+// Nothing else reads the array; in the product build RT_LSTAT is empty.
 __device__ unsigned long long g_lane_stats[32];
 #ifdef RT_LANE_STATS
 #define RT_LSTAT(k, cond)                                                                                  \
