@@ -449,7 +449,8 @@ int rt_irradiance_gather_stats(rt_ctx* ctx, rt_radiance_stats* out);
  * the library splits the work: a call is cut into batches of whole probes of at most RT_PROBE_BATCH_SAMPLES samples, whose
  * rays and radiances live in scratch of the probe gather's own, kept and grown (at most 48 B per sample of a batch, 192
  * MiB).  The rgb irradiance at a normal n follows from the coefficients by the cosine-lobe convolution (band factors pi, 2
- * pi / 3, pi / 4), a host one-liner; ringing filters and the layout of a probe grid are the caller's.
+ * pi / 3, pi / 4), a host one-liner; a probe grid with that convolution, a window against ringing and a device sampler is an
+ * irradiance volume (below).
  * The stats are an rt_radiance_stats: rays = n probes, samples = n * spp; the ray, hit, node and triangle counters and
  * workgroups are the sums over the radiance launches the call makes - hence the sums of the composed queries' counters -
  * lds is the form that was picked, and kernel_ms is the summed time of the RADIANCE launches only (k_probe_rays and
@@ -470,6 +471,75 @@ int rt_gather_probes(rt_ctx* ctx, const rt_probe* probes, uint32_t n, uint32_t m
 int rt_gather_probes_device(rt_ctx* ctx, const void* dev_probes, uint32_t n, uint32_t max_depth, uint32_t spp, uint32_t seed,
                             void* dev_out);
 int rt_probe_gather_stats(rt_ctx* ctx, rt_radiance_stats* out);
+
+/* ---- irradiance volumes: "how much light arrives at this point of space, on a surface facing this way?" for dynamic
+ * objects that have no lightmap ----
+ * A volume is an axis-aligned grid of probes (rt_volume_desc, mi355rt_layout.h): nx * ny * nz records of rt_probe_sh9,
+ * probe-major, probe (x, y, z) at p = (z * ny + y) * nx + x.  rt_bake_volume makes the grid's probes on the device, runs
+ * the probe gather's device path on them and finishes the coefficients in place; rt_sample_volume turns (position,
+ * normal) pairs into irradiance from the eight surrounding probes; rt_encode_volume exports the volume as seven texel
+ * layers for consumers that upload 3D textures (csrc/k_volume.hip.h).  The volume stays probe-major for the library's own
+ * sampler: a record is one 112-byte run and the x-neighbour of a corner the next one, so a point reads four runs of 224
+ * bytes; layers would make the same read 56 separate 16-byte pieces.
+ *
+ * THE VOLUME RULE.  All arithmetic is f32, unfused, in the order written, with rt_div / rt_min / rt_max / rt_normalize of
+ * mi355rt_math.h.
+ *   probes     of the grid, for probe (x, y, z): position[a] = origin[a] + (float)idx_a * step[a], the product rounded first;
+ *              t_max = desc.t_max; unused = +0; pad = pad_first + p.
+ *   finish     sh'[k][c] = (sh[k][c] * A_band(k)) * window[band(k)] on what the probe rule gives for those probes, with A =
+ *              3.141592654f, 2.094395102f, 0.785398163f for bands 0 (k = 0), 1 (k = 1 .. 3) and 2 (k = 4 .. 8); hit_fraction
+ *              keeps its bits.  The volume therefore holds IRRADIANCE coefficients: E(n) = sum_k sh'[k] Y_k(n).  window =
+ *              {1, 1, 1} is none; a Hanning window of width w is (1 + cos(pi l / w)) / 2 for band l.
+ *   sample     at {position, normal} of an rt_gather_point (t_max and pad are not read):
+ *     cell       per axis a with N = n_a: g = rt_div(position[a] - origin[a], step[a]); if !(g > 0) then g = +0 (NaN too); g =
+ *                rt_min(g, (float)(N - 1)); i0 = (uint32_t)g; if N > 1 and i0 > N - 2 then i0 = N - 2; i1 = i0 + 1 (i1 = i0
+ *                when N == 1); f = g - (float)i0 (f = +0 when N == 1); w0 = 1.0f - f, w1 = f.
+ *     corners    c = 0 .. 7 with dx = c & 1, dy = (c >> 1) & 1, dz = c >> 2: w_c = (wx[dx] * wy[dy]) * wz[dz], replaced by +0
+ *                when the corner probe is invalid: !(hit_fraction <= max_hit_fraction), so a NaN hit_fraction is invalid.
+ *     weight     W = ((+0 + w_0) + w_1) + ... in corner order.  If !(W > 0) the result is {+0, +0, +0, +0}.
+ *     coefs      for each of the 27 (k, ch): S = +0, then S = S + w_c * sh'_c[k][ch] for every corner with w_c != 0, in
+ *                corner order; corners of weight zero are SKIPPED, not multiplied, so a NaN or an infinity in an invalid or
+ *                zero-weight probe never reaches a result.  coef = rt_div(S, W).
+ *     evaluate   nrm = rt_normalize(normal); Y_k(nrm) with the nine constants and the operation order of the probe rule;
+ *                E[ch] = ((+0 + coef[0][ch] * Y0) + coef[1][ch] * Y1) + ... for k = 0 .. 8; rgb[ch] = rt_max(0.0f, E[ch]);
+ *                the hit_fraction slot = W, the valid share of the interpolation weight (1 when all eight corners are
+ *                valid).
+ *   layers     layer j = 0 .. 6 of the export holds the floats 4 j .. 4 j + 3 of each record, n texels per layer in probe
+ *              order: RT_LIGHTMAP_F32, 16 B per texel, the words unchanged; RT_LIGHTMAP_F16, 8 B, four rt_f32_to_f16 as in
+ *              rt_encode_atlas.  RT_LIGHTMAP_RGBE8 is refused: coefficients are signed.
+ * A sample depends on (volume, desc, point) only - never on n, the point's place in the array or the launch shape.  A
+ * baked volume depends on (scene, desc, seed, spp, max_depth) only, as the probe rule says of its probes.
+ * Refusals (RT_ERR_INVALID, every message begins with "volume:"): a dimension 0 or above 1024; nx * ny * nz > 2^24;
+ * pad_first + nx * ny * nz > 2^31; a step that is not finite and > 0; a window that is not finite and >= 0; a NaN
+ * max_hit_fraction; a non-zero reserved word.  The descriptor is checked before the context, and without one the message is
+ * what rt_last_error(NULL) returns.
+ * A bake runs on the probe gather's state: its probes and, for the blocking entry, its results live in the probe gather's
+ * staging, its stats are the probe gather's (rays = probes; kernel_ms the radiance launches only), and
+ * rt_probe_gather_stats reports the last bake like the last gather.  Sampling and encoding need no scene - they work on a
+ * context with nothing uploaded - and have staging of their own, kept and grown.  Baking, sampling and encoding leave the
+ * renderer and the other queries' state as they were.
+ *   rt_bake_volume           blocking: probes, gather (cut into batches as a probe gather is), finish, one copy of n
+ *                            records back.  stats != NULL runs the counting kernel and fills *stats.  spp as for a probe
+ *                            gather; without a valid scene RT_ERR_NOT_READY.
+ *   rt_bake_volume_device    the same into a device-accessible array of n records (16-byte aligned, on the context's
+ *                            device): only enqueues on the context's stream (rt_set_stream respected).
+ *   rt_sample_volume         blocking: copies the volume and n points in, samples, copies n results out.  n == 0 is RT_OK; n
+ *                            >= 2^31 or a NULL pointer is RT_ERR_INVALID.  It uploads the whole volume on every call and keeps
+ *                            that staging: a caller sampling every frame should keep the volume on the device and use
+ *   rt_sample_volume_device  the same on device-accessible arrays (16-byte aligned): only enqueues.
+ *   rt_encode_volume         blocking: the volume into seven layers at out, layer j at out + j * n * texel bytes; cap is the
+ *                            capacity of out in bytes.  format is RT_LIGHTMAP_F32 or RT_LIGHTMAP_F16.
+ *   rt_encode_volume_device  the same on device-accessible arrays; dev_out must not be dev_volume.  Only enqueues. */
+int rt_bake_volume(rt_ctx* ctx, const rt_volume_desc* desc, uint32_t max_depth, uint32_t spp, uint32_t seed, rt_probe_sh9* out,
+                   rt_radiance_stats* stats);
+int rt_bake_volume_device(rt_ctx* ctx, const rt_volume_desc* desc, uint32_t max_depth, uint32_t spp, uint32_t seed, void* dev_out);
+int rt_sample_volume(rt_ctx* ctx, const rt_volume_desc* desc, const rt_probe_sh9* volume, const rt_gather_point* points,
+                     uint32_t n, rt_irradiance* out);
+int rt_sample_volume_device(rt_ctx* ctx, const rt_volume_desc* desc, const void* dev_volume, const void* dev_points, uint32_t n,
+                            void* dev_out);
+int rt_encode_volume(rt_ctx* ctx, const rt_volume_desc* desc, uint32_t format, const rt_probe_sh9* volume, void* out, size_t cap);
+int rt_encode_volume_device(rt_ctx* ctx, const rt_volume_desc* desc, uint32_t format, const void* dev_volume, void* dev_out,
+                            size_t cap);
 
 /* ---- directional gathers: "which radiance arrives at this surface point, from which side?" as four spherical-harmonic
  * coefficients per colour over the hemisphere of the normal (directional lightmaps for normal-mapped surfaces) ----

@@ -168,6 +168,22 @@ typedef struct rt_probe_sh9 { /* 112 B: seven 16-byte vector stores of k_probe_p
   float hit_fraction;         /* samples whose first segment hit something / spp */
 } rt_probe_sh9;
 
+/* ---- irradiance volumes (rt_bake_volume / rt_sample_volume, mi355rt.h): an axis-aligned grid of nx * ny * nz probes.  The volume
+ * itself is n = nx * ny * nz records of rt_probe_sh9, probe-major, probe (x, y, z) at p = (z * ny + y) * nx + x; a sample goes
+ * in as an rt_gather_point (t_max and pad not read) and comes out as an rt_irradiance ---- */
+typedef struct rt_volume_desc { /* 64 B */
+  float origin[3];            /* position of probe (0, 0, 0) */
+  uint32_t nx;                /* each dimension 1 .. 1024, nx * ny * nz <= 2^24 */
+  float step[3];              /* axis-aligned spacing, finite and > 0 */
+  uint32_t ny;
+  float window[3];            /* per-band scale (bands 0, 1, 2), finite and >= 0; {1, 1, 1} = none */
+  uint32_t nz;
+  float t_max;                /* of every probe */
+  uint32_t pad_first;         /* probe p gets pad = pad_first + p; pad_first + n <= 2^31 */
+  float max_hit_fraction;     /* sampler only: a probe is valid iff hit_fraction <= this; a NaN hit_fraction is invalid */
+  uint32_t reserved;          /* 0 */
+} rt_volume_desc;
+
 /* ---- directional gathers (rt_gather_directional, mi355rt.h): rt_gather_point in; their stats are an rt_radiance_stats ---- */
 typedef struct rt_directional {   /* 64 B: four 16-byte vector stores of k_dir_project */
   float layer[4][4];              /* layer[k] = {sh[k].r, sh[k].g, sh[k].b, hit_fraction}: row k is the texel of atlas layer k */
@@ -241,6 +257,10 @@ typedef struct rt_lightmap_desc { /* 64 B */
 static_assert(sizeof(rt_lightmap_desc) == 64, "rt_lightmap_desc is 64 bytes");
 static_assert(__builtin_offsetof(rt_lightmap_desc, passes) == 32 && __builtin_offsetof(rt_lightmap_desc, format) == 56,
               "rt_lightmap_desc: the filter starts at 32, the format is at 56");
+static_assert(sizeof(rt_volume_desc) == 64, "rt_volume_desc is 64 bytes");
+static_assert(__builtin_offsetof(rt_volume_desc, step) == 16 && __builtin_offsetof(rt_volume_desc, window) == 32 &&
+                  __builtin_offsetof(rt_volume_desc, t_max) == 48 && __builtin_offsetof(rt_volume_desc, max_hit_fraction) == 56,
+              "rt_volume_desc: four 16-byte rows, a dimension closing each of the first three");
 static_assert(sizeof(rt_denoise_desc) == 32, "rt_denoise_desc is 32 bytes");
 static_assert(sizeof(rt_dilate_desc) == 32, "rt_dilate_desc is 32 bytes");
 static_assert(sizeof(rt_bake_desc) == 32, "rt_bake_desc is 32 bytes");

@@ -34,6 +34,9 @@
 //                             points, on LDS windows (rt_denoise_atlas)
 //   k_encode.hip.h            k_encode_atlas: a finished f32 atlas as half floats or shared-exponent RGBE8 words
 //                             (rt_encode_atlas, the last stage of rt_bake_atlas_lightmap)
+//   k_volume.hip.h            k_volume_probes / _finish / _sample / _layers: the probes of a grid, SH9 radiance into windowed
+//                             irradiance coefficients, the trilinear sampler (eight lanes per point) and the export into
+//                             seven texel layers (rt_bake_volume, rt_sample_volume, rt_encode_volume)
 //   k_texture_post.hip.h      k_resize_texture; k_postprocess = PostProcess.wgsl `main` (:103-176)
 //   k_validate.hip.h          k_validate_scene: every index the kernels follow, checked once per upload
 //   k_stripes.hip.h           k_pack_stripes / k_unpack_stripes: the copies of the sharded image's gather
@@ -69,6 +72,7 @@
 #include "k_dilate.hip.h"
 #include "k_denoise.hip.h"
 #include "k_encode.hip.h"
+#include "k_volume.hip.h"
 #include "k_wavefront.hip.h"
 #include "k_rayquery.hip.h"
 #include "k_texture_post.hip.h"

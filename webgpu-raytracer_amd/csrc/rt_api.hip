@@ -101,6 +101,12 @@ struct LightmapState {
   DeviceBuffer filtered, filled, encoded, in;
 };
 
+// What irradiance volumes (rt_sample_volume, rt_encode_volume) keep between calls, kept and grown: the staged volume, points
+// and results of the host entries and the encoded layers.  A bake's probes and results live in the probe gather's staging.
+struct VolumeState {
+  DeviceBuffer volume, points, out, encoded;
+};
+
 }  // namespace
 
 struct rt_ctx {
@@ -263,6 +269,7 @@ struct rt_ctx {
   DilateState dl;
   DenoiseState dn;
   LightmapState lm;
+  VolumeState vol;
 
   // kernel timing
   bool timing = false;
@@ -1000,6 +1007,7 @@ void rt_destroy(rt_ctx* c) {
                          &c->dl.atlas, &c->dl.filled, &c->dl.bitmap, &c->dl.src,
                          &c->dn.index, &c->dn.scratch, &c->dn.in, &c->dn.out, &c->dn.points, &c->dn.texels,
                          &c->lm.filtered, &c->lm.filled, &c->lm.encoded, &c->lm.in,
+                         &c->vol.volume, &c->vol.points, &c->vol.out, &c->vol.encoded,
                          &c->tex_staging, &c->bv_in, &c->bv_tri, &c->bv_order, &c->bv_nodes, &c->bv_out,
                          &c->bv_counters, &c->bv_big, &c->val_roots, &c->val_bad, &c->tnodes, &c->node_key, &c->node_newidx,
                          &c->inst_root, &c->root_w, &c->treelet_work, &c->pairs, &c->pair_of, &c->pair_parent, &c->root_rec,
@@ -3290,6 +3298,179 @@ int rt_encode_atlas(rt_ctx* c, uint32_t width, uint32_t height, uint32_t format,
   HIP_TRY(c, hipMemcpyAsync(c->lm.in.ptr, atlas_in, (size_t)texels * 16, hipMemcpyHostToDevice, c->stream));
   if ((r = launch_encode(c, texels, format, c->lm.in.ptr, c->lm.encoded.ptr)) < 0) return r;
   HIP_TRY(c, hipMemcpyAsync(out, c->lm.encoded.ptr, bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return RT_OK;
+}
+
+// ---- irradiance volumes (mi355rt.h "THE VOLUME RULE"; k_volume.hip.h): a grid of probes baked through the probe gather's
+// device path, finished into windowed irradiance coefficients, sampled trilinearly, exported as texel layers.
+static const char* const kVolume = "volume";
+// a refusal that needs no context: without one the message is what rt_last_error(NULL) returns
+static int volume_fail(rt_ctx* c, const std::string& msg) {
+  if (!c) g_create_error = msg;
+  return fail(c, RT_ERR_INVALID, msg);
+}
+// everything the limits say about a descriptor; *n_out = nx * ny * nz
+static int volume_desc_ok(rt_ctx* c, const rt_volume_desc* d, uint32_t* n_out) {
+  const std::string w(kVolume);
+  if (!d) return volume_fail(c, w + ": NULL descriptor");
+  if (d->nx == 0 || d->ny == 0 || d->nz == 0 || d->nx > 1024 || d->ny > 1024 || d->nz > 1024)
+    return volume_fail(c, w + ": nx, ny and nz must be 1 .. 1024");
+  const uint64_t n = (uint64_t)d->nx * d->ny * d->nz;
+  if (n > (1ull << 24)) return volume_fail(c, w + ": nx * ny * nz must be <= 2^24");
+  if ((uint64_t)d->pad_first + n > (1ull << 31)) return volume_fail(c, w + ": pad_first + nx * ny * nz must be <= 2^31");
+  for (int a = 0; a < 3; a++) {
+    if (!(std::isfinite(d->step[a]) && d->step[a] > 0.0f)) return volume_fail(c, w + ": step must be finite and > 0");
+    if (!(std::isfinite(d->window[a]) && d->window[a] >= 0.0f)) return volume_fail(c, w + ": window must be finite and >= 0");
+  }
+  if (d->max_hit_fraction != d->max_hit_fraction) return volume_fail(c, w + ": max_hit_fraction must not be NaN");
+  if (d->reserved) return volume_fail(c, w + ": reserved must be 0");
+  *n_out = (uint32_t)n;
+  return RT_OK;
+}
+// a refusal of the probe gather's, under the volume's name: "volume: probe gather: spp must be 1 .. 65536"
+static int volume_refused(rt_ctx* c, int code) { return fail(c, code, std::string(kVolume) + ": " + c->error); }
+
+// Enqueue a bake: the grid's probes into the probe gather's staging, its device path with its batching into d_out, the
+// finish in place.
+static int launch_bake_volume(rt_ctx* c, const rt_volume_desc& D, uint32_t n, uint32_t max_depth, uint32_t spp, uint32_t seed,
+                              void* d_out, bool detail) {
+  int r = query_scene_ready(c, kVolume, true);
+  if (r < 0) return r;
+  if ((r = ensure_buffer(c, c->pr.in, (size_t)n * sizeof(rt_probe), true)) < 0) return r;
+  hipLaunchKernelGGL(rtk::k_volume_probes, dim3((n + 255u) / 256u), dim3(256), 0, c->stream, D, (float4*)c->pr.in.ptr, n);
+  HIP_TRY(c, hipGetLastError());
+  if ((r = launch_composed_gather(c, cg_probe, c->pr.in.ptr, n, max_depth, spp, seed, d_out, detail)) < 0)
+    return volume_refused(c, r);
+  const uint32_t n_vec = n * (uint32_t)(sizeof(rt_probe_sh9) / 16);
+  hipLaunchKernelGGL(rtk::k_volume_finish, dim3((n_vec + 255u) / 256u), dim3(256), 0, c->stream, D, (float4*)d_out, n_vec);
+  HIP_TRY(c, hipGetLastError());
+  return RT_OK;
+}
+
+int rt_bake_volume_device(rt_ctx* c, const rt_volume_desc* desc, uint32_t max_depth, uint32_t spp, uint32_t seed, void* dev_out) {
+  uint32_t n = 0;
+  int r = volume_desc_ok(c, desc, &n);
+  if (r < 0 || !c) return RT_ERR_INVALID;
+  if ((r = path_query_args_ok(c, pq_probe, n, spp)) < 0) return volume_refused(c, r);
+  if (!dev_out) return fail(c, RT_ERR_INVALID, std::string(kVolume) + ": NULL array");
+  if ((r = query_device_arrays_ok(c, kVolume, dev_out, dev_out)) < 0) return r;
+  return launch_bake_volume(c, *desc, n, max_depth, spp, seed, dev_out, c->detailed_counters);
+}
+
+int rt_bake_volume(rt_ctx* c, const rt_volume_desc* desc, uint32_t max_depth, uint32_t spp, uint32_t seed, rt_probe_sh9* out,
+                   rt_radiance_stats* stats) {
+  uint32_t n = 0;
+  int r = volume_desc_ok(c, desc, &n);
+  if (r < 0 || !c) return RT_ERR_INVALID;
+  if ((r = path_query_args_ok(c, pq_probe, n, spp)) < 0) return volume_refused(c, r);
+  if (!out) return fail(c, RT_ERR_INVALID, std::string(kVolume) + ": NULL array");
+  HIP_TRY(c, hipSetDevice(c->device));
+  const size_t bytes = (size_t)n * sizeof(rt_probe_sh9);
+  if ((r = ensure_buffer(c, c->pr.out, bytes, true)) < 0) return r;
+  if ((r = launch_bake_volume(c, *desc, n, max_depth, spp, seed, c->pr.out.ptr, stats != nullptr)) < 0) return r;
+  HIP_TRY(c, hipMemcpyAsync(out, c->pr.out.ptr, bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (stats) return composed_gather_stats(c, cg_probe, stats);
+  return RT_OK;
+}
+
+// the arguments of a sample beside the descriptor; 1: nothing to do
+static int volume_sample_args_ok(rt_ctx* c, uint32_t n, const void* volume, const void* points, const void* out) {
+  const std::string w(kVolume);
+  if (n >= (1u << 31)) return fail(c, RT_ERR_INVALID, w + ": too many points for one call (n must be below 2^31)");
+  if (n == 0) return 1;
+  if (!volume || !points || !out) return fail(c, RT_ERR_INVALID, w + ": NULL array");
+  return RT_OK;
+}
+static int launch_sample_volume(rt_ctx* c, const rt_volume_desc& D, const void* d_volume, const void* d_points, uint32_t n,
+                                void* d_out) {
+  rtk::VolumeSampleArgs A;
+  A.D = D;
+  A.volume = (const float4*)d_volume;
+  A.points = (const float4*)d_points;
+  A.out = (float4*)d_out;
+  A.n = n;
+  hipLaunchKernelGGL(rtk::k_volume_sample, dim3((n + 31u) / 32u), dim3(256), 0, c->stream, A);   // 8 lanes per point
+  HIP_TRY(c, hipGetLastError());
+  return RT_OK;
+}
+
+int rt_sample_volume_device(rt_ctx* c, const rt_volume_desc* desc, const void* dev_volume, const void* dev_points, uint32_t n,
+                            void* dev_out) {
+  uint32_t probes = 0;
+  int r = volume_desc_ok(c, desc, &probes);
+  if (r < 0 || !c) return RT_ERR_INVALID;
+  if ((r = volume_sample_args_ok(c, n, dev_volume, dev_points, dev_out)) != RT_OK) return r < 0 ? r : RT_OK;
+  if ((r = query_device_arrays_ok(c, kVolume, dev_volume, dev_out)) < 0) return r;
+  if ((r = query_device_arrays_ok(c, kVolume, dev_points, dev_out)) < 0) return r;
+  return launch_sample_volume(c, *desc, dev_volume, dev_points, n, dev_out);
+}
+
+int rt_sample_volume(rt_ctx* c, const rt_volume_desc* desc, const rt_probe_sh9* volume, const rt_gather_point* points, uint32_t n,
+                     rt_irradiance* out) {
+  uint32_t probes = 0;
+  int r = volume_desc_ok(c, desc, &probes);
+  if (r < 0 || !c) return RT_ERR_INVALID;
+  if ((r = volume_sample_args_ok(c, n, volume, points, out)) != RT_OK) return r < 0 ? r : RT_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  const size_t vol_bytes = (size_t)probes * sizeof(rt_probe_sh9);
+  if ((r = ensure_buffer(c, c->vol.volume, vol_bytes, true)) < 0) return r;
+  if ((r = ensure_buffer(c, c->vol.points, (size_t)n * sizeof(rt_gather_point), true)) < 0) return r;
+  if ((r = ensure_buffer(c, c->vol.out, (size_t)n * sizeof(rt_irradiance), true)) < 0) return r;
+  HIP_TRY(c, hipMemcpyAsync(c->vol.volume.ptr, volume, vol_bytes, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(c->vol.points.ptr, points, (size_t)n * sizeof(rt_gather_point), hipMemcpyHostToDevice, c->stream));
+  if ((r = launch_sample_volume(c, *desc, c->vol.volume.ptr, c->vol.points.ptr, n, c->vol.out.ptr)) < 0) return r;
+  HIP_TRY(c, hipMemcpyAsync(out, c->vol.out.ptr, (size_t)n * sizeof(rt_irradiance), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return RT_OK;
+}
+
+// the arguments of an export beside the descriptor: the format is f32 or f16, the capacity holds seven layers
+static int volume_encode_args_ok(rt_ctx* c, uint32_t probes, uint32_t format, const void* volume, const void* out, size_t cap) {
+  const std::string w(kVolume);
+  if (format == RT_LIGHTMAP_RGBE8) return volume_fail(c, w + ": RT_LIGHTMAP_RGBE8 cannot hold signed coefficients");
+  if (format != RT_LIGHTMAP_F32 && format != RT_LIGHTMAP_F16) return volume_fail(c, w + ": format must be RT_LIGHTMAP_F32 or _F16");
+  if (!c) return RT_ERR_INVALID;
+  if (!volume || !out) return fail(c, RT_ERR_INVALID, w + ": NULL array");
+  if (cap < 7 * (size_t)probes * lightmap_texel_bytes(format))
+    return fail(c, RT_ERR_INVALID, w + ": the capacity is below seven layers of nx * ny * nz texels of the format");
+  return RT_OK;
+}
+static int launch_volume_layers(rt_ctx* c, uint32_t probes, uint32_t format, const void* d_volume, void* d_out) {
+  rtk::VolumeLayersArgs A;
+  A.volume = (const uint4*)d_volume;
+  A.out = d_out;
+  A.n = probes;
+  A.format = format;
+  hipLaunchKernelGGL(rtk::k_volume_layers, dim3((7u * probes + 255u) / 256u), dim3(256), 0, c->stream, A);
+  HIP_TRY(c, hipGetLastError());
+  return RT_OK;
+}
+
+int rt_encode_volume_device(rt_ctx* c, const rt_volume_desc* desc, uint32_t format, const void* dev_volume, void* dev_out,
+                            size_t cap) {
+  uint32_t probes = 0;
+  int r = volume_desc_ok(c, desc, &probes);
+  if (r < 0) return r;
+  if ((r = volume_encode_args_ok(c, probes, format, dev_volume, dev_out, cap)) < 0) return r;
+  if (dev_volume == dev_out) return fail(c, RT_ERR_INVALID, std::string(kVolume) + ": the output must not be the input");
+  if ((r = query_device_arrays_ok(c, kVolume, dev_volume, dev_out)) < 0) return r;
+  return launch_volume_layers(c, probes, format, dev_volume, dev_out);
+}
+
+int rt_encode_volume(rt_ctx* c, const rt_volume_desc* desc, uint32_t format, const rt_probe_sh9* volume, void* out, size_t cap) {
+  uint32_t probes = 0;
+  int r = volume_desc_ok(c, desc, &probes);
+  if (r < 0) return r;
+  if ((r = volume_encode_args_ok(c, probes, format, volume, out, cap)) < 0) return r;
+  HIP_TRY(c, hipSetDevice(c->device));
+  const size_t in_bytes = (size_t)probes * sizeof(rt_probe_sh9), out_bytes = 7 * (size_t)probes * lightmap_texel_bytes(format);
+  if ((r = ensure_buffer(c, c->vol.volume, in_bytes, true)) < 0) return r;
+  if ((r = ensure_buffer(c, c->vol.encoded, out_bytes, true)) < 0) return r;
+  HIP_TRY(c, hipMemcpyAsync(c->vol.volume.ptr, volume, in_bytes, hipMemcpyHostToDevice, c->stream));
+  if ((r = launch_volume_layers(c, probes, format, c->vol.volume.ptr, c->vol.encoded.ptr)) < 0) return r;
+  HIP_TRY(c, hipMemcpyAsync(out, c->vol.encoded.ptr, out_bytes, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return RT_OK;
 }

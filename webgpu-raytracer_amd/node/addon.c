@@ -660,6 +660,75 @@ static napi_value rtGatherProbes(napi_env env, napi_callback_info info) {
   return radiance_stats_object(env, &st);
 }
 
+/* ------------------------------------------------------- irradiance volumes (rt_bake_volume, rt_sample_volume, mi355rt.h) */
+/* the 64 bytes of an rt_volume_desc in a typed array, and its probe count (0: a dimension is 0 or the product overflows) */
+static const rt_volume_desc* get_volume_desc(napi_env env, napi_value v, size_t* n) {
+  void* d = NULL;
+  size_t nd = 0;
+  if (!get_bytes(env, v, &d, &nd)) return NULL;
+  if (nd != sizeof(rt_volume_desc)) {
+    napi_throw_range_error(env, NULL, "a volume descriptor is 64 bytes");
+    return NULL;
+  }
+  const rt_volume_desc* desc = (const rt_volume_desc*)d;
+  const uint64_t probes = (uint64_t)desc->nx * desc->ny * desc->nz;
+  *n = (desc->nx > 1024 || desc->ny > 1024 || desc->nz > 1024 || probes > (1u << 24)) ? 0 : (size_t)probes;
+  return desc;
+}
+/* (ctx, desc: 64 bytes, maxDepth, spp, seed, out: Float32Array of 28 per probe, wantStats) -> status, or the stats object */
+static napi_value rtBakeVolume(napi_env env, napi_callback_info info) {
+  napi_value a[7];
+  void* out = NULL;
+  size_t n = 0, no = 0;
+  bool want_stats = false;
+  if (!get_args(env, info, 7, a) || !get_bytes(env, a[5], &out, &no)) return NULL;
+  const rt_volume_desc* desc = get_volume_desc(env, a[1], &n);
+  if (!desc) return NULL;
+  napi_get_value_bool(env, a[6], &want_stats);
+  if (no < n * sizeof(rt_probe_sh9)) {
+    napi_throw_range_error(env, NULL, "rtBakeVolume: out must hold 28 floats per probe");
+    return NULL;
+  }
+  rt_radiance_stats st;
+  const int rc = rt_bake_volume((rt_ctx*)get_ptr(env, a[0]), desc, get_u32(env, a[2]), get_u32(env, a[3]), get_u32(env, a[4]),
+                                (rt_probe_sh9*)out, want_stats ? &st : NULL);
+  if (rc < 0 || !want_stats) return make_int(env, rc);
+  return radiance_stats_object(env, &st);
+}
+/* (ctx, desc: 64 bytes, volume: Float32Array of 28 per probe, points: Float32Array of 8 per point, out: Float32Array of 4 per
+ * point) -> status */
+static napi_value rtSampleVolume(napi_env env, napi_callback_info info) {
+  napi_value a[5];
+  void *volume = NULL, *points = NULL, *out = NULL;
+  size_t n = 0, nv = 0, np = 0, no = 0;
+  if (!get_args(env, info, 5, a) || !get_bytes(env, a[2], &volume, &nv) || !get_bytes(env, a[3], &points, &np) ||
+      !get_bytes(env, a[4], &out, &no))
+    return NULL;
+  const rt_volume_desc* desc = get_volume_desc(env, a[1], &n);
+  if (!desc) return NULL;
+  const size_t m = np / sizeof(rt_gather_point);
+  if (nv < n * sizeof(rt_probe_sh9) || np % sizeof(rt_gather_point) != 0 || no < m * sizeof(rt_irradiance) || m > 0x7fffffffu) {
+    napi_throw_range_error(env, NULL, "rtSampleVolume: volume must hold 28 floats per probe, points 8 and out 4 floats per point");
+    return NULL;
+  }
+  return make_int(env, rt_sample_volume((rt_ctx*)get_ptr(env, a[0]), desc, (const rt_probe_sh9*)volume,
+                                        (const rt_gather_point*)points, (uint32_t)m, (rt_irradiance*)out));
+}
+/* (ctx, desc: 64 bytes, format, volume: Float32Array of 28 per probe, out: a typed array of seven layers) -> status */
+static napi_value rtEncodeVolume(napi_env env, napi_callback_info info) {
+  napi_value a[5];
+  void *volume = NULL, *out = NULL;
+  size_t n = 0, nv = 0, no = 0;
+  if (!get_args(env, info, 5, a) || !get_bytes(env, a[3], &volume, &nv) || !get_bytes(env, a[4], &out, &no)) return NULL;
+  const rt_volume_desc* desc = get_volume_desc(env, a[1], &n);
+  if (!desc) return NULL;
+  if (nv < n * sizeof(rt_probe_sh9)) {
+    napi_throw_range_error(env, NULL, "rtEncodeVolume: volume must hold 28 floats per probe");
+    return NULL;
+  }
+  return make_int(env, rt_encode_volume((rt_ctx*)get_ptr(env, a[0]), desc, get_u32(env, a[2]), (const rt_probe_sh9*)volume, out, no));
+}
+
 /* ------------------------------------------------------- directional gathers (rt_gather_directional, mi355rt.h) */
 /* (ctx, points: Float32Array of 8 per point {position, t_max, normal, pad}, maxDepth, spp, seed, out: Float32Array of 16 per
  * point, four rows {sh[k].rgb, hit_fraction}, wantStats) -> status, or the stats object when wantStats and the call succeeded */
@@ -970,6 +1039,7 @@ static napi_value Init(napi_env env, napi_value exports) {
                {"rtGatherStripes", rtGatherStripes}, {"rtReadDisplay", rtReadDisplay}, {"rtTraceRays", rtTraceRays},
                {"rtRayQueryStats", rtRayQueryStats}, {"rtTraceRadiance", rtTraceRadiance},
                {"rtGatherIrradiance", rtGatherIrradiance}, {"rtGatherProbes", rtGatherProbes}, {"rtBakePoints", rtBakePoints},
+               {"rtBakeVolume", rtBakeVolume}, {"rtSampleVolume", rtSampleVolume}, {"rtEncodeVolume", rtEncodeVolume},
                {"rtGatherDirectional", rtGatherDirectional}, {"rtBakeAtlasDirectionalLightmap", rtBakeAtlasDirectionalLightmap},
                {"rtBakeIrradiance", rtBakeIrradiance}, {"rtBakeAtlasPoints", rtBakeAtlasPoints},
                {"rtBakeAtlasIrradiance", rtBakeAtlasIrradiance}, {"rtDilateAtlas", rtDilateAtlas},

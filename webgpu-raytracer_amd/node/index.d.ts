@@ -71,6 +71,20 @@ export class WebGPURenderer {
    *  query's with rays = probes; kernel_ms counts the radiance launches only. */
   gatherProbes(probes: Float32Array, maxDepth: number, spp: number, opts?: { seed?: number; stats?: boolean }):
     { data: Float32Array; n: number; stats?: RadianceQueryStats };
+  /** Irradiance volumes (rt_bake_volume / rt_sample_volume / rt_encode_volume).  A descriptor is the 64 bytes of an
+   *  rt_volume_desc; probe (x, y, z) of the dims grid sits at origin + (x, y, z) * step and is record (z * ny + y) * nx + x. */
+  static volumeDesc(o: { origin: number[]; step: number[]; dims: number[]; window?: number[]; tMax?: number; padFirst?: number;
+    maxHitFraction?: number }): Uint8Array;
+  /** `data` holds 28 floats per probe: irradiance coefficients (the probe gather times the cosine-lobe band factors and the
+   *  window), then hitFraction.  The stats are the probe gather's. */
+  bakeVolume(desc: Uint8Array, maxDepth: number, spp: number, opts?: { seed?: number; stats?: boolean }):
+    { data: Float32Array; n: number; stats?: RadianceQueryStats };
+  /** points: 8 words per point {position, -, normal, -}.  `data` holds 4 floats per point {r, g, b, W}: the irradiance at the
+   *  normal from the eight surrounding valid probes and the valid share of the interpolation weight.  Needs no scene. */
+  sampleVolume(desc: Uint8Array, volume: Float32Array, points: Float32Array): { data: Float32Array; n: number };
+  /** Seven layers of n texels, layer j holding the floats 4 j .. 4 j + 3 of every record; 'rgbe' is refused. */
+  encodeVolume(desc: Uint8Array, volume: Float32Array, format: 'f32' | 'f16'):
+    { data: Float32Array | Uint16Array; layers: 7; n: number; format: string };
   /** Directional gathers (rt_gather_directional): points as for gatherIrradiance.  `data` holds 16 floats per point, four rows
    *  {sh[k].r, sh[k].g, sh[k].b, hitFraction}: the projection of the radiance arriving over spp uniform directions on the
    *  hemisphere of the normal onto Y0 and the y, z, x harmonics of band 1, in world space; row k is the texel of atlas layer k.

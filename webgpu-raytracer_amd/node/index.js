@@ -217,6 +217,51 @@ class WebGPURenderer {
     if (typeof r === 'object' && r) out.stats = r;
     return out;
   }
+  // ---- irradiance volumes (rt_bake_volume, rt_sample_volume, rt_encode_volume): a probe grid baked into windowed irradiance
+  // coefficients, sampled trilinearly and exported as texel layers, all on the device.  A descriptor is the 64 bytes of an
+  // rt_volume_desc, made by WebGPURenderer.volumeDesc({origin, step, dims: [nx, ny, nz], window = [1, 1, 1], tMax = 1e30,
+  // padFirst = 0, maxHitFraction = 1}); probe (x, y, z) is record (z * ny + y) * nx + x.
+  static volumeDesc(o) {
+    const buf = new ArrayBuffer(64), f = new Float32Array(buf), u = new Uint32Array(buf);
+    const window = o.window || [1, 1, 1];
+    for (let a = 0; a < 3; a++) { f[a] = o.origin[a]; f[4 + a] = o.step[a]; f[8 + a] = window[a]; u[3 + 4 * a] = o.dims[a] >>> 0; }
+    f[12] = o.tMax === undefined ? 1e30 : o.tMax;
+    u[13] = (o.padFirst || 0) >>> 0;
+    f[14] = o.maxHitFraction === undefined ? 1 : o.maxHitFraction;
+    return new Uint8Array(buf);
+  }
+  static _volumeProbes(desc) { const u = new Uint32Array(desc.buffer, desc.byteOffset, 16); return u[3] * u[7] * u[11]; }
+  // Result: 28 floats per probe in .data (irradiance coefficients sh'[k][c] at 3 k + c, then hitFraction), .n probes; opts:
+  // {seed = 0, stats = false}; the stats are the probe gather's.
+  bakeVolume(desc, maxDepth, spp, opts = {}) {
+    const n = WebGPURenderer._volumeProbes(desc);
+    const data = new Float32Array(n * 28);
+    const r = native.rtBakeVolume(this._ctx, desc, maxDepth >>> 0, spp >>> 0, (opts.seed || 0) >>> 0, data, !!opts.stats);
+    if (typeof r === 'number') this._check(r, 'bakeVolume');
+    const out = { data, n };
+    if (typeof r === 'object' && r) out.stats = r;
+    return out;
+  }
+  // volume: the .data of a bake; points: 8 words per point {position, -, normal, -}.  Result: 4 floats per point in .data {r, g,
+  // b, W}: the irradiance at the normal and the valid share of the interpolation weight.  Needs no scene.
+  sampleVolume(desc, volume, points) {
+    if (!(volume instanceof Float32Array) || volume.length !== WebGPURenderer._volumeProbes(desc) * 28) throw new TypeError('sampleVolume: a Float32Array of 28 floats per probe');
+    if (!(points instanceof Float32Array) || points.length % 8 !== 0) throw new TypeError('sampleVolume: a Float32Array of 8 floats per point');
+    const n = points.length / 8;
+    const data = new Float32Array(n * 4);
+    this._check(native.rtSampleVolume(this._ctx, desc, volume, points, data), 'sampleVolume');
+    return { data, n };
+  }
+  // The volume as seven layers of n texels, layer j holding the floats 4 j .. 4 j + 3 of every record: format 'f32' or 'f16'
+  // ('rgbe' is refused: coefficients are signed).  Result: {data, layers: 7, n, format}.
+  encodeVolume(desc, volume, format) {
+    const n = WebGPURenderer._volumeProbes(desc);
+    if (!(volume instanceof Float32Array) || volume.length !== n * 28) throw new TypeError('encodeVolume: a Float32Array of 28 floats per probe');
+    const f = WebGPURenderer._lightmapFormat(format);
+    const data = WebGPURenderer._lightmapArray(7 * n, f);
+    this._check(native.rtEncodeVolume(this._ctx, desc, f, volume, data), 'encodeVolume');
+    return { data, layers: 7, n, format: ['f32', 'f16', 'rgbe'][f] };
+  }
   // ---- directional gathers (rt_gather_directional): the radiance arriving at the caller's surface points, over spp directions
   // drawn uniformly on the hemisphere of the normal on the device, projected onto the four real spherical harmonics of bands 0
   // .. 1 in world space.  points as for gatherIrradiance.  opts: {seed = 0, stats = false}.  Result: 16 floats per point in

@@ -201,6 +201,13 @@ def load_library(path=None):
         "rt_gather_probes": (i32, [vp, vp, u32, u32, u32, u32, vp, vp]),
         "rt_gather_probes_device": (i32, [vp, vp, u32, u32, u32, u32, vp]),
         "rt_probe_gather_stats": (i32, [vp, vp]),
+        # irradiance volumes
+        "rt_bake_volume": (i32, [vp, vp, u32, u32, u32, vp, vp]),
+        "rt_bake_volume_device": (i32, [vp, vp, u32, u32, u32, vp]),
+        "rt_sample_volume": (i32, [vp, vp, vp, vp, u32, vp]),
+        "rt_sample_volume_device": (i32, [vp, vp, vp, vp, u32, vp]),
+        "rt_encode_volume": (i32, [vp, vp, u32, vp, vp, ctypes.c_size_t]),
+        "rt_encode_volume_device": (i32, [vp, vp, u32, vp, vp, ctypes.c_size_t]),
         # directional gathers
         "rt_gather_directional": (i32, [vp, vp, u32, u32, u32, u32, vp, vp]),
         "rt_gather_directional_device": (i32, [vp, vp, u32, u32, u32, u32, vp]),
@@ -252,6 +259,7 @@ EXPORTED_SYMBOLS = (
     "rt_trace_radiance rt_trace_radiance_device rt_radiance_query_stats "
     "rt_gather_irradiance rt_gather_irradiance_device rt_irradiance_gather_stats "
     "rt_gather_probes rt_gather_probes_device rt_probe_gather_stats "
+    "rt_bake_volume rt_bake_volume_device rt_sample_volume rt_sample_volume_device rt_encode_volume rt_encode_volume_device "
     "rt_gather_directional rt_gather_directional_device rt_directional_gather_stats "
     "rt_bake_points rt_bake_points_device rt_bake_irradiance "
     "rt_bake_atlas_points rt_bake_atlas_points_device rt_bake_atlas_irradiance "
@@ -322,6 +330,36 @@ def sh9_irradiance(sh, normals):
     2 pi / 3, pi / 4.  Pure numpy; no ringing filter."""
     c = np.asarray(sh, np.float64) * _SH9_BAND[:, None]
     return np.einsum("mk,...kc->...mc", sh9_basis(normals), c)
+
+
+# irradiance volumes: mirror of rt_volume_desc; a volume is a PROBE_SH9_DTYPE array (nz, ny, nx), a sample an IRRADIANCE_DTYPE
+VOLUME_DESC_DTYPE = np.dtype([("origin", np.float32, (3,)), ("nx", np.uint32), ("step", np.float32, (3,)), ("ny", np.uint32),
+                              ("window", np.float32, (3,)), ("nz", np.uint32), ("t_max", np.float32), ("pad_first", np.uint32),
+                              ("max_hit_fraction", np.float32), ("reserved", np.uint32)])
+
+
+def volume_desc(origin, step, dims, window=(1.0, 1.0, 1.0), t_max=1e30, pad_first=0, max_hit_fraction=1.0):
+    """A VOLUME_DESC_DTYPE record (shape ()): probe (x, y, z) of the dims = (nx, ny, nz) grid sits at origin + (x, y, z) * step
+    and is record (z * ny + y) * nx + x of the volume.  window: the per-band scale of the finish (sh_hanning_window, or (1, 1,
+    1) for none); max_hit_fraction: the sampler takes a probe as valid iff its hit_fraction is at most this."""
+    d = np.zeros((), VOLUME_DESC_DTYPE)
+    d["origin"], d["step"], d["window"] = origin, step, window
+    d["nx"], d["ny"], d["nz"] = dims
+    d["t_max"], d["pad_first"], d["max_hit_fraction"] = t_max, pad_first, max_hit_fraction
+    return d
+
+
+def sh_hanning_window(width):
+    """The Hanning window against SH ringing (Sloan 2008) for bands l = 0, 1, 2: (1 + cos(pi l / width)) / 2 as three float32,
+    for the window field of a volume descriptor.  Pure numpy."""
+    return ((1.0 + np.cos(np.pi * np.arange(3) / float(width))) / 2.0).astype(np.float32)
+
+
+def _volume_desc(desc):
+    d = np.ascontiguousarray(desc)
+    if d.dtype != VOLUME_DESC_DTYPE or d.size != 1:
+        raise ValueError("a volume descriptor is one VOLUME_DESC_DTYPE record (volume_desc builds it)")
+    return d.reshape(())
 
 
 # directional gathers: mirror of rt_directional; points are rt_gather_point, stats an RtRadianceStats (rays = points)
@@ -778,6 +816,68 @@ class WebGPURenderer:
         st = RtRadianceStats()
         self._check(self.L.rt_probe_gather_stats(self.ctx, ctypes.addressof(st)), "probeGatherStats")
         return st.as_dict()
+
+    # ---- irradiance volumes: a probe grid baked, sampled and exported on the device (rt_bake_volume, rt_sample_volume) ----
+    def bakeVolume(self, desc, max_depth, spp, seed=0, stats=False):
+        """desc: a VOLUME_DESC_DTYPE record (volume_desc).  Returns the volume, a PROBE_SH9_DTYPE array (nz, ny, nx) of
+        IRRADIANCE coefficients (the probe gather of the grid's probes, times the cosine-lobe band factors and desc's window;
+        hit_fraction untouched) - and with stats=True the pair (volume, stats dict of the probe gather: the counting kernel
+        runs).  probeGatherStats reports a bake like a gather."""
+        d = _volume_desc(desc)
+        out = np.empty((int(d["nz"]), int(d["ny"]), int(d["nx"])), dtype=PROBE_SH9_DTYPE)
+        st = RtRadianceStats()
+        self._check(self.L.rt_bake_volume(self.ctx, _ptr(d), int(max_depth), int(spp), int(seed) & 0xffffffff,
+                                          _ptr(out) if out.size else None, ctypes.addressof(st) if stats else None), "bakeVolume")
+        return (out, st.as_dict()) if stats else out
+
+    def bakeVolumeDevice(self, desc, out_ptr, max_depth, spp, seed=0):
+        """Enqueue a bake into the nx * ny * nz rt_probe_sh9 records (112 bytes each) at the device pointer out_ptr on the
+        context's stream; no host synchronisation."""
+        d = _volume_desc(desc)
+        self._check(self.L.rt_bake_volume_device(self.ctx, _ptr(d), int(max_depth), int(spp), int(seed) & 0xffffffff,
+                                                 ctypes.c_void_p(out_ptr or 0)), "bakeVolumeDevice")
+
+    def sampleVolume(self, desc, volume, points):
+        """volume: the PROBE_SH9_DTYPE array of a bake (or (n, 28) float32); points: (n, 8) float32 in the rt_gather_point
+        layout {position, -, normal, -}.  Returns an IRRADIANCE_DTYPE array (n,): rgb the irradiance E(normal) interpolated
+        from the eight surrounding valid probes, clamped at 0, hit_fraction the valid share of the interpolation weight.  Needs
+        no scene.  Uploads the volume on every call: a caller sampling every frame keeps it on the device and uses
+        sampleVolumeDevice."""
+        d = _volume_desc(desc)
+        v = np.ascontiguousarray(volume)
+        if v.dtype != PROBE_SH9_DTYPE:
+            v = np.ascontiguousarray(v, dtype=np.float32).reshape(-1, 28)
+        if v.size * v.dtype.itemsize != 112 * int(d["nx"]) * int(d["ny"]) * int(d["nz"]):
+            raise ValueError("sampleVolume: the volume does not hold nx * ny * nz records")
+        p = np.ascontiguousarray(points, dtype=np.float32)
+        if p.ndim != 2 or p.shape[1] != 8:
+            raise ValueError("sampleVolume expects an (n, 8) float32 array of points")
+        out = np.empty(p.shape[0], dtype=IRRADIANCE_DTYPE)
+        self._check(self.L.rt_sample_volume(self.ctx, _ptr(d), _ptr(v), _ptr(p) if p.size else None, p.shape[0],
+                                            _ptr(out) if out.size else None), "sampleVolume")
+        return out
+
+    def sampleVolumeDevice(self, desc, volume_ptr, points_ptr, n, out_ptr):
+        """Enqueue the sampling of n rt_gather_point at points_ptr from the volume at volume_ptr into n rt_irradiance at
+        out_ptr (device pointers, 16-byte aligned) on the context's stream; no host synchronisation."""
+        d = _volume_desc(desc)
+        self._check(self.L.rt_sample_volume_device(self.ctx, _ptr(d), ctypes.c_void_p(volume_ptr or 0),
+                                                   ctypes.c_void_p(points_ptr or 0), int(n), ctypes.c_void_p(out_ptr or 0)),
+                    "sampleVolumeDevice")
+
+    def encodeVolume(self, desc, volume, format):
+        """The volume as seven texel layers for a 3D-texture upload: (7, nz, ny, nx, 4) float32 ("f32") or float16 ("f16"),
+        layer j holding the floats 4 j .. 4 j + 3 of every record.  "rgbe" is refused: coefficients are signed."""
+        d = _volume_desc(desc)
+        v = np.ascontiguousarray(volume)
+        if v.dtype != PROBE_SH9_DTYPE:
+            v = np.ascontiguousarray(v, dtype=np.float32).reshape(-1, 28)
+        if v.size * v.dtype.itemsize != 112 * int(d["nx"]) * int(d["ny"]) * int(d["nz"]):
+            raise ValueError("encodeVolume: the volume does not hold nx * ny * nz records")
+        fmt = _lightmap_format(format)
+        out = np.empty((7, int(d["nz"]), int(d["ny"]), int(d["nx"]), 4), np.float16 if fmt == RT_LIGHTMAP_F16 else np.float32)
+        self._check(self.L.rt_encode_volume(self.ctx, _ptr(d), fmt, _ptr(v), _ptr(out), out.nbytes), "encodeVolume")
+        return out
 
     # ---- directional gathers: SH radiance of bands 0 .. 1 over the hemisphere of surface points (rt_gather_directional) ----
     def gatherDirectional(self, points, max_depth, spp, seed=0, stats=False):
