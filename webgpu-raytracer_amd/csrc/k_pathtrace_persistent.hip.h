@@ -104,6 +104,14 @@ __global__ __launch_bounds__(64 * RT_PT_WAVES, RT_PT_SIMD_WAVES) void RT_PT_KERN
   // wave-uniform work cursor: pixels [tile_pos, 64) of the wave's tile are still unassigned; the tile's origin and frame are
   // worked out once per ticket (two divisions by run-time values, 20 instructions each: not once per regenerated lane)
   uint32_t tile_pos = 64u, tile_x0 = 0u, tile_y0 = 0u, tile_slot = 0u;
+  // PREPASS (the wide one-leaf form): the cursor is a lane mask instead, bit i set while slot i of the wave's tile is a pixel
+  // with a path to trace that no lane has taken yet (part (a) below).  The 256-thread one-leaf forms hold their registers
+  // with it too, but a single-frame dispatch has 1.3 tickets per wave and the Cornell live loop without lookahead did not
+  // gain (0.874 -> 0.880 ms per frame, one run each): they keep the cursor.
+  constexpr bool PREPASS = LEAN && SLIM;
+  unsigned long long tile_live = 0ull;
+  uint32_t tile_xy0 = 0u;   // PREPASS: the tile's origin, x0 | y0 << 16
+  uint32_t ticket_next = 0xffffffffu;   // PREPASS: the second ticket of the pair the wave drew, or none
   bool work_left = true;
 
   PathState p = idle_path();
@@ -131,7 +139,94 @@ __global__ __launch_bounds__(64 * RT_PT_WAVES, RT_PT_SIMD_WAVES) void RT_PT_KERN
     //     slot is outside the image or the rank's rows.  A background sample draws no random number, traces nothing and
     //     counts nothing, and +0 summed over the samples is +0, so the pixel gets the bits it got from a lane trip per
     //     sample.
-    {
+    //     PREPASS: the depth test is made once per ticket for the whole tile, not once per refill for the slots the refill
+    //     reaches.  When the wave takes a ticket, lane i stands for slot i of the tile: it reads its own pixel's depth (one
+    //     coalesced load per tile row), finishes the pixel there if it is background, and the wave keeps the ballot of the
+    //     others in tile_live.  A refill hands the r-th set bit of tile_live to the r-th needy lane and clears the bits it
+    //     handed out; it issues no global load and goes round the loop only when a tile runs out while lanes are needy.
+    //     The image cannot change: which lane traces a pixel has no effect on the result (the RNG is seeded from pixel,
+    //     frame and sample; the parked sums are private to a lane; the counters are sums); a background pixel draws
+    //     nothing, traces nothing, counts nothing and gets the same {+0, +0, +0, 1} at the same address whichever lane
+    //     stores it; a batched dispatch writes frame_col, a single one adds +0 to accum or overwrites it: both per pixel.
+    if constexpr (PREPASS) {
+      bool need = !alive && !have_pixel;
+      for (;;) {
+        const unsigned long long mask = __ballot(need);
+        if (mask == 0ull || !work_left) break;
+        if (tile_live == 0ull) {
+          // tickets are drawn two at a time, half the atomic round trips: the second waits in ticket_next and is range-checked
+          // like the first when its turn comes (a launch has far fewer than 2^32 - 1 tickets, the value that says "none")
+          uint32_t t = ticket_next;
+          ticket_next = 0xffffffffu;
+          if (t == 0xffffffffu) {
+            const int leader = __builtin_ctzll(mask);
+            if (lane == (uint32_t)leader) t = atomicAdd(ticket, 2u);
+            t = __builtin_amdgcn_readlane(t, leader);
+            ticket_next = t + 1u;
+          }
+          if (t >= n_tiles * n_slots) {
+            work_left = false;
+            break;
+          }
+          // frame-major ticket: frame = t / n_tiles, tile = t % n_tiles
+          tile_slot = t / n_tiles;
+          const uint32_t tile_in_frame = t - tile_slot * n_tiles;
+          uint32_t trow = tile_in_frame / tiles_x;
+          const uint32_t tx0 = (tile_in_frame - trow * tiles_x) * 8u;
+          if (F.own_period) trow = (trow / F.own_run) * F.own_period + F.own_first + (trow % F.own_run);
+          // the origin as x0 | y0 << 16, one scalar register (width, height <= 65535: rt_resize refuses more; x0 + 7 and
+          // y0 + 7 stay below 65536, so a slot's offset adds to the pair without a carry between the halves)
+          tile_xy0 = tx0 | (trow * 8u) << 16;
+          // the tile's prepass: lane i looks at slot i (the lane number taken as new: what is computed from it here is not
+          // carried in registers through the trip)
+          uint32_t slot_of_lane = lane;
+          asm volatile("" : "+v"(slot_of_lane));
+          const uint32_t xy = tile_xy0 + ((slot_of_lane & 7u) | (slot_of_lane >> 3) << 16);
+          const uint32_t x = xy & 0xffffu, y = xy >> 16;
+          bool live = false;
+          if (x < U.width && y < U.height && owns_row(fresh_stripes(F), y)) {
+            const uint32_t pixel = y * rt_fresh(U.width) + x;
+            // (MAX_DEPTH taken as new and the depth plane named global memory, as in the cursor form below)
+            const float gdepth = __builtin_bit_cast(float, ld_g32(reinterpret_cast<const uint32_t*>(slots[tile_slot].depth), pixel));
+            if (!(gdepth >= 1.0f) && rt_fresh(F.max_depth) != 0u) {   // (this form of the test: a NaN depth is live)
+              live = true;
+            } else {
+              finish_black_pixel(F, U, slots, tile_slot, pixel);
+            }
+          }
+          tile_live = __ballot(live);
+          if (tile_live == 0ull) continue;   // nothing to trace in this tile: the next ticket
+        }
+        // The r-th needy lane takes the r-th live slot.  The live slots' numbers go through the start of the wave's triangle
+        // queue (WW.items), which is idle outside the walks: the lane that stands for the j-th set bit of tile_live writes
+        // its number to word j, the needy lane of rank r reads word r.  (The LDS executes a wave's instructions in order.)
+        const uint32_t rank =
+            __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+        const uint32_t ord =
+            __builtin_amdgcn_mbcnt_hi((uint32_t)(tile_live >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)tile_live, 0u));
+        const uint32_t n_live = (uint32_t)__builtin_popcountll(tile_live);
+        __builtin_amdgcn_wave_barrier();
+        if (__builtin_amdgcn_inverse_ballot_w64(tile_live)) ((rt_lptr32_ordered)WW.items)[ord] = lane;
+        // the lowest min(needy lanes, live slots) set bits are handed out (a lane without a live slot clears no bit)
+        tile_live &= ~__ballot(ord < (uint32_t)__builtin_popcountll(mask));
+        __builtin_amdgcn_wave_barrier();
+        if (need && rank < n_live) {
+          const uint32_t slot = ld_l32(WW.items, rank);
+          need = false;
+          have_pixel = true;
+          pixel_xy = tile_xy0 + ((slot & 7u) | (slot >> 3) << 16);
+          if constexpr (!SLIM) p.pixel = (pixel_xy >> 16) * U.width + (pixel_xy & 0xffffu);
+          p.sample = 0u;
+          item_slot = tile_slot;
+          if constexpr (SLIM) {
+            col_park_clear<WAVES>(s_scene);
+          } else {
+            p.col = rt3_splat(0.0f);
+          }
+        }
+        __builtin_amdgcn_wave_barrier();
+      }
+    } else {
       bool need = !alive && !have_pixel;
       for (;;) {
         const unsigned long long mask = __ballot(need);
