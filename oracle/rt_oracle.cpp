@@ -1320,6 +1320,34 @@ void oracle_set_node_histogram(oracle_ctx* c, uint32_t* hist) {
 // ---- unit-level entry points for known-answer tests ----
 uint32_t oracle_init_rng(uint32_t pixel_idx, uint32_t frame) { return Oracle::init_rng(pixel_idx, frame); }
 float oracle_rand_pcg(uint32_t* state) { return Oracle::rand_pcg(state); }
+// The two RNG functions in bulk, for tests/test_gpu_math.py (the device's init_rng / rand_pcg against these over whole input
+// sets).  init_rng of n (pixel, frame) pairs; and rand_pcg from every state of [first, first + count) as one checksum: state
+// s gives two words, the bits of the float (k = 2 s) and the state it leaves (k = 2 s + 1), each added as word * (2 k + 1)
+// mod 2^64.
+void oracle_init_rng_array(const uint32_t* pixel_idx, const uint32_t* frame, uint32_t n, uint32_t* out) {
+  for (uint32_t k = 0; k < n; k++) out[k] = Oracle::init_rng(pixel_idx[k], frame[k]);
+}
+uint64_t oracle_rand_pcg_checksum(uint64_t first, uint64_t count, int threads) {
+  if (threads < 1) threads = 1;
+  std::vector<uint64_t> part((size_t)threads, 0);
+  std::vector<std::thread> pool;
+  for (int t = 0; t < threads; t++)
+    pool.emplace_back([&part, first, count, threads, t]() {
+      const uint64_t lo = first + (uint64_t)((unsigned __int128)count * (unsigned)t / (unsigned)threads);
+      const uint64_t hi = first + (uint64_t)((unsigned __int128)count * (unsigned)(t + 1) / (unsigned)threads);
+      uint64_t sum = 0;
+      for (uint64_t s = lo; s < hi; s++) {
+        uint32_t state = (uint32_t)s;
+        const float r = Oracle::rand_pcg(&state);
+        sum += (uint64_t)rt_f2u(r) * (2u * (2u * s) + 1u) + (uint64_t)state * (2u * (2u * s + 1u) + 1u);
+      }
+      part[(size_t)t] = sum;
+    });
+  for (auto& th : pool) th.join();
+  uint64_t sum = 0;
+  for (uint64_t p : part) sum += p;
+  return sum;
+}
 double oracle_halton(uint32_t index, uint32_t base) { return Oracle::halton(index, base); }
 void oracle_sincos(float x, float* s, float* c) { rt_sincos(x, s, c); }
 float oracle_exp(float x) { return rt_exp(x); }

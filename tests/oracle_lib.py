@@ -54,6 +54,10 @@ def lib():
         L.oracle_init_rng.argtypes = [u32, u32]
         L.oracle_rand_pcg.restype = f32
         L.oracle_rand_pcg.argtypes = [ctypes.POINTER(u32)]
+        L.oracle_init_rng_array.restype = None
+        L.oracle_init_rng_array.argtypes = [vp, vp, u32, vp]
+        L.oracle_rand_pcg_checksum.restype = ctypes.c_uint64
+        L.oracle_rand_pcg_checksum.argtypes = [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int]
         L.oracle_halton.restype = ctypes.c_double
         L.oracle_halton.argtypes = [u32, u32]
         L.oracle_sincos.argtypes = [f32, ctypes.POINTER(f32), ctypes.POINTER(f32)]
