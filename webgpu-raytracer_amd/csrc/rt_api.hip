@@ -26,6 +26,7 @@
 #include "../../include/mi355rt.h"
 #include "kernels.hip.h"
 #include "launch_plan.h"
+#include "device_owned.h"
 #include "bvh_build.hip.h"
 #include "world_update.hip.h"
 #include "k_ieee_check.hip.h"
@@ -34,17 +35,9 @@ namespace lp = launch_plan;
 
 namespace {
 
+using namespace owned;   // DeviceBuffer, Event, EventPair, Pinned, Stream
+
 std::string g_create_error;
-
-struct DeviceBuffer {
-  void* ptr = nullptr;
-  size_t capacity = 0;  // bytes allocated
-  size_t size = 0;      // bytes in use
-};
-
-struct EventPair {
-  hipEvent_t a, b;
-};
 
 // A kernel prepared for a launch (resident_blocks): the workgroup size and dynamic LDS its attribute was last set for, and
 // the workgroups of that shape a CU holds.  One entry per function.
@@ -60,8 +53,10 @@ struct PreparedKernel {
 // events around its last launch.
 struct QueryState {
   DeviceBuffer in, out, counters;
-  hipEvent_t ev[2] = {nullptr, nullptr};
+  EventPair ev;
   bool timed = false;               // the last query recorded its events
+  std::deque<EventPair> batch_ev;   // composed gathers launch once per batch, each between a pair of its own (deque: a pair never moves)
+  uint32_t batches_timed = 0;       // ... and the batches of the last call that recorded theirs
 };
 
 // What lightmap bakes (rt_bake_points, rt_bake_irradiance and their atlas forms) keep between calls: their staging arrays,
@@ -75,9 +70,9 @@ struct BakeState {
   // pinned staging ring of the entry lists: the copy to `entries` is truly asynchronous and its source outlives it (buffer k
   // is reused only after the event recorded behind its copy has completed)
   static constexpr int kEntryRing = 4;
-  void* ring[kEntryRing] = {};
+  Pinned ring[kEntryRing];
   size_t ring_bytes[kEntryRing] = {};
-  hipEvent_t ring_ev[kEntryRing] = {};
+  Event ring_ev[kEntryRing];
   bool ring_used[kEntryRing] = {};
   int ring_next = 0;
 };
@@ -111,13 +106,14 @@ struct VolumeState {
 
 struct rt_ctx {
   int device = 0;
-  hipStream_t own_stream = nullptr;
-  hipStream_t stream = nullptr;
+  // the streams come before every buffer and event: members go in reverse order of declaration, so they go last
+  Stream own_stream;
+  hipStream_t stream = nullptr;   // own_stream, or the caller's (rt_set_stream)
   // wavefront form: the any-hit trace of a depth runs on `side_stream` beside the closest-hit trace on `stream` (the two
   // read the same shade output and write different result arrays), so the drain tail of one — a few long rays stepping
   // alone — is filled by the other.  MI355RT_WF_OVERLAP=0 puts both on `stream` again.
-  hipStream_t side_stream = nullptr;
-  hipEvent_t side_fork = nullptr, side_join = nullptr;
+  Stream side_stream;
+  Event side_fork, side_join;
   bool wf_overlap = true;
   int shade_per_cu = 8;          // workgroups per CU of the wavefront shade kernels (MI355RT_SHADE_BLOCKS_PER_CU); swept 4 / 8 /
                                  // 12 / 16 / 24, shade ms per image: sponza-like 64.6 / 63.9 / 63.9 / 64.3 / 64.7, instanced x1000
@@ -127,7 +123,7 @@ struct rt_ctx {
   // scene buffers (raw bridge layout)
   DeviceBuffer topology, instances, lights, draw_commands, pos, nrm, uv, nodes, textures, tex_staging;
   uint32_t bv_levels = 0, bv_big_levels = 0, bv_last_tris = 0, bv_gen = 0;   // depth of the last rt_build_blas tree: how many levels the next build launches
-  void* bv_pinned = nullptr;  // 64 KB of pinned host memory for the read-back of the build's bookkeeping
+  Pinned bv_pinned;           // 64 KB of pinned host memory for the read-back of the build's bookkeeping
   DeviceBuffer bv_in, bv_tri, bv_order, bv_nodes, bv_out, bv_counters, bv_big;  // BLAS build work space
   // device-resident World::update(t) (rt_world_update, csrc/world_update.hip.h)
   struct {
@@ -139,7 +135,7 @@ struct rt_ctx {
     std::vector<uint32_t> inst_geom;
     uint32_t n_joints = 0, n_verts = 0, n_tris = 0, n_lights = 0, n_tlas = 0, n_inst = 0, n_skins = 0;
     DeviceBuffer stat, joints, raw_inst, geom_rows, node_base, em_flag, em_list, em_blk, tlas_scratch, stats;
-    void* pinned = nullptr;               // joint-matrix staging and the end-of-update read-back
+    Pinned pinned;                        // joint-matrix staging and the end-of-update read-back
     size_t pinned_bytes = 0;
     wu::TlasArgs tlas;
     // static-geometry cache: a geometry without a skin has the same BLAS in every frame of a static description
@@ -149,7 +145,7 @@ struct rt_ctx {
     double last_ms = 0;                   // stream time of the last update (rt_world_last_ms)
     double last_tlas_ms = 0;              // ... of its k_tlas launch alone (rt_world_last_tlas_ms)
     bool tlas_lds_set = false;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr, ev_t0 = nullptr, ev_t1 = nullptr;
+    Event ev0, ev1, ev_t0, ev_t1;
   } world;
   // derived buffers (device_scene.h)
   DeviceBuffer tri_geom, tri_shade, inst_trav, light_rec;
@@ -213,8 +209,8 @@ struct rt_ctx {
   // pinned staging ring for the slot tables: the H2D copy of a dispatch's table is truly asynchronous and its source
   // outlives it (entry k is reused only after the event recorded behind its copy has completed)
   static constexpr int kSlotRing = 8;
-  DevFrameSlot* slot_ring = nullptr;   // kSlotRing x 64 slots, hipHostMalloc
-  hipEvent_t slot_ring_ev[kSlotRing] = {};
+  Pinned slot_ring;                    // kSlotRing x 64 DevFrameSlot
+  Event slot_ring_ev[kSlotRing];
   bool slot_ring_used[kSlotRing] = {};
   int slot_ring_next = 0;
   // Speculative lookahead of the live loop (rt_set_lookahead): a compute(f) that continues a run f-1, f traces the frames
@@ -248,20 +244,15 @@ struct rt_ctx {
   rt_radiance_stats rd_last = {};
   rt_radiance_stats gi_last = {};
   // probe gathers (rt_gather_probes): a path-query kind of their own (its QueryState: the host entry's staging, the counter
-  // shards of the radiance launches), the scratch of a batch (one rt_ray and one rt_radiance per sample, kept and grown)
-  // and an event pair per radiance launch of the last call
+  // shards of the radiance launches, an event pair per radiance launch of the last call) and the scratch of a batch (one
+  // rt_ray and one rt_radiance per sample, kept and grown)
   QueryState pr;
   rt_radiance_stats pr_last = {};
   DeviceBuffer pr_rays, pr_rad;
-  std::vector<hipEvent_t> pr_ev;    // 2 per batch
-  uint32_t pr_timed = 0;            // batches of the last call that recorded their events
   // directional gathers (rt_gather_directional): the same composition at surface points, a path-query kind and a state of
-  // its own (staging, counter shards, an event pair per radiance launch); the scratch of a batch is the probe gather's,
-  // pr_rays / pr_rad, both being per-call scratch on the one stream
+  // its own; the scratch of a batch is the probe gather's, pr_rays / pr_rad, both being per-call scratch on the one stream
   QueryState dg;
   rt_radiance_stats dg_last = {};
-  std::vector<hipEvent_t> dg_ev;    // 2 per batch
-  uint32_t dg_timed = 0;
   // directional bakes (rt_bake_atlas_directional, _lightmap): the gather's results, the four scattered layers and the four
   // encoded layers, kept and grown
   DeviceBuffer db_results, db_layers, db_encoded;
@@ -320,10 +311,6 @@ int ensure_buffer(rt_ctx* c, DeviceBuffer& b, size_t bytes, bool grow_policy) {
   HIP_TRY(c, hipMalloc(&b.ptr, cap + 16));
   b.capacity = cap;
   return 1;
-}
-void free_buffer(DeviceBuffer& b) {
-  if (b.ptr) (void)hipFree(b.ptr);
-  b = DeviceBuffer();
 }
 int upload(rt_ctx* c, DeviceBuffer& b, const void* src, size_t bytes) {
   int r = ensure_buffer(c, b, bytes, true);
@@ -467,9 +454,9 @@ rtk::StripePlan dist_plan(const rt_ctx* c) {
 }
 size_t dist_block_bytes(const rt_ctx* c) { return (size_t)c->dist.max_rows * c->width * 16; }
 void dist_free_buffers(rt_ctx* c) {
-  free_buffer(c->dist.send);
-  free_buffer(c->dist.recv);
-  free_buffer(c->dist.display);
+  c->dist.send.reset();
+  c->dist.recv.reset();
+  c->dist.display.reset();
   c->dist.max_rows = 0;
 }
 // (Re)allocate a rank's buffers for the current screen, zeroed; the stream is idle on return.
@@ -760,9 +747,11 @@ DevScene dev_scene(const rt_ctx* c) {
 EventPair* next_events(rt_ctx* c, int tag) {
   if (!c->timing) return nullptr;
   if (c->ev_used == c->ev_pool.size()) {
-    EventPair p;
-    if (hipEventCreate(&p.a) != hipSuccess || hipEventCreate(&p.b) != hipSuccess) return nullptr;
-    c->ev_pool.push_back(p);
+    EventPair& p = c->ev_pool.emplace_back();
+    if (hipEventCreate(&p.a) != hipSuccess || hipEventCreate(&p.b) != hipSuccess) {
+      c->ev_pool.pop_back();
+      return nullptr;
+    }
   }
   c->ev_tags.emplace_back(c->ev_used, tag);
   return &c->ev_pool[c->ev_used++];
@@ -845,19 +834,15 @@ int query_reset_counters(rt_ctx* c, QueryState& q, uint64_t** counters, uint32_t
   *head = (uint32_t*)((char*)q.counters.ptr + counter_bytes);
   return RT_OK;
 }
-// the query kernel (256-thread workgroups) on the context's stream, between the query's events when timing is on
-int query_launch(rt_ctx* c, QueryState& q, const void* fn, uint32_t blocks, void** args, size_t dyn) {
-  q.timed = false;
+// the query kernel (256-thread workgroups) on the context's stream, between the events of `ev` when timing is on
+int query_launch(rt_ctx* c, EventPair& ev, const void* fn, uint32_t blocks, void** args, size_t dyn) {
   if (c->timing) {
-    for (hipEvent_t& e : q.ev)
-      if (!e) HIP_TRY(c, hipEventCreate(&e));
-    HIP_TRY(c, hipEventRecord(q.ev[0], c->stream));
+    if (!ev.a) HIP_TRY(c, hipEventCreate(&ev.a));
+    if (!ev.b) HIP_TRY(c, hipEventCreate(&ev.b));
+    HIP_TRY(c, hipEventRecord(ev.a, c->stream));
   }
   HIP_TRY(c, hipLaunchKernel(fn, dim3(blocks), dim3(256), args, dyn, c->stream));
-  if (c->timing) {
-    HIP_TRY(c, hipEventRecord(q.ev[1], c->stream));
-    q.timed = true;
-  }
+  if (c->timing) HIP_TRY(c, hipEventRecord(ev.b, c->stream));
   return RT_OK;
 }
 // The six counters of the last query summed over their shards (all 0 when `launched` is false: no query yet, or an empty
@@ -872,7 +857,7 @@ int query_totals(rt_ctx* c, const QueryState& q, bool launched, uint64_t sum[6],
     for (int k = 0; k < 6; k++) sum[k] += host[s * 6 + k];
   if (q.timed) {
     float ms = 0.0f;
-    HIP_TRY(c, hipEventElapsedTime(&ms, q.ev[0], q.ev[1]));
+    HIP_TRY(c, hipEventElapsedTime(&ms, q.ev.a, q.ev.b));
     *kernel_ms = (double)ms;
   }
   return RT_OK;
@@ -943,9 +928,6 @@ rt_ctx* rt_create(int device_ordinal) {
       hipEventCreateWithFlags(&c->side_fork, hipEventDisableTiming) != hipSuccess ||
       hipEventCreateWithFlags(&c->side_join, hipEventDisableTiming) != hipSuccess) {
     g_create_error = "hipStreamCreate / hipEventCreate (side stream) failed";
-    if (c->side_fork) (void)hipEventDestroy(c->side_fork);
-    if (c->side_stream) (void)hipStreamDestroy(c->side_stream);
-    (void)hipStreamDestroy(c->own_stream);
     delete c;
     return nullptr;
   }
@@ -967,7 +949,6 @@ rt_ctx* rt_create(int device_ordinal) {
   // counters: 2 banks (primary kernel, path-trace kernel) x RT_COUNTER_SHARDS x 6 u64
   if (hipMalloc(&c->counters.ptr, 2 * RT_COUNTER_SHARDS * 6 * sizeof(uint64_t)) != hipSuccess) {
     g_create_error = "hipMalloc(counters) failed";
-    (void)hipStreamDestroy(c->own_stream);
     delete c;
     return nullptr;
   }
@@ -993,57 +974,7 @@ void rt_destroy(rt_ctx* c) {
   (void)hipSetDevice(c->device);
   (void)hipStreamSynchronize(c->stream);
   dist_release(c);
-  DeviceBuffer* all[] = {&c->topology, &c->instances, &c->lights, &c->draw_commands, &c->pos, &c->nrm, &c->uv,
-                         &c->nodes, &c->textures, &c->tri_geom, &c->tri_shade, &c->inst_trav, &c->light_rec, &c->tri_shade_w,
-                         &c->accum, &c->render_target,
-                         &c->g_normal, &c->g_depth, &c->history[0], &c->history[1], &c->counters, &c->ticket,
-                         &c->slots, &c->gbuf_batch, &c->frame_col, &c->wf_state, &c->wf_queues, &c->wf_counters,
-                         &c->rq.in, &c->rq.out, &c->rq.counters, &c->rd.in, &c->rd.out, &c->rd.counters,
-                         &c->gi.in, &c->gi.out, &c->gi.counters,
-                         &c->pr.in, &c->pr.out, &c->pr.counters, &c->pr_rays, &c->pr_rad,
-                         &c->dg.in, &c->dg.out, &c->dg.counters, &c->db_results, &c->db_layers, &c->db_encoded,
-                         &c->bk.uv, &c->bk.owner, &c->bk.blocks, &c->bk.count, &c->bk.points, &c->bk.texels, &c->bk.results,
-                         &c->bk.atlas, &c->bk.entries, &c->bk.items, &c->bk.owner64,
-                         &c->dl.atlas, &c->dl.filled, &c->dl.bitmap, &c->dl.src,
-                         &c->dn.index, &c->dn.scratch, &c->dn.in, &c->dn.out, &c->dn.points, &c->dn.texels,
-                         &c->lm.filtered, &c->lm.filled, &c->lm.encoded, &c->lm.in,
-                         &c->vol.volume, &c->vol.points, &c->vol.out, &c->vol.encoded,
-                         &c->tex_staging, &c->bv_in, &c->bv_tri, &c->bv_order, &c->bv_nodes, &c->bv_out,
-                         &c->bv_counters, &c->bv_big, &c->val_roots, &c->val_bad, &c->tnodes, &c->node_key, &c->node_newidx,
-                         &c->inst_root, &c->root_w, &c->treelet_work, &c->pairs, &c->pair_of, &c->pair_parent, &c->root_rec,
-                         &c->world.stat, &c->world.joints, &c->world.raw_inst, &c->world.geom_rows, &c->world.node_base,
-                         &c->world.em_flag, &c->world.em_list, &c->world.em_blk, &c->world.tlas_scratch, &c->world.stats,
-                         &c->world.static_nodes};
-  for (DeviceBuffer* b : all) free_buffer(*b);
-  if (c->world.pinned) (void)hipHostFree(c->world.pinned);
-  for (QueryState* q : {&c->rq, &c->rd, &c->gi})
-    for (hipEvent_t e : q->ev)
-      if (e) (void)hipEventDestroy(e);
-  for (hipEvent_t e : c->pr_ev)   // (c->pr.ev only borrows these)
-    if (e) (void)hipEventDestroy(e);
-  for (hipEvent_t e : c->dg_ev)   // (c->dg.ev likewise)
-    if (e) (void)hipEventDestroy(e);
-  if (c->world.ev0) (void)hipEventDestroy(c->world.ev0);
-  if (c->world.ev1) (void)hipEventDestroy(c->world.ev1);
-  if (c->world.ev_t0) (void)hipEventDestroy(c->world.ev_t0);
-  if (c->world.ev_t1) (void)hipEventDestroy(c->world.ev_t1);
-  for (EventPair& p : c->ev_pool) {
-    (void)hipEventDestroy(p.a);
-    (void)hipEventDestroy(p.b);
-  }
-  if (c->bv_pinned) (void)hipHostFree(c->bv_pinned);
-  for (int k = 0; k < BakeState::kEntryRing; k++) {
-    if (c->bk.ring[k]) (void)hipHostFree(c->bk.ring[k]);
-    if (c->bk.ring_ev[k]) (void)hipEventDestroy(c->bk.ring_ev[k]);
-  }
-  if (c->slot_ring) (void)hipHostFree(c->slot_ring);
-  for (int k = 0; k < rt_ctx::kSlotRing; k++)
-    if (c->slot_ring_ev[k]) (void)hipEventDestroy(c->slot_ring_ev[k]);
-  if (c->side_join) (void)hipEventDestroy(c->side_join);
-  if (c->side_fork) (void)hipEventDestroy(c->side_fork);
-  if (c->side_stream) (void)hipStreamDestroy(c->side_stream);
-  if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
-  delete c;
+  delete c;   // everything else goes with its owner (device_owned.h), the streams last
 }
 
 const char* rt_last_error(const rt_ctx* c) { return c ? c->error.c_str() : g_create_error.c_str(); }
@@ -1079,7 +1010,7 @@ int rt_resize(rt_ctx* c, uint32_t width, uint32_t height) {
   } items[] = {{&c->accum, n * 16}, {&c->render_target, n * 4}, {&c->g_normal, n * 16},
                {&c->g_depth, n * 4}, {&c->history[0], n * 8},   {&c->history[1], n * 8}};
   for (auto& it : items) {
-    free_buffer(*it.b);
+    it.b->reset();
     int r = ensure_buffer(c, *it.b, it.bytes, false);
     if (r < 0) return r;
     HIP_TRY(c, hipMemsetAsync(it.b->ptr, 0, it.bytes, c->stream));
@@ -1117,7 +1048,7 @@ int rt_upload_textures(rt_ctx* c, const uint8_t* rgba, uint32_t layers) {
   if (!rgba) return fail(c, RT_ERR_INVALID, "null texture data");
   const size_t bytes = (size_t)layers * RT_TEX_SIZE * RT_TEX_SIZE * 4;
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  free_buffer(c->textures);
+  c->textures.reset();
   int r = ensure_buffer(c, c->textures, bytes, false);
   if (r < 0) return r;
   HIP_TRY(c, hipMemcpyAsync(c->textures.ptr, rgba, bytes, hipMemcpyHostToDevice, c->stream));
@@ -1136,7 +1067,7 @@ int rt_alloc_texture_layers(rt_ctx* c, uint32_t layers) {
   }
   const size_t bytes = (size_t)layers * RT_TEX_SIZE * RT_TEX_SIZE * 4;
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  free_buffer(c->textures);
+  c->textures.reset();
   int r = ensure_buffer(c, c->textures, bytes, false);
   if (r < 0) return r;
   HIP_TRY(c, hipMemsetAsync(c->textures.ptr, 0xff, bytes, c->stream));
@@ -1305,7 +1236,7 @@ int rt_build_blas(rt_ctx* c, const float* verts4, uint32_t n_verts, const uint32
   HIP_TRY(c, hipMemcpyAsync(d_pos, verts4, (size_t)n_verts * 16, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(c, hipMemcpyAsync(d_idx, indices, n * 12, hipMemcpyHostToDevice, c->stream));
   if (!c->bv_pinned) HIP_TRY(c, hipHostMalloc(&c->bv_pinned, 1 << 16, hipHostMallocDefault));
-  bvhb::Ctl* ctl = (bvhb::Ctl*)c->bv_pinned;
+  bvhb::Ctl* ctl = (bvhb::Ctl*)c->bv_pinned.h;
   // as many levels as the last build of a mesh of this size needed (+ 2), else a guess; a deeper tree is built again
   uint32_t levels = (c->bv_levels && c->bv_last_tris == n_tris) ? c->bv_levels + 2u : blas_guess_levels(n_tris);
   uint32_t big_levels = (c->bv_levels && c->bv_last_tris == n_tris) ? c->bv_big_levels : blas_guess_big_levels(n_tris);
@@ -1540,14 +1471,13 @@ static int world_update_body(rt_ctx* c, const rt_world_frame* f, bool* touched) 
   const size_t rb_bytes = (((size_t)G + 1) * 4 + (size_t)G * 16 + 16 + 32 + 4095) & ~(size_t)4095;
   if (rb_bytes + joint_bytes > W.pinned_bytes) {
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (W.pinned) (void)hipHostFree(W.pinned);
-    W.pinned = nullptr;
+    (void)W.pinned.reset();
     W.pinned_bytes = 0;
     HIP_TRY(c, hipHostMalloc(&W.pinned, (rb_bytes + joint_bytes) * 2 + 65536, hipHostMallocDefault));
     W.pinned_bytes = (rb_bytes + joint_bytes) * 2 + 65536;
   }
-  char* pinned_rb = (char*)W.pinned;
-  char* pinned_joints = (char*)W.pinned + rb_bytes;
+  char* pinned_rb = (char*)W.pinned.h;
+  char* pinned_joints = (char*)W.pinned.h + rb_bytes;
   for (uint32_t g = 0; g < G; g++) {
     wu::Geom& D = W.geoms[g];
     if (D.skinned) {
@@ -1848,7 +1778,7 @@ int rt_upload(rt_ctx* c, rt_kind kind, const void* data, size_t bytes) {
       // not on the 1.5x policy in the reference (ResourceManager.ts:264-278); kept on the host too
       bool grew = !c->draw_commands.ptr || c->draw_commands.capacity < bytes;
       if (grew) {
-        free_buffer(c->draw_commands);
+        c->draw_commands.reset();
         r = ensure_buffer(c, c->draw_commands, bytes, false);
         if (r < 0) return r;
       }
@@ -2095,7 +2025,9 @@ static int launch_ray_query(rt_ctx* c, const void* d_rays, uint32_t n, int mode,
   A.n_inst = c->n_instances;
   DevScene S = dev_scene(c);
   void* args[] = {&S, &A, &shape.nplan, &shape.plan};
-  if ((r = query_launch(c, c->rq, fn, blocks, args, shape.dyn)) < 0) return r;
+  c->rq.timed = false;
+  if ((r = query_launch(c, c->rq.ev, fn, blocks, args, shape.dyn)) < 0) return r;
+  c->rq.timed = c->timing;
   c->rq_last = rt_ray_stats();
   c->rq_last.walk = shape.pairs ? 1u : 0u;
   c->rq_last.lds = shape.trace_lds ? 1u : 0u;
@@ -2178,9 +2110,10 @@ static const PathQueryKind pq_directional = {"directional gather", "points", RT_
 #undef RT_PQ_FNS
 
 // Enqueue one query on the context's stream: n > 0 items at d_items, results to d_out (device pointers).  keep_counts: a
-// later launch of the same call, whose counters add to those of the launches before it.
+// later launch of the same call, whose counters add to those of the launches before it.  batch_ev: the launch records into
+// this pair, which its caller keeps count of, instead of the state's own.
 static int launch_path_query(rt_ctx* c, const PathQueryKind& k, const void* d_items, uint32_t n, uint32_t max_depth, uint32_t spp,
-                             uint32_t seed, void* d_out, bool detail, bool keep_counts = false) {
+                             uint32_t seed, void* d_out, bool detail, bool keep_counts = false, EventPair* batch_ev = nullptr) {
   int r = query_scene_ready(c, k.what, true);
   if (r < 0) return r;
   // the persistent kernel's 256-thread forms without the one-leaf one
@@ -2192,8 +2125,9 @@ static int launch_path_query(rt_ctx* c, const PathQueryKind& k, const void* d_it
   if (getenv("MI355RT_DEBUG_SHAPE"))
     fprintf(stderr, "[mi355rt] %s: %s form, %zu bytes of LDS, resident workgroups per CU %d, %u workgroups\n", k.what,
             shape.lds ? "LDS" : "global", shape.dyn, per_cu, blocks);
+  QueryState& q = c->*k.state;
   rtk::PathQueryArgs A;
-  if ((r = query_reset_counters(c, c->*k.state, &A.counters, &A.head, keep_counts)) < 0) return r;
+  if ((r = query_reset_counters(c, q, &A.counters, &A.head, keep_counts)) < 0) return r;
   A.items = (const float4*)d_items;
   A.out = (float4*)d_out;
   A.n_items = n;
@@ -2208,7 +2142,9 @@ static int launch_path_query(rt_ctx* c, const PathQueryKind& k, const void* d_it
   A.n_verts = c->n_verts;
   DevScene S = dev_scene(c);
   void* args[] = {&S, &A, &shape.plan};
-  if ((r = query_launch(c, c->*k.state, fn, blocks, args, shape.dyn)) < 0) return r;
+  q.timed = false;
+  if ((r = query_launch(c, batch_ev ? *batch_ev : q.ev, fn, blocks, args, shape.dyn)) < 0) return r;
+  q.timed = c->timing && !batch_ev;
   rt_radiance_stats& last = c->*k.last;
   last = rt_radiance_stats();
   last.rays = n;
@@ -2299,17 +2235,15 @@ int rt_gather_irradiance(rt_ctx* c, const rt_gather_point* points, uint32_t n, u
 // Directional gathers (mi355rt.h "directional gathers") are the same composition at surface points, with k_dir_rays and
 // k_dir_project (k_directional.hip.h).  What a composed gather has of its own:
 struct ComposedGather {
-  const PathQueryKind& kind;                 // of its radiance launches: the state, the last stats
-  std::vector<hipEvent_t> rt_ctx::*ev;       // 2 per batch
-  uint32_t rt_ctx::*timed;                   // batches of the last call that recorded their events
+  const PathQueryKind& kind;                 // of its radiance launches: the state with a pair of events per batch, the last stats
   const void* rays_fn;                       // (items, rays, n_items, spp, seed), one thread per (item, sample)
   const void* project_fn;                    // (items, radiance, out, n, spp, seed), one wave per item
   uint32_t out_vec4;                         // float4 per result
 };
-static const ComposedGather cg_probe = {pq_probe, &rt_ctx::pr_ev, &rt_ctx::pr_timed, (const void*)rtk::k_probe_rays,
-                                        (const void*)rtk::k_probe_project, sizeof(rt_probe_sh9) / 16};
-static const ComposedGather cg_directional = {pq_directional, &rt_ctx::dg_ev, &rt_ctx::dg_timed, (const void*)rtk::k_dir_rays,
-                                              (const void*)rtk::k_dir_project, sizeof(rt_directional) / 16};
+static const ComposedGather cg_probe = {pq_probe, (const void*)rtk::k_probe_rays, (const void*)rtk::k_probe_project,
+                                        sizeof(rt_probe_sh9) / 16};
+static const ComposedGather cg_directional = {pq_directional, (const void*)rtk::k_dir_rays, (const void*)rtk::k_dir_project,
+                                              sizeof(rt_directional) / 16};
 static_assert(RT_DIRECTIONAL_BATCH_SAMPLES == RT_PROBE_BATCH_SAMPLES, "the two composed gathers share the scratch of a batch");
 
 static int launch_composed_gather(rt_ctx* c, const ComposedGather& g, const void* d_items, uint32_t n, uint32_t max_depth,
@@ -2322,9 +2256,8 @@ static int launch_composed_gather(rt_ctx* c, const ComposedGather& g, const void
   if ((r = ensure_buffer(c, c->pr_rays, scratch_items * sizeof(rt_ray), false)) < 0) return r;
   if ((r = ensure_buffer(c, c->pr_rad, scratch_items * sizeof(rt_radiance), false)) < 0) return r;
   QueryState& q = c->*k.state;
-  std::vector<hipEvent_t>& ev = c->*g.ev;
   rt_radiance_stats& last = c->*k.last;
-  c->*g.timed = 0;
+  q.batches_timed = 0;
   rt_radiance_stats total = rt_radiance_stats();
   uint32_t batch = 0;
   for (uint32_t first = 0; first < n; first += per_batch, batch++) {
@@ -2340,20 +2273,12 @@ static int launch_composed_gather(rt_ctx* c, const ComposedGather& g, const void
       HIP_TRY(c, hipLaunchKernel(g.rays_fn, dim3((items + 255u) / 256u), dim3(256), args, 0, c->stream));
     }
     // the radiance launch between this batch's own event pair
-    if (ev.size() < 2 * ((size_t)batch + 1)) ev.resize(2 * ((size_t)batch + 1), nullptr);
-    q.ev[0] = ev[2 * (size_t)batch];
-    q.ev[1] = ev[2 * (size_t)batch + 1];
-    r = launch_path_query(c, k, rays, items, max_depth, 1u, 0u, rad, detail, batch != 0);
-    ev[2 * (size_t)batch] = q.ev[0];
-    ev[2 * (size_t)batch + 1] = q.ev[1];
-    const bool timed = q.timed;
-    q.ev[0] = q.ev[1] = nullptr;
-    q.timed = false;
-    if (r < 0) {
+    if (q.batch_ev.size() <= batch) q.batch_ev.emplace_back();
+    if ((r = launch_path_query(c, k, rays, items, max_depth, 1u, 0u, rad, detail, batch != 0, &q.batch_ev[batch])) < 0) {
       last = rt_radiance_stats();
       return r;
     }
-    if (timed) c->*g.timed = batch + 1;
+    if (c->timing) q.batches_timed = batch + 1;
     total.lds = last.lds;
     total.workgroups += last.workgroups;
     {
@@ -2371,12 +2296,12 @@ static int launch_composed_gather(rt_ctx* c, const ComposedGather& g, const void
 
 static int composed_gather_stats(rt_ctx* c, const ComposedGather& g, rt_radiance_stats* out) {
   if (!c || !out) return RT_ERR_INVALID;
-  const int r = path_query_stats(c, g.kind, out);   // fences the stream; the state itself carries no events
+  const int r = path_query_stats(c, g.kind, out);   // fences the stream; the time is that of the batches
   if (r < 0) return r;
-  const std::vector<hipEvent_t>& ev = c->*g.ev;
-  for (uint32_t b = 0; b < c->*g.timed; b++) {
+  const QueryState& q = c->*g.kind.state;
+  for (uint32_t b = 0; b < q.batches_timed; b++) {
     float ms = 0.0f;
-    HIP_TRY(c, hipEventElapsedTime(&ms, ev[2 * (size_t)b], ev[2 * (size_t)b + 1]));
+    HIP_TRY(c, hipEventElapsedTime(&ms, q.batch_ev[b].a, q.batch_ev[b].b));
     out->kernel_ms += (double)ms;
   }
   return RT_OK;
@@ -2389,7 +2314,7 @@ static int composed_gather_device(rt_ctx* c, const ComposedGather& g, const void
   if (r < 0) return r;
   if (n == 0) {
     c->*g.kind.last = rt_radiance_stats();
-    c->*g.timed = 0;
+    (c->*g.kind.state).batches_timed = 0;
     return RT_OK;
   }
   if ((r = query_device_arrays_ok(c, g.kind.what, dev_items, dev_out)) < 0) return r;
@@ -2404,7 +2329,7 @@ static int composed_gather_host(rt_ctx* c, const ComposedGather& g, const void* 
   if (r < 0) return r;
   if (n == 0) {
     c->*g.kind.last = rt_radiance_stats();
-    c->*g.timed = 0;
+    (c->*g.kind.state).batches_timed = 0;
     if (stats) *stats = c->*g.kind.last;
     return RT_OK;
   }
@@ -2438,12 +2363,19 @@ int rt_gather_directional(rt_ctx* c, const rt_gather_point* points, uint32_t n, 
 }
 
 // ---- lightmap bakes: the texel rule of mi355rt.h as four launches (k_bake.hip.h), then the gather path and the scatter
+// the size of an atlas, refused under the caller's name `w`
+static int atlas_size_ok(rt_ctx* c, const std::string& w, uint32_t width, uint32_t height) {
+  if (width == 0 || height == 0) return fail(c, RT_ERR_INVALID, w + ": width and height must be >= 1");
+  if ((uint64_t)width * height > (1ull << 24)) return fail(c, RT_ERR_INVALID, w + ": width * height must be <= 2^24");
+  return RT_OK;
+}
+// a refusal of one of the stages of a composed entry, under the entry's name: "lightmap: bake atlas: entry 3: ..."
+static int refused_under(rt_ctx* c, const char* what, int code) { return fail(c, code, std::string(what) + ": " + c->error); }
 // width, height and pad_base of a bake or an atlas bake
 static int bake_size_ok(rt_ctx* c, const std::string& w, uint32_t width, uint32_t height, uint32_t pad_base) {
-  if (width == 0 || height == 0) return fail(c, RT_ERR_INVALID, w + ": width and height must be >= 1");
-  const uint64_t texels = (uint64_t)width * height;
-  if (texels > (1ull << 24)) return fail(c, RT_ERR_INVALID, w + ": width * height must be <= 2^24");
-  if ((uint64_t)pad_base + texels > (1ull << 31)) return fail(c, RT_ERR_INVALID, w + ": pad_base + width * height must be <= 2^31");
+  const int r = atlas_size_ok(c, w, width, height);
+  if (r < 0) return r;
+  if ((uint64_t)pad_base + (uint64_t)width * height > (1ull << 31)) return fail(c, RT_ERR_INVALID, w + ": pad_base + width * height must be <= 2^31");
   return RT_OK;
 }
 static int bake_desc_ok(rt_ctx* c, const rt_bake_desc* d) {
@@ -2701,8 +2633,7 @@ static int bake_atlas_stage_entries(rt_ctx* c, const rt_bake_rect* entries, uint
   if (!k.ring_ev[slot]) HIP_TRY(c, hipEventCreateWithFlags(&k.ring_ev[slot], hipEventDisableTiming));
   if (k.ring_used[slot]) HIP_TRY(c, hipEventSynchronize(k.ring_ev[slot]));
   if (k.ring_bytes[slot] < bytes) {
-    if (k.ring[slot]) HIP_TRY(c, hipHostFree(k.ring[slot]));
-    k.ring[slot] = nullptr;
+    HIP_TRY(c, k.ring[slot].reset());
     k.ring_bytes[slot] = 0;
     HIP_TRY(c, hipHostMalloc(&k.ring[slot], bytes + bytes / 2, hipHostMallocDefault));
     k.ring_bytes[slot] = bytes + bytes / 2;
@@ -2836,8 +2767,8 @@ static int dilate_desc_ok(rt_ctx* c, const rt_dilate_desc* d, const void* atlas)
   if (!atlas) return fail(c, RT_ERR_INVALID, w + ": NULL atlas");
   if (d->reserved[0] | d->reserved[1] | d->reserved[2] | d->reserved[3] | d->reserved[4])
     return fail(c, RT_ERR_INVALID, w + ": reserved words must be 0");
-  if (d->width == 0 || d->height == 0) return fail(c, RT_ERR_INVALID, w + ": width and height must be >= 1");
-  if ((uint64_t)d->width * d->height > (1ull << 24)) return fail(c, RT_ERR_INVALID, w + ": width * height must be <= 2^24");
+  const int r = atlas_size_ok(c, w, d->width, d->height);
+  if (r < 0) return r;
   if (d->radius > RT_DILATE_MAX_RADIUS) return fail(c, RT_ERR_INVALID, w + ": radius must be <= 24");
   return RT_OK;
 }
@@ -2906,8 +2837,8 @@ static int denoise_desc_ok(rt_ctx* c, const rt_denoise_desc* d, const void* in, 
   if (!d) return fail(c, RT_ERR_INVALID, w + ": NULL descriptor");
   if (!in || !out || (n != 0 && (!points || !texels))) return fail(c, RT_ERR_INVALID, w + ": NULL array");
   if (d->reserved[0]) return fail(c, RT_ERR_INVALID, w + ": reserved words must be 0");
-  if (d->width == 0 || d->height == 0) return fail(c, RT_ERR_INVALID, w + ": width and height must be >= 1");
-  if ((uint64_t)d->width * d->height > (1ull << 24)) return fail(c, RT_ERR_INVALID, w + ": width * height must be <= 2^24");
+  const int r = atlas_size_ok(c, w, d->width, d->height);
+  if (r < 0) return r;
   if (d->step == 0 || d->passes == 0) return fail(c, RT_ERR_INVALID, w + ": step and passes must be >= 1");
   // step >= 1, so more than three passes always exceed the limit; below that the shift cannot overflow
   if (d->passes > 3 || d->step > RT_DENOISE_MAX_STEP || (d->step << (d->passes - 1)) > RT_DENOISE_MAX_STEP)
@@ -3008,8 +2939,6 @@ static int launch_encode(rt_ctx* c, uint32_t texels, uint32_t format, const void
   HIP_TRY(c, hipGetLastError());
   return RT_OK;
 }
-// a refusal of one of the stages, under the lightmap's name: "lightmap: bake atlas: entry 3: ..."
-static int lightmap_refused(rt_ctx* c, int code) { return fail(c, code, std::string(kLightmap) + ": " + c->error); }
 // everything the limits say that needs neither a scene nor the output
 static int lightmap_desc_ok(rt_ctx* c, const rt_lightmap_desc* d, const rt_bake_rect* entries, rt_bake_atlas_desc* bake) {
   const std::string w(kLightmap);
@@ -3027,8 +2956,48 @@ static int lightmap_desc_ok(rt_ctx* c, const rt_lightmap_desc* d, const rt_bake_
   bake->t_max = d->t_max;
   bake->n_entries = d->n_entries;
   int r = bake_atlas_desc_ok(c, bake, entries);
-  if (r < 0) return lightmap_refused(c, r);
-  if ((r = path_query_args_ok(c, pq_gather, d->width * d->height, d->spp)) < 0) return lightmap_refused(c, r);
+  if (r < 0) return refused_under(c, kLightmap, r);
+  if ((r = path_query_args_ok(c, pq_gather, d->width * d->height, d->spp)) < 0) return refused_under(c, kLightmap, r);
+  return RT_OK;
+}
+// The finishing chain of both lightmap forms, filter then gutter fill.  Its atlas-sized arrays, asked for before the first
+// launch: growing one later would wait for the stream (ensure_buffer).  The stages ask again for what is theirs, and find it.
+static int lightmap_finish_room(rt_ctx* c, const rt_lightmap_desc* d) {
+  const size_t texels = (size_t)d->width * d->height;
+  int r;
+  if (d->passes) {
+    if ((r = ensure_buffer(c, c->lm.filtered, texels * 16, true)) < 0) return r;
+    if ((r = ensure_buffer(c, c->dn.index, texels * 4, true)) < 0) return r;
+    if (d->passes > 1 && (r = ensure_buffer(c, c->dn.scratch, texels * 16, true)) < 0) return r;
+  }
+  if (d->dilate_radius) {
+    if ((r = ensure_buffer(c, c->dl.bitmap, (size_t)d->height * ((d->width + 63u) / 64u) * 8, true)) < 0) return r;
+    if ((r = ensure_buffer(c, c->dl.src, texels * 4, true)) < 0) return r;
+    if ((r = ensure_buffer(c, c->lm.filled, 16, false)) < 0) return r;
+  }
+  return RT_OK;
+}
+// Enqueue the chain on one f32 layer with the bake's n points: the filter into lm.filtered when passes != 0, then the gutter
+// fill in place when dilate_radius != 0, counting into d_filled unless that is null.  *finished: where the layer then lies,
+// `layer` itself or lm.filtered.
+static int lightmap_finish_layer(rt_ctx* c, const rt_lightmap_desc* d, void* layer, uint32_t n, void* d_filled, void** finished) {
+  int r;
+  if (d->passes) {
+    const rt_denoise_desc f = {d->width, d->height, d->step, d->passes, d->normal_cos, d->plane_eps, d->max_dist, {0}};
+    if ((r = launch_denoise(c, &f, layer, c->bk.points.ptr, c->bk.texels.ptr, n, c->lm.filtered.ptr)) < 0) return r;
+    layer = c->lm.filtered.ptr;
+  }
+  if (d->dilate_radius) {
+    const rt_dilate_desc g = {d->width, d->height, d->dilate_radius, {0}};
+    if ((r = launch_dilate(c, &g, layer, nullptr, d_filled)) < 0) return r;
+  }
+  *finished = layer;
+  return RT_OK;
+}
+// the output of a scalar lightmap holds width * height texels of the format
+static int lightmap_out_bytes_ok(rt_ctx* c, const rt_lightmap_desc* d, size_t out_bytes) {
+  if (out_bytes < (size_t)d->width * d->height * lightmap_texel_bytes(d->format))
+    return fail(c, RT_ERR_INVALID, std::string(kLightmap) + ": out_bytes is below width * height texels of the format");
   return RT_OK;
 }
 // The whole bake behind its checks.  d_out null: the host form, `out` receives the encoded atlas; else the device form.
@@ -3039,20 +3008,10 @@ static int lightmap_bake(rt_ctx* c, const rt_lightmap_desc* d, const rt_bake_atl
   const size_t atlas_bytes = (size_t)texels * 16, out_bytes = (size_t)texels * lightmap_texel_bytes(d->format);
   const bool count_filled = n_filled_out && d->dilate_radius;
   int r;
-  // every atlas-sized array before the first launch: growing one later would wait for the stream (ensure_buffer).  The
-  // stages ask again for what is theirs, and find it there.
+  // every atlas-sized array before the first launch (lightmap_finish_room)
   if ((r = ensure_buffer(c, c->bk.count, 16, false)) < 0) return r;
   if ((r = ensure_buffer(c, c->bk.atlas, atlas_bytes, true)) < 0) return r;
-  if (d->passes) {
-    if ((r = ensure_buffer(c, c->lm.filtered, atlas_bytes, true)) < 0) return r;
-    if ((r = ensure_buffer(c, c->dn.index, (size_t)texels * 4, true)) < 0) return r;
-    if (d->passes > 1 && (r = ensure_buffer(c, c->dn.scratch, atlas_bytes, true)) < 0) return r;
-  }
-  if (d->dilate_radius) {
-    if ((r = ensure_buffer(c, c->dl.bitmap, (size_t)d->height * ((d->width + 63u) / 64u) * 8, true)) < 0) return r;
-    if ((r = ensure_buffer(c, c->dl.src, (size_t)texels * 4, true)) < 0) return r;
-    if ((r = ensure_buffer(c, c->lm.filled, 16, false)) < 0) return r;
-  }
+  if ((r = lightmap_finish_room(c, d)) < 0) return r;
   if (!d_out && d->format != RT_LIGHTMAP_F32 && (r = ensure_buffer(c, c->lm.encoded, out_bytes, true)) < 0) return r;
   // the point pass, once: its points and texels stay in the bake's arrays for the filter
   rtk::BakeAtlasArgs A;
@@ -3062,26 +3021,8 @@ static int lightmap_bake(rt_ctx* c, const rt_lightmap_desc* d, const rt_bake_atl
   if ((r = bake_atlas_emit(c, A, c->bk.points.ptr, c->bk.texels.ptr, n)) < 0) return r;
   if ((r = bake_gather_scatter(c, texels, n, d->max_depth, d->spp, d->seed, stats != nullptr, rtk::k_atlas_scatter, A.owner)) < 0)
     return r;
-  void* current = c->bk.atlas.ptr;
-  if (d->passes) {
-    rt_denoise_desc f = {};
-    f.width = d->width;
-    f.height = d->height;
-    f.step = d->step;
-    f.passes = d->passes;
-    f.normal_cos = d->normal_cos;
-    f.plane_eps = d->plane_eps;
-    f.max_dist = d->max_dist;
-    if ((r = launch_denoise(c, &f, current, c->bk.points.ptr, c->bk.texels.ptr, n, c->lm.filtered.ptr)) < 0) return r;
-    current = c->lm.filtered.ptr;
-  }
-  if (d->dilate_radius) {
-    rt_dilate_desc g = {};
-    g.width = d->width;
-    g.height = d->height;
-    g.radius = d->dilate_radius;
-    if ((r = launch_dilate(c, &g, current, nullptr, count_filled ? c->lm.filled.ptr : nullptr)) < 0) return r;
-  }
+  void* current;
+  if ((r = lightmap_finish_layer(c, d, c->bk.atlas.ptr, n, count_filled ? c->lm.filled.ptr : nullptr, &current)) < 0) return r;
   uint32_t filled = 0;
   if (d_out) {
     if ((r = launch_encode(c, texels, d->format, current, d_out)) < 0) return r;
@@ -3109,9 +3050,8 @@ int rt_bake_atlas_lightmap(rt_ctx* c, const rt_lightmap_desc* d, const rt_bake_r
   int r = lightmap_desc_ok(c, d, entries, &bake);
   if (r < 0) return r;
   if (!out) return fail(c, RT_ERR_INVALID, std::string(kLightmap) + ": NULL array");
-  if (out_bytes < (size_t)d->width * d->height * lightmap_texel_bytes(d->format))
-    return fail(c, RT_ERR_INVALID, std::string(kLightmap) + ": out_bytes is below width * height texels of the format");
-  if ((r = bake_atlas_scene_ready(c, &bake, entries, true)) < 0) return lightmap_refused(c, r);
+  if ((r = lightmap_out_bytes_ok(c, d, out_bytes)) < 0) return r;
+  if ((r = bake_atlas_scene_ready(c, &bake, entries, true)) < 0) return refused_under(c, kLightmap, r);
   const void* d_uv;
   if ((r = bake_stage_uv(c, kLightmap, atlas_uv, n_uv_vertices, &d_uv)) < 0) return r;
   return lightmap_bake(c, d, &bake, entries, d_uv, out, nullptr, n_covered_out, n_filled_out, stats);
@@ -3125,9 +3065,8 @@ int rt_bake_atlas_lightmap_device(rt_ctx* c, const rt_lightmap_desc* d, const rt
   int r = lightmap_desc_ok(c, d, entries, &bake);
   if (r < 0) return r;
   if ((r = query_device_arrays_ok(c, kLightmap, dev_out, dev_atlas_uv ? dev_atlas_uv : dev_out)) < 0) return r;
-  if (out_bytes < (size_t)d->width * d->height * lightmap_texel_bytes(d->format))
-    return fail(c, RT_ERR_INVALID, std::string(kLightmap) + ": out_bytes is below width * height texels of the format");
-  if ((r = bake_atlas_scene_ready(c, &bake, entries, true)) < 0) return lightmap_refused(c, r);
+  if ((r = lightmap_out_bytes_ok(c, d, out_bytes)) < 0) return r;
+  if ((r = bake_atlas_scene_ready(c, &bake, entries, true)) < 0) return refused_under(c, kLightmap, r);
   return lightmap_bake(c, d, &bake, entries, dev_atlas_uv, nullptr, dev_out, n_covered_out, n_filled_out, stats);
 }
 
@@ -3135,8 +3074,6 @@ int rt_bake_atlas_lightmap_device(rt_ctx* c, const rt_lightmap_desc* d, const rt
 // lightmaps"; k_dir_scatter of k_directional.hip.h).  Four layers of an atlas, layer-major, in db_layers.
 static const char* const kBakeDirectional = "bake directional";
 static const char* const kDirLightmap = "directional lightmap";
-// a refusal of one of the stages, under the entry's name: "bake directional: bake atlas: entry 3: ..."
-static int refused_under(rt_ctx* c, const char* what, int code) { return fail(c, code, std::string(what) + ": " + c->error); }
 // Behind the front of an atlas bake: the one host read of the count, the arrays for *n points, their results and the four
 // layers, the emit launch, the directional gather on the points and the scatter, enqueued; the layers stay in db_layers.
 static int directional_bake(rt_ctx* c, const char* what, uint32_t texels, rtk::BakeAtlasArgs& A, uint32_t max_depth, uint32_t spp,
@@ -3210,16 +3147,7 @@ int rt_bake_atlas_directional_lightmap(rt_ctx* c, const rt_lightmap_desc* d, con
   if ((r = ensure_buffer(c, c->bk.count, 16, false)) < 0) return r;
   if ((r = ensure_buffer(c, c->db_layers, 4 * atlas_bytes, true)) < 0) return r;
   if ((r = ensure_buffer(c, c->db_encoded, 4 * layer_bytes, true)) < 0) return r;
-  if (d->passes) {
-    if ((r = ensure_buffer(c, c->lm.filtered, atlas_bytes, true)) < 0) return r;
-    if ((r = ensure_buffer(c, c->dn.index, (size_t)texels * 4, true)) < 0) return r;
-    if (d->passes > 1 && (r = ensure_buffer(c, c->dn.scratch, atlas_bytes, true)) < 0) return r;
-  }
-  if (d->dilate_radius) {
-    if ((r = ensure_buffer(c, c->dl.bitmap, (size_t)d->height * ((d->width + 63u) / 64u) * 8, true)) < 0) return r;
-    if ((r = ensure_buffer(c, c->dl.src, (size_t)texels * 4, true)) < 0) return r;
-    if ((r = ensure_buffer(c, c->lm.filled, 16, false)) < 0) return r;
-  }
+  if ((r = lightmap_finish_room(c, d)) < 0) return r;
   rtk::BakeAtlasArgs A;
   if ((r = bake_atlas_front(c, &bake, entries, d_uv, nullptr, c->bk.count.ptr, A)) < 0) return r;
   uint32_t n;
@@ -3227,26 +3155,10 @@ int rt_bake_atlas_directional_lightmap(rt_ctx* c, const rt_lightmap_desc* d, con
   // filter, gutter and encode layer by layer, with the stages as they stand: the filtered layer is lm.filtered for each in
   // turn (the stream orders the layers), the gutter fill is in place, the encoded layers lie side by side in db_encoded
   for (uint32_t k = 0; k < 4u; k++) {
-    void* current = (char*)c->db_layers.ptr + k * atlas_bytes;
-    if (d->passes) {
-      rt_denoise_desc f = {};
-      f.width = d->width;
-      f.height = d->height;
-      f.step = d->step;
-      f.passes = d->passes;
-      f.normal_cos = d->normal_cos;
-      f.plane_eps = d->plane_eps;
-      f.max_dist = d->max_dist;
-      if ((r = launch_denoise(c, &f, current, c->bk.points.ptr, c->bk.texels.ptr, n, c->lm.filtered.ptr)) < 0) return r;
-      current = c->lm.filtered.ptr;
-    }
-    if (d->dilate_radius) {
-      rt_dilate_desc g = {};
-      g.width = d->width;
-      g.height = d->height;
-      g.radius = d->dilate_radius;
-      if ((r = launch_dilate(c, &g, current, nullptr, (count_filled && k == 0) ? c->lm.filled.ptr : nullptr)) < 0) return r;
-    }
+    void* current;
+    if ((r = lightmap_finish_layer(c, d, (char*)c->db_layers.ptr + k * atlas_bytes, n,
+                                   (count_filled && k == 0) ? c->lm.filled.ptr : nullptr, &current)) < 0)
+      return r;
     if ((r = launch_encode(c, texels, d->format, current, (char*)c->db_encoded.ptr + k * layer_bytes)) < 0) return r;
   }
   uint32_t filled = 0;
@@ -3262,8 +3174,8 @@ int rt_bake_atlas_directional_lightmap(rt_ctx* c, const rt_lightmap_desc* d, con
 static int encode_args_ok(rt_ctx* c, uint32_t width, uint32_t height, uint32_t format, const void* in, const void* out,
                           size_t out_bytes) {
   const std::string w(kEncode);
-  if (width == 0 || height == 0) return fail(c, RT_ERR_INVALID, w + ": width and height must be >= 1");
-  if ((uint64_t)width * height > (1ull << 24)) return fail(c, RT_ERR_INVALID, w + ": width * height must be <= 2^24");
+  const int r = atlas_size_ok(c, w, width, height);
+  if (r < 0) return r;
   if (!lightmap_texel_bytes(format)) return fail(c, RT_ERR_INVALID, w + ": format must be RT_LIGHTMAP_F32, _F16 or _RGBE8");
   if (!in || !out) return fail(c, RT_ERR_INVALID, w + ": NULL array");
   if (out_bytes < (size_t)width * height * lightmap_texel_bytes(format))
@@ -3328,8 +3240,6 @@ static int volume_desc_ok(rt_ctx* c, const rt_volume_desc* d, uint32_t* n_out) {
   *n_out = (uint32_t)n;
   return RT_OK;
 }
-// a refusal of the probe gather's, under the volume's name: "volume: probe gather: spp must be 1 .. 65536"
-static int volume_refused(rt_ctx* c, int code) { return fail(c, code, std::string(kVolume) + ": " + c->error); }
 
 // Enqueue a bake: the grid's probes into the probe gather's staging, its device path with its batching into d_out, the
 // finish in place.
@@ -3341,7 +3251,7 @@ static int launch_bake_volume(rt_ctx* c, const rt_volume_desc& D, uint32_t n, ui
   hipLaunchKernelGGL(rtk::k_volume_probes, dim3((n + 255u) / 256u), dim3(256), 0, c->stream, D, (float4*)c->pr.in.ptr, n);
   HIP_TRY(c, hipGetLastError());
   if ((r = launch_composed_gather(c, cg_probe, c->pr.in.ptr, n, max_depth, spp, seed, d_out, detail)) < 0)
-    return volume_refused(c, r);
+    return refused_under(c, kVolume, r);
   const uint32_t n_vec = n * (uint32_t)(sizeof(rt_probe_sh9) / 16);
   hipLaunchKernelGGL(rtk::k_volume_finish, dim3((n_vec + 255u) / 256u), dim3(256), 0, c->stream, D, (float4*)d_out, n_vec);
   HIP_TRY(c, hipGetLastError());
@@ -3352,7 +3262,7 @@ int rt_bake_volume_device(rt_ctx* c, const rt_volume_desc* desc, uint32_t max_de
   uint32_t n = 0;
   int r = volume_desc_ok(c, desc, &n);
   if (r < 0 || !c) return RT_ERR_INVALID;
-  if ((r = path_query_args_ok(c, pq_probe, n, spp)) < 0) return volume_refused(c, r);
+  if ((r = path_query_args_ok(c, pq_probe, n, spp)) < 0) return refused_under(c, kVolume, r);
   if (!dev_out) return fail(c, RT_ERR_INVALID, std::string(kVolume) + ": NULL array");
   if ((r = query_device_arrays_ok(c, kVolume, dev_out, dev_out)) < 0) return r;
   return launch_bake_volume(c, *desc, n, max_depth, spp, seed, dev_out, c->detailed_counters);
@@ -3363,7 +3273,7 @@ int rt_bake_volume(rt_ctx* c, const rt_volume_desc* desc, uint32_t max_depth, ui
   uint32_t n = 0;
   int r = volume_desc_ok(c, desc, &n);
   if (r < 0 || !c) return RT_ERR_INVALID;
-  if ((r = path_query_args_ok(c, pq_probe, n, spp)) < 0) return volume_refused(c, r);
+  if ((r = path_query_args_ok(c, pq_probe, n, spp)) < 0) return refused_under(c, kVolume, r);
   if (!out) return fail(c, RT_ERR_INVALID, std::string(kVolume) + ": NULL array");
   HIP_TRY(c, hipSetDevice(c->device));
   const size_t bytes = (size_t)n * sizeof(rt_probe_sh9);
@@ -3568,7 +3478,7 @@ static int compute_frames(rt_ctx* c, const uint32_t* frame_counts, uint32_t n, u
   // The table goes through a pinned ring, one device table per ring entry: the copy is asynchronous, its source
   // outlives it, and a dispatch still in flight keeps reading its own table while the next one is being written.
   if (!c->slot_ring) {
-    HIP_TRY(c, hipHostMalloc((void**)&c->slot_ring, (size_t)rt_ctx::kSlotRing * 64 * sizeof(DevFrameSlot), hipHostMallocDefault));
+    HIP_TRY(c, hipHostMalloc(&c->slot_ring, (size_t)rt_ctx::kSlotRing * 64 * sizeof(DevFrameSlot), hipHostMallocDefault));
     for (int k = 0; k < rt_ctx::kSlotRing; k++) HIP_TRY(c, hipEventCreateWithFlags(&c->slot_ring_ev[k], hipEventDisableTiming));
   }
   r = ensure_buffer(c, c->slots, (size_t)rt_ctx::kSlotRing * 64 * sizeof(DevFrameSlot), false);
@@ -3576,7 +3486,7 @@ static int compute_frames(rt_ctx* c, const uint32_t* frame_counts, uint32_t n, u
   const int ring = c->slot_ring_next;
   c->slot_ring_next = (ring + 1) % rt_ctx::kSlotRing;
   if (c->slot_ring_used[ring]) HIP_TRY(c, hipEventSynchronize(c->slot_ring_ev[ring]));  // the dispatch that used this entry is done
-  DevFrameSlot* host_slots = c->slot_ring + (size_t)ring * 64;
+  DevFrameSlot* host_slots = (DevFrameSlot*)c->slot_ring.h + (size_t)ring * 64;
   std::memcpy(host_slots, slots.data(), (size_t)n * sizeof(DevFrameSlot));
   DevFrameSlot* dev_slots = (DevFrameSlot*)c->slots.ptr + (size_t)ring * 64;
   HIP_TRY(c, hipMemcpyAsync(dev_slots, host_slots, (size_t)n * sizeof(DevFrameSlot), hipMemcpyHostToDevice, c->stream));
@@ -4043,8 +3953,9 @@ int rt_debug_ieee_check(rt_ctx* c, int op, uint64_t first, uint64_t count, rt_ie
   if (op < 0 || op >= RT_IEEE_OP_COUNT) return fail(c, RT_ERR_INVALID, "rt_debug_ieee_check: unknown op");
   if (count == 0) return RT_OK;
   HIP_TRY(c, hipSetDevice(c->device));
-  rtk::IeeeReport* d = nullptr;
-  HIP_TRY(c, hipMalloc((void**)&d, sizeof(rtk::IeeeReport)));
+  DeviceBuffer report;   // freed on every way out
+  HIP_TRY(c, hipMalloc(&report.ptr, sizeof(rtk::IeeeReport)));
+  rtk::IeeeReport* d = (rtk::IeeeReport*)report.ptr;
   hipError_t e = hipMemsetAsync(d, 0, sizeof(rtk::IeeeReport), c->stream);
   const uint64_t want = (count + 255) / 256;
   const dim3 grid((uint32_t)std::min<uint64_t>(want, (uint64_t)c->num_cus * 32u)), block(256);
@@ -4063,7 +3974,6 @@ int rt_debug_ieee_check(rt_ctx* c, int op, uint64_t first, uint64_t count, rt_ie
   }
   if (e == hipSuccess) e = hipMemcpyAsync(out, d, sizeof(*out), hipMemcpyDeviceToHost, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  (void)hipFree(d);
   if (e != hipSuccess) return hip_fail(c, e, "rt_debug_ieee_check");
   out->n = count;
   return RT_OK;
