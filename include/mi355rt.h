@@ -270,6 +270,13 @@ int rt_debug_pt_sections(rt_ctx* ctx, uint64_t* out8, int reset);
  * one-leaf form), workgroups, dynamic LDS bytes per workgroup, resident workgroups per CU from the occupancy query}.  All
  * zero before the first such launch. */
 int rt_debug_pt_launch(rt_ctx* ctx, uint32_t* out4);
+/* Which materials the path-trace kernel of the last compute() dispatch carried code for: RT_PT_FORM_PLAIN when the host knew
+ * from the uploaded topology that every triangle is an untextured Lambertian surface or a light and ran the wide one-leaf
+ * form compiled for those alone (MI355RT_PLAIN_MATERIALS=0 in the environment of rt_create switches that off),
+ * RT_PT_FORM_GENERIC for every other launch of the persistent kernel, RT_PT_FORM_NONE before the first dispatch and after a
+ * dispatch that ran another kernel (wavefront, one pixel per lane).  The images of the two forms are the same, bit for bit. */
+enum { RT_PT_FORM_NONE = 0, RT_PT_FORM_GENERIC = 1, RT_PT_FORM_PLAIN = 2 };
+int rt_debug_pt_form(const rt_ctx* ctx);
 /* Diagnostic build (-DRT_LANE_STATS) only: lane utilisation of the parts of a trip of k_pathtrace_persistent:
  * out32[2 k] = times part k ran (wave level), out32[2 k + 1] = active lanes summed; k = 0 shade, 1 / 2 node step / triangle
  * chunk of the shadow walk, 3 / 4 of the extension walk, 5 surface frame of a new hit, 6 start of a sample, 7 end of a sample;

@@ -43,7 +43,9 @@ __device__ __forceinline__ PathState idle_path() {
 // and the geometric normal, which depends on (instance, triangle) alone, is read from it: the bits the expression below
 // gives, made once per upload.  The texture coordinates are interpolated only when the scene has a texture layer:
 // without one sample_tex returns 1 and never looks at them.
-template <bool REC = false>
+// PLAIN (k_pathtrace_persistent_plain): the host has seen every triangle of the scene fail both texture tests below
+// (scene_facts.h), which are then not made.
+template <bool REC = false, bool PLAIN = false>
 __device__ __forceinline__ void setup_surface(const DevScene& S, PathState& p, bool from_gbuffer, float gx, float gy,
                                               uint32_t galbedo, const float4* wrec = nullptr) {
   InvRows m = load_inv_rows(S, p.inst);
@@ -69,8 +71,8 @@ __device__ __forceinline__ void setup_surface(const DevScene& S, PathState& p, b
     p.normal = rt_normalize(normal_to_world(m, ln));
     float4 nd0 = ts[0], nd2 = ts[2];
     p.albedo = xyz(nd0);
-    if (nd2.x > -0.5f) p.albedo = p.albedo * sample_tex(S, p.tex_uv, rt_f2i32_sat(nd2.x));
-    if (nd2.z > -0.5f) {
+    if (!PLAIN && nd2.x > -0.5f) p.albedo = p.albedo * sample_tex(S, p.tex_uv, rt_f2i32_sat(nd2.x));
+    if (!PLAIN && nd2.z > -0.5f) {
       rt3 n_map = sample_tex(S, p.tex_uv, rt_f2i32_sat(nd2.z)) * 2.0f - rt3_splat(1.0f);
       rt3 T = rt_normalize(b.e1);
       rt3 B = rt_normalize(rt_cross(ln, T));
@@ -208,7 +210,11 @@ struct BounceOut {
   float sh_tmax;
 };
 // REC: light_pdf and sample_light read the records of the one-leaf forms (setup_surface)
-template <bool REC = false>
+// PLAIN (k_pathtrace_persistent_plain): the host has seen (scene_facts.h) that every triangle's material word decodes to 0 or
+// 3, that both texture tests below fail on every triangle and that a triangle with an emission longer than 1e-4 is a light:
+// the material is taken as 3 or 0, the texture tests are not made and the emissive test is the material's alone.  What is
+// left is evaluated as written, so a path gets the bits of the generic form.
+template <bool REC = false, bool PLAIN = false>
 __device__ __forceinline__ void shade_bounce(const DevScene& S, uint32_t light_count, uint32_t max_depth, PathState& p,
                                              BounceOut& o, const float4* wrec = nullptr) {
   o.want_shadow = o.want_extend = o.nee_valid = false;
@@ -216,23 +222,24 @@ __device__ __forceinline__ void shade_bounce(const DevScene& S, uint32_t light_c
   o.sh_tmax = 0.0f;
   const float4* ts = S.tri_shade + 8 * (size_t)p.tri;
   float4 d0 = ts[0], d1 = ts[1], d2 = ts[2], d3 = ts[3];
-  const uint32_t mat_type = rt_f2u32_sat(d0.w + 0.5f);
+  const uint32_t mat_word = rt_f2u32_sat(d0.w + 0.5f);
+  const uint32_t mat_type = PLAIN ? (mat_word == 3u ? 3u : 0u) : mat_word;
   const rt3 hit_p = p.ro + p.rd * p.hit_t;
   p.normal = (rt_dot(p.rd, p.normal) < 0.0f) ? p.normal : -p.normal;
   p.geom_n = (rt_dot(p.rd, p.geom_n) < 0.0f) ? p.geom_n : -p.geom_n;
   float metallic = d1.x, roughness = d1.y;
-  if (d2.y > -0.5f) {
+  if (!PLAIN && d2.y > -0.5f) {
     rt3 mr = sample_tex(S, p.tex_uv, rt_f2i32_sat(d2.y));
     metallic *= mr.z;
     roughness *= mr.y;
   }
   roughness = rt_max(roughness, 0.005f);
   rt3 emissive = xyz(d3);
-  if (d2.w > -0.5f) emissive = emissive * sample_tex(S, p.tex_uv, rt_f2i32_sat(d2.w));
+  if (!PLAIN && d2.w > -0.5f) emissive = emissive * sample_tex(S, p.tex_uv, rt_f2i32_sat(d2.w));
   const rt3 f0 = rt_mix3(rt3_splat(0.04f), p.albedo, metallic);
 
   bool ended = false;
-  if (mat_type == 3u || rt_length(emissive) > 1e-4f) {
+  if (mat_type == 3u || (!PLAIN && rt_length(emissive) > 1e-4f)) {
     rt3 em_val = (mat_type == 3u) ? p.albedo : emissive;
     if (p.specular) {
       p.radiance = p.radiance + p.throughput * em_val;
@@ -550,10 +557,12 @@ __device__ __forceinline__ rt3 col_park_add(f4* lds, rt3 radiance) {   // the su
 #define RT_PT_KERNEL k_pathtrace_persistent
 #define RT_PT_WAVES 4
 #define RT_PT_SIMD_WAVES (LDS ? ((ONE_INST && !DETAIL) ? RT_PT_ONE_INST_WAVES : RT_PT_LDS_WAVES) : RT_PT_GLOBAL_WAVES)
+#define RT_PT_PLAIN false
 #include "k_pathtrace_persistent.hip.h"
 #undef RT_PT_KERNEL
 #undef RT_PT_WAVES
 #undef RT_PT_SIMD_WAVES
+#undef RT_PT_PLAIN
 
 // k_pathtrace_persistent_wide: the one-leaf-TLAS LDS form of the product build (rt_api.hip instantiates <false, true, true>
 // only) in 512-thread workgroups.  Eight waves share one staged scene, so that three workgroups of a small scene (24 waves,
@@ -561,10 +570,27 @@ __device__ __forceinline__ rt3 col_park_add(f4* lds, rt3 radiance) {   // the su
 #define RT_PT_KERNEL k_pathtrace_persistent_wide
 #define RT_PT_WAVES 8
 #define RT_PT_SIMD_WAVES RT_PT_WIDE_WAVES
+#define RT_PT_PLAIN false
 #include "k_pathtrace_persistent.hip.h"
 #undef RT_PT_KERNEL
 #undef RT_PT_WAVES
 #undef RT_PT_SIMD_WAVES
+#undef RT_PT_PLAIN
+
+// k_pathtrace_persistent_plain: the wide form (<false, true, true> only, the same workgroups and LDS layout) for a scene in
+// which the host has seen nothing but untextured Lambertian triangles and lights (scene_facts.h; launch_plan.h
+// persistent_shape).  shade_bounce and setup_surface are compiled without the GGX and dielectric branches, the four texture
+// fetches and the emissive length, whose conditions the generic form evaluates on every trip to skip them; with their
+// registers gone the kernel holds its 80 VGPRs without scratch (tests/test_kernel_resources_plain.py).
+#define RT_PT_KERNEL k_pathtrace_persistent_plain
+#define RT_PT_WAVES 8
+#define RT_PT_SIMD_WAVES RT_PT_WIDE_WAVES
+#define RT_PT_PLAIN true
+#include "k_pathtrace_persistent.hip.h"
+#undef RT_PT_KERNEL
+#undef RT_PT_WAVES
+#undef RT_PT_SIMD_WAVES
+#undef RT_PT_PLAIN
 
 }  // namespace rtk
 #endif

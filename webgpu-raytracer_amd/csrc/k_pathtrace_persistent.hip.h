@@ -1,6 +1,7 @@
-// The persistent path-trace kernel, written once and compiled under two names (k_pathtrace.hip.h includes this file twice,
-// inside namespace rtk): RT_PT_KERNEL is the kernel's name, RT_PT_WAVES its waves per workgroup and RT_PT_SIMD_WAVES the
-// waves per SIMD of its launch bounds (an expression that may use the template parameters).  No include guard.
+// The persistent path-trace kernel, written once and compiled under three names (k_pathtrace.hip.h includes this file three
+// times, inside namespace rtk): RT_PT_KERNEL is the kernel's name, RT_PT_WAVES its waves per workgroup, RT_PT_SIMD_WAVES the
+// waves per SIMD of its launch bounds (an expression that may use the template parameters) and RT_PT_PLAIN whether it is the
+// form for scenes of plain materials.  No include guard.
 // ONE_INST (LDS form only): the scene's TLAS is a single leaf (k_traverse.hip.h traverse<.., ONE_INST>).  Every hit is then in
 // the one instance, and what a trip would compute from (instance, triangle) alone is read from the per-triangle world
 // records the host built at upload time behind the shading records (k_prepare_world_tris: Sg.tri_shade + 8 * n_tris).
@@ -30,6 +31,10 @@ __global__ __launch_bounds__(64 * RT_PT_WAVES, RT_PT_SIMD_WAVES) void RT_PT_KERN
   // sample and the lanes whose extension ray of the last trip found a hit together; neither start_sample nor the code behind
   // the extension walk makes a frame.  The camera is read as new where a sample starts (fresh_camera_basis).
   constexpr bool ONE_PASS = ONE_INST;
+  // PLAIN (RT_PT_PLAIN, the includer's): surface frame and bounce without the materials the host has seen the scene not to
+  // have (setup_surface, shade_bounce).  The product one-leaf form only.
+  constexpr bool PLAIN = RT_PT_PLAIN;
+  static_assert(!PLAIN || (ONE_INST && LDS && !DETAIL), "the plain form is a product one-leaf form");
   extern __shared__ f4 s_scene[];
   // per-wave triangle work queue at the start of LDS, staged scene after it
   // (LEAN: the wave's index in a scalar register, and so the addresses of its queue)
@@ -328,7 +333,7 @@ __global__ __launch_bounds__(64 * RT_PT_WAVES, RT_PT_SIMD_WAVES) void RT_PT_KERN
         // every hit, the primary pass's too, is in the one instance the TLAS leaf names: its index is read here, as traverse()
         // reads it, and p.inst is not carried through the walks
         p.inst = __builtin_amdgcn_readfirstlane(rt_f2u(ld_l(s_scene, M.l_nodes + 1u).w) >> 3);
-        setup_surface<true>(S, p, started, gs.nx, gs.ny, gs.albedo, wrec);
+        setup_surface<true, PLAIN>(S, p, started, gs.nx, gs.ny, gs.albedo, wrec);
 #ifdef RT_PT_STAMPS
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
         ps1 = __builtin_amdgcn_s_memtime();
@@ -336,7 +341,7 @@ __global__ __launch_bounds__(64 * RT_PT_WAVES, RT_PT_SIMD_WAVES) void RT_PT_KERN
       }
       if (DETAIL) cnt_shaded++;
       BounceOut bo;
-      shade_bounce<ONE_INST>(S, LEAN ? rt_fresh(U.light_count) : U.light_count, LEAN ? rt_fresh(F.max_depth) : F.max_depth, p,
+      shade_bounce<ONE_INST, PLAIN>(S, LEAN ? rt_fresh(U.light_count) : U.light_count, LEAN ? rt_fresh(F.max_depth) : F.max_depth, p,
                              bo, wrec);
       want_shadow = bo.want_shadow;
       want_extend = bo.want_extend;

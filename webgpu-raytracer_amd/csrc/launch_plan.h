@@ -32,6 +32,13 @@ struct PlanKnobs {
   int wf_block = 0;              // threads per workgroup of the wavefront trace kernels (0 = default; MI355RT_WF_BLOCK)
   int wf_blocks_per_cu = 0;      // 0 = default for the block size (MI355RT_WF_BLOCKS_PER_CU)
   int wf_rayreg = -1;            // node-walk trace kernels: -1 = by scene, 0 / 1 = MI355RT_WF_RAYREG
+  bool plain_materials = true;   // MI355RT_PLAIN_MATERIALS=0: a scene of plain materials runs the generic wide form all the same
+};
+// What the host knows of the uploaded scene's materials (scene_facts.h works it out from the bytes of a topology upload).
+// plain: every triangle is Lambertian or a light, untextured, and emits only if it is a light.  known = false: the host has
+// not seen the bytes the device holds (a device-resident world update, an upload too large to matter), and nothing is assumed.
+struct SceneFacts {
+  bool known = false, plain = false;
 };
 
 // ---- byte sizes of the arrays a walk stages, each whole or not at all
@@ -144,13 +151,14 @@ struct PersistentShape {
   uint32_t waves;      // per workgroup
   size_t dyn;          // dynamic LDS per workgroup: work queues + records
   LdsPlan plan;
+  bool plain = false;  // ... the wide form without the code of the materials the scene does not have (k_pathtrace_persistent_plain)
 };
 // The 256-thread forms of the persistent kernel (and the radiance query, which runs its path loop): the whole scene in LDS
 // when it fits beside four wave queues (scene_fits_lds), else six workgroups per CU (6 waves per SIMD), each
 // with its share of the CU's LDS for the top of the tree.
 inline PersistentShape persistent_plan(const SceneSize& s, const PlanKnobs& k) {
   const size_t queue_bytes = (size_t)4 * RT_WORK_BYTES_PER_WAVE;
-  PersistentShape P = {scene_fits_lds(s, k), false, false, 4u, 0, full_lds_plan(s)};
+  PersistentShape P = {scene_fits_lds(s, k), false, false, 4u, 0, full_lds_plan(s), false};
   if (P.lds)
     P.dyn = queue_bytes + scene_lds_bytes(s);
   else
@@ -158,7 +166,8 @@ inline PersistentShape persistent_plan(const SceneSize& s, const PlanKnobs& k) {
   return P;
 }
 // What compute() launches the persistent kernel in, for a dispatch of n_frames frames; detailed: the counting build.
-inline PersistentShape persistent_shape(const SceneSize& s, const PlanKnobs& k, uint32_t n_frames, bool detailed) {
+inline PersistentShape persistent_shape(const SceneSize& s, const PlanKnobs& k, uint32_t n_frames, bool detailed,
+                                        const SceneFacts& facts = SceneFacts()) {
   PersistentShape P = persistent_plan(s, k);
   // LDS form of a scene whose TLAS is one node, which is a leaf (k_validate_scene, or the world update's builder): the walks skip the TLAS
   // half of the node step (k_traverse.hip.h traverse<.., ONE_INST>)
@@ -176,6 +185,8 @@ inline PersistentShape persistent_shape(const SceneSize& s, const PlanKnobs& k, 
   P.wide = !detailed && n_frames > 1 && wide_blocks + scene_lds_bytes(s) <= k.lds_per_cu / 3;
   P.waves = P.wide ? 8u : 4u;
   P.dyn = (P.wide ? wide_blocks : (size_t)4 * RT_WORK_BYTES_PER_WAVE) + staged_lds;
+  // the wide form of a scene whose materials are known to be plain: the same workgroups, the same LDS layout and `dyn`
+  P.plain = P.wide && facts.known && facts.plain && k.plain_materials;
   return P;
 }
 

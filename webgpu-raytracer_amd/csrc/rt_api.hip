@@ -26,6 +26,7 @@
 #include "../../include/mi355rt.h"
 #include "kernels.hip.h"
 #include "launch_plan.h"
+#include "scene_facts.h"
 #include "device_owned.h"
 #include "bvh_build.hip.h"
 #include "world_update.hip.h"
@@ -204,6 +205,9 @@ struct rt_ctx {
   int treelet_order = 2;          // order of tnodes: 0 = by visit probability, 1 = the bridge's depth-first order, 2 = auto (MI355RT_TREELET_ORDER)
   bool nodes_from_device = false; // the node array was made by rt_world_update (an animated world), not uploaded
   uint32_t pt_launch[4] = {0, 0, 0, 0};   // last persistent launch: threads, workgroups, dynamic LDS, workgroups per CU
+  lp::SceneFacts facts;          // materials of the topology on the device (scene_facts.h): worked out from the caller's bytes
+                                 // in rt_upload(RT_KIND_TOPOLOGY), unknown after every other writer of the topology records
+  int pt_form = RT_PT_FORM_NONE; // form of the last path-trace dispatch of compute() (rt_debug_pt_form)
   DeviceBuffer ticket;    // tile ticket counter of the persistent kernel
   DeviceBuffer slots;     // DevFrameSlot table of the current (batched) dispatch
   // pinned staging ring for the slot tables: the H2D copy of a dispatch's table is truly asynchronous and its source
@@ -933,6 +937,7 @@ rt_ctx* rt_create(int device_ordinal) {
   }
   if (const char* e = getenv("MI355RT_WF_OVERLAP")) c->wf_overlap = atoi(e) != 0;
   if (const char* e = getenv("MI355RT_NO_LDS_STAGING")) c->knobs.no_lds_staging = atoi(e) != 0;
+  if (const char* e = getenv("MI355RT_PLAIN_MATERIALS")) c->knobs.plain_materials = atoi(e) != 0;
   if (const char* e = getenv("MI355RT_SHADE_BLOCKS_PER_CU")) c->shade_per_cu = std::max(1, std::min(4096, atoi(e)));
   if (const char* e = getenv("MI355RT_WF_BLOCK")) {
     const int b = atoi(e);
@@ -1442,6 +1447,7 @@ static int world_make_static(rt_ctx* c, const rt_world_frame* f) {
 static int world_update_body(rt_ctx* c, const rt_world_frame* f, bool* touched) {
   auto& W = c->world;
   c->epoch++;   // drops frames traced ahead (rt_set_lookahead)
+  c->facts = lp::SceneFacts();   // the topology records are (re)made on the device, or their buffer is resized: the host has not seen them
   HIP_TRY(c, hipSetDevice(c->device));
   int r, ret = RT_OK;
   if (!W.valid || W.epoch != f->static_epoch) {
@@ -1666,6 +1672,7 @@ int rt_world_update(rt_ctx* c, const rt_world_frame* f) {
     c->validate_dirty = false;
     c->scene_problem = "the device-resident world update failed part-way (" + why + "): the scene buffers hold a mix of two scenes; upload the scene again";
     c->tris_dirty = c->inst_dirty = c->lights_dirty = c->nodes_dirty = c->pairs_dirty = c->roots_dirty = c->world_rec_dirty = true;
+    c->facts = lp::SceneFacts();
     c->world.static_cached = false;
     c->world.valid = false;
     c->error = why;
@@ -1724,9 +1731,12 @@ int rt_upload(rt_ctx* c, rt_kind kind, const void* data, size_t bytes) {
   switch (kind) {
     case RT_KIND_TOPOLOGY:
       if (bytes % sizeof(rt_topology)) return fail(c, RT_ERR_INVALID, "topology must be 80 bytes per triangle");
+      c->facts = lp::SceneFacts();
       r = upload(c, c->topology, data, bytes);
       if (r < 0) return r;
       c->n_tris = (uint32_t)(bytes / sizeof(rt_topology));
+      // the materials of these records, from the caller's bytes (a scene too large for a one-leaf LDS form is not scanned)
+      c->facts = scene_facts::topology_facts((const rt_topology*)data, bytes / sizeof(rt_topology));
       c->validate_dirty = true;
       c->tris_dirty = true;
       c->world_rec_dirty = true;
@@ -3404,6 +3414,8 @@ static const void* const pt_fns[2][2] = {
 static const void* const pt_one_leaf_fns[2] = {(const void*)rtk::k_pathtrace_persistent<false, true, true>,
                                                (const void*)rtk::k_pathtrace_persistent<true, true, true>};
 static const void* const pt_wide_fn = (const void*)rtk::k_pathtrace_persistent_wide<false, true, true>;
+// ... and the wide form of a scene whose materials the host knows to be plain (lp::PersistentShape::plain)
+static const void* const pt_plain_fn = (const void*)rtk::k_pathtrace_persistent_plain<false, true, true>;
 
 // compute() for n consecutive frame counts in ONE dispatch of each kernel (n == 1: the plain compute()).
 // n_commit < n: frames n_commit .. n-1 are traced AHEAD (speculative lookahead): their host state is not committed and their
@@ -3539,6 +3551,7 @@ static int compute_frames(rt_ctx* c, const uint32_t* frame_counts, uint32_t n, u
   if (ev) HIP_TRY(c, hipEventRecord(ev->b, c->stream));
 
   // 2. path trace
+  c->pt_form = RT_PT_FORM_NONE;   // until the persistent kernel is launched below
   if (wavefront) {
     r = launch_wavefront(c, S, F, dslots, n);
     if (r < 0) return r;
@@ -3548,9 +3561,10 @@ static int compute_frames(rt_ctx* c, const uint32_t* frame_counts, uint32_t n, u
   } else {
     // persistent kernel: grid = resident workgroups, tiles handed out through a ticket counter
     HIP_TRY(c, hipMemsetAsync(c->ticket.ptr, 0, 4, c->stream));
-    lp::PersistentShape shape = lp::persistent_shape(size, c->knobs, n, c->detailed_counters);
+    lp::PersistentShape shape = lp::persistent_shape(size, c->knobs, n, c->detailed_counters, c->facts);
     if (shape.one_inst && c->world_rec_dirty) return fail(c, RT_ERR_INTERNAL, "one-leaf form without its world records");
-    const void* fn = shape.wide       ? pt_wide_fn
+    const void* fn = shape.plain      ? pt_plain_fn
+                     : shape.wide     ? pt_wide_fn
                      : shape.one_inst ? pt_one_leaf_fns[c->detailed_counters]
                                       : pt_fns[c->detailed_counters][shape.lds];
     int per_cu;
@@ -3567,6 +3581,7 @@ static int compute_frames(rt_ctx* c, const uint32_t* frame_counts, uint32_t n, u
     c->pt_launch[1] = blocks;
     c->pt_launch[2] = (uint32_t)shape.dyn;
     c->pt_launch[3] = (uint32_t)per_cu;
+    c->pt_form = shape.plain ? RT_PT_FORM_PLAIN : RT_PT_FORM_GENERIC;
     if (ev) HIP_TRY(c, hipEventRecord(ev->b, c->stream));
     if (n > 1)  // ordered accumulation of the batch's frame colours
       hipLaunchKernelGGL(rtk::k_accumulate_frames, dim3((uint32_t)((npx + 255) / 256)), dim3(256), 0, c->stream, F, dslots,
@@ -3916,6 +3931,7 @@ int rt_debug_pt_launch(rt_ctx* c, uint32_t* out4) {
   for (int k = 0; k < 4; k++) out4[k] = c->pt_launch[k];
   return RT_OK;
 }
+int rt_debug_pt_form(const rt_ctx* c) { return c ? c->pt_form : RT_ERR_INVALID; }
 int rt_debug_lane_stats(rt_ctx* c, uint64_t* out32, int reset) {
   if (!c || !out32) return RT_ERR_INVALID;
   HIP_TRY(c, hipSetDevice(c->device));
