@@ -548,6 +548,87 @@ int rt_encode_volume(rt_ctx* ctx, const rt_volume_desc* desc, uint32_t format, c
 int rt_encode_volume_device(rt_ctx* ctx, const rt_volume_desc* desc, uint32_t format, const void* dev_volume, void* dev_out,
                             size_t cap);
 
+/* ---- reflection probes: "which radiance arrives at this point from that direction, seen through a lobe of this
+ * roughness?" for glossy surfaces, which lightmaps and irradiance volumes do not serve ----
+ * A reflection probe is the radiance arriving at an rt_probe from every direction as an octahedral map of size * size texels
+ * {r, g, b, hit_fraction} (rt_reflection_desc, mi355rt_layout.h), and behind it a chain of smaller maps, level m pre-convolved
+ * with the renderer's own GGX lobe (sample_ggx: a = roughness, a2 = roughness * roughness) at the roughness m / (levels - 1).
+ * rt_capture_reflection makes level 0 by the renderer's path tracing; rt_filter_reflection makes the levels >= 1 of a chain
+ * from level 0 and needs no scene; rt_bake_reflection captures straight into level 0 of each chain and filters in place
+ * (csrc/k_reflection.hip.h).  A chain holds chain_texels = sum over m of (size >> m)^2 texels, level m at the texel offset
+ * sum over k < m of (size >> k)^2; n chains lie one behind the other.
+ *
+ * THE REFLECTION RULE.  All arithmetic is f32, unfused, in the order written, with rt_div / rt_rcp / rt_sqrt / rt_rsqrt /
+ * rt_sincos / rt_max / rt_min / rt_floor / rt_abs / rt_saturate / rt_normalize of mi355rt_math.h.
+ *   octahedral   unpack(px, py), a direction from a point of [-1, 1]^2: n = (px, py, 1.0f - rt_abs(px) - rt_abs(py)); t =
+ *                rt_saturate(-n.z); n.x += (n.x >= 0 ? -t : t); n.y likewise with n.y; the result is rt_normalize(n).
+ *                pack(v), its inverse: s = rt_rcp(rt_abs(v.x) + rt_abs(v.y) + rt_abs(v.z)); p = (v.x * s, v.y * s); if v.z <
+ *                0 then p = ((1.0f - rt_abs(p.y)) * (p.x >= 0 ? 1.0f : -1.0f), (1.0f - rt_abs(p.x)) * (p.y >= 0 ? 1.0f :
+ *                -1.0f)), both from the p before.
+ *   frame        onb(n): sign = n.z >= 0 ? 1.0f : -1.0f; a = -rt_rcp(sign + n.z); b = n.x * n.y * a; u = (1.0f + sign * n.x *
+ *                n.x * a, sign * b, -sign * n.x); v = (b, sign + n.y * n.y * a, -n.y); w = n.  to_world(onb, t) = t.x * u + t.y
+ *                * v + t.z * w, per component (t.x * u_c + t.y * v_c) + t.z * w_c.
+ *   capture      texel t = j * size + i of a probe, sample s in 0 .. spt - 1, f = seed * spt + s in u32 arithmetic:
+ *                pad_t = pad + t; rng_d = init_rng(pad_t ^ 0x80000000, f), the gathers' direction stream; jx = rand_pcg(rng_d),
+ *                jy = rand_pcg(rng_d); px = rt_div((float)i + jx, (float)size) * 2.0f - 1.0f, py likewise from j and jy; d =
+ *                unpack(px, py).  The sample {r, g, b, t} is exactly what rt_trace_radiance returns for the ray {position,
+ *                t_max, d, pad_t} with spp = 1 and seed = f; it is a hit iff t < t_max (false for NaN).  The texel's rgb is
+ *                ((+0 + r_0) + r_1) + ... in sample order, divided by (float)spt (three quotients; no division for spt == 1);
+ *                its fourth word is rt_div((float)hits, (float)spt).  Keep pad + size * size <= 2^31.
+ *   filter       level 0 of a chain is the map, word for word.  Level m >= 1 has the side S = size >> m and the roughness a =
+ *                rt_div((float)m, (float)(levels - 1)).  Output texel (i, j): n = unpack(cx, cy) with cx = rt_div((float)i +
+ *                0.5f, (float)S) * 2.0f - 1.0f, cy likewise from j; o = onb(n).  Sample s in 0 .. K - 1, K = filter_samples:
+ *                  ux = rt_div((float)s + 0.5f, (float)K); uy = (float)(bitreverse32(s) >> 8) * 0x1p-24f (exact);
+ *                  phi = RT_TWO_PI * ux; cos_theta = rt_sqrt(rt_max(0.0f, rt_div(1.0f - uy, 1.0f + (a * a - 1.0f) * uy)));
+ *                  sin_theta = rt_sqrt(rt_max(0.0f, 1.0f - cos_theta * cos_theta)); rt_sincos(phi, &sp, &cp);
+ *                  h = (sin_theta * cp, sin_theta * sp, cos_theta), as sample_ggx forms it in the tangent frame;
+ *                  with the view along the normal, l_t = (2.0f * (h.z * h.x), 2.0f * (h.z * h.y), 2.0f * (h.z * h.z) - 1.0f)
+ *                  and the weight w = l_t.z.  If !(w > 0), all five terms of the sample are +0.  Else l = to_world(o, l_t), q
+ *                  = pack(l); per axis u = (q * 0.5f + 0.5f) * (float)size, u = +0 if !(u > 0), index =
+ *                  min((uint32_t)rt_floor(u), size - 1); the source is texel (index_x, index_y) of LEVEL 0, nearest, no
+ *                  interpolation; the five terms are w * r, w * g, w * b, w * hit_fraction, w.
+ *                Each of the five sums is the probe rule's fixed tree: 64 strided partials ((+0 + term(l)) + term(l + 64)) +
+ *                ..., then P[l] = P[l] + P[l ^ m] for m = 32 .. 1, the sum P[0].  The texel is four rt_div(sum_c, sum_w), or
+ *                four +0 if !(sum_w > 0).  Source texels are not sanitised: a NaN in level 0 reaches what samples it.  h, l_t
+ *                and w depend on (level, s) only.
+ * A result depends on (scene, probe, desc, seed, max_depth) only - never on n, the probe's place in the array or how a call
+ * is cut: the unit of path work is the (texel, sample) pair, and a capture is cut into batches of whole texels of at most
+ * RT_PROBE_BATCH_SAMPLES samples in the composed gathers' shared scratch; a probe may span several batches and a batch
+ * several probes.  A bake is word for word rt_filter_reflection of rt_capture_reflection; levels >= 1 read level 0 only.
+ * Export needs no entry of its own: every level is a width * height array of 16-byte texels whose fourth word is never -1,
+ * which is what rt_encode_atlas(_device) takes as it stands, in all three formats - RT_LIGHTMAP_RGBE8 included, radiance
+ * not being signed.  A consumer picks the level of a roughness r as r * (levels - 1).
+ * Refusals (RT_ERR_INVALID, every message begins with "reflection:", checked before the context; without one the message is
+ * what rt_last_error(NULL) returns): size not a power of two in 8 .. 512; levels < 2; size >> (levels - 1) < 4; spt 0 or
+ * above 65536 (capture and bake); filter_samples not a multiple of 64 in 64 .. 4096 (filter and bake); a non-zero reserved
+ * word; n * chain_texels >= 2^31.  The host entries of capture and bake also refuse a probe with pad + size * size > 2^31;
+ * for the device entries that is the caller's duty.  Then as for a probe gather: a NULL or unaligned array; without a
+ * valid scene RT_ERR_NOT_READY; light_count above the uploaded lights buffer.  n == 0 is RT_OK.
+ * The stats are an rt_radiance_stats with rays = n * size * size texels and samples = rays * spt, summed over the radiance
+ * launches as a probe gather's are.  Reflection probes have a path-query state and staging of their own, kept and grown:
+ * capture, filter and bake leave the renderer and the other queries' state as they were.
+ *   rt_capture_reflection         blocking: n probes in, n maps of size * size texels out.  stats != NULL runs the counting
+ *                                 kernel and fills *stats.
+ *   rt_filter_reflection          blocking: n maps in, n chains out.  Needs no scene.
+ *   rt_bake_reflection            blocking: n probes in, n chains out.
+ *   rt_capture_reflection_device, rt_bake_reflection_device
+ *                                 the same on device-accessible arrays (16-byte aligned, on the context's device): only
+ *                                 enqueue on the context's stream.  Count while rt_set_counting(ctx, 1) is on.
+ *   rt_filter_reflection_device   dev_maps: n maps one behind the other - or dev_chains itself, and then map p is read in
+ *                                 place as level 0 of chain p (the layout of a bake).  Only enqueues.
+ *   rt_reflection_stats           stats of the last capture or bake (blocking: fences the stream). */
+int rt_capture_reflection(rt_ctx* ctx, const rt_reflection_desc* desc, const rt_probe* probes, uint32_t n, uint32_t max_depth,
+                          uint32_t seed, float* out_maps, rt_radiance_stats* stats);
+int rt_capture_reflection_device(rt_ctx* ctx, const rt_reflection_desc* desc, const void* dev_probes, uint32_t n,
+                                 uint32_t max_depth, uint32_t seed, void* dev_maps);
+int rt_filter_reflection(rt_ctx* ctx, const rt_reflection_desc* desc, const float* maps, uint32_t n, float* out_chains);
+int rt_filter_reflection_device(rt_ctx* ctx, const rt_reflection_desc* desc, const void* dev_maps, uint32_t n, void* dev_chains);
+int rt_bake_reflection(rt_ctx* ctx, const rt_reflection_desc* desc, const rt_probe* probes, uint32_t n, uint32_t max_depth,
+                       uint32_t seed, float* out_chains, rt_radiance_stats* stats);
+int rt_bake_reflection_device(rt_ctx* ctx, const rt_reflection_desc* desc, const void* dev_probes, uint32_t n, uint32_t max_depth,
+                              uint32_t seed, void* dev_chains);
+int rt_reflection_stats(rt_ctx* ctx, rt_radiance_stats* out);
+
 /* ---- directional gathers: "which radiance arrives at this surface point, from which side?" as four spherical-harmonic
  * coefficients per colour over the hemisphere of the normal (directional lightmaps for normal-mapped surfaces) ----
  * An irradiance gather returns one colour per point, the cosine-weighted mean at the interpolated normal; a renderer that

@@ -184,6 +184,18 @@ typedef struct rt_volume_desc { /* 64 B */
   uint32_t reserved;          /* 0 */
 } rt_volume_desc;
 
+/* ---- reflection probes (rt_capture_reflection / rt_filter_reflection / rt_bake_reflection, mi355rt.h): rt_probe in; a map is
+ * size * size texels of 16 bytes {r, g, b, hit_fraction} in octahedral layout, texel (i, j) at j * size + i; a chain is the
+ * levels 0 .. levels - 1 of one probe, level m of side size >> m, concatenated in level order; their stats are an
+ * rt_radiance_stats ---- */
+typedef struct rt_reflection_desc { /* 32 B */
+  uint32_t size;              /* side of level 0, in texels: a power of two, 8 .. 512 */
+  uint32_t levels;            /* of a chain: >= 2, size >> (levels - 1) >= 4; level m has the roughness m / (levels - 1) */
+  uint32_t spt;               /* capture and bake: samples per texel, 1 .. 65536 */
+  uint32_t filter_samples;    /* filter and bake: lobe samples per output texel, a multiple of 64 in 64 .. 4096 */
+  uint32_t reserved[4];       /* 0 */
+} rt_reflection_desc;
+
 /* ---- directional gathers (rt_gather_directional, mi355rt.h): rt_gather_point in; their stats are an rt_radiance_stats ---- */
 typedef struct rt_directional {   /* 64 B: four 16-byte vector stores of k_dir_project */
   float layer[4][4];              /* layer[k] = {sh[k].r, sh[k].g, sh[k].b, hit_fraction}: row k is the texel of atlas layer k */
@@ -261,6 +273,11 @@ static_assert(sizeof(rt_volume_desc) == 64, "rt_volume_desc is 64 bytes");
 static_assert(__builtin_offsetof(rt_volume_desc, step) == 16 && __builtin_offsetof(rt_volume_desc, window) == 32 &&
                   __builtin_offsetof(rt_volume_desc, t_max) == 48 && __builtin_offsetof(rt_volume_desc, max_hit_fraction) == 56,
               "rt_volume_desc: four 16-byte rows, a dimension closing each of the first three");
+static_assert(sizeof(rt_reflection_desc) == 32, "rt_reflection_desc is 32 bytes");
+static_assert(__builtin_offsetof(rt_reflection_desc, size) == 0 && __builtin_offsetof(rt_reflection_desc, levels) == 4 &&
+                  __builtin_offsetof(rt_reflection_desc, spt) == 8 && __builtin_offsetof(rt_reflection_desc, filter_samples) == 12 &&
+                  __builtin_offsetof(rt_reflection_desc, reserved) == 16,
+              "rt_reflection_desc: four words, then four reserved ones");
 static_assert(sizeof(rt_denoise_desc) == 32, "rt_denoise_desc is 32 bytes");
 static_assert(sizeof(rt_dilate_desc) == 32, "rt_dilate_desc is 32 bytes");
 static_assert(sizeof(rt_bake_desc) == 32, "rt_bake_desc is 32 bytes");

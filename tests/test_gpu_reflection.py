@@ -1,0 +1,242 @@
+"""Reflection probes on the GPU (rt_capture_reflection: k_reflection_rays -> k_radiance_query -> k_reflection_texels;
+rt_filter_reflection: k_reflection_filter per level; rt_bake_reflection) against the reference model
+(tests/model/reflection_model.cpp, tied to the radiance model and to float64 by tests/test_reflection_model.py), bit for bit:
+the filter on maps with NaN, infinities, denormals and -0, for several probes in one call, through the host entry, the device
+entry on packed maps and the device entry in place, in each of its three builds; the capture inside, outside and on a wall of
+the Cornell box in both kernel forms, against the model and against the GPU's own radiance queries on host-made rays; a call
+cut into batches inside a probe; a bake as the filter of a capture; the export; no side effect on a render or on the other
+queries' state."""
+import numpy as np
+import pytest
+
+import parity_util as pu
+import probe_util as prb
+import radiance_util as ru
+import reflection_util as rf
+from test_gpu_irradiance_gather import _render, _renderer
+
+pytestmark = pytest.mark.gpu
+
+# (size, levels, K): the first three are one, two and three strides per lane in the 4-sample build; the last two run the 16- and
+# the 64-sample build, the last at the largest K
+FILTER_CASES = ((8, 2, 64), (16, 3, 128), (16, 3, 192), (32, 4, 1024), (8, 2, 4096))
+_cache = {}
+
+
+def _scene(W):
+    """(bridge, model, probes): a probe inside the Cornell box, one on a wall and one outside, pads far apart"""
+    if "cornell" not in _cache:
+        b = pu.bridge_for(W, "cornell")
+        m = rf.model_for(W, b)
+        probes = np.array(prb.scene_probes(m, b)[[21, 70, 85]])
+        probes.view(np.uint32)[:, 7] = (11, 5000, 1 << 20)
+        probes.setflags(write=False)
+        _cache["cornell"] = (b, m, probes)
+    return _cache["cornell"]
+
+
+@pytest.mark.parametrize("size,levels,K", FILTER_CASES)
+def test_filter_bit_parity_with_the_model(W, size, levels, K):
+    import torch
+    from webgpu_raytracer_amd import renderer as R
+    W._build.build_rt()
+    d = R.reflection_desc(size, levels, 1, K)
+    maps = rf.special_maps(5, size)
+    want = rf.model_filter(rf.desc(size, levels, 1, K), maps)
+    assert np.isnan(want[:, size * size:]).any() and np.isfinite(want[:, size * size:]).any()
+    chain = want.shape[1]
+    r = W.WebGPURenderer(0)                                     # nothing uploaded: the filter needs no scene
+    try:
+        for n in (1, 2, 5):
+            tag = ("filter", size, levels, K, n)
+            got = r.filterReflection(d, maps[:n])
+            assert got.shape == (n, chain, 4)
+            rf.check_words(got, want[:n], tag, nan_as_class=True)
+            assert np.array_equal(got[:, :size * size].view(np.uint32), maps[:n].reshape(n, -1, 4).view(np.uint32)), tag
+            # the device entry on packed maps ...
+            d_maps = torch.from_numpy(maps[:n].copy()).cuda()
+            d_out = torch.full((n, chain, 4), -7.0, dtype=torch.float32, device="cuda")
+            r.filterReflectionDevice(d, d_maps.data_ptr(), n, d_out.data_ptr())
+            r.sync()
+            assert np.array_equal(d_out.cpu().numpy().view(np.uint32), got.view(np.uint32)), tag + ("device",)
+            # ... and in place, on the layout of a bake: level 0 of each chain is there, the rest is garbage
+            seeded = np.full((n, chain, 4), np.nan, np.float32)
+            seeded[:, :size * size] = maps[:n].reshape(n, -1, 4)
+            d_chain = torch.from_numpy(seeded).cuda()
+            r.filterReflectionDevice(d, d_chain.data_ptr(), n, d_chain.data_ptr())
+            r.sync()
+            assert np.array_equal(d_chain.cpu().numpy().view(np.uint32), got.view(np.uint32)), tag + ("in place",)
+    finally:
+        r.destroy()
+
+
+@pytest.mark.parametrize("no_lds,lds", [(None, 1), ("1", 0)])
+def test_capture_bit_parity_with_the_model(W, monkeypatch, no_lds, lds):
+    from webgpu_raytracer_amd import renderer as R
+    b, m, probes = _scene(W)
+    r = _renderer(W, monkeypatch, b, no_lds)
+    try:
+        for depth in (0, 4):
+            for spt in (1, 3, 64):
+                tag = ("capture", no_lds, depth, spt)
+                want, counts = m.captureReflection(rf.desc(8, 2, spt, 64), probes, depth, rf.SEED)
+                got, st = r.captureReflection(R.reflection_desc(8, 2, spt, 64), probes, depth, rf.SEED, stats=True)
+                print(tag, st)
+                rf.check_words(got, want, tag)
+                assert st["lds"] == lds and st["rays"] == 3 * 64 and st["samples"] == 3 * 64 * spt, tag
+                for k, name in enumerate(ru.COUNT_NAMES):
+                    assert st[name] == int(counts[k]), (tag, name)
+                plain = r.captureReflection(R.reflection_desc(8, 2, spt, 64), probes, depth, rf.SEED)
+                assert np.array_equal(plain.view(np.uint32), got.view(np.uint32)), tag + ("counting and product kernel differ",)
+                if depth == 4 and spt == 64:                   # parity must not pass on darkness
+                    assert got[0, ..., 3].mean() > 0.5 and (got[0, ..., :3].max(axis=-1) > 0).mean() > 0.5
+                    assert 0.0 < got[1, ..., 3].mean() < 1.0 and got[2, ..., 3].min() == 0.0
+                if depth == 0:
+                    assert not got[..., :3].view(np.uint32).any() and st["extension_rays"] == 3 * 64 * spt
+    finally:
+        r.destroy()
+
+
+def test_a_capture_is_the_mean_of_the_gpus_radiance_queries(W, monkeypatch):
+    """captureReflection equals, word for word, the rule's mean of the GPU's OWN radiance queries on rays made on the host
+    ({position, t_max, d, pad + t} at spp = 1, seed = f)."""
+    from webgpu_raytracer_amd import renderer as R
+    b, m, probes = _scene(W)
+    r = _renderer(W, monkeypatch, b)
+    try:
+        for depth, spt in ((4, 3), (0, 1)):
+            dirs = m.reflectionDirections(probes, 8, spt, rf.SEED)
+
+            def trace(rays, max_depth, one, seed):
+                return np.ascontiguousarray(r.traceRadiance(rays, max_depth, one, seed)).view(np.float32).reshape(-1, 4)
+
+            want = rf.compose_capture(trace, probes, dirs, depth, spt, rf.SEED)
+            got = r.captureReflection(R.reflection_desc(8, 2, spt, 64), probes, depth, rf.SEED)
+            rf.check_words(got, want, ("composed on the GPU", depth, spt))
+    finally:
+        r.destroy()
+
+
+def test_a_call_cut_into_batches_inside_a_probe(W, monkeypatch):
+    """Three probes of 64 texels at spt = 49152: a batch holds 4194304 // 49152 = 85 texels, so the call is the batches [0, 85),
+    [85, 170), [170, 192) of its 192 texels - a boundary at texel 21 of probe 1 and at texel 42 of probe 2 - while each probe
+    alone is one uncut batch.  The call equals the three uncut calls and the call on the reversed array, word for word; its
+    stats are the sums."""
+    from webgpu_raytracer_amd import renderer as R
+    b, m, probes = _scene(W)
+    spt = 49152
+    d = R.reflection_desc(8, 2, spt, 64)
+    r = _renderer(W, monkeypatch, b)
+    try:
+        r.setKernelTiming(True)
+        full, st = r.captureReflection(d, probes, 1, rf.SEED, stats=True)
+        singles = [r.captureReflection(d, probes[k:k + 1], 1, rf.SEED, stats=True) for k in range(3)]
+        print("full", st, "singles", [s for _, s in singles])
+        for k, (one, _) in enumerate(singles):
+            assert np.array_equal(one[0].view(np.uint32), full[k].view(np.uint32)), k
+        back = r.captureReflection(d, probes[::-1], 1, rf.SEED)
+        assert np.array_equal(back[::-1].view(np.uint32), full.view(np.uint32))
+        assert st["rays"] == 192 and st["samples"] == 192 * spt
+        for name in ru.COUNT_NAMES:
+            assert st[name] == sum(s[name] for _, s in singles), name
+        assert st["extension_rays"] >= 192 * spt and st["kernel_ms"] > 0.0
+        assert st["workgroups"] > max(s["workgroups"] for _, s in singles)       # three radiance launches against one
+    finally:
+        r.destroy()
+
+
+def test_a_bake_is_the_filter_of_a_capture(W, monkeypatch):
+    import torch
+    from webgpu_raytracer_amd import renderer as R
+    b, m, probes = _scene(W)
+    d = R.reflection_desc(16, 3, 3, 128)
+    r = _renderer(W, monkeypatch, b)
+    try:
+        maps, st_c = r.captureReflection(d, probes, 4, rf.SEED, stats=True)
+        chains = r.filterReflection(d, maps)
+        bake, st_b = r.bakeReflection(d, probes, 4, rf.SEED, stats=True)
+        assert bake.shape == (3, 336, 4) and np.array_equal(bake.view(np.uint32), chains.view(np.uint32))
+        assert st_b == dict(st_c, kernel_ms=st_b["kernel_ms"])
+        assert np.array_equal(bake[:, :256].view(np.uint32), maps.reshape(3, 256, 4).view(np.uint32))
+        rf.check_words(bake, rf.model_filter(rf.desc(16, 3, 3, 128), maps), "bake against the model's filter")
+        # the device entries: a capture into packed maps, a bake into chains
+        d_probes = torch.from_numpy(np.array(probes)).cuda()
+        d_maps = torch.empty((3, 16, 16, 4), dtype=torch.float32, device="cuda")
+        d_chains = torch.empty((3, 336, 4), dtype=torch.float32, device="cuda")
+        r.captureReflectionDevice(d, d_probes.data_ptr(), 3, d_maps.data_ptr(), 4, rf.SEED)
+        r.bakeReflectionDevice(d, d_probes.data_ptr(), 3, d_chains.data_ptr(), 4, rf.SEED)
+        r.sync()
+        assert np.array_equal(d_maps.cpu().numpy().view(np.uint32), maps.view(np.uint32))
+        assert np.array_equal(d_chains.cpu().numpy().view(np.uint32), bake.view(np.uint32))
+        assert r.L.rt_bake_reflection_device(r.ctx, d.ctypes.data, d_probes.data_ptr() + 8, 1, 4, 0, d_chains.data_ptr()) == -1   # misaligned
+        # the lobe narrows nothing at level 0 and widens with the level: the rougher level has the smaller spread
+        lit = bake[0, :, :3].astype(np.float64)
+        assert lit[256:320].std() < lit[:256].std() and lit[320:].std() < lit[256:320].std()
+    finally:
+        r.destroy()
+
+
+def test_encode_is_encode_atlas_per_level(W, monkeypatch):
+    from webgpu_raytracer_amd import renderer as R
+    b, m, probes = _scene(W)
+    d = R.reflection_desc(16, 3, 2, 64)
+    r = _renderer(W, monkeypatch, b)
+    try:
+        chain = r.bakeReflection(d, probes[:1], 4, rf.SEED)[0]
+        off = R.reflection_level_offsets(16, 3)
+        for fmt in ("f32", "f16", "rgbe"):
+            levels = r.encodeReflection(d, chain, fmt)
+            assert len(levels) == 3
+            for lv, enc in enumerate(levels):
+                side = 16 >> lv
+                want = r.encodeAtlas(chain[off[lv]:off[lv + 1]].reshape(side, side, 4), fmt)
+                assert enc.shape == want.shape and enc.dtype == want.dtype and enc.tobytes() == want.tobytes(), (fmt, lv)
+        rgbe = r.encodeReflection(d, chain, "rgbe")[0]
+        assert (rgbe != 0).mean() > 0.25                         # radiance is not signed: the shared-exponent format holds it
+    finally:
+        r.destroy()
+
+
+def test_reflection_bakes_leave_the_render_and_the_other_queries_alone(W, monkeypatch):
+    """Frames 1-4, a bake, frames 5-8 with lookahead 8 against the same frames without: accumulation, presented image,
+    counters, G-buffer and uniforms are equal.  The stats of the last radiance query, irradiance gather and probe gather read
+    the same before and after a bake, and a probe gather run again gives the same words."""
+    from webgpu_raytracer_amd import renderer as R
+    b, m, probes = _scene(W)
+    W._build.build_rt()
+    d = R.reflection_desc(8, 2, 3, 64)
+    want_maps, _ = m.captureReflection(rf.desc(8, 2, 3, 64), probes, 4, rf.SEED)
+
+    def bakes(r):
+        chains = r.bakeReflection(d, probes, 4, rf.SEED)
+        rf.check_words(chains[:, :64], want_maps, "between frames")
+
+    got = _render(W, b, (1, 2, 3, 4), (5, 6, 7, 8), bakes)
+    want = _render(W, b, (1, 2, 3, 4), (5, 6, 7, 8), lambda r: None)
+    assert np.array_equal(got[0].view(np.uint32), want[0].view(np.uint32)), "accumulation"
+    assert np.array_equal(got[1], want[1]), "captureFrame"
+    assert got[2] == want[2], (got[2], want[2])
+    for a, w in zip(got[3], want[3]):
+        assert np.array_equal(pu.bits(a), pu.bits(w)), "G-buffer"
+    assert np.array_equal(got[4], want[4]), "uniforms"
+
+    r = _renderer(W, monkeypatch, b)
+    try:
+        all_probes = prb.scene_probes(m, b)
+        points = np.array(all_probes[:40])
+        points[:, 5] = 1.0
+        rays = rf.texel_rays(probes, m.reflectionDirections(probes, 8, 1, rf.SEED), 0)
+        res_r, st_r = r.traceRadiance(rays, 4, 2, rf.SEED, stats=True)
+        res_g, st_g = r.gatherIrradiance(points, 4, 2, rf.SEED, stats=True)
+        res_p, st_p = r.gatherProbes(all_probes, 4, 5, rf.SEED, stats=True)
+        chains, st_f = r.bakeReflection(d, probes, 4, rf.SEED, stats=True)
+        rf.check_words(chains[:, :64], want_maps, "after the other queries")
+        assert (r.radianceQueryStats(), r.irradianceGatherStats(), r.probeGatherStats()) == (st_r, st_g, st_p)
+        assert r.reflectionStats() == st_f and st_f["rays"] == 192 and st_f["samples"] == 192 * 3
+        assert len({st_r["extension_rays"], st_g["extension_rays"], st_p["extension_rays"], st_f["extension_rays"]}) == 4
+        again = r.gatherProbes(all_probes, 4, 5, rf.SEED)
+        assert np.array_equal(prb.result_words(again), prb.result_words(res_p))
+        again_r = r.traceRadiance(rays, 4, 2, rf.SEED)
+        assert np.array_equal(ru.result_words(again_r), ru.result_words(res_r))
+    finally:
+        r.destroy()

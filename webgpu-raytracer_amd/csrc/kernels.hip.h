@@ -37,6 +37,9 @@
 //   k_volume.hip.h            k_volume_probes / _finish / _sample / _layers: the probes of a grid, SH9 radiance into windowed
 //                             irradiance coefficients, the trilinear sampler (eight lanes per point) and the export into
 //                             seven texel layers (rt_bake_volume, rt_sample_volume, rt_encode_volume)
+//   k_reflection.hip.h        k_reflection_rays / _texels: octahedral rays per (texel, sample) in front of k_radiance_query and
+//                             the texel mean behind it; k_reflection_filter: the GGX-filtered chain of a map, one wave per
+//                             output texel; k_reflection_copy (rt_capture_reflection, rt_filter_reflection, rt_bake_reflection)
 //   k_texture_post.hip.h      k_resize_texture; k_postprocess = PostProcess.wgsl `main` (:103-176)
 //   k_validate.hip.h          k_validate_scene: every index the kernels follow, checked once per upload
 //   k_stripes.hip.h           k_pack_stripes / k_unpack_stripes: the copies of the sharded image's gather
@@ -73,6 +76,7 @@
 #include "k_denoise.hip.h"
 #include "k_encode.hip.h"
 #include "k_volume.hip.h"
+#include "k_reflection.hip.h"
 #include "k_wavefront.hip.h"
 #include "k_rayquery.hip.h"
 #include "k_texture_post.hip.h"

@@ -103,6 +103,13 @@ struct VolumeState {
   DeviceBuffer volume, points, out, encoded;
 };
 
+// What reflection probes (rt_capture_reflection, rt_filter_reflection, rt_bake_reflection) keep between calls, kept and grown:
+// the staged probes, maps and chains of the host entries.  The counter shards and the event pairs of their radiance launches
+// live in a QueryState of their own (rt_ctx::rf); the scratch of a batch is the composed gathers'.
+struct ReflectionState {
+  DeviceBuffer probes, maps, chains;
+};
+
 }  // namespace
 
 struct rt_ctx {
@@ -265,6 +272,11 @@ struct rt_ctx {
   DenoiseState dn;
   LightmapState lm;
   VolumeState vol;
+  // reflection probes: a path-query kind of their own (counter shards, an event pair per radiance launch of the last call,
+  // the last stats) and the staging of their host entries; the scratch of a batch is pr_rays / pr_rad
+  QueryState rf;
+  rt_radiance_stats rf_last = {};
+  ReflectionState rfl;
 
   // kernel timing
   bool timing = false;
@@ -2117,6 +2129,9 @@ static const PathQueryKind pq_probe = {"probe gather", "probes", RT_PQ_FNS(k_rad
 // ... and so do directional gathers
 static const PathQueryKind pq_directional = {"directional gather", "points", RT_PQ_FNS(k_radiance_query), &rt_ctx::dg,
                                              &rt_ctx::dg_last, sizeof(rt_directional)};
+// ... and so do reflection captures
+static const PathQueryKind pq_reflection = {"reflection", "texels", RT_PQ_FNS(k_radiance_query), &rt_ctx::rf, &rt_ctx::rf_last,
+                                            sizeof(rt_radiance)};
 #undef RT_PQ_FNS
 
 // Enqueue one query on the context's stream: n > 0 items at d_items, results to d_out (device pointers).  keep_counts: a
@@ -2304,17 +2319,21 @@ static int launch_composed_gather(rt_ctx* c, const ComposedGather& g, const void
   return RT_OK;
 }
 
-static int composed_gather_stats(rt_ctx* c, const ComposedGather& g, rt_radiance_stats* out) {
+// the stats of a kind whose calls launch once per batch (the composed gathers, reflection captures)
+static int batched_query_stats(rt_ctx* c, const PathQueryKind& k, rt_radiance_stats* out) {
   if (!c || !out) return RT_ERR_INVALID;
-  const int r = path_query_stats(c, g.kind, out);   // fences the stream; the time is that of the batches
+  const int r = path_query_stats(c, k, out);   // fences the stream; the time is that of the batches
   if (r < 0) return r;
-  const QueryState& q = c->*g.kind.state;
+  const QueryState& q = c->*k.state;
   for (uint32_t b = 0; b < q.batches_timed; b++) {
     float ms = 0.0f;
     HIP_TRY(c, hipEventElapsedTime(&ms, q.batch_ev[b].a, q.batch_ev[b].b));
     out->kernel_ms += (double)ms;
   }
   return RT_OK;
+}
+static int composed_gather_stats(rt_ctx* c, const ComposedGather& g, rt_radiance_stats* out) {
+  return batched_query_stats(c, g.kind, out);
 }
 // detail: run the counting kernel; < 0: as rt_set_counting says
 static int composed_gather_device(rt_ctx* c, const ComposedGather& g, const void* dev_items, uint32_t n, uint32_t max_depth,
@@ -3393,6 +3412,218 @@ int rt_encode_volume(rt_ctx* c, const rt_volume_desc* desc, uint32_t format, con
   HIP_TRY(c, hipMemcpyAsync(out, c->vol.encoded.ptr, out_bytes, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return RT_OK;
+}
+
+// ---- reflection probes (mi355rt.h "THE REFLECTION RULE"; k_reflection.hip.h): octahedral radiance maps captured through the
+// radiance query's kernel, one path item per (texel, sample), and their GGX-filtered chains.
+static const char* const kReflection = "reflection";
+// a refusal that needs no context: without one the message is what rt_last_error(NULL) returns
+static int reflection_fail(rt_ctx* c, const std::string& msg) {
+  if (!c) g_create_error = msg;
+  return fail(c, RT_ERR_INVALID, msg);
+}
+struct ReflectionShape {
+  uint32_t size_log2;
+  uint32_t map, chain;   // texels of level 0, of a whole chain
+};
+enum { RF_CAPTURE = 1, RF_FILTER = 2 };
+// everything the limits say about a descriptor and n, for the parts (RF_*) an entry runs
+static int reflection_desc_ok(rt_ctx* c, const rt_reflection_desc* d, uint32_t n, int parts, ReflectionShape* sh) {
+  const std::string w(kReflection);
+  if (!d) return reflection_fail(c, w + ": NULL descriptor");
+  if (d->size < 8 || d->size > 512 || (d->size & (d->size - 1u))) return reflection_fail(c, w + ": size must be a power of two in 8 .. 512");
+  if (d->levels < 2) return reflection_fail(c, w + ": levels must be >= 2");
+  if (d->levels > 32 || (d->size >> (d->levels - 1u)) < 4) return reflection_fail(c, w + ": size >> (levels - 1) must be >= 4");
+  if ((parts & RF_CAPTURE) && (d->spt == 0 || d->spt > 65536)) return reflection_fail(c, w + ": spt must be 1 .. 65536");
+  if ((parts & RF_FILTER) && (d->filter_samples < 64 || d->filter_samples > 4096 || (d->filter_samples & 63u)))
+    return reflection_fail(c, w + ": filter_samples must be a multiple of 64 in 64 .. 4096");
+  for (int k = 0; k < 4; k++)
+    if (d->reserved[k]) return reflection_fail(c, w + ": reserved must be 0");
+  sh->size_log2 = (uint32_t)__builtin_ctz(d->size);
+  sh->map = d->size * d->size;
+  sh->chain = 0;
+  for (uint32_t m = 0; m < d->levels; m++) sh->chain += (d->size >> m) * (d->size >> m);
+  if ((uint64_t)n * sh->chain >= (1ull << 31)) return reflection_fail(c, w + ": n * texels of a chain must be below 2^31");
+  return RT_OK;
+}
+// the host entries of capture and bake: every probe's pads stay below 2^31
+static int reflection_pads_ok(rt_ctx* c, const rt_probe* probes, uint32_t n, const ReflectionShape& sh) {
+  for (uint32_t i = 0; i < n; i++)
+    if ((uint64_t)probes[i].pad + sh.map > (1ull << 31))
+      return fail(c, RT_ERR_INVALID, std::string(kReflection) + ": probe " + std::to_string(i) + ": pad + size * size must be <= 2^31");
+  return RT_OK;
+}
+static void reflection_no_work(rt_ctx* c) {
+  c->rf_last = rt_radiance_stats();
+  c->rf.batches_timed = 0;
+}
+
+// Enqueue a capture: the n * size^2 texels of the call in batches of whole texels, each k_reflection_rays -> the radiance
+// query's kernel (spp = 1, seed = 0 on the pad' rays) -> k_reflection_texels, map p to d_out + p * out_stride texels.  The
+// probe gather's sequence with a global first-texel index per batch, so a probe may span batches and a batch probes.
+static int launch_reflection_capture(rt_ctx* c, const rt_reflection_desc& D, const ReflectionShape& sh, const void* d_probes,
+                                     uint32_t n, uint32_t max_depth, uint32_t seed, void* d_out, uint32_t out_stride, bool detail) {
+  const PathQueryKind& k = pq_reflection;
+  int r = query_scene_ready(c, k.what, true);
+  if (r < 0) return r;
+  const uint32_t spt = D.spt, total = n * sh.map;                 // < 2^31
+  const uint32_t per_batch = RT_PROBE_BATCH_SAMPLES / spt;      // whole texels: >= 64, spt being <= 65536
+  const size_t scratch_items = (size_t)std::min(total, per_batch) * spt;
+  if ((r = ensure_buffer(c, c->pr_rays, scratch_items * sizeof(rt_ray), false)) < 0) return r;
+  if ((r = ensure_buffer(c, c->pr_rad, scratch_items * sizeof(rt_radiance), false)) < 0) return r;
+  QueryState& q = c->*k.state;
+  rt_radiance_stats& last = c->*k.last;
+  q.batches_timed = 0;
+  rt_radiance_stats sum = rt_radiance_stats();
+  uint32_t batch = 0;
+  for (uint32_t first = 0; first < total; first += per_batch, batch++) {
+    const uint32_t nt = std::min(per_batch, total - first);
+    const uint32_t items = nt * spt;                            // <= RT_PROBE_BATCH_SAMPLES
+    float4* rays = (float4*)c->pr_rays.ptr;
+    float4* rad = (float4*)c->pr_rad.ptr;
+    hipLaunchKernelGGL(rtk::k_reflection_rays, dim3((items + 255u) / 256u), dim3(256), 0, c->stream, (const float4*)d_probes, rays,
+                       items, spt, seed, first, sh.size_log2);
+    HIP_TRY(c, hipGetLastError());
+    if (q.batch_ev.size() <= batch) q.batch_ev.emplace_back();
+    if ((r = launch_path_query(c, k, rays, items, max_depth, 1u, 0u, rad, detail, batch != 0, &q.batch_ev[batch])) < 0) {
+      last = rt_radiance_stats();
+      return r;
+    }
+    if (c->timing) q.batches_timed = batch + 1;
+    sum.lds = last.lds;
+    sum.workgroups += last.workgroups;
+    hipLaunchKernelGGL(rtk::k_reflection_texels, dim3((nt + 255u) / 256u), dim3(256), 0, c->stream, (const float4*)d_probes,
+                       (const float4*)rad, (float4*)d_out, nt, spt, first, sh.size_log2, out_stride);
+    HIP_TRY(c, hipGetLastError());
+  }
+  sum.rays = total;
+  sum.samples = (uint64_t)total * spt;
+  last = sum;
+  return RT_OK;
+}
+
+// Enqueue a filter: level 0 of chain p is read at d_src + p * src_stride texels; where that is not the chain itself the maps
+// are copied into level 0 first; then one launch per level >= 1 over all n probes.
+static int launch_reflection_filter(rt_ctx* c, const rt_reflection_desc& D, const ReflectionShape& sh, const void* d_src,
+                                    uint32_t src_stride, void* d_out, uint32_t n) {
+  if (d_src != (const void*)d_out) {
+    const uint32_t texels = n * sh.map;
+    hipLaunchKernelGGL(rtk::k_reflection_copy, dim3((texels + 255u) / 256u), dim3(256), 0, c->stream, (const float4*)d_src,
+                       (float4*)d_out, texels, sh.size_log2, sh.chain);
+    HIP_TRY(c, hipGetLastError());
+  }
+  rtk::ReflectionFilterArgs A;
+  A.src = (const float4*)d_src;
+  A.out = (float4*)d_out;
+  A.src_stride = src_stride;
+  A.chain = sh.chain;
+  A.n = n;
+  A.size_log2 = sh.size_log2;
+  A.levels = D.levels;
+  A.K = D.filter_samples;
+  const uint32_t ns = D.filter_samples / 64u;
+  uint32_t offset = sh.map;
+  for (uint32_t m = 1; m < D.levels; m++) {
+    const uint32_t S = D.size >> m, texels = n * S * S;
+    A.level = m;
+    A.offset = offset;
+    offset += S * S;
+    // one wave per texel at a time, four per workgroup, persistent: at most eight workgroups per CU
+    const uint32_t blocks = std::min((texels + 3u) / 4u, (uint32_t)c->num_cus * 8u);
+    if (ns <= 4)
+      hipLaunchKernelGGL(rtk::k_reflection_filter<4>, dim3(blocks), dim3(256), 0, c->stream, A);
+    else if (ns <= 16)
+      hipLaunchKernelGGL(rtk::k_reflection_filter<16>, dim3(blocks), dim3(256), 0, c->stream, A);
+    else
+      hipLaunchKernelGGL(rtk::k_reflection_filter<64>, dim3(blocks), dim3(256), 0, c->stream, A);
+    HIP_TRY(c, hipGetLastError());
+  }
+  return RT_OK;
+}
+
+int rt_reflection_stats(rt_ctx* c, rt_radiance_stats* out) { return batched_query_stats(c, pq_reflection, out); }
+
+int rt_capture_reflection_device(rt_ctx* c, const rt_reflection_desc* desc, const void* dev_probes, uint32_t n, uint32_t max_depth,
+                                 uint32_t seed, void* dev_maps) {
+  ReflectionShape sh;
+  int r = reflection_desc_ok(c, desc, n, RF_CAPTURE, &sh);
+  if (r < 0 || !c) return RT_ERR_INVALID;
+  if (n == 0) return reflection_no_work(c), RT_OK;
+  if ((r = query_device_arrays_ok(c, kReflection, dev_probes, dev_maps)) < 0) return r;
+  return launch_reflection_capture(c, *desc, sh, dev_probes, n, max_depth, seed, dev_maps, sh.map, c->detailed_counters);
+}
+
+int rt_bake_reflection_device(rt_ctx* c, const rt_reflection_desc* desc, const void* dev_probes, uint32_t n, uint32_t max_depth,
+                              uint32_t seed, void* dev_chains) {
+  ReflectionShape sh;
+  int r = reflection_desc_ok(c, desc, n, RF_CAPTURE | RF_FILTER, &sh);
+  if (r < 0 || !c) return RT_ERR_INVALID;
+  if (n == 0) return reflection_no_work(c), RT_OK;
+  if ((r = query_device_arrays_ok(c, kReflection, dev_probes, dev_chains)) < 0) return r;
+  if ((r = launch_reflection_capture(c, *desc, sh, dev_probes, n, max_depth, seed, dev_chains, sh.chain, c->detailed_counters)) < 0)
+    return r;
+  return launch_reflection_filter(c, *desc, sh, dev_chains, sh.chain, dev_chains, n);
+}
+
+int rt_filter_reflection_device(rt_ctx* c, const rt_reflection_desc* desc, const void* dev_maps, uint32_t n, void* dev_chains) {
+  ReflectionShape sh;
+  int r = reflection_desc_ok(c, desc, n, RF_FILTER, &sh);
+  if (r < 0 || !c) return RT_ERR_INVALID;
+  if (n == 0) return RT_OK;
+  if ((r = query_device_arrays_ok(c, kReflection, dev_maps, dev_chains)) < 0) return r;
+  return launch_reflection_filter(c, *desc, sh, dev_maps, dev_maps == (const void*)dev_chains ? sh.chain : sh.map, dev_chains, n);
+}
+
+// the blocking entries: probes or maps up into the reflection staging, the chains or maps back; the stream is idle on return
+static int reflection_from_host(rt_ctx* c, const rt_reflection_desc* desc, int parts, const rt_probe* probes, const float* maps,
+                                uint32_t n, uint32_t max_depth, uint32_t seed, float* out, rt_radiance_stats* stats) {
+  ReflectionShape sh;
+  int r = reflection_desc_ok(c, desc, n, parts, &sh);
+  if (r < 0 || !c) return RT_ERR_INVALID;
+  const bool capture = (parts & RF_CAPTURE) != 0, filter = (parts & RF_FILTER) != 0;
+  if (n == 0) {
+    if (capture) {
+      reflection_no_work(c);
+      if (stats) *stats = c->rf_last;
+    }
+    return RT_OK;
+  }
+  if (!(capture ? (const void*)probes : (const void*)maps) || !out) return fail(c, RT_ERR_INVALID, std::string(kReflection) + ": NULL array");
+  if (capture && (r = reflection_pads_ok(c, probes, n, sh)) < 0) return r;
+  HIP_TRY(c, hipSetDevice(c->device));
+  ReflectionState& st = c->rfl;
+  const size_t map_bytes = (size_t)n * sh.map * 16, chain_bytes = (size_t)n * sh.chain * 16;
+  DeviceBuffer& result = filter ? st.chains : st.maps;
+  const size_t result_bytes = filter ? chain_bytes : map_bytes;
+  if ((r = ensure_buffer(c, result, result_bytes, true)) < 0) return r;
+  if (capture) {
+    if ((r = ensure_buffer(c, st.probes, (size_t)n * sizeof(rt_probe), true)) < 0) return r;
+    HIP_TRY(c, hipMemcpyAsync(st.probes.ptr, probes, (size_t)n * sizeof(rt_probe), hipMemcpyHostToDevice, c->stream));
+    if ((r = launch_reflection_capture(c, *desc, sh, st.probes.ptr, n, max_depth, seed, result.ptr, filter ? sh.chain : sh.map,
+                                       stats != nullptr)) < 0)
+      return r;
+    if (filter && (r = launch_reflection_filter(c, *desc, sh, result.ptr, sh.chain, result.ptr, n)) < 0) return r;
+  } else {
+    if ((r = ensure_buffer(c, st.maps, map_bytes, true)) < 0) return r;
+    HIP_TRY(c, hipMemcpyAsync(st.maps.ptr, maps, map_bytes, hipMemcpyHostToDevice, c->stream));
+    if ((r = launch_reflection_filter(c, *desc, sh, st.maps.ptr, sh.map, result.ptr, n)) < 0) return r;
+  }
+  HIP_TRY(c, hipMemcpyAsync(out, result.ptr, result_bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (capture && stats) return rt_reflection_stats(c, stats);
+  return RT_OK;
+}
+
+int rt_capture_reflection(rt_ctx* c, const rt_reflection_desc* desc, const rt_probe* probes, uint32_t n, uint32_t max_depth,
+                          uint32_t seed, float* out_maps, rt_radiance_stats* stats) {
+  return reflection_from_host(c, desc, RF_CAPTURE, probes, nullptr, n, max_depth, seed, out_maps, stats);
+}
+int rt_filter_reflection(rt_ctx* c, const rt_reflection_desc* desc, const float* maps, uint32_t n, float* out_chains) {
+  return reflection_from_host(c, desc, RF_FILTER, nullptr, maps, n, 0, 0, out_chains, nullptr);
+}
+int rt_bake_reflection(rt_ctx* c, const rt_reflection_desc* desc, const rt_probe* probes, uint32_t n, uint32_t max_depth,
+                       uint32_t seed, float* out_chains, rt_radiance_stats* stats) {
+  return reflection_from_host(c, desc, RF_CAPTURE | RF_FILTER, probes, nullptr, n, max_depth, seed, out_chains, stats);
 }
 
 // ---- the kernels of compute().  Variant 0, the one-pixel-per-lane megakernel: one tile per workgroup, no dynamic LDS.

@@ -729,6 +729,63 @@ static napi_value rtEncodeVolume(napi_env env, napi_callback_info info) {
   return make_int(env, rt_encode_volume((rt_ctx*)get_ptr(env, a[0]), desc, get_u32(env, a[2]), (const rt_probe_sh9*)volume, out, no));
 }
 
+/* ------------------------------------------------------- reflection probes (rt_bake_reflection, rt_filter_reflection, mi355rt.h) */
+/* the 32 bytes of an rt_reflection_desc in a typed array, and the texels of its level 0 and of a chain (0: the library will
+ * refuse the descriptor) */
+static const rt_reflection_desc* get_reflection_desc(napi_env env, napi_value v, size_t* map, size_t* chain) {
+  void* d = NULL;
+  size_t nd = 0;
+  if (!get_bytes(env, v, &d, &nd)) return NULL;
+  if (nd != sizeof(rt_reflection_desc)) {
+    napi_throw_range_error(env, NULL, "a reflection descriptor is 32 bytes");
+    return NULL;
+  }
+  const rt_reflection_desc* desc = (const rt_reflection_desc*)d;
+  *map = *chain = 0;
+  if (desc->size >= 8 && desc->size <= 512 && desc->levels >= 2 && desc->levels <= 32) {
+    *map = (size_t)desc->size * desc->size;
+    for (uint32_t m = 0; m < desc->levels; m++) *chain += (size_t)(desc->size >> m) * (desc->size >> m);
+  }
+  return desc;
+}
+/* (ctx, desc: 32 bytes, probes: Float32Array of 8 per probe, maxDepth, seed, out: Float32Array of a chain per probe, wantStats)
+ * -> status, or the stats object when wantStats and the call succeeded */
+static napi_value rtBakeReflection(napi_env env, napi_callback_info info) {
+  napi_value a[7];
+  void *probes = NULL, *out = NULL;
+  size_t np = 0, no = 0, map = 0, chain = 0;
+  bool want_stats = false;
+  if (!get_args(env, info, 7, a) || !get_bytes(env, a[2], &probes, &np) || !get_bytes(env, a[5], &out, &no)) return NULL;
+  const rt_reflection_desc* desc = get_reflection_desc(env, a[1], &map, &chain);
+  if (!desc) return NULL;
+  napi_get_value_bool(env, a[6], &want_stats);
+  const size_t n = np / sizeof(rt_probe);
+  if (np % sizeof(rt_probe) != 0 || n > 0x7fffffffu || no < n * chain * 16) {
+    napi_throw_range_error(env, NULL, "rtBakeReflection: probes must hold 8 floats per probe and out a chain of 4 floats per texel per probe");
+    return NULL;
+  }
+  rt_radiance_stats st;
+  const int rc = rt_bake_reflection((rt_ctx*)get_ptr(env, a[0]), desc, (const rt_probe*)probes, (uint32_t)n, get_u32(env, a[3]),
+                                    get_u32(env, a[4]), (float*)out, want_stats ? &st : NULL);
+  if (rc < 0 || !want_stats) return make_int(env, rc);
+  return radiance_stats_object(env, &st);
+}
+/* (ctx, desc: 32 bytes, maps: Float32Array of size * size * 4 per probe, out: Float32Array of a chain per probe) -> status */
+static napi_value rtFilterReflection(napi_env env, napi_callback_info info) {
+  napi_value a[4];
+  void *maps = NULL, *out = NULL;
+  size_t nm = 0, no = 0, map = 0, chain = 0;
+  if (!get_args(env, info, 4, a) || !get_bytes(env, a[2], &maps, &nm) || !get_bytes(env, a[3], &out, &no)) return NULL;
+  const rt_reflection_desc* desc = get_reflection_desc(env, a[1], &map, &chain);
+  if (!desc) return NULL;
+  const size_t n = map ? nm / (map * 16) : 0;
+  if ((map && nm % (map * 16) != 0) || n > 0x7fffffffu || no < n * chain * 16) {
+    napi_throw_range_error(env, NULL, "rtFilterReflection: maps must hold size * size texels of 4 floats per probe and out a chain per probe");
+    return NULL;
+  }
+  return make_int(env, rt_filter_reflection((rt_ctx*)get_ptr(env, a[0]), desc, (const float*)maps, (uint32_t)n, (float*)out));
+}
+
 /* ------------------------------------------------------- directional gathers (rt_gather_directional, mi355rt.h) */
 /* (ctx, points: Float32Array of 8 per point {position, t_max, normal, pad}, maxDepth, spp, seed, out: Float32Array of 16 per
  * point, four rows {sh[k].rgb, hit_fraction}, wantStats) -> status, or the stats object when wantStats and the call succeeded */
@@ -1040,6 +1097,7 @@ static napi_value Init(napi_env env, napi_value exports) {
                {"rtRayQueryStats", rtRayQueryStats}, {"rtTraceRadiance", rtTraceRadiance},
                {"rtGatherIrradiance", rtGatherIrradiance}, {"rtGatherProbes", rtGatherProbes}, {"rtBakePoints", rtBakePoints},
                {"rtBakeVolume", rtBakeVolume}, {"rtSampleVolume", rtSampleVolume}, {"rtEncodeVolume", rtEncodeVolume},
+               {"rtBakeReflection", rtBakeReflection}, {"rtFilterReflection", rtFilterReflection},
                {"rtGatherDirectional", rtGatherDirectional}, {"rtBakeAtlasDirectionalLightmap", rtBakeAtlasDirectionalLightmap},
                {"rtBakeIrradiance", rtBakeIrradiance}, {"rtBakeAtlasPoints", rtBakeAtlasPoints},
                {"rtBakeAtlasIrradiance", rtBakeAtlasIrradiance}, {"rtDilateAtlas", rtDilateAtlas},

@@ -85,6 +85,20 @@ export class WebGPURenderer {
   /** Seven layers of n texels, layer j holding the floats 4 j .. 4 j + 3 of every record; 'rgbe' is refused. */
   encodeVolume(desc: Uint8Array, volume: Float32Array, format: 'f32' | 'f16'):
     { data: Float32Array | Uint16Array; layers: 7; n: number; format: string };
+  /** Reflection probes (rt_bake_reflection / rt_filter_reflection).  A descriptor is the 32 bytes of an rt_reflection_desc:
+   *  level 0 of size x size octahedral texels {r, g, b, hitFraction}, `levels` levels with level m of side size >> m,
+   *  GGX-filtered at the roughness m / (levels - 1); spt samples per texel of a capture, filterSamples lobe samples per texel. */
+  static reflectionDesc(o: { size: number; levels: number; spt?: number; filterSamples?: number }): Uint8Array;
+  /** levels + 1 texel offsets of a chain's levels; the last is the length of a chain. */
+  static reflectionLevelOffsets(desc: Uint8Array): number[];
+  /** `data` holds a chain per probe, 4 floats per texel.  The stats are a radiance query's with rays = texels. */
+  bakeReflection(desc: Uint8Array, probes: Float32Array, maxDepth: number, opts?: { seed?: number; stats?: boolean }):
+    { data: Float32Array; n: number; chainTexels: number; offsets: number[]; stats?: RadianceQueryStats };
+  /** maps: size * size texels of 4 floats per probe; level 0 of each chain is its map word for word.  Needs no scene. */
+  filterReflection(desc: Uint8Array, maps: Float32Array): { data: Float32Array; n: number; chainTexels: number; offsets: number[] };
+  /** One encodeAtlas result per level of ONE chain; all three formats apply. */
+  encodeReflection(desc: Uint8Array, chain: Float32Array, format: 'f32' | 'f16' | 'rgbe'):
+    { data: Float32Array | Uint16Array | Uint32Array; width: number; height: number; format: string }[];
   /** Directional gathers (rt_gather_directional): points as for gatherIrradiance.  `data` holds 16 floats per point, four rows
    *  {sh[k].r, sh[k].g, sh[k].b, hitFraction}: the projection of the radiance arriving over spp uniform directions on the
    *  hemisphere of the normal onto Y0 and the y, z, x harmonics of band 1, in world space; row k is the texel of atlas layer k.

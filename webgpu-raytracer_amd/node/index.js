@@ -262,6 +262,50 @@ class WebGPURenderer {
     this._check(native.rtEncodeVolume(this._ctx, desc, f, volume, data), 'encodeVolume');
     return { data, layers: 7, n, format: ['f32', 'f16', 'rgbe'][f] };
   }
+  // ---- reflection probes (rt_bake_reflection, rt_filter_reflection): octahedral radiance maps of size x size texels {r, g, b,
+  // hitFraction} and their GGX-filtered chains, level m of side size >> m at the roughness m / (levels - 1).  A descriptor is
+  // the 32 bytes of an rt_reflection_desc, made by WebGPURenderer.reflectionDesc({size, levels, spt = 1, filterSamples = 256}).
+  static reflectionDesc(o) {
+    return new Uint8Array(Uint32Array.of(o.size >>> 0, o.levels >>> 0, (o.spt === undefined ? 1 : o.spt) >>> 0,
+      (o.filterSamples === undefined ? 256 : o.filterSamples) >>> 0, 0, 0, 0, 0).buffer);
+  }
+  // levels + 1 texel offsets: level m of a chain is the texels [offsets[m], offsets[m + 1]); the last is the length of a chain
+  static reflectionLevelOffsets(desc) {
+    const u = new Uint32Array(desc.buffer, desc.byteOffset, 8), off = [0];
+    if (u[1] > 32) throw new RangeError('reflection: levels');
+    for (let m = 0; m < u[1]; m++) off.push(off[m] + (u[0] >>> m) * (u[0] >>> m));
+    return off;
+  }
+  // probes as for gatherProbes.  opts: {seed = 0, stats = false}.  Result: .data holds a chain per probe, 4 floats per texel; .n
+  // probes, .chainTexels, .offsets; with stats the capture's .stats (rays = texels).
+  bakeReflection(desc, probes, maxDepth, opts = {}) {
+    if (!(probes instanceof Float32Array) || probes.length % 8 !== 0) throw new TypeError('bakeReflection: a Float32Array of 8 floats per probe');
+    const n = probes.length / 8, offsets = WebGPURenderer.reflectionLevelOffsets(desc), chainTexels = offsets[offsets.length - 1];
+    const data = new Float32Array(n * chainTexels * 4);
+    const r = native.rtBakeReflection(this._ctx, desc, probes, maxDepth >>> 0, (opts.seed || 0) >>> 0, data, !!opts.stats);
+    if (typeof r === 'number') this._check(r, 'bakeReflection');
+    const out = { data, n, chainTexels, offsets };
+    if (typeof r === 'object' && r) out.stats = r;
+    return out;
+  }
+  // maps: size * size texels of 4 floats per probe.  Result as for bakeReflection, level 0 the map word for word.  Needs no scene.
+  filterReflection(desc, maps) {
+    const offsets = WebGPURenderer.reflectionLevelOffsets(desc), chainTexels = offsets[offsets.length - 1], map = offsets[1] * 4;
+    if (!(maps instanceof Float32Array) || maps.length % map !== 0) throw new TypeError('filterReflection: a Float32Array of size * size * 4 floats per probe');
+    const n = maps.length / map;
+    const data = new Float32Array(n * chainTexels * 4);
+    this._check(native.rtFilterReflection(this._ctx, desc, maps, data), 'filterReflection');
+    return { data, n, chainTexels, offsets };
+  }
+  // chain: the floats of ONE chain.  Result: one encodeAtlas result per level, in 'f32', 'f16' or 'rgbe' (radiance is not
+  // signed, so the shared-exponent format applies).
+  encodeReflection(desc, chain, format) {
+    const offsets = WebGPURenderer.reflectionLevelOffsets(desc), size = new Uint32Array(desc.buffer, desc.byteOffset, 8)[0];
+    if (!(chain instanceof Float32Array) || chain.length !== offsets[offsets.length - 1] * 4) throw new TypeError('encodeReflection: the floats of one chain');
+    const out = [];
+    for (let m = 0; m + 1 < offsets.length; m++) out.push(this.encodeAtlas(chain.slice(offsets[m] * 4, offsets[m + 1] * 4), size >>> m, size >>> m, format));
+    return out;
+  }
   // ---- directional gathers (rt_gather_directional): the radiance arriving at the caller's surface points, over spp directions
   // drawn uniformly on the hemisphere of the normal on the device, projected onto the four real spherical harmonics of bands 0
   // .. 1 in world space.  points as for gatherIrradiance.  opts: {seed = 0, stats = false}.  Result: 16 floats per point in

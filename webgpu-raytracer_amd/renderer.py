@@ -208,6 +208,14 @@ def load_library(path=None):
         "rt_sample_volume_device": (i32, [vp, vp, vp, vp, u32, vp]),
         "rt_encode_volume": (i32, [vp, vp, u32, vp, vp, ctypes.c_size_t]),
         "rt_encode_volume_device": (i32, [vp, vp, u32, vp, vp, ctypes.c_size_t]),
+        # reflection probes
+        "rt_capture_reflection": (i32, [vp, vp, vp, u32, u32, u32, vp, vp]),
+        "rt_capture_reflection_device": (i32, [vp, vp, vp, u32, u32, u32, vp]),
+        "rt_filter_reflection": (i32, [vp, vp, vp, u32, vp]),
+        "rt_filter_reflection_device": (i32, [vp, vp, vp, u32, vp]),
+        "rt_bake_reflection": (i32, [vp, vp, vp, u32, u32, u32, vp, vp]),
+        "rt_bake_reflection_device": (i32, [vp, vp, vp, u32, u32, u32, vp]),
+        "rt_reflection_stats": (i32, [vp, vp]),
         # directional gathers
         "rt_gather_directional": (i32, [vp, vp, u32, u32, u32, u32, vp, vp]),
         "rt_gather_directional_device": (i32, [vp, vp, u32, u32, u32, u32, vp]),
@@ -260,6 +268,8 @@ EXPORTED_SYMBOLS = (
     "rt_gather_irradiance rt_gather_irradiance_device rt_irradiance_gather_stats "
     "rt_gather_probes rt_gather_probes_device rt_probe_gather_stats "
     "rt_bake_volume rt_bake_volume_device rt_sample_volume rt_sample_volume_device rt_encode_volume rt_encode_volume_device "
+    "rt_capture_reflection rt_capture_reflection_device rt_filter_reflection rt_filter_reflection_device rt_bake_reflection "
+    "rt_bake_reflection_device rt_reflection_stats "
     "rt_gather_directional rt_gather_directional_device rt_directional_gather_stats "
     "rt_bake_points rt_bake_points_device rt_bake_irradiance "
     "rt_bake_atlas_points rt_bake_atlas_points_device rt_bake_atlas_irradiance "
@@ -360,6 +370,65 @@ def _volume_desc(desc):
     if d.dtype != VOLUME_DESC_DTYPE or d.size != 1:
         raise ValueError("a volume descriptor is one VOLUME_DESC_DTYPE record (volume_desc builds it)")
     return d.reshape(())
+
+
+# reflection probes: mirror of rt_reflection_desc; a map is (size, size, 4) float32 {r, g, b, hit_fraction} in octahedral layout,
+# a chain (chain_texels, 4) float32 with level m at reflection_level_offsets(size, levels)[m]
+REFLECTION_DESC_DTYPE = np.dtype([("size", np.uint32), ("levels", np.uint32), ("spt", np.uint32), ("filter_samples", np.uint32),
+                                  ("reserved", np.uint32, (4,))])
+
+
+def reflection_desc(size, levels, spt=1, filter_samples=256):
+    """A REFLECTION_DESC_DTYPE record (shape ()): level 0 of size x size texels, `levels` levels with level m of side size >> m
+    at the roughness m / (levels - 1); spt samples per texel of a capture; filter_samples lobe samples per texel of a filter."""
+    d = np.zeros((), REFLECTION_DESC_DTYPE)
+    d["size"], d["levels"], d["spt"], d["filter_samples"] = size, levels, spt, filter_samples
+    return d
+
+
+def reflection_level_offsets(size, levels):
+    """levels + 1 texel offsets: level m of a chain is the texels [offsets[m], offsets[m + 1]) - (size >> m)^2 of them, texel
+    (i, j) at j * (size >> m) + i - and offsets[levels] is the length of a chain."""
+    sides = np.array([int(size) >> m for m in range(int(levels))], np.int64)
+    return np.concatenate([[0], np.cumsum(sides * sides)])
+
+
+def octa_directions(size):
+    """The unit directions of the texel centres of a size x size octahedral map: (size, size, 3) float64, [j, i] for texel
+    (i, j) - the mapping of the reflection rule, in double precision.  Pure numpy."""
+    c = (np.arange(int(size)) + 0.5) / int(size) * 2.0 - 1.0
+    px, py = np.meshgrid(c, c, indexing="xy")
+    nz = 1.0 - np.abs(px) - np.abs(py)
+    t = np.clip(-nz, 0.0, 1.0)
+    nx = px + np.where(px >= 0.0, -t, t)
+    ny = py + np.where(py >= 0.0, -t, t)
+    n = np.stack([nx, ny, nz], axis=-1)
+    return n / np.linalg.norm(n, axis=-1, keepdims=True)
+
+
+def _reflection_desc(desc):
+    d = np.ascontiguousarray(desc)
+    if d.dtype != REFLECTION_DESC_DTYPE or d.size != 1:
+        raise ValueError("a reflection descriptor is one REFLECTION_DESC_DTYPE record (reflection_desc builds it)")
+    return d.reshape(())
+
+
+def _reflection_chain_texels(d):
+    """texels of a chain; 0 for a descriptor the library will refuse"""
+    size, levels = int(d["size"]), int(d["levels"])
+    if not (8 <= size <= 512) or not (2 <= levels <= 32):
+        return 0
+    return int(reflection_level_offsets(size, levels)[-1])
+
+
+def _probe_array(probes, what):
+    p = np.ascontiguousarray(probes)
+    if p.dtype == PROBE_DTYPE:
+        p = p.reshape(-1).view(np.float32).reshape(-1, 8)
+    p = np.ascontiguousarray(p, dtype=np.float32)
+    if p.ndim != 2 or p.shape[1] != 8:
+        raise ValueError("%s expects an (n, 8) float32 array" % what)
+    return p
 
 
 # directional gathers: mirror of rt_directional; points are rt_gather_point, stats an RtRadianceStats (rays = points)
@@ -885,6 +954,97 @@ class WebGPURenderer:
         fmt = _lightmap_format(format)
         out = np.empty((7, int(d["nz"]), int(d["ny"]), int(d["nx"]), 4), np.float16 if fmt == RT_LIGHTMAP_F16 else np.float32)
         self._check(self.L.rt_encode_volume(self.ctx, _ptr(d), fmt, _ptr(v), _ptr(out), out.nbytes), "encodeVolume")
+        return out
+
+    # ---- reflection probes: octahedral radiance maps and their GGX-filtered chains (rt_capture_reflection, rt_filter_reflection,
+    # rt_bake_reflection) ----
+    def captureReflection(self, desc, probes, max_depth, seed=0, stats=False):
+        """desc: a REFLECTION_DESC_DTYPE record (reflection_desc); probes: (n, 8) float32 in the rt_probe layout (or a
+        PROBE_DTYPE array), pad + size * size <= 2^31.  Returns the maps, (n, size, size, 4) float32 {r, g, b, hit_fraction},
+        [p, j, i] for texel (i, j) of probe p: the radiance arriving at the probe through each octahedral texel, the mean of
+        desc.spt jittered samples - and with stats=True the pair (maps, stats dict of rt_radiance_stats with rays = texels: the
+        counting kernel runs)."""
+        d = _reflection_desc(desc)
+        p = _probe_array(probes, "captureReflection")
+        n, size = p.shape[0], int(d["size"])
+        out = np.empty((n, size, size, 4), np.float32)
+        st = RtRadianceStats()
+        self._check(self.L.rt_capture_reflection(self.ctx, _ptr(d), _ptr(p) if n else None, n, int(max_depth),
+                                                 int(seed) & 0xffffffff, _ptr(out) if out.size else None,
+                                                 ctypes.addressof(st) if stats else None), "captureReflection")
+        return (out, st.as_dict()) if stats else out
+
+    def captureReflectionDevice(self, desc, probes_ptr, n, out_ptr, max_depth, seed=0):
+        """Enqueue a capture on device arrays (n rt_probe at probes_ptr, n maps of size * size 16-byte texels to out_ptr) on the
+        context's stream; no host synchronisation."""
+        d = _reflection_desc(desc)
+        self._check(self.L.rt_capture_reflection_device(self.ctx, _ptr(d), ctypes.c_void_p(probes_ptr or 0), int(n), int(max_depth),
+                                                        int(seed) & 0xffffffff, ctypes.c_void_p(out_ptr or 0)),
+                    "captureReflectionDevice")
+
+    def filterReflection(self, desc, maps):
+        """maps: (n, size, size, 4) float32 (or one (size, size, 4) map).  Returns the chains, (n, chain_texels, 4) float32:
+        level 0 the map word for word, level m >= 1 its GGX-filtered form at the roughness m / (levels - 1), at the texel
+        offsets of reflection_level_offsets.  Needs no scene."""
+        d = _reflection_desc(desc)
+        size = int(d["size"])
+        m = np.ascontiguousarray(maps, dtype=np.float32)
+        if m.ndim == 3:
+            m = m[None]
+        if m.ndim != 4 or m.shape[1:] != (size, size, 4):
+            raise ValueError("filterReflection expects (n, size, size, 4) float32 maps")
+        n = m.shape[0]
+        out = np.empty((n, _reflection_chain_texels(d), 4), np.float32)
+        self._check(self.L.rt_filter_reflection(self.ctx, _ptr(d), _ptr(m) if n else None, n, _ptr(out) if out.size else None),
+                    "filterReflection")
+        return out
+
+    def filterReflectionDevice(self, desc, maps_ptr, n, chains_ptr):
+        """Enqueue a filter on device arrays: n packed maps at maps_ptr into n chains at chains_ptr - or, with maps_ptr ==
+        chains_ptr, in place on chains whose level 0 is there already (the layout of a bake).  No host synchronisation."""
+        d = _reflection_desc(desc)
+        self._check(self.L.rt_filter_reflection_device(self.ctx, _ptr(d), ctypes.c_void_p(maps_ptr or 0), int(n),
+                                                       ctypes.c_void_p(chains_ptr or 0)), "filterReflectionDevice")
+
+    def bakeReflection(self, desc, probes, max_depth, seed=0, stats=False):
+        """captureReflection straight into level 0 of each chain, then filterReflection in place, without leaving the device:
+        (n, chain_texels, 4) float32 - and with stats=True the pair (chains, stats dict of the capture)."""
+        d = _reflection_desc(desc)
+        p = _probe_array(probes, "bakeReflection")
+        n = p.shape[0]
+        out = np.empty((n, _reflection_chain_texels(d), 4), np.float32)
+        st = RtRadianceStats()
+        self._check(self.L.rt_bake_reflection(self.ctx, _ptr(d), _ptr(p) if n else None, n, int(max_depth), int(seed) & 0xffffffff,
+                                              _ptr(out) if out.size else None, ctypes.addressof(st) if stats else None),
+                    "bakeReflection")
+        return (out, st.as_dict()) if stats else out
+
+    def bakeReflectionDevice(self, desc, probes_ptr, n, chains_ptr, max_depth, seed=0):
+        """Enqueue a bake on device arrays (n rt_probe at probes_ptr, n chains to chains_ptr) on the context's stream; no host
+        synchronisation."""
+        d = _reflection_desc(desc)
+        self._check(self.L.rt_bake_reflection_device(self.ctx, _ptr(d), ctypes.c_void_p(probes_ptr or 0), int(n), int(max_depth),
+                                                     int(seed) & 0xffffffff, ctypes.c_void_p(chains_ptr or 0)),
+                    "bakeReflectionDevice")
+
+    def reflectionStats(self):
+        """rt_radiance_stats of the last reflection capture or bake as a dict (blocking)."""
+        st = RtRadianceStats()
+        self._check(self.L.rt_reflection_stats(self.ctx, ctypes.addressof(st)), "reflectionStats")
+        return st.as_dict()
+
+    def encodeReflection(self, desc, chain, format):
+        """chain: one chain, (chain_texels, 4) float32.  Returns the list of its levels, each encodeAtlas of the level's (S, S, 4)
+        texels in the format "f32", "f16" or "rgbe" (radiance is not signed, so all three apply)."""
+        d = _reflection_desc(desc)
+        off = reflection_level_offsets(int(d["size"]), int(d["levels"]))
+        c = np.ascontiguousarray(chain, dtype=np.float32)
+        if c.shape != (int(off[-1]), 4):
+            raise ValueError("encodeReflection expects one chain, (chain_texels, 4) float32")
+        out = []
+        for m in range(int(d["levels"])):
+            side = int(d["size"]) >> m
+            out.append(self.encodeAtlas(c[off[m]:off[m + 1]].reshape(side, side, 4), format))
         return out
 
     # ---- directional gathers: SH radiance of bands 0 .. 1 over the hemisphere of surface points (rt_gather_directional) ----
