@@ -878,6 +878,99 @@ int rt_denoise_atlas(rt_ctx* ctx, const rt_denoise_desc* desc, const float* atla
 int rt_denoise_atlas_device(rt_ctx* ctx, const rt_denoise_desc* desc, const void* dev_in, const void* dev_points,
                             const void* dev_texels, uint32_t n, void* dev_out);
 
+/* ---- frame denoise: "a clean frame from one sample per pixel", an edge-stopped a-trous filter of the frame ahead of present()
+ * ----
+ * The live loop shows a 1-spp image almost all the time, and the post pass has a 3 x 3 bilateral only.  After every compute()
+ * the guides an edge-stopped filter needs are in HBM: the octahedral normal with triangle and instance id, the clip depth and
+ * the unorm8 albedo, 24 B per pixel.  The filter runs there (csrc/k_frame_denoise.hip.h) and writes an image in the
+ * accumulator's format, which present() can read through rt_bind_present_source or by itself (rt_set_present_denoise).
+ *
+ * THE FRAME DENOISE RULE.  All arithmetic is f32, unfused (no FMA contraction), in the order written, with rt_div / rt_sqrt /
+ * rt_exp / rt_max / rt_abs / rt_normalize / rt_length / rt_from_unorm8 of mi355rt_math.h; `/` below is the language's division
+ * where the post pass uses it.  Inputs: an rt_frame_denoise_desc {passes, step, flags, normal_cos, plane_eps, sigma_lum}
+ * (mi355rt_layout.h); the context's accumulation buffer A (a bound one included), W x H texels {r, g, b, a}, pixel (x, y) at i
+ * = y * W + x; the G-buffer of the last compute() - the planes rt_read_gbuffer reads, the slot of a frame traced ahead
+ * included: albedo word alb[i], normal_id[i] = {ox, oy, bits(tri), bits(inst)}, depth[i]; and U, the uniform block of that
+ * frame (rt_read_uniforms).  lum(r, g, b) = (0.2126f * r + 0.7152f * g) + 0.0722f * b.
+ *   background  pixel i is BACKGROUND iff the alpha byte of alb[i] is 0 (k_primary_visibility writes 0 for a miss, 255 for a
+ *               hit), else a SURFACE.
+ *   radiance    rad(x, y), coordinates clamped to the image: get_radiance of the post pass, a <= 0 ? (0, 0, 0) : (r / a, g / a,
+ *               b / a).
+ *   modulation  m[i] = (1, 1, 1) without RT_FRAME_DENOISE_DEMODULATE and on the background; else m[i][c] =
+ *               rt_max(rt_from_unorm8(byte c of alb[i]), RT_FRAME_DENOISE_MIN_ALBEDO), c = 0 .. 2.  alpha[i] = a > 0 ? 1 : 0.
+ *   quantity    q(x, y), coordinates clamped: (rt_div(rad[0], m[0]), rt_div(rad[1], m[1]), rt_div(rad[2], m[2])) - what the
+ *               passes filter.
+ *   variance    m1 = m2 = +0; for dy = -1 .. 1 outer, dx = -1 .. 1 inner: l = lum(q(x + dx, y + dy)); m1 = m1 + l; m2 = m2 + l
+ *               * l.  mean = rt_div(m1, 9.0f); var = rt_max(rt_div(m2, 9.0f) - mean * mean, 0.0f), as the post pass forms it.
+ *   guide       of a surface: the normal N = n / |n| by rt_normalize of n = (ox, oy, 1.0f - rt_abs(ox) - rt_abs(oy)) with t =
+ *               rt_saturate(-n.z) and n.x += (n.x >= 0 ? -t : t), n.y likewise (unpack_normal of the path tracer); the
+ *               instance, the bits of normal_id[i].w; the world position P, the inverse of k_primary_visibility's depth on the
+ *               pixel's own jittered pinhole ray: center = ll + hor * 0.5f + ver * 0.5f; focal = rt_length(center - eye); u =
+ *               ((float)x + 0.5f + U.jitter[0] * (float)W) / (float)W; v = 1.0f - ((float)y + 0.5f + U.jitter[1] * (float)H) /
+ *               (float)H; d = ll + u * hor + v * ver - eye (left to right, per component); ca = 10000.0f / (10000.0f -
+ *               0.001f); cb = (10000.0f * 0.001f) / (10000.0f - 0.001f); z_view = rt_div(cb, ca - depth[i]); t = rt_div(z_view,
+ *               focal); P[c] = eye[c] + d[c] * t.  The stored depth is ca - cb / z_view with ca one ulp above 1, so z_view
+ *               comes back in steps of z^2 * 2^-24 / cb = 6e-5 z^2: DESIGN.md 4.3b.  The guide of a background pixel is all
+ *               zero.  A guide is 32 bytes, {P.xyz, bits(inst)} {N.xyz, bits(surface ? 1 : 0)}: the unit normal as three f32,
+ *               so that no tap decodes anything.
+ *   prepare     one pass over the image, out of place: colour texel col[i] = {q(x, y), var}, guide[i], modulation texel {m[i],
+ *               alpha[i]}.
+ *   one pass    at spacing s, out of place.  A background pixel's 16 bytes are copied bit for bit.  A surface pixel p = (x, y)
+ *               with centre values lum_p = lum(col[p].rgb), den = sigma_lum * rt_sqrt(col[p].w) + 1e-4f visits the taps (dx,
+ *               dy), dy = -2 .. 2 outer and dx = -2 .. 2 inner; the tap pixel is q = (x + dx * s, y + dy * s) and h = k[|dx|] *
+ *               k[|dy|] with k = {0.375f, 0.25f, 0.0625f}, as in the atlas rule.
+ *   accepted    the centre tap always.  Any other tap iff all of these hold (a NaN fails each float comparison):  q is inside
+ *               the image and a surface;  with RT_FRAME_DENOISE_SAME_INSTANCE, q's instance word equals p's;  (N.x * Nq.x +
+ *               N.y * Nq.y) + N.z * Nq.z >= normal_cos;  with e = Pq - P, rt_abs((N.x * e.x + N.y * e.y) + N.z * e.z) <=
+ *               plane_eps.
+ *   weight      of an accepted tap, the centre included: w = h when !(sigma_lum > 0) - no exponential is evaluated - else w =
+ *               h * rt_exp(rt_div(-rt_abs(lum(col[q].rgb) - lum_p), den)).
+ *   result      acc[0 .. 2], vacc and wsum start at +0; for every accepted tap in visiting order acc[c] = acc[c] + w *
+ *               col[q][c], vacc = vacc + (w * w) * col[q].w, wsum = wsum + w.  out = {rt_div(acc[c], wsum), rt_div(vacc, wsum
+ *               * wsum)}: the weighted mean and the variance of that mean.
+ *   finish      after the last pass: out[i] = {col[i][0] * m[i][0], col[i][1] * m[i][1], col[i][2] * m[i][2], alpha[i]} - the
+ *               accumulator's format with weight 1, so present() can read it as it stands.
+ *   a call      prepare, then `passes` passes, pass p at spacing `step << p`, by ping-pong through two colour images the
+ *               library owns, then finish.  The accumulation buffer and the G-buffer are never written.
+ * Three things follow.  (1) {step 1, passes 3} is prepare, the passes at 1, 2 and 4 and finish, word for word.  (2) A result
+ * word depends only on the inputs, never on the form of a pass, tile shape or scheduling: no atomics, no cross-lane sums,
+ * every sum in a fixed order.  (3) Background radiance passes through bit for bit (rad * 1) and never enters a surface.
+ * The forms of a pass: k_frame_pass_lds stages the tile's window in LDS (spacings 1 .. 4, where the window fits),
+ * k_frame_pass_direct reads its taps through L1 / L2 (every spacing).  rt_set_frame_denoise_form: 0 = auto (per spacing, what
+ * was measured faster, DESIGN.md 4.3b: the LDS form at spacings 1 .. 3, the direct form from 4), 1 = LDS, 2 = direct; 1 is
+ * refused by a call with a spacing above 4.
+ * THE ALBEDO PLANE IS THE RENDER TARGET: present() overwrites it.  The outputs of the prepare stage are therefore kept, keyed
+ * on a per-context count of dispatches that wrote a G-buffer: after a present() with no compute() between, the calls reuse
+ * them when flags has the same DEMODULATE bit and the accumulation buffer has not been written through the API since
+ * (rt_write_accum, rt_reset_accum, rt_bind_accum drop them, as do rt_resize, the uploads and rt_set_scene); else they fail with
+ * RT_ERR_NOT_READY, "frame denoise: the albedo plane was overwritten by present(); call compute first".
+ * Refusals, all RT_ERR_INVALID with messages that begin "frame denoise:", made before anything is enqueued: a NULL
+ * descriptor or output, passes == 0 or > 5, step == 0, step << (passes - 1) > RT_FRAME_DENOISE_MAX_STEP (16), an unknown flag
+ * bit, a non-zero reserved word, an output that is the accumulation buffer, a capacity below W * H * 16, a forced LDS form with
+ * a spacing above 4.  Without a screen or a G-buffer (no rt_resize, no compute() yet): RT_ERR_NOT_READY.  The float
+ * parameters are not validated: a NaN normal_cos rejects every tap but the centre.
+ * Not built: temporal reprojection and moment history (SVGF's temporal half; the reference's TAA in the post pass stays the
+ * only temporal term); separate treatment of specular and emissive surfaces under demodulation (a light's radiance is
+ * divided by its albedo like any other); stripes and ranks (a rank's G-buffer covers only its own rows: refused).
+ * The two explicit calls leave accumulation, history, counters, the G-buffer, frames traced ahead and every query's state
+ * unchanged.
+ *   rt_denoise_frame          blocking, one fence: filters into a buffer of the library's and copies W * H * 16 bytes out.
+ *   rt_denoise_frame_device   enqueue only, on the context's stream: dev_out is W * H float4 on the context's device, may
+ *                             afterwards be given to rt_bind_present_source, and must not be the accumulation buffer.
+ *   rt_set_present_denoise    desc != NULL: from now on rt_present filters into a buffer the context owns and the post pass
+ *                             reads that; NULL (the default) restores the plain path exactly.  Refused, with an explicit
+ *                             message, while a present source is bound, on a rank (rt_dist_init) and with stripes on; and
+ *                             while it is set, rt_bind_present_source(non-NULL), rt_dist_init and rt_set_stripes(count > 1)
+ *                             are refused.
+ *   rt_set_frame_denoise_form see above.
+ *   rt_frame_denoise_stats    blocking: stream times of the last call's stages (an event pair of its own: no RT_TIMER_* entry),
+ *                             the form of every pass and whether the cache was hit. */
+int rt_denoise_frame(rt_ctx* ctx, const rt_frame_denoise_desc* desc, float* out_rgba32f, size_t cap_bytes);
+int rt_denoise_frame_device(rt_ctx* ctx, const rt_frame_denoise_desc* desc, void* dev_out);
+int rt_set_present_denoise(rt_ctx* ctx, const rt_frame_denoise_desc* desc_or_null);
+int rt_set_frame_denoise_form(rt_ctx* ctx, int form);
+int rt_frame_denoise_stats(rt_ctx* ctx, rt_frame_denoise_report* out);
+
 /* ---- lightmaps: "the finished lightmap of these instances, in the texel format a renderer loads", in one call ----
  * The four sections above are the stages of a lightmap: points, gather, filter, gutter.  A caller who chains their host
  * entries pays a second point pass for the filter's guides and two more round trips of the atlas, and receives 16 bytes per

@@ -244,6 +244,33 @@ typedef struct rt_denoise_desc { /* 32 B */
   uint32_t reserved[1];       /* 0 */
 } rt_denoise_desc;
 
+/* ---- frame denoise (rt_denoise_frame, mi355rt.h): the G-buffer-guided a-trous filter of a frame ---- */
+#define RT_FRAME_DENOISE_MAX_STEP 16u
+#define RT_FRAME_DENOISE_MAX_PASSES 5u
+#define RT_FRAME_DENOISE_DEMODULATE 1u    /* filter radiance / albedo, multiply the albedo back after the last pass */
+#define RT_FRAME_DENOISE_SAME_INSTANCE 2u /* a tap must lie on the centre's instance */
+#define RT_FRAME_DENOISE_MIN_ALBEDO 0.00392156886f /* f32(1 / 255): the least albedo component a radiance is divided by */
+typedef struct rt_frame_denoise_desc { /* 32 B */
+  uint32_t passes;            /* 1 .. 5; pass p has the spacing step << p */
+  uint32_t step;              /* tap spacing of the first pass, in pixels: >= 1, step << (passes - 1) <= RT_FRAME_DENOISE_MAX_STEP */
+  uint32_t flags;             /* RT_FRAME_DENOISE_*; any other bit is refused */
+  float normal_cos;           /* a tap's normal must have at least this dot product with the centre's */
+  float plane_eps;            /* a tap's position lies at most this far from the centre's tangent plane */
+  float sigma_lum;            /* luminance stop in standard deviations; <= 0: none, no exponential is evaluated */
+  uint32_t reserved[2];       /* 0 */
+} rt_frame_denoise_desc;
+/* what rt_frame_denoise_stats reports: stream times (ms, device events) of the last rt_denoise_frame* call or filtered present() */
+typedef struct rt_frame_denoise_report { /* 48 B */
+  float prepare_ms;           /* k_frame_prepare; 0 when the cache was hit */
+  float pass_ms[5];           /* per pass; 0 beyond `passes` */
+  float finish_ms;            /* k_frame_finish */
+  uint32_t passes;
+  uint8_t form[5];            /* per pass: 1 = LDS form, 2 = direct form; 0 beyond `passes` */
+  uint8_t cache_hit;          /* 1: the prepare stage's outputs were those of an earlier call on the same G-buffer */
+  uint8_t pad[2];
+  uint32_t reserved[2];
+} rt_frame_denoise_report;
+
 /* ---- lightmaps (rt_bake_atlas_lightmap, mi355rt.h): an atlas bake, its filter, its gutter fill and its texel format ---- */
 #define RT_LIGHTMAP_F32 0u    /* 16 B per texel: {r, g, b, w} as the bakes return it */
 #define RT_LIGHTMAP_F16 1u    /* 8 B per texel: four halves, w included */
@@ -279,6 +306,8 @@ static_assert(__builtin_offsetof(rt_reflection_desc, size) == 0 && __builtin_off
                   __builtin_offsetof(rt_reflection_desc, reserved) == 16,
               "rt_reflection_desc: four words, then four reserved ones");
 static_assert(sizeof(rt_denoise_desc) == 32, "rt_denoise_desc is 32 bytes");
+static_assert(sizeof(rt_frame_denoise_desc) == 32, "rt_frame_denoise_desc is 32 bytes");
+static_assert(sizeof(rt_frame_denoise_report) == 48, "rt_frame_denoise_report is 48 bytes");
 static_assert(sizeof(rt_dilate_desc) == 32, "rt_dilate_desc is 32 bytes");
 static_assert(sizeof(rt_bake_desc) == 32, "rt_bake_desc is 32 bytes");
 static_assert(sizeof(rt_bake_atlas_desc) == 32, "rt_bake_atlas_desc is 32 bytes");

@@ -90,6 +90,26 @@ struct DenoiseState {
   DeviceBuffer index, scratch, in, out, points, texels;
 };
 
+// What the frame denoiser (rt_denoise_frame, rt_set_present_denoise) keeps between calls, kept and grown, and dropped by
+// rt_resize: the outputs of the prepare stage (colour, guides, modulation) with the key they were made under - present()
+// overwrites the albedo plane, so a call after it can only reuse them - the two colour images of the ping-pong, the filtered
+// image of the host entry and of a filtered present(), the albedo plane of a frame traced ahead into the main planes
+// (rt_set_lookahead), the events around every stage of the last call and its stats.
+struct DenoiseFrameState {
+  DeviceBuffer col, guide, mod, ping, pong, out, albedo_keep;
+  bool cache_valid = false;
+  uint64_t cache_gen = 0, cache_epoch = 0;
+  uint32_t cache_flags = 0;
+  bool keep_valid = false;          // albedo_keep holds the albedo of the last frame of the dispatch in flight
+  bool wanted = false;              // a frame-denoise call was made on this context: dispatches that trace ahead keep that plane
+  bool present_on = false;
+  rt_frame_denoise_desc present_desc = {};
+  int form = 0;                     // rt_set_frame_denoise_form
+  EventPair ev[2 + RT_FRAME_DENOISE_MAX_PASSES];   // prepare, finish, the passes
+  bool ev_ready = false, timed = false;
+  rt_frame_denoise_report last = {};
+};
+
 // What a lightmap bake (rt_bake_atlas_lightmap) and the encode entries (rt_encode_atlas) keep between calls beyond the state of
 // the stages they are made of, kept and grown: the filtered atlas, the gutter fill's count, the encoded atlas and the staged
 // input of the host encode entry.
@@ -270,6 +290,9 @@ struct rt_ctx {
   BakeState bk;
   DilateState dl;
   DenoiseState dn;
+  DenoiseFrameState fd;
+  uint64_t gbuf_gen = 0;            // dispatches and consumed frames that made a G-buffer current: the key of fd's cache
+  bool albedo_plane_valid = false;  // the render target holds the albedo a compute() wrote (present() overwrites it)
   LightmapState lm;
   VolumeState vol;
   // reflection probes: a path-query kind of their own (counter shards, an event pair per radiance launch of the last call,
@@ -1034,6 +1057,11 @@ int rt_resize(rt_ctx* c, uint32_t width, uint32_t height) {
   }
   c->width = width;
   c->height = height;
+  // the frame denoiser's images were sized for the old screen, and the new G-buffer is empty
+  for (DeviceBuffer* b : {&c->fd.col, &c->fd.guide, &c->fd.mod, &c->fd.ping, &c->fd.pong, &c->fd.out, &c->fd.albedo_keep}) b->reset();
+  c->fd.cache_valid = c->fd.keep_valid = false;
+  c->gbuf_gen = 0;
+  c->albedo_plane_valid = false;
   // A bound accumulation / present buffer was sized for the old screen: it is dropped, and until the caller binds
   // again (rt_bind_accum / rt_bind_present_source, NULL included) compute() and present() refuse to run instead of
   // silently rendering into the internal buffer while the caller keeps reducing its stale one.
@@ -1049,6 +1077,7 @@ int rt_resize(rt_ctx* c, uint32_t width, uint32_t height) {
 int rt_reset_accum(rt_ctx* c) {
   if (!c) return RT_ERR_INVALID;
   if (!c->accum.ptr) return RT_OK;  // `if (!this.accumulateBuffer) return;`
+  c->fd.cache_valid = false;   // the frame denoiser's colour image was made from the old accumulation
   HIP_TRY(c, hipSetDevice(c->device));
   HIP_TRY(c, hipMemsetAsync(accum_ptr(c), 0, (size_t)c->width * c->height * 16, c->stream));
   return RT_OK;
@@ -2946,6 +2975,220 @@ int rt_denoise_atlas(rt_ctx* c, const rt_denoise_desc* d, const float* atlas_in,
   return RT_OK;
 }
 
+// ---- frame denoise: the G-buffer-guided a-trous filter of mi355rt.h "frame denoise" as one prepare launch (or its cached
+// outputs), `passes` launches in the form picked per pass, and the finish (k_frame_denoise.hip.h).
+static const char* const kFrameDenoise = "frame denoise";
+// a refusal that needs no context: without one the message is what rt_last_error(NULL) returns
+static int frame_denoise_fail(rt_ctx* c, const std::string& what) {
+  const std::string msg = std::string(kFrameDenoise) + ": " + what;
+  if (!c) g_create_error = msg;
+  return fail(c, RT_ERR_INVALID, msg);
+}
+static int frame_denoise_desc_ok(rt_ctx* c, const rt_frame_denoise_desc* d) {
+  if (!d) return frame_denoise_fail(c, "NULL descriptor");
+  if (d->reserved[0] | d->reserved[1]) return frame_denoise_fail(c, "reserved words must be 0");
+  if (d->flags & ~(RT_FRAME_DENOISE_DEMODULATE | RT_FRAME_DENOISE_SAME_INSTANCE)) return frame_denoise_fail(c, "unknown flag bit");
+  if (d->passes == 0 || d->passes > RT_FRAME_DENOISE_MAX_PASSES) return frame_denoise_fail(c, "passes must be 1 .. 5");
+  if (d->step == 0) return frame_denoise_fail(c, "step must be >= 1");
+  // step <= 16 and passes <= 5: the shift cannot overflow
+  if (d->step > RT_FRAME_DENOISE_MAX_STEP || (d->step << (d->passes - 1)) > RT_FRAME_DENOISE_MAX_STEP)
+    return frame_denoise_fail(c, "step << (passes - 1) must be <= 16");
+  return RT_OK;
+}
+// what a call needs of the context, checked before anything is enqueued
+static int frame_denoise_ctx_ok(rt_ctx* c, const rt_frame_denoise_desc* d) {
+  const std::string w(kFrameDenoise);
+  if (c->fd.form == 1 && (d->step << (d->passes - 1)) > RT_FRAME_LDS_MAX_STEP)
+    return frame_denoise_fail(c, "the LDS form is forced (rt_set_frame_denoise_form) and a spacing above 4 has no LDS window");
+  if (c->dist.active) return frame_denoise_fail(c, "the context is a rank of a sharded image: its G-buffer covers only its own rows");
+  if (c->stripe_count > 1) return frame_denoise_fail(c, "stripes are on: the G-buffer covers only this context's rows");
+  if (!c->width || !c->render_target.ptr || !c->accum.ptr) return fail(c, RT_ERR_NOT_READY, w + ": no screen (rt_resize first)");
+  if (c->accum_stale)
+    return fail(c, RT_ERR_INVALID, w + ": the bound accumulation buffer was dropped by rt_resize: call rt_bind_accum again");
+  if (c->gbuf_gen == 0) return fail(c, RT_ERR_NOT_READY, w + ": no G-buffer yet; call compute first");
+  return RT_OK;
+}
+static const void* const frame_lds_fns[RT_FRAME_LDS_MAX_STEP] = {
+    (const void*)rtk::k_frame_pass_lds<1>, (const void*)rtk::k_frame_pass_lds<2>, (const void*)rtk::k_frame_pass_lds<3>,
+    (const void*)rtk::k_frame_pass_lds<4>};
+// The form of a pass at spacing s: the forced one, else what was measured faster at 1920 x 1080 (the staged
+// form at spacings 1 and 2, 77 against 139 us and 87 against 134 us; the direct form at 4, 131 against 165 us).  Spacing 3 was
+// not timed and keeps the staged form.
+static int frame_pass_form(const rt_ctx* c, uint32_t s) {
+  if (s > RT_FRAME_LDS_MAX_STEP) return 2;
+  if (c->fd.form) return c->fd.form;
+  return s >= 4 ? 2 : 1;
+}
+// Enqueue a whole call on the context's stream: `d` and the context have been checked.  dev_out: W * H float4.
+static int frame_denoise_run(rt_ctx* c, const rt_frame_denoise_desc* d, void* dev_out) {
+  DenoiseFrameState& fd = c->fd;
+  fd.wanted = true;
+  const size_t npx = (size_t)c->width * c->height;
+  // the G-buffer of the last compute(), as rt_read_gbuffer finds it
+  const void *pa = c->render_target.ptr, *pn = c->g_normal.ptr, *pd = c->g_depth.ptr;
+  bool plane_ok = c->albedo_plane_valid;
+  if (c->gbuf_slot >= 0 && (size_t)c->gbuf_slot < c->spec.slots.size()) {
+    const DevFrameSlot& sl = c->spec.slots[c->gbuf_slot];
+    pn = sl.normal_id;
+    pd = sl.depth;
+    if (sl.albedo != (uint32_t*)c->render_target.ptr) {
+      pa = sl.albedo;   // a plane of the batch: present() does not write there
+      plane_ok = true;
+    } else if (fd.keep_valid) {
+      pa = fd.albedo_keep.ptr;
+      plane_ok = true;
+    }
+  }
+  const uint32_t demod = d->flags & RT_FRAME_DENOISE_DEMODULATE;
+  const bool hit = fd.cache_valid && fd.cache_gen == c->gbuf_gen && fd.cache_epoch == c->epoch && fd.cache_flags == demod;
+  if (!hit && !plane_ok)
+    return fail(c, RT_ERR_NOT_READY, std::string(kFrameDenoise) + ": the albedo plane was overwritten by present(); call compute first");
+  int r;
+  if ((r = ensure_buffer(c, fd.col, npx * 16, false)) < 0) return r;
+  if ((r = ensure_buffer(c, fd.guide, npx * 32, false)) < 0) return r;
+  if ((r = ensure_buffer(c, fd.mod, npx * 16, false)) < 0) return r;
+  if ((r = ensure_buffer(c, fd.ping, npx * 16, false)) < 0) return r;
+  if (d->passes > 1 && (r = ensure_buffer(c, fd.pong, npx * 16, false)) < 0) return r;
+  if (!fd.ev_ready) {
+    for (EventPair& p : fd.ev) {
+      HIP_TRY(c, hipEventCreate(&p.a));
+      HIP_TRY(c, hipEventCreate(&p.b));
+    }
+    fd.ev_ready = true;
+  }
+  fd.timed = false;
+  fd.last = {};
+  fd.last.passes = d->passes;
+  fd.last.cache_hit = hit ? 1 : 0;
+  if (!hit) {
+    fd.cache_valid = false;
+    rtk::FramePrepareArgs A;
+    A.accum = accum_ptr(c);
+    A.albedo = (const uint32_t*)pa;
+    A.normal_id = (const float4*)pn;
+    A.depth = (const float*)pd;
+    A.col = (float4*)fd.col.ptr;
+    A.guide = (float4*)fd.guide.ptr;
+    A.mod = (float4*)fd.mod.ptr;
+    A.flags = d->flags;
+    HIP_TRY(c, hipEventRecord(fd.ev[0].a, c->stream));
+    hipLaunchKernelGGL(rtk::k_frame_prepare, dim3((c->width + 255u) / 256u, c->height), dim3(256), 0, c->stream, A, c->uniforms);
+    HIP_TRY(c, hipEventRecord(fd.ev[0].b, c->stream));
+    fd.cache_gen = c->gbuf_gen;
+    fd.cache_epoch = c->epoch;
+    fd.cache_flags = demod;
+    fd.cache_valid = true;
+  }
+  rtk::FramePassArgs P;
+  P.guide = (const float4*)fd.guide.ptr;
+  P.W = c->width;
+  P.H = c->height;
+  P.tiles_x = (c->width + RT_FRAME_TILE_W - 1u) / RT_FRAME_TILE_W;
+  const uint32_t tiles_y = (c->height + RT_FRAME_TILE_H - 1u) / RT_FRAME_TILE_H;
+  P.flags = d->flags;
+  P.normal_cos = d->normal_cos;
+  P.plane_eps = d->plane_eps;
+  P.sigma_lum = d->sigma_lum;
+  P.in = (const float4*)fd.col.ptr;
+  for (uint32_t p = 0; p < d->passes; p++) {
+    P.out = (float4*)((p & 1u) ? fd.pong.ptr : fd.ping.ptr);
+    P.step = d->step << p;
+    const int form = frame_pass_form(c, P.step);
+    fd.last.form[p] = (uint8_t)form;
+    HIP_TRY(c, hipEventRecord(fd.ev[2 + p].a, c->stream));
+    if (form == 1) {
+      void* args[] = {&P};
+      HIP_TRY(c, hipLaunchKernel(frame_lds_fns[P.step - 1u], dim3(P.tiles_x * tiles_y), dim3(256), args, 0, c->stream));
+    } else {
+      hipLaunchKernelGGL(rtk::k_frame_pass_direct, dim3((c->width + 255u) / 256u, c->height), dim3(256), 0, c->stream, P);
+    }
+    HIP_TRY(c, hipEventRecord(fd.ev[2 + p].b, c->stream));
+    P.in = P.out;
+  }
+  HIP_TRY(c, hipEventRecord(fd.ev[1].a, c->stream));
+  hipLaunchKernelGGL(rtk::k_frame_finish, dim3((uint32_t)((npx + 255) / 256)), dim3(256), 0, c->stream, P.in,
+                     (const float4*)fd.mod.ptr, (float4*)dev_out, (uint32_t)npx);
+  HIP_TRY(c, hipEventRecord(fd.ev[1].b, c->stream));
+  HIP_TRY(c, hipGetLastError());
+  fd.timed = true;
+  return RT_OK;
+}
+
+int rt_denoise_frame_device(rt_ctx* c, const rt_frame_denoise_desc* d, void* dev_out) {
+  int r = frame_denoise_desc_ok(c, d);
+  if (r < 0) return r;
+  if (!c) return RT_ERR_INVALID;
+  if (!dev_out) return frame_denoise_fail(c, "NULL output");
+  if ((r = frame_denoise_ctx_ok(c, d)) < 0) return r;
+  if (dev_out == (void*)accum_ptr(c) || dev_out == c->accum.ptr)
+    return frame_denoise_fail(c, "the output must not be the accumulation buffer");
+  if ((r = query_device_arrays_ok(c, kFrameDenoise, dev_out, dev_out)) < 0) return r;
+  return frame_denoise_run(c, d, dev_out);
+}
+
+int rt_denoise_frame(rt_ctx* c, const rt_frame_denoise_desc* d, float* out, size_t cap_bytes) {
+  int r = frame_denoise_desc_ok(c, d);
+  if (r < 0) return r;
+  if (!c) return RT_ERR_INVALID;
+  if (!out) return frame_denoise_fail(c, "NULL output");
+  if ((r = frame_denoise_ctx_ok(c, d)) < 0) return r;
+  const size_t bytes = (size_t)c->width * c->height * 16;
+  if (cap_bytes < bytes) return frame_denoise_fail(c, "output buffer too small");
+  HIP_TRY(c, hipSetDevice(c->device));
+  if ((r = ensure_buffer(c, c->fd.out, bytes, false)) < 0) return r;
+  if ((r = frame_denoise_run(c, d, c->fd.out.ptr)) < 0) return r;
+  HIP_TRY(c, hipMemcpyAsync(out, c->fd.out.ptr, bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return RT_OK;
+}
+
+int rt_set_present_denoise(rt_ctx* c, const rt_frame_denoise_desc* d) {
+  if (!d) {
+    if (!c) return RT_ERR_INVALID;
+    c->fd.present_on = false;
+    return RT_OK;
+  }
+  int r = frame_denoise_desc_ok(c, d);
+  if (r < 0) return r;
+  if (!c) return RT_ERR_INVALID;
+  if (c->present_source || c->present_stale)
+    return frame_denoise_fail(c, "a present source is bound (rt_bind_present_source(NULL) first): present() cannot read both");
+  if (c->dist.active)
+    return frame_denoise_fail(c, "the context is a rank of a sharded image (rt_dist_init): its G-buffer covers only its own rows");
+  if (c->stripe_count > 1) return frame_denoise_fail(c, "stripes are on (rt_set_stripes): the G-buffer covers only this context's rows");
+  if (c->fd.form == 1 && (d->step << (d->passes - 1)) > RT_FRAME_LDS_MAX_STEP)
+    return frame_denoise_fail(c, "the LDS form is forced (rt_set_frame_denoise_form) and a spacing above 4 has no LDS window");
+  c->fd.present_desc = *d;
+  c->fd.present_on = true;
+  c->fd.wanted = true;
+  return RT_OK;
+}
+
+int rt_set_frame_denoise_form(rt_ctx* c, int form) {
+  if (form < 0 || form > 2) return frame_denoise_fail(c, "form must be 0 (auto), 1 (LDS) or 2 (direct)");
+  if (!c) return RT_ERR_INVALID;
+  if (form == 1 && c->fd.present_on &&
+      (c->fd.present_desc.step << (c->fd.present_desc.passes - 1)) > RT_FRAME_LDS_MAX_STEP)
+    return frame_denoise_fail(c, "present() filters at a spacing above 4, which has no LDS window");
+  c->fd.form = form;
+  return RT_OK;
+}
+
+int rt_frame_denoise_stats(rt_ctx* c, rt_frame_denoise_report* out) {
+  if (!c || !out) return RT_ERR_INVALID;
+  DenoiseFrameState& fd = c->fd;
+  if (fd.timed) {
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (!fd.last.cache_hit) HIP_TRY(c, hipEventElapsedTime(&fd.last.prepare_ms, fd.ev[0].a, fd.ev[0].b));
+    HIP_TRY(c, hipEventElapsedTime(&fd.last.finish_ms, fd.ev[1].a, fd.ev[1].b));
+    for (uint32_t p = 0; p < fd.last.passes; p++) HIP_TRY(c, hipEventElapsedTime(&fd.last.pass_ms[p], fd.ev[2 + p].a, fd.ev[2 + p].b));
+    fd.timed = false;
+  }
+  *out = fd.last;
+  return RT_OK;
+}
+
 // ---- lightmaps: the stages above back to back on the context's stream, and the encode stage (mi355rt.h "lightmaps";
 // k_encode.hip.h).  Bytes per texel of a format; 0 = not a format.
 static const char* const kLightmap = "lightmap";
@@ -3780,6 +4023,17 @@ static int compute_frames(rt_ctx* c, const uint32_t* frame_counts, uint32_t n, u
                                dim3(shape.block), args, shape.dyn, c->stream));
   }
   if (ev) HIP_TRY(c, hipEventRecord(ev->b, c->stream));
+  // the frame denoiser's key: a new G-buffer is current, and the render target holds its last frame's albedo again.  A last
+  // frame that is traced AHEAD is consumed after present() calls that overwrite the plane: a context that denoises frames
+  // keeps a copy (4 B / px, only then)
+  c->gbuf_gen++;
+  c->albedo_plane_valid = true;
+  c->fd.keep_valid = false;
+  if (c->fd.wanted && n_commit < n) {
+    if ((r = ensure_buffer(c, c->fd.albedo_keep, npx * 4, false)) < 0) return r;
+    HIP_TRY(c, hipMemcpyAsync(c->fd.albedo_keep.ptr, c->render_target.ptr, npx * 4, hipMemcpyDeviceToDevice, c->stream));
+    c->fd.keep_valid = true;
+  }
 
   // 2. path trace
   c->pt_form = RT_PT_FORM_NONE;   // until the persistent kernel is launched below
@@ -3854,6 +4108,7 @@ static int consume_ahead(rt_ctx* c, uint32_t frame_count) {
                      c->width, c->height);
   HIP_TRY(c, hipGetLastError());
   c->gbuf_slot = (int)k;
+  c->gbuf_gen++;   // another frame's G-buffer is current (the frame denoiser's key)
   sp.k++;
   if (sp.k >= sp.n) sp.valid = false;
   return RT_OK;
@@ -3917,6 +4172,15 @@ int rt_present(rt_ctx* c) {
   DevPost P;
   P.accum = c->present_source ? (const float4*)c->present_source : accum_ptr(c);
   if (c->dist.active && c->dist.rank == 0) P.accum = (const float4*)c->dist.display.ptr;   // the assembled image
+  if (c->fd.present_on) {   // rt_set_present_denoise: the post pass reads the filtered frame (no source bound, no rank: refused there)
+    const size_t bytes = (size_t)c->width * c->height * 16;
+    int r = frame_denoise_ctx_ok(c, &c->fd.present_desc);
+    if (r < 0) return r;
+    if ((r = ensure_buffer(c, c->fd.out, bytes, false)) < 0) return r;
+    if ((r = frame_denoise_run(c, &c->fd.present_desc, c->fd.out.ptr)) < 0) return r;
+    P.accum = (const float4*)c->fd.out.ptr;
+  }
+  c->albedo_plane_valid = false;   // the post pass writes the render target, which is the albedo plane
   P.history_in = (const ushort4*)c->history[1 - c->history_index].ptr;  // previous frame (read)
   P.history_out = (ushort4*)c->history[c->history_index].ptr;           // current frame (write)
   P.out_rgba8 = (uint32_t*)c->render_target.ptr;
@@ -4049,6 +4313,8 @@ int rt_set_stripes(rt_ctx* c, uint32_t stripe_rows, uint32_t rank, uint32_t coun
       return fail(c, RT_ERR_INVALID, "rt_set_stripes contradicts the rank rt_dist_init made this context (rt_dist_shutdown first)");
     return RT_OK;
   }
+  if (count > 1 && c->fd.present_on)
+    return fail(c, RT_ERR_INVALID, "rt_set_stripes: present() filters the frame, and a striped G-buffer covers only its own rows (rt_set_present_denoise(NULL) first)");
   c->epoch++;
   c->stripe_rows = stripe_rows;
   c->stripe_rank = rank;
@@ -4064,12 +4330,15 @@ int rt_bind_accum(rt_ctx* c, void* device_ptr) {
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   c->external_accum = device_ptr;
   c->accum_stale = false;
+  c->fd.cache_valid = false;   // the frame denoiser's colour image was made from the other accumulation buffer
   return RT_OK;
 }
 int rt_bind_present_source(rt_ctx* c, void* device_ptr) {
   if (!c) return RT_ERR_INVALID;
   if (c->dist.active)
     return fail(c, RT_ERR_INVALID, "rt_bind_present_source: the context is a rank of a sharded image and presents its own display buffer (rt_dist_shutdown first)");
+  if (device_ptr && c->fd.present_on)
+    return fail(c, RT_ERR_INVALID, "rt_bind_present_source: present() filters the frame into its own source (rt_set_present_denoise(NULL) first)");
   HIP_TRY(c, hipSetDevice(c->device));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   c->present_source = device_ptr;
@@ -4282,6 +4551,8 @@ int rt_dist_init(rt_ctx* c, uint32_t rank, uint32_t world, uint32_t stripe_rows,
   if (c->dist.active) return fail(c, RT_ERR_INVALID, "rt_dist_init: the context is a rank already (rt_dist_shutdown first)");
   if (c->external_accum || c->present_source || c->accum_stale || c->present_stale)
     return fail(c, RT_ERR_INVALID, "rt_dist_init: unbind rt_bind_accum / rt_bind_present_source first (a rank uses the context's own buffers)");
+  if (c->fd.present_on)
+    return fail(c, RT_ERR_INVALID, "rt_dist_init: present() filters the frame, and a rank's G-buffer covers only its own rows (rt_set_present_denoise(NULL) first)");
   HIP_TRY(c, hipSetDevice(c->device));
   void* comm = nullptr;
   if (unique_id128) {

@@ -1005,6 +1005,47 @@ static napi_value rtDenoiseAtlas(napi_env env, napi_callback_info info) {
                                         (const uint32_t*)texels, (uint32_t)n, (float*)out));
 }
 
+/* ------------------------------------------------------- frame denoise (rt_denoise_frame, mi355rt.h) */
+/* desc: Float64Array {passes, step, flags, normalCos, planeEps, sigmaLum} -> an rt_frame_denoise_desc */
+static int frame_denoise_desc(napi_env env, napi_value v, rt_frame_denoise_desc* d) {
+  void* p = NULL;
+  size_t n = 0;
+  if (!get_bytes(env, v, &p, &n)) return 0;
+  if (!p || n != 6 * sizeof(double)) {
+    napi_throw_range_error(env, NULL, "frame denoise: the descriptor is a Float64Array of 6");
+    return 0;
+  }
+  const double* s = (const double*)p;
+  memset(d, 0, sizeof(*d));
+  d->passes = (uint32_t)s[0];
+  d->step = (uint32_t)s[1];
+  d->flags = (uint32_t)s[2];
+  d->normal_cos = (float)s[3];
+  d->plane_eps = (float)s[4];
+  d->sigma_lum = (float)s[5];
+  return 1;
+}
+/* (ctx, desc, out: Float32Array of width * height * 4) -> 0, or a negative status */
+static napi_value rtDenoiseFrame(napi_env env, napi_callback_info info) {
+  napi_value a[3];
+  void* out = NULL;
+  size_t no = 0;
+  rt_frame_denoise_desc d;
+  if (!get_args(env, info, 3, a) || !frame_denoise_desc(env, a[1], &d) || !get_bytes(env, a[2], &out, &no)) return NULL;
+  return make_int(env, rt_denoise_frame((rt_ctx*)get_ptr(env, a[0]), &d, (float*)out, no));
+}
+/* (ctx, desc or null) -> 0, or a negative status */
+static napi_value rtSetPresentDenoise(napi_env env, napi_callback_info info) {
+  napi_value a[2];
+  napi_valuetype t;
+  rt_frame_denoise_desc d;
+  if (!get_args(env, info, 2, a)) return NULL;
+  if (napi_typeof(env, a[1], &t) == napi_ok && (t == napi_null || t == napi_undefined))
+    return make_int(env, rt_set_present_denoise((rt_ctx*)get_ptr(env, a[0]), NULL));
+  if (!frame_denoise_desc(env, a[1], &d)) return NULL;
+  return make_int(env, rt_set_present_denoise((rt_ctx*)get_ptr(env, a[0]), &d));
+}
+
 /* ------------------------------------------------------- lightmaps (rt_bake_atlas_lightmap, rt_encode_atlas, mi355rt.h) */
 /* (ctx, width, height, padBase, tMax, entries, atlasUv or null, maxDepth, spp, seed, stages: Float64Array {passes, step,
  * normalCos, planeEps, maxDist, dilateRadius, format}, out: a typed array of width * height texels of the format, wantStats)
@@ -1102,6 +1143,7 @@ static napi_value Init(napi_env env, napi_value exports) {
                {"rtBakeIrradiance", rtBakeIrradiance}, {"rtBakeAtlasPoints", rtBakeAtlasPoints},
                {"rtBakeAtlasIrradiance", rtBakeAtlasIrradiance}, {"rtDilateAtlas", rtDilateAtlas},
                {"rtDenoiseAtlas", rtDenoiseAtlas}, {"rtBakeAtlasLightmap", rtBakeAtlasLightmap},
+               {"rtDenoiseFrame", rtDenoiseFrame}, {"rtSetPresentDenoise", rtSetPresentDenoise},
                {"rtEncodeAtlas", rtEncodeAtlas}, {"msCreate", msCreate}, {"msDestroy", msDestroy},
                {"msUpdate", msUpdate}, {"msUpdateCamera", msUpdateCamera}, {"msGet", msGet},
                {"msTextureCount", msTextureCount}, {"msTexture", msTexture},

@@ -133,6 +133,15 @@ export class WebGPURenderer {
    *  filled ones, 0xffffffff elsewhere). */
   dilateAtlas(atlas: Float32Array, width: number, height: number, radius: number, opts?: { src?: boolean }):
     { data: Float32Array; width: number; height: number; filled: number; src?: Uint32Array };
+  /** Frame denoise (rt_denoise_frame): the descriptor of denoiseFrame / setPresentDenoise - `passes` passes (1 .. 5) of the
+   *  5 x 5 a-trous kernel at tap spacings step, 2 * step, ... (at most 16), taps accepted by normal (normalCos), tangent plane
+   *  (planeEps, world units) and - sigmaLum > 0 - luminance; demodulate filters radiance / albedo. */
+  static frameDenoiseDesc(opts: { planeEps: number; passes?: number; step?: number; normalCos?: number; sigmaLum?: number;
+                                  demodulate?: boolean; sameInstance?: boolean }): Float64Array;
+  /** The filtered frame of the last compute(): 4 floats per pixel, rgb = radiance, a = 1 where the accumulation weight was > 0. */
+  denoiseFrame(desc: Float64Array | object): { data: Float32Array; width: number; height: number };
+  /** present() filters the frame first (null: the plain path). */
+  setPresentDenoise(desc: Float64Array | object | null): void;
   /** Atlas denoise (rt_denoise_atlas): `passes` passes of the 5 x 5 a-trous kernel at tap spacings step, 2 * step, ... (at
    *  most 4), guided by the points of bakePoints / bakeAtlasPoints for the same atlas: a tap counts only where its normal has
    *  a dot product >= normalCos with the texel's and its position lies within planeEps of the texel's tangent plane and

@@ -397,6 +397,31 @@ class WebGPURenderer {
     if (src) out.src = src;
     return out;
   }
+  // ---- frame denoise (rt_denoise_frame): the G-buffer-guided a-trous filter of the frame of the last compute(), by the frame
+  // denoise rule of include/mi355rt.h.  frameDenoiseDesc({passes = 4, step = 1, planeEps, normalCos = 0.9, sigmaLum = 4,
+  // demodulate = true, sameInstance = false}) -> the descriptor both calls take.  denoiseFrame(desc) -> {data: a Float32Array of
+  // 4 per pixel in the accumulator's format (rgb = radiance, a = 1 where the accumulation weight was > 0), width, height}.
+  // setPresentDenoise(desc | null): present() filters the frame first; null restores the plain path.
+  static frameDenoiseDesc(opts = {}) {
+    if (opts.planeEps === undefined) throw new TypeError('frameDenoiseDesc: opts.planeEps is required');
+    const flags = ((opts.demodulate === undefined || opts.demodulate) ? 1 : 0) | (opts.sameInstance ? 2 : 0);
+    return Float64Array.of(opts.passes === undefined ? 4 : opts.passes, opts.step === undefined ? 1 : opts.step, flags,
+      opts.normalCos === undefined ? 0.9 : opts.normalCos, opts.planeEps, opts.sigmaLum === undefined ? 4 : opts.sigmaLum);
+  }
+  static _frameDenoiseDesc(desc, what) {
+    const d = desc instanceof Float64Array ? desc : WebGPURenderer.frameDenoiseDesc(desc);
+    if (d.length !== 6) throw new TypeError(what + ': a descriptor of frameDenoiseDesc()');
+    return d;
+  }
+  denoiseFrame(desc) {
+    const data = new Float32Array(this.width * this.height * 4);
+    this._check(native.rtDenoiseFrame(this._ctx, WebGPURenderer._frameDenoiseDesc(desc, 'denoiseFrame'), data), 'denoiseFrame');
+    return { data, width: this.width, height: this.height };
+  }
+  setPresentDenoise(desc) {
+    const d = (desc === null || desc === undefined) ? null : WebGPURenderer._frameDenoiseDesc(desc, 'setPresentDenoise');
+    this._check(native.rtSetPresentDenoise(this._ctx, d), 'setPresentDenoise');
+  }
   // ---- atlas denoise (rt_denoise_atlas): the edge-stopped a-trous filter of a baked atlas.  atlas = 4 floats per texel;
   // points (8 floats each) and texels as bakePoints / bakeAtlasPoints return them for the same atlas.  opts: {planeEps,
   // maxDist (both required, world units), normalCos = 0.9, passes = 3, step = 1}: `passes` passes of the 5 x 5 kernel at tap

@@ -1,12 +1,24 @@
 'use strict';
 // Headless driver reproducing the reference's call sequence (src/main.ts:51-116,119-181):
 // load scene -> upload buffers -> resolution -> N x { compute(frame); present() } -> captureFrame.
-// usage: node render_cornell.js [scene] [width] [height] [frames] [depth]   -> prints one JSON line
+// usage: node render_cornell.js [scene] [width] [height] [frames] [depth] [--denoise PASSES [--plane-eps E]]   -> prints one JSON line
+// --denoise PASSES (1 .. 5): every present() filters the frame first (setPresentDenoise: the G-buffer-guided a-trous filter,
+// demodulated, planeEps E = 0.02 unless given), and the line also carries the sha256 of denoiseFrame()'s image of the last frame.
 const crypto = require('crypto');
 const { WebGPURenderer, WorldBridge } = require('./index.js');
 
 (async () => {
-  const [scene = 'cornell', w = '96', h = '96', frames = '3', depth = '4'] = process.argv.slice(2);
+  const argv = process.argv.slice(2);
+  const flag = (name, parse, dflt) => {
+    const i = argv.indexOf(name);
+    if (i < 0) return dflt;
+    const v = parse(argv[i + 1]);
+    argv.splice(i, 2);
+    return v;
+  };
+  const denoise = flag('--denoise', (v) => parseInt(v, 10), 0);
+  const planeEps = flag('--plane-eps', parseFloat, 0.02);
+  const [scene = 'cornell', w = '96', h = '96', frames = '3', depth = '4'] = argv;
   const width = parseInt(w, 10), height = parseInt(h, 10);
   const bridge = new WorldBridge();
   await bridge.initWasm();
@@ -30,6 +42,8 @@ const { WebGPURenderer, WorldBridge } = require('./index.js');
   renderer.updateSceneUniforms(bridge.cameraData, 0, bridge.lightCount);
   renderer.recreateBindGroup();
   renderer.resetAccumulation();
+  const desc = denoise > 0 ? WebGPURenderer.frameDenoiseDesc({ passes: denoise, planeEps }) : null;
+  if (desc) renderer.setPresentDenoise(desc);
   for (let f = 1; f <= parseInt(frames, 10); f++) { renderer.compute(f); renderer.present(); }
   if (process.env.RT_NODE_BATCH) {  // extra frames through the batched entry point
     const n = parseInt(process.env.RT_NODE_BATCH, 10), first = parseInt(frames, 10) + 1;
@@ -41,6 +55,7 @@ const { WebGPURenderer, WorldBridge } = require('./index.js');
   const acc = renderer.readAccum();
   const sha = (buf) => crypto.createHash('sha256').update(Buffer.from(buf)).digest('hex');
   console.log(JSON.stringify({ scene, width, height, frames: parseInt(frames, 10),
-    rgba_sha256: sha(frame.data), accum_sha256: sha(acc.buffer), counters: renderer.getCounters() }));
+    rgba_sha256: sha(frame.data), accum_sha256: sha(acc.buffer), counters: renderer.getCounters(),
+    ...(desc ? { denoise, planeEps, denoised_sha256: sha(renderer.denoiseFrame(desc).data.buffer) } : {}) }));
   renderer.destroy();
 })().catch((e) => { console.error(e); process.exit(1); });

@@ -16,12 +16,16 @@ import numpy as np
 
 
 class FrameLoop:
-    def __init__(self, renderer, bridge, width, height, batch=20, clock=time.perf_counter):
+    def __init__(self, renderer, bridge, width, height, batch=20, clock=time.perf_counter, denoise=None):
+        """denoise: None (the reference's loop, unchanged), or a frame_denoise_desc record / a dict of its keyword arguments:
+        every present() then filters the frame first (WebGPURenderer.setPresentDenoise)."""
         self.renderer = renderer
         self.bridge = bridge
         self.width, self.height = width, height
         self.current_batch_size = batch      # VideoRecorder.currentBatchSize, initialised from config.batch
         self.clock = clock
+        if denoise is not None:
+            renderer.setPresentDenoise(denoise)
 
     # VideoRecorder.updateSceneBuffers (:231-268) — note the upload order differs from main.ts
     def update_scene_buffers(self):

@@ -234,6 +234,12 @@ def load_library(path=None):
         # atlas denoise
         "rt_denoise_atlas": (i32, [vp, vp, vp, vp, vp, u32, vp]),
         "rt_denoise_atlas_device": (i32, [vp, vp, vp, vp, vp, u32, vp]),
+        # frame denoise
+        "rt_denoise_frame": (i32, [vp, vp, vp, ctypes.c_size_t]),
+        "rt_denoise_frame_device": (i32, [vp, vp, vp]),
+        "rt_set_present_denoise": (i32, [vp, vp]),
+        "rt_set_frame_denoise_form": (i32, [vp, ctypes.c_int]),
+        "rt_frame_denoise_stats": (i32, [vp, vp]),
         # lightmaps
         "rt_bake_atlas_lightmap": (i32, [vp, vp, vp, vp, u32, vp, ctypes.c_size_t, vp, vp, vp]),
         "rt_bake_atlas_lightmap_device": (i32, [vp, vp, vp, vp, vp, ctypes.c_size_t, vp, vp, vp]),
@@ -275,6 +281,7 @@ EXPORTED_SYMBOLS = (
     "rt_bake_atlas_points rt_bake_atlas_points_device rt_bake_atlas_irradiance "
     "rt_dilate_atlas rt_dilate_atlas_device "
     "rt_denoise_atlas rt_denoise_atlas_device "
+    "rt_denoise_frame rt_denoise_frame_device rt_set_present_denoise rt_set_frame_denoise_form rt_frame_denoise_stats "
     "rt_bake_atlas_lightmap rt_bake_atlas_lightmap_device rt_encode_atlas rt_encode_atlas_device "
     "rt_bake_atlas_directional rt_bake_atlas_directional_lightmap").split()
 
@@ -483,6 +490,51 @@ class RtDenoiseDesc(ctypes.Structure):
     _fields_ = [("width", ctypes.c_uint32), ("height", ctypes.c_uint32), ("step", ctypes.c_uint32), ("passes", ctypes.c_uint32),
                 ("normal_cos", ctypes.c_float), ("plane_eps", ctypes.c_float), ("max_dist", ctypes.c_float),
                 ("reserved", ctypes.c_uint32 * 1)]
+
+
+# frame denoise: mirrors of rt_frame_denoise_desc and rt_frame_denoise_report, and the descriptor as a numpy record
+RT_FRAME_DENOISE_MAX_STEP = 16
+RT_FRAME_DENOISE_DEMODULATE, RT_FRAME_DENOISE_SAME_INSTANCE = 1, 2
+FRAME_DENOISE_FORMS = {"auto": 0, "lds": 1, "direct": 2}
+
+
+class RtFrameDenoiseDesc(ctypes.Structure):
+    _fields_ = [("passes", ctypes.c_uint32), ("step", ctypes.c_uint32), ("flags", ctypes.c_uint32),
+                ("normal_cos", ctypes.c_float), ("plane_eps", ctypes.c_float), ("sigma_lum", ctypes.c_float),
+                ("reserved", ctypes.c_uint32 * 2)]
+
+
+class RtFrameDenoiseReport(ctypes.Structure):
+    _fields_ = [("prepare_ms", ctypes.c_float), ("pass_ms", ctypes.c_float * 5), ("finish_ms", ctypes.c_float),
+                ("passes", ctypes.c_uint32), ("form", ctypes.c_uint8 * 5), ("cache_hit", ctypes.c_uint8),
+                ("pad", ctypes.c_uint8 * 2), ("reserved", ctypes.c_uint32 * 2)]
+
+
+FRAME_DENOISE_DESC_DTYPE = np.dtype([("passes", "<u4"), ("step", "<u4"), ("flags", "<u4"), ("normal_cos", "<f4"),
+                                     ("plane_eps", "<f4"), ("sigma_lum", "<f4"), ("reserved", "<u4", (2,))])
+
+
+def frame_denoise_desc(passes=4, step=1, *, plane_eps, normal_cos=0.9, sigma_lum=4.0, demodulate=True, same_instance=False):
+    """An rt_frame_denoise_desc as a one-element FRAME_DENOISE_DESC_DTYPE record: `passes` passes (1 .. 5) of the 5 x 5
+    a-trous kernel at tap spacings step, 2 * step, ... (at most 16); a tap is accepted where its normal has a dot product >=
+    normal_cos with the centre's and its world position lies within plane_eps (world units) of the centre's tangent plane;
+    sigma_lum > 0 adds the luminance stop in standard deviations of the 3 x 3 neighbourhood; demodulate filters radiance /
+    albedo and multiplies the albedo back; same_instance keeps taps on the centre's instance."""
+    d = np.zeros(1, FRAME_DENOISE_DESC_DTYPE)
+    d["passes"], d["step"] = int(passes), int(step)
+    d["flags"] = (RT_FRAME_DENOISE_DEMODULATE if demodulate else 0) | (RT_FRAME_DENOISE_SAME_INSTANCE if same_instance else 0)
+    d["normal_cos"], d["plane_eps"], d["sigma_lum"] = normal_cos, plane_eps, sigma_lum
+    return d
+
+
+def _frame_denoise_record(desc):
+    """a frame_denoise_desc record, or a dict of its keyword arguments -> a contiguous one-element record"""
+    if isinstance(desc, dict):
+        desc = frame_denoise_desc(**desc)
+    d = np.ascontiguousarray(desc, dtype=FRAME_DENOISE_DESC_DTYPE).reshape(-1)
+    if d.size != 1:
+        raise ValueError("one rt_frame_denoise_desc record expected")
+    return d
 
 
 # lightmaps: mirror of rt_lightmap_desc, the RT_LIGHTMAP_* formats by name, and what a texel of each is on the host
@@ -1301,6 +1353,53 @@ class WebGPURenderer:
         self._check(self.L.rt_denoise_atlas_device(self.ctx, ctypes.addressof(d), ctypes.c_void_p(in_ptr or 0),
                                                    ctypes.c_void_p(points_ptr or 0), ctypes.c_void_p(texels_ptr or 0), int(n),
                                                    ctypes.c_void_p(out_ptr or 0)), "denoiseAtlasDevice")
+
+    # ---- frame denoise: the G-buffer-guided a-trous filter of the frame of the last compute() (rt_denoise_frame) ----
+    def denoiseFrame(self, desc):
+        """The filtered frame as an (H, W, 4) float32 array in the accumulator's format (rgb = radiance, a = 1 where the
+        accumulation weight was > 0): by the frame denoise rule of include/mi355rt.h, from the accumulation buffer and the
+        G-buffer of the last compute().  desc: a frame_denoise_desc record or a dict of its keyword arguments.  Blocking."""
+        d = _frame_denoise_record(desc)
+        out = np.empty((self.height, self.width, 4), dtype=np.float32)
+        self._check(self.L.rt_denoise_frame(self.ctx, _ptr(d), _ptr(out), out.nbytes), "denoiseFrame")
+        return out
+
+    def denoiseFrameDevice(self, tensor, desc):
+        """Enqueue the same filter into `tensor` - a contiguous float32 tensor of H * W * 4 elements on the context's device,
+        or a device pointer - on the context's stream; no host synchronisation.  The tensor may afterwards be given to
+        bindPresentSource."""
+        d = _frame_denoise_record(desc)
+        ptr = tensor
+        if hasattr(tensor, "data_ptr"):
+            if tensor.numel() * tensor.element_size() != self.width * self.height * 16 or not tensor.is_contiguous():
+                raise ValueError("denoiseFrameDevice expects a contiguous tensor of H * W * 16 bytes")
+            ptr = tensor.data_ptr()
+        self._check(self.L.rt_denoise_frame_device(self.ctx, _ptr(d), ctypes.c_void_p(ptr or 0)), "denoiseFrameDevice")
+
+    def setPresentDenoise(self, desc):
+        """desc (a frame_denoise_desc record or a dict): from now on present() filters the frame into a buffer the context
+        owns and the post pass reads that; None restores the plain path exactly."""
+        if desc is None:
+            self._check(self.L.rt_set_present_denoise(self.ctx, None), "setPresentDenoise")
+            return
+        d = _frame_denoise_record(desc)
+        self._check(self.L.rt_set_present_denoise(self.ctx, _ptr(d)), "setPresentDenoise")
+
+    def setFrameDenoiseForm(self, form):
+        """"auto" / 0 (per spacing, what was measured faster), "lds" / 1 (the staged form: spacings 1 .. 4 only) or
+        "direct" / 2 (taps through L1 / L2).  Same words either way."""
+        f = FRAME_DENOISE_FORMS[form.lower()] if isinstance(form, str) else int(form)
+        self._check(self.L.rt_set_frame_denoise_form(self.ctx, f), "setFrameDenoiseForm")
+
+    def frameDenoiseStats(self):
+        """Stream times of the last denoiseFrame* call or filtered present(): {prepare_ms, pass_ms [per pass], finish_ms,
+        forms [per pass: "lds" / "direct"], cache_hit}.  Blocking."""
+        r = RtFrameDenoiseReport()
+        self._check(self.L.rt_frame_denoise_stats(self.ctx, ctypes.addressof(r)), "frameDenoiseStats")
+        n = int(r.passes)
+        return {"prepare_ms": float(r.prepare_ms), "pass_ms": [float(r.pass_ms[p]) for p in range(n)],
+                "finish_ms": float(r.finish_ms), "forms": [("none", "lds", "direct")[r.form[p]] for p in range(n)],
+                "cache_hit": bool(r.cache_hit)}
 
     # ---- lightmaps: bake, filter, gutter fill and encode in one call, without leaving the device (rt_bake_atlas_lightmap) ----
     @staticmethod
