@@ -274,8 +274,13 @@ int rt_debug_pt_launch(rt_ctx* ctx, uint32_t* out4);
  * from the uploaded topology that every triangle is an untextured Lambertian surface or a light and ran the wide one-leaf
  * form compiled for those alone (MI355RT_PLAIN_MATERIALS=0 in the environment of rt_create switches that off),
  * RT_PT_FORM_GENERIC for every other launch of the persistent kernel, RT_PT_FORM_NONE before the first dispatch and after a
- * dispatch that ran another kernel (wavefront, one pixel per lane).  The images of the two forms are the same, bit for bit. */
-enum { RT_PT_FORM_NONE = 0, RT_PT_FORM_GENERIC = 1, RT_PT_FORM_PLAIN = 2 };
+ * dispatch that ran another kernel (wavefront, one pixel per lane).  RT_PT_FORM_GENERIC_SWEEP and RT_PT_FORM_PLAIN_SWEEP are
+ * those two in the form whose walks test the BLAS leaves alone, in wave lock-step: the host takes it for a batched dispatch
+ * of a one-leaf scene when the BLAS bytes of rt_upload_bvh are a canonical pre-order tree of finite, nested boxes with at
+ * most 16 leaves of 1-7 triangles (MI355RT_LEAF_SWEEP=0 in the environment of rt_create switches that off;
+ * MI355RT_LEAF_SWEEP_GUARD=1 sends every walk of such a form through the node walk it keeps for rays with a non-finite
+ * reciprocal direction).  The images of all forms are the same, bit for bit. */
+enum { RT_PT_FORM_NONE = 0, RT_PT_FORM_GENERIC = 1, RT_PT_FORM_PLAIN = 2, RT_PT_FORM_GENERIC_SWEEP = 3, RT_PT_FORM_PLAIN_SWEEP = 4 };
 int rt_debug_pt_form(const rt_ctx* ctx);
 /* Diagnostic build (-DRT_LANE_STATS) only: lane utilisation of the parts of a trip of k_pathtrace_persistent:
  * out32[2 k] = times part k ran (wave level), out32[2 k + 1] = active lanes summed; k = 0 shade, 1 / 2 node step / triangle

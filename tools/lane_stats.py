@@ -16,7 +16,8 @@ scene = sys.argv[1] if len(sys.argv) > 1 else "cornell"
 # one-leaf forms: a new hit only records itself (part 5) and a new sample only makes its camera ray and loads its G-buffer
 # words (part 6); one pass at the start of the trip makes the surface frame of both (part 8).  The other forms make the
 # frame in parts 5 and 6 and have no part 8.
-PARTS = ("shade", "shadow walk: node step", "shadow walk: triangle chunk", "extension walk: node step",
+# a sweep form (k_traverse.hip.h traverse_leaves; MI355RT_LEAF_SWEEP=0 gives the node walk) counts a leaf step as a node step
+PARTS = ("shade", "shadow walk: node step (sweep: leaf step)", "shadow walk: triangle chunk", "extension walk: node step (sweep: leaf step)",
          "extension walk: triangle chunk", "new hit (one-leaf: recorded; else + surface frame)",
          "start of a sample (one-leaf: camera ray + G-buffer words; else + surface frame)", "end of a sample",
          "surface frame, one pass (one-leaf forms)")
@@ -45,7 +46,7 @@ try:
     r.L.rt_debug_lane_stats(r.ctx, buf.ctypes.data_as(ctypes.c_void_p), 1)
     n, lanes = buf[0:18:2].astype(float), buf[1:18:2].astype(float)
     trips = n[0]
-    print("scene=%s, one 32-frame batch: %d wave-level trips that shade" % (scene, trips))
+    print("scene=%s, one 32-frame batch: %d wave-level trips that shade (walk: %s)" % (scene, trips, r.debugPtWalk()))
     print("   %-80s %14s %12s %12s" % ("part", "runs per trip", "lanes / run", "utilisation"))
     for k, name in enumerate(PARTS):
         if n[k]:

@@ -558,11 +558,17 @@ __device__ __forceinline__ rt3 col_park_add(f4* lds, rt3 radiance) {   // the su
 #define RT_PT_WAVES 4
 #define RT_PT_SIMD_WAVES (LDS ? ((ONE_INST && !DETAIL) ? RT_PT_ONE_INST_WAVES : RT_PT_LDS_WAVES) : RT_PT_GLOBAL_WAVES)
 #define RT_PT_PLAIN false
+#define RT_PT_SWEEP false
+#define RT_PT_SWEEP_PARAMS
+#define RT_PT_SWEEP_ARG nullptr, 0u, false
 #include "k_pathtrace_persistent.hip.h"
 #undef RT_PT_KERNEL
 #undef RT_PT_WAVES
 #undef RT_PT_SIMD_WAVES
 #undef RT_PT_PLAIN
+#undef RT_PT_SWEEP
+#undef RT_PT_SWEEP_PARAMS
+#undef RT_PT_SWEEP_ARG
 
 // k_pathtrace_persistent_wide: the one-leaf-TLAS LDS form of the product build (rt_api.hip instantiates <false, true, true>
 // only) in 512-thread workgroups.  Eight waves share one staged scene, so that three workgroups of a small scene (24 waves,
@@ -571,11 +577,17 @@ __device__ __forceinline__ rt3 col_park_add(f4* lds, rt3 radiance) {   // the su
 #define RT_PT_WAVES 8
 #define RT_PT_SIMD_WAVES RT_PT_WIDE_WAVES
 #define RT_PT_PLAIN false
+#define RT_PT_SWEEP false
+#define RT_PT_SWEEP_PARAMS
+#define RT_PT_SWEEP_ARG nullptr, 0u, false
 #include "k_pathtrace_persistent.hip.h"
 #undef RT_PT_KERNEL
 #undef RT_PT_WAVES
 #undef RT_PT_SIMD_WAVES
 #undef RT_PT_PLAIN
+#undef RT_PT_SWEEP
+#undef RT_PT_SWEEP_PARAMS
+#undef RT_PT_SWEEP_ARG
 
 // k_pathtrace_persistent_plain: the wide form (<false, true, true> only, the same workgroups and LDS layout) for a scene in
 // which the host has seen nothing but untextured Lambertian triangles and lights (scene_facts.h; launch_plan.h
@@ -586,11 +598,42 @@ __device__ __forceinline__ rt3 col_park_add(f4* lds, rt3 radiance) {   // the su
 #define RT_PT_WAVES 8
 #define RT_PT_SIMD_WAVES RT_PT_WIDE_WAVES
 #define RT_PT_PLAIN true
+#define RT_PT_SWEEP false
+#define RT_PT_SWEEP_PARAMS
+#define RT_PT_SWEEP_ARG nullptr, 0u, false
 #include "k_pathtrace_persistent.hip.h"
 #undef RT_PT_KERNEL
 #undef RT_PT_WAVES
 #undef RT_PT_SIMD_WAVES
 #undef RT_PT_PLAIN
+#undef RT_PT_SWEEP
+#undef RT_PT_SWEEP_PARAMS
+#undef RT_PT_SWEEP_ARG
+
+// k_pathtrace_sweep_wide, k_pathtrace_sweep_plain: the wide form and its plain twin (<false, true, true> only, the same
+// workgroups and LDS layout) for a scene whose BLAS the host has found sweepable (scene_facts.h walk_facts; launch_plan.h
+// persistent_shape): both walks of a trip test the BLAS leaves in wave lock-step (k_traverse.hip.h traverse_leaves).  They
+// take two parameters more: the leaf records, and their number with bit 31 set when every walk is to take the guard's branch.
+#define RT_PT_SWEEP true
+#define RT_PT_SWEEP_PARAMS , const float4* __restrict__ leaf_recs, uint32_t leaf_info
+#define RT_PT_SWEEP_ARG leaf_recs, leaf_info & 0xffffu, (leaf_info >> 31) != 0u
+#define RT_PT_WAVES 8
+#define RT_PT_SIMD_WAVES RT_PT_WIDE_WAVES
+#define RT_PT_KERNEL k_pathtrace_sweep_wide
+#define RT_PT_PLAIN false
+#include "k_pathtrace_persistent.hip.h"
+#undef RT_PT_KERNEL
+#undef RT_PT_PLAIN
+#define RT_PT_KERNEL k_pathtrace_sweep_plain
+#define RT_PT_PLAIN true
+#include "k_pathtrace_persistent.hip.h"
+#undef RT_PT_KERNEL
+#undef RT_PT_PLAIN
+#undef RT_PT_WAVES
+#undef RT_PT_SIMD_WAVES
+#undef RT_PT_SWEEP
+#undef RT_PT_SWEEP_PARAMS
+#undef RT_PT_SWEEP_ARG
 
 }  // namespace rtk
 #endif

@@ -1,7 +1,9 @@
-// The persistent path-trace kernel, written once and compiled under three names (k_pathtrace.hip.h includes this file three
+// The persistent path-trace kernel, written once and compiled under five names (k_pathtrace.hip.h includes this file five
 // times, inside namespace rtk): RT_PT_KERNEL is the kernel's name, RT_PT_WAVES its waves per workgroup, RT_PT_SIMD_WAVES the
 // waves per SIMD of its launch bounds (an expression that may use the template parameters) and RT_PT_PLAIN whether it is the
-// form for scenes of plain materials.  No include guard.
+// form for scenes of plain materials.  RT_PT_SWEEP: whether the walks sweep the BLAS leaves (k_traverse.hip.h traverse_leaves);
+// such a form takes RT_PT_SWEEP_PARAMS behind the common parameters, the leaf records and their number, and RT_PT_SWEEP_ARG
+// makes the walk's LeafSweep of them (the other forms define both empty, and keep their parameter list).  No include guard.
 // ONE_INST (LDS form only): the scene's TLAS is a single leaf (k_traverse.hip.h traverse<.., ONE_INST>).  Every hit is then in
 // the one instance, and what a trip would compute from (instance, triangle) alone is read from the per-triangle world
 // records the host built at upload time behind the shading records (k_prepare_world_tris: Sg.tri_shade + 8 * n_tris).
@@ -11,7 +13,7 @@ __global__ __launch_bounds__(64 * RT_PT_WAVES, RT_PT_SIMD_WAVES) void RT_PT_KERN
                                                               uint32_t n_tris_total, uint32_t n_inst_total,
                                                               uint32_t n_verts_total,
                                                               const DevFrameSlot* __restrict__ slots, uint32_t n_slots,
-                                                              LdsPlan plan) {
+                                                              LdsPlan plan RT_PT_SWEEP_PARAMS) {
   // Batched dispatch (rt_compute_batch): the launch covers n_slots consecutive compute() frames. The work item is
   // one (frame, pixel): tickets enumerate (frame, tile) pairs, so a launch has n_slots times as many tickets and the
   // persistent waves stay fed and balanced even when a rank owns 1/8 of the image. With n_slots > 1 every item
@@ -35,6 +37,10 @@ __global__ __launch_bounds__(64 * RT_PT_WAVES, RT_PT_SIMD_WAVES) void RT_PT_KERN
   // have (setup_surface, shade_bounce).  The product one-leaf form only.
   constexpr bool PLAIN = RT_PT_PLAIN;
   static_assert(!PLAIN || (ONE_INST && LDS && !DETAIL), "the plain form is a product one-leaf form");
+  // SWEEP (RT_PT_SWEEP, the includer's): the host has seen that the BLAS is sweepable (scene_facts.h walk_facts); both walks
+  // of a trip test its leaves alone.  A product one-leaf form only.
+  constexpr bool SWEEP = RT_PT_SWEEP;
+  static_assert(!SWEEP || (ONE_INST && LDS && !DETAIL), "a sweep form is a product one-leaf form");
   extern __shared__ f4 s_scene[];
   // per-wave triangle work queue at the start of LDS, staged scene after it
   // (LEAN: the wave's index in a scalar register, and so the addresses of its queue)
@@ -365,8 +371,13 @@ __global__ __launch_bounds__(64 * RT_PT_WAVES, RT_PT_SIMD_WAVES) void RT_PT_KERN
       float t_;
       int32_t a_, b_;
       bool occluded;
-      traverse<true, DETAIL, MODE, ONE_INST>(M, s_scene, WW, U.blas_base_idx, want_shadow, sh_o, sh_d, sh_tmax, t_, a_, b_,
-                                   occluded, cnt_nodes, cnt_tris);
+      if constexpr (SWEEP) {
+        traverse_leaves<true, MODE>(M, s_scene, WW, LeafSweep{RT_PT_SWEEP_ARG}, U.blas_base_idx, want_shadow, sh_o, sh_d, sh_tmax,
+                                    t_, a_, b_, occluded);
+      } else {
+        traverse<true, DETAIL, MODE, ONE_INST>(M, s_scene, WW, U.blas_base_idx, want_shadow, sh_o, sh_d, sh_tmax, t_, a_, b_,
+                                     occluded, cnt_nodes, cnt_tris);
+      }
       if (want_shadow) {
         if (!occluded && nee_valid) p.radiance = p.radiance + nee;  // nothing is added when bsdf_pdf <= 0
       }
@@ -383,8 +394,13 @@ __global__ __launch_bounds__(64 * RT_PT_WAVES, RT_PT_SIMD_WAVES) void RT_PT_KERN
       float t_;
       int32_t tri_, inst_;
       bool any_;
-      traverse<false, DETAIL, MODE, ONE_INST>(M, s_scene, WW, U.blas_base_idx, want_extend, p.ro, p.rd, RT_T_MAX, t_, tri_,
-                                    inst_, any_, cnt_nodes, cnt_tris);
+      if constexpr (SWEEP) {
+        traverse_leaves<false, MODE>(M, s_scene, WW, LeafSweep{RT_PT_SWEEP_ARG}, U.blas_base_idx, want_extend, p.ro, p.rd, RT_T_MAX,
+                                     t_, tri_, inst_, any_);
+      } else {
+        traverse<false, DETAIL, MODE, ONE_INST>(M, s_scene, WW, U.blas_base_idx, want_extend, p.ro, p.rd, RT_T_MAX, t_, tri_,
+                                      inst_, any_, cnt_nodes, cnt_tris);
+      }
       RT_LSTAT(5, want_extend && inst_ >= 0);
       if (want_extend) {
         if (inst_ < 0) {

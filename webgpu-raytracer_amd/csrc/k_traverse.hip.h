@@ -160,7 +160,7 @@ __device__ __forceinline__ void wave_work_at(WaveWork& W, char* wbase) {
 
 // Diagnostic build only (-DRT_LANE_STATS, tools/lane_stats.py): how many lanes are active each time a wave executes one of
 // the parts of a trip — g_lane_stats[2 k] = times part k ran, [2 k + 1] = active lanes summed.  Parts: 0 shade, 1 / 2 node step
-// and triangle chunk of the shadow walk, 3 / 4 the same of the extension walk, 5 surface frame of the new hit, 6 start of a
+// and triangle chunk of the shadow walk (a sweep form: leaf step and chunk), 3 / 4 the same of the extension walk, 5 surface frame of the new hit, 6 start of a
 // sample (camera ray + G-buffer surface), 7 end of a sample.  In the one-leaf forms of the persistent kernel part 5 only records
 // the hit and part 6 makes the camera ray and loads the G-buffer words; 8 is the one pass that makes the surface frame of both.
 // Nothing else reads the array; in the product build RT_LSTAT is empty.
@@ -627,6 +627,175 @@ __device__ __forceinline__ void traverse(const TravMem& M, const f4* lds, const 
   } else {
     out_inst = s.best_inst;
   }
+}
+
+// ---------------------------------------------------------------------------------------------
+// traverse_leaves(): the walk of a one-leaf scene whose BLAS the host has found sweepable (scene_facts.h walk_facts): the
+// stored box of every node lies inside its parent's, so a leaf's slab test can pass only where every ancestor's passed, and
+// the leaves the node walk reaches and hits are the leaves whose own test passes, in pre-order, each against the bound the
+// leaves before it left.  The wave therefore tests the LEAVES alone, all lanes at the same leaf at the same time:
+//   * no lane has a node of its own (no curr, leaf, resume, no trav_leave, no look every four steps);
+//   * the leaf record (L.recs: the node's box and word, and the multiplier that divides by its count) is wave-uniform: read
+//     through the scalar cache, one record ahead, it is an operand of the slab test, not a divergent LDS read;
+//   * the owner of an item is the r-th lane that hit the leaf and its triangle the k-th of the leaf, (r, k) = divmod(item,
+//     count): no prefix sums over per-lane counts.
+// Closest hit: the lanes that hit a leaf need its result as the bound of the next leaf, so the wave tests the leaf's items
+// at that leaf, each against its owner's bound at leaf entry, accepted by the atomicMin of tri_flush.  Any hit: the answer
+// does not depend on a bound or an order, so nobody waits; the lanes queue (owner, triangle) items across leaves, the wave
+// tests 64 of them whenever the queue holds as many and the rest at the end, and a lane found occluded queues no more.
+// Node 0 (the TLAS leaf, world space) and the instance entry are those of traverse<.., ONE_INST>.
+// Guard: the argument needs finite inv_d and o_inv_d (fmin / fmax drop a NaN, and 0 * inf makes one where a direction
+// component is zero and a box face lies at 0).  If a walking lane of the wave has a non-finite component, or the host asks
+// for it (L.guard, a test hook), the whole wave takes traverse() for this walk.
+// Product build only: the nodes a ray visits are not those of the reference, so there is nothing to count.
+typedef const f4 __attribute__((address_space(4))) * rt_cptr;   // wave-uniform reads through the scalar cache
+struct LeafSweep {
+  const float4* recs;   // n_leaves + 1 records of 32 bytes (the last one padding for the read ahead)
+  uint32_t n_leaves;
+  bool guard;
+};
+__device__ __forceinline__ bool rt_finite3(rt3 v) {   // on the bits: no comparison a compiler flag could fold
+  return (rt_f2u(v.x) & 0x7f800000u) != 0x7f800000u && (rt_f2u(v.y) & 0x7f800000u) != 0x7f800000u &&
+         (rt_f2u(v.z) & 0x7f800000u) != 0x7f800000u;
+}
+// one triangle test of a sweep: item owner's ray from W.rays, the triangle from LDS
+__device__ __forceinline__ bool sweep_test(const TravMem& M, const f4* lds, const WaveWork& W, uint32_t owner, uint32_t tri, float& t) {
+  const f4 ra = W.rays[2 * owner];
+  const rt_f3_16 rb = *(const rt_f3_16 __attribute__((address_space(3)))*)(W.rays + 2 * owner + 1);
+  LocalRay q;
+  q.o = rt3_make(ra.x, ra.y, ra.z);
+  q.d = rt3_make(rb.x, rb.y, rb.z);
+  const uint32_t slot = M.l_tri + __umul24(tri, (uint32_t)RT_TRI_STRIDE);
+  const f4 g0 = ld_l(lds, slot), g1 = ld_l(lds, slot + 1u), g2 = ld_l(lds, slot + 2u);
+  return hit_tri_nb(g0, g1, g2, q, M.t_min, ra.w, t);
+}
+template <bool ANY, int MODE>
+__device__ __forceinline__ void traverse_leaves(const TravMem& M, const f4* lds, const WaveWork& W, const LeafSweep& L,
+                                                uint32_t blas_base, bool active, rt3 o, rt3 d, float t_max, float& out_t,
+                                                int32_t& out_tri, int32_t& out_inst, bool& out_any) {
+  static_assert(MODE == RT_TRAV_LDS, "the leaf sweep is a one-leaf LDS form");
+  const uint32_t lane = threadIdx.x & 63u;
+  out_t = t_max;
+  out_tri = -1;
+  out_inst = -1;
+  out_any = false;
+  // node 0, the TLAS leaf: a miss ends the walk, a hit enters the one instance
+  const f4 lo0 = ld_l(lds, M.l_nodes), hi0 = ld_l(lds, M.l_nodes + 1u);
+  const LocalRay rw = make_ray(o, d);
+  const bool walking = active && blas_base != 0u && hit_box4(lo0, hi0, rw.inv_d, rw.o_inv_d, M.t_min, t_max);
+  if (__builtin_amdgcn_ballot_w64(walking) == 0ull) return;
+  const uint32_t inst0 = __builtin_amdgcn_readfirstlane(rt_f2u(hi0.w) >> 3);
+  uint32_t root_;
+  const LocalRay q = to_instance<MODE>(M, lds, inst0, o, d, root_);
+  const bool finite = rt_finite3(q.inv_d) && rt_finite3(q.o_inv_d);
+  if (L.guard || __builtin_amdgcn_ballot_w64(walking && !finite) != 0ull) {
+    // (inlined, the node walk costs the plain sweep form 27 spilled VGPRs, 48 bytes of scratch per lane; called as a function
+    // of its own, or replaced by the one-ray-per-lane walk of k_intersect.hip.h, it cost more: 57 and 39)
+    uint32_t n0 = 0u, n1 = 0u;
+    traverse<ANY, false, MODE, true>(M, lds, W, blas_base, active, o, d, t_max, out_t, out_tri, out_inst, out_any, n0, n1);
+    return;
+  }
+  if (walking) {
+    f4 ra, rb;
+    ra.x = q.o.x; ra.y = q.o.y; ra.z = q.o.z; ra.w = t_max;   // .w: the bound the lane's items are tested against
+    rb.x = q.d.x; rb.y = q.d.y; rb.z = q.d.z; rb.w = 0.0f;    // .w (any hit): non-zero once an item of the lane was accepted
+    W.rays[2 * lane] = ra;
+    W.rays[2 * lane + 1] = rb;
+  }
+  const rt_lptr32_ordered items = (rt_lptr32_ordered)W.items;
+  const rt_cptr recs = (rt_cptr)L.recs;
+  const uint32_t n = L.n_leaves;
+  f4 lo = recs[0], hi = recs[1];
+  if (ANY) {
+    // The queue is the wave's items followed by its result slots, which this walk does not use: it holds fewer than 64 items
+    // when a leaf appends at most 64 * 7, and RT_WORK_BYTES_PER_WAVE leaves 64 * 7 + 128 words.
+    const rt_lptr32_ordered flags = (rt_lptr32_ordered)W.rays;   // word 8 * lane + 7
+    bool occluded = false;
+    uint32_t queued = 0u;   // wave-uniform
+    auto test_chunk = [&](uint32_t base, uint32_t count) {
+      __builtin_amdgcn_wave_barrier();
+      RT_LSTAT(2, lane < count);
+      if (lane < count) {
+        const uint32_t it = items[base + lane];
+        const uint32_t owner = it >> 26, tri = it & 0x03ffffffu;
+        float t;
+        if (sweep_test(M, lds, W, owner, tri, t)) flags[8u * owner + 7u] = 1u;
+      }
+      __builtin_amdgcn_wave_barrier();
+    };
+    for (uint32_t i = 0; i < n; i++) {
+      const f4 clo = lo, chi = hi;
+      lo = recs[2u * i + 2u];
+      hi = recs[2u * i + 3u];
+      RT_LSTAT(1, walking & !occluded);
+      const bool hit = walking & !occluded & hit_box4(clo, chi, q.inv_d, q.o_inv_d, M.t_min, t_max);
+      const unsigned long long hm = __builtin_amdgcn_ballot_w64(hit);
+      if (hm == 0ull) continue;
+      const uint32_t data = rt_f2u(chi.w), cnt = data & 7u;
+      const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(hm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)hm, 0u));
+      if (hit) {
+        const rt_lptr32_ordered it = items + queued + __umul24(rank, cnt);
+        const uint32_t word = (lane << 26) | (data >> 3);
+        for (uint32_t k = 0; k < cnt; k++) it[k] = word + k;
+      }
+      queued += (uint32_t)__builtin_popcountll(hm) * cnt;
+      if (queued >= 64u) {
+        do {
+          queued -= 64u;
+          test_chunk(queued, 64u);   // the 64 newest: what stays is the front of the queue
+        } while (queued >= 64u);
+        occluded = flags[8u * lane + 7u] != 0u;
+      }
+    }
+    if (queued) test_chunk(0u, queued);
+    __builtin_amdgcn_wave_barrier();
+    out_any = walking && flags[8u * lane + 7u] != 0u;
+    __builtin_amdgcn_wave_barrier();
+    return;
+  }
+  float closest = t_max;
+  int32_t best_tri = -1;
+  for (uint32_t i = 0; i < n; i++) {
+    const f4 clo = lo, chi = hi;
+    lo = recs[2u * i + 2u];
+    hi = recs[2u * i + 3u];
+    RT_LSTAT(3, walking);
+    const bool hit = walking & hit_box4(clo, chi, q.inv_d, q.o_inv_d, M.t_min, closest);
+    const unsigned long long hm = __builtin_amdgcn_ballot_w64(hit);
+    if (hm == 0ull) continue;
+    const uint32_t data = rt_f2u(chi.w), cnt = data & 7u, first = data >> 3, div = rt_f2u(clo.w);
+    const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(hm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)hm, 0u));
+    const uint32_t total = (uint32_t)__builtin_popcountll(hm) * cnt;
+    if (hit) {
+      items[rank] = lane;
+      reinterpret_cast<float*>(W.rays)[8u * lane + 3u] = closest;
+      W.res[lane] = ~0ull;
+    }
+    __builtin_amdgcn_wave_barrier();
+    for (uint32_t c = 0; c < total; c += 64u) {
+      const uint32_t j = c + lane;
+      RT_LSTAT(4, j < total);
+      if (j < total) {
+        const uint32_t r = (j * div) >> 16, k = j - r * cnt;   // j < 64 * 7: exact (scene_facts.h leaf_divider)
+        const uint32_t owner = items[r], tri = first + k;
+        float t;
+        if (sweep_test(M, lds, W, owner, tri, t)) atomicMin(&W.res[owner], ((unsigned long long)rt_f2u(t) << 32) | tri);
+      }
+    }
+    __builtin_amdgcn_wave_barrier();
+    if (hit) {
+      const unsigned long long best = W.res[lane];
+      if (best != ~0ull) {
+        closest = rt_u2f((uint32_t)(best >> 32));
+        best_tri = (int32_t)(uint32_t)best;
+      }
+    }
+    __builtin_amdgcn_wave_barrier();
+  }
+  out_t = closest;
+  out_tri = best_tri;
+  out_any = best_tri != -1;
+  out_inst = out_any ? (int32_t)inst0 : -1;
 }
 
 }  // namespace rtk

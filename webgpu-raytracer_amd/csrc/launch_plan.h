@@ -33,12 +33,25 @@ struct PlanKnobs {
   int wf_blocks_per_cu = 0;      // 0 = default for the block size (MI355RT_WF_BLOCKS_PER_CU)
   int wf_rayreg = -1;            // node-walk trace kernels: -1 = by scene, 0 / 1 = MI355RT_WF_RAYREG
   bool plain_materials = true;   // MI355RT_PLAIN_MATERIALS=0: a scene of plain materials runs the generic wide form all the same
+  bool leaf_sweep = true;        // MI355RT_LEAF_SWEEP=0: a sweepable one-leaf scene keeps the node walk in the wide forms all the same
+  uint32_t leaf_sweep_cap = 16;  // the most BLAS leaves a scene may have and still be swept (scene_facts.h walk_facts)
+  bool leaf_sweep_guard = false; // MI355RT_LEAF_SWEEP_GUARD=1 (test hook): every walk of a sweep form takes its node-walk branch,
+                                 // the one a ray with a non-finite slab operand sends its wave to
 };
 // What the host knows of the uploaded scene's materials (scene_facts.h works it out from the bytes of a topology upload).
 // plain: every triangle is Lambertian or a light, untextured, and emits only if it is a light.  known = false: the host has
 // not seen the bytes the device holds (a device-resident world update, an upload too large to matter), and nothing is assumed.
 struct SceneFacts {
   bool known = false, plain = false;
+};
+// What the host knows of the BLAS the one TLAS leaf of a one-leaf scene names (scene_facts.h walk_facts works it out from the
+// caller's bytes of rt_upload_bvh).  sweepable: the tree is a canonical pre-order tree of finite, nested boxes with at most
+// PlanKnobs::leaf_sweep_cap leaves of 1-7 triangles, so that a walk over its n_leaves leaf boxes alone visits the triangles
+// the node walk visits (k_traverse.hip.h traverse_leaves).  known = false: the nodes were written on the device, or are too
+// many to belong to a one-leaf LDS scene.
+struct WalkFacts {
+  bool known = false, sweepable = false;
+  uint32_t n_leaves = 0;
 };
 
 // ---- byte sizes of the arrays a walk stages, each whole or not at all
@@ -152,6 +165,7 @@ struct PersistentShape {
   size_t dyn;          // dynamic LDS per workgroup: work queues + records
   LdsPlan plan;
   bool plain = false;  // ... the wide form without the code of the materials the scene does not have (k_pathtrace_persistent_plain)
+  bool sweep = false;  // ... the wide form (plain or not) whose walks sweep the BLAS leaves (k_pathtrace_sweep_wide / _plain)
 };
 // The 256-thread forms of the persistent kernel (and the radiance query, which runs its path loop): the whole scene in LDS
 // when it fits beside four wave queues (scene_fits_lds), else six workgroups per CU (6 waves per SIMD), each
@@ -167,7 +181,7 @@ inline PersistentShape persistent_plan(const SceneSize& s, const PlanKnobs& k) {
 }
 // What compute() launches the persistent kernel in, for a dispatch of n_frames frames; detailed: the counting build.
 inline PersistentShape persistent_shape(const SceneSize& s, const PlanKnobs& k, uint32_t n_frames, bool detailed,
-                                        const SceneFacts& facts = SceneFacts()) {
+                                        const SceneFacts& facts = SceneFacts(), const WalkFacts& walk = WalkFacts()) {
   PersistentShape P = persistent_plan(s, k);
   // LDS form of a scene whose TLAS is one node, which is a leaf (k_validate_scene, or the world update's builder): the walks skip the TLAS
   // half of the node step (k_traverse.hip.h traverse<.., ONE_INST>)
@@ -187,6 +201,9 @@ inline PersistentShape persistent_shape(const SceneSize& s, const PlanKnobs& k, 
   P.dyn = (P.wide ? wide_blocks : (size_t)4 * RT_WORK_BYTES_PER_WAVE) + staged_lds;
   // the wide form of a scene whose materials are known to be plain: the same workgroups, the same LDS layout and `dyn`
   P.plain = P.wide && facts.known && facts.plain && k.plain_materials;
+  // the wide form of a scene whose BLAS the host knows to be sweepable: again the same workgroups, LDS layout and `dyn` (the
+  // leaf records are read from global memory through the scalar cache)
+  P.sweep = P.wide && walk.known && walk.sweepable && walk.n_leaves >= 1 && walk.n_leaves <= k.leaf_sweep_cap && k.leaf_sweep;
   return P;
 }
 

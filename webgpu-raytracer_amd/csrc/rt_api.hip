@@ -235,6 +235,15 @@ struct rt_ctx {
   lp::SceneFacts facts;          // materials of the topology on the device (scene_facts.h): worked out from the caller's bytes
                                  // in rt_upload(RT_KIND_TOPOLOGY), unknown after every other writer of the topology records
   int pt_form = RT_PT_FORM_NONE; // form of the last path-trace dispatch of compute() (rt_debug_pt_form)
+  // The leaf sweep of a one-leaf scene (scene_facts.h walk_facts).  The host keeps the caller's bytes it is worked out from: the
+  // BLAS nodes and the TLAS leaf of rt_upload_bvh when they are few enough to belong to a one-leaf LDS scene, and the BLAS
+  // root of every instance of an instance upload.  A device-resident world update forgets them (walk_forget).
+  std::vector<rt_node> blas_host;          // empty: not kept (too large, not a one-node TLAS, or made on the device)
+  rt_node tlas0_host = {};
+  std::vector<uint32_t> inst_root_host;    // empty: not kept
+  lp::WalkFacts walk;                      // of the nodes and instances on the device, once walk_dirty is cleared
+  bool walk_dirty = true;
+  DeviceBuffer leaf_recs;                  // walk.n_leaves + 1 records of 32 bytes
   DeviceBuffer ticket;    // tile ticket counter of the persistent kernel
   DeviceBuffer slots;     // DevFrameSlot table of the current (batched) dispatch
   // pinned staging ring for the slot tables: the H2D copy of a dispatch's table is truly asynchronous and its source
@@ -611,10 +620,46 @@ lp::SceneSize scene_size(const rt_ctx* c) {
   return {c->n_nodes, c->n_pairs, c->n_tris, c->n_instances, c->n_verts, c->n_lights, c->blas_offset};
 }
 
+// the nodes or the instances on the device are no longer bytes the host has seen
+void walk_forget(rt_ctx* c) {
+  c->blas_host.clear();
+  c->inst_root_host.clear();
+  c->walk = lp::WalkFacts();
+  c->walk_dirty = true;
+}
+
+// The walk facts of the scene on the device and, when its BLAS is sweepable, the leaf records traverse_leaves reads: worked
+// out again when the node or the instance array has changed.
+static int walk_prepare(rt_ctx* c) {
+  if (!c->walk_dirty) return RT_OK;
+  c->walk = lp::WalkFacts();
+  c->walk_dirty = false;
+  if (c->nodes_from_device || c->blas_offset != 1u || c->blas_host.empty() ||
+      c->blas_host.size() != (size_t)c->n_nodes - c->blas_offset || c->inst_root_host.size() != c->n_instances)
+    return RT_OK;
+  const uint32_t word = c->tlas0_host.data;   // the TLAS leaf: instance << 3 | 1 (k_validate_scene has seen the device's copy)
+  const uint32_t inst = word >> 3;
+  if (word == 0u || inst >= c->n_instances) return RT_OK;
+  scene_facts::LeafRecord recs[scene_facts::kMaxLeafRecords + 1];
+  const lp::WalkFacts f = scene_facts::walk_facts(c->blas_host.data(), c->blas_host.size(), c->inst_root_host[inst],
+                                                  c->knobs.leaf_sweep_cap, recs);
+  if (f.known && f.sweepable) {
+    recs[f.n_leaves] = recs[f.n_leaves - 1u];   // the record the sweep reads ahead at its last leaf, and does not use
+    const size_t bytes = ((size_t)f.n_leaves + 1) * sizeof(scene_facts::LeafRecord);
+    int r = ensure_buffer(c, c->leaf_recs, bytes, false);
+    if (r < 0) return r;
+    HIP_TRY(c, hipMemcpyAsync(c->leaf_recs.ptr, recs, bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));   // the source is on the stack
+  }
+  c->walk = f;
+  return RT_OK;
+}
+
 int prepare_scene(rt_ctx* c) {
   {
     int r = validate_scene(c);
     if (r < 0) return r;
+    if ((r = walk_prepare(c)) < 0) return r;
   }
   if (c->tris_dirty && c->n_tris && c->n_verts) {
     int r = ensure_buffer(c, c->tri_geom, (size_t)c->n_tris * 16 * RT_TRI_STRIDE, true);
@@ -973,6 +1018,8 @@ rt_ctx* rt_create(int device_ordinal) {
   if (const char* e = getenv("MI355RT_WF_OVERLAP")) c->wf_overlap = atoi(e) != 0;
   if (const char* e = getenv("MI355RT_NO_LDS_STAGING")) c->knobs.no_lds_staging = atoi(e) != 0;
   if (const char* e = getenv("MI355RT_PLAIN_MATERIALS")) c->knobs.plain_materials = atoi(e) != 0;
+  if (const char* e = getenv("MI355RT_LEAF_SWEEP")) c->knobs.leaf_sweep = atoi(e) != 0;
+  if (const char* e = getenv("MI355RT_LEAF_SWEEP_GUARD")) c->knobs.leaf_sweep_guard = atoi(e) != 0;
   if (const char* e = getenv("MI355RT_SHADE_BLOCKS_PER_CU")) c->shade_per_cu = std::max(1, std::min(4096, atoi(e)));
   if (const char* e = getenv("MI355RT_WF_BLOCK")) {
     const int b = atoi(e);
@@ -1489,6 +1536,7 @@ static int world_update_body(rt_ctx* c, const rt_world_frame* f, bool* touched) 
   auto& W = c->world;
   c->epoch++;   // drops frames traced ahead (rt_set_lookahead)
   c->facts = lp::SceneFacts();   // the topology records are (re)made on the device, or their buffer is resized: the host has not seen them
+  walk_forget(c);                // ... nor the nodes and the instances
   HIP_TRY(c, hipSetDevice(c->device));
   int r, ret = RT_OK;
   if (!W.valid || W.epoch != f->static_epoch) {
@@ -1714,6 +1762,7 @@ int rt_world_update(rt_ctx* c, const rt_world_frame* f) {
     c->scene_problem = "the device-resident world update failed part-way (" + why + "): the scene buffers hold a mix of two scenes; upload the scene again";
     c->tris_dirty = c->inst_dirty = c->lights_dirty = c->nodes_dirty = c->pairs_dirty = c->roots_dirty = c->world_rec_dirty = true;
     c->facts = lp::SceneFacts();
+    walk_forget(c);
     c->world.static_cached = false;
     c->world.valid = false;
     c->error = why;
@@ -1809,6 +1858,11 @@ int rt_upload(rt_ctx* c, rt_kind kind, const void* data, size_t bytes) {
           c->root_w_host[r] += (float)s2;
         }
         if (old_roots != c->blas_roots) c->pairs_dirty = true;   // BLAS-local skips are resolved against the set of roots
+        // the BLAS root of every instance, for the walk facts of a one-leaf scene (which has few)
+        c->inst_root_host.clear();
+        if (c->n_instances <= scene_facts::kMaxWalkNodes)
+          for (uint32_t k = 0; k < c->n_instances; k++) c->inst_root_host.push_back(hi[k].blas_node_offset);
+        c->walk_dirty = true;
       }
       c->roots_dirty = true;
       c->nodes_dirty = true;
@@ -1907,6 +1961,13 @@ int rt_upload_bvh(rt_ctx* c, const float* tlas, uint32_t n_tlas, const float* bl
   c->world_rec_dirty = true;
   c->pairs_dirty = true;
   c->nodes_from_device = false;
+  // the caller's bytes, for the walk facts: a one-node TLAS over a BLAS small enough for a one-leaf LDS scene
+  c->blas_host.clear();
+  if (n_tlas == 1u && n_blas && n_blas <= scene_facts::kMaxWalkNodes) {
+    c->blas_host.assign((const rt_node*)blas, (const rt_node*)blas + n_blas);
+    std::memcpy(&c->tlas0_host, tlas, sizeof(rt_node));
+  }
+  c->walk_dirty = true;
   return r ? RT_REALLOCATED : RT_OK;
 }
 
@@ -3890,6 +3951,9 @@ static const void* const pt_one_leaf_fns[2] = {(const void*)rtk::k_pathtrace_per
 static const void* const pt_wide_fn = (const void*)rtk::k_pathtrace_persistent_wide<false, true, true>;
 // ... and the wide form of a scene whose materials the host knows to be plain (lp::PersistentShape::plain)
 static const void* const pt_plain_fn = (const void*)rtk::k_pathtrace_persistent_plain<false, true, true>;
+// ... and the two of them with the leaf sweep for walks (lp::PersistentShape::sweep), by [plain]
+static const void* const pt_sweep_fns[2] = {(const void*)rtk::k_pathtrace_sweep_wide<false, true, true>,
+                                            (const void*)rtk::k_pathtrace_sweep_plain<false, true, true>};
 
 // compute() for n consecutive frame counts in ONE dispatch of each kernel (n == 1: the plain compute()).
 // n_commit < n: frames n_commit .. n-1 are traced AHEAD (speculative lookahead): their host state is not committed and their
@@ -4046,9 +4110,11 @@ static int compute_frames(rt_ctx* c, const uint32_t* frame_counts, uint32_t n, u
   } else {
     // persistent kernel: grid = resident workgroups, tiles handed out through a ticket counter
     HIP_TRY(c, hipMemsetAsync(c->ticket.ptr, 0, 4, c->stream));
-    lp::PersistentShape shape = lp::persistent_shape(size, c->knobs, n, c->detailed_counters, c->facts);
+    lp::PersistentShape shape = lp::persistent_shape(size, c->knobs, n, c->detailed_counters, c->facts, c->walk);
     if (shape.one_inst && c->world_rec_dirty) return fail(c, RT_ERR_INTERNAL, "one-leaf form without its world records");
-    const void* fn = shape.plain      ? pt_plain_fn
+    if (shape.sweep && (c->walk_dirty || !c->leaf_recs.ptr)) return fail(c, RT_ERR_INTERNAL, "sweep form without its leaf records");
+    const void* fn = shape.sweep      ? pt_sweep_fns[shape.plain]
+                     : shape.plain    ? pt_plain_fn
                      : shape.wide     ? pt_wide_fn
                      : shape.one_inst ? pt_one_leaf_fns[c->detailed_counters]
                                       : pt_fns[c->detailed_counters][shape.lds];
@@ -4058,7 +4124,10 @@ static int compute_frames(rt_ctx* c, const uint32_t* frame_counts, uint32_t n, u
     const uint32_t blocks = grid_blocks(c, per_cu, 0, (own_tiles * n + shape.waves - 1) / shape.waves);
     uint32_t* ticket = (uint32_t*)c->ticket.ptr;
     uint32_t nn = c->n_nodes, nt = c->n_tris, ni = c->n_instances, nv = c->n_verts, ns = n;
-    void* args[] = {&S, &F, &c->uniforms, &ticket, &nn, &nt, &ni, &nv, &dslots, &ns, &shape.plan};
+    // (the two sweep forms read two parameters more; the others have no such parameters and are not handed them)
+    const float4* leaf_recs = (const float4*)c->leaf_recs.ptr;
+    uint32_t leaf_info = c->walk.n_leaves | (c->knobs.leaf_sweep_guard ? 0x80000000u : 0u);
+    void* args[] = {&S, &F, &c->uniforms, &ticket, &nn, &nt, &ni, &nv, &dslots, &ns, &shape.plan, &leaf_recs, &leaf_info};
     ev = next_events(c, RT_TIMER_PATHTRACE);
     if (ev) HIP_TRY(c, hipEventRecord(ev->a, c->stream));
     HIP_TRY(c, hipLaunchKernel(fn, dim3(blocks), dim3(64 * shape.waves), args, shape.dyn, c->stream));
@@ -4066,7 +4135,8 @@ static int compute_frames(rt_ctx* c, const uint32_t* frame_counts, uint32_t n, u
     c->pt_launch[1] = blocks;
     c->pt_launch[2] = (uint32_t)shape.dyn;
     c->pt_launch[3] = (uint32_t)per_cu;
-    c->pt_form = shape.plain ? RT_PT_FORM_PLAIN : RT_PT_FORM_GENERIC;
+    c->pt_form = shape.sweep ? (shape.plain ? RT_PT_FORM_PLAIN_SWEEP : RT_PT_FORM_GENERIC_SWEEP)
+                             : (shape.plain ? RT_PT_FORM_PLAIN : RT_PT_FORM_GENERIC);
     if (ev) HIP_TRY(c, hipEventRecord(ev->b, c->stream));
     if (n > 1)  // ordered accumulation of the batch's frame colours
       hipLaunchKernelGGL(rtk::k_accumulate_frames, dim3((uint32_t)((npx + 255) / 256)), dim3(256), 0, c->stream, F, dslots,

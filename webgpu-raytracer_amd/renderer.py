@@ -794,10 +794,19 @@ class WebGPURenderer:
     def debugPtForm(self):
         """Materials the path-trace kernel of the last compute() dispatch carried code for: "plain" (the wide one-leaf form
         of a scene the host knows to hold untextured Lambertian triangles and lights only), "generic" (every other launch
-        of the persistent kernel) or "none" (no dispatch yet, or one that ran another kernel)."""
+        of the persistent kernel) or "none" (no dispatch yet, or one that ran another kernel).  The answer is the same
+        whichever walk the kernel ran (debugPtWalk)."""
         form = int(self.L.rt_debug_pt_form(self.ctx))
         self._check(min(form, 0), "debugPtForm")
-        return ("none", "generic", "plain")[form]
+        return ("none", "generic", "plain", "generic", "plain")[form]
+
+    def debugPtWalk(self):
+        """How the path-trace kernel of the last compute() dispatch walked the BLAS: "sweep" (RT_PT_FORM_GENERIC_SWEEP,
+        RT_PT_FORM_PLAIN_SWEEP: the leaves alone, in wave lock-step), "nodes" (every other launch of the persistent kernel)
+        or "none" (no dispatch yet, or one that ran another kernel)."""
+        form = int(self.L.rt_debug_pt_form(self.ctx))
+        self._check(min(form, 0), "debugPtWalk")
+        return ("none", "nodes", "nodes", "sweep", "sweep")[form]
 
     def getKernelCounters(self, kernel):
         """kernel: 0 = primary visibility, 1 = path trace"""
