@@ -3,23 +3,20 @@ bake_model.cpp: the gather model's translation unit plus the texel rule of inclu
 built with the flags of oracle/Makefile and driven through a GatherModel that loads the bake library instead; a bake of the
 model is its points followed by its gather.  Also grid_uv, an override UV layout with one triangle per grid cell."""
 import ctypes
+import functools
 import math
 import os
-import subprocess
 
 import numpy as np
 
 import gather_util as gu
-import oracle_lib
+import model_build
 import radiance_util as ru
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-REPO = os.path.dirname(HERE)
 SRC = os.path.join(HERE, "model", "bake_model.cpp")
 LIB = os.path.join(HERE, "model", "_build", "libbake_model.so")
 SEED = gu.SEED
-
-_model = None
 
 
 class BakeDesc(ctypes.Structure):
@@ -28,47 +25,19 @@ class BakeDesc(ctypes.Structure):
                 ("t_max", ctypes.c_float), ("reserved", ctypes.c_uint32 * 3)]
 
 
+@functools.lru_cache(maxsize=None)
 def model_lib():
     """the bake library: everything gather_util declares on its own, plus bake_model_points"""
-    global _model
-    if _model is not None:
-        return _model
-    deps = [SRC, gu.SRC, ru.SRC, os.path.join(REPO, "oracle", "rt_oracle.cpp"), os.path.join(REPO, "include", "mi355rt_math.h"),
-            os.path.join(REPO, "include", "mi355rt_layout.h")]
-    if not os.path.exists(LIB) or any(os.path.getmtime(d) > os.path.getmtime(LIB) for d in deps):
-        os.makedirs(os.path.dirname(LIB), exist_ok=True)
-        tmp = "%s.%d.so" % (LIB[:-3], os.getpid())   # parallel test processes: each builds its own, the rename is atomic
-        subprocess.run(["g++"] + ru.FLAGS + ["-shared", "-o", tmp, SRC], check=True)
-        os.replace(tmp, LIB)
-    saved = (oracle_lib.ORACLE_LIB, oracle_lib._lib)
-    try:
-        oracle_lib.ORACLE_LIB, oracle_lib._lib = LIB, None
-        L = oracle_lib.lib()
-    finally:
-        oracle_lib.ORACLE_LIB, oracle_lib._lib = saved
-    vp, u32 = ctypes.c_void_p, ctypes.c_uint32
-    L.radiance_model_trace.argtypes = [vp, vp, u32, u32, u32, u32, ctypes.c_int, vp, vp]
-    L.radiance_model_trace.restype = None
-    L.radiance_model_camera_rays.argtypes = [vp, vp]
-    L.radiance_model_camera_rays.restype = None
-    L.gather_model_directions.argtypes = [vp, u32, u32, u32, vp]
-    L.gather_model_directions.restype = None
-    L.gather_model_gather.argtypes = [vp, vp, u32, u32, u32, u32, vp, vp, vp]
-    L.gather_model_gather.restype = None
+    L = gu.bind_model(model_build.build(SRC, LIB, ru.FLAGS + ["-shared"]))
+    vp = ctypes.c_void_p
     L.bake_model_points.argtypes = [vp, vp, vp, vp, vp, vp, vp]
-    L.bake_model_points.restype = u32
-    _model = L
+    L.bake_model_points.restype = ctypes.c_uint32
     return L
 
 
 class BakeModel(gu.GatherModel):
     """GatherModel on the bake library, plus bakePoints / bakeIrradiance"""
-
-    def __init__(self, threads=0):
-        self.L = model_lib()
-        self.ctx = self.L.oracle_create()
-        self.L.oracle_set_threads(self.ctx, threads)
-        self.width = self.height = 0
+    _library = staticmethod(model_lib)
 
     def bakePoints(self, inst, width, height, t_max=1e30, pad_base=0, atlas_uv=None, weights=False):
         """-> (points (n, 8) f32 in the rt_gather_point layout, texels (n,) u32, owner (height, width) i32); weights=True:
@@ -98,12 +67,7 @@ class BakeModel(gu.GatherModel):
         return atlas.reshape(height, width, 4), points, texels, counts
 
 
-def model_for(W, bridge, width=16, height=16):
-    """a bake model with the scene uploaded as upload_scene does it"""
-    m = BakeModel()
-    m.buildPipeline(4, 1)
-    W.upload_scene(m, bridge, width, height)
-    return m
+model_for = functools.partial(ru.model_for, cls=BakeModel)
 
 
 def instance_triangles(bridge, inst):

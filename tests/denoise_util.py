@@ -3,11 +3,13 @@ plain loops with the six tap counts), built with the flags of oracle/Makefile as
 composition into a call; the synthetic guide generator "two walls"; the named patterns with their written-out counts; and the
 hand-worked cases with written-out answers."""
 import ctypes
+import functools
 import os
-import subprocess
 
 import numpy as np
 
+import dilate_util
+import model_build
 import radiance_util as ru
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -20,23 +22,13 @@ COUNTS = ("accepted", "outside", "unguided", "normal", "plane", "distance")
 CELL = 0.1
 PARAMS = dict(normal_cos=0.9, plane_eps=0.02, max_dist=0.5)
 
-_model = None
 
-
+@functools.lru_cache(maxsize=None)
 def model_lib():
-    global _model
-    if _model is not None:
-        return _model
-    if not os.path.exists(LIB) or os.path.getmtime(SRC) > os.path.getmtime(LIB):
-        os.makedirs(os.path.dirname(LIB), exist_ok=True)
-        tmp = "%s.%d.so" % (LIB[:-3], os.getpid())   # parallel test processes: each builds its own, the rename is atomic
-        subprocess.run(["g++"] + ru.FLAGS + ["-I", os.path.join(REPO, "include"), "-shared", "-o", tmp, SRC], check=True)
-        os.replace(tmp, LIB)
-    L = ctypes.CDLL(LIB)
+    L = ctypes.CDLL(model_build.build(SRC, LIB, ru.FLAGS + ["-I", os.path.join(REPO, "include"), "-shared"]))
     vp, u32, f32 = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_float
     L.denoise_model_pass.argtypes = [vp, u32, u32, u32, f32, f32, f32, vp, vp, u32, vp, vp]
     L.denoise_model_pass.restype = None
-    _model = L
     return L
 
 
@@ -49,10 +41,7 @@ def as_f32(atlas):
     return a
 
 
-def words(a):
-    """any 16-byte-texel atlas -> (H, W, 4) u32"""
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint32).reshape(a.shape[0], a.shape[1], 4)
+words = dilate_util.words   # any 16-byte-texel atlas -> (H, W, 4) u32
 
 
 def model_pass(atlas, points, texels, step, *, plane_eps, max_dist, normal_cos=0.9):

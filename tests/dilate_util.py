@@ -3,11 +3,12 @@ force over every texel of the disc), built with the flags of oracle/Makefile as 
 cases with written-out source maps; the random patterns of the GPU tests with the figures they must show; and the numpy
 application of a source map, which ties the model's atlas to its own source map."""
 import ctypes
+import functools
 import os
-import subprocess
 
 import numpy as np
 
+import model_build
 import radiance_util as ru
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -18,23 +19,13 @@ NONE = 0xffffffff
 MINUS_TWO = 0xc0000000            # the bits of -2.0f
 NAN, INF = float("nan"), float("inf")
 
-_model = None
 
-
+@functools.lru_cache(maxsize=None)
 def model_lib():
-    global _model
-    if _model is not None:
-        return _model
-    if not os.path.exists(LIB) or os.path.getmtime(SRC) > os.path.getmtime(LIB):
-        os.makedirs(os.path.dirname(LIB), exist_ok=True)
-        tmp = "%s.%d.so" % (LIB[:-3], os.getpid())   # parallel test processes: each builds its own, the rename is atomic
-        subprocess.run(["g++"] + ru.FLAGS + ["-shared", "-o", tmp, SRC], check=True)
-        os.replace(tmp, LIB)
-    L = ctypes.CDLL(LIB)
+    L = ctypes.CDLL(model_build.build(SRC, LIB, ru.FLAGS + ["-shared"]))
     vp, u32 = ctypes.c_void_p, ctypes.c_uint32
     L.dilate_model.argtypes = [vp, u32, u32, u32, vp, vp]
     L.dilate_model.restype = u32
-    _model = L
     return L
 
 

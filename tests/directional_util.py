@@ -4,17 +4,16 @@ bounce functions), built with the flags of oracle/Makefile and driven through a 
 library instead; and the numpy restatement of the projection (band 0 .. 1 basis, fixed summation tree) that the composition
 tests put behind radiance queries."""
 import ctypes
+import functools
 import os
-import subprocess
 
 import numpy as np
 
-import oracle_lib
+import model_build
 import probe_util as prb
 import radiance_util as ru
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-REPO = os.path.dirname(HERE)
 SRC = os.path.join(HERE, "model", "directional_model.cpp")
 LIB = os.path.join(HERE, "model", "_build", "libdirectional_model.so")
 COUNT_NAMES = ru.COUNT_NAMES
@@ -23,49 +22,23 @@ TWO_PI = np.float32(6.283185307)
 Y0 = np.float32(0.282094792)
 Y1 = np.float32(0.488602512)
 
-_model = None
 
-
+@functools.lru_cache(maxsize=None)
 def model_lib():
     """the directional library: every oracle_* and radiance_model_* entry declared as radiance_util declares it, plus the
     two directional_model_* ones"""
-    global _model
-    if _model is not None:
-        return _model
-    deps = [SRC, ru.SRC, os.path.join(REPO, "oracle", "rt_oracle.cpp"), os.path.join(REPO, "include", "mi355rt_math.h"),
-            os.path.join(REPO, "include", "mi355rt_layout.h")]
-    if not os.path.exists(LIB) or any(os.path.getmtime(d) > os.path.getmtime(LIB) for d in deps):
-        os.makedirs(os.path.dirname(LIB), exist_ok=True)
-        tmp = "%s.%d.so" % (LIB[:-3], os.getpid())   # parallel test processes: each builds its own, the rename is atomic
-        subprocess.run(["g++"] + ru.FLAGS + ["-shared", "-o", tmp, SRC], check=True)
-        os.replace(tmp, LIB)
-    saved = (oracle_lib.ORACLE_LIB, oracle_lib._lib)
-    try:
-        oracle_lib.ORACLE_LIB, oracle_lib._lib = LIB, None
-        L = oracle_lib.lib()
-    finally:
-        oracle_lib.ORACLE_LIB, oracle_lib._lib = saved
+    L = ru.bind_model(model_build.build(SRC, LIB, ru.FLAGS + ["-shared"]))
     vp, u32 = ctypes.c_void_p, ctypes.c_uint32
-    L.radiance_model_trace.argtypes = [vp, vp, u32, u32, u32, u32, ctypes.c_int, vp, vp]
-    L.radiance_model_trace.restype = None
-    L.radiance_model_camera_rays.argtypes = [vp, vp]
-    L.radiance_model_camera_rays.restype = None
     L.directional_model_directions.argtypes = [vp, u32, u32, u32, vp]
     L.directional_model_directions.restype = None
     L.directional_model_gather.argtypes = [vp, vp, u32, u32, u32, u32, vp, vp, vp]
     L.directional_model_gather.restype = None
-    _model = L
     return L
 
 
 class DirectionalModel(ru.ModelRenderer):
     """ModelRenderer on the directional library: the oracle, traceRadiance / cameraRays, plus directions / gatherDirectional"""
-
-    def __init__(self, threads=0):
-        self.L = model_lib()
-        self.ctx = self.L.oracle_create()
-        self.L.oracle_set_threads(self.ctx, threads)
-        self.width = self.height = 0
+    _library = staticmethod(model_lib)
 
     def directions(self, points, spp, seed):
         """points (n, 8) f32 in the rt_gather_point layout -> (n, spp, 3) f32: the direction of every sample"""
@@ -86,12 +59,7 @@ class DirectionalModel(ru.ModelRenderer):
         return out, hits, counts
 
 
-def model_for(W, bridge, width=16, height=16):
-    """a directional model with the scene uploaded as upload_scene does it (textures, light count of the bridge)"""
-    m = DirectionalModel()
-    m.buildPipeline(4, 1)
-    W.upload_scene(m, bridge, width, height)
-    return m
+model_for = functools.partial(ru.model_for, cls=DirectionalModel)
 
 
 def make_points(positions, normals, t_max=1e30, pad_step=ru.PAD_STEP, pad_first=ru.PAD_0):
@@ -162,23 +130,7 @@ def compose_pad_prime(trace, points, dirs, max_depth, spp, seed):
     return out, hits, extra
 
 
-def result_words(res):
-    """structured DIRECTIONAL_DTYPE (n,) -> (n, 16) u32"""
-    return np.ascontiguousarray(res).view(np.uint32).reshape(-1, 16)
-
-
-def check_against_model(res, ref, tag, nan_as_class=False):
-    """res: DIRECTIONAL_DTYPE (n,); ref: (n, 16) f32.  Bit for bit, point by point.  nan_as_class: in rows where the REFERENCE
-    has a NaN, NaNs compare as a class; every other row stays bit-exact."""
-    got, want = result_words(res), ru.u32(ref)
-    bad = got != want
-    if nan_as_class:
-        gf, wf = got.view(np.float32), want.view(np.float32)
-        model_nan_row = np.isnan(wf).any(axis=1)
-        bad &= ~(np.isnan(gf) & np.isnan(wf) & model_nan_row[:, None])
-    rows = np.nonzero(bad.any(axis=1))[0]
-    assert rows.size == 0, (tag, "points that differ", int(rows.size), rows[:8].tolist(),
-                            got[rows[:2]].view(np.float32).tolist(), want[rows[:2]].view(np.float32).tolist())
-
-
+result_words = functools.partial(ru.result_words, width=16)   # DIRECTIONAL_DTYPE (n,) -> (n, 16) u32
+# res: DIRECTIONAL_DTYPE (n,); ref: (n, 16) f32; the rule of the gathers
+check_against_model = functools.partial(ru.check_records_against_model, width=16, what="points", shown=2)
 check_counts = ru.check_counts

@@ -4,11 +4,12 @@ include/mi355rt.h "lightmaps" restated in numpy, in float64 and integer arithmet
 exact in float64); the atlas of special values the GPU tests encode; and the host build of the two per-texel functions the
 kernel applies (tests/model/encode_model.cpp), built with the flags of oracle/Makefile as the other models are."""
 import ctypes
+import functools
 import os
-import subprocess
 
 import numpy as np
 
+import model_build
 import radiance_util as ru
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -18,8 +19,6 @@ LIB = os.path.join(HERE, "model", "_build", "libencode_model.so")
 TOP = float(np.float32(2.0 ** 127 - 2.0 ** 103))      # 0x1.fffffep+126f, the largest colour the rule keeps
 NAN, INF = float("nan"), float("inf")
 F32, F16, RGBE8 = 0, 1, 2
-
-_host = None
 
 
 def as_f32(atlas):
@@ -121,21 +120,12 @@ def special_atlas(width, height, seed):
     return a.reshape(height, width, 4)
 
 
+@functools.lru_cache(maxsize=None)
 def host_lib():
-    global _host
-    if _host is not None:
-        return _host
-    if not os.path.exists(LIB) or os.path.getmtime(SRC) > os.path.getmtime(LIB) or \
-            os.path.getmtime(os.path.join(REPO, "include", "mi355rt_math.h")) > os.path.getmtime(LIB):
-        os.makedirs(os.path.dirname(LIB), exist_ok=True)
-        tmp = "%s.%d.so" % (LIB[:-3], os.getpid())   # parallel test processes: each builds its own, the rename is atomic
-        subprocess.run(["g++"] + ru.FLAGS + ["-I", os.path.join(REPO, "include"), "-shared", "-o", tmp, SRC], check=True)
-        os.replace(tmp, LIB)
-    L = ctypes.CDLL(LIB)
+    L = ctypes.CDLL(model_build.build(SRC, LIB, ru.FLAGS + ["-I", os.path.join(REPO, "include"), "-shared"]))
     for f in (L.encode_host_rgbe8, L.encode_host_f16):
         f.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]
         f.restype = None
-    _host = L
     return L
 
 

@@ -3,11 +3,12 @@ one pass, finish and a call in plain loops), built with the flags of oracle/Make
 G-buffer generator (surfaces facing a pinhole camera at the origin); a numpy restatement of the h-only pass; the "specials"
 accumulator; and the cornell renders of the oracle the quality gate uses."""
 import ctypes
+import functools
 import os
-import subprocess
 
 import numpy as np
 
+import model_build
 import radiance_util as ru
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -22,20 +23,10 @@ DESC_DTYPE = np.dtype([("passes", "<u4"), ("step", "<u4"), ("flags", "<u4"), ("n
 # the documented parameters of the cornell quality gate and of the GPU tests on cornell
 CORNELL = dict(passes=4, step=1, flags=DEMODULATE, normal_cos=0.9, plane_eps=0.02, sigma_lum=4.0)
 
-_model = None
 
-
+@functools.lru_cache(maxsize=None)
 def model_lib():
-    global _model
-    if _model is not None:
-        return _model
-    deps = [SRC] + [os.path.join(REPO, "include", h) for h in ("mi355rt.h", "mi355rt_layout.h", "mi355rt_math.h")]
-    if not os.path.exists(LIB) or max(os.path.getmtime(d) for d in deps) > os.path.getmtime(LIB):
-        os.makedirs(os.path.dirname(LIB), exist_ok=True)
-        tmp = "%s.%d.so" % (LIB[:-3], os.getpid())   # parallel test processes: each builds its own, the rename is atomic
-        subprocess.run(["g++"] + ru.FLAGS + ["-I", os.path.join(REPO, "include"), "-shared", "-o", tmp, SRC], check=True)
-        os.replace(tmp, LIB)
-    L = ctypes.CDLL(LIB)
+    L = ctypes.CDLL(model_build.build(SRC, LIB, ru.FLAGS + ["-I", os.path.join(REPO, "include"), "-shared"]))
     vp, u32, f32 = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_float
     L.fd_model_prepare.argtypes = [vp, vp, vp, vp, vp, u32, vp, vp, vp]
     L.fd_model_prepare.restype = None
@@ -45,7 +36,6 @@ def model_lib():
     L.fd_model_finish.restype = None
     L.fd_model_call.argtypes = [vp] * 7
     L.fd_model_call.restype = ctypes.c_int
-    _model = L
     return L
 
 

@@ -3,65 +3,42 @@ the radiance model's translation unit plus the gather stated once on its first-h
 flags of oracle/Makefile and driven through a ModelRenderer that loads the gather library instead; and the point set of the
 GPU tests."""
 import ctypes
+import functools
 import os
-import subprocess
 
 import numpy as np
 
-import oracle_lib
+import model_build
 import radiance_util as ru
 import ray_query_util as rq
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-REPO = os.path.dirname(HERE)
 SRC = os.path.join(HERE, "model", "gather_model.cpp")
 LIB = os.path.join(HERE, "model", "_build", "libgather_model.so")
 COUNT_NAMES = ru.COUNT_NAMES
 SEED = ru.SEED
 
-_model = None
 
-
-def model_lib():
-    """the gather library: every oracle_* and radiance_model_* entry declared as radiance_util declares it, plus the two
-    gather_model_* ones"""
-    global _model
-    if _model is not None:
-        return _model
-    deps = [SRC, ru.SRC, os.path.join(REPO, "oracle", "rt_oracle.cpp"), os.path.join(REPO, "include", "mi355rt_math.h"),
-            os.path.join(REPO, "include", "mi355rt_layout.h")]
-    if not os.path.exists(LIB) or any(os.path.getmtime(d) > os.path.getmtime(LIB) for d in deps):
-        os.makedirs(os.path.dirname(LIB), exist_ok=True)
-        tmp = "%s.%d.so" % (LIB[:-3], os.getpid())   # parallel test processes: each builds its own, the rename is atomic
-        subprocess.run(["g++"] + ru.FLAGS + ["-shared", "-o", tmp, SRC], check=True)
-        os.replace(tmp, LIB)
-    saved = (oracle_lib.ORACLE_LIB, oracle_lib._lib)
-    try:
-        oracle_lib.ORACLE_LIB, oracle_lib._lib = LIB, None
-        L = oracle_lib.lib()
-    finally:
-        oracle_lib.ORACLE_LIB, oracle_lib._lib = saved
+def bind_model(path):
+    """a library that holds the gather model's translation unit: every oracle_* and radiance_model_* entry declared as
+    radiance_util declares it, plus the two gather_model_* ones"""
+    L = ru.bind_model(path)
     vp, u32 = ctypes.c_void_p, ctypes.c_uint32
-    L.radiance_model_trace.argtypes = [vp, vp, u32, u32, u32, u32, ctypes.c_int, vp, vp]
-    L.radiance_model_trace.restype = None
-    L.radiance_model_camera_rays.argtypes = [vp, vp]
-    L.radiance_model_camera_rays.restype = None
     L.gather_model_directions.argtypes = [vp, u32, u32, u32, vp]
     L.gather_model_directions.restype = None
     L.gather_model_gather.argtypes = [vp, vp, u32, u32, u32, u32, vp, vp, vp]
     L.gather_model_gather.restype = None
-    _model = L
     return L
+
+
+@functools.lru_cache(maxsize=None)
+def model_lib():
+    return bind_model(model_build.build(SRC, LIB, ru.FLAGS + ["-shared"]))
 
 
 class GatherModel(ru.ModelRenderer):
     """ModelRenderer on the gather library: the oracle, traceRadiance / cameraRays, plus gatherDirections / gatherIrradiance"""
-
-    def __init__(self, threads=0):
-        self.L = model_lib()
-        self.ctx = self.L.oracle_create()
-        self.L.oracle_set_threads(self.ctx, threads)
-        self.width = self.height = 0
+    _library = staticmethod(model_lib)
 
     def gatherDirections(self, points, spp, seed):
         """points (n, 8) f32 in the rt_gather_point layout -> (n, spp, 3) f32: the direction of every sample"""
@@ -82,12 +59,7 @@ class GatherModel(ru.ModelRenderer):
         return out, hits, counts
 
 
-def model_for(W, bridge, width=16, height=16):
-    """a gather model with the scene uploaded as upload_scene does it (textures, light count of the bridge)"""
-    m = GatherModel()
-    m.buildPipeline(4, 1)
-    W.upload_scene(m, bridge, width, height)
-    return m
+model_for = functools.partial(ru.model_for, cls=GatherModel)
 
 
 def sample_rays(points, dirs, s):
@@ -142,23 +114,6 @@ def scene_points(model, bridge):
     return points_from_rays(model, ru.with_pads(rq.to_rt_rays(rq.scene_rays(bridge, False, 700, 324))))
 
 
-def result_words(res):
-    """structured IRRADIANCE_DTYPE (n,) -> (n, 4) u32"""
-    return np.ascontiguousarray(res).view(np.uint32).reshape(-1, 4)
-
-
-def check_against_model(res, ref, tag, nan_as_class=False):
-    """res: IRRADIANCE_DTYPE (n,); ref: the model's (n, 4) f32.  Bit for bit, point by point.  nan_as_class: in rows where
-    the MODEL has a NaN, NaNs compare as a class; every other row stays bit-exact."""
-    got, want = result_words(res), ru.u32(ref)
-    bad = got != want
-    if nan_as_class:
-        gf, wf = got.view(np.float32), want.view(np.float32)
-        model_nan_row = np.isnan(wf).any(axis=1)
-        bad &= ~(np.isnan(gf) & np.isnan(wf) & model_nan_row[:, None])
-    rows = np.nonzero(bad.any(axis=1))[0]
-    assert rows.size == 0, (tag, "points that differ", int(rows.size), rows[:8].tolist(),
-                            got[rows[:4]].view(np.float32).tolist(), want[rows[:4]].view(np.float32).tolist())
-
-
+result_words = ru.result_words                          # IRRADIANCE_DTYPE (n,) -> (n, 4) u32
+check_against_model = ru.check_records_against_model    # res: IRRADIANCE_DTYPE (n,); ref: the model's (n, 4) f32
 check_counts = ru.check_counts

@@ -8,7 +8,8 @@ tests/test_gpu_math.py (GPU)."""
 import ctypes
 import os
 import struct
-import subprocess
+
+import model_build
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(HERE)
@@ -52,52 +53,26 @@ def threads():
     return min(16, len(os.sched_getaffinity(0)))
 
 
-def _shared_deps():
-    deps = [os.path.join(MODEL, "math_inputs.h"), os.path.join(MODEL, "math_ops.h"), os.path.join(INCLUDE, "mi355rt_math.h")]
-    return deps + sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.startswith("k_ieee") and f.endswith(".h"))
-
-
-def _check_deps():   # the kernels' RNG comes with the scene types
-    return _shared_deps() + [os.path.join(CSRC, f) for f in ("k_common.hip.h", "device_scene.h", "lds_sizes.h")] + \
-        [os.path.join(INCLUDE, "mi355rt_layout.h")]
-
-
-def _stale(target, deps):
-    return not os.path.exists(target) or any(os.path.getmtime(d) > os.path.getmtime(target) for d in deps)
-
-
-def _run(cmd, target):
-    os.makedirs(BUILD, exist_ok=True)
-    tmp = "%s.tmp.%d" % (target, os.getpid())
-    try:
-        subprocess.run([tmp if a == target else a for a in cmd], check=True)
-        os.replace(tmp, target)
-    finally:
-        if os.path.exists(tmp):
-            os.remove(tmp)
-
-
-def build_ref(name="libmath_ref.so", compiler="g++", extra=(), program=False):
+def build_ref(name="libmath_ref.so", compiler=model_build.CXX, extra=(), program=False):
     """math_ref.cpp as a shared library, or with program=True as the stand-alone program with its own main()."""
-    target = os.path.join(BUILD, name)
-    if _stale(target, [REF_SRC] + _shared_deps()):
-        kind = ["-DMATH_REF_MAIN"] if program else ["-shared", "-fPIC"]
-        _run([compiler] + HOST_FLAGS + list(extra) + kind + ["-o", target, REF_SRC], target)
-    return target
+    kind = ["-DMATH_REF_MAIN"] if program else ["-shared", "-fPIC"]
+    return model_build.build(REF_SRC, os.path.join(BUILD, name), HOST_FLAGS + list(extra) + kind, compiler, program)
+
+
+def check_flags(flags):
+    return list(flags) + ["-I", INCLUDE, "-I", CSRC]
 
 
 def check_command(hipcc, flags, output):
-    return [hipcc] + list(flags) + ["-I", INCLUDE, "-I", CSRC, "-o", output, CHECK_SRC]
+    return [hipcc] + check_flags(flags) + ["-o", output, CHECK_SRC]
 
 
 def build_check(build):
     """math_check.hip with exactly the product's compiler and flags (`build` is webgpu_raytracer_amd._build)."""
-    target = os.path.join(BUILD, "libmath_check.so")
-    if _stale(target, [CHECK_SRC] + _check_deps()):
-        if not os.path.exists(build.HIPCC):
-            raise RuntimeError("hipcc not found at %s: the device side of the math check cannot be built" % build.HIPCC)
-        _run(check_command(build.HIPCC, build.HIP_FLAGS, target), target)
-    return target
+    try:
+        return model_build.build(CHECK_SRC, os.path.join(BUILD, "libmath_check.so"), check_flags(build.HIP_FLAGS), build.HIPCC)
+    except FileNotFoundError:
+        raise RuntimeError("hipcc not found at %s: the device side of the math check cannot be built" % build.HIPCC)
 
 
 def bind_ref(path):

@@ -25,59 +25,63 @@ def build_oracle(force=False):
     return ORACLE_LIB
 
 
+def bind(path):
+    """the library at `path` (the oracle's, or a model's that exports the same C API) with every oracle_* entry declared"""
+    L = ctypes.CDLL(path)
+    vp, u32, f32 = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_float
+    L.oracle_create.restype = vp
+    for name, args in {
+        "oracle_destroy": [vp], "oracle_set_threads": [vp, ctypes.c_int],
+        "oracle_build_pipeline": [vp, u32, u32], "oracle_update_screen_size": [vp, u32, u32],
+        "oracle_reset_accumulation": [vp], "oracle_upload_textures": [vp, vp, u32],
+        "oracle_update_topology": [vp, vp, ctypes.c_size_t], "oracle_update_instances": [vp, vp, ctypes.c_size_t],
+        "oracle_update_lights": [vp, vp, ctypes.c_size_t], "oracle_update_draw_commands": [vp, vp, ctypes.c_size_t],
+        "oracle_update_geometry": [vp, vp, vp, vp, u32], "oracle_update_bvh": [vp, vp, u32, vp, u32],
+        "oracle_update_scene_uniforms": [vp, vp, u32, u32], "oracle_set_stripes": [vp, u32, u32, u32],
+        "oracle_compute": [vp, u32], "oracle_present": [vp], "oracle_capture_frame": [vp, vp],
+        "oracle_read_accum": [vp, vp], "oracle_write_accum": [vp, vp], "oracle_read_gbuffer": [vp, vp, vp, vp],
+        "oracle_read_history": [vp, vp], "oracle_read_uniforms": [vp, vp], "oracle_get_counters": [vp, vp],
+        "oracle_reset_counters": [vp], "oracle_resize_texture": [vp, u32, u32, vp],
+        "oracle_set_node_histogram": [vp, vp], "oracle_trace_vs_brute_force": [vp, vp, u32, vp, vp, vp],
+        "oracle_trace_rays": [vp, vp, u32, ctypes.c_int, vp, vp],
+    }.items():
+        getattr(L, name).argtypes = args
+        getattr(L, name).restype = None
+    L.oracle_hardware_threads.restype = ctypes.c_int
+    L.oracle_init_rng.restype = u32
+    L.oracle_init_rng.argtypes = [u32, u32]
+    L.oracle_rand_pcg.restype = f32
+    L.oracle_rand_pcg.argtypes = [ctypes.POINTER(u32)]
+    L.oracle_init_rng_array.restype = None
+    L.oracle_init_rng_array.argtypes = [vp, vp, u32, vp]
+    L.oracle_rand_pcg_checksum.restype = ctypes.c_uint64
+    L.oracle_rand_pcg_checksum.argtypes = [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int]
+    L.oracle_halton.restype = ctypes.c_double
+    L.oracle_halton.argtypes = [u32, u32]
+    L.oracle_sincos.argtypes = [f32, ctypes.POINTER(f32), ctypes.POINTER(f32)]
+    for n in ("oracle_exp", "oracle_log"):
+        getattr(L, n).restype = f32
+        getattr(L, n).argtypes = [f32]
+    for n in ("oracle_pow", "oracle_min", "oracle_max"):
+        getattr(L, n).restype = f32
+        getattr(L, n).argtypes = [f32, f32]
+    L.oracle_f32_to_f16.restype = ctypes.c_uint16
+    L.oracle_f32_to_f16.argtypes = [f32]
+    L.oracle_f16_to_f32.restype = f32
+    L.oracle_f16_to_f32.argtypes = [ctypes.c_uint16]
+    L.oracle_pack_normal.argtypes = [vp, vp]
+    L.oracle_unpack_normal.argtypes = [vp, vp]
+    L.oracle_hit_triangle.restype = f32
+    L.oracle_hit_triangle.argtypes = [vp, vp, vp, vp, vp, f32, f32]
+    L.oracle_intersect_aabb.restype = f32
+    L.oracle_intersect_aabb.argtypes = [vp, vp, vp, vp, f32, f32]
+    return L
+
+
 def lib():
     global _lib
     if _lib is None:
-        build_oracle()
-        L = ctypes.CDLL(ORACLE_LIB)
-        vp, u32, f32 = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_float
-        L.oracle_create.restype = vp
-        for name, args in {
-            "oracle_destroy": [vp], "oracle_set_threads": [vp, ctypes.c_int],
-            "oracle_build_pipeline": [vp, u32, u32], "oracle_update_screen_size": [vp, u32, u32],
-            "oracle_reset_accumulation": [vp], "oracle_upload_textures": [vp, vp, u32],
-            "oracle_update_topology": [vp, vp, ctypes.c_size_t], "oracle_update_instances": [vp, vp, ctypes.c_size_t],
-            "oracle_update_lights": [vp, vp, ctypes.c_size_t], "oracle_update_draw_commands": [vp, vp, ctypes.c_size_t],
-            "oracle_update_geometry": [vp, vp, vp, vp, u32], "oracle_update_bvh": [vp, vp, u32, vp, u32],
-            "oracle_update_scene_uniforms": [vp, vp, u32, u32], "oracle_set_stripes": [vp, u32, u32, u32],
-            "oracle_compute": [vp, u32], "oracle_present": [vp], "oracle_capture_frame": [vp, vp],
-            "oracle_read_accum": [vp, vp], "oracle_write_accum": [vp, vp], "oracle_read_gbuffer": [vp, vp, vp, vp],
-            "oracle_read_history": [vp, vp], "oracle_read_uniforms": [vp, vp], "oracle_get_counters": [vp, vp],
-            "oracle_reset_counters": [vp], "oracle_resize_texture": [vp, u32, u32, vp],
-            "oracle_set_node_histogram": [vp, vp], "oracle_trace_vs_brute_force": [vp, vp, u32, vp, vp, vp],
-            "oracle_trace_rays": [vp, vp, u32, ctypes.c_int, vp, vp],
-        }.items():
-            getattr(L, name).argtypes = args
-            getattr(L, name).restype = None
-        L.oracle_hardware_threads.restype = ctypes.c_int
-        L.oracle_init_rng.restype = u32
-        L.oracle_init_rng.argtypes = [u32, u32]
-        L.oracle_rand_pcg.restype = f32
-        L.oracle_rand_pcg.argtypes = [ctypes.POINTER(u32)]
-        L.oracle_init_rng_array.restype = None
-        L.oracle_init_rng_array.argtypes = [vp, vp, u32, vp]
-        L.oracle_rand_pcg_checksum.restype = ctypes.c_uint64
-        L.oracle_rand_pcg_checksum.argtypes = [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int]
-        L.oracle_halton.restype = ctypes.c_double
-        L.oracle_halton.argtypes = [u32, u32]
-        L.oracle_sincos.argtypes = [f32, ctypes.POINTER(f32), ctypes.POINTER(f32)]
-        for n in ("oracle_exp", "oracle_log"):
-            getattr(L, n).restype = f32
-            getattr(L, n).argtypes = [f32]
-        for n in ("oracle_pow", "oracle_min", "oracle_max"):
-            getattr(L, n).restype = f32
-            getattr(L, n).argtypes = [f32, f32]
-        L.oracle_f32_to_f16.restype = ctypes.c_uint16
-        L.oracle_f32_to_f16.argtypes = [f32]
-        L.oracle_f16_to_f32.restype = f32
-        L.oracle_f16_to_f32.argtypes = [ctypes.c_uint16]
-        L.oracle_pack_normal.argtypes = [vp, vp]
-        L.oracle_unpack_normal.argtypes = [vp, vp]
-        L.oracle_hit_triangle.restype = f32
-        L.oracle_hit_triangle.argtypes = [vp, vp, vp, vp, vp, f32, f32]
-        L.oracle_intersect_aabb.restype = f32
-        L.oracle_intersect_aabb.argtypes = [vp, vp, vp, vp, f32, f32]
-        _lib = L
+        _lib = bind(build_oracle())
     return _lib
 
 
@@ -91,8 +95,10 @@ COUNTER_NAMES = ("primary_rays", "extension_rays", "shadow_rays", "nodes_visited
 class OracleRenderer:
     """CPU oracle with the WebGPURenderer method names (WebGPURenderer.ts:7-138)."""
 
+    _library = staticmethod(lib)   # a subclass on a model library names its own
+
     def __init__(self, threads=0):
-        self.L = lib()
+        self.L = self._library()
         self.ctx = self.L.oracle_create()
         self.L.oracle_set_threads(self.ctx, threads)
         self.width = self.height = 0

@@ -4,16 +4,15 @@ oracle/Makefile and driven through a ModelRenderer that loads the probe library 
 projection (basis, fixed summation tree) that the composition tests put behind radiance queries; and the probe set of the GPU
 tests."""
 import ctypes
+import functools
 import os
-import subprocess
 
 import numpy as np
 
-import oracle_lib
+import model_build
 import radiance_util as ru
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-REPO = os.path.dirname(HERE)
 SRC = os.path.join(HERE, "model", "probe_model.cpp")
 LIB = os.path.join(HERE, "model", "_build", "libprobe_model.so")
 COUNT_NAMES = ru.COUNT_NAMES
@@ -22,49 +21,23 @@ RNG_STEP = 719393                 # init_rng(a, b) hashes a + b * RNG_STEP
 FOUR_PI = np.float32(12.566370614)
 Y0 = np.float32(0.282094792)
 
-_model = None
 
-
+@functools.lru_cache(maxsize=None)
 def model_lib():
     """the probe library: every oracle_* and radiance_model_* entry declared as radiance_util declares it, plus the two
     probe_model_* ones"""
-    global _model
-    if _model is not None:
-        return _model
-    deps = [SRC, ru.SRC, os.path.join(REPO, "oracle", "rt_oracle.cpp"), os.path.join(REPO, "include", "mi355rt_math.h"),
-            os.path.join(REPO, "include", "mi355rt_layout.h")]
-    if not os.path.exists(LIB) or any(os.path.getmtime(d) > os.path.getmtime(LIB) for d in deps):
-        os.makedirs(os.path.dirname(LIB), exist_ok=True)
-        tmp = "%s.%d.so" % (LIB[:-3], os.getpid())   # parallel test processes: each builds its own, the rename is atomic
-        subprocess.run(["g++"] + ru.FLAGS + ["-shared", "-o", tmp, SRC], check=True)
-        os.replace(tmp, LIB)
-    saved = (oracle_lib.ORACLE_LIB, oracle_lib._lib)
-    try:
-        oracle_lib.ORACLE_LIB, oracle_lib._lib = LIB, None
-        L = oracle_lib.lib()
-    finally:
-        oracle_lib.ORACLE_LIB, oracle_lib._lib = saved
+    L = ru.bind_model(model_build.build(SRC, LIB, ru.FLAGS + ["-shared"]))
     vp, u32 = ctypes.c_void_p, ctypes.c_uint32
-    L.radiance_model_trace.argtypes = [vp, vp, u32, u32, u32, u32, ctypes.c_int, vp, vp]
-    L.radiance_model_trace.restype = None
-    L.radiance_model_camera_rays.argtypes = [vp, vp]
-    L.radiance_model_camera_rays.restype = None
     L.probe_model_directions.argtypes = [vp, u32, u32, u32, vp]
     L.probe_model_directions.restype = None
     L.probe_model_gather.argtypes = [vp, vp, u32, u32, u32, u32, vp, vp, vp]
     L.probe_model_gather.restype = None
-    _model = L
     return L
 
 
 class ProbeModel(ru.ModelRenderer):
     """ModelRenderer on the probe library: the oracle, traceRadiance / cameraRays, plus probeDirections / gatherProbes"""
-
-    def __init__(self, threads=0):
-        self.L = model_lib()
-        self.ctx = self.L.oracle_create()
-        self.L.oracle_set_threads(self.ctx, threads)
-        self.width = self.height = 0
+    _library = staticmethod(model_lib)
 
     def probeDirections(self, probes, spp, seed):
         """probes (n, 8) f32 in the rt_probe layout -> (n, spp, 3) f32: the direction of every sample"""
@@ -85,12 +58,7 @@ class ProbeModel(ru.ModelRenderer):
         return out, hits, counts
 
 
-def model_for(W, bridge, width=16, height=16):
-    """a probe model with the scene uploaded as upload_scene does it (textures, light count of the bridge)"""
-    m = ProbeModel()
-    m.buildPipeline(4, 1)
-    W.upload_scene(m, bridge, width, height)
-    return m
+model_for = functools.partial(ru.model_for, cls=ProbeModel)
 
 
 def make_probes(positions, t_max=1e30, pad_step=ru.PAD_STEP, pad_first=ru.PAD_0):
@@ -222,23 +190,7 @@ def scene_probes(model, bridge):
     return make_probes(np.concatenate([grid_positions(bridge, 4), surf, outside]))
 
 
-def result_words(res):
-    """structured PROBE_SH9_DTYPE (n,) -> (n, 28) u32"""
-    return np.ascontiguousarray(res).view(np.uint32).reshape(-1, 28)
-
-
-def check_against_model(res, ref, tag, nan_as_class=False):
-    """res: PROBE_SH9_DTYPE (n,); ref: (n, 28) f32.  Bit for bit, probe by probe.  nan_as_class: in rows where the REFERENCE
-    has a NaN, NaNs compare as a class; every other row stays bit-exact."""
-    got, want = result_words(res), ru.u32(ref)
-    bad = got != want
-    if nan_as_class:
-        gf, wf = got.view(np.float32), want.view(np.float32)
-        model_nan_row = np.isnan(wf).any(axis=1)
-        bad &= ~(np.isnan(gf) & np.isnan(wf) & model_nan_row[:, None])
-    rows = np.nonzero(bad.any(axis=1))[0]
-    assert rows.size == 0, (tag, "probes that differ", int(rows.size), rows[:8].tolist(),
-                            got[rows[:2]].view(np.float32).tolist(), want[rows[:2]].view(np.float32).tolist())
-
-
+result_words = functools.partial(ru.result_words, width=28)   # PROBE_SH9_DTYPE (n,) -> (n, 28) u32
+# res: PROBE_SH9_DTYPE (n,); ref: (n, 28) f32; the rule of the gathers
+check_against_model = functools.partial(ru.check_records_against_model, width=28, what="probes", shown=2)
 check_counts = ru.check_counts

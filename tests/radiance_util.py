@@ -3,15 +3,15 @@ oracle's translation unit plus the bounce loop restated once, with one surface-f
 oracle's G-buffer depth 0 and the traced depth 0 of a query), built with the flags of oracle/Makefile and driven through an
 OracleRenderer that loads the model library instead of librt_oracle.so."""
 import ctypes
+import functools
 import os
-import subprocess
 
 import numpy as np
 
+import model_build
 import oracle_lib
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-REPO = os.path.dirname(HERE)
 SRC = os.path.join(HERE, "model", "radiance_model.cpp")
 LIB = os.path.join(HERE, "model", "_build", "libradiance_model.so")
 # CXXFLAGS of oracle/Makefile
@@ -19,46 +19,27 @@ FLAGS = ["-std=c++17", "-O2", "-ffp-contract=off", "-fno-fast-math", "-fPIC", "-
 COUNT_NAMES = ("extension_rays", "shadow_rays", "shaded_hits", "nodes_visited", "tris_tested")
 PAD_STEP, PAD_0, SEED = 7, 3, 5
 
-_model = None
 
-
-def model_lib():
-    """the model library with every oracle_* entry declared as oracle_lib declares it, plus the two radiance_model_* ones"""
-    global _model
-    if _model is not None:
-        return _model
-    deps = [SRC, os.path.join(REPO, "oracle", "rt_oracle.cpp"), os.path.join(REPO, "include", "mi355rt_math.h"),
-            os.path.join(REPO, "include", "mi355rt_layout.h")]
-    if not os.path.exists(LIB) or any(os.path.getmtime(d) > os.path.getmtime(LIB) for d in deps):
-        os.makedirs(os.path.dirname(LIB), exist_ok=True)
-        tmp = "%s.%d.so" % (LIB[:-3], os.getpid())   # parallel test processes: each builds its own, the rename is atomic
-        subprocess.run(["g++"] + FLAGS + ["-shared", "-o", tmp, SRC], check=True)
-        os.replace(tmp, LIB)
-    # oracle_lib.lib() declares the argument types of the oracle's C API on whatever ORACLE_LIB names: let it do that on
-    # the model library (which exports the same API), then put the oracle's own binding back
-    saved = (oracle_lib.ORACLE_LIB, oracle_lib._lib)
-    try:
-        oracle_lib.ORACLE_LIB, oracle_lib._lib = LIB, None
-        L = oracle_lib.lib()
-    finally:
-        oracle_lib.ORACLE_LIB, oracle_lib._lib = saved
+def bind_model(path):
+    """a library that holds the radiance model's translation unit: every oracle_* entry declared as oracle_lib declares it,
+    plus the two radiance_model_* ones"""
+    L = oracle_lib.bind(path)
     vp, u32 = ctypes.c_void_p, ctypes.c_uint32
     L.radiance_model_trace.argtypes = [vp, vp, u32, u32, u32, u32, ctypes.c_int, vp, vp]
     L.radiance_model_trace.restype = None
     L.radiance_model_camera_rays.argtypes = [vp, vp]
     L.radiance_model_camera_rays.restype = None
-    _model = L
     return L
+
+
+@functools.lru_cache(maxsize=None)
+def model_lib():
+    return bind_model(model_build.build(SRC, LIB, FLAGS + ["-shared"]))
 
 
 class ModelRenderer(oracle_lib.OracleRenderer):
     """OracleRenderer on the model library: the whole oracle, plus traceRadiance / cameraRays"""
-
-    def __init__(self, threads=0):
-        self.L = model_lib()
-        self.ctx = self.L.oracle_create()
-        self.L.oracle_set_threads(self.ctx, threads)
-        self.width = self.height = 0
+    _library = staticmethod(model_lib)
 
     def traceRadiance(self, rays, max_depth, spp, seed, gbuffer_depth0=False):
         """rays (n, 8) f32 in the rt_ray layout -> (out (n, 4) f32 {r, g, b, t}, counts (n, 5) u64 COUNT_NAMES)"""
@@ -77,9 +58,9 @@ class ModelRenderer(oracle_lib.OracleRenderer):
         return out
 
 
-def model_for(W, bridge, width=16, height=16):
-    """a model with the scene uploaded as upload_scene does it (textures, light count of the bridge)"""
-    m = ModelRenderer()
+def model_for(W, bridge, width=16, height=16, cls=ModelRenderer):
+    """a model of class `cls` with the scene uploaded as upload_scene does it (textures, light count of the bridge)"""
+    m = cls()
     m.buildPipeline(4, 1)
     W.upload_scene(m, bridge, width, height)
     return m
@@ -96,9 +77,9 @@ def u32(a):
     return np.ascontiguousarray(a).view(np.uint32)
 
 
-def result_words(res):
-    """structured RADIANCE_DTYPE (n,) -> (n, 4) u32"""
-    return np.ascontiguousarray(res).view(np.uint32).reshape(-1, 4)
+def result_words(res, width=4):
+    """structured result records (n,) of `width` words each (RADIANCE_DTYPE, IRRADIANCE_DTYPE: 4) -> (n, width) u32"""
+    return np.ascontiguousarray(res).view(np.uint32).reshape(-1, width)
 
 
 def check_against_model(res, ref, tag, nan_as_class=False):
@@ -113,6 +94,20 @@ def check_against_model(res, ref, tag, nan_as_class=False):
     rows = np.nonzero(bad.any(axis=1))[0]
     assert rows.size == 0, (tag, "rays that differ", int(rows.size), rows[:8].tolist(),
                             got[rows[:4]].view(np.float32).tolist(), want[rows[:4]].view(np.float32).tolist())
+
+
+def check_records_against_model(res, ref, tag, nan_as_class=False, width=4, what="points", shown=4):
+    """The rule of the gathers: res: structured records (n,); ref: the model's (n, width) f32.  Bit for bit, record by record.
+    nan_as_class: in rows where the MODEL has a NaN, NaNs compare as a class; every other row stays bit-exact."""
+    got, want = result_words(res, width), u32(ref)
+    bad = got != want
+    if nan_as_class:
+        gf, wf = got.view(np.float32), want.view(np.float32)
+        model_nan_row = np.isnan(wf).any(axis=1)
+        bad &= ~(np.isnan(gf) & np.isnan(wf) & model_nan_row[:, None])
+    rows = np.nonzero(bad.any(axis=1))[0]
+    assert rows.size == 0, (tag, what + " that differ", int(rows.size), rows[:8].tolist(),
+                            got[rows[:shown]].view(np.float32).tolist(), want[rows[:shown]].view(np.float32).tolist())
 
 
 def check_counts(stats, counts, n, spp, tag):

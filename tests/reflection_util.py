@@ -5,25 +5,21 @@ driven through a ModelRenderer that loads the reflection library instead; the nu
 (octahedral mapping, frame, lookup, fixed summation tree) on the model's exported lobe; a float64 evaluation of the lobe; and
 the descriptors, probes and rays of the tests."""
 import ctypes
+import functools
 import os
-import subprocess
 
 import numpy as np
 
-import oracle_lib
+import model_build
 import probe_util as prb
 import radiance_util as ru
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-REPO = os.path.dirname(HERE)
 SRC = os.path.join(HERE, "model", "reflection_model.cpp")
 LIB = os.path.join(HERE, "model", "_build", "libreflection_model.so")
 SEED = ru.SEED
 DESC_DTYPE = np.dtype([("size", np.uint32), ("levels", np.uint32), ("spt", np.uint32), ("filter_samples", np.uint32),
                        ("reserved", np.uint32, (4,))])
-
-_model = None
-
 
 def desc(size, levels, spt=1, filter_samples=64):
     d = np.zeros((), DESC_DTYPE)
@@ -36,30 +32,12 @@ def level_offsets(size, levels):
     return np.concatenate([[0], np.cumsum(sides * sides)])
 
 
+@functools.lru_cache(maxsize=None)
 def model_lib():
     """the reflection library: every oracle_* and radiance_model_* entry declared as radiance_util declares it, plus the
     reflection_model_* ones"""
-    global _model
-    if _model is not None:
-        return _model
-    deps = [SRC, ru.SRC, os.path.join(REPO, "oracle", "rt_oracle.cpp"), os.path.join(REPO, "include", "mi355rt_math.h"),
-            os.path.join(REPO, "include", "mi355rt_layout.h")]
-    if not os.path.exists(LIB) or any(os.path.getmtime(d) > os.path.getmtime(LIB) for d in deps):
-        os.makedirs(os.path.dirname(LIB), exist_ok=True)
-        tmp = "%s.%d.so" % (LIB[:-3], os.getpid())   # parallel test processes: each builds its own, the rename is atomic
-        subprocess.run(["g++"] + ru.FLAGS + ["-shared", "-o", tmp, SRC], check=True)
-        os.replace(tmp, LIB)
-    saved = (oracle_lib.ORACLE_LIB, oracle_lib._lib)
-    try:
-        oracle_lib.ORACLE_LIB, oracle_lib._lib = LIB, None
-        L = oracle_lib.lib()
-    finally:
-        oracle_lib.ORACLE_LIB, oracle_lib._lib = saved
+    L = ru.bind_model(model_build.build(SRC, LIB, ru.FLAGS + ["-shared"]))
     vp, u32 = ctypes.c_void_p, ctypes.c_uint32
-    L.radiance_model_trace.argtypes = [vp, vp, u32, u32, u32, u32, ctypes.c_int, vp, vp]
-    L.radiance_model_trace.restype = None
-    L.radiance_model_camera_rays.argtypes = [vp, vp]
-    L.radiance_model_camera_rays.restype = None
     L.reflection_model_directions.argtypes = [vp, u32, u32, u32, u32, vp]
     L.reflection_model_directions.restype = None
     L.reflection_model_capture.argtypes = [vp, vp, vp, u32, u32, u32, vp, vp]
@@ -70,7 +48,6 @@ def model_lib():
     L.reflection_model_lobe.restype = None
     L.reflection_model_centres.argtypes = [u32, vp]
     L.reflection_model_centres.restype = None
-    _model = L
     return L
 
 
@@ -100,12 +77,7 @@ def model_centres(size):
 
 class ReflectionModel(ru.ModelRenderer):
     """ModelRenderer on the reflection library: the oracle, traceRadiance, plus the capture"""
-
-    def __init__(self, threads=0):
-        self.L = model_lib()
-        self.ctx = self.L.oracle_create()
-        self.L.oracle_set_threads(self.ctx, threads)
-        self.width = self.height = 0
+    _library = staticmethod(model_lib)
 
     def reflectionDirections(self, probes, size, spt, seed):
         """-> (n, size * size, spt, 3) f32: the direction of every sample of every texel"""
@@ -125,11 +97,7 @@ class ReflectionModel(ru.ModelRenderer):
         return out, counts
 
 
-def model_for(W, bridge, width=16, height=16):
-    m = ReflectionModel()
-    m.buildPipeline(4, 1)
-    W.upload_scene(m, bridge, width, height)
-    return m
+model_for = functools.partial(ru.model_for, cls=ReflectionModel)
 
 
 def texel_rays(probes, dirs, s):

@@ -19,6 +19,7 @@ import numpy as np
 import pytest
 
 import bake_util as bu
+import model_build
 import random_scene
 
 MARGIN = 1e-4
@@ -170,9 +171,8 @@ def test_hand_worked_cases(scenes, name):
 def test_stand_alone_cases_under_the_sanitizers(tmp_path):
     """the model's own main (hand-worked cases on the restated rule) built with ASan and UBSan, on the CPU"""
     exe = str(tmp_path / "bake_model_check")
-    flags = [f for f in bu.ru.FLAGS if f not in ("-fPIC", "-O2")]
-    subprocess.run(["g++"] + flags + ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                                      "-DBAKE_MODEL_MAIN", "-o", exe, bu.SRC], check=True, capture_output=True)
+    flags = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-DBAKE_MODEL_MAIN"]
+    model_build.build(bu.SRC, exe, [f for f in bu.ru.FLAGS if f not in ("-fPIC", "-O2")] + flags, program=True)
     r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "hand-worked cases ok" in r.stdout

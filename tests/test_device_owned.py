@@ -8,6 +8,8 @@ undefined-behaviour sanitizers linked in, and run once (no GPU)."""
 import os
 import subprocess
 
+import model_build
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(HERE)
 CSRC = os.path.join(REPO, "webgpu-raytracer_amd", "csrc")
@@ -16,12 +18,9 @@ EXE = os.path.join(HERE, "model", "_build", "owned_check")
 
 
 def test_every_owner_under_the_sanitizers():
-    os.makedirs(os.path.dirname(EXE), exist_ok=True)
-    tmp = "%s.%d" % (EXE, os.getpid())   # parallel test processes: each builds its own, the rename is atomic
-    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
-                    "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan", "-o", tmp, SRC], check=True)
-    os.replace(tmp, EXE)
-    run = subprocess.run([EXE], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=120)
+    flags = ["-O1", "-g", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+             "-static-libasan", "-static-libubsan"]
+    run = subprocess.run([model_build.build(SRC, EXE, flags, program=True)], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=120)
     assert run.returncode == 0, run.stdout
     assert run.stdout.strip().splitlines()[-1] == "owned_check: every check held, 0 live", run.stdout
 

@@ -25,10 +25,10 @@ def test_model_self_check_builds_and_runs_stand_alone(tmp_path):
     """the model has a main of its own: the same file as a program"""
     import os
     import subprocess
+    import model_build
     import radiance_util as ru
     exe = str(tmp_path / "frame_denoise_model")
-    subprocess.run(["g++"] + [f for f in ru.FLAGS if f != "-fPIC"] + ["-I", os.path.join(fu.REPO, "include"), "-o", exe, fu.SRC],
-                   check=True)
+    model_build.build(fu.SRC, exe, [f for f in ru.FLAGS if f != "-fPIC"] + ["-I", os.path.join(fu.REPO, "include")], program=True)
     r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
     assert r.returncode == 0, r.stdout + r.stderr
 

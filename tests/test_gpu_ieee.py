@@ -15,14 +15,14 @@ The oracle is not involved: this pins arithmetic, not rendering.
 """
 import ctypes
 import os
-import subprocess
 
 import pytest
+
+import model_build
 
 pytestmark = pytest.mark.gpu
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-REPO = os.path.dirname(HERE)
 SRC = os.path.join(HERE, "model", "ieee_ref.cpp")
 LIB = os.path.join(HERE, "model", "_build", "libieee_ref.so")
 OPS = {"rcp": 0, "sqrt": 1, "rsqrt": 2, "div": 3, "div3": 4, "div3z": 5, "div_pi": 6, "unorm8": 7}
@@ -35,12 +35,7 @@ class Report(ctypes.Structure):
 
 
 def ref_lib():
-    deps = [SRC, os.path.join(REPO, "webgpu-raytracer_amd", "csrc", "k_ieee_inputs.h")]
-    if not os.path.exists(LIB) or any(os.path.getmtime(d) > os.path.getmtime(LIB) for d in deps):
-        os.makedirs(os.path.dirname(LIB), exist_ok=True)
-        subprocess.run(["g++", "-O2", "-ffp-contract=off", "-fno-fast-math", "-std=c++17", "-shared", "-fPIC", "-pthread", "-o", LIB, SRC],
-                       check=True)
-    L = ctypes.CDLL(LIB)
+    L = ctypes.CDLL(model_build.build(SRC, LIB, ["-O2", "-ffp-contract=off", "-fno-fast-math", "-std=c++17", "-shared", "-fPIC", "-pthread"]))
     L.ieee_ref_checksum.argtypes = [ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int]
     L.ieee_ref_checksum.restype = ctypes.c_uint64
     return L

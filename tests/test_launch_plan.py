@@ -12,9 +12,10 @@ plus exactly the arrays the plan stages, the workgroups a shape plans per CU fit
 import ctypes
 import json
 import os
-import subprocess
 
 import pytest
+
+import model_build
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(HERE)
@@ -33,13 +34,7 @@ ROWS = TABLE["rows"]
 
 @pytest.fixture(scope="module")
 def planner():
-    deps = [SRC, os.path.join(CSRC, "launch_plan.h"), os.path.join(CSRC, "lds_sizes.h")]
-    if not os.path.exists(LIB) or any(os.path.getmtime(d) > os.path.getmtime(LIB) for d in deps):
-        os.makedirs(os.path.dirname(LIB), exist_ok=True)
-        tmp = "%s.%d.so" % (LIB[:-3], os.getpid())   # parallel test processes: each builds its own, the rename is atomic
-        subprocess.run(["g++", "-O1", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-shared", "-fPIC", "-o", tmp, SRC], check=True)
-        os.replace(tmp, LIB)
-    L = ctypes.CDLL(LIB)
+    L = ctypes.CDLL(model_build.build(SRC, LIB, ["-O1", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-shared", "-fPIC"]))
     L.lpc_fields.restype = ctypes.c_char_p
     L.lpc_eval.argtypes = [ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]
     L.lpc_eval.restype = ctypes.c_int

@@ -8,16 +8,14 @@ The argument fails for a ray with a zero or denormal direction component (1 / 0 
 the NaN): such rays must raise the guard's predicate, and one hand-made ray shows the two walks apart without it."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import model_build
 import random_scene
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-REPO = os.path.dirname(HERE)
-CSRC = os.path.join(REPO, "webgpu-raytracer_amd", "csrc")
 SRC = os.path.join(HERE, "model", "leaf_sweep_model.cpp")
 LIB = os.path.join(HERE, "model", "_build", "libleaf_sweep_model.so")
 N_RAYS = 100_000
@@ -27,15 +25,8 @@ T_MIN, T_MAX = f32(1e-3), f32(1e30)
 
 @pytest.fixture(scope="module")
 def model():
-    deps = [SRC] + [os.path.join(CSRC, n) for n in ("scene_facts.h", "launch_plan.h", "lds_sizes.h")] + \
-           [os.path.join(REPO, "include", n) for n in ("mi355rt_math.h", "mi355rt_layout.h")]
-    if not os.path.exists(LIB) or any(os.path.getmtime(d) > os.path.getmtime(LIB) for d in deps):
-        os.makedirs(os.path.dirname(LIB), exist_ok=True)
-        tmp = "%s.%d.so" % (LIB[:-3], os.getpid())
-        subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-Wall", "-Wextra", "-Werror", "-shared", "-fPIC",
-                        "-o", tmp, SRC], check=True)
-        os.replace(tmp, LIB)
-    L = ctypes.CDLL(LIB)
+    flags = ["-O2", "-std=c++17", "-ffp-contract=off", "-Wall", "-Wextra", "-Werror", "-shared", "-fPIC"]
+    L = ctypes.CDLL(model_build.build(SRC, LIB, flags))
     vp = ctypes.c_void_p
     L.lsm_reference.argtypes = [vp, ctypes.c_uint32, vp, vp, ctypes.c_uint64, vp]
     L.lsm_reference.restype = None

@@ -4,28 +4,21 @@ BOTH counters of every ray, on every scene, for closest-hit and shadow rays, wit
 overflowing into the stackless fall-back) to 64 (never).  No GPU: this pins the traversal LOGIC the GPU runs."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import model_build
 import pair_layout
 import parity_util as pu
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-REPO = os.path.dirname(HERE)
 SRC = os.path.join(HERE, "model", "pairwalk_model.cpp")
 LIB = os.path.join(HERE, "model", "_build", "libpairwalk_model.so")
 
 
 def model_lib():
-    deps = [SRC, os.path.join(REPO, "webgpu-raytracer_amd", "csrc", "k_pairwalk.hip.h"), os.path.join(REPO, "include", "mi355rt_math.h")]
-    if not os.path.exists(LIB) or any(os.path.getmtime(d) > os.path.getmtime(LIB) for d in deps):
-        os.makedirs(os.path.dirname(LIB), exist_ok=True)
-        tmp = "%s.%d.so" % (LIB[:-3], os.getpid())   # parallel test processes: each builds its own, the rename is atomic
-        subprocess.run(["g++", "-O2", "-ffp-contract=off", "-std=c++17", "-shared", "-fPIC", "-o", tmp, SRC], check=True)
-        os.replace(tmp, LIB)
-    L = ctypes.CDLL(LIB)
+    L = ctypes.CDLL(model_build.build(SRC, LIB, ["-O2", "-ffp-contract=off", "-std=c++17", "-shared", "-fPIC"]))
     vp = ctypes.c_void_p
     L.pwm_trace.argtypes = [vp, vp, vp, vp, vp, vp, ctypes.c_uint32, ctypes.c_int, ctypes.c_uint32, ctypes.c_int, vp, vp, vp]
     L.pwm_trace.restype = None

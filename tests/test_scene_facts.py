@@ -6,10 +6,11 @@ material word saturates to 0, a NaN texture index fails `> -0.5`, the emission i
 tests/model/scene_facts_check.cpp wraps the header; host compiler only, no GPU."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 import pytest
+
+import model_build
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(HERE)
@@ -23,15 +24,8 @@ f32 = np.float32
 
 @pytest.fixture(scope="module")
 def facts():
-    deps = [SRC] + [os.path.join(CSRC, n) for n in ("scene_facts.h", "launch_plan.h", "lds_sizes.h")] + \
-           [os.path.join(REPO, "include", n) for n in ("mi355rt_math.h", "mi355rt_layout.h")]
-    if not os.path.exists(LIB) or any(os.path.getmtime(d) > os.path.getmtime(LIB) for d in deps):
-        os.makedirs(os.path.dirname(LIB), exist_ok=True)
-        tmp = "%s.%d.so" % (LIB[:-3], os.getpid())   # parallel test processes: each builds its own, the rename is atomic
-        subprocess.run(["g++", "-O1", "-std=c++17", "-ffp-contract=off", "-Wall", "-Wextra", "-Werror", "-shared", "-fPIC",
-                        "-o", tmp, SRC], check=True)
-        os.replace(tmp, LIB)
-    L = ctypes.CDLL(LIB)
+    flags = ["-O1", "-std=c++17", "-ffp-contract=off", "-Wall", "-Wextra", "-Werror", "-shared", "-fPIC"]
+    L = ctypes.CDLL(model_build.build(SRC, LIB, flags))
     L.sfc_max_tris.restype = ctypes.c_uint64
     L.sfc_eval.argtypes = [ctypes.c_void_p, ctypes.c_uint64]
     L.sfc_eval.restype = ctypes.c_int

@@ -6,11 +6,11 @@ eleven leaves in walk order, bit for bit, and each clause of the condition is br
 tests/model/walk_facts_check.cpp wraps the header; host compiler only, no GPU."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import model_build
 import odd_bvh
 import parity_util as pu
 
@@ -29,15 +29,8 @@ f32, u32 = np.float32, np.uint32
 
 @pytest.fixture(scope="module")
 def facts():
-    deps = [SRC] + [os.path.join(CSRC, n) for n in ("scene_facts.h", "launch_plan.h", "lds_sizes.h")] + \
-           [os.path.join(REPO, "include", n) for n in ("mi355rt_math.h", "mi355rt_layout.h")]
-    if not os.path.exists(LIB) or any(os.path.getmtime(d) > os.path.getmtime(LIB) for d in deps):
-        os.makedirs(os.path.dirname(LIB), exist_ok=True)
-        tmp = "%s.%d.so" % (LIB[:-3], os.getpid())   # parallel test processes: each builds its own, the rename is atomic
-        subprocess.run(["g++", "-O1", "-std=c++17", "-ffp-contract=off", "-Wall", "-Wextra", "-Werror", "-shared", "-fPIC",
-                        "-o", tmp, SRC], check=True)
-        os.replace(tmp, LIB)
-    L = ctypes.CDLL(LIB)
+    flags = ["-O1", "-std=c++17", "-ffp-contract=off", "-Wall", "-Wextra", "-Werror", "-shared", "-fPIC"]
+    L = ctypes.CDLL(model_build.build(SRC, LIB, flags))
     L.wfc_max_nodes.restype = ctypes.c_uint64
     for name in ("wfc_max_records", "wfc_default_cap"):
         getattr(L, name).restype = ctypes.c_uint32

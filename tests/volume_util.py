@@ -3,11 +3,12 @@ model (tests/model/volume_model.cpp, built with the flags the other models use),
 probes and of the finish that the composition tests put around probe gathers, the float64 restatement of the sampler, and the
 volumes and points of the parity tests."""
 import ctypes
+import functools
 import os
-import subprocess
 
 import numpy as np
 
+import model_build
 import radiance_util as ru
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -20,25 +21,15 @@ BAND_OF = np.array([0, 1, 1, 1, 2, 2, 2, 2, 2])
 # development host (its docstring has the figure), times four: the margin is for other libm / compiler versions
 FLOAT_TOLERANCE = 4 * 1.16e-6
 
-_model = None
-
 
 def _renderer_module():
     from webgpu_raytracer_amd import renderer
     return renderer
 
 
+@functools.lru_cache(maxsize=None)
 def model_lib():
-    global _model
-    if _model is not None:
-        return _model
-    deps = [SRC, os.path.join(REPO, "include", "mi355rt_math.h"), os.path.join(REPO, "include", "mi355rt_layout.h")]
-    if not os.path.exists(LIB) or any(os.path.getmtime(d) > os.path.getmtime(LIB) for d in deps):
-        os.makedirs(os.path.dirname(LIB), exist_ok=True)
-        tmp = "%s.%d.so" % (LIB[:-3], os.getpid())   # parallel test processes: each builds its own, the rename is atomic
-        subprocess.run(["g++"] + ru.FLAGS + ["-I", os.path.join(REPO, "include"), "-shared", "-o", tmp, SRC], check=True)
-        os.replace(tmp, LIB)
-    L = ctypes.CDLL(LIB)
+    L = ctypes.CDLL(model_build.build(SRC, LIB, ru.FLAGS + ["-I", os.path.join(REPO, "include"), "-shared"]))
     vp = ctypes.c_void_p
     L.volume_model_probes.argtypes = [vp, vp]
     L.volume_model_finish.argtypes = [vp, vp]
@@ -46,7 +37,6 @@ def model_lib():
     L.volume_model_layers.argtypes = [vp, vp, ctypes.c_int, vp]
     for f in (L.volume_model_probes, L.volume_model_finish, L.volume_model_sample, L.volume_model_layers):
         f.restype = None
-    _model = L
     return L
 
 

@@ -23,12 +23,9 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import webgpu_raytracer_amd as W  # noqa: E402
+from timing_util import fmt2 as fmt  # noqa: E402,F401  (dilate_time, denoise_time and lightmap_time take it from here)
 
 SCENE, CELL, SIDE, DEPTH, SPP, ROUNDS, SEED = "instanced1000", 32, 32, 4, 16, 5, 5
-
-
-def fmt(vals, unit="ms"):
-    return "%.2f %s (min %.2f .. max %.2f over %d rounds)" % (statistics.median(vals), unit, min(vals), max(vals), len(vals))
 
 
 def merged_grid_uv(bridge, insts):

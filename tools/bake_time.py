@@ -26,12 +26,9 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import webgpu_raytracer_amd as W  # noqa: E402
+from timing_util import fmt  # noqa: E402
 
 SIZE, DEPTH, SPP, ROUNDS, SEED = 1024, 4, 16, 5, 5
-
-
-def fmt(vals, unit="ms"):
-    return "%.3f %s (min %.3f .. max %.3f over %d rounds)" % (statistics.median(vals), unit, min(vals), max(vals), len(vals))
 
 
 def unindexed(bridge):

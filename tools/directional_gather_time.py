@@ -16,7 +16,6 @@ usage: python tools/directional_gather_time.py [--out profiles/directional_gathe
 import argparse
 import math
 import os
-import statistics
 import sys
 import time
 
@@ -25,12 +24,9 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import webgpu_raytracer_amd as W  # noqa: E402
 from atlas_bake_time import merged_grid_uv  # noqa: E402
+from timing_util import fmt  # noqa: E402
 
 ATLAS, MAX_ENTRIES, DEPTH, SPPS, ROUNDS, SEED = 1024, 64, 4, (16, 64), 5, 5
-
-
-def fmt(vals, unit):
-    return "%.3f %s (min %.3f .. max %.3f over %d rounds)" % (statistics.median(vals), unit, min(vals), max(vals), len(vals))
 
 
 def atlas_points(r, b):

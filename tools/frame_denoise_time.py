@@ -16,7 +16,9 @@ Every median comes with its spread.  Nothing is gated on these numbers.
 
 usage: python tools/frame_denoise_time.py [--out profiles/frame_denoise_rate.txt] [--width 1920 --height 1080]"""
 import argparse
+import functools
 import os
+import statistics
 import sys
 import time
 
@@ -25,17 +27,13 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import webgpu_raytracer_amd as W  # noqa: E402
 from webgpu_raytracer_amd import renderer as R  # noqa: E402
+import timing_util  # noqa: E402
 
 ROUNDS, FRAMES, DEPTH = 5, 20, 8
 PARAMS = dict(plane_eps=0.02, normal_cos=0.9, sigma_lum=4.0)
 KW = (0.375, 0.25, 0.0625)
 F = np.float32
-
-
-def fmt(v, unit="us"):
-    v = sorted(v)
-    f = "%.3f" if unit == "ms" else "%.1f"
-    return (f + " %s (min " + f + " .. max " + f + " over %d rounds)") % (v[len(v) // 2], unit, v[0], v[-1], len(v))
+fmt = functools.partial(timing_util.fmt, median=statistics.median_high)   # of 2 x ROUNDS values: the upper one
 
 
 def numpy_prepare(accum, alb, nid, depth, u):
@@ -160,9 +158,9 @@ def main():
              "%g, plane_eps %g, sigma_lum %g}" % (width, height, DEPTH, PARAMS["normal_cos"], PARAMS["plane_eps"], PARAMS["sigma_lum"]),
              "the library's own device events around every launch; one warm-up, %d rounds, the two forms alternated" % ROUNDS,
              "k_frame_prepare (reads 24 B of G-buffer and 9 x 20 B of neighbourhood, writes 64 B per pixel)   %s"
-             % fmt(times[("prepare", "")]),
+             % fmt(times[("prepare", "")], "us", 1),
              "k_frame_finish  (48 B per pixel)                                                                %s"
-             % fmt(times[("finish", "")])]
+             % fmt(times[("finish", "")], "us", 1)]
     verdict = []
     for step in (1, 2, 4, 8, 16):
         for form in ("lds", "direct"):
@@ -170,7 +168,7 @@ def main():
                 v = times[(step, form)]
                 med = sorted(v)[len(v) // 2]
                 lines.append("pass at spacing %2d, %-6s form   %s   = %.0f GB/s of (48 B in + 16 B out) per pixel"
-                             % (step, form, fmt(v), npx * 64 / med / 1e3))
+                             % (step, form, fmt(v, "us", 1), npx * 64 / med / 1e3))
         if (step, "lds") in times:
             l, d = (sorted(times[(step, f)])[ROUNDS // 2] for f in ("lds", "direct"))
             verdict.append("%d: %s" % (step, "lds" if l < d else "direct"))

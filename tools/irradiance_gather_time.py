@@ -15,7 +15,6 @@ gather's kernel time within the spread of the composed kernels' (the same rays),
 usage: python tools/irradiance_gather_time.py [--out profiles/irradiance_gather_rate.txt] [--scenes cornell,sponza_like]"""
 import argparse
 import os
-import statistics
 import sys
 import time
 
@@ -23,26 +22,9 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import webgpu_raytracer_amd as W  # noqa: E402
+from timing_util import camera_rays, fmt, init_rng, rand_pcg  # noqa: E402
 
 GRID, DEPTH, SPP, ROUNDS, SEED = 512, 4, 16, 5, 5
-
-
-def fmt(vals, unit):
-    return "%.3f %s (min %.3f .. max %.3f over %d rounds)" % (statistics.median(vals), unit, min(vals), max(vals), len(vals))
-
-
-def camera_rays(bridge):
-    """one pinhole ray per cell centre of a GRID x GRID raster, row order, rt_ray layout, pad = cell index"""
-    cam = np.asarray(bridge.cameraData, np.float32).reshape(6, 4)
-    o, ll, hz, vt = cam[0, :3], cam[1, :3], cam[2, :3], cam[3, :3]
-    u = (np.arange(GRID, dtype=np.float32) + np.float32(0.5)) / np.float32(GRID)
-    d = ll[None, None, :] + u[None, :, None] * hz[None, None, :] + u[:, None, None] * vt[None, None, :] - o[None, None, :]
-    rays = np.zeros((GRID * GRID, 8), np.float32)
-    rays[:, 0:3] = o
-    rays[:, 3] = 1e30
-    rays[:, 4:7] = d.reshape(-1, 3)
-    rays.view(np.uint32)[:, 7] = np.arange(GRID * GRID, dtype=np.uint32)
-    return rays
 
 
 def points_from_hits(rays, t, hit):
@@ -54,29 +36,10 @@ def points_from_hits(rays, t, hit):
     return np.ascontiguousarray(p, np.float32)
 
 
-def _init_rng(stream, frame):
-    seed = (stream + frame * np.uint32(719393)).astype(np.uint32)
-    seed ^= np.uint32(2747636419)
-    for _ in range(2):
-        seed *= np.uint32(2654435769)
-        seed ^= seed >> np.uint32(16)
-    seed *= np.uint32(2654435769)
-    return seed
-
-
-def _rand_pcg(state):
-    old = state.copy()
-    state *= np.uint32(747796405)
-    state += np.uint32(2891336453)
-    word = (state >> ((old >> np.uint32(28)) + np.uint32(4))) ^ state
-    return ((word >> np.uint32(22)) ^ word).astype(np.float32) / np.float32(4294967296.0)
-
-
 def directions(points, f):
     """sample f of every point: the Lambert sampler's direction (Raytracer.wgsl:228-233, 191-199, 207-214) in float32"""
-    with np.errstate(over="ignore"):
-        rng = _init_rng(points.view(np.uint32)[:, 7] ^ np.uint32(0x80000000), np.uint32(f))
-        r1, r2 = _rand_pcg(rng), _rand_pcg(rng)
+    rng = init_rng(points.view(np.uint32)[:, 7] ^ np.uint32(0x80000000), np.uint32(f))
+    r1, r2 = rand_pcg(rng), rand_pcg(rng)
     n = points[:, 4:7]
     n = n / np.sqrt((n * n).sum(axis=1, dtype=np.float32))[:, None]
     x, y, z = n[:, 0], n[:, 1], n[:, 2]
@@ -104,7 +67,7 @@ def main():
         r = W.WebGPURenderer(0)
         W.upload_scene(r, b, GRID, GRID)
         r.setKernelTiming(True)
-        rays = camera_rays(b)
+        rays = camera_rays(b, GRID, GRID, pads=True)
         first = r.traceRays(rays)
         hit = first["hit"] != 0
         points = points_from_hits(rays, first["t"], hit)

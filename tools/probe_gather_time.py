@@ -18,7 +18,6 @@ projection.
 usage: python tools/probe_gather_time.py [--out profiles/probe_gather_rate.txt] [--scenes cornell,sponza_like]"""
 import argparse
 import os
-import statistics
 import sys
 import time
 
@@ -27,13 +26,10 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import webgpu_raytracer_amd as W  # noqa: E402
 from webgpu_raytracer_amd import renderer as R  # noqa: E402
+from timing_util import fmt, init_rng, rand_pcg  # noqa: E402
 
 GRID, DEPTH, SPP, ROUNDS, SEED = 16, 4, 1024, 5, 5
 RNG_STEP = np.uint32(719393)
-
-
-def fmt(vals, unit):
-    return "%.3f %s (min %.3f .. max %.3f over %d rounds)" % (statistics.median(vals), unit, min(vals), max(vals), len(vals))
 
 
 def grid_probes(bridge):
@@ -48,32 +44,14 @@ def grid_probes(bridge):
     return p
 
 
-def _init_rng(stream, frame):
-    seed = (stream + frame * RNG_STEP).astype(np.uint32)
-    seed ^= np.uint32(2747636419)
-    for _ in range(2):
-        seed *= np.uint32(2654435769)
-        seed ^= seed >> np.uint32(16)
-    seed *= np.uint32(2654435769)
-    return seed
-
-
-def _rand_pcg(state):
-    old = state.copy()
-    state *= np.uint32(747796405)
-    state += np.uint32(2891336453)
-    word = (state >> ((old >> np.uint32(28)) + np.uint32(4))) ^ state
-    return ((word >> np.uint32(22)) ^ word).astype(np.float32) / np.float32(4294967296.0)
-
-
 def host_rays(probes):
     """(rays (n * spp, 8) with pad', directions (n * spp, 3)): the probe rule's uniform-sphere directions in float32 numpy"""
     n = probes.shape[0]
     pads = np.repeat(probes.view(np.uint32)[:, 7], SPP)
     f = np.tile(((SEED * SPP + np.arange(SPP, dtype=np.uint64)) & 0xffffffff).astype(np.uint32), n)
+    rng = init_rng(pads ^ np.uint32(0x80000000), f)
+    u1, u2 = rand_pcg(rng), rand_pcg(rng)
     with np.errstate(over="ignore"):
-        rng = _init_rng(pads ^ np.uint32(0x80000000), f)
-        u1, u2 = _rand_pcg(rng), _rand_pcg(rng)
         pad_prime = pads + f * RNG_STEP
     z = np.float32(1) - np.float32(2) * u1
     rad = np.sqrt(np.maximum(np.float32(0), np.float32(1) - z * z))

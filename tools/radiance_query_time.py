@@ -15,7 +15,6 @@ kernel lacks.
 usage: python tools/radiance_query_time.py [--out profiles/radiance_query_rate.txt] [--scenes cornell,instanced1000,sponza_like]"""
 import argparse
 import os
-import statistics
 import sys
 
 import numpy as np
@@ -24,13 +23,10 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import webgpu_raytracer_amd as W  # noqa: E402
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from ray_query_time import camera_rays, WIDTH, HEIGHT  # noqa: E402
+from ray_query_time import WIDTH, HEIGHT  # noqa: E402
+from timing_util import camera_rays, fmt  # noqa: E402
 
 DEPTH, SPP, ROUNDS = 8, 1, 5
-
-
-def fmt(vals, unit):
-    return "%.3f %s (min %.3f .. max %.3f over %d rounds)" % (statistics.median(vals), unit, min(vals), max(vals), len(vals))
 
 
 def main():
@@ -48,7 +44,7 @@ def main():
         W.upload_scene(r, b, WIDTH, HEIGHT)
         r.setKernelVariant(1)
         r.setKernelTiming(True)
-        rays = camera_rays(b)
+        rays = camera_rays(b, WIDTH, HEIGHT)
         n = rays.shape[0]
         rays.view(np.uint32)[:, 7] = np.arange(n, dtype=np.uint32)
         sets = {"ordered": torch.from_numpy(rays).cuda(),

@@ -12,33 +12,15 @@ over the rounds).  Nothing is gated on these numbers.
 usage: python tools/ray_query_time.py [--out profiles/ray_query_rate.txt] [--scenes cornell,instanced1000,sponza_like]"""
 import argparse
 import os
-import statistics
 import sys
 
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import webgpu_raytracer_amd as W  # noqa: E402
+from timing_util import camera_rays, fmt  # noqa: E402
 
 WIDTH, HEIGHT, DEPTH, BATCH, ROUNDS = 1920, 1080, 8, 4, 5
-
-
-def camera_rays(bridge):
-    """one pinhole ray per pixel centre, row order, rt_ray layout"""
-    cam = np.asarray(bridge.cameraData, np.float32).reshape(6, 4)
-    o, ll, hz, vt = cam[0, :3], cam[1, :3], cam[2, :3], cam[3, :3]
-    u = (np.arange(WIDTH, dtype=np.float32) + np.float32(0.5)) / np.float32(WIDTH)
-    v = (np.arange(HEIGHT, dtype=np.float32) + np.float32(0.5)) / np.float32(HEIGHT)
-    d = ll[None, None, :] + u[None, :, None] * hz[None, None, :] + v[:, None, None] * vt[None, None, :] - o[None, None, :]
-    rays = np.zeros((HEIGHT * WIDTH, 8), np.float32)
-    rays[:, 0:3] = o
-    rays[:, 3] = 1e30
-    rays[:, 4:7] = d.reshape(-1, 3)
-    return rays
-
-
-def fmt(vals, unit):
-    return "%.3f %s (min %.3f .. max %.3f over %d rounds)" % (statistics.median(vals), unit, min(vals), max(vals), len(vals))
 
 
 def main():
@@ -56,7 +38,7 @@ def main():
         W.upload_scene(r, b, WIDTH, HEIGHT)
         r.setKernelVariant(2)
         r.setKernelTiming(True)
-        rays = camera_rays(b)
+        rays = camera_rays(b, WIDTH, HEIGHT)
         n = rays.shape[0]
         sets = {"ordered": torch.from_numpy(rays).cuda(),
                 "shuffled": torch.from_numpy(rays[np.random.default_rng(1).permutation(n)]).cuda()}

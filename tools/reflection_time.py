@@ -18,7 +18,6 @@ rounds with (min .. max) beside it.  Nothing is gated on these numbers.  What to
 usage: python tools/reflection_time.py [--out profiles/reflection_rate.txt]"""
 import argparse
 import os
-import statistics
 import sys
 import time
 
@@ -27,6 +26,7 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import webgpu_raytracer_amd as W  # noqa: E402
 from webgpu_raytracer_amd import renderer as R  # noqa: E402
+from timing_util import fmt, init_rng, rand_pcg  # noqa: E402
 
 N_PROBES, SIZE, LEVELS, SPT, K, DEPTH, ROUNDS, SEED = 4, 64, 5, 16, 256, 4, 5, 5
 N_FILTER, F_SIZE, F_LEVELS, F_KS = 8, 128, 6, (256, 1024, 4096)
@@ -34,31 +34,7 @@ F = np.float32
 U = np.uint32
 
 
-def fmt(vals, unit):
-    return "%.3f %s (min %.3f .. max %.3f over %d rounds)" % (statistics.median(vals), unit, min(vals), max(vals), len(vals))
-
-
 # ---- the rule in numpy: uint32 / float32 arithmetic in the order of mi355rt.h
-def init_rng(a, b):
-    with np.errstate(over="ignore"):
-        s = (a + b * U(719393)).astype(U)
-        s ^= U(2747636419)
-        s *= U(2654435769)
-        s ^= s >> U(16)
-        s *= U(2654435769)
-        s ^= s >> U(16)
-        s *= U(2654435769)
-    return s
-
-
-def rand_pcg(state):
-    with np.errstate(over="ignore"):
-        old = state.copy()
-        state[...] = old * U(747796405) + U(2891336453)
-        word = (state >> ((old >> U(28)) + U(4))) ^ state
-    return ((word >> U(22)) ^ word).astype(F) * F(2.3283064365386962890625e-10)
-
-
 def sincos(x):
     kf = np.floor(x * F(0.636619746685028076171875) + F(0.5))
     k = kf.astype(np.int32)

@@ -23,7 +23,6 @@ per point, that is, near the copy's rate.
 usage: python tools/volume_time.py [--out profiles/volume_rate.txt] [--scenes cornell,sponza_like]"""
 import argparse
 import os
-import statistics
 import sys
 import time
 
@@ -32,15 +31,12 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import webgpu_raytracer_amd as W  # noqa: E402
 from webgpu_raytracer_amd import renderer as R  # noqa: E402
+from timing_util import fmt  # noqa: E402
 
 GRID, DEPTH, SPP, ROUNDS, SEED = 16, 4, 1024, 5, 5
 N_POINTS, SHEET = 1 << 22, 2048
 BAND_A = np.array([3.141592654] + [2.094395102] * 3 + [0.785398163] * 5, np.float32)
 BAND_OF = np.array([0, 1, 1, 1, 2, 2, 2, 2, 2])
-
-
-def fmt(vals, unit):
-    return "%.3f %s (min %.3f .. max %.3f over %d rounds)" % (statistics.median(vals), unit, min(vals), max(vals), len(vals))
 
 
 def bounds(bridge):
