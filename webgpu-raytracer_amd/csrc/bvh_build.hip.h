@@ -145,25 +145,6 @@ __device__ __forceinline__ float area_of(const float mn[3], const float mx[3]) {
   return 2.0f * (dx * dy + dy * dz + dz * dx);
 }
 
-// exclusive prefix sum of a flag over the T threads of the block; returns this thread's rank and the block total
-template <int T>
-__device__ __forceinline__ uint32_t block_rank(bool flag, uint32_t* s_wave, uint32_t& total) {
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  const unsigned long long m = __ballot(flag);
-  const uint32_t in_wave = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-  __syncthreads();  // s_wave may still be read by the previous call
-  if (lane == 0u) s_wave[wave] = (uint32_t)__builtin_popcountll(m);
-  __syncthreads();
-  uint32_t before = 0, all = 0;
-  for (uint32_t w = 0; w < (uint32_t)(T / 64); w++) {
-    const uint32_t v = s_wave[w];
-    before += w < wave ? v : 0u;
-    all += v;
-  }
-  total = all;
-  return before + in_wave;
-}
-
 // blas.rs:149-177 + 201-217 for one node from its bins: best split, left count, child order.  Called by ALL 64 lanes of one
 // wave; lane i < 16 owns bin i.  The sweep's running unions are prefix (left) and suffix (right) scans over the bins — min /
 // max on the key order do not depend on the order of the operands, so the scans give the bits of the sequential loops —
@@ -603,7 +584,7 @@ __global__ __launch_bounds__(T) void k_level(Build B, uint32_t level) {
       bool bad = false;
       if (base + tid < L) bad = B.bin_cache[p] > split;
       uint32_t total;
-      const uint32_t r = block_rank<T>(bad, s_wave, total);
+      const uint32_t r = rtk::block_rank<T>(bad, s_wave, total);
       if (bad) B.scratch_l[first + run_l + r] = p;
       run_l += total;
     }
@@ -613,7 +594,7 @@ __global__ __launch_bounds__(T) void k_level(Build B, uint32_t level) {
       bool bad = false;
       if (base + tid < R) bad = B.bin_cache[p] <= split;
       uint32_t total;
-      const uint32_t r = block_rank<T>(bad, s_wave, total);
+      const uint32_t r = rtk::block_rank<T>(bad, s_wave, total);
       if (bad) B.scratch_r[first + run_r + r] = p;
       run_r += total;
     }
@@ -682,17 +663,9 @@ __global__ __launch_bounds__(1024) void k_big_plan(Build B, uint32_t level, BigN
     const bool big = live && count > kBig;
     const uint32_t nch = big ? (count + kChunk - 1u) / kChunk : 0u;
     uint32_t n_big_here, n_small_here;
-    const uint32_t r_big = block_rank<1024>(big, s_wave, n_big_here);
-    const uint32_t r_small = block_rank<1024>(live && !big, s_wave, n_small_here);
-    s_scan[tid] = nch;
-    __syncthreads();
-    for (uint32_t off = 1u; off < 1024u; off <<= 1) {
-      const uint32_t w = tid >= off ? s_scan[tid - off] : 0u;
-      __syncthreads();
-      s_scan[tid] += w;
-      __syncthreads();
-    }
-    const uint32_t ch_before = s_scan[tid] - nch, ch_here = s_scan[1023];
+    const uint32_t r_big = rtk::block_rank<1024>(big, s_wave, n_big_here);
+    const uint32_t r_small = rtk::block_rank<1024>(live && !big, s_wave, n_small_here);
+    const uint32_t ch_before = rtk::block_scan_inclusive<1024>(nch, s_scan) - nch, ch_here = s_scan[1023];
     const uint32_t c_big = s_carry[0], c_ch = s_carry[1], c_small = s_carry[2];
     if (big) {
       BigNode& N = bn[c_big + r_big];
@@ -792,7 +765,7 @@ __global__ __launch_bounds__(64) void k_big_setup(Build B, BigNode* bn) {
 }
 
 __global__ __launch_bounds__(256) void k_big_bin(Build B, uint32_t level, BigNode* bn, const Chunk* __restrict__ chunks) {
-  __shared__ uint32_t s_cnt[kBins];
+  __shared__ uint32_t s_bin_cnt[kBins];
   __shared__ uint32_t s_box[kBins][6];
   if (blockIdx.x >= B.ctl->n_chunks) return;
   const uint32_t* order_in = B.ord[level & 1u];
@@ -800,7 +773,7 @@ __global__ __launch_bounds__(256) void k_big_bin(Build B, uint32_t level, BigNod
   BigNode& N = bn[ch.big];
   if (N.leaf) return;
   if (threadIdx.x < (uint32_t)kBins) {
-    s_cnt[threadIdx.x] = 0u;
+    s_bin_cnt[threadIdx.x] = 0u;
     for (int c = 0; c < 3; c++) {
       s_box[threadIdx.x][c] = 0xffffffffu;
       s_box[threadIdx.x][c + 3] = 0u;
@@ -815,14 +788,14 @@ __global__ __launch_bounds__(256) void k_big_bin(Build B, uint32_t level, BigNod
     const uint32_t b = bin_of(axis_of(B.tri_c[t], axis), split_min, scale);
     B.bin_cache[p] = (uint8_t)b;
     const float4 a = B.tri_mn[t], c = B.tri_mx[t];
-    atomicAdd(&s_cnt[b], 1u);
+    atomicAdd(&s_bin_cnt[b], 1u);
     atomicMin(&s_box[b][0], key_of(a.x)); atomicMin(&s_box[b][1], key_of(a.y)); atomicMin(&s_box[b][2], key_of(a.z));
     atomicMax(&s_box[b][3], key_of(c.x)); atomicMax(&s_box[b][4], key_of(c.y)); atomicMax(&s_box[b][5], key_of(c.z));
   }
   __syncthreads();
-  if (threadIdx.x < (uint32_t)kBins && s_cnt[threadIdx.x]) {
+  if (threadIdx.x < (uint32_t)kBins && s_bin_cnt[threadIdx.x]) {
     const uint32_t b = threadIdx.x;
-    atomicAdd(&N.bin_cnt[b], s_cnt[b]);
+    atomicAdd(&N.bin_cnt[b], s_bin_cnt[b]);
     for (int c = 0; c < 3; c++) {
       atomicMin(&N.bin_box[b][c], s_box[b][c]);
       atomicMax(&N.bin_box[b][c + 3], s_box[b][c + 3]);
@@ -917,10 +890,10 @@ __global__ __launch_bounds__(256) void k_big_scatter(Build B, const BigNode* __r
       br = p >= mid && !right;
     }
     uint32_t total;
-    uint32_t r = block_rank<256>(bl, s_wave, total);
+    uint32_t r = rtk::block_rank<256>(bl, s_wave, total);
     if (bl) B.scratch_l[N.first + base_l + run_l + r] = p;
     run_l += total;
-    r = block_rank<256>(br, s_wave, total);
+    r = rtk::block_rank<256>(br, s_wave, total);
     // ranks of the right region count from the node's right end: inside the chunk the highest position comes first
     if (br) B.scratch_r[N.first + base_r + (tot_r - 1u - (run_r + r))] = p;
     run_r += total;
@@ -975,40 +948,18 @@ __global__ __launch_bounds__(256) void k_big_copy(Build B, uint32_t level, const
 // ------------------------------------------------------------------------------------------- pre-order layout
 // LB = exclusive prefix sum of leaf_flag over the n positions (+ the total at index n), in three launches
 __global__ __launch_bounds__(1024) void k_scan_blocks(const uint32_t* __restrict__ flag, uint32_t n, uint32_t* __restrict__ blk) {
-  __shared__ uint32_t s_cnt;
-  if (threadIdx.x == 0u) s_cnt = 0u;
-  __syncthreads();
+  __shared__ uint32_t s_wave[16];
   const uint32_t i = blockIdx.x * 1024u + threadIdx.x;
-  const unsigned long long m = __ballot(i < n && flag[i] != 0u);
-  if ((threadIdx.x & 63u) == 0u && m) atomicAdd(&s_cnt, (uint32_t)__builtin_popcountll(m));
-  __syncthreads();
-  if (threadIdx.x == 0u) blk[blockIdx.x] = s_cnt;
+  const uint32_t cnt = rtk::block_count<1024>(i < n && flag[i] != 0u, s_wave);
+  if (threadIdx.x == 0u) blk[blockIdx.x] = cnt;
 }
 // one workgroup: exclusive scan of the block counts in place; the totals of the build; where the NEXT mesh's nodes start
 // in a shared node array (node_base[0] = this mesh's first node, node_base[1] is written)
 __global__ __launch_bounds__(1024) void k_scan_top(uint32_t* __restrict__ blk, uint32_t n_blocks, Ctl* ctl, uint32_t* node_base) {
   __shared__ uint32_t s_scan[1024];
-  __shared__ uint32_t s_carry;
-  if (threadIdx.x == 0u) s_carry = 0u;
-  __syncthreads();
-  for (uint32_t c0 = 0u; c0 < n_blocks; c0 += 1024u) {
-    const uint32_t i = c0 + threadIdx.x;
-    const uint32_t v = i < n_blocks ? blk[i] : 0u;
-    s_scan[threadIdx.x] = v;
-    __syncthreads();
-    for (uint32_t off = 1u; off < 1024u; off <<= 1) {
-      const uint32_t w = threadIdx.x >= off ? s_scan[threadIdx.x - off] : 0u;
-      __syncthreads();
-      s_scan[threadIdx.x] += w;
-      __syncthreads();
-    }
-    if (i < n_blocks) blk[i] = s_carry + s_scan[threadIdx.x] - v;
-    __syncthreads();
-    if (threadIdx.x == 1023u) s_carry += s_scan[1023];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0u && ctl) {   // ctl == NULL: a plain scan of flags (world_update.hip.h's emissive list)
-    const uint32_t leaves = s_carry;
+  rtk::array_scan_exclusive<1024>(blk, n_blocks, (uint32_t*)nullptr, s_scan);
+  if (threadIdx.x == 0u) {
+    const uint32_t leaves = s_scan[1023];   // the sum: final since the scan's last barrier
     ctl->n_leaves = leaves;
     ctl->n_nodes = leaves ? 2u * leaves - 1u : 0u;
     if (node_base) node_base[1] = node_base[0] + ctl->n_nodes;
@@ -1018,15 +969,9 @@ __global__ __launch_bounds__(1024) void k_scan_apply(const uint32_t* __restrict_
                                                       const Ctl* __restrict__ ctl, uint32_t* __restrict__ lb) {
   __shared__ uint32_t s_wave[16];
   const uint32_t i = blockIdx.x * 1024u + threadIdx.x;
-  const bool f = i < n && flag[i] != 0u;
-  const unsigned long long m = __ballot(f);
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-  if (lane == 0u) s_wave[wave] = (uint32_t)__builtin_popcountll(m);
-  __syncthreads();
-  uint32_t before = 0u;
-  for (uint32_t w = 0; w < wave; w++) before += s_wave[w];
-  if (i < n) lb[i] = blk[blockIdx.x] + before + rank;
+  uint32_t in_block;
+  const uint32_t rank = rtk::block_rank<1024>(i < n && flag[i] != 0u, s_wave, in_block);
+  if (i < n) lb[i] = blk[blockIdx.x] + rank;
   if (i == 0u) lb[n] = ctl->n_leaves;
 }
 // The node array the traversal reads: {min, skip} {max, data}, skip = index after the subtree (BLAS-local).  Written at

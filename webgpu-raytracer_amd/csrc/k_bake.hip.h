@@ -19,21 +19,20 @@ namespace rtk {
 //                  in which the waves arrive, so the map is the same in every run.  A triangle that spans the atlas is
 //                  thereby split over tiles_y / RT_BAKE_BAND_TILES items instead of being one wave's loop; the item list
 //                  is a function of W, H and the scene's triangle count alone.
-//   k_bake_count   256 texels per workgroup: covered texels by wave ballot and popcount, one total per workgroup
-//   k_bake_scan    one workgroup: exclusive prefix sums of those totals in place, the grand total to the device count
+//   k_bake_count   256 texels per workgroup: covered texels (block_count, k_block_scan.hip.h), one total per workgroup
+//   k_scan_counts  one workgroup: exclusive prefix sums of those totals in place, the grand total to the device count
 //   k_bake_emit    256 texels per workgroup again: rank of a covered texel = prefix of its workgroup + covered texels
-//                  before it in the workgroup, which is ascending texel order; its point is computed and stored there
-//                  (two 16-byte stores) with its texel index, when the rank is below cap
+//                  before it in the workgroup (block_rank), which is ascending texel order; its point is computed and
+//                  stored there (two 16-byte stores) with its texel index, when the rank is below cap
 // and k_bake_scatter, the way back: atlas[texels[j]] = results[j], every uncovered texel {+0, +0, +0, -1}.
 #define RT_BAKE_NONE 0xffffffffu     // owner map: no triangle covers the texel (-1 as the i32 the host reads)
 #define RT_BAKE_BAND_TILES 4u        // tile rows of one owner-pass item
-#define RT_BAKE_SCAN_THREADS 1024u
 
 struct BakeArgs {
   const float2* auv;       // atlas UV of every global vertex: the caller's override array, or the scene's uv
   const uint4* draw;       // draw commands, one per TLAS-order instance: {3 n_tris, 1, 3 first_tri, i}
   uint32_t* owner;         // W * H
-  uint32_t* block_count;   // n_blocks: covered texels of each 256-texel block, then (k_bake_scan) their exclusive prefix
+  uint32_t* block_count;   // n_blocks: covered texels of each 256-texel block, then (k_scan_counts) their exclusive prefix
   float4* points;          // 2 per covered texel (rt_gather_point)
   uint32_t* texels;
   uint32_t inst, W, H, pad_base;
@@ -168,49 +167,11 @@ __global__ __launch_bounds__(256) void k_bake_owner(DevScene S, BakeArgs A) {
   }
 }
 
-// covered texels of this workgroup's 256 (every thread calls it) -> block_count[blockIdx.x]
-__device__ __forceinline__ void bake_count_block(bool covered, uint32_t* block_count) {
-  __shared__ uint32_t wave_n[4];
-  const uint64_t m = __ballot(covered);
-  if ((threadIdx.x & 63u) == 0u) wave_n[threadIdx.x >> 6] = (uint32_t)__popcll(m);
-  __syncthreads();
-  if (threadIdx.x == 0u) block_count[blockIdx.x] = wave_n[0] + wave_n[1] + wave_n[2] + wave_n[3];
-}
 __global__ __launch_bounds__(256) void k_bake_count(BakeArgs A) {
+  __shared__ uint32_t s_wave[4];
   const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-  bake_count_block(i < A.W * A.H && A.owner[i] != RT_BAKE_NONE, A.block_count);
-}
-
-// One workgroup of RT_BAKE_SCAN_THREADS: a[0 .. n) becomes its exclusive prefix sums in place, *total their sum (total lies
-// outside a[0 .. n)); s: RT_BAKE_SCAN_THREADS words of LDS.
-template <class T>
-__device__ __forceinline__ void bake_scan(T* a, uint32_t n, T* total, T* s) {
-  const uint32_t tid = threadIdx.x;
-  const uint32_t per = (n + RT_BAKE_SCAN_THREADS - 1u) / RT_BAKE_SCAN_THREADS;
-  const uint32_t b0 = rt_min_u32(tid * per, n), b1 = rt_min_u32(b0 + per, n);
-  T sum = 0;
-  for (uint32_t b = b0; b < b1; b++) sum += a[b];
-  s[tid] = sum;
-  __syncthreads();
-  for (uint32_t off = 1u; off < RT_BAKE_SCAN_THREADS; off <<= 1) {
-    const T v = tid >= off ? s[tid - off] : 0;
-    __syncthreads();
-    s[tid] += v;
-    __syncthreads();
-  }
-  T run = s[tid] - sum;   // the sum of the elements before b0
-  for (uint32_t b = b0; b < b1; b++) {
-    const T v = a[b];
-    a[b] = run;
-    run += v;
-  }
-  if (tid == RT_BAKE_SCAN_THREADS - 1u) *total = s[tid];
-}
-
-// block_count[0 .. n_blocks) of either count kernel -> their exclusive prefix in place, the grand total to *count
-__global__ __launch_bounds__(RT_BAKE_SCAN_THREADS) void k_bake_scan(uint32_t* block_count, uint32_t n_blocks, uint32_t* count) {
-  __shared__ uint32_t s[RT_BAKE_SCAN_THREADS];
-  bake_scan(block_count, n_blocks, count, s);
+  const uint32_t n = block_count<256>(i < A.W * A.H && A.owner[i] != RT_BAKE_NONE, s_wave);
+  if (threadIdx.x == 0u) A.block_count[blockIdx.x] = n;
 }
 
 // the point of texel (x, y) of instance inst's W x H atlas, owned by global triangle k
@@ -232,25 +193,15 @@ __device__ __forceinline__ void bake_point(const DevScene& S, const float2* auv,
   r0 = make_float4(pos.x, pos.y, pos.z, t_max);
   r1 = make_float4(n.x, n.y, n.z, rt_u2f(pad));
 }
-// The rank of a covered texel in ascending texel order, from the exclusive prefix of its workgroup (every thread of the 256
-// calls it); false: the texel is not covered.
-__device__ __forceinline__ bool bake_rank(bool covered, const uint32_t* block_count, uint32_t& rank) {
-  __shared__ uint32_t wave_n[4];
-  const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-  const uint64_t m = __ballot(covered);
-  if (lane == 0u) wave_n[w] = (uint32_t)__popcll(m);
-  __syncthreads();
-  if (!covered) return false;
-  rank = block_count[blockIdx.x] + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-  for (uint32_t v = 0u; v < w; v++) rank += wave_n[v];
-  return true;
-}
-
+// The rank of a covered texel in ascending texel order: the exclusive prefix of its workgroup + the covered texels before it
+// in the workgroup.
 __global__ __launch_bounds__(256) void k_bake_emit(DevScene S, BakeArgs A) {
+  __shared__ uint32_t s_wave[4];
   const uint32_t i = blockIdx.x * 256u + threadIdx.x;
   const uint32_t k = i < A.W * A.H ? A.owner[i] : RT_BAKE_NONE;
-  uint32_t rank;
-  if (!bake_rank(k != RT_BAKE_NONE, A.block_count, rank) || rank >= A.cap) return;
+  uint32_t in_block;
+  const uint32_t rank = A.block_count[blockIdx.x] + block_rank<256>(k != RT_BAKE_NONE, s_wave, in_block);
+  if (k == RT_BAKE_NONE || rank >= A.cap) return;
   float4 r0, r1;
   bake_point(S, A.auv, A.W, A.H, A.inst, A.t_max, A.pad_base + i, k, i % A.W, i / A.W, r0, r1);
   A.points[2 * (size_t)rank] = r0;
@@ -283,8 +234,8 @@ __global__ __launch_bounds__(256) void k_bake_scatter(BakeScatterArgs A) { bake_
 //   k_atlas_owner   a persistent grid: the waves stride over item < total, find the entry by a wave-uniform binary search in
 //                   the prefix array and run bake_owner_item on the entry's local atlas; ownership is an atomicMin of
 //                   (entry << 32) | triangle on the u64 map at the atlas texel, the lexicographic minimum of (entry, triangle)
-//   k_atlas_count, k_bake_scan, k_atlas_emit, k_atlas_scatter   as their namesakes, on the u64 map; emit decodes (entry,
-//                   triangle), loads the entry and computes the point of its local texel
+//   k_atlas_count, k_scan_counts, k_atlas_emit, k_atlas_scatter   as in the instance bake, on the u64 map; emit decodes
+//                   (entry, triangle), loads the entry and computes the point of its local texel
 struct BakeAtlasArgs {
   const float2* auv;
   const uint4* draw;
@@ -313,9 +264,9 @@ __global__ __launch_bounds__(256) void k_atlas_items(BakeAtlasArgs A) {
   A.items[e] = (unsigned long long)((n_own + 63u) / 64u) * atlas_bands(e1.x);
 }
 
-__global__ __launch_bounds__(RT_BAKE_SCAN_THREADS) void k_atlas_scan(BakeAtlasArgs A) {
-  __shared__ unsigned long long s[RT_BAKE_SCAN_THREADS];
-  bake_scan(A.items, A.n_entries, A.items + A.n_entries, s);
+__global__ __launch_bounds__(1024) void k_atlas_scan(BakeAtlasArgs A) {
+  __shared__ unsigned long long s[1024];
+  array_scan_exclusive<1024>(A.items, A.n_entries, A.items + A.n_entries, s);
 }
 
 __global__ __launch_bounds__(256) void k_atlas_owner(DevScene S, BakeAtlasArgs A) {
@@ -345,15 +296,19 @@ __global__ __launch_bounds__(256) void k_atlas_owner(DevScene S, BakeAtlasArgs A
 }
 
 __global__ __launch_bounds__(256) void k_atlas_count(BakeAtlasArgs A) {
+  __shared__ uint32_t s_wave[4];
   const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-  bake_count_block(i < A.W * A.H && A.owner[i] != RT_ATLAS_NONE, A.block_count);
+  const uint32_t n = block_count<256>(i < A.W * A.H && A.owner[i] != RT_ATLAS_NONE, s_wave);
+  if (threadIdx.x == 0u) A.block_count[blockIdx.x] = n;
 }
 
 __global__ __launch_bounds__(256) void k_atlas_emit(DevScene S, BakeAtlasArgs A) {
+  __shared__ uint32_t s_wave[4];
   const uint32_t i = blockIdx.x * 256u + threadIdx.x;
   const unsigned long long o = i < A.W * A.H ? A.owner[i] : RT_ATLAS_NONE;
-  uint32_t rank;
-  if (!bake_rank(o != RT_ATLAS_NONE, A.block_count, rank) || rank >= A.cap) return;
+  uint32_t in_block;
+  const uint32_t rank = A.block_count[blockIdx.x] + block_rank<256>(o != RT_ATLAS_NONE, s_wave, in_block);
+  if (o == RT_ATLAS_NONE || rank >= A.cap) return;
   const uint32_t e = (uint32_t)(o >> 32), k = (uint32_t)o;
   const uint4 e0 = A.entries[2 * (size_t)e], e1 = A.entries[2 * (size_t)e + 1];
   float4 r0, r1;

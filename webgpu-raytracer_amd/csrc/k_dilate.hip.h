@@ -54,7 +54,7 @@ void k_dilate_mask(DilateArgs A) {
 __global__ __launch_bounds__(256)
 void k_dilate_source(DilateArgs A) {
   __shared__ uint64_t win[RT_DILATE_WINDOW];
-  __shared__ uint32_t wave_filled[4];
+  __shared__ uint32_t s_wave[4];
   const uint32_t t = threadIdx.x;
   const uint32_t ty = blockIdx.x / A.tiles_x, tx = blockIdx.x - ty * A.tiles_x;
   const int x0 = (int)(tx * RT_DILATE_TILE), y0 = (int)(ty * RT_DILATE_TILE);
@@ -102,13 +102,8 @@ void k_dilate_source(DilateArgs A) {
   }
   const bool got = open && best != RT_DILATE_NONE;
   if (inside) A.src[(size_t)y * A.W + x] = covered ? y * A.W + x : best;
-  const uint32_t n = (uint32_t)__popcll(__ballot(got));
-  if ((t & 63u) == 0u) wave_filled[t >> 6] = n;
-  __syncthreads();
-  if (t == 0u && A.filled) {
-    const uint32_t sum = wave_filled[0] + wave_filled[1] + wave_filled[2] + wave_filled[3];
-    if (sum) atomicAdd(A.filled, sum);
-  }
+  const uint32_t sum = block_count<256>(got, s_wave);
+  if (t == 0u && A.filled && sum) atomicAdd(A.filled, sum);
 }
 
 // One thread per texel.  A filled texel (a source that is not itself) receives the source's first three words bit for bit

@@ -68,31 +68,20 @@ __device__ __forceinline__ void pair_level(const PairArgs& A, uint32_t i, uint32
   if (end > A.n_nodes) end = A.n_nodes;
 }
 
-// numbering of the inner nodes: per-1024-block counts -> k_treelet_blockscan's scan -> ranks (work[RT_TREELET_WORK_HEAD + b])
-__global__ __launch_bounds__(1024) void k_pair_count(PairArgs A, uint32_t* __restrict__ work) {
-  __shared__ uint32_t s_cnt;
-  if (threadIdx.x == 0u) s_cnt = 0u;
-  __syncthreads();
-  const uint32_t i = blockIdx.x * 1024u + threadIdx.x;
-  const bool inner = i < A.n_nodes && pair_is_inner(A, i);
-  const unsigned long long m = __ballot(inner);
-  if ((threadIdx.x & 63u) == 0u && m) atomicAdd(&s_cnt, (uint32_t)__builtin_popcountll(m));
-  __syncthreads();
-  if (threadIdx.x == 0u) work[RT_TREELET_WORK_HEAD + blockIdx.x] = s_cnt;
-}
-__global__ __launch_bounds__(1024) void k_pair_number(PairArgs A, const uint32_t* __restrict__ work) {
+// numbering of the inner nodes: per-1024-block counts (blk[b]) -> k_scan_counts -> ranks (k_block_scan.hip.h)
+__global__ __launch_bounds__(1024) void k_pair_count(PairArgs A, uint32_t* __restrict__ blk) {
   __shared__ uint32_t s_wave[16];
   const uint32_t i = blockIdx.x * 1024u + threadIdx.x;
-  const bool inner = i < A.n_nodes && pair_is_inner(A, i);
-  const unsigned long long m = __ballot(inner);
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-  if (lane == 0u) s_wave[wave] = (uint32_t)__builtin_popcountll(m);
-  __syncthreads();
-  uint32_t before = 0u;
-  for (uint32_t w = 0; w < wave; w++) before += s_wave[w];
+  const uint32_t n = block_count<1024>(i < A.n_nodes && pair_is_inner(A, i), s_wave);
+  if (threadIdx.x == 0u) blk[blockIdx.x] = n;
+}
+__global__ __launch_bounds__(1024) void k_pair_number(PairArgs A, const uint32_t* __restrict__ blk) {
+  __shared__ uint32_t s_wave[16];
+  const uint32_t i = blockIdx.x * 1024u + threadIdx.x;
+  uint32_t inner_in_block;
+  const uint32_t rank = block_rank<1024>(i < A.n_nodes && pair_is_inner(A, i), s_wave, inner_in_block);
   if (i >= A.n_nodes) return;
-  A.pair_of[i] = work[RT_TREELET_WORK_HEAD + blockIdx.x] + before + rank;
+  A.pair_of[i] = blk[blockIdx.x] + rank;
   A.parent[i] = 0xffffffffu;
 }
 // children of inner node i (absolute indices; r = RT_PAIR_NO_CHILD for a single-child node), or false when the node is not

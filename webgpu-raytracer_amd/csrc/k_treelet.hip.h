@@ -67,10 +67,10 @@ __global__ __launch_bounds__(256) void k_treelet_weight(TreeletArgs A) {
 // would pay on every update):
 //   k_treelet_hist<0>, k_treelet_pick<0>   4096-bin histogram of the keys' top 12 bits; the bin that does not fit k_max whole
 //   k_treelet_hist<1>, k_treelet_pick<1>   the same inside that bin on the next 12 bits -> key threshold (24 bits deep)
-//   k_treelet_count, k_treelet_blockscan, k_treelet_number
+//   k_treelet_count, k_scan_counts, k_treelet_number
 //                                          selected nodes (key >= threshold) are numbered first, in original order, the
-//                                          others after them in original order: per-1024-node block counts, their scan,
-//                                          ballot ranks inside a block
+//                                          others after them in original order: per-1024-node block counts, their scan
+//                                          (k_block_scan.hip.h; n_blocks is small, 1 per 1024 nodes), ranks inside a block
 // work: [0, 4096) level-0 histogram, [4096, 8192) level-1 histogram, then the TreeletPick words, then one count per block.
 struct TreeletPick {
   uint32_t bin0, above0, threshold, total_sel, all, pad[3];
@@ -108,16 +108,8 @@ __global__ __launch_bounds__(256) void k_treelet_pick(TreeletArgs A, uint32_t* _
   const uint32_t top = 4096u - 16u * t;
   uint32_t sum = 0u;
   for (uint32_t k = 0; k < 16u; k++) sum += hist[top - 1u - k];
-  s_part[t] = sum;
-  __syncthreads();
-  for (uint32_t off = 1u; off < 256u; off <<= 1) {
-    const uint32_t v = t >= off ? s_part[t - off] : 0u;
-    __syncthreads();
-    s_part[t] += v;
-    __syncthreads();
-  }
   const uint32_t base = LEVEL == 0 ? 0u : P->above0;
-  const uint32_t before = base + s_part[t] - sum;   // nodes in all bins above this thread's sixteen
+  const uint32_t before = base + block_scan_inclusive<256>(sum, s_part) - sum;   // nodes in all bins above this thread's sixteen
   const uint32_t total = base + s_part[255];
   __syncthreads();
   if (LEVEL == 0 && t == 0u) {
@@ -149,54 +141,20 @@ __device__ __forceinline__ bool treelet_selected(const TreeletArgs& A, const Tre
   return i < A.n_nodes && (P->all != 0u || A.key[i] >= P->threshold);
 }
 __global__ __launch_bounds__(1024) void k_treelet_count(TreeletArgs A, uint32_t* __restrict__ work) {
-  __shared__ uint32_t s_cnt;
+  __shared__ uint32_t s_wave[16];
   const TreeletPick* P = reinterpret_cast<const TreeletPick*>(work + 8192);
-  if (threadIdx.x == 0u) s_cnt = 0u;
-  __syncthreads();
-  const bool sel = treelet_selected(A, P, blockIdx.x * 1024u + threadIdx.x);
-  const unsigned long long m = __ballot(sel);
-  if ((threadIdx.x & 63u) == 0u && m) atomicAdd(&s_cnt, (uint32_t)__builtin_popcountll(m));
-  __syncthreads();
-  if (threadIdx.x == 0u) work[RT_TREELET_WORK_HEAD + blockIdx.x] = s_cnt;
-}
-// exclusive scan of the per-block counts, in place (one workgroup; n_blocks is small: 1 per 1024 nodes)
-__global__ __launch_bounds__(1024) void k_treelet_blockscan(uint32_t* __restrict__ work, uint32_t n_blocks) {
-  __shared__ uint32_t s_scan[1024];
-  __shared__ uint32_t s_carry;
-  uint32_t* cnt = work + RT_TREELET_WORK_HEAD;
-  if (threadIdx.x == 0u) s_carry = 0u;
-  __syncthreads();
-  for (uint32_t c0 = 0u; c0 < n_blocks; c0 += 1024u) {
-    const uint32_t i = c0 + threadIdx.x;
-    const uint32_t v = i < n_blocks ? cnt[i] : 0u;
-    s_scan[threadIdx.x] = v;
-    __syncthreads();
-    for (uint32_t off = 1u; off < 1024u; off <<= 1) {
-      const uint32_t w = threadIdx.x >= off ? s_scan[threadIdx.x - off] : 0u;
-      __syncthreads();
-      s_scan[threadIdx.x] += w;
-      __syncthreads();
-    }
-    if (i < n_blocks) cnt[i] = s_carry + s_scan[threadIdx.x] - v;
-    __syncthreads();
-    if (threadIdx.x == 1023u) s_carry += s_scan[1023];
-    __syncthreads();
-  }
+  const uint32_t n = block_count<1024>(treelet_selected(A, P, blockIdx.x * 1024u + threadIdx.x), s_wave);
+  if (threadIdx.x == 0u) work[RT_TREELET_WORK_HEAD + blockIdx.x] = n;
 }
 __global__ __launch_bounds__(1024) void k_treelet_number(TreeletArgs A, const uint32_t* __restrict__ work) {
   __shared__ uint32_t s_wave[16];
   const TreeletPick* P = reinterpret_cast<const TreeletPick*>(work + 8192);
   const uint32_t i = blockIdx.x * 1024u + threadIdx.x;
   const bool sel = treelet_selected(A, P, i);
-  const unsigned long long m = __ballot(sel);
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  const uint32_t rank_in_wave = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-  if (lane == 0u) s_wave[wave] = (uint32_t)__builtin_popcountll(m);
-  __syncthreads();
-  uint32_t before = 0u;   // selected nodes of this block in earlier waves
-  for (uint32_t w = 0; w < wave; w++) before += s_wave[w];
+  uint32_t sel_in_block;
+  const uint32_t rank = block_rank<1024>(sel, s_wave, sel_in_block);   // selected nodes of this block before this one
   if (i >= A.n_nodes) return;
-  const uint32_t sel_before = work[RT_TREELET_WORK_HEAD + blockIdx.x] + before + rank_in_wave;   // selected nodes with a smaller index
+  const uint32_t sel_before = work[RT_TREELET_WORK_HEAD + blockIdx.x] + rank;   // selected nodes with a smaller index
   const uint32_t total_sel = P->all ? A.n_nodes : P->total_sel;
   A.new_index[i] = sel ? sel_before : total_sel + (i - sel_before);
 }

@@ -2,6 +2,8 @@
 //
 //   lds_sizes.h               per-wave LDS blocks and the LdsPlan / PairPlan records, shared with the host's launch_plan.h
 //   k_common.hip.h            helpers, texture fetch, RNG
+//   k_block_scan.hip.h        block_count / block_rank / block_scan_inclusive / array_scan_exclusive: the block-level count,
+//                             rank and prefix sum of the build-path kernels, and k_scan_counts, their one-workgroup u32 scan
 //   k_intersect.hip.h         rays, slab / triangle tests, per-lane stackless walk
 //   k_shading.hip.h           surface frame, BSDFs, light sampling, counters
 //   k_prepare_primary.hip.h   k_prepare_tris / _tri_shade / _instances / _lights / _world_tris (upload-time re-layout and
@@ -26,7 +28,7 @@
 //   k_directional.hip.h       k_dir_rays / k_dir_project: the same around k_radiance_query at surface points, directions on the
 //                             hemisphere of the normal, bands 0 .. 1 (rt_gather_directional), and k_dir_scatter: the results
 //                             into the four layers of an atlas (rt_bake_atlas_directional)
-//   k_bake.hip.h              k_bake_owner / _count / _scan / _emit: the UV-space rasteriser that makes such points from the
+//   k_bake.hip.h              k_bake_owner / _count / _emit: the UV-space rasteriser that makes such points from the
 //                             texels of an instance's atlas (rt_bake_points), and k_bake_scatter, the way back
 //   k_dilate.hip.h            k_dilate_mask / _source / _apply: the nearest-texel gutter fill of a baked atlas on a coverage
 //                             bitmap (rt_dilate_atlas)
@@ -61,6 +63,7 @@
 #define RT_COUNTER_SHARDS 1024
 
 #include "k_common.hip.h"
+#include "k_block_scan.hip.h"
 #include "k_intersect.hip.h"
 #include "k_shading.hip.h"
 #include "k_prepare_primary.hip.h"

@@ -725,7 +725,7 @@ int prepare_scene(rt_ctx* c) {
       hipLaunchKernelGGL(rtk::k_treelet_hist<1>, hgrid, dim3(256), 0, c->stream, T, work);
       hipLaunchKernelGGL(rtk::k_treelet_pick<1>, dim3(1), dim3(256), 0, c->stream, T, work);
       hipLaunchKernelGGL(rtk::k_treelet_count, dim3(n_blocks), dim3(1024), 0, c->stream, T, work);
-      hipLaunchKernelGGL(rtk::k_treelet_blockscan, dim3(1), dim3(1024), 0, c->stream, work, n_blocks);
+      hipLaunchKernelGGL(rtk::k_scan_counts, dim3(1), dim3(1024), 0, c->stream, work + RT_TREELET_WORK_HEAD, n_blocks, (uint32_t*)nullptr);
       hipLaunchKernelGGL(rtk::k_treelet_number, dim3(n_blocks), dim3(1024), 0, c->stream, T, (const uint32_t*)work);
     }
     hipLaunchKernelGGL(rtk::k_treelet_remap, grid, dim3(256), 0, c->stream, T);
@@ -762,9 +762,9 @@ int prepare_scene(rt_ctx* c) {
       if ((r = ensure_buffer(c, c->treelet_work, ((size_t)RT_TREELET_WORK_HEAD + n_blocks) * 4, true)) < 0) return r;
       uint32_t* work = (uint32_t*)c->treelet_work.ptr;
       const dim3 grid((c->n_nodes + 255) / 256);
-      hipLaunchKernelGGL(rtk::k_pair_count, dim3(n_blocks), dim3(1024), 0, c->stream, P, work);
-      hipLaunchKernelGGL(rtk::k_treelet_blockscan, dim3(1), dim3(1024), 0, c->stream, work, n_blocks);
-      hipLaunchKernelGGL(rtk::k_pair_number, dim3(n_blocks), dim3(1024), 0, c->stream, P, (const uint32_t*)work);
+      hipLaunchKernelGGL(rtk::k_pair_count, dim3(n_blocks), dim3(1024), 0, c->stream, P, work + RT_TREELET_WORK_HEAD);
+      hipLaunchKernelGGL(rtk::k_scan_counts, dim3(1), dim3(1024), 0, c->stream, work + RT_TREELET_WORK_HEAD, n_blocks, (uint32_t*)nullptr);
+      hipLaunchKernelGGL(rtk::k_pair_number, dim3(n_blocks), dim3(1024), 0, c->stream, P, (const uint32_t*)(work + RT_TREELET_WORK_HEAD));
       hipLaunchKernelGGL(rtk::k_pair_parent, grid, dim3(256), 0, c->stream, P);
       hipLaunchKernelGGL(rtk::k_pair_emit, grid, dim3(256), 0, c->stream, P);
       c->pairs_dirty = false;
@@ -1620,7 +1620,7 @@ static int world_update_body(rt_ctx* c, const rt_world_frame* f, bool* touched) 
       if (D.em_count) {
         const uint32_t n_blk = (D.n_tris + 1023u) / 1024u;
         hipLaunchKernelGGL(bvhb::k_scan_blocks, dim3(n_blk), dim3(1024), 0, c->stream, (const uint32_t*)em_flag, D.n_tris, (uint32_t*)W.em_blk.ptr);
-        hipLaunchKernelGGL(bvhb::k_scan_top, dim3(1), dim3(1024), 0, c->stream, (uint32_t*)W.em_blk.ptr, n_blk, (bvhb::Ctl*)nullptr, (uint32_t*)nullptr);
+        hipLaunchKernelGGL(rtk::k_scan_counts, dim3(1), dim3(1024), 0, c->stream, (uint32_t*)W.em_blk.ptr, n_blk, (uint32_t*)nullptr);
         hipLaunchKernelGGL(wu::k_emissive_apply, dim3(n_blk), dim3(1024), 0, c->stream, D, (const uint32_t*)em_flag, (const uint32_t*)W.em_blk.ptr,
                            (uint32_t*)W.em_list.ptr);
       }
@@ -2563,7 +2563,7 @@ static int bake_front(rt_ctx* c, const rt_bake_desc* d, const void* d_uv, void* 
   const uint32_t owner_blocks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((items + 3) / 4, (uint64_t)c->num_cus * 8));
   hipLaunchKernelGGL(rtk::k_bake_owner, dim3(owner_blocks), dim3(256), 0, c->stream, S, A);
   hipLaunchKernelGGL(rtk::k_bake_count, dim3(A.n_blocks), dim3(256), 0, c->stream, A);
-  hipLaunchKernelGGL(rtk::k_bake_scan, dim3(1), dim3(RT_BAKE_SCAN_THREADS), 0, c->stream, A.block_count, A.n_blocks, (uint32_t*)d_count);
+  hipLaunchKernelGGL(rtk::k_scan_counts, dim3(1), dim3(1024), 0, c->stream, A.block_count, A.n_blocks, (uint32_t*)d_count);
   HIP_TRY(c, hipGetLastError());
   return RT_OK;
 }
@@ -2799,10 +2799,10 @@ static int bake_atlas_front(rt_ctx* c, const rt_bake_atlas_desc* d, const rt_bak
     bound += (uint64_t)((c->n_tris + 63u) / 64u) * (((entries[e].height + 7u) / 8u + RT_BAKE_BAND_TILES - 1u) / RT_BAKE_BAND_TILES);
   const uint32_t owner_blocks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((bound + 3) / 4, (uint64_t)c->num_cus * 8));
   hipLaunchKernelGGL(rtk::k_atlas_items, dim3((n + 255u) / 256u), dim3(256), 0, c->stream, A);
-  hipLaunchKernelGGL(rtk::k_atlas_scan, dim3(1), dim3(RT_BAKE_SCAN_THREADS), 0, c->stream, A);
+  hipLaunchKernelGGL(rtk::k_atlas_scan, dim3(1), dim3(1024), 0, c->stream, A);
   hipLaunchKernelGGL(rtk::k_atlas_owner, dim3(owner_blocks), dim3(256), 0, c->stream, S, A);
   hipLaunchKernelGGL(rtk::k_atlas_count, dim3(A.n_blocks), dim3(256), 0, c->stream, A);
-  hipLaunchKernelGGL(rtk::k_bake_scan, dim3(1), dim3(RT_BAKE_SCAN_THREADS), 0, c->stream, A.block_count, A.n_blocks, (uint32_t*)d_count);
+  hipLaunchKernelGGL(rtk::k_scan_counts, dim3(1), dim3(1024), 0, c->stream, A.block_count, A.n_blocks, (uint32_t*)d_count);
   HIP_TRY(c, hipGetLastError());
   return RT_OK;
 }

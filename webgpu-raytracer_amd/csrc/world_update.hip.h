@@ -117,20 +117,14 @@ __global__ __launch_bounds__(256) void k_topology(Geom G, uint32_t gi, const uin
   row[4] = a[3];
   if (em_flag) em_flag[i] = __builtin_fabsf(a0.w - 3.0f) < 1e-6f ? 1u : 0u;
 }
-// emissive triangles in topology order -> em_list[G.em_first ...] (ranks from bvhb::k_scan_blocks / k_scan_top)
+// emissive triangles in topology order -> em_list[G.em_first ...] (block prefixes from bvhb::k_scan_blocks / rtk::k_scan_counts)
 __global__ __launch_bounds__(1024) void k_emissive_apply(Geom G, const uint32_t* __restrict__ flag, const uint32_t* __restrict__ blk,
                                                           uint32_t* __restrict__ em_list) {
   __shared__ uint32_t s_wave[16];
   const uint32_t i = blockIdx.x * 1024u + threadIdx.x;
   const bool f = i < G.n_tris && flag[i] != 0u;
-  const unsigned long long m = __ballot(f);
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-  if (lane == 0u) s_wave[wave] = (uint32_t)__builtin_popcountll(m);
-  __syncthreads();
-  uint32_t before = 0u;
-  for (uint32_t w = 0; w < wave; w++) before += s_wave[w];
-  const uint32_t k = blk[blockIdx.x] + before + rank;
+  uint32_t in_block;
+  const uint32_t k = blk[blockIdx.x] + rtk::block_rank<1024>(f, s_wave, in_block);
   if (f && k < G.em_count) em_list[G.em_first + k] = G.topo_start + i;
 }
 
@@ -258,15 +252,8 @@ __device__ __forceinline__ void tlas_pack_tail(const TlasArgs& A, uint32_t* s_sc
       A.draw_out[p] = make_uint4(G.n_tris * 3u, 1u, G.topo_start * 3u, p);
       e = G.em_count;
     }
-    s_scan[tid] = e;
-    __syncthreads();
-    for (uint32_t off = 1u; off < 1024u; off <<= 1) {
-      const uint32_t w = tid >= off ? s_scan[tid - off] : 0u;
-      __syncthreads();
-      s_scan[tid] += w;
-      __syncthreads();
-    }
-    if (p < N) A.light_off[p] = s_carry + s_scan[tid] - e;
+    const uint32_t before = rtk::block_scan_inclusive<1024>(e, s_scan) - e;
+    if (p < N) A.light_off[p] = s_carry + before;
     __syncthreads();
     if (tid == 1023u) s_carry += s_scan[1023];
     __syncthreads();
