@@ -132,8 +132,9 @@ struct Oracle {
     float fx0 = rt_floor(x), fy0 = rt_floor(y);
     float fx = x - fx0, fy = y - fy0;
     int ix = rt_f2i32_sat(fx0), iy = rt_f2i32_sat(fy0);
-    auto wrap = [&](int v) { return (int)(((uint32_t)v) & (uint32_t)(N - 1)); };  // two's complement mod 1024
-    int x0 = wrap(ix), x1 = wrap(ix + 1), y0 = wrap(iy), y1 = wrap(iy + 1);
+    // two's complement mod 1024; the increment in uint32_t (a uv of 1e30 saturates ix to INT_MAX: ix + 1 would overflow)
+    auto wrap = [&](uint32_t v) { return (int)(v & (uint32_t)(N - 1)); };
+    int x0 = wrap((uint32_t)ix), x1 = wrap((uint32_t)ix + 1u), y0 = wrap((uint32_t)iy), y1 = wrap((uint32_t)iy + 1u);
     const uint8_t* base = &tex[(size_t)layer * N * N * 4];
     auto texel = [&](int xx, int yy) {
       const uint8_t* p = base + ((size_t)yy * N + xx) * 4;

@@ -9,7 +9,9 @@
 //   gbuffer_depth0 = 1   (tri, inst), normal, albedo and the background test of stream id `pad` come from the oracle's
 //                        G-buffer and t is recomputed: the oracle's ray_color to the letter.  It exists only to tie the
 //                        restated loop to the oracle (tests/test_radiance_model.py: bit for bit the oracle's frame).
-// build: the flags of oracle/Makefile (tests/radiance_util.py does it)
+// build: the flags of oracle/Makefile (tests/radiance_util.py does it).  With -DRADIANCE_MODEL_MAIN the file is a stand-alone
+// program that renders frames and traces radiance queries on scene arrays read from files (for a sanitizer build on the CPU;
+// tests/test_hostile_records_model.py writes the files).
 #include "../../oracle/rt_oracle.cpp"
 
 namespace {
@@ -277,3 +279,79 @@ void radiance_model_camera_rays(oracle_ctx* ctx, rt_ray* out) {
 }
 
 }  // extern "C"
+
+#ifdef RADIANCE_MODEL_MAIN
+// ---- the oracle's frames and the radiance queries on a scene read from files, as a program of its own
+#include <cstdio>
+#include <cstdlib>
+#include <string>
+
+namespace {
+
+template <class T>
+std::vector<T> read_file(const std::string& path) {
+  std::vector<T> v;
+  FILE* f = std::fopen(path.c_str(), "rb");
+  if (!f) {
+    std::printf("cannot open %s\n", path.c_str());
+    std::exit(2);
+  }
+  std::fseek(f, 0, SEEK_END);
+  const long bytes = std::ftell(f);
+  std::fseek(f, 0, SEEK_SET);
+  v.resize((size_t)bytes / sizeof(T));
+  if (bytes && std::fread(v.data(), 1, (size_t)bytes, f) != (size_t)bytes) std::exit(2);
+  std::fclose(f);
+  return v;
+}
+
+}  // namespace
+
+// usage: <textures.u8 or -> <width> <height> <max_depth> <scene directory>...
+// A scene directory holds vertices.f32, normals.f32, uvs.f32, topology.u32, tlas.f32, blas.f32, instances.f32, lights.u32,
+// draw_commands.u32, camera.f32 and rays.f32 (rt_ray records).  Every scene is uploaded in the order of upload_scene, three
+// frames are computed and presented, and the rays are traced as a radiance query with 2 samples.
+int main(int argc, char** argv) {
+  if (argc < 6) return 2;
+  const std::string tex_path = argv[1];
+  const uint32_t width = (uint32_t)std::atoi(argv[2]), height = (uint32_t)std::atoi(argv[3]), depth = (uint32_t)std::atoi(argv[4]);
+  std::vector<uint8_t> tex;
+  if (tex_path != "-") tex = read_file<uint8_t>(tex_path);
+  for (int a = 5; a < argc; a++) {
+    const std::string dir = std::string(argv[a]) + "/";
+    auto pos = read_file<float>(dir + "vertices.f32"), nrm = read_file<float>(dir + "normals.f32"), uv = read_file<float>(dir + "uvs.f32");
+    auto topo = read_file<uint32_t>(dir + "topology.u32"), lights = read_file<uint32_t>(dir + "lights.u32");
+    auto draw = read_file<uint32_t>(dir + "draw_commands.u32");
+    auto tlas = read_file<float>(dir + "tlas.f32"), blas = read_file<float>(dir + "blas.f32"), inst = read_file<float>(dir + "instances.f32");
+    auto cam = read_file<float>(dir + "camera.f32");
+    auto rays = read_file<float>(dir + "rays.f32");
+    if (cam.size() != 24 || pos.size() % 4 || nrm.size() != pos.size() || uv.size() * 2 != pos.size()) return 2;
+    oracle_ctx* c = oracle_create();
+    oracle_set_threads(c, 1);
+    oracle_build_pipeline(c, depth, 1);
+    if (!tex.empty()) oracle_upload_textures(c, tex.data(), (uint32_t)(tex.size() / ((size_t)RT_TEX_SIZE * RT_TEX_SIZE * 4)));
+    oracle_update_geometry(c, pos.data(), nrm.data(), uv.data(), (uint32_t)(pos.size() / 4));
+    oracle_update_bvh(c, tlas.data(), (uint32_t)(tlas.size() / 8), blas.data(), (uint32_t)(blas.size() / 8));
+    oracle_update_topology(c, topo.data(), topo.size());
+    oracle_update_instances(c, inst.data(), inst.size());
+    oracle_update_lights(c, lights.data(), lights.size());
+    oracle_update_draw_commands(c, draw.data(), draw.size());
+    oracle_update_screen_size(c, width, height);
+    oracle_update_scene_uniforms(c, cam.data(), 0, (uint32_t)(lights.size() / 2));
+    for (uint32_t f = 1; f <= 3; f++) {
+      oracle_compute(c, f);
+      oracle_present(c);
+    }
+    const uint32_t n = (uint32_t)(rays.size() / 8);
+    std::vector<float> out((size_t)n * 4);
+    std::vector<uint64_t> counts((size_t)n * 5);
+    radiance_model_trace(c, reinterpret_cast<const rt_ray*>(rays.data()), n, depth, 2, 5, 0, out.data(), counts.data());
+    uint64_t shaded = 0;
+    for (uint32_t i = 0; i < n; i++) shaded += counts[(size_t)i * 5 + 2];
+    std::printf("%s %u rays, %llu shaded hits\n", argv[a], n, (unsigned long long)shaded);
+    oracle_destroy(c);
+  }
+  std::printf("hostile records ok\n");
+  return 0;
+}
+#endif

@@ -6,7 +6,31 @@ import numpy as np
 DIAMOND_OBJ = ("v 0.0 1.0 0.0\nv 1.0 0.0 0.0\nv 0.0 0.0 1.0\nv -1.0 0.0 0.0\nv 0.0 0.0 -1.0\nv 0.0 -1.0 0.0\n"
                "f 1 3 2\nf 1 2 5\nf 1 5 4\nf 1 4 3\nf 6 2 3\nf 6 5 2\nf 6 4 5\nf 6 3 4\n")
 
+# the ray counters every build maintains (nodes_visited, tris_tested and shaded_hits: the counting build only)
+RAY_COUNTERS = ("primary_rays", "extension_rays", "shadow_rays")
+
+LDS_PER_CU = 160 * 1024
+WAVE_QUEUE = 64 * 32 + 64 * 7 * 4 + 64 * 8   # RT_WORK_BYTES_PER_WAVE
+COL_PARK = 64 * 12                           # RT_PT_COL_BYTES_PER_WAVE
+
 _bridges = {}
+
+
+def dyn_lds(b):
+    """Dynamic LDS of one workgroup of the persistent kernel's LDS form for the bridge `b` (rt_api.hip: four wave queues +
+    launch_plan.h scene_lds_slots x 16 bytes)."""
+    n_nodes = (len(b.tlas) + len(b.blas)) // 8
+    n_tris, n_inst = len(b.mesh_topology) // 20, len(b.instances) // 36
+    n_verts, n_lights = len(b.vertices) // 4, len(b.lights) // 2
+    slots = (2 * n_nodes + 3 * n_tris + 4 * n_inst + (n_inst + 3) // 4 + 8 * n_tris + 5 * n_tris + n_verts +
+             (n_verts + 1) // 2 + 9 * n_inst + (n_lights + 1) // 2 + 4 * n_lights)
+    return 4 * WAVE_QUEUE + 16 * slots
+
+
+def takes_wide_form(b):
+    """the host runs a batched product dispatch of the one-leaf scene `b` in 512-thread workgroups: three of them, each with
+    eight wave queues and eight waves' parked sample sums, fit the CU's LDS (tests/test_gpu_one_leaf_wide.py)"""
+    return dyn_lds(b) + 4 * WAVE_QUEUE + 8 * COL_PARK <= LDS_PER_CU // 3
 
 
 def diamond_obj_subdivided(n=11):
@@ -75,6 +99,20 @@ def describe_mismatch(name, a, b):
     first = tuple(idx[0])
     return "%s differs at %d of %d elements; first at %s: gpu=%r oracle=%r" % (
         name, int(ne.sum()), ne.size, first, a[first], b[first])
+
+
+def assert_accum_against_oracle(got, want, what, nan_as_class=False):
+    """The accumulation-buffer twin of radiance_util.check_records_against_model.  got, want: (h, w, 4) f32, the renderer's
+    and the oracle's.  Bit for bit, word by word.  nan_as_class: a word where the ORACLE has a NaN may hold a NaN of any
+    payload and sign (they are not pinned across the two instruction sets); every other word stays bit-exact."""
+    g, w = bits(got), bits(want)
+    bad = g != w
+    if nan_as_class:
+        bad &= ~(np.isnan(np.asarray(got, np.float32)) & np.isnan(np.asarray(want, np.float32)))
+    pixels = np.argwhere(bad.any(axis=-1))
+    assert pixels.size == 0, ("accumulation buffer, " + what, "pixels that differ", len(pixels), pixels[:8].tolist(),
+                              [np.asarray(got)[tuple(p)].tolist() for p in pixels[:4]],
+                              [np.asarray(want)[tuple(p)].tolist() for p in pixels[:4]])
 
 
 def assert_parity(gpu, cpu, check_output=True, check_counters=True):

@@ -14,7 +14,7 @@ pytestmark = pytest.mark.gpu
 
 W_, H_ = 203, 117
 FRAMES = (1, 2, 3, 4)
-RAYS = ("primary_rays", "extension_rays", "shadow_rays")
+RAYS = pu.RAY_COUNTERS
 VIEWS = ("stock", "mixed", "away")
 # (spp, depth, stripes): stripes = (rows, rank, count); 8 rows is the tile-aligned form, 1 row the per-row test
 CASES = [(1, 8, None), (3, 8, None), (1, 0, None), (3, 8, (8, 1, 3)), (1, 8, (1, 0, 2))]

@@ -6,24 +6,15 @@ the five-workgroup line, against the oracle, bit for bit (product build and coun
 import pytest
 
 import parity_util as pu
+from parity_util import dyn_lds   # (tests that import it from here keep working)
 import random_scene
 from test_gpu_product_build import _check as check_product
 
 pytestmark = pytest.mark.gpu
 
 W_, H_, DEPTH, FRAMES = 64, 48, 8, (1, 2, 3)
-LDS_PER_CU = 160 * 1024
-WAVE_QUEUES = 4 * (64 * 32 + 64 * 7 * 4 + 64 * 8)   # RT_WORK_BYTES_PER_WAVE x 4 waves
-
-
-def dyn_lds(b):
-    """Dynamic LDS of one workgroup (rt_api.hip: wave queues + scene_lds_slots x 16 bytes)."""
-    n_nodes = (len(b.tlas) + len(b.blas)) // 8
-    n_tris, n_inst = len(b.mesh_topology) // 20, len(b.instances) // 36
-    n_verts, n_lights = len(b.vertices) // 4, len(b.lights) // 2
-    slots = (2 * n_nodes + 3 * n_tris + 4 * n_inst + (n_inst + 3) // 4 + 8 * n_tris + 5 * n_tris + n_verts +
-             (n_verts + 1) // 2 + 9 * n_inst + (n_lights + 1) // 2 + 4 * n_lights)
-    return WAVE_QUEUES + 16 * slots
+LDS_PER_CU = pu.LDS_PER_CU
+WAVE_QUEUES = 4 * pu.WAVE_QUEUE   # RT_WORK_BYTES_PER_WAVE x 4 waves
 
 
 # (seed, triangles per geometry): workgroups per CU the LDS alone would allow

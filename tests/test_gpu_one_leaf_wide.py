@@ -14,9 +14,7 @@ from test_gpu_product_build import RAYS, _check as check_product, _run
 
 pytestmark = pytest.mark.gpu
 
-LDS_PER_CU = 160 * 1024
-WAVE_QUEUE = 64 * 32 + 64 * 7 * 4 + 64 * 8   # RT_WORK_BYTES_PER_WAVE
-COL_PARK = 64 * 12                           # RT_PT_COL_BYTES_PER_WAVE
+LDS_PER_CU, WAVE_QUEUE, COL_PARK = pu.LDS_PER_CU, pu.WAVE_QUEUE, pu.COL_PARK
 DEPTH, FRAMES = 8, (1, 2, 3)
 
 # scene -> whether the host takes the wide form (random one-leaf scenes: (seed, triangles))

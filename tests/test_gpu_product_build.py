@@ -14,7 +14,7 @@ import random_scene
 
 pytestmark = pytest.mark.gpu
 
-RAYS = ("primary_rays", "extension_rays", "shadow_rays")
+RAYS = pu.RAY_COUNTERS
 
 
 def _run(W, r, b, w, h, depth, spp, frames, batch, variant, walk=None):

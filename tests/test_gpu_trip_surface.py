@@ -21,7 +21,7 @@ from test_gpu_world_records import _one_leaf, _rotated_scaled
 pytestmark = pytest.mark.gpu
 
 FRAMES = (1, 2, 3, 4)
-RAYS = ("primary_rays", "extension_rays", "shadow_rays")
+RAYS = pu.RAY_COUNTERS
 _scenes = {}
 _oracle = {}   # case -> (accum, gbuffer planes, counters) of the oracle, computed once and left unchanged
 

@@ -55,8 +55,9 @@ __device__ rt3 sample_tex(const DevScene& S, rt2 tuv, int32_t layer) {
   float fx0 = rt_floor(x), fy0 = rt_floor(y);
   float fx = x - fx0, fy = y - fy0;
   int ix = rt_f2i32_sat(fx0), iy = rt_f2i32_sat(fy0);
-  int x0 = (int)((uint32_t)ix & (uint32_t)(N - 1)), x1 = (int)((uint32_t)(ix + 1) & (uint32_t)(N - 1));
-  int y0 = (int)((uint32_t)iy & (uint32_t)(N - 1)), y1 = (int)((uint32_t)(iy + 1) & (uint32_t)(N - 1));
+  // the increment in uint32_t: a uv of 1e30 saturates ix to INT_MAX, and ix + 1 would overflow the signed type
+  int x0 = (int)((uint32_t)ix & (uint32_t)(N - 1)), x1 = (int)(((uint32_t)ix + 1u) & (uint32_t)(N - 1));
+  int y0 = (int)((uint32_t)iy & (uint32_t)(N - 1)), y1 = (int)(((uint32_t)iy + 1u) & (uint32_t)(N - 1));
   const uint8_t* base = S.tex + (size_t)layer * N * N * 4;
   rt3 top = rt_mix3(texel_rgb(base, x0, y0), texel_rgb(base, x1, y0), fx);
   rt3 bot = rt_mix3(texel_rgb(base, x0, y1), texel_rgb(base, x1, y1), fx);
