@@ -954,8 +954,8 @@ int rt_denoise_atlas_device(rt_ctx* ctx, const rt_denoise_desc* desc, const void
  * bit, a non-zero reserved word, an output that is the accumulation buffer, a capacity below W * H * 16, a forced LDS form with
  * a spacing above 4.  Without a screen or a G-buffer (no rt_resize, no compute() yet): RT_ERR_NOT_READY.  The float
  * parameters are not validated: a NaN normal_cos rejects every tap but the centre.
- * Not built: temporal reprojection and moment history (SVGF's temporal half; the reference's TAA in the post pass stays the
- * only temporal term); separate treatment of specular and emissive surfaces under demodulation (a light's radiance is
+ * Temporal reprojection and moment history (SVGF's temporal half) are the optional stage of "frame temporal" below.
+ * Not built: separate treatment of specular and emissive surfaces under demodulation (a light's radiance is
  * divided by its albedo like any other); stripes and ranks (a rank's G-buffer covers only its own rows: refused).
  * The two explicit calls leave accumulation, history, counters, the G-buffer, frames traced ahead and every query's state
  * unchanged.
@@ -975,6 +975,76 @@ int rt_denoise_frame_device(rt_ctx* ctx, const rt_frame_denoise_desc* desc, void
 int rt_set_present_denoise(rt_ctx* ctx, const rt_frame_denoise_desc* desc_or_null);
 int rt_set_frame_denoise_form(rt_ctx* ctx, int form);
 int rt_frame_denoise_stats(rt_ctx* ctx, rt_frame_denoise_report* out);
+
+/* ---- frame temporal: "carry last frame's result to this frame's pixels", an optional stage of the frame denoiser ----
+ * Whenever the camera moves or the world updates the accumulator starts over, and the spatial filter above then has one sample
+ * per pixel to work on.  With this stage on, the frame denoiser keeps, per pixel, a history colour with its length n, the first
+ * two moments of its luminance and the guide of the frame the history was made from; between the prepare stage and the first
+ * pass, one gather kernel (csrc/k_frame_temporal.hip.h) reprojects every surface pixel into the previous frame, tests what it
+ * finds there against the previous guide and blends it with the current colour.  The passes and the finish are unchanged: they
+ * read the integrated image where they read the prepare stage's colour image, the current guide and the current modulation.
+ * The stage is OFF by default, and with it off every word the library produces is what it produced without the stage.
+ *
+ * THE FRAME TEMPORAL RULE.  All arithmetic is f32, unfused (no FMA contraction), in the order written, with rt_div / rt_floor /
+ * rt_max / rt_abs of mi355rt_math.h.  dot(a, b) = (a.x * b.x + a.y * b.y) + a.z * b.z; cross(a, b) = (a.y * b.z - a.z * b.y,
+ * a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x); lum as in the frame denoise rule.  Inputs: an rt_frame_temporal_desc {flags,
+ * max_history, var_history, normal_cos, plane_eps} (mi355rt_layout.h); of the CURRENT frame the outputs of the prepare stage,
+ * colour texel col[p] = {c.rgb, vs} and guide {P, inst} {N, surface flag}; of the PREVIOUS frame - the last frame this stage
+ * ran on - the history texel hist[q] = {q.rgb, n}, n a whole number stored as f32, the moments texel {m1, m2}, the guide {Pq,
+ * instq} {Nq, flagq}, and of the uniform block k_frame_prepare was given for it the pinhole eye', ll', hor', ver' (origin,
+ * lower_left, horizontal, vertical) and the jitter j'.  Per pixel p = (x, y), l = lum(c):
+ *   background  (surface flag 0): the integrated texel is col[p] bit for bit, the history {c, 0}, the moments {0, 0}.
+ *   no history  when none is kept (the first frame after a drop), when max_history == 1, or when `reproject` accepts no tap:
+ *               the integrated texel is col[p] bit for bit, the history {c, 1}, the moments {l, l * l}.
+ *   reproject   the world is taken as static, so the surface point was at P in the previous frame too.  e = P - eye'; c0 = ll'
+ *               - eye'; nrm = cross(hor', ver'); s = rt_div(dot(c0, nrm), dot(e, nrm)); r = e * s - c0 (per component); u =
+ *               rt_div(dot(r, hor'), dot(hor', hor')); v = rt_div(dot(r, ver'), dot(ver', ver')) - THE CAMERA'S hor AND ver ARE
+ *               ORTHOGONAL (look-at cameras make them so), which is what makes these two quotients the plane coordinates; fx
+ *               = (u * (float)W - 0.5f) - j'.x * (float)W; fy = ((1.0f - v) * (float)H - 0.5f) - j'.y * (float)H: the exact
+ *               inverse of the u, v k_frame_prepare forms.  Required: s > 0 && fx >= -1 && fx < W && fy >= -1 && fy < H (a
+ *               NaN fails each).  x0 = (int)rt_floor(fx), tx = fx - rt_floor(fx), y0 and ty likewise.  The taps are (x0, y0),
+ *               (x0 + 1, y0), (x0, y0 + 1), (x0 + 1, y0 + 1) in that order, their weights w = (1.0f - tx) * (1.0f - ty), tx *
+ *               (1.0f - ty), (1.0f - tx) * ty, tx * ty.  A tap is VISITED iff w > 0.
+ *   accepted    a visited tap q iff all of these hold (a NaN fails each float comparison): q is inside the image; flagq != 0;
+ *               n >= 1.0f; with RT_FRAME_TEMPORAL_SAME_INSTANCE, instq equals inst; dot(N, Nq) >= normal_cos; with d = Pq -
+ *               P (per component), rt_abs(dot(N, d)) <= plane_eps.
+ *   sums        wsum, acc[0 .. 2], s1, s2 start at +0; for every accepted tap in visiting order wsum = wsum + w; acc[c] =
+ *               acc[c] + w * hist[q][c]; s1 = s1 + w * m1; s2 = s2 + w * m2.  n_prev is the n of the first accepted tap,
+ *               replaced by a later accepted tap's n iff that is < n_prev: the least.  hq[c] = rt_div(acc[c], wsum); hm1 =
+ *               rt_div(s1, wsum); hm2 = rt_div(s2, wsum).
+ *   blend       n' = n_prev + 1.0f, replaced by (float)max_history unless n' < (float)max_history; a = rt_div(1.0f, n'); q'[c]
+ *               = hq[c] + a * (c[c] - hq[c]); m1' = hm1 + a * (l - hm1); m2' = hm2 + a * (l * l - hm2); var' = n' >=
+ *               (float)var_history ? rt_max(m2' - m1' * m1', 0.0f) : vs.  The integrated texel is {q', var'}, the history
+ *               {q', n'}, the moments {m1', m2'}.
+ * The history holds PRE-FILTER colour, in the filtered quantity of the prepare stage (radiance / albedo under DEMODULATE).
+ * WHEN IT RUNS: exactly when the prepare stage runs - on a miss of its cache - never otherwise: one run of prepare is one
+ * frame of history.  A second call on the same G-buffer reuses the integrated image and does not advance the history.  Colour,
+ * moments and guide are double-buffered: the stage reads the previous set and writes the next, into which k_frame_prepare has
+ * written its guide.
+ * THE HISTORY IS DROPPED (the next frame is a first frame) by rt_set_frame_temporal, rt_reset_frame_history, rt_resize and a
+ * change of the DEMODULATE bit between runs, since the stored quantity changes; the first two also drop the prepare stage's
+ * cache, so the next call runs both stages.  It is NOT dropped by rt_set_scene, rt_world_update, the uploads or rt_reset_accum:
+ * a moved camera and a rebuilt world are the cases it exists for.  A caller who swaps the whole scene calls
+ * rt_reset_frame_history.
+ * Refusals, RT_ERR_INVALID with messages that begin "frame temporal:", made before the context is looked at: an unknown flag
+ * bit, a non-zero reserved word, max_history == 0 or > RT_FRAME_TEMPORAL_MAX_HISTORY (256), var_history == 0.  The float
+ * parameters are not validated: a NaN rejects every tap.  The rank and stripe refusals of the frame denoiser apply as they
+ * stand.
+ * Not built: motion of instances and skinned vertices (it needs instance identity across TLAS reorders and last frame's
+ * transforms; a moved surface fails the plane test and restarts at n = 1, correct but noisy); SVGF's 3 x 3 search when all four
+ * taps fail; neighbourhood clamping of the history; feeding back the first pass's filtered colour; weighting by the
+ * accumulator's sample count (with a growing accumulator the history averages successive means).
+ *   rt_set_frame_temporal     desc != NULL: every later rt_denoise_frame, rt_denoise_frame_device and filtered present() runs
+ *                             the stage; NULL (the default) restores the plain path exactly.  Any call drops the history.
+ *   rt_reset_frame_history    drops the history.
+ *   rt_read_frame_history     blocking, for tests and tools: the current history colour (W * H x 4 f32) and moments (W * H x 2
+ *                             f32), either may be NULL; cap_pixels >= W * H.  frames_out (may be NULL): the frames integrated
+ *                             since the last drop.  With both arrays NULL only that count is read.  RT_ERR_NOT_READY while
+ *                             there is no history.
+ * rt_frame_denoise_stats reports the stage in `temporal` (0 off, 1 ran, 2 its image was reused) and `temporal_ms`. */
+int rt_set_frame_temporal(rt_ctx* ctx, const rt_frame_temporal_desc* desc_or_null);
+int rt_reset_frame_history(rt_ctx* ctx);
+int rt_read_frame_history(rt_ctx* ctx, float* colour_rgba32f, float* moments_rg32f, size_t cap_pixels, uint32_t* frames_out);
 
 /* ---- lightmaps: "the finished lightmap of these instances, in the texel format a renderer loads", in one call ----
  * The four sections above are the stages of a lightmap: points, gather, filter, gutter.  A caller who chains their host

@@ -267,9 +267,23 @@ typedef struct rt_frame_denoise_report { /* 48 B */
   uint32_t passes;
   uint8_t form[5];            /* per pass: 1 = LDS form, 2 = direct form; 0 beyond `passes` */
   uint8_t cache_hit;          /* 1: the prepare stage's outputs were those of an earlier call on the same G-buffer */
-  uint8_t pad[2];
-  uint32_t reserved[2];
+  uint8_t temporal;           /* the temporal stage (rt_set_frame_temporal): 0 = off, 1 = ran, 2 = its integrated image was reused */
+  uint8_t pad[1];
+  float temporal_ms;          /* k_frame_temporal; 0 when the stage is off or its image was reused */
+  uint32_t reserved[1];
 } rt_frame_denoise_report;
+
+/* ---- frame temporal (rt_set_frame_temporal, mi355rt.h): reprojection of last frame's history ahead of the a-trous passes ---- */
+#define RT_FRAME_TEMPORAL_MAX_HISTORY 256u
+#define RT_FRAME_TEMPORAL_SAME_INSTANCE 1u /* a history tap must lie on the pixel's instance */
+typedef struct rt_frame_temporal_desc { /* 32 B */
+  uint32_t flags;             /* RT_FRAME_TEMPORAL_*; any other bit is refused */
+  uint32_t max_history;       /* 1 .. RT_FRAME_TEMPORAL_MAX_HISTORY: the blend factor never falls below 1 / max_history; 1 keeps none */
+  uint32_t var_history;       /* >= 1: from this many frames of history on, the variance is the temporal one */
+  float normal_cos;           /* a history tap's normal must have at least this dot product with the pixel's */
+  float plane_eps;            /* a history tap's position lies at most this far from the pixel's tangent plane */
+  uint32_t reserved[3];       /* 0 */
+} rt_frame_temporal_desc;
 
 /* ---- lightmaps (rt_bake_atlas_lightmap, mi355rt.h): an atlas bake, its filter, its gutter fill and its texel format ---- */
 #define RT_LIGHTMAP_F32 0u    /* 16 B per texel: {r, g, b, w} as the bakes return it */
@@ -308,6 +322,11 @@ static_assert(__builtin_offsetof(rt_reflection_desc, size) == 0 && __builtin_off
 static_assert(sizeof(rt_denoise_desc) == 32, "rt_denoise_desc is 32 bytes");
 static_assert(sizeof(rt_frame_denoise_desc) == 32, "rt_frame_denoise_desc is 32 bytes");
 static_assert(sizeof(rt_frame_denoise_report) == 48, "rt_frame_denoise_report is 48 bytes");
+static_assert(__builtin_offsetof(rt_frame_denoise_report, temporal) == 38 && __builtin_offsetof(rt_frame_denoise_report, temporal_ms) == 40,
+              "rt_frame_denoise_report: the temporal stage took the first pad byte and the first reserved word");
+static_assert(sizeof(rt_frame_temporal_desc) == 32, "rt_frame_temporal_desc is 32 bytes");
+static_assert(__builtin_offsetof(rt_frame_temporal_desc, normal_cos) == 12 && __builtin_offsetof(rt_frame_temporal_desc, reserved) == 20,
+              "rt_frame_temporal_desc: three words, two floats, three reserved words");
 static_assert(sizeof(rt_dilate_desc) == 32, "rt_dilate_desc is 32 bytes");
 static_assert(sizeof(rt_bake_desc) == 32, "rt_bake_desc is 32 bytes");
 static_assert(sizeof(rt_bake_atlas_desc) == 32, "rt_bake_atlas_desc is 32 bytes");

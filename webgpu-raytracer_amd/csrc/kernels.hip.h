@@ -37,6 +37,9 @@
 //   k_frame_denoise.hip.h     k_frame_prepare / _pass_lds / _pass_direct / _finish: the edge-stopped a-trous filter of a FRAME,
 //                             guided by the G-buffer of the last compute(), staged in LDS or read through L2 per spacing
 //                             (rt_denoise_frame, rt_set_present_denoise)
+//   k_frame_temporal.hip.h    k_frame_temporal: the temporal stage between k_frame_prepare and the first pass: last frame's
+//                             history reprojected through last frame's camera, tested against last frame's guide and blended
+//                             (rt_set_frame_temporal)
 //   k_encode.hip.h            k_encode_atlas: a finished f32 atlas as half floats or shared-exponent RGBE8 words
 //                             (rt_encode_atlas, the last stage of rt_bake_atlas_lightmap)
 //   k_volume.hip.h            k_volume_probes / _finish / _sample / _layers: the probes of a grid, SH9 radiance into windowed
@@ -81,6 +84,7 @@
 #include "k_dilate.hip.h"
 #include "k_denoise.hip.h"
 #include "k_frame_denoise.hip.h"
+#include "k_frame_temporal.hip.h"
 #include "k_encode.hip.h"
 #include "k_volume.hip.h"
 #include "k_reflection.hip.h"

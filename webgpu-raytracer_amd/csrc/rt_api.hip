@@ -110,6 +110,23 @@ struct DenoiseFrameState {
   rt_frame_denoise_report last = {};
 };
 
+// What the temporal stage of the frame denoiser (rt_set_frame_temporal) keeps between frames, beside DenoiseFrameState and
+// dropped with it by rt_resize: per pixel the history colour {q.rgb, (float)n}, the moments {m1, m2} of lum(q) and the guide of
+// the frame the history was made from, all double-buffered (the stage reads set `cur` and writes the other one, into which
+// k_frame_prepare has written its guide); the integrated image, which takes fd.col's place as the input of pass 0; and the
+// uniform block k_frame_prepare was given for the frame of set `cur`.  `have` says that set `cur` holds a history at all.
+struct FrameTemporalState {
+  bool on = false;
+  rt_frame_temporal_desc desc = {};
+  DeviceBuffer hist[2], mom[2], guide[2], integ;
+  int cur = 0;
+  bool have = false;
+  uint32_t hist_flags = 0;          // the DEMODULATE bit the stored quantity was made under
+  uint32_t frames = 0;              // frames integrated since the last drop
+  rt_scene_uniforms prev_uniforms = {};
+  EventPair ev;
+};
+
 // What a lightmap bake (rt_bake_atlas_lightmap) and the encode entries (rt_encode_atlas) keep between calls beyond the state of
 // the stages they are made of, kept and grown: the filtered atlas, the gutter fill's count, the encoded atlas and the staged
 // input of the host encode entry.
@@ -300,6 +317,7 @@ struct rt_ctx {
   DilateState dl;
   DenoiseState dn;
   DenoiseFrameState fd;
+  FrameTemporalState ft;
   uint64_t gbuf_gen = 0;            // dispatches and consumed frames that made a G-buffer current: the key of fd's cache
   bool albedo_plane_valid = false;  // the render target holds the albedo a compute() wrote (present() overwrites it)
   LightmapState lm;
@@ -1107,6 +1125,10 @@ int rt_resize(rt_ctx* c, uint32_t width, uint32_t height) {
   // the frame denoiser's images were sized for the old screen, and the new G-buffer is empty
   for (DeviceBuffer* b : {&c->fd.col, &c->fd.guide, &c->fd.mod, &c->fd.ping, &c->fd.pong, &c->fd.out, &c->fd.albedo_keep}) b->reset();
   c->fd.cache_valid = c->fd.keep_valid = false;
+  for (DeviceBuffer* b : {&c->ft.hist[0], &c->ft.hist[1], &c->ft.mom[0], &c->ft.mom[1], &c->ft.guide[0], &c->ft.guide[1], &c->ft.integ})
+    b->reset();
+  c->ft.have = false;
+  c->ft.frames = 0;
   c->gbuf_gen = 0;
   c->albedo_plane_valid = false;
   // A bound accumulation / present buffer was sized for the old screen: it is dropped, and until the caller binds
@@ -3106,7 +3128,17 @@ static int frame_denoise_run(rt_ctx* c, const rt_frame_denoise_desc* d, void* de
     return fail(c, RT_ERR_NOT_READY, std::string(kFrameDenoise) + ": the albedo plane was overwritten by present(); call compute first");
   int r;
   if ((r = ensure_buffer(c, fd.col, npx * 16, false)) < 0) return r;
-  if ((r = ensure_buffer(c, fd.guide, npx * 32, false)) < 0) return r;
+  FrameTemporalState& ft = c->ft;
+  if (ft.on) {
+    for (int k = 0; k < 2; k++) {
+      if ((r = ensure_buffer(c, ft.hist[k], npx * 16, false)) < 0) return r;
+      if ((r = ensure_buffer(c, ft.mom[k], npx * 8, false)) < 0) return r;
+      if ((r = ensure_buffer(c, ft.guide[k], npx * 32, false)) < 0) return r;
+    }
+    if ((r = ensure_buffer(c, ft.integ, npx * 16, false)) < 0) return r;
+  } else if ((r = ensure_buffer(c, fd.guide, npx * 32, false)) < 0) {
+    return r;
+  }
   if ((r = ensure_buffer(c, fd.mod, npx * 16, false)) < 0) return r;
   if ((r = ensure_buffer(c, fd.ping, npx * 16, false)) < 0) return r;
   if (d->passes > 1 && (r = ensure_buffer(c, fd.pong, npx * 16, false)) < 0) return r;
@@ -3115,33 +3147,74 @@ static int frame_denoise_run(rt_ctx* c, const rt_frame_denoise_desc* d, void* de
       HIP_TRY(c, hipEventCreate(&p.a));
       HIP_TRY(c, hipEventCreate(&p.b));
     }
+    HIP_TRY(c, hipEventCreate(&ft.ev.a));
+    HIP_TRY(c, hipEventCreate(&ft.ev.b));
     fd.ev_ready = true;
   }
   fd.timed = false;
   fd.last = {};
   fd.last.passes = d->passes;
   fd.last.cache_hit = hit ? 1 : 0;
+  fd.last.temporal = ft.on ? (hit ? 2 : 1) : 0;
   if (!hit) {
     fd.cache_valid = false;
+    const int next = ft.cur ^ 1;
     rtk::FramePrepareArgs A;
     A.accum = accum_ptr(c);
     A.albedo = (const uint32_t*)pa;
     A.normal_id = (const float4*)pn;
     A.depth = (const float*)pd;
     A.col = (float4*)fd.col.ptr;
-    A.guide = (float4*)fd.guide.ptr;
+    A.guide = (float4*)(ft.on ? ft.guide[next].ptr : fd.guide.ptr);
     A.mod = (float4*)fd.mod.ptr;
     A.flags = d->flags;
     HIP_TRY(c, hipEventRecord(fd.ev[0].a, c->stream));
     hipLaunchKernelGGL(rtk::k_frame_prepare, dim3((c->width + 255u) / 256u, c->height), dim3(256), 0, c->stream, A, c->uniforms);
     HIP_TRY(c, hipEventRecord(fd.ev[0].b, c->stream));
+    if (ft.on) {   // one run of prepare is one frame of history
+      if (ft.have && ft.hist_flags != demod) ft.have = false, ft.frames = 0;   // the stored quantity changes: dropped
+      const rt_scene_uniforms& V = ft.prev_uniforms;
+      rtk::FrameTemporalArgs T;
+      T.col = (const float4*)fd.col.ptr;
+      T.guide = (const float4*)ft.guide[next].ptr;
+      T.prev_hist = (const float4*)ft.hist[ft.cur].ptr;
+      T.prev_mom = (const float2*)ft.mom[ft.cur].ptr;
+      T.prev_guide = (const float4*)ft.guide[ft.cur].ptr;
+      T.integ = (float4*)ft.integ.ptr;
+      T.hist = (float4*)ft.hist[next].ptr;
+      T.mom = (float2*)ft.mom[next].ptr;
+      T.W = c->width;
+      T.H = c->height;
+      T.flags = ft.desc.flags;
+      T.have = ft.have ? 1u : 0u;
+      T.max_history = (float)ft.desc.max_history;
+      T.var_history = (float)ft.desc.var_history;
+      T.normal_cos = ft.desc.normal_cos;
+      T.plane_eps = ft.desc.plane_eps;
+      for (int k = 0; k < 3; k++) {
+        T.eye[k] = V.camera.origin[k];
+        T.ll[k] = V.camera.lower_left[k];
+        T.hor[k] = V.camera.horizontal[k];
+        T.ver[k] = V.camera.vertical[k];
+      }
+      T.jit[0] = V.jitter[0];
+      T.jit[1] = V.jitter[1];
+      HIP_TRY(c, hipEventRecord(ft.ev.a, c->stream));
+      hipLaunchKernelGGL(rtk::k_frame_temporal, dim3((c->width + 255u) / 256u, c->height), dim3(256), 0, c->stream, T);
+      HIP_TRY(c, hipEventRecord(ft.ev.b, c->stream));
+      ft.cur = next;
+      ft.have = true;
+      ft.hist_flags = demod;
+      ft.frames++;
+      ft.prev_uniforms = c->uniforms;
+    }
     fd.cache_gen = c->gbuf_gen;
     fd.cache_epoch = c->epoch;
     fd.cache_flags = demod;
     fd.cache_valid = true;
   }
   rtk::FramePassArgs P;
-  P.guide = (const float4*)fd.guide.ptr;
+  P.guide = (const float4*)(ft.on ? ft.guide[ft.cur].ptr : fd.guide.ptr);
   P.W = c->width;
   P.H = c->height;
   P.tiles_x = (c->width + RT_FRAME_TILE_W - 1u) / RT_FRAME_TILE_W;
@@ -3150,7 +3223,7 @@ static int frame_denoise_run(rt_ctx* c, const rt_frame_denoise_desc* d, void* de
   P.normal_cos = d->normal_cos;
   P.plane_eps = d->plane_eps;
   P.sigma_lum = d->sigma_lum;
-  P.in = (const float4*)fd.col.ptr;
+  P.in = (const float4*)(ft.on ? ft.integ.ptr : fd.col.ptr);
   for (uint32_t p = 0; p < d->passes; p++) {
     P.out = (float4*)((p & 1u) ? fd.pong.ptr : fd.ping.ptr);
     P.step = d->step << p;
@@ -3242,11 +3315,63 @@ int rt_frame_denoise_stats(rt_ctx* c, rt_frame_denoise_report* out) {
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (!fd.last.cache_hit) HIP_TRY(c, hipEventElapsedTime(&fd.last.prepare_ms, fd.ev[0].a, fd.ev[0].b));
+    if (fd.last.temporal == 1) HIP_TRY(c, hipEventElapsedTime(&fd.last.temporal_ms, c->ft.ev.a, c->ft.ev.b));
     HIP_TRY(c, hipEventElapsedTime(&fd.last.finish_ms, fd.ev[1].a, fd.ev[1].b));
     for (uint32_t p = 0; p < fd.last.passes; p++) HIP_TRY(c, hipEventElapsedTime(&fd.last.pass_ms[p], fd.ev[2 + p].a, fd.ev[2 + p].b));
     fd.timed = false;
   }
   *out = fd.last;
+  return RT_OK;
+}
+
+// ---- frame temporal: the stage between the prepare stage and the first pass (mi355rt.h "THE FRAME TEMPORAL RULE";
+// k_frame_temporal.hip.h).  It runs inside frame_denoise_run, exactly when the prepare stage does.
+static int frame_temporal_fail(rt_ctx* c, const std::string& what) {
+  const std::string msg = "frame temporal: " + what;
+  if (!c) g_create_error = msg;
+  return fail(c, RT_ERR_INVALID, msg);
+}
+// the history, and the prepare outputs that were made beside it: the next call runs both stages again
+static void frame_history_drop(rt_ctx* c) {
+  c->ft.have = false;
+  c->ft.frames = 0;
+  c->fd.cache_valid = false;
+}
+
+int rt_set_frame_temporal(rt_ctx* c, const rt_frame_temporal_desc* d) {
+  if (d) {
+    if (d->reserved[0] | d->reserved[1] | d->reserved[2]) return frame_temporal_fail(c, "reserved words must be 0");
+    if (d->flags & ~RT_FRAME_TEMPORAL_SAME_INSTANCE) return frame_temporal_fail(c, "unknown flag bit");
+    if (d->max_history == 0 || d->max_history > RT_FRAME_TEMPORAL_MAX_HISTORY)
+      return frame_temporal_fail(c, "max_history must be 1 .. 256");
+    if (d->var_history == 0) return frame_temporal_fail(c, "var_history must be >= 1");
+  }
+  if (!c) return RT_ERR_INVALID;
+  frame_history_drop(c);
+  c->ft.on = d != nullptr;
+  if (d) c->ft.desc = *d;
+  return RT_OK;
+}
+
+int rt_reset_frame_history(rt_ctx* c) {
+  if (!c) return RT_ERR_INVALID;
+  frame_history_drop(c);
+  return RT_OK;
+}
+
+int rt_read_frame_history(rt_ctx* c, float* colour, float* moments, size_t cap_pixels, uint32_t* frames_out) {
+  if (!c) return RT_ERR_INVALID;
+  const FrameTemporalState& ft = c->ft;
+  if (frames_out) *frames_out = ft.frames;
+  if (!colour && !moments) return RT_OK;
+  if (!ft.on) return frame_temporal_fail(c, "the stage is off (rt_set_frame_temporal)");
+  if (!ft.have || !ft.hist[ft.cur].ptr) return fail(c, RT_ERR_NOT_READY, "frame temporal: no history yet");
+  const size_t npx = (size_t)c->width * c->height;
+  if (cap_pixels < npx) return frame_temporal_fail(c, "output buffers too small");
+  HIP_TRY(c, hipSetDevice(c->device));
+  if (colour) HIP_TRY(c, hipMemcpyAsync(colour, ft.hist[ft.cur].ptr, npx * 16, hipMemcpyDeviceToHost, c->stream));
+  if (moments) HIP_TRY(c, hipMemcpyAsync(moments, ft.mom[ft.cur].ptr, npx * 8, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
   return RT_OK;
 }
 

@@ -1046,6 +1046,38 @@ static napi_value rtSetPresentDenoise(napi_env env, napi_callback_info info) {
   return make_int(env, rt_set_present_denoise((rt_ctx*)get_ptr(env, a[0]), &d));
 }
 
+/* ------------------------------------------------------- frame temporal (rt_set_frame_temporal, mi355rt.h) */
+/* (ctx, desc: Float64Array {flags, maxHistory, varHistory, normalCos, planeEps} or null) -> 0, or a negative status */
+static napi_value rtSetFrameTemporal(napi_env env, napi_callback_info info) {
+  napi_value a[2];
+  napi_valuetype t;
+  rt_frame_temporal_desc d;
+  void* p = NULL;
+  size_t n = 0;
+  if (!get_args(env, info, 2, a)) return NULL;
+  if (napi_typeof(env, a[1], &t) == napi_ok && (t == napi_null || t == napi_undefined))
+    return make_int(env, rt_set_frame_temporal((rt_ctx*)get_ptr(env, a[0]), NULL));
+  if (!get_bytes(env, a[1], &p, &n)) return NULL;
+  if (!p || n != 5 * sizeof(double)) {
+    napi_throw_range_error(env, NULL, "frame temporal: the descriptor is a Float64Array of 5");
+    return NULL;
+  }
+  const double* s = (const double*)p;
+  memset(&d, 0, sizeof(d));
+  d.flags = (uint32_t)s[0];
+  d.max_history = (uint32_t)s[1];
+  d.var_history = (uint32_t)s[2];
+  d.normal_cos = (float)s[3];
+  d.plane_eps = (float)s[4];
+  return make_int(env, rt_set_frame_temporal((rt_ctx*)get_ptr(env, a[0]), &d));
+}
+/* (ctx) -> 0, or a negative status */
+static napi_value rtResetFrameHistory(napi_env env, napi_callback_info info) {
+  napi_value a[1];
+  if (!get_args(env, info, 1, a)) return NULL;
+  return make_int(env, rt_reset_frame_history((rt_ctx*)get_ptr(env, a[0])));
+}
+
 /* ------------------------------------------------------- lightmaps (rt_bake_atlas_lightmap, rt_encode_atlas, mi355rt.h) */
 /* (ctx, width, height, padBase, tMax, entries, atlasUv or null, maxDepth, spp, seed, stages: Float64Array {passes, step,
  * normalCos, planeEps, maxDist, dilateRadius, format}, out: a typed array of width * height texels of the format, wantStats)
@@ -1144,6 +1176,7 @@ static napi_value Init(napi_env env, napi_value exports) {
                {"rtBakeAtlasIrradiance", rtBakeAtlasIrradiance}, {"rtDilateAtlas", rtDilateAtlas},
                {"rtDenoiseAtlas", rtDenoiseAtlas}, {"rtBakeAtlasLightmap", rtBakeAtlasLightmap},
                {"rtDenoiseFrame", rtDenoiseFrame}, {"rtSetPresentDenoise", rtSetPresentDenoise},
+               {"rtSetFrameTemporal", rtSetFrameTemporal}, {"rtResetFrameHistory", rtResetFrameHistory},
                {"rtEncodeAtlas", rtEncodeAtlas}, {"msCreate", msCreate}, {"msDestroy", msDestroy},
                {"msUpdate", msUpdate}, {"msUpdateCamera", msUpdateCamera}, {"msGet", msGet},
                {"msTextureCount", msTextureCount}, {"msTexture", msTexture},

@@ -142,6 +142,15 @@ export class WebGPURenderer {
   denoiseFrame(desc: Float64Array | object): { data: Float32Array; width: number; height: number };
   /** present() filters the frame first (null: the plain path). */
   setPresentDenoise(desc: Float64Array | object | null): void;
+  /** Frame temporal (rt_set_frame_temporal): the descriptor of setFrameTemporal - a pixel's history grows to maxHistory frames
+   *  (1 .. 256), the variance is the temporal one from varHistory frames on, history taps are accepted by normal (normalCos) and
+   *  tangent plane (planeEps, world units). */
+  static frameTemporalDesc(opts: { planeEps: number; maxHistory?: number; varHistory?: number; normalCos?: number;
+                                   sameInstance?: boolean }): Float64Array;
+  /** denoiseFrame and a filtered present() reproject and blend last frame's history first (null: the plain path). */
+  setFrameTemporal(desc: Float64Array | object | null): void;
+  /** Drop the temporal stage's history: the next frame is a first frame. */
+  resetFrameHistory(): void;
   /** Atlas denoise (rt_denoise_atlas): `passes` passes of the 5 x 5 a-trous kernel at tap spacings step, 2 * step, ... (at
    *  most 4), guided by the points of bakePoints / bakeAtlasPoints for the same atlas: a tap counts only where its normal has
    *  a dot product >= normalCos with the texel's and its position lies within planeEps of the texel's tangent plane and

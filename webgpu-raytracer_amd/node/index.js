@@ -422,6 +422,27 @@ class WebGPURenderer {
     const d = (desc === null || desc === undefined) ? null : WebGPURenderer._frameDenoiseDesc(desc, 'setPresentDenoise');
     this._check(native.rtSetPresentDenoise(this._ctx, d), 'setPresentDenoise');
   }
+  // ---- frame temporal (rt_set_frame_temporal): the optional stage of the frame denoiser that reprojects last frame's history
+  // ahead of the first pass, by the frame temporal rule of include/mi355rt.h.  frameTemporalDesc({maxHistory = 32, varHistory =
+  // 4, planeEps, normalCos = 0.9, sameInstance = false}) -> the descriptor.  setFrameTemporal(desc | null): denoiseFrame and a
+  // filtered present() run the stage; null restores the plain path; any call drops the history.  resetFrameHistory(): the next
+  // frame is a first frame (for a caller who swaps the whole scene).
+  static frameTemporalDesc(opts = {}) {
+    if (opts.planeEps === undefined) throw new TypeError('frameTemporalDesc: opts.planeEps is required');
+    return Float64Array.of(opts.sameInstance ? 1 : 0, opts.maxHistory === undefined ? 32 : opts.maxHistory,
+      opts.varHistory === undefined ? 4 : opts.varHistory, opts.normalCos === undefined ? 0.9 : opts.normalCos, opts.planeEps);
+  }
+  setFrameTemporal(desc) {
+    let d = null;
+    if (desc !== null && desc !== undefined) {
+      d = desc instanceof Float64Array ? desc : WebGPURenderer.frameTemporalDesc(desc);
+      if (d.length !== 5) throw new TypeError('setFrameTemporal: a descriptor of frameTemporalDesc()');
+    }
+    this._check(native.rtSetFrameTemporal(this._ctx, d), 'setFrameTemporal');
+  }
+  resetFrameHistory() {
+    this._check(native.rtResetFrameHistory(this._ctx), 'resetFrameHistory');
+  }
   // ---- atlas denoise (rt_denoise_atlas): the edge-stopped a-trous filter of a baked atlas.  atlas = 4 floats per texel;
   // points (8 floats each) and texels as bakePoints / bakeAtlasPoints return them for the same atlas.  opts: {planeEps,
   // maxDist (both required, world units), normalCos = 0.9, passes = 3, step = 1}: `passes` passes of the 5 x 5 kernel at tap

@@ -16,9 +16,14 @@ import numpy as np
 
 
 class FrameLoop:
-    def __init__(self, renderer, bridge, width, height, batch=20, clock=time.perf_counter, denoise=None):
+    def __init__(self, renderer, bridge, width, height, batch=20, clock=time.perf_counter, denoise=None,
+                 temporal=None):
         """denoise: None (the reference's loop, unchanged), or a frame_denoise_desc record / a dict of its keyword arguments:
-        every present() then filters the frame first (WebGPURenderer.setPresentDenoise)."""
+        every present() then filters the frame first (WebGPURenderer.setPresentDenoise).  temporal: None, or a
+        frame_temporal_desc record / dict: the filter then reprojects last frame's history first
+        (WebGPURenderer.setFrameTemporal); valid only together with denoise=."""
+        if temporal is not None and denoise is None:
+            raise ValueError("temporal= needs denoise=: the temporal stage is a stage of the frame denoiser")
         self.renderer = renderer
         self.bridge = bridge
         self.width, self.height = width, height
@@ -26,6 +31,8 @@ class FrameLoop:
         self.clock = clock
         if denoise is not None:
             renderer.setPresentDenoise(denoise)
+        if temporal is not None:
+            renderer.setFrameTemporal(temporal)
 
     # VideoRecorder.updateSceneBuffers (:231-268) — note the upload order differs from main.ts
     def update_scene_buffers(self):

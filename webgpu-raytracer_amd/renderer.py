@@ -240,6 +240,10 @@ def load_library(path=None):
         "rt_set_present_denoise": (i32, [vp, vp]),
         "rt_set_frame_denoise_form": (i32, [vp, ctypes.c_int]),
         "rt_frame_denoise_stats": (i32, [vp, vp]),
+        # frame temporal
+        "rt_set_frame_temporal": (i32, [vp, vp]),
+        "rt_reset_frame_history": (i32, [vp]),
+        "rt_read_frame_history": (i32, [vp, vp, vp, ctypes.c_size_t, vp]),
         # lightmaps
         "rt_bake_atlas_lightmap": (i32, [vp, vp, vp, vp, u32, vp, ctypes.c_size_t, vp, vp, vp]),
         "rt_bake_atlas_lightmap_device": (i32, [vp, vp, vp, vp, vp, ctypes.c_size_t, vp, vp, vp]),
@@ -282,6 +286,7 @@ EXPORTED_SYMBOLS = (
     "rt_dilate_atlas rt_dilate_atlas_device "
     "rt_denoise_atlas rt_denoise_atlas_device "
     "rt_denoise_frame rt_denoise_frame_device rt_set_present_denoise rt_set_frame_denoise_form rt_frame_denoise_stats "
+    "rt_set_frame_temporal rt_reset_frame_history rt_read_frame_history "
     "rt_bake_atlas_lightmap rt_bake_atlas_lightmap_device rt_encode_atlas rt_encode_atlas_device "
     "rt_bake_atlas_directional rt_bake_atlas_directional_lightmap").split()
 
@@ -507,7 +512,8 @@ class RtFrameDenoiseDesc(ctypes.Structure):
 class RtFrameDenoiseReport(ctypes.Structure):
     _fields_ = [("prepare_ms", ctypes.c_float), ("pass_ms", ctypes.c_float * 5), ("finish_ms", ctypes.c_float),
                 ("passes", ctypes.c_uint32), ("form", ctypes.c_uint8 * 5), ("cache_hit", ctypes.c_uint8),
-                ("pad", ctypes.c_uint8 * 2), ("reserved", ctypes.c_uint32 * 2)]
+                ("temporal", ctypes.c_uint8), ("pad", ctypes.c_uint8 * 1), ("temporal_ms", ctypes.c_float),
+                ("reserved", ctypes.c_uint32 * 1)]
 
 
 FRAME_DENOISE_DESC_DTYPE = np.dtype([("passes", "<u4"), ("step", "<u4"), ("flags", "<u4"), ("normal_cos", "<f4"),
@@ -524,6 +530,43 @@ def frame_denoise_desc(passes=4, step=1, *, plane_eps, normal_cos=0.9, sigma_lum
     d["passes"], d["step"] = int(passes), int(step)
     d["flags"] = (RT_FRAME_DENOISE_DEMODULATE if demodulate else 0) | (RT_FRAME_DENOISE_SAME_INSTANCE if same_instance else 0)
     d["normal_cos"], d["plane_eps"], d["sigma_lum"] = normal_cos, plane_eps, sigma_lum
+    return d
+
+
+# frame temporal: mirror of rt_frame_temporal_desc, and the descriptor as a numpy record
+RT_FRAME_TEMPORAL_MAX_HISTORY = 256
+RT_FRAME_TEMPORAL_SAME_INSTANCE = 1
+
+
+class RtFrameTemporalDesc(ctypes.Structure):
+    _fields_ = [("flags", ctypes.c_uint32), ("max_history", ctypes.c_uint32), ("var_history", ctypes.c_uint32),
+                ("normal_cos", ctypes.c_float), ("plane_eps", ctypes.c_float), ("reserved", ctypes.c_uint32 * 3)]
+
+
+FRAME_TEMPORAL_DESC_DTYPE = np.dtype([("flags", "<u4"), ("max_history", "<u4"), ("var_history", "<u4"), ("normal_cos", "<f4"),
+                                      ("plane_eps", "<f4"), ("reserved", "<u4", (3,))])
+
+
+def frame_temporal_desc(max_history=32, var_history=4, *, plane_eps, normal_cos=0.9, same_instance=False):
+    """An rt_frame_temporal_desc as a one-element FRAME_TEMPORAL_DESC_DTYPE record: the history of a pixel grows to
+    max_history frames (1 .. 256; 1 keeps none), after which the blend factor stays 1 / max_history; from var_history frames on
+    the variance the passes see is the temporal one; a history tap is accepted where its normal has a dot product >= normal_cos
+    with the pixel's and its world position lies within plane_eps (world units) of the pixel's tangent plane; same_instance
+    keeps taps on the pixel's instance."""
+    d = np.zeros(1, FRAME_TEMPORAL_DESC_DTYPE)
+    d["flags"] = RT_FRAME_TEMPORAL_SAME_INSTANCE if same_instance else 0
+    d["max_history"], d["var_history"] = int(max_history), int(var_history)
+    d["normal_cos"], d["plane_eps"] = normal_cos, plane_eps
+    return d
+
+
+def _frame_temporal_record(desc):
+    """a frame_temporal_desc record, or a dict of its keyword arguments -> a contiguous one-element record"""
+    if isinstance(desc, dict):
+        desc = frame_temporal_desc(**desc)
+    d = np.ascontiguousarray(desc, dtype=FRAME_TEMPORAL_DESC_DTYPE).reshape(-1)
+    if d.size != 1:
+        raise ValueError("one rt_frame_temporal_desc record expected")
     return d
 
 
@@ -1408,7 +1451,35 @@ class WebGPURenderer:
         n = int(r.passes)
         return {"prepare_ms": float(r.prepare_ms), "pass_ms": [float(r.pass_ms[p]) for p in range(n)],
                 "finish_ms": float(r.finish_ms), "forms": [("none", "lds", "direct")[r.form[p]] for p in range(n)],
-                "cache_hit": bool(r.cache_hit)}
+                "cache_hit": bool(r.cache_hit), "temporal_ms": float(r.temporal_ms),
+                "temporal": ("off", "ran", "reused")[r.temporal]}
+
+    def setFrameTemporal(self, desc):
+        """desc (a frame_temporal_desc record or a dict): from now on denoiseFrame, denoiseFrameDevice and a filtered present()
+        reproject and blend last frame's history ahead of the first pass; None restores the plain path.  Any call drops the
+        history."""
+        if desc is None:
+            self._check(self.L.rt_set_frame_temporal(self.ctx, None), "setFrameTemporal")
+            return
+        d = _frame_temporal_record(desc)
+        self._check(self.L.rt_set_frame_temporal(self.ctx, _ptr(d)), "setFrameTemporal")
+
+    def resetFrameHistory(self):
+        """Drop the temporal stage's history: the next frame is a first frame.  For a caller who swaps the whole scene."""
+        self._check(self.L.rt_reset_frame_history(self.ctx), "resetFrameHistory")
+
+    def readFrameHistory(self, frames_only=False):
+        """-> (colour (H, W, 4) f32 {q.rgb, n}, moments (H, W, 2) f32, frames integrated since the last drop); with
+        frames_only, that count alone.  Blocking; for tests and tools."""
+        n = ctypes.c_uint32(0)
+        if frames_only:
+            self._check(self.L.rt_read_frame_history(self.ctx, None, None, 0, ctypes.addressof(n)), "readFrameHistory")
+            return int(n.value)
+        col = np.empty((self.height, self.width, 4), np.float32)
+        mom = np.empty((self.height, self.width, 2), np.float32)
+        self._check(self.L.rt_read_frame_history(self.ctx, _ptr(col), _ptr(mom), self.width * self.height,
+                                                 ctypes.addressof(n)), "readFrameHistory")
+        return col, mom, int(n.value)
 
     # ---- lightmaps: bake, filter, gutter fill and encode in one call, without leaving the device (rt_bake_atlas_lightmap) ----
     @staticmethod
