@@ -278,15 +278,16 @@ int rt_debug_pt_launch(rt_ctx* ctx, uint32_t* out4);
  * those two in the form whose walks test the BLAS leaves alone, in wave lock-step: the host takes it for a batched dispatch
  * of a one-leaf scene when the BLAS bytes of rt_upload_bvh are a canonical pre-order tree of finite, nested boxes with at
  * most 16 leaves of 1-7 triangles (MI355RT_LEAF_SWEEP=0 in the environment of rt_create switches that off;
- * MI355RT_LEAF_SWEEP_GUARD=1 sends every walk of such a form through the node walk it keeps for rays with a non-finite
- * reciprocal direction).  The images of all forms are the same, bit for bit. */
+ * MI355RT_LEAF_SWEEP_GUARD=1 sends every walk of such a form through the sweep over all nodes of the tree that it keeps for
+ * rays with a non-finite reciprocal direction).  The images of all forms are the same, bit for bit. */
 enum { RT_PT_FORM_NONE = 0, RT_PT_FORM_GENERIC = 1, RT_PT_FORM_PLAIN = 2, RT_PT_FORM_GENERIC_SWEEP = 3, RT_PT_FORM_PLAIN_SWEEP = 4 };
 int rt_debug_pt_form(const rt_ctx* ctx);
 /* Diagnostic build (-DRT_LANE_STATS) only: lane utilisation of the parts of a trip of k_pathtrace_persistent:
  * out32[2 k] = times part k ran (wave level), out32[2 k + 1] = active lanes summed; k = 0 shade, 1 / 2 node step / triangle
  * chunk of the shadow walk, 3 / 4 of the extension walk, 5 surface frame of a new hit, 6 start of a sample, 7 end of a sample;
  * in the one-leaf forms 5 only records the hit, 6 makes the camera ray and loads the G-buffer words, and 8 is the one pass that
- * makes the surface frame of both.
+ * makes the surface frame of both; in the sweep forms, per walk with a walking lane, 9 counts every walk, 10 those that sweep
+ * the node records and 11 those with a lane of a non-finite slab operand (and those lanes).
  * Returns 1 in the diagnostic build, 0 in the product build (no counter executes, the array stays zero). */
 int rt_debug_lane_stats(rt_ctx* ctx, uint64_t* out32, int reset);
 /* Proof obligation of the device build's short division / reciprocal / square-root sequences (csrc/k_ieee.hip.h): run

@@ -21,6 +21,9 @@ PARTS = ("shade", "shadow walk: node step (sweep: leaf step)", "shadow walk: tri
          "extension walk: triangle chunk", "new hit (one-leaf: recorded; else + surface frame)",
          "start of a sample (one-leaf: camera ray + G-buffer words; else + surface frame)", "end of a sample",
          "surface frame, one pass (one-leaf forms)")
+# sweep forms only, per walk that has a walking lane: all of them, those that take the node sweep (a lane with a non-finite
+# reciprocal direction or origin term sends its wave there), and the lanes that have such a term
+WALKS = ("sweep-form walk", "... through the node sweep (cold path)", "... with a lane of a non-finite slab operand")
 
 
 def render(flags):
@@ -51,6 +54,12 @@ try:
     for k, name in enumerate(PARTS):
         if n[k]:
             print("   %-80s %14.2f %12.1f %12.3f" % (name, n[k] / trips, lanes[k] / n[k], lanes[k] / n[k] / 64.0))
+    wn, wl = buf[18:24:2].astype(float), buf[19:24:2].astype(float)
+    if wn[0]:
+        print("   %-80s %14s %12s %12s" % ("walks", "per trip", "lanes / walk", "share of walks"))
+        for k, name in enumerate(WALKS):
+            print("   %-80s %14.4f %12.1f %12.6f" % (name, wn[k] / trips, wl[k] / wn[k] if wn[k] else 0.0, wn[k] / wn[0]))
+        print("   lanes with a non-finite slab operand: %d of %d walking lanes (%.3g)" % (wl[2], wl[0], wl[2] / wl[0]))
     r.destroy()
 finally:
     W._build.build_rt(force=True)

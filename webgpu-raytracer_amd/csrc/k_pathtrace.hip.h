@@ -613,10 +613,11 @@ __device__ __forceinline__ rt3 col_park_add(f4* lds, rt3 radiance) {   // the su
 // k_pathtrace_sweep_wide, k_pathtrace_sweep_plain: the wide form and its plain twin (<false, true, true> only, the same
 // workgroups and LDS layout) for a scene whose BLAS the host has found sweepable (scene_facts.h walk_facts; launch_plan.h
 // persistent_shape): both walks of a trip test the BLAS leaves in wave lock-step (k_traverse.hip.h traverse_leaves).  They
-// take two parameters more: the leaf records, and their number with bit 31 set when every walk is to take the guard's branch.
+// take two parameters more: the leaf records with the node records behind them, and a word of the number of leaves (bits 0-15),
+// the number of nodes (bits 16-30) and bit 31, set when every walk is to take the node sweep.
 #define RT_PT_SWEEP true
 #define RT_PT_SWEEP_PARAMS , const float4* __restrict__ leaf_recs, uint32_t leaf_info
-#define RT_PT_SWEEP_ARG leaf_recs, leaf_info & 0xffffu, (leaf_info >> 31) != 0u
+#define RT_PT_SWEEP_ARG leaf_recs, leaf_info & 0xffffu, (leaf_info >> 31) != 0u, (leaf_info >> 16) & 0x7fffu
 #define RT_PT_WAVES 8
 #define RT_PT_SIMD_WAVES RT_PT_WIDE_WAVES
 #define RT_PT_KERNEL k_pathtrace_sweep_wide

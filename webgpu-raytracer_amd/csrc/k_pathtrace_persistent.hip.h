@@ -2,7 +2,7 @@
 // times, inside namespace rtk): RT_PT_KERNEL is the kernel's name, RT_PT_WAVES its waves per workgroup, RT_PT_SIMD_WAVES the
 // waves per SIMD of its launch bounds (an expression that may use the template parameters) and RT_PT_PLAIN whether it is the
 // form for scenes of plain materials.  RT_PT_SWEEP: whether the walks sweep the BLAS leaves (k_traverse.hip.h traverse_leaves);
-// such a form takes RT_PT_SWEEP_PARAMS behind the common parameters, the leaf records and their number, and RT_PT_SWEEP_ARG
+// such a form takes RT_PT_SWEEP_PARAMS behind the common parameters, the leaf and node records and their numbers, and RT_PT_SWEEP_ARG
 // makes the walk's LeafSweep of them (the other forms define both empty, and keep their parameter list).  No include guard.
 // ONE_INST (LDS form only): the scene's TLAS is a single leaf (k_traverse.hip.h traverse<.., ONE_INST>).  Every hit is then in
 // the one instance, and what a trip would compute from (instance, triangle) alone is read from the per-triangle world
@@ -372,7 +372,7 @@ __global__ __launch_bounds__(64 * RT_PT_WAVES, RT_PT_SIMD_WAVES) void RT_PT_KERN
       int32_t a_, b_;
       bool occluded;
       if constexpr (SWEEP) {
-        traverse_leaves<true, MODE>(M, s_scene, WW, LeafSweep{RT_PT_SWEEP_ARG}, U.blas_base_idx, want_shadow, sh_o, sh_d, sh_tmax,
+        traverse_leaves<true, MODE, !PLAIN>(M, s_scene, WW, LeafSweep{RT_PT_SWEEP_ARG}, U.blas_base_idx, want_shadow, sh_o, sh_d, sh_tmax,
                                     t_, a_, b_, occluded);
       } else {
         traverse<true, DETAIL, MODE, ONE_INST>(M, s_scene, WW, U.blas_base_idx, want_shadow, sh_o, sh_d, sh_tmax, t_, a_, b_,
@@ -395,7 +395,7 @@ __global__ __launch_bounds__(64 * RT_PT_WAVES, RT_PT_SIMD_WAVES) void RT_PT_KERN
       int32_t tri_, inst_;
       bool any_;
       if constexpr (SWEEP) {
-        traverse_leaves<false, MODE>(M, s_scene, WW, LeafSweep{RT_PT_SWEEP_ARG}, U.blas_base_idx, want_extend, p.ro, p.rd, RT_T_MAX,
+        traverse_leaves<false, MODE, !PLAIN>(M, s_scene, WW, LeafSweep{RT_PT_SWEEP_ARG}, U.blas_base_idx, want_extend, p.ro, p.rd, RT_T_MAX,
                                      t_, tri_, inst_, any_);
       } else {
         traverse<false, DETAIL, MODE, ONE_INST>(M, s_scene, WW, U.blas_base_idx, want_extend, p.ro, p.rd, RT_T_MAX, t_, tri_,

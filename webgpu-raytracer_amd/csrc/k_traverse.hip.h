@@ -163,6 +163,8 @@ __device__ __forceinline__ void wave_work_at(WaveWork& W, char* wbase) {
 // and triangle chunk of the shadow walk (a sweep form: leaf step and chunk), 3 / 4 the same of the extension walk, 5 surface frame of the new hit, 6 start of a
 // sample (camera ray + G-buffer surface), 7 end of a sample.  In the one-leaf forms of the persistent kernel part 5 only records
 // the hit and part 6 makes the camera ray and loads the G-buffer words; 8 is the one pass that makes the surface frame of both.
+// Sweep forms (traverse_leaves), per walk with a walking lane: 9 every walk, 10 the walks that take the node sweep (the cold
+// path), 11 the walks with a lane whose slab operands are not finite, and those lanes.
 // Nothing else reads the array; in the product build RT_LSTAT is empty.
 __device__ unsigned long long g_lane_stats[32];
 #ifdef RT_LANE_STATS
@@ -644,15 +646,26 @@ __device__ __forceinline__ void traverse(const TravMem& M, const f4* lds, const 
 // does not depend on a bound or an order, so nobody waits; the lanes queue (owner, triangle) items across leaves, the wave
 // tests 64 of them whenever the queue holds as many and the rest at the end, and a lane found occluded queues no more.
 // Node 0 (the TLAS leaf, world space) and the instance entry are those of traverse<.., ONE_INST>.
-// Guard: the argument needs finite inv_d and o_inv_d (fmin / fmax drop a NaN, and 0 * inf makes one where a direction
+// Node sweep: the argument needs finite inv_d and o_inv_d (fmin / fmax drop a NaN, and 0 * inf makes one where a direction
 // component is zero and a box face lies at 0).  If a walking lane of the wave has a non-finite component, or the host asks
-// for it (L.guard, a test hook), the whole wave takes traverse() for this walk.
+// for it (L.guard, a test hook), the wave sweeps the NODE records for this walk instead (scene_facts.h NodeRecord: every node
+// of the tree in array order, an inner node under a zero word with the end of its subtree as a position).  On a canonical
+// pre-order tree that is the reference's stackless walk with one word of state per lane, skip_until, the first position the
+// lane tests again: at position i a lane tests the box iff i >= skip_until; a missed inner node moves skip_until to the end
+// of its subtree, a hit one does nothing, and a leaf is the leaf of the sweep above.  Per lane these are the reference's
+// nodes, in its order, against its bounds, whatever the bits of the ray: no nesting argument, no finite operands.
+// ONE_LOOP: one loop for both sweeps (the record array and its length picked by the wave-uniform `cold`; the leaf sweep
+// pays a compare, a mask `and` and a scalar test of the leaf word per step), or a loop each, instances of the same code, which
+// costs the leaf sweep nothing.  The kernel chooses by what the compiler and the GPU said of it: two loops
+// in the plain form (no scratch either way, and 1.9 % faster per image), one in the generic form (19 spilled VGPRs, not 20).
 // Product build only: the nodes a ray visits are not those of the reference, so there is nothing to count.
 typedef const f4 __attribute__((address_space(4))) * rt_cptr;   // wave-uniform reads through the scalar cache
 struct LeafSweep {
-  const float4* recs;   // n_leaves + 1 records of 32 bytes (the last one padding for the read ahead)
+  const float4* recs;   // n_leaves + 1 leaf records of 32 bytes, then n_nodes + 1 node records (the last one of each array is
+                        // padding for the read ahead)
   uint32_t n_leaves;
   bool guard;
+  uint32_t n_nodes;
 };
 __device__ __forceinline__ bool rt_finite3(rt3 v) {   // on the bits: no comparison a compiler flag could fold
   return (rt_f2u(v.x) & 0x7f800000u) != 0x7f800000u && (rt_f2u(v.y) & 0x7f800000u) != 0x7f800000u &&
@@ -669,42 +682,19 @@ __device__ __forceinline__ bool sweep_test(const TravMem& M, const f4* lds, cons
   const f4 g0 = ld_l(lds, slot), g1 = ld_l(lds, slot + 1u), g2 = ld_l(lds, slot + 2u);
   return hit_tri_nb(g0, g1, g2, q, M.t_min, ra.w, t);
 }
-template <bool ANY, int MODE>
-__device__ __forceinline__ void traverse_leaves(const TravMem& M, const f4* lds, const WaveWork& W, const LeafSweep& L,
-                                                uint32_t blas_base, bool active, rt3 o, rt3 d, float t_max, float& out_t,
-                                                int32_t& out_tri, int32_t& out_inst, bool& out_any) {
-  static_assert(MODE == RT_TRAV_LDS, "the leaf sweep is a one-leaf LDS form");
+// The sweep over n records (the walking lanes' rays are posted in W.rays).  NODES: RT_SWEEP_LEAVES = every record is a leaf,
+// RT_SWEEP_NODES = node records, RT_SWEEP_EITHER = node records if there is a zero word among them (a leaf array has none,
+// and then skip_until stays 0).
+#define RT_SWEEP_LEAVES 0
+#define RT_SWEEP_NODES 1
+#define RT_SWEEP_EITHER 2
+template <bool ANY, int NODES>
+__device__ __forceinline__ void sweep_records(const TravMem& M, const f4* lds, const WaveWork& W, rt_cptr recs, uint32_t n,
+                                              bool walking, rt3 inv_d, rt3 o_inv_d, float t_max, float& out_t,
+                                              int32_t& out_tri, bool& out_any) {
   const uint32_t lane = threadIdx.x & 63u;
-  out_t = t_max;
-  out_tri = -1;
-  out_inst = -1;
-  out_any = false;
-  // node 0, the TLAS leaf: a miss ends the walk, a hit enters the one instance
-  const f4 lo0 = ld_l(lds, M.l_nodes), hi0 = ld_l(lds, M.l_nodes + 1u);
-  const LocalRay rw = make_ray(o, d);
-  const bool walking = active && blas_base != 0u && hit_box4(lo0, hi0, rw.inv_d, rw.o_inv_d, M.t_min, t_max);
-  if (__builtin_amdgcn_ballot_w64(walking) == 0ull) return;
-  const uint32_t inst0 = __builtin_amdgcn_readfirstlane(rt_f2u(hi0.w) >> 3);
-  uint32_t root_;
-  const LocalRay q = to_instance<MODE>(M, lds, inst0, o, d, root_);
-  const bool finite = rt_finite3(q.inv_d) && rt_finite3(q.o_inv_d);
-  if (L.guard || __builtin_amdgcn_ballot_w64(walking && !finite) != 0ull) {
-    // (inlined, the node walk costs the plain sweep form 27 spilled VGPRs, 48 bytes of scratch per lane; called as a function
-    // of its own, or replaced by the one-ray-per-lane walk of k_intersect.hip.h, it cost more: 57 and 39)
-    uint32_t n0 = 0u, n1 = 0u;
-    traverse<ANY, false, MODE, true>(M, lds, W, blas_base, active, o, d, t_max, out_t, out_tri, out_inst, out_any, n0, n1);
-    return;
-  }
-  if (walking) {
-    f4 ra, rb;
-    ra.x = q.o.x; ra.y = q.o.y; ra.z = q.o.z; ra.w = t_max;   // .w: the bound the lane's items are tested against
-    rb.x = q.d.x; rb.y = q.d.y; rb.z = q.d.z; rb.w = 0.0f;    // .w (any hit): non-zero once an item of the lane was accepted
-    W.rays[2 * lane] = ra;
-    W.rays[2 * lane + 1] = rb;
-  }
   const rt_lptr32_ordered items = (rt_lptr32_ordered)W.items;
-  const rt_cptr recs = (rt_cptr)L.recs;
-  const uint32_t n = L.n_leaves;
+  uint32_t skip_until = 0u;   // NODES: the first position the lane tests again
   f4 lo = recs[0], hi = recs[1];
   if (ANY) {
     // The queue is the wave's items followed by its result slots, which this walk does not use: it holds fewer than 64 items
@@ -727,11 +717,16 @@ __device__ __forceinline__ void traverse_leaves(const TravMem& M, const f4* lds,
       const f4 clo = lo, chi = hi;
       lo = recs[2u * i + 2u];
       hi = recs[2u * i + 3u];
-      RT_LSTAT(1, walking & !occluded);
-      const bool hit = walking & !occluded & hit_box4(clo, chi, q.inv_d, q.o_inv_d, M.t_min, t_max);
+      const bool tests = NODES != RT_SWEEP_LEAVES ? (walking & !occluded & (i >= skip_until)) : (walking & !occluded);
+      RT_LSTAT(1, tests);
+      const bool hit = tests & hit_box4(clo, chi, inv_d, o_inv_d, M.t_min, t_max);
+      const uint32_t data = rt_f2u(chi.w), cnt = data & 7u;
+      if (NODES != RT_SWEEP_LEAVES && data == 0u) {   // an inner node (wave-uniform): a miss skips its subtree
+        skip_until = (tests & !hit) ? rt_f2u(clo.w) : skip_until;
+        continue;
+      }
       const unsigned long long hm = __builtin_amdgcn_ballot_w64(hit);
       if (hm == 0ull) continue;
-      const uint32_t data = rt_f2u(chi.w), cnt = data & 7u;
       const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(hm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)hm, 0u));
       if (hit) {
         const rt_lptr32_ordered it = items + queued + __umul24(rank, cnt);
@@ -759,11 +754,16 @@ __device__ __forceinline__ void traverse_leaves(const TravMem& M, const f4* lds,
     const f4 clo = lo, chi = hi;
     lo = recs[2u * i + 2u];
     hi = recs[2u * i + 3u];
-    RT_LSTAT(3, walking);
-    const bool hit = walking & hit_box4(clo, chi, q.inv_d, q.o_inv_d, M.t_min, closest);
+    const bool tests = NODES != RT_SWEEP_LEAVES ? (walking & (i >= skip_until)) : walking;
+    RT_LSTAT(3, tests);
+    const bool hit = tests & hit_box4(clo, chi, inv_d, o_inv_d, M.t_min, closest);
+    const uint32_t data = rt_f2u(chi.w), cnt = data & 7u, first = data >> 3, div = rt_f2u(clo.w);
+    if (NODES != RT_SWEEP_LEAVES && data == 0u) {   // an inner node (wave-uniform): a miss skips its subtree
+      skip_until = (tests & !hit) ? div : skip_until;
+      continue;
+    }
     const unsigned long long hm = __builtin_amdgcn_ballot_w64(hit);
     if (hm == 0ull) continue;
-    const uint32_t data = rt_f2u(chi.w), cnt = data & 7u, first = data >> 3, div = rt_f2u(clo.w);
     const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(hm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)hm, 0u));
     const uint32_t total = (uint32_t)__builtin_popcountll(hm) * cnt;
     if (hit) {
@@ -795,7 +795,46 @@ __device__ __forceinline__ void traverse_leaves(const TravMem& M, const f4* lds,
   out_t = closest;
   out_tri = best_tri;
   out_any = best_tri != -1;
-  out_inst = out_any ? (int32_t)inst0 : -1;
+}
+template <bool ANY, int MODE, bool ONE_LOOP>
+__device__ __forceinline__ void traverse_leaves(const TravMem& M, const f4* lds, const WaveWork& W, const LeafSweep& L,
+                                                uint32_t blas_base, bool active, rt3 o, rt3 d, float t_max, float& out_t,
+                                                int32_t& out_tri, int32_t& out_inst, bool& out_any) {
+  static_assert(MODE == RT_TRAV_LDS, "the leaf sweep is a one-leaf LDS form");
+  const uint32_t lane = threadIdx.x & 63u;
+  out_t = t_max;
+  out_tri = -1;
+  out_inst = -1;
+  out_any = false;
+  // node 0, the TLAS leaf: a miss ends the walk, a hit enters the one instance
+  const f4 lo0 = ld_l(lds, M.l_nodes), hi0 = ld_l(lds, M.l_nodes + 1u);
+  const LocalRay rw = make_ray(o, d);
+  const bool walking = active && blas_base != 0u && hit_box4(lo0, hi0, rw.inv_d, rw.o_inv_d, M.t_min, t_max);
+  if (__builtin_amdgcn_ballot_w64(walking) == 0ull) return;
+  const uint32_t inst0 = __builtin_amdgcn_readfirstlane(rt_f2u(hi0.w) >> 3);
+  uint32_t root_;
+  const LocalRay q = to_instance<MODE>(M, lds, inst0, o, d, root_);
+  const bool finite = rt_finite3(q.inv_d) && rt_finite3(q.o_inv_d);
+  const bool cold = L.guard || __builtin_amdgcn_ballot_w64(walking && !finite) != 0ull;   // wave-uniform
+  RT_LSTAT(9, walking);
+  RT_LSTAT(10, walking && cold);
+  RT_LSTAT(11, walking && !finite);
+  if (walking) {
+    f4 ra, rb;
+    ra.x = q.o.x; ra.y = q.o.y; ra.z = q.o.z; ra.w = t_max;   // .w: the bound the lane's items are tested against
+    rb.x = q.d.x; rb.y = q.d.y; rb.z = q.d.z; rb.w = 0.0f;    // .w (any hit): non-zero once an item of the lane was accepted
+    W.rays[2 * lane] = ra;
+    W.rays[2 * lane + 1] = rb;
+  }
+  const rt_cptr leaves = (rt_cptr)L.recs, nodes = leaves + 2u * (L.n_leaves + 1u);
+  if (ONE_LOOP)
+    sweep_records<ANY, RT_SWEEP_EITHER>(M, lds, W, cold ? nodes : leaves, cold ? L.n_nodes : L.n_leaves, walking, q.inv_d,
+                                        q.o_inv_d, t_max, out_t, out_tri, out_any);
+  else if (cold)
+    sweep_records<ANY, RT_SWEEP_NODES>(M, lds, W, nodes, L.n_nodes, walking, q.inv_d, q.o_inv_d, t_max, out_t, out_tri, out_any);
+  else
+    sweep_records<ANY, RT_SWEEP_LEAVES>(M, lds, W, leaves, L.n_leaves, walking, q.inv_d, q.o_inv_d, t_max, out_t, out_tri, out_any);
+  if (!ANY) out_inst = out_any ? (int32_t)inst0 : -1;
 }
 
 }  // namespace rtk

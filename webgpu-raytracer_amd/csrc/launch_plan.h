@@ -35,8 +35,9 @@ struct PlanKnobs {
   bool plain_materials = true;   // MI355RT_PLAIN_MATERIALS=0: a scene of plain materials runs the generic wide form all the same
   bool leaf_sweep = true;        // MI355RT_LEAF_SWEEP=0: a sweepable one-leaf scene keeps the node walk in the wide forms all the same
   uint32_t leaf_sweep_cap = 16;  // the most BLAS leaves a scene may have and still be swept (scene_facts.h walk_facts)
-  bool leaf_sweep_guard = false; // MI355RT_LEAF_SWEEP_GUARD=1 (test hook): every walk of a sweep form takes its node-walk branch,
-                                 // the one a ray with a non-finite slab operand sends its wave to
+  bool leaf_sweep_guard = false; // MI355RT_LEAF_SWEEP_GUARD=1 (test hook): every walk of a sweep form sweeps the node records
+                                 // instead of the leaf records (k_traverse.hip.h traverse_leaves), as the wave of a ray with
+                                 // a non-finite slab operand does
 };
 // What the host knows of the uploaded scene's materials (scene_facts.h works it out from the bytes of a topology upload).
 // plain: every triangle is Lambertian or a light, untextured, and emits only if it is a light.  known = false: the host has

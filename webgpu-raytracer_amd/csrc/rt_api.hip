@@ -260,7 +260,8 @@ struct rt_ctx {
   std::vector<uint32_t> inst_root_host;    // empty: not kept
   lp::WalkFacts walk;                      // of the nodes and instances on the device, once walk_dirty is cleared
   bool walk_dirty = true;
-  DeviceBuffer leaf_recs;                  // walk.n_leaves + 1 records of 32 bytes
+  uint32_t walk_nodes = 0;                 // nodes of the sweepable BLAS, leaves included (walk.sweepable only)
+  DeviceBuffer leaf_recs;                  // walk.n_leaves + 1 leaf records of 32 bytes, then walk_nodes + 1 node records
   DeviceBuffer ticket;    // tile ticket counter of the persistent kernel
   DeviceBuffer slots;     // DevFrameSlot table of the current (batched) dispatch
   // pinned staging ring for the slot tables: the H2D copy of a dispatch's table is truly asynchronous and its source
@@ -643,6 +644,7 @@ void walk_forget(rt_ctx* c) {
   c->blas_host.clear();
   c->inst_root_host.clear();
   c->walk = lp::WalkFacts();
+  c->walk_nodes = 0;
   c->walk_dirty = true;
 }
 
@@ -651,6 +653,7 @@ void walk_forget(rt_ctx* c) {
 static int walk_prepare(rt_ctx* c) {
   if (!c->walk_dirty) return RT_OK;
   c->walk = lp::WalkFacts();
+  c->walk_nodes = 0;
   c->walk_dirty = false;
   if (c->nodes_from_device || c->blas_offset != 1u || c->blas_host.empty() ||
       c->blas_host.size() != (size_t)c->n_nodes - c->blas_offset || c->inst_root_host.size() != c->n_instances)
@@ -658,16 +661,24 @@ static int walk_prepare(rt_ctx* c) {
   const uint32_t word = c->tlas0_host.data;   // the TLAS leaf: instance << 3 | 1 (k_validate_scene has seen the device's copy)
   const uint32_t inst = word >> 3;
   if (word == 0u || inst >= c->n_instances) return RT_OK;
-  scene_facts::LeafRecord recs[scene_facts::kMaxLeafRecords + 1];
+  // the leaf records, their padding, the node records, their padding: one buffer (traverse_leaves finds the second array
+  // behind the first)
+  scene_facts::LeafRecord recs[scene_facts::kMaxLeafRecords + 1 + scene_facts::kMaxNodeRecords + 1];
+  scene_facts::NodeRecord nodes[scene_facts::kMaxNodeRecords];
+  uint32_t n_nodes = 0;
   const lp::WalkFacts f = scene_facts::walk_facts(c->blas_host.data(), c->blas_host.size(), c->inst_root_host[inst],
-                                                  c->knobs.leaf_sweep_cap, recs);
+                                                  c->knobs.leaf_sweep_cap, recs, nodes, &n_nodes);
   if (f.known && f.sweepable) {
-    recs[f.n_leaves] = recs[f.n_leaves - 1u];   // the record the sweep reads ahead at its last leaf, and does not use
-    const size_t bytes = ((size_t)f.n_leaves + 1) * sizeof(scene_facts::LeafRecord);
+    // (each sweep reads one record ahead at its last one, and does not use it)
+    recs[f.n_leaves] = scene_facts::padding_record();
+    for (uint32_t i = 0; i < n_nodes; i++) recs[f.n_leaves + 1u + i] = nodes[i];
+    recs[f.n_leaves + 1u + n_nodes] = scene_facts::padding_record();
+    const size_t bytes = ((size_t)f.n_leaves + n_nodes + 2) * sizeof(scene_facts::LeafRecord);
     int r = ensure_buffer(c, c->leaf_recs, bytes, false);
     if (r < 0) return r;
     HIP_TRY(c, hipMemcpyAsync(c->leaf_recs.ptr, recs, bytes, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));   // the source is on the stack
+    c->walk_nodes = n_nodes;
   }
   c->walk = f;
   return RT_OK;
@@ -4238,6 +4249,8 @@ static int compute_frames(rt_ctx* c, const uint32_t* frame_counts, uint32_t n, u
     lp::PersistentShape shape = lp::persistent_shape(size, c->knobs, n, c->detailed_counters, c->facts, c->walk);
     if (shape.one_inst && c->world_rec_dirty) return fail(c, RT_ERR_INTERNAL, "one-leaf form without its world records");
     if (shape.sweep && (c->walk_dirty || !c->leaf_recs.ptr)) return fail(c, RT_ERR_INTERNAL, "sweep form without its leaf records");
+    if (shape.sweep && (c->walk_nodes < c->walk.n_leaves || c->walk_nodes > scene_facts::kMaxNodeRecords))
+      return fail(c, RT_ERR_INTERNAL, "sweep form without its node records");
     const void* fn = shape.sweep      ? pt_sweep_fns[shape.plain]
                      : shape.plain    ? pt_plain_fn
                      : shape.wide     ? pt_wide_fn
@@ -4251,7 +4264,7 @@ static int compute_frames(rt_ctx* c, const uint32_t* frame_counts, uint32_t n, u
     uint32_t nn = c->n_nodes, nt = c->n_tris, ni = c->n_instances, nv = c->n_verts, ns = n;
     // (the two sweep forms read two parameters more; the others have no such parameters and are not handed them)
     const float4* leaf_recs = (const float4*)c->leaf_recs.ptr;
-    uint32_t leaf_info = c->walk.n_leaves | (c->knobs.leaf_sweep_guard ? 0x80000000u : 0u);
+    uint32_t leaf_info = c->walk.n_leaves | (c->walk_nodes << 16) | (c->knobs.leaf_sweep_guard ? 0x80000000u : 0u);
     void* args[] = {&S, &F, &c->uniforms, &ticket, &nn, &nt, &ni, &nv, &dslots, &ns, &shape.plan, &leaf_recs, &leaf_info};
     ev = next_events(c, RT_TIMER_PATHTRACE);
     if (ev) HIP_TRY(c, hipEventRecord(ev->a, c->stream));

@@ -82,11 +82,35 @@ struct LeafRecord {
 static_assert(sizeof(LeafRecord) == 32, "a leaf record is a node's 32 bytes");
 constexpr uint32_t kMaxLeafRecords = 64;   // what `out` of walk_facts must hold: no cap above it is honoured
 
+// One node as the node sweep of traverse_leaves reads it (the walk a wave takes when the nesting argument above does not
+// cover one of its rays): every node of the root's subtree in array order, which on a sweepable tree is the walk's order.  A
+// leaf's record is its LeafRecord.  An inner node's has a zero word, which no leaf has, and in place of the skip the end of
+// its subtree as a position in this array: where a ray that misses the box goes on.
+typedef LeafRecord NodeRecord;
+// every inner node of a sweepable tree has two children or more: what `nodes` of walk_facts must hold
+constexpr uint32_t kMaxNodeRecords = 2u * kMaxLeafRecords - 1u;
+
 inline uint32_t leaf_divider(uint32_t count) { return 65536u / count + 1u; }
 
+// The record behind the last one of either array, which a sweep reads ahead and does not use.  It is no node: an inverted
+// box under a zero word whose subtree would end at position 0, before the record itself.
+inline LeafRecord padding_record() {
+  LeafRecord r;
+  for (int k = 0; k < 3; k++) {
+    r.lo[k] = 3.402823466e+38f;
+    r.hi[k] = -3.402823466e+38f;
+  }
+  r.div = 0u;
+  r.data = 0u;
+  return r;
+}
+
 // blas: the n_blas nodes of the caller's BLAS array; root: BLAS-local index of the root the one instance names.  Writes the
-// leaves in walk order to out[0 .. n_leaves) when the tree is sweepable (out holds kMaxLeafRecords).
-inline WalkFacts walk_facts(const rt_node* blas, size_t n_blas, uint32_t root, uint32_t cap, LeafRecord* out) {
+// leaves in walk order to out[0 .. n_leaves) when the tree is sweepable (out holds kMaxLeafRecords) and, when `nodes` is
+// given (it holds kMaxNodeRecords), all its nodes in walk order to nodes[0 .. *n_nodes).
+inline WalkFacts walk_facts(const rt_node* blas, size_t n_blas, uint32_t root, uint32_t cap, LeafRecord* out,
+                            NodeRecord* nodes = nullptr, uint32_t* n_nodes = nullptr) {
+  if (n_nodes) *n_nodes = 0u;
   WalkFacts f;
   if (!blas || !out || n_blas == 0 || n_blas > kMaxWalkNodes || root >= n_blas) return f;
   f.known = true;
@@ -121,6 +145,15 @@ inline WalkFacts walk_facts(const rt_node* blas, size_t n_blas, uint32_t root, u
     if (n.data == 0u) {   // inner: the first child is the next node, and a second one needs a node of its own
       if (n_end < i + 3u || depth == 64u) return f;
       open[depth++] = {n_end, i, 0u};
+      if (nodes && i - root < kMaxNodeRecords) {   // (a tree of more nodes fails a test further on)
+        NodeRecord& r = nodes[i - root];
+        for (int k = 0; k < 3; k++) {
+          r.lo[k] = n.min_b[k];
+          r.hi[k] = n.max_b[k];
+        }
+        r.div = n.skip;   // n_end - root
+        r.data = 0u;
+      }
     } else {
       if (n_end != i + 1u) return f;   // nodes behind a leaf, inside its range: never reached
       const uint32_t count = n.data & 7u;
@@ -132,6 +165,7 @@ inline WalkFacts walk_facts(const rt_node* blas, size_t n_blas, uint32_t root, u
       }
       r.div = leaf_divider(count);
       r.data = n.data;
+      if (nodes && i - root < kMaxNodeRecords) nodes[i - root] = r;
     }
     while (depth && open[depth - 1u].end == i + 1u) {
       if (open[depth - 1u].kids < 2u) return f;
@@ -139,8 +173,10 @@ inline WalkFacts walk_facts(const rt_node* blas, size_t n_blas, uint32_t root, u
     }
   }
   if (depth != 0u) return f;
+  if (nodes && (span > kMaxNodeRecords || !n_nodes)) return f;   // (unreachable for span: at most 2 * cap - 1 nodes got here)
   f.sweepable = true;
   f.n_leaves = n_leaves;
+  if (n_nodes) *n_nodes = span;
   return f;
 }
 
