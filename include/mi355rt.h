@@ -635,6 +635,86 @@ int rt_bake_reflection_device(rt_ctx* ctx, const rt_reflection_desc* desc, const
                               uint32_t seed, void* dev_chains);
 int rt_reflection_stats(rt_ctx* ctx, rt_radiance_stats* out);
 
+/* ---- probe visibility maps: "does this probe of the volume see the point it is about to light?" - the weight that keeps a
+ * probe behind a wall from lighting the room in front of it ----
+ * rt_sample_volume blends the eight surrounding probes by their trilinear weight alone, so indoors light leaks through
+ * walls.  A visibility volume (rt_volume_visibility_desc, mi355rt_layout.h) holds, per probe of an irradiance volume, an
+ * octahedral map of the mean and the mean square of the distance to the nearest surface; the sampler turns the two moments
+ * into a Chebyshev bound on the share of the probe's surroundings that lies at least as far as the point, and multiplies the
+ * trilinear weight by it (Majercik et al. 2019).  rt_bake_volume_visibility captures the maps with closest-hit ray queries;
+ * rt_sample_volume_visible is rt_sample_volume with that weight; rt_encode_volume_visibility exports bordered tiles for
+ * consumers that sample with a texture unit (csrc/k_volume_visibility.hip.h).
+ *
+ * THE VISIBILITY RULE.  All arithmetic is f32, unfused, in the order written, with rt_div / rt_rcp / rt_sqrt / rt_min / rt_max /
+ * rt_abs / rt_floor / rt_normalize of mi355rt_math.h; pack, unpack, init_rng and the jitter are THE REFLECTION RULE's.
+ *   capture    for probe p of the grid, texel t = j * size + i and sample s = 0 .. spt - 1: f = seed * spt + s (u32); pad_t =
+ *              pad_first + p * size * size + t; the position is THE VOLUME RULE's; rng_d = init_rng(pad_t ^ 0x80000000, f), jx
+ *              and jy its first two draws, px = rt_div((float)i + jx, (float)size) * 2 - 1, py alike, d = unpack(px, py).  The
+ *              sample is x = rt_min(hit.t, max_distance), hit being what rt_trace_rays returns in RT_RAYS_CLOSEST mode at
+ *              t_min = 0.001f for the ray {position, max_distance, d, pad_t}: a miss contributes max_distance, a NaN t too.
+ *              Word 0 of the texel is ((+0 + x_0) + x_1) + ... in sample order, divided (rt_div) by (float)spt unless spt ==
+ *              1; word 1 the same sum of x_s * x_s.  A map depends on (scene, desc, volume desc, seed) only - never on how the
+ *              call is cut into batches.
+ *   wrap       a tap (i, j) outside the map folds back across the octahedral edge, x first, then y: if i < 0 then i = -1 - i
+ *              and j = size - 1 - j, else if i >= size then i = 2 size - 1 - i and j = size - 1 - j; then the same for j,
+ *              mirroring i.
+ *   fetch      at a unit direction v: q = pack(v); per axis u = (q * 0.5f + 0.5f) * (float)size - 0.5f; fl = rt_floor(u); if
+ *              !(fl >= -1) then fl = -1 (a NaN u too); fl = rt_min(fl, (float)(size - 1)); i0 = (int)fl, fx = u - fl.  So
+ *              every u, finite or not, names a tap in -1 .. size - 1 and its neighbour, which the wrap puts inside the map; a
+ *              non-finite u only makes the weight fx non-finite.  The four wrapped taps t00 (i0, j0), t10, t01, t11 are read;
+ *              for each of the two words a = t00 + fx * (t10 - t00), b = t01 + fx * (t11 - t01), the result a + fy * (b - a):
+ *              a constant map fetches its constant exactly.
+ *   sample     at {position, normal}: cell, corners, the trilinear weight tri_c, validity, W, the 27 sums, the division, the
+ *              evaluation and the result layout are THE VOLUME RULE's with w_c = vis_c * tri_c in place of w_c = tri_c, the
+ *              product rounded once; the replacement by +0 for an invalid probe still comes last.  With n =
+ *              rt_normalize(normal), B = position + n * normal_bias and P_c the position of corner probe c:
+ *                e = B - P_c, len = rt_sqrt(dot(e, e)).  If !(len > 0) then vis = 1 (a NaN len too).  Otherwise (m1, m2) =
+ *                fetch(map_c, e * rt_rcp(len)); if len <= m1 then vis = 1; otherwise var = rt_abs(m1 * m1 - m2), g = len - m1,
+ *                c = rt_div(var, var + g * g), if !(c > 0) then c = +0, c = (c * c) * c, vis = rt_max(c, min_visibility).
+ *                With RT_VOLUME_VIS_BACKFACE: h = rt_normalize(P_c - position), b = (dot(h, n) + 1.0f) * 0.5f, vis = vis *
+ *                (b * b + 0.2f).  (A point exactly on a probe has no h: that corner's weight is NaN, W is, and the result is
+ *                {+0, +0, +0, +0} by the volume rule's !(W > 0).)
+ *                If crush_threshold > 0 and vis < crush_threshold then vis = rt_div((vis * vis) * vis, crush_threshold *
+ *                crush_threshold).
+ *   export     every map becomes a tile of (size + 2)^2 texels whose one-texel border is the wrapped neighbour; the tiles lie
+ *              nx per row in ny * nz rows, probe p at tile (p % nx, p / nx), in one image of nx (size + 2) by ny nz (size + 2)
+ *              texels, rows top down: RT_LIGHTMAP_F32, 8 B per texel, the words unchanged; RT_LIGHTMAP_F16, 4 B, two
+ *              rt_f32_to_f16.  RT_LIGHTMAP_RGBE8 is refused.
+ * Refusals (RT_ERR_INVALID, every message begins with "volume visibility:", checked before the context - without one the
+ * message is what rt_last_error(NULL) returns): a size that is no power of two in 4 .. 32; spt outside 1 .. 65536 (bake); a
+ * max_distance that is not finite and > 0; a normal_bias that is not finite and >= 0; min_visibility or crush_threshold
+ * outside [0, 1]; an unknown flag; a non-zero reserved word; nx * ny * nz * size * size >= 2^31; pad_first + nx * ny * nz * size
+ * * size > 2^31 (bake); a NULL array; a device array that is not 16-byte aligned; dev_out == dev_visibility for the export.
+ * The volume descriptor is checked first, by the volume's own check and with its messages.
+ * A bake has a state of its own - counter shards, an event pair per ray launch, staging - and shares only the scratch of a
+ * batch with the composed gathers: items are cut into batches of whole texels of at most RT_PROBE_BATCH_SAMPLES samples.  Its
+ * stats are an rt_ray_stats summed over the batches (kernel_ms: the ray launches only).  Sampling and export need no scene
+ * and have staging of their own.  All three leave the renderer and every other query's state, rt_ray_query_stats included,
+ * as they were.
+ *   rt_bake_volume_visibility          blocking: n * size * size texels back.  stats != NULL runs the counting kernel and
+ *                                      fills *stats.  Without a valid scene RT_ERR_NOT_READY.
+ *   rt_bake_volume_visibility_device   the same into a device-accessible array: only enqueues on the context's stream.
+ *   rt_sample_volume_visible           blocking: copies the volume, the maps and n points in, samples, copies n results out.
+ *                                      n == 0 is RT_OK; n >= 2^31 is RT_ERR_INVALID.
+ *   rt_sample_volume_visible_device    the same on device-accessible arrays: only enqueues.
+ *   rt_encode_volume_visibility        blocking: the maps into the tiled image at out; cap is its capacity in bytes.
+ *   rt_encode_volume_visibility_device the same on device-accessible arrays.  Only enqueues. */
+int rt_bake_volume_visibility(rt_ctx* ctx, const rt_volume_desc* desc, const rt_volume_visibility_desc* vis, uint32_t seed,
+                              float* out, rt_ray_stats* stats);
+int rt_bake_volume_visibility_device(rt_ctx* ctx, const rt_volume_desc* desc, const rt_volume_visibility_desc* vis, uint32_t seed,
+                                     void* dev_out);
+int rt_volume_visibility_stats(rt_ctx* ctx, rt_ray_stats* out);
+int rt_sample_volume_visible(rt_ctx* ctx, const rt_volume_desc* desc, const rt_volume_visibility_desc* vis,
+                             const rt_probe_sh9* volume, const float* visibility, const rt_gather_point* points, uint32_t n,
+                             rt_irradiance* out);
+int rt_sample_volume_visible_device(rt_ctx* ctx, const rt_volume_desc* desc, const rt_volume_visibility_desc* vis,
+                                    const void* dev_volume, const void* dev_visibility, const void* dev_points, uint32_t n,
+                                    void* dev_out);
+int rt_encode_volume_visibility(rt_ctx* ctx, const rt_volume_desc* desc, const rt_volume_visibility_desc* vis, uint32_t format,
+                                const float* visibility, void* out, size_t cap);
+int rt_encode_volume_visibility_device(rt_ctx* ctx, const rt_volume_desc* desc, const rt_volume_visibility_desc* vis,
+                                       uint32_t format, const void* dev_visibility, void* dev_out, size_t cap);
+
 /* ---- directional gathers: "which radiance arrives at this surface point, from which side?" as four spherical-harmonic
  * coefficients per colour over the hemisphere of the normal (directional lightmaps for normal-mapped surfaces) ----
  * An irradiance gather returns one colour per point, the cosine-weighted mean at the interpolated normal; a renderer that

@@ -184,6 +184,22 @@ typedef struct rt_volume_desc { /* 64 B */
   uint32_t reserved;          /* 0 */
 } rt_volume_desc;
 
+/* ---- probe visibility maps (rt_bake_volume_visibility / rt_sample_volume_visible / rt_encode_volume_visibility, mi355rt.h): a
+ * visibility volume is n = nx * ny * nz maps, probe-major in the order of the volume itself; a map is size * size texels of 8
+ * bytes {mean distance, mean squared distance} in octahedral layout, texel (i, j) at j * size + i; the stats of a bake are an
+ * rt_ray_stats ---- */
+#define RT_VOLUME_VIS_BACKFACE 1u /* flags: weight a probe down that lies behind the surface the normal belongs to */
+typedef struct rt_volume_visibility_desc { /* 32 B */
+  uint32_t size;              /* side of a probe's map, in texels: a power of two, 4 .. 32 */
+  uint32_t spt;               /* bake: samples per texel, 1 .. 65536 */
+  float max_distance;         /* finite and > 0: the t_max of every visibility ray and the clamp of every distance */
+  float normal_bias;          /* finite and >= 0: the sampled point moves this far along its normal before it looks at a probe */
+  float min_visibility;       /* in [0, 1]: the floor of the Chebyshev weight */
+  float crush_threshold;      /* in [0, 1]: weights below it are cubed and divided by its square; 0 = no crush */
+  uint32_t flags;             /* RT_VOLUME_VIS_BACKFACE; every other bit is refused */
+  uint32_t reserved;          /* 0 */
+} rt_volume_visibility_desc;
+
 /* ---- reflection probes (rt_capture_reflection / rt_filter_reflection / rt_bake_reflection, mi355rt.h): rt_probe in; a map is
  * size * size texels of 16 bytes {r, g, b, hit_fraction} in octahedral layout, texel (i, j) at j * size + i; a chain is the
  * levels 0 .. levels - 1 of one probe, level m of side size >> m, concatenated in level order; their stats are an
@@ -314,6 +330,11 @@ static_assert(sizeof(rt_volume_desc) == 64, "rt_volume_desc is 64 bytes");
 static_assert(__builtin_offsetof(rt_volume_desc, step) == 16 && __builtin_offsetof(rt_volume_desc, window) == 32 &&
                   __builtin_offsetof(rt_volume_desc, t_max) == 48 && __builtin_offsetof(rt_volume_desc, max_hit_fraction) == 56,
               "rt_volume_desc: four 16-byte rows, a dimension closing each of the first three");
+static_assert(sizeof(rt_volume_visibility_desc) == 32, "rt_volume_visibility_desc is 32 bytes");
+static_assert(__builtin_offsetof(rt_volume_visibility_desc, max_distance) == 8 &&
+                  __builtin_offsetof(rt_volume_visibility_desc, min_visibility) == 16 &&
+                  __builtin_offsetof(rt_volume_visibility_desc, flags) == 24,
+              "rt_volume_visibility_desc: two 16-byte rows, size and spt opening the first, flags and reserved closing the second");
 static_assert(sizeof(rt_reflection_desc) == 32, "rt_reflection_desc is 32 bytes");
 static_assert(__builtin_offsetof(rt_reflection_desc, size) == 0 && __builtin_offsetof(rt_reflection_desc, levels) == 4 &&
                   __builtin_offsetof(rt_reflection_desc, spt) == 8 && __builtin_offsetof(rt_reflection_desc, filter_samples) == 12 &&

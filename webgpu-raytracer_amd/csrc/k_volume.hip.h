@@ -82,8 +82,17 @@ struct VolumeSampleArgs {
   uint32_t n;               // < 2^31
 };
 
-__global__ __launch_bounds__(256)
-void k_volume_sample(VolumeSampleArgs A) {
+// no weight beside the trilinear one: k_volume_sample's.  k_volume_sample_visible (k_volume_visibility.hip.h) has another.
+struct VolumeNoWeight {
+  __device__ __forceinline__ void operator()(const rt_volume_desc&, VolumeAxis, VolumeAxis, VolumeAxis,
+                                             const float4&, const float4&, uint32_t, float (&)[8]) const {}
+};
+
+// the sampler's body for the arguments A (VolumeSampleArgs, or a record with the same members); corner_weights(D, ax, ay, az,
+// p0, p1, j, w) may scale the eight trilinear weights of lane j's point, the same in all eight lanes, after the loads are issued
+// (the three axis records go by value: handed over by reference they stayed in memory, which the compiler then put into LDS)
+template <class Args, class CornerWeights>
+__device__ __forceinline__ void volume_sample_body(const Args& A, const CornerWeights& corner_weights) {
   const uint32_t i = blockIdx.x * 32u + (threadIdx.x >> 3);
   if (i >= A.n) return;                                  // whole groups leave together
   const uint32_t j = threadIdx.x & 7u;
@@ -103,6 +112,7 @@ void k_volume_sample(VolumeSampleArgs A) {
     v[c] = A.volume[RT_VOLUME_VEC4 * (size_t)p + vec];
     w[c] = (((c & 1) ? ax.w1 : ax.w0) * ((c & 2) ? ay.w1 : ay.w0)) * ((c & 4) ? az.w1 : az.w0);
   }
+  corner_weights(D, ax, ay, az, p0, p1, j, w);
   float W = 0.0f;
 #pragma unroll
   for (int c = 0; c < 8; c++) {
@@ -145,6 +155,9 @@ void k_volume_sample(VolumeSampleArgs A) {
     A.out[i] = any ? make_float4(rt_max(0.0f, E[0]), rt_max(0.0f, E[1]), rt_max(0.0f, E[2]), W)
                    : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
 }
+
+__global__ __launch_bounds__(256)
+void k_volume_sample(VolumeSampleArgs A) { volume_sample_body(A, VolumeNoWeight()); }
 
 // The export for consumers that upload 3D textures: n probe-major records into 7 layers of n texels, layer j holding the
 // floats 4 j .. 4 j + 3 of each record.  One thread per (probe, vector), the probe fastest, so a wave writes one run of a

@@ -48,6 +48,10 @@
 //   k_reflection.hip.h        k_reflection_rays / _texels: octahedral rays per (texel, sample) in front of k_radiance_query and
 //                             the texel mean behind it; k_reflection_filter: the GGX-filtered chain of a map, one wave per
 //                             output texel; k_reflection_copy (rt_capture_reflection, rt_filter_reflection, rt_bake_reflection)
+//   k_volume_visibility.hip.h k_visibility_rays / _texels: octahedral rays per (texel, sample) in front of k_ray_query and the
+//                             distance moments behind it; k_volume_sample_visible: the sampler with a Chebyshev weight per
+//                             corner; k_visibility_tiles: bordered tiles (rt_bake_volume_visibility, rt_sample_volume_visible,
+//                             rt_encode_volume_visibility)
 //   k_texture_post.hip.h      k_resize_texture; k_postprocess = PostProcess.wgsl `main` (:103-176)
 //   k_validate.hip.h          k_validate_scene: every index the kernels follow, checked once per upload
 //   k_stripes.hip.h           k_pack_stripes / k_unpack_stripes: the copies of the sharded image's gather
@@ -88,6 +92,7 @@
 #include "k_encode.hip.h"
 #include "k_volume.hip.h"
 #include "k_reflection.hip.h"
+#include "k_volume_visibility.hip.h"
 #include "k_wavefront.hip.h"
 #include "k_rayquery.hip.h"
 #include "k_texture_post.hip.h"

@@ -147,6 +147,14 @@ struct ReflectionState {
   DeviceBuffer probes, maps, chains;
 };
 
+// What probe visibility maps (rt_bake_volume_visibility, rt_sample_volume_visible, rt_encode_volume_visibility) keep between
+// calls, kept and grown: the staged maps, volume, points, results and tiles of the host entries.  The counter shards and the
+// event pairs of a bake's ray launches live in a QueryState of their own (rt_ctx::vv); the scratch of a batch is the composed
+// gathers'.
+struct VisibilityState {
+  DeviceBuffer maps, volume, points, out, encoded;
+};
+
 }  // namespace
 
 struct rt_ctx {
@@ -328,6 +336,11 @@ struct rt_ctx {
   QueryState rf;
   rt_radiance_stats rf_last = {};
   ReflectionState rfl;
+  // probe visibility maps: their ray launches count and time on a state of their own, so rt_ray_query_stats keeps reporting
+  // the caller's last rt_trace_rays; the scratch of a batch is pr_rays / pr_rad (an rt_ray_hit is 16 bytes, like an rt_radiance)
+  QueryState vv;
+  rt_ray_stats vv_last = {};
+  VisibilityState vis;
 
   // kernel timing
   bool timing = false;
@@ -2145,9 +2158,14 @@ static const void* const rq_fns[5][2][2] = {RT_RQ_FNS(rtk::RT_RQ_NODE_LDS), RT_R
                                             RT_RQ_FNS(rtk::RT_RQ_PAIR_LDS), RT_RQ_FNS(rtk::RT_RQ_PAIR_GLOBAL)};
 #undef RT_RQ_FNS
 
-// Enqueue one query on the context's stream: n > 0 rays at d_rays, results to d_out (device pointers).
-static int launch_ray_query(rt_ctx* c, const void* d_rays, uint32_t n, int mode, float t_min, void* d_out, bool detail) {
-  int r = query_scene_ready(c, "ray query", false);
+// Enqueue one query on the context's stream: n > 0 rays at d_rays, results to d_out (device pointers), on the state q and the
+// last stats `last` of the kind that asks (`what`: the prefix of its messages).  keep_counts: a later launch of the same call,
+// whose counters add to those of the launches before it.  batch_ev: the launch records into this pair, which its caller
+// keeps count of, instead of the state's own.
+static int launch_ray_query_on(rt_ctx* c, QueryState& q, rt_ray_stats& last, const char* what, const void* d_rays, uint32_t n,
+                               int mode, float t_min, void* d_out, bool detail, bool keep_counts = false,
+                               EventPair* batch_ev = nullptr) {
+  int r = query_scene_ready(c, what, false);
   if (r < 0) return r;
   lp::TraceShape shape = lp::trace_shape(scene_size(c), c->knobs, 0);
   shape.plan.troot = c->troot;
@@ -2156,10 +2174,10 @@ static int launch_ray_query(rt_ctx* c, const void* d_rays, uint32_t n, int mode,
   if ((r = resident_blocks(c, fn, 256, shape.dyn, &per_cu)) < 0) return r;
   const uint32_t blocks = grid_blocks(c, per_cu, c->knobs.wf_blocks_per_cu, (n + 255u) / 256u);
   if (getenv("MI355RT_DEBUG_SHAPE"))
-    fprintf(stderr, "[mi355rt] ray query: %s walk, form %d, %zu bytes of LDS, resident workgroups per CU %d, %u workgroups\n",
+    fprintf(stderr, "[mi355rt] %s: %s walk, form %d, %zu bytes of LDS, resident workgroups per CU %d, %u workgroups\n", what,
             shape.pairs ? "pair" : "node", shape.rq_form, shape.dyn, per_cu, blocks);
   rtk::RayQueryArgs A;
-  if ((r = query_reset_counters(c, c->rq, &A.counters, &A.head)) < 0) return r;
+  if ((r = query_reset_counters(c, q, &A.counters, &A.head, keep_counts)) < 0) return r;
   A.rays = (const float4*)d_rays;
   A.out = (uint4*)d_out;
   A.n_rays = n;
@@ -2170,15 +2188,18 @@ static int launch_ray_query(rt_ctx* c, const void* d_rays, uint32_t n, int mode,
   A.n_inst = c->n_instances;
   DevScene S = dev_scene(c);
   void* args[] = {&S, &A, &shape.nplan, &shape.plan};
-  c->rq.timed = false;
-  if ((r = query_launch(c, c->rq.ev, fn, blocks, args, shape.dyn)) < 0) return r;
-  c->rq.timed = c->timing;
-  c->rq_last = rt_ray_stats();
-  c->rq_last.walk = shape.pairs ? 1u : 0u;
-  c->rq_last.lds = shape.trace_lds ? 1u : 0u;
-  c->rq_last.rayreg = shape.rq_form == rtk::RT_RQ_NODE_RAYREG ? 1u : 0u;
-  c->rq_last.workgroups = blocks;
+  q.timed = false;
+  if ((r = query_launch(c, batch_ev ? *batch_ev : q.ev, fn, blocks, args, shape.dyn)) < 0) return r;
+  q.timed = c->timing && !batch_ev;
+  last = rt_ray_stats();
+  last.walk = shape.pairs ? 1u : 0u;
+  last.lds = shape.trace_lds ? 1u : 0u;
+  last.rayreg = shape.rq_form == rtk::RT_RQ_NODE_RAYREG ? 1u : 0u;
+  last.workgroups = blocks;
   return RT_OK;
+}
+static int launch_ray_query(rt_ctx* c, const void* d_rays, uint32_t n, int mode, float t_min, void* d_out, bool detail) {
+  return launch_ray_query_on(c, c->rq, c->rq_last, "ray query", d_rays, n, mode, t_min, d_out, detail);
 }
 
 static int ray_query_args_ok(rt_ctx* c, uint32_t n, int mode, float t_min) {
@@ -2188,18 +2209,20 @@ static int ray_query_args_ok(rt_ctx* c, uint32_t n, int mode, float t_min) {
   return RT_OK;
 }
 
-int rt_ray_query_stats(rt_ctx* c, rt_ray_stats* out) {
+// the stats of the last call of a kind that launches k_ray_query on the state q
+static int ray_query_stats_of(rt_ctx* c, const QueryState& q, const rt_ray_stats& last, rt_ray_stats* out) {
   if (!c || !out) return RT_ERR_INVALID;
   HIP_TRY(c, hipSetDevice(c->device));
-  *out = c->rq_last;
+  *out = last;
   uint64_t sum[6];
-  const int r = query_totals(c, c->rq, c->rq_last.workgroups != 0, sum, &out->kernel_ms);
+  const int r = query_totals(c, q, last.workgroups != 0, sum, &out->kernel_ms);
   if (r < 0) return r;
   out->rays += sum[1] + sum[2];
   out->nodes_visited += sum[3];
   out->tris_tested += sum[4];
   return RT_OK;
 }
+int rt_ray_query_stats(rt_ctx* c, rt_ray_stats* out) { return c ? ray_query_stats_of(c, c->rq, c->rq_last, out) : RT_ERR_INVALID; }
 
 int rt_trace_rays_device(rt_ctx* c, const void* dev_rays, uint32_t n, int mode, float t_min, void* dev_out) {
   if (!c) return RT_ERR_INVALID;
@@ -4064,6 +4087,241 @@ int rt_filter_reflection(rt_ctx* c, const rt_reflection_desc* desc, const float*
 int rt_bake_reflection(rt_ctx* c, const rt_reflection_desc* desc, const rt_probe* probes, uint32_t n, uint32_t max_depth,
                        uint32_t seed, float* out_chains, rt_radiance_stats* stats) {
   return reflection_from_host(c, desc, RF_CAPTURE | RF_FILTER, probes, nullptr, n, max_depth, seed, out_chains, stats);
+}
+
+// ---- probe visibility maps (mi355rt.h "THE VISIBILITY RULE"; k_volume_visibility.hip.h): per probe of an irradiance volume an
+// octahedral map of distance moments, captured through the ray query's kernel, one ray per (texel, sample); a sampler that
+// weights each corner by a Chebyshev bound from them; the export into bordered tiles.
+static const char* const kVisibility = "volume visibility";
+// a refusal that needs no context: without one the message is what rt_last_error(NULL) returns
+static int visibility_fail(rt_ctx* c, const std::string& msg) {
+  if (!c) g_create_error = msg;
+  return fail(c, RT_ERR_INVALID, msg);
+}
+enum { VV_BAKE = 1 };
+// everything the limits say about the two descriptors, for the parts (VV_*) an entry runs; *n_out = nx * ny * nz
+static int visibility_desc_ok(rt_ctx* c, const rt_volume_desc* d, const rt_volume_visibility_desc* v, int parts, uint32_t* n_out) {
+  int r = volume_desc_ok(c, d, n_out);
+  if (r < 0) return r;
+  const std::string w(kVisibility);
+  if (!v) return visibility_fail(c, w + ": NULL descriptor");
+  if (v->size < 4 || v->size > 32 || (v->size & (v->size - 1u))) return visibility_fail(c, w + ": size must be a power of two in 4 .. 32");
+  if ((parts & VV_BAKE) && (v->spt == 0 || v->spt > 65536)) return visibility_fail(c, w + ": spt must be 1 .. 65536");
+  if (!(std::isfinite(v->max_distance) && v->max_distance > 0.0f)) return visibility_fail(c, w + ": max_distance must be finite and > 0");
+  if (!(std::isfinite(v->normal_bias) && v->normal_bias >= 0.0f)) return visibility_fail(c, w + ": normal_bias must be finite and >= 0");
+  if (!(v->min_visibility >= 0.0f && v->min_visibility <= 1.0f)) return visibility_fail(c, w + ": min_visibility must be in [0, 1]");
+  if (!(v->crush_threshold >= 0.0f && v->crush_threshold <= 1.0f)) return visibility_fail(c, w + ": crush_threshold must be in [0, 1]");
+  if (v->flags & ~RT_VOLUME_VIS_BACKFACE) return visibility_fail(c, w + ": unknown flags");
+  if (v->reserved) return visibility_fail(c, w + ": reserved must be 0");
+  const uint64_t texels = (uint64_t)*n_out * v->size * v->size;
+  if (texels >= (1ull << 31)) return visibility_fail(c, w + ": nx * ny * nz * size * size must be below 2^31");
+  if ((parts & VV_BAKE) && (uint64_t)d->pad_first + texels > (1ull << 31))
+    return visibility_fail(c, w + ": pad_first + nx * ny * nz * size * size must be <= 2^31");
+  return RT_OK;
+}
+// the caller's arrays: there and, for the device entries, 16-byte aligned
+static int visibility_arrays_ok(rt_ctx* c, std::initializer_list<const void*> arrays, bool device) {
+  uintptr_t bits = 0;
+  for (const void* a : arrays) {
+    if (!a) return visibility_fail(c, std::string(kVisibility) + ": NULL array");
+    bits |= (uintptr_t)a;
+  }
+  if (device && (bits & 15u)) return visibility_fail(c, std::string(kVisibility) + ": device arrays must be 16-byte aligned");
+  return RT_OK;
+}
+
+// Enqueue a bake: the n * size^2 texels of the grid in batches of whole texels, each k_visibility_rays -> the ray query's
+// closest-hit kernel -> k_visibility_texels.  The reflection capture's sequence on the ray query: a probe may span batches and
+// a batch probes.
+static int launch_visibility_bake(rt_ctx* c, const rt_volume_desc& D, const rt_volume_visibility_desc& V, uint32_t n, uint32_t seed,
+                                  void* d_out, bool detail) {
+  int r = query_scene_ready(c, kVisibility, false);
+  if (r < 0) return r;
+  const uint32_t size_log2 = (uint32_t)__builtin_ctz(V.size);
+  const uint32_t spt = V.spt, total = n * V.size * V.size;      // < 2^31
+  const uint32_t per_batch = RT_PROBE_BATCH_SAMPLES / spt;      // whole texels: >= 64, spt being <= 65536
+  const size_t scratch_items = (size_t)std::min(total, per_batch) * spt;
+  static_assert(sizeof(rt_ray_hit) == sizeof(rt_radiance), "the hits of a batch live in the radiance scratch");
+  if ((r = ensure_buffer(c, c->pr_rays, scratch_items * sizeof(rt_ray), false)) < 0) return r;
+  if ((r = ensure_buffer(c, c->pr_rad, scratch_items * sizeof(rt_ray_hit), false)) < 0) return r;
+  QueryState& q = c->vv;
+  q.batches_timed = 0;
+  rt_ray_stats sum = rt_ray_stats();
+  uint32_t batch = 0;
+  for (uint32_t first = 0; first < total; first += per_batch, batch++) {
+    const uint32_t nt = std::min(per_batch, total - first);
+    const uint32_t items = nt * spt;                            // <= RT_PROBE_BATCH_SAMPLES
+    float4* rays = (float4*)c->pr_rays.ptr;
+    uint4* hits = (uint4*)c->pr_rad.ptr;
+    hipLaunchKernelGGL(rtk::k_visibility_rays, dim3((items + 255u) / 256u), dim3(256), 0, c->stream, D, rays, items, spt, seed, first,
+                       size_log2, V.max_distance);
+    HIP_TRY(c, hipGetLastError());
+    if (q.batch_ev.size() <= batch) q.batch_ev.emplace_back();
+    if ((r = launch_ray_query_on(c, q, c->vv_last, kVisibility, rays, items, RT_RAYS_CLOSEST, 0.001f, hits, detail, batch != 0,
+                                 &q.batch_ev[batch])) < 0) {
+      c->vv_last = rt_ray_stats();
+      return r;
+    }
+    if (c->timing) q.batches_timed = batch + 1;
+    sum.walk = c->vv_last.walk;
+    sum.lds = c->vv_last.lds;
+    sum.rayreg = c->vv_last.rayreg;
+    sum.workgroups += c->vv_last.workgroups;
+    hipLaunchKernelGGL(rtk::k_visibility_texels, dim3((nt + 255u) / 256u), dim3(256), 0, c->stream, (const uint4*)hits, (float2*)d_out,
+                       nt, spt, first, V.max_distance);
+    HIP_TRY(c, hipGetLastError());
+  }
+  c->vv_last = sum;
+  return RT_OK;
+}
+
+int rt_volume_visibility_stats(rt_ctx* c, rt_ray_stats* out) {
+  if (!c || !out) return RT_ERR_INVALID;
+  const int r = ray_query_stats_of(c, c->vv, c->vv_last, out);   // fences the stream; the time is that of the batches
+  if (r < 0) return r;
+  for (uint32_t b = 0; b < c->vv.batches_timed; b++) {
+    float ms = 0.0f;
+    HIP_TRY(c, hipEventElapsedTime(&ms, c->vv.batch_ev[b].a, c->vv.batch_ev[b].b));
+    out->kernel_ms += (double)ms;
+  }
+  return RT_OK;
+}
+
+int rt_bake_volume_visibility_device(rt_ctx* c, const rt_volume_desc* desc, const rt_volume_visibility_desc* vis, uint32_t seed,
+                                     void* dev_out) {
+  uint32_t n = 0;
+  int r = visibility_desc_ok(c, desc, vis, VV_BAKE, &n);
+  if (r < 0) return r;
+  if ((r = visibility_arrays_ok(c, {dev_out}, true)) < 0 || !c) return RT_ERR_INVALID;
+  if ((r = query_device_arrays_ok(c, kVisibility, dev_out, dev_out)) < 0) return r;
+  return launch_visibility_bake(c, *desc, *vis, n, seed, dev_out, c->detailed_counters);
+}
+
+int rt_bake_volume_visibility(rt_ctx* c, const rt_volume_desc* desc, const rt_volume_visibility_desc* vis, uint32_t seed, float* out,
+                              rt_ray_stats* stats) {
+  uint32_t n = 0;
+  int r = visibility_desc_ok(c, desc, vis, VV_BAKE, &n);
+  if (r < 0) return r;
+  if ((r = visibility_arrays_ok(c, {out}, false)) < 0 || !c) return RT_ERR_INVALID;
+  HIP_TRY(c, hipSetDevice(c->device));
+  const size_t bytes = (size_t)n * vis->size * vis->size * 8;
+  if ((r = ensure_buffer(c, c->vis.maps, bytes, true)) < 0) return r;
+  if ((r = launch_visibility_bake(c, *desc, *vis, n, seed, c->vis.maps.ptr, stats != nullptr)) < 0) return r;
+  HIP_TRY(c, hipMemcpyAsync(out, c->vis.maps.ptr, bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (stats) return rt_volume_visibility_stats(c, stats);
+  return RT_OK;
+}
+
+static int launch_sample_volume_visible(rt_ctx* c, const rt_volume_desc& D, const rt_volume_visibility_desc& V, const void* d_volume,
+                                        const void* d_vis, const void* d_points, uint32_t n, void* d_out) {
+  rtk::VolumeSampleVisibleArgs A;
+  A.D = D;
+  A.V = V;
+  A.volume = (const float4*)d_volume;
+  A.visibility = (const float2*)d_vis;
+  A.points = (const float4*)d_points;
+  A.out = (float4*)d_out;
+  A.n = n;
+  hipLaunchKernelGGL(rtk::k_volume_sample_visible, dim3((n + 31u) / 32u), dim3(256), 0, c->stream, A);   // 8 lanes per point
+  HIP_TRY(c, hipGetLastError());
+  return RT_OK;
+}
+
+int rt_sample_volume_visible_device(rt_ctx* c, const rt_volume_desc* desc, const rt_volume_visibility_desc* vis, const void* dev_volume,
+                                    const void* dev_visibility, const void* dev_points, uint32_t n, void* dev_out) {
+  uint32_t probes = 0;
+  int r = visibility_desc_ok(c, desc, vis, 0, &probes);
+  if (r < 0) return r;
+  if (n >= (1u << 31)) return visibility_fail(c, std::string(kVisibility) + ": too many points for one call (n must be below 2^31)");
+  if (n == 0) return c ? RT_OK : RT_ERR_INVALID;
+  if ((r = visibility_arrays_ok(c, {dev_volume, dev_visibility, dev_points, dev_out}, true)) < 0 || !c) return RT_ERR_INVALID;
+  if ((r = query_device_arrays_ok(c, kVisibility, dev_volume, dev_out)) < 0) return r;
+  if ((r = query_device_arrays_ok(c, kVisibility, dev_visibility, dev_points)) < 0) return r;
+  return launch_sample_volume_visible(c, *desc, *vis, dev_volume, dev_visibility, dev_points, n, dev_out);
+}
+
+int rt_sample_volume_visible(rt_ctx* c, const rt_volume_desc* desc, const rt_volume_visibility_desc* vis, const rt_probe_sh9* volume,
+                             const float* visibility, const rt_gather_point* points, uint32_t n, rt_irradiance* out) {
+  uint32_t probes = 0;
+  int r = visibility_desc_ok(c, desc, vis, 0, &probes);
+  if (r < 0) return r;
+  if (n >= (1u << 31)) return visibility_fail(c, std::string(kVisibility) + ": too many points for one call (n must be below 2^31)");
+  if (n == 0) return c ? RT_OK : RT_ERR_INVALID;
+  if ((r = visibility_arrays_ok(c, {volume, visibility, points, out}, false)) < 0 || !c) return RT_ERR_INVALID;
+  HIP_TRY(c, hipSetDevice(c->device));
+  VisibilityState& st = c->vis;
+  const size_t vol_bytes = (size_t)probes * sizeof(rt_probe_sh9), map_bytes = (size_t)probes * vis->size * vis->size * 8;
+  if ((r = ensure_buffer(c, st.volume, vol_bytes, true)) < 0) return r;
+  if ((r = ensure_buffer(c, st.maps, map_bytes, true)) < 0) return r;
+  if ((r = ensure_buffer(c, st.points, (size_t)n * sizeof(rt_gather_point), true)) < 0) return r;
+  if ((r = ensure_buffer(c, st.out, (size_t)n * sizeof(rt_irradiance), true)) < 0) return r;
+  HIP_TRY(c, hipMemcpyAsync(st.volume.ptr, volume, vol_bytes, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(st.maps.ptr, visibility, map_bytes, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(st.points.ptr, points, (size_t)n * sizeof(rt_gather_point), hipMemcpyHostToDevice, c->stream));
+  if ((r = launch_sample_volume_visible(c, *desc, *vis, st.volume.ptr, st.maps.ptr, st.points.ptr, n, st.out.ptr)) < 0) return r;
+  HIP_TRY(c, hipMemcpyAsync(out, st.out.ptr, (size_t)n * sizeof(rt_irradiance), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return RT_OK;
+}
+
+// bytes of the tiled image of an export
+static size_t visibility_tiles_bytes(uint32_t probes, uint32_t size, uint32_t format) {
+  return (size_t)probes * (size + 2u) * (size + 2u) * (format == RT_LIGHTMAP_F16 ? 4 : 8);
+}
+// the arguments of an export beside the descriptors: the format is f32 or f16, the capacity holds the image
+static int visibility_encode_args_ok(rt_ctx* c, uint32_t probes, uint32_t size, uint32_t format, const void* in, const void* out,
+                                     size_t cap, bool device) {
+  const std::string w(kVisibility);
+  if (format == RT_LIGHTMAP_RGBE8) return visibility_fail(c, w + ": RT_LIGHTMAP_RGBE8 cannot hold two distance moments");
+  if (format != RT_LIGHTMAP_F32 && format != RT_LIGHTMAP_F16) return visibility_fail(c, w + ": format must be RT_LIGHTMAP_F32 or _F16");
+  int r = visibility_arrays_ok(c, {in, out}, device);
+  if (r < 0) return r;
+  if (device && in == out) return visibility_fail(c, w + ": the output must not be the input");
+  if (cap < visibility_tiles_bytes(probes, size, format))
+    return visibility_fail(c, w + ": the capacity is below nx * ny * nz tiles of (size + 2)^2 texels of the format");
+  return c ? RT_OK : RT_ERR_INVALID;
+}
+static int launch_visibility_tiles(rt_ctx* c, const rt_volume_desc& D, const rt_volume_visibility_desc& V, uint32_t format,
+                                   const void* d_vis, void* d_out) {
+  rtk::VisibilityTilesArgs A;
+  A.visibility = (const float2*)d_vis;
+  A.out = d_out;
+  A.nx = D.nx;
+  A.rows = D.ny * D.nz;
+  A.size = V.size;
+  A.format = format;
+  const uint64_t texels = (uint64_t)D.nx * A.rows * (V.size + 2u) * (V.size + 2u);   // < 2^31 * 2.25
+  hipLaunchKernelGGL(rtk::k_visibility_tiles, dim3((uint32_t)((texels + 255u) / 256u)), dim3(256), 0, c->stream, A);
+  HIP_TRY(c, hipGetLastError());
+  return RT_OK;
+}
+
+int rt_encode_volume_visibility_device(rt_ctx* c, const rt_volume_desc* desc, const rt_volume_visibility_desc* vis, uint32_t format,
+                                       const void* dev_visibility, void* dev_out, size_t cap) {
+  uint32_t probes = 0;
+  int r = visibility_desc_ok(c, desc, vis, 0, &probes);
+  if (r < 0) return r;
+  if ((r = visibility_encode_args_ok(c, probes, vis->size, format, dev_visibility, dev_out, cap, true)) < 0) return r;
+  if ((r = query_device_arrays_ok(c, kVisibility, dev_visibility, dev_out)) < 0) return r;
+  return launch_visibility_tiles(c, *desc, *vis, format, dev_visibility, dev_out);
+}
+
+int rt_encode_volume_visibility(rt_ctx* c, const rt_volume_desc* desc, const rt_volume_visibility_desc* vis, uint32_t format,
+                                const float* visibility, void* out, size_t cap) {
+  uint32_t probes = 0;
+  int r = visibility_desc_ok(c, desc, vis, 0, &probes);
+  if (r < 0) return r;
+  if ((r = visibility_encode_args_ok(c, probes, vis->size, format, visibility, out, cap, false)) < 0) return r;
+  HIP_TRY(c, hipSetDevice(c->device));
+  const size_t in_bytes = (size_t)probes * vis->size * vis->size * 8, out_bytes = visibility_tiles_bytes(probes, vis->size, format);
+  if ((r = ensure_buffer(c, c->vis.maps, in_bytes, true)) < 0) return r;
+  if ((r = ensure_buffer(c, c->vis.encoded, out_bytes, true)) < 0) return r;
+  HIP_TRY(c, hipMemcpyAsync(c->vis.maps.ptr, visibility, in_bytes, hipMemcpyHostToDevice, c->stream));
+  if ((r = launch_visibility_tiles(c, *desc, *vis, format, c->vis.maps.ptr, c->vis.encoded.ptr)) < 0) return r;
+  HIP_TRY(c, hipMemcpyAsync(out, c->vis.encoded.ptr, out_bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return RT_OK;
 }
 
 // ---- the kernels of compute().  Variant 0, the one-pixel-per-lane megakernel: one tile per workgroup, no dynamic LDS.

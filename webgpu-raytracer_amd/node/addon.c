@@ -729,6 +729,85 @@ static napi_value rtEncodeVolume(napi_env env, napi_callback_info info) {
   return make_int(env, rt_encode_volume((rt_ctx*)get_ptr(env, a[0]), desc, get_u32(env, a[2]), (const rt_probe_sh9*)volume, out, no));
 }
 
+/* ------------------------------------------------------- probe visibility maps (rt_bake_volume_visibility, mi355rt.h) */
+/* the 32 bytes of an rt_volume_visibility_desc in a typed array, and the texels of one map (0: the library will refuse the size) */
+static const rt_volume_visibility_desc* get_visibility_desc(napi_env env, napi_value v, size_t* map) {
+  void* d = NULL;
+  size_t nd = 0;
+  if (!get_bytes(env, v, &d, &nd)) return NULL;
+  if (nd != sizeof(rt_volume_visibility_desc)) {
+    napi_throw_range_error(env, NULL, "a visibility descriptor is 32 bytes");
+    return NULL;
+  }
+  const rt_volume_visibility_desc* desc = (const rt_volume_visibility_desc*)d;
+  *map = desc->size > 32 ? 0 : (size_t)desc->size * desc->size;
+  return desc;
+}
+/* (ctx, desc: 64 bytes, vis: 32 bytes, seed, out: Float32Array of 2 per texel, wantStats) -> status, or the stats object */
+static napi_value rtBakeVolumeVisibility(napi_env env, napi_callback_info info) {
+  napi_value a[6];
+  void* out = NULL;
+  size_t n = 0, map = 0, no = 0;
+  bool want_stats = false;
+  if (!get_args(env, info, 6, a) || !get_bytes(env, a[4], &out, &no)) return NULL;
+  const rt_volume_desc* desc = get_volume_desc(env, a[1], &n);
+  if (!desc) return NULL;
+  const rt_volume_visibility_desc* vis = get_visibility_desc(env, a[2], &map);
+  if (!vis) return NULL;
+  napi_get_value_bool(env, a[5], &want_stats);
+  if (no < n * map * 8) {
+    napi_throw_range_error(env, NULL, "rtBakeVolumeVisibility: out must hold 2 floats per texel of every probe's map");
+    return NULL;
+  }
+  rt_ray_stats st;
+  const int rc = rt_bake_volume_visibility((rt_ctx*)get_ptr(env, a[0]), desc, vis, get_u32(env, a[3]), (float*)out,
+                                           want_stats ? &st : NULL);
+  if (rc < 0 || !want_stats) return make_int(env, rc);
+  return ray_stats_object(env, &st);
+}
+/* (ctx, desc: 64 bytes, vis: 32 bytes, volume: Float32Array of 28 per probe, visibility: Float32Array of 2 per texel, points:
+ * Float32Array of 8 per point, out: Float32Array of 4 per point) -> status */
+static napi_value rtSampleVolumeVisible(napi_env env, napi_callback_info info) {
+  napi_value a[7];
+  void *volume = NULL, *maps = NULL, *points = NULL, *out = NULL;
+  size_t n = 0, map = 0, nv = 0, nm = 0, np = 0, no = 0;
+  if (!get_args(env, info, 7, a) || !get_bytes(env, a[3], &volume, &nv) || !get_bytes(env, a[4], &maps, &nm) ||
+      !get_bytes(env, a[5], &points, &np) || !get_bytes(env, a[6], &out, &no))
+    return NULL;
+  const rt_volume_desc* desc = get_volume_desc(env, a[1], &n);
+  if (!desc) return NULL;
+  const rt_volume_visibility_desc* vis = get_visibility_desc(env, a[2], &map);
+  if (!vis) return NULL;
+  const size_t m = np / sizeof(rt_gather_point);
+  if (nv < n * sizeof(rt_probe_sh9) || nm < n * map * 8 || np % sizeof(rt_gather_point) != 0 || no < m * sizeof(rt_irradiance) ||
+      m > 0x7fffffffu) {
+    napi_throw_range_error(env, NULL, "rtSampleVolumeVisible: volume must hold 28 floats per probe, visibility 2 per texel, points 8 "
+                                      "and out 4 floats per point");
+    return NULL;
+  }
+  return make_int(env, rt_sample_volume_visible((rt_ctx*)get_ptr(env, a[0]), desc, vis, (const rt_probe_sh9*)volume,
+                                                (const float*)maps, (const rt_gather_point*)points, (uint32_t)m,
+                                                (rt_irradiance*)out));
+}
+/* (ctx, desc: 64 bytes, vis: 32 bytes, format, visibility: Float32Array of 2 per texel, out: a typed array of the tiled image)
+ * -> status */
+static napi_value rtEncodeVolumeVisibility(napi_env env, napi_callback_info info) {
+  napi_value a[6];
+  void *maps = NULL, *out = NULL;
+  size_t n = 0, map = 0, nm = 0, no = 0;
+  if (!get_args(env, info, 6, a) || !get_bytes(env, a[4], &maps, &nm) || !get_bytes(env, a[5], &out, &no)) return NULL;
+  const rt_volume_desc* desc = get_volume_desc(env, a[1], &n);
+  if (!desc) return NULL;
+  const rt_volume_visibility_desc* vis = get_visibility_desc(env, a[2], &map);
+  if (!vis) return NULL;
+  if (nm < n * map * 8) {
+    napi_throw_range_error(env, NULL, "rtEncodeVolumeVisibility: visibility must hold 2 floats per texel of every probe's map");
+    return NULL;
+  }
+  return make_int(env, rt_encode_volume_visibility((rt_ctx*)get_ptr(env, a[0]), desc, vis, get_u32(env, a[3]), (const float*)maps,
+                                                   out, no));
+}
+
 /* ------------------------------------------------------- reflection probes (rt_bake_reflection, rt_filter_reflection, mi355rt.h) */
 /* the 32 bytes of an rt_reflection_desc in a typed array, and the texels of its level 0 and of a chain (0: the library will
  * refuse the descriptor) */
@@ -1170,6 +1249,8 @@ static napi_value Init(napi_env env, napi_value exports) {
                {"rtRayQueryStats", rtRayQueryStats}, {"rtTraceRadiance", rtTraceRadiance},
                {"rtGatherIrradiance", rtGatherIrradiance}, {"rtGatherProbes", rtGatherProbes}, {"rtBakePoints", rtBakePoints},
                {"rtBakeVolume", rtBakeVolume}, {"rtSampleVolume", rtSampleVolume}, {"rtEncodeVolume", rtEncodeVolume},
+               {"rtBakeVolumeVisibility", rtBakeVolumeVisibility}, {"rtSampleVolumeVisible", rtSampleVolumeVisible},
+               {"rtEncodeVolumeVisibility", rtEncodeVolumeVisibility},
                {"rtBakeReflection", rtBakeReflection}, {"rtFilterReflection", rtFilterReflection},
                {"rtGatherDirectional", rtGatherDirectional}, {"rtBakeAtlasDirectionalLightmap", rtBakeAtlasDirectionalLightmap},
                {"rtBakeIrradiance", rtBakeIrradiance}, {"rtBakeAtlasPoints", rtBakeAtlasPoints},

@@ -85,6 +85,21 @@ export class WebGPURenderer {
   /** Seven layers of n texels, layer j holding the floats 4 j .. 4 j + 3 of every record; 'rgbe' is refused. */
   encodeVolume(desc: Uint8Array, volume: Float32Array, format: 'f32' | 'f16'):
     { data: Float32Array | Uint16Array; layers: 7; n: number; format: string };
+  /** Probe visibility maps (rt_bake_volume_visibility / rt_sample_volume_visible / rt_encode_volume_visibility).  A descriptor
+   *  is the 32 bytes of an rt_volume_visibility_desc: maps of size x size octahedral texels {mean distance, mean squared
+   *  distance} per probe of a volume, spt samples per texel, maxDistance the length of every visibility ray. */
+  static volumeVisibilityDesc(o: { size: number; maxDistance: number; spt?: number; normalBias?: number; minVisibility?: number;
+    crushThreshold?: number; backface?: boolean }): Uint8Array;
+  /** `data` holds 2 floats per texel, probe-major, texel (i, j) of a map at j * size + i.  The stats are a ray query's, summed
+   *  over the batches. */
+  bakeVolumeVisibility(desc: Uint8Array, vis: Uint8Array, opts?: { seed?: number; stats?: boolean }):
+    { data: Float32Array; n: number; size: number; stats?: RayQueryStats };
+  /** sampleVolume with every corner probe's weight multiplied by its visibility of the point.  Needs no scene. */
+  sampleVolumeVisible(desc: Uint8Array, vis: Uint8Array, volume: Float32Array, visibility: Float32Array, points: Float32Array):
+    { data: Float32Array; n: number };
+  /** One image of bordered tiles, probe (x, y, z) at tile (x, z * ny + y), 2 channels per texel; 'rgbe' is refused. */
+  encodeVolumeVisibility(desc: Uint8Array, vis: Uint8Array, visibility: Float32Array, format: 'f32' | 'f16'):
+    { data: Float32Array | Uint16Array; width: number; height: number; tile: number; format: string };
   /** Reflection probes (rt_bake_reflection / rt_filter_reflection).  A descriptor is the 32 bytes of an rt_reflection_desc:
    *  level 0 of size x size octahedral texels {r, g, b, hitFraction}, `levels` levels with level m of side size >> m,
    *  GGX-filtered at the roughness m / (levels - 1); spt samples per texel of a capture, filterSamples lobe samples per texel. */

@@ -262,6 +262,57 @@ class WebGPURenderer {
     this._check(native.rtEncodeVolume(this._ctx, desc, f, volume, data), 'encodeVolume');
     return { data, layers: 7, n, format: ['f32', 'f16', 'rgbe'][f] };
   }
+  // ---- probe visibility maps (rt_bake_volume_visibility, rt_sample_volume_visible, rt_encode_volume_visibility): per probe of
+  // a volume an octahedral map of size x size texels {mean distance, mean squared distance}, and the sampler that weights every
+  // corner probe by its visibility of the point, so that a probe behind a wall does not light the room in front of it.  A
+  // descriptor is the 32 bytes of an rt_volume_visibility_desc, made by WebGPURenderer.volumeVisibilityDesc({size,
+  // maxDistance, spt = 64, normalBias = 0, minVisibility = 0, crushThreshold = 0, backface = false}).
+  static volumeVisibilityDesc(o) {
+    const buf = new ArrayBuffer(32), f = new Float32Array(buf), u = new Uint32Array(buf);
+    u[0] = o.size >>> 0;
+    u[1] = (o.spt === undefined ? 64 : o.spt) >>> 0;
+    f[2] = o.maxDistance;
+    f[3] = o.normalBias || 0;
+    f[4] = o.minVisibility || 0;
+    f[5] = o.crushThreshold || 0;
+    u[6] = o.backface ? 1 : 0;
+    return new Uint8Array(buf);
+  }
+  static _visibilityTexels(desc, vis) {
+    const size = new Uint32Array(vis.buffer, vis.byteOffset, 8)[0];
+    return WebGPURenderer._volumeProbes(desc) * size * size;
+  }
+  // Result: 2 floats per texel in .data, probe-major, texel (i, j) of a map at j * size + i; .n probes, .size; opts: {seed = 0,
+  // stats = false}; the stats are a ray query's, summed over the batches.
+  bakeVolumeVisibility(desc, vis, opts = {}) {
+    const data = new Float32Array(WebGPURenderer._visibilityTexels(desc, vis) * 2);
+    const r = native.rtBakeVolumeVisibility(this._ctx, desc, vis, (opts.seed || 0) >>> 0, data, !!opts.stats);
+    if (typeof r === 'number') this._check(r, 'bakeVolumeVisibility');
+    const out = { data, n: WebGPURenderer._volumeProbes(desc), size: new Uint32Array(vis.buffer, vis.byteOffset, 8)[0] };
+    if (typeof r === 'object' && r) out.stats = r;
+    return out;
+  }
+  // sampleVolume with the visibility weight: volume and points as there, visibility the .data of a bakeVolumeVisibility.
+  sampleVolumeVisible(desc, vis, volume, visibility, points) {
+    if (!(volume instanceof Float32Array) || volume.length !== WebGPURenderer._volumeProbes(desc) * 28) throw new TypeError('sampleVolumeVisible: a Float32Array of 28 floats per probe');
+    if (!(visibility instanceof Float32Array) || visibility.length !== WebGPURenderer._visibilityTexels(desc, vis) * 2) throw new TypeError('sampleVolumeVisible: a Float32Array of 2 floats per texel of every map');
+    if (!(points instanceof Float32Array) || points.length % 8 !== 0) throw new TypeError('sampleVolumeVisible: a Float32Array of 8 floats per point');
+    const n = points.length / 8;
+    const data = new Float32Array(n * 4);
+    this._check(native.rtSampleVolumeVisible(this._ctx, desc, vis, volume, visibility, points, data), 'sampleVolumeVisible');
+    return { data, n };
+  }
+  // The maps as one image of bordered tiles, probe (x, y, z) at tile (x, z * ny + y), each (size + 2)^2 texels with the wrapped
+  // neighbours as its border: format 'f32' or 'f16' ('rgbe' is refused).  Result: {data, width, height, tile, format}.
+  encodeVolumeVisibility(desc, vis, visibility, format) {
+    if (!(visibility instanceof Float32Array) || visibility.length !== WebGPURenderer._visibilityTexels(desc, vis) * 2) throw new TypeError('encodeVolumeVisibility: a Float32Array of 2 floats per texel of every map');
+    const f = WebGPURenderer._lightmapFormat(format);
+    const u = new Uint32Array(desc.buffer, desc.byteOffset, 16), tile = new Uint32Array(vis.buffer, vis.byteOffset, 8)[0] + 2;
+    const width = u[3] * tile, height = u[7] * u[11] * tile;
+    const data = f === 1 ? new Uint16Array(width * height * 2) : new Float32Array(width * height * 2);
+    this._check(native.rtEncodeVolumeVisibility(this._ctx, desc, vis, f, visibility, data), 'encodeVolumeVisibility');
+    return { data, width, height, tile, format: ['f32', 'f16', 'rgbe'][f] };
+  }
   // ---- reflection probes (rt_bake_reflection, rt_filter_reflection): octahedral radiance maps of size x size texels {r, g, b,
   // hitFraction} and their GGX-filtered chains, level m of side size >> m at the roughness m / (levels - 1).  A descriptor is
   // the 32 bytes of an rt_reflection_desc, made by WebGPURenderer.reflectionDesc({size, levels, spt = 1, filterSamples = 256}).

@@ -216,6 +216,14 @@ def load_library(path=None):
         "rt_bake_reflection": (i32, [vp, vp, vp, u32, u32, u32, vp, vp]),
         "rt_bake_reflection_device": (i32, [vp, vp, vp, u32, u32, u32, vp]),
         "rt_reflection_stats": (i32, [vp, vp]),
+        # probe visibility maps
+        "rt_bake_volume_visibility": (i32, [vp, vp, vp, u32, vp, vp]),
+        "rt_bake_volume_visibility_device": (i32, [vp, vp, vp, u32, vp]),
+        "rt_volume_visibility_stats": (i32, [vp, vp]),
+        "rt_sample_volume_visible": (i32, [vp, vp, vp, vp, vp, vp, u32, vp]),
+        "rt_sample_volume_visible_device": (i32, [vp, vp, vp, vp, vp, vp, u32, vp]),
+        "rt_encode_volume_visibility": (i32, [vp, vp, vp, u32, vp, vp, ctypes.c_size_t]),
+        "rt_encode_volume_visibility_device": (i32, [vp, vp, vp, u32, vp, vp, ctypes.c_size_t]),
         # directional gathers
         "rt_gather_directional": (i32, [vp, vp, u32, u32, u32, u32, vp, vp]),
         "rt_gather_directional_device": (i32, [vp, vp, u32, u32, u32, u32, vp]),
@@ -280,6 +288,8 @@ EXPORTED_SYMBOLS = (
     "rt_bake_volume rt_bake_volume_device rt_sample_volume rt_sample_volume_device rt_encode_volume rt_encode_volume_device "
     "rt_capture_reflection rt_capture_reflection_device rt_filter_reflection rt_filter_reflection_device rt_bake_reflection "
     "rt_bake_reflection_device rt_reflection_stats "
+    "rt_bake_volume_visibility rt_bake_volume_visibility_device rt_volume_visibility_stats rt_sample_volume_visible "
+    "rt_sample_volume_visible_device rt_encode_volume_visibility rt_encode_volume_visibility_device "
     "rt_gather_directional rt_gather_directional_device rt_directional_gather_stats "
     "rt_bake_points rt_bake_points_device rt_bake_irradiance "
     "rt_bake_atlas_points rt_bake_atlas_points_device rt_bake_atlas_irradiance "
@@ -382,6 +392,41 @@ def _volume_desc(desc):
     if d.dtype != VOLUME_DESC_DTYPE or d.size != 1:
         raise ValueError("a volume descriptor is one VOLUME_DESC_DTYPE record (volume_desc builds it)")
     return d.reshape(())
+
+
+# probe visibility maps: mirror of rt_volume_visibility_desc; a visibility volume is (nz, ny, nx, size, size, 2) float32 {mean
+# distance, mean squared distance}, a map in octahedral layout, texel (i, j) at [j, i]
+RT_VOLUME_VIS_BACKFACE = 1
+VOLUME_VISIBILITY_DESC_DTYPE = np.dtype([("size", np.uint32), ("spt", np.uint32), ("max_distance", np.float32),
+                                         ("normal_bias", np.float32), ("min_visibility", np.float32),
+                                         ("crush_threshold", np.float32), ("flags", np.uint32), ("reserved", np.uint32)])
+
+
+def volume_visibility_desc(size, max_distance, spt=64, normal_bias=0.0, min_visibility=0.0, crush_threshold=0.0, backface=False):
+    """A VOLUME_VISIBILITY_DESC_DTYPE record (shape ()): maps of size x size texels (a power of two in 4 .. 32) baked at spt
+    samples per texel; max_distance is the t_max of every visibility ray and the clamp of every distance - the diagonal of a
+    cell, or a little more, is the usual choice.  The sampler moves a point normal_bias along its normal before it looks at a
+    probe, never lets the Chebyshev weight fall below min_visibility, cubes weights below crush_threshold (0 = none), and with
+    backface weights a probe down that lies behind the surface."""
+    d = np.zeros((), VOLUME_VISIBILITY_DESC_DTYPE)
+    d["size"], d["spt"], d["max_distance"], d["normal_bias"] = size, spt, max_distance, normal_bias
+    d["min_visibility"], d["crush_threshold"] = min_visibility, crush_threshold
+    d["flags"] = RT_VOLUME_VIS_BACKFACE if backface else 0
+    return d
+
+
+def _volume_visibility_desc(desc):
+    d = np.ascontiguousarray(desc)
+    if d.dtype != VOLUME_VISIBILITY_DESC_DTYPE or d.size != 1:
+        raise ValueError("a visibility descriptor is one VOLUME_VISIBILITY_DESC_DTYPE record (volume_visibility_desc builds it)")
+    return d.reshape(())
+
+
+def _visibility_maps(d, v, visibility, who):
+    m = np.ascontiguousarray(visibility, dtype=np.float32)
+    if m.size != 2 * int(d["nx"]) * int(d["ny"]) * int(d["nz"]) * int(v["size"]) ** 2:
+        raise ValueError("%s: the visibility volume does not hold nx * ny * nz maps of size * size texels" % who)
+    return m
 
 
 # reflection probes: mirror of rt_reflection_desc; a map is (size, size, 4) float32 {r, g, b, hit_fraction} in octahedral layout,
@@ -1149,6 +1194,76 @@ class WebGPURenderer:
         for m in range(int(d["levels"])):
             side = int(d["size"]) >> m
             out.append(self.encodeAtlas(c[off[m]:off[m + 1]].reshape(side, side, 4), format))
+        return out
+
+    # ---- probe visibility maps: distance moments per probe of a volume, and the sampler they keep from leaking light ----
+    def bakeVolumeVisibility(self, desc, vis, seed=0, stats=False):
+        """desc: the VOLUME_DESC_DTYPE record of the volume; vis: a VOLUME_VISIBILITY_DESC_DTYPE record
+        (volume_visibility_desc).  Returns the visibility volume, (nz, ny, nx, size, size, 2) float32 {mean distance, mean
+        squared distance} - and with stats=True the pair (maps, rt_ray_stats dict summed over the batches: the counting kernel
+        runs).  rayQueryStats keeps reporting the last traceRays."""
+        d, v = _volume_desc(desc), _volume_visibility_desc(vis)
+        size = int(v["size"])
+        out = np.empty((int(d["nz"]), int(d["ny"]), int(d["nx"]), size, size, 2), np.float32)
+        st = RtRayStats()
+        self._check(self.L.rt_bake_volume_visibility(self.ctx, _ptr(d), _ptr(v), int(seed) & 0xffffffff,
+                                                     _ptr(out) if out.size else None, ctypes.addressof(st) if stats else None),
+                    "bakeVolumeVisibility")
+        return (out, st.as_dict()) if stats else out
+
+    def bakeVolumeVisibilityDevice(self, desc, vis, out_ptr, seed=0):
+        """Enqueue a bake into the nx * ny * nz * size * size texels (8 bytes each) at the device pointer out_ptr on the
+        context's stream; no host synchronisation."""
+        d, v = _volume_desc(desc), _volume_visibility_desc(vis)
+        self._check(self.L.rt_bake_volume_visibility_device(self.ctx, _ptr(d), _ptr(v), int(seed) & 0xffffffff,
+                                                            ctypes.c_void_p(out_ptr or 0)), "bakeVolumeVisibilityDevice")
+
+    def volumeVisibilityStats(self):
+        """rt_ray_stats of the last visibility bake as a dict (blocking)."""
+        st = RtRayStats()
+        self._check(self.L.rt_volume_visibility_stats(self.ctx, ctypes.addressof(st)), "volumeVisibilityStats")
+        return st.as_dict()
+
+    def sampleVolumeVisible(self, desc, vis, volume, visibility, points):
+        """sampleVolume with every corner probe's trilinear weight multiplied by its visibility of the point (THE VISIBILITY
+        RULE): volume as for sampleVolume, visibility the array of bakeVolumeVisibility, points (n, 8) float32.  Returns an
+        IRRADIANCE_DTYPE array (n,).  Needs no scene.  Uploads the volume and the maps on every call: a caller sampling every
+        frame keeps them on the device and uses sampleVolumeVisibleDevice."""
+        d, v = _volume_desc(desc), _volume_visibility_desc(vis)
+        vol = np.ascontiguousarray(volume)
+        if vol.dtype != PROBE_SH9_DTYPE:
+            vol = np.ascontiguousarray(vol, dtype=np.float32).reshape(-1, 28)
+        if vol.size * vol.dtype.itemsize != 112 * int(d["nx"]) * int(d["ny"]) * int(d["nz"]):
+            raise ValueError("sampleVolumeVisible: the volume does not hold nx * ny * nz records")
+        m = _visibility_maps(d, v, visibility, "sampleVolumeVisible")
+        p = np.ascontiguousarray(points, dtype=np.float32)
+        if p.ndim != 2 or p.shape[1] != 8:
+            raise ValueError("sampleVolumeVisible expects an (n, 8) float32 array of points")
+        out = np.empty(p.shape[0], dtype=IRRADIANCE_DTYPE)
+        self._check(self.L.rt_sample_volume_visible(self.ctx, _ptr(d), _ptr(v), _ptr(vol), _ptr(m), _ptr(p) if p.size else None,
+                                                    p.shape[0], _ptr(out) if out.size else None), "sampleVolumeVisible")
+        return out
+
+    def sampleVolumeVisibleDevice(self, desc, vis, volume_ptr, visibility_ptr, points_ptr, n, out_ptr):
+        """Enqueue the sampling of n rt_gather_point at points_ptr from the volume at volume_ptr and the maps at visibility_ptr
+        into n rt_irradiance at out_ptr (device pointers, 16-byte aligned) on the context's stream; no host synchronisation."""
+        d, v = _volume_desc(desc), _volume_visibility_desc(vis)
+        self._check(self.L.rt_sample_volume_visible_device(self.ctx, _ptr(d), _ptr(v), ctypes.c_void_p(volume_ptr or 0),
+                                                           ctypes.c_void_p(visibility_ptr or 0), ctypes.c_void_p(points_ptr or 0),
+                                                           int(n), ctypes.c_void_p(out_ptr or 0)), "sampleVolumeVisibleDevice")
+
+    def encodeVolumeVisibility(self, desc, vis, visibility, format):
+        """The maps as one image of bordered tiles for a 2D-texture upload: (ny * nz * (size + 2), nx * (size + 2), 2) float32
+        ("f32") or float16 ("f16"), probe (x, y, z) at tile (x, z * ny + y), a tile's border the wrapped neighbour texel.
+        "rgbe" is refused."""
+        d, v = _volume_desc(desc), _volume_visibility_desc(vis)
+        m = _visibility_maps(d, v, visibility, "encodeVolumeVisibility")
+        fmt = _lightmap_format(format)
+        tile = int(v["size"]) + 2
+        out = np.empty((int(d["ny"]) * int(d["nz"]) * tile, int(d["nx"]) * tile, 2),
+                       np.float16 if fmt == RT_LIGHTMAP_F16 else np.float32)
+        self._check(self.L.rt_encode_volume_visibility(self.ctx, _ptr(d), _ptr(v), fmt, _ptr(m), _ptr(out), out.nbytes),
+                    "encodeVolumeVisibility")
         return out
 
     # ---- directional gathers: SH radiance of bands 0 .. 1 over the hemisphere of surface points (rt_gather_directional) ----
