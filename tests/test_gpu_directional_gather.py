@@ -130,6 +130,11 @@ def test_a_call_cut_into_two_batches(W, monkeypatch):
             assert st[name] == st_a[name] + st_b[name], (name, st[name], st_a[name], st_b[name])
         assert st["extension_rays"] >= 65 * spp and min(st["kernel_ms"], st_a["kernel_ms"], st_b["kernel_ms"]) > 0.0
         assert (full["layer"][:, 0, 3] > 0).any() and (full["layer"][:, 1:, :3] != 0).any()
+        # with timing off no batch records its events: the same call reports the same stats and no time
+        r.setKernelTiming(False)
+        again, st_off = r.gatherDirectional(pts, 1, spp, dru.SEED, stats=True)
+        assert np.array_equal(dru.result_words(again), words)
+        assert st_off["kernel_ms"] == 0.0 and st_off == dict(st, kernel_ms=0.0)
     finally:
         r.destroy()
 

@@ -128,6 +128,11 @@ def test_a_call_cut_into_two_batches(W, monkeypatch):
             assert st[name] == st_a[name] + st_b[name], (name, st[name], st_a[name], st_b[name])
         assert st["extension_rays"] >= 65 * spp and min(st["kernel_ms"], st_a["kernel_ms"], st_b["kernel_ms"]) > 0.0
         assert (full["hit_fraction"][:64] > 0).all()            # the grid probes are inside the box
+        # with timing off no batch records its events: the same call reports the same stats and no time
+        r.setKernelTiming(False)
+        again, st_off = r.gatherProbes(pts, 1, spp, prb.SEED, stats=True)
+        assert np.array_equal(prb.result_words(again), words)
+        assert st_off["kernel_ms"] == 0.0 and st_off == dict(st, kernel_ms=0.0)
     finally:
         r.destroy()
 

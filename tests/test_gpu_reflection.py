@@ -141,6 +141,16 @@ def test_a_call_cut_into_batches_inside_a_probe(W, monkeypatch):
             assert st[name] == sum(s[name] for _, s in singles), name
         assert st["extension_rays"] >= 192 * spt and st["kernel_ms"] > 0.0
         assert st["workgroups"] > max(s["workgroups"] for _, s in singles)       # three radiance launches against one
+        # a launch has a workgroup per 256 items up to the resident ones, which an uncut call of 64 * spt items shows (a CU
+        # holds at most eight workgroups of 256 threads): the call's workgroups are the sum over its three batches
+        resident = singles[0][1]["workgroups"]
+        assert resident < 64 * spt // 256 and all(s["workgroups"] == resident for _, s in singles)
+        assert st["workgroups"] == sum(min(resident, texels * spt // 256) for texels in (85, 85, 22))
+        # with timing off no batch records its events: the same call reports the same stats and no time
+        r.setKernelTiming(False)
+        again, st_off = r.captureReflection(d, probes, 1, rf.SEED, stats=True)
+        assert np.array_equal(again.view(np.uint32), full.view(np.uint32))
+        assert st_off["kernel_ms"] == 0.0 and st_off == dict(st, kernel_ms=0.0)
     finally:
         r.destroy()
 

@@ -192,6 +192,17 @@ def test_a_bake_cut_into_batches(W, monkeypatch):
             for name in ("rays", "samples", "workgroups") + prb.COUNT_NAMES:
                 assert st[name] == st_g[name], (nx, name)
             assert st["samples"] == nx * spp and (vol["hit_fraction"] > 0).all()
+            assert st["kernel_ms"] == 0.0                        # timing is off: no batch recorded its events
+            if nx == 65:
+                # the stats of the cut bake are the sums over its two batches, its time that of both radiance launches
+                st_a = r.gatherProbes(probes[:64], 1, spp, prb.SEED, stats=True)[1]
+                st_b = r.gatherProbes(probes[64:], 1, spp, prb.SEED, stats=True)[1]
+                for name in ("rays", "samples", "workgroups") + prb.COUNT_NAMES:
+                    assert st[name] == st_a[name] + st_b[name], (name, st[name], st_a[name], st_b[name])
+                r.setKernelTiming(True)
+                st_t = r.bakeVolume(d, 1, spp, prb.SEED, stats=True)[1]
+                r.setKernelTiming(False)
+                assert st_t["kernel_ms"] > 0.0 and st_t == dict(st, kernel_ms=st_t["kernel_ms"])
             vols[nx] = vu.words(vol).reshape(-1, 28)
         assert np.array_equal(vols[65][:5], vols[5])
     finally:

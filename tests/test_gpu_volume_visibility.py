@@ -207,7 +207,7 @@ def test_a_bake_is_the_reduction_of_the_gpus_own_ray_query(W, monkeypatch, scene
 @pytest.mark.timeout(300)
 def test_a_bake_cut_into_batches(W, monkeypatch):
     """A (1, 1, 2) grid at size 8 and spt 65536: 128 texels of 2^16 samples are two batches of RT_PROBE_BATCH_SAMPLES.  The call
-    equals, word for word, two one-probe bakes with pad_first advanced by size * size."""
+    equals, word for word, two one-probe bakes with pad_first advanced by size * size; its stats are their sums."""
     R = _R()
     b, d, v = _bake_case(W, "cornell", dims=(1, 1, 2), size=8, spt=65536, pad_first=9)
     r = _renderer(W, monkeypatch, b)
@@ -215,11 +215,25 @@ def test_a_bake_cut_into_batches(W, monkeypatch):
         both, st = r.bakeVolumeVisibility(d, v, prb.SEED, stats=True)
         assert both.shape == (2, 1, 1, 8, 8, 2) and st["rays"] == 128 * 65536
         probes = vu.numpy_probes(d)
+        each = []
         for p in (0, 1):
             one = R.volume_desc(probes[p, 0:3], d["step"], (1, 1, 1), pad_first=9 + 64 * p)
             assert np.array_equal(vu.numpy_probes(one)[0, 0:3], probes[p, 0:3])
             alone = r.bakeVolumeVisibility(one, v, prb.SEED)
             assert np.array_equal(vu.words(alone), vu.words(both[p])), p
+            each.append(r.bakeVolumeVisibility(one, v, prb.SEED, stats=True)[1])
+        # a batch is one probe here: the stats of the cut bake are the sums over the two ray launches, the form theirs
+        print("both", st, "each", each)
+        for name in ("rays", "nodes_visited", "tris_tested", "workgroups"):
+            assert st[name] == each[0][name] + each[1][name], (name, st[name], each[0][name], each[1][name])
+        for name in ("walk", "lds", "rayreg"):
+            assert st[name] == each[0][name] == each[1][name], name
+        assert st["nodes_visited"] > 0 and st["kernel_ms"] == 0.0 # timing is off: no batch recorded its events
+        r.setKernelTiming(True)
+        timed, st_t = r.bakeVolumeVisibility(d, v, prb.SEED, stats=True)
+        r.setKernelTiming(False)
+        assert np.array_equal(vu.words(timed), vu.words(both))
+        assert st_t["kernel_ms"] > 0.0 and st_t == dict(st, kernel_ms=st_t["kernel_ms"])
         far = np.float32(v["max_distance"])
         # (the f32 sum of 65536 samples in sample order carries its rounding: a mean may lie a few 1e-4 above the clamp)
         assert (both[..., 0] < far * np.float32(1.001)).all() and (both[..., 1] > both[..., 0] * both[..., 0]).any()

@@ -56,8 +56,8 @@ struct QueryState {
   DeviceBuffer in, out, counters;
   EventPair ev;
   bool timed = false;               // the last query recorded its events
-  std::deque<EventPair> batch_ev;   // composed gathers launch once per batch, each between a pair of its own (deque: a pair never moves)
-  uint32_t batches_timed = 0;       // ... and the batches of the last call that recorded theirs
+  std::deque<EventPair> batch_ev;   // a batched call (run_batches) traces once per batch, each between a pair of its own (deque: a pair never moves)
+  uint32_t batches_timed = 0;       // ... and the batches of the last call that recorded theirs (batch_time_ms)
 };
 
 // What lightmap bakes (rt_bake_points, rt_bake_irradiance and their atlas forms) keep between calls: their staging arrays,
@@ -309,14 +309,16 @@ struct rt_ctx {
   rt_ray_stats rq_last = {};
   rt_radiance_stats rd_last = {};
   rt_radiance_stats gi_last = {};
-  // probe gathers (rt_gather_probes): a path-query kind of their own (its QueryState: the host entry's staging, the counter
-  // shards of the radiance launches, an event pair per radiance launch of the last call) and the scratch of a batch (one
-  // rt_ray and one rt_radiance per sample, kept and grown)
+  // The batched kinds - probe and directional gathers, reflection captures, visibility bakes - all go through the one batch
+  // driver (run_batches): per batch a kernel that makes rays, a trace of them, a kernel that reduces the results.  Each has a
+  // QueryState of its own (the host entry's staging, the counter shards of its trace launches, an event pair per trace launch
+  // of the last call) and its last stats; the scratch of a batch is shared, pr_rays / pr_rad (one rt_ray and one 16-byte
+  // result per sample, kept and grown by the driver), being per-call scratch on the one stream.
+  // probe gathers (rt_gather_probes): a path-query kind of their own
   QueryState pr;
   rt_radiance_stats pr_last = {};
   DeviceBuffer pr_rays, pr_rad;
-  // directional gathers (rt_gather_directional): the same composition at surface points, a path-query kind and a state of
-  // its own; the scratch of a batch is the probe gather's, pr_rays / pr_rad, both being per-call scratch on the one stream
+  // directional gathers (rt_gather_directional): the same composition at surface points
   QueryState dg;
   rt_radiance_stats dg_last = {};
   // directional bakes (rt_bake_atlas_directional, _lightmap): the gather's results, the four scattered layers and the four
@@ -331,13 +333,12 @@ struct rt_ctx {
   bool albedo_plane_valid = false;  // the render target holds the albedo a compute() wrote (present() overwrites it)
   LightmapState lm;
   VolumeState vol;
-  // reflection probes: a path-query kind of their own (counter shards, an event pair per radiance launch of the last call,
-  // the last stats) and the staging of their host entries; the scratch of a batch is pr_rays / pr_rad
+  // reflection probes: a path-query kind of their own and the staging of their host entries
   QueryState rf;
   rt_radiance_stats rf_last = {};
   ReflectionState rfl;
   // probe visibility maps: their ray launches count and time on a state of their own, so rt_ray_query_stats keeps reporting
-  // the caller's last rt_trace_rays; the scratch of a batch is pr_rays / pr_rad (an rt_ray_hit is 16 bytes, like an rt_radiance)
+  // the caller's last rt_trace_rays (an rt_ray_hit is 16 bytes, like an rt_radiance)
   QueryState vv;
   rt_ray_stats vv_last = {};
   VisibilityState vis;
@@ -359,6 +360,13 @@ namespace {
 int fail(rt_ctx* c, int code, const std::string& msg) {
   if (c) c->error = msg;
   return code;
+}
+// A refusal that needs no context, "<what>: <msg>": without one the message is what rt_last_error(NULL) returns.  (The
+// entries of a family that has no such refusal return before they get here.)
+int refuse(rt_ctx* c, const char* what, const std::string& why) {
+  const std::string msg = std::string(what) + ": " + why;
+  if (!c) g_create_error = msg;
+  return fail(c, RT_ERR_INVALID, msg);
 }
 int hip_fail(rt_ctx* c, hipError_t e, const char* what) {
   char buf[256];
@@ -927,22 +935,38 @@ int query_scene_ready(rt_ctx* c, const char* what, bool lights) {
   if (r < 0 && !c->validate_dirty && !c->scene_valid) return fail(c, RT_ERR_NOT_READY, w + ": " + c->scene_problem);
   return r;
 }
-// the caller's device arrays of the device entries: there, aligned, and memory the context's device can reach
-int query_device_arrays_ok(rt_ctx* c, const char* what, const void* dev_rays, const void* dev_out) {
-  const std::string w(what);
-  if (!dev_rays || !dev_out) return fail(c, RT_ERR_INVALID, w + ": NULL array");
-  if ((((uintptr_t)dev_rays) | ((uintptr_t)dev_out)) & 15u) return fail(c, RT_ERR_INVALID, w + ": device arrays must be 16-byte aligned");
+// One of the caller's arrays of an entry.  when: the call uses it.
+struct CallerArray {
+  const void* p;
+  bool when;
+  CallerArray(const void* p_, bool when_ = true) : p(p_), when(when_) {}
+};
+// an array the caller may leave out by passing NULL
+CallerArray optional_array(const void* p) { return {p, p != nullptr}; }
+// The caller's arrays of an entry: all there and, for a device entry, all 16-byte aligned - which needs no context, so a
+// family with a context-free refusal asks here before it looks at its context - and then each of them, once, memory the
+// context's device can reach.
+int caller_arrays_ok(rt_ctx* c, const char* what, std::initializer_list<CallerArray> arrays, bool device = true) {
+  uintptr_t bits = 0;
+  for (const CallerArray& a : arrays) {
+    if (!a.when) continue;
+    if (!a.p) return refuse(c, what, "NULL array");
+    bits |= (uintptr_t)a.p;
+  }
+  if (device && (bits & 15u)) return refuse(c, what, "device arrays must be 16-byte aligned");
+  if (!c || !device) return RT_OK;
   HIP_TRY(c, hipSetDevice(c->device));
-  for (const void* p : {dev_rays, dev_out}) {
+  for (const CallerArray* a = arrays.begin(); a != arrays.end(); ++a) {
+    if (!a->when || std::any_of(arrays.begin(), a, [a](const CallerArray& b) { return b.when && b.p == a->p; })) continue;
     hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, p) != hipSuccess) {
+    if (hipPointerGetAttributes(&at, a->p) != hipSuccess) {
       (void)hipGetLastError();
-      return fail(c, RT_ERR_INVALID, w + ": not a device-accessible pointer");
+      return refuse(c, what, "not a device-accessible pointer");
     }
     if (at.type == hipMemoryTypeDevice && at.device != c->device)
-      return fail(c, RT_ERR_INVALID, w + ": the array lives on another device than the context");
+      return refuse(c, what, "the array lives on another device than the context");
     if (at.type != hipMemoryTypeDevice && at.type != hipMemoryTypeHost && at.type != hipMemoryTypeManaged)
-      return fail(c, RT_ERR_INVALID, w + ": not a device-accessible pointer");
+      return refuse(c, what, "not a device-accessible pointer");
   }
   return RT_OK;
 }
@@ -971,6 +995,20 @@ int query_launch(rt_ctx* c, EventPair& ev, const void* fn, uint32_t blocks, void
   if (c->timing) HIP_TRY(c, hipEventRecord(ev.b, c->stream));
   return RT_OK;
 }
+// The tail the query launches share, behind their choice of kernel and grid: the MI355RT_DEBUG_SHAPE line (print_shape writes
+// the kind's), the counters zeroed and handed to the kernel (*counters and *head are fields of a struct that args points
+// at), the launch between the events of batch_ev - a pair its caller keeps count of - or else the state's own, and `timed`.
+template <class PrintShape>
+int query_enqueue(rt_ctx* c, QueryState& q, const void* fn, uint32_t blocks, void** args, size_t dyn, uint64_t** counters,
+                  uint32_t** head, bool keep_counts, EventPair* batch_ev, PrintShape print_shape) {
+  if (getenv("MI355RT_DEBUG_SHAPE")) print_shape();
+  int r = query_reset_counters(c, q, counters, head, keep_counts);
+  if (r < 0) return r;
+  q.timed = false;
+  if ((r = query_launch(c, batch_ev ? *batch_ev : q.ev, fn, blocks, args, dyn)) < 0) return r;
+  q.timed = c->timing && !batch_ev;
+  return RT_OK;
+}
 // The six counters of the last query summed over their shards (all 0 when `launched` is false: no query yet, or an empty
 // one); *kernel_ms is written when that query recorded its events.  Waits for the stream.
 int query_totals(rt_ctx* c, const QueryState& q, bool launched, uint64_t sum[6], double* kernel_ms) {
@@ -988,20 +1026,111 @@ int query_totals(rt_ctx* c, const QueryState& q, bool launched, uint64_t sum[6],
   }
   return RT_OK;
 }
-// The host entries: n > 0 records (rt_ray, rt_gather_point) up to the query's staging array, launch(d_rays, d_out) enqueues
-// the kind's kernel, n results of out_stride bytes come back; the stream is idle on return.
+// ---- the blocking host entries: what each stages, stated once per array.
+enum : unsigned {
+  STAGE_ROOM = 0,   // room for `bytes` in the buffer, which every array gets, and nothing else
+  STAGE_IN = 1,     // the host's bytes are copied up before the launch
+  STAGE_OUT = 2,    // the buffer's bytes are copied down behind the launch
+  STAGE_MADE = 4    // (with STAGE_OUT) no room is made here: the launch makes it
+};
+struct Staged {
+  DeviceBuffer& buf;   // of the entry's own state: kept and grown across calls
+  const void* host;    // STAGE_IN: read; STAGE_OUT: the caller's writable array
+  size_t bytes;
+  unsigned dir;        // STAGE_*
+  bool grow = true;    // ensure_buffer's grow_policy
+  bool when = true;    // false: the call leaves this array out
+};
+// A blocking host entry behind its checks: room for every array, the inputs up, launch() enqueues the work on the arrays'
+// buffers, the outputs down, one wait; the stream is idle on return and the stats of the work can be read.
+template <class Launch>
+int staged_call(rt_ctx* c, std::initializer_list<Staged> arrays, Launch launch) {
+  HIP_TRY(c, hipSetDevice(c->device));
+  int r;
+  for (const Staged& a : arrays)
+    if (a.when && !(a.dir & STAGE_MADE) && (r = ensure_buffer(c, a.buf, a.bytes, a.grow)) < 0) return r;
+  for (const Staged& a : arrays)
+    if (a.when && (a.dir & STAGE_IN)) HIP_TRY(c, hipMemcpyAsync(a.buf.ptr, a.host, a.bytes, hipMemcpyHostToDevice, c->stream));
+  if ((r = launch()) < 0) return r;
+  for (const Staged& a : arrays)
+    if (a.when && (a.dir & STAGE_OUT))
+      HIP_TRY(c, hipMemcpyAsync(const_cast<void*>(a.host), a.buf.ptr, a.bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return RT_OK;
+}
+// The host entries of the queries: n > 0 records (rt_ray, rt_gather_point) up to the query's staging array, launch(d_rays,
+// d_out) enqueues the kind's kernel, n results of out_stride bytes come back.
 template <class Record, class Launch>
 int query_from_host(rt_ctx* c, QueryState& q, const char* what, const Record* rays, uint32_t n, void* out, size_t out_stride,
                     Launch launch) {
   if (!rays || !out) return fail(c, RT_ERR_INVALID, std::string(what) + ": NULL array");
-  HIP_TRY(c, hipSetDevice(c->device));
+  return staged_call(c, {{q.in, rays, (size_t)n * sizeof(Record), STAGE_IN}, {q.out, out, (size_t)n * out_stride, STAGE_OUT}},
+                     [&] { return launch((const void*)q.in.ptr, q.out.ptr); });
+}
+
+// ---- the calls that trace in batches: probe and directional gathers, reflection captures (rt_radiance_stats, on the path
+// query) and visibility bakes (rt_ray_stats, on the ray query).
+// What the last stats of a batch's trace add to the call's: the form is that of the last batch, the workgroups add up ...
+void fold_batch(rt_radiance_stats& sum, const rt_radiance_stats& b) {
+  sum.lds = b.lds;
+  sum.workgroups += b.workgroups;
+}
+void fold_batch(rt_ray_stats& sum, const rt_ray_stats& b) {
+  sum.walk = b.walk;
+  sum.lds = b.lds;
+  sum.rayreg = b.rayreg;
+  sum.workgroups += b.workgroups;
+}
+// ... and what the call knows itself: the items and samples of a path kind (the rays of the ray kind come from its counters)
+void batches_done(rt_radiance_stats& sum, uint32_t total, uint32_t spp) {
+  sum.rays = total;
+  sum.samples = (uint64_t)total * spp;
+}
+void batches_done(rt_ray_stats&, uint32_t, uint32_t) {}
+// The one batch loop.  `total` > 0 items of `spp` samples (< 2^31 in all) in batches of RT_PROBE_BATCH_SAMPLES / spp whole
+// items, each of them on the stream, in this order:
+//   make_rays(first, count, items)             the kind's kernel writes the count * spp = items rays of the batch to pr_rays
+//   trace(rays, items, out, keep_counts, ev)   launch_path_query or launch_ray_query_on, on the state q and the stats `last`:
+//                                              pr_rays to pr_rad, between the batch's own pair of events
+//   reduce(first, count)                       the kind's kernel folds pr_rad into the caller's results
+// Every (item, sample) is a trace item of its own, so the cut into batches cannot show in a result.  The counters of the
+// batches add up in q's shards; `last` ends as the call's stats, or zeroed when a trace could not be launched.
+template <class Stats, class MakeRays, class Trace, class Reduce>
+int run_batches(rt_ctx* c, QueryState& q, Stats& last, uint32_t total, uint32_t spp, MakeRays make_rays, Trace trace, Reduce reduce) {
+  const uint32_t per_batch = RT_PROBE_BATCH_SAMPLES / spp;   // whole items: >= 64, spp being <= 65536
+  const size_t scratch_items = (size_t)std::min(total, per_batch) * spp;
+  static_assert(sizeof(rt_ray_hit) == sizeof(rt_radiance), "the hits of a batch live in the radiance scratch");
   int r;
-  if ((r = ensure_buffer(c, q.in, (size_t)n * sizeof(Record), true)) < 0) return r;
-  if ((r = ensure_buffer(c, q.out, (size_t)n * out_stride, true)) < 0) return r;
-  HIP_TRY(c, hipMemcpyAsync(q.in.ptr, rays, (size_t)n * sizeof(Record), hipMemcpyHostToDevice, c->stream));
-  if ((r = launch((const void*)q.in.ptr, q.out.ptr)) < 0) return r;
-  HIP_TRY(c, hipMemcpyAsync(out, q.out.ptr, (size_t)n * out_stride, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if ((r = ensure_buffer(c, c->pr_rays, scratch_items * sizeof(rt_ray), false)) < 0) return r;
+  if ((r = ensure_buffer(c, c->pr_rad, scratch_items * sizeof(rt_radiance), false)) < 0) return r;
+  q.batches_timed = 0;
+  Stats sum = Stats();
+  uint32_t batch = 0;
+  for (uint32_t first = 0; first < total; first += per_batch, batch++) {
+    const uint32_t count = std::min(per_batch, total - first);
+    const uint32_t items = count * spp;                       // <= RT_PROBE_BATCH_SAMPLES
+    if ((r = make_rays(first, count, items)) < 0) return r;
+    if (q.batch_ev.size() <= batch) q.batch_ev.emplace_back();
+    if ((r = trace((const void*)c->pr_rays.ptr, items, c->pr_rad.ptr, batch != 0, &q.batch_ev[batch])) < 0) {
+      last = Stats();
+      return r;
+    }
+    if (c->timing) q.batches_timed = batch + 1;
+    fold_batch(sum, last);
+    if ((r = reduce(first, count)) < 0) return r;
+  }
+  batches_done(sum, total, spp);
+  last = sum;
+  return RT_OK;
+}
+// The stream time of the batches of q's last call that recorded their events (0.0 with timing off), added to *kernel_ms.  The
+// stream has been fenced.
+int batch_time_ms(rt_ctx* c, const QueryState& q, double* kernel_ms) {
+  for (uint32_t b = 0; b < q.batches_timed; b++) {
+    float ms = 0.0f;
+    HIP_TRY(c, hipEventElapsedTime(&ms, q.batch_ev[b].a, q.batch_ev[b].b));
+    *kernel_ms += (double)ms;
+  }
   return RT_OK;
 }
 
@@ -2173,11 +2302,7 @@ static int launch_ray_query_on(rt_ctx* c, QueryState& q, rt_ray_stats& last, con
   int per_cu;
   if ((r = resident_blocks(c, fn, 256, shape.dyn, &per_cu)) < 0) return r;
   const uint32_t blocks = grid_blocks(c, per_cu, c->knobs.wf_blocks_per_cu, (n + 255u) / 256u);
-  if (getenv("MI355RT_DEBUG_SHAPE"))
-    fprintf(stderr, "[mi355rt] %s: %s walk, form %d, %zu bytes of LDS, resident workgroups per CU %d, %u workgroups\n", what,
-            shape.pairs ? "pair" : "node", shape.rq_form, shape.dyn, per_cu, blocks);
   rtk::RayQueryArgs A;
-  if ((r = query_reset_counters(c, q, &A.counters, &A.head, keep_counts)) < 0) return r;
   A.rays = (const float4*)d_rays;
   A.out = (uint4*)d_out;
   A.n_rays = n;
@@ -2188,9 +2313,11 @@ static int launch_ray_query_on(rt_ctx* c, QueryState& q, rt_ray_stats& last, con
   A.n_inst = c->n_instances;
   DevScene S = dev_scene(c);
   void* args[] = {&S, &A, &shape.nplan, &shape.plan};
-  q.timed = false;
-  if ((r = query_launch(c, batch_ev ? *batch_ev : q.ev, fn, blocks, args, shape.dyn)) < 0) return r;
-  q.timed = c->timing && !batch_ev;
+  r = query_enqueue(c, q, fn, blocks, args, shape.dyn, &A.counters, &A.head, keep_counts, batch_ev, [&] {
+    fprintf(stderr, "[mi355rt] %s: %s walk, form %d, %zu bytes of LDS, resident workgroups per CU %d, %u workgroups\n", what,
+            shape.pairs ? "pair" : "node", shape.rq_form, shape.dyn, per_cu, blocks);
+  });
+  if (r < 0) return r;
   last = rt_ray_stats();
   last.walk = shape.pairs ? 1u : 0u;
   last.lds = shape.trace_lds ? 1u : 0u;
@@ -2232,7 +2359,7 @@ int rt_trace_rays_device(rt_ctx* c, const void* dev_rays, uint32_t n, int mode, 
     c->rq_last = rt_ray_stats();
     return RT_OK;
   }
-  if ((r = query_device_arrays_ok(c, "ray query", dev_rays, dev_out)) < 0) return r;
+  if ((r = caller_arrays_ok(c, "ray query", {dev_rays, dev_out})) < 0) return r;
   return launch_ray_query(c, dev_rays, n, mode, t_min, dev_out, c->detailed_counters);
 }
 
@@ -2293,12 +2420,7 @@ static int launch_path_query(rt_ctx* c, const PathQueryKind& k, const void* d_it
   int per_cu;
   if ((r = resident_blocks(c, fn, 256, shape.dyn, &per_cu)) < 0) return r;
   const uint32_t blocks = grid_blocks(c, per_cu, 0, (n + 255u) / 256u);
-  if (getenv("MI355RT_DEBUG_SHAPE"))
-    fprintf(stderr, "[mi355rt] %s: %s form, %zu bytes of LDS, resident workgroups per CU %d, %u workgroups\n", k.what,
-            shape.lds ? "LDS" : "global", shape.dyn, per_cu, blocks);
-  QueryState& q = c->*k.state;
   rtk::PathQueryArgs A;
-  if ((r = query_reset_counters(c, q, &A.counters, &A.head, keep_counts)) < 0) return r;
   A.items = (const float4*)d_items;
   A.out = (float4*)d_out;
   A.n_items = n;
@@ -2313,9 +2435,11 @@ static int launch_path_query(rt_ctx* c, const PathQueryKind& k, const void* d_it
   A.n_verts = c->n_verts;
   DevScene S = dev_scene(c);
   void* args[] = {&S, &A, &shape.plan};
-  q.timed = false;
-  if ((r = query_launch(c, batch_ev ? *batch_ev : q.ev, fn, blocks, args, shape.dyn)) < 0) return r;
-  q.timed = c->timing && !batch_ev;
+  r = query_enqueue(c, c->*k.state, fn, blocks, args, shape.dyn, &A.counters, &A.head, keep_counts, batch_ev, [&] {
+    fprintf(stderr, "[mi355rt] %s: %s form, %zu bytes of LDS, resident workgroups per CU %d, %u workgroups\n", k.what,
+            shape.lds ? "LDS" : "global", shape.dyn, per_cu, blocks);
+  });
+  if (r < 0) return r;
   rt_radiance_stats& last = c->*k.last;
   last = rt_radiance_stats();
   last.rays = n;
@@ -2357,7 +2481,7 @@ static int path_query_device(rt_ctx* c, const PathQueryKind& k, const void* dev_
     c->*k.last = rt_radiance_stats();
     return RT_OK;
   }
-  if ((r = query_device_arrays_ok(c, k.what, dev_items, dev_out)) < 0) return r;
+  if ((r = caller_arrays_ok(c, k.what, {dev_items, dev_out})) < 0) return r;
   return launch_path_query(c, k, dev_items, n, max_depth, spp, seed, dev_out, detail < 0 ? c->detailed_counters : detail != 0);
 }
 
@@ -2401,8 +2525,8 @@ int rt_gather_irradiance(rt_ctx* c, const rt_gather_point* points, uint32_t n, u
 }
 
 // ---- probe gathers: SH9 radiance per probe (mi355rt.h "probe gathers"), by composition around the radiance query's kernel:
-// per batch of whole probes k_probe_rays -> k_radiance_query (spp = 1, seed = 0 on the pad' rays) -> k_probe_project
-// (k_probe.hip.h).  Every (probe, sample) is an item of its own, so the cut into batches cannot show in a result.
+// per batch of whole probes (run_batches) k_probe_rays -> k_radiance_query (spp = 1, seed = 0 on the pad' rays) ->
+// k_probe_project (k_probe.hip.h).
 // Directional gathers (mi355rt.h "directional gathers") are the same composition at surface points, with k_dir_rays and
 // k_dir_project (k_directional.hip.h).  What a composed gather has of its own:
 struct ComposedGather {
@@ -2420,63 +2544,38 @@ static_assert(RT_DIRECTIONAL_BATCH_SAMPLES == RT_PROBE_BATCH_SAMPLES, "the two c
 static int launch_composed_gather(rt_ctx* c, const ComposedGather& g, const void* d_items, uint32_t n, uint32_t max_depth,
                                   uint32_t spp, uint32_t seed, void* d_out, bool detail) {
   const PathQueryKind& k = g.kind;
-  int r = query_scene_ready(c, k.what, true);
+  const int r = query_scene_ready(c, k.what, true);
   if (r < 0) return r;
-  const uint32_t per_batch = RT_PROBE_BATCH_SAMPLES / spp;   // whole items: >= 64, spp being <= 65536
-  const size_t scratch_items = (size_t)std::min(n, per_batch) * spp;
-  if ((r = ensure_buffer(c, c->pr_rays, scratch_items * sizeof(rt_ray), false)) < 0) return r;
-  if ((r = ensure_buffer(c, c->pr_rad, scratch_items * sizeof(rt_radiance), false)) < 0) return r;
-  QueryState& q = c->*k.state;
-  rt_radiance_stats& last = c->*k.last;
-  q.batches_timed = 0;
-  rt_radiance_stats total = rt_radiance_stats();
-  uint32_t batch = 0;
-  for (uint32_t first = 0; first < n; first += per_batch, batch++) {
-    const uint32_t np = std::min(per_batch, n - first);
-    const uint32_t items = np * spp;                         // <= RT_PROBE_BATCH_SAMPLES
-    const float4* src = (const float4*)d_items + 2 * (size_t)first;
-    float4* rays = (float4*)c->pr_rays.ptr;
-    float4* rad = (float4*)c->pr_rad.ptr;
-    float4* out = (float4*)d_out + g.out_vec4 * (size_t)first;
-    {
-      uint32_t a_items = items, a_spp = spp, a_seed = seed;
-      void* args[] = {&src, &rays, &a_items, &a_spp, &a_seed};
-      HIP_TRY(c, hipLaunchKernel(g.rays_fn, dim3((items + 255u) / 256u), dim3(256), args, 0, c->stream));
-    }
-    // the radiance launch between this batch's own event pair
-    if (q.batch_ev.size() <= batch) q.batch_ev.emplace_back();
-    if ((r = launch_path_query(c, k, rays, items, max_depth, 1u, 0u, rad, detail, batch != 0, &q.batch_ev[batch])) < 0) {
-      last = rt_radiance_stats();
-      return r;
-    }
-    if (c->timing) q.batches_timed = batch + 1;
-    total.lds = last.lds;
-    total.workgroups += last.workgroups;
-    {
-      uint32_t a_np = np, a_spp = spp, a_seed = seed;
-      const float4* rad_in = rad;
-      void* args[] = {&src, &rad_in, &out, &a_np, &a_spp, &a_seed};
-      HIP_TRY(c, hipLaunchKernel(g.project_fn, dim3((np + 3u) / 4u), dim3(256), args, 0, c->stream));
-    }
-  }
-  total.rays = n;
-  total.samples = (uint64_t)n * spp;
-  last = total;
-  return RT_OK;
+  return run_batches(
+      c, c->*k.state, c->*k.last, n, spp,
+      [&](uint32_t first, uint32_t, uint32_t items) -> int {
+        const float4* src = (const float4*)d_items + 2 * (size_t)first;
+        float4* rays = (float4*)c->pr_rays.ptr;
+        uint32_t a_items = items, a_spp = spp, a_seed = seed;
+        void* args[] = {&src, &rays, &a_items, &a_spp, &a_seed};
+        HIP_TRY(c, hipLaunchKernel(g.rays_fn, dim3((items + 255u) / 256u), dim3(256), args, 0, c->stream));
+        return RT_OK;
+      },
+      [&](const void* rays, uint32_t items, void* rad, bool keep_counts, EventPair* ev) {
+        return launch_path_query(c, k, rays, items, max_depth, 1u, 0u, rad, detail, keep_counts, ev);
+      },
+      [&](uint32_t first, uint32_t np) -> int {
+        const float4* src = (const float4*)d_items + 2 * (size_t)first;
+        const float4* rad = (const float4*)c->pr_rad.ptr;
+        float4* out = (float4*)d_out + g.out_vec4 * (size_t)first;
+        uint32_t a_np = np, a_spp = spp, a_seed = seed;
+        void* args[] = {&src, &rad, &out, &a_np, &a_spp, &a_seed};
+        HIP_TRY(c, hipLaunchKernel(g.project_fn, dim3((np + 3u) / 4u), dim3(256), args, 0, c->stream));
+        return RT_OK;
+      });
 }
 
-// the stats of a kind whose calls launch once per batch (the composed gathers, reflection captures)
+// the stats of a path kind whose calls trace once per batch (the composed gathers, reflection captures)
 static int batched_query_stats(rt_ctx* c, const PathQueryKind& k, rt_radiance_stats* out) {
   if (!c || !out) return RT_ERR_INVALID;
   const int r = path_query_stats(c, k, out);   // fences the stream; the time is that of the batches
   if (r < 0) return r;
-  const QueryState& q = c->*k.state;
-  for (uint32_t b = 0; b < q.batches_timed; b++) {
-    float ms = 0.0f;
-    HIP_TRY(c, hipEventElapsedTime(&ms, q.batch_ev[b].a, q.batch_ev[b].b));
-    out->kernel_ms += (double)ms;
-  }
-  return RT_OK;
+  return batch_time_ms(c, c->*k.state, &out->kernel_ms);
 }
 static int composed_gather_stats(rt_ctx* c, const ComposedGather& g, rt_radiance_stats* out) {
   return batched_query_stats(c, g.kind, out);
@@ -2492,7 +2591,7 @@ static int composed_gather_device(rt_ctx* c, const ComposedGather& g, const void
     (c->*g.kind.state).batches_timed = 0;
     return RT_OK;
   }
-  if ((r = query_device_arrays_ok(c, g.kind.what, dev_items, dev_out)) < 0) return r;
+  if ((r = caller_arrays_ok(c, g.kind.what, {dev_items, dev_out})) < 0) return r;
   return launch_composed_gather(c, g, dev_items, n, max_depth, spp, seed, dev_out,
                                 detail < 0 ? c->detailed_counters : detail != 0);
 }
@@ -2718,10 +2817,9 @@ int rt_bake_points_device(rt_ctx* c, const rt_bake_desc* d, const void* dev_atla
   if (!c) return RT_ERR_INVALID;
   int r = bake_desc_ok(c, d);
   if (r < 0) return r;
-  if (!dev_count) return fail(c, RT_ERR_INVALID, "bake: NULL array");
-  if (cap != 0 && (r = query_device_arrays_ok(c, "bake", dev_points, dev_texels)) < 0) return r;
-  if ((r = query_device_arrays_ok(c, "bake", dev_count, dev_owner ? dev_owner : dev_count)) < 0) return r;
-  if (dev_atlas_uv && (r = query_device_arrays_ok(c, "bake", dev_atlas_uv, dev_count)) < 0) return r;
+  if ((r = caller_arrays_ok(c, "bake", {dev_count, {dev_points, cap != 0}, {dev_texels, cap != 0}, optional_array(dev_owner),
+                                         optional_array(dev_atlas_uv)})) < 0)
+    return r;
   if ((r = bake_scene_ready(c, d, false)) < 0) return r;
   rtk::BakeArgs A;
   if ((r = bake_front(c, d, dev_atlas_uv, dev_owner, dev_count, A)) < 0) return r;
@@ -2878,10 +2976,9 @@ int rt_bake_atlas_points_device(rt_ctx* c, const rt_bake_atlas_desc* d, const rt
   if (!c) return RT_ERR_INVALID;
   int r = bake_atlas_desc_ok(c, d, entries);
   if (r < 0) return r;
-  if (!dev_count) return fail(c, RT_ERR_INVALID, std::string(kAtlas) + ": NULL array");
-  if (cap != 0 && (r = query_device_arrays_ok(c, kAtlas, dev_points, dev_texels)) < 0) return r;
-  if ((r = query_device_arrays_ok(c, kAtlas, dev_count, dev_owner ? dev_owner : dev_count)) < 0) return r;
-  if (dev_atlas_uv && (r = query_device_arrays_ok(c, kAtlas, dev_atlas_uv, dev_count)) < 0) return r;
+  if ((r = caller_arrays_ok(c, kAtlas, {dev_count, {dev_points, cap != 0}, {dev_texels, cap != 0}, optional_array(dev_owner),
+                                        optional_array(dev_atlas_uv)})) < 0)
+    return r;
   if ((r = bake_atlas_scene_ready(c, d, entries, false)) < 0) return r;
   rtk::BakeAtlasArgs A;
   if ((r = bake_atlas_front(c, d, entries, dev_atlas_uv, dev_owner, dev_count, A)) < 0) return r;
@@ -2981,8 +3078,7 @@ int rt_dilate_atlas_device(rt_ctx* c, const rt_dilate_desc* d, void* dev_atlas, 
   if (!c) return RT_ERR_INVALID;
   int r = dilate_desc_ok(c, d, dev_atlas);
   if (r < 0) return r;
-  if ((r = query_device_arrays_ok(c, kDilate, dev_atlas, dev_src ? dev_src : dev_atlas)) < 0) return r;
-  if (dev_filled && (r = query_device_arrays_ok(c, kDilate, dev_atlas, dev_filled)) < 0) return r;
+  if ((r = caller_arrays_ok(c, kDilate, {dev_atlas, optional_array(dev_src), optional_array(dev_filled)})) < 0) return r;
   return launch_dilate(c, d, dev_atlas, dev_src, dev_filled);
 }
 
@@ -2990,17 +3086,15 @@ int rt_dilate_atlas(rt_ctx* c, const rt_dilate_desc* d, float* atlas, uint32_t* 
   if (!c) return RT_ERR_INVALID;
   int r = dilate_desc_ok(c, d, atlas);
   if (r < 0) return r;
-  HIP_TRY(c, hipSetDevice(c->device));
   const size_t texels = (size_t)d->width * d->height;
-  if ((r = ensure_buffer(c, c->dl.atlas, texels * 16, true)) < 0) return r;
-  if ((r = ensure_buffer(c, c->dl.filled, 16, false)) < 0) return r;
-  HIP_TRY(c, hipMemcpyAsync(c->dl.atlas.ptr, atlas, texels * 16, hipMemcpyHostToDevice, c->stream));
-  if ((r = launch_dilate(c, d, c->dl.atlas.ptr, nullptr, filled_out ? c->dl.filled.ptr : nullptr)) < 0) return r;
-  HIP_TRY(c, hipMemcpyAsync(atlas, c->dl.atlas.ptr, texels * 16, hipMemcpyDeviceToHost, c->stream));
-  if (src_out) HIP_TRY(c, hipMemcpyAsync(src_out, c->dl.src.ptr, texels * 4, hipMemcpyDeviceToHost, c->stream));
-  if (filled_out) HIP_TRY(c, hipMemcpyAsync(filled_out, c->dl.filled.ptr, 4, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return RT_OK;
+  DilateState& st = c->dl;
+  // the atlas goes up and comes back; the source map comes from the scratch that launch_dilate makes room for; the count has
+  // its room (16 bytes, as every buffer has at least) whether or not it is asked for
+  return staged_call(c,
+                     {{st.atlas, atlas, texels * 16, STAGE_IN | STAGE_OUT},
+                      {st.src, src_out, texels * 4, STAGE_OUT | STAGE_MADE, true, src_out != nullptr},
+                      {st.filled, filled_out, 4, filled_out ? STAGE_OUT : STAGE_ROOM, false}},
+                     [&] { return launch_dilate(c, d, st.atlas.ptr, nullptr, filled_out ? st.filled.ptr : nullptr); });
 }
 
 // ---- atlas denoise: the edge-stopped a-trous filter of mi355rt.h "atlas denoise" as one index build and `passes` launches
@@ -3063,8 +3157,7 @@ int rt_denoise_atlas_device(rt_ctx* c, const rt_denoise_desc* d, const void* dev
   int r = denoise_desc_ok(c, d, dev_in, dev_points, dev_texels, n, dev_out);
   if (r < 0) return r;
   if (dev_in == dev_out) return fail(c, RT_ERR_INVALID, std::string(kDenoise) + ": the output must not be the input");
-  if ((r = query_device_arrays_ok(c, kDenoise, dev_in, dev_out)) < 0) return r;
-  if (n != 0 && (r = query_device_arrays_ok(c, kDenoise, dev_points, dev_texels)) < 0) return r;
+  if ((r = caller_arrays_ok(c, kDenoise, {dev_in, dev_out, {dev_points, n != 0}, {dev_texels, n != 0}})) < 0) return r;
   return launch_denoise(c, d, dev_in, dev_points, dev_texels, n, dev_out);
 }
 
@@ -3073,52 +3166,40 @@ int rt_denoise_atlas(rt_ctx* c, const rt_denoise_desc* d, const float* atlas_in,
   if (!c) return RT_ERR_INVALID;
   int r = denoise_desc_ok(c, d, atlas_in, points, texels, n, atlas_out);
   if (r < 0) return r;
-  HIP_TRY(c, hipSetDevice(c->device));
   const size_t bytes = (size_t)d->width * d->height * 16;
-  if ((r = ensure_buffer(c, c->dn.in, bytes, true)) < 0) return r;
-  if ((r = ensure_buffer(c, c->dn.out, bytes, true)) < 0) return r;
-  HIP_TRY(c, hipMemcpyAsync(c->dn.in.ptr, atlas_in, bytes, hipMemcpyHostToDevice, c->stream));
-  if (n) {
-    if ((r = ensure_buffer(c, c->dn.points, (size_t)n * sizeof(rt_gather_point), true)) < 0) return r;
-    if ((r = ensure_buffer(c, c->dn.texels, (size_t)n * 4, true)) < 0) return r;
-    HIP_TRY(c, hipMemcpyAsync(c->dn.points.ptr, points, (size_t)n * sizeof(rt_gather_point), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(c->dn.texels.ptr, texels, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-  }
-  if ((r = launch_denoise(c, d, c->dn.in.ptr, n ? c->dn.points.ptr : nullptr, n ? c->dn.texels.ptr : nullptr, n,
-                          c->dn.out.ptr)) < 0)
-    return r;
-  HIP_TRY(c, hipMemcpyAsync(atlas_out, c->dn.out.ptr, bytes, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return RT_OK;
+  DenoiseState& st = c->dn;
+  return staged_call(c,
+                     {{st.in, atlas_in, bytes, STAGE_IN},
+                      {st.out, atlas_out, bytes, STAGE_OUT},
+                      {st.points, points, (size_t)n * sizeof(rt_gather_point), STAGE_IN, true, n != 0},
+                      {st.texels, texels, (size_t)n * 4, STAGE_IN, true, n != 0}},
+                     [&] {
+                       return launch_denoise(c, d, st.in.ptr, n ? st.points.ptr : nullptr, n ? st.texels.ptr : nullptr, n,
+                                             st.out.ptr);
+                     });
 }
 
 // ---- frame denoise: the G-buffer-guided a-trous filter of mi355rt.h "frame denoise" as one prepare launch (or its cached
 // outputs), `passes` launches in the form picked per pass, and the finish (k_frame_denoise.hip.h).
 static const char* const kFrameDenoise = "frame denoise";
-// a refusal that needs no context: without one the message is what rt_last_error(NULL) returns
-static int frame_denoise_fail(rt_ctx* c, const std::string& what) {
-  const std::string msg = std::string(kFrameDenoise) + ": " + what;
-  if (!c) g_create_error = msg;
-  return fail(c, RT_ERR_INVALID, msg);
-}
 static int frame_denoise_desc_ok(rt_ctx* c, const rt_frame_denoise_desc* d) {
-  if (!d) return frame_denoise_fail(c, "NULL descriptor");
-  if (d->reserved[0] | d->reserved[1]) return frame_denoise_fail(c, "reserved words must be 0");
-  if (d->flags & ~(RT_FRAME_DENOISE_DEMODULATE | RT_FRAME_DENOISE_SAME_INSTANCE)) return frame_denoise_fail(c, "unknown flag bit");
-  if (d->passes == 0 || d->passes > RT_FRAME_DENOISE_MAX_PASSES) return frame_denoise_fail(c, "passes must be 1 .. 5");
-  if (d->step == 0) return frame_denoise_fail(c, "step must be >= 1");
+  if (!d) return refuse(c, kFrameDenoise, "NULL descriptor");
+  if (d->reserved[0] | d->reserved[1]) return refuse(c, kFrameDenoise, "reserved words must be 0");
+  if (d->flags & ~(RT_FRAME_DENOISE_DEMODULATE | RT_FRAME_DENOISE_SAME_INSTANCE)) return refuse(c, kFrameDenoise, "unknown flag bit");
+  if (d->passes == 0 || d->passes > RT_FRAME_DENOISE_MAX_PASSES) return refuse(c, kFrameDenoise, "passes must be 1 .. 5");
+  if (d->step == 0) return refuse(c, kFrameDenoise, "step must be >= 1");
   // step <= 16 and passes <= 5: the shift cannot overflow
   if (d->step > RT_FRAME_DENOISE_MAX_STEP || (d->step << (d->passes - 1)) > RT_FRAME_DENOISE_MAX_STEP)
-    return frame_denoise_fail(c, "step << (passes - 1) must be <= 16");
+    return refuse(c, kFrameDenoise, "step << (passes - 1) must be <= 16");
   return RT_OK;
 }
 // what a call needs of the context, checked before anything is enqueued
 static int frame_denoise_ctx_ok(rt_ctx* c, const rt_frame_denoise_desc* d) {
   const std::string w(kFrameDenoise);
   if (c->fd.form == 1 && (d->step << (d->passes - 1)) > RT_FRAME_LDS_MAX_STEP)
-    return frame_denoise_fail(c, "the LDS form is forced (rt_set_frame_denoise_form) and a spacing above 4 has no LDS window");
-  if (c->dist.active) return frame_denoise_fail(c, "the context is a rank of a sharded image: its G-buffer covers only its own rows");
-  if (c->stripe_count > 1) return frame_denoise_fail(c, "stripes are on: the G-buffer covers only this context's rows");
+    return refuse(c, kFrameDenoise, "the LDS form is forced (rt_set_frame_denoise_form) and a spacing above 4 has no LDS window");
+  if (c->dist.active) return refuse(c, kFrameDenoise, "the context is a rank of a sharded image: its G-buffer covers only its own rows");
+  if (c->stripe_count > 1) return refuse(c, kFrameDenoise, "stripes are on: the G-buffer covers only this context's rows");
   if (!c->width || !c->render_target.ptr || !c->accum.ptr) return fail(c, RT_ERR_NOT_READY, w + ": no screen (rt_resize first)");
   if (c->accum_stale)
     return fail(c, RT_ERR_INVALID, w + ": the bound accumulation buffer was dropped by rt_resize: call rt_bind_accum again");
@@ -3286,11 +3367,11 @@ int rt_denoise_frame_device(rt_ctx* c, const rt_frame_denoise_desc* d, void* dev
   int r = frame_denoise_desc_ok(c, d);
   if (r < 0) return r;
   if (!c) return RT_ERR_INVALID;
-  if (!dev_out) return frame_denoise_fail(c, "NULL output");
+  if (!dev_out) return refuse(c, kFrameDenoise, "NULL output");
   if ((r = frame_denoise_ctx_ok(c, d)) < 0) return r;
   if (dev_out == (void*)accum_ptr(c) || dev_out == c->accum.ptr)
-    return frame_denoise_fail(c, "the output must not be the accumulation buffer");
-  if ((r = query_device_arrays_ok(c, kFrameDenoise, dev_out, dev_out)) < 0) return r;
+    return refuse(c, kFrameDenoise, "the output must not be the accumulation buffer");
+  if ((r = caller_arrays_ok(c, kFrameDenoise, {dev_out})) < 0) return r;
   return frame_denoise_run(c, d, dev_out);
 }
 
@@ -3298,16 +3379,11 @@ int rt_denoise_frame(rt_ctx* c, const rt_frame_denoise_desc* d, float* out, size
   int r = frame_denoise_desc_ok(c, d);
   if (r < 0) return r;
   if (!c) return RT_ERR_INVALID;
-  if (!out) return frame_denoise_fail(c, "NULL output");
+  if (!out) return refuse(c, kFrameDenoise, "NULL output");
   if ((r = frame_denoise_ctx_ok(c, d)) < 0) return r;
   const size_t bytes = (size_t)c->width * c->height * 16;
-  if (cap_bytes < bytes) return frame_denoise_fail(c, "output buffer too small");
-  HIP_TRY(c, hipSetDevice(c->device));
-  if ((r = ensure_buffer(c, c->fd.out, bytes, false)) < 0) return r;
-  if ((r = frame_denoise_run(c, d, c->fd.out.ptr)) < 0) return r;
-  HIP_TRY(c, hipMemcpyAsync(out, c->fd.out.ptr, bytes, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return RT_OK;
+  if (cap_bytes < bytes) return refuse(c, kFrameDenoise, "output buffer too small");
+  return staged_call(c, {{c->fd.out, out, bytes, STAGE_OUT, false}}, [&] { return frame_denoise_run(c, d, c->fd.out.ptr); });
 }
 
 int rt_set_present_denoise(rt_ctx* c, const rt_frame_denoise_desc* d) {
@@ -3320,12 +3396,12 @@ int rt_set_present_denoise(rt_ctx* c, const rt_frame_denoise_desc* d) {
   if (r < 0) return r;
   if (!c) return RT_ERR_INVALID;
   if (c->present_source || c->present_stale)
-    return frame_denoise_fail(c, "a present source is bound (rt_bind_present_source(NULL) first): present() cannot read both");
+    return refuse(c, kFrameDenoise, "a present source is bound (rt_bind_present_source(NULL) first): present() cannot read both");
   if (c->dist.active)
-    return frame_denoise_fail(c, "the context is a rank of a sharded image (rt_dist_init): its G-buffer covers only its own rows");
-  if (c->stripe_count > 1) return frame_denoise_fail(c, "stripes are on (rt_set_stripes): the G-buffer covers only this context's rows");
+    return refuse(c, kFrameDenoise, "the context is a rank of a sharded image (rt_dist_init): its G-buffer covers only its own rows");
+  if (c->stripe_count > 1) return refuse(c, kFrameDenoise, "stripes are on (rt_set_stripes): the G-buffer covers only this context's rows");
   if (c->fd.form == 1 && (d->step << (d->passes - 1)) > RT_FRAME_LDS_MAX_STEP)
-    return frame_denoise_fail(c, "the LDS form is forced (rt_set_frame_denoise_form) and a spacing above 4 has no LDS window");
+    return refuse(c, kFrameDenoise, "the LDS form is forced (rt_set_frame_denoise_form) and a spacing above 4 has no LDS window");
   c->fd.present_desc = *d;
   c->fd.present_on = true;
   c->fd.wanted = true;
@@ -3333,11 +3409,11 @@ int rt_set_present_denoise(rt_ctx* c, const rt_frame_denoise_desc* d) {
 }
 
 int rt_set_frame_denoise_form(rt_ctx* c, int form) {
-  if (form < 0 || form > 2) return frame_denoise_fail(c, "form must be 0 (auto), 1 (LDS) or 2 (direct)");
+  if (form < 0 || form > 2) return refuse(c, kFrameDenoise, "form must be 0 (auto), 1 (LDS) or 2 (direct)");
   if (!c) return RT_ERR_INVALID;
   if (form == 1 && c->fd.present_on &&
       (c->fd.present_desc.step << (c->fd.present_desc.passes - 1)) > RT_FRAME_LDS_MAX_STEP)
-    return frame_denoise_fail(c, "present() filters at a spacing above 4, which has no LDS window");
+    return refuse(c, kFrameDenoise, "present() filters at a spacing above 4, which has no LDS window");
   c->fd.form = form;
   return RT_OK;
 }
@@ -3360,11 +3436,7 @@ int rt_frame_denoise_stats(rt_ctx* c, rt_frame_denoise_report* out) {
 
 // ---- frame temporal: the stage between the prepare stage and the first pass (mi355rt.h "THE FRAME TEMPORAL RULE";
 // k_frame_temporal.hip.h).  It runs inside frame_denoise_run, exactly when the prepare stage does.
-static int frame_temporal_fail(rt_ctx* c, const std::string& what) {
-  const std::string msg = "frame temporal: " + what;
-  if (!c) g_create_error = msg;
-  return fail(c, RT_ERR_INVALID, msg);
-}
+static const char* const kFrameTemporal = "frame temporal";
 // the history, and the prepare outputs that were made beside it: the next call runs both stages again
 static void frame_history_drop(rt_ctx* c) {
   c->ft.have = false;
@@ -3374,11 +3446,11 @@ static void frame_history_drop(rt_ctx* c) {
 
 int rt_set_frame_temporal(rt_ctx* c, const rt_frame_temporal_desc* d) {
   if (d) {
-    if (d->reserved[0] | d->reserved[1] | d->reserved[2]) return frame_temporal_fail(c, "reserved words must be 0");
-    if (d->flags & ~RT_FRAME_TEMPORAL_SAME_INSTANCE) return frame_temporal_fail(c, "unknown flag bit");
+    if (d->reserved[0] | d->reserved[1] | d->reserved[2]) return refuse(c, kFrameTemporal, "reserved words must be 0");
+    if (d->flags & ~RT_FRAME_TEMPORAL_SAME_INSTANCE) return refuse(c, kFrameTemporal, "unknown flag bit");
     if (d->max_history == 0 || d->max_history > RT_FRAME_TEMPORAL_MAX_HISTORY)
-      return frame_temporal_fail(c, "max_history must be 1 .. 256");
-    if (d->var_history == 0) return frame_temporal_fail(c, "var_history must be >= 1");
+      return refuse(c, kFrameTemporal, "max_history must be 1 .. 256");
+    if (d->var_history == 0) return refuse(c, kFrameTemporal, "var_history must be >= 1");
   }
   if (!c) return RT_ERR_INVALID;
   frame_history_drop(c);
@@ -3398,10 +3470,10 @@ int rt_read_frame_history(rt_ctx* c, float* colour, float* moments, size_t cap_p
   const FrameTemporalState& ft = c->ft;
   if (frames_out) *frames_out = ft.frames;
   if (!colour && !moments) return RT_OK;
-  if (!ft.on) return frame_temporal_fail(c, "the stage is off (rt_set_frame_temporal)");
+  if (!ft.on) return refuse(c, kFrameTemporal, "the stage is off (rt_set_frame_temporal)");
   if (!ft.have || !ft.hist[ft.cur].ptr) return fail(c, RT_ERR_NOT_READY, "frame temporal: no history yet");
   const size_t npx = (size_t)c->width * c->height;
-  if (cap_pixels < npx) return frame_temporal_fail(c, "output buffers too small");
+  if (cap_pixels < npx) return refuse(c, kFrameTemporal, "output buffers too small");
   HIP_TRY(c, hipSetDevice(c->device));
   if (colour) HIP_TRY(c, hipMemcpyAsync(colour, ft.hist[ft.cur].ptr, npx * 16, hipMemcpyDeviceToHost, c->stream));
   if (moments) HIP_TRY(c, hipMemcpyAsync(moments, ft.mom[ft.cur].ptr, npx * 8, hipMemcpyDeviceToHost, c->stream));
@@ -3556,7 +3628,7 @@ int rt_bake_atlas_lightmap_device(rt_ctx* c, const rt_lightmap_desc* d, const rt
   rt_bake_atlas_desc bake;
   int r = lightmap_desc_ok(c, d, entries, &bake);
   if (r < 0) return r;
-  if ((r = query_device_arrays_ok(c, kLightmap, dev_out, dev_atlas_uv ? dev_atlas_uv : dev_out)) < 0) return r;
+  if ((r = caller_arrays_ok(c, kLightmap, {dev_out, optional_array(dev_atlas_uv)})) < 0) return r;
   if ((r = lightmap_out_bytes_ok(c, d, out_bytes)) < 0) return r;
   if ((r = bake_atlas_scene_ready(c, &bake, entries, true)) < 0) return refused_under(c, kLightmap, r);
   return lightmap_bake(c, d, &bake, entries, dev_atlas_uv, nullptr, dev_out, n_covered_out, n_filled_out, stats);
@@ -3681,7 +3753,7 @@ int rt_encode_atlas_device(rt_ctx* c, uint32_t width, uint32_t height, uint32_t 
   int r = encode_args_ok(c, width, height, format, dev_in, dev_out, out_bytes);
   if (r < 0) return r;
   if (dev_in == dev_out) return fail(c, RT_ERR_INVALID, std::string(kEncode) + ": the output must not be the input");
-  if ((r = query_device_arrays_ok(c, kEncode, dev_in, dev_out)) < 0) return r;
+  if ((r = caller_arrays_ok(c, kEncode, {dev_in, dev_out})) < 0) return r;
   return launch_encode(c, width * height, format, dev_in, dev_out);
 }
 
@@ -3696,39 +3768,27 @@ int rt_encode_atlas(rt_ctx* c, uint32_t width, uint32_t height, uint32_t format,
     if (out != (const void*)atlas_in) std::memmove(out, atlas_in, bytes);
     return RT_OK;
   }
-  HIP_TRY(c, hipSetDevice(c->device));
-  if ((r = ensure_buffer(c, c->lm.in, (size_t)texels * 16, true)) < 0) return r;
-  if ((r = ensure_buffer(c, c->lm.encoded, bytes, true)) < 0) return r;
-  HIP_TRY(c, hipMemcpyAsync(c->lm.in.ptr, atlas_in, (size_t)texels * 16, hipMemcpyHostToDevice, c->stream));
-  if ((r = launch_encode(c, texels, format, c->lm.in.ptr, c->lm.encoded.ptr)) < 0) return r;
-  HIP_TRY(c, hipMemcpyAsync(out, c->lm.encoded.ptr, bytes, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return RT_OK;
+  return staged_call(c, {{c->lm.in, atlas_in, (size_t)texels * 16, STAGE_IN}, {c->lm.encoded, out, bytes, STAGE_OUT}},
+                     [&] { return launch_encode(c, texels, format, c->lm.in.ptr, c->lm.encoded.ptr); });
 }
 
 // ---- irradiance volumes (mi355rt.h "THE VOLUME RULE"; k_volume.hip.h): a grid of probes baked through the probe gather's
 // device path, finished into windowed irradiance coefficients, sampled trilinearly, exported as texel layers.
 static const char* const kVolume = "volume";
-// a refusal that needs no context: without one the message is what rt_last_error(NULL) returns
-static int volume_fail(rt_ctx* c, const std::string& msg) {
-  if (!c) g_create_error = msg;
-  return fail(c, RT_ERR_INVALID, msg);
-}
 // everything the limits say about a descriptor; *n_out = nx * ny * nz
 static int volume_desc_ok(rt_ctx* c, const rt_volume_desc* d, uint32_t* n_out) {
-  const std::string w(kVolume);
-  if (!d) return volume_fail(c, w + ": NULL descriptor");
+  if (!d) return refuse(c, kVolume, "NULL descriptor");
   if (d->nx == 0 || d->ny == 0 || d->nz == 0 || d->nx > 1024 || d->ny > 1024 || d->nz > 1024)
-    return volume_fail(c, w + ": nx, ny and nz must be 1 .. 1024");
+    return refuse(c, kVolume, "nx, ny and nz must be 1 .. 1024");
   const uint64_t n = (uint64_t)d->nx * d->ny * d->nz;
-  if (n > (1ull << 24)) return volume_fail(c, w + ": nx * ny * nz must be <= 2^24");
-  if ((uint64_t)d->pad_first + n > (1ull << 31)) return volume_fail(c, w + ": pad_first + nx * ny * nz must be <= 2^31");
+  if (n > (1ull << 24)) return refuse(c, kVolume, "nx * ny * nz must be <= 2^24");
+  if ((uint64_t)d->pad_first + n > (1ull << 31)) return refuse(c, kVolume, "pad_first + nx * ny * nz must be <= 2^31");
   for (int a = 0; a < 3; a++) {
-    if (!(std::isfinite(d->step[a]) && d->step[a] > 0.0f)) return volume_fail(c, w + ": step must be finite and > 0");
-    if (!(std::isfinite(d->window[a]) && d->window[a] >= 0.0f)) return volume_fail(c, w + ": window must be finite and >= 0");
+    if (!(std::isfinite(d->step[a]) && d->step[a] > 0.0f)) return refuse(c, kVolume, "step must be finite and > 0");
+    if (!(std::isfinite(d->window[a]) && d->window[a] >= 0.0f)) return refuse(c, kVolume, "window must be finite and >= 0");
   }
-  if (d->max_hit_fraction != d->max_hit_fraction) return volume_fail(c, w + ": max_hit_fraction must not be NaN");
-  if (d->reserved) return volume_fail(c, w + ": reserved must be 0");
+  if (d->max_hit_fraction != d->max_hit_fraction) return refuse(c, kVolume, "max_hit_fraction must not be NaN");
+  if (d->reserved) return refuse(c, kVolume, "reserved must be 0");
   *n_out = (uint32_t)n;
   return RT_OK;
 }
@@ -3755,8 +3815,7 @@ int rt_bake_volume_device(rt_ctx* c, const rt_volume_desc* desc, uint32_t max_de
   int r = volume_desc_ok(c, desc, &n);
   if (r < 0 || !c) return RT_ERR_INVALID;
   if ((r = path_query_args_ok(c, pq_probe, n, spp)) < 0) return refused_under(c, kVolume, r);
-  if (!dev_out) return fail(c, RT_ERR_INVALID, std::string(kVolume) + ": NULL array");
-  if ((r = query_device_arrays_ok(c, kVolume, dev_out, dev_out)) < 0) return r;
+  if ((r = caller_arrays_ok(c, kVolume, {dev_out})) < 0) return r;
   return launch_bake_volume(c, *desc, n, max_depth, spp, seed, dev_out, c->detailed_counters);
 }
 
@@ -3767,12 +3826,9 @@ int rt_bake_volume(rt_ctx* c, const rt_volume_desc* desc, uint32_t max_depth, ui
   if (r < 0 || !c) return RT_ERR_INVALID;
   if ((r = path_query_args_ok(c, pq_probe, n, spp)) < 0) return refused_under(c, kVolume, r);
   if (!out) return fail(c, RT_ERR_INVALID, std::string(kVolume) + ": NULL array");
-  HIP_TRY(c, hipSetDevice(c->device));
-  const size_t bytes = (size_t)n * sizeof(rt_probe_sh9);
-  if ((r = ensure_buffer(c, c->pr.out, bytes, true)) < 0) return r;
-  if ((r = launch_bake_volume(c, *desc, n, max_depth, spp, seed, c->pr.out.ptr, stats != nullptr)) < 0) return r;
-  HIP_TRY(c, hipMemcpyAsync(out, c->pr.out.ptr, bytes, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  r = staged_call(c, {{c->pr.out, out, (size_t)n * sizeof(rt_probe_sh9), STAGE_OUT}},
+                  [&] { return launch_bake_volume(c, *desc, n, max_depth, spp, seed, c->pr.out.ptr, stats != nullptr); });
+  if (r < 0) return r;
   if (stats) return composed_gather_stats(c, cg_probe, stats);
   return RT_OK;
 }
@@ -3804,8 +3860,7 @@ int rt_sample_volume_device(rt_ctx* c, const rt_volume_desc* desc, const void* d
   int r = volume_desc_ok(c, desc, &probes);
   if (r < 0 || !c) return RT_ERR_INVALID;
   if ((r = volume_sample_args_ok(c, n, dev_volume, dev_points, dev_out)) != RT_OK) return r < 0 ? r : RT_OK;
-  if ((r = query_device_arrays_ok(c, kVolume, dev_volume, dev_out)) < 0) return r;
-  if ((r = query_device_arrays_ok(c, kVolume, dev_points, dev_out)) < 0) return r;
+  if ((r = caller_arrays_ok(c, kVolume, {dev_volume, dev_points, dev_out})) < 0) return r;
   return launch_sample_volume(c, *desc, dev_volume, dev_points, n, dev_out);
 }
 
@@ -3815,24 +3870,19 @@ int rt_sample_volume(rt_ctx* c, const rt_volume_desc* desc, const rt_probe_sh9* 
   int r = volume_desc_ok(c, desc, &probes);
   if (r < 0 || !c) return RT_ERR_INVALID;
   if ((r = volume_sample_args_ok(c, n, volume, points, out)) != RT_OK) return r < 0 ? r : RT_OK;
-  HIP_TRY(c, hipSetDevice(c->device));
-  const size_t vol_bytes = (size_t)probes * sizeof(rt_probe_sh9);
-  if ((r = ensure_buffer(c, c->vol.volume, vol_bytes, true)) < 0) return r;
-  if ((r = ensure_buffer(c, c->vol.points, (size_t)n * sizeof(rt_gather_point), true)) < 0) return r;
-  if ((r = ensure_buffer(c, c->vol.out, (size_t)n * sizeof(rt_irradiance), true)) < 0) return r;
-  HIP_TRY(c, hipMemcpyAsync(c->vol.volume.ptr, volume, vol_bytes, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(c->vol.points.ptr, points, (size_t)n * sizeof(rt_gather_point), hipMemcpyHostToDevice, c->stream));
-  if ((r = launch_sample_volume(c, *desc, c->vol.volume.ptr, c->vol.points.ptr, n, c->vol.out.ptr)) < 0) return r;
-  HIP_TRY(c, hipMemcpyAsync(out, c->vol.out.ptr, (size_t)n * sizeof(rt_irradiance), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return RT_OK;
+  VolumeState& st = c->vol;
+  return staged_call(c,
+                     {{st.volume, volume, (size_t)probes * sizeof(rt_probe_sh9), STAGE_IN},
+                      {st.points, points, (size_t)n * sizeof(rt_gather_point), STAGE_IN},
+                      {st.out, out, (size_t)n * sizeof(rt_irradiance), STAGE_OUT}},
+                     [&] { return launch_sample_volume(c, *desc, st.volume.ptr, st.points.ptr, n, st.out.ptr); });
 }
 
 // the arguments of an export beside the descriptor: the format is f32 or f16, the capacity holds seven layers
 static int volume_encode_args_ok(rt_ctx* c, uint32_t probes, uint32_t format, const void* volume, const void* out, size_t cap) {
   const std::string w(kVolume);
-  if (format == RT_LIGHTMAP_RGBE8) return volume_fail(c, w + ": RT_LIGHTMAP_RGBE8 cannot hold signed coefficients");
-  if (format != RT_LIGHTMAP_F32 && format != RT_LIGHTMAP_F16) return volume_fail(c, w + ": format must be RT_LIGHTMAP_F32 or _F16");
+  if (format == RT_LIGHTMAP_RGBE8) return refuse(c, kVolume, "RT_LIGHTMAP_RGBE8 cannot hold signed coefficients");
+  if (format != RT_LIGHTMAP_F32 && format != RT_LIGHTMAP_F16) return refuse(c, kVolume, "format must be RT_LIGHTMAP_F32 or _F16");
   if (!c) return RT_ERR_INVALID;
   if (!volume || !out) return fail(c, RT_ERR_INVALID, w + ": NULL array");
   if (cap < 7 * (size_t)probes * lightmap_texel_bytes(format))
@@ -3857,7 +3907,7 @@ int rt_encode_volume_device(rt_ctx* c, const rt_volume_desc* desc, uint32_t form
   if (r < 0) return r;
   if ((r = volume_encode_args_ok(c, probes, format, dev_volume, dev_out, cap)) < 0) return r;
   if (dev_volume == dev_out) return fail(c, RT_ERR_INVALID, std::string(kVolume) + ": the output must not be the input");
-  if ((r = query_device_arrays_ok(c, kVolume, dev_volume, dev_out)) < 0) return r;
+  if ((r = caller_arrays_ok(c, kVolume, {dev_volume, dev_out})) < 0) return r;
   return launch_volume_layers(c, probes, format, dev_volume, dev_out);
 }
 
@@ -3866,25 +3916,14 @@ int rt_encode_volume(rt_ctx* c, const rt_volume_desc* desc, uint32_t format, con
   int r = volume_desc_ok(c, desc, &probes);
   if (r < 0) return r;
   if ((r = volume_encode_args_ok(c, probes, format, volume, out, cap)) < 0) return r;
-  HIP_TRY(c, hipSetDevice(c->device));
   const size_t in_bytes = (size_t)probes * sizeof(rt_probe_sh9), out_bytes = 7 * (size_t)probes * lightmap_texel_bytes(format);
-  if ((r = ensure_buffer(c, c->vol.volume, in_bytes, true)) < 0) return r;
-  if ((r = ensure_buffer(c, c->vol.encoded, out_bytes, true)) < 0) return r;
-  HIP_TRY(c, hipMemcpyAsync(c->vol.volume.ptr, volume, in_bytes, hipMemcpyHostToDevice, c->stream));
-  if ((r = launch_volume_layers(c, probes, format, c->vol.volume.ptr, c->vol.encoded.ptr)) < 0) return r;
-  HIP_TRY(c, hipMemcpyAsync(out, c->vol.encoded.ptr, out_bytes, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return RT_OK;
+  return staged_call(c, {{c->vol.volume, volume, in_bytes, STAGE_IN}, {c->vol.encoded, out, out_bytes, STAGE_OUT}},
+                     [&] { return launch_volume_layers(c, probes, format, c->vol.volume.ptr, c->vol.encoded.ptr); });
 }
 
 // ---- reflection probes (mi355rt.h "THE REFLECTION RULE"; k_reflection.hip.h): octahedral radiance maps captured through the
 // radiance query's kernel, one path item per (texel, sample), and their GGX-filtered chains.
 static const char* const kReflection = "reflection";
-// a refusal that needs no context: without one the message is what rt_last_error(NULL) returns
-static int reflection_fail(rt_ctx* c, const std::string& msg) {
-  if (!c) g_create_error = msg;
-  return fail(c, RT_ERR_INVALID, msg);
-}
 struct ReflectionShape {
   uint32_t size_log2;
   uint32_t map, chain;   // texels of level 0, of a whole chain
@@ -3892,21 +3931,20 @@ struct ReflectionShape {
 enum { RF_CAPTURE = 1, RF_FILTER = 2 };
 // everything the limits say about a descriptor and n, for the parts (RF_*) an entry runs
 static int reflection_desc_ok(rt_ctx* c, const rt_reflection_desc* d, uint32_t n, int parts, ReflectionShape* sh) {
-  const std::string w(kReflection);
-  if (!d) return reflection_fail(c, w + ": NULL descriptor");
-  if (d->size < 8 || d->size > 512 || (d->size & (d->size - 1u))) return reflection_fail(c, w + ": size must be a power of two in 8 .. 512");
-  if (d->levels < 2) return reflection_fail(c, w + ": levels must be >= 2");
-  if (d->levels > 32 || (d->size >> (d->levels - 1u)) < 4) return reflection_fail(c, w + ": size >> (levels - 1) must be >= 4");
-  if ((parts & RF_CAPTURE) && (d->spt == 0 || d->spt > 65536)) return reflection_fail(c, w + ": spt must be 1 .. 65536");
+  if (!d) return refuse(c, kReflection, "NULL descriptor");
+  if (d->size < 8 || d->size > 512 || (d->size & (d->size - 1u))) return refuse(c, kReflection, "size must be a power of two in 8 .. 512");
+  if (d->levels < 2) return refuse(c, kReflection, "levels must be >= 2");
+  if (d->levels > 32 || (d->size >> (d->levels - 1u)) < 4) return refuse(c, kReflection, "size >> (levels - 1) must be >= 4");
+  if ((parts & RF_CAPTURE) && (d->spt == 0 || d->spt > 65536)) return refuse(c, kReflection, "spt must be 1 .. 65536");
   if ((parts & RF_FILTER) && (d->filter_samples < 64 || d->filter_samples > 4096 || (d->filter_samples & 63u)))
-    return reflection_fail(c, w + ": filter_samples must be a multiple of 64 in 64 .. 4096");
+    return refuse(c, kReflection, "filter_samples must be a multiple of 64 in 64 .. 4096");
   for (int k = 0; k < 4; k++)
-    if (d->reserved[k]) return reflection_fail(c, w + ": reserved must be 0");
+    if (d->reserved[k]) return refuse(c, kReflection, "reserved must be 0");
   sh->size_log2 = (uint32_t)__builtin_ctz(d->size);
   sh->map = d->size * d->size;
   sh->chain = 0;
   for (uint32_t m = 0; m < d->levels; m++) sh->chain += (d->size >> m) * (d->size >> m);
-  if ((uint64_t)n * sh->chain >= (1ull << 31)) return reflection_fail(c, w + ": n * texels of a chain must be below 2^31");
+  if ((uint64_t)n * sh->chain >= (1ull << 31)) return refuse(c, kReflection, "n * texels of a chain must be below 2^31");
   return RT_OK;
 }
 // the host entries of capture and bake: every probe's pads stay below 2^31
@@ -3923,46 +3961,30 @@ static void reflection_no_work(rt_ctx* c) {
 
 // Enqueue a capture: the n * size^2 texels of the call in batches of whole texels, each k_reflection_rays -> the radiance
 // query's kernel (spp = 1, seed = 0 on the pad' rays) -> k_reflection_texels, map p to d_out + p * out_stride texels.  The
-// probe gather's sequence with a global first-texel index per batch, so a probe may span batches and a batch probes.
+// items of run_batches are the texels, under a global index: a probe may span batches and a batch probes.
 static int launch_reflection_capture(rt_ctx* c, const rt_reflection_desc& D, const ReflectionShape& sh, const void* d_probes,
                                      uint32_t n, uint32_t max_depth, uint32_t seed, void* d_out, uint32_t out_stride, bool detail) {
   const PathQueryKind& k = pq_reflection;
-  int r = query_scene_ready(c, k.what, true);
+  const int r = query_scene_ready(c, k.what, true);
   if (r < 0) return r;
-  const uint32_t spt = D.spt, total = n * sh.map;                 // < 2^31
-  const uint32_t per_batch = RT_PROBE_BATCH_SAMPLES / spt;      // whole texels: >= 64, spt being <= 65536
-  const size_t scratch_items = (size_t)std::min(total, per_batch) * spt;
-  if ((r = ensure_buffer(c, c->pr_rays, scratch_items * sizeof(rt_ray), false)) < 0) return r;
-  if ((r = ensure_buffer(c, c->pr_rad, scratch_items * sizeof(rt_radiance), false)) < 0) return r;
-  QueryState& q = c->*k.state;
-  rt_radiance_stats& last = c->*k.last;
-  q.batches_timed = 0;
-  rt_radiance_stats sum = rt_radiance_stats();
-  uint32_t batch = 0;
-  for (uint32_t first = 0; first < total; first += per_batch, batch++) {
-    const uint32_t nt = std::min(per_batch, total - first);
-    const uint32_t items = nt * spt;                            // <= RT_PROBE_BATCH_SAMPLES
-    float4* rays = (float4*)c->pr_rays.ptr;
-    float4* rad = (float4*)c->pr_rad.ptr;
-    hipLaunchKernelGGL(rtk::k_reflection_rays, dim3((items + 255u) / 256u), dim3(256), 0, c->stream, (const float4*)d_probes, rays,
-                       items, spt, seed, first, sh.size_log2);
-    HIP_TRY(c, hipGetLastError());
-    if (q.batch_ev.size() <= batch) q.batch_ev.emplace_back();
-    if ((r = launch_path_query(c, k, rays, items, max_depth, 1u, 0u, rad, detail, batch != 0, &q.batch_ev[batch])) < 0) {
-      last = rt_radiance_stats();
-      return r;
-    }
-    if (c->timing) q.batches_timed = batch + 1;
-    sum.lds = last.lds;
-    sum.workgroups += last.workgroups;
-    hipLaunchKernelGGL(rtk::k_reflection_texels, dim3((nt + 255u) / 256u), dim3(256), 0, c->stream, (const float4*)d_probes,
-                       (const float4*)rad, (float4*)d_out, nt, spt, first, sh.size_log2, out_stride);
-    HIP_TRY(c, hipGetLastError());
-  }
-  sum.rays = total;
-  sum.samples = (uint64_t)total * spt;
-  last = sum;
-  return RT_OK;
+  const uint32_t spt = D.spt;
+  return run_batches(
+      c, c->*k.state, c->*k.last, n * sh.map, spt,
+      [&](uint32_t first, uint32_t, uint32_t items) -> int {
+        hipLaunchKernelGGL(rtk::k_reflection_rays, dim3((items + 255u) / 256u), dim3(256), 0, c->stream, (const float4*)d_probes,
+                           (float4*)c->pr_rays.ptr, items, spt, seed, first, sh.size_log2);
+        HIP_TRY(c, hipGetLastError());
+        return RT_OK;
+      },
+      [&](const void* rays, uint32_t items, void* rad, bool keep_counts, EventPair* ev) {
+        return launch_path_query(c, k, rays, items, max_depth, 1u, 0u, rad, detail, keep_counts, ev);
+      },
+      [&](uint32_t first, uint32_t nt) -> int {
+        hipLaunchKernelGGL(rtk::k_reflection_texels, dim3((nt + 255u) / 256u), dim3(256), 0, c->stream, (const float4*)d_probes,
+                           (const float4*)c->pr_rad.ptr, (float4*)d_out, nt, spt, first, sh.size_log2, out_stride);
+        HIP_TRY(c, hipGetLastError());
+        return RT_OK;
+      });
 }
 
 // Enqueue a filter: level 0 of chain p is read at d_src + p * src_stride texels; where that is not the chain itself the maps
@@ -4012,7 +4034,7 @@ int rt_capture_reflection_device(rt_ctx* c, const rt_reflection_desc* desc, cons
   int r = reflection_desc_ok(c, desc, n, RF_CAPTURE, &sh);
   if (r < 0 || !c) return RT_ERR_INVALID;
   if (n == 0) return reflection_no_work(c), RT_OK;
-  if ((r = query_device_arrays_ok(c, kReflection, dev_probes, dev_maps)) < 0) return r;
+  if ((r = caller_arrays_ok(c, kReflection, {dev_probes, dev_maps})) < 0) return r;
   return launch_reflection_capture(c, *desc, sh, dev_probes, n, max_depth, seed, dev_maps, sh.map, c->detailed_counters);
 }
 
@@ -4022,7 +4044,7 @@ int rt_bake_reflection_device(rt_ctx* c, const rt_reflection_desc* desc, const v
   int r = reflection_desc_ok(c, desc, n, RF_CAPTURE | RF_FILTER, &sh);
   if (r < 0 || !c) return RT_ERR_INVALID;
   if (n == 0) return reflection_no_work(c), RT_OK;
-  if ((r = query_device_arrays_ok(c, kReflection, dev_probes, dev_chains)) < 0) return r;
+  if ((r = caller_arrays_ok(c, kReflection, {dev_probes, dev_chains})) < 0) return r;
   if ((r = launch_reflection_capture(c, *desc, sh, dev_probes, n, max_depth, seed, dev_chains, sh.chain, c->detailed_counters)) < 0)
     return r;
   return launch_reflection_filter(c, *desc, sh, dev_chains, sh.chain, dev_chains, n);
@@ -4033,7 +4055,7 @@ int rt_filter_reflection_device(rt_ctx* c, const rt_reflection_desc* desc, const
   int r = reflection_desc_ok(c, desc, n, RF_FILTER, &sh);
   if (r < 0 || !c) return RT_ERR_INVALID;
   if (n == 0) return RT_OK;
-  if ((r = query_device_arrays_ok(c, kReflection, dev_maps, dev_chains)) < 0) return r;
+  if ((r = caller_arrays_ok(c, kReflection, {dev_maps, dev_chains})) < 0) return r;
   return launch_reflection_filter(c, *desc, sh, dev_maps, dev_maps == (const void*)dev_chains ? sh.chain : sh.map, dev_chains, n);
 }
 
@@ -4053,26 +4075,21 @@ static int reflection_from_host(rt_ctx* c, const rt_reflection_desc* desc, int p
   }
   if (!(capture ? (const void*)probes : (const void*)maps) || !out) return fail(c, RT_ERR_INVALID, std::string(kReflection) + ": NULL array");
   if (capture && (r = reflection_pads_ok(c, probes, n, sh)) < 0) return r;
-  HIP_TRY(c, hipSetDevice(c->device));
   ReflectionState& st = c->rfl;
   const size_t map_bytes = (size_t)n * sh.map * 16, chain_bytes = (size_t)n * sh.chain * 16;
-  DeviceBuffer& result = filter ? st.chains : st.maps;
-  const size_t result_bytes = filter ? chain_bytes : map_bytes;
-  if ((r = ensure_buffer(c, result, result_bytes, true)) < 0) return r;
-  if (capture) {
-    if ((r = ensure_buffer(c, st.probes, (size_t)n * sizeof(rt_probe), true)) < 0) return r;
-    HIP_TRY(c, hipMemcpyAsync(st.probes.ptr, probes, (size_t)n * sizeof(rt_probe), hipMemcpyHostToDevice, c->stream));
-    if ((r = launch_reflection_capture(c, *desc, sh, st.probes.ptr, n, max_depth, seed, result.ptr, filter ? sh.chain : sh.map,
-                                       stats != nullptr)) < 0)
-      return r;
-    if (filter && (r = launch_reflection_filter(c, *desc, sh, result.ptr, sh.chain, result.ptr, n)) < 0) return r;
-  } else {
-    if ((r = ensure_buffer(c, st.maps, map_bytes, true)) < 0) return r;
-    HIP_TRY(c, hipMemcpyAsync(st.maps.ptr, maps, map_bytes, hipMemcpyHostToDevice, c->stream));
-    if ((r = launch_reflection_filter(c, *desc, sh, st.maps.ptr, sh.map, result.ptr, n)) < 0) return r;
-  }
-  HIP_TRY(c, hipMemcpyAsync(out, result.ptr, result_bytes, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  DeviceBuffer& result = filter ? st.chains : st.maps;   // (a filter alone reads st.maps and writes st.chains)
+  r = staged_call(c,
+                  {{result, out, filter ? chain_bytes : map_bytes, STAGE_OUT},
+                   {st.probes, probes, (size_t)n * sizeof(rt_probe), STAGE_IN, true, capture},
+                   {st.maps, maps, map_bytes, STAGE_IN, true, !capture}},
+                  [&] {
+                    if (!capture) return launch_reflection_filter(c, *desc, sh, st.maps.ptr, sh.map, result.ptr, n);
+                    const int e = launch_reflection_capture(c, *desc, sh, st.probes.ptr, n, max_depth, seed, result.ptr,
+                                                            filter ? sh.chain : sh.map, stats != nullptr);
+                    if (e < 0 || !filter) return e;
+                    return launch_reflection_filter(c, *desc, sh, result.ptr, sh.chain, result.ptr, n);
+                  });
+  if (r < 0) return r;
   if (capture && stats) return rt_reflection_stats(c, stats);
   return RT_OK;
 }
@@ -4093,98 +4110,60 @@ int rt_bake_reflection(rt_ctx* c, const rt_reflection_desc* desc, const rt_probe
 // octahedral map of distance moments, captured through the ray query's kernel, one ray per (texel, sample); a sampler that
 // weights each corner by a Chebyshev bound from them; the export into bordered tiles.
 static const char* const kVisibility = "volume visibility";
-// a refusal that needs no context: without one the message is what rt_last_error(NULL) returns
-static int visibility_fail(rt_ctx* c, const std::string& msg) {
-  if (!c) g_create_error = msg;
-  return fail(c, RT_ERR_INVALID, msg);
-}
 enum { VV_BAKE = 1 };
 // everything the limits say about the two descriptors, for the parts (VV_*) an entry runs; *n_out = nx * ny * nz
 static int visibility_desc_ok(rt_ctx* c, const rt_volume_desc* d, const rt_volume_visibility_desc* v, int parts, uint32_t* n_out) {
   int r = volume_desc_ok(c, d, n_out);
   if (r < 0) return r;
-  const std::string w(kVisibility);
-  if (!v) return visibility_fail(c, w + ": NULL descriptor");
-  if (v->size < 4 || v->size > 32 || (v->size & (v->size - 1u))) return visibility_fail(c, w + ": size must be a power of two in 4 .. 32");
-  if ((parts & VV_BAKE) && (v->spt == 0 || v->spt > 65536)) return visibility_fail(c, w + ": spt must be 1 .. 65536");
-  if (!(std::isfinite(v->max_distance) && v->max_distance > 0.0f)) return visibility_fail(c, w + ": max_distance must be finite and > 0");
-  if (!(std::isfinite(v->normal_bias) && v->normal_bias >= 0.0f)) return visibility_fail(c, w + ": normal_bias must be finite and >= 0");
-  if (!(v->min_visibility >= 0.0f && v->min_visibility <= 1.0f)) return visibility_fail(c, w + ": min_visibility must be in [0, 1]");
-  if (!(v->crush_threshold >= 0.0f && v->crush_threshold <= 1.0f)) return visibility_fail(c, w + ": crush_threshold must be in [0, 1]");
-  if (v->flags & ~RT_VOLUME_VIS_BACKFACE) return visibility_fail(c, w + ": unknown flags");
-  if (v->reserved) return visibility_fail(c, w + ": reserved must be 0");
+  if (!v) return refuse(c, kVisibility, "NULL descriptor");
+  if (v->size < 4 || v->size > 32 || (v->size & (v->size - 1u))) return refuse(c, kVisibility, "size must be a power of two in 4 .. 32");
+  if ((parts & VV_BAKE) && (v->spt == 0 || v->spt > 65536)) return refuse(c, kVisibility, "spt must be 1 .. 65536");
+  if (!(std::isfinite(v->max_distance) && v->max_distance > 0.0f)) return refuse(c, kVisibility, "max_distance must be finite and > 0");
+  if (!(std::isfinite(v->normal_bias) && v->normal_bias >= 0.0f)) return refuse(c, kVisibility, "normal_bias must be finite and >= 0");
+  if (!(v->min_visibility >= 0.0f && v->min_visibility <= 1.0f)) return refuse(c, kVisibility, "min_visibility must be in [0, 1]");
+  if (!(v->crush_threshold >= 0.0f && v->crush_threshold <= 1.0f)) return refuse(c, kVisibility, "crush_threshold must be in [0, 1]");
+  if (v->flags & ~RT_VOLUME_VIS_BACKFACE) return refuse(c, kVisibility, "unknown flags");
+  if (v->reserved) return refuse(c, kVisibility, "reserved must be 0");
   const uint64_t texels = (uint64_t)*n_out * v->size * v->size;
-  if (texels >= (1ull << 31)) return visibility_fail(c, w + ": nx * ny * nz * size * size must be below 2^31");
+  if (texels >= (1ull << 31)) return refuse(c, kVisibility, "nx * ny * nz * size * size must be below 2^31");
   if ((parts & VV_BAKE) && (uint64_t)d->pad_first + texels > (1ull << 31))
-    return visibility_fail(c, w + ": pad_first + nx * ny * nz * size * size must be <= 2^31");
-  return RT_OK;
-}
-// the caller's arrays: there and, for the device entries, 16-byte aligned
-static int visibility_arrays_ok(rt_ctx* c, std::initializer_list<const void*> arrays, bool device) {
-  uintptr_t bits = 0;
-  for (const void* a : arrays) {
-    if (!a) return visibility_fail(c, std::string(kVisibility) + ": NULL array");
-    bits |= (uintptr_t)a;
-  }
-  if (device && (bits & 15u)) return visibility_fail(c, std::string(kVisibility) + ": device arrays must be 16-byte aligned");
+    return refuse(c, kVisibility, "pad_first + nx * ny * nz * size * size must be <= 2^31");
   return RT_OK;
 }
 
 // Enqueue a bake: the n * size^2 texels of the grid in batches of whole texels, each k_visibility_rays -> the ray query's
-// closest-hit kernel -> k_visibility_texels.  The reflection capture's sequence on the ray query: a probe may span batches and
-// a batch probes.
+// closest-hit kernel -> k_visibility_texels.  The items of run_batches are the texels, as in a reflection capture: a probe may
+// span batches and a batch probes.
 static int launch_visibility_bake(rt_ctx* c, const rt_volume_desc& D, const rt_volume_visibility_desc& V, uint32_t n, uint32_t seed,
                                   void* d_out, bool detail) {
-  int r = query_scene_ready(c, kVisibility, false);
+  const int r = query_scene_ready(c, kVisibility, false);
   if (r < 0) return r;
-  const uint32_t size_log2 = (uint32_t)__builtin_ctz(V.size);
-  const uint32_t spt = V.spt, total = n * V.size * V.size;      // < 2^31
-  const uint32_t per_batch = RT_PROBE_BATCH_SAMPLES / spt;      // whole texels: >= 64, spt being <= 65536
-  const size_t scratch_items = (size_t)std::min(total, per_batch) * spt;
-  static_assert(sizeof(rt_ray_hit) == sizeof(rt_radiance), "the hits of a batch live in the radiance scratch");
-  if ((r = ensure_buffer(c, c->pr_rays, scratch_items * sizeof(rt_ray), false)) < 0) return r;
-  if ((r = ensure_buffer(c, c->pr_rad, scratch_items * sizeof(rt_ray_hit), false)) < 0) return r;
-  QueryState& q = c->vv;
-  q.batches_timed = 0;
-  rt_ray_stats sum = rt_ray_stats();
-  uint32_t batch = 0;
-  for (uint32_t first = 0; first < total; first += per_batch, batch++) {
-    const uint32_t nt = std::min(per_batch, total - first);
-    const uint32_t items = nt * spt;                            // <= RT_PROBE_BATCH_SAMPLES
-    float4* rays = (float4*)c->pr_rays.ptr;
-    uint4* hits = (uint4*)c->pr_rad.ptr;
-    hipLaunchKernelGGL(rtk::k_visibility_rays, dim3((items + 255u) / 256u), dim3(256), 0, c->stream, D, rays, items, spt, seed, first,
-                       size_log2, V.max_distance);
-    HIP_TRY(c, hipGetLastError());
-    if (q.batch_ev.size() <= batch) q.batch_ev.emplace_back();
-    if ((r = launch_ray_query_on(c, q, c->vv_last, kVisibility, rays, items, RT_RAYS_CLOSEST, 0.001f, hits, detail, batch != 0,
-                                 &q.batch_ev[batch])) < 0) {
-      c->vv_last = rt_ray_stats();
-      return r;
-    }
-    if (c->timing) q.batches_timed = batch + 1;
-    sum.walk = c->vv_last.walk;
-    sum.lds = c->vv_last.lds;
-    sum.rayreg = c->vv_last.rayreg;
-    sum.workgroups += c->vv_last.workgroups;
-    hipLaunchKernelGGL(rtk::k_visibility_texels, dim3((nt + 255u) / 256u), dim3(256), 0, c->stream, (const uint4*)hits, (float2*)d_out,
-                       nt, spt, first, V.max_distance);
-    HIP_TRY(c, hipGetLastError());
-  }
-  c->vv_last = sum;
-  return RT_OK;
+  const uint32_t size_log2 = (uint32_t)__builtin_ctz(V.size), spt = V.spt;
+  return run_batches(
+      c, c->vv, c->vv_last, n * V.size * V.size, spt,
+      [&](uint32_t first, uint32_t, uint32_t items) -> int {
+        hipLaunchKernelGGL(rtk::k_visibility_rays, dim3((items + 255u) / 256u), dim3(256), 0, c->stream, D, (float4*)c->pr_rays.ptr,
+                           items, spt, seed, first, size_log2, V.max_distance);
+        HIP_TRY(c, hipGetLastError());
+        return RT_OK;
+      },
+      [&](const void* rays, uint32_t items, void* hits, bool keep_counts, EventPair* ev) {
+        return launch_ray_query_on(c, c->vv, c->vv_last, kVisibility, rays, items, RT_RAYS_CLOSEST, 0.001f, hits, detail,
+                                   keep_counts, ev);
+      },
+      [&](uint32_t first, uint32_t nt) -> int {
+        hipLaunchKernelGGL(rtk::k_visibility_texels, dim3((nt + 255u) / 256u), dim3(256), 0, c->stream,
+                           (const uint4*)c->pr_rad.ptr, (float2*)d_out, nt, spt, first, V.max_distance);
+        HIP_TRY(c, hipGetLastError());
+        return RT_OK;
+      });
 }
 
 int rt_volume_visibility_stats(rt_ctx* c, rt_ray_stats* out) {
   if (!c || !out) return RT_ERR_INVALID;
   const int r = ray_query_stats_of(c, c->vv, c->vv_last, out);   // fences the stream; the time is that of the batches
   if (r < 0) return r;
-  for (uint32_t b = 0; b < c->vv.batches_timed; b++) {
-    float ms = 0.0f;
-    HIP_TRY(c, hipEventElapsedTime(&ms, c->vv.batch_ev[b].a, c->vv.batch_ev[b].b));
-    out->kernel_ms += (double)ms;
-  }
-  return RT_OK;
+  return batch_time_ms(c, c->vv, &out->kernel_ms);
 }
 
 int rt_bake_volume_visibility_device(rt_ctx* c, const rt_volume_desc* desc, const rt_volume_visibility_desc* vis, uint32_t seed,
@@ -4192,8 +4171,8 @@ int rt_bake_volume_visibility_device(rt_ctx* c, const rt_volume_desc* desc, cons
   uint32_t n = 0;
   int r = visibility_desc_ok(c, desc, vis, VV_BAKE, &n);
   if (r < 0) return r;
-  if ((r = visibility_arrays_ok(c, {dev_out}, true)) < 0 || !c) return RT_ERR_INVALID;
-  if ((r = query_device_arrays_ok(c, kVisibility, dev_out, dev_out)) < 0) return r;
+  if ((r = caller_arrays_ok(c, kVisibility, {dev_out})) < 0) return r;
+  if (!c) return RT_ERR_INVALID;
   return launch_visibility_bake(c, *desc, *vis, n, seed, dev_out, c->detailed_counters);
 }
 
@@ -4202,13 +4181,10 @@ int rt_bake_volume_visibility(rt_ctx* c, const rt_volume_desc* desc, const rt_vo
   uint32_t n = 0;
   int r = visibility_desc_ok(c, desc, vis, VV_BAKE, &n);
   if (r < 0) return r;
-  if ((r = visibility_arrays_ok(c, {out}, false)) < 0 || !c) return RT_ERR_INVALID;
-  HIP_TRY(c, hipSetDevice(c->device));
-  const size_t bytes = (size_t)n * vis->size * vis->size * 8;
-  if ((r = ensure_buffer(c, c->vis.maps, bytes, true)) < 0) return r;
-  if ((r = launch_visibility_bake(c, *desc, *vis, n, seed, c->vis.maps.ptr, stats != nullptr)) < 0) return r;
-  HIP_TRY(c, hipMemcpyAsync(out, c->vis.maps.ptr, bytes, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if ((r = caller_arrays_ok(c, kVisibility, {out}, false)) < 0 || !c) return RT_ERR_INVALID;
+  r = staged_call(c, {{c->vis.maps, out, (size_t)n * vis->size * vis->size * 8, STAGE_OUT}},
+                  [&] { return launch_visibility_bake(c, *desc, *vis, n, seed, c->vis.maps.ptr, stats != nullptr); });
+  if (r < 0) return r;
   if (stats) return rt_volume_visibility_stats(c, stats);
   return RT_OK;
 }
@@ -4233,11 +4209,10 @@ int rt_sample_volume_visible_device(rt_ctx* c, const rt_volume_desc* desc, const
   uint32_t probes = 0;
   int r = visibility_desc_ok(c, desc, vis, 0, &probes);
   if (r < 0) return r;
-  if (n >= (1u << 31)) return visibility_fail(c, std::string(kVisibility) + ": too many points for one call (n must be below 2^31)");
+  if (n >= (1u << 31)) return refuse(c, kVisibility, "too many points for one call (n must be below 2^31)");
   if (n == 0) return c ? RT_OK : RT_ERR_INVALID;
-  if ((r = visibility_arrays_ok(c, {dev_volume, dev_visibility, dev_points, dev_out}, true)) < 0 || !c) return RT_ERR_INVALID;
-  if ((r = query_device_arrays_ok(c, kVisibility, dev_volume, dev_out)) < 0) return r;
-  if ((r = query_device_arrays_ok(c, kVisibility, dev_visibility, dev_points)) < 0) return r;
+  if ((r = caller_arrays_ok(c, kVisibility, {dev_volume, dev_visibility, dev_points, dev_out})) < 0) return r;
+  if (!c) return RT_ERR_INVALID;
   return launch_sample_volume_visible(c, *desc, *vis, dev_volume, dev_visibility, dev_points, n, dev_out);
 }
 
@@ -4246,23 +4221,18 @@ int rt_sample_volume_visible(rt_ctx* c, const rt_volume_desc* desc, const rt_vol
   uint32_t probes = 0;
   int r = visibility_desc_ok(c, desc, vis, 0, &probes);
   if (r < 0) return r;
-  if (n >= (1u << 31)) return visibility_fail(c, std::string(kVisibility) + ": too many points for one call (n must be below 2^31)");
+  if (n >= (1u << 31)) return refuse(c, kVisibility, "too many points for one call (n must be below 2^31)");
   if (n == 0) return c ? RT_OK : RT_ERR_INVALID;
-  if ((r = visibility_arrays_ok(c, {volume, visibility, points, out}, false)) < 0 || !c) return RT_ERR_INVALID;
-  HIP_TRY(c, hipSetDevice(c->device));
+  if ((r = caller_arrays_ok(c, kVisibility, {volume, visibility, points, out}, false)) < 0 || !c) return RT_ERR_INVALID;
   VisibilityState& st = c->vis;
-  const size_t vol_bytes = (size_t)probes * sizeof(rt_probe_sh9), map_bytes = (size_t)probes * vis->size * vis->size * 8;
-  if ((r = ensure_buffer(c, st.volume, vol_bytes, true)) < 0) return r;
-  if ((r = ensure_buffer(c, st.maps, map_bytes, true)) < 0) return r;
-  if ((r = ensure_buffer(c, st.points, (size_t)n * sizeof(rt_gather_point), true)) < 0) return r;
-  if ((r = ensure_buffer(c, st.out, (size_t)n * sizeof(rt_irradiance), true)) < 0) return r;
-  HIP_TRY(c, hipMemcpyAsync(st.volume.ptr, volume, vol_bytes, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(st.maps.ptr, visibility, map_bytes, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(st.points.ptr, points, (size_t)n * sizeof(rt_gather_point), hipMemcpyHostToDevice, c->stream));
-  if ((r = launch_sample_volume_visible(c, *desc, *vis, st.volume.ptr, st.maps.ptr, st.points.ptr, n, st.out.ptr)) < 0) return r;
-  HIP_TRY(c, hipMemcpyAsync(out, st.out.ptr, (size_t)n * sizeof(rt_irradiance), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return RT_OK;
+  return staged_call(c,
+                     {{st.volume, volume, (size_t)probes * sizeof(rt_probe_sh9), STAGE_IN},
+                      {st.maps, visibility, (size_t)probes * vis->size * vis->size * 8, STAGE_IN},
+                      {st.points, points, (size_t)n * sizeof(rt_gather_point), STAGE_IN},
+                      {st.out, out, (size_t)n * sizeof(rt_irradiance), STAGE_OUT}},
+                     [&] {
+                       return launch_sample_volume_visible(c, *desc, *vis, st.volume.ptr, st.maps.ptr, st.points.ptr, n, st.out.ptr);
+                     });
 }
 
 // bytes of the tiled image of an export
@@ -4272,14 +4242,13 @@ static size_t visibility_tiles_bytes(uint32_t probes, uint32_t size, uint32_t fo
 // the arguments of an export beside the descriptors: the format is f32 or f16, the capacity holds the image
 static int visibility_encode_args_ok(rt_ctx* c, uint32_t probes, uint32_t size, uint32_t format, const void* in, const void* out,
                                      size_t cap, bool device) {
-  const std::string w(kVisibility);
-  if (format == RT_LIGHTMAP_RGBE8) return visibility_fail(c, w + ": RT_LIGHTMAP_RGBE8 cannot hold two distance moments");
-  if (format != RT_LIGHTMAP_F32 && format != RT_LIGHTMAP_F16) return visibility_fail(c, w + ": format must be RT_LIGHTMAP_F32 or _F16");
-  int r = visibility_arrays_ok(c, {in, out}, device);
+  if (format == RT_LIGHTMAP_RGBE8) return refuse(c, kVisibility, "RT_LIGHTMAP_RGBE8 cannot hold two distance moments");
+  if (format != RT_LIGHTMAP_F32 && format != RT_LIGHTMAP_F16) return refuse(c, kVisibility, "format must be RT_LIGHTMAP_F32 or _F16");
+  const int r = caller_arrays_ok(c, kVisibility, {in, out}, device);
   if (r < 0) return r;
-  if (device && in == out) return visibility_fail(c, w + ": the output must not be the input");
+  if (device && in == out) return refuse(c, kVisibility, "the output must not be the input");
   if (cap < visibility_tiles_bytes(probes, size, format))
-    return visibility_fail(c, w + ": the capacity is below nx * ny * nz tiles of (size + 2)^2 texels of the format");
+    return refuse(c, kVisibility, "the capacity is below nx * ny * nz tiles of (size + 2)^2 texels of the format");
   return c ? RT_OK : RT_ERR_INVALID;
 }
 static int launch_visibility_tiles(rt_ctx* c, const rt_volume_desc& D, const rt_volume_visibility_desc& V, uint32_t format,
@@ -4303,7 +4272,6 @@ int rt_encode_volume_visibility_device(rt_ctx* c, const rt_volume_desc* desc, co
   int r = visibility_desc_ok(c, desc, vis, 0, &probes);
   if (r < 0) return r;
   if ((r = visibility_encode_args_ok(c, probes, vis->size, format, dev_visibility, dev_out, cap, true)) < 0) return r;
-  if ((r = query_device_arrays_ok(c, kVisibility, dev_visibility, dev_out)) < 0) return r;
   return launch_visibility_tiles(c, *desc, *vis, format, dev_visibility, dev_out);
 }
 
@@ -4313,15 +4281,9 @@ int rt_encode_volume_visibility(rt_ctx* c, const rt_volume_desc* desc, const rt_
   int r = visibility_desc_ok(c, desc, vis, 0, &probes);
   if (r < 0) return r;
   if ((r = visibility_encode_args_ok(c, probes, vis->size, format, visibility, out, cap, false)) < 0) return r;
-  HIP_TRY(c, hipSetDevice(c->device));
   const size_t in_bytes = (size_t)probes * vis->size * vis->size * 8, out_bytes = visibility_tiles_bytes(probes, vis->size, format);
-  if ((r = ensure_buffer(c, c->vis.maps, in_bytes, true)) < 0) return r;
-  if ((r = ensure_buffer(c, c->vis.encoded, out_bytes, true)) < 0) return r;
-  HIP_TRY(c, hipMemcpyAsync(c->vis.maps.ptr, visibility, in_bytes, hipMemcpyHostToDevice, c->stream));
-  if ((r = launch_visibility_tiles(c, *desc, *vis, format, c->vis.maps.ptr, c->vis.encoded.ptr)) < 0) return r;
-  HIP_TRY(c, hipMemcpyAsync(out, c->vis.encoded.ptr, out_bytes, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return RT_OK;
+  return staged_call(c, {{c->vis.maps, visibility, in_bytes, STAGE_IN}, {c->vis.encoded, out, out_bytes, STAGE_OUT}},
+                     [&] { return launch_visibility_tiles(c, *desc, *vis, format, c->vis.maps.ptr, c->vis.encoded.ptr); });
 }
 
 // ---- the kernels of compute().  Variant 0, the one-pixel-per-lane megakernel: one tile per workgroup, no dynamic LDS.
