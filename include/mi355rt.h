@@ -249,7 +249,8 @@ double rt_world_last_tlas_ms(const rt_ctx* ctx);
  * only *bytes_out is set. */
 typedef enum rt_world_array {
   RT_WORLD_VERTICES = 0, RT_WORLD_NORMALS, RT_WORLD_UVS, RT_WORLD_TOPOLOGY, RT_WORLD_TLAS, RT_WORLD_BLAS, RT_WORLD_INSTANCES,
-  RT_WORLD_LIGHTS, RT_WORLD_DRAW_COMMANDS
+  RT_WORLD_LIGHTS, RT_WORLD_DRAW_COMMANDS,
+  RT_WORLD_INSTANCE_ORDER   /* n_instances u32: the declaration index of the instance at each TLAS position (frame motion's ids) */
 } rt_world_array;
 int rt_world_read(rt_ctx* ctx, int which, void* out, size_t cap_bytes, size_t* bytes_out);
 /* Debug / test read-back of the child-pair records the trace kernels walk (csrc/k_pairs.hip.h): pairs_out receives
@@ -1111,8 +1112,9 @@ int rt_frame_denoise_stats(rt_ctx* ctx, rt_frame_denoise_report* out);
  * bit, a non-zero reserved word, max_history == 0 or > RT_FRAME_TEMPORAL_MAX_HISTORY (256), var_history == 0.  The float
  * parameters are not validated: a NaN rejects every tap.  The rank and stripe refusals of the frame denoiser apply as they
  * stand.
- * Not built: motion of instances and skinned vertices (it needs instance identity across TLAS reorders and last frame's
- * transforms; a moved surface fails the plane test and restarts at n = 1, correct but noisy); SVGF's 3 x 3 search when all four
+ * Motion of instances and skinned vertices is the optional "frame motion" below (RT_FRAME_TEMPORAL_MOTION); without that flag
+ * a moved surface fails the plane test and restarts at n = 1, correct but noisy.
+ * Not built: SVGF's 3 x 3 search when all four
  * taps fail; neighbourhood clamping of the history; feeding back the first pass's filtered colour; weighting by the
  * accumulator's sample count (with a growing accumulator the history averages successive means).
  *   rt_set_frame_temporal     desc != NULL: every later rt_denoise_frame, rt_denoise_frame_device and filtered present() runs
@@ -1126,6 +1128,71 @@ int rt_frame_denoise_stats(rt_ctx* ctx, rt_frame_denoise_report* out);
 int rt_set_frame_temporal(rt_ctx* ctx, const rt_frame_temporal_desc* desc_or_null);
 int rt_reset_frame_history(rt_ctx* ctx);
 int rt_read_frame_history(rt_ctx* ctx, float* colour_rgba32f, float* moments_rg32f, size_t cap_pixels, uint32_t* frames_out);
+
+/* ---- frame motion: "follow the surface point, not the place", RT_FRAME_TEMPORAL_MOTION in rt_frame_temporal_desc.flags ----
+ * The temporal rule takes the world as static.  In the loop it exists for - a world rebuilt every frame - that fails three
+ * ways: a surface that leaves its plane restarts at n = 1 every frame; a surface that slides within its plane passes every
+ * test and blends the history of another surface point; and SAME_INSTANCE compares TLAS positions, which every update
+ * re-sorts.  With the flag set, one more kernel (csrc/k_frame_motion.hip.h) runs between the prepare stage and
+ * k_frame_temporal: it finds where the pixel's own point of its own triangle was in the previous frame, from a snapshot of
+ * that frame's vertex positions and instance transforms, and the temporal stage reprojects THAT point.  With the flag clear
+ * every word the library produces is what it produced before the flag existed.
+ *
+ * THE FRAME MOTION RULE.  f32, unfused, in the order written, with rt_div / rt_normalize / rt_abs / rt_mat_mul_point of
+ * mi355rt_math.h; dot and cross as in the temporal rule.  Inputs per surface pixel p (surface flag of its guide != 0): tri =
+ * bits(normal_id[p].z), inst = bits(normal_id[p].w) of the G-buffer; P and N of this frame's guide; the scene arrays as they
+ * are now: n_tris topology rows, n_verts positions, n_inst instance records in TLAS order; ids, n_inst words (below: IDENTITY);
+ * the SNAPSHOT of the previous frame - the last frame this stage ran on - when one is kept: n_verts positions by vertex id, the
+ * forward transforms of that frame's instances BY STABLE ID, and per pixel the stable id that frame recorded.
+ *   ids         sid = ids[inst] when inst < n_inst and ids[inst] < n_inst, else RT_FRAME_MOTION_NO_ID (0xffffffff).  The id
+ *               the frame records for the pixel is sid; for a background pixel NO_ID.
+ *   untracked   the pixel is UNTRACKED when tri >= n_tris; or inst >= n_inst; or sid == NO_ID; or one of v0, v1, v2 - the first
+ *               three words of topology row tri - is >= n_verts; or no snapshot is kept; or, below, !(den > 0) or a word of P'
+ *               is not finite (its exponent field is all ones).  Every index is compared BEFORE the load it guards; a load
+ *               that fails its guard is not made through that index.  An untracked pixel takes the temporal rule's
+ *               no-history path.  Its carry is {P, UNTRACKED} {N, sid}.
+ *   corners     M = the 16 words of transform of instance record inst; M' = the snapshot's transform of sid.  A =
+ *               rt_mat_mul_point(M, pos[v0]), B of v1, C of v2 - what the kernels' world_triangle gives; A', B', C' the same
+ *               of M' and the snapshot's positions of the same three vertex ids.
+ *   unmoved     when the nine words of A, B, C equal those of A', B', C' bit for bit: P' = P, N' = N, status UNMOVED: the
+ *               temporal rule then applies word for word.
+ *   moved       else e1 = B - A, e2 = C - A, ep = P - A (per component); d11 = dot(e1, e1), d12 = dot(e1, e2), d22 = dot(e2,
+ *               e2), dp1 = dot(ep, e1), dp2 = dot(ep, e2); den = d11 * d22 - d12 * d12; b1 = rt_div(d22 * dp1 - d12 * dp2, den);
+ *               b2 = rt_div(d11 * dp2 - d12 * dp1, den) - the barycentrics of the foot of P in the triangle's plane, by the 2 x 2
+ *               normal equations; e1' = B' - A', e2' = C' - A'; P'[c] = A'[c] + (b1 * e1'[c] + b2 * e2'[c]); N' =
+ *               rt_normalize(cross(e1', e2')), every component negated when dot(cross(e1, e2), N) < 0; status MOVED.  A
+ *               previous triangle of no area gives a NaN N', which fails every tap's normal test: no history.
+ *   carry       per pixel 32 bytes, {P'.xyz, bits(status)} {N'.xyz, bits(sid)}; a background pixel: {0, 0, 0, BACKGROUND}
+ *               {0, 0, 0, NO_ID}.  rt_read_frame_motion reads it; P' - P is the pixel's world-space motion vector.
+ *   temporal    the temporal rule with these changes: an UNTRACKED pixel takes the no-history path; `reproject` starts from e
+ *               = P' - eye'; `accepted` tests dot(N', Nq) >= normal_cos and, with d = Pq - P', rt_abs(dot(N', d)) <=
+ *               plane_eps; with RT_FRAME_TEMPORAL_SAME_INSTANCE the tap's id AS THE PREVIOUS FRAME RECORDED IT must equal sid
+ *               (the guides' TLAS positions are not compared).  Sums and blend are unchanged.
+ * LIMITATION: the shading normal is not carried.  N' is the GEOMETRIC normal of the previous triangle, Nq the previous
+ * frame's shading normal: on a smoothly shaded mesh normal_cos has to tolerate the angle between the two, up to half a facet
+ * angle.  An UNMOVED pixel keeps its shading normal.
+ * IDENTITY.  ids[p] is the stable id of the instance at TLAS position p.  rt_world_update supplies it on the device: the
+ * declaration index of the instance its TLAS builder put at position p (RT_WORLD_INSTANCE_ORDER of rt_world_read).  On the
+ * upload path ids is the identity mapping after every upload of RT_KIND_INSTANCE, until rt_set_frame_motion_ids declares the
+ * ids of the instance array now uploaded: a permutation of 0 .. n - 1 with n the instance count, else RT_ERR_INVALID, "frame
+ * motion: ...".
+ * THE SNAPSHOT is taken on the context's stream right after the temporal stage has run, and only while the flag is set:
+ * the vertex positions (16 B per vertex, a device copy), the transforms scattered by stable id (64 B per instance), the id
+ * plane (4 B per pixel, double-buffered with the history).  The history is dropped, as by rt_reset_frame_history, when the
+ * vertex count or the instance count differs from the snapshot's, and by every rt_set_frame_temporal.
+ * THE SCENE MUST BE THE G-BUFFER'S.  The stage follows G-buffer indices into the scene arrays, so with the flag set a frame
+ * denoise call is refused with RT_ERR_NOT_READY, "frame motion: the scene changed since the last compute()", when geometry,
+ * topology, instances or BVH were uploaded, or rt_world_update ran, after the compute() that made the G-buffer.  A camera
+ * change alone does not trigger it.  Frames traced ahead are dropped by everything that rewrites the scene.
+ * rt_set_frame_temporal refuses the flag, "frame temporal: RT_FRAME_TEMPORAL_MOTION needs an uploaded scene ...", on a context
+ * that has no triangles, vertices or instances yet (and without a context): set it after the first upload or world update.
+ * Not built: carrying the shading normal; motion of the camera's lens; motion vectors for anything but the primary hit.
+ *   rt_set_frame_motion_ids   see IDENTITY.  n must equal the instance count of the context.  Does not drop the history.
+ *   rt_read_frame_motion      blocking, for tests and for callers who want motion vectors: the carry plane of the last run,
+ *                             W * H x 8 f32; cap_pixels >= W * H.  RT_ERR_NOT_READY before the first run with the flag set.
+ * rt_frame_denoise_stats reports the stage in `motion` (1: k_frame_motion ran in that call) and `motion_ms`. */
+int rt_set_frame_motion_ids(rt_ctx* ctx, const uint32_t* ids, uint32_t n);
+int rt_read_frame_motion(rt_ctx* ctx, float* carry_2xrgba32f, size_t cap_pixels);
 
 /* ---- lightmaps: "the finished lightmap of these instances, in the texel format a renderer loads", in one call ----
  * The four sections above are the stages of a lightmap: points, gather, filter, gutter.  A caller who chains their host

@@ -284,14 +284,21 @@ typedef struct rt_frame_denoise_report { /* 48 B */
   uint8_t form[5];            /* per pass: 1 = LDS form, 2 = direct form; 0 beyond `passes` */
   uint8_t cache_hit;          /* 1: the prepare stage's outputs were those of an earlier call on the same G-buffer */
   uint8_t temporal;           /* the temporal stage (rt_set_frame_temporal): 0 = off, 1 = ran, 2 = its integrated image was reused */
-  uint8_t pad[1];
+  uint8_t motion;             /* the motion stage (RT_FRAME_TEMPORAL_MOTION): 1 = k_frame_motion ran in this call, else 0 */
   float temporal_ms;          /* k_frame_temporal; 0 when the stage is off or its image was reused */
-  uint32_t reserved[1];
+  float motion_ms;            /* k_frame_motion; 0 unless `motion` is 1 */
 } rt_frame_denoise_report;
 
 /* ---- frame temporal (rt_set_frame_temporal, mi355rt.h): reprojection of last frame's history ahead of the a-trous passes ---- */
 #define RT_FRAME_TEMPORAL_MAX_HISTORY 256u
 #define RT_FRAME_TEMPORAL_SAME_INSTANCE 1u /* a history tap must lie on the pixel's instance */
+#define RT_FRAME_TEMPORAL_MOTION 2u        /* carry every surface pixel back along its own triangle's motion before it is reprojected */
+/* the status word of a carry texel (rt_read_frame_motion) and the id of a pixel that has none */
+#define RT_FRAME_MOTION_BACKGROUND 0u
+#define RT_FRAME_MOTION_UNTRACKED 1u
+#define RT_FRAME_MOTION_UNMOVED 2u
+#define RT_FRAME_MOTION_MOVED 3u
+#define RT_FRAME_MOTION_NO_ID 0xffffffffu
 typedef struct rt_frame_temporal_desc { /* 32 B */
   uint32_t flags;             /* RT_FRAME_TEMPORAL_*; any other bit is refused */
   uint32_t max_history;       /* 1 .. RT_FRAME_TEMPORAL_MAX_HISTORY: the blend factor never falls below 1 / max_history; 1 keeps none */
@@ -345,6 +352,8 @@ static_assert(sizeof(rt_frame_denoise_desc) == 32, "rt_frame_denoise_desc is 32 
 static_assert(sizeof(rt_frame_denoise_report) == 48, "rt_frame_denoise_report is 48 bytes");
 static_assert(__builtin_offsetof(rt_frame_denoise_report, temporal) == 38 && __builtin_offsetof(rt_frame_denoise_report, temporal_ms) == 40,
               "rt_frame_denoise_report: the temporal stage took the first pad byte and the first reserved word");
+static_assert(__builtin_offsetof(rt_frame_denoise_report, motion) == 39 && __builtin_offsetof(rt_frame_denoise_report, motion_ms) == 44,
+              "rt_frame_denoise_report: the motion stage took the last pad byte and the last reserved word");
 static_assert(sizeof(rt_frame_temporal_desc) == 32, "rt_frame_temporal_desc is 32 bytes");
 static_assert(__builtin_offsetof(rt_frame_temporal_desc, normal_cos) == 12 && __builtin_offsetof(rt_frame_temporal_desc, reserved) == 20,
               "rt_frame_temporal_desc: three words, two floats, three reserved words");

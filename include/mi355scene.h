@@ -103,6 +103,9 @@ const float* ms_world_blas(const ms_world* w, size_t* len);             /* 8 f32
 const float* ms_world_instances(const ms_world* w, size_t* len);        /* 36 f32 / inst   */
 const uint32_t* ms_world_lights(const ms_world* w, size_t* len);        /* 2 u32 / light   */
 const uint32_t* ms_world_draw_commands(const ms_world* w, size_t* len); /* 4 u32 / inst    */
+/* 1 u32 / inst: the declaration index of the instance at each position of `instances` - the order the TLAS builder computes,
+ * stable ids for rt_set_frame_motion_ids (mi355rt.h, frame motion) */
+const uint32_t* ms_world_instance_order(const ms_world* w, size_t* len);
 const float* ms_world_camera(const ms_world* w, size_t* len);           /* 24 f32          */
 
 /* World::get_texture_count lib.rs:355-357.  The reference hands out *encoded*

@@ -37,7 +37,12 @@ struct FrameTemporalArgs {
 
 __device__ __forceinline__ float ft_dot(rt3 a, rt3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
 
-__global__ __launch_bounds__(256) void k_frame_temporal(FrameTemporalArgs A) {
+// The stage's body.  MOTION false: the rule as it stands (k_frame_temporal).  MOTION true (k_frame_temporal_motion, mi355rt.h
+// "THE FRAME MOTION RULE"): P, N and the pixel's stable id come from the carry plane k_frame_motion wrote, an UNTRACKED pixel
+// has no history, and SAME_INSTANCE compares the id the previous frame recorded for the tap - four more 4-byte loads, issued
+// with the sixteen of the footprint.
+template <bool MOTION>
+__device__ __forceinline__ void frame_temporal_body(const FrameTemporalArgs A, const float4* carry, const uint32_t* prev_id) {
   const uint32_t x = blockIdx.x * 256u + threadIdx.x, y = blockIdx.y;
   if (x >= A.W || y >= A.H) return;
   const size_t i = (size_t)y * A.W + x;
@@ -52,8 +57,15 @@ __global__ __launch_bounds__(256) void k_frame_temporal(FrameTemporalArgs A) {
   const float l = fd_lum(c.x, c.y, c.z);
   float wsum = 0.0f, a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, s1 = 0.0f, s2 = 0.0f, n_prev = 0.0f;
   bool any = false;
-  if (A.have != 0u && A.max_history > 1.0f) {
-    const rt3 P = rt3_make(g0.x, g0.y, g0.z), N = rt3_make(g1.x, g1.y, g1.z);
+  float4 k0 = g0, k1 = g1;   // {P, -} {N, -}: the guide's, or the carry's {P', status} {N', sid}
+  bool tracked = true;
+  if constexpr (MOTION) {
+    k0 = carry[2 * i];
+    k1 = carry[2 * i + 1];
+    tracked = rt_f2u(k0.w) != RT_FRAME_MOTION_UNTRACKED;
+  }
+  if (A.have != 0u && A.max_history > 1.0f && tracked) {
+    const rt3 P = rt3_make(k0.x, k0.y, k0.z), N = rt3_make(k1.x, k1.y, k1.z);
     const rt3 eye = rt3_make(A.eye[0], A.eye[1], A.eye[2]), ll = rt3_make(A.ll[0], A.ll[1], A.ll[2]);
     const rt3 hor = rt3_make(A.hor[0], A.hor[1], A.hor[2]), ver = rt3_make(A.ver[0], A.ver[1], A.ver[2]);
     const rt3 e = P - eye, c0 = ll - eye;
@@ -70,6 +82,7 @@ __global__ __launch_bounds__(256) void k_frame_temporal(FrameTemporalArgs A) {
       const float w[4] = {(1.0f - tx) * (1.0f - ty), tx * (1.0f - ty), (1.0f - tx) * ty, tx * ty};
       float4 t0[4], t1[4], th[4];
       float2 tm[4];
+      uint32_t tid[4] = {0u, 0u, 0u, 0u};
       bool use[4];
 #pragma unroll
       for (int k = 0; k < 4; k++) {   // the loads of the footprint, all in flight before the first is used
@@ -80,11 +93,13 @@ __global__ __launch_bounds__(256) void k_frame_temporal(FrameTemporalArgs A) {
         t1[k] = A.prev_guide[2 * q + 1];
         th[k] = A.prev_hist[q];
         tm[k] = A.prev_mom[q];
+        if constexpr (MOTION) tid[k] = prev_id[q];
       }
 #pragma unroll
       for (int k = 0; k < 4; k++) {
+        // the tap's instance is the pixel's: by stable id, else by the guides' TLAS positions
         bool ok = use[k] && rt_f2u(t1[k].w) != 0u && th[k].w >= 1.0f &&
-                  (!(A.flags & RT_FRAME_TEMPORAL_SAME_INSTANCE) || rt_f2u(t0[k].w) == rt_f2u(g0.w));
+                  (!(A.flags & RT_FRAME_TEMPORAL_SAME_INSTANCE) || (MOTION ? tid[k] : rt_f2u(t0[k].w)) == rt_f2u(MOTION ? k1.w : g0.w));
         if (ok) {
           const rt3 d = rt3_make(t0[k].x - P.x, t0[k].y - P.y, t0[k].z - P.z);
           const float nd = ft_dot(N, rt3_make(t1[k].x, t1[k].y, t1[k].z));
@@ -121,6 +136,11 @@ __global__ __launch_bounds__(256) void k_frame_temporal(FrameTemporalArgs A) {
   A.integ[i] = make_float4(q0, q1, q2, var);
   A.hist[i] = make_float4(q0, q1, q2, n);
   A.mom[i] = make_float2(m1, m2);
+}
+
+__global__ __launch_bounds__(256) void k_frame_temporal(FrameTemporalArgs A) { frame_temporal_body<false>(A, nullptr, nullptr); }
+__global__ __launch_bounds__(256) void k_frame_temporal_motion(FrameTemporalArgs A, const float4* carry, const uint32_t* prev_id) {
+  frame_temporal_body<true>(A, carry, prev_id);
 }
 
 }  // namespace rtk

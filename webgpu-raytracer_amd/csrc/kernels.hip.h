@@ -39,7 +39,9 @@
 //                             (rt_denoise_frame, rt_set_present_denoise)
 //   k_frame_temporal.hip.h    k_frame_temporal: the temporal stage between k_frame_prepare and the first pass: last frame's
 //                             history reprojected through last frame's camera, tested against last frame's guide and blended
-//                             (rt_set_frame_temporal)
+//                             (rt_set_frame_temporal); k_frame_temporal_motion: the same body on the carry plane
+//   k_frame_motion.hip.h      k_frame_motion / _scatter: where a pixel's own point of its own triangle was in the previous frame,
+//                             from a snapshot of that frame's vertices and transforms (RT_FRAME_TEMPORAL_MOTION)
 //   k_encode.hip.h            k_encode_atlas: a finished f32 atlas as half floats or shared-exponent RGBE8 words
 //                             (rt_encode_atlas, the last stage of rt_bake_atlas_lightmap)
 //   k_volume.hip.h            k_volume_probes / _finish / _sample / _layers: the probes of a grid, SH9 radiance into windowed
@@ -89,6 +91,7 @@
 #include "k_denoise.hip.h"
 #include "k_frame_denoise.hip.h"
 #include "k_frame_temporal.hip.h"
+#include "k_frame_motion.hip.h"
 #include "k_encode.hip.h"
 #include "k_volume.hip.h"
 #include "k_reflection.hip.h"

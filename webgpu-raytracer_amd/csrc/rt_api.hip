@@ -127,6 +127,20 @@ struct FrameTemporalState {
   EventPair ev;
 };
 
+// What frame motion (RT_FRAME_TEMPORAL_MOTION, mi355rt.h "THE FRAME MOTION RULE") keeps beside FrameTemporalState, and only
+// while the flag is set: the carry plane of the last run; the snapshot of the frame of set `cur` - vertex positions, forward
+// transforms by stable id, and the id plane, double-buffered with the history (pix_id[ft.cur] belongs to ft.hist[ft.cur]) - with
+// the counts it was taken at; and where the stable ids of the instance array now on the device come from.
+struct FrameMotionState {
+  DeviceBuffer carry, snap_pos, snap_xf, pix_id[2], ids;
+  uint32_t snap_verts = 0, snap_inst = 0;
+  enum { IDS_IDENTITY, IDS_DECLARED, IDS_WORLD } ids_from = IDS_IDENTITY;
+  bool ran = false;                 // `carry` holds a run at the current size
+  uint64_t scene_gen = 0;           // writes of geometry, topology, instances or BVH (uploads, rt_world_update) ...
+  uint64_t gbuf_scene_gen = 0;      // ... and its value when the last G-buffer was made (recorded with gbuf_gen)
+  EventPair ev;
+};
+
 // What a lightmap bake (rt_bake_atlas_lightmap) and the encode entries (rt_encode_atlas) keep between calls beyond the state of
 // the stages they are made of, kept and grown: the filtered atlas, the gutter fill's count, the encoded atlas and the staged
 // input of the host encode entry.
@@ -329,6 +343,7 @@ struct rt_ctx {
   DenoiseState dn;
   DenoiseFrameState fd;
   FrameTemporalState ft;
+  FrameMotionState fm;
   uint64_t gbuf_gen = 0;            // dispatches and consumed frames that made a G-buffer current: the key of fd's cache
   bool albedo_plane_valid = false;  // the render target holds the albedo a compute() wrote (present() overwrites it)
   LightmapState lm;
@@ -1280,6 +1295,8 @@ int rt_resize(rt_ctx* c, uint32_t width, uint32_t height) {
   c->fd.cache_valid = c->fd.keep_valid = false;
   for (DeviceBuffer* b : {&c->ft.hist[0], &c->ft.hist[1], &c->ft.mom[0], &c->ft.mom[1], &c->ft.guide[0], &c->ft.guide[1], &c->ft.integ})
     b->reset();
+  for (DeviceBuffer* b : {&c->fm.carry, &c->fm.pix_id[0], &c->fm.pix_id[1]}) b->reset();
+  c->fm.ran = false;
   c->ft.have = false;
   c->ft.frames = 0;
   c->gbuf_gen = 0;
@@ -1710,6 +1727,7 @@ static int world_make_static(rt_ctx* c, const rt_world_frame* f) {
 static int world_update_body(rt_ctx* c, const rt_world_frame* f, bool* touched) {
   auto& W = c->world;
   c->epoch++;   // drops frames traced ahead (rt_set_lookahead)
+  c->fm.scene_gen++;
   c->facts = lp::SceneFacts();   // the topology records are (re)made on the device, or their buffer is resized: the host has not seen them
   walk_forget(c);                // ... nor the nodes and the instances
   HIP_TRY(c, hipSetDevice(c->device));
@@ -1899,6 +1917,7 @@ static int world_update_body(rt_ctx* c, const rt_world_frame* f, bool* touched) 
     c->validate_dirty = false;
     c->scene_valid = true;
     c->nodes_from_device = true;
+    c->fm.ids_from = FrameMotionState::IDS_WORLD;   // the stable id of a TLAS position is W.tlas.ord's declaration index
     c->tris_dirty = c->inst_dirty = c->lights_dirty = c->nodes_dirty = c->pairs_dirty = c->roots_dirty = c->world_rec_dirty = true;
     if (W.cache_enabled && !W.static_cached) {   // first full update of this description: keep the static geometries' node blocks
       W.static_count.assign(G, 0u);
@@ -1973,6 +1992,7 @@ int rt_world_read(rt_ctx* c, int which, void* out, size_t cap_bytes, size_t* byt
     case RT_WORLD_INSTANCES: src = c->instances.ptr; n = (size_t)c->n_instances * sizeof(rt_instance); break;
     case RT_WORLD_LIGHTS: src = c->lights.ptr; n = (size_t)c->n_lights * sizeof(rt_light_ref); break;
     case RT_WORLD_DRAW_COMMANDS: src = c->draw_commands.ptr; n = (size_t)c->n_instances * 16; break;
+    case RT_WORLD_INSTANCE_ORDER: src = c->world.tlas.ord; n = (size_t)c->world.n_inst * 4; break;
     default: return fail(c, RT_ERR_INVALID, "rt_world_read: unknown array");
   }
   *bytes_out = n;
@@ -1990,6 +2010,8 @@ int rt_upload(rt_ctx* c, rt_kind kind, const void* data, size_t bytes) {
   if (!c) return RT_ERR_INVALID;
   c->epoch++;
   c->world.static_cached = false;   // host arrays replace what the device update left in the scene buffers   // drops frames traced ahead (rt_set_lookahead)
+  if (kind == RT_KIND_TOPOLOGY || kind == RT_KIND_INSTANCE) c->fm.scene_gen++;
+  if (kind == RT_KIND_INSTANCE) c->fm.ids_from = FrameMotionState::IDS_IDENTITY;
   if (bytes && !data) return fail(c, RT_ERR_INVALID, "null data");
   HIP_TRY(c, hipSetDevice(c->device));
   int r;
@@ -2078,6 +2100,7 @@ int rt_upload_geometry(rt_ctx* c, const float* pos4, const float* nrm4, const fl
   if (!c) return RT_ERR_INVALID;
   c->epoch++;
   c->world.static_cached = false;   // host arrays replace what the device update left in the scene buffers   // drops frames traced ahead (rt_set_lookahead)
+  c->fm.scene_gen++;
   if (vertex_count && (!pos4 || !nrm4 || !uv2)) return fail(c, RT_ERR_INVALID, "null geometry array");
   HIP_TRY(c, hipSetDevice(c->device));
   // The reference packs the three arrays into one buffer at 256-byte aligned offsets because WebGPU
@@ -2101,6 +2124,7 @@ int rt_upload_bvh(rt_ctx* c, const float* tlas, uint32_t n_tlas, const float* bl
   if (!c) return RT_ERR_INVALID;
   c->epoch++;
   c->world.static_cached = false;   // host arrays replace what the device update left in the scene buffers   // drops frames traced ahead (rt_set_lookahead)
+  c->fm.scene_gen++;
   if ((n_tlas && !tlas) || (n_blas && !blas)) return fail(c, RT_ERR_INVALID, "null BVH array");
   HIP_TRY(c, hipSetDevice(c->device));
   const size_t total = ((size_t)n_tlas + n_blas) * sizeof(rt_node);
@@ -3204,6 +3228,9 @@ static int frame_denoise_ctx_ok(rt_ctx* c, const rt_frame_denoise_desc* d) {
   if (c->accum_stale)
     return fail(c, RT_ERR_INVALID, w + ": the bound accumulation buffer was dropped by rt_resize: call rt_bind_accum again");
   if (c->gbuf_gen == 0) return fail(c, RT_ERR_NOT_READY, w + ": no G-buffer yet; call compute first");
+  // frame motion follows the G-buffer's indices into the scene arrays: they must be the arrays that G-buffer was traced in
+  if (c->ft.on && (c->ft.desc.flags & RT_FRAME_TEMPORAL_MOTION) && c->fm.gbuf_scene_gen != c->fm.scene_gen)
+    return fail(c, RT_ERR_NOT_READY, "frame motion: the scene changed since the last compute()");
   return RT_OK;
 }
 static const void* const frame_lds_fns[RT_FRAME_LDS_MAX_STEP] = {
@@ -3244,6 +3271,8 @@ static int frame_denoise_run(rt_ctx* c, const rt_frame_denoise_desc* d, void* de
   int r;
   if ((r = ensure_buffer(c, fd.col, npx * 16, false)) < 0) return r;
   FrameTemporalState& ft = c->ft;
+  FrameMotionState& fm = c->fm;
+  const bool motion = ft.on && (ft.desc.flags & RT_FRAME_TEMPORAL_MOTION) != 0u;
   if (ft.on) {
     for (int k = 0; k < 2; k++) {
       if ((r = ensure_buffer(c, ft.hist[k], npx * 16, false)) < 0) return r;
@@ -3251,6 +3280,13 @@ static int frame_denoise_run(rt_ctx* c, const rt_frame_denoise_desc* d, void* de
       if ((r = ensure_buffer(c, ft.guide[k], npx * 32, false)) < 0) return r;
     }
     if ((r = ensure_buffer(c, ft.integ, npx * 16, false)) < 0) return r;
+    if (motion) {
+      if ((r = ensure_buffer(c, fm.carry, npx * 32, false)) < 0) return r;
+      for (int k = 0; k < 2; k++)
+        if ((r = ensure_buffer(c, fm.pix_id[k], npx * 4, false)) < 0) return r;
+      if ((r = ensure_buffer(c, fm.snap_pos, std::max<size_t>(16, (size_t)c->n_verts * 16), false)) < 0) return r;
+      if ((r = ensure_buffer(c, fm.snap_xf, std::max<size_t>(64, (size_t)c->n_instances * 64), false)) < 0) return r;
+    }
   } else if ((r = ensure_buffer(c, fd.guide, npx * 32, false)) < 0) {
     return r;
   }
@@ -3264,6 +3300,8 @@ static int frame_denoise_run(rt_ctx* c, const rt_frame_denoise_desc* d, void* de
     }
     HIP_TRY(c, hipEventCreate(&ft.ev.a));
     HIP_TRY(c, hipEventCreate(&ft.ev.b));
+    HIP_TRY(c, hipEventCreate(&fm.ev.a));
+    HIP_TRY(c, hipEventCreate(&fm.ev.b));
     fd.ev_ready = true;
   }
   fd.timed = false;
@@ -3288,6 +3326,36 @@ static int frame_denoise_run(rt_ctx* c, const rt_frame_denoise_desc* d, void* de
     HIP_TRY(c, hipEventRecord(fd.ev[0].b, c->stream));
     if (ft.on) {   // one run of prepare is one frame of history
       if (ft.have && ft.hist_flags != demod) ft.have = false, ft.frames = 0;   // the stored quantity changes: dropped
+      // frame motion: a snapshot of other counts is of another scene - dropped, as by rt_reset_frame_history
+      if (motion && ft.have && (fm.snap_verts != c->n_verts || fm.snap_inst != c->n_instances)) ft.have = false, ft.frames = 0;
+      const uint32_t* ids = fm.ids_from == FrameMotionState::IDS_WORLD      ? (const uint32_t*)c->world.tlas.ord
+                            : fm.ids_from == FrameMotionState::IDS_DECLARED ? (const uint32_t*)fm.ids.ptr
+                                                                            : nullptr;
+      if (motion) {
+        rtk::FrameMotionArgs M;
+        M.normal_id = (const float4*)pn;
+        M.guide = (const float4*)ft.guide[next].ptr;
+        M.topo = (const float4*)c->topology.ptr;
+        M.pos = (const float4*)c->pos.ptr;
+        M.inst = (const float4*)c->instances.ptr;
+        M.ids = ids;
+        M.snap_pos = (const float4*)fm.snap_pos.ptr;
+        M.snap_xf = (const float4*)fm.snap_xf.ptr;
+        M.carry = (float4*)fm.carry.ptr;
+        M.pix_id = (uint32_t*)fm.pix_id[next].ptr;
+        M.W = c->width;
+        M.H = c->height;
+        // a count is the count of ITS array: nothing is followed into an array that is not on the device
+        M.n_tris = c->topology.ptr ? c->n_tris : 0u;
+        M.n_verts = c->pos.ptr ? c->n_verts : 0u;
+        M.n_inst = c->instances.ptr ? c->n_instances : 0u;
+        M.have = ft.have ? 1u : 0u;
+        HIP_TRY(c, hipEventRecord(fm.ev.a, c->stream));
+        hipLaunchKernelGGL(rtk::k_frame_motion, dim3((c->width + 255u) / 256u, c->height), dim3(256), 0, c->stream, M);
+        HIP_TRY(c, hipEventRecord(fm.ev.b, c->stream));
+        fm.ran = true;
+        fd.last.motion = 1;
+      }
       const rt_scene_uniforms& V = ft.prev_uniforms;
       rtk::FrameTemporalArgs T;
       T.col = (const float4*)fd.col.ptr;
@@ -3315,8 +3383,21 @@ static int frame_denoise_run(rt_ctx* c, const rt_frame_denoise_desc* d, void* de
       T.jit[0] = V.jitter[0];
       T.jit[1] = V.jitter[1];
       HIP_TRY(c, hipEventRecord(ft.ev.a, c->stream));
-      hipLaunchKernelGGL(rtk::k_frame_temporal, dim3((c->width + 255u) / 256u, c->height), dim3(256), 0, c->stream, T);
+      if (motion)
+        hipLaunchKernelGGL(rtk::k_frame_temporal_motion, dim3((c->width + 255u) / 256u, c->height), dim3(256), 0, c->stream, T,
+                           (const float4*)fm.carry.ptr, (const uint32_t*)fm.pix_id[ft.cur].ptr);
+      else
+        hipLaunchKernelGGL(rtk::k_frame_temporal, dim3((c->width + 255u) / 256u, c->height), dim3(256), 0, c->stream, T);
       HIP_TRY(c, hipEventRecord(ft.ev.b, c->stream));
+      if (motion) {   // the snapshot of this frame, behind its last reader on the stream
+        if (c->n_verts && c->pos.ptr)
+          HIP_TRY(c, hipMemcpyAsync(fm.snap_pos.ptr, c->pos.ptr, (size_t)c->n_verts * 16, hipMemcpyDeviceToDevice, c->stream));
+        if (c->n_instances && c->instances.ptr)
+          hipLaunchKernelGGL(rtk::k_frame_motion_scatter, dim3((c->n_instances + 255u) / 256u), dim3(256), 0, c->stream,
+                             (const float4*)c->instances.ptr, ids, (float4*)fm.snap_xf.ptr, c->n_instances);
+        fm.snap_verts = c->n_verts;
+        fm.snap_inst = c->n_instances;
+      }
       ft.cur = next;
       ft.have = true;
       ft.hist_flags = demod;
@@ -3426,6 +3507,7 @@ int rt_frame_denoise_stats(rt_ctx* c, rt_frame_denoise_report* out) {
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (!fd.last.cache_hit) HIP_TRY(c, hipEventElapsedTime(&fd.last.prepare_ms, fd.ev[0].a, fd.ev[0].b));
     if (fd.last.temporal == 1) HIP_TRY(c, hipEventElapsedTime(&fd.last.temporal_ms, c->ft.ev.a, c->ft.ev.b));
+    if (fd.last.motion == 1) HIP_TRY(c, hipEventElapsedTime(&fd.last.motion_ms, c->fm.ev.a, c->fm.ev.b));
     HIP_TRY(c, hipEventElapsedTime(&fd.last.finish_ms, fd.ev[1].a, fd.ev[1].b));
     for (uint32_t p = 0; p < fd.last.passes; p++) HIP_TRY(c, hipEventElapsedTime(&fd.last.pass_ms[p], fd.ev[2 + p].a, fd.ev[2 + p].b));
     fd.timed = false;
@@ -3447,13 +3529,17 @@ static void frame_history_drop(rt_ctx* c) {
 int rt_set_frame_temporal(rt_ctx* c, const rt_frame_temporal_desc* d) {
   if (d) {
     if (d->reserved[0] | d->reserved[1] | d->reserved[2]) return refuse(c, kFrameTemporal, "reserved words must be 0");
-    if (d->flags & ~RT_FRAME_TEMPORAL_SAME_INSTANCE) return refuse(c, kFrameTemporal, "unknown flag bit");
+    if (d->flags & ~(RT_FRAME_TEMPORAL_SAME_INSTANCE | RT_FRAME_TEMPORAL_MOTION)) return refuse(c, kFrameTemporal, "unknown flag bit");
     if (d->max_history == 0 || d->max_history > RT_FRAME_TEMPORAL_MAX_HISTORY)
       return refuse(c, kFrameTemporal, "max_history must be 1 .. 256");
     if (d->var_history == 0) return refuse(c, kFrameTemporal, "var_history must be >= 1");
+    // the motion stage follows G-buffer indices into the scene arrays: there is nothing to follow them into before a scene
+    if ((d->flags & RT_FRAME_TEMPORAL_MOTION) && !(c && c->n_tris && c->n_verts && c->n_instances))
+      return refuse(c, kFrameTemporal, "RT_FRAME_TEMPORAL_MOTION needs an uploaded scene: set it after the first upload or rt_world_update");
   }
   if (!c) return RT_ERR_INVALID;
   frame_history_drop(c);
+  c->fm.ran = false;
   c->ft.on = d != nullptr;
   if (d) c->ft.desc = *d;
   return RT_OK;
@@ -3477,6 +3563,41 @@ int rt_read_frame_history(rt_ctx* c, float* colour, float* moments, size_t cap_p
   HIP_TRY(c, hipSetDevice(c->device));
   if (colour) HIP_TRY(c, hipMemcpyAsync(colour, ft.hist[ft.cur].ptr, npx * 16, hipMemcpyDeviceToHost, c->stream));
   if (moments) HIP_TRY(c, hipMemcpyAsync(moments, ft.mom[ft.cur].ptr, npx * 8, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return RT_OK;
+}
+
+// ---- frame motion (mi355rt.h "THE FRAME MOTION RULE"; k_frame_motion.hip.h): the stage itself runs inside frame_denoise_run
+static const char* const kFrameMotion = "frame motion";
+int rt_set_frame_motion_ids(rt_ctx* c, const uint32_t* ids, uint32_t n) {
+  if (!ids) return refuse(c, kFrameMotion, "NULL ids");
+  if (!c) return RT_ERR_INVALID;
+  if (n != c->n_instances || !n) return refuse(c, kFrameMotion, "n must be the instance count of the uploaded instance array");
+  std::vector<uint8_t> seen(n, 0);
+  for (uint32_t p = 0; p < n; p++) {
+    if (ids[p] >= n || seen[ids[p]]) return refuse(c, kFrameMotion, "the ids must be a permutation of 0 .. n - 1");
+    seen[ids[p]] = 1;
+  }
+  HIP_TRY(c, hipSetDevice(c->device));
+  // no kernel in flight may still read the old ids: the buffer is rewritten in place
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  int r = ensure_buffer(c, c->fm.ids, (size_t)n * 4, false);
+  if (r < 0) return r;
+  HIP_TRY(c, hipMemcpyAsync(c->fm.ids.ptr, ids, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  c->fm.ids_from = FrameMotionState::IDS_DECLARED;
+  return RT_OK;
+}
+
+int rt_read_frame_motion(rt_ctx* c, float* carry, size_t cap_pixels) {
+  if (!c) return RT_ERR_INVALID;
+  if (!carry) return refuse(c, kFrameMotion, "NULL output");
+  const FrameMotionState& fm = c->fm;
+  if (!fm.ran || !fm.carry.ptr) return fail(c, RT_ERR_NOT_READY, "frame motion: the stage has not run yet");
+  const size_t npx = (size_t)c->width * c->height;
+  if (cap_pixels < npx) return refuse(c, kFrameMotion, "output buffer too small");
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, hipMemcpyAsync(carry, fm.carry.ptr, npx * 32, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return RT_OK;
 }
@@ -4447,6 +4568,7 @@ static int compute_frames(rt_ctx* c, const uint32_t* frame_counts, uint32_t n, u
   // frame that is traced AHEAD is consumed after present() calls that overwrite the plane: a context that denoises frames
   // keeps a copy (4 B / px, only then)
   c->gbuf_gen++;
+  c->fm.gbuf_scene_gen = c->fm.scene_gen;   // frame motion: the scene arrays are those this G-buffer's indices point into
   c->albedo_plane_valid = true;
   c->fd.keep_valid = false;
   if (c->fd.wanted && n_commit < n) {
@@ -4537,6 +4659,7 @@ static int consume_ahead(rt_ctx* c, uint32_t frame_count) {
   HIP_TRY(c, hipGetLastError());
   c->gbuf_slot = (int)k;
   c->gbuf_gen++;   // another frame's G-buffer is current (the frame denoiser's key)
+  c->fm.gbuf_scene_gen = c->fm.scene_gen;   // whatever rewrites the scene drops the frames traced ahead: it is still their scene
   sp.k++;
   if (sp.k >= sp.n) sp.valid = false;
   return RT_OK;

@@ -1118,6 +1118,7 @@ struct ms_world {
   RawVec<uint32_t> topology;
   std::vector<float> tlas, instances, camera;
   std::vector<uint32_t> lights, draw_commands;
+  std::vector<uint32_t> instance_order;   // declaration index of the instance at each TLAS position (the TLAS builder's order)
   // glTF scene graph (SceneData.nodes / skins / animations) and World.active_anim_index
   GltfScene gltf;
   size_t active_anim = 0;
@@ -1554,6 +1555,7 @@ static void world_update(ms_world& w, float time = 0.0f) {
   w.tlas.clear();
   pack_nodes(tb.nodes, w.tlas);
   w.instances.clear();
+  w.instance_order.assign(tb.order.begin(), tb.order.end());
   for (size_t i = 0; i < tb.order.size(); i++) {
     const RawInstance& inst = w.raw_instances[tb.order[i]];
     size_t gi = inst.instance_id;
@@ -1765,6 +1767,7 @@ MS_GETTER(blas, float, blas)
 MS_GETTER(instances, float, instances)
 MS_GETTER(lights, uint32_t, lights)
 MS_GETTER(draw_commands, uint32_t, draw_commands)
+MS_GETTER(instance_order, uint32_t, instance_order)
 MS_GETTER(camera, float, camera)
 
 size_t ms_world_texture_count(const ms_world* w) { return w ? w->scene.textures_rgba.size() : 0; }

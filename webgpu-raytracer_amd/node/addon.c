@@ -1157,6 +1157,24 @@ static napi_value rtResetFrameHistory(napi_env env, napi_callback_info info) {
   return make_int(env, rt_reset_frame_history((rt_ctx*)get_ptr(env, a[0])));
 }
 
+/* ------------------------------------------------------- frame motion (RT_FRAME_TEMPORAL_MOTION, mi355rt.h) */
+/* (ctx, ids: Uint32Array of one stable id per instance) -> 0, or a negative status */
+static napi_value rtSetFrameMotionIds(napi_env env, napi_callback_info info) {
+  napi_value a[2];
+  void* p = NULL;
+  size_t n = 0;
+  if (!get_args(env, info, 2, a) || !get_bytes(env, a[1], &p, &n)) return NULL;
+  return make_int(env, rt_set_frame_motion_ids((rt_ctx*)get_ptr(env, a[0]), (const uint32_t*)p, (uint32_t)(n / 4)));
+}
+/* (ctx, out: Float32Array of width * height * 8) -> 0, or a negative status */
+static napi_value rtReadFrameMotion(napi_env env, napi_callback_info info) {
+  napi_value a[2];
+  void* out = NULL;
+  size_t no = 0;
+  if (!get_args(env, info, 2, a) || !get_bytes(env, a[1], &out, &no)) return NULL;
+  return make_int(env, rt_read_frame_motion((rt_ctx*)get_ptr(env, a[0]), (float*)out, no / 32));
+}
+
 /* ------------------------------------------------------- lightmaps (rt_bake_atlas_lightmap, rt_encode_atlas, mi355rt.h) */
 /* (ctx, width, height, padBase, tMax, entries, atlasUv or null, maxDepth, spp, seed, stages: Float64Array {passes, step,
  * normalCos, planeEps, maxDist, dilateRadius, format}, out: a typed array of width * height texels of the format, wantStats)
@@ -1258,6 +1276,7 @@ static napi_value Init(napi_env env, napi_value exports) {
                {"rtDenoiseAtlas", rtDenoiseAtlas}, {"rtBakeAtlasLightmap", rtBakeAtlasLightmap},
                {"rtDenoiseFrame", rtDenoiseFrame}, {"rtSetPresentDenoise", rtSetPresentDenoise},
                {"rtSetFrameTemporal", rtSetFrameTemporal}, {"rtResetFrameHistory", rtResetFrameHistory},
+               {"rtSetFrameMotionIds", rtSetFrameMotionIds}, {"rtReadFrameMotion", rtReadFrameMotion},
                {"rtEncodeAtlas", rtEncodeAtlas}, {"msCreate", msCreate}, {"msDestroy", msDestroy},
                {"msUpdate", msUpdate}, {"msUpdateCamera", msUpdateCamera}, {"msGet", msGet},
                {"msTextureCount", msTextureCount}, {"msTexture", msTexture},

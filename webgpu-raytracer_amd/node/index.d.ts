@@ -161,11 +161,16 @@ export class WebGPURenderer {
    *  (1 .. 256), the variance is the temporal one from varHistory frames on, history taps are accepted by normal (normalCos) and
    *  tangent plane (planeEps, world units). */
   static frameTemporalDesc(opts: { planeEps: number; maxHistory?: number; varHistory?: number; normalCos?: number;
-                                   sameInstance?: boolean }): Float64Array;
+                                   sameInstance?: boolean; motion?: boolean }): Float64Array;
   /** denoiseFrame and a filtered present() reproject and blend last frame's history first (null: the plain path). */
   setFrameTemporal(desc: Float64Array | object | null): void;
   /** Drop the temporal stage's history: the next frame is a first frame. */
   resetFrameHistory(): void;
+  /** Frame motion (frameTemporalDesc({motion: true})): the stable id of the instance at each position of the uploaded instance
+   *  array, a permutation of 0 .. n - 1; the identity after every instance upload. */
+  setFrameMotionIds(ids: Uint32Array | number[]): void;
+  /** The carry plane of the last run of the motion stage: 8 floats per pixel, {P'.xyz, bits(status)} {N'.xyz, bits(stable id)}. */
+  readFrameMotion(): { data: Float32Array; width: number; height: number };
   /** Atlas denoise (rt_denoise_atlas): `passes` passes of the 5 x 5 a-trous kernel at tap spacings step, 2 * step, ... (at
    *  most 4), guided by the points of bakePoints / bakeAtlasPoints for the same atlas: a tap counts only where its normal has
    *  a dot product >= normalCos with the texel's and its position lies within planeEps of the texel's tangent plane and

@@ -480,7 +480,7 @@ class WebGPURenderer {
   // frame is a first frame (for a caller who swaps the whole scene).
   static frameTemporalDesc(opts = {}) {
     if (opts.planeEps === undefined) throw new TypeError('frameTemporalDesc: opts.planeEps is required');
-    return Float64Array.of(opts.sameInstance ? 1 : 0, opts.maxHistory === undefined ? 32 : opts.maxHistory,
+    return Float64Array.of((opts.sameInstance ? 1 : 0) | (opts.motion ? 2 : 0), opts.maxHistory === undefined ? 32 : opts.maxHistory,
       opts.varHistory === undefined ? 4 : opts.varHistory, opts.normalCos === undefined ? 0.9 : opts.normalCos, opts.planeEps);
   }
   setFrameTemporal(desc) {
@@ -493,6 +493,21 @@ class WebGPURenderer {
   }
   resetFrameHistory() {
     this._check(native.rtResetFrameHistory(this._ctx), 'resetFrameHistory');
+  }
+  // ---- frame motion (frameTemporalDesc({..., motion: true}), RT_FRAME_TEMPORAL_MOTION): the temporal stage follows moving
+  // instances and skinned surfaces, by the frame motion rule of include/mi355rt.h; set it once a scene is uploaded.
+  // setFrameMotionIds(ids): on the upload path, the stable id of the instance at each position of the instance array now
+  // uploaded, a permutation of 0 .. n - 1 (the identity after every instance upload; a device-resident world update supplies
+  // its own).  readFrameMotion() -> {data: a Float32Array of 8 per pixel {P'.xyz, bits(status)} {N'.xyz, bits(stable id)},
+  // width, height}: where every pixel's surface point was in the previous frame.
+  setFrameMotionIds(ids) {
+    const a = ids instanceof Uint32Array ? ids : Uint32Array.from(ids);
+    this._check(native.rtSetFrameMotionIds(this._ctx, a), 'setFrameMotionIds');
+  }
+  readFrameMotion() {
+    const data = new Float32Array(this.width * this.height * 8);
+    this._check(native.rtReadFrameMotion(this._ctx, data), 'readFrameMotion');
+    return { data, width: this.width, height: this.height };
   }
   // ---- atlas denoise (rt_denoise_atlas): the edge-stopped a-trous filter of a baked atlas.  atlas = 4 floats per texel;
   // points (8 floats each) and texels as bakePoints / bakeAtlasPoints return them for the same atlas.  opts: {planeEps,

@@ -21,7 +21,8 @@ class FrameLoop:
         """denoise: None (the reference's loop, unchanged), or a frame_denoise_desc record / a dict of its keyword arguments:
         every present() then filters the frame first (WebGPURenderer.setPresentDenoise).  temporal: None, or a
         frame_temporal_desc record / dict: the filter then reprojects last frame's history first
-        (WebGPURenderer.setFrameTemporal); valid only together with denoise=."""
+        (WebGPURenderer.setFrameTemporal); valid only together with denoise=.  With motion=True in it (frame motion: the
+        stage follows moving instances and skinned surfaces) the renderer must hold a scene already - upload_scene first."""
         if temporal is not None and denoise is None:
             raise ValueError("temporal= needs denoise=: the temporal stage is a stage of the frame denoiser")
         self.renderer = renderer

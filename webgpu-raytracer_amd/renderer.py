@@ -252,6 +252,9 @@ def load_library(path=None):
         "rt_set_frame_temporal": (i32, [vp, vp]),
         "rt_reset_frame_history": (i32, [vp]),
         "rt_read_frame_history": (i32, [vp, vp, vp, ctypes.c_size_t, vp]),
+        # frame motion
+        "rt_set_frame_motion_ids": (i32, [vp, vp, u32]),
+        "rt_read_frame_motion": (i32, [vp, vp, ctypes.c_size_t]),
         # lightmaps
         "rt_bake_atlas_lightmap": (i32, [vp, vp, vp, vp, u32, vp, ctypes.c_size_t, vp, vp, vp]),
         "rt_bake_atlas_lightmap_device": (i32, [vp, vp, vp, vp, vp, ctypes.c_size_t, vp, vp, vp]),
@@ -296,7 +299,7 @@ EXPORTED_SYMBOLS = (
     "rt_dilate_atlas rt_dilate_atlas_device "
     "rt_denoise_atlas rt_denoise_atlas_device "
     "rt_denoise_frame rt_denoise_frame_device rt_set_present_denoise rt_set_frame_denoise_form rt_frame_denoise_stats "
-    "rt_set_frame_temporal rt_reset_frame_history rt_read_frame_history "
+    "rt_set_frame_temporal rt_reset_frame_history rt_read_frame_history rt_set_frame_motion_ids rt_read_frame_motion "
     "rt_bake_atlas_lightmap rt_bake_atlas_lightmap_device rt_encode_atlas rt_encode_atlas_device "
     "rt_bake_atlas_directional rt_bake_atlas_directional_lightmap").split()
 
@@ -557,8 +560,8 @@ class RtFrameDenoiseDesc(ctypes.Structure):
 class RtFrameDenoiseReport(ctypes.Structure):
     _fields_ = [("prepare_ms", ctypes.c_float), ("pass_ms", ctypes.c_float * 5), ("finish_ms", ctypes.c_float),
                 ("passes", ctypes.c_uint32), ("form", ctypes.c_uint8 * 5), ("cache_hit", ctypes.c_uint8),
-                ("temporal", ctypes.c_uint8), ("pad", ctypes.c_uint8 * 1), ("temporal_ms", ctypes.c_float),
-                ("reserved", ctypes.c_uint32 * 1)]
+                ("temporal", ctypes.c_uint8), ("motion", ctypes.c_uint8), ("temporal_ms", ctypes.c_float),
+                ("motion_ms", ctypes.c_float)]
 
 
 FRAME_DENOISE_DESC_DTYPE = np.dtype([("passes", "<u4"), ("step", "<u4"), ("flags", "<u4"), ("normal_cos", "<f4"),
@@ -581,6 +584,10 @@ def frame_denoise_desc(passes=4, step=1, *, plane_eps, normal_cos=0.9, sigma_lum
 # frame temporal: mirror of rt_frame_temporal_desc, and the descriptor as a numpy record
 RT_FRAME_TEMPORAL_MAX_HISTORY = 256
 RT_FRAME_TEMPORAL_SAME_INSTANCE = 1
+RT_FRAME_TEMPORAL_MOTION = 2
+# the status word of a carry texel (readFrameMotion) and the id of a pixel that has none
+RT_FRAME_MOTION_BACKGROUND, RT_FRAME_MOTION_UNTRACKED, RT_FRAME_MOTION_UNMOVED, RT_FRAME_MOTION_MOVED = 0, 1, 2, 3
+RT_FRAME_MOTION_NO_ID = 0xffffffff
 
 
 class RtFrameTemporalDesc(ctypes.Structure):
@@ -592,17 +599,41 @@ FRAME_TEMPORAL_DESC_DTYPE = np.dtype([("flags", "<u4"), ("max_history", "<u4"), 
                                       ("plane_eps", "<f4"), ("reserved", "<u4", (3,))])
 
 
-def frame_temporal_desc(max_history=32, var_history=4, *, plane_eps, normal_cos=0.9, same_instance=False):
+def frame_temporal_desc(max_history=32, var_history=4, *, plane_eps, normal_cos=0.9, same_instance=False, motion=False):
     """An rt_frame_temporal_desc as a one-element FRAME_TEMPORAL_DESC_DTYPE record: the history of a pixel grows to
     max_history frames (1 .. 256; 1 keeps none), after which the blend factor stays 1 / max_history; from var_history frames on
     the variance the passes see is the temporal one; a history tap is accepted where its normal has a dot product >= normal_cos
     with the pixel's and its world position lies within plane_eps (world units) of the pixel's tangent plane; same_instance
-    keeps taps on the pixel's instance."""
+    keeps taps on the pixel's instance; motion carries every pixel back along its own triangle's motion first (moving instances,
+    skinned surfaces), and same_instance then compares stable ids (setFrameMotionIds)."""
     d = np.zeros(1, FRAME_TEMPORAL_DESC_DTYPE)
-    d["flags"] = RT_FRAME_TEMPORAL_SAME_INSTANCE if same_instance else 0
+    d["flags"] = (RT_FRAME_TEMPORAL_SAME_INSTANCE if same_instance else 0) | (RT_FRAME_TEMPORAL_MOTION if motion else 0)
     d["max_history"], d["var_history"] = int(max_history), int(var_history)
     d["normal_cos"], d["plane_eps"] = normal_cos, plane_eps
     return d
+
+
+def frame_motion_pixels(carry, prev_uniforms):
+    """Screen-space motion from the carry plane of readFrameMotion and the 256-byte uniform block of the PREVIOUS frame: ->
+    (H, W, 2) float64, for every pixel the position (x, y) in the previous frame's image, pixel centres at whole numbers, of
+    the surface point it shows now; NaN where the pixel is background or untracked, or the point lay behind that camera.
+    Subtract the pixel's own coordinates for a motion vector.  Float64, a convenience: not part of the rule."""
+    c = np.asarray(carry, np.float32)
+    u32 = np.ascontiguousarray(prev_uniforms).view(np.uint8).reshape(-1)[:256]
+    u = u32.view(np.float32).astype(np.float64)
+    eye, ll, hor, ver = u[0:3], u[4:7], u[8:11], u[12:15]
+    Wd, Hd = (float(v) for v in u32.view(np.uint32)[53:55])
+    jx, jy = u[56], u[57]
+    status = np.ascontiguousarray(c[..., 3]).view(np.uint32)
+    P = c[..., 0:3].astype(np.float64)
+    nrm = np.cross(hor, ver)
+    with np.errstate(all="ignore"):
+        s = np.dot(ll - eye, nrm) / ((P - eye) @ nrm)
+        r = (P - eye) * s[..., None] - (ll - eye)
+        uu, vv = (r @ hor) / np.dot(hor, hor), (r @ ver) / np.dot(ver, ver)
+    out = np.stack([uu * Wd - 0.5 - jx * Wd, (1.0 - vv) * Hd - 0.5 - jy * Hd], axis=-1)
+    out[(status < RT_FRAME_MOTION_UNMOVED) | ~(s > 0)] = np.nan
+    return out
 
 
 def _frame_temporal_record(desc):
@@ -761,7 +792,8 @@ class WebGPURenderer:
     # the bridge arrays of the device-resident world (rt_world_read): name -> (rt_world_array, dtype, row width)
     _WORLD_ARRAYS = {"vertices": (0, np.float32, 4), "normals": (1, np.float32, 4), "uvs": (2, np.float32, 2),
                      "mesh_topology": (3, np.uint32, 20), "tlas": (4, np.float32, 8), "blas": (5, np.float32, 8),
-                     "instances": (6, np.float32, 36), "lights": (7, np.uint32, 2), "draw_commands": (8, np.uint32, 4)}
+                     "instances": (6, np.float32, 36), "lights": (7, np.uint32, 2), "draw_commands": (8, np.uint32, 4),
+                     "instance_order": (9, np.uint32, 1)}
 
     def worldRead(self, name):
         """One bridge array as the last device-resident update(t) left it in HBM (flat, the bridge getter's dtype)."""
@@ -1567,7 +1599,7 @@ class WebGPURenderer:
         return {"prepare_ms": float(r.prepare_ms), "pass_ms": [float(r.pass_ms[p]) for p in range(n)],
                 "finish_ms": float(r.finish_ms), "forms": [("none", "lds", "direct")[r.form[p]] for p in range(n)],
                 "cache_hit": bool(r.cache_hit), "temporal_ms": float(r.temporal_ms),
-                "temporal": ("off", "ran", "reused")[r.temporal]}
+                "temporal": ("off", "ran", "reused")[r.temporal], "motion": bool(r.motion), "motion_ms": float(r.motion_ms)}
 
     def setFrameTemporal(self, desc):
         """desc (a frame_temporal_desc record or a dict): from now on denoiseFrame, denoiseFrameDevice and a filtered present()
@@ -1578,6 +1610,20 @@ class WebGPURenderer:
             return
         d = _frame_temporal_record(desc)
         self._check(self.L.rt_set_frame_temporal(self.ctx, _ptr(d)), "setFrameTemporal")
+
+    def setFrameMotionIds(self, ids):
+        """Frame motion on the upload path: ids[p] is the stable id of the instance at position p of the instance array now
+        uploaded - a permutation of 0 .. n - 1 (WorldBridge.instanceOrder).  Every upload of instances resets it to the
+        identity; a device-resident world update supplies its own."""
+        a = np.ascontiguousarray(ids, dtype=np.uint32).reshape(-1)
+        self._check(self.L.rt_set_frame_motion_ids(self.ctx, _ptr(a), a.size), "setFrameMotionIds")
+
+    def readFrameMotion(self):
+        """-> (H, W, 8) f32, the carry plane of the last run of the motion stage: {P'.xyz, bits(status)} {N'.xyz, bits(stable
+        id)}, P' where the pixel's surface point was in the previous frame (frame_motion_pixels).  Blocking."""
+        out = np.empty((self.height, self.width, 8), np.float32)
+        self._check(self.L.rt_read_frame_motion(self.ctx, _ptr(out), self.width * self.height), "readFrameMotion")
+        return out
 
     def resetFrameHistory(self):
         """Drop the temporal stage's history: the next frame is a first frame.  For a caller who swaps the whole scene."""
@@ -1819,6 +1865,14 @@ def _kernel_times(self):
 WebGPURenderer.kernelTimes = _kernel_times
 
 
+def _declare_motion_ids(renderer, bridge):
+    """after an upload of the bridge's instances: their stable ids, the TLAS builder's order, for frame motion - where both
+    sides have them (the oracle binding and hand-made bridges do not)"""
+    order = getattr(bridge, "instanceOrder", None)
+    if order is not None and len(order) and hasattr(renderer, "setFrameMotionIds"):
+        renderer.setFrameMotionIds(order)
+
+
 def upload_scene(renderer, bridge, width, height):
     """The reference's scene-load sequence (src/main.ts:51-67,99-116): textures, geometry, BVH,
     topology, instances, lights, draw commands, uniforms, then resolution + reset.
@@ -1828,6 +1882,7 @@ def upload_scene(renderer, bridge, width, height):
     renderer.updateCombinedBVH(bridge.tlas, bridge.blas)
     renderer.updateBuffer("topology", bridge.mesh_topology)
     renderer.updateBuffer("instance", bridge.instances)
+    _declare_motion_ids(renderer, bridge)
     renderer.updateBuffer("lights", bridge.lights)
     renderer.updateBuffer("draw_commands", bridge.draw_commands)
     renderer.updateScreenSize(width, height)
@@ -1855,6 +1910,7 @@ def sync_world(renderer, bridge, width, height):
         return True
     rebind |= bool(renderer.updateCombinedBVH(bridge.tlas, bridge.blas))
     rebind |= bool(renderer.updateBuffer("instance", bridge.instances))
+    _declare_motion_ids(renderer, bridge)
     rebind |= bool(renderer.updateBuffer("draw_commands", bridge.draw_commands))
     if bridge.hasNewGeometry:
         rebind |= bool(renderer.updateCombinedGeometry(bridge.vertices, bridge.normals, bridge.uvs))

@@ -35,7 +35,7 @@ def _load():
         f = getattr(lib, "ms_world_" + name)
         f.restype = _F32P
         f.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_size_t)]
-    for name in ("mesh_topology", "lights", "draw_commands"):
+    for name in ("mesh_topology", "lights", "draw_commands", "instance_order"):
         f = getattr(lib, "ms_world_" + name)
         f.restype = _U32P
         f.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_size_t)]
@@ -196,7 +196,7 @@ class WorldBridge:
     def _refresh(self):
         for name in ("vertices", "normals", "uvs", "tlas", "blas", "instances", "camera"):
             self._cache[name] = self._get(name, np.float32)
-        for name in ("mesh_topology", "lights", "draw_commands"):
+        for name in ("mesh_topology", "lights", "draw_commands", "instance_order"):
             self._cache[name] = self._get(name, np.uint32)
 
     vertices = property(lambda s: s._cache["vertices"])
@@ -209,6 +209,8 @@ class WorldBridge:
     lights = property(lambda s: s._cache["lights"])
     draw_commands = property(lambda s: s._cache["draw_commands"])
     cameraData = property(lambda s: s._cache["camera"])
+    # the declaration index of the instance at each position of `instances`: stable ids for WebGPURenderer.setFrameMotionIds
+    instanceOrder = property(lambda s: s._cache["instance_order"])
 
     @property
     def lightCount(self):
