@@ -113,15 +113,35 @@ __global__ void k_prepare_instances(const float4* __restrict__ inst, float4* __r
 }
 
 // ================================================================ primary visibility
-// LDS = false: one wave (one 8x8 tile) per workgroup, records through L1 / L2.  LDS = true (small scenes): four tiles per
-// 256-thread workgroup and the records staged in LDS first — the walk is a chain of dependent fetches, and an LDS
+// LDS = false: one wave (one 8x8 tile) per workgroup, records through L1 / L2.  LDS = true (small scenes): 256-thread
+// workgroups, one wave per tile, and the records staged in LDS first — the walk is a chain of dependent fetches, and an LDS
 // fetch returns in a fraction of an L1 hit's time.  The launch's dynamic LDS: launch_plan.h primary_lds_slots.
-template <bool DETAIL, bool LDS>
-__global__ __launch_bounds__(LDS ? 256 : 64) void k_primary_visibility(DevScene Sg, DevFrame F, rt_scene_uniforms U,
-                                                                       const DevFrameSlot* __restrict__ slots, uint32_t n_tiles,
-                                                                       uint32_t n_nodes_total, uint32_t n_tris_total,
-                                                                       uint32_t n_inst_total, uint32_t n_verts_total,
-                                                                       const float4* __restrict__ tri_shade_w) {
+// TILES = true (an LDS form, k_primary_visibility_tiles): a wave casts `rounds` tiles one after the other, tile primary_tile(blockIdx.x, rounds, r, wave)
+// in round r (lds_sizes.h), so that the staging, the barrier, everything that depends on the dispatch alone and the counter
+// flush are paid once per wave, not once per tile.  It is the form of an unstriped dispatch of a one-leaf scene (the TLAS is
+// one node, a leaf: launch_plan.h one_leaf_lds), which is what keeps it inside the registers of eight waves per SIMD: no
+// TLAS loop around the walk of the one instance, none of the stripe tests and their reciprocals, and what is read once per
+// wave lives in scalar registers: at most 96 of them (amdgpu_num_sgpr on k_primary_visibility_tiles alone), which is what
+// eight waves per SIMD may have; left to itself the compiler takes 105 and the form runs at seven.  launch_plan.h
+// primary_shape chooses the form and rounds, primary_grid_x the grid.
+// Results do not depend on where these values live; the eighth wave does.  Both devices below were needed with the
+// compiler of ROCm 7.2.0 (AMD clang 22.0.0git, roc-7.2.0) and are held by tests/test_kernel_resources_primary.py (VGPRs,
+// SGPRs, spills, waves per SIMD): with another compiler, look there first.
+//
+// A value every lane of the wave holds alike, kept in a scalar register from here on.  `zero` is 0 in every lane in a way
+// the compiler does not see through: it moves a readfirstlane of a value it can prove uniform back in front of the
+// arithmetic that made it, which leaves the result in a vector register.
+__device__ __forceinline__ float wave_uniform(float x, uint32_t zero = 0u) {
+  return rt_u2f((uint32_t)__builtin_amdgcn_readfirstlane((int)(rt_f2u(x) | zero)));
+}
+__device__ __forceinline__ float4 wave_uniform(float4 q) {
+  return make_float4(wave_uniform(q.x), wave_uniform(q.y), wave_uniform(q.z), wave_uniform(q.w));
+}
+template <bool DETAIL, bool LDS, bool TILES>
+__device__ __forceinline__ void primary_visibility(DevScene Sg, DevFrame F, rt_scene_uniforms U, const DevFrameSlot* __restrict__ slots,
+                                                   uint32_t n_tiles, uint32_t n_nodes_total, uint32_t n_tris_total,
+                                                   uint32_t n_inst_total, const float4* __restrict__ tri_shade_w, uint32_t rounds) {
+  static_assert(LDS || !TILES, "the form of many tiles per wave is an LDS form");
   // tri_shade_w (LDS form, one-leaf-TLAS scenes; else null): the shading records with world-space vertex normals
   // (k_prepare_world_tris), staged in place of tri_shade
   extern __shared__ float4 s_primary[];
@@ -141,8 +161,10 @@ __global__ __launch_bounds__(LDS ? 256 : 64) void k_primary_visibility(DevScene 
     S.tri_shade = stage(tri_shade_w ? tri_shade_w : Sg.tri_shade, (size_t)8 * n_tris_total);
     __syncthreads();
   }
-  const uint32_t tile_id = LDS ? blockIdx.x * 4u + (threadIdx.x >> 6) : blockIdx.x;
+  const uint32_t wave = TILES ? (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : threadIdx.x >> 6;
   const uint32_t lane_id = threadIdx.x & 63u;
+  const uint32_t n_rounds = TILES ? rounds : 1u;
+  const uint32_t first_tile = LDS ? primary_tile(blockIdx.x, n_rounds, 0u, wave) : blockIdx.x;
   // batched dispatch: blockIdx.y selects the frame; its jitter and G-buffer planes come from the slot table
   if (slots) {
     const DevFrameSlot sl = slots[blockIdx.y];
@@ -153,55 +175,88 @@ __global__ __launch_bounds__(LDS ? 256 : 64) void k_primary_visibility(DevScene 
     F.normal_id = sl.normal_id;
     F.depth = sl.depth;
   }
-  uint32_t x, y;
-  bool live;
-  if (F.own_period) {
-    // sharded render with tile-aligned stripes: blockIdx.x enumerates only the tiles of the rows this rank owns
-    const uint32_t tiles_x = (U.width + 7u) / 8u;
-    uint32_t trow = tile_id / tiles_x;
-    trow = (trow / F.own_run) * F.own_period + F.own_first + (trow % F.own_run);
-    x = (tile_id % tiles_x) * 8u + (lane_id & 7u);
-    y = trow * 8u + (lane_id >> 3);
-    live = x < U.width && y < U.height;
-  } else {
-    live = tile_pixel(U, tile_id, lane_id, x, y) && owns_row(F, y);
+  // What depends on the dispatch and the frame alone: every lane computes it from kernel arguments and the slot.
+  const rt3 eye = rt3_make(U.camera.origin[0], U.camera.origin[1], U.camera.origin[2]);
+  const rt3 ll = rt3_make(U.camera.lower_left[0], U.camera.lower_left[1], U.camera.lower_left[2]);
+  const rt3 hor = rt3_make(U.camera.horizontal[0], U.camera.horizontal[1], U.camera.horizontal[2]);
+  const rt3 ver = rt3_make(U.camera.vertical[0], U.camera.vertical[1], U.camera.vertical[2]);
+  const rt3 center = ll + hor * 0.5f + ver * 0.5f;
+  float focal_length = rt_length(center - eye);
+  const float z_near = 0.001f, z_far = 10000.0f;
+  float t_near = z_near / focal_length, t_far = z_far / focal_length;
+  float width_f = (float)U.width, height_f = (float)U.height;
+  float jitter_x = U.jitter[0] * width_f, jitter_y = U.jitter[1] * height_f;
+  TlasLeaf leaf = {};
+  if (TILES) {
+    const uint32_t zero = (threadIdx.x >> 6) ^ wave;
+    focal_length = wave_uniform(focal_length, zero);
+    t_near = wave_uniform(t_near, zero);
+    t_far = wave_uniform(t_far, zero);
+    width_f = wave_uniform(width_f, zero);
+    height_f = wave_uniform(height_f, zero);
+    jitter_x = wave_uniform(jitter_x, zero);
+    jitter_y = wave_uniform(jitter_y, zero);
+    if (U.blas_base_idx != 0u) {   // node 0, the TLAS leaf, and the rows of the one instance it names
+      leaf.lo = wave_uniform(S.nodes[0]);
+      leaf.hi = wave_uniform(S.nodes[1]);
+      const InvRows m = load_inv_rows(S, rt_f2u(leaf.hi.w) >> 3);
+      leaf.m.r0 = wave_uniform(m.r0);
+      leaf.m.r1 = wave_uniform(m.r1);
+      leaf.m.r2 = wave_uniform(m.r2);
+      leaf.m.tail = wave_uniform(m.tail);
+    }
   }
-  live = live && tile_id < n_tiles;
+  uint32_t n_live = 0;   // TILES: pixels cast by this wave (wave-uniform)
   LaneCounters c = {0, 0, 0, 0, 0, 0};
-  if (live) {
+  for (uint32_t r = 0; r < n_rounds; r++) {
+    const uint32_t tile_id = first_tile + 4u * r;   // = primary_tile(blockIdx.x, n_rounds, r, wave)
+    if (TILES && tile_id >= n_tiles) break;         // wave-uniform; the rounds after it lie higher still
+    uint32_t x, y;
+    bool live;
+    if (!TILES && F.own_period) {
+      // sharded render with tile-aligned stripes: blockIdx.x enumerates only the tiles of the rows this rank owns
+      const uint32_t tiles_x = (U.width + 7u) / 8u;
+      uint32_t trow = tile_id / tiles_x;
+      trow = (trow / F.own_run) * F.own_period + F.own_first + (trow % F.own_run);
+      x = (tile_id % tiles_x) * 8u + (lane_id & 7u);
+      y = trow * 8u + (lane_id >> 3);
+      live = x < U.width && y < U.height;
+    } else {
+      live = tile_pixel(U, tile_id, lane_id, x, y) && (TILES || owns_row(F, y));
+    }
+    live = live && tile_id < n_tiles;
+    if (TILES)
+      n_live += (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(live));
+    else if (live)
+      c.primary = 1;
+    if (!live) continue;
     const uint32_t p_idx = y * U.width + x;
-    rt3 eye = rt3_make(U.camera.origin[0], U.camera.origin[1], U.camera.origin[2]);
-    rt3 ll = rt3_make(U.camera.lower_left[0], U.camera.lower_left[1], U.camera.lower_left[2]);
-    rt3 hor = rt3_make(U.camera.horizontal[0], U.camera.horizontal[1], U.camera.horizontal[2]);
-    rt3 ver = rt3_make(U.camera.vertical[0], U.camera.vertical[1], U.camera.vertical[2]);
-    rt3 center = ll + hor * 0.5f + ver * 0.5f;
-    float focal_length = rt_length(center - eye);
-    const float z_near = 0.001f, z_far = 10000.0f;
-    float u = ((float)x + 0.5f + U.jitter[0] * (float)U.width) / (float)U.width;
-    float v = 1.0f - ((float)y + 0.5f + U.jitter[1] * (float)U.height) / (float)U.height;
+    float u = ((float)x + 0.5f + jitter_x) / width_f;
+    float v = 1.0f - ((float)y + 0.5f + jitter_y) / height_f;
     rt3 d = ll + u * hor + v * ver - eye;
-    c.primary = 1;
-    Hit hit = trace_closest<DETAIL>(S, U.blas_base_idx, eye, d, z_near / focal_length, z_far / focal_length, c);
+    const HitUV hv = trace_closest_uv<DETAIL, TILES>(S, U.blas_base_idx, eye, d, t_near, t_far, c, leaf);
+    const Hit hit = hv.hit;
     if (hit.inst < 0) {
       F.albedo[p_idx] = 0u;
       F.normal_id[p_idx] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
       F.depth[p_idx] = 1.0f;
     } else {
-      InvRows m = load_inv_rows(S, (uint32_t)hit.inst);
-      Bary b = barycentrics(S, (uint32_t)hit.tri, mul_point(m, eye), mul_dir(m, d));
+      // u and v of the accepted triangle test are the barycentrics of the hit (trace_closest_uv)
+      const float b_u = hv.u, b_v = hv.v, b_w = 1.0f - hv.u - hv.v;
       const float4* ts = S.tri_shade + 8 * (size_t)hit.tri;
       const float4 d0 = ts[0], d2 = ts[2], q4 = ts[4], q5 = ts[5], q6 = ts[6], q7 = ts[7];
       rt3 wn0 = xyz(q4), wn1 = xyz(q5), wn2 = xyz(q6);
       if (!LDS || !tri_shade_w) {   // wave-uniform
+        const InvRows m = TILES ? leaf.m : load_inv_rows(S, (uint32_t)hit.inst);
         wn0 = rt_normalize(normal_to_world(m, wn0));
         wn1 = rt_normalize(normal_to_world(m, wn1));
         wn2 = rt_normalize(normal_to_world(m, wn2));
       }
-      rt3 n = rt_normalize(wn0 * b.w + wn1 * b.u + wn2 * b.v);
+      rt3 n = rt_normalize(wn0 * b_w + wn1 * b_u + wn2 * b_v);
       rt2 pn = pack_normal(n);
       rt3 albedo = xyz(d0);
       if (d2.x > -0.5f) {
-        rt2 tuv = rt2_make(q4.w, q5.w) * b.w + rt2_make(q6.w, q7.x) * b.u + rt2_make(q7.y, q7.z) * b.v;
+        rt2 tuv = rt2_make(q4.w, q5.w) * b_w + rt2_make(q6.w, q7.x) * b_u + rt2_make(q7.y, q7.z) * b_v;
         albedo = albedo * sample_tex(S, tuv, rt_f2i32_sat(d2.x));
       }
       F.albedo[p_idx] = rt_unorm8(albedo.x) | (rt_unorm8(albedo.y) << 8) | (rt_unorm8(albedo.z) << 16) | (255u << 24);
@@ -211,7 +266,24 @@ __global__ __launch_bounds__(LDS ? 256 : 64) void k_primary_visibility(DevScene 
       F.depth[p_idx] = z_clip / z_view;
     }
   }
-  flush_counters<DETAIL>(c, F.counters, tile_id + blockIdx.y * 977u);
+  if (TILES) c.primary = lane_id == 0u ? n_live : 0u;   // the wave's sum is what the flush adds
+  flush_counters<DETAIL>(c, F.counters, first_tile + blockIdx.y * 977u);
+}
+// The forms of one tile per wave; `rounds` is not read.
+template <bool DETAIL, bool LDS>
+__global__ __launch_bounds__(LDS ? 256 : 64) void k_primary_visibility(DevScene Sg, DevFrame F, rt_scene_uniforms U,
+                                                                       const DevFrameSlot* __restrict__ slots, uint32_t n_tiles,
+                                                                       uint32_t n_nodes_total, uint32_t n_tris_total,
+                                                                       uint32_t n_inst_total, uint32_t n_verts_total,
+                                                                       const float4* __restrict__ tri_shade_w, uint32_t rounds) {
+  primary_visibility<DETAIL, LDS, false>(Sg, F, U, slots, n_tiles, n_nodes_total, n_tris_total, n_inst_total, tri_shade_w, rounds);
+}
+// The form of many tiles per wave, alone under the cap of 96 scalar registers (above).
+template <bool DETAIL>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(96))) void k_primary_visibility_tiles(
+    DevScene Sg, DevFrame F, rt_scene_uniforms U, const DevFrameSlot* __restrict__ slots, uint32_t n_tiles, uint32_t n_nodes_total,
+    uint32_t n_tris_total, uint32_t n_inst_total, uint32_t n_verts_total, const float4* __restrict__ tri_shade_w, uint32_t rounds) {
+  primary_visibility<DETAIL, true, true>(Sg, F, U, slots, n_tiles, n_nodes_total, n_tris_total, n_inst_total, tri_shade_w, rounds);
 }
 
 }  // namespace rtk

@@ -38,6 +38,9 @@ struct PlanKnobs {
   bool leaf_sweep_guard = false; // MI355RT_LEAF_SWEEP_GUARD=1 (test hook): every walk of a sweep form sweeps the node records
                                  // instead of the leaf records (k_traverse.hip.h traverse_leaves), as the wave of a ray with
                                  // a non-finite slab operand does
+  uint32_t n_cus = 256;          // compute units of the device (rt_create; the MI355X has 256)
+  uint32_t primary_rounds = 0;   // MI355RT_PRIMARY_ROUNDS=n (test hook, sweeps): the LDS form of the primary kernel casts n
+                                 // tiles per wave whatever the dispatch's size; 0 = primary_shape chooses
 };
 // What the host knows of the uploaded scene's materials (scene_facts.h works it out from the bytes of a topology upload).
 // plain: every triangle is Lambertian or a light, untextured, and emits only if it is a light.  known = false: the host has
@@ -100,6 +103,8 @@ inline bool scene_fits_lds(const SceneSize& s, const PlanKnobs& k) {
 }
 // ... and its TLAS is one node, which is a leaf (k_validate_scene, or the world update's builder): the one-leaf forms, which
 // read the per-triangle world records
+// The forms chosen on this (the ONE_INST forms of the path tracer, k_primary_visibility_tiles) do not test the node's leaf
+// word again: a TLAS of one node that is not a leaf naming an instance never reaches a launch (k_validate_scene refuses it).
 inline bool one_leaf_lds(const SceneSize& s, const PlanKnobs& k) { return scene_fits_lds(s, k) && s.n_tlas == 1; }
 // the trace kernels walk child-pair records, not single nodes (rt_set_walk; auto: a scene of one instance).  prepare_scene
 // builds the records this says a launch will read.
@@ -210,15 +215,42 @@ inline PersistentShape persistent_shape(const SceneSize& s, const PlanKnobs& k, 
 
 // ---- the primary kernel
 struct PrimaryShape {
-  bool lds;   // small scene: records staged in LDS, four tiles per workgroup
+  bool lds;   // small scene: records staged in LDS, four tiles at a time per workgroup
   int block;
-  uint32_t tiles_per_workgroup;
+  uint32_t tiles_per_workgroup;   // at a time: one per wave
   size_t dyn;
+  uint32_t rounds = 1;   // tiles each wave casts, one after the other, behind the one staging of its workgroup
+  bool tiles = false;    // ... in the LDS form that does so (k_primary_visibility_tiles) when rounds > 1: an
+                         // unstriped dispatch of a one-leaf scene with tiles enough
 };
-inline PrimaryShape primary_shape(const SceneSize& s, const PlanKnobs& k) {
+// The most rounds the planner chooses on its own (sweep of 1 / 2 / 4 / 8 / 16 on the headline: profiles/r15_primary_tiles.txt).
+constexpr uint32_t PRIMARY_ROUNDS_MAX = 8;
+// ... and the fewest workgroups it leaves the grid, in units of what the chip keeps resident (eight 256-thread workgroups
+// per CU at 8 waves per SIMD): longer workgroups quantise the end of the grid more coarsely.  Measured at 1080p (32 400
+// tiles a frame): one frame in two rounds, 4 050 workgroups or 2.0 times the resident 2 048, is 0.9 % slower per frame of
+// the live loop than one round; the 32-frame batch in 16 rounds, 7.9 times, is slower than in 8 rounds, 15.8 times.
+constexpr uint32_t PRIMARY_MIN_RESIDENT_ROUNDS = 12;
+// tile_frames: the tiles the dispatch casts, this rank's tiles x its frames (0: not said, one round); striped: the rank
+// renders some of the image's rows only.  The form of many tiles per wave stages the scene once per workgroup, so fewer and
+// longer workgroups stage less.  rounds = the largest power of two, PRIMARY_ROUNDS_MAX at most, that leaves the grid
+// PRIMARY_MIN_RESIDENT_ROUNDS x 8 workgroups per CU: up to four 1080p frames keep one round, eight get 2, a 32-frame batch
+// gets 8.  With one round the form of one tile per wave runs: the other one pays its once-per-wave part for a single tile
+// (Cornell headline forced to one round: 21.92 ms per image against the parent's 21.65).
+inline PrimaryShape primary_shape(const SceneSize& s, const PlanKnobs& k, uint64_t tile_frames = 0, bool striped = false) {
   const size_t plds = primary_lds_slots(s) * 16;
-  if (plds <= 32 * 1024 && !k.no_lds_staging) return {true, 256, 4u, plds};
-  return {false, 64, 1u, 0};
+  if (plds > 32 * 1024 || k.no_lds_staging) return {false, 64, 1u, 0, 1u, false};
+  if (!one_leaf_lds(s, k) || striped) return {true, 256, 4u, plds, 1u, false};
+  uint32_t rounds = 1;
+  if (k.primary_rounds)
+    rounds = k.primary_rounds;
+  else
+    while (rounds < PRIMARY_ROUNDS_MAX && tile_frames / ((uint64_t)8 * rounds) >= (uint64_t)PRIMARY_MIN_RESIDENT_ROUNDS * 8 * k.n_cus) rounds *= 2;
+  return {true, 256, 4u, plds, rounds, rounds > 1};
+}
+// x size of the primary kernel's grid for a rank that owns own_tiles (> 0) tiles; y is the number of frames
+inline uint32_t primary_grid_x(const PrimaryShape& p, uint32_t own_tiles) {
+  const uint64_t per_wg = (uint64_t)p.tiles_per_workgroup * p.rounds;
+  return (uint32_t)((own_tiles + per_wg - 1) / per_wg);
 }
 
 // ---- the trace kernels

@@ -51,6 +51,12 @@ struct PairPlan {
   TlasRoot troot;
 };
 
+// The 8x8 tile that wave `wave` (0-3) of workgroup `wg` casts in round `r` of the LDS form of k_primary_visibility, whose
+// workgroups stage the scene once and then walk `rounds` tiles per wave: contiguous, so that a workgroup's tiles are
+// neighbours and the tiles at or above the dispatch's count are the last ones of the last workgroup (launch_plan.h
+// primary_shape chooses rounds, primary_grid_x the grid).  constexpr: the kernel and the host's tests call the same function.
+constexpr uint32_t primary_tile(uint32_t wg, uint32_t rounds, uint32_t r, uint32_t wave) { return (wg * rounds + r) * 4u + wave; }
+
 // FORM of k_ray_query: the five forms of the 256-thread trace kernels (launch_plan.h trace_shape picks as it does for
 // k_wf_trace / k_wf_trace_pairs)
 enum { RT_RQ_NODE_LDS = 0, RT_RQ_NODE_MIXED = 1, RT_RQ_NODE_RAYREG = 2, RT_RQ_PAIR_LDS = 3, RT_RQ_PAIR_GLOBAL = 4 };

@@ -1215,6 +1215,7 @@ rt_ctx* rt_create(int device_ordinal) {
   if (const char* e = getenv("MI355RT_TREELET_ORDER")) c->treelet_order = e[0] == 'w' ? 0 : (e[0] == 'i' ? 1 : 2);
   if (const char* e = getenv("MI355RT_WALK")) c->knobs.walk = (e[0] == 'n' || e[0] == '0') ? 0 : ((e[0] == 'a' || e[0] == '2') ? 2 : 1);   // node / pairs / auto
   if (const char* e = getenv("MI355RT_WF_RAYREG")) c->knobs.wf_rayreg = atoi(e) != 0 ? 1 : 0;
+  if (const char* e = getenv("MI355RT_PRIMARY_ROUNDS")) c->knobs.primary_rounds = (uint32_t)std::max(0, std::min(64, atoi(e)));
   if (const char* e = getenv("MI355RT_WF_BLOCKS_PER_CU")) {
     const int b = atoi(e);
     if (b >= 1 && b <= 8) c->knobs.wf_blocks_per_cu = b;
@@ -1230,6 +1231,7 @@ rt_ctx* rt_create(int device_ordinal) {
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device_ordinal) == hipSuccess && prop.multiProcessorCount > 0)
       c->num_cus = prop.multiProcessorCount;
+    c->knobs.n_cus = (uint32_t)c->num_cus;
     (void)hipMalloc(&c->ticket.ptr, 256);
     c->ticket.capacity = c->ticket.size = 256;
   }
@@ -2203,9 +2205,12 @@ static const void* const wf_node_rayreg_fns[2][2] = {
 // the shade kernel by [first depth][detail], the primary kernel by [detail][lds]
 static const void* const wf_shade_fns[2][2] = {{(const void*)rtk::k_wf_shade<false, false>, (const void*)rtk::k_wf_shade<false, true>},
                                                {(const void*)rtk::k_wf_shade<true, false>, (const void*)rtk::k_wf_shade<true, true>}};
-static const void* const primary_fns[2][2] = {
-    {(const void*)rtk::k_primary_visibility<false, false>, (const void*)rtk::k_primary_visibility<false, true>},
-    {(const void*)rtk::k_primary_visibility<true, false>, (const void*)rtk::k_primary_visibility<true, true>}};
+// [counting build][form]: global memory, LDS, LDS with many tiles per wave (launch_plan.h primary_shape)
+static const void* const primary_fns[2][3] = {
+    {(const void*)rtk::k_primary_visibility<false, false>, (const void*)rtk::k_primary_visibility<false, true>,
+     (const void*)rtk::k_primary_visibility_tiles<false>},
+    {(const void*)rtk::k_primary_visibility<true, false>, (const void*)rtk::k_primary_visibility<true, true>,
+     (const void*)rtk::k_primary_visibility_tiles<true>}};
 // Wavefront form: per depth one shade launch and two trace launches, all enqueued without host readback.
 static int launch_wavefront(rt_ctx* c, const DevScene& S, const DevFrame& F, const DevFrameSlot* dslots, uint32_t n) {
   const size_t npx = (size_t)c->width * c->height;
@@ -4554,13 +4559,17 @@ static int compute_frames(rt_ctx* c, const uint32_t* frame_counts, uint32_t n, u
   // own_tiles == 0: tile-aligned stripes and a rank that owns no tile row (fewer tile rows than ranks) - nothing to cast, and
   // a grid of x-size 0 is an invalid launch configuration
   if (own_tiles) {
-    const lp::PrimaryShape shape = lp::primary_shape(size, c->knobs);
+    const lp::PrimaryShape shape = lp::primary_shape(size, c->knobs, (uint64_t)own_tiles * n, c->stripe_count > 1 && c->stripe_rows);
     uint32_t nn = c->n_nodes, nt = c->n_tris, ni = c->n_instances, nv = c->n_verts, n_ptiles = own_tiles;
     // one-leaf scenes: the LDS form stages the shading records with world-space vertex normals
-    const float4* tsw = (lp::one_leaf_lds(size, c->knobs) && !c->world_rec_dirty) ? (const float4*)c->tri_shade_w.ptr : nullptr;
-    void* args[] = {&S, &Fp, &c->uniforms, &dslots, &n_ptiles, &nn, &nt, &ni, &nv, &tsw};
-    const uint32_t per_wg = shape.tiles_per_workgroup;
-    HIP_TRY(c, hipLaunchKernel(primary_fns[c->detailed_counters][shape.lds], dim3((own_tiles + per_wg - 1) / per_wg, n),
+    const bool one_leaf = lp::one_leaf_lds(size, c->knobs);
+    const float4* tsw = (one_leaf && !c->world_rec_dirty) ? (const float4*)c->tri_shade_w.ptr : nullptr;
+    uint32_t rounds = shape.rounds;   // LDS form: tiles per wave behind one staging (lds_sizes.h primary_tile)
+    if (getenv("MI355RT_DEBUG_SHAPE"))
+      fprintf(stderr, "[mi355rt] primary kernel: %s form, %u rounds, grid %u x %u, %zu bytes of LDS\n",
+              shape.lds ? (shape.tiles ? "LDS many-tiles" : "LDS") : "global", rounds, lp::primary_grid_x(shape, own_tiles), (unsigned)n, shape.dyn);
+    void* args[] = {&S, &Fp, &c->uniforms, &dslots, &n_ptiles, &nn, &nt, &ni, &nv, &tsw, &rounds};
+    HIP_TRY(c, hipLaunchKernel(primary_fns[c->detailed_counters][shape.lds ? (shape.tiles ? 2 : 1) : 0], dim3(lp::primary_grid_x(shape, own_tiles), n),
                                dim3(shape.block), args, shape.dyn, c->stream));
   }
   if (ev) HIP_TRY(c, hipEventRecord(ev->b, c->stream));
