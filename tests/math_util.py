@@ -63,10 +63,6 @@ def check_flags(flags):
     return list(flags) + ["-I", INCLUDE, "-I", CSRC]
 
 
-def check_command(hipcc, flags, output):
-    return [hipcc] + check_flags(flags) + ["-o", output, CHECK_SRC]
-
-
 def build_check(build):
     """math_check.hip with exactly the product's compiler and flags (`build` is webgpu_raytracer_amd._build)."""
     try:

@@ -13,7 +13,6 @@ compares it with the device compilation (tests/test_gpu_math.py) shown to be abl
   * the device side compiles for gfx950 with the product flags and keeps everything in registers.
 """
 import os
-import re
 import subprocess
 
 import pytest
@@ -235,28 +234,14 @@ def test_rng_host_side_is_the_oracles(oracle_lib):
 def test_device_side_compiles_without_scratch(tmp_path):
     """math_check.hip for gfx950 with the product's flags: it compiles and no check kernel spills (a kernel that spills is
     not running the register-resident code the renderer runs).  Read from the compiler's resource remarks."""
+    import kernel_report
     import webgpu_raytracer_amd as W
-    hipcc = W._build.HIPCC
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not found at %s" % hipcc)
+    if kernel_report.hipcc_missing():
+        pytest.skip(kernel_report.hipcc_missing())
     for want in ("-ffp-contract=off", "-fno-fast-math", "-O3", "--offload-arch=gfx950"):
         assert want in W._build.HIP_FLAGS
-    flags = [f for f in W._build.HIP_FLAGS if f not in ("-shared", "-fPIC")]
-    cmd = M.check_command(hipcc, flags + ["--cuda-device-only", "-c", "-Rpass-analysis=kernel-resource-usage"], str(tmp_path / "math_check.o"))
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-4000:]
-    kernels, cur = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"remark:\s+(.*?) \[-Rpass", line)
-        if not m:
-            continue
-        text = m.group(1).strip()
-        if text.startswith("Function Name:"):
-            cur = kernels.setdefault(text.split(":", 1)[1].strip(), {})
-        elif cur is not None and ":" in text:
-            k, v = text.split(":", 1)
-            cur[k.strip()] = v.strip()
+    kernels = kernel_report.compile_report(M.CHECK_SRC, tmp_path, (M.INCLUDE, M.CSRC))
     checks = {n: res for n, res in kernels.items() if "k_math_check" in n}
     assert len(checks) == len(M.OPS), sorted(kernels)
     for name, res in checks.items():
-        assert int(res["ScratchSize [bytes/lane]"]) == 0 and int(res["VGPRs Spill"]) == 0, (name, res)
+        assert res["ScratchSize [bytes/lane]"] == 0 and res["VGPRs Spill"] == 0, (name, res)

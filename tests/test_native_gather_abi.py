@@ -3,7 +3,6 @@ run time only (never a NEEDED entry; a missing library is an error code with a m
 kernels of csrc/k_stripes.hip.h compile for gfx950 without scratch.  No GPU needed."""
 import ctypes
 import os
-import re
 import subprocess
 import sys
 
@@ -64,31 +63,16 @@ def test_missing_rccl_is_an_error_code_with_a_message(W, tmp_path):
 
 def test_copy_kernels_use_no_scratch(W, tmp_path):
     """hipcc -Rpass-analysis=kernel-resource-usage on the two kernels alone (the header stands on its own)."""
-    hipcc = W._build.HIPCC
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not found at %s" % hipcc)
+    import kernel_report
+    if kernel_report.hipcc_missing():
+        pytest.skip(kernel_report.hipcc_missing())
     src = tmp_path / "stripes.hip"
     src.write_text('#include <hip/hip_runtime.h>\n#include <stdint.h>\n#include "k_stripes.hip.h"\n')
-    flags = [f for f in W._build.HIP_FLAGS if f not in ("-shared", "-fPIC")]
-    cmd = [hipcc] + flags + ["--cuda-device-only", "-c", "-Rpass-analysis=kernel-resource-usage",
-                             "-I", os.path.join(REPO, "webgpu-raytracer_amd", "csrc"), "-o", str(tmp_path / "stripes.o"), str(src)]
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-4000:]
-    kernels, cur = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"remark:\s+(.*?) \[-Rpass", line)
-        if not m:
-            continue
-        text = m.group(1).strip()
-        if text.startswith("Function Name:"):
-            cur = kernels.setdefault(text.split(":", 1)[1].strip(), {})
-        elif cur is not None and ":" in text:
-            k, v = text.split(":", 1)
-            cur[k.strip()] = v.strip()
+    kernels = kernel_report.compile_report(src, tmp_path, (os.path.join(REPO, "webgpu-raytracer_amd", "csrc"),), timeout=300)
     for want in ("k_pack_stripes", "k_unpack_stripes"):
         names = [n for n in kernels if want in n]
         assert len(names) == 1, sorted(kernels)
         res = kernels[names[0]]
         print(want, res)
-        assert int(res["ScratchSize [bytes/lane]"]) == 0 and int(res["VGPRs Spill"]) == 0, res
-        assert int(res["VGPRs"]) <= 32, res   # a streaming copy: full occupancy
+        assert res["ScratchSize [bytes/lane]"] == 0 and res["VGPRs Spill"] == 0, res
+        assert res["VGPRs"] <= 32, res   # a streaming copy: full occupancy
