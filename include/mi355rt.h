@@ -636,6 +636,64 @@ int rt_bake_reflection_device(rt_ctx* ctx, const rt_reflection_desc* desc, const
                               uint32_t seed, void* dev_chains);
 int rt_reflection_stats(rt_ctx* ctx, rt_radiance_stats* out);
 
+/* ---- the reflection sampler: "which radiance does this surface point reflect at this roughness?" read from baked chains on
+ * the device, as rt_sample_volume reads a baked volume ----
+ * A query (rt_reflection_query, mi355rt_layout.h) names a probe, the reflected direction and a roughness, and - for the
+ * parallax correction - the position of the shaded point; the result is one 16-byte texel {r, g, b, hit_fraction}: a bilinear
+ * fetch that follows the octahedral map across its seams, from the two levels of the chain around the roughness, mixed
+ * linearly.  With RT_REFLECTION_SAMPLE_PARALLAX the direction is first bent to where it leaves the probe's proxy box
+ * (rt_reflection_box), seen from the probe (Lagarde & Zanuttini 2012): a probe captured in the middle of a room then serves
+ * points near its walls (csrc/k_reflection_sample.hip.h).  The second factor of the split sum, the BRDF integral, stays the
+ * consumer's.
+ *
+ * THE REFLECTION SAMPLE RULE.  All arithmetic is f32, unfused, in the order written, with rt_div / rt_min / rt_floor of
+ * mi355rt_math.h; pack is THE REFLECTION RULE's.  The chains are n_probes chains laid out as a bake lays them: chain p at the
+ * texel p * chain_texels, its level m of side S = size >> m at the texel offset sum over k < m of (size >> k)^2, texel (i, j)
+ * at j * S + i.
+ *   probe      p = query.probe.  If p >= n_probes the result is {+0, +0, +0, +0} and nothing is loaded for the query.
+ *   direction  d = query.direction, as given (not normalised).  Without RT_REFLECTION_SAMPLE_PARALLAX d' = d: the position,
+ *              probes and boxes are never read, and the two arrays may be NULL.
+ *   parallax   with the flag: x = query.position, c = probes[p].position, lo and hi of boxes[p].  inside = for every axis
+ *              lo[a] <= x[a] && x[a] <= hi[a] (false with a NaN).  If !inside then d' = d.  Else per axis a: if d[a] > 0 then
+ *              t_a = rt_div(hi[a] - x[a], d[a]); else if d[a] < 0 then t_a = rt_div(lo[a] - x[a], d[a]); else t_a = +inf (a
+ *              zero and a NaN d[a] too).  t = rt_min(rt_min(t_x, t_y), t_z).  If !(t < +inf) then d' = d (a NaN t too).  Else
+ *              h[a] = x[a] + d[a] * t, the product rounded before the sum, and d'[a] = h[a] - c[a].
+ *   level      r = query.roughness; if !(r > 0) then r = +0 (a NaN too); r = rt_min(r, 1.0f).  xl = r * (float)(levels - 1);
+ *              m0 = (uint32_t)xl, and if m0 > levels - 2 then m0 = levels - 2; m1 = m0 + 1; g = xl - (float)m0.  Level m0 has
+ *              the weight 1.0f - g and level m1 the weight g.
+ *   fold       a tap (i, j) with i and j in -1 .. S of a level of side S is folded across the octahedral seam, x first, then y:
+ *              if i < 0 then i = -1 - i and j = S - 1 - j, else if i >= S then i = 2 S - 1 - i and j = S - 1 - j; then if j <
+ *              0 then j = -1 - j and i = S - 1 - i, else if j >= S then j = 2 S - 1 - j and i = S - 1 - i.  (THE VISIBILITY
+ *              RULE's wrap.)  The corner (-1, -1) becomes (S - 1, S - 1).
+ *   fetch      of a level of side S at d': q = pack(d'), once for both levels.  Per axis u = (q * 0.5f + 0.5f) * (float)S -
+ *              0.5f; if !(u >= -0.5f) then u = -0.5f (a NaN too); u = rt_min(u, (float)S - 0.5f); fl = rt_floor(u); i0 =
+ *              (int)fl, in -1 .. S - 1; f = u - fl.  With (i0, fx) from q.x and (j0, fy) from q.y, wx = {1.0f - fx, fx}, wy =
+ *              {1.0f - fy, fy}, the tap t_ab is the folded texel (i0 + a, j0 + b) and its weight w_ab = wx[a] * wy[b].  Per
+ *              channel the level's value is (((+0 + w00 * t00) + w10 * t10) + w01 * t01) + w11 * t11, and a tap whose weight
+ *              is exactly zero (+0 or -0) is left out of the sum, not multiplied: a NaN texel never reaches a result it has
+ *              no weight in.  Every index is inside the map for every input.
+ *   mix        out[ch] = (+0 + (1.0f - g) * A[ch]) + g * B[ch] for all four channels, A the value fetched from level m0 and B
+ *              from level m1; a level whose weight is exactly zero is left out: it does not contribute, whatever it holds.
+ *              (An implementation may still load the texels of a tap or a level it leaves out and drop them: every texel of
+ *              every chain must be readable memory.)  Source texels are not sanitised.
+ * A result depends on (chains, desc, probes[p], boxes[p], query) only - never on n or on the query's place in the array.
+ * Refusals (RT_ERR_INVALID, every message begins with "reflection:", the descriptor checked before the context - without one
+ * the message is what rt_last_error(NULL) returns): a NULL descriptor; size, levels and the smallest level as for
+ * rt_reflection_desc; an unknown flag; a non-zero reserved word; n_probes == 0 with n > 0; n_probes * chain_texels >= 2^31;
+ * n >= 2^31; a NULL array, or a device array that is not 16-byte aligned - probes and boxes only with
+ * RT_REFLECTION_SAMPLE_PARALLAX.  n == 0 is RT_OK.  The sampler needs no scene, has staging of its own, kept and grown, and
+ * leaves the renderer, rt_reflection_stats and every other query's state as they were.
+ *   rt_sample_reflection         blocking: copies the n_probes chains (and with the flag the probes and boxes) and n queries
+ *                                in, samples, copies n results of four floats out.  It uploads the chains on every call: a
+ *                                caller sampling every frame keeps them on the device and uses
+ *   rt_sample_reflection_device  the same on device-accessible arrays (16-byte aligned): only enqueues on the context's
+ *                                stream. */
+int rt_sample_reflection(rt_ctx* ctx, const rt_reflection_sample_desc* desc, const float* chains, uint32_t n_probes,
+                         const rt_probe* probes, const rt_reflection_box* boxes, const rt_reflection_query* queries, uint32_t n,
+                         float* out);
+int rt_sample_reflection_device(rt_ctx* ctx, const rt_reflection_sample_desc* desc, const void* dev_chains, uint32_t n_probes,
+                                const void* dev_probes, const void* dev_boxes, const void* dev_queries, uint32_t n, void* dev_out);
+
 /* ---- probe visibility maps: "does this probe of the volume see the point it is about to light?" - the weight that keeps a
  * probe behind a wall from lighting the room in front of it ----
  * rt_sample_volume blends the eight surrounding probes by their trilinear weight alone, so indoors light leaks through

@@ -212,6 +212,28 @@ typedef struct rt_reflection_desc { /* 32 B */
   uint32_t reserved[4];       /* 0 */
 } rt_reflection_desc;
 
+/* ---- the reflection sampler (rt_sample_reflection, mi355rt.h "THE REFLECTION SAMPLE RULE"): chains as a bake lays them out
+ * in, one 16-byte texel {r, g, b, hit_fraction} per query out ---- */
+#define RT_REFLECTION_SAMPLE_PARALLAX 1u /* flags: correct the direction by the probe's box; every other bit is refused */
+typedef struct rt_reflection_sample_desc { /* 32 B */
+  uint32_t size;              /* side of level 0 of the chains: a power of two, 8 .. 512 */
+  uint32_t levels;            /* of a chain: >= 2, size >> (levels - 1) >= 4 */
+  uint32_t flags;             /* RT_REFLECTION_SAMPLE_PARALLAX */
+  uint32_t reserved[5];       /* 0 */
+} rt_reflection_sample_desc;
+typedef struct rt_reflection_query { /* 32 B: the slots of rt_ray {position, probe} {direction, roughness} */
+  float position[3];          /* of the shaded point; read only with RT_REFLECTION_SAMPLE_PARALLAX */
+  uint32_t probe;             /* index of the chain; >= n_probes gives four +0 */
+  float direction[3];         /* the reflected direction; need not be normalised */
+  float roughness;            /* 0 .. 1 picks the level roughness * (levels - 1); clamped, a NaN is 0 */
+} rt_reflection_query;
+typedef struct rt_reflection_box { /* 32 B: the proxy volume of one probe, axis-aligned */
+  float lo[3];
+  float unused0;              /* not read; write 0 */
+  float hi[3];
+  float unused1;              /* not read; write 0 */
+} rt_reflection_box;
+
 /* ---- directional gathers (rt_gather_directional, mi355rt.h): rt_gather_point in; their stats are an rt_radiance_stats ---- */
 typedef struct rt_directional {   /* 64 B: four 16-byte vector stores of k_dir_project */
   float layer[4][4];              /* layer[k] = {sh[k].r, sh[k].g, sh[k].b, hit_fraction}: row k is the texel of atlas layer k */
@@ -347,6 +369,18 @@ static_assert(__builtin_offsetof(rt_reflection_desc, size) == 0 && __builtin_off
                   __builtin_offsetof(rt_reflection_desc, spt) == 8 && __builtin_offsetof(rt_reflection_desc, filter_samples) == 12 &&
                   __builtin_offsetof(rt_reflection_desc, reserved) == 16,
               "rt_reflection_desc: four words, then four reserved ones");
+static_assert(sizeof(rt_reflection_sample_desc) == 32, "rt_reflection_sample_desc is 32 bytes");
+static_assert(__builtin_offsetof(rt_reflection_sample_desc, size) == 0 && __builtin_offsetof(rt_reflection_sample_desc, levels) == 4 &&
+                  __builtin_offsetof(rt_reflection_sample_desc, flags) == 8 &&
+                  __builtin_offsetof(rt_reflection_sample_desc, reserved) == 12,
+              "rt_reflection_sample_desc: three words, then five reserved ones");
+static_assert(sizeof(rt_reflection_query) == 32, "rt_reflection_query is 32 bytes");
+static_assert(__builtin_offsetof(rt_reflection_query, probe) == 12 && __builtin_offsetof(rt_reflection_query, direction) == 16 &&
+                  __builtin_offsetof(rt_reflection_query, roughness) == 28,
+              "rt_reflection_query has the slots of rt_ray");
+static_assert(sizeof(rt_reflection_box) == 32, "rt_reflection_box is 32 bytes");
+static_assert(__builtin_offsetof(rt_reflection_box, lo) == 0 && __builtin_offsetof(rt_reflection_box, hi) == 16,
+              "rt_reflection_box: lo in the first 16 bytes, hi in the second");
 static_assert(sizeof(rt_denoise_desc) == 32, "rt_denoise_desc is 32 bytes");
 static_assert(sizeof(rt_frame_denoise_desc) == 32, "rt_frame_denoise_desc is 32 bytes");
 static_assert(sizeof(rt_frame_denoise_report) == 48, "rt_frame_denoise_report is 48 bytes");

@@ -21,6 +21,11 @@ if K.hipcc_missing():
     sys.exit(K.hipcc_missing())
 with tempfile.TemporaryDirectory() as tmp:
     report = K.library_report(tmp, sys.argv[1:])
+    # the translation units beside rt_api.hip (the reflection sampler): their budget is tests/test_reflection_sample_budgets.py's
+    import test_reflection_sample_budgets as S
+    other = {}
+    for unit in K.W._build.RT_SOURCES[1:]:
+        other.update(K.compile_report(os.path.join(K.CSRC, unit), tmp, (K.W._build.INCLUDE,), sys.argv[1:]))
 print("%-62s" % "kernel" + "".join(" %9s" % c[0] for c in COLUMNS) + "  note")
 for name, res in report.items():
     rows = B.matching(name, B.ROWS)
@@ -29,3 +34,7 @@ for name, res in report.items():
     mark = ("; ".join(B.violations(limits, res)) if rows else "reference only" if B.matching(name, B.REFERENCES) else
             "unbudgeted" if B.matching(name, B.UNBUDGETED) else "NO ROW")
     print("%-62s" % name[:62] + "".join(" %9s" % c for c in cells) + "  " + mark)
+for name, res in other.items():
+    cells = ["%s" % res.get(key) for _, key, _ in COLUMNS]
+    mark = "; ".join(B.violations(S.LIMITS, res)) if name in S.KERNELS else "NO ROW"
+    print("%-62s" % name[:62] + "".join(" %9s" % c for c in cells) + "  reflection_sample.hip " + mark)

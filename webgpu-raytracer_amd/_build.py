@@ -1,7 +1,7 @@
 """Build recipes for the native pieces (explicit compiler invocations, in-tree outputs).
 
   lib/libmi355scene.so   g++    csrc/scene/scene_compiler.cpp      (host, scene compiler)
-  lib/libmi355rt.so      hipcc  csrc/rt_api.hip (+ kernels)        (gfx950, the C-ABI renderer)
+  lib/libmi355rt.so      hipcc  csrc/rt_api.hip (+ kernels), csrc/reflection_sample.hip      (gfx950, the C-ABI renderer)
   lib/libmi355tex.so     g++    csrc/texture/image_decode.cpp      (host, PNG / JPEG decode for texture ingest)
   node/mi355rt.node      gcc    node/addon.c                       (N-API shim over libmi355rt.so)
 
@@ -123,6 +123,8 @@ def build_tex(force=False):
     return TEX_LIB
 
 
+# the translation units of the HIP library: the renderer with the kernel set of kernels.hip.h, and the reflection sampler
+RT_SOURCES = ("rt_api.hip", "reflection_sample.hip")
 RT_FLAGS_SIDECAR = RT_LIB + ".flags"   # the extra compiler flags the library in the tree was built with ("" = the product build)
 
 
@@ -137,7 +139,7 @@ def build_rt(force=False, extra_flags=()):
     """The HIP renderer.  extra_flags: a VARIANT build (sweeps, diagnostic stamps).  The flags of the library on disk are kept
     in a sidecar file, so a variant library is never taken for the product one: a call that asks for other flags than the
     library was built with rebuilds it, however new the file is."""
-    src = os.path.join(CSRC, "rt_api.hip")
+    srcs = [os.path.join(CSRC, name) for name in RT_SOURCES]
     deps = _glob_sources(CSRC, (".hip", ".h", ".hpp")) + _headers()
     want = " ".join(extra_flags)
 
@@ -151,7 +153,7 @@ def build_rt(force=False, extra_flags=()):
     with _build_lock():
         if not force and fresh():
             return RT_LIB
-        cmd = [HIPCC] + HIP_FLAGS + list(extra_flags) + ["-I", INCLUDE, "-o", RT_LIB, src]
+        cmd = [HIPCC] + HIP_FLAGS + list(extra_flags) + ["-I", INCLUDE, "-o", RT_LIB] + srcs
         _compile(cmd, RT_LIB)
         with open(RT_FLAGS_SIDECAR, "w") as f:
             f.write(want)

@@ -58,6 +58,9 @@
 //   k_validate.hip.h          k_validate_scene: every index the kernels follow, checked once per upload
 //   k_stripes.hip.h           k_pack_stripes / k_unpack_stripes: the copies of the sharded image's gather
 //
+// (k_reflection_sample.hip.h, the reflection sampler of rt_sample_reflection, is not of this set: it needs nothing of it and
+// is the translation unit reflection_sample.hip.)
+//
 // All arithmetic is unfused IEEE f32 (-ffp-contract=off) with the builtin semantics of
 // include/mi355rt_math.h, in the evaluation order of the WGSL source, so that every path
 // takes the same branches as the CPU oracle and results agree bit for bit.

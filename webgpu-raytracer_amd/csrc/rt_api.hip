@@ -25,6 +25,7 @@
 
 #include "../../include/mi355rt.h"
 #include "kernels.hip.h"
+#include "reflection_sample.h"
 #include "launch_plan.h"
 #include "scene_facts.h"
 #include "device_owned.h"
@@ -167,6 +168,12 @@ struct ReflectionState {
 // gathers'.
 struct VisibilityState {
   DeviceBuffer maps, volume, points, out, encoded;
+};
+
+// What the reflection sampler (rt_sample_reflection) keeps between calls, kept and grown: the staged chains, probes, boxes,
+// queries and results of the host entry.  Nothing of the reflection probes' own state is touched.
+struct ReflectionSampleState {
+  DeviceBuffer chains, probes, boxes, queries, out;
 };
 
 }  // namespace
@@ -357,6 +364,7 @@ struct rt_ctx {
   QueryState vv;
   rt_ray_stats vv_last = {};
   VisibilityState vis;
+  ReflectionSampleState rfs;
 
   // kernel timing
   bool timing = false;
@@ -4230,6 +4238,78 @@ int rt_filter_reflection(rt_ctx* c, const rt_reflection_desc* desc, const float*
 int rt_bake_reflection(rt_ctx* c, const rt_reflection_desc* desc, const rt_probe* probes, uint32_t n, uint32_t max_depth,
                        uint32_t seed, float* out_chains, rt_radiance_stats* stats) {
   return reflection_from_host(c, desc, RF_CAPTURE | RF_FILTER, probes, nullptr, n, max_depth, seed, out_chains, stats);
+}
+
+// ---- the reflection sampler (mi355rt.h "THE REFLECTION SAMPLE RULE"; k_reflection_sample.hip.h): baked chains read at the
+// caller's queries, one thread per query.  Needs no scene; the kernel and its launcher are reflection_sample.hip.
+// everything the limits say about the descriptor and the two counts; *chain = texels of a chain
+static int reflection_sample_desc_ok(rt_ctx* c, const rt_reflection_sample_desc* d, uint32_t n_probes, uint32_t n, uint32_t* chain) {
+  if (!d) return refuse(c, kReflection, "NULL descriptor");
+  if (d->size < 8 || d->size > 512 || (d->size & (d->size - 1u))) return refuse(c, kReflection, "size must be a power of two in 8 .. 512");
+  if (d->levels < 2) return refuse(c, kReflection, "levels must be >= 2");
+  if (d->levels > 32 || (d->size >> (d->levels - 1u)) < 4) return refuse(c, kReflection, "size >> (levels - 1) must be >= 4");
+  if (d->flags & ~RT_REFLECTION_SAMPLE_PARALLAX) return refuse(c, kReflection, "unknown flags");
+  for (int k = 0; k < 5; k++)
+    if (d->reserved[k]) return refuse(c, kReflection, "reserved must be 0");
+  *chain = 0;
+  for (uint32_t m = 0; m < d->levels; m++) *chain += (d->size >> m) * (d->size >> m);
+  if (n_probes == 0 && n > 0) return refuse(c, kReflection, "n_probes must be > 0");
+  if ((uint64_t)n_probes * *chain >= (1ull << 31)) return refuse(c, kReflection, "n_probes * texels of a chain must be below 2^31");
+  if (n >= (1u << 31)) return refuse(c, kReflection, "too many queries for one call (n must be below 2^31)");
+  return RT_OK;
+}
+static int launch_sample_reflection(rt_ctx* c, const rt_reflection_sample_desc& D, uint32_t chain, const void* d_chains,
+                                    uint32_t n_probes, const void* d_probes, const void* d_boxes, const void* d_queries, uint32_t n,
+                                    void* d_out) {
+  rtk::ReflectionSampleArgs A;
+  A.chains = (const float4*)d_chains;
+  A.probes = (const float4*)d_probes;
+  A.boxes = (const float4*)d_boxes;
+  A.queries = (const float4*)d_queries;
+  A.out = (float4*)d_out;
+  A.n = n;
+  A.n_probes = n_probes;
+  A.chain = chain;
+  A.size_log2 = (uint32_t)__builtin_ctz(D.size);
+  A.levels = D.levels;
+  HIP_TRY(c, rtk::launch_reflection_sample(A, (D.flags & RT_REFLECTION_SAMPLE_PARALLAX) != 0, c->stream));
+  return RT_OK;
+}
+
+int rt_sample_reflection_device(rt_ctx* c, const rt_reflection_sample_desc* desc, const void* dev_chains, uint32_t n_probes,
+                                const void* dev_probes, const void* dev_boxes, const void* dev_queries, uint32_t n, void* dev_out) {
+  uint32_t chain = 0;
+  int r = reflection_sample_desc_ok(c, desc, n_probes, n, &chain);
+  if (r < 0) return r;
+  if (n == 0) return c ? RT_OK : RT_ERR_INVALID;
+  const bool parallax = (desc->flags & RT_REFLECTION_SAMPLE_PARALLAX) != 0;
+  if ((r = caller_arrays_ok(c, kReflection, {dev_chains, {dev_probes, parallax}, {dev_boxes, parallax}, dev_queries, dev_out})) < 0)
+    return r;
+  if (!c) return RT_ERR_INVALID;
+  return launch_sample_reflection(c, *desc, chain, dev_chains, n_probes, dev_probes, dev_boxes, dev_queries, n, dev_out);
+}
+
+int rt_sample_reflection(rt_ctx* c, const rt_reflection_sample_desc* desc, const float* chains, uint32_t n_probes,
+                         const rt_probe* probes, const rt_reflection_box* boxes, const rt_reflection_query* queries, uint32_t n,
+                         float* out) {
+  uint32_t chain = 0;
+  int r = reflection_sample_desc_ok(c, desc, n_probes, n, &chain);
+  if (r < 0) return r;
+  if (n == 0) return c ? RT_OK : RT_ERR_INVALID;
+  const bool parallax = (desc->flags & RT_REFLECTION_SAMPLE_PARALLAX) != 0;
+  if ((r = caller_arrays_ok(c, kReflection, {chains, {probes, parallax}, {boxes, parallax}, queries, out}, false)) < 0 || !c)
+    return RT_ERR_INVALID;
+  ReflectionSampleState& st = c->rfs;
+  return staged_call(c,
+                     {{st.chains, chains, (size_t)n_probes * chain * 16, STAGE_IN},
+                      {st.probes, probes, (size_t)n_probes * sizeof(rt_probe), STAGE_IN, true, parallax},
+                      {st.boxes, boxes, (size_t)n_probes * sizeof(rt_reflection_box), STAGE_IN, true, parallax},
+                      {st.queries, queries, (size_t)n * sizeof(rt_reflection_query), STAGE_IN},
+                      {st.out, out, (size_t)n * 16, STAGE_OUT}},
+                     [&] {
+                       return launch_sample_reflection(c, *desc, chain, st.chains.ptr, n_probes, st.probes.ptr, st.boxes.ptr,
+                                                       st.queries.ptr, n, st.out.ptr);
+                     });
 }
 
 // ---- probe visibility maps (mi355rt.h "THE VISIBILITY RULE"; k_volume_visibility.hip.h): per probe of an irradiance volume an

@@ -865,6 +865,38 @@ static napi_value rtFilterReflection(napi_env env, napi_callback_info info) {
   return make_int(env, rt_filter_reflection((rt_ctx*)get_ptr(env, a[0]), desc, (const float*)maps, (uint32_t)n, (float*)out));
 }
 
+/* (ctx, desc: the 32 bytes of an rt_reflection_sample_desc, chains: Float32Array of whole chains, probes and boxes: Float32Array
+ * of 8 per chain or null (read with the parallax flag only), queries: 8 floats per query {position, probe bits, direction,
+ * roughness}, out: Float32Array of 4 per query) -> status */
+static napi_value rtSampleReflection(napi_env env, napi_callback_info info) {
+  napi_value a[7];
+  void *d = NULL, *chains = NULL, *probes = NULL, *boxes = NULL, *queries = NULL, *out = NULL;
+  size_t nd = 0, nc = 0, np = 0, nb = 0, nq = 0, no = 0, chain = 0;
+  if (!get_args(env, info, 7, a) || !get_bytes(env, a[1], &d, &nd) || !get_bytes(env, a[2], &chains, &nc) ||
+      !get_bytes(env, a[3], &probes, &np) || !get_bytes(env, a[4], &boxes, &nb) || !get_bytes(env, a[5], &queries, &nq) ||
+      !get_bytes(env, a[6], &out, &no))
+    return NULL;
+  if (nd != sizeof(rt_reflection_sample_desc)) {
+    napi_throw_range_error(env, NULL, "a reflection sample descriptor is 32 bytes");
+    return NULL;
+  }
+  const rt_reflection_sample_desc* desc = (const rt_reflection_sample_desc*)d;
+  if (desc->size >= 8 && desc->size <= 512 && desc->levels >= 2 && desc->levels <= 32)   /* else 0: the library will refuse it */
+    for (uint32_t m = 0; m < desc->levels; m++) chain += (size_t)(desc->size >> m) * (desc->size >> m);
+  const size_t n_probes = chain ? nc / (chain * 16) : 0, n = nq / sizeof(rt_reflection_query);
+  const bool parallax = (desc->flags & RT_REFLECTION_SAMPLE_PARALLAX) != 0;
+  if ((chain && nc % (chain * 16) != 0) || n_probes > 0x7fffffffu || nq % sizeof(rt_reflection_query) != 0 || n > 0x7fffffffu ||
+      no < n * 16 || (parallax && probes && np < n_probes * sizeof(rt_probe)) ||   /* (a missing array: the library refuses it) */
+      (parallax && boxes && nb < n_probes * sizeof(rt_reflection_box))) {
+    napi_throw_range_error(env, NULL, "rtSampleReflection: chains must hold whole chains of 4 floats per texel, probes and boxes 8 "
+                                      "floats per chain, queries 8 and out 4 floats per query");
+    return NULL;
+  }
+  return make_int(env, rt_sample_reflection((rt_ctx*)get_ptr(env, a[0]), desc, (const float*)chains, (uint32_t)n_probes,
+                                            (const rt_probe*)probes, (const rt_reflection_box*)boxes,
+                                            (const rt_reflection_query*)queries, (uint32_t)n, (float*)out));
+}
+
 /* ------------------------------------------------------- directional gathers (rt_gather_directional, mi355rt.h) */
 /* (ctx, points: Float32Array of 8 per point {position, t_max, normal, pad}, maxDepth, spp, seed, out: Float32Array of 16 per
  * point, four rows {sh[k].rgb, hit_fraction}, wantStats) -> status, or the stats object when wantStats and the call succeeded */
@@ -1270,6 +1302,7 @@ static napi_value Init(napi_env env, napi_value exports) {
                {"rtBakeVolumeVisibility", rtBakeVolumeVisibility}, {"rtSampleVolumeVisible", rtSampleVolumeVisible},
                {"rtEncodeVolumeVisibility", rtEncodeVolumeVisibility},
                {"rtBakeReflection", rtBakeReflection}, {"rtFilterReflection", rtFilterReflection},
+               {"rtSampleReflection", rtSampleReflection},
                {"rtGatherDirectional", rtGatherDirectional}, {"rtBakeAtlasDirectionalLightmap", rtBakeAtlasDirectionalLightmap},
                {"rtBakeIrradiance", rtBakeIrradiance}, {"rtBakeAtlasPoints", rtBakeAtlasPoints},
                {"rtBakeAtlasIrradiance", rtBakeAtlasIrradiance}, {"rtDilateAtlas", rtDilateAtlas},

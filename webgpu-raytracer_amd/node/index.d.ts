@@ -114,6 +114,14 @@ export class WebGPURenderer {
   /** One encodeAtlas result per level of ONE chain; all three formats apply. */
   encodeReflection(desc: Uint8Array, chain: Float32Array, format: 'f32' | 'f16' | 'rgbe'):
     { data: Float32Array | Uint16Array | Uint32Array; width: number; height: number; format: string }[];
+  /** The reflection sampler (rt_sample_reflection).  A descriptor is the 32 bytes of an rt_reflection_sample_desc: the size
+   *  and levels of the chains, and whether directions are bent to where they leave the probe's box. */
+  static reflectionSampleDesc(o: { size: number; levels: number; parallax?: boolean }): Uint8Array;
+  /** chains: whole chains, 4 floats per texel; queries: 8 floats per query {position, probe index as u32 bits, direction,
+   *  roughness}; probes and boxes: 8 floats per chain, read with parallax only.  `data` holds 4 floats {r, g, b, hitFraction}
+   *  per query: the seam-aware bilinear fetch from the two levels around roughness * (levels - 1).  Needs no scene. */
+  sampleReflection(desc: Uint8Array, chains: Float32Array, queries: Float32Array, opts?: { probes?: Float32Array; boxes?: Float32Array }):
+    { data: Float32Array; n: number };
   /** Directional gathers (rt_gather_directional): points as for gatherIrradiance.  `data` holds 16 floats per point, four rows
    *  {sh[k].r, sh[k].g, sh[k].b, hitFraction}: the projection of the radiance arriving over spp uniform directions on the
    *  hemisphere of the normal onto Y0 and the y, z, x harmonics of band 1, in world space; row k is the texel of atlas layer k.

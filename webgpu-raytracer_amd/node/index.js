@@ -357,6 +357,23 @@ class WebGPURenderer {
     for (let m = 0; m + 1 < offsets.length; m++) out.push(this.encodeAtlas(chain.slice(offsets[m] * 4, offsets[m + 1] * 4), size >>> m, size >>> m, format));
     return out;
   }
+  // ---- the reflection sampler (rt_sample_reflection): baked chains read on the device at a direction and a roughness, with a
+  // bilinear fetch that follows the octahedral map across its seams and, with parallax, the direction bent to where it leaves
+  // the probe's box.  A descriptor is the 32 bytes of an rt_reflection_sample_desc.
+  static reflectionSampleDesc(o) {
+    return new Uint8Array(Uint32Array.of(o.size >>> 0, o.levels >>> 0, o.parallax ? 1 : 0, 0, 0, 0, 0, 0).buffer);
+  }
+  // chains: whole chains as bakeReflection's .data holds them; queries: 8 floats per query {position, probe index as the bits
+  // of a u32, direction, roughness}; opts: {probes, boxes}, 8 floats per chain each ({position, tMax, -, pad} and {lo, -, hi, -}),
+  // read with parallax only.  Result: .data holds 4 floats {r, g, b, hitFraction} per query.  Needs no scene.
+  sampleReflection(desc, chains, queries, opts = {}) {
+    if (!(chains instanceof Float32Array)) throw new TypeError('sampleReflection: the chains are a Float32Array');
+    if (!(queries instanceof Float32Array) || queries.length % 8 !== 0) throw new TypeError('sampleReflection: a Float32Array of 8 floats per query');
+    const n = queries.length / 8;
+    const data = new Float32Array(n * 4);
+    this._check(native.rtSampleReflection(this._ctx, desc, chains, opts.probes || null, opts.boxes || null, queries, data), 'sampleReflection');
+    return { data, n };
+  }
   // ---- directional gathers (rt_gather_directional): the radiance arriving at the caller's surface points, over spp directions
   // drawn uniformly on the hemisphere of the normal on the device, projected onto the four real spherical harmonics of bands 0
   // .. 1 in world space.  points as for gatherIrradiance.  opts: {seed = 0, stats = false}.  Result: 16 floats per point in

@@ -216,6 +216,9 @@ def load_library(path=None):
         "rt_bake_reflection": (i32, [vp, vp, vp, u32, u32, u32, vp, vp]),
         "rt_bake_reflection_device": (i32, [vp, vp, vp, u32, u32, u32, vp]),
         "rt_reflection_stats": (i32, [vp, vp]),
+        # the reflection sampler
+        "rt_sample_reflection": (i32, [vp, vp, vp, u32, vp, vp, vp, u32, vp]),
+        "rt_sample_reflection_device": (i32, [vp, vp, vp, u32, vp, vp, vp, u32, vp]),
         # probe visibility maps
         "rt_bake_volume_visibility": (i32, [vp, vp, vp, u32, vp, vp]),
         "rt_bake_volume_visibility_device": (i32, [vp, vp, vp, u32, vp]),
@@ -290,7 +293,7 @@ EXPORTED_SYMBOLS = (
     "rt_gather_probes rt_gather_probes_device rt_probe_gather_stats "
     "rt_bake_volume rt_bake_volume_device rt_sample_volume rt_sample_volume_device rt_encode_volume rt_encode_volume_device "
     "rt_capture_reflection rt_capture_reflection_device rt_filter_reflection rt_filter_reflection_device rt_bake_reflection "
-    "rt_bake_reflection_device rt_reflection_stats "
+    "rt_bake_reflection_device rt_reflection_stats rt_sample_reflection rt_sample_reflection_device "
     "rt_bake_volume_visibility rt_bake_volume_visibility_device rt_volume_visibility_stats rt_sample_volume_visible "
     "rt_sample_volume_visible_device rt_encode_volume_visibility rt_encode_volume_visibility_device "
     "rt_gather_directional rt_gather_directional_device rt_directional_gather_stats "
@@ -481,14 +484,60 @@ def _reflection_chain_texels(d):
     return int(reflection_level_offsets(size, levels)[-1])
 
 
-def _probe_array(probes, what):
-    p = np.ascontiguousarray(probes)
-    if p.dtype == PROBE_DTYPE:
-        p = p.reshape(-1).view(np.float32).reshape(-1, 8)
-    p = np.ascontiguousarray(p, dtype=np.float32)
-    if p.ndim != 2 or p.shape[1] != 8:
+# the reflection sampler: mirrors of rt_reflection_sample_desc / rt_reflection_query / rt_reflection_box; a result is one texel
+# {r, g, b, hit_fraction}
+RT_REFLECTION_SAMPLE_PARALLAX = 1
+REFLECTION_SAMPLE_DESC_DTYPE = np.dtype([("size", np.uint32), ("levels", np.uint32), ("flags", np.uint32),
+                                         ("reserved", np.uint32, (5,))])
+REFLECTION_QUERY_DTYPE = np.dtype([("position", np.float32, (3,)), ("probe", np.uint32), ("direction", np.float32, (3,)),
+                                   ("roughness", np.float32)])
+REFLECTION_BOX_DTYPE = np.dtype([("lo", np.float32, (3,)), ("unused0", np.float32), ("hi", np.float32, (3,)),
+                                 ("unused1", np.float32)])
+
+
+def reflection_sample_desc(size, levels, parallax=False):
+    """A REFLECTION_SAMPLE_DESC_DTYPE record (shape ()): the size and levels of the chains to sample, as their bake's
+    reflection_desc had them; parallax: bend every direction to where it leaves the probe's box (sampleReflection then wants
+    probes and boxes)."""
+    d = np.zeros((), REFLECTION_SAMPLE_DESC_DTYPE)
+    d["size"], d["levels"] = size, levels
+    d["flags"] = RT_REFLECTION_SAMPLE_PARALLAX if parallax else 0
+    return d
+
+
+def reflection_queries(positions, probes, directions, roughness):
+    """A REFLECTION_QUERY_DTYPE array (n,): positions (n, 3) of the shaded points (read with parallax only), the index of each
+    point's probe, the reflected directions (n, 3), which need not be unit, and the roughness of each, 0 .. 1 (scalars
+    broadcast)."""
+    dirs = np.asarray(directions, np.float32).reshape(-1, 3)
+    q = np.zeros(dirs.shape[0], REFLECTION_QUERY_DTYPE)
+    q["direction"] = dirs
+    q["position"] = np.broadcast_to(np.asarray(positions, np.float32), (dirs.shape[0], 3))
+    q["probe"] = np.broadcast_to(np.asarray(probes, np.uint32), dirs.shape[:1])
+    q["roughness"] = np.broadcast_to(np.asarray(roughness, np.float32), dirs.shape[:1])
+    return q
+
+
+def _reflection_sample_desc(desc):
+    d = np.ascontiguousarray(desc)
+    if d.dtype != REFLECTION_SAMPLE_DESC_DTYPE or d.size != 1:
+        raise ValueError("a reflection sample descriptor is one REFLECTION_SAMPLE_DESC_DTYPE record (reflection_sample_desc builds it)")
+    return d.reshape(())
+
+
+def _records(a, dtype, what):
+    """a: an array of `dtype` or of float32 words, eight per record -> (n, 8) float32, C-contiguous"""
+    r = np.ascontiguousarray(a)
+    if r.dtype == dtype:
+        r = r.reshape(-1).view(np.float32).reshape(-1, 8)
+    r = np.ascontiguousarray(r, dtype=np.float32)
+    if r.ndim != 2 or r.shape[1] != 8:
         raise ValueError("%s expects an (n, 8) float32 array" % what)
-    return p
+    return r
+
+
+def _probe_array(probes, what):
+    return _records(probes, PROBE_DTYPE, what)
 
 
 # directional gathers: mirror of rt_directional; points are rt_gather_point, stats an RtRadianceStats (rays = points)
@@ -1227,6 +1276,47 @@ class WebGPURenderer:
             side = int(d["size"]) >> m
             out.append(self.encodeAtlas(c[off[m]:off[m + 1]].reshape(side, side, 4), format))
         return out
+
+    # ---- the reflection sampler: baked chains read at a direction and a roughness (rt_sample_reflection) ----
+    def sampleReflection(self, desc, chains, queries, probes=None, boxes=None):
+        """desc: a REFLECTION_SAMPLE_DESC_DTYPE record (reflection_sample_desc); chains: (n_probes, chain_texels, 4) float32 as
+        bakeReflection returns them; queries: a REFLECTION_QUERY_DTYPE array (reflection_queries) or (n, 8) float32.  With
+        parallax also probes, the (n_probes, 8) rt_probe records the chains were baked at, and boxes, a REFLECTION_BOX_DTYPE
+        array (n_probes,) or (n_probes, 8) float32.  Returns (n, 4) float32 {r, g, b, hit_fraction}: the seam-aware bilinear
+        fetch at each direction from the two levels around roughness * (levels - 1), mixed (THE REFLECTION SAMPLE RULE).
+        Needs no scene.  Uploads the chains on every call: a caller sampling every frame keeps them on the device and uses
+        sampleReflectionDevice."""
+        d = _reflection_sample_desc(desc)
+        texels = _reflection_chain_texels(d)
+        c = np.ascontiguousarray(chains, dtype=np.float32)
+        if texels and c.size % (4 * texels) != 0:
+            raise ValueError("sampleReflection: the chains do not hold whole chains of the descriptor's size and levels")
+        n_probes = c.size // (4 * texels) if texels else 0   # (0: the library refuses the descriptor)
+        q = _records(queries, REFLECTION_QUERY_DTYPE, "sampleReflection")
+        p = b = None
+        if int(d["flags"]) & RT_REFLECTION_SAMPLE_PARALLAX:
+            if probes is None or boxes is None:
+                raise ValueError("sampleReflection: parallax needs the probes and their boxes")
+            p = _probe_array(probes, "sampleReflection")
+            b = _records(boxes, REFLECTION_BOX_DTYPE, "sampleReflection")
+            if p.shape[0] != n_probes or b.shape[0] != n_probes:
+                raise ValueError("sampleReflection: one probe and one box per chain")
+        out = np.empty((q.shape[0], 4), np.float32)
+        self._check(self.L.rt_sample_reflection(self.ctx, _ptr(d), _ptr(c) if c.size else None, n_probes,
+                                                _ptr(p) if p is not None and p.size else None,
+                                                _ptr(b) if b is not None and b.size else None, _ptr(q) if q.size else None,
+                                                q.shape[0], _ptr(out) if out.size else None), "sampleReflection")
+        return out
+
+    def sampleReflectionDevice(self, desc, chains_ptr, n_probes, queries_ptr, n, out_ptr, probes_ptr=0, boxes_ptr=0):
+        """Enqueue the sampling of n rt_reflection_query at queries_ptr from the n_probes chains at chains_ptr into n texels at
+        out_ptr (device pointers, 16-byte aligned; with parallax also the rt_probe and rt_reflection_box arrays) on the
+        context's stream; no host synchronisation."""
+        d = _reflection_sample_desc(desc)
+        self._check(self.L.rt_sample_reflection_device(self.ctx, _ptr(d), ctypes.c_void_p(chains_ptr or 0), int(n_probes),
+                                                       ctypes.c_void_p(probes_ptr or 0), ctypes.c_void_p(boxes_ptr or 0),
+                                                       ctypes.c_void_p(queries_ptr or 0), int(n), ctypes.c_void_p(out_ptr or 0)),
+                    "sampleReflectionDevice")
 
     # ---- probe visibility maps: distance moments per probe of a volume, and the sampler they keep from leaking light ----
     def bakeVolumeVisibility(self, desc, vis, seed=0, stats=False):
